@@ -37,6 +37,44 @@ BLK = 65536                    # Airspy block length (main.cpp:687)
 FS = 10e6
 AM_BLK, AM_FS = 2048, 384e3    # FileSource default block length (FileSource.h:34), configs[2] rate
 STAGE_KERNELS = ("ifr_fused", "ifr_decim", "ifr_poly", "fm_block", "disc")
+DUMP_BUDGET = 60 << 20         # --dump-outputs: bytes of all .npy files of one run together (headers included)
+DUMP_SEED = 20261015           # --dump-outputs: the sample of an array that does not fit the budget
+
+
+def phase_period_steps(blk, fs, B, am):
+    """Steps of B blocks after which the chain's rate converters (IF 384 kHz, audio 48 kHz; AM: 48 kHz) are back at the same
+    phase.  The input buffer repeats every step, so the stream position modulo this many steps fixes what a step computes."""
+    from fractions import Fraction
+    from math import gcd
+    per_block = 1
+    for rate in ((48000,) if am else (384000, 48000)):
+        d = (Fraction(blk) * Fraction(rate, int(fs))).denominator
+        per_block = per_block * d // gcd(per_block, d)
+    return per_block // gcd(per_block, B)
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET, suffix=""):
+    """--dump-outputs: write each array as <path>/<name><suffix>.npy in float64.  Arrays are kept whole, smallest first,
+    while they fit their share of the budget; one that does not is replaced by a fixed, seeded sample of its elements
+    (<name>.npy, flat) with the flat indices of the sample into the whole array beside it (<name>_index.npy).
+    Returns what was written, for the result line."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    left, info = budget, {}
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(arrays) - i) - 256                 # room for two 128-byte .npy headers (values, indices)
+        if a.nbytes <= share:
+            np.save(os.path.join(path, name + suffix + ".npy"), a)
+            left -= a.nbytes + 128
+            info[name] = {"shape": list(a.shape)}
+            continue
+        k = max(0, share - 128) // 16                          # a value and its index per sampled element
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, k, replace=False))
+        np.save(os.path.join(path, name + suffix + ".npy"), a.reshape(-1)[idx])
+        np.save(os.path.join(path, name + suffix + "_index.npy"), idx.astype(np.float64))
+        left -= 16 * k + 256
+        info[name] = {"shape": list(a.shape), "sampled_elements": int(k), "seed": DUMP_SEED}
+    return {"dir": path, "arrays": info}
 
 
 def synth_fm_stereo_torch(n, fs, stream_id, device, pilot=0.10, sigma=1e-3):
@@ -346,7 +384,17 @@ def main():
     ap.add_argument("--all-configs", action="store_true",
                     help="after the headline line, print one line each for configs[2] (AM), configs[3] (-E 64), configs[4] "
                          "(32 streams per GPU) and the mono-station case, each with its own audio check and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float64, "
+                         "at most 64 MB in all; a larger array as a fixed, seeded sample): audio (streams x samples) and "
+                         "audio_block_len.  The spin-up is then rounded up to whole periods of the resampler's phase, so that "
+                         "runs with the same arguments dump the same step (its values agree to ~1e-8 between runs: the GPU path is not "
+                         "bit-reproducible)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.cpu_dry_run:
+        ap.error("--dump-outputs needs the GPU path (the dry run computes nothing a caller would receive)")
 
     global R8B, IF_FILTER
     R8B = args.resampler_class == "r8b"
@@ -430,6 +478,13 @@ def main():
     while (time.perf_counter() - t_sp) * 1e3 < args.spinup_ms:
         step()
         spin_steps += 1
+    if args.dump_outputs:
+        # the stream position of the last timed step sets the resampler's phase there: a spin-up of whole phase periods makes
+        # the dumped step the same from run to run, however many steps the time-bound spin-up took
+        period = phase_period_steps(blk, fs, B, am)
+        while spin_steps % period:
+            step()
+            spin_steps += 1
     for _ in range(args.warmup):
         step()
     ch.synchronize()
@@ -458,6 +513,10 @@ def main():
     mhz.append(fmr.probe_shader_clock(local_rank))
     blocks_done = (1 + spin_steps + args.warmup + args.steps) * B     # stream blocks decoded so far (set-up call + spin-up + warm-up + timed steps)
     audio_last = audio[0, :int(alen.sum())].cpu().numpy().copy()      # stream 0 of this rank, the last TIMED step
+    dumped = None
+    if args.dump_outputs:      # every stream of this rank, the last TIMED step (the steps below overwrite the buffer)
+        dumped = dump_outputs(args.dump_outputs, {"audio": audio[:, :int(alen.sum())].cpu().numpy(), "audio_block_len": alen},
+                              budget=DUMP_BUDGET // world, suffix=f"_rank{rank}" if world > 1 else "")
     region = {}
     for name, ms in ch.kernel_times():
         region.setdefault(name, []).append(ms)
@@ -666,6 +725,7 @@ def main():
                             "agc_residuals": [float("%.3g" % v) for v in st.agc_residual_history[:min(st.agc_iterations, 16)]],
                             "agc_serial_fallback": st.agc_fallback, "pll_serial_fallback": st.pll_fallback,
                             "af_tail_serial_fallback": st.af_agc_fallback},
+            **({"dump_outputs": dumped} if dumped else {}),
         }
     ch.close()
     headline = (not am and fmt == 0 and S == 1 and not R8B and not IF_FILTER and not args.multipath_stages and not args.no_pilot
@@ -795,9 +855,10 @@ def block_api(args, ch, iq, blk, fs, rank, world, am):
             k = 0                                # the buffer is periodic (tones snapped to its length): no seam
         t1 = time.perf_counter()
         if K == 1:
-            ch.process(blocks[k])
+            last = {"audio": ch.process(blocks[k])}
         else:                                    # K blocks the caller handed over one by one, decoded in one call
-            ch.process_blocks(x[None, k * blk:(k + K) * blk], [blk] * K)
+            a, al = ch.process_blocks(x[None, k * blk:(k + K) * blk], [blk] * K)
+            last = {"audio": a, "audio_block_len": al}
         k += K
         lat.append(time.perf_counter() - t1)
     dt = time.perf_counter() - t0
@@ -812,6 +873,9 @@ def block_api(args, ch, iq, blk, fs, rank, world, am):
                           "p99": round(float(np.percentile(lat, 99)), 1), "min": round(float(lat.min()), 1)},
            "roofline": None,
            "cpu_baseline": None if args.no_cpu_baseline else cpu_baseline(args.mode, args.multipath_stages, 4.0)}
+    if args.dump_outputs:      # what the last timed call returned
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, last, budget=DUMP_BUDGET // world,
+                                           suffix=f"_rank{rank}" if world > 1 else "")
     if rank == 0:
         print(json.dumps(out))
     ch.close()
@@ -826,6 +890,11 @@ def dry_run(args, rank, world, S, B, blk, pinned=None):
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo", rank=rank, world_size=world)
+
+    def barrier():
+        # dist.barrier() first asks torch for the machine's accelerator, which brings the GPU runtime up in every rank:
+        # a gloo all-reduce of a CPU tensor holds the ranks the same way and leaves the GPU alone
+        dist.all_reduce(torch.zeros(1))
     nb = min(B, 2)
     xs = [siggen.fm_stereo_iq(nb * blk, FS, stream_id=rank * S + s) for s in range(S)]
     chains = [_oracle_chain("fm") for _ in range(S)]
@@ -840,12 +909,12 @@ def dry_run(args, rank, world, S, B, blk, pinned=None):
     for _ in range(args.warmup):
         step()
     if world > 1:
-        dist.barrier()
+        barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     if world > 1:
-        dist.barrier()
+        barrier()
     dt = time.perf_counter() - t0
     per_rank_ms = [round(dt / args.steps * 1e3, 4)]
     if world > 1:
@@ -857,7 +926,7 @@ def dry_run(args, rank, world, S, B, blk, pinned=None):
         dt = float(mine.item())
     total = world * S * nb * blk * args.steps
     if world > 1:
-        dist.barrier()
+        barrier()
         dist.destroy_process_group()
     if rank == 0:
         # as in main(): the CPU legs on rank 0 once every rank's timed part is over, whatever the world size (bounded here)

@@ -1,8 +1,9 @@
 """Pins oracle constants/fixtures against the NUMERIC DATA of the reference
-tree.  Runs only where /root/reference exists (the build container); skipped on
-the GPU box.  Reads numbers, never code."""
+tree.  Reads numbers, never code.  The tables of the reference's
+sfmbase/FilterParameters.cpp are kept as parsed numbers (float64) in
+tests/golden/reference_filter_tables.npz, written by tools/make_filter_fixtures.py,
+so these tests need nothing outside the repository."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -10,16 +11,10 @@ import pytest
 import oracle_py as ora
 from conftest import GOLD, load_filter
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
-
 
 def _cpp_tables():
-    txt = open(os.path.join(REF, "sfmbase/FilterParameters.cpp")).read()
-    out = {}
-    for m in re.finditer(r"FilterParameters::(\w+)\s*=\s*\{([^}]*)\}", txt):
-        out[m.group(1)] = np.array([float(x) for x in re.findall(r"[-+]?\d[\d.]*(?:[eE][-+]?\d+)?", m.group(2))])
-    return out
+    with np.load(os.path.join(GOLD, "reference_filter_tables.npz")) as z:
+        return {k: z[k] for k in z.files}
 
 
 def test_filter_fixtures_equal_reference_tables():
