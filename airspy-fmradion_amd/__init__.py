@@ -29,6 +29,10 @@ IQ_CF32, IQ_S16, IQ_U8, IQ_S8 = 0, 1, 2, 3
 RESAMPLER_FAST, RESAMPLER_R8B = 0, 1
 _IQ_DTYPE = {0: np.complex64, 1: np.int16, 2: np.uint8, 3: np.int8}
 OK, ERR_NO_DEVICE, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_CAPACITY, ERR_HIP = 0, -1, -2, -3, -4, -5
+# FMR_FE_* (include/fmradion_amd.h): the kernel forms of the IF resampler, by bit
+FE_FORMS = {"fused": 1 << 0, "decim16": 1 << 1, "decim2_16": 1 << 2, "decim2_24": 1 << 3, "decim": 1 << 4,
+            "poly5h": 1 << 5, "poly5h_disc": 1 << 6, "poly4": 1 << 7, "poly4_am": 1 << 8, "poly3": 1 << 9,
+            "poly2": 1 << 10, "poly_frac": 1 << 11, "poly": 1 << 12}
 
 EXPORTS = [
     "fmr_create", "fmr_destroy", "fmr_last_error", "fmr_version", "fmr_resampler_info", "fmr_process",
@@ -261,6 +265,11 @@ class Chain:
 
     def resampler_info(self):
         return {k: self._L.fmr_resampler_info(self.h, i) for i, k in enumerate(["D", "NA", "LB", "MB", "TB", "LT"])}
+
+    def front_end_forms(self):
+        """Names (FE_FORMS) of the IF-resampler kernel forms this chain has launched since create, both stages."""
+        mask = self._L.fmr_resampler_info(self.h, 6) | self._L.fmr_resampler_info(self.h, 7)
+        return {k for k, bit in FE_FORMS.items() if mask >= 0 and mask & bit}
 
     # --- host-buffer API ---------------------------------------------------------
     def process(self, iq):

@@ -281,6 +281,7 @@ struct fmr_chain {
   DevBuf<float> d_hBp;                 // zero-padded tap rows for v3
   DevBuf<float> d_hpA;                 // stage-A taps in polyphase order [D][Q] (k_ifr_decim2)
   int qa = 0;                          // taps per phase (even), 0 = v2 kernel not applicable
+  unsigned fe_forms_a = 0, fe_forms_b = 0;   // FMR_FE_* bits of the stage-A / stage-B forms launched since create
   int hB_pitch = 0;                    // fractional-phase stage B: row pitch of d_hB (floats)
   DevBuf<float> d_gain, d_dec, d_hA, d_hB, d_coeff, d_atan, d_if_rms_blk, d_bb_mean_blk, d_bb_rms_blk, d_blk_ph;
   DevBuf<double> d_base, d_raw, d_am0, d_am1, d_a10, d_a11, d_pc0, d_pc1, d_audio, d_ahA, d_ahB, d_pilotcut;
@@ -1344,6 +1345,7 @@ int fmr_chain::run_front_end(CallCtx &k) {
         constexpr int BL = decltype(bl_tag)::value;
         const dim3 grid((count_mid + BL - 1) / BL, S);
         const size_t lds = sizeof(float2) * ((size_t)BL * rs.D + rs.NA - 1);
+        fe_forms_a |= FMR_FE_DECIM;
         hipLaunchKernelGGL(k_ifr_decim<BL>, grid, dim3(BL), lds, fes, d_iq, (long long)stride, N_in,
                            d_in_halo.p, H_in, d_hA.p, rs.NA, rs.D, top0, count_mid, d_mid.p,
                            (long long)(H_mid + max_mid), H_mid, (unsigned)(abs_in & 3u), cfg.enable_fourth_down);
@@ -1360,6 +1362,7 @@ int fmr_chain::run_front_end(CallCtx &k) {
         if (!((qa == 16 || (qa == 24 && in_fmt == 0)) && lds2 <= 64000 && (size_t)rs.D * (T2 + qa) <= (size_t)2 * 16 * BL2)) return;
         const unsigned magic = (unsigned)((1u << 24) / (unsigned)rs.D + 1);
         const dim3 grid2((count_mid + T2 - 1) / T2, S);
+        fe_forms_a |= qa == 24 ? FMR_FE_DECIM2_24 : FMR_FE_DECIM2_16;
         timed_on(fes, "ifr_decim", [&] {
           auto go = [&](auto kern) {
             hipLaunchKernelGGL(kern, grid2, dim3(BL2), lds2, fes, d_iq, (long long)stride, N_in, d_in_halo.p, H_in,
@@ -1396,6 +1399,7 @@ int fmr_chain::run_front_end(CallCtx &k) {
         const int wgs = std::max(1, fe_cus / S);
         a.tiles_per_wg = (a.n_tiles + wgs - 1) / wgs;
         const int grid16 = (a.n_tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
+        fe_forms_a |= FMR_FE_DECIM16;
         timed_on(fes, "ifr_decim", [&] {
           if (par16) hipLaunchKernelGGL((k_ifr_decim16<10, 195, 1>), dim3(grid16, S), dim3(DECIM16_THREADS), SH16::LDS_BYTES, fes, a);
           else hipLaunchKernelGGL((k_ifr_decim16<10, 195, 0>), dim3(grid16, S), dim3(DECIM16_THREADS), SH16::LDS_BYTES, fes, a);
@@ -1419,6 +1423,7 @@ int fmr_chain::run_front_end(CallCtx &k) {
     } else if (N_if > 0 && poly2_tile > 0) {
       const long long P_first = kB_prev / rs.LB, P_last = (kB_prev + N_if - 1) / rs.LB;
       const int tiles = (int)((P_last - P_first) / 64 + 1);
+      fe_forms_b |= poly5h ? FMR_FE_POLY5H : poly4_am ? FMR_FE_POLY4_AM : poly4 ? FMR_FE_POLY4 : poly3 ? FMR_FE_POLY3 : FMR_FE_POLY2;
       timed_on(fes, "ifr_poly", [&] {
         if (poly5h)
           hipLaunchKernelGGL((k_ifr_poly5h<48, 125>), dim3(std::min(tiles, n_cu), S), dim3(64 * FMR_POLY5H_WAVES), poly5h_lds,
@@ -1452,6 +1457,7 @@ int fmr_chain::run_front_end(CallCtx &k) {
       constexpr int BL = 256;
       const dim3 grid((unsigned)((N_if + BL - 1) / BL), S);
       const int span = (int)(((unsigned long long)(BL - 1) * rs.MB) / rs.LB) + rs.TB + 2;
+      fe_forms_b |= rs.LT ? FMR_FE_POLY_FRAC : FMR_FE_POLY;
       timed_on(fes, "ifr_poly", [&] {
         if (rs.LT) {
           // fractional-phase form: exact integer positions, call-relative on the device
@@ -1812,6 +1818,7 @@ int fmr_chain::run_tables(CallCtx &k) {
     if ((size_t)grid * S * 2 * FusedShape<D, NA>::MIDR > d_fused_mid32.n) { set_err("internal capacity exceeded (fused workgroups)"); return FMR_ERR_CAPACITY; }
     a.mid32 = d_fused_mid32.p;
     if (d_fe_stamps.p) hipLaunchKernelGGL(k_fused_stamp, dim3(1), dim3(1), 0, fes, stamp_slot(0), 16 * kStampCalls);
+    fe_forms_a |= FMR_FE_FUSED; fe_forms_b |= FMR_FE_FUSED;
     timed_on(fes, "ifr_fused", [&] {
       if (ext_a) {      // (timed with the events of its own dispatch)
         if (par) hipExtLaunchKernelGGL((k_ifr_fused<D, NA, 1, 0>), dim3(grid, S), dim3(FUSED_THREADS), kLds, fes, ext_a, ext_b, 0, a);
@@ -1858,6 +1865,7 @@ int fmr_chain::run_tables(CallCtx &k) {
     a.mid32 = d_run_ph.p;
     if ((size_t)a.n_tiles * 3 * S > d_fused_part.n || (size_t)r8b_grid * 2 * S > d_run_ph.n) { set_err("internal capacity exceeded (stage-B tiles)"); return FMR_ERR_CAPACITY; }
     if (pipelined && disc_commit_on_side) HIPCHK(hipStreamWaitEvent(stream, ev_stats, 0));
+    fe_forms_b |= FMR_FE_POLY5H_DISC;
     timed_on(stream, "ifr_poly", [&] {
       hipLaunchKernelGGL((k_ifr_poly5h<48, 125, Poly5hDiscEpi>), dim3(r8b_grid, S), dim3(64 * FMR_POLY5H_WAVES), poly5h_lds, stream,
                          d_mid.p, (long long)(H_mid + max_mid), k.r8b_mA_prev - H_mid, H_mid + k.r8b_count_mid, d_afrag5h.p,
@@ -2668,6 +2676,8 @@ long long fmr_resampler_info(const fmr_chain *c, int which) {
   case 3: return c->rs.MB;
   case 4: return c->rs.TB;
   case 5: return c->rs.LT;
+  case 6: return c->fe_forms_a;
+  case 7: return c->fe_forms_b;
   }
   return -1;
 }

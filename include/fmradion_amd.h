@@ -151,9 +151,28 @@ void fmr_destroy(fmr_chain *c);
 const char *fmr_last_error(void);
 const char *fmr_version(void);
 
+/* Kernel forms of the IF resampler (fmr_resampler_info which = 6 / 7).  The form is picked at create from the design
+ * shape, the class, input_format and enable_fourth_down, and again on every call from its size. */
+enum {
+  FMR_FE_FUSED = 1 << 0,        /* k_ifr_fused: stage A + stage B (+ discriminator) in one kernel (set in both masks) */
+  FMR_FE_DECIM16 = 1 << 1,      /* stage A: k_ifr_decim16 (R8B class at 10 MS/s, long calls) */
+  FMR_FE_DECIM2_16 = 1 << 2,    /* stage A: k_ifr_decim2, up to 16 taps per phase (also the raw-format ingest) */
+  FMR_FE_DECIM2_24 = 1 << 3,    /* stage A: k_ifr_decim2, 17..24 taps per phase (cf32 only) */
+  FMR_FE_DECIM = 1 << 4,        /* stage A: k_ifr_decim, the generic form (D = 1, D > 15, long filters) */
+  FMR_FE_POLY5H = 1 << 5,       /* stage B: k_ifr_poly5h (48/125, fp16 three-product form) */
+  FMR_FE_POLY5H_DISC = 1 << 6,  /* stage B: k_ifr_poly5h with the discriminator epilogue */
+  FMR_FE_POLY4 = 1 << 7,        /* stage B: k_ifr_poly4<48, 125, 210> */
+  FMR_FE_POLY4_AM = 1 << 8,     /* stage B: k_ifr_poly4<48, 128, 214> (the 3/8/214 shape) */
+  FMR_FE_POLY3 = 1 << 9,        /* stage B: k_ifr_poly3 */
+  FMR_FE_POLY2 = 1 << 10,       /* stage B: k_ifr_poly2 */
+  FMR_FE_POLY_FRAC = 1 << 11,   /* stage B: k_ifr_poly_frac (fractional-phase form) */
+  FMR_FE_POLY = 1 << 12         /* stage B: k_ifr_poly, the generic form */
+};
+
 /* Design introspection of the resampler stand-in (DESIGN.md "Resampler
  * specification").  which = 0:D 1:NA 2:LB 3:MB 4:TB 5:LT (rows of the interpolated
- * phase table of the fractional-phase form, 0 = one row per phase); -1 when no resampler. */
+ * phase table of the fractional-phase form, 0 = one row per phase); 6 / 7: bitmask of the stage-A / stage-B kernel
+ * forms (FMR_FE_*) this chain has launched since create (test introspection); -1 when no resampler. */
 long long fmr_resampler_info(const fmr_chain *c, int which);
 
 /* The product's resampler design on the host (no GPU needed): taps of stage A (stage = 0, NA doubles) or of the
