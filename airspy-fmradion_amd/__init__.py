@@ -33,6 +33,8 @@ OK, ERR_NO_DEVICE, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_CAPACITY, ERR_HIP = 0, -1, 
 FE_FORMS = {"fused": 1 << 0, "decim16": 1 << 1, "decim2_16": 1 << 2, "decim2_24": 1 << 3, "decim": 1 << 4,
             "poly5h": 1 << 5, "poly5h_disc": 1 << 6, "poly4": 1 << 7, "poly4_am": 1 << 8, "poly3": 1 << 9,
             "poly2": 1 << 10, "poly_frac": 1 << 11, "poly": 1 << 12}
+# FMR_CB_* (include/fmradion_amd.h): the kernel forms of a channel bank's stage A (fmr_resampler_info which = 8)
+CB_FORMS = {"modtap": 1 << 0}
 
 EXPORTS = [
     "fmr_create", "fmr_destroy", "fmr_last_error", "fmr_version", "fmr_resampler_info", "fmr_process",
@@ -56,7 +58,7 @@ class Config(C.Structure):
         ("deemphasis_us", C.c_double), ("pilot_shift", C.c_int), ("multipath_stages", C.c_uint),
         ("max_block_len", C.c_size_t), ("max_blocks", C.c_int), ("nbfm_freq_dev", C.c_double),
         ("input_format", C.c_int), ("output_rate", C.c_double), ("resampler_class", C.c_int), ("struct_size", C.c_uint),
-        ("in_order", C.c_int),
+        ("in_order", C.c_int), ("channel_offset_hz", C.POINTER(C.c_int32)),
     ]
 
 
@@ -223,8 +225,16 @@ class Chain:
     def __init__(self, mode=MODE_FM, input_rate=384000.0, enable_resampler=False, fourth_down=False,
                  fmfilter_enable=False, filter_coeff=None, stereo=True, deemphasis_us=50.0, pilot_shift=False,
                  multipath_stages=0, max_block_len=65536, max_blocks=1, n_streams=1, device=0, nbfm_freq_dev=0.0, input_format=0,
-                 output_rate=0.0, resampler_class=RESAMPLER_FAST, in_order=False, ab=False):
+                 output_rate=0.0, resampler_class=RESAMPLER_FAST, in_order=False, ab=False, channel_offsets_hz=None):
+        """channel_offsets_hz: a channel bank -- n_streams offsets [Hz] (n_streams may be left at 1: it follows the
+        list); every iq argument then holds one row, the capture, and stream s decodes the station at +offset[s] Hz."""
         self._L = lib(ab=bool(ab))
+        self.bank = channel_offsets_hz is not None
+        if self.bank:
+            self._offsets = (C.c_int32 * len(channel_offsets_hz))(*[int(f) for f in channel_offsets_hz])
+            if n_streams == 1:
+                n_streams = len(channel_offsets_hz)
+            assert n_streams == len(channel_offsets_hz), "channel_offsets_hz needs n_streams entries"
         coeff = np.ascontiguousarray(DELAY_3TAPS if filter_coeff is None else filter_coeff, dtype=np.float32)
         self._coeff = coeff
         cfg = Config()
@@ -242,6 +252,8 @@ class Chain:
         cfg.resampler_class = int(resampler_class)
         cfg.struct_size = C.sizeof(Config)
         cfg.in_order = int(bool(in_order))
+        if self.bank:
+            cfg.channel_offset_hz = self._offsets
         self.input_format = int(input_format)
         self.n_streams, self.mode, self.stereo = n_streams, mode, bool(stereo) and mode == MODE_FM
         self.h = C.c_void_p()
@@ -271,6 +283,11 @@ class Chain:
         mask = self._L.fmr_resampler_info(self.h, 6) | self._L.fmr_resampler_info(self.h, 7)
         return {k for k, bit in FE_FORMS.items() if mask >= 0 and mask & bit}
 
+    def channel_bank_forms(self):
+        """Names (CB_FORMS) of the channel-bank kernel forms this chain has launched since create (empty: no bank)."""
+        mask = self._L.fmr_resampler_info(self.h, 8)
+        return {k for k, bit in CB_FORMS.items() if mask >= 0 and mask & bit}
+
     # --- host-buffer API ---------------------------------------------------------
     def process(self, iq):
         """FmDecoder::process / AmDecoder::process shape: one block in, audio doubles out."""
@@ -282,13 +299,14 @@ class Chain:
         return out[:n.value].copy()
 
     def process_blocks(self, iq, block_len):
-        """iq: (n_streams, N) complex64; block_len: consecutive block lengths. Returns (audio[S][total], audio_len)."""
+        """iq: (n_streams, N) complex64 (a channel bank: the capture, shape (N,) or (1, N)); block_len: consecutive block
+        lengths. Returns (audio[S][total], audio_len)."""
         if self.input_format == IQ_CF32:
             iq = np.ascontiguousarray(np.atleast_2d(iq), dtype=np.complex64)
         else:   # raw formats: (n_streams, N, 2) interleaved I,Q of the format's integer type
             iq = np.ascontiguousarray(iq, dtype=_IQ_DTYPE[self.input_format])
             assert iq.ndim == 3 and iq.shape[2] == 2
-        assert iq.shape[0] == self.n_streams
+        assert iq.shape[0] == (1 if self.bank else self.n_streams)
         bl = np.ascontiguousarray(block_len, dtype=np.uint32)
         assert int(bl.sum()) <= iq.shape[1]
         acap = 2 * (int(bl.sum()) + 64 * len(bl))
@@ -320,6 +338,7 @@ class Chain:
 
     # --- device-buffer API (pointers are raw device addresses, e.g. torch .data_ptr()) -------------
     def process_blocks_device(self, d_iq_ptr, stream_stride, block_len, d_audio_ptr, audio_stride, sync=False):
+        """A channel bank reads one row at d_iq_ptr (stream_stride is ignored)."""
         bl = np.ascontiguousarray(block_len, dtype=np.uint32)
         alen = np.zeros(len(bl), dtype=np.uint32)
         u32p = C.POINTER(C.c_uint32)

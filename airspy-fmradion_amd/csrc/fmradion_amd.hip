@@ -29,6 +29,7 @@
 #include "kernels_par.hpp"
 #include "kernels_fused.hpp"
 #include "kernels_decim16.hpp"
+#include "kernels_chanbank.hpp"
 
 namespace {
 #include "filter_tables.inc"
@@ -282,6 +283,14 @@ struct fmr_chain {
   DevBuf<float> d_hpA;                 // stage-A taps in polyphase order [D][Q] (k_ifr_decim2)
   int qa = 0;                          // taps per phase (even), 0 = v2 kernel not applicable
   unsigned fe_forms_a = 0, fe_forms_b = 0;   // FMR_FE_* bits of the stage-A / stage-B forms launched since create
+  // channel bank (fmr_config.channel_offset_hz): S channels of one input row, stage A in k_ifr_chan (kernels_chanbank.hpp)
+  bool bank = false;
+  std::vector<int32_t> cb_off;              // the offsets [Hz], copied at create
+  unsigned long long cb_F = 0;              // input_rate [Hz]
+  DevBuf<float2> d_cb_taps;                 // modulated stage-A taps [group][k][FMR_CB_G]
+  DevBuf<ChanPhase> d_cb_ph;                // per channel: f mod F, f D mod F
+  unsigned cb_forms = 0;                    // FMR_CB_* bits launched since create
+  int in_rows() const { return bank ? 1 : S; }   // rows of the input buffers (d_in, d_in_halo)
   int hB_pitch = 0;                    // fractional-phase stage B: row pitch of d_hB (floats)
   DevBuf<float> d_gain, d_dec, d_hA, d_hB, d_coeff, d_atan, d_if_rms_blk, d_bb_mean_blk, d_bb_rms_blk, d_blk_ph;
   DevBuf<double> d_base, d_raw, d_am0, d_am1, d_a10, d_a11, d_pc0, d_pc1, d_audio, d_ahA, d_ahB, d_pilotcut;
@@ -379,6 +388,7 @@ struct fmr_chain {
     d_pll_wgr.release(); d_pll_pre.release(); d_pll_wfirst.release(); d_pll_sync.release(); d_pll_tick2.release(); d_ck_mask.release(); d_walk_go.release(); d_pll_gres.release(); d_pll_PQ2.release(); d_pll_dstart2.release(); d_pll_PQ.release(); d_pll_dstart.release(); d_blk_level.release(); d_blk_wraps.release(); d_agc_M.release(); d_agc_tick.release(); d_af_tick.release(); d_dc_G.release(); d_dc_start.release(); d_agc_nodes.release();
     d_agc_G.release(); d_ck_wraps.release(); d_flags.release();
     d_af_nodes.release(); d_af_G.release(); d_af_M.release(); d_af_out.release();
+    d_cb_taps.release(); d_cb_ph.release();
     if (h_tab_all) (void)hipHostFree(h_tab_all);
     if (h_marks) (void)hipHostFree(h_marks);
     for (hipEvent_t e : {ev_disc, ev_pll, ev_stats, ev_fin, ev_if}) if (e) (void)hipEventDestroy(e);
@@ -418,6 +428,7 @@ struct fmr_chain {
     auto launch = [&] { launch_(); if (d_fe_stamps.p) stamp_after(st, name); };
     // mode 2: only the kernels of the FIR+discriminator stage carry events (two per kernel per call)
     const bool stage_kernel = std::strcmp(name, "ifr_decim") == 0 || std::strcmp(name, "ifr_poly") == 0 ||
+                              std::strcmp(name, "ifr_chan") == 0 ||
                               std::strcmp(name, "disc") == 0 || std::strcmp(name, "ifr_fused") == 0 ||
                               std::strcmp(name, "blk_reduce") == 0 ||
                               (mode == FMR_MODE_FM && std::strcmp(name, "fm_block") == 0);   // FM with the IF FIR on
@@ -494,6 +505,8 @@ struct fmr_chain {
     return FMR_OK;
   }
   int init(const fmr_config *c);
+  int check_bank(const fmr_config *c);
+  int upload_bank(const std::vector<float> &fa);
   bool cold = true;                     // no call yet: AGC at its initial gain, PLL unlocked
   int pps_block_base = 0;               // blocks of the call that ran before the part whose PPS events the state holds
   int run_cold_aware(const float2 *d_iq, size_t stride, const uint32_t *block_len, int nb, double *d_aud,
@@ -599,6 +612,7 @@ struct fmr_chain {
   int flush_tail(hipEvent_t gate);
   int enqueue_tail(hipEvent_t gate);
   int run_front_end(CallCtx &k);
+  int launch_chan(hipStream_t st, const float2 *d_iq, long long N_in, long long mA_prev, long long n_prev, int count_mid);
   int finish_front_end_stage(CallCtx &k);
   int run_tables(CallCtx &k);
   int run_if_stage(CallCtx &k);
@@ -632,6 +646,13 @@ int fmr_chain::init(const fmr_config *c) {
     return FMR_ERR_UNSUPPORTED;
   }
   has_dec = (mode != FMR_MODE_NONE);
+  if (c->channel_offset_hz) {
+    if (int rc = check_bank(c)) return rc;
+    bank = true;
+    cb_off.assign(c->channel_offset_hz, c->channel_offset_hz + S);
+    cb_F = (unsigned long long)c->input_rate;
+    cfg.channel_offset_hz = nullptr;       // (copied: the caller's array need not outlive fmr_create)
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err("no HIP device"); return FMR_ERR_NO_DEVICE; }
   if (c->device < 0 || c->device >= ndev) { set_err("device %d out of range (%d devices)", c->device, ndev); return FMR_ERR_BAD_ARG; }
@@ -724,7 +745,7 @@ int fmr_chain::init(const fmr_config *c) {
         if ((rc = upload(d_hpA, hp.data(), hp.size()))) return rc;
       }
     }
-    if (rs.D == 10 && rs.NA == 195 && in_fmt == 0 && !c->enable_fourth_down && !env.no_fused && !env.serial) {
+    if (rs.D == 10 && rs.NA == 195 && in_fmt == 0 && !c->enable_fourth_down && !bank && !env.no_fused && !env.serial) {
       bool sym = true;
       for (int k = 0; sym && k < rs.NA / 2; k++) sym = (fa[k] == fa[rs.NA - 1 - k]);
       if (sym) {
@@ -857,7 +878,7 @@ int fmr_chain::init(const fmr_config *c) {
           // epilogue; with either of them the epilogue stores the IF samples and the chain goes on as usual.
           bool sym = rs.D == kFusedD && rs.NA == kFusedNA;
           for (int k = 0; sym && k < rs.NA / 2; k++) sym = (fa[k] == fa[rs.NA - 1 - k]);
-          if (sym && mode == FMR_MODE_FM && in_fmt == 0 && !c->enable_fourth_down && !env.no_fused) {
+          if (sym && mode == FMR_MODE_FM && in_fmt == 0 && !c->enable_fourth_down && !bank && !env.no_fused) {
             if ((rc = upload(d_hB_last, fb.data() + (size_t)phi[47] * rs.TB, (size_t)rs.TB))) return rc;
             { std::vector<unsigned short> fr((size_t)2 * 8 * 2 * 64 * 8);
               fused_make_afragA<kFusedD, kFusedNA>(fa.data(), fr.data());
@@ -876,13 +897,14 @@ int fmr_chain::init(const fmr_config *c) {
         }
       }
     }
-    if ((rc = d_in_halo.alloc((size_t)S * H_in))) return rc;
+    if ((rc = d_in_halo.alloc((size_t)in_rows() * H_in))) return rc;
     if ((rc = d_mid.alloc((size_t)S * (H_mid + max_mid)))) return rc;
+    if (bank && (rc = upload_bank(fa))) return rc;
   } else {
     max_if = max_in;
   }
   int rc;
-  if ((rc = d_in.alloc((size_t)S * max_in))) return rc;
+  if ((rc = d_in.alloc((size_t)in_rows() * max_in))) return rc;
   ntaps = c->n_filter_coeff;
   ssb_like = (mode == FMR_MODE_USB || mode == FMR_MODE_LSB || mode == FMR_MODE_CW || mode == FMR_MODE_WSPR);
   const float *filter_src = c->filter_coeff;
@@ -1183,6 +1205,95 @@ int fmr_chain::init(const fmr_config *c) {
   return FMR_OK;
 }
 
+// ---- channel bank (fmr_config.channel_offset_hz; DESIGN.md "Channel bank") ----
+// The rules of a bank, checked before the device is opened.  Stage-A shapes in the kernel's range: D = 2 .. 24 (the LDS
+// span of 64 outputs stays under 60 KB) and NA <= 400 (the taps of a group of channels stay in the scalar cache's reach).
+constexpr int kBankMaxD = 24, kBankMaxNA = 400;
+int fmr_chain::check_bank(const fmr_config *c) {
+  if (c->mode == FMR_MODE_NONE || !c->enable_resampler) {
+    set_err("channel bank: needs a decoder chain with the IF resampler (enable_resampler = 1, mode != -1)");
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (c->input_format != FMR_IQ_CF32) {
+    set_err("channel bank: input_format must be FMR_IQ_CF32 (convert raw samples on the host)");
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (c->enable_fourth_down) {
+    set_err("channel bank: enable_fourth_down must be 0 (add input_rate / 4 to the offsets instead)");
+    return FMR_ERR_BAD_ARG;
+  }
+  const double F = c->input_rate;
+  if (!(F >= 1.0 && F < 4294967296.0) || F != std::floor(F)) {
+    set_err("channel bank: input_rate %.6f is not a whole number of hertz (ppm-corrected rates are not supported)", F);
+    return FMR_ERR_UNSUPPORTED;
+  }
+  const double dec_rate = c->mode == FMR_MODE_FM ? kFmRate : kAmRate;
+  for (int s = 0; s < c->n_streams; s++) {
+    const double f = (double)c->channel_offset_hz[s];
+    if (std::fabs(f) > 0.5 * (F - dec_rate)) {
+      set_err("channel bank: |channel_offset_hz[%d]| = %.0f Hz exceeds (input_rate - decoder rate) / 2 = %.0f Hz", s,
+              std::fabs(f), 0.5 * (F - dec_rate));
+      return FMR_ERR_BAD_ARG;
+    }
+  }
+  if (c->resampler_class != FMR_RESAMPLER_FAST && c->resampler_class != FMR_RESAMPLER_R8B) return FMR_OK;   // (init refuses it)
+  ResamplerDesign d;
+  const bool ok = c->resampler_class == FMR_RESAMPLER_R8B ? d.design(F, dec_rate, kR8bAtten, kR8bPassFrac, true)
+                                                          : d.design(F, dec_rate, kIfAtten);
+  if (!ok) return FMR_OK;     // (init refuses the ratio)
+  if (d.D < 2 || d.D > kBankMaxD || d.NA > kBankMaxNA) {
+    set_err("channel bank: stage-A shape D = %d, NA = %d (%.0f -> %.0f Hz) is outside the bank kernel's range "
+            "(D = 2 .. %d, NA <= %d)", d.D, d.D == 1 ? 1 : d.NA, F, dec_rate, kBankMaxD, kBankMaxNA);
+    return FMR_ERR_UNSUPPORTED;
+  }
+  return FMR_OK;
+}
+
+// c_s[k] = hA[k] exp(+2 pi i ((f_s k) mod F) / F) in double, rounded once; [group][k][g], channels beyond S are zero
+int fmr_chain::upload_bank(const std::vector<float> &fa) {
+  const int G = FMR_CB_G, ng = (S + G - 1) / G, NA = rs.NA;
+  const unsigned long long F = cb_F;
+  std::vector<float2> taps((size_t)ng * NA * G, make_float2(0.f, 0.f));
+  std::vector<ChanPhase> ph((size_t)S);
+  for (int s = 0; s < S; s++) {
+    const long long fl = cb_off[s];
+    const unsigned long long fm = (unsigned long long)(((fl % (long long)F) + (long long)F) % (long long)F);
+    ph[s] = ChanPhase{fm, (fm * (unsigned long long)rs.D) % F};
+    for (int k = 0; k < NA; k++) {
+      const double a = 2.0 * M_PI * (double)((fm * (unsigned long long)k) % F) / (double)F;
+      const double h = (double)fa[k];
+      taps[((size_t)(s / G) * NA + k) * G + (s % G)] = make_float2((float)(h * std::cos(a)), (float)(h * std::sin(a)));
+    }
+  }
+  if (int rc = upload(d_cb_taps, taps.data(), taps.size())) return rc;
+  if (int rc = upload(d_cb_ph, ph.data(), ph.size())) return rc;
+  return FMR_OK;
+}
+
+// stage A of every channel for count_mid outputs from mA_prev on (k_ifr_chan)
+int fmr_chain::launch_chan(hipStream_t st, const float2 *d_iq, long long N_in, long long mA_prev, long long n_prev, int count_mid) {
+  constexpr int G = FMR_CB_G;
+  const long long top0 = (long long)rs.D * mA_prev + rs.ca() - n_prev;
+  const unsigned long long N0 = (unsigned long long)rs.D * (unsigned long long)mA_prev + (unsigned long long)rs.ca();
+  const unsigned long long nmod0 = N0 % cb_F;
+  const size_t tail = sizeof(float2) * (size_t)(rs.NA - 1), per_out = sizeof(float2) * (size_t)rs.D;
+  auto go = [&](auto bl_tag) {
+    constexpr int BL = decltype(bl_tag)::value;
+    const dim3 grid((unsigned)((count_mid + BL - 1) / BL), (unsigned)((S + G - 1) / G));
+    hipLaunchKernelGGL((k_ifr_chan<BL, G>), grid, dim3(BL), per_out * BL + tail, st, d_iq, N_in, d_in_halo.p, H_in,
+                       d_cb_taps.p, rs.NA, rs.D, top0, count_mid, d_mid.p, (long long)(H_mid + max_mid), H_mid, d_cb_ph.p, S,
+                       nmod0, cb_F);
+  };
+  cb_forms |= FMR_CB_MODTAP;
+  timed_on(st, "ifr_chan", [&] {
+    if (256 * per_out + tail <= 60000) go(std::integral_constant<int, 256>{});
+    else if (128 * per_out + tail <= 60000) go(std::integral_constant<int, 128>{});
+    else go(std::integral_constant<int, 64>{});
+  });
+  HIPCHK(hipGetLastError());
+  return FMR_OK;
+}
+
 // A chain's first call starts from the initial AGC gain and an unlocked PLL; over that transient the Newton
 // iterations of the time-parallel recurrences diverge and the serial kernels take over -- 2 s for a 2048-block
 // call.  A call is by construction equal to its blocks processed one after the other, so a long first call is
@@ -1339,6 +1450,8 @@ int fmr_chain::run_front_end(CallCtx &k) {
     if_valid = dec_valid;                      // ... and so are the IF samples behind its discriminator epilogue (the slot holds |x|^2 then)
     if (use_fused) {
       fused_geom = {mA_prev, kB_prev, n_prev, count_mid};
+    } else if (count_mid > 0 && bank) {
+      if (int rc = launch_chan(fes, d_iq, N_in, mA_prev, n_prev, count_mid)) return rc;
     } else if (count_mid > 0) {
       const long long top0 = (long long)rs.D * mA_prev + rs.ca() - n_prev;
       auto launch_decim = [&](auto bl_tag) {
@@ -1475,7 +1588,11 @@ int fmr_chain::run_front_end(CallCtx &k) {
                            ifbuf, (long long)(H_if + max_if), H_if);
       });
     }
-    if (N_in > 0 && !use_fused && !(k.r8b_tail && pipelined)) {
+    if (N_in > 0 && bank) {      // (one row; the pipelined R8B tail's k_fe_post leaves the input history to this kernel)
+      timed_on(fes, "in_halo", [&] {
+        hipLaunchKernelGGL((k_update_in_halo<256, 0>), dim3(1, 1), dim3(256), 0, fes, d_in_halo.p, H_in, d_iq, 0ll, N_in);
+      });
+    } else if (N_in > 0 && !use_fused && !(k.r8b_tail && pipelined)) {
       timed_on(fes, "in_halo", [&] {
         switch (in_fmt) {
         case 1: hipLaunchKernelGGL((k_update_in_halo<256, 1>), dim3(1, S), dim3(256), 0, fes, d_in_halo.p, H_in, d_iq, (long long)stride, N_in); break;
@@ -1880,8 +1997,8 @@ int fmr_chain::run_tables(CallCtx &k) {
       HIPCHK(hipEventRecord(ev_fe[k.par], stream));
       const int count_mid = k.r8b_count_mid;
       k.fe_post = [=] {
-        hipLaunchKernelGGL(k_fe_post<256>, dim3(3, S), dim3(256), 0, stream, d_in_halo.p, H_in, d_iq, (long long)stride, N_in,
-                           d_mid.p, (long long)(H_mid + max_mid), H_mid, count_mid, d_state.p, 1);
+        hipLaunchKernelGGL(k_fe_post<256>, dim3(3, S), dim3(256), 0, stream, d_in_halo.p, H_in, d_iq, (long long)stride,
+                           bank ? 0ll : N_in, d_mid.p, (long long)(H_mid + max_mid), H_mid, count_mid, d_state.p, 1);
       };
       if (int rc = flush_tail(ev_fe[k.par])) return rc;
     }
@@ -2678,6 +2795,7 @@ long long fmr_resampler_info(const fmr_chain *c, int which) {
   case 5: return c->rs.LT;
   case 6: return c->fe_forms_a;
   case 7: return c->fe_forms_b;
+  case 8: return c->cb_forms;
   }
   return -1;
 }
@@ -2774,7 +2892,7 @@ int fmr_process_blocks(fmr_chain *c, const float *iq, size_t stream_stride, cons
   HIPCHK(hipSetDevice(c->cfg.device));
   if (N_in)
     HIPCHK(hipMemcpy2DAsync(c->d_in.p, (size_t)c->in_bps * c->max_in, iq, (size_t)c->in_bps * stream_stride,
-                            (size_t)c->in_bps * N_in, c->S, hipMemcpyHostToDevice, c->stream));
+                            (size_t)c->in_bps * N_in, (size_t)c->in_rows(), hipMemcpyHostToDevice, c->stream));
   const size_t dstride = c->stereo ? 2 * c->max_au : c->max_au;
   std::vector<uint32_t> alen(n_blocks, 0);
   const int rc = c->run_cold_aware(c->d_in.p, c->max_in, block_len, n_blocks, c->d_audio.p, dstride, alen.data());
@@ -2810,6 +2928,10 @@ int fmr_fourth_convert(fmr_chain *c, const float *iq, size_t n, float *out_iq, i
 int fmr_process(fmr_chain *c, const float *iq, size_t n, double *audio, size_t audio_cap, size_t *n_audio) {
   if (!c || !n_audio) return FMR_ERR_BAD_ARG;
   *n_audio = 0;
+  if (c->bank && c->S > 1) {
+    set_err("fmr_process: a channel bank of %d channels produces %d audio rows; use fmr_process_blocks", c->S, c->S);
+    return FMR_ERR_BAD_ARG;
+  }
   if (n == 0) return FMR_OK;             // FmDecode.cpp:89-92
   uint32_t bl = (uint32_t)n, al = 0;
   const int rc = fmr_process_blocks(c, iq, n, &bl, 1, audio, audio_cap, &al);

@@ -26,6 +26,7 @@
 //    main.cpp treats its own fatal errors (message on stderr, exit(1), main.cpp:764-767); define
 //    FMR_FACADE_THROW before including this header to get std::runtime_error instead (the tests do).
 #pragma once
+#include <algorithm>
 #include <complex>
 #include <cstdint>
 #include <cstdio>
@@ -424,3 +425,85 @@ private:
   fmr_chain *m_chain = nullptr;
 };
 
+
+// ChannelBank (no counterpart in the reference): K stations out of one wideband capture.  Channel k decodes the station
+// at +offsets_hz[k] Hz in the capture's spectrum (fmr_config.channel_offset_hz) with the FmDecoder / AmDecoder /
+// NbfmDecoder of `mode` behind an IfResampler of `resampler_class`; every channel shares that one configuration.
+// filter_coeff is what the decoder of `mode` takes: FmDecoder's IF filter (used when fmfilter_enable), AmDecoder's
+// amfilter_coeff (AM / DSB; USB / LSB / CW / WSPR use AmDecoder's built-in filters), NbfmDecoder's nbfmfilter_coeff.
+// stereo / deemphasis / pilot_shift / multipath_stages are FmDecoder's and ignored by the other modes; nbfm_freq_dev is
+// NbfmDecoder's freq_dev (0 = its default, 8000 Hz).
+// process() takes the capture block once and returns one audio vector per channel; the getters take the channel.
+class ChannelBank {
+public:
+  ChannelBank(double input_rate, const std::vector<int32_t> &offsets_hz, ModType mode, bool fmfilter_enable,
+              IQSampleCoeff &filter_coeff, bool stereo, double deemphasis, bool pilot_shift, unsigned int multipath_stages,
+              int resampler_class = FMR_RESAMPLER_R8B, int device = 0, size_t max_block_len = 65536,
+              double nbfm_freq_dev = 0.0)
+      : m_offsets(offsets_hz), m_max_block(max_block_len),
+        m_freq_dev(mode == ModType::FM ? FmDecoder::freq_dev : nbfm_freq_dev > 0 ? nbfm_freq_dev : 8000.0) {
+    if (m_offsets.empty()) fmr_detail::fail("ChannelBank: no channel");
+    fmr_config cfg{};
+    cfg.device = device; cfg.n_streams = (int)m_offsets.size(); cfg.mode = static_cast<int>(mode);
+    cfg.input_rate = input_rate; cfg.enable_resampler = 1; cfg.resampler_class = resampler_class;
+    cfg.fmfilter_enable = fmfilter_enable; cfg.filter_coeff = filter_coeff.data(); cfg.n_filter_coeff = (int)filter_coeff.size();
+    cfg.stereo = stereo; cfg.deemphasis_us = deemphasis; cfg.pilot_shift = pilot_shift; cfg.multipath_stages = multipath_stages;
+    cfg.max_block_len = max_block_len; cfg.max_blocks = 1; cfg.nbfm_freq_dev = nbfm_freq_dev;
+    cfg.channel_offset_hz = m_offsets.data();
+    m_chain = fmr_detail::make(cfg);
+  }
+  ~ChannelBank() { fmr_destroy(m_chain); }
+  ChannelBank(const ChannelBank &) = delete;
+  ChannelBank &operator=(const ChannelBank &) = delete;
+
+  size_t channels() const { return m_offsets.size(); }
+  int32_t offset_hz(size_t ch) const { return m_offsets.at(ch); }
+
+  // audio[k] = what channel k produced from this capture block (empty = "nothing yet"); blocks longer than the chain's
+  // block capacity are decoded in consecutive pieces
+  void process(const IQSampleVector &samples_in, std::vector<SampleVector> &audio) {
+    const size_t K = m_offsets.size();
+    audio.assign(K, SampleVector());
+    std::vector<double> buf;
+    for (size_t off = 0; off < samples_in.size(); off += m_max_block) {
+      const size_t n = std::min(m_max_block, samples_in.size() - off);
+      const size_t stride = 2 * (n + 64);
+      buf.assign(K * stride, 0.0);
+      uint32_t bl = (uint32_t)n, al = 0;
+      fmr_detail::check(fmr_process_blocks(m_chain, reinterpret_cast<const float *>(samples_in.data() + off), n, &bl, 1,
+                                           buf.data(), stride, &al),
+                        "fmr_process_blocks");
+      for (size_t k = 0; k < K; k++) audio[k].insert(audio[k].end(), buf.begin() + k * stride, buf.begin() + k * stride + al);
+    }
+  }
+  bool stereo_detected(size_t ch) { return status(ch).stereo_detected != 0; }
+  float get_tuning_offset(size_t ch) {     // FmDecoder: x 75 kHz; NbfmDecoder: x its freq_dev
+    return (float)(status(ch).baseband_mean * m_freq_dev);
+  }
+  float get_baseband_level(size_t ch) { return status(ch).baseband_level; }
+  double get_pilot_level(size_t ch) { return status(ch).pilot_level; }
+  float get_if_rms(size_t ch) { return status(ch).if_rms; }
+  float get_if_agc_gain(size_t ch) { return status(ch).if_agc_gain; }
+  double get_multipath_error(size_t ch) { return status(ch).multipath_error; }
+  // PPS events of channel ch in the most recent process() call
+  std::vector<PilotPhaseLock::PpsEvent> get_pps_events(size_t ch) {
+    status(ch);
+    fmr_pps_event ev[64];
+    const int n = fmr_get_pps_events(m_chain, (int)ch, ev, 64);
+    std::vector<PilotPhaseLock::PpsEvent> out;
+    for (int i = 0; i < n && i < 64; i++) out.push_back({ev[i].pps_index, ev[i].sample_index, ev[i].block_position});
+    return out;
+  }
+
+private:
+  fmr_status status(size_t ch) {
+    if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
+    fmr_status st{};
+    fmr_detail::check(fmr_get_status(m_chain, (int)ch, &st), "fmr_get_status");
+    return st;
+  }
+  std::vector<int32_t> m_offsets;
+  size_t m_max_block;
+  double m_freq_dev;
+  fmr_chain *m_chain = nullptr;
+};

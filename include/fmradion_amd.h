@@ -109,6 +109,21 @@ typedef struct {
    * through host buffers, the facade's FmDecoder::process -- the pipelined chain has nothing to overlap and pays for its
    * stage hand-offs: 341 against 303 us per 65536-sample block.  Same audio, bit for bit.  0 (default): pipelined. */
   int in_order;
+  /* Channel bank: n_streams frequency offsets in Hz, read and copied at create; NULL (default) = n_streams independent
+   * IQ rows as before.  Set, every `iq` argument holds ONE row, the capture (stream_stride is ignored), and stream s
+   * decodes  u_s[n] = x[n] exp(-2 pi i ((f_s n) mod F) / F),  F = input_rate,  n = samples since the chain's first
+   * sample (across calls of any length): a station at +f_s Hz in the capture's spectrum.  Stage A of the IF resampler
+   * runs for all channels in one kernel ("ifr_chan") that reads the capture once per group of channels; everything
+   * behind it is the plain chain's with n_streams = the number of channels.  Refused at create ("Channel
+   * bank"): front-end-only chains and chains without the resampler, input_format != FMR_IQ_CF32, enable_fourth_down
+   * (add F/4 to the offsets instead), an input_rate that is not a whole number of hertz, |f_s| > (input_rate -
+   * decoder rate) / 2, and stage-A shapes outside the kernel's range (D = 1, D > 24, NA > 400).  fmr_process takes a
+   * bank of one channel only (it returns one audio row).
+   * KNOWN LIMITATION: a bank never takes the fused front end, and the stage B it runs instead at some shapes (the banded
+   * matrix-core k_ifr_poly4 at 10 MS/s FAST) widens a non-finite input sample to its whole tile of IF samples, where a
+   * one-stream chain fed u_s keeps the reference's tap support: around a NaN in the capture a channel's audio can
+   * differ from that chain's (the NaN itself never reaches the audio).  DESIGN.md, "Channel bank". */
+  const int32_t *channel_offset_hz;
 } fmr_config;
 
 /* Per-stream status after the most recent call (getters of FmDecode.h:77-105 /
@@ -169,10 +184,17 @@ enum {
   FMR_FE_POLY = 1 << 12         /* stage B: k_ifr_poly, the generic form */
 };
 
+/* Kernel forms of a channel bank's stage A (fmr_resampler_info which = 8; fmr_config.channel_offset_hz).  Masks 6 and 7
+ * keep their meaning: a bank's stage B is reported in mask 7, and its stage A sets no FMR_FE_* bit. */
+enum {
+  FMR_CB_MODTAP = 1 << 0        /* k_ifr_chan: modulated complex taps over the shared input tile, one rotation per output */
+};
+
 /* Design introspection of the resampler stand-in (DESIGN.md "Resampler
  * specification").  which = 0:D 1:NA 2:LB 3:MB 4:TB 5:LT (rows of the interpolated
  * phase table of the fractional-phase form, 0 = one row per phase); 6 / 7: bitmask of the stage-A / stage-B kernel
- * forms (FMR_FE_*) this chain has launched since create (test introspection); -1 when no resampler. */
+ * forms (FMR_FE_*) this chain has launched since create (test introspection); 8: bitmask of the channel-bank kernel
+ * forms (FMR_CB_*) launched since create (0 for a chain that is no bank); -1 when no resampler. */
 long long fmr_resampler_info(const fmr_chain *c, int which);
 
 /* The product's resampler design on the host (no GPU needed): taps of stage A (stage = 0, NA doubles) or of the
@@ -260,8 +282,8 @@ long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t 
 
 /* Kernel timing with HIP events on the chain's own streams.  enable = 1: every kernel of
  * the most recent call (diagnostics; the extra events cost host time).  enable = 2: only the
- * kernels of the FIR + discriminator stage ("ifr_fused", or "ifr_decim" / "ifr_poly" / "disc", and the IF FIR
- * "fm_block" of an FM chain), one entry per launch accumulated until queried
+ * kernels of the FIR + discriminator stage ("ifr_fused", or "ifr_decim" / "ifr_poly" / "disc", a channel bank's stage A
+ * "ifr_chan", and the IF FIR "fm_block" of an FM chain), one entry per launch accumulated until queried
  * (what bench.py uses inside its timed region); enable = 4: the same on every fourth call only (the two event
  * markers of a stage kernel cost 7-10 us on the decoder stream: bench.py samples); enable = 5: as 4, and the fused front
  * end ("ifr_fused") on EVERY call.  The fused front end is timed with the start / stop events of its own dispatch
