@@ -243,27 +243,37 @@ struct fmr_chain {
   unsigned ft_index = 0;                 // FineTuner::m_index, the same for every tuner of the chain
   double af_ref = 0.6, af_rate = 0.001;  // AfSimpleAgc reference / rate (AmDecode.cpp:54-66)
   int in_fmt = 0, in_bps = 8;          // source sample format (fmr_config.input_format) and its bytes per IQ sample
-  bool poly3 = false;                  // stage-B v3 (Q positions per wave share the LDS reads)
-  bool poly4 = false;                  // stage-B v4 (f32 MFMA, 48/125 shape)
-  bool fir_mfma_fm = false;            // FM with the 127-tap IF filter (-f): k_ifr_poly4<48, 48, 127, 2, Poly4FirDiscEpi> (filter + discriminator + block sums)
+  // ---- front-end kernel forms: init() records what the chain's shape allows, plan_call() picks per call what runs
+  enum class StageA : unsigned char { none, pass, bank, fused, decim16, decim2_16, decim2_24, decim };
+  enum class StageB : unsigned char { none, fused, poly5h_disc, poly5h, poly4_am, poly4, poly3, poly2, poly_frac, poly };
+  // the IF filter: none (FM without it: the block RMS is taken inside the discriminator kernel), the matrix-core form with
+  // the discriminator epilogue (FM -f), k_fm_block3 with / without it, the matrix-core form + k_fir_finish (48 kHz modes),
+  // k_fm_block2, k_fm_block
+  enum class IfForm : unsigned char { none, poly4_disc, block3_disc, block3, poly4_finish, block2, block };
+  enum class FusedFe : unsigned char { none, if_only, disc };
+  struct FeForms {
+    // stage B of a call that takes no upgrade, the first the shape allows of: poly5h (48/125 on the fp16 matrix cores,
+    // three-product split), poly4_am (the 3/8 shape of 384 k -> 48 k as sixteen periods per row block: 48/128), poly4 (f32
+    // MFMA, 48/125/210), poly3 (Q positions per wave share the LDS reads), poly2, poly_frac (fractional phases), poly
+    StageB b = StageB::poly;
+    FusedFe fused = FusedFe::none;   // fused front end (kernels_fused.hpp; 10 MS/s class, FM, cf32, no Fs/4): IF samples only, or
+                                     // with the discriminator as its epilogue (nothing between resampler and discriminator)
+    bool decim16 = false;            // R8B class at 10 MS/s: stage A in the fused front end's matrix-core form (k_ifr_decim16<10, 195>)
+    bool poly5h_disc = false;        // R8B class, FM, nothing between resampler and discriminator: the discriminator is k_ifr_poly5h's epilogue
+    IfForm fir = IfForm::none;       // the IF filter on the matrix cores: poly4_disc (FM -f, k_ifr_poly4<48, 48, 127, 2, Poly4FirDiscEpi>:
+                                     // filter + discriminator + block sums) or poly4_finish (k_ifr_poly4<48, 48, 255 | 127> + k_fir_finish)
+  } fe;
   DevBuf<float> d_afrag_fir_fm;
-  bool fir_mfma = false;               // the 255-tap IF FIR of the 48 kHz modes on the matrix cores (k_ifr_poly4<48, 48, 255> + k_fir_finish)
   DevBuf<float> d_afrag_fir;
-  bool poly4_am = false;               // ... the 3/8 shape (384 k -> 48 k, AM / NBFM) as sixteen periods per row block: 48/128
   int poly4_am_tile = 0;
-  bool poly5h = false;                 // ... on the fp16 matrix cores, three-product split (k_ifr_poly5h): the form that runs
   int poly5h_nkb = 0;
   float poly5h_inv_scale = 1.f;
   size_t poly5h_lds = 0;
   DevBuf<_Float16> d_afrag5h;
   DevBuf<float> d_afrag;               // v4: constant A fragments
   // fused front end (kernels_fused.hpp): stage A + stage B + discriminator in one persistent kernel
-  bool fused_ok = false;               // the chain's shape fits (10 MS/s class, FM, cf32, no Fs/4)
-  bool decim16_ok = false;             // R8B class at 10 MS/s: stage A in the fused front end's matrix-core form (k_ifr_decim16<10, 195>)
   DevBuf<unsigned short> d_dec16_afrag;
-  bool r8b_disc_ok = false;            // R8B class, FM, nothing between resampler and discriminator: the discriminator is k_ifr_poly5h's epilogue
-  DevBuf<float> d_run_ph;              // ... [S][workgroup][2]: phases on either side of the workgroups' run boundaries (k_poly5h_heads)
-  bool fused_disc_ok = false;          // ... and nothing sits between the resampler and the discriminator (no IF FIR, no equaliser)
+  DevBuf<float> d_run_ph;              // R8B / FM -f epilogues [S][workgroup][2]: phases on either side of the workgroups' run boundaries (k_poly5h_heads)
   DevBuf<float> d_hB_last;             // stage-B tap row of position 47
   DevBuf<unsigned short> d_fused_afragA;   // stage-A tap fragments (fp16 high / low terms, both parities)
   DevBuf<unsigned short> d_fused_afragB;   // stage-B tap fragments (fp16 high / low terms) and the inverse of their scale
@@ -278,10 +288,10 @@ struct fmr_chain {
   // trace reads -- and no marker packets on the decoder stream (two markers around a kernel cost 7-10 us of the step and
   // put their own processing time, ~4 us, into the interval).  Set by timed_on for the launch it wraps.
   hipEvent_t ext_a = nullptr, ext_b = nullptr;
-  int n_cu = 256;
+  int n_cu = 256;                      // compute units of the device (read at create)
   DevBuf<float> d_hBp;                 // zero-padded tap rows for v3
   DevBuf<float> d_hpA;                 // stage-A taps in polyphase order [D][Q] (k_ifr_decim2)
-  int qa = 0;                          // taps per phase (even), 0 = v2 kernel not applicable
+  int qa = 0;                          // stage-A taps per phase of k_ifr_decim2 (16 or 24), 0 = that kernel not applicable
   unsigned fe_forms_a = 0, fe_forms_b = 0;   // FMR_FE_* bits of the stage-A / stage-B forms launched since create
   // channel bank (fmr_config.channel_offset_hz): S channels of one input row, stage A in k_ifr_chan (kernels_chanbank.hpp)
   bool bank = false;
@@ -511,8 +521,26 @@ struct fmr_chain {
   int pps_block_base = 0;               // blocks of the call that ran before the part whose PPS events the state holds
   int run_cold_aware(const float2 *d_iq, size_t stride, const uint32_t *block_len, int nb, double *d_aud,
                      size_t astride, uint32_t *audio_len);
+  struct TileRuns {      // a tiled kernel's runs: tiles, workgroups per stream, tiles per run (balanced: the first rem runs one longer)
+    int tiles = 0, grid = 0, tpw = 0, rem = 0;
+    static TileRuns balanced(int tiles, int wgs) { const int g = std::min(wgs, tiles); return {tiles, g, tiles / g, tiles % g}; }
+  };
+  // what one call runs (plan_call): decided before anything is enqueued or any counter moves
+  struct CallPlan {
+    StageA a = StageA::none;
+    StageB b = StageB::none;
+    bool b_disc = false;          // stage B carries the discriminator (fused with it, poly5h_disc): the MPX and the block sums
+    IfForm fir = IfForm::none;
+    int TL = 0;                   // k_fm_block3: tile length (1024 outputs, or the call's longest IF block rounded up to four) ...
+    size_t lds_fb = 0;            // ... and its LDS
+    ResamplerCounter prev, next;  // the IF resampler's counters before and after the call
+    int count_mid = 0;            // stage-A outputs of the call
+    TileRuns fe_runs, fir_runs;   // fused (macro tiles of 384 IF samples) or poly5h_disc (3072), and poly4_disc (3072)
+    bool fir_disc() const { return fir == IfForm::poly4_disc || fir == IfForm::block3_disc; }
+    bool fir_tail() const { return fir == IfForm::poly4_disc; }
+    bool b_in_tables() const { return b == StageB::fused || b == StageB::poly5h_disc; }   // launched from run_tables (it needs the block table)
+  };
   // values one call's stages hand each other (run() fills the head, every stage adds its part)
-  struct FusedGeom { long long mA_prev, kB_prev, n_prev; int count_mid; };
   struct CallCtx {
     const float2 *d_iq = nullptr;
     size_t stride{};
@@ -531,16 +559,8 @@ struct fmr_chain {
     int *t_au_len = nullptr;
     int *t_mpf = nullptr;
     long long N_if{};
-    bool use_fused{};
-    bool fused_disc{};     // the fused kernel's epilogue is the discriminator (else: IF samples only)
-    bool fir_disc{};       // the IF filter kernel's epilogue is the discriminator (k_fm_block3<.., true>)
+    CallPlan plan{};
     bool tail_deferred{};  // the previous call's tail stage is still to be enqueued (behind this call's IF filter kernel)
-    bool fir_tail{};       // FM -f: the IF filter on the matrix cores with the discriminator epilogue (fir_disc is set too; block sums as FusedPart)
-    int fir_grid{}, fir_tpw{}, fir_rem{}, fir_tiles{}, fir_part_from{};
-    bool r8b_tail{};       // R8B class: stage B is launched from run_tables with the discriminator as its epilogue (fused_disc is set too)
-    long long r8b_mA_prev{}, r8b_kB_prev{};
-    int r8b_count_mid{};
-    FusedGeom fused_geom{};
     int par{};
     float2 *ifbuf = nullptr;
     HaloTable ht{};
@@ -556,7 +576,6 @@ struct fmr_chain {
     bool iter_on_side{};
     BlockTab bt{};
     long long if_stride{};
-    bool rms_in_disc{};
     const float2 *xin = nullptr;
     long long x_stride{};
     int x_off{};
@@ -567,7 +586,6 @@ struct fmr_chain {
     bool done = false;                 // the front end found nothing to decode
     hipEvent_t ev_mpx = nullptr;       // recorded where this call's MPX (discriminator output) is complete
     std::function<void()> fe_post{};   // pipelined chain: the front-end stage's end-of-call kernel, when it is still to be launched
-    long long count_mid_call{};        // stage-A outputs of this call
     // this call's slot of the rings the stages hand each other (plain chain: the one buffer of each kind)
     fm_mpx_t *base = nullptr;
     double *raw = nullptr;
@@ -611,10 +629,12 @@ struct fmr_chain {
   int tail_stage(const TailCtx &t, hipStream_t ts);
   int flush_tail(hipEvent_t gate);
   int enqueue_tail(hipEvent_t gate);
+  int plan_call(CallCtx &k);
   int run_front_end(CallCtx &k);
   int launch_chan(hipStream_t st, const float2 *d_iq, long long N_in, long long mA_prev, long long n_prev, int count_mid);
   int finish_front_end_stage(CallCtx &k);
   int run_tables(CallCtx &k);
+  void fill_run_blocks(const CallCtx &k, int *blk0, const TileRuns &r, const int *tile0, long long kb_ref, int tile_len);
   int run_if_stage(CallCtx &k);
   int run_fm(CallCtx &k);
   int run_fm_pll(CallCtx &k, long long base_stride, bool split_mono,
@@ -632,6 +652,37 @@ static int upload(DevBuf<T> &b, const T *src, size_t n) {
   if (rc) return rc;
   if (n) HIPCHK(hipMemcpy(b.p, src, n * sizeof(T), hipMemcpyHostToDevice));
   return FMR_OK;
+}
+
+// k_ifr_decim2, 128 lanes per workgroup (256 -- half the tile-halo over-fetch, twice the LDS per workgroup -- measured no
+// faster in round 2): kDecim2Out outputs per tile, and the padded row length of its LDS tile for qa taps per phase
+constexpr int kDecim2Lanes = 128, kDecim2Out = 2 * kDecim2Lanes;
+static int decim2_pad(int qa) {
+  int s_pad = kDecim2Out + qa;
+  while ((s_pad & 15) != 2) s_pad++;
+  return s_pad;
+}
+
+// A fragments of the banded matrix-core kernel (k_ifr_poly4, shape SH): the row of output position pp = 16 mt + lane % 16
+// over window position m = 4 (ks_lo(mt) + i) + lane / 16 holds tap(pp, m) (0 where the row has no tap)
+template <class SH, class Tap>
+static std::vector<float> poly4_afrag(Tap &&tap) {
+  std::vector<float> af((size_t)SH::MT * SH::NK * 64, 0.f);
+  for (int mt = 0; mt < SH::MT; mt++)
+    for (int i = 0; i < SH::nks(mt); i++)
+      for (int l = 0; l < 64; l++) af[((size_t)mt * SH::NK + i) * 64 + l] = tap(16 * mt + (l & 15), 4 * (SH::ks_lo(mt) + i) + (l >> 4));
+  return af;
+}
+
+// The first block whose partial sums k_stats reads: its walk (kernels.hpp, k_stats) starts at the 64-block group in which
+// it has seen 400 non-empty blocks counting from the end; the blocks before it need none.  The same rule as that walk.
+static int first_part_block(const int *if_len, int nb) {
+  int seen = 0;
+  for (int b0 = ((nb - 1) / 64) * 64; b0 > 0; b0 -= 64) {
+    for (int b = b0; b < std::min(b0 + 64, nb); b++) seen += if_len[b] != 0;
+    if (seen >= 400) return b0;
+  }
+  return 0;
 }
 
 int fmr_chain::init(const fmr_config *c) {
@@ -657,6 +708,8 @@ int fmr_chain::init(const fmr_config *c) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err("no HIP device"); return FMR_ERR_NO_DEVICE; }
   if (c->device < 0 || c->device >= ndev) { set_err("device %d out of range (%d devices)", c->device, ndev); return FMR_ERR_BAD_ARG; }
   HIPCHK(hipSetDevice(c->device));
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
   // The stages of consecutive calls run beside each other for FM chains with the resampler (the default; FMR_PIPELINE=0:
   // one in-order chain per call).  THREE streams ("Three stages in flight"):
   //   stream  the critical chain: front end of call N, PLL of call N, front end of call N+1 ... -- both hold the whole chip
@@ -738,12 +791,20 @@ int fmr_chain::init(const fmr_config *c) {
     if (rs.D >= 2) {
       int q = (rs.NA + rs.D - 1) / rs.D;
       if (q & 1) q++;
-      if (q <= 24) {
-        qa = (q <= 16) ? 16 : 24;          // 24: stage A of the R8B class (195 taps at D = 10), cf32 input only
+      const int qa2 = (q <= 16) ? 16 : 24;     // 24: stage A of the R8B class (195 taps at D = 10), cf32 input only
+      const size_t lds2 = sizeof(float2) * ((size_t)rs.D * decim2_pad(qa2) + 2);   // + the spare slot
+      if (q <= 24 && (qa2 == 16 || in_fmt == 0) && lds2 <= 64000 && (size_t)rs.D * (kDecim2Out + qa2) <= (size_t)16 * kDecim2Out) {
+        qa = qa2;
         std::vector<float> hp((size_t)rs.D * qa, 0.f);
         for (int k = 0; k < rs.NA; k++) hp[(size_t)(k % rs.D) * qa + k / rs.D] = fa[k];
         if ((rc = upload(d_hpA, hp.data(), hp.size()))) return rc;
       }
+    }
+    if (in_fmt != 0 && qa != 16) {
+      // the fused sample conversion lives in the v2 front-end kernel only: refuse the chain now, not on every call
+      set_err("input_format != cf32 needs the FAST resampler class and a source rate with integer pre-decimation >= 2 (%.0f -> %.0f Hz gives D = %d): "
+              "convert on the host or use cf32 input", c->input_rate, dec_rate, rs.D);
+      return FMR_ERR_UNSUPPORTED;
     }
     if (rs.D == 10 && rs.NA == 195 && in_fmt == 0 && !c->enable_fourth_down && !bank && !env.no_fused && !env.serial) {
       bool sym = true;
@@ -756,23 +817,10 @@ int fmr_chain::init(const fmr_config *c) {
         if ((rc = d_zero16.alloc(4))) return rc;
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_decim16<10, 195, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, SH16::LDS_BYTES));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_decim16<10, 195, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, SH16::LDS_BYTES));
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-        decim16_ok = true;
+        fe.decim16 = true;
       }
     }
-    if (in_fmt != 0) {
-      // the fused sample conversion lives in the v2 front-end kernel only: refuse the chain now, not on every call
-      constexpr int BL2 = 128, T2 = 2 * BL2;
-      int s_pad = T2 + 16;
-      while ((s_pad & 15) != 2) s_pad++;
-      const size_t lds2 = sizeof(float2) * ((size_t)rs.D * s_pad + 2);
-      if (!(qa == 16 && lds2 <= 64000 && (size_t)rs.D * (T2 + 16) <= (size_t)2 * 16 * BL2)) {
-        set_err("input_format != cf32 needs the FAST resampler class and a source rate with integer pre-decimation >= 2 (%.0f -> %.0f Hz gives D = %d): "
-                "convert on the host or use cf32 input", c->input_rate, dec_rate, rs.D);
-        return FMR_ERR_UNSUPPORTED;
-      }
-    }
+    fe.b = rs.LT ? StageB::poly_frac : StageB::poly;
     if (!rs.LT) {
       // stage-B v2: 64 periods per tile must fit in LDS, odd MB keeps the lane stride conflict-free
       std::vector<int> phi((size_t)rs.LB), off((size_t)rs.LB);
@@ -780,6 +828,7 @@ int fmr_chain::init(const fmr_config *c) {
       const long long tl = 64 * rs.MB + off[rs.LB - 1] + rs.TB;
       if (tl * 8 <= 98304 && rs.LB <= 4096) {
         poly2_tile = (int)tl;
+        fe.b = StageB::poly2;
         if ((rc = upload(d_bphi, phi.data(), phi.size()))) return rc;
         if ((rc = upload(d_boff, off.data(), off.size()))) return rc;
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly2<512>),
@@ -796,7 +845,7 @@ int fmr_chain::init(const fmr_config *c) {
             for (int j = 0; j < rs.TB; j++) hp[(size_t)r * TBP + FMR_POLY_PADZ + j] = fb[(size_t)r * rs.TB + j];
           if ((rc = upload(d_hBp, hp.data(), hp.size()))) return rc;
           poly2_tile = (int)tl + 64;       // slack: the last 8-sample step may run past the union window
-          poly3 = true;
+          fe.b = StageB::poly3;
           HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly3<384, Q3>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
         }
@@ -832,45 +881,33 @@ int fmr_chain::init(const fmr_config *c) {
               const size_t lds5h = 8 * x_len + 2 * (size_t)KCH * 3 * 2 * 64 * 16;      // (planes + two A chunks; the results are staged over the A buffers)
               if (lds5h <= 160 * 1024 - 64 && (size_t)63 * 125 + 32 * (size_t)nkb <= x_len && x_len <= 48 * 256) {
                 if ((rc = upload(d_afrag5h, ah.data(), ah.size()))) return rc;
-                poly5h = true; poly5h_nkb = nkb; poly5h_inv_scale = std::ldexp(1.0f, -ea); poly5h_lds = lds5h;
+                fe.b = StageB::poly5h; poly5h_nkb = nkb; poly5h_inv_scale = std::ldexp(1.0f, -ea); poly5h_lds = lds5h;
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly5h<48, 125>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5h));
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly5h<48, 125, Poly5hDiscEpi>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5h));
-                r8b_disc_ok = mode == FMR_MODE_FM && in_fmt == 0 && !c->fmfilter_enable && c->multipath_stages == 0 && !env.no_fused;
-                hipDeviceProp_t prop;
-                if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
+                fe.poly5h_disc = mode == FMR_MODE_FM && in_fmt == 0 && !c->fmfilter_enable && c->multipath_stages == 0 && !env.no_fused;
               }
             }
           }
         }
-        if (poly3 && rs.LB == 3 && rs.MB == 8 && rs.TB == 214 && !env.no_fused) {
+        if (fe.b == StageB::poly3 && rs.LB == 3 && rs.MB == 8 && rs.TB == 214 && !env.no_fused) {
           // 384 k -> 48 k (config 3): sixteen periods of 3 outputs / 8 mid samples are one period of 48 / 128 -- output
           // 3 a + b of it starts (8 (3 a + b)) / 3 = 8 a + off[b] samples in and takes phase row phi[b] -- so the banded
           // matrix-core kernel of the 48/125 shape serves it (round 6: k_ifr_poly3 took 0.147 ms per 2.1 M IF samples)
           using SH = Poly4Shape<48, 128, 214>;
-          std::vector<float> af((size_t)SH::MT * SH::NK * 64, 0.f);
-          for (int mt = 0; mt < SH::MT; mt++)
-            for (int i = 0; i < SH::nks(mt); i++)
-              for (int l = 0; l < 64; l++) {
-                const int pp = 16 * mt + (l & 15), m = 4 * (SH::ks_lo(mt) + i) + (l >> 4), j = m - SH::off(pp);
-                if (j >= 0 && j < rs.TB) af[((size_t)mt * SH::NK + i) * 64 + l] = fb[(size_t)phi[pp % 3] * rs.TB + j];
-              }
+          const auto af = poly4_afrag<SH>([&](int pp, int m) {
+            const int j = m - SH::off(pp); return j >= 0 && j < rs.TB ? fb[(size_t)phi[pp % 3] * rs.TB + j] : 0.f; });
           if ((rc = upload(d_afrag, af.data(), af.size()))) return rc;
-          poly4_am = true;
+          fe.b = StageB::poly4_am;
           poly4_am_tile = 64 * 128 + SH::off(47) + rs.TB + 64;
           HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly4<48, 128, 214>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
         }
-        if (poly3 && rs.LB == 48 && rs.MB == 125 && rs.TB == 210) {
+        if (fe.b == StageB::poly3 && rs.LB == 48 && rs.MB == 125 && rs.TB == 210) {
           using SH = Poly4Shape<48, 125, 210>;
-          std::vector<float> af((size_t)SH::MT * SH::NK * 64, 0.f);
-          for (int mt = 0; mt < SH::MT; mt++)
-            for (int i = 0; i < SH::nks(mt); i++)
-              for (int l = 0; l < 64; l++) {
-                const int pp = 16 * mt + (l & 15), m = 4 * (SH::ks_lo(mt) + i) + (l >> 4), j = m - off[pp];
-                if (j >= 0 && j < rs.TB) af[((size_t)mt * SH::NK + i) * 64 + l] = fb[(size_t)phi[pp] * rs.TB + j];
-              }
+          const auto af = poly4_afrag<SH>([&](int pp, int m) {
+            const int j = m - off[pp]; return j >= 0 && j < rs.TB ? fb[(size_t)phi[pp] * rs.TB + j] : 0.f; });
           if ((rc = upload(d_afrag, af.data(), af.size()))) return rc;
-          poly4 = true;
+          fe.b = StageB::poly4;
           HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly4<48, 125, 210>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
           // fused front end: the 10 MS/s shape (D = 10, NA = 103) with a symmetric stage-A filter, FM, cf32 input, no
@@ -889,10 +926,7 @@ int fmr_chain::init(const fmr_config *c) {
             constexpr int kL = FusedShape<kFusedD, kFusedNA>::LDS_BYTES;
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_fused<kFusedD, kFusedNA, 0, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, kL));
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_fused<kFusedD, kFusedNA, 1, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, kL));
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-            fused_ok = true;
-            fused_disc_ok = !c->fmfilter_enable && c->multipath_stages == 0;
+            fe.fused = (!c->fmfilter_enable && c->multipath_stages == 0) ? FusedFe::disc : FusedFe::if_only;
           }
         }
       }
@@ -961,18 +995,10 @@ int fmr_chain::init(const fmr_config *c) {
     // FM -f: lags 1 .. 126 as the 48 / 48 shape of the banded matrix-core kernel (see the 48 kHz modes below), lag 0 and the
     // discriminator in its epilogue (Poly4FirDiscEpi)
     using SH = Poly4Shape<48, 48, 127>;
-    std::vector<float> af((size_t)SH::MT * SH::NK * 64, 0.f);
-    for (int mt = 0; mt < SH::MT; mt++)
-      for (int i = 0; i < SH::nks(mt); i++)
-        for (int l = 0; l < 64; l++) {
-          const int pp = 16 * mt + (l & 15), m = 4 * (SH::ks_lo(mt) + i) + (l >> 4), j = m - SH::off(pp);
-          if (j >= 0 && j < 126) af[((size_t)mt * SH::NK + i) * 64 + l] = filter_src[126 - j];
-        }
+    const auto af = poly4_afrag<SH>([&](int pp, int m) { const int j = m - SH::off(pp); return j >= 0 && j < 126 ? filter_src[126 - j] : 0.f; });
     if ((rc = upload(d_afrag_fir_fm, af.data(), af.size()))) return rc;
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly4<48, 48, 127, 2, Poly4FirDiscEpi>), hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-    fir_mfma_fm = true;
+    fe.fir = IfForm::poly4_disc;
   }
   if (fir_enable && mode != FMR_MODE_FM && !ssb_like && (ntaps == 255 || ntaps == 127) && !env.no_fused && !env.serial) {
     // AM / DSB / NBFM (255 or 127 taps): out[i] = sum_{j = 1 .. order} c[j] x[i - j] as the 1 : 1 "polyphase" shape 48 / 48 of the
@@ -982,13 +1008,7 @@ int fmr_chain::init(const fmr_config *c) {
     auto make = [&](auto sh_tag) {
       using SH = decltype(sh_tag);
       const int order = ntaps - 1;
-      std::vector<float> af((size_t)SH::MT * SH::NK * 64, 0.f);
-      for (int mt = 0; mt < SH::MT; mt++)
-        for (int i = 0; i < SH::nks(mt); i++)
-          for (int l = 0; l < 64; l++) {
-            const int pp = 16 * mt + (l & 15), m = 4 * (SH::ks_lo(mt) + i) + (l >> 4), j = m - SH::off(pp);
-            if (j >= 0 && j < order) af[((size_t)mt * SH::NK + i) * 64 + l] = filter_src[order - j];
-          }
+      const auto af = poly4_afrag<SH>([&](int pp, int m) { const int j = m - SH::off(pp); return j >= 0 && j < order ? filter_src[order - j] : 0.f; });
       return upload(d_afrag_fir, af.data(), af.size());
     };
     if (ntaps == 255) {
@@ -998,15 +1018,16 @@ int fmr_chain::init(const fmr_config *c) {
       if ((rc = make(Poly4Shape<48, 48, 127>{}))) return rc;
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly4<48, 48, 127, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
     }
-    fir_mfma = true;
+    fe.fir = IfForm::poly4_finish;
   }
   if ((rc = d_gain.alloc((size_t)S * max_if))) return rc;
   if ((rc = d_dec.alloc((size_t)S * max_if))) return rc;
-  if ((fused_ok || r8b_disc_ok || fir_mfma_fm) && (rc = d_fused_part.alloc((size_t)S * 3 * (max_if / 384 + 20)))) return rc;
-  if ((r8b_disc_ok || fir_mfma_fm) && (rc = d_run_ph.alloc((size_t)S * 2 * kMaxFusedWg))) return rc;
-  if (fused_ok && (rc = d_fused_mid32.alloc((size_t)std::max(std::max(n_cu, S), 256) * 2 * FusedShape<kFusedD, kFusedNA>::MIDR))) return rc;
-  if (fused_ok && (rc = d_zero16.alloc(4))) return rc;
-  if (fused_ok && env.fe_stamps && (rc = d_fe_stamps.alloc(3 * (size_t)kMaxFusedWg * S + 2 * kStampCalls * 16))) return rc;
+  const bool fused = fe.fused != FusedFe::none, tiled_epi = fe.poly5h_disc || fe.fir == IfForm::poly4_disc;   // (the epilogues that leave block sums)
+  if ((fused || tiled_epi) && (rc = d_fused_part.alloc((size_t)S * 3 * (max_if / 384 + 20)))) return rc;
+  if (tiled_epi && (rc = d_run_ph.alloc((size_t)S * 2 * kMaxFusedWg))) return rc;
+  if (fused && (rc = d_fused_mid32.alloc((size_t)std::max(std::max(n_cu, S), 256) * 2 * FusedShape<kFusedD, kFusedNA>::MIDR))) return rc;
+  if (fused && (rc = d_zero16.alloc(4))) return rc;
+  if (fused && env.fe_stamps && (rc = d_fe_stamps.alloc(3 * (size_t)kMaxFusedWg * S + 2 * kStampCalls * 16))) return rc;
   if ((rc = d_if_rms_blk.alloc((size_t)S * max_blocks))) return rc;
   if ((rc = d_bb_mean_blk.alloc((size_t)S * max_blocks))) return rc;
   if ((rc = d_bb_rms_blk.alloc((size_t)S * max_blocks))) return rc;
@@ -1086,7 +1107,7 @@ int fmr_chain::init(const fmr_config *c) {
       for (int q = 1; q < kPipe; q++) {
         if ((rc = d_base_pp[q].alloc((size_t)S * (H_b + max_if)))) return rc;
         if ((rc = d_raw_pp[q].alloc((size_t)S * (H_b + max_if)))) return rc;
-        if ((fused_ok || r8b_disc_ok || fir_mfma_fm) && (rc = d_part_pp[q].alloc(d_fused_part.n))) return rc;
+        if ((fused || tiled_epi) && (rc = d_part_pp[q].alloc(d_fused_part.n))) return rc;
         if ((rc = d_stereo_pp[q].alloc((size_t)S * max_blocks))) return rc;
       }
     if ((rc = d_base_de.alloc((size_t)S * (H_a + max_if)))) return rc;
@@ -1389,30 +1410,113 @@ int fmr_chain::run(const float2 *d_iq, size_t stride, const uint32_t *block_len,
   return FMR_OK;
 }
 
+// the FMR_FE_* bit of every form, in the order of StageA / StageB (a bank's stage A sets none: FMR_CB_*)
+static constexpr unsigned kFeBitA[] = {0, 0, 0, FMR_FE_FUSED, FMR_FE_DECIM16, FMR_FE_DECIM2_16, FMR_FE_DECIM2_24, FMR_FE_DECIM};
+static constexpr unsigned kFeBitB[] = {0, FMR_FE_FUSED, FMR_FE_POLY5H_DISC, FMR_FE_POLY5H, FMR_FE_POLY4_AM, FMR_FE_POLY4,
+                                       FMR_FE_POLY3, FMR_FE_POLY2, FMR_FE_POLY_FRAC, FMR_FE_POLY};
+
+// The kernel forms of one call, from its IF block lengths, the input's alignment and the forms init() allowed.  Fills the
+// IF block table and nothing else: a call refused here leaves the chain as it found it.
+int fmr_chain::plan_call(CallCtx &k) {
+  CallPlan &p = k.plan;
+  p = CallPlan{};
+  p.prev = p.next = rsc;
+  k.N_if = 0;
+  bool short_blk = false;      // a non-empty IF block shorter than 128 samples: the tiled forms' epilogues take none
+  int tl = 4;
+  for (int b = 0; b < k.nb; b++) {
+    const int n = has_rs ? (int)p.next.advance(rs, k.block_len[b]) : (int)k.block_len[b];
+    k.t_if_off[b] = (int)k.N_if;
+    k.t_if_len[b] = n;
+    k.N_if += n;
+    short_blk |= n != 0 && n < 128;
+    tl = std::max(tl, (n + 3) & ~3);
+  }
+  const long long N_if = k.N_if;
+  p.count_mid = (int)(p.next.mA - p.prev.mA);
+  const bool tiled = has_dec && !serial_mode && !short_blk;
+  // Pipelined chain: the front end leaves one CU of every XCD free.  A workgroup is dispatched inside the XCD its index
+  // maps to, and the kernels that run beside the front end -- lock logic (32 KB of LDS), the DC block's node pass (213
+  // VGPRs), the spare PLL rounds -- do not fit beside a 152 KB workgroup: on an XCD the front end fills they wait for
+  // it to end (measured: the lock logic 250 instead of 55 us, and the next PLL pass behind it).
+  const int fe_cus = pipelined ? std::max(8, n_cu - kFeSpareCus) : n_cu;
+  if (!has_rs) {
+    p.a = StageA::pass;
+  } else {
+    if ((size_t)p.count_mid > max_mid || (size_t)N_if > max_if) { set_err("internal capacity exceeded"); return FMR_ERR_CAPACITY; }
+    const bool aligned = ((uintptr_t)k.d_iq % 16) == 0 && (k.stride % 2) == 0;
+    if (fe.fused != FusedFe::none && tiled && N_if >= 4 * 384 && p.count_mid >= H_mid && aligned) {
+      // Fused front end (stage A + stage B + discriminator in one persistent kernel) when this call is long enough and
+      // its blocks are not tiny; any other call takes the three-kernel path -- both keep the same carried state.
+      p.a = StageA::fused;
+      p.b = StageB::fused;
+      p.b_disc = fe.fused == FusedFe::disc;
+      const long long P_first = p.prev.kB / 48, P_last = (p.prev.kB + N_if - 1) / 48;
+      TileRuns &r = p.fe_runs;
+      r.tiles = (int)(P_last / 8 - P_first / 8 + 1);
+      const int cus = (pipelined && env.fe_cus > 0) ? std::min(env.fe_cus, n_cu) : fe_cus;
+      const int wg_per_stream = std::max(1, std::min(kFusedTile0Off - 1, cus / S));
+      // (ceil(n / grid) macro tiles for all but the last workgroup.  Balanced runs -- n mod grid workgroups with one tile more --
+      // were measured in round 6: 248 instead of 245 workgroups at 2^27 samples, and the launch 5 us LONGER in the chain: the
+      // three compute units more that the uneven split leaves free serve the kernels beside it)
+      r.tpw = (r.tiles + wg_per_stream - 1) / wg_per_stream;
+      r.grid = (r.tiles + r.tpw - 1) / r.tpw;
+      if ((size_t)r.tiles * 3 * S > d_fused_part.n) { set_err("internal capacity exceeded (fused tiles)"); return FMR_ERR_CAPACITY; }
+      if ((size_t)r.grid * S * 2 * FusedShape<kFusedD, kFusedNA>::MIDR > d_fused_mid32.n) { set_err("internal capacity exceeded (fused workgroups)"); return FMR_ERR_CAPACITY; }
+    } else {
+      if (p.count_mid > 0)
+        p.a = bank ? StageA::bank
+            : (fe.decim16 && p.count_mid >= 4 * 500 && aligned) ? StageA::decim16
+            : qa == 24 ? StageA::decim2_24 : qa == 16 ? StageA::decim2_16 : StageA::decim;
+      if (p.a == StageA::decim && in_fmt != 0) { set_err("input_format != cf32 needs the v2 front-end kernel (decimation ratio out of its range)"); return FMR_ERR_UNSUPPORTED; }
+      if (fe.poly5h_disc && tiled && N_if >= 3072 && p.count_mid > 0) {
+        // R8B class: the dense stage B carries the discriminator epilogue (it needs the block table: launched from
+        // run_tables), in contiguous runs of stage-B tiles (64 periods = 3072 IF samples) per workgroup.  Balanced runs: ceil(tiles / workgroups) for everybody left 16 of 256 compute units
+        // idle at 2^27 samples per call and put seven tiles WITH partial sums on the workgroups that end the launch.
+        p.b = StageB::poly5h_disc;
+        p.b_disc = true;
+        const long long P_first = p.prev.kB / 48, P_last = (p.prev.kB + N_if - 1) / 48;
+        p.fe_runs = TileRuns::balanced((int)((P_last - P_first) / 64 + 1), std::max(1, std::min(kFusedTile0Off - 1, fe_cus / S)));
+        if ((size_t)8 * p.fe_runs.tiles * 3 * S > d_fused_part.n || (size_t)p.fe_runs.grid * 2 * S > d_run_ph.n) { set_err("internal capacity exceeded (stage-B tiles)"); return FMR_ERR_CAPACITY; }
+      } else if (N_if > 0) {
+        p.b = fe.b;
+      }
+    }
+  }
+  if (has_dec && !(mode == FMR_MODE_FM && !fir_enable && !serial_mode)) {
+    // (FM without the IF FIR: the block RMS is taken inside the discriminator kernel, IfForm::none)
+    p.TL = std::min(1024, tl);
+    p.lds_fb = sizeof(float2) * (4 * (size_t)fm_block3_plane(ntaps - 1, p.TL) + ((size_t)ntaps + 4) / 2 + (size_t)(ntaps - 1) + p.TL);
+    const bool blocked = fir_enable && ntaps >= 2 && p.lds_fb <= 60000 && !serial_mode;
+    if (blocked && mode == FMR_MODE_FM && !enable_mpf)
+      p.fir = (fe.fir == IfForm::poly4_disc && tiled && N_if >= 3072) ? IfForm::poly4_disc : IfForm::block3_disc;
+    else if (blocked && mode == FMR_MODE_FM) p.fir = IfForm::block3;
+    else if (blocked && fe.fir == IfForm::poly4_finish && N_if >= 48) p.fir = IfForm::poly4_finish;
+    else p.fir = blocked ? IfForm::block2 : IfForm::block;
+  }
+  if (p.fir == IfForm::poly4_disc) {
+    // FM -f on the matrix cores: contiguous runs of 3072-output tiles per workgroup (call-relative).  Two workgroups share a
+    // compute unit: balanced runs keep all of them busy, where ceil(tiles / slots) for everybody left 46 of 256 units idle at
+    // 2^27 samples per call.
+    p.fir_runs = TileRuns::balanced((int)((N_if - 1) / 3072 + 1), std::max(1, std::min(kMaxFusedWg - kFirBlk0Off, 2 * n_cu / S)));
+    if ((size_t)8 * p.fir_runs.tiles * 3 * S > d_fused_part.n || (size_t)p.fir_runs.grid * 2 * S > d_run_ph.n) { set_err("internal capacity exceeded (IF filter tiles)"); return FMR_ERR_CAPACITY; }
+  }
+  return FMR_OK;
+}
+
 // IfResampler (or the pass-through copy): input -> IF buffer, input history, first halo entries
 int fmr_chain::run_front_end(CallCtx &k) {
-  auto &d_iq = k.d_iq; auto &stride = k.stride; auto &block_len = k.block_len; auto &nb = k.nb;
-  auto &audio_len = k.audio_len; auto &N_in = k.N_in; auto &t_if_off = k.t_if_off;
-  auto &t_if_len = k.t_if_len; auto &N_if = k.N_if; auto &use_fused = k.use_fused; auto &fused_geom = k.fused_geom;
-  auto &par = k.par; auto &ifbuf = k.ifbuf; auto &ht = k.ht;
-  auto add_halo = [&](void *buf, long long stride_e, int H, long long N, int words = 2) { k.add_halo(buf, stride_e, H, N, words); };
-  // ------------------------------------------------------------------ front end
-  long long count_mid_call = 0;
-  N_if = 0;
-  use_fused = false;
+  if (int rc = plan_call(k)) return rc;
+  const CallPlan &p = k.plan;
+  const long long N_if = k.N_if, N_in = k.N_in, mA_prev = p.prev.mA, kB_prev = p.prev.kB;
+  const int count_mid = p.count_mid;
+  fe_forms_a |= kFeBitA[(int)p.a];
+  fe_forms_b |= kFeBitB[(int)p.b];
   fe_spare_cus = 0;
-  k.fused_disc = false;
-  fused_geom = FusedGeom{};
   hipStream_t fes = stream;      // (pipelined chain too: the front end alternates with the PLL stage on the decoder stream)
-  par = 0;
+  k.par = 0;
   if (has_rs) {
-    const long long mA_prev = rsc.mA, kB_prev = rsc.kB, n_prev = rsc.n_in;
-    for (int b = 0; b < nb; b++) {
-      t_if_off[b] = (int)N_if;
-      const long long k = rsc.advance(rs, block_len[b]);
-      t_if_len[b] = (int)k;
-      N_if += k;
-    }
+    rsc = p.next;
     // Cross-call pipelining: this call's front end (its own stream, its own slot of the IF / MPX / partial-sum ring) runs
     // beside the PLL stage of the call before it and the audio tail of the call before that.  The slot was last read by the
     // tail of the call kPipe calls ago: the host polls a counter that a one-thread kernel at the end of every tail writes
@@ -1421,218 +1525,172 @@ int fmr_chain::run_front_end(CallCtx &k) {
     // decodes nothing and takes no slot.
     if (pipelined && N_if > 0) {
       pipe_seq++;
-      par = (int)(pipe_seq % kPipe);
+      k.par = (int)(pipe_seq % kPipe);
       // (one slot less than the ring holds: the slot of call N is still read at the head of call N+1, by the kernel that
       // carries its halos over, and that kernel is only ordered before the tail of call N+1)
       if (int rcw = wait_mark(&h_marks[1], pipe_seq > (unsigned long long)(kPipe - 1) ? pipe_seq - (kPipe - 1) : 0)) return rcw;
     }
-    ifbuf = if_slot(par);
-    last_if = ifbuf;
-    const int count_mid = (int)(rsc.mA - mA_prev);
-    count_mid_call = count_mid;
-    if ((size_t)count_mid > max_mid || (size_t)N_if > max_if) { set_err("internal capacity exceeded"); return FMR_ERR_CAPACITY; }
-    // Fused front end (stage A + stage B + discriminator in one persistent kernel) when this call is long enough and
-    // its blocks are not tiny; any other call takes the three-kernel path -- both keep the same carried state.
-    if (fused_ok && has_dec && !serial_mode && N_if >= 4 * 384 && count_mid >= H_mid &&
-        ((uintptr_t)d_iq % 16) == 0 && (stride % 2) == 0) {
-      use_fused = true;
-      for (int b = 0; b < nb; b++) if (t_if_len[b] != 0 && t_if_len[b] < 128) use_fused = false;
-    }
-    k.fused_disc = use_fused && fused_disc_ok;
-    // R8B class: the dense stage B carries the discriminator epilogue (it needs the block table: launched from run_tables)
-    k.r8b_tail = false;
-    if (!use_fused && r8b_disc_ok && poly5h && has_dec && !serial_mode && N_if >= 3072 && count_mid > 0) {
-      k.r8b_tail = true;
-      for (int b = 0; b < nb; b++) if (t_if_len[b] != 0 && t_if_len[b] < 128) k.r8b_tail = false;
-    }
-    if (k.r8b_tail) { k.fused_disc = true; k.r8b_mA_prev = mA_prev; k.r8b_kB_prev = kB_prev; k.r8b_count_mid = count_mid; }
-    dec_valid = !k.fused_disc || debug_taps;   // the float copy of the discriminator output is a debug tap of the fused kernel
-    if_valid = dec_valid;                      // ... and so are the IF samples behind its discriminator epilogue (the slot holds |x|^2 then)
-    if (use_fused) {
-      fused_geom = {mA_prev, kB_prev, n_prev, count_mid};
-    } else if (count_mid > 0 && bank) {
-      if (int rc = launch_chan(fes, d_iq, N_in, mA_prev, n_prev, count_mid)) return rc;
-    } else if (count_mid > 0) {
-      const long long top0 = (long long)rs.D * mA_prev + rs.ca() - n_prev;
+    k.ifbuf = if_slot(k.par);
+    last_if = k.ifbuf;
+    dec_valid = !p.b_disc || debug_taps;   // the float copy of the discriminator output is a debug tap of the fused kernel
+    if_valid = dec_valid;                  // ... and so are the IF samples behind its discriminator epilogue (the slot holds |x|^2 then)
+    const long long top0 = (long long)rs.D * mA_prev + rs.ca() - p.prev.n_in;
+    if (p.a == StageA::bank) {
+      if (int rc = launch_chan(fes, k.d_iq, N_in, mA_prev, p.prev.n_in, count_mid)) return rc;
+    } else if (p.a == StageA::decim16) {
+      // R8B class, 10 MS/s: the matrix-core form behind the fused front end's input ring, a contiguous run of 500-output epochs
+      // per workgroup (calls of a few epochs per compute unit and up)
+      using SH16 = Decim16Shape<10, 195>;
+      FusedArgs a{};
+      a.iq = k.d_iq; a.iq_stride = (long long)k.stride; a.n_valid = N_in;
+      a.in_halo = d_in_halo.p; a.H_in = H_in; a.afragA = reinterpret_cast<const uint4 *>(d_dec16_afrag.p); a.hA = d_hA.p;
+      a.zero16 = reinterpret_cast<const float2 *>(d_zero16.p);
+      const long long lo0 = top0 - (rs.NA - 1);
+      const int par16 = (int)(((lo0 % 2) + 2) % 2);
+      a.nbase = lo0 - par16;
+      a.count_mid = count_mid;
+      a.mid = d_mid.p; a.mid_stride = (long long)(H_mid + max_mid); a.H_mid = H_mid;
+      a.n_tiles = (count_mid + SH16::ME - 1) / SH16::ME;
+      const int fe_cus = pipelined ? std::max(8, n_cu - kFeSpareCus) : n_cu;
+      const int wgs = std::max(1, fe_cus / S);
+      a.tiles_per_wg = (a.n_tiles + wgs - 1) / wgs;
+      const int grid16 = (a.n_tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
+      timed_on(fes, "ifr_decim", [&] {
+        if (par16) hipLaunchKernelGGL((k_ifr_decim16<10, 195, 1>), dim3(grid16, S), dim3(DECIM16_THREADS), SH16::LDS_BYTES, fes, a);
+        else hipLaunchKernelGGL((k_ifr_decim16<10, 195, 0>), dim3(grid16, S), dim3(DECIM16_THREADS), SH16::LDS_BYTES, fes, a);
+      });
+    } else if (p.a == StageA::decim2_16 || p.a == StageA::decim2_24) {
+      const int s_pad = decim2_pad(qa);
+      const size_t lds2 = sizeof(float2) * ((size_t)rs.D * s_pad + 2);   // + the spare slot
+      const unsigned magic = (unsigned)((1u << 24) / (unsigned)rs.D + 1);
+      const dim3 grid2((count_mid + kDecim2Out - 1) / kDecim2Out, S);
+      timed_on(fes, "ifr_decim", [&] {
+        auto go = [&](auto kern) {
+          hipLaunchKernelGGL(kern, grid2, dim3(kDecim2Lanes), lds2, fes, k.d_iq, (long long)k.stride, N_in, d_in_halo.p, H_in,
+                             d_hpA.p, rs.D, rs.ca(), top0 - rs.ca(), count_mid, d_mid.p,
+                             (long long)(H_mid + max_mid), H_mid, (unsigned)(abs_in & 3u),
+                             (int)cfg.enable_fourth_down, s_pad, magic);
+        };
+        constexpr int BL2 = kDecim2Lanes;
+        const bool f4 = cfg.enable_fourth_down != 0;
+        if (qa == 24) { f4 ? go(k_ifr_decim2<BL2, 24, 0, true>) : go(k_ifr_decim2<BL2, 24, 0, false>); return; }
+        switch (in_fmt) {
+        case 1: f4 ? go(k_ifr_decim2<BL2, 16, 0, true, 1, 1>) : go(k_ifr_decim2<BL2, 16, 0, false, 1, 1>); break;
+        case 2: f4 ? go(k_ifr_decim2<BL2, 16, 0, true, 1, 2>) : go(k_ifr_decim2<BL2, 16, 0, false, 1, 2>); break;
+        case 3: f4 ? go(k_ifr_decim2<BL2, 16, 0, true, 1, 3>) : go(k_ifr_decim2<BL2, 16, 0, false, 1, 3>); break;
+        default: f4 ? go(k_ifr_decim2<BL2, 16, 0, true>) : go(k_ifr_decim2<BL2, 16, 0, false>); break;
+        }
+      });
+    } else if (p.a == StageA::decim) {
       auto launch_decim = [&](auto bl_tag) {
         constexpr int BL = decltype(bl_tag)::value;
         const dim3 grid((count_mid + BL - 1) / BL, S);
         const size_t lds = sizeof(float2) * ((size_t)BL * rs.D + rs.NA - 1);
-        fe_forms_a |= FMR_FE_DECIM;
-        hipLaunchKernelGGL(k_ifr_decim<BL>, grid, dim3(BL), lds, fes, d_iq, (long long)stride, N_in,
+        hipLaunchKernelGGL(k_ifr_decim<BL>, grid, dim3(BL), lds, fes, k.d_iq, (long long)k.stride, N_in,
                            d_in_halo.p, H_in, d_hA.p, rs.NA, rs.D, top0, count_mid, d_mid.p,
                            (long long)(H_mid + max_mid), H_mid, (unsigned)(abs_in & 3u), cfg.enable_fourth_down);
       };
       const size_t per_out = sizeof(float2) * (size_t)rs.D, tail = sizeof(float2) * (size_t)(rs.NA - 1);
-      // v2 kernel, 128 lanes per workgroup (256 -- half the tile-halo over-fetch, twice the LDS per workgroup -- measured
-      // no faster in round 2)
-      bool v2_done = false;
-      auto launch_decim2 = [&](auto bl_tag) {
-        constexpr int BL2 = decltype(bl_tag)::value, T2 = 2 * BL2;
-        int s_pad = T2 + qa;
-        while ((s_pad & 15) != 2) s_pad++;
-        const size_t lds2 = sizeof(float2) * ((size_t)rs.D * s_pad + 2);   // + the spare slot
-        if (!((qa == 16 || (qa == 24 && in_fmt == 0)) && lds2 <= 64000 && (size_t)rs.D * (T2 + qa) <= (size_t)2 * 16 * BL2)) return;
-        const unsigned magic = (unsigned)((1u << 24) / (unsigned)rs.D + 1);
-        const dim3 grid2((count_mid + T2 - 1) / T2, S);
-        fe_forms_a |= qa == 24 ? FMR_FE_DECIM2_24 : FMR_FE_DECIM2_16;
-        timed_on(fes, "ifr_decim", [&] {
-          auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, grid2, dim3(BL2), lds2, fes, d_iq, (long long)stride, N_in, d_in_halo.p, H_in,
-                               d_hpA.p, rs.D, rs.ca(), top0 - rs.ca(), count_mid, d_mid.p,
-                               (long long)(H_mid + max_mid), H_mid, (unsigned)(abs_in & 3u),
-                               (int)cfg.enable_fourth_down, s_pad, magic);
-          };
-          const bool f4 = cfg.enable_fourth_down != 0;
-          if (qa == 24) { f4 ? go(k_ifr_decim2<BL2, 24, 0, true>) : go(k_ifr_decim2<BL2, 24, 0, false>); return; }
-          switch (in_fmt) {
-          case 1: f4 ? go(k_ifr_decim2<BL2, 16, 0, true, 1, 1>) : go(k_ifr_decim2<BL2, 16, 0, false, 1, 1>); break;
-          case 2: f4 ? go(k_ifr_decim2<BL2, 16, 0, true, 1, 2>) : go(k_ifr_decim2<BL2, 16, 0, false, 1, 2>); break;
-          case 3: f4 ? go(k_ifr_decim2<BL2, 16, 0, true, 1, 3>) : go(k_ifr_decim2<BL2, 16, 0, false, 1, 3>); break;
-          default: f4 ? go(k_ifr_decim2<BL2, 16, 0, true>) : go(k_ifr_decim2<BL2, 16, 0, false>); break;
-          }
-        });
-        v2_done = true;
-      };
-      // R8B class, 10 MS/s: the matrix-core form behind the fused front end's input ring, a contiguous run of 500-output epochs
-      // per workgroup (calls of a few epochs per compute unit and up)
-      if (decim16_ok && count_mid >= 4 * 500 && ((uintptr_t)d_iq % 16) == 0 && (stride % 2) == 0) {
-        using SH16 = Decim16Shape<10, 195>;
-        FusedArgs a{};
-        a.iq = d_iq; a.iq_stride = (long long)stride; a.n_valid = N_in;
-        a.in_halo = d_in_halo.p; a.H_in = H_in; a.afragA = reinterpret_cast<const uint4 *>(d_dec16_afrag.p); a.hA = d_hA.p;
-        a.zero16 = reinterpret_cast<const float2 *>(d_zero16.p);
-        const long long lo0 = top0 - (rs.NA - 1);
-        const int par16 = (int)(((lo0 % 2) + 2) % 2);
-        a.nbase = lo0 - par16;
-        a.count_mid = count_mid;
-        a.mid = d_mid.p; a.mid_stride = (long long)(H_mid + max_mid); a.H_mid = H_mid;
-        a.n_tiles = (count_mid + SH16::ME - 1) / SH16::ME;
-        const int fe_cus = pipelined ? std::max(8, n_cu - kFeSpareCus) : n_cu;
-        const int wgs = std::max(1, fe_cus / S);
-        a.tiles_per_wg = (a.n_tiles + wgs - 1) / wgs;
-        const int grid16 = (a.n_tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
-        fe_forms_a |= FMR_FE_DECIM16;
-        timed_on(fes, "ifr_decim", [&] {
-          if (par16) hipLaunchKernelGGL((k_ifr_decim16<10, 195, 1>), dim3(grid16, S), dim3(DECIM16_THREADS), SH16::LDS_BYTES, fes, a);
-          else hipLaunchKernelGGL((k_ifr_decim16<10, 195, 0>), dim3(grid16, S), dim3(DECIM16_THREADS), SH16::LDS_BYTES, fes, a);
-        });
-        v2_done = true;
-      } else
-      launch_decim2(std::integral_constant<int, 128>{});
-      if (v2_done) {
-      } else if (in_fmt != 0) {
-        set_err("input_format != cf32 needs the v2 front-end kernel (decimation ratio out of its range)");
-        return FMR_ERR_UNSUPPORTED;
-      } else {
-        timed_on(fes, "ifr_decim", [&] {
-          if (256 * per_out + tail <= 60000) launch_decim(std::integral_constant<int, 256>{});
-          else if (128 * per_out + tail <= 60000) launch_decim(std::integral_constant<int, 128>{});
-          else launch_decim(std::integral_constant<int, 64>{});
-        });
-      }
-    }
-    if (use_fused || k.r8b_tail) {
-    } else if (N_if > 0 && poly2_tile > 0) {
-      const long long P_first = kB_prev / rs.LB, P_last = (kB_prev + N_if - 1) / rs.LB;
-      const int tiles = (int)((P_last - P_first) / 64 + 1);
-      fe_forms_b |= poly5h ? FMR_FE_POLY5H : poly4_am ? FMR_FE_POLY4_AM : poly4 ? FMR_FE_POLY4 : poly3 ? FMR_FE_POLY3 : FMR_FE_POLY2;
+      timed_on(fes, "ifr_decim", [&] {
+        if (256 * per_out + tail <= 60000) launch_decim(std::integral_constant<int, 256>{});
+        else if (128 * per_out + tail <= 60000) launch_decim(std::integral_constant<int, 128>{});
+        else launch_decim(std::integral_constant<int, 64>{});
+      });
+    }     // (fused: launched from run_tables)
+    float2 *const ifbuf = k.ifbuf;
+    const long long mid_stride = H_mid + max_mid, if_stride = H_if + max_if;
+    if (p.b != StageB::none && !p.b_in_tables())
       timed_on(fes, "ifr_poly", [&] {
-        if (poly5h)
+        // the tiled forms: tiles of 64 stage-B periods; the generic forms: 256 outputs per workgroup
+        const long long P_first = kB_prev / rs.LB, P_last = (kB_prev + N_if - 1) / rs.LB;
+        const int tiles = (int)((P_last - P_first) / 64 + 1);
+        constexpr int BL = 256;
+        const dim3 grid((unsigned)((N_if + BL - 1) / BL), S);
+        const int span = (int)(((unsigned long long)(BL - 1) * rs.MB) / rs.LB) + rs.TB + 2;
+        if (p.b == StageB::poly5h)
           hipLaunchKernelGGL((k_ifr_poly5h<48, 125>), dim3(std::min(tiles, n_cu), S), dim3(64 * FMR_POLY5H_WAVES), poly5h_lds,
-                             fes, d_mid.p, (long long)(H_mid + max_mid), mA_prev - H_mid, H_mid + count_mid, d_afrag5h.p,
-                             poly5h_nkb, poly5h_inv_scale, rs.TB, kB_prev, (int)N_if, ifbuf, (long long)(H_if + max_if), H_if,
+                             fes, d_mid.p, mid_stride, mA_prev - H_mid, H_mid + count_mid, d_afrag5h.p,
+                             poly5h_nkb, poly5h_inv_scale, rs.TB, kB_prev, (int)N_if, ifbuf, if_stride, H_if,
                              poly2_tile, tiles);
-        else if (poly4_am) {
+        else if (p.b == StageB::poly4_am) {
           const long long Pf = kB_prev / 48, Pl = (kB_prev + N_if - 1) / 48;
           const int tiles_am = (int)((Pl - Pf) / 64 + 1);
           hipLaunchKernelGGL((k_ifr_poly4<48, 128, 214>), dim3(std::min(tiles_am, 512), S), dim3(256),
                              sizeof(float2) * (size_t)(((poly4_am_tile + 127) / 128) * 128 + 4 * 8 * 48), fes, d_mid.p,
-                             (long long)(H_mid + max_mid), mA_prev - H_mid, H_mid + count_mid, d_afrag.p, kB_prev,
-                             (int)N_if, ifbuf, (long long)(H_if + max_if), H_if, poly4_am_tile, tiles_am);
-        } else if (poly4)
+                             mid_stride, mA_prev - H_mid, H_mid + count_mid, d_afrag.p, kB_prev,
+                             (int)N_if, ifbuf, if_stride, H_if, poly4_am_tile, tiles_am);
+        } else if (p.b == StageB::poly4)
           hipLaunchKernelGGL((k_ifr_poly4<48, 125, 210>), dim3(std::min(tiles, 512), S), dim3(256),
                              sizeof(float2) * (size_t)(((poly2_tile + 127) / 128) * 128 + 4 * 8 * 48), fes, d_mid.p,
-                             (long long)(H_mid + max_mid), mA_prev - H_mid, H_mid + count_mid, d_afrag.p, kB_prev,
-                             (int)N_if, ifbuf, (long long)(H_if + max_if), H_if, poly2_tile, tiles);
-        else if (poly3)
+                             mid_stride, mA_prev - H_mid, H_mid + count_mid, d_afrag.p, kB_prev,
+                             (int)N_if, ifbuf, if_stride, H_if, poly2_tile, tiles);
+        else if (p.b == StageB::poly3)
           hipLaunchKernelGGL((k_ifr_poly3<384, 4>), dim3(tiles, S), dim3(384), sizeof(float2) * (size_t)poly2_tile, fes,
-                             d_mid.p, (long long)(H_mid + max_mid), mA_prev - H_mid, H_mid + count_mid, d_hBp.p, rs.TB,
+                             d_mid.p, mid_stride, mA_prev - H_mid, H_mid + count_mid, d_hBp.p, rs.TB,
                              (int)rs.LB, (int)rs.MB, d_bphi.p, d_boff.p, kB_prev, (int)N_if, ifbuf,
-                             (long long)(H_if + max_if), H_if, poly2_tile);
-        else
-        hipLaunchKernelGGL(k_ifr_poly2<512>, dim3(tiles, S), dim3(512), sizeof(float2) * (size_t)poly2_tile, fes,
-                           d_mid.p, (long long)(H_mid + max_mid), mA_prev - H_mid, H_mid + count_mid, d_hB.p, rs.TB,
-                           (int)rs.LB, (int)rs.MB, d_bphi.p, d_boff.p, kB_prev, (int)N_if, ifbuf,
-                           (long long)(H_if + max_if), H_if, poly2_tile);
-      });
-    } else if (N_if > 0) {
-      constexpr int BL = 256;
-      const dim3 grid((unsigned)((N_if + BL - 1) / BL), S);
-      const int span = (int)(((unsigned long long)(BL - 1) * rs.MB) / rs.LB) + rs.TB + 2;
-      fe_forms_b |= rs.LT ? FMR_FE_POLY_FRAC : FMR_FE_POLY;
-      timed_on(fes, "ifr_poly", [&] {
-        if (rs.LT) {
+                             if_stride, H_if, poly2_tile);
+        else if (p.b == StageB::poly2)
+          hipLaunchKernelGGL(k_ifr_poly2<512>, dim3(tiles, S), dim3(512), sizeof(float2) * (size_t)poly2_tile, fes,
+                             d_mid.p, mid_stride, mA_prev - H_mid, H_mid + count_mid, d_hB.p, rs.TB,
+                             (int)rs.LB, (int)rs.MB, d_bphi.p, d_boff.p, kB_prev, (int)N_if, ifbuf,
+                             if_stride, H_if, poly2_tile);
+        else if (p.b == StageB::poly_frac) {
           // fractional-phase form: exact integer positions, call-relative on the device
           const __int128 tt = (__int128)kB_prev * rs.MB;
           const long long nk0 = (long long)(tt / rs.LB);
           const unsigned long long rem0 = (unsigned long long)(tt % rs.LB);
           hipLaunchKernelGGL(k_ifr_poly_frac<BL>, grid, dim3(BL), sizeof(float2) * (span + 4), fes, d_mid.p,
-                             (long long)(H_mid + max_mid), nk0 - rs.W() + 1 - (mA_prev - H_mid), H_mid + count_mid, d_hB.p,
+                             mid_stride, nk0 - rs.W() + 1 - (mA_prev - H_mid), H_mid + count_mid, d_hB.p,
                              rs.TB, hB_pitch, rs.LT, (unsigned long long)rs.LB, (unsigned long long)rs.MB, rem0, (int)N_if,
-                             ifbuf, (long long)(H_if + max_if), H_if);
+                             ifbuf, if_stride, H_if);
         } else
-        hipLaunchKernelGGL(k_ifr_poly<BL>, grid, dim3(BL), sizeof(float2) * span, fes, d_mid.p,
-                           (long long)(H_mid + max_mid), mA_prev - H_mid, H_mid + count_mid, d_hB.p, rs.TB,
-                           (unsigned)rs.LB, (unsigned)rs.MB, (unsigned long long)kB_prev * rs.MB, (int)N_if,
-                           ifbuf, (long long)(H_if + max_if), H_if);
+          hipLaunchKernelGGL(k_ifr_poly<BL>, grid, dim3(BL), sizeof(float2) * span, fes, d_mid.p,
+                             mid_stride, mA_prev - H_mid, H_mid + count_mid, d_hB.p, rs.TB,
+                             (unsigned)rs.LB, (unsigned)rs.MB, (unsigned long long)kB_prev * rs.MB, (int)N_if,
+                             ifbuf, if_stride, H_if);
       });
-    }
     if (N_in > 0 && bank) {      // (one row; the pipelined R8B tail's k_fe_post leaves the input history to this kernel)
       timed_on(fes, "in_halo", [&] {
-        hipLaunchKernelGGL((k_update_in_halo<256, 0>), dim3(1, 1), dim3(256), 0, fes, d_in_halo.p, H_in, d_iq, 0ll, N_in);
+        hipLaunchKernelGGL((k_update_in_halo<256, 0>), dim3(1, 1), dim3(256), 0, fes, d_in_halo.p, H_in, k.d_iq, 0ll, N_in);
       });
-    } else if (N_in > 0 && !use_fused && !(k.r8b_tail && pipelined)) {
+    } else if (N_in > 0 && p.a != StageA::fused && !(p.b == StageB::poly5h_disc && pipelined)) {
+      const long long stride = (long long)k.stride;
       timed_on(fes, "in_halo", [&] {
         switch (in_fmt) {
-        case 1: hipLaunchKernelGGL((k_update_in_halo<256, 1>), dim3(1, S), dim3(256), 0, fes, d_in_halo.p, H_in, d_iq, (long long)stride, N_in); break;
-        case 2: hipLaunchKernelGGL((k_update_in_halo<256, 2>), dim3(1, S), dim3(256), 0, fes, d_in_halo.p, H_in, d_iq, (long long)stride, N_in); break;
-        case 3: hipLaunchKernelGGL((k_update_in_halo<256, 3>), dim3(1, S), dim3(256), 0, fes, d_in_halo.p, H_in, d_iq, (long long)stride, N_in); break;
-        default: hipLaunchKernelGGL((k_update_in_halo<256, 0>), dim3(1, S), dim3(256), 0, fes, d_in_halo.p, H_in, d_iq, (long long)stride, N_in); break;
+        case 1: hipLaunchKernelGGL((k_update_in_halo<256, 1>), dim3(1, S), dim3(256), 0, fes, d_in_halo.p, H_in, k.d_iq, stride, N_in); break;
+        case 2: hipLaunchKernelGGL((k_update_in_halo<256, 2>), dim3(1, S), dim3(256), 0, fes, d_in_halo.p, H_in, k.d_iq, stride, N_in); break;
+        case 3: hipLaunchKernelGGL((k_update_in_halo<256, 3>), dim3(1, S), dim3(256), 0, fes, d_in_halo.p, H_in, k.d_iq, stride, N_in); break;
+        default: hipLaunchKernelGGL((k_update_in_halo<256, 0>), dim3(1, S), dim3(256), 0, fes, d_in_halo.p, H_in, k.d_iq, stride, N_in); break;
         }
       });
     }
   } else {
-    ifbuf = d_if.p;
-    last_if = ifbuf;
+    k.ifbuf = d_if.p;
+    last_if = k.ifbuf;
     if_valid = true;
-    for (int b = 0; b < nb; b++) { t_if_off[b] = (int)N_if; t_if_len[b] = (int)block_len[b]; N_if += block_len[b]; }
     if (N_if > 0)
-      HIPCHK(hipMemcpy2DAsync(ifbuf + H_if, sizeof(float2) * (H_if + max_if), d_iq, sizeof(float2) * stride,
+      HIPCHK(hipMemcpy2DAsync(k.ifbuf + H_if, sizeof(float2) * (H_if + max_if), k.d_iq, sizeof(float2) * k.stride,
                               sizeof(float2) * N_if, S, hipMemcpyDeviceToDevice, stream));
   }
   abs_in += (unsigned long long)N_in;
-  last_n_if = N_if; last_nb = nb; last_n_au = 0;
-  ht = HaloTable{};
-  ht.n = 0;
-  k.count_mid_call = count_mid_call;
+  last_n_if = N_if; last_nb = k.nb; last_n_au = 0;
+  k.ht = HaloTable{};
   if (has_rs && pipelined) {
     // the front-end stage keeps its own history: the stage-B halo is re-seated on its stream (after the fused kernel,
     // which is launched from run_tables, when that one runs)
-    if (!use_fused && !k.r8b_tail) {
+    if (!p.b_in_tables()) {
       if (int rcf = finish_front_end_stage(k)) return rcf;
     }
   } else if (has_rs) {
-    add_halo(d_mid.p, H_mid + (long long)max_mid, H_mid, count_mid_call);
+    k.add_halo(d_mid.p, H_mid + (long long)max_mid, H_mid, count_mid);
   }
   if (!has_dec || N_if == 0) {
     hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, side, &h_marks[0], call_seq);   // no table this call
-    if (audio_len) for (int b = 0; b < nb; b++) audio_len[b] = 0;
-    if (has_dec && fir_enable && !pipelined) add_halo(ifbuf, H_if + (long long)max_if, H_if, N_if);
-    if (ht.n) hipLaunchKernelGGL(k_shift_halo<256>, dim3(ht.n, S), dim3(256), 0, stream, ht);
+    if (k.audio_len) for (int b = 0; b < k.nb; b++) k.audio_len[b] = 0;
+    if (has_dec && fir_enable && !pipelined) k.add_halo(k.ifbuf, H_if + (long long)max_if, H_if, N_if);
+    if (k.ht.n) hipLaunchKernelGGL(k_shift_halo<256>, dim3(k.ht.n, S), dim3(256), 0, stream, k.ht);
     HIPCHK(hipGetLastError());
     k.done = true;                      // nothing to decode this call
-    return FMR_OK;
   }
   return FMR_OK;
 }
@@ -1640,9 +1698,9 @@ int fmr_chain::run_front_end(CallCtx &k) {
 // Pipelined chain, end of the front-end stage on its stream: stage-B history for the next call, then the event the PLL
 // stage of this call waits for.
 int fmr_chain::finish_front_end_stage(CallCtx &k) {
-  if (k.count_mid_call > 0) {
+  if (k.plan.count_mid > 0) {
     HaloTable hm{};
-    hm.d[0] = HaloDesc{(unsigned *)d_mid.p, 2 * (H_mid + (long long)max_mid), 2 * H_mid, 2 * (int)k.count_mid_call};
+    hm.d[0] = HaloDesc{(unsigned *)d_mid.p, 2 * (H_mid + (long long)max_mid), 2 * H_mid, 2 * k.plan.count_mid};
     hm.n = 1;
     hipLaunchKernelGGL(k_shift_halo<256>, dim3(1, S), dim3(256), 0, stream, hm);
   }
@@ -1654,86 +1712,86 @@ int fmr_chain::finish_front_end_stage(CallCtx &k) {
   return FMR_OK;
 }
 
+// First block of every workgroup's run of a tiled front-end kernel (the epilogue walks the block table from there): the
+// block that holds the run's first IF sample, kb_ref + tile_len x its first tile -- tile0[w] when given (the fused front
+// end's runs of equal weight), else balanced runs of r.tpw tiles, the first r.rem of them one tile longer
+void fmr_chain::fill_run_blocks(const CallCtx &k, int *blk0, const TileRuns &r, const int *tile0, long long kb_ref, int tile_len) {
+  int b = 0;
+  for (int w = 0; w < r.grid; w++) {
+    const long long t = tile0 ? tile0[w] : (long long)w * r.tpw + std::min(w, r.rem);
+    const long long kf = std::max<long long>(0, kb_ref + tile_len * t);
+    while (b < k.nb && (long long)k.t_if_off[b] + k.t_if_len[b] <= kf) b++;
+    blk0[w] = b;
+  }
+}
+
 // per-call block / chunk tables on the side stream, then the fused front end (it needs the block table)
 int fmr_chain::run_tables(CallCtx &k) {
-  auto &d_iq = k.d_iq; auto &stride = k.stride; auto &nb = k.nb; auto &N_in = k.N_in;
-  auto &h_tab = k.h_tab; auto &d_tab_slot = k.d_tab_slot; auto &t_if_off = k.t_if_off; auto &t_if_len = k.t_if_len;
-  auto &t_au_off = k.t_au_off; auto &t_au_len = k.t_au_len; auto &t_mpf = k.t_mpf; auto &N_if = k.N_if;
-  auto &use_fused = k.use_fused; auto &fused_geom = k.fused_geom; auto &ifbuf = k.ifbuf;
-  auto &N_au = k.N_au; auto &any_mpf = k.any_mpf; auto &amA_prev = k.amA_prev; auto &akB_prev = k.akB_prev;
-  auto &an_prev = k.an_prev; auto &nck = k.nck; auto &fused_n_tiles = k.fused_n_tiles;
-  auto &fused_kb_ref = k.fused_kb_ref; auto &ct = k.ct; auto &iter_on_side = k.iter_on_side; auto &bt = k.bt;
-  auto &if_stride = k.if_stride;
+  const CallPlan &p = k.plan;
+  const int nb = k.nb;
+  const long long N_if = k.N_if;
+  int *const h_tab = k.h_tab, *const d_tab_slot = k.d_tab_slot;
   // --------------------------------------------------------------- block tables
-  N_au = 0;
-  any_mpf = false;
-  amA_prev = arsc.mA; akB_prev = arsc.kB; an_prev = arsc.n_in;
+  k.N_au = 0;
+  k.any_mpf = false;
+  k.amA_prev = arsc.mA; k.akB_prev = arsc.kB; k.an_prev = arsc.n_in;
   for (int b = 0; b < nb; b++) {
-    t_mpf[b] = 0;
-    t_au_off[b] = (int)N_au;
-    t_au_len[b] = 0;
-    if (t_if_len[b] == 0) continue;          // the decoder is not called for an empty IF block (main.cpp:931-934)
+    k.t_mpf[b] = 0;
+    k.t_au_off[b] = (int)k.N_au;
+    k.t_au_len[b] = 0;
+    if (k.t_if_len[b] == 0) continue;          // the decoder is not called for an empty IF block (main.cpp:931-934)
     if (mode == FMR_MODE_FM) {
       if (wait_multipath_blocks > 0) wait_multipath_blocks--;     // FmDecode.cpp:107-110
-      else if (enable_mpf) { t_mpf[b] = 1; any_mpf = true; }
-      const long long k = arsc.advance(ars, t_if_len[b]);
-      t_au_len[b] = (int)k;
-      N_au += k;
+      else if (enable_mpf) { k.t_mpf[b] = 1; k.any_mpf = true; }
+      const long long n = arsc.advance(ars, k.t_if_len[b]);
+      k.t_au_len[b] = (int)n;
+      k.N_au += n;
     } else {
-      t_au_len[b] = t_if_len[b];
-      N_au += t_if_len[b];
+      k.t_au_len[b] = k.t_if_len[b];
+      k.N_au += k.t_if_len[b];
     }
   }
-  last_n_au = N_au;
+  last_n_au = k.N_au;
   // PLL chunk table: every decoder block is cut into chunks of <= C_PLL samples
   // The per-chunk arrays (off, len, blk) are filled on the device from the block table; the
   // host only sends 6*max_blocks+1 ints per call.
   int *t_first = h_tab + 5 * (size_t)max_blocks;
-  nck = 0;
+  k.nck = 0;
   const int c_call = (N_if <= kSmallCall && env.x_cpll == 0) ? kCPllSmall : c_pll;       // (the same rule in both chain forms: N_if only)
   for (int b = 0; b < nb; b++) {
-    t_first[b] = nck;
-    nck += (t_if_len[b] + c_call - 1) / c_call;
+    t_first[b] = k.nck;
+    k.nck += (k.t_if_len[b] + c_call - 1) / c_call;
   }
-  t_first[nb] = nck;
+  t_first[nb] = k.nck;
   const size_t head_ints = 6 * (size_t)max_blocks + 1;
   // a kernel pulls the table out of the pinned host slot: hipMemcpyAsync H2D made the caller wait for the
   // stream to drain up to the copy (0.5-1 ms of host time per call), a launch does not
   // Table kernels and the PLL's initial node guess run on the side stream, beside the front end.
   hipLaunchKernelGGL(k_copy_ints, dim3((unsigned)((head_ints + 255) / 256)), dim3(256), 0, side,
                      (const int *)h_tab, d_tab_slot, (int)head_ints);
-  int fused_grid = 0, fused_tiles_per_wg = 0, fused_part_from = 0;
-  fused_n_tiles = 0; fused_kb_ref = 0;
-  long long fused_T_first = 0;
-  if (use_fused) {
-    // one workgroup per CU: contiguous runs of macro tiles, the streams share the CUs.  The table's tail carries the
-    // block that holds the first IF sample of every workgroup's run (the epilogue walks the block table from there).
-    const long long P_first = fused_geom.kB_prev / 48, P_last = (fused_geom.kB_prev + N_if - 1) / 48;
-    fused_T_first = P_first / 8;
-    fused_n_tiles = (int)(P_last / 8 - fused_T_first + 1);
-    // Pipelined chain: the front end leaves one CU of every XCD free.  A workgroup is dispatched inside the XCD its index
-    // maps to, and the kernels that run beside the front end -- lock logic (32 KB of LDS), the DC block's node pass (213
-    // VGPRs), the spare PLL rounds -- do not fit beside a 152 KB workgroup: on an XCD the front end fills they wait for
-    // it to end (measured: the lock logic 250 instead of 55 us, and the next PLL pass behind it).
-    const int fe_dflt = pipelined ? std::max(8, n_cu - kFeSpareCus) : n_cu;
-    const int fe_cus = (pipelined && env.fe_cus > 0) ? std::min(env.fe_cus, n_cu) : fe_dflt;
-    const int wg_per_stream = std::max(1, std::min(kFusedTile0Off - 1, fe_cus / S));
-    // (ceil(n / grid) macro tiles for all but the last workgroup.  Balanced runs -- n mod grid workgroups with one tile more --
-    // were measured in round 6: 248 instead of 245 workgroups at 2^27 samples, and the launch 5 us LONGER in the chain: the
-    // three compute units more that the uneven split leaves free serve the kernels beside it)
-    fused_tiles_per_wg = (fused_n_tiles + wg_per_stream - 1) / wg_per_stream;
-    fused_grid = (fused_n_tiles + fused_tiles_per_wg - 1) / fused_tiles_per_wg;
-    fe_spare_cus = std::max(0, n_cu - fused_grid * S);
-    int *t_wg = h_tab + (tab_ints - kMaxFusedWg);
-    const long long kb_ref = 384 * fused_T_first - fused_geom.kB_prev;
-    {   // the first block k_stats walks (kernels.hpp, same rule): earlier blocks need no partial sums
-      int seen = 0, b_first = 0;
-      for (int b0 = ((nb - 1) / 64) * 64; b0 > 0 && !b_first; b0 -= 64) {
-        for (int b = b0; b < std::min(b0 + 64, nb); b++) seen += t_if_len[b] != 0;
-        if (seen >= 400) b_first = b0;
-      }
-      fused_part_from = t_if_off[b_first];
-    }
+  // the table's tail: first block (fused front end: and first macro tile) of every run of the front end's tiled kernel,
+  // first block of every run of the IF filter's
+  int *const t_wg = h_tab + (tab_ints - kMaxFusedWg), *const d_wg = d_tab_slot + (tab_ints - kMaxFusedWg);
+  // the kernel's own tables: first block of every workgroup and, when the front end runs a call ahead of the decoder,
+  // the block table too (the side stream's copy of it sits behind the previous call's lock logic; both copies write
+  // the same values)
+  auto copy_runs = [&](int n) {
+    if (pipelined)
+      hipLaunchKernelGGL(k_copy_ints2, dim3((unsigned)((n + 2 * (size_t)max_blocks + 255) / 256)), dim3(256), 0, stream,
+                         (const int *)t_wg, d_wg, n, (const int *)h_tab, d_tab_slot, 2 * max_blocks);
+    else
+      hipLaunchKernelGGL(k_copy_ints, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, side, (const int *)t_wg, d_wg, n);
+  };
+  const TileRuns &fr = p.fe_runs;
+  int fused_part_from = 0;
+  k.fused_n_tiles = 0; k.fused_kb_ref = 0;
+  const long long fused_T_first = p.prev.kB / 48 / 8;
+  if (p.b == StageB::fused) {
+    // one workgroup per CU: contiguous runs of macro tiles, the streams share the CUs
+    k.fused_n_tiles = fr.tiles;
+    fe_spare_cus = std::max(0, n_cu - fr.grid * S);
+    const long long kb_ref = 384 * fused_T_first - p.prev.kB;
+    fused_part_from = k.t_if_off[first_part_block(k.t_if_len, nb)];
     // Where the runs start: a macro tile whose epilogue writes the per-block partial sums (the last ~400 blocks of a call:
     // block walk, six wave reductions and a store per 128 samples) costs its workgroup kFusedSumWeight more than one that does
     // not -- measured, round 6: the workgroups of the last fifth of a 2048-block call took 207-213 us against the others' 194-197
@@ -1741,126 +1799,56 @@ int fmr_chain::run_tables(CallCtx &k) {
     // every run behind the first block of every run.
     int *t_tile0 = t_wg + kFusedTile0Off;
     {
-      const double eps = k.fused_disc ? (env.x_sumw >= 0 ? env.x_sumw * 1e-3 : kFusedSumWeight) : 0.0;
-      const long long tp = std::min<long long>(fused_n_tiles, std::max<long long>(0, (fused_part_from - kb_ref) / 384));   // first tile with sums
-      const double W = (double)tp + (double)(fused_n_tiles - tp) * (1.0 + eps);
+      const double eps = p.b_disc ? (env.x_sumw >= 0 ? env.x_sumw * 1e-3 : kFusedSumWeight) : 0.0;
+      const long long tp = std::min<long long>(fr.tiles, std::max<long long>(0, (fused_part_from - kb_ref) / 384));   // first tile with sums
+      const double W = (double)tp + (double)(fr.tiles - tp) * (1.0 + eps);
       t_tile0[0] = 0;
-      for (int w = 1; w < fused_grid; w++) {
-        const double cum = W * w / fused_grid;
+      for (int w = 1; w < fr.grid; w++) {
+        const double cum = W * w / fr.grid;
         const double tt = cum <= (double)tp ? cum : (double)tp + (cum - (double)tp) / (1.0 + eps);
         int ti = (int)(tt + 0.5);
         ti = std::max(ti, t_tile0[w - 1] + 1);                              // every run holds a tile
-        ti = std::min(ti, fused_n_tiles - (fused_grid - w));                // ... the later ones too
+        ti = std::min(ti, fr.tiles - (fr.grid - w));                        // ... the later ones too
         t_tile0[w] = ti;
       }
-      t_tile0[fused_grid] = fused_n_tiles;
+      t_tile0[fr.grid] = fr.tiles;
     }
-    int b = 0;
-    for (int w = 0; w < fused_grid; w++) {
-      const long long kf = std::max<long long>(0, kb_ref + 384ll * t_tile0[w]);
-      while (b < nb && (long long)t_if_off[b] + t_if_len[b] <= kf) b++;
-      t_wg[w] = b;
-    }
-    // the kernel's own tables: first block of every workgroup and, when the front end runs a call ahead of the decoder,
-    // the block table too (the side stream's copy of it sits behind the previous call's lock logic; both copies write
-    // the same values)
-    if (pipelined)
-      hipLaunchKernelGGL(k_copy_ints2, dim3((unsigned)((kFusedTile0Off + fused_grid + 1 + 2 * (size_t)max_blocks + 255) / 256)), dim3(256), 0, stream,
-                         (const int *)t_wg, d_tab_slot + (tab_ints - kMaxFusedWg), kFusedTile0Off + fused_grid + 1, (const int *)h_tab, d_tab_slot,
-                         2 * max_blocks);
-    else
-      hipLaunchKernelGGL(k_copy_ints, dim3((unsigned)((kFusedTile0Off + fused_grid + 1 + 255) / 256)), dim3(256), 0, side,
-                         (const int *)t_wg, d_tab_slot + (tab_ints - kMaxFusedWg), kFusedTile0Off + fused_grid + 1);
+    fill_run_blocks(k, t_wg, fr, t_tile0, kb_ref, 384);
+    copy_runs(kFusedTile0Off + fr.grid + 1);
   }
-  k.fir_tail = false;
-  if (fir_mfma_fm && mode == FMR_MODE_FM && fir_enable && !enable_mpf && !serial_mode && N_if >= 3072) {
-    // FM -f on the matrix cores: contiguous runs of 3072-output tiles per workgroup (call-relative), first block of every run
-    k.fir_tail = true;
-    for (int b = 0; b < nb; b++) if (t_if_len[b] != 0 && t_if_len[b] < 128) k.fir_tail = false;
+  const TileRuns &ir = p.fir_runs;
+  if (p.fir_tail()) {
+    fill_run_blocks(k, t_wg + kFirBlk0Off, ir, nullptr, 0, 3072);
+    hipLaunchKernelGGL(k_copy_ints, dim3((unsigned)((ir.grid + 255) / 256)), dim3(256), 0, side,
+                       (const int *)(t_wg + kFirBlk0Off), d_wg + kFirBlk0Off, ir.grid);
   }
-  if (k.fir_tail) {
-    k.fir_tiles = (int)((N_if - 1) / 3072 + 1);
-    const int wgs = std::max(1, std::min(kMaxFusedWg - kFirBlk0Off, 2 * n_cu / S));
-    // (two workgroups share a compute unit: balanced runs -- fir_rem of them one tile longer -- keep all of them busy, where
-    // ceil(tiles / slots) for everybody left 46 of 256 units idle at 2^27 samples per call)
-    k.fir_grid = std::min(wgs, k.fir_tiles);
-    k.fir_tpw = k.fir_tiles / k.fir_grid;
-    k.fir_rem = k.fir_tiles - k.fir_tpw * k.fir_grid;
-    {
-      int seen = 0, b_first = 0;
-      for (int b0 = ((nb - 1) / 64) * 64; b0 > 0 && !b_first; b0 -= 64) {
-        for (int b = b0; b < std::min(b0 + 64, nb); b++) seen += t_if_len[b] != 0;
-        if (seen >= 400) b_first = b0;
-      }
-      k.fir_part_from = t_if_off[b_first];
-    }
-    int *t_fb = h_tab + (tab_ints - kMaxFusedWg) + kFirBlk0Off;
-    int b = 0;
-    for (int w = 0; w < k.fir_grid; w++) {
-      const long long kf = 3072ll * ((long long)w * k.fir_tpw + std::min(w, k.fir_rem));
-      while (b < nb && (long long)t_if_off[b] + t_if_len[b] <= kf) b++;
-      t_fb[w] = b;
-    }
-    hipLaunchKernelGGL(k_copy_ints, dim3((unsigned)((k.fir_grid + 255) / 256)), dim3(256), 0, side,
-                       (const int *)t_fb, d_tab_slot + (tab_ints - kMaxFusedWg) + kFirBlk0Off, k.fir_grid);
-  }
-  int r8b_grid = 0, r8b_tpw = 0, r8b_rem = 0, r8b_tiles = 0;
-  if (k.r8b_tail) {
-    // R8B class: contiguous runs of stage-B tiles (64 periods = 3072 IF samples) per workgroup; the table's tail carries the
-    // block that holds the first IF sample of every run, as for the fused front end
-    const long long P_first = k.r8b_kB_prev / 48, P_last = (k.r8b_kB_prev + N_if - 1) / 48;
-    r8b_tiles = (int)((P_last - P_first) / 64 + 1);
-    // (pipelined chain: a compute unit per XCD stays free for the kernels beside the front end, as under the fused kernel)
-    const int wgs = std::max(1, std::min(kFusedTile0Off - 1, (pipelined ? std::max(8, n_cu - kFeSpareCus) : n_cu) / S));
-    // balanced runs: r8b_rem of them one tile longer (ceil(tiles / workgroups) for everybody left 16 of 256 compute units idle
-    // at 2^27 samples per call and put seven tiles WITH partial sums on the workgroups that end the launch)
-    r8b_grid = std::min(wgs, r8b_tiles);
-    r8b_tpw = r8b_tiles / r8b_grid;
-    r8b_rem = r8b_tiles - r8b_tpw * r8b_grid;
-    fused_n_tiles = 8 * r8b_tiles;                             // in the epilogue's macro tiles of 384 samples
-    const long long kb_ref = 48 * P_first - k.r8b_kB_prev;
-    fused_kb_ref = (int)kb_ref;
-    {   // the first block k_stats walks (same rule as above)
-      int seen = 0, b_first = 0;
-      for (int b0 = ((nb - 1) / 64) * 64; b0 > 0 && !b_first; b0 -= 64) {
-        for (int b = b0; b < std::min(b0 + 64, nb); b++) seen += t_if_len[b] != 0;
-        if (seen >= 400) b_first = b0;
-      }
-      fused_part_from = t_if_off[b_first];
-    }
-    int *t_wg = h_tab + (tab_ints - kMaxFusedWg);
-    int b = 0;
-    for (int w = 0; w < r8b_grid; w++) {
-      const long long kf = std::max<long long>(0, kb_ref + 3072ll * ((long long)w * r8b_tpw + std::min(w, r8b_rem)));
-      while (b < nb && (long long)t_if_off[b] + t_if_len[b] <= kf) b++;
-      t_wg[w] = b;
-    }
-    if (pipelined)
-      hipLaunchKernelGGL(k_copy_ints2, dim3((unsigned)((r8b_grid + 2 * (size_t)max_blocks + 255) / 256)), dim3(256), 0, stream,
-                         (const int *)t_wg, d_tab_slot + (tab_ints - kMaxFusedWg), r8b_grid, (const int *)h_tab, d_tab_slot,
-                         2 * max_blocks);
-    else
-      hipLaunchKernelGGL(k_copy_ints, dim3((unsigned)((r8b_grid + 255) / 256)), dim3(256), 0, side,
-                         (const int *)t_wg, d_tab_slot + (tab_ints - kMaxFusedWg), r8b_grid);
+  if (p.b == StageB::poly5h_disc) {
+    // R8B class: the table's tail carries the block that holds the first IF sample of every run, as for the fused front end
+    k.fused_n_tiles = 8 * fr.tiles;                             // in the epilogue's macro tiles of 384 samples
+    const long long kb_ref = 48 * (p.prev.kB / 48) - p.prev.kB;
+    k.fused_kb_ref = (int)kb_ref;
+    fused_part_from = k.t_if_off[first_part_block(k.t_if_len, nb)];
+    fill_run_blocks(k, t_wg, fr, nullptr, kb_ref, 3072);
+    copy_runs(fr.grid);
   }
   int *d_first = d_tab_slot + 5 * (size_t)max_blocks;
   int *d_ck = d_tab_slot + head_ints;
-  ct = ChunkTab{d_ck, d_ck + max_ck, d_ck + 2 * max_ck, d_first, nck};
+  k.ct = ChunkTab{d_ck, d_ck + max_ck, d_ck + 2 * max_ck, d_first, k.nck};
   hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, side, &h_marks[0], call_seq);
-  if (mode == FMR_MODE_FM && nck > 0) {
+  if (mode == FMR_MODE_FM && k.nck > 0) {
     hipLaunchKernelGGL(k_chunk_tab, dim3(nb), dim3(64), 0, side, d_tab_slot, d_tab_slot + max_blocks, d_first, c_call,
                        d_ck, d_ck + max_ck, d_ck + 2 * max_ck);
     if (stereo && !serial_mode)
       timed_on(side, "pll_begin", [&] {
-        hipLaunchKernelGGL(k_pll_begin, dim3((nck + 1 + 63) / 64, S), dim3(64), 0, side, d_pll_nodes.p, ct, d_state.p,
+        hipLaunchKernelGGL(k_pll_begin, dim3((k.nck + 1 + 63) / 64, S), dim3(64), 0, side, d_pll_nodes.p, k.ct, d_state.p,
                            pllc);
       });
   }
   // FM without the equaliser: the round flags and the AGC's start nodes are reset here too, beside the front end (5-10 us
   // of the critical path when launched between the front end and the PLL's first pass).  Their last readers of the previous
   // call are the PLL kernels (ordered before this stream's k_pll_finish) and the side-stream AGC (ev_agc).
-  iter_on_side = (mode == FMR_MODE_FM) && !serial_mode && !enable_mpf;
-  if (iter_on_side) {
+  k.iter_on_side = (mode == FMR_MODE_FM) && !serial_mode && !enable_mpf;
+  if (k.iter_on_side) {
     if (ev_agc_live) HIPCHK(hipStreamWaitEvent(side, ev_agc, 0));
     const int nc = (int)((N_if + C_AGC - 1) / C_AGC);
     hipLaunchKernelGGL(k_iter_begin, dim3(S), dim3(256), 0, side, d_flags.p, d_agc_nodes.p, nc, d_state.p, S,
@@ -1874,68 +1862,70 @@ int fmr_chain::run_tables(CallCtx &k) {
     const int np = (int)ring_prev_n;
     ctab.d[ctab.n++] = CarryDesc{(const unsigned *)base_slot(ring_prev), (unsigned *)k.base, bstr, H_b, np};
     if (stereo) ctab.d[ctab.n++] = CarryDesc{(const unsigned *)raw_slot(ring_prev), (unsigned *)k.raw, 2 * bstr, 2 * H_b, 2 * np};
-    if (fir_enable) ctab.d[ctab.n++] = CarryDesc{(const unsigned *)if_slot(ring_prev), (unsigned *)ifbuf, 2 * (H_if + (long long)max_if), 2 * H_if, 2 * np};
+    if (fir_enable) ctab.d[ctab.n++] = CarryDesc{(const unsigned *)if_slot(ring_prev), (unsigned *)k.ifbuf, 2 * (H_if + (long long)max_if), 2 * H_if, 2 * np};
     hipLaunchKernelGGL(k_carry_halo<256>, dim3(ctab.n, S), dim3(256), 0, side, ctab);
   }
   // the decoder waits for the tables.  In the pipelined chain the front end shares its stream and must not: the wait is
   // enqueued behind the front end's launch (below)
   HIPCHK(hipEventRecord(ev_tab, side));
   if (!pipelined) HIPCHK(hipStreamWaitEvent(stream, ev_tab, 0));
-  bt = BlockTab{d_tab_slot, d_tab_slot + max_blocks, d_tab_slot + 2 * max_blocks, d_tab_slot + 3 * max_blocks,
-              d_tab_slot + 4 * max_blocks, nb};
-  if_stride = H_if + (long long)max_if;
-  if (use_fused) {
+  k.bt = BlockTab{d_tab_slot, d_tab_slot + max_blocks, d_tab_slot + 2 * max_blocks, d_tab_slot + 3 * max_blocks,
+                  d_tab_slot + 4 * max_blocks, nb};
+  k.if_stride = H_if + (long long)max_if;
+  float2 *const ifbuf = k.ifbuf;
+  const long long if_stride = k.if_stride;
+  // (what the pipelined chain's k_fe_post reads, by value)
+  const float2 *const d_iq = k.d_iq;
+  const long long stride = (long long)k.stride, N_in = k.N_in;
+  // the discriminator's carried phase: when the previous call ran the discriminator in its decoder stage (a call too
+  // short for the fused kernel), its phase is committed by that call's statistics kernel on the side stream
+  if (pipelined && p.b_disc && disc_commit_on_side) HIPCHK(hipStreamWaitEvent(stream, ev_stats, 0));
+  if (p.b == StageB::fused) {
     // ---- fused front end: needs the block table (per-block statistics), hence launched here, after the table copy
     constexpr int D = kFusedD, NA = kFusedNA;
     FusedArgs a{};
-    a.iq = d_iq; a.iq_stride = (long long)stride; a.n_valid = N_in;
+    a.iq = d_iq; a.iq_stride = stride; a.n_valid = N_in;
     a.in_halo = d_in_halo.p; a.H_in = H_in; a.afragA = reinterpret_cast<const uint4 *>(d_fused_afragA.p); a.hA = d_hA.p; a.hB = d_hB.p;
-    const long long n0 = (long long)rs.D * fused_geom.mA_prev - fused_geom.n_prev;
+    const long long n0 = (long long)rs.D * p.prev.mA - p.prev.n_in;
     const long long lo0 = n0 + rs.ca() - (NA - 1);
     const int par = (int)(((lo0 % 2) + 2) % 2);
     a.nbase = lo0 - par;
     constexpr int kME = FusedShape<kFusedD, kFusedNA>::ME, kEPT = FusedShape<kFusedD, kFusedNA>::EPT;
     const long long T_first = fused_T_first, E_ref = kEPT * T_first - 1;
-    a.j_ref = (int)(kME * E_ref + 104 - fused_geom.mA_prev);
+    a.j_ref = (int)(kME * E_ref + 104 - p.prev.mA);
     a.pos_ref = (int)((((kME * E_ref + 208) % 3000) + 3000) % 3000);
     a.t3_ref = (int)(T_first % 3);
-    a.kb_ref = (int)(384 * T_first - fused_geom.kB_prev);
-    a.count_mid = fused_geom.count_mid;
+    a.kb_ref = (int)(384 * T_first - p.prev.kB);
+    a.count_mid = p.count_mid;
     a.mid = d_mid.p; a.mid_stride = (long long)(H_mid + max_mid); a.H_mid = H_mid;
     a.afragB = reinterpret_cast<const uint4 *>(d_fused_afragB.p); a.hB_inv_scale = fused_hB_inv_scale; a.n_if = (int)N_if;
     a.out = ifbuf; a.out_stride = if_stride; a.out_off = H_if;
     k.nrm = nullptr;
-    if (k.fused_disc && !debug_taps) {
+    if (p.b_disc && !debug_taps) {
       // nobody but the AGC's state solve reads the IF behind the discriminator epilogue: it gets |x|^2 (4 B per sample, in the
       // IF slot's memory) and the IF samples stay on chip
       a.out = nullptr;
       a.nrm = reinterpret_cast<float *>(ifbuf); a.nrm_stride = 2 * if_stride; a.nrm_off = 0;
       k.nrm = a.nrm; k.nrm_stride = a.nrm_stride;
     }
-    a.n_tiles = fused_n_tiles;
-    a.tiles_per_wg = fused_tiles_per_wg;
-    const int grid = fused_grid;
-    a.wg_blk0 = d_tab_slot + (tab_ints - kMaxFusedWg);
+    a.n_tiles = fr.tiles;
+    a.tiles_per_wg = fr.tpw;
+    const int grid = fr.grid;
+    a.wg_blk0 = d_wg;
     a.wg_tile0 = a.wg_blk0 + kFusedTile0Off;
     a.zero16 = reinterpret_cast<const float2 *>(d_zero16.p);
-    a.base = k.fused_disc ? k.base : nullptr;        // null: IF samples only (an IF FIR or the equaliser comes first)
+    a.base = p.b_disc ? k.base : nullptr;        // null: IF samples only (an IF FIR or the equaliser comes first)
     a.base_stride = H_b + (long long)max_if; a.base_off = H_b;
     a.dec = debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
     a.nf = disc_nf; a.bound = disc_bound;
     a.st = d_state.p; a.hB_last = d_hB_last.p; a.part = k.part;
-    a.if_off = bt.if_off; a.if_len = bt.if_len; a.nb = nb;
+    a.if_off = k.bt.if_off; a.if_len = k.bt.if_len; a.nb = nb;
     a.part_from = fused_part_from;
-    if ((size_t)a.n_tiles * 3 * S > d_fused_part.n) { set_err("internal capacity exceeded (fused tiles)"); return FMR_ERR_CAPACITY; }
     constexpr size_t kLds = FusedShape<D, NA>::LDS_BYTES;
     hipStream_t fes = stream;
-    // the discriminator's carried phase: when the previous call ran the discriminator in its decoder stage (a call too
-    // short for the fused kernel), its phase is committed by that call's statistics kernel on the side stream
-    if (pipelined && k.fused_disc && disc_commit_on_side) HIPCHK(hipStreamWaitEvent(stream, ev_stats, 0));
     if (d_fe_stamps.p) { a.stamps = d_fe_stamps.p; fe_stamps_n = grid * S; }
-    if ((size_t)grid * S * 2 * FusedShape<D, NA>::MIDR > d_fused_mid32.n) { set_err("internal capacity exceeded (fused workgroups)"); return FMR_ERR_CAPACITY; }
     a.mid32 = d_fused_mid32.p;
     if (d_fe_stamps.p) hipLaunchKernelGGL(k_fused_stamp, dim3(1), dim3(1), 0, fes, stamp_slot(0), 16 * kStampCalls);
-    fe_forms_a |= FMR_FE_FUSED; fe_forms_b |= FMR_FE_FUSED;
     timed_on(fes, "ifr_fused", [&] {
       if (ext_a) {      // (timed with the events of its own dispatch)
         if (par) hipExtLaunchKernelGGL((k_ifr_fused<D, NA, 1, 0>), dim3(grid, S), dim3(FUSED_THREADS), kLds, fes, ext_a, ext_b, 0, a);
@@ -1946,29 +1936,12 @@ int fmr_chain::run_tables(CallCtx &k) {
       else hipLaunchKernelGGL((k_ifr_fused<D, NA, 0, 0>), dim3(grid, S), dim3(FUSED_THREADS), kLds, fes, a);
     });
     if (d_fe_stamps.p) hipLaunchKernelGGL(k_fused_stamp, dim3(1), dim3(1), 0, fes, stamp_slot(1), 0);
-    fused_kb_ref = a.kb_ref;
-    if (pipelined) {
-      // The PLL stage starts from here.  What the front-end stage carries into its next call -- the input history, the
-      // stage-B history, the discriminator's last phase -- is one small kernel on its stream; when that stream is the
-      // decoder's it is launched behind the PLL's first pass (run_fm_pll), not between the front end and that pass.
-      HIPCHK(hipEventRecord(ev_fe[k.par], stream));
-      const int commit = (int)k.fused_disc, count_mid = fused_geom.count_mid;
-      k.fe_post = [=] {
-        hipLaunchKernelGGL(k_fe_post<256>, dim3(3, S), dim3(256), 0, stream, d_in_halo.p, H_in, d_iq, (long long)stride, N_in,
-                           d_mid.p, (long long)(H_mid + max_mid), H_mid, count_mid, d_state.p, commit);
-      };
-      // the previous call's tail stage: behind this front end, beside this call's PLL stage
-#ifndef FMR_FIR_TAIL_EARLY
-      // (... and behind the IF filter's kernel where that one sits between front end and PLL: run_fm)
-      if (k.fir_tail) { k.tail_deferred = true; if (int rc = flush_walk()) return rc; } else
-#endif
-      if (int rc = flush_tail(ev_fe[k.par])) return rc;
-    }
+    k.fused_kb_ref = a.kb_ref;
   }
-  if (k.r8b_tail) {
+  if (p.b == StageB::poly5h_disc) {
     // ---- R8B class: stage B with the discriminator epilogue (the fused front end's, a wave per 384 staged samples)
     FusedArgs a{};
-    a.n_if = (int)N_if; a.kb_ref = fused_kb_ref;
+    a.n_if = (int)N_if; a.kb_ref = k.fused_kb_ref;
     a.out = nullptr; a.out_stride = if_stride; a.out_off = H_if;
     a.nrm = reinterpret_cast<float *>(ifbuf); a.nrm_stride = 2 * if_stride; a.nrm_off = 0;
     if (debug_taps) { a.out = ifbuf; a.nrm = nullptr; }      // the IF samples themselves (fmr_debug_read 0); the AGC reads them then
@@ -1976,32 +1949,37 @@ int fmr_chain::run_tables(CallCtx &k) {
     a.base = k.base; a.base_stride = H_b + (long long)max_if; a.base_off = H_b;
     a.dec = debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
     a.nf = disc_nf; a.bound = disc_bound;
-    a.st = d_state.p; a.part = k.part; a.n_tiles = fused_n_tiles; a.part_from = fused_part_from;
-    a.if_off = bt.if_off; a.if_len = bt.if_len; a.nb = nb;
-    a.wg_blk0 = d_tab_slot + (tab_ints - kMaxFusedWg);
+    a.st = d_state.p; a.part = k.part; a.n_tiles = k.fused_n_tiles; a.part_from = fused_part_from;
+    a.if_off = k.bt.if_off; a.if_len = k.bt.if_len; a.nb = nb;
+    a.wg_blk0 = d_wg;
     a.mid32 = d_run_ph.p;
-    if ((size_t)a.n_tiles * 3 * S > d_fused_part.n || (size_t)r8b_grid * 2 * S > d_run_ph.n) { set_err("internal capacity exceeded (stage-B tiles)"); return FMR_ERR_CAPACITY; }
-    if (pipelined && disc_commit_on_side) HIPCHK(hipStreamWaitEvent(stream, ev_stats, 0));
-    fe_forms_b |= FMR_FE_POLY5H_DISC;
     timed_on(stream, "ifr_poly", [&] {
-      hipLaunchKernelGGL((k_ifr_poly5h<48, 125, Poly5hDiscEpi>), dim3(r8b_grid, S), dim3(64 * FMR_POLY5H_WAVES), poly5h_lds, stream,
-                         d_mid.p, (long long)(H_mid + max_mid), k.r8b_mA_prev - H_mid, H_mid + k.r8b_count_mid, d_afrag5h.p,
-                         poly5h_nkb, poly5h_inv_scale, rs.TB, k.r8b_kB_prev, (int)N_if, (float2 *)nullptr, 0ll, 0, poly2_tile, r8b_tiles,
-                         a, r8b_tpw, r8b_rem);
-      if (r8b_grid > 1)
-        hipLaunchKernelGGL(k_poly5h_heads, dim3((r8b_grid + 62) / 64, S), dim3(64), 0, stream, a, r8b_grid, r8b_tpw, r8b_rem);
+      hipLaunchKernelGGL((k_ifr_poly5h<48, 125, Poly5hDiscEpi>), dim3(fr.grid, S), dim3(64 * FMR_POLY5H_WAVES), poly5h_lds, stream,
+                         d_mid.p, (long long)(H_mid + max_mid), p.prev.mA - H_mid, H_mid + p.count_mid, d_afrag5h.p,
+                         poly5h_nkb, poly5h_inv_scale, rs.TB, p.prev.kB, (int)N_if, (float2 *)nullptr, 0ll, 0, poly2_tile, fr.tiles,
+                         a, fr.tpw, fr.rem);
+      if (fr.grid > 1)
+        hipLaunchKernelGGL(k_poly5h_heads, dim3((fr.grid + 62) / 64, S), dim3(64), 0, stream, a, fr.grid, fr.tpw, fr.rem);
     });
-    if (pipelined) {
-      // as behind the fused front end: the PLL stage starts from here; input history, stage-B history and the
-      // discriminator's phase are one small kernel behind the PLL's first pass
-      HIPCHK(hipEventRecord(ev_fe[k.par], stream));
-      const int count_mid = k.r8b_count_mid;
-      k.fe_post = [=] {
-        hipLaunchKernelGGL(k_fe_post<256>, dim3(3, S), dim3(256), 0, stream, d_in_halo.p, H_in, d_iq, (long long)stride,
-                           bank ? 0ll : N_in, d_mid.p, (long long)(H_mid + max_mid), H_mid, count_mid, d_state.p, 1);
-      };
-      if (int rc = flush_tail(ev_fe[k.par])) return rc;
-    }
+  }
+  if (pipelined && p.b_in_tables()) {
+    // The PLL stage starts from here.  What the front-end stage carries into its next call -- the input history (a bank's
+    // is left to its own kernel), the stage-B history, the discriminator's last phase -- is one small kernel on its stream;
+    // when that stream is the decoder's it is launched behind the PLL's first pass (run_fm_pll), not between the front end
+    // and that pass.
+    HIPCHK(hipEventRecord(ev_fe[k.par], stream));
+    const int commit = (int)p.b_disc, count_mid = p.count_mid;
+    const long long n_in = bank ? 0ll : N_in;
+    k.fe_post = [=] {
+      hipLaunchKernelGGL(k_fe_post<256>, dim3(3, S), dim3(256), 0, stream, d_in_halo.p, H_in, d_iq, stride, n_in,
+                         d_mid.p, (long long)(H_mid + max_mid), H_mid, count_mid, d_state.p, commit);
+    };
+    // the previous call's tail stage: behind this front end, beside this call's PLL stage
+#ifndef FMR_FIR_TAIL_EARLY
+    // (... and behind the IF filter's kernel where that one sits between front end and PLL: run_fm)
+    if (p.fir_tail()) { k.tail_deferred = true; if (int rc = flush_walk()) return rc; } else
+#endif
+    if (int rc = flush_tail(ev_fe[k.par])) return rc;
   }
   if (pipelined) HIPCHK(hipStreamWaitEvent(stream, ev_tab, 0));
   return FMR_OK;
@@ -2009,10 +1987,11 @@ int fmr_chain::run_tables(CallCtx &k) {
 
 // IF-rate part common to all decoders: fine tuner, IF filter + level, IF AGC
 int fmr_chain::run_if_stage(CallCtx &k) {
-  auto &nb = k.nb; auto &N_if = k.N_if; auto &ifbuf = k.ifbuf; auto &iter_on_side = k.iter_on_side; auto &bt = k.bt;
-  auto &if_stride = k.if_stride; auto &rms_in_disc = k.rms_in_disc; auto &xin = k.xin; auto &x_stride = k.x_stride;
-  auto &x_off = k.x_off; auto &disc_gain = k.disc_gain; auto &agc_on_side = k.agc_on_side;
-  auto &agc_deferred = k.agc_deferred; auto &enqueue_agc = k.enqueue_agc;
+  const CallPlan &p = k.plan;
+  const int nb = k.nb;
+  const long long N_if = k.N_if, if_stride = k.if_stride;
+  float2 *const ifbuf = k.ifbuf;
+  const BlockTab &bt = k.bt;
   // ------------------------------------------------------- decoder, IF-rate part
   // SSB / WSPR: mix the new IF samples in place before the filter (the filter history in the halo is already mixed)
   if (ssb_like && d_ft_pre.p)
@@ -2020,52 +1999,43 @@ int fmr_chain::run_if_stage(CallCtx &k) {
       hipLaunchKernelGGL(k_finetune<256>, dim3(nb, S), dim3(256), 0, stream, ifbuf, if_stride, H_if, bt, d_ft_pre.p,
                          480, ft_index, (float *)nullptr);
     });
-  // FM without the IF FIR: the block RMS is taken inside the discriminator kernel (same samples, same lane order)
-  rms_in_disc = (mode == FMR_MODE_FM) && !fir_enable && !serial_mode;
-  if (!rms_in_disc) {
+  if (p.fir == IfForm::poly4_disc) {
+    FusedArgs a{};
+    a.n_if = (int)N_if; a.kb_ref = 0;
+    a.out = d_fir.p; a.out_stride = (long long)max_if; a.out_off = 0;
+    a.base = k.base; a.base_stride = H_b + (long long)max_if; a.base_off = H_b;
+    a.dec = debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
+    a.nf = disc_nf; a.bound = disc_bound;
+    const TileRuns &r = p.fir_runs;
+    a.st = d_state.p; a.part = k.part; a.n_tiles = 8 * r.tiles; a.part_from = k.t_if_off[first_part_block(k.t_if_len, nb)];
+    a.if_off = bt.if_off; a.if_len = bt.if_len; a.nb = nb;
+    a.wg_blk0 = k.d_tab_slot + (tab_ints - kMaxFusedWg) + kFirBlk0Off;
+    a.mid32 = d_run_ph.p;
+    a.fir_c0 = h_coeff0; a.fir_order = ntaps - 1; a.hA = d_coeff.p;      // (hA: the filter's taps, for the repair of tiles that hold a non-finite sample)
+    timed("fm_block", [&] {
+      constexpr int kTile = 64 * 48 + 47 + 127 + 64;
+      hipLaunchKernelGGL((k_ifr_poly4<48, 48, 127, 2, Poly4FirDiscEpi>), dim3(r.grid, S), dim3(256),
+                         sizeof(float2) * (size_t)(((kTile + 127) / 128) * 128 + 4 * 8 * 48), stream, ifbuf, if_stride,
+                         (long long)(64 - H_if), H_if + (int)N_if, d_afrag_fir_fm.p, 0ll, (int)N_if, (float2 *)nullptr, 0ll, 0,
+                         kTile, r.tiles, a, r.tpw, r.rem);
+      if (r.grid > 1)
+        hipLaunchKernelGGL(k_poly5h_heads, dim3((r.grid + 62) / 64, S), dim3(64), 0, stream, a, r.grid, r.tpw, r.rem);
+    });
+  } else if (p.fir != IfForm::none) {
     timed("fm_block", [&] {
       // four outputs per lane; FM without the equaliser: the discriminator is its epilogue (k_disc is not launched)
-      // tile length: 1024 outputs, or the longest IF block of the call rounded up to four when that is shorter
-      int tl = 4;
-      for (int b = 0; b < nb; b++) tl = std::max(tl, (k.t_if_len[b] + 3) & ~3);
-      const int TL = std::min(1024, tl);
-      const size_t lds_fb = sizeof(float2) * (4 * (size_t)fm_block3_plane(ntaps - 1, TL) + ((size_t)ntaps + 4) / 2 + (size_t)(ntaps - 1) + TL);
-      const bool blocked = fir_enable && ntaps >= 2 && lds_fb <= 60000 && !serial_mode;
-      k.fir_disc = blocked && mode == FMR_MODE_FM && !enable_mpf;
-      if (!k.fir_disc) k.fir_tail = false;
       auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(nb, S), dim3(256), lds_fb, stream, ifbuf, if_stride, H_if, bt,
+        hipLaunchKernelGGL(kern, dim3(nb, S), dim3(256), p.lds_fb, stream, ifbuf, if_stride, H_if, bt,
                            d_coeff.p, ntaps, (int)(mode != FMR_MODE_FM), d_fir.p, (long long)max_if, d_if_rms_blk.p,
                            disc_nf, disc_bound, d_dec.p, (long long)max_if, k.base, H_b + (long long)max_if, H_b,
-                           d_bb_mean_blk.p, d_bb_rms_blk.p, d_blk_ph.p, TL);
+                           d_bb_mean_blk.p, d_bb_rms_blk.p, d_blk_ph.p, p.TL);
       };
-      if (k.fir_disc && k.fir_tail) {
-        FusedArgs a{};
-        a.n_if = (int)N_if; a.kb_ref = 0;
-        a.out = d_fir.p; a.out_stride = (long long)max_if; a.out_off = 0;
-        a.base = k.base; a.base_stride = H_b + (long long)max_if; a.base_off = H_b;
-        a.dec = debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
-        a.nf = disc_nf; a.bound = disc_bound;
-        a.st = d_state.p; a.part = k.part; a.n_tiles = 8 * k.fir_tiles; a.part_from = k.fir_part_from;
-        a.if_off = bt.if_off; a.if_len = bt.if_len; a.nb = nb;
-        a.wg_blk0 = k.d_tab_slot + (tab_ints - kMaxFusedWg) + kFirBlk0Off;
-        a.mid32 = d_run_ph.p;
-        a.fir_c0 = h_coeff0; a.fir_order = ntaps - 1; a.hA = d_coeff.p;      // (hA: the filter's taps, for the repair of tiles that hold a non-finite sample)
-        if ((size_t)a.n_tiles * 3 * S > d_fused_part.n || (size_t)k.fir_grid * 2 * S > d_run_ph.n) { set_err("internal capacity exceeded (IF filter tiles)"); return; }
-        constexpr int kTile = 64 * 48 + 47 + 127 + 64;
-        hipLaunchKernelGGL((k_ifr_poly4<48, 48, 127, 2, Poly4FirDiscEpi>), dim3(k.fir_grid, S), dim3(256),
-                           sizeof(float2) * (size_t)(((kTile + 127) / 128) * 128 + 4 * 8 * 48), stream, ifbuf, if_stride,
-                           (long long)(64 - H_if), H_if + (int)N_if, d_afrag_fir_fm.p, 0ll, (int)N_if, (float2 *)nullptr, 0ll, 0,
-                           kTile, k.fir_tiles, a, k.fir_tpw, k.fir_rem);
-        if (k.fir_grid > 1)
-          hipLaunchKernelGGL(k_poly5h_heads, dim3((k.fir_grid + 62) / 64, S), dim3(64), 0, stream, a, k.fir_grid, k.fir_tpw, k.fir_rem);
-      } else if (k.fir_disc) {
+      if (p.fir == IfForm::block3_disc) {
         go(k_fm_block3<256, true>);
         hipLaunchKernelGGL(k_disc_heads, dim3((nb + 255) / 256, S), dim3(256), 0, stream, bt, d_blk_ph.p, disc_bound, d_dec.p,
                            (long long)max_if, k.base, H_b + (long long)max_if, H_b, d_bb_mean_blk.p, d_bb_rms_blk.p, d_state.p);
-      }
-      else if (blocked && mode == FMR_MODE_FM) go(k_fm_block3<256, false>);       // (FM with the equaliser behind the filter)
-      else if (blocked && fir_mfma && N_if >= 48) {
+      } else if (p.fir == IfForm::block3) go(k_fm_block3<256, false>);       // (FM with the equaliser behind the filter)
+      else if (p.fir == IfForm::poly4_finish) {
         // AM / DSB / NBFM, 255 or 127 taps: the matrix-core form (call-relative periods of 48 outputs; buffer index m of the
         // kernel's window arithmetic is x[m - (order - (W - 1))], W = taps / 2: the "absolute" index of the buffer's first element
         // is order - W + 1 - H_if)
@@ -2081,18 +2051,16 @@ int fmr_chain::run_if_stage(CallCtx &k) {
         if (ntaps == 255) gof(k_ifr_poly4<48, 48, 255, 1>); else gof(k_ifr_poly4<48, 48, 127, 2>);
         hipLaunchKernelGGL(k_fir_finish<256>, dim3(nb, S), dim3(256), 0, stream, ifbuf, if_stride, H_if, bt, d_coeff.p, ntaps,
                            d_fir.p, (long long)max_if, d_if_rms_blk.p);
-      }
-      else if (blocked) {
+      } else if (p.fir == IfForm::block2) {
         // the 48 kHz modes: blocks of a few hundred samples behind 255 or 2049 taps, nearly every output a head output
         constexpr int TL2 = 1024;
         const size_t lds2 = sizeof(float2) * ((size_t)(ntaps - 1) + TL2) + sizeof(float) * (size_t)ntaps;
         hipLaunchKernelGGL((k_fm_block2<256, TL2>), dim3(nb, S), dim3(256), lds2, stream, ifbuf, if_stride, H_if, bt,
                            d_coeff.p, ntaps, (int)(mode != FMR_MODE_FM), d_fir.p, (long long)max_if, d_if_rms_blk.p);
-      }
-      else
-      hipLaunchKernelGGL(k_fm_block<256>, dim3(nb, S), dim3(256), 0, stream, ifbuf, if_stride, H_if, bt, d_coeff.p,
-                         ntaps, (int)fir_enable, (int)(mode != FMR_MODE_FM), d_fir.p, (long long)max_if,
-                         d_if_rms_blk.p);
+      } else
+        hipLaunchKernelGGL(k_fm_block<256>, dim3(nb, S), dim3(256), 0, stream, ifbuf, if_stride, H_if, bt, d_coeff.p,
+                           ntaps, (int)fir_enable, (int)(mode != FMR_MODE_FM), d_fir.p, (long long)max_if,
+                           d_if_rms_blk.p);
     });
   }
   if (ssb_like) {    // mix the filter output in place; the IF level is measured after it (AmDecode.cpp:114,122,128,136,154)
@@ -2102,15 +2070,15 @@ int fmr_chain::run_if_stage(CallCtx &k) {
     });
     ft_index = (unsigned)((ft_index + (unsigned long long)N_if) % 480u);
   }
-  xin = fir_enable ? d_fir.p : ifbuf;
-  x_stride = fir_enable ? (long long)max_if : if_stride;
-  x_off = fir_enable ? 0 : H_if;
+  const float2 *const xin = k.xin = fir_enable ? d_fir.p : ifbuf;
+  const long long x_stride = k.x_stride = fir_enable ? (long long)max_if : if_stride;
+  const int x_off = k.x_off = fir_enable ? 0 : H_if;
   // ---- IF AGC: Newton multiple shooting over chunks of C_AGC samples (kernels_par.hpp)
-  disc_gain = d_gain.p;      // gain sequence the discriminator multiplies in (nullptr = none)
-  agc_on_side = false; agc_deferred = false; agc_beside_mpf = false;
-  enqueue_agc = nullptr;      // argument: event that gates the side stream (null: a new marker on the main stream)
+  k.disc_gain = d_gain.p;      // gain sequence the discriminator multiplies in (nullptr = none)
+  k.agc_on_side = false; k.agc_deferred = false; agc_beside_mpf = false;
+  k.enqueue_agc = nullptr;      // argument: event that gates the side stream (null: a new marker on the main stream)
   const int agc_nc = (int)((N_if + C_AGC - 1) / C_AGC);
-  if (!iter_on_side)
+  if (!k.iter_on_side)
     hipLaunchKernelGGL(k_iter_begin, dim3(S), dim3(256), 0, stream, d_flags.p,
                        (serial_mode || enable_mpf) ? (float *)nullptr : d_agc_nodes.p,
                        agc_nc, d_state.p, S, (unsigned long long *)d_pll_sync.p, (int)(sizeof(PllSync) / 8), d_pll_tick2.p,
@@ -2157,10 +2125,10 @@ int fmr_chain::run_if_stage(CallCtx &k) {
     hipStream_t as = agc_aside ? side2 : stream;
     // With the PLL on, the side-stream AGC starts only after the PLL's first (Jacobian) integration pass: that
     // pass runs one wave per SIMD and every co-resident AGC wave stretches it (measured 118 -> 160 us).
-    agc_deferred = agc_aside && stereo;
+    k.agc_deferred = agc_aside && stereo;
     const float *const nrm_in = (agc_aside && !fir_enable) ? k.nrm : nullptr;     // (non-null: the front end stored |x|^2, not the IF samples)
     const long long nrm_in_stride = k.nrm_stride;
-    enqueue_agc = [=](hipEvent_t gate) -> int {
+    k.enqueue_agc = [=](hipEvent_t gate) -> int {
     if (agc_aside) {
       if (gate) {
         HIPCHK(hipStreamWaitEvent(side2, gate, 0));
@@ -2199,9 +2167,9 @@ int fmr_chain::run_if_stage(CallCtx &k) {
     if (agc_aside) { HIPCHK(hipEventRecord(ev_agc, side2)); ev_agc_live = true; }
     return FMR_OK;
     };
-    if (agc_aside) { disc_gain = nullptr; agc_on_side = true; }
+    if (agc_aside) { k.disc_gain = nullptr; k.agc_on_side = true; }
     gain_valid = !(agc_aside && !debug_taps);
-    if (!agc_deferred) { if (int rca = enqueue_agc(nullptr)) return rca; }
+    if (!k.agc_deferred) { if (int rca = k.enqueue_agc(nullptr)) return rca; }
   }
   return FMR_OK;
 }
@@ -2377,13 +2345,14 @@ int fmr_chain::run_fm_pll(CallCtx &k, long long base_stride, bool split_mono,
 int fmr_chain::run_fm(CallCtx &k) {
   auto &d_iq = k.d_iq; auto &stride = k.stride; auto &nb = k.nb; auto &d_aud = k.d_aud; auto &astride = k.astride;
   auto &audio_len = k.audio_len; auto &N_in = k.N_in; auto &t_au_len = k.t_au_len; auto &N_if = k.N_if;
-  auto &use_fused = k.use_fused; auto &ifbuf = k.ifbuf; auto &N_au = k.N_au; auto &any_mpf = k.any_mpf;
+  auto &ifbuf = k.ifbuf; auto &N_au = k.N_au; auto &any_mpf = k.any_mpf;
   auto &amA_prev = k.amA_prev; auto &akB_prev = k.akB_prev; auto &an_prev = k.an_prev;
   auto &fused_n_tiles = k.fused_n_tiles; auto &fused_kb_ref = k.fused_kb_ref; auto &bt = k.bt;
-  auto &if_stride = k.if_stride; auto &rms_in_disc = k.rms_in_disc; auto &xin = k.xin; auto &x_stride = k.x_stride;
+  auto &if_stride = k.if_stride; auto &xin = k.xin; auto &x_stride = k.x_stride;
   auto &x_off = k.x_off; auto &disc_gain = k.disc_gain; auto &agc_on_side = k.agc_on_side;
   auto &agc_deferred = k.agc_deferred; auto &enqueue_agc = k.enqueue_agc;
   auto add_halo = [&](void *buf, long long stride_e, int H, long long N, int words = 2) { k.add_halo(buf, stride_e, H, N, words); };
+  const CallPlan &p = k.plan;
   if (any_mpf) {
     timed("mpf", [&] {
       // the chain-and-helpers form (k_mpf4: no barrier inside a chunk)
@@ -2412,32 +2381,32 @@ int fmr_chain::run_fm(CallCtx &k) {
   }
   const long long base_stride = H_b + (long long)max_if;   // pre-de-emphasis buffers
   const long long de_stride = H_a + (long long)max_if;     // de-emphasised copies feeding the audio resampler
-  if (!k.fused_disc && !k.fir_disc)     // (the fused front end's / the IF filter's discriminator epilogue has already written the MPX and the block statistics)
+  if (!p.b_disc && !p.fir_disc())     // (the fused front end's / the IF filter's discriminator epilogue has already written the MPX and the block statistics)
   timed("disc", [&] {
     hipLaunchKernelGGL((k_disc<256, fm_mpx_t>), dim3(nb, S), dim3(256), 0, stream, xin, x_stride, x_off, disc_gain,
                        (long long)max_if, any_mpf ? d_mpf.p : (float2 *)nullptr, (long long)max_if, d_mpf_ok.p, bt,
                        disc_nf, disc_bound, d_dec.p, (long long)max_if, k.base, base_stride, H_b,
-                       d_bb_mean_blk.p, d_bb_rms_blk.p, d_state.p, rms_in_disc ? d_if_rms_blk.p : (float *)nullptr);
+                       d_bb_mean_blk.p, d_bb_rms_blk.p, d_state.p, p.fir == IfForm::none ? d_if_rms_blk.p : (float *)nullptr);
   });
   // "the MPX is there": what the side streams start from.  Behind the fused front end on the decoder's own stream that is
   // the event recorded behind it already (a second marker on the critical stream costs what a small kernel costs).
-  k.ev_mpx = (pipelined && k.fused_disc) ? ev_fe[k.par] : ev_disc;
+  k.ev_mpx = (pipelined && p.b_disc) ? ev_fe[k.par] : ev_disc;
   if (k.ev_mpx == ev_disc) HIPCHK(hipEventRecord(ev_disc, stream));
   if (k.tail_deferred) { k.tail_deferred = false; if (int rc = flush_tail(ev_disc)) return rc; }
   HIPCHK(hipStreamWaitEvent(side, k.ev_mpx, 0));
-  if (use_fused && !pipelined)      // input history for the next call's front end: off the critical path (the next
+  if (p.b == StageB::fused && !pipelined)      // input history for the next call's front end: off the critical path (the next
     timed_on(side, "in_halo", [&] {   // front end waits for this stream's table kernels anyway)
       hipLaunchKernelGGL((k_update_in_halo<256, 0>), dim3(1, S), dim3(256), 0, side, d_in_halo.p, H_in, d_iq, (long long)stride, N_in);
     });
   const size_t stats_ballast = side_ballast();
   timed_on(side, "stats", [&] {     // (fused front end: the block values are summed from its partial sums on the fly)
     hipLaunchKernelGGL(k_stats, dim3(S), dim3(FMR_STATS_THREADS), stats_ballast, side, bt, d_if_rms_blk.p, d_bb_mean_blk.p,
-                       d_bb_rms_blk.p, d_state.p, S, (int)!(pipelined && k.fused_disc),   // (the front-end stage commits its own phase)
-                       (k.fused_disc || k.fir_tail) ? k.part : (const FusedPart *)nullptr, k.fir_tail ? 8 * k.fir_tiles : fused_n_tiles,
-                       k.fir_tail ? 0 : fused_kb_ref);
+                       d_bb_rms_blk.p, d_state.p, S, (int)!(pipelined && p.b_disc),   // (the front-end stage commits its own phase)
+                       (p.b_disc || p.fir_tail()) ? k.part : (const FusedPart *)nullptr, p.fir_tail() ? 8 * p.fir_runs.tiles : fused_n_tiles,
+                       p.fir_tail() ? 0 : fused_kb_ref);
   });
   HIPCHK(hipEventRecord(ev_stats, side));
-  disc_commit_on_side = !(pipelined && k.fused_disc);
+  disc_commit_on_side = !(pipelined && p.b_disc);
   bool fin_on_side = false, fin_covers_all = false;
   // ---------------------------------------------------- audio resampler + tail
   TailCtx t{};
