@@ -15,9 +15,15 @@ Other configs of BASELINE.json (extra lines kept under profiles/, never the head
 Prints ONE JSON line on rank 0: value = whole-job IQ MS/s, plus
   roofline     -- the HBM-bound kernel that reads every IQ sample, timed with HIP events on the chain's own stream
                   inside the timed region; `stage` = the whole FIR+discriminator stage (north star's 60 % target)
-  audio_check  -- RMS error of this chain's audio (its first call, cold start included) against the CPU oracle
+A plain run does only what that line needs: set-up, spin-up, warm-up, the timed steps, --dump-outputs, the line.  With
+--full the same run goes on to measure and check the rest (what is not in a plain line):
+  audio_check  -- RMS error of this chain's audio (its first call, cold start included, and the last timed step) against
+                  the CPU oracle
   cpu_baseline -- the CPU oracle (port of the reference algorithm) on the same workload: 1 core, and N streams on
                   N cores (bounded sample; rank 0, N=1 only)
+  r8b          -- the same step through the reference-equivalent resampler class, a short region of its own (headline only)
+  kernel_ms_per_step, host_enqueue_ms_per_step, roofline.box_streaming_read -- one instrumented step, three calls into an
+                  idle queue and a plain read-only kernel, each after the timed region
 """
 import argparse
 import importlib
@@ -347,7 +353,11 @@ def main():
                          "AM: 8192 x 2048)")
     ap.add_argument("--streams", type=int, default=1, help="independent streams per GPU")
     ap.add_argument("--mode", choices=["fm", "am"], default="fm")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: the audio against "
+                         "the CPU oracle, the CPU baseline, the R8B-class leg, the per-kernel table of an instrumented step, the "
+                         "host's enqueue cost and the box's streaming read (off: the run ends with the result line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--multipath-stages", type=int, default=0,
                     help="configs[3]: FM stereo with the MultipathFilter equaliser (-E N); 0 = configs[1], the headline")
     ap.add_argument("--input-format", choices=["cf32", "s16", "u8"], default="cf32",
@@ -358,7 +368,7 @@ def main():
                          "and a 5 + 20-step region ends before the ramp does; a stream that runs continuously never sees it.  The "
                          "line reports the clock before the spin-up and on either side of the timed region (`clock`)")
     ap.add_argument("--no-region-events", action="store_true",
-                    help="diagnostic: no HIP events inside the timed region (roofline from the instrumented step)")
+                    help="diagnostic: no HIP events inside the timed region (roofline from the instrumented step of --full)")
     ap.add_argument("--api-mode", choices=["batch", "block"], default="batch",
                     help="block: one block per fmr_process() call through host buffers (the drop-in call, PCIe-inclusive; "
                          "never the headline)")
@@ -380,10 +390,10 @@ def main():
                     help="noise per I / Q component of the synthetic FM signal (carrier amplitude 0.3): 1e-3 = 46.5 dB C/N (default), "
                          "1e-2 = 26.5 dB, 3e-2 = 17 dB -- what the PLL's Newton iteration needs on a noisier station (recurrences.pll_newton_rounds)")
     ap.add_argument("--no-r8b-leg", action="store_true",
-                    help="default headline run only: skip the second, short region that times the reference-equivalent (R8B) resampler class")
+                    help="with --full, default headline run only: skip the second, short region that times the reference-equivalent (R8B) resampler class")
     ap.add_argument("--all-configs", action="store_true",
-                    help="after the headline line, print one line each for configs[2] (AM), configs[3] (-E 64), configs[4] "
-                         "(32 streams per GPU) and the mono-station case, each with its own audio check and CPU baseline")
+                    help="implies --full; after the headline line, print one line each for configs[2] (AM), configs[3] (-E 64), "
+                         "configs[4] (32 streams per GPU) and the mono-station case, each with its own audio check and CPU baseline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float64, "
                          "at most 64 MB in all; a larger array as a fixed, seeded sample): audio (streams x samples) and "
@@ -395,6 +405,7 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.cpu_dry_run:
         ap.error("--dump-outputs needs the GPU path (the dry run computes nothing a caller would receive)")
+    args.full = args.full or args.all_configs
 
     global R8B, IF_FILTER
     R8B = args.resampler_class == "r8b"
@@ -469,7 +480,7 @@ def main():
     # audio of the first call (cold start included) on the first blocks of stream 0: checked against the oracle below
     nchk = min(B, 4096 if am else 100)
     n_au_chk = int(alen0[:nchk].sum())
-    audio_chk = audio[0, :n_au_chk].cpu().numpy().copy() if fmt == 0 else None      # every rank checks its own stream 0
+    audio_chk = audio[0, :n_au_chk].cpu().numpy().copy() if fmt == 0 and args.full else None      # every rank checks its own stream 0
     iq_chk = iq[0, :nchk * blk].cpu().numpy().view(np.complex64).reshape(-1).copy() if audio_chk is not None else None
     # Spin-up (round 6): the same step, untimed, until the shader clock has ramped.  What the ramp costs a short region:
     # profiles/r06_clock_ramp.txt (5 / 20 / 40 / 80 warm-up steps in front of 20 timed ones: 0.538 / 0.522 / 0.514 / 0.512 ms).
@@ -512,7 +523,7 @@ def main():
     dt = time.perf_counter() - t0
     mhz.append(fmr.probe_shader_clock(local_rank))
     blocks_done = (1 + spin_steps + args.warmup + args.steps) * B     # stream blocks decoded so far (set-up call + spin-up + warm-up + timed steps)
-    audio_last = audio[0, :int(alen.sum())].cpu().numpy().copy()      # stream 0 of this rank, the last TIMED step
+    audio_last = audio[0, :int(alen.sum())].cpu().numpy().copy() if args.full else None      # stream 0 of this rank, the last TIMED step
     dumped = None
     if args.dump_outputs:      # every stream of this rank, the last TIMED step (the steps below overwrite the buffer)
         dumped = dump_outputs(args.dump_outputs, {"audio": audio[:, :int(alen.sum())].cpu().numpy(), "audio_block_len": alen},
@@ -562,33 +573,34 @@ def main():
         print("[fe stamps] last to end: " + ", ".join("wg %d xcc %d start %.1f dur %.1f end %.1f" % (w, xcc[w], rel_s[w], dur[w], rel_e[w]) for w in late), file=sys.stderr)
         print("[fe stamps] per XCC mean duration: " + ", ".join("%d: %.1f (n %d)" % (x, dur[xcc == x].mean(), int((xcc == x).sum())) for x in sorted(set(xcc.tolist()))), file=sys.stderr)
     st = ch.status(0)
-    # The host's own cost per call.  Inside the timed loop the host runs ahead of the GPU until the chain's eight table
-    # slots are taken and is then paced by the GPU: over a long loop t_enq / steps converges to ms_per_step whatever the
-    # host spends.  Four calls enqueued into an idle queue (fewer than the slots) are not paced by anything.
     ch.enable_kernel_timing(0)
-    t1 = time.perf_counter()
-    for _ in range(3):                        # (the pipelined chain keeps three calls in flight: a fourth would wait for the first)
+    host_unpaced_ms, box_read, ktot = None, 0.0, {}
+    if args.full:
+        # The host's own cost per call.  Inside the timed loop the host runs ahead of the GPU until the chain's eight table
+        # slots are taken and is then paced by the GPU: over a long loop t_enq / steps converges to ms_per_step whatever the
+        # host spends.  Four calls enqueued into an idle queue (fewer than the slots) are not paced by anything.
+        t1 = time.perf_counter()
+        for _ in range(3):                        # (the pipelined chain keeps three calls in flight: a fourth would wait for the first)
+            step()
+        host_unpaced_ms = (time.perf_counter() - t1) / 3 * 1e3
+        ch.synchronize()
+        torch.cuda.synchronize()
+        # what this box delivers to a kernel that only reads the same input buffer (context for the roofline fraction)
+        try:
+            box_read = fmr.probe_read_bandwidth(local_rank, iq.data_ptr(), iq.numel() * iq.element_size())
+        except Exception as e:      # a measurement aid must not take the line down with it
+            print(f"[bench] read-bandwidth probe failed: {e}", file=sys.stderr)
+            box_read = 0.0
+        # one extra, untimed step with every kernel instrumented: the per-kernel table.  The instrumented step
+        # serialises nothing, but its event pairs span the overlap of the chain's three HIP streams: the entries
+        # sum to more than ms_per_step.
+        ch.enable_kernel_timing(1)
         step()
-    host_unpaced_ms = (time.perf_counter() - t1) / 3 * 1e3
-    ch.synchronize()
-    torch.cuda.synchronize()
-    # what this box delivers to a kernel that only reads the same input buffer (context for the roofline fraction)
-    try:
-        box_read = fmr.probe_read_bandwidth(local_rank, iq.data_ptr(), iq.numel() * iq.element_size())
-    except Exception as e:      # a measurement aid must not take the line down with it
-        print(f"[bench] read-bandwidth probe failed: {e}", file=sys.stderr)
-        box_read = 0.0
-    # one extra, untimed step with every kernel instrumented: the per-kernel table.  The instrumented step
-    # serialises nothing, but its event pairs span the overlap of the chain's three HIP streams: the entries
-    # sum to more than ms_per_step.
-    ch.enable_kernel_timing(1)
-    step()
-    ktot = {}
-    for name, ms in ch.kernel_times():
-        a = ktot.setdefault(name, [0.0, 0])
-        a[0] += ms
-        a[1] += 1
-    ch.enable_kernel_timing(0)
+        for name, ms in ch.kernel_times():
+            a = ktot.setdefault(name, [0.0, 0])
+            a[0] += ms
+            a[1] += 1
+        ch.enable_kernel_timing(0)
     per_rank_ms = [round(dt / args.steps * 1e3, 4)]
     if world > 1:
         mine = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -603,8 +615,8 @@ def main():
         assert st.stereo_detected == 1, "PLL did not lock: the timed work is not the stereo path"
     assert int(alen.sum()) > 0 and bool(torch.isfinite(audio[0, :int(alen.sum())]).all())
 
-    # ---- audio of THIS rank's stream 0 against the oracle: the chain's first call (cold start and lock included) and the
-    # last blocks of the last timed step.  Every rank checks its own stream; rank 0 reports all of them.
+    # ---- --full: audio of THIS rank's stream 0 against the oracle: the chain's first call (cold start and lock included) and
+    # the last blocks of the last timed step.  Every rank checks its own stream; rank 0 reports all of them.
     audio_check = {"stereo_locked": int(st.stereo_detected), "pilot_level": round(st.pilot_level, 6)}
     my_errs = [-1.0, -1.0]
     if audio_chk is not None:
@@ -617,7 +629,7 @@ def main():
                             "blocks_checked": nchk, "audio_samples_checked": len(ref), "tolerance": 1e-5,
                             "what": "stream 0 of the rank, first call of this chain (cold start and lock included)"})
         assert err < 1e-5, f"rank {rank}: audio RMS error {err} vs oracle exceeds the north-star tolerance"
-    if fmt == 0 and not am and not args.multipath_stages and B >= 20:
+    if audio_last is not None and fmt == 0 and not am and not args.multipath_stages and B >= 20:
         iq0 = iq[0].cpu().numpy().view(np.complex64).reshape(-1)
         tv = verify_timed_step(iq0, audio_last, alen, B, blk, blocks_done)
         del iq0
@@ -625,7 +637,7 @@ def main():
             audio_check["timed_step"] = tv
             my_errs[1] = tv["rms_err_vs_oracle"]
             assert tv["rms_err_vs_oracle"] < 1e-5, f"rank {rank}, timed step: audio RMS error {tv} vs oracle exceeds the north-star tolerance"
-    if world > 1:
+    if world > 1 and args.full:
         mine = torch.tensor(my_errs, dtype=torch.float64, device=dev)
         alle = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(alle, mine)
@@ -705,14 +717,14 @@ def main():
                                            + " + ".join(k for k in STAGE_KERNELS if k in stage_src),
                                    "ms": round(stage_ms, 5), "achieved": round(stage_achieved, 2),
                                    "frac": round(stage_achieved / HBM_PEAK_GBS, 4),
-                                   "kernels_ms": {k: round(stage_src[k], 5) for k in STAGE_KERNELS if k in stage_src}}},
+                                   "kernels_ms": {k: round(stage_src[k], 5) for k in STAGE_KERNELS if k in stage_src}}} if stage_src else None,
             **({"roofline_mfma": mfma_roofline} if mfma_roofline else {}),
-            "kernel_ms_per_step": {k: round(v, 5) for k, v in kavg.items()},
-            "kernel_ms_note": "from one extra instrumented step; kernels on the chain's three HIP streams overlap, so the entries sum to more than ms_per_step",
-            "host_enqueue_ms_per_step": round(host_unpaced_ms, 4),
-            "host_enqueue_note": "host time per call for three calls enqueued into an idle queue (the host's own cost); in the "
-                                 "timed loop the host is paced by the GPU once it is three calls ahead: " +
-                                 "%.4f ms per step there" % (t_enq / args.steps * 1e3),
+            **({"kernel_ms_per_step": {k: round(v, 5) for k, v in kavg.items()},
+                "kernel_ms_note": "from one extra instrumented step; kernels on the chain's three HIP streams overlap, so the entries sum to more than ms_per_step",
+                "host_enqueue_ms_per_step": round(host_unpaced_ms, 4),
+                "host_enqueue_note": "host time per call for three calls enqueued into an idle queue (the host's own cost); in the "
+                                     "timed loop the host is paced by the GPU once it is three calls ahead: " +
+                                     "%.4f ms per step there" % (t_enq / args.steps * 1e3)} if args.full else {}),
             "cold_first_call_ms": round(cold_ms, 2),
             "clock": {"spinup_ms": args.spinup_ms, "spinup_steps": spin_steps,
                       "shader_mhz": {"before_spinup": round(mhz[0]), "before_timed_region": round(mhz[1]), "after_timed_region": round(mhz[2])},
@@ -730,7 +742,7 @@ def main():
     ch.close()
     headline = (not am and fmt == 0 and S == 1 and not R8B and not IF_FILTER and not args.multipath_stages and not args.no_pilot
                 and args.sigma == 1e-3)
-    if rank == 0 and world == 1 and headline and not args.no_r8b_leg:
+    if args.full and rank == 0 and world == 1 and headline and not args.no_r8b_leg:
         out["r8b"] = r8b_leg(fmr, iq, audio, n, blk, B, local_rank, spinup_ms=args.spinup_ms)
     if world > 1:
         dist.barrier()
@@ -738,7 +750,7 @@ def main():
     if rank == 0:
         # The CPU legs run on rank 0 once the GPU part of every rank is over (the other ranks have left: the host's
         # cores are free), on all the cores of the box again (the rank was pinned to its slice for the timed region).
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             if hasattr(os, "sched_setaffinity"):
                 try:
                     os.sched_setaffinity(0, range(os.cpu_count() or 1))
@@ -829,7 +841,7 @@ OTHER_CONFIGS = [["--mode", "am", "--steps", "20", "--warmup", "3"],            
 def run_other_configs(n_gpus):
     import subprocess
     for fl in OTHER_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__)] + (["--gpus", str(n_gpus)] if n_gpus > 1 else []) + fl
+        cmd = [sys.executable, os.path.abspath(__file__)] + (["--gpus", str(n_gpus)] if n_gpus > 1 else []) + fl + ["--full"]
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_PORT")}
         r = subprocess.run(cmd, capture_output=True, text=True, env=env)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -872,7 +884,7 @@ def block_api(args, ch, iq, blk, fs, rank, world, am):
            "latency_us": {"p50": round(float(np.percentile(lat, 50)), 1), "p90": round(float(np.percentile(lat, 90)), 1),
                           "p99": round(float(np.percentile(lat, 99)), 1), "min": round(float(lat.min()), 1)},
            "roofline": None,
-           "cpu_baseline": None if args.no_cpu_baseline else cpu_baseline(args.mode, args.multipath_stages, 4.0)}
+           "cpu_baseline": cpu_baseline(args.mode, args.multipath_stages, 4.0) if args.full and not args.no_cpu_baseline else None}
     if args.dump_outputs:      # what the last timed call returned
         out["dump_outputs"] = dump_outputs(args.dump_outputs, last, budget=DUMP_BUDGET // world,
                                            suffix=f"_rank{rank}" if world > 1 else "")
@@ -930,7 +942,7 @@ def dry_run(args, rank, world, S, B, blk, pinned=None):
         dist.destroy_process_group()
     if rank == 0:
         # as in main(): the CPU legs on rank 0 once every rank's timed part is over, whatever the world size (bounded here)
-        cpu = None if args.no_cpu_baseline else cpu_baseline("fm", 0, seconds=0.5, max_procs=2)
+        cpu = cpu_baseline("fm", 0, seconds=0.5, max_procs=2) if args.full and not args.no_cpu_baseline else None
         print(json.dumps({"metric": "IQ MS/s (FM stereo, 10 MS/s in), whole job", "value": round(total / dt / 1e6, 3), "unit": "MS/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
                           "ranks_seen": world, "per_rank_ms_per_step": per_rank_ms, "host_thread_pinning": pinned,

@@ -21,7 +21,7 @@ import siggen
 pytestmark = pytest.mark.gpu
 
 fmr = importlib.import_module("airspy-fmradion_amd")
-OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
+OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "out")
 
 
 def rms(a):

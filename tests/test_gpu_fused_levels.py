@@ -47,7 +47,7 @@ def rms(a):
 
 def _report(key, **kw):
     REPORT[key] = kw
-    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "out")
     os.makedirs(out, exist_ok=True)
     with open(os.path.join(out, "parity_report_levels.json"), "w") as f:
         json.dump(REPORT, f, indent=1)

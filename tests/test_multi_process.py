@@ -69,7 +69,7 @@ def test_bench_launch_contract_two_ranks_gloo():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--streams", "2", "--cpu-dry-run"]
+           "--streams", "2", "--cpu-dry-run", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -80,7 +80,7 @@ def test_bench_launch_contract_two_ranks_gloo():
     assert out["config"]["samples_per_step_per_gpu"] == 2 * 2 * 65536
     assert out["value"] == pytest.approx(2 * 2 * 2 * 65536 * 2 / (out["ms_per_step"] * 2 * 1e-3) / 1e6, rel=1e-2)
     assert "DRY RUN" in out["data"]
-    # the CPU baseline is part of an N > 1 line too (rank 0, after the timed region)
+    # with --full the CPU baseline is part of an N > 1 line too (rank 0, after the timed region)
     assert out["cpu_baseline"] is not None and out["cpu_baseline"]["value"] > 0 and out["cpu_baseline"]["cores"] == 1
     assert out["cpu_baseline"]["all_cores"]["cores"] >= 1
 

@@ -1,9 +1,9 @@
-"""Copy the summaries tools/collect_profiles.sh left under gpurun_out/<tag>_* into profiles/, write
+"""Copy the summaries tools/collect_profiles.sh left under out/<tag>_* into profiles/, write
 profiles/<tag>_summary.json and refresh the measured rows of DESIGN.md section 7.   python tools/finish_profiles.py r02"""
 import csv, glob, json, os, re, shutil, subprocess, sys
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-g = lambda *a: os.path.join(root, "gpurun_out", *a)
+g = lambda *a: os.path.join(root, "out", *a)
 prof = lambda *a: os.path.join(root, "profiles", *a)
 os.makedirs(prof(), exist_ok=True)
 

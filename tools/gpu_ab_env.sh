@@ -1,7 +1,7 @@
 #!/bin/bash
 # interleaved A/B on bench.py: variants are "name[@lib][:VAR=val,VAR=val...]" (lib = tools/tmp_<lib>.so, default the library in place)
 #   tools/gpu_ab_env.sh <rounds> "<bench args>" base x:FMR_X_SPARE_ASIDE=1 y@lpl16:FMR_X_CPLL=80
-O=gpurun_out/abenv; mkdir -p $O
+O=out/abenv; mkdir -p $O
 rounds=$1; shift; args=$1; shift
 cp airspy-fmradion_amd/libfmradion_amd.so /tmp/keep.so
 for r in $(seq 1 $rounds); do
@@ -9,7 +9,7 @@ for r in $(seq 1 $rounds); do
     nl=${spec%%:*}; envs=""; [[ "$spec" == *:* ]] && envs=${spec#*:}
     name=${nl%%@*}; lib=""; [[ "$nl" == *@* ]] && lib=${nl#*@}
     if [ -n "$lib" ]; then cp tools/tmp_$lib.so airspy-fmradion_amd/libfmradion_amd.so; else cp /tmp/keep.so airspy-fmradion_amd/libfmradion_amd.so; fi
-    env FMR_FE_STAMPS=1 $(echo $envs | tr ',' ' ') timeout 200 python bench.py $args --no-cpu-baseline --no-r8b-leg > $O/$name.json 2> $O/$name.err < /dev/null
+    env FMR_FE_STAMPS=1 $(echo $envs | tr ',' ' ') timeout 200 python bench.py --full $args --no-cpu-baseline --no-r8b-leg > $O/$name.json 2> $O/$name.err < /dev/null
     timeout 20 python - $name $O <<'PY'
 import json,sys,re
 v,O=sys.argv[1:3]

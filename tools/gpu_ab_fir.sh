@@ -1,12 +1,12 @@
 #!/bin/bash
 # interleaved A/B of prebuilt libraries on bench.py --if-filter:  tools/gpu_ab_fir.sh <rounds> <name> ...
-O=gpurun_out/abfir; mkdir -p $O
+O=out/abfir; mkdir -p $O
 rounds=$1; shift
 cp airspy-fmradion_amd/libfmradion_amd.so /tmp/keep.so
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
     cp tools/tmp_$v.so airspy-fmradion_amd/libfmradion_amd.so
-    timeout 200 python bench.py --if-filter --steps 100 --warmup 10 --no-cpu-baseline < /dev/null > $O/$v.json 2> $O/$v.err
+    timeout 200 python bench.py --full --if-filter --steps 100 --warmup 10 --no-cpu-baseline < /dev/null > $O/$v.json 2> $O/$v.err
     python - $v $O <<'PY'
 import json,sys
 v,O=sys.argv[1:3]

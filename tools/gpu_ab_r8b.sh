@@ -1,12 +1,12 @@
 #!/bin/bash
 # interleaved A/B of prebuilt libraries on the R8B class:  tools/gpu_ab_r8b.sh <rounds> <name> ...
-O=gpurun_out/abr8b; mkdir -p $O
+O=out/abr8b; mkdir -p $O
 rounds=$1; shift
 cp airspy-fmradion_amd/libfmradion_amd.so /tmp/keep.so
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
     cp tools/tmp_$v.so airspy-fmradion_amd/libfmradion_amd.so
-    timeout 200 python bench.py --resampler-class r8b --steps 20 --warmup 3 --no-cpu-baseline < /dev/null > $O/$v.json 2> $O/$v.err
+    timeout 200 python bench.py --full --resampler-class r8b --steps 20 --warmup 3 --no-cpu-baseline < /dev/null > $O/$v.json 2> $O/$v.err
     python - $v $O <<'PY'
 import json,sys
 v,O=sys.argv[1:3]

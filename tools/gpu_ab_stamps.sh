@@ -1,13 +1,13 @@
 #!/bin/bash
 # interleaved A/B of prebuilt libraries (tools/tmp_<name>.so) on the driver's form of the bench (20 steps), with the front end's
 # per-workgroup stamps:  tools/gpu_ab_stamps.sh <rounds> <steps> <name> <name> ...
-O=gpurun_out/abst; mkdir -p $O
+O=out/abst; mkdir -p $O
 rounds=$1; steps=$2; shift; shift
 cp airspy-fmradion_amd/libfmradion_amd.so /tmp/keep.so
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
     cp tools/tmp_$v.so airspy-fmradion_amd/libfmradion_amd.so
-    FMR_FE_STAMPS=1 timeout 200 python bench.py --steps $steps --warmup 5 --no-cpu-baseline --no-r8b-leg > $O/$v.json 2> $O/$v.err < /dev/null
+    FMR_FE_STAMPS=1 timeout 200 python bench.py --full --steps $steps --warmup 5 --no-cpu-baseline --no-r8b-leg > $O/$v.json 2> $O/$v.err < /dev/null
     timeout 20 python - $v $O <<'PY'
 import json,sys
 v,O=sys.argv[1:3]

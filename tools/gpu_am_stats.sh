@@ -1,10 +1,11 @@
 #!/bin/bash
 # per-kernel averages of the AM chain (config 3), rocprofv3 --kernel-trace --stats
-mkdir -p gpurun_out/amstats
+root=$(pwd)
+mkdir -p out/amstats
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/amstats -o am -- python $GRAFT_REPO_ROOT/bench.py --mode am --steps 30 --warmup 3 --no-cpu-baseline > $GRAFT_REPO_ROOT/gpurun_out/amstats/bench.log 2>&1 < /dev/null
-cd $GRAFT_REPO_ROOT
-f=$(find gpurun_out/amstats -name "*kernel_stats.csv" | head -1)
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $root/out/amstats -o am -- python $root/bench.py --mode am --steps 30 --warmup 3 --no-cpu-baseline > $root/out/amstats/bench.log 2>&1 < /dev/null
+cd $root
+f=$(find out/amstats -name "*kernel_stats.csv" | head -1)
 python - "$f" <<'PY'
 import csv,sys
 rows=list(csv.DictReader(open(sys.argv[1])))

@@ -2,7 +2,7 @@
 # Runs every prebuilt harness variant tools/tmp/fused_<name>.bin on the GPU box, twice (box drift check).
 #   gpurun -- 'bash tools/gpu_fused_variants.sh <outdir-tag>'
 tag=${1:-fv}
-out=gpurun_out/$tag
+out=out/$tag
 mkdir -p $out
 for r in 1 2; do
 for b in tools/tmp/fused_*.bin; do

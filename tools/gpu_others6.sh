@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6: where the other configurations stand (AM, IF filter, R8B, one-block host API, config 4)
-O=gpurun_out/others6; mkdir -p $O
-run() { name=$1; shift; timeout 400 python bench.py "$@" --no-cpu-baseline < /dev/null > $O/$name.json 2> $O/$name.err; python - $O/$name.json <<'PY'
+O=out/others6; mkdir -p $O
+run() { name=$1; shift; timeout 400 python bench.py --full "$@" --no-cpu-baseline < /dev/null > $O/$name.json 2> $O/$name.err; python - $O/$name.json <<'PY'
 import json,sys
 try:
     b=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

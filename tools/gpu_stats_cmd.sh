@@ -1,11 +1,12 @@
 #!/bin/bash
 # per-kernel averages (rocprofv3 --kernel-trace --stats) of one bench command line:  tools/gpu_stats_cmd.sh <tag> <bench args...>
+root=$(pwd)
 tag=$1; shift
-mkdir -p gpurun_out/stats_$tag
+mkdir -p out/stats_$tag
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/stats_$tag -o s -- python $GRAFT_REPO_ROOT/bench.py "$@" --no-cpu-baseline > $GRAFT_REPO_ROOT/gpurun_out/stats_$tag/bench.log 2>&1 < /dev/null
-cd $GRAFT_REPO_ROOT
-f=$(find gpurun_out/stats_$tag -name "*kernel_stats.csv" | head -1)
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $root/out/stats_$tag -o s -- python $root/bench.py "$@" --no-cpu-baseline > $root/out/stats_$tag/bench.log 2>&1 < /dev/null
+cd $root
+f=$(find out/stats_$tag -name "*kernel_stats.csv" | head -1)
 python - "$f" <<'PY'
 import csv,sys
 rows=list(csv.DictReader(open(sys.argv[1])))
