@@ -43,6 +43,7 @@ EXPORTS = [
     "fmr_probe_read_bandwidth", "fmr_probe_shader_clock", "fmr_get_kernel_trace",
     "fmr_enable_kernel_timing", "fmr_filter_table", "fmr_fourth_convert", "fmr_design_taps", "fmr_design_taps_class",
     "fmr_host_alloc", "fmr_host_free", "fmr_create_sized", "fmr_get_status_sized",
+    "fmr_create_channelizer", "fmr_resample_blocks", "fmr_resample_blocks_device",
 ]
 
 
@@ -132,6 +133,12 @@ def lib(ab=False):
     L.fmr_synchronize.argtypes = [vp]
     L.fmr_resample.restype = C.c_int
     L.fmr_resample.argtypes = [vp, fp, C.c_size_t, fp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.fmr_create_channelizer.restype = C.c_int
+    L.fmr_create_channelizer.argtypes = [C.POINTER(Config), C.c_size_t, C.POINTER(vp)]
+    L.fmr_resample_blocks.restype = C.c_int
+    L.fmr_resample_blocks.argtypes = [vp, vp, C.c_size_t, u32p, C.c_int, vp, C.c_size_t, u32p]
+    L.fmr_resample_blocks_device.restype = C.c_int
+    L.fmr_resample_blocks_device.argtypes = [vp, vp, C.c_size_t, u32p, C.c_int, vp, C.c_size_t, u32p, C.c_int]
     L.fmr_get_status.restype = C.c_int
     L.fmr_get_status.argtypes = [vp, C.c_int, C.POINTER(Status)]
     L.fmr_get_pps_events.restype = C.c_int
@@ -257,10 +264,15 @@ class Chain:
         self.input_format = int(input_format)
         self.n_streams, self.mode, self.stereo = n_streams, mode, bool(stereo) and mode == MODE_FM
         self.h = C.c_void_p()
-        rc = self._L.fmr_create(C.byref(cfg), C.byref(self.h))
+        rc = self._create(cfg)
         if rc != OK:
             self.h = None
-            raise FmrError(f"fmr_create failed ({rc}): {self._L.fmr_last_error().decode()}")
+            raise FmrError(f"{self._CREATE} failed ({rc}): {self._L.fmr_last_error().decode()}")
+
+    _CREATE = "fmr_create"
+
+    def _create(self, cfg):
+        return self._L.fmr_create(C.byref(cfg), C.byref(self.h))
 
     def close(self):
         if getattr(self, "h", None) and getattr(self, "_L", None) is not None:
@@ -336,7 +348,37 @@ class Chain:
                                      out.ctypes.data_as(C.POINTER(C.c_float)), len(out), C.byref(n)))
         return out[:n.value].copy()
 
+    def resample_blocks(self, iq, block_len):
+        """Front end only, batched (fmr_resample_blocks): iq (n_streams, N) complex64 -- a channelizer: the capture, shape
+        (N,) or (1, N); block_len: consecutive block lengths.  Returns (rows complex64 [n_streams, n], out_len)."""
+        if self.input_format == IQ_CF32:
+            iq = np.ascontiguousarray(np.atleast_2d(iq), dtype=np.complex64)
+        else:   # raw formats: (n_streams, N, 2) interleaved I,Q of the format's integer type
+            iq = np.ascontiguousarray(iq, dtype=_IQ_DTYPE[self.input_format])
+            assert iq.ndim == 3 and iq.shape[2] == 2
+        assert iq.shape[0] == (1 if self.bank else self.n_streams)
+        bl = np.ascontiguousarray(block_len, dtype=np.uint32)
+        assert int(bl.sum()) <= iq.shape[1]
+        ocap = int(bl.sum()) + 64 * len(bl)
+        out = np.zeros((self.n_streams, ocap), dtype=np.complex64)
+        olen = np.zeros(len(bl), dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        self._chk(self._L.fmr_resample_blocks(self.h, iq.ctypes.data, iq.shape[1], bl.ctypes.data_as(u32p), len(bl),
+                                            out.ctypes.data, ocap, olen.ctypes.data_as(u32p)))
+        return out[:, :int(olen.sum())].copy(), olen
+
     # --- device-buffer API (pointers are raw device addresses, e.g. torch .data_ptr()) -------------
+    def resample_blocks_device(self, d_iq_ptr, stream_stride, block_len, d_out_ptr, out_stride, sync=False):
+        """fmr_resample_blocks_device: rows of out_stride complex samples at d_out_ptr; returns out_len (complete after
+        synchronize() or a call with sync=True)."""
+        bl = np.ascontiguousarray(block_len, dtype=np.uint32)
+        olen = np.zeros(len(bl), dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        self._chk(self._L.fmr_resample_blocks_device(self.h, C.c_void_p(d_iq_ptr), stream_stride,
+                                                   bl.ctypes.data_as(u32p), len(bl), C.c_void_p(d_out_ptr), out_stride,
+                                                   olen.ctypes.data_as(u32p), int(sync)))
+        return olen
+
     def process_blocks_device(self, d_iq_ptr, stream_stride, block_len, d_audio_ptr, audio_stride, sync=False):
         """A channel bank reads one row at d_iq_ptr (stream_stride is ignored)."""
         bl = np.ascontiguousarray(block_len, dtype=np.uint32)
@@ -393,3 +435,24 @@ class Chain:
         ms = (C.c_float * cap)()
         n = self._chk(self._L.fmr_get_kernel_times(self.h, names, ms, cap))
         return [(names[i].decode(), ms[i]) for i in range(min(n, cap))]
+
+
+class Channelizer(Chain):
+    """Channelizer (fmr_create_channelizer): one wideband capture in, one row of IQ at output_rate per offset out -- row s
+    is IfResampler(input_rate, output_rate) of the capture shifted down by offsets_hz[s] (the station at +offsets_hz[s]
+    Hz).  output_rate 0 = 384 kHz."""
+
+    _CREATE = "fmr_create_channelizer"
+
+    def __init__(self, input_rate, offsets_hz, output_rate=0.0, resampler_class=RESAMPLER_FAST, max_block_len=65536,
+                 max_blocks=1, device=0):
+        super().__init__(mode=MODE_NONE, input_rate=input_rate, enable_resampler=True, max_block_len=max_block_len,
+                         max_blocks=max_blocks, device=device, output_rate=output_rate, resampler_class=resampler_class,
+                         channel_offsets_hz=list(offsets_hz))
+
+    def _create(self, cfg):
+        return self._L.fmr_create_channelizer(C.byref(cfg), C.sizeof(Config), C.byref(self.h))
+
+    def resample_blocks_device(self, d_iq_ptr, block_len, d_out_ptr, out_stride, sync=False):
+        """The capture (one row) at d_iq_ptr; K rows of out_stride complex samples at d_out_ptr.  Returns out_len."""
+        return super().resample_blocks_device(d_iq_ptr, 0, block_len, d_out_ptr, out_stride, sync)

@@ -301,6 +301,10 @@ struct fmr_chain {
   DevBuf<ChanPhase> d_cb_ph;                // per channel: f mod F, f D mod F
   unsigned cb_forms = 0;                    // FMR_CB_* bits launched since create
   int in_rows() const { return bank ? 1 : S; }   // rows of the input buffers (d_in, d_in_halo)
+  // front end only (fmr_resample_blocks_device): stage B writes row s of this call's IF samples to if_out + s if_out_stride
+  // instead of the chain's IF buffer (nullptr: the IF buffer)
+  float2 *if_out = nullptr;
+  long long if_out_stride = 0;
   int hB_pitch = 0;                    // fractional-phase stage B: row pitch of d_hB (floats)
   DevBuf<float> d_gain, d_dec, d_hA, d_hB, d_coeff, d_atan, d_if_rms_blk, d_bb_mean_blk, d_bb_rms_blk, d_blk_ph;
   DevBuf<double> d_base, d_raw, d_am0, d_am1, d_a10, d_a11, d_pc0, d_pc1, d_audio, d_ahA, d_ahB, d_pilotcut;
@@ -514,8 +518,8 @@ struct fmr_chain {
     }
     return FMR_OK;
   }
-  int init(const fmr_config *c);
-  int check_bank(const fmr_config *c);
+  int init(const fmr_config *c, bool channelizer = false);
+  int check_bank(const fmr_config *c, bool channelizer);
   int upload_bank(const std::vector<float> &fa);
   bool cold = true;                     // no call yet: AGC at its initial gain, PLL unlocked
   int pps_block_base = 0;               // blocks of the call that ran before the part whose PPS events the state holds
@@ -685,7 +689,7 @@ static int first_part_block(const int *if_len, int nb) {
   return 0;
 }
 
-int fmr_chain::init(const fmr_config *c) {
+int fmr_chain::init(const fmr_config *c, bool channelizer) {
   env.load();
   if (env.x_cpll >= C_PLL_MIN) c_pll = env.x_cpll;
   cfg = *c;
@@ -697,8 +701,8 @@ int fmr_chain::init(const fmr_config *c) {
     return FMR_ERR_UNSUPPORTED;
   }
   has_dec = (mode != FMR_MODE_NONE);
-  if (c->channel_offset_hz) {
-    if (int rc = check_bank(c)) return rc;
+  if (c->channel_offset_hz || channelizer) {
+    if (int rc = check_bank(c, channelizer)) return rc;
     bank = true;
     cb_off.assign(c->channel_offset_hz, c->channel_offset_hz + S);
     cb_F = (unsigned long long)c->input_rate;
@@ -1229,31 +1233,47 @@ int fmr_chain::init(const fmr_config *c) {
 // ---- channel bank (fmr_config.channel_offset_hz; DESIGN.md "Channel bank") ----
 // The rules of a bank, checked before the device is opened.  Stage-A shapes in the kernel's range: D = 2 .. 24 (the LDS
 // span of 64 outputs stays under 60 KB) and NA <= 400 (the taps of a group of channels stay in the scalar cache's reach).
+// A channelizer (fmr_create_channelizer) is a bank without a decoder: the same rules, with output_rate as the target
+// rate where a decoder bank has its decoder's rate.
 constexpr int kBankMaxD = 24, kBankMaxNA = 400;
-int fmr_chain::check_bank(const fmr_config *c) {
-  if (c->mode == FMR_MODE_NONE || !c->enable_resampler) {
+int fmr_chain::check_bank(const fmr_config *c, bool channelizer) {
+  if (channelizer) {
+    if (c->mode != FMR_MODE_NONE || !c->enable_resampler) {
+      set_err("channelizer: needs a front-end-only chain with the IF resampler (mode = -1, enable_resampler = 1); "
+              "a decoder bank is fmr_create with channel_offset_hz");
+      return FMR_ERR_UNSUPPORTED;
+    }
+    if (!c->channel_offset_hz) {
+      set_err("channelizer: channel_offset_hz is NULL (it needs n_streams offsets, one per channel)");
+      return FMR_ERR_BAD_ARG;
+    }
+  } else if (c->mode == FMR_MODE_NONE || !c->enable_resampler) {
     set_err("channel bank: needs a decoder chain with the IF resampler (enable_resampler = 1, mode != -1)");
     return FMR_ERR_UNSUPPORTED;
   }
+  const char *const who = channelizer ? "channelizer" : "channel bank";
   if (c->input_format != FMR_IQ_CF32) {
-    set_err("channel bank: input_format must be FMR_IQ_CF32 (convert raw samples on the host)");
+    set_err("%s: input_format must be FMR_IQ_CF32 (convert raw samples on the host)", who);
     return FMR_ERR_UNSUPPORTED;
   }
   if (c->enable_fourth_down) {
-    set_err("channel bank: enable_fourth_down must be 0 (add input_rate / 4 to the offsets instead)");
+    set_err("%s: enable_fourth_down must be 0 (add input_rate / 4 to the offsets instead)", who);
     return FMR_ERR_BAD_ARG;
   }
   const double F = c->input_rate;
   if (!(F >= 1.0 && F < 4294967296.0) || F != std::floor(F)) {
-    set_err("channel bank: input_rate %.6f is not a whole number of hertz (ppm-corrected rates are not supported)", F);
+    set_err("%s: input_rate %.6f is not a whole number of hertz (ppm-corrected rates are not supported)", who, F);
     return FMR_ERR_UNSUPPORTED;
   }
-  const double dec_rate = c->mode == FMR_MODE_FM ? kFmRate : kAmRate;
+  // the rate stage B delivers: the decoder's, or a channelizer's output_rate (0: the FM IF rate, as for any front-end-only chain)
+  const double dec_rate = channelizer ? (c->output_rate > 0 ? c->output_rate : kFmRate)
+                                      : c->mode == FMR_MODE_FM ? kFmRate : kAmRate;
+  const char *const rate_name = channelizer ? "output_rate" : "decoder rate";
   for (int s = 0; s < c->n_streams; s++) {
     const double f = (double)c->channel_offset_hz[s];
     if (std::fabs(f) > 0.5 * (F - dec_rate)) {
-      set_err("channel bank: |channel_offset_hz[%d]| = %.0f Hz exceeds (input_rate - decoder rate) / 2 = %.0f Hz", s,
-              std::fabs(f), 0.5 * (F - dec_rate));
+      set_err("%s: |channel_offset_hz[%d]| = %.0f Hz exceeds (input_rate - %s) / 2 = %.0f Hz", who, s,
+              std::fabs(f), rate_name, 0.5 * (F - dec_rate));
       return FMR_ERR_BAD_ARG;
     }
   }
@@ -1263,8 +1283,8 @@ int fmr_chain::check_bank(const fmr_config *c) {
                                                           : d.design(F, dec_rate, kIfAtten);
   if (!ok) return FMR_OK;     // (init refuses the ratio)
   if (d.D < 2 || d.D > kBankMaxD || d.NA > kBankMaxNA) {
-    set_err("channel bank: stage-A shape D = %d, NA = %d (%.0f -> %.0f Hz) is outside the bank kernel's range "
-            "(D = 2 .. %d, NA <= %d)", d.D, d.D == 1 ? 1 : d.NA, F, dec_rate, kBankMaxD, kBankMaxNA);
+    set_err("%s: stage-A shape D = %d, NA = %d (%.0f -> %.0f Hz) is outside the bank kernel's range "
+            "(D = 2 .. %d, NA <= %d)", who, d.D, d.D == 1 ? 1 : d.NA, F, dec_rate, kBankMaxD, kBankMaxNA);
     return FMR_ERR_UNSUPPORTED;
   }
   return FMR_OK;
@@ -1597,8 +1617,12 @@ int fmr_chain::run_front_end(CallCtx &k) {
         else launch_decim(std::integral_constant<int, 64>{});
       });
     }     // (fused: launched from run_tables)
-    float2 *const ifbuf = k.ifbuf;
-    const long long mid_stride = H_mid + max_mid, if_stride = H_if + max_if;
+    // stage B writes [if_off, if_off + N_if) of every row (every form stores only its own outputs): the chain's IF
+    // buffer, or the caller's rows (front end only, fmr_resample_blocks_device)
+    float2 *const ifbuf = if_out ? if_out : k.ifbuf;
+    const long long mid_stride = H_mid + max_mid, if_stride = if_out ? if_out_stride : H_if + (long long)max_if;
+    const int if_off = if_out ? 0 : H_if;
+    if (if_out) if_valid = false;          // (nothing of this call in the IF buffer: fmr_debug_read 0 has no samples)
     if (p.b != StageB::none && !p.b_in_tables())
       timed_on(fes, "ifr_poly", [&] {
         // the tiled forms: tiles of 64 stage-B periods; the generic forms: 256 outputs per workgroup
@@ -1610,7 +1634,7 @@ int fmr_chain::run_front_end(CallCtx &k) {
         if (p.b == StageB::poly5h)
           hipLaunchKernelGGL((k_ifr_poly5h<48, 125>), dim3(std::min(tiles, n_cu), S), dim3(64 * FMR_POLY5H_WAVES), poly5h_lds,
                              fes, d_mid.p, mid_stride, mA_prev - H_mid, H_mid + count_mid, d_afrag5h.p,
-                             poly5h_nkb, poly5h_inv_scale, rs.TB, kB_prev, (int)N_if, ifbuf, if_stride, H_if,
+                             poly5h_nkb, poly5h_inv_scale, rs.TB, kB_prev, (int)N_if, ifbuf, if_stride, if_off,
                              poly2_tile, tiles);
         else if (p.b == StageB::poly4_am) {
           const long long Pf = kB_prev / 48, Pl = (kB_prev + N_if - 1) / 48;
@@ -1618,22 +1642,22 @@ int fmr_chain::run_front_end(CallCtx &k) {
           hipLaunchKernelGGL((k_ifr_poly4<48, 128, 214>), dim3(std::min(tiles_am, 512), S), dim3(256),
                              sizeof(float2) * (size_t)(((poly4_am_tile + 127) / 128) * 128 + 4 * 8 * 48), fes, d_mid.p,
                              mid_stride, mA_prev - H_mid, H_mid + count_mid, d_afrag.p, kB_prev,
-                             (int)N_if, ifbuf, if_stride, H_if, poly4_am_tile, tiles_am);
+                             (int)N_if, ifbuf, if_stride, if_off, poly4_am_tile, tiles_am);
         } else if (p.b == StageB::poly4)
           hipLaunchKernelGGL((k_ifr_poly4<48, 125, 210>), dim3(std::min(tiles, 512), S), dim3(256),
                              sizeof(float2) * (size_t)(((poly2_tile + 127) / 128) * 128 + 4 * 8 * 48), fes, d_mid.p,
                              mid_stride, mA_prev - H_mid, H_mid + count_mid, d_afrag.p, kB_prev,
-                             (int)N_if, ifbuf, if_stride, H_if, poly2_tile, tiles);
+                             (int)N_if, ifbuf, if_stride, if_off, poly2_tile, tiles);
         else if (p.b == StageB::poly3)
           hipLaunchKernelGGL((k_ifr_poly3<384, 4>), dim3(tiles, S), dim3(384), sizeof(float2) * (size_t)poly2_tile, fes,
                              d_mid.p, mid_stride, mA_prev - H_mid, H_mid + count_mid, d_hBp.p, rs.TB,
                              (int)rs.LB, (int)rs.MB, d_bphi.p, d_boff.p, kB_prev, (int)N_if, ifbuf,
-                             if_stride, H_if, poly2_tile);
+                             if_stride, if_off, poly2_tile);
         else if (p.b == StageB::poly2)
           hipLaunchKernelGGL(k_ifr_poly2<512>, dim3(tiles, S), dim3(512), sizeof(float2) * (size_t)poly2_tile, fes,
                              d_mid.p, mid_stride, mA_prev - H_mid, H_mid + count_mid, d_hB.p, rs.TB,
                              (int)rs.LB, (int)rs.MB, d_bphi.p, d_boff.p, kB_prev, (int)N_if, ifbuf,
-                             if_stride, H_if, poly2_tile);
+                             if_stride, if_off, poly2_tile);
         else if (p.b == StageB::poly_frac) {
           // fractional-phase form: exact integer positions, call-relative on the device
           const __int128 tt = (__int128)kB_prev * rs.MB;
@@ -1642,12 +1666,12 @@ int fmr_chain::run_front_end(CallCtx &k) {
           hipLaunchKernelGGL(k_ifr_poly_frac<BL>, grid, dim3(BL), sizeof(float2) * (span + 4), fes, d_mid.p,
                              mid_stride, nk0 - rs.W() + 1 - (mA_prev - H_mid), H_mid + count_mid, d_hB.p,
                              rs.TB, hB_pitch, rs.LT, (unsigned long long)rs.LB, (unsigned long long)rs.MB, rem0, (int)N_if,
-                             ifbuf, if_stride, H_if);
+                             ifbuf, if_stride, if_off);
         } else
           hipLaunchKernelGGL(k_ifr_poly<BL>, grid, dim3(BL), sizeof(float2) * span, fes, d_mid.p,
                              mid_stride, mA_prev - H_mid, H_mid + count_mid, d_hB.p, rs.TB,
                              (unsigned)rs.LB, (unsigned)rs.MB, (unsigned long long)kB_prev * rs.MB, (int)N_if,
-                             ifbuf, if_stride, H_if);
+                             ifbuf, if_stride, if_off);
       });
     if (N_in > 0 && bank) {      // (one row; the pipelined R8B tail's k_fe_post leaves the input history to this kernel)
       timed_on(fes, "in_halo", [&] {
@@ -2721,21 +2745,19 @@ extern "C" {
 const char *fmr_last_error(void) { return g_err.c_str(); }
 const char *fmr_version(void) { return "fmradion_amd 0.4 (gfx950)"; }
 
-int fmr_create_sized(const fmr_config *cfg, size_t cfg_size, fmr_chain **out) {
-  if (!cfg || !out) return FMR_ERR_BAD_ARG;
-  *out = nullptr;
+// the caller's cfg_size bytes of an fmr_config, the fields its header does not have zero ("as before")
+static int widen_config(const char *fn, const fmr_config *cfg, size_t cfg_size, fmr_config *full) {
   if (cfg_size > sizeof(fmr_config)) {
-    set_err("fmr_create_sized: the caller's fmr_config has %zu bytes, this library's %zu: the caller is newer than the library", cfg_size, sizeof(fmr_config));
+    set_err("%s: the caller's fmr_config has %zu bytes, this library's %zu: the caller is newer than the library", fn, cfg_size, sizeof(fmr_config));
     return FMR_ERR_BAD_ARG;
   }
-  fmr_config full;
-  memset(&full, 0, sizeof full);               // fields the caller's header does not have: 0 = "as before"
-  memcpy(&full, cfg, cfg_size);
-  if (cfg_size >= offsetof(fmr_config, struct_size) + sizeof(unsigned)) full.struct_size = 0;     // (stated through the argument)
-  return fmr_create(&full, out);
+  memset(full, 0, sizeof *full);
+  memcpy(full, cfg, cfg_size);
+  if (cfg_size >= offsetof(fmr_config, struct_size) + sizeof(unsigned)) full->struct_size = 0;     // (stated through the argument)
+  return FMR_OK;
 }
 
-int fmr_create(const fmr_config *cfg, fmr_chain **out) {
+static int create_chain(const fmr_config *cfg, fmr_chain **out, bool channelizer) {
   if (!cfg || !out) return FMR_ERR_BAD_ARG;
   *out = nullptr;
   if (cfg->struct_size != 0 && cfg->struct_size != sizeof(fmr_config)) {
@@ -2744,11 +2766,29 @@ int fmr_create(const fmr_config *cfg, fmr_chain **out) {
     return FMR_ERR_BAD_ARG;
   }
   fmr_chain *c = new fmr_chain();
-  const int rc = c->init(cfg);
+  const int rc = c->init(cfg, channelizer);
   if (rc != FMR_OK) { delete c; return rc; }
   if (c->sync_all() != FMR_OK) { delete c; return FMR_ERR_HIP; }
   *out = c;
   return FMR_OK;
+}
+
+int fmr_create_sized(const fmr_config *cfg, size_t cfg_size, fmr_chain **out) {
+  if (!cfg || !out) return FMR_ERR_BAD_ARG;
+  *out = nullptr;
+  fmr_config full;
+  if (int rc = widen_config("fmr_create_sized", cfg, cfg_size, &full)) return rc;
+  return fmr_create(&full, out);
+}
+
+int fmr_create(const fmr_config *cfg, fmr_chain **out) { return create_chain(cfg, out, false); }
+
+int fmr_create_channelizer(const fmr_config *cfg, size_t cfg_size, fmr_chain **out) {
+  if (!cfg || !out) return FMR_ERR_BAD_ARG;
+  *out = nullptr;
+  fmr_config full;
+  if (int rc = widen_config("fmr_create_channelizer", cfg, cfg_size ? cfg_size : sizeof(fmr_config), &full)) return rc;
+  return create_chain(&full, out, true);
 }
 
 void fmr_destroy(fmr_chain *c) { delete c; }
@@ -2813,6 +2853,19 @@ int fmr_synchronize(fmr_chain *c) {
   if (!c) return FMR_ERR_BAD_ARG;
   if (int rc = c->sync_all()) return rc;
   return c->check_agc_sync();
+}
+
+// how many IF samples per stream every block would produce (if_len[b]) and in all, from a copy of the resampler counter
+// (nothing is advanced)
+static size_t predict_if(const fmr_chain *c, const uint32_t *block_len, int nb, uint32_t *if_len) {
+  ResamplerCounter r = c->rsc;
+  size_t total = 0;
+  for (int b = 0; b < nb; b++) {
+    const size_t n = c->has_rs ? (size_t)r.advance(c->rs, block_len[b]) : (size_t)block_len[b];
+    if (if_len) if_len[b] = (uint32_t)n;
+    total += n;
+  }
+  return total;
 }
 
 // how many doubles per stream the blocks would produce, from copies of the count-law counters (nothing is advanced)
@@ -2913,6 +2966,10 @@ int fmr_resample(fmr_chain *c, const float *iq, size_t n, float *out_iq, size_t 
   if (!c || !n_out || !c->has_rs) return FMR_ERR_BAD_ARG;
   *n_out = 0;
   if (c->has_dec) { set_err("fmr_resample needs a chain created with mode -1 (front end only)"); return FMR_ERR_BAD_ARG; }
+  if (c->bank && c->S > 1) {
+    set_err("fmr_resample: a channelizer of %d channels produces %d IQ rows; use fmr_resample_blocks", c->S, c->S);
+    return FMR_ERR_BAD_ARG;
+  }
   if (n == 0) return FMR_OK;
   if (n > c->max_in) return FMR_ERR_CAPACITY;
   HIPCHK(hipSetDevice(c->cfg.device));
@@ -2926,6 +2983,73 @@ int fmr_resample(fmr_chain *c, const float *iq, size_t n, float *out_iq, size_t 
   HIPCHK(hipStreamSynchronize(c->stream));
   *n_out = (size_t)c->last_n_if;
   return FMR_OK;
+}
+
+// The checks both fmr_resample_blocks forms make before anything is enqueued or any counter moves: a refused call can be
+// retried.  Fills if_len[b] (the IF samples block b produces, the same in every row) and *n_if (their sum).
+static int check_resample_blocks(fmr_chain *c, const void *iq, size_t stream_stride, const uint32_t *block_len, int n_blocks,
+                                 const void *out_iq, size_t out_stride, uint32_t *if_len, size_t *n_if) {
+  if (!c || !iq || !block_len || n_blocks < 1 || !out_iq) return FMR_ERR_BAD_ARG;
+  if (!c->has_rs || c->has_dec) {
+    set_err("fmr_resample_blocks needs a front-end-only chain with the IF resampler (mode -1, enable_resampler)");
+    return FMR_ERR_BAD_ARG;
+  }
+  if (n_blocks > c->max_blocks) { set_err("n_blocks %d outside 1..%d", n_blocks, c->max_blocks); return FMR_ERR_CAPACITY; }
+  size_t N_in = 0;
+  for (int b = 0; b < n_blocks; b++) {
+    if (block_len[b] > c->cfg.max_block_len) { set_err("block %d longer than max_block_len", b); return FMR_ERR_CAPACITY; }
+    N_in += block_len[b];
+  }
+  if (!c->bank && c->S > 1 && stream_stride < N_in) {
+    set_err("stream_stride %zu is shorter than the %zu input samples of a row", stream_stride, N_in);
+    return FMR_ERR_BAD_ARG;
+  }
+  *n_if = predict_if(c, block_len, n_blocks, if_len);
+  if (*n_if > out_stride) {
+    set_err("out_stride %zu too small: these blocks produce %zu IQ samples per row (nothing was processed)", out_stride, *n_if);
+    return FMR_ERR_CAPACITY;
+  }
+  return FMR_OK;
+}
+
+int fmr_resample_blocks(fmr_chain *c, const float *iq, size_t stream_stride, const uint32_t *block_len, int n_blocks,
+                        float *out_iq, size_t out_stride, uint32_t *out_len) {
+  try {
+    std::vector<uint32_t> lens((size_t)std::max(n_blocks, 0));
+    size_t n_if = 0;
+    if (int rc = check_resample_blocks(c, iq, stream_stride, block_len, n_blocks, out_iq, out_stride, lens.data(), &n_if)) return rc;
+    size_t N_in = 0;
+    for (int b = 0; b < n_blocks; b++) N_in += block_len[b];
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t row = (size_t)c->in_bps * N_in;
+    if (N_in)
+      HIPCHK(hipMemcpy2DAsync(c->d_in.p, (size_t)c->in_bps * c->max_in, iq, c->bank ? row : (size_t)c->in_bps * stream_stride, row,
+                              (size_t)c->in_rows(), hipMemcpyHostToDevice, c->stream));
+    if (int rc = c->run(c->d_in.p, c->max_in, block_len, n_blocks, nullptr, 0, nullptr)) return rc;
+    if (n_if)
+      HIPCHK(hipMemcpy2DAsync(out_iq, sizeof(float2) * out_stride, c->d_if.p + c->H_if, sizeof(float2) * (c->H_if + c->max_if),
+                              sizeof(float2) * n_if, (size_t)c->S, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (out_len) for (int b = 0; b < n_blocks; b++) out_len[b] = lens[b];
+    return FMR_OK;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_resample_blocks_device(fmr_chain *c, const float *d_iq, size_t stream_stride, const uint32_t *block_len, int n_blocks,
+                               float *d_out_iq, size_t out_stride, uint32_t *out_len, int sync) {
+  try {
+    std::vector<uint32_t> lens((size_t)std::max(n_blocks, 0));
+    size_t n_if = 0;
+    if (int rc = check_resample_blocks(c, d_iq, stream_stride, block_len, n_blocks, d_out_iq, out_stride, lens.data(), &n_if)) return rc;
+    c->if_out = reinterpret_cast<float2 *>(d_out_iq);
+    c->if_out_stride = (long long)out_stride;
+    const int rc = c->run((const float2 *)d_iq, stream_stride, block_len, n_blocks, nullptr, 0, nullptr);
+    c->if_out = nullptr;
+    if (rc) return rc;
+    if (out_len) for (int b = 0; b < n_blocks; b++) out_len[b] = lens[b];
+    if (sync) return c->sync_all();
+    return FMR_OK;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
 static int fetch_state(fmr_chain *c) {

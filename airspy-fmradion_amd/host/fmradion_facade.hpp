@@ -9,6 +9,8 @@
 //   AmDecoder           include/AmDecode.h:33-103
 //   NbfmDecoder         include/NbfmDecode.h:30-95
 //   FilterParameters    include/FilterParameters.h:29-53
+//   ChannelBank         several decoders over one wideband capture (no reference counterpart)
+//   Channelizer         several IfResamplers over one wideband capture (no reference counterpart)
 //
 // Header-only; link with libfmradion_amd.so.  Every process() call is one
 // fmr_process()/fmr_resample() on a one-stream chain (host buffers in, host
@@ -505,5 +507,52 @@ private:
   std::vector<int32_t> m_offsets;
   size_t m_max_block;
   double m_freq_dev;
+  fmr_chain *m_chain = nullptr;
+};
+
+// Channelizer (fmr_create_channelizer): the IfResampler of several stations out of one wideband capture -- channel k is
+// IfResampler(input_rate, output_rate) (IfResampler.h:35-38) of the capture shifted down by offsets_hz[k], the station
+// at +offsets_hz[k] Hz.  Same default class as IfResampler and ChannelBank.  process() takes the capture block once and
+// returns one IQ vector per channel at output_rate, e.g. for fmr_io::IqFileWriter or a decoder of the caller's own.
+class Channelizer {
+public:
+  Channelizer(double input_rate, const std::vector<int32_t> &offsets_hz, double output_rate = 384000,
+              int resampler_class = FMR_RESAMPLER_R8B, int device = 0, size_t max_block_len = 65536)
+      : m_offsets(offsets_hz), m_max_block(max_block_len) {
+    if (m_offsets.empty()) fmr_detail::fail("Channelizer: no channel");
+    fmr_config cfg{};
+    cfg.device = device; cfg.n_streams = (int)m_offsets.size(); cfg.mode = -1; cfg.input_rate = input_rate;
+    cfg.output_rate = output_rate; cfg.enable_resampler = 1; cfg.resampler_class = resampler_class;
+    cfg.max_block_len = max_block_len; cfg.max_blocks = 1; cfg.channel_offset_hz = m_offsets.data();
+    fmr_detail::check(fmr_create_channelizer(&cfg, sizeof cfg, &m_chain), "fmr_create_channelizer");
+  }
+  ~Channelizer() { fmr_destroy(m_chain); }
+  Channelizer(const Channelizer &) = delete;
+  Channelizer &operator=(const Channelizer &) = delete;
+
+  size_t channels() const { return m_offsets.size(); }
+  int32_t offset_hz(size_t ch) const { return m_offsets.at(ch); }
+
+  // out[k] = what channel k produced from this capture block; blocks longer than the chain's block capacity are
+  // resampled in consecutive pieces
+  void process(const IQSampleVector &in, std::vector<IQSampleVector> &out) {
+    const size_t K = m_offsets.size();
+    out.assign(K, IQSampleVector());
+    IQSampleVector buf;
+    for (size_t off = 0; off < in.size(); off += m_max_block) {
+      const size_t n = std::min(m_max_block, in.size() - off);
+      const size_t stride = n + 64;
+      buf.assign(K * stride, IQSample());
+      uint32_t bl = (uint32_t)n, ol = 0;
+      fmr_detail::check(fmr_resample_blocks(m_chain, reinterpret_cast<const float *>(in.data() + off), n, &bl, 1,
+                                            reinterpret_cast<float *>(buf.data()), stride, &ol),
+                        "fmr_resample_blocks");
+      for (size_t k = 0; k < K; k++) out[k].insert(out[k].end(), buf.begin() + k * stride, buf.begin() + k * stride + ol);
+    }
+  }
+
+private:
+  std::vector<int32_t> m_offsets;
+  size_t m_max_block;
   fmr_chain *m_chain = nullptr;
 };

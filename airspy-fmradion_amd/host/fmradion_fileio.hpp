@@ -11,6 +11,10 @@
 //                   header is valid from the start and refreshed as the data grow (SFC_SET_UPDATE_HEADER_AUTO, :91-93),
 //                   as RF64 ('ds64' chunk) when the data passes 4 GiB -- the outcome of
 //                   SFC_RF64_AUTO_DOWNGRADE (:78-89).
+//   IqFileWriter    the container IqFileReader and FileSource read as FLOAT (FileSource.cpp:491-531): a WAV of
+//                   IEEE float32 frames of 2 channels (I = ch 0, Q = ch 1), the samples' bits as they are; the header is
+//                   valid from the start and refreshed as the data grow, as AudioFileWriter's.  For the IQ rows of a
+//                   Channelizer (fmradion_facade.hpp), to be replayed through the reference's -t filesource.
 //   adjust_gain     the -6 dB of main.cpp:1000-1002;  pps_line: the PPS text record of main.cpp:1084-1111.
 //
 // Host-side plumbing only: nothing here touches the GPU; the decoders take the blocks these classes deliver.
@@ -203,11 +207,14 @@ public:
       if (std::fwrite(m_f32.data(), 4, m_f32.size(), m_fp) != m_f32.size()) { m_error = "write failed"; return false; }
       m_bytes += 4 * m_f32.size();
     }
-    // refresh the header every ~second of audio (and on close): cheap, and the file stays valid
-    if (is_wav() && m_bytes - m_header_at >= (uint64_t)m_rate * m_channels * 2) {
-      if (!write_header()) { m_error = "header update failed"; return false; }
-    }
-    return true;
+    return refresh();
+  }
+  // float32 formats: n floats as they are (IqFileWriter: interleaved I, Q)
+  bool write_f32(const float *v, size_t n) {
+    if (!m_fp || (m_fmt != AudioFormat::RAW_FLOAT32 && m_fmt != AudioFormat::WAV_FLOAT32)) return false;
+    if (n && std::fwrite(v, 4, n, m_fp) != n) { m_error = "write failed"; return false; }
+    m_bytes += 4 * (uint64_t)n;
+    return refresh();
   }
   void close() {
     if (!m_fp) return;
@@ -221,6 +228,13 @@ public:
 
 private:
   bool is_wav() const { return m_fmt == AudioFormat::WAV_INT16 || m_fmt == AudioFormat::WAV_FLOAT32; }
+  // refresh the header every ~second of audio (and on close): cheap, and the file stays valid
+  bool refresh() {
+    if (is_wav() && m_bytes - m_header_at >= (uint64_t)m_rate * m_channels * 2) {
+      if (!write_header()) { m_error = "header update failed"; return false; }
+    }
+    return true;
+  }
   // one layout for both outcomes: 'RIFF' + 'JUNK' placeholder (plain WAV), or 'RF64' + 'ds64' (data >= 4 GiB)
   static constexpr size_t header_size() { return 12 + 8 + 28 + 8 + 16 + 8; }
   static void put32(unsigned char *p, uint32_t v) { p[0] = v; p[1] = v >> 8; p[2] = v >> 16; p[3] = v >> 24; }
@@ -263,6 +277,21 @@ private:
   std::vector<int16_t> m_i16;
   std::vector<float> m_f32;
   std::string m_error;
+};
+
+// IQ samples as a 2-channel IEEE-float WAV (IqFileReader / FileSource FLOAT), through AudioFileWriter's header logic:
+// the interleaved I, Q floats are written bit for bit (no conversion), the header is refreshed every ~second of samples
+class IqFileWriter {
+public:
+  bool open(const std::string &path, unsigned sample_rate) { return m_w.open(path, sample_rate, true, AudioFormat::WAV_FLOAT32); }
+  bool write(const IQSampleVector &samples) {
+    return m_w.write_f32(reinterpret_cast<const float *>(samples.data()), 2 * samples.size());
+  }
+  void close() { m_w.close(); }
+  const std::string &error() const { return m_w.error(); }
+
+private:
+  AudioFileWriter m_w;
 };
 
 // Utility::adjust_gain (include/Utility.h), used at main.cpp:1000-1002 with 0.5 (squelch open) or 0.0

@@ -115,7 +115,7 @@ typedef struct {
    * sample (across calls of any length): a station at +f_s Hz in the capture's spectrum.  Stage A of the IF resampler
    * runs for all channels in one kernel ("ifr_chan") that reads the capture once per group of channels; everything
    * behind it is the plain chain's with n_streams = the number of channels.  Refused at create ("Channel
-   * bank"): front-end-only chains and chains without the resampler, input_format != FMR_IQ_CF32, enable_fourth_down
+   * bank"): front-end-only chains (fmr_create_channelizer builds those) and chains without the resampler, input_format != FMR_IQ_CF32, enable_fourth_down
    * (add F/4 to the offsets instead), an input_rate that is not a whole number of hertz, |f_s| > (input_rate -
    * decoder rate) / 2, and stage-A shapes outside the kernel's range (D = 1, D > 24, NA > 400).  fmr_process takes a
    * bank of one channel only (it returns one audio row).
@@ -162,6 +162,20 @@ int fmr_create(const fmr_config *cfg, fmr_chain **out);
  * size larger than its own.  fmr_create itself can only check the struct_size FIELD, which an older, shorter struct does
  * not contain. */
 int fmr_create_sized(const fmr_config *cfg, size_t cfg_size, fmr_chain **out);
+/* Channelizer: a channel bank without a decoder -- one capture row in, n_streams rows of IQ out at output_rate.  Row s
+ * is IfResampler(input_rate, output_rate) (IfResampler.h:35-38) applied to
+ *     u_s[n] = x[n] exp(-2 pi i ((f_s n) mod F) / F),   F = input_rate,  f_s = channel_offset_hz[s],
+ * n counted from the chain's first sample: the channel bank's definition with nothing behind the resampler.  cfg_size
+ * as for fmr_create_sized (0 = this header's size).  Requires mode = -1, enable_resampler = 1 and channel_offset_hz
+ * (n_streams entries, copied); reads input_rate, output_rate (0 = 384 kHz), resampler_class, max_block_len, max_blocks
+ * and device.  The bank's rules are checked before the device is opened, with output_rate as the target rate:
+ * input_format FMR_IQ_CF32, enable_fourth_down = 0, a whole-hertz input_rate, |f_s| <= (input_rate - output_rate) / 2,
+ * stage-A shape D = 2 .. 24 and NA <= 400.  Stage A runs for all channels in "ifr_chan" (fmr_resampler_info 8 reports
+ * FMR_CB_MODTAP), stage B in the form a plain chain of the same rate and class takes ("ifr_poly*", mask 7).  Output:
+ * fmr_resample_blocks / fmr_resample_blocks_device (fmr_resample for a channelizer of one channel).  A non-finite
+ * capture sample widens as in the bank (its KNOWN LIMITATION above): exact in stage A, a whole banded tile of IF
+ * samples behind k_ifr_poly4. */
+int fmr_create_channelizer(const fmr_config *cfg, size_t cfg_size, fmr_chain **out);
 void fmr_destroy(fmr_chain *c);
 const char *fmr_last_error(void);
 const char *fmr_version(void);
@@ -252,9 +266,25 @@ int fmr_process_blocks_device(fmr_chain *c, const float *d_iq,
 int fmr_synchronize(fmr_chain *c);
 
 /* --- front end only: IfResampler::process (IfResampler.h:35-38).  Valid on a
- * chain created with enable_resampler; bypasses the decoder.  Host buffers. */
+ * chain created with enable_resampler; bypasses the decoder.  Host buffers.  Stream 0 only; a channelizer of more
+ * than one channel is refused (FMR_ERR_BAD_ARG): use fmr_resample_blocks. */
 int fmr_resample(fmr_chain *c, const float *iq, size_t n, float *out_iq,
                  size_t out_cap, size_t *n_out);
+
+/* --- front end only, batched: IfResampler::process (IfResampler.h:35-38) for every row and block, host buffers.  Valid
+ * on any front-end-only chain with the resampler (mode = -1, enable_resampler): a plain chain reads n_streams input rows
+ * of stream_stride samples; a channelizer (fmr_create_channelizer) reads ONE row, the capture (stream_stride is ignored).
+ * out_iq holds n_streams rows of out_stride complex samples (interleaved float pairs); out_len[b] receives the number of
+ * complex samples block b produced, the same in every row.  Semantics = n_blocks successive fmr_resample calls per row.
+ * The output capacity is checked before any state advances: FMR_ERR_CAPACITY leaves the chain as it was, and the call
+ * can be retried with more room. */
+int fmr_resample_blocks(fmr_chain *c, const float *iq, size_t stream_stride, const uint32_t *block_len, int n_blocks,
+                        float *out_iq, size_t out_stride, uint32_t *out_len);
+/* The same on device buffers (HBM in, HBM out), with fmr_process_blocks_device's asynchronous contract: the rows are
+ * complete after fmr_synchronize() or a later call with sync != 0; out_len is filled before the call returns.  Stage B
+ * writes every row straight into d_out_iq (columns [0, out_len sum) of each row, nothing else). */
+int fmr_resample_blocks_device(fmr_chain *c, const float *d_iq, size_t stream_stride, const uint32_t *block_len,
+                               int n_blocks, float *d_out_iq, size_t out_stride, uint32_t *out_len, int sync);
 
 /* --- FourthConverterIQ::process (include/FourthConverterIQ.h:38-82) on host buffers: multiply by the Fs/4 table,
  * `up` selects FourthConverterIQ(true); `index` (in/out, 0..3) is the object's m_index.  Exact (+-1, +-j swaps).
