@@ -43,8 +43,13 @@ EXPORTS = [
     "fmr_probe_read_bandwidth", "fmr_probe_shader_clock", "fmr_get_kernel_trace",
     "fmr_enable_kernel_timing", "fmr_filter_table", "fmr_fourth_convert", "fmr_design_taps", "fmr_design_taps_class",
     "fmr_host_alloc", "fmr_host_free", "fmr_create_sized", "fmr_get_status_sized",
-    "fmr_create_channelizer", "fmr_resample_blocks", "fmr_resample_blocks_device",
+    "fmr_create_channelizer", "fmr_resample_blocks", "fmr_resample_blocks_device", "fmr_create_rds",
+    "fmr_get_rds_groups", "fmr_get_rds_status",
 ]
+# FMR_RDS_* (include/fmradion_amd.h): per-block status of an RDS group
+RDS_OK, RDS_CORRECTED, RDS_BAD, RDS_CPRIME = 0, 1, 2, 4
+# fmr_rds_group as a numpy structured type (24 bytes)
+RDS_GROUP = np.dtype([("sample_index", np.uint64), ("block", np.uint16, 4), ("status", np.uint8, 4), ("reserved", np.uint32)])
 
 
 class FmrError(RuntimeError):
@@ -88,6 +93,7 @@ def build_library(force=False, verbose=False):
     import glob
     deps = sorted(glob.glob(os.path.join(_DIR, "csrc", "*")))      # every header of the translation unit
     deps.append(os.path.join(os.path.dirname(_DIR), "include", "fmradion_amd.h"))
+    deps.append(os.path.join(_DIR, "host", "fmradion_rds.hpp"))          # (the library's RDS entry point compiles it in)
     procs = []
     for path, extra in ((LIB_PATH, []), (LIB_PATH_AB, ["-DFMR_AB_PARTNERS"])):
         if not force and os.path.exists(path) and all(os.path.getmtime(path) >= os.path.getmtime(d) for d in deps):
@@ -223,6 +229,36 @@ def probe_read_bandwidth(device, dev_ptr, nbytes, reps=5):
     return out.value
 
 
+class RdsStatus(C.Structure):
+    _fields_ = [("synced", C.c_int), ("reserved", C.c_int), ("blocks_ok", C.c_uint64), ("blocks_corrected", C.c_uint64),
+                ("blocks_bad", C.c_uint64), ("groups_decoded", C.c_uint64), ("groups_dropped", C.c_uint64),
+                ("injection", C.c_double), ("timing", C.c_double), ("carrier_phase", C.c_double),
+                ("carrier_offset_hz", C.c_double)]
+
+
+def _rds_ok(g, i):
+    return (int(g["status"][i]) & RDS_BAD) == 0
+
+
+def rds_pi(groups):
+    """Programme identification: the most frequent block A among the groups whose block A is good (None: none)."""
+    vals = [int(g["block"][0]) for g in groups if _rds_ok(g, 0)]
+    return max(set(vals), key=vals.count) if vals else None
+
+
+def rds_ps(groups):
+    """Programme service name from the groups 0A / 0B (segment address in block B, two characters in block D); None
+    until all four segments have been seen.  The latest value of each segment wins."""
+    ps, seen = [" "] * 8, 0
+    for g in groups:
+        if not (_rds_ok(g, 1) and _rds_ok(g, 3)) or int(g["block"][1]) >> 12 != 0:
+            continue
+        seg, d = int(g["block"][1]) & 3, int(g["block"][3])
+        ps[2 * seg], ps[2 * seg + 1] = chr(d >> 8), chr(d & 0xFF)
+        seen |= 1 << seg
+    return "".join(ps) if seen == 0xF else None
+
+
 DELAY_3TAPS = np.array([0.0, 1.0, 0.0], dtype=np.float32)  # FilterParameters::delay_3taps_only_iq
 
 
@@ -232,9 +268,12 @@ class Chain:
     def __init__(self, mode=MODE_FM, input_rate=384000.0, enable_resampler=False, fourth_down=False,
                  fmfilter_enable=False, filter_coeff=None, stereo=True, deemphasis_us=50.0, pilot_shift=False,
                  multipath_stages=0, max_block_len=65536, max_blocks=1, n_streams=1, device=0, nbfm_freq_dev=0.0, input_format=0,
-                 output_rate=0.0, resampler_class=RESAMPLER_FAST, in_order=False, ab=False, channel_offsets_hz=None):
+                 output_rate=0.0, resampler_class=RESAMPLER_FAST, in_order=False, ab=False, channel_offsets_hz=None,
+                 enable_rds=False):
         """channel_offsets_hz: a channel bank -- n_streams offsets [Hz] (n_streams may be left at 1: it follows the
-        list); every iq argument then holds one row, the capture, and stream s decodes the station at +offset[s] Hz."""
+        list); every iq argument then holds one row, the capture, and stream s decodes the station at +offset[s] Hz.
+        enable_rds: the chain is made by fmr_create_rds (RDS groups of every stream: rds_groups / rds_status)."""
+        self.enable_rds = bool(enable_rds)
         self._L = lib(ab=bool(ab))
         self.bank = channel_offsets_hz is not None
         if self.bank:
@@ -272,6 +311,12 @@ class Chain:
     _CREATE = "fmr_create"
 
     def _create(self, cfg):
+        if self.enable_rds:
+            self._CREATE = "fmr_create_rds"
+            L = self._L
+            L.fmr_create_rds.restype = C.c_int
+            L.fmr_create_rds.argtypes = [C.POINTER(Config), C.c_size_t, C.POINTER(C.c_void_p)]
+            return L.fmr_create_rds(C.byref(cfg), C.sizeof(Config), C.byref(self.h))
         return self._L.fmr_create(C.byref(cfg), C.byref(self.h))
 
     def close(self):
@@ -396,6 +441,23 @@ class Chain:
     def status(self, stream=0):
         st = Status()
         self._chk(self._L.fmr_get_status(self.h, stream, C.byref(st)))
+        return st
+
+    def rds_groups(self, stream=0, cap=4096):
+        """fmr_get_rds_groups: the groups decoded so far on `stream` (drained from its queue), as an RDS_GROUP array."""
+        out = np.zeros(cap, dtype=RDS_GROUP)
+        L = self._L
+        L.fmr_get_rds_groups.restype = C.c_int
+        L.fmr_get_rds_groups.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        n = self._chk(L.fmr_get_rds_groups(self.h, int(stream), out.ctypes.data, cap))
+        return out[:n].copy()
+
+    def rds_status(self, stream=0):
+        st = RdsStatus()
+        L = self._L
+        L.fmr_get_rds_status.restype = C.c_int
+        L.fmr_get_rds_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(RdsStatus), C.c_size_t]
+        self._chk(L.fmr_get_rds_status(self.h, int(stream), C.byref(st), C.sizeof(RdsStatus)))
         return st
 
     def pps_events(self, stream=0):

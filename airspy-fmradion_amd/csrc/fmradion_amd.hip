@@ -30,6 +30,8 @@
 #include "kernels_fused.hpp"
 #include "kernels_decim16.hpp"
 #include "kernels_chanbank.hpp"
+#include "kernels_rds.hpp"
+#include "../host/fmradion_rds.hpp"
 
 namespace {
 #include "filter_tables.inc"
@@ -300,6 +302,29 @@ struct fmr_chain {
   DevBuf<float2> d_cb_taps;                 // modulated stage-A taps [group][k][FMR_CB_G]
   DevBuf<ChanPhase> d_cb_ph;                // per channel: f mod F, f D mod F
   unsigned cb_forms = 0;                    // FMR_CB_* bits launched since create
+  // ---- RDS (fmr_create_rds; kernels_rds.hpp, host/fmradion_rds.hpp).  The stage runs at the head
+  // of the audio tail (tail_stage): it reads the call's MPX from the base slot and carries everything else in buffers of
+  // its own (MPX history, y1 / y2 rings, RdsState), which only it writes.  The bits of a call go to a slot of a ring of
+  // page-locked host slots; k_signal_host marks the slot filled and the host decoders drain it (rds_drain).
+  bool rds = false;
+  static constexpr int kRdsSlots = 8;
+  int rds_R = 0, rds_maxw = 0;               // ring length (power of two), windows per call
+  size_t rds_slot_stride = 0;                // bytes per stream in a host slot
+  DevBuf<float> d_rds_h1, d_rds_h2, d_rds_xhalo;
+  DevBuf<float2> d_rds_lo, d_rds_y1, d_rds_y2;
+  DevBuf<RdsState> d_rds_state;
+  DevBuf<RdsEst> d_rds_est;
+  DevBuf<RdsRec> d_rds_rec;
+  char *h_rds_slots = nullptr;
+  unsigned long long *h_rds_mark = nullptr;  // calls whose RDS slot is filled
+  long long rds_n = 0, rds_w = 0;            // MPX samples seen, next window
+  unsigned long long rds_seq = 0, rds_drained = 0;
+  double rds_gain = 1.0;                     // |soft symbol| of a unit subcarrier (injection estimate)
+  std::vector<fmr_rds::Decoder> rds_dec;
+  std::vector<RdsSlotHdr> rds_hdr;
+  int rds_init();
+  int rds_stage(const fm_mpx_t *base, long long N, hipStream_t st);
+  void rds_drain();
   int in_rows() const { return bank ? 1 : S; }   // rows of the input buffers (d_in, d_in_halo)
   // front end only (fmr_resample_blocks_device): stage B writes row s of this call's IF samples to if_out + s if_out_stride
   // instead of the chain's IF buffer (nullptr: the IF buffer)
@@ -403,6 +428,10 @@ struct fmr_chain {
     d_agc_G.release(); d_ck_wraps.release(); d_flags.release();
     d_af_nodes.release(); d_af_G.release(); d_af_M.release(); d_af_out.release();
     d_cb_taps.release(); d_cb_ph.release();
+    d_rds_h1.release(); d_rds_h2.release(); d_rds_xhalo.release(); d_rds_lo.release(); d_rds_y1.release(); d_rds_y2.release();
+    d_rds_state.release(); d_rds_est.release(); d_rds_rec.release();
+    if (h_rds_slots) (void)hipHostFree(h_rds_slots);
+    if (h_rds_mark) (void)hipHostFree(h_rds_mark);
     if (h_tab_all) (void)hipHostFree(h_tab_all);
     if (h_marks) (void)hipHostFree(h_marks);
     for (hipEvent_t e : {ev_disc, ev_pll, ev_stats, ev_fin, ev_if}) if (e) (void)hipEventDestroy(e);
@@ -1401,6 +1430,7 @@ int fmr_chain::run(const float2 *d_iq, size_t stride, const uint32_t *block_len,
   // That kernel's successor writes a counter into pinned host memory which is polled here -- hipEventSynchronize
   // would block until the newest signal of the side stream at call time (most of the PREVIOUS call) and stop the
   // host from enqueueing ahead (measured).
+  if (rds) rds_drain();                 // (what the device has finished: keeps the host decoders a call or two behind)
   call_seq++;
   const int slot = (int)(call_seq % kTabSlots);
   if (int rcw = wait_mark(&h_marks[0], call_seq > (unsigned long long)kTabSlots ? call_seq - kTabSlots : 0)) return rcw;
@@ -2581,6 +2611,7 @@ void fmr_chain::tail_channels(const TailCtx &t, hipStream_t st, int ch_base, int
 // The audio tail of one call on stream ts: the channels the PLL stage has not already run beside itself, the DC block's
 // node pass, the output mux, and the joins with what ran beside the decoder stream (statistics, AGC, lock logic).
 int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
+  if (rds) if (int rc = rds_stage(t.base, t.N_if, ts)) return rc;
   const int nch = t.nch, dc_nc = t.dc_nc;
   const long long N_au = t.N_au;
   if (t.mono_enqueued) tail_channels(t, ts, 1, 1);
@@ -2613,6 +2644,129 @@ int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
     if (t.fin_on_side) HIPCHK(hipStreamWaitEvent(ts, ev_fin, 0));
   }
   return FMR_OK;
+}
+
+// ---- RDS stage (kernels_rds.hpp) ----
+// Taps: h1 = Blackman-windowed sinc, cut-off 12 kHz at 384 kHz (flat to 3.7 kHz, -74 dB from 20.3 kHz on, where the
+// 24 kHz output would alias into the RDS band); h2 = the standard's shaping filter cos(pi f td / 4), |f| < 2 / td, whose
+// impulse response is p(t) = cos(4 pi t / td) / (1 - (8 t / td)^2), sampled at 24 kHz over +-2 symbols.
+static double rds_pulse(double t) {
+  const double td = 1.0 / 1187.5, u = 8.0 * t / td;
+  if (std::fabs(std::fabs(u) - 1.0) < 1e-9) return M_PI / 4.0;
+  return std::cos(M_PI * u / 2.0) / (1.0 - u * u);
+}
+int fmr_chain::rds_init() {
+  const size_t need = max_if / kRdsD + 5 * 1300 + 256;
+  rds_R = 1;
+  while ((size_t)rds_R < need) rds_R <<= 1;
+  rds_maxw = (int)(((double)max_if * 19.0) / (double)(kRdsWin * kRdsSym)) + 3;
+  std::vector<float> h1(kRdsNT1), h2(kRdsNT2);
+  double sum = 0.0;
+  std::vector<double> hd(kRdsNT1);
+  for (int k = 0; k < kRdsNT1; k++) {
+    const double x = k - (kRdsNT1 - 1) / 2.0, fc = 12000.0 / kFmRate;
+    const double sinc = 2.0 * fc * (x == 0.0 ? 1.0 : std::sin(2.0 * M_PI * fc * x) / (2.0 * M_PI * fc * x));
+    const double w = 0.42 - 0.5 * std::cos(2.0 * M_PI * k / (kRdsNT1 - 1)) + 0.08 * std::cos(4.0 * M_PI * k / (kRdsNT1 - 1));
+    hd[k] = sinc * w;
+    sum += hd[k];
+  }
+  for (int k = 0; k < kRdsNT1; k++) h1[k] = (float)(hd[k] / sum);
+  const double fs2 = kFmRate / kRdsD, T = 0.5 / 1187.5;
+  for (int j = 0; j < kRdsNT2; j++) h2[j] = (float)rds_pulse((j - (kRdsNT2 - 1) / 2) / fs2);
+  // soft symbol of one isolated symbol of a unit subcarrier: the mixer halves it, z = d / 2 with d(t) = p(t) - p(t - T)
+  auto d = [&](double t) { return rds_pulse(t) - rds_pulse(t - T); };
+  double y0 = 0.0, yT = 0.0;
+  for (int j = 0; j < kRdsNT2; j++) {
+    const double u = (j - (kRdsNT2 - 1) / 2) / fs2;
+    y0 += h2[j] * 0.5 * d(-u);
+    yT += h2[j] * 0.5 * d(T - u);
+  }
+  rds_gain = std::fabs(y0 - yT);
+  std::vector<float2> lo(128);
+  for (int i = 0; i < 128; i++) lo[i] = make_float2((float)std::cos(2.0 * M_PI * i / 128.0), (float)-std::sin(2.0 * M_PI * i / 128.0));
+  int rc;
+  if ((rc = upload(d_rds_h1, h1.data(), h1.size()))) return rc;
+  if ((rc = upload(d_rds_h2, h2.data(), h2.size()))) return rc;
+  if ((rc = upload(d_rds_lo, lo.data(), lo.size()))) return rc;
+  if ((rc = d_rds_xhalo.alloc((size_t)S * kRdsHalo))) return rc;
+  if ((rc = d_rds_y1.alloc((size_t)S * rds_R))) return rc;
+  if ((rc = d_rds_y2.alloc((size_t)S * rds_R))) return rc;
+  if ((rc = d_rds_state.alloc((size_t)S))) return rc;
+  if ((rc = d_rds_est.alloc((size_t)S * rds_maxw))) return rc;
+  if ((rc = d_rds_rec.alloc((size_t)S * (rds_maxw + 1)))) return rc;
+  rds_slot_stride = (sizeof(RdsSlotHdr) + sizeof(RdsRec) * (size_t)rds_maxw + (size_t)kRdsMaxSym * rds_maxw + 63) & ~(size_t)63;
+  HIPCHK(hipHostMalloc((void **)&h_rds_slots, rds_slot_stride * (size_t)S * kRdsSlots, hipHostMallocCoherent));
+  HIPCHK(hipHostMalloc((void **)&h_rds_mark, sizeof(unsigned long long), hipHostMallocCoherent));
+  *h_rds_mark = 0;
+  rds_dec.assign(S, fmr_rds::Decoder());
+  rds_hdr.assign(S, RdsSlotHdr{});
+  return FMR_OK;
+}
+
+// one call's MPX (N samples per stream from the base slot) through the RDS stage, on stream st
+int fmr_chain::rds_stage(const fm_mpx_t *base, long long N, hipStream_t st) {
+  if (N <= 0) return FMR_OK;
+  const long long base_stride = H_b + (long long)max_if;
+  const long long n0 = rds_n, m0 = (n0 + kRdsD - 1) / kRdsD, m1 = (n0 + N + kRdsD - 1) / kRdsD;
+  const int cnt = (int)(m1 - m0);
+  timed_on(st, "rds_mix", [&] {
+    if (cnt > 0) {
+      hipLaunchKernelGGL(k_rds_mix<256>, dim3((cnt + 255) / 256, S), dim3(256), 0, st, base, base_stride, H_b, d_rds_xhalo.p,
+                         n0, m0, cnt, d_rds_h1.p, d_rds_lo.p, d_rds_y1.p, rds_R);
+      hipLaunchKernelGGL(k_rds_mf<256>, dim3((cnt + 255) / 256, S), dim3(256), 0, st, d_rds_y1.p, d_rds_y2.p, rds_R, m0, cnt,
+                         d_rds_h2.p);
+    }
+    hipLaunchKernelGGL(k_rds_halo, dim3(S), dim3(kRdsHalo), 0, st, base, base_stride, H_b, d_rds_xhalo.p, n0, (int)N);
+  });
+  rds_n = n0 + N;
+  // window w is complete once the y2 sample behind its last symbol's second half (+ the interpolator's reach) is there
+  auto ready = [&](long long w) {
+    const double T = (double)((w + 1) * kRdsWin * kRdsSym + kRdsSym) / 19.0;
+    return (long long)std::floor((T + kRdsDelay1) / kRdsD + kRdsDelay2) + 3 <= m1;
+  };
+  int nw = 0;
+  while (nw < rds_maxw && ready(rds_w + nw)) nw++;
+  if (nw == 0) { HIPCHK(hipGetLastError()); return FMR_OK; }
+  const unsigned long long seq = ++rds_seq;
+  if (seq > (unsigned long long)kRdsSlots) {      // the slot's previous call must have been drained
+    if (int rc = wait_mark(h_rds_mark, seq - kRdsSlots)) return rc;
+    rds_drain();
+  }
+  char *slot = h_rds_slots + (size_t)(seq % kRdsSlots) * S * rds_slot_stride;
+  timed_on(st, "rds_sym", [&] {
+    hipLaunchKernelGGL(k_rds_est, dim3(nw, S), dim3(64), 0, st, d_rds_y2.p, rds_R, rds_w, d_rds_est.p, rds_maxw);
+    hipLaunchKernelGGL(k_rds_scan, dim3((S + 63) / 64), dim3(64), 0, st, d_rds_est.p, nw, rds_w, rds_maxw, d_rds_state.p,
+                       d_rds_rec.p, slot, rds_slot_stride, S);
+    hipLaunchKernelGGL(k_rds_bits, dim3(nw, S), dim3(128), 0, st, d_rds_y2.p, rds_R, d_rds_rec.p, rds_maxw, slot,
+                       rds_slot_stride);
+  });
+  hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, st, h_rds_mark, seq);
+  rds_w += nw;
+  HIPCHK(hipGetLastError());
+  return FMR_OK;
+}
+
+// the filled slots, in call order, through the host decoders (never blocks)
+void fmr_chain::rds_drain() {
+  while (rds_drained < rds_seq && __atomic_load_n(h_rds_mark, __ATOMIC_ACQUIRE) > rds_drained) {
+    const unsigned long long seq = ++rds_drained;
+    const char *slot = h_rds_slots + (size_t)(seq % kRdsSlots) * S * rds_slot_stride;
+    for (int s = 0; s < S; s++) {
+      const char *sl = slot + (size_t)s * rds_slot_stride;
+      RdsSlotHdr h;
+      memcpy(&h, sl, sizeof h);
+      const RdsRec *rec = reinterpret_cast<const RdsRec *>(sl + sizeof(RdsSlotHdr));
+      const unsigned char *bits = reinterpret_cast<const unsigned char *>(sl + sizeof(RdsSlotHdr) + sizeof(RdsRec) * (size_t)rds_maxw);
+      for (int w = 0; w < h.nw && w < rds_maxw; w++) {
+        const RdsRec r = rec[w];
+        for (int t = 0; t < r.count && t < kRdsMaxSym; t++) {
+          const long long pos = (r.k_first + t) * kRdsSym + r.tau;       // [U]
+          rds_dec[s].push(bits[(size_t)w * kRdsMaxSym + t], pos > 0 ? (uint64_t)((pos + 9) / 19) : 0);
+        }
+      }
+      rds_hdr[s] = h;
+    }
+  }
 }
 
 // Pipelined chain: enqueue the tail stage of the last decoded call on the tail stream, behind `gate` (the front end of
@@ -2757,7 +2911,7 @@ static int widen_config(const char *fn, const fmr_config *cfg, size_t cfg_size, 
   return FMR_OK;
 }
 
-static int create_chain(const fmr_config *cfg, fmr_chain **out, bool channelizer) {
+static int create_chain(const fmr_config *cfg, fmr_chain **out, bool channelizer, bool rds = false) {
   if (!cfg || !out) return FMR_ERR_BAD_ARG;
   *out = nullptr;
   if (cfg->struct_size != 0 && cfg->struct_size != sizeof(fmr_config)) {
@@ -2766,7 +2920,9 @@ static int create_chain(const fmr_config *cfg, fmr_chain **out, bool channelizer
     return FMR_ERR_BAD_ARG;
   }
   fmr_chain *c = new fmr_chain();
-  const int rc = c->init(cfg, channelizer);
+  c->rds = rds;
+  int rc = c->init(cfg, channelizer);
+  if (rc == FMR_OK && rds) rc = c->rds_init();
   if (rc != FMR_OK) { delete c; return rc; }
   if (c->sync_all() != FMR_OK) { delete c; return FMR_ERR_HIP; }
   *out = c;
@@ -3271,6 +3427,55 @@ int fmr_get_kernel_times(fmr_chain *c, const char **names, float *ms, int cap) {
     n++;
   }
   return n;
+}
+
+int fmr_create_rds(const fmr_config *cfg, size_t cfg_size, fmr_chain **out) {
+  if (!cfg || !out) return FMR_ERR_BAD_ARG;
+  *out = nullptr;
+  fmr_config full;
+  if (int rc = widen_config("fmr_create_rds", cfg, cfg_size ? cfg_size : sizeof(fmr_config), &full)) return rc;
+  // the rules of the option, before the device is opened
+  if (full.mode != FMR_MODE_FM) {
+    set_err("enable_rds: the RDS decoder reads the MPX of an FM chain (mode FMR_MODE_FM); mode %d %s", full.mode,
+            full.mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no MPX" : "has no RDS");
+    return FMR_ERR_UNSUPPORTED;
+  }
+  return create_chain(&full, out, false, true);
+}
+
+int fmr_get_rds_groups(fmr_chain *c, int stream, fmr_rds_group *groups, int cap) {
+  if (!c || stream < 0 || stream >= c->S || cap < 0 || (cap > 0 && !groups)) return FMR_ERR_BAD_ARG;
+  if (!c->rds) { set_err("fmr_get_rds_groups: the chain was created without the RDS decoder (fmr_create_rds)"); return FMR_ERR_BAD_ARG; }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    c->rds_drain();
+    fmr_rds::Decoder &d = c->rds_dec[stream];
+    if (cap == 0) return (int)d.queued();
+    return (int)d.pop(groups, (size_t)cap);
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_get_rds_status(fmr_chain *c, int stream, fmr_rds_status *st, size_t st_size) {
+  if (!c || !st || stream < 0 || stream >= c->S) return FMR_ERR_BAD_ARG;
+  if (!c->rds) { set_err("fmr_get_rds_status: the chain was created without the RDS decoder (fmr_create_rds)"); return FMR_ERR_BAD_ARG; }
+  HIPCHK(hipSetDevice(c->cfg.device));
+  if (int rc = c->sync_all()) return rc;
+  c->rds_drain();
+  const fmr_rds::Decoder &d = c->rds_dec[stream];
+  const RdsSlotHdr &h = c->rds_hdr[stream];
+  fmr_rds_status full{};
+  full.synced = d.synced();
+  full.blocks_ok = d.blocks_ok();
+  full.blocks_bad = d.blocks_bad();
+  full.groups_decoded = d.groups_decoded();
+  full.groups_dropped = d.groups_dropped();
+  full.injection = h.level > 0.f ? std::sqrt((double)h.level) / c->rds_gain : 0.0;
+  full.timing = h.timing_frac;
+  full.carrier_phase = h.theta;
+  full.carrier_offset_hz = h.freq_hz;
+  memcpy(st, &full, st_size < sizeof full ? st_size : sizeof full);
+  return FMR_OK;
 }
 
 int fmr_filter_table(const char *name, const void **data, int *is_double) {

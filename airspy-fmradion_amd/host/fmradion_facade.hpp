@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../../include/fmradion_amd.h"
+#include "fmradion_rds.hpp"
 
 using IQSample = std::complex<float>;
 using IQSampleVector = std::vector<IQSample>;
@@ -66,14 +67,23 @@ inline void fail(const char *what) {
   std::exit(1);
 #endif
 }
-inline fmr_chain *make(const fmr_config &cfg0) {
+inline fmr_chain *make(const fmr_config &cfg0, bool rds = false) {
   fmr_config cfg = cfg0;
   cfg.struct_size = sizeof(fmr_config);      // the header this translation unit was built against
   cfg.in_order = 1;                          // every facade call goes through host buffers and synchronises: nothing for the
                                              // pipelined chain to overlap (include/fmradion_amd.h)
   fmr_chain *c = nullptr;
-  check(fmr_create(&cfg, &c), "fmr_create");
+  if (rds) check(fmr_create_rds(&cfg, sizeof cfg, &c), "fmr_create_rds");
+  else check(fmr_create(&cfg, &c), "fmr_create");
   return c;
+}
+// the RDS groups of one stream decoded so far (drained from its queue), also collected into `station`
+inline std::vector<fmr_rds_group> rds_groups(fmr_chain *c, int stream, fmr_rds::Station &station) {
+  std::vector<fmr_rds_group> out;
+  fmr_rds_group buf[256];
+  for (int n; (n = fmr_get_rds_groups(c, stream, buf, 256)) > 0;) out.insert(out.end(), buf, buf + n);
+  for (const auto &g : out) station.add(g);
+  return out;
 }
 }  // namespace fmr_detail
 
@@ -209,8 +219,19 @@ public:
     fmr_destroy(m_chain);
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
-    m_chain = fmr_detail::make(m_cfg);
+    m_chain = fmr_detail::make(m_cfg, m_rds);
   }
+
+  // RDS (no counterpart in the reference; fmr_create_rds): re-creates the chain with the RDS decoder, before the first
+  // process().  get_rds_groups() drains the groups decoded so far; rds_station() holds PI / PTY / PS / RadioText.
+  void enable_rds() {
+    if (m_started) fmr_detail::fail("FmDecoder::enable_rds: after the first process()");
+    m_rds = true;
+    fmr_destroy(m_chain);
+    m_chain = fmr_detail::make(m_cfg, true);
+  }
+  std::vector<fmr_rds_group> get_rds_groups() { return fmr_detail::rds_groups(m_chain, 0, m_station); }
+  const fmr_rds::Station &rds_station() { get_rds_groups(); return m_station; }
 
   // Latency for throughput: hold back `blocks` - 1 calls and decode `blocks` blocks in ONE batched call.  process()
   // then returns an empty vector ("nothing yet": the contract of FmDecode.cpp:89-92,185-188, which main.cpp:981-984
@@ -230,7 +251,7 @@ public:
       if (m_started) fmr_detail::fail("FmDecoder::set_batch_blocks: a larger batch than the chain was created for, after the first process()");
       fmr_destroy(m_chain);
       m_cfg.max_blocks = (int)blocks;
-      m_chain = fmr_detail::make(m_cfg);
+      m_chain = fmr_detail::make(m_cfg, m_rds);
       m_capacity = blocks;
     }
     m_batch = blocks;
@@ -324,6 +345,8 @@ private:
   }
   fmr_config m_cfg{};
   fmr_chain *m_chain = nullptr;
+  bool m_rds = false;
+  fmr_rds::Station m_station;
   bool m_stereo;
   bool m_pps_fetched = true;
   std::vector<PilotPhaseLock::PpsEvent> m_pps;
@@ -452,6 +475,7 @@ public:
     cfg.stereo = stereo; cfg.deemphasis_us = deemphasis; cfg.pilot_shift = pilot_shift; cfg.multipath_stages = multipath_stages;
     cfg.max_block_len = max_block_len; cfg.max_blocks = 1; cfg.nbfm_freq_dev = nbfm_freq_dev;
     cfg.channel_offset_hz = m_offsets.data();
+    m_cfg = cfg;
     m_chain = fmr_detail::make(cfg);
   }
   ~ChannelBank() { fmr_destroy(m_chain); }
@@ -460,6 +484,19 @@ public:
 
   size_t channels() const { return m_offsets.size(); }
   int32_t offset_hz(size_t ch) const { return m_offsets.at(ch); }
+
+  // RDS of every channel (fmr_create_rds): re-creates the chain with the RDS decoder, before the first process()
+  void enable_rds() {
+    fmr_destroy(m_chain);
+    m_cfg.channel_offset_hz = m_offsets.data();
+    m_chain = fmr_detail::make(m_cfg, true);
+    m_stations.assign(m_offsets.size(), fmr_rds::Station());
+  }
+  std::vector<fmr_rds_group> get_rds_groups(size_t ch) {
+    if (ch >= m_offsets.size() || m_stations.empty()) fmr_detail::fail("ChannelBank: no RDS on this channel (enable_rds)");
+    return fmr_detail::rds_groups(m_chain, (int)ch, m_stations[ch]);
+  }
+  const fmr_rds::Station &rds_station(size_t ch) { get_rds_groups(ch); return m_stations[ch]; }
 
   // audio[k] = what channel k produced from this capture block (empty = "nothing yet"); blocks longer than the chain's
   // block capacity are decoded in consecutive pieces
@@ -507,6 +544,8 @@ private:
   std::vector<int32_t> m_offsets;
   size_t m_max_block;
   double m_freq_dev;
+  fmr_config m_cfg{};
+  std::vector<fmr_rds::Station> m_stations;
   fmr_chain *m_chain = nullptr;
 };
 

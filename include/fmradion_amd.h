@@ -345,6 +345,53 @@ int fmr_probe_shader_clock(int device, double *mhz);
  * e.g. "jj1bdx_fm_384kHz_medium"; returns the length, *is_double tells the type. */
 int fmr_filter_table(const char *name, const void **data, int *is_double);
 
+/* --- RDS (no counterpart in the reference).  An FM chain created with fmr_create_rds decodes the
+ * RDS data on the 57 kHz subcarrier of every stream's MPX (every channel of a bank): a device stage behind the
+ * discriminator estimates symbol timing and carrier phase from the RDS signal itself (no pilot needed; in phase or in
+ * quadrature with 3 x pilot) and hands the bits to a host decoder per stream (airspy-fmradion_amd/host/fmradion_rds.hpp:
+ * 26-bit blocks, checkword of g(x) = x^10+x^8+x^7+x^5+x^4+x^3+1 plus the offset words A 0x0FC, B 0x198, C 0x168,
+ * C' 0x350, D 0x1B4, acquisition on two consecutive valid syndromes, loss of synchronisation after 8 bad blocks in a row,
+ * error detection only).  The decoded groups do not depend on how the input is cut into blocks and calls.
+ * One RDS group: four 16-bit blocks in the order A, B, C (or C'), D, a status per block and the absolute 384 kHz MPX
+ * sample index (counted from the chain's first sample) at which the group's first bit starts. */
+enum {
+  FMR_RDS_OK = 0,             /* the block's syndrome is its position's offset */
+  FMR_RDS_CORRECTED = 1,      /* (reserved: burst correction is not built) */
+  FMR_RDS_BAD = 2,            /* syndrome mismatch: the block's 16 bits are as received */
+  FMR_RDS_CPRIME = 4          /* block 3 carried offset C' (version-B groups) instead of C */
+};
+typedef struct {
+  uint64_t sample_index;
+  uint16_t block[4];
+  uint8_t status[4];          /* FMR_RDS_OK | FMR_RDS_BAD, | FMR_RDS_CPRIME on block 3 */
+  uint32_t reserved;
+} fmr_rds_group;
+typedef struct {
+  int synced;                 /* 1: block-synchronised after the last bit decoded */
+  int reserved;
+  uint64_t blocks_ok, blocks_corrected, blocks_bad;
+  uint64_t groups_decoded;    /* groups assembled in synchronisation since create */
+  uint64_t groups_dropped;    /* ... lost because the stream's queue (256 groups) was full: drain it with fmr_get_rds_groups */
+  double injection;           /* estimated amplitude of the RDS subcarrier in MPX units (1.0 = 75 kHz deviation) */
+  double timing;              /* symbol timing: where a symbol starts within its period [symbols, 0 .. 1) */
+  double carrier_phase;       /* carrier phase estimate [rad] (modulo pi: BPSK) */
+  double carrier_offset_hz;   /* tracked offset of the subcarrier from 57 kHz [Hz] */
+} fmr_rds_status;
+
+/* fmr_create with the RDS decoder on (cfg_size as for fmr_create_sized, 0 = this header's size).  FMR_MODE_FM chains of
+ * every shape fmr_create accepts: with or without the resampler (either class), stereo or mono, -f, the equaliser,
+ * ppm-corrected rates, pipelined or in_order, channel banks (a decoder per channel).  Any other mode and front-end-only
+ * chains (mode = -1, the channelizer's shape) are refused with FMR_ERR_UNSUPPORTED before the device is opened.  The
+ * audio and fmr_status are those of the same chain made by fmr_create: the stage only reads the MPX. */
+int fmr_create_rds(const fmr_config *cfg, size_t cfg_size, fmr_chain **out);
+/* Drain up to cap groups (oldest first) from stream `stream`'s queue; returns the count.  cap = 0: the number queued.
+ * Synchronises like the other getters: after it, the groups of every call issued so far are in the queue (on the
+ * asynchronous device path they are complete, like the audio, after fmr_synchronize).  FMR_ERR_BAD_ARG on a chain
+ * created without RDS. */
+int fmr_get_rds_groups(fmr_chain *c, int stream, fmr_rds_group *groups, int cap);
+/* Counters and estimates of stream `stream` (synchronises); st_size = sizeof(fmr_rds_status) as the caller knows it. */
+int fmr_get_rds_status(fmr_chain *c, int stream, fmr_rds_status *st, size_t st_size);
+
 #ifdef __cplusplus
 }
 #endif
