@@ -45,7 +45,11 @@ EXPORTS = [
     "fmr_host_alloc", "fmr_host_free", "fmr_create_sized", "fmr_get_status_sized",
     "fmr_create_channelizer", "fmr_resample_blocks", "fmr_resample_blocks_device", "fmr_create_rds",
     "fmr_get_rds_groups", "fmr_get_rds_status",
+    "fmr_spectrum_create", "fmr_spectrum_destroy", "fmr_spectrum_process", "fmr_spectrum_process_device",
+    "fmr_spectrum_synchronize", "fmr_spectrum_read", "fmr_spectrum_reset", "fmr_find_stations",
 ]
+# FMR_WINDOW_* (include/fmradion_amd.h): windows of the band spectrum
+WINDOW_HANN, WINDOW_RECT, WINDOW_BLACKMAN_HARRIS = 0, 1, 2
 # FMR_RDS_* (include/fmradion_amd.h): per-block status of an RDS group
 RDS_OK, RDS_CORRECTED, RDS_BAD, RDS_CPRIME = 0, 1, 2, 4
 # fmr_rds_group as a numpy structured type (24 bytes)
@@ -86,6 +90,27 @@ class Status(C.Structure):
 class PpsEvent(C.Structure):
     _fields_ = [("pps_index", C.c_uint64), ("sample_index", C.c_uint64), ("block_position", C.c_double),
                 ("block", C.c_uint32), ("stream", C.c_uint32)]
+
+
+class SpectrumConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("device", C.c_int), ("n_rows", C.c_int), ("input_rate", C.c_double),
+                ("input_format", C.c_int), ("fft_size", C.c_int), ("hop", C.c_int), ("window", C.c_int),
+                ("max_call_len", C.c_size_t)]
+
+
+class SpectrumInfo(C.Structure):
+    _fields_ = [("segments", C.c_uint64), ("segments_skipped", C.c_uint64), ("first_segment", C.c_uint64),
+                ("samples_seen", C.c_uint64), ("bin_hz", C.c_double), ("enbw_hz", C.c_double)]
+
+
+class StationRule(C.Structure):
+    _fields_ = [("raster_hz", C.c_int32), ("raster_offset_hz", C.c_int32), ("bandwidth_hz", C.c_int32),
+                ("max_abs_offset_hz", C.c_int32), ("threshold_db", C.c_double), ("floor_percentile", C.c_double)]
+
+
+class Station(C.Structure):
+    _fields_ = [("offset_hz", C.c_int32), ("reserved", C.c_int32), ("level_db", C.c_double), ("snr_db", C.c_double),
+                ("centroid_hz", C.c_double)]
 
 
 def build_library(force=False, verbose=False):
@@ -165,6 +190,22 @@ def lib(ab=False):
     L.fmr_design_taps_class.argtypes = [C.c_double, C.c_double, C.c_int, C.c_int, dp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.fmr_filter_table.restype = C.c_int
     L.fmr_filter_table.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int)]
+    L.fmr_spectrum_create.restype = C.c_int
+    L.fmr_spectrum_create.argtypes = [C.POINTER(SpectrumConfig), C.c_size_t, C.POINTER(vp)]
+    L.fmr_spectrum_destroy.restype = None
+    L.fmr_spectrum_destroy.argtypes = [vp]
+    L.fmr_spectrum_process.restype = C.c_int
+    L.fmr_spectrum_process.argtypes = [vp, vp, C.c_size_t, C.c_size_t]
+    L.fmr_spectrum_process_device.restype = C.c_int
+    L.fmr_spectrum_process_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int]
+    L.fmr_spectrum_synchronize.restype = C.c_int
+    L.fmr_spectrum_synchronize.argtypes = [vp]
+    L.fmr_spectrum_read.restype = C.c_int
+    L.fmr_spectrum_read.argtypes = [vp, C.c_int, C.c_int, dp, C.c_size_t, C.POINTER(SpectrumInfo)]
+    L.fmr_spectrum_reset.restype = C.c_int
+    L.fmr_spectrum_reset.argtypes = [vp]
+    L.fmr_find_stations.restype = C.c_int
+    L.fmr_find_stations.argtypes = [dp, C.c_int, C.c_double, C.POINTER(StationRule), C.POINTER(Station), C.c_int]
     _libs[ab] = L
     return L
 
@@ -518,3 +559,97 @@ class Channelizer(Chain):
     def resample_blocks_device(self, d_iq_ptr, block_len, d_out_ptr, out_stride, sync=False):
         """The capture (one row) at d_iq_ptr; K rows of out_stride complex samples at d_out_ptr.  Returns out_len."""
         return super().resample_blocks_device(d_iq_ptr, 0, block_len, d_out_ptr, out_stride, sync)
+
+
+def find_stations(psd, input_rate, raster_hz=100000, raster_offset_hz=0, bandwidth_hz=200000, max_abs_offset_hz=0,
+                  threshold_db=10.0, floor_percentile=0.0, cap=None):
+    """fmr_find_stations (host only): the stations of a spectrum in fftshift order (Spectrum.psd), as a list of dicts
+    {offset_hz, level_db, snr_db, centroid_hz} in ascending offset order.  cap: write at most cap (None: all)."""
+    psd = np.ascontiguousarray(psd, dtype=np.float64)
+    rule = StationRule(int(raster_hz), int(raster_offset_hz), int(bandwidth_hz), int(max_abs_offset_hz),
+                       float(threshold_db), float(floor_percentile))
+    L = lib()
+    dp = C.POINTER(C.c_double)
+    n = L.fmr_find_stations(psd.ctypes.data_as(dp), len(psd), float(input_rate), C.byref(rule), None, 0)
+    if n < 0:
+        raise FmrError(f"fmr_find_stations failed ({n}): {L.fmr_last_error().decode()}")
+    k = n if cap is None else min(n, int(cap))
+    out = (Station * max(k, 1))()
+    n2 = L.fmr_find_stations(psd.ctypes.data_as(dp), len(psd), float(input_rate), C.byref(rule), out, k)
+    assert n2 == n
+    return [{"offset_hz": int(st.offset_hz), "level_db": st.level_db, "snr_db": st.snr_db, "centroid_hz": st.centroid_hz}
+            for st in out[:k]]
+
+
+class Spectrum:
+    """Welch power spectrum of n_rows IQ rows on the GPU (fmr_spectrum_*): mean PSD and peak hold per row, density-scaled,
+    in fftshift order (element k = bin (k - N/2) F / N Hz)."""
+
+    def __init__(self, input_rate, fft_size=8192, hop=0, window=WINDOW_HANN, n_rows=1, input_format=IQ_CF32,
+                 max_call_len=1 << 20, device=0):
+        self._L = lib()
+        cfg = SpectrumConfig()
+        cfg.struct_size = C.sizeof(SpectrumConfig)
+        cfg.device, cfg.n_rows, cfg.input_rate, cfg.input_format = int(device), int(n_rows), float(input_rate), int(input_format)
+        cfg.fft_size, cfg.hop, cfg.window, cfg.max_call_len = int(fft_size), int(hop), int(window), int(max_call_len)
+        self.n_rows, self.fft_size, self.input_rate, self.input_format = int(n_rows), int(fft_size), float(input_rate), int(input_format)
+        self.h = C.c_void_p()
+        rc = self._L.fmr_spectrum_create(C.byref(cfg), C.sizeof(SpectrumConfig), C.byref(self.h))
+        if rc != OK:
+            self.h = None
+            raise FmrError(f"fmr_spectrum_create failed ({rc}): {self._L.fmr_last_error().decode()}")
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self, "_L", None) is not None:
+            self._L.fmr_spectrum_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _chk(self, rc):
+        if rc < 0:
+            raise FmrError(f"fmradion_amd error {rc}: {self._L.fmr_last_error().decode()}")
+        return rc
+
+    def process(self, x):
+        """x: (n,) or (n_rows, n) complex64 -- or, for a raw input_format, (n, 2) / (n_rows, n, 2) of its integer type."""
+        if self.input_format == IQ_CF32:
+            x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.complex64)
+        else:
+            x = np.ascontiguousarray(x, dtype=_IQ_DTYPE[self.input_format])
+            if x.ndim == 2:
+                x = x[None]
+            assert x.ndim == 3 and x.shape[2] == 2
+        assert x.shape[0] == self.n_rows, (x.shape, self.n_rows)
+        self._chk(self._L.fmr_spectrum_process(self.h, x.ctypes.data, x.shape[1], x.shape[1]))
+
+    def process_device(self, ptr, n, stride=0, sync=True):
+        """Rows of `stride` IQ samples (0 = n) at the device address ptr (e.g. a torch tensor's data_ptr())."""
+        self._chk(self._L.fmr_spectrum_process_device(self.h, C.c_void_p(int(ptr)), int(stride), int(n), int(sync)))
+
+    def synchronize(self):
+        self._chk(self._L.fmr_spectrum_synchronize(self.h))
+
+    def _read(self, row, which):
+        out = np.empty(self.fft_size, dtype=np.float64)
+        info = SpectrumInfo()
+        self._chk(self._L.fmr_spectrum_read(self.h, int(row), which, out.ctypes.data_as(C.POINTER(C.c_double)),
+                                            len(out), C.byref(info)))
+        return out, info
+
+    def psd(self, row=0):
+        return self._read(row, 0)[0]
+
+    def peak_hold(self, row=0):
+        return self._read(row, 1)[0]
+
+    def info(self, row=0):
+        i = self._read(row, 0)[1]
+        return {k: getattr(i, k) for k, _ in SpectrumInfo._fields_}
+
+    def freqs(self):
+        return (np.arange(self.fft_size) - self.fft_size // 2) * (self.input_rate / self.fft_size)
+
+    def reset(self):
+        self._chk(self._L.fmr_spectrum_reset(self.h))

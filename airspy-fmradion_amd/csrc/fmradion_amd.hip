@@ -31,6 +31,7 @@
 #include "kernels_decim16.hpp"
 #include "kernels_chanbank.hpp"
 #include "kernels_rds.hpp"
+#include "kernels_spectrum.hpp"
 #include "../host/fmradion_rds.hpp"
 
 namespace {
@@ -2892,6 +2893,201 @@ int fmr_chain::run_am(CallCtx &k) {
 }
 
 // ============================================================================
+// Band spectrum (fmr_spectrum_*, kernels_spectrum.hpp)
+// ============================================================================
+struct fmr_spectrum {
+  fmr_spectrum_config cfg{};
+  int N = 0, H = 0, logn = 0, rows = 0, fmt = 0;
+  int rmax = 1;                          // runs per row and call (capacity of the partials)
+  int n_cu = 256;
+  hipStream_t stream = nullptr;
+  DevBuf<float> d_win, d_pmax, d_max;
+  DevBuf<float2> d_tw, d_ring;
+  DevBuf<double> d_psum, d_sum;
+  DevBuf<int2> d_pcnt;
+  DevBuf<unsigned long long> d_cnt;      // per row: segments counted, segments skipped
+  DevBuf<unsigned char> d_stage;         // host path: the call's rows
+  unsigned long long total = 0;          // samples per row since create
+  unsigned long long next_seg = 0;       // segments completed since create
+  unsigned long long first_seg = 0;      // first segment processed since create / the last reset
+  double sumw = 0.0, sumw2 = 0.0;
+  int init();
+  int run(const void *d_in, size_t stride, size_t n);
+  ~fmr_spectrum() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    d_win.release(); d_pmax.release(); d_max.release(); d_tw.release(); d_ring.release(); d_psum.release(); d_sum.release();
+    d_pcnt.release(); d_cnt.release(); d_stage.release();
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+namespace {
+constexpr int kSpecBps[4] = {8, 4, 2, 2};    // bytes per IQ sample of FMR_IQ_CF32 / S16 / U8 / S8
+// limits of fmr_spectrum_create: grid.y is 65535 rows at most; a call of 2^30 samples per row has at most 2^30 segments
+// (H = 1), so every segment count and index k_spec_seg and the engine hold in int stays below 2^31
+constexpr int kSpecMaxRows = 65535;
+constexpr size_t kSpecMaxCall = (size_t)1 << 30;
+
+template <int LOGN, int FMT>
+int spec_seg_launch(fmr_spectrum *s, dim3 grid, const void *in, long long stride, long long tb, long long seg0, int n_seg,
+                    int per_run) {
+  hipLaunchKernelGGL((k_spec_seg<LOGN, FMT>), grid, dim3(SpecShape<LOGN>::T), SpecShape<LOGN>::LDS_BYTES, s->stream, in,
+                     stride, (const float2 *)s->d_ring.p, tb, seg0, n_seg, per_run, s->H, (const float *)s->d_win.p,
+                     (const float2 *)s->d_tw.p, s->d_psum.p, s->d_pmax.p, s->d_pcnt.p, s->rmax);
+  HIPCHK(hipGetLastError());
+  return FMR_OK;
+}
+template <int LOGN, int FMT>
+int spec_seg_attr() {
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spec_seg<LOGN, FMT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             SpecShape<LOGN>::LDS_BYTES));
+  return FMR_OK;
+}
+using SpecSegFn = int (*)(fmr_spectrum *, dim3, const void *, long long, long long, long long, int, int);
+using SpecAttrFn = int (*)();
+#define FMR_SPEC_ROW(L) {&spec_seg_launch<L, 0>, &spec_seg_launch<L, 1>, &spec_seg_launch<L, 2>, &spec_seg_launch<L, 3>}
+#define FMR_SPEC_ATTR(L) {&spec_seg_attr<L, 0>, &spec_seg_attr<L, 1>, &spec_seg_attr<L, 2>, &spec_seg_attr<L, 3>}
+const SpecSegFn kSpecSeg[7][4] = {FMR_SPEC_ROW(8), FMR_SPEC_ROW(9), FMR_SPEC_ROW(10), FMR_SPEC_ROW(11), FMR_SPEC_ROW(12),
+                                  FMR_SPEC_ROW(13), FMR_SPEC_ROW(14)};
+const SpecAttrFn kSpecAttr[7][4] = {FMR_SPEC_ATTR(8), FMR_SPEC_ATTR(9), FMR_SPEC_ATTR(10), FMR_SPEC_ATTR(11), FMR_SPEC_ATTR(12),
+                                    FMR_SPEC_ATTR(13), FMR_SPEC_ATTR(14)};
+#undef FMR_SPEC_ROW
+#undef FMR_SPEC_ATTR
+const decltype(&k_spec_reduce<0>) kSpecReduce[4] = {&k_spec_reduce<0>, &k_spec_reduce<1>, &k_spec_reduce<2>, &k_spec_reduce<3>};
+
+
+// the periodic window of kind `window` at N points, in double
+double spec_window(int window, int n, int N) {
+  const double x = 2.0 * M_PI * n / N;
+  if (window == FMR_WINDOW_HANN) return 0.5 - 0.5 * std::cos(x);
+  if (window == FMR_WINDOW_BLACKMAN_HARRIS) return 0.35875 - 0.48829 * std::cos(x) + 0.14128 * std::cos(2 * x) - 0.01168 * std::cos(3 * x);
+  return 1.0;
+}
+
+// the rules of fmr_spectrum_create, before the device is opened
+int spec_check(const fmr_spectrum_config &c) {
+  if (c.fft_size < 256 || c.fft_size > 16384 || (c.fft_size & (c.fft_size - 1)) != 0) {
+    set_err("fmr_spectrum_create: fft_size %d is not a power of two in 256 .. 16384", c.fft_size);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (c.hop < 0 || c.hop > c.fft_size) { set_err("fmr_spectrum_create: hop %d is outside 0 .. fft_size (%d)", c.hop, c.fft_size); return FMR_ERR_BAD_ARG; }
+  if (c.window < FMR_WINDOW_HANN || c.window > FMR_WINDOW_BLACKMAN_HARRIS) { set_err("fmr_spectrum_create: unknown window %d", c.window); return FMR_ERR_BAD_ARG; }
+  if (c.input_format < FMR_IQ_CF32 || c.input_format > FMR_IQ_S8) { set_err("fmr_spectrum_create: unknown input_format %d", c.input_format); return FMR_ERR_BAD_ARG; }
+  if (!(c.input_rate > 0.0) || !std::isfinite(c.input_rate)) { set_err("fmr_spectrum_create: input_rate %g is not > 0", c.input_rate); return FMR_ERR_BAD_ARG; }
+  if (c.n_rows < 1 || c.n_rows > kSpecMaxRows) {
+    set_err("fmr_spectrum_create: n_rows %d is outside 1 .. %d (one grid row per IQ row)", c.n_rows, kSpecMaxRows);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (c.max_call_len == 0 || c.max_call_len > kSpecMaxCall) {
+    set_err("fmr_spectrum_create: max_call_len %zu is outside 1 .. %zu (segments per call are counted in int)", c.max_call_len, kSpecMaxCall);
+    return FMR_ERR_BAD_ARG;
+  }
+  return FMR_OK;
+}
+}  // namespace
+
+int fmr_spectrum::init() {
+  N = cfg.fft_size;
+  H = cfg.hop ? cfg.hop : N / 2;
+  logn = 0;
+  while ((1 << logn) < N) logn++;
+  rows = cfg.n_rows;
+  fmt = cfg.input_format;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err("no HIP device"); return FMR_ERR_NO_DEVICE; }
+  if (cfg.device < 0 || cfg.device >= ndev) { set_err("fmr_spectrum_create: device %d out of range (%d devices)", cfg.device, ndev); return FMR_ERR_BAD_ARG; }
+  HIPCHK(hipSetDevice(cfg.device));
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, cfg.device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
+  HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  if (int rc = kSpecAttr[logn - 8][fmt]()) return rc;
+  // window and twiddles: double, rounded once to fp32
+  std::vector<float> w(N);
+  std::vector<float2> tw(N);
+  double sw = 0.0, sw2 = 0.0;
+  for (int n = 0; n < N; n++) {
+    w[n] = (float)spec_window(cfg.window, n, N);
+    sw += w[n];
+    sw2 += (double)w[n] * w[n];
+    const double a = -2.0 * M_PI * n / N;
+    tw[n] = make_float2((float)std::cos(a), (float)std::sin(a));
+  }
+  sumw = sw;
+  sumw2 = sw2;
+  if (int rc = upload(d_win, w.data(), w.size())) return rc;
+  if (int rc = upload(d_tw, tw.data(), tw.size())) return rc;
+  // runs: about one workgroup per slot the chip holds at this N, shared by the rows; no more than a call's segments
+  const int occ = std::max(1, std::min(163840 / spec_lds_bytes(logn), 2048 / spec_threads(logn)));
+  const long long smax = (long long)((cfg.max_call_len + H - 1) / H) + 1;
+  rmax = (int)std::max(1LL, std::min(smax, (long long)((n_cu * occ + rows - 1) / rows)));
+  const size_t part = (size_t)rows * rmax;
+  if (int rc = d_psum.alloc(part * N)) return rc;
+  if (int rc = d_pmax.alloc(part * N)) return rc;
+  if (int rc = d_pcnt.alloc(part)) return rc;
+  if (int rc = d_sum.alloc((size_t)rows * N)) return rc;
+  if (int rc = d_max.alloc((size_t)rows * N)) return rc;
+  if (int rc = d_ring.alloc((size_t)rows * N)) return rc;
+  if (int rc = d_cnt.alloc((size_t)rows * 2)) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  return FMR_OK;
+}
+
+// one call: n samples of every row at d_in (row r at d_in + r stride samples), on the object's stream
+int fmr_spectrum::run(const void *d_in, size_t stride, size_t n) {
+  const long long tb = (long long)total, ta = tb + (long long)n;
+  const long long j_hi = ta >= N ? (ta - N) / H + 1 : 0;
+  const long long n_seg = std::max(0LL, j_hi - (long long)next_seg);
+  int runs = 0;
+  if (n_seg > 0) {
+    runs = (int)std::min<long long>(n_seg, rmax);
+    const int per_run = (int)((n_seg + runs - 1) / runs);
+    runs = (int)((n_seg + per_run - 1) / per_run);
+    if (int rc = kSpecSeg[logn - 8][fmt](this, dim3(runs, rows), d_in, (long long)stride, tb, (long long)next_seg, (int)n_seg, per_run))
+      return rc;
+  }
+  hipLaunchKernelGGL(kSpecReduce[fmt], dim3((N + 63) / 64, rows), dim3(64 * SPEC_RW), 0, stream, (const double *)d_psum.p,
+                     (const float *)d_pmax.p, (const int2 *)d_pcnt.p, runs, rmax, N, d_sum.p, d_max.p, d_cnt.p, d_in,
+                     (long long)stride, tb, ta, d_ring.p);
+  HIPCHK(hipGetLastError());
+  if (n_seg > 0) next_seg = (unsigned long long)j_hi;
+  total = (unsigned long long)ta;
+  return FMR_OK;
+}
+
+static int spectrum_call(fmr_spectrum *s, const void *iq, size_t row_stride, size_t n, bool host, int sync) {
+  if (!s || (!iq && n > 0)) { set_err("fmr_spectrum_process: null argument"); return FMR_ERR_BAD_ARG; }
+  if (n > s->cfg.max_call_len) {
+    set_err("fmr_spectrum_process: n = %zu > max_call_len = %zu (nothing was processed)", n, s->cfg.max_call_len);
+    return FMR_ERR_CAPACITY;
+  }
+  if (row_stride == 0) row_stride = n;
+  if (row_stride < n) { set_err("fmr_spectrum_process: row_stride %zu < n %zu", row_stride, n); return FMR_ERR_BAD_ARG; }
+  if (n == 0) return FMR_OK;
+  try {
+    HIPCHK(hipSetDevice(s->cfg.device));
+    const size_t bps = kSpecBps[s->fmt];
+    const void *d_in = iq;
+    size_t stride = row_stride;
+    if (host) {
+      const size_t need = (size_t)s->rows * s->cfg.max_call_len * bps;
+      if (!s->d_stage.p) {
+        if (s->d_stage.alloc(need)) return FMR_ERR_HIP;
+        HIPCHK(hipDeviceSynchronize());      // (alloc's memset runs on the null stream, which the object's stream does not wait for)
+      }
+      HIPCHK(hipMemcpy2DAsync(s->d_stage.p, n * bps, iq, row_stride * bps, n * bps, s->rows, hipMemcpyHostToDevice, s->stream));
+      d_in = s->d_stage.p;
+      stride = n;
+    }
+    if (int rc = s->run(d_in, stride, n)) return rc;
+    if (host || sync) HIPCHK(hipStreamSynchronize(s->stream));
+    return FMR_OK;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+// 10 log10 of a power ratio
+static double spec_db(double x) { return 10.0 * std::log10(x); }
+
+// ============================================================================
 // C-ABI
 // ============================================================================
 extern "C" {
@@ -3504,6 +3700,147 @@ int fmr_filter_table(const char *name, const void **data, int *is_double) {
       return e.n;
     }
   return FMR_ERR_BAD_ARG;
+}
+
+
+int fmr_spectrum_create(const fmr_spectrum_config *cfg, size_t cfg_size, fmr_spectrum **out) {
+  if (!cfg || !out) { set_err("fmr_spectrum_create: null argument"); return FMR_ERR_BAD_ARG; }
+  *out = nullptr;
+  const size_t size = cfg_size ? cfg_size : sizeof(fmr_spectrum_config);
+  if (size > sizeof(fmr_spectrum_config) || cfg->struct_size > sizeof(fmr_spectrum_config)) {
+    set_err("fmr_spectrum_create: struct_size %zu is larger than this library's fmr_spectrum_config (%zu): the caller is "
+            "newer than the library", std::max(size, (size_t)cfg->struct_size), sizeof(fmr_spectrum_config));
+    return FMR_ERR_BAD_ARG;
+  }
+  fmr_spectrum_config full;
+  memset(&full, 0, sizeof full);
+  memcpy(&full, cfg, size);
+  if (int rc = spec_check(full)) return rc;
+  fmr_spectrum *s = new fmr_spectrum();
+  s->cfg = full;
+  if (int rc = s->init()) { delete s; return rc; }
+  *out = s;
+  return FMR_OK;
+}
+
+void fmr_spectrum_destroy(fmr_spectrum *s) { delete s; }
+
+int fmr_spectrum_process(fmr_spectrum *s, const void *iq, size_t row_stride, size_t n) {
+  return spectrum_call(s, iq, row_stride, n, true, 1);
+}
+
+int fmr_spectrum_process_device(fmr_spectrum *s, const void *d_iq, size_t row_stride, size_t n, int sync) {
+  return spectrum_call(s, d_iq, row_stride, n, false, sync);
+}
+
+int fmr_spectrum_synchronize(fmr_spectrum *s) {
+  if (!s) return FMR_ERR_BAD_ARG;
+  HIPCHK(hipSetDevice(s->cfg.device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return FMR_OK;
+}
+
+int fmr_spectrum_read(fmr_spectrum *s, int row, int which, double *out, size_t cap, fmr_spectrum_info *info) {
+  if (!s || row < 0 || row >= s->rows || (which != 0 && which != 1)) { set_err("fmr_spectrum_read: bad row or which"); return FMR_ERR_BAD_ARG; }
+  const int N = s->N;
+  if (cap < (size_t)N) { set_err("fmr_spectrum_read: cap %zu < fft_size %d", cap, N); return FMR_ERR_CAPACITY; }
+  if (!out) { set_err("fmr_spectrum_read: out is null"); return FMR_ERR_BAD_ARG; }
+  HIPCHK(hipSetDevice(s->cfg.device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  unsigned long long cnt[2];
+  HIPCHK(hipMemcpy(cnt, s->d_cnt.p + 2 * row, sizeof cnt, hipMemcpyDeviceToHost));
+  std::vector<double> v(N, 0.0);
+  if (which == 0) {
+    HIPCHK(hipMemcpy(v.data(), s->d_sum.p + (size_t)row * N, N * sizeof(double), hipMemcpyDeviceToHost));
+  } else {
+    std::vector<float> m(N);
+    HIPCHK(hipMemcpy(m.data(), s->d_max.p + (size_t)row * N, N * sizeof(float), hipMemcpyDeviceToHost));
+    for (int k = 0; k < N; k++) v[k] = m[k];
+  }
+  const double F = s->cfg.input_rate;
+  const double scale = 1.0 / (F * s->sumw2);
+  for (int k = 0; k < N; k++) {
+    const double x = v[(k + N / 2) & (N - 1)];          // fftshift: element k is bin k - N/2
+    out[k] = cnt[0] == 0 ? 0.0 : which == 0 ? x / (double)cnt[0] * scale : x * scale;
+  }
+  if (info) {
+    info->segments = cnt[0];
+    info->segments_skipped = cnt[1];
+    info->first_segment = s->first_seg;
+    info->samples_seen = s->total;
+    info->bin_hz = F / N;
+    info->enbw_hz = F * s->sumw2 / (s->sumw * s->sumw);
+  }
+  return N;
+}
+
+int fmr_spectrum_reset(fmr_spectrum *s) {
+  if (!s) return FMR_ERR_BAD_ARG;
+  HIPCHK(hipSetDevice(s->cfg.device));
+  HIPCHK(hipMemsetAsync(s->d_sum.p, 0, s->d_sum.n * sizeof(double), s->stream));
+  HIPCHK(hipMemsetAsync(s->d_max.p, 0, s->d_max.n * sizeof(float), s->stream));
+  HIPCHK(hipMemsetAsync(s->d_cnt.p, 0, s->d_cnt.n * sizeof(unsigned long long), s->stream));
+  s->first_seg = s->next_seg;
+  return FMR_OK;
+}
+
+int fmr_find_stations(const double *psd, int fft_size, double input_rate, const fmr_station_rule *rule, fmr_station *out,
+                      int cap) {
+  if (!psd || !rule || cap < 0 || (cap > 0 && !out)) { set_err("fmr_find_stations: null argument"); return FMR_ERR_BAD_ARG; }
+  const int N = fft_size;
+  if (N < 2 || (N & (N - 1)) != 0) { set_err("fmr_find_stations: fft_size %d is not a power of two", N); return FMR_ERR_BAD_ARG; }
+  if (!(input_rate > 0.0) || !std::isfinite(input_rate)) { set_err("fmr_find_stations: input_rate %g is not > 0", input_rate); return FMR_ERR_BAD_ARG; }
+  if (rule->raster_hz <= 0) { set_err("fmr_find_stations: raster_hz %d <= 0", rule->raster_hz); return FMR_ERR_BAD_ARG; }
+  if (rule->bandwidth_hz <= 0) { set_err("fmr_find_stations: bandwidth_hz %d <= 0", rule->bandwidth_hz); return FMR_ERR_BAD_ARG; }
+  const double p = rule->floor_percentile == 0.0 ? 20.0 : rule->floor_percentile;
+  if (!(p >= 0.0 && p < 100.0)) { set_err("fmr_find_stations: floor_percentile %g is outside [0, 100)", p); return FMR_ERR_BAD_ARG; }
+  const double F = input_rate, df = F / N;
+  const double mab = rule->max_abs_offset_hz != 0 ? (double)rule->max_abs_offset_hz : (F - kFmRate) / 2.0;
+  auto fk = [&](int k) { return (double)(k - N / 2) * df; };
+  // 1. floor density
+  std::vector<double> in_band;
+  for (int k = 0; k < N; k++)
+    if (std::fabs(fk(k)) <= mab) in_band.push_back(psd[k]);
+  if (in_band.empty()) return 0;
+  std::sort(in_band.begin(), in_band.end());
+  const double floor_d = in_band[(size_t)std::floor(p / 100.0 * (double)(in_band.size() - 1))];
+  // 2. candidates, 3. band power
+  const double bw = rule->bandwidth_hz, half = bw / 2.0, raster = rule->raster_hz, off = rule->raster_offset_hz;
+  struct Cand { double f, B, noise, cen; };
+  std::vector<Cand> c;
+  for (long long j = (long long)std::ceil((-mab - off) / raster); ; j++) {
+    const double f = off + (double)j * raster;
+    if (f > mab) break;
+    if (std::fabs(f) > mab) continue;
+    double B = 0.0, fp = 0.0, pp = 0.0;
+    int nb = 0;
+    for (int k = 0; k < N; k++)
+      if (std::fabs(fk(k) - f) <= half) { B += psd[k] * df; fp += fk(k) * psd[k]; pp += psd[k]; nb++; }
+    c.push_back({f, B, floor_d * nb * df, fp / pp});
+  }
+  // 4. acceptance, 5. output
+  int count = 0;
+  for (size_t i = 0; i < c.size(); i++) {
+    const double snr = spec_db(c[i].B / c[i].noise);
+    if (!(snr >= rule->threshold_db)) continue;
+    bool keep = true;
+    for (size_t q = 0; q < c.size() && keep; q++) {
+      const double d = std::fabs(c[q].f - c[i].f);
+      if (q == i || !(d > 0.0 && d < bw)) continue;
+      if (c[q].B > c[i].B || (c[q].B == c[i].B && c[q].f < c[i].f)) keep = false;
+    }
+    if (!keep) continue;
+    if (count < cap) {
+      fmr_station &o = out[count];
+      o.offset_hz = (int32_t)c[i].f;
+      o.reserved = 0;
+      o.level_db = spec_db(c[i].B);
+      o.snr_db = snr;
+      o.centroid_hz = c[i].cen;
+    }
+    count++;
+  }
+  return count;
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 //   FilterParameters    include/FilterParameters.h:29-53
 //   ChannelBank         several decoders over one wideband capture (no reference counterpart)
 //   Channelizer         several IfResamplers over one wideband capture (no reference counterpart)
+//   SpectrumMonitor     band spectrum of a capture and the stations in it (no reference counterpart)
 //
 // Header-only; link with libfmradion_amd.so.  Every process() call is one
 // fmr_process()/fmr_resample() on a one-stream chain (host buffers in, host
@@ -594,4 +595,56 @@ private:
   std::vector<int32_t> m_offsets;
   size_t m_max_block;
   fmr_chain *m_chain = nullptr;
+};
+
+// SpectrumMonitor (fmr_spectrum_*): the Welch power spectrum of a capture on the GPU (mean PSD, density-scaled, fftshift
+// order: element k is the bin at (k - N/2) input_rate / N Hz) and the stations it holds.  find_stations() returns offsets
+// that go straight into ChannelBank / Channelizer.  Blocks longer than max_call_len are taken in consecutive pieces.
+class SpectrumMonitor {
+public:
+  explicit SpectrumMonitor(double input_rate, int fft_size = 8192, int hop = 0, int window = FMR_WINDOW_HANN, int device = 0,
+                           size_t max_call_len = 1 << 20)
+      : m_rate(input_rate), m_n(fft_size), m_max(max_call_len) {
+    fmr_spectrum_config cfg{};
+    cfg.struct_size = sizeof cfg; cfg.device = device; cfg.n_rows = 1; cfg.input_rate = input_rate;
+    cfg.input_format = FMR_IQ_CF32; cfg.fft_size = fft_size; cfg.hop = hop; cfg.window = window; cfg.max_call_len = max_call_len;
+    fmr_detail::check(fmr_spectrum_create(&cfg, sizeof cfg, &m_s), "fmr_spectrum_create");
+  }
+  ~SpectrumMonitor() { fmr_spectrum_destroy(m_s); }
+  SpectrumMonitor(const SpectrumMonitor &) = delete;
+  SpectrumMonitor &operator=(const SpectrumMonitor &) = delete;
+
+  void process(const IQSampleVector &samples_in) {
+    for (size_t off = 0; off < samples_in.size(); off += m_max) {
+      const size_t n = std::min(m_max, samples_in.size() - off);
+      fmr_detail::check(fmr_spectrum_process(m_s, samples_in.data() + off, n, n), "fmr_spectrum_process");
+    }
+  }
+  // the mean PSD since construction / reset()
+  std::vector<double> psd() { return read(0); }
+  std::vector<double> peak_hold() { return read(1); }
+  void reset() { fmr_detail::check(fmr_spectrum_reset(m_s), "fmr_spectrum_reset"); }
+  // fmr_find_stations on the current mean PSD: offsets in ascending order
+  std::vector<int32_t> find_stations(const fmr_station_rule &rule) {
+    const std::vector<double> p = psd();
+    const int n = fmr_find_stations(p.data(), m_n, m_rate, &rule, nullptr, 0);
+    if (n < 0) fmr_detail::check(n, "fmr_find_stations");
+    std::vector<fmr_station> st((size_t)n);
+    fmr_find_stations(p.data(), m_n, m_rate, &rule, st.data(), n);
+    std::vector<int32_t> out;
+    for (const fmr_station &x : st) out.push_back(x.offset_hz);
+    return out;
+  }
+
+private:
+  std::vector<double> read(int which) {
+    std::vector<double> v((size_t)m_n);
+    const int rc = fmr_spectrum_read(m_s, 0, which, v.data(), v.size(), nullptr);
+    if (rc < 0) fmr_detail::check(rc, "fmr_spectrum_read");
+    return v;
+  }
+  double m_rate;
+  int m_n;
+  size_t m_max;
+  fmr_spectrum *m_s = nullptr;
 };

@@ -392,6 +392,82 @@ int fmr_get_rds_groups(fmr_chain *c, int stream, fmr_rds_group *groups, int cap)
 /* Counters and estimates of stream `stream` (synchronises); st_size = sizeof(fmr_rds_status) as the caller knows it. */
 int fmr_get_rds_status(fmr_chain *c, int stream, fmr_rds_status *st, size_t st_size);
 
+/* --- Band spectrum and station finder (no counterpart in the reference).  A handle of its own:
+ * a Welch power spectrum (mean and peak hold) of n_rows IQ rows on the GPU, and a host-side finder that turns a spectrum
+ * into offsets fmr_config.channel_offset_hz takes as they are.
+ * Segment j of a row covers the absolute samples [j H, j H + N) (counted from the object's first sample, across calls of
+ * any length) and is processed in the call that delivers its last sample; the row's last N samples stay on the device.
+ * Periodic windows, built in double and rounded once to fp32: Hann w[n] = 0.5 - 0.5 cos(2 pi n / N); rect w[n] = 1;
+ * 4-term Blackman-Harris a = 0.35875, 0.48829, 0.14128, 0.01168.
+ * Output (doubles, fftshift order: element k is the bin at (k - N/2) F / N Hz, F = input_rate), density-scaled:
+ *     |sum_n w[n] x_j[n] exp(-2 pi i k n / N)|^2 / (F sum w^2)
+ * which = 0: the mean over the counted segments, which = 1: their peak hold.  sum psd F / N is the mean power.
+ * A segment that holds a non-finite sample is left out of both and counted in segments_skipped.
+ * Reproducibility: the per-segment arithmetic does not depend on where a segment falls in a call (the peak hold is
+ * bit-identical for any cut of the input into calls); float sums run in a fixed order without atomics (the same cut
+ * gives the same bits); the mean's partial sums are fp64 (across cuts it differs only at their rounding). */
+enum { FMR_WINDOW_HANN = 0, FMR_WINDOW_RECT = 1, FMR_WINDOW_BLACKMAN_HARRIS = 2 };
+typedef struct {
+  unsigned struct_size;   /* as fmr_config: 0 = this header's size; a larger size is refused */
+  int device;
+  int n_rows;             /* 1 .. 65535 independent IQ rows (a plain capture, or a channelizer's K output rows) */
+  double input_rate;      /* Hz, > 0 */
+  int input_format;       /* FMR_IQ_CF32 | _S16 | _U8 | _S8, converted as fmr_config.input_format */
+  int fft_size;           /* N: power of two, 256 .. 16384 */
+  int hop;                /* H: 1 .. N; 0 = N / 2 */
+  int window;             /* FMR_WINDOW_* */
+  size_t max_call_len;    /* largest n per call and row: 1 .. 2^30 */
+} fmr_spectrum_config;
+typedef struct {
+  uint64_t segments;          /* averaged since create / the last reset */
+  uint64_t segments_skipped;  /* held a non-finite sample: left out of both the mean and the peak hold */
+  uint64_t first_segment;     /* absolute index of the first segment processed since create / the last reset */
+  uint64_t samples_seen;      /* per row, since create */
+  double bin_hz;              /* input_rate / N */
+  double enbw_hz;             /* input_rate * sum w^2 / (sum w)^2 */
+} fmr_spectrum_info;
+/* Station finder rule (fmr_find_stations): candidates f_c = raster_offset_hz + j raster_hz, |f_c| <= max_abs_offset_hz
+ * (0 = (input_rate - 384000) / 2, the channel bank's limit); band = the bins within bandwidth_hz / 2 of f_c; floor =
+ * the floor_percentile (0 = 20) percentile of the bins within max_abs (sorted value at floor(p / 100 (M - 1))). */
+typedef struct {
+  int32_t raster_hz, raster_offset_hz, bandwidth_hz, max_abs_offset_hz;
+  double threshold_db, floor_percentile;
+} fmr_station_rule;
+typedef struct {
+  int32_t offset_hz, reserved;
+  double level_db;      /* band power, dB re a full-scale complex sinusoid (power 1) */
+  double snr_db;        /* band power over floor density x band width */
+  double centroid_hz;   /* power-weighted mean frequency of the band */
+} fmr_station;
+typedef struct fmr_spectrum fmr_spectrum;
+
+/* cfg_size = sizeof(fmr_spectrum_config) as the caller knows it (0 = this header's).  FMR_ERR_BAD_ARG (before the device
+ * is opened; fmr_last_error names the field) for an N that is not a power of two in 256 .. 16384, a hop outside 0 .. N,
+ * an unknown window or input_format, input_rate <= 0, n_rows outside 1 .. 65535, max_call_len outside 1 .. 2^30 or a size
+ * larger than this header's;
+ * FMR_ERR_NO_DEVICE for a valid configuration without a device. */
+int fmr_spectrum_create(const fmr_spectrum_config *cfg, size_t cfg_size, fmr_spectrum **out);
+void fmr_spectrum_destroy(fmr_spectrum *s);
+/* n samples of every row: row r at iq + r row_stride IQ samples (row_stride 0 = n), host buffers.  n > max_call_len is
+ * refused with FMR_ERR_CAPACITY and leaves the object as it was. */
+int fmr_spectrum_process(fmr_spectrum *s, const void *iq, size_t row_stride, size_t n);
+/* The same on device buffers with fmr_process_blocks_device's asynchronous contract (sync = 0: d_iq stays valid until
+ * fmr_spectrum_synchronize, a call with sync != 0 or fmr_spectrum_read).  Raw-format rows are 16-byte aligned. */
+int fmr_spectrum_process_device(fmr_spectrum *s, const void *d_iq, size_t row_stride, size_t n, int sync);
+int fmr_spectrum_synchronize(fmr_spectrum *s);
+/* Synchronises; writes N doubles of row `row` (which 0 = mean PSD, 1 = peak hold; zeros before any segment was counted)
+ * and, if info is not NULL, the row's counters.  Returns N, or FMR_ERR_CAPACITY when cap < N. */
+int fmr_spectrum_read(fmr_spectrum *s, int row, int which, double *out, size_t cap, fmr_spectrum_info *info);
+/* Zeroes both accumulators and the counts of every row; the segment grid keeps its absolute positions. */
+int fmr_spectrum_reset(fmr_spectrum *s);
+/* Host only (no device).  psd: fft_size doubles in the layout above.  Keeps f_c when snr_db >= threshold_db and its band
+ * power is >= that of every candidate f' with 0 < |f' - f_c| < bandwidth_hz (a tie goes to the lower frequency).
+ * Writes up to cap stations in ascending offset order and returns how many there are (possibly more than cap);
+ * FMR_ERR_BAD_ARG for raster_hz <= 0, bandwidth_hz <= 0, floor_percentile outside [0, 100), an invalid fft_size or
+ * input_rate. */
+int fmr_find_stations(const double *psd, int fft_size, double input_rate, const fmr_station_rule *rule, fmr_station *out,
+                      int cap);
+
 #ifdef __cplusplus
 }
 #endif
