@@ -148,8 +148,14 @@ __global__ __launch_bounds__(64) void k_rds_est(const float2 *__restrict__ y2, i
   const long long w = w0 + wl;
   const float2 *r = y2 + (long long)s * R;
   const long long j0 = w * kRdsWin;
+  // The stream's first symbol period is left out of the timing: its symbol is cut by the start of the stream (its pulse
+  // reaches back before sample 0), or, for the candidates past a symbol that starts late in the period, not there at all,
+  // so the candidates on either side of that symbol would be compared over different symbols (up to 3.7 samples of bias).
+  // (The sums for the phase and the level below keep it: there a cut symbol only weighs less, it has the phase of the
+  // others, and the scan smooths the level.)
+  const int k_lo = w == 0 ? 1 : 0;
   float acc = 0.f;
-  for (int k = 0; k < kRdsWin; k++) {
+  for (int k = k_lo; k < kRdsWin; k++) {
     const float2 v = rds_soft(r, R, (j0 + k) * kRdsSym + (long long)c * (kRdsSym / kRdsCand));
     acc += v.x * v.x + v.y * v.y;
   }
@@ -197,7 +203,10 @@ __global__ void k_rds_scan(const RdsEst *__restrict__ est, int nw, long long w0,
       d -= P * rint(d / P);                                // nearest representative: the timing stays continuous
       z.tau += 0.5 * d;
       const double pred = z.theta + z.fr * kRdsWin;
-      const double th = th_raw + PI * rint((pred - th_raw) / PI);   // modulo pi: differential decoding cancels pi
+      // th_raw is the phase at the mean start of the estimate's 64 symbols, (64 w + 31.5) P + phi; kmid names the
+      // window's centre, (64 w + 32) P: carry the phase there along the tracked slope (at 3 Hz up to 8 mrad)
+      const double th_c = th_raw + z.fr * (0.5 - (double)e.phi / P);
+      const double th = th_c + PI * rint((pred - th_c) / PI);       // modulo pi: differential decoding cancels pi
       z.fr += 0.5 * ((th - z.theta) / kRdsWin - z.fr);
       z.theta = th;
     } else {                                               // a dropout: hold the timing, let the phase run on

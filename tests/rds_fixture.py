@@ -129,11 +129,7 @@ def station_mpx(t, groups, level=2.0 / 75.0, phase=-np.pi / 2, stereo_id=0, pilo
     """MPX of a station: 0.9 x siggen.fm_stereo_mpx (or a mono programme without pilot) plus the RDS subcarrier
     level m(t) cos(2 pi 57000 t + phase).  phase = -pi/2: in phase with the third harmonic of the pilot sin(2 pi 19 k t);
     phase = 0: in quadrature."""
-    import siggen
-    if mono:
-        prog = 0.45 * (np.sin(2 * np.pi * 1000.0 * t) + np.sin(2 * np.pi * 400.0 * t))
-    else:
-        prog = 0.9 * siggen.fm_stereo_mpx(t, stereo_id, pilot)
+    prog = programme(t, "mono") if mono else programme(t, "stereo", stereo_id, pilot)
     return prog + level * rds_baseband(t, groups, t0) * np.cos(2 * np.pi * 57000.0 * t + phase)
 
 
@@ -144,3 +140,33 @@ def fm_iq(mpx, fs, amplitude=0.3, sigma=1e-3, seed=1):
         rng = np.random.default_rng(seed)
         x = x + sigma * (rng.standard_normal(len(x)) + 1j * rng.standard_normal(len(x)))
     return x
+
+
+# ---- a known MPX in front of the RDS stage (tests/rds_reference.py is the receiver it is compared with) ---------------
+def programme(t, kind, stereo_id=0, pilot=0.10):
+    """The programme part of an MPX: "mono" (two tones, no pilot), "stereo" (0.9 x siggen.fm_stereo_mpx), "tone15"
+    (pilot plus a full-scale 15 kHz L-R tone: its upper sideband lies at 53 kHz, 4 kHz below the RDS subcarrier)."""
+    import siggen
+    if kind == "mono":
+        return 0.45 * (np.sin(2 * np.pi * 1000.0 * t) + np.sin(2 * np.pi * 400.0 * t))
+    if kind == "stereo":
+        return 0.9 * siggen.fm_stereo_mpx(t, stereo_id, pilot)
+    if kind == "tone15":
+        th = 2 * np.pi * 19000.0 * t
+        return 0.9 * (0.10 * np.sin(th) + 0.9 * np.sin(2 * np.pi * 15000.0 * t) * np.sin(2 * th))
+    raise ValueError(kind)
+
+
+def known_mpx(n, groups, kind="mono", level=2.0 / 75.0, phase=-np.pi / 2, t0=0.002, f_off=0.0, fs=384000.0):
+    """n samples of programme + level m(t) cos(2 pi (57000 + f_off) t + phase), float64: what rds_reference receives and,
+    through mpx_iq, what the chain's discriminator hands to the RDS stage."""
+    t = np.arange(n, dtype=np.float64) / fs
+    return programme(t, kind) + level * rds_baseband(t, groups, t0) * np.cos(2 * np.pi * (57000.0 + f_off) * t + phase)
+
+
+def mpx_iq(mpx, fs=384000.0, amplitude=0.3):
+    """Constant-envelope, noise-free FM of the MPX (75 kHz deviation) as complex64.  Noise goes on the MPX before the
+    modulation: the phase discriminator then returns the MPX as generated, noise included, sample for sample (peak
+    |mpx| must stay below fs / 150000 = 2.56, where the phase step would wrap)."""
+    assert np.abs(mpx).max() < fs / 150000.0
+    return fm_iq(mpx, fs, amplitude=amplitude, sigma=0).astype(np.complex64)
