@@ -44,7 +44,7 @@ EXPORTS = [
     "fmr_enable_kernel_timing", "fmr_filter_table", "fmr_fourth_convert", "fmr_design_taps", "fmr_design_taps_class",
     "fmr_host_alloc", "fmr_host_free", "fmr_create_sized", "fmr_get_status_sized",
     "fmr_create_channelizer", "fmr_resample_blocks", "fmr_resample_blocks_device", "fmr_create_rds",
-    "fmr_get_rds_groups", "fmr_get_rds_status",
+    "fmr_get_rds_groups", "fmr_get_rds_status", "fmr_set_rds_correction",
     "fmr_spectrum_create", "fmr_spectrum_destroy", "fmr_spectrum_process", "fmr_spectrum_process_device",
     "fmr_spectrum_synchronize", "fmr_spectrum_read", "fmr_spectrum_reset", "fmr_find_stations",
 ]
@@ -52,6 +52,8 @@ EXPORTS = [
 WINDOW_HANN, WINDOW_RECT, WINDOW_BLACKMAN_HARRIS = 0, 1, 2
 # FMR_RDS_* (include/fmradion_amd.h): per-block status of an RDS group
 RDS_OK, RDS_CORRECTED, RDS_BAD, RDS_CPRIME = 0, 1, 2, 4
+# FMR_RDS_FEC_* (include/fmradion_amd.h): error correction of synchronised blocks (Chain.set_rds_correction)
+RDS_FEC_OFF, RDS_FEC_BURST, RDS_FEC_SOFT = 0, 1, 2
 # fmr_rds_group as a numpy structured type (24 bytes)
 RDS_GROUP = np.dtype([("sample_index", np.uint64), ("block", np.uint16, 4), ("status", np.uint8, 4), ("reserved", np.uint32)])
 
@@ -277,6 +279,11 @@ class RdsStatus(C.Structure):
                 ("carrier_offset_hz", C.c_double)]
 
 
+class RdsFec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("mode", C.c_int), ("max_burst", C.c_int), ("soft_symbols", C.c_int),
+                ("soft_max_cost", C.c_double)]
+
+
 def _rds_ok(g, i):
     return (int(g["status"][i]) & RDS_BAD) == 0
 
@@ -500,6 +507,21 @@ class Chain:
         L.fmr_get_rds_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(RdsStatus), C.c_size_t]
         self._chk(L.fmr_get_rds_status(self.h, int(stream), C.byref(st), C.sizeof(RdsStatus)))
         return st
+
+    def set_rds_correction(self, mode, max_burst=0, soft_symbols=0, soft_max_cost=0.0):
+        """fmr_set_rds_correction: RDS_FEC_OFF / RDS_FEC_BURST / RDS_FEC_SOFT for every stream, from each decoder's next
+        block boundary on (0 = the default: bursts of up to 2 bits, the 4 least reliable symbols, cost up to 1.0)."""
+        fec = RdsFec(C.sizeof(RdsFec), int(mode), int(max_burst), int(soft_symbols), float(soft_max_cost))
+        L = self._L
+        L.fmr_set_rds_correction.restype = C.c_int
+        L.fmr_set_rds_correction.argtypes = [C.c_void_p, C.POINTER(RdsFec), C.c_size_t]
+        self._chk(L.fmr_set_rds_correction(self.h, C.byref(fec), C.sizeof(RdsFec)))
+
+    def rds_reliabilities(self, stream=0, cap=1 << 16):
+        """fmr_debug_read 5: the signed reliabilities rho_k of the symbols the most recent call decided (float32)."""
+        buf = np.empty(cap, dtype=np.float32)
+        n = self._chk(self._L.fmr_debug_read(self.h, int(stream), 5, buf.ctypes.data_as(C.c_void_p), buf.nbytes))
+        return buf[:n].copy()
 
     def pps_events(self, stream=0):
         ev = (PpsEvent * 64)()

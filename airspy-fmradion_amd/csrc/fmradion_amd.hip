@@ -320,6 +320,7 @@ struct fmr_chain {
   unsigned long long *h_rds_mark = nullptr;  // calls whose RDS slot is filled
   long long rds_n = 0, rds_w = 0;            // MPX samples seen, next window
   unsigned long long rds_seq = 0, rds_drained = 0;
+  unsigned long long rds_tap_seq = 0;        // slot of the most recent call's windows (0: it completed none): fmr_debug_read 5
   double rds_gain = 1.0;                     // |soft symbol| of a unit subcarrier (injection estimate)
   std::vector<fmr_rds::Decoder> rds_dec;
   std::vector<RdsSlotHdr> rds_hdr;
@@ -2695,7 +2696,7 @@ int fmr_chain::rds_init() {
   if ((rc = d_rds_state.alloc((size_t)S))) return rc;
   if ((rc = d_rds_est.alloc((size_t)S * rds_maxw))) return rc;
   if ((rc = d_rds_rec.alloc((size_t)S * (rds_maxw + 1)))) return rc;
-  rds_slot_stride = (sizeof(RdsSlotHdr) + sizeof(RdsRec) * (size_t)rds_maxw + (size_t)kRdsMaxSym * rds_maxw + 63) & ~(size_t)63;
+  rds_slot_stride = (rds_slot_bytes(rds_maxw) + 63) & ~(size_t)63;
   HIPCHK(hipHostMalloc((void **)&h_rds_slots, rds_slot_stride * (size_t)S * kRdsSlots, hipHostMallocCoherent));
   HIPCHK(hipHostMalloc((void **)&h_rds_mark, sizeof(unsigned long long), hipHostMallocCoherent));
   *h_rds_mark = 0;
@@ -2706,6 +2707,7 @@ int fmr_chain::rds_init() {
 
 // one call's MPX (N samples per stream from the base slot) through the RDS stage, on stream st
 int fmr_chain::rds_stage(const fm_mpx_t *base, long long N, hipStream_t st) {
+  rds_tap_seq = 0;
   if (N <= 0) return FMR_OK;
   const long long base_stride = H_b + (long long)max_if;
   const long long n0 = rds_n, m0 = (n0 + kRdsD - 1) / kRdsD, m1 = (n0 + N + kRdsD - 1) / kRdsD;
@@ -2743,6 +2745,7 @@ int fmr_chain::rds_stage(const fm_mpx_t *base, long long N, hipStream_t st) {
   });
   hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, st, h_rds_mark, seq);
   rds_w += nw;
+  rds_tap_seq = seq;
   HIPCHK(hipGetLastError());
   return FMR_OK;
 }
@@ -2757,12 +2760,15 @@ void fmr_chain::rds_drain() {
       RdsSlotHdr h;
       memcpy(&h, sl, sizeof h);
       const RdsRec *rec = reinterpret_cast<const RdsRec *>(sl + sizeof(RdsSlotHdr));
-      const unsigned char *bits = reinterpret_cast<const unsigned char *>(sl + sizeof(RdsSlotHdr) + sizeof(RdsRec) * (size_t)rds_maxw);
+      const unsigned char *bits = reinterpret_cast<const unsigned char *>(sl + rds_slot_bits_off(rds_maxw));
+      const float *rho = reinterpret_cast<const float *>(sl + rds_slot_rho_off(rds_maxw));
       for (int w = 0; w < h.nw && w < rds_maxw; w++) {
         const RdsRec r = rec[w];
+        const float *rw = rho + (size_t)w * (kRdsMaxSym + 1);
+        if (r.count > 0) rds_dec[s].carried(rw[0]);
         for (int t = 0; t < r.count && t < kRdsMaxSym; t++) {
           const long long pos = (r.k_first + t) * kRdsSym + r.tau;       // [U]
-          rds_dec[s].push(bits[(size_t)w * kRdsMaxSym + t], pos > 0 ? (uint64_t)((pos + 9) / 19) : 0);
+          rds_dec[s].push(bits[(size_t)w * kRdsMaxSym + t], pos > 0 ? (uint64_t)((pos + 9) / 19) : 0, rw[t + 1]);
         }
       }
       rds_hdr[s] = h;
@@ -3480,7 +3486,24 @@ long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t 
   long long n = c->last_n_if;
   const void *src = nullptr;
   size_t esz = 0;
-  if (which == 5) {       // FMR_FE_STAMPS=1: {start, end [10 ns units of the constant clock], hardware id} per workgroup of the last fused launch
+  if (which == 5 && !c->d_fe_stamps.p) {      // the symbol reliabilities of the most recent call (chains with RDS)
+    if (!c->rds) { set_err("fmr_debug_read: tap 5 (RDS symbol reliabilities) needs a chain made by fmr_create_rds"); return FMR_ERR_BAD_ARG; }
+    c->rds_drain();
+    if (!c->rds_tap_seq) return 0;
+    const char *sl = c->h_rds_slots + ((size_t)(c->rds_tap_seq % fmr_chain::kRdsSlots) * c->S + stream) * c->rds_slot_stride;
+    RdsSlotHdr h;
+    memcpy(&h, sl, sizeof h);
+    const RdsRec *rec = reinterpret_cast<const RdsRec *>(sl + sizeof(RdsSlotHdr));
+    const float *rho = reinterpret_cast<const float *>(sl + rds_slot_rho_off(c->rds_maxw));
+    n = 0;
+    for (int w = 0; w < h.nw && w < c->rds_maxw; w++) n += std::min(std::max(rec[w].count, 0), kRdsMaxSym);
+    if ((size_t)n * sizeof(float) > cap_bytes) return FMR_ERR_CAPACITY;
+    float *o = reinterpret_cast<float *>(out);
+    for (int w = 0; w < h.nw && w < c->rds_maxw; w++)
+      for (int t = 0; t < rec[w].count && t < kRdsMaxSym; t++) *o++ = rho[(size_t)w * (kRdsMaxSym + 1) + t + 1];
+    return n;
+  }
+  if (which == 5) {       // FMR_FE_STAMPS=1 (diagnostics; the tap then keeps this meaning on every chain): {start, end [10 ns units of the constant clock], hardware id} per workgroup of the last fused launch
     if (!c->d_fe_stamps.p || stream != 0) return FMR_ERR_BAD_ARG;
     constexpr long long R = 2 * 16 * fmr_chain::kStampCalls;
     n = 3ll * c->fe_stamps_n;        // ... followed by the two rings of stream stamps (32 calls x 16 ids: constant clock, shader cycles) and the sequence number of the last call
@@ -3664,6 +3687,7 @@ int fmr_get_rds_status(fmr_chain *c, int stream, fmr_rds_status *st, size_t st_s
   full.synced = d.synced();
   full.blocks_ok = d.blocks_ok();
   full.blocks_bad = d.blocks_bad();
+  full.blocks_corrected = d.blocks_corrected();
   full.groups_decoded = d.groups_decoded();
   full.groups_dropped = d.groups_dropped();
   full.injection = h.level > 0.f ? std::sqrt((double)h.level) / c->rds_gain : 0.0;
@@ -3672,6 +3696,49 @@ int fmr_get_rds_status(fmr_chain *c, int stream, fmr_rds_status *st, size_t st_s
   full.carrier_offset_hz = h.freq_hz;
   memcpy(st, &full, st_size < sizeof full ? st_size : sizeof full);
   return FMR_OK;
+}
+
+int fmr_set_rds_correction(fmr_chain *c, const fmr_rds_fec *fec, size_t fec_size) {
+  if (!fec) { set_err("fmr_set_rds_correction: fec is null"); return FMR_ERR_BAD_ARG; }
+  const size_t size = fec_size ? fec_size : sizeof(fmr_rds_fec);
+  if (size > sizeof(fmr_rds_fec) || (size >= sizeof(unsigned) && fec->struct_size > sizeof(fmr_rds_fec))) {
+    set_err("fmr_set_rds_correction: struct_size %zu is larger than this library's fmr_rds_fec (%zu): the caller is newer "
+            "than the library", std::max(size, size >= sizeof(unsigned) ? (size_t)fec->struct_size : (size_t)0), sizeof(fmr_rds_fec));
+    return FMR_ERR_BAD_ARG;
+  }
+  fmr_rds_fec full;
+  memset(&full, 0, sizeof full);
+  memcpy(&full, fec, size);
+  fmr_rds::Correction k;
+  k.mode = full.mode;
+  if (full.max_burst) k.max_burst = full.max_burst;
+  if (full.soft_symbols) k.soft_symbols = full.soft_symbols;
+  if (full.soft_max_cost != 0.0) k.soft_max_cost = full.soft_max_cost;
+  if (k.mode != FMR_RDS_FEC_OFF && k.mode != FMR_RDS_FEC_BURST && k.mode != FMR_RDS_FEC_SOFT) {
+    set_err("fmr_set_rds_correction: mode %d is none of FMR_RDS_FEC_OFF / BURST / SOFT", k.mode);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (k.max_burst < 1 || k.max_burst > fmr_rds::kMaxBurst) {
+    set_err("fmr_set_rds_correction: max_burst %d is outside 1 .. %d (0 = default)", k.max_burst, fmr_rds::kMaxBurst);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (k.soft_symbols < 1 || k.soft_symbols > fmr_rds::kMaxSoftSymbols) {
+    set_err("fmr_set_rds_correction: soft_symbols %d is outside 1 .. %d (0 = default)", k.soft_symbols, fmr_rds::kMaxSoftSymbols);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!(k.soft_max_cost >= 0.0) || !std::isfinite(k.soft_max_cost)) {
+    set_err("fmr_set_rds_correction: soft_max_cost %g is not a finite value >= 0", k.soft_max_cost);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!c) { set_err("fmr_set_rds_correction: chain is null"); return FMR_ERR_BAD_ARG; }
+  if (!c->rds) { set_err("fmr_set_rds_correction: the chain was created without the RDS decoder (fmr_create_rds)"); return FMR_ERR_BAD_ARG; }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    c->rds_drain();
+    for (fmr_rds::Decoder &d : c->rds_dec) d.set_correction(k);
+    return FMR_OK;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
 int fmr_filter_table(const char *name, const void **data, int *is_double) {

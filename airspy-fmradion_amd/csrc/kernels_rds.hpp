@@ -21,8 +21,9 @@
 //                candidate phases (parabolic refinement), and sum s^2 of the soft symbols at that timing
 //   k_rds_scan   one lane per stream walks the call's windows: keeps the timing continuous, unwraps the carrier phase
 //                arg(sum s^2) / 2 modulo pi against a tracked frequency term, assigns the symbols to windows
-//   k_rds_bits   per window: soft biphase symbol s = y2(start) - y2(mid) at the scan's timing, hard bit of
-//                Re(s e^{-i theta}), differential decoding (the pi ambiguity of the carrier cancels), out to host memory
+//   k_rds_bits   per window: soft biphase symbol s = y2(start) - y2(mid) at the scan's timing, decision variable
+//                d = Re(s e^{-i theta}), hard bit of its sign, differential decoding (the pi ambiguity of the carrier
+//                cancels), and the reliability rho = d / sqrt(window energy) of every symbol, out to host memory
 // A non-finite MPX sample is read as 0: nothing non-finite reaches an estimate or a bit.  y1 and y2 live in per-stream
 // rings of R (a power of two) samples indexed by m mod R; a ring holds the call plus four windows of history.
 #pragma once
@@ -67,6 +68,15 @@ struct RdsSlotHdr {        // per stream, in front of the records and bits of a 
   float tau_samples, theta, freq_hz, level;    // the scan's estimates after the call's last window
   float timing_frac, pad2;                     // timing within a symbol [symbols]
 };
+
+// A stream's part of a host slot: RdsSlotHdr, max_w RdsRec, max_w x kRdsMaxSym bits (bytes), then max_w x
+// (kRdsMaxSym + 1) reliabilities (floats): per window the symbol before its first (the one the differential decoding
+// reads, under the window before's record) and then its symbols.
+__host__ __device__ inline size_t rds_slot_bits_off(int max_w) { return sizeof(RdsSlotHdr) + sizeof(RdsRec) * (size_t)max_w; }
+__host__ __device__ inline size_t rds_slot_rho_off(int max_w) { return rds_slot_bits_off(max_w) + (size_t)kRdsMaxSym * max_w; }
+__host__ __device__ inline size_t rds_slot_bytes(int max_w) {
+  return rds_slot_rho_off(max_w) + sizeof(float) * (size_t)(kRdsMaxSym + 1) * max_w;
+}
 
 __device__ __forceinline__ float rds_fin(float v) { return isfinite(v) ? v : 0.f; }
 
@@ -235,16 +245,23 @@ __global__ void k_rds_scan(const RdsEst *__restrict__ est, int nw, long long w0,
                  (float)(tf / P), 0.f};
 }
 
-// hard decision of symbol k under record r: the sign of Re(s e^{-i phase}), phase = theta + fr (k - kmid)
-__device__ __forceinline__ int rds_hard(const float2 *__restrict__ y, int R, const RdsRec &r, long long k) {
+// decision variable of symbol k under record r: Re(s e^{-i phase}), phase = theta + fr (k - kmid); the hard decision is
+// its sign
+__device__ __forceinline__ float rds_decide(const float2 *__restrict__ y, int R, const RdsRec &r, long long k) {
   const float2 v = rds_soft(y, R, k * kRdsSym + r.tau);
   const float ph = r.theta + r.fr * (float)((double)k - r.kmid);
   float sn, cs;
   sincosf(ph, &sn, &cs);
-  return (v.x * cs + v.y * sn) < 0.f ? 1 : 0;
+  return v.x * cs + v.y * sn;
 }
 
-// grid (nw, S), 128 lanes: bits of window wl (one symbol per lane); records and bits go to the host slot of the call
+// reliability of a decision: d in units of the record's rms symbol level (0 where the window carried nothing)
+__device__ __forceinline__ float rds_rho(float d, const RdsRec &r) {
+  return r.energy > 0.f ? rds_fin(d / sqrtf(r.energy)) : 0.f;
+}
+
+// grid (nw, S), 128 lanes: bits and reliabilities of window wl (one symbol per lane); records, bits and reliabilities go
+// to the host slot of the call
 __global__ __launch_bounds__(128) void k_rds_bits(const float2 *__restrict__ y2, int R, const RdsRec *__restrict__ rec,
                                                   int max_w, char *__restrict__ slot, size_t slot_stride) {
   __shared__ int hs[kRdsMaxSym + 1];
@@ -254,12 +271,19 @@ __global__ __launch_bounds__(128) void k_rds_bits(const float2 *__restrict__ y2,
   const float2 *y = y2 + (long long)s * R;
   char *sl = slot + (size_t)s * slot_stride;
   RdsRec *hrec = reinterpret_cast<RdsRec *>(sl + sizeof(RdsSlotHdr));
-  unsigned char *bits = reinterpret_cast<unsigned char *>(sl + sizeof(RdsSlotHdr) + sizeof(RdsRec) * (size_t)max_w) +
-                        (size_t)wl * kRdsMaxSym;
-  if (t < r.count) hs[t + 1] = rds_hard(y, R, r, r.k_first + t);
+  unsigned char *bits = reinterpret_cast<unsigned char *>(sl + rds_slot_bits_off(max_w)) + (size_t)wl * kRdsMaxSym;
+  float *rho = reinterpret_cast<float *>(sl + rds_slot_rho_off(max_w)) + (size_t)wl * (kRdsMaxSym + 1);
+  if (t < r.count) {                                        // (count <= kRdsMaxSym: the scan clamps it)
+    const float d = rds_decide(y, R, r, r.k_first + t);
+    hs[t + 1] = d < 0.f ? 1 : 0;
+    rho[t + 1] = rds_rho(d, r);
+  }
   if (t == 0) {
     const RdsRec p = rs[wl];                                // the window before (of this call, or carried)
-    hs[0] = (p.valid && p.count > 0) ? rds_hard(y, R, p, r.k_first - 1) : 0;
+    const bool have = p.valid && p.count > 0;
+    const float d = have ? rds_decide(y, R, p, r.k_first - 1) : 0.f;
+    hs[0] = d < 0.f ? 1 : 0;
+    rho[0] = have ? rds_rho(d, p) : 0.f;
     hrec[wl] = r;
   }
   __syncthreads();

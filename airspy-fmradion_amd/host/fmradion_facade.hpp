@@ -78,6 +78,13 @@ inline fmr_chain *make(const fmr_config &cfg0, bool rds = false) {
   else check(fmr_create(&cfg, &c), "fmr_create");
   return c;
 }
+inline void rds_correction(fmr_chain *c, int mode, int max_burst, int soft_symbols, double soft_max_cost) {
+  fmr_rds_fec fec{};
+  fec.struct_size = sizeof fec;
+  fec.mode = mode; fec.max_burst = max_burst; fec.soft_symbols = soft_symbols; fec.soft_max_cost = soft_max_cost;
+  check(fmr_set_rds_correction(c, &fec, sizeof fec), "fmr_set_rds_correction");
+}
+
 // the RDS groups of one stream decoded so far (drained from its queue), also collected into `station`
 inline std::vector<fmr_rds_group> rds_groups(fmr_chain *c, int stream, fmr_rds::Station &station) {
   std::vector<fmr_rds_group> out;
@@ -230,6 +237,11 @@ public:
     m_rds = true;
     fmr_destroy(m_chain);
     m_chain = fmr_detail::make(m_cfg, true);
+  }
+  // error correction of the RDS blocks (fmr_set_rds_correction: FMR_RDS_FEC_OFF / _BURST / _SOFT; 0 = the defaults); at
+  // any time after enable_rds(), from the decoder's next block boundary on.  enable_rds() starts with it off.
+  void set_rds_correction(int mode, int max_burst = 0, int soft_symbols = 0, double soft_max_cost = 0.0) {
+    fmr_detail::rds_correction(m_chain, mode, max_burst, soft_symbols, soft_max_cost);
   }
   std::vector<fmr_rds_group> get_rds_groups() { return fmr_detail::rds_groups(m_chain, 0, m_station); }
   const fmr_rds::Station &rds_station() { get_rds_groups(); return m_station; }
@@ -492,6 +504,10 @@ public:
     m_cfg.channel_offset_hz = m_offsets.data();
     m_chain = fmr_detail::make(m_cfg, true);
     m_stations.assign(m_offsets.size(), fmr_rds::Station());
+  }
+  // error correction of every channel's RDS blocks (fmr_set_rds_correction), at any time after enable_rds()
+  void set_rds_correction(int mode, int max_burst = 0, int soft_symbols = 0, double soft_max_cost = 0.0) {
+    fmr_detail::rds_correction(m_chain, mode, max_burst, soft_symbols, soft_max_cost);
   }
   std::vector<fmr_rds_group> get_rds_groups(size_t ch) {
     if (ch >= m_offsets.size() || m_stations.empty()) fmr_detail::fail("ChannelBank: no RDS on this channel (enable_rds)");

@@ -9,7 +9,21 @@
 //     last valid syndrome is remembered per bit phase modulo 26, so a false one in between does not hide a true pair.
 //   * Synchronised: every 26 bits one block of the expected position; a block whose syndrome is not that position's
 //     offset is "bad".  kLoseSync bad blocks in a row drop the synchronisation, and acquisition starts again.
-//   * Error detection only: no burst correction (the status value FMR_RDS_CORRECTED is never produced).
+//   * Error correction (set_correction; off by default), for synchronised blocks only -- acquisition always works on
+//     uncorrected syndromes.  The error syndrome of a bad block is its syndrome xor the expected offset's syndrome.
+//       burst  the error syndrome is looked up among all bursts of up to max_burst bits (1 .. 5, default 2; bursts of up
+//              to five bits have distinct syndromes in this code, so a longer one is never taken for a shorter one).  A
+//              wrong symbol gives two adjacent wrong bits after differential decoding: a burst of two.
+//       soft   with a reliability |rho| per symbol (push with three arguments): of the 27 symbols the block's bits
+//              depend on, the soft_symbols (1 .. 8, default 4) least reliable ones are tried in every non-empty
+//              combination; flipping a symbol toggles its two bits (one, at either edge of the block).  The combination
+//              that gives the expected syndrome at the smallest summed |rho| is taken if that sum is at most
+//              soft_max_cost (default 1.0, one full symbol).  A block with a bit pushed without reliability is treated
+//              in burst mode.
+//     Position 3 takes C or C': the offset block B's version bit names if B is good or corrected, otherwise both, the
+//     shorter burst / lower cost winning and a tie going to C.  A corrected block has status FMR_RDS_CORRECTED, counts in
+//     blocks_corrected, and leaves the run of bad blocks as it is: it neither extends nor ends it, so miscorrected noise
+//     cannot hold a false lock.
 //   * A group is queued when its four positions have been received in synchronisation; a group whose acquisition
 //     happened inside it after its block A is not queued (acquired on D-A, the A opens the next group).  A full queue drops its oldest group and counts it.
 //
@@ -77,36 +91,69 @@ inline int offset_of(uint16_t syn) {
   return -1;
 }
 inline int slot_of(int off) { return off <= 1 ? off : off == 4 ? 3 : 2; }   // group position 0..3 of an offset
+inline uint16_t syndrome_of_offset(int off) {
+  static const uint16_t s[5] = {offset_syndrome(kOffsetA), offset_syndrome(kOffsetB), offset_syndrome(kOffsetC),
+                                offset_syndrome(kOffsetCp), offset_syndrome(kOffsetD)};
+  return s[off];
+}
+
+// every burst of up to kMaxBurst bits at every place of a 26-bit block, by its syndrome (all distinct): pattern and length
+constexpr int kMaxBurst = 5, kMaxSoftSymbols = 8, kBlockSymbols = 27;
+struct BurstTable {
+  uint32_t pattern[1024];
+  uint8_t length[1024];                     // 0: no burst of up to kMaxBurst bits has this syndrome
+  bool distinct = true;
+  BurstTable() {
+    for (int i = 0; i < 1024; i++) { pattern[i] = 0; length[i] = 0; }
+    for (int len = 1; len <= kMaxBurst; len++)
+      for (uint32_t mid = 0; mid < (len > 2 ? 1u << (len - 2) : 1u); mid++) {
+        const uint32_t shape = len == 1 ? 1u : (1u << (len - 1)) | (mid << 1) | 1u;
+        for (int at = 0; at + len <= 26; at++) {
+          const uint16_t syn = syndrome(shape << at);
+          if (length[syn]) distinct = false;
+          pattern[syn] = shape << at;
+          length[syn] = (uint8_t)len;
+        }
+      }
+  }
+};
+inline const BurstTable &burst_table() { static const BurstTable t; return t; }
+
+struct Correction {                        // mode: FMR_RDS_FEC_*
+  int mode = FMR_RDS_FEC_OFF, max_burst = 2, soft_symbols = 4;
+  double soft_max_cost = 1.0;
+};
 
 class Decoder {
 public:
-  // one data bit (0 / 1) and the 384 kHz sample index of its symbol
-  void push(int bit, uint64_t sample_index) {
-    reg_ = ((reg_ << 1) | (uint32_t)(bit & 1)) & 0x3FFFFFFu;
-    idx_[nbits_ % 32] = sample_index;
-    nbits_++;
-    if (nbits_ < 26) return;
-    if (!synced_) { acquire(); return; }
-    if (++in_block_ < 26) return;
-    in_block_ = 0;
-    const uint16_t info = (uint16_t)(reg_ >> 10);
-    const int off = offset_of(syndrome(reg_));
-    const int want = expect_;
-    const bool ok = want == 2 ? (off == 2 || off == 3) : (off >= 0 && slot_of(off) == want);
-    if (ok) {
-      blocks_ok_++; bad_run_ = 0;
-      store(want, info, off == 3 ? FMR_RDS_CPRIME : 0, first_index());
-    } else {
-      blocks_bad_++;
-      store(want, info, FMR_RDS_BAD, first_index());
-      if (++bad_run_ >= kLoseSync) { synced_ = false; have_ = 0; bad_run_ = 0; }
-    }
-    expect_ = (want + 1) & 3;
+  // one data bit (0 / 1) and the 384 kHz sample index of its symbol: no reliability
+  void push(int bit, uint64_t sample_index) { push_bit(bit, sample_index, -1.f); }
+  // ... with the symbol's reliability rho (its decision variable in units of the signal level; the sign is not read).
+  // The bit also depends on the symbol before, whose reliability is that of the push before (or what carried() set).
+  void push(int bit, uint64_t sample_index, float reliability) {
+    const float a = reliability < 0.f ? -reliability : reliability;
+    push_bit(bit, sample_index, a >= 0.f ? a : 0.f);                       // (NaN counts as unreliable)
   }
+  // the reliability of the symbol before the next push, where the caller knows it better than the push before did
+  void carried(float reliability) {
+    const float a = reliability < 0.f ? -reliability : reliability;
+    rel_[(nbits_ + 31) % 32] = a >= 0.f ? a : 0.f;
+  }
+  // error correction from the next block boundary on (while not synchronised: at once); false: out of range
+  bool set_correction(const Correction &c) {
+    if (c.mode != FMR_RDS_FEC_OFF && c.mode != FMR_RDS_FEC_BURST && c.mode != FMR_RDS_FEC_SOFT) return false;
+    if (c.max_burst < 1 || c.max_burst > kMaxBurst || c.soft_symbols < 1 || c.soft_symbols > kMaxSoftSymbols) return false;
+    if (!(c.soft_max_cost >= 0.0)) return false;
+    next_ = c;
+    if (!synced_ || in_block_ == 0) fec_ = next_;
+    return true;
+  }
+  const Correction &correction() const { return next_; }
 
   bool synced() const { return synced_; }
   uint64_t blocks_ok() const { return blocks_ok_; }
   uint64_t blocks_bad() const { return blocks_bad_; }
+  uint64_t blocks_corrected() const { return blocks_corrected_; }
   uint64_t groups_dropped() const { return dropped_; }
   uint64_t groups_decoded() const { return decoded_; }
   size_t queued() const { return q_.size(); }
@@ -118,6 +165,92 @@ public:
   }
 
 private:
+  void push_bit(int bit, uint64_t sample_index, float rel) {
+    reg_ = ((reg_ << 1) | (uint32_t)(bit & 1)) & 0x3FFFFFFu;
+    idx_[nbits_ % 32] = sample_index;
+    rel_[nbits_ % 32] = rel;
+    nbits_++;
+    if (nbits_ < 26) return;
+    if (!synced_) { fec_ = next_; acquire(); return; }
+    if (++in_block_ < 26) return;
+    in_block_ = 0;
+    const uint16_t info = (uint16_t)(reg_ >> 10);
+    const int off = offset_of(syndrome(reg_));
+    const int want = expect_;
+    const bool ok = want == 2 ? (off == 2 || off == 3) : (off >= 0 && slot_of(off) == want);
+    Fix fix;
+    if (ok) {
+      blocks_ok_++; bad_run_ = 0;
+      store(want, info, off == 3 ? FMR_RDS_CPRIME : 0, first_index());
+    } else if (fec_.mode != FMR_RDS_FEC_OFF && correct(want, fix)) {
+      blocks_corrected_++;
+      store(want, (uint16_t)((reg_ ^ fix.pattern) >> 10), FMR_RDS_CORRECTED | (fix.off == 3 ? FMR_RDS_CPRIME : 0), first_index());
+    } else {
+      blocks_bad_++;
+      store(want, info, FMR_RDS_BAD, first_index());
+      if (++bad_run_ >= kLoseSync) { synced_ = false; have_ = 0; bad_run_ = 0; }
+    }
+    expect_ = (want + 1) & 3;
+    fec_ = next_;
+  }
+
+  struct Fix { uint32_t pattern = 0; int off = -1; double key = 0.0; };
+  // the block in reg_ against offset `off`: the error pattern of the active mode and its key (burst length or cost)
+  bool fix_for(int off, bool soft, Fix &f) const {
+    const uint16_t es = (uint16_t)(syndrome(reg_) ^ syndrome_of_offset(off));
+    f.off = off;
+    if (!soft) {
+      const BurstTable &t = burst_table();
+      if (t.length[es] == 0 || t.length[es] > fec_.max_burst) return false;
+      f.pattern = t.pattern[es]; f.key = t.length[es];
+      return true;
+    }
+    // symbol j = 0 .. 26 of the block: the one before its first bit, then the symbols of its 26 bits; its reliability
+    // is that of push nbits_ - 27 + j, and flipping it toggles the bits on air j - 1 and j (bit on air i = bit 25 - i)
+    int pick[kMaxSoftSymbols];
+    const int m = fec_.soft_symbols;
+    bool used[kBlockSymbols] = {};
+    for (int q = 0; q < m; q++) {                       // the m least reliable, the earlier symbol first among equals
+      int best = -1;
+      for (int j = 0; j < kBlockSymbols; j++)
+        if (!used[j] && (best < 0 || rel_at(j) < rel_at(best))) best = j;
+      used[best] = true; pick[q] = best;
+    }
+    uint32_t pat[kMaxSoftSymbols]; uint16_t syn[kMaxSoftSymbols];
+    for (int q = 0; q < m; q++) {
+      const int j = pick[q];
+      pat[q] = (j >= 1 ? 1u << (26 - j) : 0u) | (j <= 25 ? 1u << (25 - j) : 0u);
+      syn[q] = syndrome(pat[q]);
+    }
+    bool found = false;
+    for (unsigned mask = 1; mask < (1u << m); mask++) {
+      uint16_t sy = 0; uint32_t p = 0; double cost = 0.0;
+      for (int q = 0; q < m; q++)
+        if (mask >> q & 1) { sy ^= syn[q]; p ^= pat[q]; cost += (double)rel_at(pick[q]); }
+      if (sy != es || (found && !(cost < f.key))) continue;
+      found = true; f.pattern = p; f.key = cost;
+    }
+    return found && f.key <= fec_.soft_max_cost;
+  }
+  float rel_at(int j) const { return rel_[(nbits_ - 27 + j) % 32]; }
+  bool correct(int want, Fix &best) const {
+    bool soft = fec_.mode == FMR_RDS_FEC_SOFT;
+    if (soft) {
+      if (nbits_ < 27) soft = false;
+      for (int j = 0; soft && j < kBlockSymbols; j++)
+        if (rel_at(j) < 0.f) soft = false;               // a bit without reliability: burst mode for this block
+    }
+    if (want != 2) return fix_for(want == 3 ? 4 : want, soft, best);
+    // C or C': what a good (or corrected) block B says, otherwise both; the smaller key wins, a tie goes to C
+    const bool b_known = (have_ & 2u) && !(cur_.status[1] & FMR_RDS_BAD);
+    const bool ver_b = b_known && ((cur_.block[1] >> 11) & 1);
+    Fix c, cp;
+    const bool hc = (!b_known || !ver_b) && fix_for(2, soft, c);
+    const bool hp = (!b_known || ver_b) && fix_for(3, soft, cp);
+    if (!hc && !hp) return false;
+    best = hc && (!hp || c.key <= cp.key) ? c : cp;
+    return true;
+  }
   uint64_t first_index() const { return idx_[(nbits_ - 26) % 32]; }
   // a valid syndrome is remembered per bit phase (mod 26): a false hit in between does not hide the true hit 26 bits back
   void acquire() {
@@ -152,6 +285,8 @@ private:
   uint32_t reg_ = 0;
   uint64_t nbits_ = 0;
   uint64_t idx_[32] = {};
+  float rel_[32] = {};                       // |rho| of the symbol of each bit; < 0: pushed without reliability
+  Correction fec_, next_;                    // in force for the block being received; from the next block boundary
   bool synced_ = false;
   int in_block_ = 0, expect_ = 0, bad_run_ = 0;
   struct Hit { bool valid; int slot; uint16_t info; uint64_t at, index; };
@@ -159,11 +294,11 @@ private:
   fmr_rds_group cur_{};
   unsigned have_ = 0;
   std::deque<fmr_rds_group> q_;
-  uint64_t blocks_ok_ = 0, blocks_bad_ = 0, dropped_ = 0, decoded_ = 0;
+  uint64_t blocks_ok_ = 0, blocks_bad_ = 0, blocks_corrected_ = 0, dropped_ = 0, decoded_ = 0;
 };
 
 // ---- parser: programme identification, programme type, programme service name (0A / 0B), RadioText (2A / 2B).  Only
-// blocks whose status is FMR_RDS_OK (or corrected) are read.
+// blocks whose status is FMR_RDS_OK or FMR_RDS_CORRECTED are read.
 inline bool block_ok(const fmr_rds_group &g, int i) { return (g.status[i] & FMR_RDS_BAD) == 0; }
 inline int group_type(const fmr_rds_group &g) { return g.block[1] >> 12; }
 inline int group_version_b(const fmr_rds_group &g) { return (g.block[1] >> 11) & 1; }

@@ -304,7 +304,9 @@ int fmr_get_multipath_coefficients(fmr_chain *c, int stream, float *coeff, int c
  * most recent call to the host.  which: 0 = IF samples entering the decoder
  * (complex float, 2 floats each), 1 = discriminator output (float),
  * 2 = stereo difference after demod+de-emphasis (double), 3 = mono after
- * de-emphasis (double), 4 = AGC gain sequence (float).  Returns element count, or FMR_ERR_BAD_ARG for a
+ * de-emphasis (double), 4 = AGC gain sequence (float), 5 = on a chain made by fmr_create_rds, the signed symbol
+ * reliabilities rho_k (float) of the symbols the most recent call decided, in symbol order (FMR_ERR_BAD_ARG on a
+ * chain without RDS).  Returns element count, or FMR_ERR_BAD_ARG for a
  * tap the most recent call did not leave in memory: behind the fused front end's discriminator epilogue (FM at
  * 10 MS/s without IF filter / equaliser) taps 0, 1 and 4 exist only in a chain created with FMR_DEBUG_TAPS=1 in the
  * environment -- the product keeps those signals on chip. */
@@ -351,19 +353,19 @@ int fmr_filter_table(const char *name, const void **data, int *is_double);
  * quadrature with 3 x pilot) and hands the bits to a host decoder per stream (airspy-fmradion_amd/host/fmradion_rds.hpp:
  * 26-bit blocks, checkword of g(x) = x^10+x^8+x^7+x^5+x^4+x^3+1 plus the offset words A 0x0FC, B 0x198, C 0x168,
  * C' 0x350, D 0x1B4, acquisition on two consecutive valid syndromes, loss of synchronisation after 8 bad blocks in a row,
- * error detection only).  The decoded groups do not depend on how the input is cut into blocks and calls.
+ * error correction by burst trapping or soft-decision block repair on request: fmr_set_rds_correction).  The decoded groups do not depend on how the input is cut into blocks and calls.
  * One RDS group: four 16-bit blocks in the order A, B, C (or C'), D, a status per block and the absolute 384 kHz MPX
  * sample index (counted from the chain's first sample) at which the group's first bit starts. */
 enum {
   FMR_RDS_OK = 0,             /* the block's syndrome is its position's offset */
-  FMR_RDS_CORRECTED = 1,      /* (reserved: burst correction is not built) */
+  FMR_RDS_CORRECTED = 1,      /* the block was bad and fmr_set_rds_correction's mode repaired it: the 16 bits are the repaired ones */
   FMR_RDS_BAD = 2,            /* syndrome mismatch: the block's 16 bits are as received */
   FMR_RDS_CPRIME = 4          /* block 3 carried offset C' (version-B groups) instead of C */
 };
 typedef struct {
   uint64_t sample_index;
   uint16_t block[4];
-  uint8_t status[4];          /* FMR_RDS_OK | FMR_RDS_BAD, | FMR_RDS_CPRIME on block 3 */
+  uint8_t status[4];          /* FMR_RDS_OK | FMR_RDS_CORRECTED | FMR_RDS_BAD, | FMR_RDS_CPRIME on block 3 */
   uint32_t reserved;
 } fmr_rds_group;
 typedef struct {
@@ -391,6 +393,28 @@ int fmr_create_rds(const fmr_config *cfg, size_t cfg_size, fmr_chain **out);
 int fmr_get_rds_groups(fmr_chain *c, int stream, fmr_rds_group *groups, int cap);
 /* Counters and estimates of stream `stream` (synchronises); st_size = sizeof(fmr_rds_status) as the caller knows it. */
 int fmr_get_rds_status(fmr_chain *c, int stream, fmr_rds_status *st, size_t st_size);
+
+/* Error correction of synchronised blocks ("Error correction"; the rules are written out in
+ * host/fmradion_rds.hpp).  BURST: the error syndrome of a bad block is looked up among all bursts of up to max_burst
+ * bits (1 .. 5; 0 = the default, 2: one wrong symbol is two adjacent wrong bits).  SOFT: the device stage hands over the
+ * reliability of every symbol; the soft_symbols (1 .. 8; 0 = 4) least reliable of the block's 27 symbols are flipped in
+ * every combination and the cheapest one that gives the expected syndrome is taken if its summed reliability is at most
+ * soft_max_cost (>= 0, in units of the symbol level; 0 = 1.0).  Acquisition always works on uncorrected syndromes, and
+ * a corrected block neither extends nor ends the run of eight bad blocks that drops the synchronisation. */
+enum { FMR_RDS_FEC_OFF = 0, FMR_RDS_FEC_BURST = 1, FMR_RDS_FEC_SOFT = 2 };
+typedef struct {
+  unsigned struct_size;       /* sizeof(fmr_rds_fec) as the caller knows it (0: fec_size) */
+  int mode;                   /* FMR_RDS_FEC_* */
+  int max_burst;
+  int soft_symbols;
+  double soft_max_cost;
+} fmr_rds_fec;
+/* Synchronises, then sets the correction of every stream / channel of the chain; each decoder takes it from its next
+ * block boundary on.  May be called at any time; after fmr_create_rds the mode is OFF, and groups, statuses and audio
+ * are then what they were before this call existed.  FMR_ERR_BAD_ARG (fmr_last_error names the field) for an unknown
+ * mode, a value out of range, a size larger than this library's fmr_rds_fec, and for a chain created without RDS; the
+ * fields are checked before the chain is looked at. */
+int fmr_set_rds_correction(fmr_chain *c, const fmr_rds_fec *fec, size_t fec_size);
 
 /* --- Band spectrum and station finder (no counterpart in the reference).  A handle of its own:
  * a Welch power spectrum (mean and peak hold) of n_rows IQ rows on the GPU, and a host-side finder that turns a spectrum

@@ -1,9 +1,10 @@
-"""RDS cost (fmr_create_rds): the bench-shaped step with RDS off and on.
+"""RDS cost (fmr_create_rds): the bench-shaped step with RDS off, on, and on with soft-decision error
+correction (fmr_set_rds_correction, FMR_RDS_FEC_SOFT).
 
 10 MS/s FM stereo, 2^27 capture samples per step in 65536-sample blocks (bench.py's step) for one stream, and the
 32-channel bank of tools/bench_channel_bank.py (2^23 samples per step), device buffers in and out, asynchronous calls,
 one synchronisation per step; the groups are drained once per step (what a live receiver does).  Prints one JSON line per
-shape: ms per step off / on, the difference, and the medians of the RDS kernels' own times ("rds_mix": mix + low-pass +
+shape: ms per step off / on / on with soft correction, the differences, and the medians of the RDS kernels' own times ("rds_mix": mix + low-pass +
 matched filter + MPX history; "rds_sym": window estimates + scan + bits) from the chain's kernel timing in a separate
 pass.
 Usage: python tools/bench_rds.py [--steps 10] [--warmup 3] [--shapes 1 32] [--out FILE]
@@ -80,11 +81,16 @@ def main():
         astride = 2 * (N * 48000 // F + 64 * nb)
         d_out = torch.zeros((K, astride), dtype=torch.float64, device="cuda")
         res = {}
-        for rds in (False, True):
+        for leg in ("off", "on", "soft"):
+            rds = leg != "off"
             ch = fmr.Chain(mode=fmr.MODE_FM, input_rate=float(F), enable_resampler=True, stereo=True, max_block_len=BLK,
                            max_blocks=nb, enable_rds=rds, **kw)
-            res[rds] = timed(ch, d_x, N, nb, d_out, astride, a.steps, a.warmup, torch, K)
-            if rds:
+            if leg == "soft":
+                ch.set_rds_correction(fmr.RDS_FEC_SOFT)
+            res[leg] = timed(ch, d_x, N, nb, d_out, astride, a.steps, a.warmup, torch, K)
+            if leg == "soft":
+                corrected = sum(ch.rds_status(s).blocks_corrected for s in range(K))
+            if leg == "on":
                 ch.enable_kernel_timing(1)
                 kt = {}
                 for _ in range(3):
@@ -98,8 +104,9 @@ def main():
                 synced = sum(ch.rds_status(s).synced for s in range(K))
             ch.close()
         rec = dict(tool="bench_rds", channels=K, samples_per_step=N, steps=a.steps, warmup=a.warmup,
-                   off_ms_per_step=round(res[False] * 1e3, 4), on_ms_per_step=round(res[True] * 1e3, 4),
-                   rds_cost_ms=round((res[True] - res[False]) * 1e3, 4),
+                   off_ms_per_step=round(res["off"] * 1e3, 4), on_ms_per_step=round(res["on"] * 1e3, 4),
+                   rds_cost_ms=round((res["on"] - res["off"]) * 1e3, 4), soft_ms_per_step=round(res["soft"] * 1e3, 4),
+                   soft_cost_ms=round((res["soft"] - res["on"]) * 1e3, 4), blocks_corrected=int(corrected),
                    rds_kernels_ms={k: round(float(np.median(v)), 4) for k, v in kt.items()},
                    channels_synced=int(synced), groups_last_pass=int(groups), injection_ch0=round(st.injection, 5))
         line = json.dumps(rec)
