@@ -47,9 +47,12 @@ EXPORTS = [
     "fmr_get_rds_groups", "fmr_get_rds_status", "fmr_set_rds_correction",
     "fmr_spectrum_create", "fmr_spectrum_destroy", "fmr_spectrum_process", "fmr_spectrum_process_device",
     "fmr_spectrum_synchronize", "fmr_spectrum_read", "fmr_spectrum_reset", "fmr_find_stations",
+    "fmr_spectrum_create_waterfall", "fmr_spectrum_read_waterfall",
 ]
 # FMR_WINDOW_* (include/fmradion_amd.h): windows of the band spectrum
 WINDOW_HANN, WINDOW_RECT, WINDOW_BLACKMAN_HARRIS = 0, 1, 2
+# FMR_WATERFALL_* (include/fmradion_amd.h): what a waterfall line holds
+WATERFALL_MEAN, WATERFALL_PEAK = 0, 1
 # FMR_RDS_* (include/fmradion_amd.h): per-block status of an RDS group
 RDS_OK, RDS_CORRECTED, RDS_BAD, RDS_CPRIME = 0, 1, 2, 4
 # FMR_RDS_FEC_* (include/fmradion_amd.h): error correction of synchronised blocks (Chain.set_rds_correction)
@@ -103,6 +106,15 @@ class SpectrumConfig(C.Structure):
 class SpectrumInfo(C.Structure):
     _fields_ = [("segments", C.c_uint64), ("segments_skipped", C.c_uint64), ("first_segment", C.c_uint64),
                 ("samples_seen", C.c_uint64), ("bin_hz", C.c_double), ("enbw_hz", C.c_double)]
+
+
+class WaterfallConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("segments_per_line", C.c_int), ("max_lines", C.c_int), ("which", C.c_int)]
+
+
+class WaterfallInfo(C.Structure):
+    _fields_ = [("first_line", C.c_uint64), ("lines_ready", C.c_uint64), ("lines_dropped", C.c_uint64),
+                ("line_seconds", C.c_double)]
 
 
 class StationRule(C.Structure):
@@ -206,6 +218,11 @@ def lib(ab=False):
     L.fmr_spectrum_read.argtypes = [vp, C.c_int, C.c_int, dp, C.c_size_t, C.POINTER(SpectrumInfo)]
     L.fmr_spectrum_reset.restype = C.c_int
     L.fmr_spectrum_reset.argtypes = [vp]
+    L.fmr_spectrum_create_waterfall.restype = C.c_int
+    L.fmr_spectrum_create_waterfall.argtypes = [C.POINTER(SpectrumConfig), C.c_size_t, C.POINTER(WaterfallConfig), C.c_size_t,
+                                                C.POINTER(vp)]
+    L.fmr_spectrum_read_waterfall.restype = C.c_int
+    L.fmr_spectrum_read_waterfall.argtypes = [vp, C.c_int, fp, u32p, C.c_size_t, C.POINTER(WaterfallInfo)]
     L.fmr_find_stations.restype = C.c_int
     L.fmr_find_stations.argtypes = [dp, C.c_int, C.c_double, C.POINTER(StationRule), C.POINTER(Station), C.c_int]
     _libs[ab] = L
@@ -605,10 +622,11 @@ def find_stations(psd, input_rate, raster_hz=100000, raster_offset_hz=0, bandwid
 
 class Spectrum:
     """Welch power spectrum of n_rows IQ rows on the GPU (fmr_spectrum_*): mean PSD and peak hold per row, density-scaled,
-    in fftshift order (element k = bin (k - N/2) F / N Hz)."""
+    in fftshift order (element k = bin (k - N/2) F / N Hz).  waterfall_segments = R > 0 adds a waterfall (one line per R
+    segments, waterfall_lines of them kept per row, read with waterfall()); 0 is the plain object."""
 
     def __init__(self, input_rate, fft_size=8192, hop=0, window=WINDOW_HANN, n_rows=1, input_format=IQ_CF32,
-                 max_call_len=1 << 20, device=0):
+                 max_call_len=1 << 20, device=0, waterfall_segments=0, waterfall_lines=0, waterfall_which=WATERFALL_MEAN):
         self._L = lib()
         cfg = SpectrumConfig()
         cfg.struct_size = C.sizeof(SpectrumConfig)
@@ -616,10 +634,17 @@ class Spectrum:
         cfg.fft_size, cfg.hop, cfg.window, cfg.max_call_len = int(fft_size), int(hop), int(window), int(max_call_len)
         self.n_rows, self.fft_size, self.input_rate, self.input_format = int(n_rows), int(fft_size), float(input_rate), int(input_format)
         self.h = C.c_void_p()
-        rc = self._L.fmr_spectrum_create(C.byref(cfg), C.sizeof(SpectrumConfig), C.byref(self.h))
+        name = "fmr_spectrum_create"
+        if waterfall_segments:
+            name = "fmr_spectrum_create_waterfall"
+            wf = WaterfallConfig(C.sizeof(WaterfallConfig), int(waterfall_segments), int(waterfall_lines), int(waterfall_which))
+            rc = self._L.fmr_spectrum_create_waterfall(C.byref(cfg), C.sizeof(SpectrumConfig), C.byref(wf),
+                                                       C.sizeof(WaterfallConfig), C.byref(self.h))
+        else:
+            rc = self._L.fmr_spectrum_create(C.byref(cfg), C.sizeof(SpectrumConfig), C.byref(self.h))
         if rc != OK:
             self.h = None
-            raise FmrError(f"fmr_spectrum_create failed ({rc}): {self._L.fmr_last_error().decode()}")
+            raise FmrError(f"{name} failed ({rc}): {self._L.fmr_last_error().decode()}")
 
     def close(self):
         if getattr(self, "h", None) and getattr(self, "_L", None) is not None:
@@ -675,3 +700,18 @@ class Spectrum:
 
     def reset(self):
         self._chk(self._L.fmr_spectrum_reset(self.h))
+
+    def waterfall(self, row=0, cap=None):
+        """The oldest unread complete waterfall lines of `row` (at most cap; None: all that are ready): (lines float32
+        [n, N] in fftshift order, counted uint32 [n], info dict of fmr_waterfall_info).  Reading drains them."""
+        info = WaterfallInfo()
+        if cap is None:
+            cap = self._chk(self._L.fmr_spectrum_read_waterfall(self.h, int(row), None, None, 0, C.byref(info)))
+        lines = np.empty((int(cap), self.fft_size), dtype=np.float32)
+        counted = np.empty(int(cap), dtype=np.uint32)
+        n = self._chk(self._L.fmr_spectrum_read_waterfall(
+            self.h, int(row), lines.ctypes.data_as(C.POINTER(C.c_float)), counted.ctypes.data_as(C.POINTER(C.c_uint32)),
+            int(cap), C.byref(info)))
+        if int(cap) == 0:
+            n = 0
+        return lines[:n], counted[:n], {k: getattr(info, k) for k, _ in WaterfallInfo._fields_}

@@ -17,6 +17,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -2917,10 +2918,21 @@ struct fmr_spectrum {
   unsigned long long next_seg = 0;       // segments completed since create
   unsigned long long first_seg = 0;      // first segment processed since create / the last reset
   double sumw = 0.0, sumw2 = 0.0;
+  // waterfall (fmr_spectrum_create_waterfall; wf.segments_per_line = 0: none)
+  fmr_waterfall_config wf{};
+  int wf_sb = 0, wf_par = 0;             // sub-blocks per line; which copy of the open line's partial is current
+  DevBuf<float> d_plsub, d_wopen, d_wline, d_wring;
+  DevBuf<int> d_plcnt, d_wopen_cnt, d_wline_cnt;
+  DevBuf<unsigned> d_wring_cnt;
+  std::vector<unsigned long long> wf_read, wf_dropped;   // per row: next unread line, lines overwritten unread
   int init();
   int run(const void *d_in, size_t stride, size_t n);
+  int run_waterfall(const void *d_in, size_t stride, long long tb, long long ta, long long j_hi);
+  void wf_catch_up(int row);
   ~fmr_spectrum() {
     if (stream) (void)hipStreamSynchronize(stream);
+    d_plsub.release(); d_wopen.release(); d_wline.release(); d_wring.release(); d_plcnt.release(); d_wopen_cnt.release();
+    d_wline_cnt.release(); d_wring_cnt.release();
     d_win.release(); d_pmax.release(); d_max.release(); d_tw.release(); d_ring.release(); d_psum.release(); d_sum.release();
     d_pcnt.release(); d_cnt.release(); d_stage.release();
     if (stream) (void)hipStreamDestroy(stream);
@@ -2934,23 +2946,30 @@ constexpr int kSpecBps[4] = {8, 4, 2, 2};    // bytes per IQ sample of FMR_IQ_CF
 constexpr int kSpecMaxRows = 65535;
 constexpr size_t kSpecMaxCall = (size_t)1 << 30;
 
+// wf = nullptr: the plain form; else the waterfall form with these arguments
 template <int LOGN, int FMT>
 int spec_seg_launch(fmr_spectrum *s, dim3 grid, const void *in, long long stride, long long tb, long long seg0, int n_seg,
-                    int per_run) {
-  hipLaunchKernelGGL((k_spec_seg<LOGN, FMT>), grid, dim3(SpecShape<LOGN>::T), SpecShape<LOGN>::LDS_BYTES, s->stream, in,
-                     stride, (const float2 *)s->d_ring.p, tb, seg0, n_seg, per_run, s->H, (const float *)s->d_win.p,
-                     (const float2 *)s->d_tw.p, s->d_psum.p, s->d_pmax.p, s->d_pcnt.p, s->rmax);
+                    int per_run, const SpecWf *wf) {
+  if (wf)
+    hipLaunchKernelGGL((k_spec_seg<LOGN, FMT, true>), grid, dim3(SpecShape<LOGN>::T), SpecShape<LOGN>::LDS_BYTES, s->stream, in,
+                       stride, (const float2 *)s->d_ring.p, tb, seg0, n_seg, per_run, s->H, (const float *)s->d_win.p,
+                       (const float2 *)s->d_tw.p, s->d_psum.p, s->d_pmax.p, s->d_pcnt.p, s->rmax, *wf);
+  else
+    hipLaunchKernelGGL((k_spec_seg<LOGN, FMT, false>), grid, dim3(SpecShape<LOGN>::T), SpecShape<LOGN>::LDS_BYTES, s->stream, in,
+                       stride, (const float2 *)s->d_ring.p, tb, seg0, n_seg, per_run, s->H, (const float *)s->d_win.p,
+                       (const float2 *)s->d_tw.p, s->d_psum.p, s->d_pmax.p, s->d_pcnt.p, s->rmax, SpecWf{});
   HIPCHK(hipGetLastError());
   return FMR_OK;
 }
 template <int LOGN, int FMT>
-int spec_seg_attr() {
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spec_seg<LOGN, FMT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             SpecShape<LOGN>::LDS_BYTES));
+int spec_seg_attr(bool wf) {
+  const void *fn = wf ? reinterpret_cast<const void *>(&k_spec_seg<LOGN, FMT, true>)
+                      : reinterpret_cast<const void *>(&k_spec_seg<LOGN, FMT, false>);
+  HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SpecShape<LOGN>::LDS_BYTES));
   return FMR_OK;
 }
-using SpecSegFn = int (*)(fmr_spectrum *, dim3, const void *, long long, long long, long long, int, int);
-using SpecAttrFn = int (*)();
+using SpecSegFn = int (*)(fmr_spectrum *, dim3, const void *, long long, long long, long long, int, int, const SpecWf *);
+using SpecAttrFn = int (*)(bool);
 #define FMR_SPEC_ROW(L) {&spec_seg_launch<L, 0>, &spec_seg_launch<L, 1>, &spec_seg_launch<L, 2>, &spec_seg_launch<L, 3>}
 #define FMR_SPEC_ATTR(L) {&spec_seg_attr<L, 0>, &spec_seg_attr<L, 1>, &spec_seg_attr<L, 2>, &spec_seg_attr<L, 3>}
 const SpecSegFn kSpecSeg[7][4] = {FMR_SPEC_ROW(8), FMR_SPEC_ROW(9), FMR_SPEC_ROW(10), FMR_SPEC_ROW(11), FMR_SPEC_ROW(12),
@@ -2990,6 +3009,39 @@ int spec_check(const fmr_spectrum_config &c) {
   }
   return FMR_OK;
 }
+
+// the rules of fmr_spectrum_create_waterfall for the waterfall's own fields, before the device is opened
+constexpr size_t kWfMaxBytes = (size_t)1 << 30;
+int wf_check(const fmr_spectrum_config &c, const fmr_waterfall_config &w) {
+  if (w.segments_per_line < 1 || w.segments_per_line > 65536) {
+    set_err("fmr_spectrum_create_waterfall: segments_per_line %d is outside 1 .. 65536", w.segments_per_line);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (w.max_lines < 1) { set_err("fmr_spectrum_create_waterfall: max_lines %d is < 1", w.max_lines); return FMR_ERR_BAD_ARG; }
+  if (w.which != FMR_WATERFALL_MEAN && w.which != FMR_WATERFALL_PEAK) {
+    set_err("fmr_spectrum_create_waterfall: unknown which %d", w.which);
+    return FMR_ERR_BAD_ARG;
+  }
+  if ((size_t)w.max_lines > kWfMaxBytes / 4 / (size_t)c.fft_size / (size_t)c.n_rows) {
+    set_err("fmr_spectrum_create_waterfall: max_lines %d: n_rows (%d) x max_lines x fft_size (%d) x 4 bytes is above 1 GiB",
+            w.max_lines, c.n_rows, c.fft_size);
+    return FMR_ERR_BAD_ARG;
+  }
+  return FMR_OK;
+}
+
+// fmr_spectrum_config as the caller knows it (cfg_size, struct_size) -> this library's, zero-filled; then spec_check
+int spec_take_cfg(const fmr_spectrum_config *cfg, size_t cfg_size, fmr_spectrum_config &full) {
+  const size_t size = cfg_size ? cfg_size : sizeof(fmr_spectrum_config);
+  if (size > sizeof(fmr_spectrum_config) || cfg->struct_size > sizeof(fmr_spectrum_config)) {
+    set_err("fmr_spectrum_create: struct_size %zu is larger than this library's fmr_spectrum_config (%zu): the caller is "
+            "newer than the library", std::max(size, (size_t)cfg->struct_size), sizeof(fmr_spectrum_config));
+    return FMR_ERR_BAD_ARG;
+  }
+  memset(&full, 0, sizeof full);
+  memcpy(&full, cfg, size);
+  return spec_check(full);
+}
 }  // namespace
 
 int fmr_spectrum::init() {
@@ -3006,7 +3058,8 @@ int fmr_spectrum::init() {
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, cfg.device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
   HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  if (int rc = kSpecAttr[logn - 8][fmt]()) return rc;
+  const bool wfon = wf.segments_per_line > 0;
+  if (int rc = kSpecAttr[logn - 8][fmt](wfon)) return rc;
   // window and twiddles: double, rounded once to fp32
   std::vector<float> w(N);
   std::vector<float2> tw(N);
@@ -3026,6 +3079,13 @@ int fmr_spectrum::init() {
   const int occ = std::max(1, std::min(163840 / spec_lds_bytes(logn), 2048 / spec_threads(logn)));
   const long long smax = (long long)((cfg.max_call_len + H - 1) / H) + 1;
   rmax = (int)std::max(1LL, std::min(smax, (long long)((n_cu * occ + rows - 1) / rows)));
+  if (wfon) {
+    // waterfall runs hold SPEC_WF_SUB segments at most, so a call is taken in launches of rmax runs per row: room for
+    // more runs than the chip holds at once (up to 128 MiB of partials, 16 N bytes per run) keeps the launches few
+    wf_sb = (wf.segments_per_line + SPEC_WF_SUB - 1) / SPEC_WF_SUB;
+    const long long room = ((long long)128 << 20) / ((long long)rows * N * 16);
+    rmax = (int)std::max<long long>(rmax, std::min(smax, room));
+  }
   const size_t part = (size_t)rows * rmax;
   if (int rc = d_psum.alloc(part * N)) return rc;
   if (int rc = d_pmax.alloc(part * N)) return rc;
@@ -3034,6 +3094,18 @@ int fmr_spectrum::init() {
   if (int rc = d_max.alloc((size_t)rows * N)) return rc;
   if (int rc = d_ring.alloc((size_t)rows * N)) return rc;
   if (int rc = d_cnt.alloc((size_t)rows * 2)) return rc;
+  if (wfon) {
+    if (int rc = d_plsub.alloc(part * N)) return rc;
+    if (int rc = d_plcnt.alloc(part)) return rc;
+    if (int rc = d_wopen.alloc((size_t)rows * N)) return rc;
+    if (int rc = d_wopen_cnt.alloc(rows)) return rc;
+    if (int rc = d_wline.alloc((size_t)2 * rows * N)) return rc;
+    if (int rc = d_wline_cnt.alloc((size_t)2 * rows)) return rc;
+    if (int rc = d_wring.alloc((size_t)rows * wf.max_lines * N)) return rc;
+    if (int rc = d_wring_cnt.alloc((size_t)rows * wf.max_lines)) return rc;
+    wf_read.assign(rows, 0);
+    wf_dropped.assign(rows, 0);
+  }
   HIPCHK(hipDeviceSynchronize());
   return FMR_OK;
 }
@@ -3043,12 +3115,13 @@ int fmr_spectrum::run(const void *d_in, size_t stride, size_t n) {
   const long long tb = (long long)total, ta = tb + (long long)n;
   const long long j_hi = ta >= N ? (ta - N) / H + 1 : 0;
   const long long n_seg = std::max(0LL, j_hi - (long long)next_seg);
+  if (wf.segments_per_line > 0 && n_seg > 0) return run_waterfall(d_in, stride, tb, ta, j_hi);
   int runs = 0;
   if (n_seg > 0) {
     runs = (int)std::min<long long>(n_seg, rmax);
     const int per_run = (int)((n_seg + runs - 1) / runs);
     runs = (int)((n_seg + per_run - 1) / per_run);
-    if (int rc = kSpecSeg[logn - 8][fmt](this, dim3(runs, rows), d_in, (long long)stride, tb, (long long)next_seg, (int)n_seg, per_run))
+    if (int rc = kSpecSeg[logn - 8][fmt](this, dim3(runs, rows), d_in, (long long)stride, tb, (long long)next_seg, (int)n_seg, per_run, nullptr))
       return rc;
   }
   hipLaunchKernelGGL(kSpecReduce[fmt], dim3((N + 63) / 64, rows), dim3(64 * SPEC_RW), 0, stream, (const double *)d_psum.p,
@@ -3058,6 +3131,50 @@ int fmr_spectrum::run(const void *d_in, size_t stride, size_t n) {
   if (n_seg > 0) next_seg = (unsigned long long)j_hi;
   total = (unsigned long long)ta;
   return FMR_OK;
+}
+
+// The call's segments [next_seg, j_hi) with the waterfall on: launches of at most rmax runs per row, run r of a launch =
+// sub-block g0 + r of the line grid clipped to the launch (kernels_spectrum.hpp), each followed by the reduction of its
+// partials (the sample ring is refreshed by the last one only: the launches before it still read it) and by the lines.
+int fmr_spectrum::run_waterfall(const void *d_in, size_t stride, long long tb, long long ta, long long j_hi) {
+  const int R = wf.segments_per_line;
+  long long a = (long long)next_seg;
+  while (a < j_hi) {
+    const long long l = a / R;
+    SpecWf w{};
+    w.which = wf.which; w.R = R; w.SB = wf_sb;
+    w.g0 = l * wf_sb + (a - l * R) / SPEC_WF_SUB;
+    long long lo, hi;
+    spec_wf_sub(R, wf_sb, w.g0 + rmax - 1, lo, hi);
+    w.a1 = std::min(j_hi, hi);
+    const long long l_end = (w.a1 - 1) / R;
+    const long long g_last = l_end * wf_sb + (w.a1 - 1 - l_end * R) / SPEC_WF_SUB;
+    const int runs = (int)(g_last - w.g0 + 1);
+    w.plsub = d_plsub.p; w.plcnt = d_plcnt.p; w.open_sub = d_wopen.p; w.open_cnt = d_wopen_cnt.p;
+    if (int rc = kSpecSeg[logn - 8][fmt](this, dim3(runs, rows), d_in, (long long)stride, tb, a, (int)(w.a1 - a), 0, &w))
+      return rc;
+    hipLaunchKernelGGL(kSpecReduce[fmt], dim3((N + 63) / 64, rows), dim3(64 * SPEC_RW), 0, stream, (const double *)d_psum.p,
+                       (const float *)d_pmax.p, (const int2 *)d_pcnt.p, runs, rmax, N, d_sum.p, d_max.p, d_cnt.p, d_in,
+                       (long long)stride, tb, w.a1 == j_hi ? ta : tb, d_ring.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_spec_lines, dim3((unsigned)(l_end - l + 1), rows, (N + 255) / 256), dim3(256), 0, stream, w, a, runs,
+                       rmax, N, wf.max_lines, wf_par, d_wline.p, d_wline_cnt.p, d_wring.p, d_wring_cnt.p);
+    HIPCHK(hipGetLastError());
+    wf_par ^= 1;
+    a = w.a1;
+  }
+  next_seg = (unsigned long long)j_hi;
+  total = (unsigned long long)ta;
+  return FMR_OK;
+}
+
+// Lines of `row` that completed beyond the ring's depth since the last read were overwritten unread: count them
+void fmr_spectrum::wf_catch_up(int row) {
+  const unsigned long long done = next_seg / (unsigned long long)wf.segments_per_line, L = (unsigned long long)wf.max_lines;
+  if (done > L && wf_read[row] < done - L) {
+    wf_dropped[row] += done - L - wf_read[row];
+    wf_read[row] = done - L;
+  }
 }
 
 static int spectrum_call(fmr_spectrum *s, const void *iq, size_t row_stride, size_t n, bool host, int sync) {
@@ -3099,7 +3216,7 @@ static double spec_db(double x) { return 10.0 * std::log10(x); }
 extern "C" {
 
 const char *fmr_last_error(void) { return g_err.c_str(); }
-const char *fmr_version(void) { return "fmradion_amd 0.4 (gfx950)"; }
+const char *fmr_version(void) { return "fmradion_amd 0.4.1 (gfx950)"; }
 
 // the caller's cfg_size bytes of an fmr_config, the fields its header does not have zero ("as before")
 static int widen_config(const char *fn, const fmr_config *cfg, size_t cfg_size, fmr_config *full) {
@@ -3773,18 +3890,34 @@ int fmr_filter_table(const char *name, const void **data, int *is_double) {
 int fmr_spectrum_create(const fmr_spectrum_config *cfg, size_t cfg_size, fmr_spectrum **out) {
   if (!cfg || !out) { set_err("fmr_spectrum_create: null argument"); return FMR_ERR_BAD_ARG; }
   *out = nullptr;
-  const size_t size = cfg_size ? cfg_size : sizeof(fmr_spectrum_config);
-  if (size > sizeof(fmr_spectrum_config) || cfg->struct_size > sizeof(fmr_spectrum_config)) {
-    set_err("fmr_spectrum_create: struct_size %zu is larger than this library's fmr_spectrum_config (%zu): the caller is "
-            "newer than the library", std::max(size, (size_t)cfg->struct_size), sizeof(fmr_spectrum_config));
-    return FMR_ERR_BAD_ARG;
-  }
   fmr_spectrum_config full;
-  memset(&full, 0, sizeof full);
-  memcpy(&full, cfg, size);
-  if (int rc = spec_check(full)) return rc;
+  if (int rc = spec_take_cfg(cfg, cfg_size, full)) return rc;
   fmr_spectrum *s = new fmr_spectrum();
   s->cfg = full;
+  if (int rc = s->init()) { delete s; return rc; }
+  *out = s;
+  return FMR_OK;
+}
+
+int fmr_spectrum_create_waterfall(const fmr_spectrum_config *cfg, size_t cfg_size, const fmr_waterfall_config *wf,
+                                  size_t wf_size, fmr_spectrum **out) {
+  if (!cfg || !wf || !out) { set_err("fmr_spectrum_create_waterfall: null argument"); return FMR_ERR_BAD_ARG; }
+  *out = nullptr;
+  fmr_spectrum_config full;
+  if (int rc = spec_take_cfg(cfg, cfg_size, full)) return rc;
+  const size_t size = wf_size ? wf_size : sizeof(fmr_waterfall_config);
+  if (size > sizeof(fmr_waterfall_config) || wf->struct_size > sizeof(fmr_waterfall_config)) {
+    set_err("fmr_spectrum_create_waterfall: struct_size %zu is larger than this library's fmr_waterfall_config (%zu): the "
+            "caller is newer than the library", std::max(size, (size_t)wf->struct_size), sizeof(fmr_waterfall_config));
+    return FMR_ERR_BAD_ARG;
+  }
+  fmr_waterfall_config w;
+  memset(&w, 0, sizeof w);
+  memcpy(&w, wf, size);
+  if (int rc = wf_check(full, w)) return rc;
+  fmr_spectrum *s = new fmr_spectrum();
+  s->cfg = full;
+  s->wf = w;
   if (int rc = s->init()) { delete s; return rc; }
   *out = s;
   return FMR_OK;
@@ -3839,6 +3972,53 @@ int fmr_spectrum_read(fmr_spectrum *s, int row, int which, double *out, size_t c
     info->enbw_hz = F * s->sumw2 / (s->sumw * s->sumw);
   }
   return N;
+}
+
+int fmr_spectrum_read_waterfall(fmr_spectrum *s, int row, float *out, uint32_t *counted, size_t cap_lines,
+                                fmr_waterfall_info *info) {
+  if (!s || row < 0 || row >= s->rows) { set_err("fmr_spectrum_read_waterfall: bad row"); return FMR_ERR_BAD_ARG; }
+  if (s->wf.segments_per_line <= 0) {
+    set_err("fmr_spectrum_read_waterfall: the object has no waterfall (it was made by fmr_spectrum_create)");
+    return FMR_ERR_BAD_ARG;
+  }
+  if (cap_lines > 0 && !out) { set_err("fmr_spectrum_read_waterfall: out is null"); return FMR_ERR_BAD_ARG; }
+  HIPCHK(hipSetDevice(s->cfg.device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  const int N = s->N;
+  const unsigned long long R = (unsigned long long)s->wf.segments_per_line, L = (unsigned long long)s->wf.max_lines;
+  const unsigned long long done = s->next_seg / R;
+  s->wf_catch_up(row);
+  const unsigned long long first = s->wf_read[row], ready = done - first;
+  const size_t n = cap_lines == 0 ? 0 : (size_t)std::min<unsigned long long>({ready, cap_lines, (unsigned long long)INT_MAX});
+  if (n > 0) {
+    // the ring slots first % L .. in at most two contiguous pieces, copied straight into `out` and scaled there
+    std::vector<unsigned> cnt(n);
+    for (size_t k = 0; k < n;) {
+      const size_t slot = (size_t)((first + k) % L), m = std::min(n - k, (size_t)L - slot);
+      HIPCHK(hipMemcpy(out + k * N, s->d_wring.p + ((size_t)row * L + slot) * N, m * N * sizeof(float), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(cnt.data() + k, s->d_wring_cnt.p + (size_t)row * L + slot, m * sizeof(unsigned), hipMemcpyDeviceToHost));
+      k += m;
+    }
+    const double scale = 1.0 / (s->cfg.input_rate * s->sumw2);
+    for (size_t k = 0; k < n; k++) {
+      const double div = s->wf.which == FMR_WATERFALL_MEAN ? (double)cnt[k] : 1.0;
+      float *ln = out + k * N;
+      for (int i = 0; i < N / 2; i++) {                                // fftshift: element i is bin i - N/2
+        const double lo = ln[i], hi = ln[i + N / 2];
+        ln[i] = cnt[k] == 0 ? 0.f : (float)(hi / div * scale);
+        ln[i + N / 2] = cnt[k] == 0 ? 0.f : (float)(lo / div * scale);
+      }
+      if (counted) counted[k] = cnt[k];
+    }
+    s->wf_read[row] = first + n;
+  }
+  if (info) {
+    info->first_line = first;
+    info->lines_ready = done - s->wf_read[row];
+    info->lines_dropped = s->wf_dropped[row];
+    info->line_seconds = (double)R * s->H / s->cfg.input_rate;
+  }
+  return cap_lines == 0 ? (int)std::min<unsigned long long>(ready, (unsigned long long)INT_MAX) : (int)n;
 }
 
 int fmr_spectrum_reset(fmr_spectrum *s) {

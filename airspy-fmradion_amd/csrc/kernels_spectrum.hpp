@@ -19,6 +19,24 @@
 // stride of 4 elements, spreads a 32-lane ds_read_b64 group over all 64 banks instead of 16 of them.  N = 16384 needs
 // 132 KiB: one workgroup per CU; N <= 8192 fits two.
 // Twiddles tw[i] = exp(-2 pi i i / N) and the window are built on the host in double and rounded once to fp32.
+//
+// Waterfall (fmr_spectrum_create_waterfall; k_spec_seg<.., WF = true> and k_spec_lines).  Line l of a row is made of the
+// segments [l R, (l + 1) R) (absolute indices); it is complete in the call that delivers the last sample of segment
+// (l + 1) R - 1.  MEAN keeps the fp32 sum of the counted segments' P_j[k] and their count c_l, PEAK their maximum; the
+// division, the density scaling and the fftshift happen on the host when a line is read.
+// Addition order (a function of a segment's index q = j - l R within its line only, never of the call cut or of the
+// run partition): the line is cut into sub-blocks of SPEC_WF_SUB segments, sub-block b = q / SPEC_WF_SUB (the last one
+// of a line is shorter when SPEC_WF_SUB does not divide R).  Within a sub-block the counted P_j are added one by one in
+// segment order, starting from the first (S_b = (..((P_q0 + P_q0+1) + P_q0+2) ..)); the line is
+// (..((S_0 + S_1) + S_2) ..) in sub-block order.  A skipped segment adds nothing.
+// A workgroup run of the waterfall form never straddles a sub-block boundary: run r of a launch is (the part inside
+// the launch of) sub-block g0 + r, sub-blocks numbered g = l ceil(R / SPEC_WF_SUB) + b.  A sub-block cut by the end of a
+// call is carried in open_sub / open_cnt and the run that continues it starts from there, so its additions go on in
+// the same order.  k_spec_lines (one block column per line the launch touches) combines the sub-block values in order,
+// starting from the open line's partial of the launch before, writes complete lines into the ring [row][l mod L][N]
+// and their counts beside it, and leaves the open line's partial for the next launch (two copies by launch parity: the
+// block that reads the old one is not the block that writes the new one).  The line state lives in registers and HBM:
+// the LDS of the segment pass is unchanged.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +52,24 @@ struct SpecShape {
   static constexpr int LDS_BYTES = spec_lds_bytes(LOGN);
 };
 
+// Waterfall arguments of one launch (by value).  The launch takes the segments [a0, a1) (a0 = k_spec_seg's seg0).
+constexpr int SPEC_WF_SUB = 8;                 // segments per sub-block of a line (the addition order above)
+struct SpecWf {
+  int which;                 // 0 = mean (sum), 1 = peak (max)
+  int R, SB;                 // segments per line, sub-blocks per line = ceil(R / SPEC_WF_SUB)
+  long long g0, a1;          // sub-block of the launch's first segment; end of the launch's segments
+  float *plsub;              // [row * rmax + run][N]: the sub-block's value so far (the carried part included)
+  int *plcnt;                // [row * rmax + run]: its counted segments so far
+  float *open_sub;           // [row][N], open_cnt [row]: the sub-block a call's end cut
+  int *open_cnt;
+};
+// segments [lo, hi) of sub-block g (whole, before a launch clips it)
+__host__ __device__ inline void spec_wf_sub(int R, int SB, long long g, long long &lo, long long &hi) {
+  const long long l = g / SB, b = g - l * SB;
+  lo = l * R + b * SPEC_WF_SUB;
+  hi = lo + SPEC_WF_SUB < (l + 1) * R ? lo + SPEC_WF_SUB : (l + 1) * R;
+}
+
 __device__ __forceinline__ int spec_pad(int e) { return e + (e >> 5); }
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
@@ -43,18 +79,32 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
 // ring + row * N (sample p of the stream at ring[p mod N] for p < tb).  Segments seg0 .. seg0 + n_seg - 1 of this call,
 // run r = blockIdx.x takes [r per_run, min((r + 1) per_run, n_seg)).  Partials of run r: psum / pmax row (row * rmax + r)
 // of N bins, pcnt[row * rmax + r] = (segments counted, segments skipped).
-template <int LOGN, int FMT>
+// WF (waterfall form): run r is sub-block wf.g0 + r clipped to the launch's segments [seg0, wf.a1); beside the partials
+// above it keeps the sub-block's line value (fp32 sum or maximum in segment order) and writes it to wf.plsub / wf.plcnt.
+template <int LOGN, int FMT, bool WF>
 __global__ __launch_bounds__(SpecShape<LOGN>::T) void k_spec_seg(
     const void *__restrict__ in, long long in_stride, const float2 *__restrict__ ring, long long tb, long long seg0,
     int n_seg, int per_run, int hop, const float *__restrict__ win, const float2 *__restrict__ tw,
-    double *__restrict__ psum, float *__restrict__ pmax, int2 *__restrict__ pcnt, int rmax) {
+    double *__restrict__ psum, float *__restrict__ pmax, int2 *__restrict__ pcnt, int rmax, SpecWf wf) {
   using S = SpecShape<LOGN>;
   constexpr int N = S::N, T = S::T;
   extern __shared__ float2 lds_sp[];
   const int tid = threadIdx.x;
   const int run = blockIdx.x, row = blockIdx.y;
-  const int j_lo = run * per_run;
-  const int j_hi = min(j_lo + per_run, n_seg);
+  int j_lo = run * per_run;
+  int j_hi = min(j_lo + per_run, n_seg);
+  [[maybe_unused]] float ls[WF ? S::BINS : 1];      // the sub-block's line value of this thread's bins
+  [[maybe_unused]] int lcnt = 0;
+  if constexpr (WF) {
+    long long lo, hi;
+    spec_wf_sub(wf.R, wf.SB, wf.g0 + run, lo, hi);
+    const bool carried = lo < seg0;        // the call before ended inside this sub-block (the launch's first run only)
+    j_lo = (int)(max(lo, seg0) - seg0);
+    j_hi = (int)(min(hi, wf.a1) - seg0);
+#pragma unroll
+    for (int b = 0; b < S::BINS; b++) ls[b] = carried ? wf.open_sub[(size_t)row * N + tid + b * T] : 0.f;
+    if (carried) lcnt = wf.open_cnt[row];
+  }
   const unsigned char *inrow = reinterpret_cast<const unsigned char *>(in) + (size_t)row * in_stride * fmr::IqFmt<FMT>::BPS;
   const float2 *ringrow = ring + (size_t)row * N;
 
@@ -118,6 +168,7 @@ __global__ __launch_bounds__(SpecShape<LOGN>::T) void k_spec_seg(
       const float pw = x.x * x.x + x.y * x.y;
       acc[b] += (double)pw;
       pk[b] = fmaxf(pk[b], pw);
+      if constexpr (WF) ls[b] = wf.which ? fmaxf(ls[b], pw) : ls[b] + pw;
     }
     counted++;
     __syncthreads();                       // every thread has read its bins before the next segment's stores
@@ -129,6 +180,11 @@ __global__ __launch_bounds__(SpecShape<LOGN>::T) void k_spec_seg(
     pmax[prow * N + tid + b * T] = pk[b];
   }
   if (tid == 0) pcnt[prow] = make_int2(counted, skipped);
+  if constexpr (WF) {
+#pragma unroll
+    for (int b = 0; b < S::BINS; b++) wf.plsub[prow * N + tid + b * T] = ls[b];
+    if (tid == 0) wf.plcnt[prow] = lcnt + counted;
+  }
 }
 
 // Per row (grid.y) and 64 bins (grid.x): add the runs' partials into the row's accumulators in a fixed order -- wave g of
@@ -184,5 +240,56 @@ __global__ __launch_bounds__(64 * SPEC_RW) void k_spec_reduce(
   for (int q = blockIdx.x * 64 * SPEC_RW + threadIdx.x; q < N; q += gridDim.x * 64 * SPEC_RW) {
     const long long p = ta - N + q;
     if (p >= tb && p >= 0) ring[(size_t)row * N + (p & (N - 1))] = fmr::iq_load1<FMT>(inrow, p - tb);
+  }
+}
+
+// Waterfall lines of one launch of k_spec_seg<.., WF = true> (same stream, after it).  Block (x = line l0 + blockIdx.x,
+// y = row, z = 256 bins); the launch took the segments [a0, wf.a1) in `runs` runs.  The thread of bin i walks the line's
+// sub-blocks inside the launch in order: a complete one joins the line value (the first starts it, or the open line's
+// partial of the launch before: line_part[par]), one the call's end cut goes to open_sub.  A complete line goes to
+// ring[row][l mod L] (unless a later line of the same launch takes that slot: l + L <= last complete line), an open
+// one to line_part[par ^ 1].  Thread 0 of the line's first block does the same with the counts.
+__global__ __launch_bounds__(256) void k_spec_lines(SpecWf wf, long long a0, int runs, int rmax, int N, int L, int par,
+                                                    float *__restrict__ line_part, int *__restrict__ line_cnt,
+                                                    float *__restrict__ ring, unsigned *__restrict__ ring_cnt) {
+  const int row = blockIdx.y, rows = gridDim.y;
+  const int i = blockIdx.z * 256 + threadIdx.x;
+  if (i >= N) return;
+  const long long l0 = wf.g0 / wf.SB;
+  const long long l = l0 + blockIdx.x;
+  const long long g_last = wf.g0 + runs - 1;
+  const int b_lo = blockIdx.x == 0 ? (int)(wf.g0 - l0 * wf.SB) : 0;
+  const int b_hi = (int)min((long long)wf.SB, g_last - l * wf.SB + 1);
+  const long long last_done = wf.a1 / wf.R - 1;            // last line complete after this launch
+  const bool cnt_thread = i == 0;
+  float v = 0.f;
+  int c = 0;
+  if (b_lo > 0) {
+    v = line_part[((size_t)par * rows + row) * N + i];
+    if (cnt_thread) c = line_cnt[par * rows + row];
+  }
+  for (int b = b_lo; b < b_hi; b++) {
+    const long long g = l * wf.SB + b;
+    const size_t pr = (size_t)row * rmax + (size_t)(g - wf.g0);
+    long long lo, hi;
+    spec_wf_sub(wf.R, wf.SB, g, lo, hi);
+    const float s = wf.plsub[pr * N + i];
+    if (hi <= wf.a1) {
+      v = b == 0 ? s : wf.which ? fmaxf(v, s) : v + s;
+      if (cnt_thread) c = b == 0 ? wf.plcnt[pr] : c + wf.plcnt[pr];
+    } else {                                               // cut by the call's end: the launch's last run
+      wf.open_sub[(size_t)row * N + i] = s;
+      if (cnt_thread) wf.open_cnt[row] = wf.plcnt[pr];
+    }
+  }
+  if (l <= last_done) {
+    if (l + L > last_done) {
+      const size_t slot = (size_t)row * L + (size_t)(l % L);
+      ring[slot * N + i] = v;
+      if (cnt_thread) ring_cnt[slot] = (unsigned)c;
+    }
+  } else {
+    line_part[((size_t)(par ^ 1) * rows + row) * N + i] = v;
+    if (cnt_thread) line_cnt[(par ^ 1) * rows + row] = c;
   }
 }

@@ -616,6 +616,8 @@ private:
 // SpectrumMonitor (fmr_spectrum_*): the Welch power spectrum of a capture on the GPU (mean PSD, density-scaled, fftshift
 // order: element k is the bin at (k - N/2) input_rate / N Hz) and the stations it holds.  find_stations() returns offsets
 // that go straight into ChannelBank / Channelizer.  Blocks longer than max_call_len are taken in consecutive pieces.
+// The second constructor adds a waterfall (fmr_spectrum_create_waterfall): one line per waterfall_segments segments,
+// waterfall_lines of them kept until read_waterfall() takes them.
 class SpectrumMonitor {
 public:
   explicit SpectrumMonitor(double input_rate, int fft_size = 8192, int hop = 0, int window = FMR_WINDOW_HANN, int device = 0,
@@ -625,6 +627,16 @@ public:
     cfg.struct_size = sizeof cfg; cfg.device = device; cfg.n_rows = 1; cfg.input_rate = input_rate;
     cfg.input_format = FMR_IQ_CF32; cfg.fft_size = fft_size; cfg.hop = hop; cfg.window = window; cfg.max_call_len = max_call_len;
     fmr_detail::check(fmr_spectrum_create(&cfg, sizeof cfg, &m_s), "fmr_spectrum_create");
+  }
+  SpectrumMonitor(double input_rate, int fft_size, int hop, int window, int device, size_t max_call_len,
+                  int waterfall_segments, int waterfall_lines, int waterfall_which = FMR_WATERFALL_MEAN)
+      : m_rate(input_rate), m_n(fft_size), m_max(max_call_len) {
+    fmr_spectrum_config cfg{};
+    cfg.struct_size = sizeof cfg; cfg.device = device; cfg.n_rows = 1; cfg.input_rate = input_rate;
+    cfg.input_format = FMR_IQ_CF32; cfg.fft_size = fft_size; cfg.hop = hop; cfg.window = window; cfg.max_call_len = max_call_len;
+    fmr_waterfall_config wf{};
+    wf.struct_size = sizeof wf; wf.segments_per_line = waterfall_segments; wf.max_lines = waterfall_lines; wf.which = waterfall_which;
+    fmr_detail::check(fmr_spectrum_create_waterfall(&cfg, sizeof cfg, &wf, sizeof wf, &m_s), "fmr_spectrum_create_waterfall");
   }
   ~SpectrumMonitor() { fmr_spectrum_destroy(m_s); }
   SpectrumMonitor(const SpectrumMonitor &) = delete;
@@ -640,6 +652,20 @@ public:
   std::vector<double> psd() { return read(0); }
   std::vector<double> peak_hold() { return read(1); }
   void reset() { fmr_detail::check(fmr_spectrum_reset(m_s), "fmr_spectrum_reset"); }
+  // Every complete waterfall line not read yet (row 0 is the monitor's only row): lines.size() / fft_size lines of
+  // fft_size floats in fftshift order, their counted segments in `counted`.  Returns the first line's absolute index.
+  uint64_t read_waterfall(int row, std::vector<float> &lines, std::vector<uint32_t> &counted) {
+    fmr_waterfall_info info{};
+    const int ready = fmr_spectrum_read_waterfall(m_s, row, nullptr, nullptr, 0, &info);
+    if (ready < 0) fmr_detail::check(ready, "fmr_spectrum_read_waterfall");
+    lines.assign((size_t)ready * (size_t)m_n, 0.f);
+    counted.assign((size_t)ready, 0);
+    if (ready > 0) {
+      const int rc = fmr_spectrum_read_waterfall(m_s, row, lines.data(), counted.data(), (size_t)ready, &info);
+      if (rc < 0) fmr_detail::check(rc, "fmr_spectrum_read_waterfall");
+    }
+    return info.first_line;
+  }
   // fmr_find_stations on the current mean PSD: offsets in ascending order
   std::vector<int32_t> find_stations(const fmr_station_rule &rule) {
     const std::vector<double> p = psd();

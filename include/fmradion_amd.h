@@ -482,8 +482,51 @@ int fmr_spectrum_synchronize(fmr_spectrum *s);
 /* Synchronises; writes N doubles of row `row` (which 0 = mean PSD, 1 = peak hold; zeros before any segment was counted)
  * and, if info is not NULL, the row's counters.  Returns N, or FMR_ERR_CAPACITY when cap < N. */
 int fmr_spectrum_read(fmr_spectrum *s, int row, int which, double *out, size_t cap, fmr_spectrum_info *info);
-/* Zeroes both accumulators and the counts of every row; the segment grid keeps its absolute positions. */
+/* Zeroes both accumulators and the counts of every row; the segment grid keeps its absolute positions.  A waterfall
+ * (below) is left alone: it is a stream that reading drains, its unread lines and its line grid stay as they were. */
 int fmr_spectrum_reset(fmr_spectrum *s);
+
+/* --- Waterfall: time-resolved lines of the same spectrum, kept in the same pass over the input.
+ * R = segments_per_line, L = max_lines (the ring's depth per row).  Line l of a row is made of the segments j in
+ * [l R, (l + 1) R) of that row (absolute indices on the object's segment grid); it is complete in the call that delivers
+ * the last sample of segment (l + 1) R - 1 and covers the absolute samples [l R H, ((l + 1) R - 1) H + N).  A segment
+ * that holds a non-finite sample is skipped as it is for the accumulators; c_l is the number of counted segments.
+ *   FMR_WATERFALL_MEAN: (sum P_j[k]) / c_l over the counted segments, the sum in fp32;
+ *   FMR_WATERFALL_PEAK: max P_j[k] over the counted segments;      c_l = 0: all zeros (the count tells).
+ * Output: floats in fftshift order, density-scaled by the 1 / (F sum w^2) of fmr_spectrum_read; division and scaling
+ * are done in double on the host when the line is read, then rounded once to float.
+ * Cut independence: a line's values are bit-identical for any cut of the input into calls, on the host and the device
+ * path, whatever else a call holds.  The fp32 additions of a MEAN line run in an order that depends on a segment's index
+ * q within its line only: aligned sub-blocks of 8 segments (q / 8; the last one shorter when 8 does not divide R) are
+ * each summed one segment after the other, and the sub-block sums are added in sub-block order.  A line a call leaves
+ * open carries its state on the device to the next call.
+ * Ring overrun: when a row holds L unread lines and another completes, the oldest unread one is overwritten and counted
+ * in lines_dropped; processing never fails because of it.  fmr_spectrum_reset leaves the waterfall alone.
+ * fmr_spectrum_config and fmr_spectrum_create are unchanged: an object made by fmr_spectrum_create has no waterfall. */
+enum { FMR_WATERFALL_MEAN = 0, FMR_WATERFALL_PEAK = 1 };
+typedef struct {
+  unsigned struct_size;    /* 0 = this header's size; a larger size is refused */
+  int segments_per_line;   /* R: 1 .. 65536 */
+  int max_lines;           /* L >= 1; n_rows x L x N x 4 bytes <= 1 GiB */
+  int which;               /* FMR_WATERFALL_* */
+} fmr_waterfall_config;
+typedef struct {
+  uint64_t first_line;     /* absolute index of the first line returned */
+  uint64_t lines_ready;    /* complete lines still unread after this call */
+  uint64_t lines_dropped;  /* since create: overwritten unread (of this row) */
+  double line_seconds;     /* R * H / input_rate */
+} fmr_waterfall_info;
+/* Checks cfg exactly as fmr_spectrum_create does (same codes and messages), then wf: FMR_ERR_BAD_ARG (before the device
+ * is opened; fmr_last_error names the field) for segments_per_line outside 1 .. 65536, max_lines < 1, an unknown which,
+ * a struct_size larger than this library's, or n_rows x max_lines x fft_size x 4 bytes above 1 GiB; FMR_ERR_NO_DEVICE
+ * for a valid pair without a device. */
+int fmr_spectrum_create_waterfall(const fmr_spectrum_config *cfg, size_t cfg_size, const fmr_waterfall_config *wf,
+                                  size_t wf_size, fmr_spectrum **out);
+/* Synchronises; copies the oldest unread complete lines of `row` to out (up to cap_lines of them, N floats each) and
+ * their c_l to counted (may be NULL), marks them read and returns how many it copied.  cap_lines = 0 returns the number
+ * ready and copies nothing.  Each row has its own read position.  FMR_ERR_BAD_ARG for an object without a waterfall. */
+int fmr_spectrum_read_waterfall(fmr_spectrum *s, int row, float *out, uint32_t *counted, size_t cap_lines,
+                                fmr_waterfall_info *info);
 /* Host only (no device).  psd: fft_size doubles in the layout above.  Keeps f_c when snr_db >= threshold_db and its band
  * power is >= that of every candidate f' with 0 < |f' - f_c| < bandwidth_hz (a tie goes to the lower frequency).
  * Writes up to cap stations in ascending offset order and returns how many there are (possibly more than cap);
