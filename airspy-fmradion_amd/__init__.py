@@ -48,6 +48,7 @@ EXPORTS = [
     "fmr_spectrum_create", "fmr_spectrum_destroy", "fmr_spectrum_process", "fmr_spectrum_process_device",
     "fmr_spectrum_synchronize", "fmr_spectrum_read", "fmr_spectrum_reset", "fmr_find_stations",
     "fmr_spectrum_create_waterfall", "fmr_spectrum_read_waterfall",
+    "fmr_enable_monitor", "fmr_monitor_read", "fmr_monitor_derive",
 ]
 # FMR_WINDOW_* (include/fmradion_amd.h): windows of the band spectrum
 WINDOW_HANN, WINDOW_RECT, WINDOW_BLACKMAN_HARRIS = 0, 1, 2
@@ -59,6 +60,11 @@ RDS_OK, RDS_CORRECTED, RDS_BAD, RDS_CPRIME = 0, 1, 2, 4
 RDS_FEC_OFF, RDS_FEC_BURST, RDS_FEC_SOFT = 0, 1, 2
 # fmr_rds_group as a numpy structured type (24 bytes)
 RDS_GROUP = np.dtype([("sample_index", np.uint64), ("block", np.uint16, 4), ("status", np.uint8, 4), ("reserved", np.uint32)])
+# fmr_monitor_record as a numpy structured type (56 bytes)
+MONITOR_RECORD = np.dtype([("index", np.uint64), ("first_sample", np.uint64), ("n_finite", np.uint32),
+                           ("n_nonfinite", np.uint32), ("segments", np.uint32), ("segments_skipped", np.uint32),
+                           ("min", np.float32), ("max", np.float32), ("sum", np.float64), ("sumsq", np.float64)])
+MONITOR_PSD_BINS = 513
 
 
 class FmrError(RuntimeError):
@@ -125,6 +131,25 @@ class StationRule(C.Structure):
 class Station(C.Structure):
     _fields_ = [("offset_hz", C.c_int32), ("reserved", C.c_int32), ("level_db", C.c_double), ("snr_db", C.c_double),
                 ("centroid_hz", C.c_double)]
+
+
+class MonitorConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("interval_samples", C.c_uint32), ("hist_bins", C.c_int),
+                ("hist_range", C.c_double), ("max_records", C.c_int)]
+
+
+class MonitorInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("hist_bins", C.c_int), ("psd_bins", C.c_int),
+                ("records_complete", C.c_uint64), ("records_dropped", C.c_uint64), ("first_unread", C.c_uint64),
+                ("records_ready", C.c_uint64), ("interval_samples", C.c_uint32), ("max_records", C.c_int),
+                ("hist_range", C.c_double), ("bin_hz", C.c_double)]
+
+
+class MonitorLevels(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("reserved", C.c_int), ("tuning_offset_hz", C.c_double),
+                ("peak_deviation_hz", C.c_double), ("rms", C.c_double), ("mpx_power_dbr", C.c_double),
+                ("pilot_deviation_hz", C.c_double), ("rds_deviation_hz", C.c_double), ("hf_noise_density", C.c_double),
+                ("n_finite", C.c_uint64), ("segments", C.c_uint64)]
 
 
 def build_library(force=False, verbose=False):
@@ -225,6 +250,12 @@ def lib(ab=False):
     L.fmr_spectrum_read_waterfall.argtypes = [vp, C.c_int, fp, u32p, C.c_size_t, C.POINTER(WaterfallInfo)]
     L.fmr_find_stations.restype = C.c_int
     L.fmr_find_stations.argtypes = [dp, C.c_int, C.c_double, C.POINTER(StationRule), C.POINTER(Station), C.c_int]
+    L.fmr_enable_monitor.restype = C.c_int
+    L.fmr_enable_monitor.argtypes = [vp, C.POINTER(MonitorConfig), C.c_size_t]
+    L.fmr_monitor_read.restype = C.c_int
+    L.fmr_monitor_read.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.POINTER(MonitorInfo), C.c_size_t]
+    L.fmr_monitor_derive.restype = C.c_int
+    L.fmr_monitor_derive.argtypes = [vp, vp, C.c_int, C.POINTER(MonitorLevels), C.c_size_t]
     _libs[ab] = L
     return L
 
@@ -299,6 +330,20 @@ class RdsStatus(C.Structure):
 class RdsFec(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("mode", C.c_int), ("max_burst", C.c_int), ("soft_symbols", C.c_int),
                 ("soft_max_cost", C.c_double)]
+
+
+def monitor_levels(records, psd):
+    """fmr_monitor_derive (host only): the levels of the pooled records (a MONITOR_RECORD array and their psd [n, 513], as
+    Chain.monitor_records returns them), as a dict of fmr_monitor_levels."""
+    records = np.ascontiguousarray(records, dtype=MONITOR_RECORD)
+    psd = np.ascontiguousarray(psd, dtype=np.float64)
+    assert psd.shape == (len(records), MONITOR_PSD_BINS), psd.shape
+    out = MonitorLevels()
+    L = lib()
+    rc = L.fmr_monitor_derive(records.ctypes.data, psd.ctypes.data, len(records), C.byref(out), C.sizeof(MonitorLevels))
+    if rc != OK:
+        raise FmrError(f"fmr_monitor_derive failed ({rc}): {L.fmr_last_error().decode()}")
+    return {k: getattr(out, k) for k, _ in MonitorLevels._fields_ if k not in ("struct_size", "reserved")}
 
 
 def _rds_ok(g, i):
@@ -539,6 +584,31 @@ class Chain:
         buf = np.empty(cap, dtype=np.float32)
         n = self._chk(self._L.fmr_debug_read(self.h, int(stream), 5, buf.ctypes.data_as(C.c_void_p), buf.nbytes))
         return buf[:n].copy()
+
+    def enable_monitor(self, interval_samples=0, hist_bins=0, hist_range=0.0, max_records=0):
+        """fmr_enable_monitor: the modulation monitor of every stream / channel (FM chains, once, before the first call);
+        0 = the defaults (one-second records, 256 bins over +-2.0, 64 records kept)."""
+        cfg = MonitorConfig(C.sizeof(MonitorConfig), int(interval_samples), int(hist_bins), float(hist_range), int(max_records))
+        self._chk(self._L.fmr_enable_monitor(self.h, C.byref(cfg), C.sizeof(MonitorConfig)))
+
+    def monitor_records(self, stream=0, cap=None):
+        """fmr_monitor_read: the oldest unread complete records of `stream` (at most cap; None: all that wait) as
+        (records MONITOR_RECORD [n], hist uint32 [n, B], psd float64 [n, 513], info dict).  Reading drains them."""
+        info = MonitorInfo()
+        L = self._L
+        if cap is None:
+            cap = self._chk(L.fmr_monitor_read(self.h, int(stream), None, None, None, 0, C.byref(info), C.sizeof(MonitorInfo)))
+        else:
+            self._chk(L.fmr_monitor_read(self.h, int(stream), None, None, None, 0, C.byref(info), C.sizeof(MonitorInfo)))
+        cap, B = int(cap), int(info.hist_bins)
+        recs = np.zeros(cap, dtype=MONITOR_RECORD)
+        hist = np.zeros((cap, B), dtype=np.uint32)
+        psd = np.zeros((cap, MONITOR_PSD_BINS), dtype=np.float64)
+        n = 0
+        if cap > 0:
+            n = self._chk(L.fmr_monitor_read(self.h, int(stream), recs.ctypes.data, hist.ctypes.data, psd.ctypes.data, cap,
+                                             C.byref(info), C.sizeof(MonitorInfo)))
+        return recs[:n], hist[:n], psd[:n], {k: getattr(info, k) for k, _ in MonitorInfo._fields_}
 
     def pps_events(self, stream=0):
         ev = (PpsEvent * 64)()

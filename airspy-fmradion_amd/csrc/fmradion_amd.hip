@@ -33,6 +33,7 @@
 #include "kernels_chanbank.hpp"
 #include "kernels_rds.hpp"
 #include "kernels_spectrum.hpp"
+#include "kernels_monitor.hpp"
 #include "../host/fmradion_rds.hpp"
 
 namespace {
@@ -328,6 +329,25 @@ struct fmr_chain {
   int rds_init();
   int rds_stage(const fm_mpx_t *base, long long N, hipStream_t st);
   void rds_drain();
+  // ---- modulation monitor (fmr_enable_monitor; kernels_monitor.hpp).  A second reader of the
+  // call's MPX at the head of the audio tail, beside the RDS stage: it carries the stream's last unconsumed samples in a
+  // buffer of its own and counts in absolute samples (mon_n), so H_b and the cut into calls do not matter.  Nothing of it
+  // exists on a chain that never enabled it.
+  bool mon = false;
+  fmr_monitor_config mon_cfg{};              // the defaults filled in
+  int mon_spr = 0, mon_sub_n = 0, mon_sb = 0, mon_rmax = 0;   // segments per record / per sub-block, sub-blocks per record, runs per stream and launch
+  int mon_par = 0;                           // which copy of the open records is current
+  double mon_sumw2 = 0.0;
+  long long mon_n = 0, mon_next_seg = 0;     // MPX samples seen, segments processed
+  DevBuf<float> d_mon_win, d_mon_carry;
+  DevBuf<float2> d_mon_tw;
+  DevBuf<double> d_mon_ppsd, d_mon_open_psd, d_mon_ring_psd;
+  DevBuf<unsigned> d_mon_phist, d_mon_open_hist, d_mon_ring_hist;
+  DevBuf<MonRec> d_mon_prec, d_mon_open_rec, d_mon_ring_rec;
+  std::vector<unsigned long long> mon_read, mon_dropped;   // per stream: next unread record, records overwritten unread
+  int mon_init(const fmr_monitor_config &m);
+  int mon_stage(const fm_mpx_t *base, long long N, hipStream_t st);
+  void mon_catch_up(int s);
   int in_rows() const { return bank ? 1 : S; }   // rows of the input buffers (d_in, d_in_halo)
   // front end only (fmr_resample_blocks_device): stage B writes row s of this call's IF samples to if_out + s if_out_stride
   // instead of the chain's IF buffer (nullptr: the IF buffer)
@@ -433,6 +453,9 @@ struct fmr_chain {
     d_cb_taps.release(); d_cb_ph.release();
     d_rds_h1.release(); d_rds_h2.release(); d_rds_xhalo.release(); d_rds_lo.release(); d_rds_y1.release(); d_rds_y2.release();
     d_rds_state.release(); d_rds_est.release(); d_rds_rec.release();
+    d_mon_win.release(); d_mon_carry.release(); d_mon_tw.release(); d_mon_ppsd.release(); d_mon_open_psd.release();
+    d_mon_ring_psd.release(); d_mon_phist.release(); d_mon_open_hist.release(); d_mon_ring_hist.release();
+    d_mon_prec.release(); d_mon_open_rec.release(); d_mon_ring_rec.release();
     if (h_rds_slots) (void)hipHostFree(h_rds_slots);
     if (h_rds_mark) (void)hipHostFree(h_rds_mark);
     if (h_tab_all) (void)hipHostFree(h_tab_all);
@@ -2615,6 +2638,7 @@ void fmr_chain::tail_channels(const TailCtx &t, hipStream_t st, int ch_base, int
 // node pass, the output mux, and the joins with what ran beside the decoder stream (statistics, AGC, lock logic).
 int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
   if (rds) if (int rc = rds_stage(t.base, t.N_if, ts)) return rc;
+  if (mon) if (int rc = mon_stage(t.base, t.N_if, ts)) return rc;
   const int nch = t.nch, dc_nc = t.dc_nc;
   const long long N_au = t.N_au;
   if (t.mono_enqueued) tail_channels(t, ts, 1, 1);
@@ -2749,6 +2773,100 @@ int fmr_chain::rds_stage(const fm_mpx_t *base, long long N, hipStream_t st) {
   rds_tap_seq = seq;
   HIPCHK(hipGetLastError());
   return FMR_OK;
+}
+
+// ---- modulation monitor (kernels_monitor.hpp) ----
+int fmr_chain::mon_init(const fmr_monitor_config &m) {
+  static_assert(sizeof(MonRec) == sizeof(fmr_monitor_record), "MonRec is fmr_monitor_record");
+  mon_cfg = m;
+  mon_spr = (int)(m.interval_samples / kMonH);
+  // a full call in about 512 runs per stream: sub-blocks of 4 .. 32 segments (a run is a workgroup's serial work, and the
+  // partition only moves the fp64 rounding of the sums)
+  const size_t max_seg = max_if / kMonH + 2;
+  mon_sub_n = (int)std::min<size_t>(kMonSubMax, std::max<size_t>(kMonSubMin, (max_seg + 511) / 512));
+  mon_sb = (mon_spr + mon_sub_n - 1) / mon_sub_n;
+  mon_rmax = (int)std::min<size_t>(1024, max_seg / mon_sub_n + 2 * (max_seg / mon_spr + 2) + 2);
+  std::vector<float> w(kMonN);
+  std::vector<float2> tw(kMonN);
+  mon_sumw2 = 0.0;
+  for (int i = 0; i < kMonN; i++) {
+    w[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / kMonN));
+    mon_sumw2 += (double)w[i] * (double)w[i];
+    tw[i] = make_float2((float)std::cos(2.0 * M_PI * i / kMonN), (float)-std::sin(2.0 * M_PI * i / kMonN));
+  }
+  const size_t B = (size_t)m.hist_bins, L = (size_t)m.max_records, rows = (size_t)S * mon_rmax;
+  int rc;
+  if ((rc = upload(d_mon_win, w.data(), w.size()))) return rc;
+  if ((rc = upload(d_mon_tw, tw.data(), tw.size()))) return rc;
+  if ((rc = d_mon_carry.alloc((size_t)S * kMonN))) return rc;
+  if ((rc = d_mon_ppsd.alloc(rows * kMonPsd))) return rc;
+  if ((rc = d_mon_phist.alloc(rows * B))) return rc;
+  if ((rc = d_mon_prec.alloc(rows))) return rc;
+  if ((rc = d_mon_open_psd.alloc(2 * (size_t)S * kMonPsd))) return rc;
+  if ((rc = d_mon_open_hist.alloc(2 * (size_t)S * B))) return rc;
+  if ((rc = d_mon_open_rec.alloc(2 * (size_t)S))) return rc;
+  if ((rc = d_mon_ring_psd.alloc((size_t)S * L * kMonPsd))) return rc;
+  if ((rc = d_mon_ring_hist.alloc((size_t)S * L * B))) return rc;
+  if ((rc = d_mon_ring_rec.alloc((size_t)S * L))) return rc;
+  mon_read.assign(S, 0);
+  mon_dropped.assign(S, 0);
+  mon_n = mon_next_seg = 0;
+  mon_par = 0;
+  mon = true;
+  return FMR_OK;
+}
+
+// one call's MPX (N samples per stream from the base slot) through the monitor, on stream st: the segments whose last
+// sample the call delivers, in launches of at most mon_rmax runs per stream, then the carry
+int fmr_chain::mon_stage(const fm_mpx_t *base, long long N, hipStream_t st) {
+  if (N <= 0) return FMR_OK;
+  const long long base_stride = H_b + (long long)max_if;
+  const long long n0 = mon_n, n1 = n0 + N;
+  const long long j_hi = n1 >= kMonN ? (n1 - kMonN) / kMonH + 1 : 0;
+  MonArgs a{};
+  a.n0 = n0; a.spr = mon_spr; a.sub = mon_sub_n; a.sb = mon_sb; a.bins = mon_cfg.hist_bins;
+  a.rf = (float)mon_cfg.hist_range; a.scale = (float)((double)mon_cfg.hist_bins / (2.0 * mon_cfg.hist_range));
+  const int L = mon_cfg.max_records;
+  const long long M = (long long)mon_cfg.interval_samples;
+  long long j = mon_next_seg;
+  do {
+    int runs = 0, nrec = 1;
+    a.a0 = a.a1 = j; a.g0 = 0;
+    if (j < j_hi) {
+      const long long l = j / mon_spr;
+      a.g0 = l * mon_sb + (j - l * mon_spr) / mon_sub_n;
+      long long lo, hi;
+      mon_sub(mon_spr, mon_sub_n, mon_sb, a.g0 + mon_rmax - 1, lo, hi);
+      a.a1 = std::min(j_hi, hi);
+      const long long l_end = (a.a1 - 1) / mon_spr;
+      runs = (int)(l_end * mon_sb + (a.a1 - 1 - l_end * mon_spr) / mon_sub_n - a.g0 + 1);
+      nrec = (int)(l_end - l + 1);
+      timed_on(st, "mon_seg", [&] {
+        hipLaunchKernelGGL(k_mon_seg, dim3(runs, S), dim3(kMonT), 0, st, base, base_stride, H_b, d_mon_carry.p, a,
+                           d_mon_win.p, d_mon_tw.p, mon_rmax, d_mon_ppsd.p, d_mon_phist.p, d_mon_prec.p);
+      });
+    }
+    j = a.a1;
+    timed_on(st, "mon_reduce", [&] {
+      hipLaunchKernelGGL(k_mon_reduce, dim3(nrec, S), dim3(kMonT), 0, st, d_mon_ppsd.p, d_mon_phist.p, d_mon_prec.p, runs,
+                         mon_rmax, a, L, M, mon_par, d_mon_open_psd.p, d_mon_open_hist.p, d_mon_open_rec.p, d_mon_ring_psd.p,
+                         d_mon_ring_hist.p, d_mon_ring_rec.p, base, base_stride, H_b, d_mon_carry.p, n1, (int)(j >= j_hi));
+    });
+    if (runs > 0) mon_par ^= 1;
+  } while (j < j_hi);
+  mon_next_seg = std::max(mon_next_seg, j_hi);
+  mon_n = n1;
+  HIPCHK(hipGetLastError());
+  return FMR_OK;
+}
+
+// records the ring has overwritten unread: the read position follows, the loss is counted
+void fmr_chain::mon_catch_up(int s) {
+  const unsigned long long done = (unsigned long long)(mon_next_seg / mon_spr), L = (unsigned long long)mon_cfg.max_records;
+  if (done > L && mon_read[s] < done - L) {
+    mon_dropped[s] += done - L - mon_read[s];
+    mon_read[s] = done - L;
+  }
 }
 
 // the filled slots, in call order, through the host decoders (never blocks)
@@ -3856,6 +3974,143 @@ int fmr_set_rds_correction(fmr_chain *c, const fmr_rds_fec *fec, size_t fec_size
     for (fmr_rds::Decoder &d : c->rds_dec) d.set_correction(k);
     return FMR_OK;
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+// ---- modulation monitor: C-ABI ----
+int fmr_enable_monitor(fmr_chain *c, const fmr_monitor_config *cfg, size_t cfg_size) {
+  if (!cfg) { set_err("fmr_enable_monitor: cfg is null"); return FMR_ERR_BAD_ARG; }
+  const size_t size = cfg_size ? cfg_size : sizeof(fmr_monitor_config);
+  if (size > sizeof(fmr_monitor_config) || (size >= sizeof(unsigned) && cfg->struct_size > sizeof(fmr_monitor_config))) {
+    set_err("fmr_enable_monitor: struct_size %zu is larger than this library's fmr_monitor_config (%zu): the caller is newer "
+            "than the library", std::max(size, size >= sizeof(unsigned) ? (size_t)cfg->struct_size : (size_t)0), sizeof(fmr_monitor_config));
+    return FMR_ERR_BAD_ARG;
+  }
+  fmr_monitor_config m;
+  memset(&m, 0, sizeof m);
+  memcpy(&m, cfg, size);
+  if (m.interval_samples == 0) m.interval_samples = 384000;
+  if (m.hist_bins == 0) m.hist_bins = 256;
+  if (m.hist_range == 0.0) m.hist_range = 2.0;
+  if (m.max_records == 0) m.max_records = 64;
+  if (m.interval_samples % kMonH != 0 || m.interval_samples < (uint32_t)kMonH || m.interval_samples > (1u << 30)) {
+    set_err("fmr_enable_monitor: interval_samples %u is not a multiple of 512 in 512 .. 2^30 (0 = 384000)", m.interval_samples);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.hist_bins < 2 || m.hist_bins > kMonMaxHist) {
+    set_err("fmr_enable_monitor: hist_bins %d is outside 2 .. %d (0 = 256)", m.hist_bins, kMonMaxHist);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!(m.hist_range > 0.0) || !std::isfinite(m.hist_range)) {
+    set_err("fmr_enable_monitor: hist_range %g is not a finite value > 0 (0 = 2.0)", m.hist_range);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.max_records < 1 || m.max_records > 4096) {
+    set_err("fmr_enable_monitor: max_records %d is outside 1 .. 4096 (0 = 64)", m.max_records);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!c) { set_err("fmr_enable_monitor: chain is null"); return FMR_ERR_BAD_ARG; }
+  if (c->mode != FMR_MODE_FM) {
+    set_err("fmr_enable_monitor: the monitor reads the MPX of an FM chain (mode FMR_MODE_FM); mode %d %s", c->mode,
+            c->mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no MPX" : "has no MPX");
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (c->mon) { set_err("fmr_enable_monitor: the monitor of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
+  if (c->call_seq != 0) {
+    set_err("fmr_enable_monitor: the chain has already taken samples (the monitor counts from the chain's first MPX sample)");
+    return FMR_ERR_BAD_ARG;
+  }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    return c->mon_init(m);
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_monitor_read(fmr_chain *c, int stream, fmr_monitor_record *recs, uint32_t *hist, double *psd, int cap,
+                     fmr_monitor_info *info, size_t info_size) {
+  if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_monitor_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
+  if (!c->mon) { set_err("fmr_monitor_read: the chain has no monitor (fmr_enable_monitor)"); return FMR_ERR_BAD_ARG; }
+  if (cap > 0 && !recs) { set_err("fmr_monitor_read: recs is null"); return FMR_ERR_BAD_ARG; }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    const size_t B = (size_t)c->mon_cfg.hist_bins;
+    const unsigned long long L = (unsigned long long)c->mon_cfg.max_records;
+    const unsigned long long done = (unsigned long long)(c->mon_next_seg / c->mon_spr);
+    c->mon_catch_up(stream);
+    const unsigned long long first = c->mon_read[stream], ready = done - first;
+    const size_t n = (size_t)std::min<unsigned long long>(ready, (unsigned long long)cap);
+    for (size_t k = 0; k < n;) {       // the ring slots first % L .. in at most two contiguous pieces
+      const size_t slot = (size_t)((first + k) % L), m = std::min(n - k, (size_t)L - slot), at = (size_t)stream * L + slot;
+      HIPCHK(hipMemcpy(recs + k, c->d_mon_ring_rec.p + at, m * sizeof(fmr_monitor_record), hipMemcpyDeviceToHost));
+      if (hist) HIPCHK(hipMemcpy(hist + k * B, c->d_mon_ring_hist.p + at * B, m * B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      if (psd) HIPCHK(hipMemcpy(psd + k * kMonPsd, c->d_mon_ring_psd.p + at * kMonPsd, m * kMonPsd * sizeof(double), hipMemcpyDeviceToHost));
+      k += m;
+    }
+    if (psd) {
+      const double scale = 1.0 / (kFmRate * c->mon_sumw2);
+      for (size_t k = 0; k < n; k++) {
+        const double cnt = (double)recs[k].segments;
+        double *p = psd + k * kMonPsd;
+        for (int i = 0; i < kMonPsd; i++)
+          p[i] = recs[k].segments == 0 ? 0.0 : p[i] / cnt * ((i == 0 || i == kMonPsd - 1) ? 1.0 : 2.0) * scale;
+      }
+    }
+    c->mon_read[stream] = first + n;
+    if (info) {
+      fmr_monitor_info full{};
+      full.struct_size = (unsigned)sizeof full;
+      full.hist_bins = c->mon_cfg.hist_bins;
+      full.psd_bins = kMonPsd;
+      full.records_complete = done;
+      full.records_dropped = c->mon_dropped[stream];
+      full.first_unread = c->mon_read[stream];
+      full.records_ready = done - c->mon_read[stream];
+      full.interval_samples = c->mon_cfg.interval_samples;
+      full.max_records = c->mon_cfg.max_records;
+      full.hist_range = c->mon_cfg.hist_range;
+      full.bin_hz = kFmRate / kMonN;
+      const size_t isz = info_size ? info_size : sizeof full;
+      memcpy(info, &full, isz < sizeof full ? isz : sizeof full);
+    }
+    return cap == 0 ? (int)std::min<unsigned long long>(ready, (unsigned long long)INT_MAX) : (int)n;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_monitor_derive(const fmr_monitor_record *recs, const double *psd, int n, fmr_monitor_levels *out, size_t out_size) {
+  if (!recs || !out || n < 1) { set_err("fmr_monitor_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
+  const double F = kFmRate, df = F / kMonN;
+  double sum = 0.0, sumsq = 0.0, mn = INFINITY, mx = -INFINITY;
+  unsigned long long nf = 0, seg = 0;
+  std::vector<double> p(kMonPsd, 0.0);
+  for (int i = 0; i < n; i++) {
+    const fmr_monitor_record &r = recs[i];
+    sum += r.sum; sumsq += r.sumsq; nf += r.n_finite; seg += r.segments;
+    if (r.n_finite > 0) { mn = std::min(mn, (double)r.min); mx = std::max(mx, (double)r.max); }
+    if (psd && r.segments > 0)
+      for (int k = 0; k < kMonPsd; k++) p[k] += (double)r.segments * psd[(size_t)i * kMonPsd + k];
+  }
+  if (seg > 0) for (double &v : p) v /= (double)seg;
+  const double mean = nf ? sum / (double)nf : 0.0;
+  const double var = nf ? sumsq / (double)nf - mean * mean : 0.0;
+  auto band = [&](double lo, double hi, bool avg) {
+    double b = 0.0; int cnt = 0;
+    for (int k = 0; k < kMonPsd; k++) if (k * df >= lo && k * df <= hi) { b += p[k]; cnt++; }
+    return avg ? (cnt ? b / cnt : 0.0) : b * df;
+  };
+  fmr_monitor_levels full{};
+  full.struct_size = (unsigned)sizeof full;
+  full.tuning_offset_hz = 75000.0 * mean;
+  full.peak_deviation_hz = nf ? 75000.0 * std::max(mx - mean, mean - mn) : 0.0;
+  full.rms = var > 0.0 ? std::sqrt(var) : 0.0;
+  full.mpx_power_dbr = var > 0.0 ? 10.0 * std::log10(2.0 * (75.0 / 19.0) * (75.0 / 19.0) * var) : -INFINITY;
+  full.pilot_deviation_hz = 75000.0 * std::sqrt(2.0 * band(17875.0, 20125.0, false));
+  full.rds_deviation_hz = 75000.0 * std::sqrt(2.0 * band(54600.0, 59400.0, false));
+  full.hf_noise_density = band(100000.0, 150000.0, true);
+  full.n_finite = nf;
+  full.segments = seg;
+  const size_t osz = out_size ? out_size : sizeof full;
+  memcpy(out, &full, osz < sizeof full ? osz : sizeof full);
+  return FMR_OK;
 }
 
 int fmr_filter_table(const char *name, const void **data, int *is_double) {

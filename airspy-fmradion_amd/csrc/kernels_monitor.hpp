@@ -1,0 +1,271 @@
+// kernels_monitor.hpp -- modulation monitor of the 384 kHz MPX (fmr_enable_monitor).
+//
+// Indices are absolute, counted from the chain's first MPX sample.  N = 1024, H = 512, M = interval_samples (a multiple
+// of H).  Record i covers the samples [i M, (i + 1) M); segment j covers [j H, j H + N) and belongs to record
+// floor(j H / M): a record holds M / H segments, and its last one reaches H samples into the next record.  A segment is
+// processed in the call that delivers its last sample; the time-domain part of a record (counts, min, max, sum, sum of
+// squares, histogram) is taken over the FIRST H samples of each of its segments, so every sample enters it exactly
+// once, in the segment it starts, wherever a call ends.
+//
+// k_mon_seg: one workgroup (256 threads) = one run of segments of one stream.  A record is cut into aligned sub-blocks
+// of `sub` segments (4 .. 32, fixed per chain; the last one shorter); run r of a launch is sub-block g0 + r clipped to the launch's segments, so
+// a run never straddles a record boundary.  Per segment: 1024 floats from the call's MPX (or, in front of the call's
+// first sample, from the stream's carry), the time-domain part of the first 512 (histogram through LDS integer
+// atomics), then window, bit-reversed store, five radix-4 passes in LDS (the band spectrum's butterfly and padding)
+// and |X[k]|^2 of the bins 0 .. 512 into fp64 registers.  A segment with a non-finite sample is skipped for the spectral
+// part and counted; its finite samples still enter the time-domain part.  The run's values go to a partial once.
+//
+// k_mon_reduce: one workgroup per stream and record the launch touches adds the record's partials in run order (fp64,
+// fixed order, no float atomics), starting from the stream's open record when the record began in an earlier launch;
+// a record whose last segment is in goes to the ring [S][L], an open one back to the open record (two copies by launch
+// parity).  In the call's last launch it also copies the call's last samples into the carry (sample p at
+// carry[p mod 1024]: the up to 1023 samples no complete segment has consumed never collide there).
+//
+// Nothing here waits on another workgroup or on the host.  The density scaling c_k / (F sum w^2) and the division by the
+// segment count happen on the host when a record is read.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kernels_spectrum.hpp"
+
+namespace fmr {
+
+constexpr int kMonLog = 10, kMonN = 1 << kMonLog, kMonH = kMonN / 2, kMonPsd = kMonN / 2 + 1;
+constexpr int kMonT = 256;             // threads of both kernels: one radix-4 butterfly each per pass
+constexpr int kMonSubMin = 4, kMonSubMax = 32;   // segments per sub-block of a record (per chain: MonArgs::sub)
+constexpr int kMonMaxHist = 1024;
+
+// fmr_monitor_record, field for field (the engine checks the sizes); mn / mx hold +inf / -inf while nothing finite is in
+struct MonRec {
+  uint64_t index, first_sample;
+  uint32_t n_finite, n_nonfinite, segments, skipped;
+  float mn, mx;
+  double sum, sumsq;
+};
+
+struct MonArgs {
+  long long n0;        // absolute index of the call's first sample
+  long long a0, a1;    // the launch takes the segments [a0, a1)
+  long long g0;        // sub-block of segment a0
+  int spr, sub, sb;    // segments per record, per sub-block, sub-blocks per record = ceil(spr / sub)
+  int bins;            // histogram: B, Rf = (float)R, scale = (float)(B / (2 R))
+  float rf, scale;
+};
+
+// segments [lo, hi) of sub-block g (whole, before a launch clips it)
+__host__ __device__ inline void mon_sub(int spr, int sub, int sb, long long g, long long &lo, long long &hi) {
+  const long long l = g / sb, b = g - l * sb;
+  lo = l * spr + b * sub;
+  hi = lo + sub < (l + 1) * spr ? lo + sub : (l + 1) * spr;
+}
+
+// the histogram's bin rule, unfused fp32 (the clamp runs on the float: a huge sample never reaches the conversion)
+__device__ __forceinline__ int mon_bin(float x, float rf, float scale, int bins) {
+  float t = floorf((x + rf) * scale);
+  t = t < 0.f ? 0.f : t;
+  t = t > (float)(bins - 1) ? (float)(bins - 1) : t;
+  return (int)t;
+}
+
+// Stream s = blockIdx.y: the call's MPX at base + s base_stride + base_off (sample n0 first), the carry at
+// carry + s kMonN.  Partials of run r = blockIdx.x at row s rmax + r: ppsd [kMonPsd], phist [bins], prec.
+__global__ __launch_bounds__(kMonT) void k_mon_seg(const float *__restrict__ base, long long base_stride, int base_off,
+                                                   const float *__restrict__ carry, MonArgs a,
+                                                   const float *__restrict__ win, const float2 *__restrict__ tw, int rmax,
+                                                   double *__restrict__ ppsd, unsigned *__restrict__ phist,
+                                                   MonRec *__restrict__ prec) {
+  constexpr int N = kMonN, T = kMonT;
+  __shared__ float2 lds[N + (N >> 5)];
+  __shared__ unsigned s_hist[kMonMaxHist];
+  const int tid = threadIdx.x, run = blockIdx.x, s = blockIdx.y;
+  long long lo, hi;
+  mon_sub(a.spr, a.sub, a.sb, a.g0 + run, lo, hi);
+  const long long j_lo = lo > a.a0 ? lo : a.a0, j_hi = hi < a.a1 ? hi : a.a1;
+  const float *xin = base + (long long)s * base_stride + base_off;
+  const float *cin = carry + (long long)s * N;
+  for (int b = tid; b < a.bins; b += T) s_hist[b] = 0u;
+  __syncthreads();
+
+  double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;       // bins tid, tid + 256 and (thread 0) 512
+  double sum = 0.0, sumsq = 0.0;
+  float mn = INFINITY, mx = -INFINITY;
+  unsigned nfin = 0, nnon = 0, counted = 0, skipped = 0;
+
+  for (long long j = j_lo; j < j_hi; j++) {
+    const long long p0 = j * kMonH;
+    int bad = 0;
+#pragma unroll
+    for (int q = 0; q < N / T; q++) {
+      const int i = tid + q * T;
+      const long long p = p0 + i;
+      const float v = p < a.n0 ? cin[p & (N - 1)] : xin[p - a.n0];
+      const bool fin = isfinite(v);
+      bad |= !fin;
+      if (q < kMonH / T) {                 // the segment's first H samples: the time-domain part
+        if (fin) {
+          nfin++;
+          mn = fminf(mn, v);
+          mx = fmaxf(mx, v);
+          sum += (double)v;
+          sumsq += (double)v * (double)v;
+          atomicAdd(&s_hist[mon_bin(v, a.rf, a.scale, a.bins)], 1u);
+        } else {
+          nnon++;
+        }
+      }
+      lds[spec_pad((int)(__brev((unsigned)i) >> (32 - kMonLog)))] = make_float2(v * win[i], 0.f);
+    }
+    bad = __syncthreads_or(bad);
+    if (bad) { skipped++; continue; }      // (uniform: nobody has read the LDS, the next segment's stores may follow)
+    for (int span = 1; span < N; span *= 4) {
+      const int tstep = N / (4 * span);
+      const int jj = tid & (span - 1);
+      const int b0 = (tid - jj) * 4 + jj;
+      const int e0 = spec_pad(b0), e1 = spec_pad(b0 + 2 * span), e2 = spec_pad(b0 + span), e3 = spec_pad(b0 + 3 * span);
+      const float2 a0 = lds[e0];
+      const float2 a1 = cmul(lds[e1], tw[jj * tstep]);
+      const float2 a2 = cmul(lds[e2], tw[2 * jj * tstep]);
+      const float2 a3 = cmul(lds[e3], tw[3 * jj * tstep]);
+      const float2 s02 = make_float2(a0.x + a2.x, a0.y + a2.y), d02 = make_float2(a0.x - a2.x, a0.y - a2.y);
+      const float2 s13 = make_float2(a1.x + a3.x, a1.y + a3.y), d13 = make_float2(a1.x - a3.x, a1.y - a3.y);
+      lds[e0] = make_float2(s02.x + s13.x, s02.y + s13.y);
+      lds[e2] = make_float2(d02.x + d13.y, d02.y - d13.x);
+      lds[e1] = make_float2(s02.x - s13.x, s02.y - s13.y);
+      lds[e3] = make_float2(d02.x - d13.y, d02.y + d13.x);
+      __syncthreads();
+    }
+    {
+      const float2 x0 = lds[spec_pad(tid)], x1 = lds[spec_pad(tid + T)];
+      acc0 += (double)(x0.x * x0.x + x0.y * x0.y);
+      acc1 += (double)(x1.x * x1.x + x1.y * x1.y);
+      if (tid == 0) {
+        const float2 x2 = lds[spec_pad(N / 2)];
+        acc2 += (double)(x2.x * x2.x + x2.y * x2.y);
+      }
+    }
+    counted++;
+    __syncthreads();                       // every thread has read its bins before the next segment's stores
+  }
+
+  // the run's time-domain values: a fixed tree over the 256 threads (the FFT's LDS is free now)
+  __syncthreads();
+  double *r_sum = reinterpret_cast<double *>(lds), *r_sq = r_sum + T;
+  float *r_mn = reinterpret_cast<float *>(r_sq + T), *r_mx = r_mn + T;
+  unsigned *r_fin = reinterpret_cast<unsigned *>(r_mx + T), *r_non = r_fin + T;      // 8 KiB of the 8448 bytes
+  r_sum[tid] = sum; r_sq[tid] = sumsq; r_mn[tid] = mn; r_mx[tid] = mx; r_fin[tid] = nfin; r_non[tid] = nnon;
+  __syncthreads();
+  for (int st = T / 2; st > 0; st >>= 1) {
+    if (tid < st) {
+      r_sum[tid] += r_sum[tid + st];
+      r_sq[tid] += r_sq[tid + st];
+      r_mn[tid] = fminf(r_mn[tid], r_mn[tid + st]);
+      r_mx[tid] = fmaxf(r_mx[tid], r_mx[tid + st]);
+      r_fin[tid] += r_fin[tid + st];
+      r_non[tid] += r_non[tid + st];
+    }
+    __syncthreads();
+  }
+  const size_t prow = (size_t)s * rmax + run;
+  ppsd[prow * kMonPsd + tid] = acc0;
+  ppsd[prow * kMonPsd + tid + T] = acc1;
+  for (int b = tid; b < a.bins; b += T) phist[prow * a.bins + b] = s_hist[b];
+  if (tid == 0) {
+    ppsd[prow * kMonPsd + N / 2] = acc2;
+    MonRec r;
+    r.index = 0; r.first_sample = 0;
+    r.n_finite = r_fin[0]; r.n_nonfinite = r_non[0]; r.segments = counted; r.skipped = skipped;
+    r.mn = r_mn[0]; r.mx = r_mx[0]; r.sum = r_sum[0]; r.sumsq = r_sq[0];
+    prec[prow] = r;
+  }
+}
+
+// Block (x = record l0 + blockIdx.x of the launch, y = stream); l0 = the record of segment a0.  The block adds the
+// partials of its record's sub-blocks inside the launch in run order (fp64, no float atomics), starting from the open
+// record of the launch before (open_*[par]: [2][S] records, [2][S][bins] counters, [2][S][kMonPsd] sums) when the record
+// began there.  A record whose last segment is in goes to slot (index mod L) of the rings -- unless a later record of
+// the same launch takes that slot --, an open one to open_*[par ^ 1]: the block that reads the old copy is not the one
+// that writes the new one.  last != 0 (the call's last launch; runs may be 0): block 0 copies the samples
+// [max(n0, n_end - 1023), n_end) of the call to the carry.
+__global__ __launch_bounds__(kMonT) void k_mon_reduce(const double *__restrict__ ppsd, const unsigned *__restrict__ phist,
+                                                      const MonRec *__restrict__ prec, int runs, int rmax, MonArgs a,
+                                                      int L, long long M, int par, double *__restrict__ open_psd,
+                                                      unsigned *__restrict__ open_hist, MonRec *__restrict__ open_rec,
+                                                      double *__restrict__ ring_psd, unsigned *__restrict__ ring_hist,
+                                                      MonRec *__restrict__ ring_rec, const float *__restrict__ base,
+                                                      long long base_stride, int base_off, float *__restrict__ carry,
+                                                      long long n_end, int last) {
+  constexpr int T = kMonT, HB = kMonMaxHist / kMonT;
+  const int tid = threadIdx.x, s = blockIdx.y, S = gridDim.y;
+  if (runs > 0) {
+    const long long l = a.g0 / a.sb + blockIdx.x;
+    const long long g_last = a.g0 + runs - 1;
+    const int b_lo = blockIdx.x == 0 ? (int)(a.g0 - l * a.sb) : 0;
+    const int b_hi = (int)(a.sb < g_last - l * a.sb + 1 ? a.sb : g_last - l * a.sb + 1);
+    double p0 = 0.0, p1 = 0.0, p2 = 0.0;
+    unsigned h[HB];
+#pragma unroll
+    for (int k = 0; k < HB; k++) h[k] = 0u;
+    MonRec o{};
+    o.mn = INFINITY; o.mx = -INFINITY;
+    if (a.a0 > l * a.spr) {                 // the record began in an earlier launch (the launch's first record only)
+      const size_t os = (size_t)par * S + s;
+      p0 = open_psd[os * kMonPsd + tid];
+      p1 = open_psd[os * kMonPsd + tid + T];
+#pragma unroll
+      for (int k = 0; k < HB; k++)
+        if (tid + k * T < a.bins) h[k] = open_hist[os * a.bins + tid + k * T];
+      if (tid == 0) { p2 = open_psd[os * kMonPsd + kMonN / 2]; o = open_rec[os]; }
+    }
+    for (int b = b_lo; b < b_hi; b++) {
+      const size_t prow = (size_t)s * rmax + (size_t)(l * a.sb + b - a.g0);
+      p0 += ppsd[prow * kMonPsd + tid];
+      p1 += ppsd[prow * kMonPsd + tid + T];
+#pragma unroll
+      for (int k = 0; k < HB; k++)
+        if (tid + k * T < a.bins) h[k] += phist[prow * a.bins + tid + k * T];
+      if (tid == 0) {
+        const MonRec q = prec[prow];
+        p2 += ppsd[prow * kMonPsd + kMonN / 2];
+        o.n_finite += q.n_finite; o.n_nonfinite += q.n_nonfinite; o.segments += q.segments; o.skipped += q.skipped;
+        o.mn = fminf(o.mn, q.mn); o.mx = fmaxf(o.mx, q.mx);
+        o.sum += q.sum; o.sumsq += q.sumsq;
+      }
+    }
+    const long long last_done = a.a1 / a.spr - 1;      // last record complete after this launch
+    if (l <= last_done) {
+      if (l + L > last_done) {
+        const size_t slot = (size_t)s * L + (size_t)(l % L);
+        ring_psd[slot * kMonPsd + tid] = p0;
+        ring_psd[slot * kMonPsd + tid + T] = p1;
+#pragma unroll
+        for (int k = 0; k < HB; k++)
+          if (tid + k * T < a.bins) ring_hist[slot * a.bins + tid + k * T] = h[k];
+        if (tid == 0) {
+          ring_psd[slot * kMonPsd + kMonN / 2] = p2;
+          o.index = (uint64_t)l;
+          o.first_sample = (uint64_t)(l * M);
+          if (o.n_finite == 0) { o.mn = 0.f; o.mx = 0.f; }
+          ring_rec[slot] = o;
+        }
+      }
+    } else {
+      const size_t os = (size_t)(par ^ 1) * S + s;
+      open_psd[os * kMonPsd + tid] = p0;
+      open_psd[os * kMonPsd + tid + T] = p1;
+#pragma unroll
+      for (int k = 0; k < HB; k++)
+        if (tid + k * T < a.bins) open_hist[os * a.bins + tid + k * T] = h[k];
+      if (tid == 0) { open_psd[os * kMonPsd + kMonN / 2] = p2; open_rec[os] = o; }
+    }
+  }
+  if (last && blockIdx.x == 0) {
+    const float *xin = base + (long long)s * base_stride + base_off;
+    for (int q = tid; q < kMonN - 1; q += T) {
+      const long long p = n_end - (kMonN - 1) + q;
+      if (p >= a.n0) carry[(long long)s * kMonN + (p & (kMonN - 1))] = xin[p - a.n0];
+    }
+  }
+}
+
+}  // namespace fmr

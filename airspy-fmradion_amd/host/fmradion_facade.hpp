@@ -93,7 +93,38 @@ inline std::vector<fmr_rds_group> rds_groups(fmr_chain *c, int stream, fmr_rds::
   for (const auto &g : out) station.add(g);
   return out;
 }
+
+// modulation monitor (fmr_enable_monitor / fmr_monitor_read / fmr_monitor_derive): one drained record with its histogram,
+// its one-sided PSD (513 bins of 375 Hz) and the levels derived from it alone
+struct ModulationRecord {
+  fmr_monitor_record rec{};
+  std::vector<uint32_t> hist;
+  std::vector<double> psd;
+  fmr_monitor_levels levels{};
+};
+inline void monitor(fmr_chain *c, const fmr_monitor_config &m) {
+  check(fmr_enable_monitor(c, &m, sizeof m), "fmr_enable_monitor");
+}
+inline std::vector<ModulationRecord> monitor_records(fmr_chain *c, int stream) {
+  fmr_monitor_info info{};
+  const int ready = fmr_monitor_read(c, stream, nullptr, nullptr, nullptr, 0, &info, sizeof info);
+  if (ready < 0) check(ready, "fmr_monitor_read");
+  std::vector<ModulationRecord> out;
+  for (int i = 0; i < ready; i++) {
+    ModulationRecord r;
+    r.hist.resize((size_t)info.hist_bins);
+    r.psd.resize((size_t)info.psd_bins);
+    const int n = fmr_monitor_read(c, stream, &r.rec, r.hist.data(), r.psd.data(), 1, nullptr, 0);
+    if (n < 0) check(n, "fmr_monitor_read");
+    if (n == 0) break;
+    r.levels.struct_size = sizeof r.levels;
+    check(fmr_monitor_derive(&r.rec, r.psd.data(), 1, &r.levels, sizeof r.levels), "fmr_monitor_derive");
+    out.push_back(std::move(r));
+  }
+  return out;
+}
 }  // namespace fmr_detail
+using ModulationRecord = fmr_detail::ModulationRecord;
 
 // FilterParameters (include/FilterParameters.h:31-49): tables served by the library.
 struct FilterParameters {
@@ -228,6 +259,7 @@ public:
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg, m_rds);
+    if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
   }
 
   // RDS (no counterpart in the reference; fmr_create_rds): re-creates the chain with the RDS decoder, before the first
@@ -237,6 +269,7 @@ public:
     m_rds = true;
     fmr_destroy(m_chain);
     m_chain = fmr_detail::make(m_cfg, true);
+    if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
   }
   // error correction of the RDS blocks (fmr_set_rds_correction: FMR_RDS_FEC_OFF / _BURST / _SOFT; 0 = the defaults); at
   // any time after enable_rds(), from the decoder's next block boundary on.  enable_rds() starts with it off.
@@ -245,6 +278,19 @@ public:
   }
   std::vector<fmr_rds_group> get_rds_groups() { return fmr_detail::rds_groups(m_chain, 0, m_station); }
   const fmr_rds::Station &rds_station() { get_rds_groups(); return m_station; }
+
+  // Modulation monitor (no counterpart in the reference; fmr_enable_monitor): records of interval_samples MPX samples
+  // (0 = one second) with peak deviation, MPX power, pilot and RDS injection; before the first process(), once.
+  // read_modulation_records() drains the complete ones, oldest first.
+  void enable_modulation_monitor(uint32_t interval_samples = 0, int hist_bins = 0, double hist_range = 0.0, int max_records = 0) {
+    if (m_started) fmr_detail::fail("FmDecoder::enable_modulation_monitor: after the first process()");
+    m_mon_cfg = fmr_monitor_config{};
+    m_mon_cfg.struct_size = sizeof m_mon_cfg; m_mon_cfg.interval_samples = interval_samples; m_mon_cfg.hist_bins = hist_bins;
+    m_mon_cfg.hist_range = hist_range; m_mon_cfg.max_records = max_records;
+    fmr_detail::monitor(m_chain, m_mon_cfg);
+    m_mon = true;
+  }
+  std::vector<ModulationRecord> read_modulation_records() { return fmr_detail::monitor_records(m_chain, 0); }
 
   // Latency for throughput: hold back `blocks` - 1 calls and decode `blocks` blocks in ONE batched call.  process()
   // then returns an empty vector ("nothing yet": the contract of FmDecode.cpp:89-92,185-188, which main.cpp:981-984
@@ -265,6 +311,7 @@ public:
       fmr_destroy(m_chain);
       m_cfg.max_blocks = (int)blocks;
       m_chain = fmr_detail::make(m_cfg, m_rds);
+    if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
       m_capacity = blocks;
     }
     m_batch = blocks;
@@ -357,6 +404,8 @@ private:
     m_pps_fetched = true;
   }
   fmr_config m_cfg{};
+  bool m_mon = false;
+  fmr_monitor_config m_mon_cfg{};
   fmr_chain *m_chain = nullptr;
   bool m_rds = false;
   fmr_rds::Station m_station;
@@ -503,6 +552,7 @@ public:
     fmr_destroy(m_chain);
     m_cfg.channel_offset_hz = m_offsets.data();
     m_chain = fmr_detail::make(m_cfg, true);
+    if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     m_stations.assign(m_offsets.size(), fmr_rds::Station());
   }
   // error correction of every channel's RDS blocks (fmr_set_rds_correction), at any time after enable_rds()
@@ -514,6 +564,20 @@ public:
     return fmr_detail::rds_groups(m_chain, (int)ch, m_stations[ch]);
   }
   const fmr_rds::Station &rds_station(size_t ch) { get_rds_groups(ch); return m_stations[ch]; }
+
+  // Modulation monitor of every channel (fmr_enable_monitor), before the first process(), once; FM banks only.
+  // read_modulation_records(ch) drains channel ch's complete records, oldest first.
+  void enable_modulation_monitor(uint32_t interval_samples = 0, int hist_bins = 0, double hist_range = 0.0, int max_records = 0) {
+    m_mon_cfg = fmr_monitor_config{};
+    m_mon_cfg.struct_size = sizeof m_mon_cfg; m_mon_cfg.interval_samples = interval_samples; m_mon_cfg.hist_bins = hist_bins;
+    m_mon_cfg.hist_range = hist_range; m_mon_cfg.max_records = max_records;
+    fmr_detail::monitor(m_chain, m_mon_cfg);
+    m_mon = true;
+  }
+  std::vector<ModulationRecord> read_modulation_records(size_t ch) {
+    if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
+    return fmr_detail::monitor_records(m_chain, (int)ch);
+  }
 
   // audio[k] = what channel k produced from this capture block (empty = "nothing yet"); blocks longer than the chain's
   // block capacity are decoded in consecutive pieces
@@ -563,6 +627,8 @@ private:
   double m_freq_dev;
   fmr_config m_cfg{};
   std::vector<fmr_rds::Station> m_stations;
+  bool m_mon = false;
+  fmr_monitor_config m_mon_cfg{};
   fmr_chain *m_chain = nullptr;
 };
 

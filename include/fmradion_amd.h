@@ -535,6 +535,86 @@ int fmr_spectrum_read_waterfall(fmr_spectrum *s, int row, float *out, uint32_t *
 int fmr_find_stations(const double *psd, int fft_size, double input_rate, const fmr_station_rule *rule, fmr_station *out,
                       int cap);
 
+/* --- Modulation monitor (no counterpart in the reference).  An FM chain with the monitor enabled
+ * measures the 384 kHz MPX of every stream / bank channel where it lies on the device: peak deviation and its
+ * distribution (ITU-R SM.1268), MPX power (ITU-R BS.412), pilot and RDS injection, the noise above the multiplex.  The
+ * audio, fmr_status, PPS events and RDS groups of the chain are what they are without it: the stage only reads the MPX.
+ * Indices are absolute, counted from the chain's first MPX sample; nothing depends on the cut into blocks and calls.
+ *   F = 384000, N = 1024, H = 512, M = interval_samples.  Record i covers the MPX samples [i M, (i + 1) M).
+ * Time-domain part, over the finite samples x of the record (a non-finite sample is counted in n_nonfinite and enters
+ * nothing else): n_finite; min and max (the samples' own fp32 values; both 0 when n_finite = 0); sum and sumsq (fp64 sums
+ * of the fp32 samples and of their fp64 squares); a histogram of B = hist_bins uint32 counters over [-R, R), R =
+ * hist_range (1.0 = 75 kHz): a sample's bin is clamp(floorf((x + Rf) * scale), 0, B - 1) with Rf = (float)R and
+ * scale = (float)(B / (2 R)), all unfused fp32 (numpy float32 gives the same bin for every sample); samples beyond the
+ * range land in the end bins.
+ * Spectral part: segment j covers [j H, j H + N) and belongs to record floor(j H / M) (the last segment of a record
+ * reaches 512 samples into the next record).  Periodic Hann window, built in double and rounded once to fp32.  One-sided
+ * density, k = 0 .. 512 (bin k at k F / N Hz):  P_j[k] = c_k |sum_n w[n] x[j H + n] exp(-2 pi i k n / N)|^2 / (F sum w^2),
+ * c_k = 2 for 0 < k < 512 and 1 at both ends, so that sum_k psd[k] F / N is the mean square.  A segment that holds a
+ * non-finite sample is skipped and counted in segments_skipped; psd is the mean of the counted P_j (fp64 sum on the
+ * device, divided on the host when read), all zeros when segments = 0.
+ * Completion: record i is complete in the call that delivers the absolute sample (i + 1) M + 511, the last sample of
+ * its last segment.
+ * Ring: max_records = L records per stream.  When L unread records exist and another completes, the oldest is
+ * overwritten and counted in records_dropped; processing never fails because of it.
+ * Reproducibility: counts, histogram, min, max, segments and segments_skipped are bit-identical for any cut of the
+ * input into calls; sum, sumsq and psd add the same fp32 per-segment values in fp64 in a fixed order without float atomics
+ * (the same cut gives the same bits; another cut differs at fp64 rounding, ~1e-15 relative). */
+typedef struct {
+  unsigned struct_size;       /* sizeof(fmr_monitor_config) as the caller knows it (0: cfg_size); a larger size is refused */
+  uint32_t interval_samples;  /* M: a multiple of 512 in 512 .. 2^30; 0 = 384000 (one second) */
+  int hist_bins;              /* B: 2 .. 1024; 0 = 256 */
+  double hist_range;          /* R > 0, finite; 0 = 2.0 */
+  int max_records;            /* L: 1 .. 4096; 0 = 64 */
+} fmr_monitor_config;
+typedef struct {
+  uint64_t index, first_sample;   /* i and i M */
+  uint32_t n_finite, n_nonfinite, segments, segments_skipped;
+  float min, max;
+  double sum, sumsq;
+} fmr_monitor_record;
+typedef struct {
+  unsigned struct_size;
+  int hist_bins, psd_bins;        /* B; 513 */
+  uint64_t records_complete;      /* since create (of every stream: they run in step) */
+  uint64_t records_dropped;       /* of this stream: overwritten unread */
+  uint64_t first_unread;          /* index of the oldest unread record after this call */
+  uint64_t records_ready;         /* complete records still unread after this call */
+  uint32_t interval_samples;      /* M, B's range and L as enabled (defaults filled in) */
+  int max_records;
+  double hist_range;
+  double bin_hz;                  /* F / N = 375 */
+} fmr_monitor_info;
+typedef struct {
+  unsigned struct_size;
+  int reserved;
+  double tuning_offset_hz;        /* 75000 mean */
+  double peak_deviation_hz;       /* 75000 max(max - mean, mean - min) */
+  double rms;                     /* sqrt(var), MPX units */
+  double mpx_power_dbr;           /* 10 log10(2 (75/19)^2 var): 0 dBr is a sine of +-19 kHz (BS.412); -INFINITY when var <= 0 */
+  double pilot_deviation_hz;      /* 75000 sqrt(2 B(17875, 20125)) */
+  double rds_deviation_hz;        /* 75000 sqrt(2 B(54600, 59400)): the unmodulated carrier of the same band power */
+  double hf_noise_density;        /* mean psd[k] over 100 kHz <= k F / N <= 150 kHz, MPX^2 / Hz */
+  uint64_t n_finite, segments;    /* pooled */
+} fmr_monitor_levels;
+/* Checks the fields first (FMR_ERR_BAD_ARG, fmr_last_error names the field; also a size larger than this library's
+ * struct), then the chain: NULL is FMR_ERR_BAD_ARG; any FMR_MODE_FM chain is accepted (fmr_create and fmr_create_rds,
+ * banks, either resampler class, pipelined or in_order, -f, the equaliser); every other mode and front-end-only chains
+ * are FMR_ERR_UNSUPPORTED.  Allowed once, before the chain's first sample: a second call, or one after any processing
+ * call, is FMR_ERR_BAD_ARG.  A chain that never calls it allocates nothing for the monitor and runs none of its kernels. */
+int fmr_enable_monitor(fmr_chain *c, const fmr_monitor_config *cfg, size_t cfg_size);
+/* Synchronises like the other getters, then drains up to cap complete records of `stream`, oldest first, and returns how
+ * many: recs[cap], hist[cap x B] and psd[cap x 513] (either may be NULL).  cap = 0 returns the number waiting and drains
+ * nothing.  info (may be NULL) takes info_size bytes (0 = this header's size).  FMR_ERR_BAD_ARG on a chain without the
+ * monitor. */
+int fmr_monitor_read(fmr_chain *c, int stream, fmr_monitor_record *recs, uint32_t *hist, double *psd, int cap,
+                     fmr_monitor_info *info, size_t info_size);
+/* Host only, in double, no device.  Pools n records (psd: n x 513 as read, or NULL: the band levels are 0): sums and
+ * counts add, min and max run over the records with n_finite > 0, psd is weighted by segments.  With mean = sum / n_finite,
+ * var = sumsq / n_finite - mean^2 and B(lo, hi) = sum of psd[k] F / N over lo <= k F / N <= hi it fills the levels above
+ * (n_finite = 0: mean, var and the peak deviation are 0). */
+int fmr_monitor_derive(const fmr_monitor_record *recs, const double *psd, int n, fmr_monitor_levels *out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif
