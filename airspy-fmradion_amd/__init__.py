@@ -49,6 +49,7 @@ EXPORTS = [
     "fmr_spectrum_synchronize", "fmr_spectrum_read", "fmr_spectrum_reset", "fmr_find_stations",
     "fmr_spectrum_create_waterfall", "fmr_spectrum_read_waterfall",
     "fmr_enable_monitor", "fmr_monitor_read", "fmr_monitor_derive",
+    "fmr_enable_loudness", "fmr_loudness_read", "fmr_loudness_derive",
 ]
 # FMR_WINDOW_* (include/fmradion_amd.h): windows of the band spectrum
 WINDOW_HANN, WINDOW_RECT, WINDOW_BLACKMAN_HARRIS = 0, 1, 2
@@ -65,6 +66,11 @@ MONITOR_RECORD = np.dtype([("index", np.uint64), ("first_sample", np.uint64), ("
                            ("n_nonfinite", np.uint32), ("segments", np.uint32), ("segments_skipped", np.uint32),
                            ("min", np.float32), ("max", np.float32), ("sum", np.float64), ("sumsq", np.float64)])
 MONITOR_PSD_BINS = 513
+# fmr_loudness_record as a numpy structured type (104 bytes)
+LOUDNESS_RECORD = np.dtype([("index", np.uint64), ("first_sample", np.uint64), ("n_nonfinite", np.uint32),
+                            ("channels", np.uint32), ("step_samples", np.uint32), ("reserved", np.uint32),
+                            ("kw_sumsq", np.float64, 2), ("sumsq", np.float64, 2), ("sum_lr", np.float64),
+                            ("sample_peak", np.float64, 2), ("true_peak", np.float64, 2)])
 
 
 class FmrError(RuntimeError):
@@ -150,6 +156,25 @@ class MonitorLevels(C.Structure):
                 ("peak_deviation_hz", C.c_double), ("rms", C.c_double), ("mpx_power_dbr", C.c_double),
                 ("pilot_deviation_hz", C.c_double), ("rds_deviation_hz", C.c_double), ("hf_noise_density", C.c_double),
                 ("n_finite", C.c_uint64), ("segments", C.c_uint64)]
+
+
+class LoudnessConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("step_samples", C.c_uint32), ("max_records", C.c_int)]
+
+
+class LoudnessInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("channels", C.c_int), ("records_complete", C.c_uint64),
+                ("records_dropped", C.c_uint64), ("first_unread", C.c_uint64), ("records_ready", C.c_uint64),
+                ("step_samples", C.c_uint32), ("max_records", C.c_int)]
+
+
+class LoudnessLevels(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("reserved", C.c_int), ("momentary_lufs", C.c_double),
+                ("momentary_max_lufs", C.c_double), ("short_term_lufs", C.c_double), ("short_term_max_lufs", C.c_double),
+                ("integrated_lufs", C.c_double), ("sample_peak_dbfs", C.c_double), ("true_peak_dbtp", C.c_double),
+                ("correlation", C.c_double), ("side_to_mid_db", C.c_double), ("longest_silence_blocks", C.c_uint64),
+                ("trailing_silence_blocks", C.c_uint64), ("n_nonfinite", C.c_uint64), ("momentary_windows", C.c_uint64),
+                ("gated_windows", C.c_uint64)]
 
 
 def build_library(force=False, verbose=False):
@@ -256,6 +281,12 @@ def lib(ab=False):
     L.fmr_monitor_read.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.POINTER(MonitorInfo), C.c_size_t]
     L.fmr_monitor_derive.restype = C.c_int
     L.fmr_monitor_derive.argtypes = [vp, vp, C.c_int, C.POINTER(MonitorLevels), C.c_size_t]
+    L.fmr_enable_loudness.restype = C.c_int
+    L.fmr_enable_loudness.argtypes = [vp, C.POINTER(LoudnessConfig), C.c_size_t]
+    L.fmr_loudness_read.restype = C.c_int
+    L.fmr_loudness_read.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(LoudnessInfo), C.c_size_t]
+    L.fmr_loudness_derive.restype = C.c_int
+    L.fmr_loudness_derive.argtypes = [vp, C.c_int, C.c_double, C.POINTER(LoudnessLevels), C.c_size_t]
     _libs[ab] = L
     return L
 
@@ -330,6 +361,18 @@ class RdsStatus(C.Structure):
 class RdsFec(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("mode", C.c_int), ("max_burst", C.c_int), ("soft_symbols", C.c_int),
                 ("soft_max_cost", C.c_double)]
+
+
+def loudness_levels(records, silence_dbfs=-60.0):
+    """fmr_loudness_derive (host only): loudness, peaks, stereo and silence figures of the records (a LOUDNESS_RECORD
+    array in ascending order, as Chain.loudness_records returns them), as a dict of fmr_loudness_levels."""
+    L = lib()
+    records = np.ascontiguousarray(records, dtype=LOUDNESS_RECORD)
+    out = LoudnessLevels()
+    rc = L.fmr_loudness_derive(records.ctypes.data, len(records), float(silence_dbfs), C.byref(out), C.sizeof(LoudnessLevels))
+    if rc != OK:
+        raise FmrError(f"fmr_loudness_derive failed ({rc}): {L.fmr_last_error().decode()}")
+    return {k: getattr(out, k) for k, _ in LoudnessLevels._fields_ if k not in ("struct_size", "reserved")}
 
 
 def monitor_levels(records, psd):
@@ -609,6 +652,25 @@ class Chain:
             n = self._chk(L.fmr_monitor_read(self.h, int(stream), recs.ctypes.data, hist.ctypes.data, psd.ctypes.data, cap,
                                              C.byref(info), C.sizeof(MonitorInfo)))
         return recs[:n], hist[:n], psd[:n], {k: getattr(info, k) for k, _ in MonitorInfo._fields_}
+
+    def enable_loudness(self, step_samples=0, max_records=0):
+        """fmr_enable_loudness: the audio monitor of every stream / channel (FM chains, once, before the first call);
+        0 = the defaults (sub-blocks of 4800 audio samples, 1024 records kept)."""
+        cfg = LoudnessConfig(C.sizeof(LoudnessConfig), int(step_samples), int(max_records))
+        self._chk(self._L.fmr_enable_loudness(self.h, C.byref(cfg), C.sizeof(LoudnessConfig)))
+
+    def loudness_records(self, stream=0, cap=None):
+        """fmr_loudness_read: the oldest unread complete records of `stream` (at most cap; None: all that wait) as
+        (records LOUDNESS_RECORD [n], info dict).  Reading drains them."""
+        info = LoudnessInfo()
+        L = self._L
+        waiting = self._chk(L.fmr_loudness_read(self.h, int(stream), None, 0, C.byref(info), C.sizeof(LoudnessInfo)))
+        cap = int(waiting if cap is None else cap)
+        recs = np.zeros(cap, dtype=LOUDNESS_RECORD)
+        n = 0
+        if cap > 0:
+            n = self._chk(L.fmr_loudness_read(self.h, int(stream), recs.ctypes.data, cap, C.byref(info), C.sizeof(LoudnessInfo)))
+        return recs[:n], {k: getattr(info, k) for k, _ in LoudnessInfo._fields_}
 
     def pps_events(self, stream=0):
         ev = (PpsEvent * 64)()

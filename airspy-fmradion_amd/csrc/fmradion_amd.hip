@@ -34,6 +34,7 @@
 #include "kernels_rds.hpp"
 #include "kernels_spectrum.hpp"
 #include "kernels_monitor.hpp"
+#include "kernels_loudness.hpp"
 #include "../host/fmradion_rds.hpp"
 
 namespace {
@@ -348,6 +349,21 @@ struct fmr_chain {
   int mon_init(const fmr_monitor_config &m);
   int mon_stage(const fm_mpx_t *base, long long N, hipStream_t st);
   void mon_catch_up(int s);
+  // ---- audio monitor (fmr_enable_loudness; kernels_loudness.hpp).  A reader of the call's finished
+  // audio behind the output mux, on the tail's stream: it counts in absolute audio samples (ld_n) and keeps its own
+  // carries (the K-weighting state, the true-peak history, the open record).  Nothing of it exists unless it is enabled.
+  bool ld = false;
+  fmr_loudness_config ld_cfg{};              // the defaults filled in
+  int ld_cps = 0, ld_rmax = 0, ld_par = 0;   // chunks per sub-block, runs per stream and launch, current copy of the open records
+  long long ld_n = 0;                        // audio samples seen (per channel)
+  LdCoef ld_coef{};
+  DevBuf<double> d_ld_pw, d_ld_taps, d_ld_G, d_ld_start, d_ld_pkw, d_ld_state, d_ld_hist;
+  DevBuf<LdPart> d_ld_part;
+  DevBuf<LdRec> d_ld_open, d_ld_ring;
+  std::vector<unsigned long long> ld_read, ld_dropped;     // per stream: next unread record, records overwritten unread
+  int ld_init(const fmr_loudness_config &m);
+  int ld_stage(const double *d_aud, long long astride, long long N, hipStream_t st);
+  void ld_catch_up(int s);
   int in_rows() const { return bank ? 1 : S; }   // rows of the input buffers (d_in, d_in_halo)
   // front end only (fmr_resample_blocks_device): stage B writes row s of this call's IF samples to if_out + s if_out_stride
   // instead of the chain's IF buffer (nullptr: the IF buffer)
@@ -456,6 +472,8 @@ struct fmr_chain {
     d_mon_win.release(); d_mon_carry.release(); d_mon_tw.release(); d_mon_ppsd.release(); d_mon_open_psd.release();
     d_mon_ring_psd.release(); d_mon_phist.release(); d_mon_open_hist.release(); d_mon_ring_hist.release();
     d_mon_prec.release(); d_mon_open_rec.release(); d_mon_ring_rec.release();
+    d_ld_pw.release(); d_ld_taps.release(); d_ld_G.release(); d_ld_start.release(); d_ld_pkw.release(); d_ld_state.release();
+    d_ld_hist.release(); d_ld_part.release(); d_ld_open.release(); d_ld_ring.release();
     if (h_rds_slots) (void)hipHostFree(h_rds_slots);
     if (h_rds_mark) (void)hipHostFree(h_rds_mark);
     if (h_tab_all) (void)hipHostFree(h_tab_all);
@@ -2665,6 +2683,7 @@ int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
       });
     }
   }
+  if (ld) if (int rc = ld_stage(t.d_aud, t.astride, N_au, ts)) return rc;
   if (!(t.fin_covers_all && N_au > 0)) {        // (otherwise the wait before the output mux covered all three)
     HIPCHK(hipStreamWaitEvent(ts, ev_stats, 0));
     if (t.agc_on_side) HIPCHK(hipStreamWaitEvent(ts, ev_agc, 0));
@@ -2866,6 +2885,117 @@ void fmr_chain::mon_catch_up(int s) {
   if (done > L && mon_read[s] < done - L) {
     mon_dropped[s] += done - L - mon_read[s];
     mon_read[s] = done - L;
+  }
+}
+
+// ---- audio monitor (kernels_loudness.hpp) ----
+int fmr_chain::ld_init(const fmr_loudness_config &m) {
+  static_assert(sizeof(LdRec) == sizeof(fmr_loudness_record), "LdRec is fmr_loudness_record");
+  ld_cfg = m;
+  const int Q = (int)m.step_samples;
+  ld_cps = (Q + kLdC - 1) / kLdC;
+  // a call's runs: its whole chunks, one more per sub-block it touches, one at either end
+  ld_rmax = (int)std::min<size_t>(kLdMaxRuns, max_au / kLdC + max_au / Q + 4);
+  // BS.1770-4 K-weighting at 48 kHz: the shelf, then the high-pass
+  ld_coef.b0[0] = 1.53512485958697; ld_coef.b1[0] = -2.69169618940638; ld_coef.b2[0] = 1.19839281085285;
+  ld_coef.a1[0] = -1.69065929318241; ld_coef.a2[0] = 0.73248077421585;
+  ld_coef.b0[1] = 1.0; ld_coef.b1[1] = -2.0; ld_coef.b2[1] = 1.0;
+  ld_coef.a1[1] = -1.99004745483398; ld_coef.a2[1] = 0.99007225036621;
+  // A: one step of the recurrence itself on the unit states (column j = the state after e_j), then A^(2^b) by squaring
+  std::vector<double> pw((size_t)kLdPow * 16);
+  for (int j = 0; j < 4; j++) {
+    double z[4] = {0.0, 0.0, 0.0, 0.0};
+    z[j] = 1.0;
+    (void)ld_step(ld_coef, 0.0, z);
+    for (int i = 0; i < 4; i++) pw[(size_t)i * 4 + j] = z[i];
+  }
+  for (int b = 1; b < kLdPow; b++) {
+    const double *x = &pw[(size_t)(b - 1) * 16];
+    for (int i = 0; i < 4; i++)
+      for (int j = 0; j < 4; j++) {
+        long double acc = 0.0L;
+        for (int k = 0; k < 4; k++) acc += (long double)x[i * 4 + k] * (long double)x[k * 4 + j];
+        pw[(size_t)b * 16 + i * 4 + j] = (double)acc;
+      }
+  }
+  // true peak: g_p[k] = sinc(k - p/4) (0.5 + 0.5 cos(pi (k - p/4) / 6)), p = 1 .. 3, k = -5 .. 6
+  std::vector<double> taps(3 * kLdTaps);
+  for (int p = 1; p < 4; p++)
+    for (int k = -5; k <= 6; k++) {
+      const double t = (double)k - (double)p / 4.0;
+      const double u = M_PI * t;
+      taps[(size_t)(p - 1) * kLdTaps + (k + 5)] = (std::sin(u) / u) * (0.5 + 0.5 * std::cos(u / 6.0));
+    }
+  const size_t L = (size_t)m.max_records, rows = (size_t)S * 2 * ld_rmax;
+  int rc;
+  if ((rc = upload(d_ld_pw, pw.data(), pw.size()))) return rc;
+  if ((rc = upload(d_ld_taps, taps.data(), taps.size()))) return rc;
+  if ((rc = d_ld_G.alloc(rows * 4))) return rc;
+  if ((rc = d_ld_start.alloc(rows * 4))) return rc;
+  if ((rc = d_ld_pkw.alloc(rows))) return rc;
+  if ((rc = d_ld_part.alloc((size_t)S * ld_rmax))) return rc;
+  if ((rc = d_ld_state.alloc((size_t)S * 2 * 4))) return rc;
+  if ((rc = d_ld_hist.alloc((size_t)S * 2 * kLdHist))) return rc;
+  if ((rc = d_ld_open.alloc(2 * (size_t)S))) return rc;
+  if ((rc = d_ld_ring.alloc((size_t)S * L))) return rc;
+  ld_read.assign(S, 0);
+  ld_dropped.assign(S, 0);
+  ld_n = 0;
+  ld_par = 0;
+  ld = true;
+  return FMR_OK;
+}
+
+// one call's audio (N samples per channel and stream, where the mux wrote them) through the audio monitor, on stream st,
+// in launches of at most ld_rmax runs per stream
+int fmr_chain::ld_stage(const double *d_aud, long long astride, long long N, hipStream_t st) {
+  if (N <= 0) return FMR_OK;
+  LdArgs a{};
+  a.n0 = ld_n; a.Q = (int)ld_cfg.step_samples; a.cps = ld_cps; a.ch = stereo ? 2 : 1;
+  const long long n1 = ld_n + N;
+  auto chunk_of = [&](long long p) { const long long q = p / a.Q; return q * a.cps + (p - q * a.Q) / kLdC; };
+  long long p = ld_n;
+  while (p < n1) {
+    a.a0 = p; a.g0 = chunk_of(p);
+    long long lo, hi;
+    ld_chunk(a.Q, a.cps, a.g0 + ld_rmax - 1, lo, hi);
+    a.a1 = std::min(n1, hi);
+    const int runs = (int)(chunk_of(a.a1 - 1) - a.g0 + 1);
+    const int nrec = (int)((a.a1 - 1) / a.Q - a.a0 / a.Q + 1);
+    const int lanes = runs * a.ch;
+    timed_on(st, "ld_nodes", [&] {
+      hipLaunchKernelGGL(k_ld_pass1, dim3((lanes + 63) / 64, S), dim3(64), 0, st, d_aud, astride, a, ld_coef, runs, ld_rmax,
+                         d_ld_G.p);
+      hipLaunchKernelGGL(k_ld_nodes, dim3(S * a.ch), dim3(64), 0, st, d_ld_G.p, d_ld_start.p, a, runs, ld_rmax, d_ld_pw.p,
+                         d_ld_state.p);
+    });
+    timed_on(st, "ld_pass2", [&] {
+      hipLaunchKernelGGL(k_ld_pass2, dim3((lanes + 63) / 64, S), dim3(64), 0, st, d_aud, astride, a, ld_coef, runs, ld_rmax,
+                         d_ld_start.p, d_ld_pkw.p, d_ld_state.p);
+    });
+    timed_on(st, "ld_block", [&] {
+      hipLaunchKernelGGL(k_ld_block, dim3(runs, S), dim3(kLdC), 0, st, d_aud, astride, a, ld_rmax, d_ld_taps.p, d_ld_hist.p,
+                         d_ld_part.p);
+    });
+    timed_on(st, "ld_reduce", [&] {
+      hipLaunchKernelGGL(k_ld_reduce, dim3(nrec, S), dim3(64), 0, st, d_ld_pkw.p, d_ld_part.p, runs, ld_rmax, a,
+                         (int)ld_cfg.max_records, ld_par, d_ld_open.p, d_ld_ring.p, d_aud, astride, d_ld_hist.p,
+                         (int)(a.a1 >= n1));
+    });
+    ld_par ^= 1;
+    p = a.a1;
+  }
+  ld_n = n1;
+  HIPCHK(hipGetLastError());
+  return FMR_OK;
+}
+
+// records the ring has overwritten unread: the read position follows, the loss is counted
+void fmr_chain::ld_catch_up(int s) {
+  const unsigned long long done = (unsigned long long)(ld_n / (long long)ld_cfg.step_samples), L = (unsigned long long)ld_cfg.max_records;
+  if (done > L && ld_read[s] < done - L) {
+    ld_dropped[s] += done - L - ld_read[s];
+    ld_read[s] = done - L;
   }
 }
 
@@ -4108,6 +4238,153 @@ int fmr_monitor_derive(const fmr_monitor_record *recs, const double *psd, int n,
   full.hf_noise_density = band(100000.0, 150000.0, true);
   full.n_finite = nf;
   full.segments = seg;
+  const size_t osz = out_size ? out_size : sizeof full;
+  memcpy(out, &full, osz < sizeof full ? osz : sizeof full);
+  return FMR_OK;
+}
+
+// ---- audio monitor: C-ABI ----
+int fmr_enable_loudness(fmr_chain *c, const fmr_loudness_config *cfg, size_t cfg_size) {
+  if (!cfg) { set_err("fmr_enable_loudness: cfg is null"); return FMR_ERR_BAD_ARG; }
+  const size_t size = cfg_size ? cfg_size : sizeof(fmr_loudness_config);
+  if (size > sizeof(fmr_loudness_config) || (size >= sizeof(unsigned) && cfg->struct_size > sizeof(fmr_loudness_config))) {
+    set_err("fmr_enable_loudness: struct_size %zu is larger than this library's fmr_loudness_config (%zu): the caller is newer "
+            "than the library", std::max(size, size >= sizeof(unsigned) ? (size_t)cfg->struct_size : (size_t)0), sizeof(fmr_loudness_config));
+    return FMR_ERR_BAD_ARG;
+  }
+  fmr_loudness_config m;
+  memset(&m, 0, sizeof m);
+  memcpy(&m, cfg, size);
+  if (m.step_samples == 0) m.step_samples = 4800;
+  if (m.max_records == 0) m.max_records = 1024;
+  if (m.step_samples % 16 != 0 || m.step_samples < 48 || m.step_samples > (1u << 20)) {
+    set_err("fmr_enable_loudness: step_samples %u is not a multiple of 16 in 48 .. 2^20 (0 = 4800)", m.step_samples);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.max_records < 1 || m.max_records > 65536) {
+    set_err("fmr_enable_loudness: max_records %d is outside 1 .. 65536 (0 = 1024)", m.max_records);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!c) { set_err("fmr_enable_loudness: chain is null"); return FMR_ERR_BAD_ARG; }
+  if (c->mode != FMR_MODE_FM) {
+    set_err("fmr_enable_loudness: the audio monitor reads the audio of an FM chain (mode FMR_MODE_FM); mode %d %s", c->mode,
+            c->mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no audio" : "is not covered");
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (c->ld) { set_err("fmr_enable_loudness: the audio monitor of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
+  if (c->call_seq != 0) {
+    set_err("fmr_enable_loudness: the chain has already taken samples (the audio monitor counts from the chain's first audio sample)");
+    return FMR_ERR_BAD_ARG;
+  }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    return c->ld_init(m);
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_loudness_read(fmr_chain *c, int stream, fmr_loudness_record *recs, int cap, fmr_loudness_info *info, size_t info_size) {
+  if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_loudness_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
+  if (!c->ld) { set_err("fmr_loudness_read: the chain has no audio monitor (fmr_enable_loudness)"); return FMR_ERR_BAD_ARG; }
+  if (cap > 0 && !recs) { set_err("fmr_loudness_read: recs is null"); return FMR_ERR_BAD_ARG; }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    const unsigned long long L = (unsigned long long)c->ld_cfg.max_records;
+    const unsigned long long done = (unsigned long long)(c->ld_n / (long long)c->ld_cfg.step_samples);
+    c->ld_catch_up(stream);
+    const unsigned long long first = c->ld_read[stream], ready = done - first;
+    const size_t n = (size_t)std::min<unsigned long long>(ready, (unsigned long long)cap);
+    for (size_t k = 0; k < n;) {       // the ring slots first % L .. in at most two contiguous pieces
+      const size_t slot = (size_t)((first + k) % L), m = std::min(n - k, (size_t)L - slot), at = (size_t)stream * L + slot;
+      HIPCHK(hipMemcpy(recs + k, c->d_ld_ring.p + at, m * sizeof(fmr_loudness_record), hipMemcpyDeviceToHost));
+      k += m;
+    }
+    c->ld_read[stream] = first + n;
+    if (info) {
+      fmr_loudness_info full{};
+      full.struct_size = (unsigned)sizeof full;
+      full.channels = c->stereo ? 2 : 1;
+      full.records_complete = done;
+      full.records_dropped = c->ld_dropped[stream];
+      full.first_unread = c->ld_read[stream];
+      full.records_ready = done - c->ld_read[stream];
+      full.step_samples = c->ld_cfg.step_samples;
+      full.max_records = c->ld_cfg.max_records;
+      const size_t isz = info_size ? info_size : sizeof full;
+      memcpy(info, &full, isz < sizeof full ? isz : sizeof full);
+    }
+    return cap == 0 ? (int)std::min<unsigned long long>(ready, (unsigned long long)INT_MAX) : (int)n;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_loudness_derive(const fmr_loudness_record *recs, int n, double silence_dbfs, fmr_loudness_levels *out, size_t out_size) {
+  if (!recs || !out || n < 1) { set_err("fmr_loudness_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
+  if (std::isnan(silence_dbfs)) { set_err("fmr_loudness_derive: silence_dbfs is not a number"); return FMR_ERR_BAD_ARG; }
+  for (int i = 0; i < n; i++)
+    if (recs[i].step_samples == 0 || recs[i].channels < 1 || recs[i].channels > 2) {
+      set_err("fmr_loudness_derive: record %d has step_samples %u and channels %u (not a record of fmr_loudness_read)", i,
+              recs[i].step_samples, recs[i].channels);
+      return FMR_ERR_BAD_ARG;
+    }
+  auto lufs = [](double z) { return z > 0.0 ? -0.691 + 10.0 * std::log10(z) : -INFINITY; };
+  auto db20 = [](double v) { return v > 0.0 ? 20.0 * std::log10(v) : -INFINITY; };
+  fmr_loudness_levels full{};
+  full.struct_size = (unsigned)sizeof full;
+  full.momentary_lufs = full.momentary_max_lufs = full.short_term_lufs = full.short_term_max_lufs = -INFINITY;
+  std::vector<double> zm;            // the mean squares of all momentary windows
+  double sl = 0.0, sr = 0.0, slr = 0.0, sp = 0.0, tp = 0.0;
+  unsigned long long run = 0;        // silent records that end at i
+  const double thr = std::pow(10.0, silence_dbfs / 10.0);
+  int consec = 0;                    // records with consecutive index that end at i
+  for (int i = 0; i < n; i++) {
+    const fmr_loudness_record &r = recs[i];
+    const bool follows = i > 0 && r.index == recs[i - 1].index + 1;
+    consec = follows ? consec + 1 : 1;
+    if (!follows) run = 0;
+    const double Q = (double)r.step_samples;
+    sl += r.sumsq[0]; sr += r.sumsq[1]; slr += r.sum_lr;
+    sp = std::max(sp, std::max(r.sample_peak[0], r.sample_peak[1]));
+    tp = std::max(tp, std::max(r.true_peak[0], r.true_peak[1]));
+    full.n_nonfinite += r.n_nonfinite;
+    auto window = [&](int w) {       // the K-weighted mean square of the records i - w + 1 .. i, channels added
+      double z = 0.0;
+      for (int j = i - w + 1; j <= i; j++) z += recs[j].kw_sumsq[0] + recs[j].kw_sumsq[1];
+      return z / ((double)w * Q);
+    };
+    if (consec >= 4) {
+      const double z = window(4);
+      zm.push_back(z);
+      full.momentary_lufs = lufs(z);
+      full.momentary_max_lufs = std::max(full.momentary_max_lufs, full.momentary_lufs);
+    }
+    if (consec >= 30) {
+      full.short_term_lufs = lufs(window(30));
+      full.short_term_max_lufs = std::max(full.short_term_max_lufs, full.short_term_lufs);
+    }
+    run = (r.sumsq[0] + r.sumsq[1]) / ((double)r.channels * Q) < thr ? run + 1 : 0;
+    full.longest_silence_blocks = std::max<uint64_t>(full.longest_silence_blocks, run);
+  }
+  full.trailing_silence_blocks = run;
+  // BS.1770-4 gating over the momentary windows: -70 LUFS absolute, then 10 LU under the mean of what passed
+  full.momentary_windows = zm.size();
+  full.integrated_lufs = -INFINITY;
+  double za = 0.0;
+  size_t na = 0;
+  for (double z : zm) if (lufs(z) > -70.0) { za += z; na++; }
+  if (na > 0) {
+    const double gate = lufs(za / (double)na) - 10.0;
+    double zg = 0.0;
+    size_t ng = 0;
+    for (double z : zm) if (lufs(z) > -70.0 && lufs(z) > gate) { zg += z; ng++; }
+    full.gated_windows = ng;
+    if (ng > 0) full.integrated_lufs = lufs(zg / (double)ng);
+  }
+  full.sample_peak_dbfs = db20(sp);
+  full.true_peak_dbtp = db20(tp);
+  const double den = sl * sr;
+  full.correlation = den > 0.0 ? slr / std::sqrt(den) : 0.0;
+  const double side = sl + sr - 2.0 * slr, mid = sl + sr + 2.0 * slr;
+  full.side_to_mid_db = side <= 0.0 && mid <= 0.0 ? 0.0 : side <= 0.0 ? -INFINITY : mid <= 0.0 ? INFINITY : 10.0 * std::log10(side / mid);
   const size_t osz = out_size ? out_size : sizeof full;
   memcpy(out, &full, osz < sizeof full ? osz : sizeof full);
   return FMR_OK;

@@ -123,8 +123,31 @@ inline std::vector<ModulationRecord> monitor_records(fmr_chain *c, int stream) {
   }
   return out;
 }
+// audio monitor (fmr_enable_loudness / fmr_loudness_read / fmr_loudness_derive): the drained sub-block records in
+// ascending order and the levels derived from them together
+struct LoudnessReport {
+  std::vector<fmr_loudness_record> records;
+  fmr_loudness_info info{};
+  fmr_loudness_levels levels{};      // (of `records`; all zero when there are none)
+};
+inline void loudness(fmr_chain *c, const fmr_loudness_config &m) {
+  check(fmr_enable_loudness(c, &m, sizeof m), "fmr_enable_loudness");
+}
+inline LoudnessReport loudness_report(fmr_chain *c, int stream, double silence_dbfs) {
+  LoudnessReport out;
+  const int ready = fmr_loudness_read(c, stream, nullptr, 0, &out.info, sizeof out.info);
+  if (ready < 0) check(ready, "fmr_loudness_read");
+  if (ready == 0) return out;
+  out.records.resize((size_t)ready);
+  const int n = fmr_loudness_read(c, stream, out.records.data(), ready, &out.info, sizeof out.info);
+  if (n < 0) check(n, "fmr_loudness_read");
+  out.records.resize((size_t)n);
+  if (n > 0) check(fmr_loudness_derive(out.records.data(), n, silence_dbfs, &out.levels, sizeof out.levels), "fmr_loudness_derive");
+  return out;
+}
 }  // namespace fmr_detail
 using ModulationRecord = fmr_detail::ModulationRecord;
+using LoudnessReport = fmr_detail::LoudnessReport;
 
 // FilterParameters (include/FilterParameters.h:31-49): tables served by the library.
 struct FilterParameters {
@@ -260,6 +283,7 @@ public:
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg, m_rds);
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
+    if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
   }
 
   // RDS (no counterpart in the reference; fmr_create_rds): re-creates the chain with the RDS decoder, before the first
@@ -270,6 +294,7 @@ public:
     fmr_destroy(m_chain);
     m_chain = fmr_detail::make(m_cfg, true);
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
+    if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
   }
   // error correction of the RDS blocks (fmr_set_rds_correction: FMR_RDS_FEC_OFF / _BURST / _SOFT; 0 = the defaults); at
   // any time after enable_rds(), from the decoder's next block boundary on.  enable_rds() starts with it off.
@@ -292,6 +317,18 @@ public:
   }
   std::vector<ModulationRecord> read_modulation_records() { return fmr_detail::monitor_records(m_chain, 0); }
 
+  // Audio monitor (the level meter main.cpp prints beside the IF level, on the device; fmr_enable_loudness): records of
+  // step_samples audio samples (0 = 4800) with K-weighted power, sample and true peak, L/R sums; before the first
+  // process(), once.  read_loudness() drains the complete ones and derives loudness, peaks, correlation and silence.
+  void enable_loudness(uint32_t step_samples = 0, int max_records = 0) {
+    if (m_started) fmr_detail::fail("FmDecoder::enable_loudness: after the first process()");
+    m_ld_cfg = fmr_loudness_config{};
+    m_ld_cfg.struct_size = sizeof m_ld_cfg; m_ld_cfg.step_samples = step_samples; m_ld_cfg.max_records = max_records;
+    fmr_detail::loudness(m_chain, m_ld_cfg);
+    m_ld = true;
+  }
+  LoudnessReport read_loudness(double silence_dbfs = -60.0) { return fmr_detail::loudness_report(m_chain, 0, silence_dbfs); }
+
   // Latency for throughput: hold back `blocks` - 1 calls and decode `blocks` blocks in ONE batched call.  process()
   // then returns an empty vector ("nothing yet": the contract of FmDecode.cpp:89-92,185-188, which main.cpp:981-984
   // already handles) until the batch is full, and the audio of all its blocks at once.  One 65536-sample block per
@@ -312,6 +349,7 @@ public:
       m_cfg.max_blocks = (int)blocks;
       m_chain = fmr_detail::make(m_cfg, m_rds);
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
+    if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
       m_capacity = blocks;
     }
     m_batch = blocks;
@@ -406,6 +444,8 @@ private:
   fmr_config m_cfg{};
   bool m_mon = false;
   fmr_monitor_config m_mon_cfg{};
+  bool m_ld = false;
+  fmr_loudness_config m_ld_cfg{};
   fmr_chain *m_chain = nullptr;
   bool m_rds = false;
   fmr_rds::Station m_station;
@@ -553,6 +593,7 @@ public:
     m_cfg.channel_offset_hz = m_offsets.data();
     m_chain = fmr_detail::make(m_cfg, true);
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
+    if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     m_stations.assign(m_offsets.size(), fmr_rds::Station());
   }
   // error correction of every channel's RDS blocks (fmr_set_rds_correction), at any time after enable_rds()
@@ -577,6 +618,18 @@ public:
   std::vector<ModulationRecord> read_modulation_records(size_t ch) {
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
     return fmr_detail::monitor_records(m_chain, (int)ch);
+  }
+  // Audio monitor of every channel (fmr_enable_loudness), before the first process(), once; FM banks only.
+  // read_loudness(ch) drains channel ch's complete records and derives their levels.
+  void enable_loudness(uint32_t step_samples = 0, int max_records = 0) {
+    m_ld_cfg = fmr_loudness_config{};
+    m_ld_cfg.struct_size = sizeof m_ld_cfg; m_ld_cfg.step_samples = step_samples; m_ld_cfg.max_records = max_records;
+    fmr_detail::loudness(m_chain, m_ld_cfg);
+    m_ld = true;
+  }
+  LoudnessReport read_loudness(size_t ch, double silence_dbfs = -60.0) {
+    if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
+    return fmr_detail::loudness_report(m_chain, (int)ch, silence_dbfs);
   }
 
   // audio[k] = what channel k produced from this capture block (empty = "nothing yet"); blocks longer than the chain's
@@ -629,6 +682,8 @@ private:
   std::vector<fmr_rds::Station> m_stations;
   bool m_mon = false;
   fmr_monitor_config m_mon_cfg{};
+  bool m_ld = false;
+  fmr_loudness_config m_ld_cfg{};
   fmr_chain *m_chain = nullptr;
 };
 

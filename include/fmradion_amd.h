@@ -615,6 +615,91 @@ int fmr_monitor_read(fmr_chain *c, int stream, fmr_monitor_record *recs, uint32_
  * (n_finite = 0: mean, var and the peak deviation are 0). */
 int fmr_monitor_derive(const fmr_monitor_record *recs, const double *psd, int n, fmr_monitor_levels *out, size_t out_size);
 
+/* --- Audio monitor: a level meter on the decoded audio, the other half of a broadcast monitor.
+ * An FM chain with it enabled measures the finished audio of every stream / bank channel where the output mux wrote it
+ * on the device: programme loudness (ITU-R BS.1770-4 / EBU R 128), sample and true peak, stereo correlation, silence.
+ * The audio, fmr_status, PPS events, RDS groups and modulation-monitor records of the chain are what they are without
+ * it: the stage only reads the audio.  The AM family (and NBFM) is out of scope: FMR_MODE_FM chains only.
+ * Indices are absolute audio sample indices per stream, counted from the chain's first audio sample; nothing depends
+ * on the cut into blocks and calls.  ch = 2 for a stereo chain (its audio is interleaved L/R doubles, also when the
+ * station is mono and L = R), ch = 1 for stereo = 0.  A non-finite audio sample is counted in n_nonfinite (once per
+ * channel value) and enters everything below as 0.0.
+ * K-weighting (BS.1770-4, 48 kHz), two biquads in the form w = x - a1 w1 - a2 w2; y = b0 w + b1 w1 + b2 w2:
+ *   stage 1: b = 1.53512485958697, -2.69169618940638, 1.19839281085285; a = 1, -1.69065929318241, 0.73248077421585
+ *   stage 2: b = 1, -2, 1;                                              a = 1, -1.99004745483398, 0.99007225036621
+ * fp64, unfused, evaluated left to right, state zero at the chain's first sample and carried on the device across calls.
+ * (A 0 dBFS 997 Hz sine in one channel reads -3.01 LKFS; the coefficients are used as they are at every output rate.)
+ * Sub-block q covers the samples [q Q, (q + 1) Q), Q = step_samples.  Its record holds, per channel c:
+ *   kw_sumsq[c]    sum of the squared K-weighted samples;   sumsq[c]  sum x^2;   sum_lr  sum L R (0 when ch = 1);
+ *   sample_peak[c] max |x|, the sample's own value;
+ *   true_peak[c]   max over n in the sub-block and p = 0 .. 3 of |y[n, p]|, a 4x interpolator with an identity phase:
+ *                  y[n, p] = sum_{k = -5 .. 6} x[n - 6 + k] g_p[k],  g_p[k] = sinc(k - p/4) (0.5 + 0.5 cos(pi (k - p/4) / 6)),
+ *                  summed with k ascending, samples before index 0 being 0, and y[n, 0] = x[n - 6] itself.  It is a
+ *                  causal 12-tap polyphase filter reaching 11 samples back: a sub-block needs no future sample.  (A unit
+ *                  sine at fs/4 sampled at 45 degrees has sample peak 0.7071 and reads 0.9962.)
+ * Channel-1 fields are 0 when ch = 1.
+ * Completion: record q is complete in the call that delivers the sample (q + 1) Q - 1.
+ * Ring: max_records = L records per stream.  When L unread records exist and another completes, the oldest is
+ * overwritten and counted in records_dropped; processing never fails because of it.
+ * Reproducibility: index, first_sample, n_nonfinite, channels, step_samples, sample_peak and true_peak are bit-identical
+ * for any cut of the input into calls.  The sums are fp64 in a fixed order without float atomics (the same cut gives the
+ * same bits; another cut differs at fp64 rounding: ~1e-15 relative for sumsq and sum_lr, and for kw_sumsq ~1e-13 of the
+ * largest sub-block nearby, because the recurrence is restarted from chunk states). */
+typedef struct {
+  unsigned struct_size;       /* sizeof(fmr_loudness_config) as the caller knows it (0: cfg_size); a larger size is refused */
+  uint32_t step_samples;      /* Q: a multiple of 16 in 48 .. 2^20; 0 = 4800 (100 ms at 48 kHz) */
+  int max_records;            /* L: 1 .. 65536; 0 = 1024 */
+} fmr_loudness_config;
+typedef struct {
+  uint64_t index, first_sample;   /* q and q Q */
+  uint32_t n_nonfinite, channels; /* ch */
+  uint32_t step_samples, reserved;/* Q, so that a record can be derived from by itself */
+  double kw_sumsq[2], sumsq[2], sum_lr, sample_peak[2], true_peak[2];
+} fmr_loudness_record;
+typedef struct {
+  unsigned struct_size;
+  int channels;                   /* ch */
+  uint64_t records_complete;      /* since create (of every stream: they run in step) */
+  uint64_t records_dropped;       /* of this stream: overwritten unread */
+  uint64_t first_unread;          /* index of the oldest unread record after this call */
+  uint64_t records_ready;         /* complete records still unread after this call */
+  uint32_t step_samples;          /* Q and L as enabled (defaults filled in) */
+  int max_records;
+} fmr_loudness_info;
+typedef struct {
+  unsigned struct_size;
+  int reserved;
+  double momentary_lufs, momentary_max_lufs;      /* the last window that exists and the maximum; -INFINITY when none */
+  double short_term_lufs, short_term_max_lufs;
+  double integrated_lufs;                         /* -INFINITY when no window passes the absolute gate */
+  double sample_peak_dbfs, true_peak_dbtp;        /* 20 log10 of the largest peak of all records; -INFINITY for 0 */
+  double correlation;                             /* sum LR / sqrt(sum L^2 sum R^2); 0 when the denominator is 0 */
+  double side_to_mid_db;                          /* +-INFINITY when mid / side is 0, 0 when both are */
+  uint64_t longest_silence_blocks, trailing_silence_blocks;
+  uint64_t n_nonfinite;                           /* pooled */
+  uint64_t momentary_windows, gated_windows;      /* windows that exist; windows that pass both gates */
+} fmr_loudness_levels;
+/* Checks the fields first (FMR_ERR_BAD_ARG, fmr_last_error names the field; also a size larger than this library's
+ * struct), then the chain: NULL is FMR_ERR_BAD_ARG; any FMR_MODE_FM chain is accepted (fmr_create and fmr_create_rds,
+ * banks, pipelined or in_order); every other mode and front-end-only chains are FMR_ERR_UNSUPPORTED.  Allowed once,
+ * before the chain's first sample: a second call, or one after any processing call, is FMR_ERR_BAD_ARG.  A chain that
+ * never calls it allocates nothing for the audio monitor and runs none of its kernels. */
+int fmr_enable_loudness(fmr_chain *c, const fmr_loudness_config *cfg, size_t cfg_size);
+/* Synchronises like the other getters, then drains up to cap complete records of `stream`, oldest first, and returns how
+ * many.  cap = 0 returns the number waiting and drains nothing.  info (may be NULL) takes info_size bytes (0 = this
+ * header's size).  FMR_ERR_BAD_ARG on a chain without the audio monitor. */
+int fmr_loudness_read(fmr_chain *c, int stream, fmr_loudness_record *recs, int cap, fmr_loudness_info *info, size_t info_size);
+/* Host only, in double, no device.  n records in ascending order as read.  Windows are built only over records with
+ * consecutive index: a gap left by dropped records breaks windows and silence runs.  With Q = step_samples and
+ *   Z_i = sum_c sum_{j = i - 3 .. i} kw_sumsq_c[j] / (4 Q),  momentary = -0.691 + 10 log10 Z_i  (-INFINITY for Z = 0),
+ * short-term the same over 30 sub-blocks.  integrated_lufs gates all momentary windows as BS.1770-4 does: the absolute
+ * gate -70, then the relative gate 10 LU under the loudness of the mean Z of the windows that passed the absolute one;
+ * the loudness of the mean Z of what passes both.  correlation and side_to_mid_db = 10 log10((sum L^2 + sum R^2 -
+ * 2 sum LR) / (sum L^2 + sum R^2 + 2 sum LR)) pool all records.  A sub-block is silent when (sumsq_0 + sumsq_1) / (ch Q) <
+ * 10^(silence_dbfs / 10); longest_silence_blocks is the longest run of consecutive silent sub-blocks,
+ * trailing_silence_blocks the run that ends at the last record.  Loudness range (EBU 3342) is not computed. */
+int fmr_loudness_derive(const fmr_loudness_record *recs, int n, double silence_dbfs, fmr_loudness_levels *out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif
