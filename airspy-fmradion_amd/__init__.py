@@ -50,6 +50,7 @@ EXPORTS = [
     "fmr_spectrum_create_waterfall", "fmr_spectrum_read_waterfall",
     "fmr_enable_monitor", "fmr_monitor_read", "fmr_monitor_derive",
     "fmr_enable_loudness", "fmr_loudness_read", "fmr_loudness_derive",
+    "fmr_enable_rf_monitor", "fmr_rf_monitor_read", "fmr_rf_monitor_derive",
 ]
 # FMR_WINDOW_* (include/fmradion_amd.h): windows of the band spectrum
 WINDOW_HANN, WINDOW_RECT, WINDOW_BLACKMAN_HARRIS = 0, 1, 2
@@ -71,6 +72,11 @@ LOUDNESS_RECORD = np.dtype([("index", np.uint64), ("first_sample", np.uint64), (
                             ("channels", np.uint32), ("step_samples", np.uint32), ("reserved", np.uint32),
                             ("kw_sumsq", np.float64, 2), ("sumsq", np.float64, 2), ("sum_lr", np.float64),
                             ("sample_peak", np.float64, 2), ("true_peak", np.float64, 2)])
+# fmr_rf_monitor_record as a numpy structured type (56 bytes)
+RF_MONITOR_RECORD = np.dtype([("index", np.uint64), ("first_sample", np.uint64), ("n_finite", np.uint32),
+                              ("n_nonfinite", np.uint32), ("segments", np.uint32), ("segments_skipped", np.uint32),
+                              ("p_min", np.float32), ("p_max", np.float32), ("m2", np.float64), ("m4", np.float64)])
+RF_HIST_BINS, RF_PSD_BINS = 384, 513
 
 
 class FmrError(RuntimeError):
@@ -156,6 +162,24 @@ class MonitorLevels(C.Structure):
                 ("peak_deviation_hz", C.c_double), ("rms", C.c_double), ("mpx_power_dbr", C.c_double),
                 ("pilot_deviation_hz", C.c_double), ("rds_deviation_hz", C.c_double), ("hf_noise_density", C.c_double),
                 ("n_finite", C.c_uint64), ("segments", C.c_uint64)]
+
+
+class RfMonitorConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("interval_samples", C.c_uint32), ("max_records", C.c_int)]
+
+
+class RfMonitorInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("hist_bins", C.c_int), ("psd_bins", C.c_int),
+                ("records_complete", C.c_uint64), ("records_dropped", C.c_uint64), ("first_unread", C.c_uint64),
+                ("records_ready", C.c_uint64), ("interval_samples", C.c_uint32), ("max_records", C.c_int),
+                ("bin_hz", C.c_double)]
+
+
+class RfMonitorLevels(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("reserved", C.c_int), ("level_dbfs", C.c_double), ("carrier_dbfs", C.c_double),
+                ("noise_dbfs", C.c_double), ("cn_db", C.c_double), ("am_rms", C.c_double), ("am_audio_db", C.c_double),
+                ("am_pilot_db", C.c_double), ("am_floor_dbc_hz", C.c_double), ("p10_dbfs", C.c_double),
+                ("p50_dbfs", C.c_double), ("p90_dbfs", C.c_double), ("n_finite", C.c_uint64), ("segments", C.c_uint64)]
 
 
 class LoudnessConfig(C.Structure):
@@ -287,6 +311,12 @@ def lib(ab=False):
     L.fmr_loudness_read.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(LoudnessInfo), C.c_size_t]
     L.fmr_loudness_derive.restype = C.c_int
     L.fmr_loudness_derive.argtypes = [vp, C.c_int, C.c_double, C.POINTER(LoudnessLevels), C.c_size_t]
+    L.fmr_enable_rf_monitor.restype = C.c_int
+    L.fmr_enable_rf_monitor.argtypes = [vp, C.POINTER(RfMonitorConfig), C.c_size_t]
+    L.fmr_rf_monitor_read.restype = C.c_int
+    L.fmr_rf_monitor_read.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.POINTER(RfMonitorInfo), C.c_size_t]
+    L.fmr_rf_monitor_derive.restype = C.c_int
+    L.fmr_rf_monitor_derive.argtypes = [vp, vp, vp, C.c_int, C.POINTER(RfMonitorLevels), C.c_size_t]
     _libs[ab] = L
     return L
 
@@ -373,6 +403,23 @@ def loudness_levels(records, silence_dbfs=-60.0):
     if rc != OK:
         raise FmrError(f"fmr_loudness_derive failed ({rc}): {L.fmr_last_error().decode()}")
     return {k: getattr(out, k) for k, _ in LoudnessLevels._fields_ if k not in ("struct_size", "reserved")}
+
+
+def rf_levels(records, hist, psd):
+    """fmr_rf_monitor_derive (host only): level, C/N, envelope AM and fade percentiles of the pooled records (an
+    RF_MONITOR_RECORD array with hist [n, 384] and psd [n, 513], as Chain.rf_monitor_records returns them), as a dict of
+    fmr_rf_monitor_levels."""
+    records = np.ascontiguousarray(records, dtype=RF_MONITOR_RECORD)
+    hist = np.ascontiguousarray(hist, dtype=np.uint32)
+    psd = np.ascontiguousarray(psd, dtype=np.float64)
+    assert hist.shape == (len(records), RF_HIST_BINS) and psd.shape == (len(records), RF_PSD_BINS), (hist.shape, psd.shape)
+    out = RfMonitorLevels()
+    L = lib()
+    rc = L.fmr_rf_monitor_derive(records.ctypes.data, hist.ctypes.data, psd.ctypes.data, len(records), C.byref(out),
+                                 C.sizeof(RfMonitorLevels))
+    if rc != OK:
+        raise FmrError(f"fmr_rf_monitor_derive failed ({rc}): {L.fmr_last_error().decode()}")
+    return {k: getattr(out, k) for k, _ in RfMonitorLevels._fields_ if k not in ("struct_size", "reserved")}
 
 
 def monitor_levels(records, psd):
@@ -671,6 +718,28 @@ class Chain:
         if cap > 0:
             n = self._chk(L.fmr_loudness_read(self.h, int(stream), recs.ctypes.data, cap, C.byref(info), C.sizeof(LoudnessInfo)))
         return recs[:n], {k: getattr(info, k) for k, _ in LoudnessInfo._fields_}
+
+    def enable_rf_monitor(self, interval_samples=0, max_records=0):
+        """fmr_enable_rf_monitor: the RF monitor of every stream / channel (FM chains, once, before the first call);
+        0 = the defaults (records of 38400 IF samples = 100 ms, 64 records kept)."""
+        cfg = RfMonitorConfig(C.sizeof(RfMonitorConfig), int(interval_samples), int(max_records))
+        self._chk(self._L.fmr_enable_rf_monitor(self.h, C.byref(cfg), C.sizeof(RfMonitorConfig)))
+
+    def rf_monitor_records(self, stream=0, cap=None):
+        """fmr_rf_monitor_read: the oldest unread complete records of `stream` (at most cap; None: all that wait) as
+        (records RF_MONITOR_RECORD [n], hist uint32 [n, 384], psd float64 [n, 513], info dict).  Reading drains them."""
+        info = RfMonitorInfo()
+        L = self._L
+        waiting = self._chk(L.fmr_rf_monitor_read(self.h, int(stream), None, None, None, 0, C.byref(info), C.sizeof(RfMonitorInfo)))
+        cap = int(waiting if cap is None else cap)
+        recs = np.zeros(cap, dtype=RF_MONITOR_RECORD)
+        hist = np.zeros((cap, RF_HIST_BINS), dtype=np.uint32)
+        psd = np.zeros((cap, RF_PSD_BINS), dtype=np.float64)
+        n = 0
+        if cap > 0:
+            n = self._chk(L.fmr_rf_monitor_read(self.h, int(stream), recs.ctypes.data, hist.ctypes.data, psd.ctypes.data, cap,
+                                                C.byref(info), C.sizeof(RfMonitorInfo)))
+        return recs[:n], hist[:n], psd[:n], {k: getattr(info, k) for k, _ in RfMonitorInfo._fields_}
 
     def pps_events(self, stream=0):
         ev = (PpsEvent * 64)()

@@ -35,6 +35,7 @@
 #include "kernels_spectrum.hpp"
 #include "kernels_monitor.hpp"
 #include "kernels_loudness.hpp"
+#include "kernels_rfmon.hpp"
 #include "../host/fmradion_rds.hpp"
 
 namespace {
@@ -352,6 +353,25 @@ struct fmr_chain {
   // ---- audio monitor (fmr_enable_loudness; kernels_loudness.hpp).  A reader of the call's finished
   // audio behind the output mux, on the tail's stream: it counts in absolute audio samples (ld_n) and keeps its own
   // carries (the K-weighting state, the true-peak history, the open record).  Nothing of it exists unless it is enabled.
+  // ---- RF monitor (fmr_enable_rf_monitor; kernels_rfmon.hpp).  A second reader of the call's IF
+  // ring slot (the decoder's input, or |x|^2 behind a discriminator epilogue) at the head of the audio tail, beside the RDS
+  // stage and the modulation monitor, whose partition, launches and ring it shares.  Nothing of it exists on a chain that
+  // never enabled it.
+  bool rfm = false;
+  fmr_rf_monitor_config rfm_cfg{};           // the defaults filled in
+  int rfm_spr = 0, rfm_sub_n = 0, rfm_sb = 0, rfm_rmax = 0;
+  int rfm_par = 0;
+  double rfm_sumw2 = 0.0;
+  long long rfm_n = 0, rfm_next_seg = 0;     // IF samples seen, segments processed
+  DevBuf<float> d_rfm_win, d_rfm_carry;
+  DevBuf<float2> d_rfm_tw;
+  DevBuf<double> d_rfm_ppsd, d_rfm_open_psd, d_rfm_ring_psd;
+  DevBuf<unsigned> d_rfm_phist, d_rfm_open_hist, d_rfm_ring_hist;
+  DevBuf<MonRec> d_rfm_prec, d_rfm_open_rec, d_rfm_ring_rec;
+  std::vector<unsigned long long> rfm_read, rfm_dropped;
+  int rfm_init(const fmr_rf_monitor_config &m);
+  int rfm_stage(const float2 *slot, bool is_nrm, long long N, hipStream_t st);
+  void rfm_catch_up(int s);
   bool ld = false;
   fmr_loudness_config ld_cfg{};              // the defaults filled in
   int ld_cps = 0, ld_rmax = 0, ld_par = 0;   // chunks per sub-block, runs per stream and launch, current copy of the open records
@@ -474,6 +494,9 @@ struct fmr_chain {
     d_mon_prec.release(); d_mon_open_rec.release(); d_mon_ring_rec.release();
     d_ld_pw.release(); d_ld_taps.release(); d_ld_G.release(); d_ld_start.release(); d_ld_pkw.release(); d_ld_state.release();
     d_ld_hist.release(); d_ld_part.release(); d_ld_open.release(); d_ld_ring.release();
+    d_rfm_win.release(); d_rfm_carry.release(); d_rfm_tw.release(); d_rfm_ppsd.release(); d_rfm_open_psd.release();
+    d_rfm_ring_psd.release(); d_rfm_phist.release(); d_rfm_open_hist.release(); d_rfm_ring_hist.release();
+    d_rfm_prec.release(); d_rfm_open_rec.release(); d_rfm_ring_rec.release();
     if (h_rds_slots) (void)hipHostFree(h_rds_slots);
     if (h_rds_mark) (void)hipHostFree(h_rds_mark);
     if (h_tab_all) (void)hipHostFree(h_tab_all);
@@ -677,6 +700,8 @@ struct fmr_chain {
   // what the audio tail of one call needs, by value: in the pipelined chain the tail stage is enqueued a call later
   struct TailCtx {
     fm_mpx_t *base = nullptr;
+    const float2 *ifbuf = nullptr;     // the call's IF ring slot (the RF monitor reads it) ...
+    bool if_nrm = false;               // ... holding |x|^2 (float, from the slot's first word) instead of the IF samples
     double *raw = nullptr;
     int *stereo_blk = nullptr;
     long long N_if{}, N_au{}, a_top0{}, amA_prev{}, akB_prev{}, astride{};
@@ -2508,6 +2533,7 @@ int fmr_chain::run_fm(CallCtx &k) {
   bool fin_on_side = false, fin_covers_all = false;
   // ---------------------------------------------------- audio resampler + tail
   TailCtx t{};
+  t.ifbuf = ifbuf; t.if_nrm = k.nrm != nullptr;
   t.base = k.base; t.raw = k.raw; t.stereo_blk = k.stereo_blk; t.N_if = N_if; t.N_au = N_au; t.nb = nb; t.bt = bt;
   t.d_aud = d_aud; t.astride = (long long)astride; t.amA_prev = amA_prev; t.akB_prev = akB_prev;
   t.nch = stereo ? 2 : 1;
@@ -2657,6 +2683,7 @@ void fmr_chain::tail_channels(const TailCtx &t, hipStream_t st, int ch_base, int
 int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
   if (rds) if (int rc = rds_stage(t.base, t.N_if, ts)) return rc;
   if (mon) if (int rc = mon_stage(t.base, t.N_if, ts)) return rc;
+  if (rfm) if (int rc = rfm_stage(t.ifbuf, t.if_nrm, t.N_if, ts)) return rc;
   const int nch = t.nch, dc_nc = t.dc_nc;
   const long long N_au = t.N_au;
   if (t.mono_enqueued) tail_channels(t, ts, 1, 1);
@@ -2835,6 +2862,23 @@ int fmr_chain::mon_init(const fmr_monitor_config &m) {
   return FMR_OK;
 }
 
+// The next launch of a monitor's stage (modulation and RF monitor): the segments [j, a.a1) of the call's [j, j_hi) that
+// fit into rmax runs per stream, the runs and the records they touch.  j >= j_hi: no segment is left (runs = 0, one block
+// per stream for the carry).
+static void mon_plan_launch(MonArgs &a, long long j, long long j_hi, int rmax, int &runs, int &nrec) {
+  runs = 0; nrec = 1;
+  a.a0 = a.a1 = j; a.g0 = 0;
+  if (j >= j_hi) return;
+  const long long l = j / a.spr;
+  a.g0 = l * a.sb + (j - l * a.spr) / a.sub;
+  long long lo, hi;
+  mon_sub(a.spr, a.sub, a.sb, a.g0 + rmax - 1, lo, hi);
+  a.a1 = std::min(j_hi, hi);
+  const long long l_end = (a.a1 - 1) / a.spr;
+  runs = (int)(l_end * a.sb + (a.a1 - 1 - l_end * a.spr) / a.sub - a.g0 + 1);
+  nrec = (int)(l_end - l + 1);
+}
+
 // one call's MPX (N samples per stream from the base slot) through the monitor, on stream st: the segments whose last
 // sample the call delivers, in launches of at most mon_rmax runs per stream, then the carry
 int fmr_chain::mon_stage(const fm_mpx_t *base, long long N, hipStream_t st) {
@@ -2849,22 +2893,13 @@ int fmr_chain::mon_stage(const fm_mpx_t *base, long long N, hipStream_t st) {
   const long long M = (long long)mon_cfg.interval_samples;
   long long j = mon_next_seg;
   do {
-    int runs = 0, nrec = 1;
-    a.a0 = a.a1 = j; a.g0 = 0;
-    if (j < j_hi) {
-      const long long l = j / mon_spr;
-      a.g0 = l * mon_sb + (j - l * mon_spr) / mon_sub_n;
-      long long lo, hi;
-      mon_sub(mon_spr, mon_sub_n, mon_sb, a.g0 + mon_rmax - 1, lo, hi);
-      a.a1 = std::min(j_hi, hi);
-      const long long l_end = (a.a1 - 1) / mon_spr;
-      runs = (int)(l_end * mon_sb + (a.a1 - 1 - l_end * mon_spr) / mon_sub_n - a.g0 + 1);
-      nrec = (int)(l_end - l + 1);
+    int runs, nrec;
+    mon_plan_launch(a, j, j_hi, mon_rmax, runs, nrec);
+    if (runs > 0)
       timed_on(st, "mon_seg", [&] {
         hipLaunchKernelGGL(k_mon_seg, dim3(runs, S), dim3(kMonT), 0, st, base, base_stride, H_b, d_mon_carry.p, a,
                            d_mon_win.p, d_mon_tw.p, mon_rmax, d_mon_ppsd.p, d_mon_phist.p, d_mon_prec.p);
       });
-    }
     j = a.a1;
     timed_on(st, "mon_reduce", [&] {
       hipLaunchKernelGGL(k_mon_reduce, dim3(nrec, S), dim3(kMonT), 0, st, d_mon_ppsd.p, d_mon_phist.p, d_mon_prec.p, runs,
@@ -2885,6 +2920,96 @@ void fmr_chain::mon_catch_up(int s) {
   if (done > L && mon_read[s] < done - L) {
     mon_dropped[s] += done - L - mon_read[s];
     mon_read[s] = done - L;
+  }
+}
+
+// ---- RF monitor (kernels_rfmon.hpp) ----
+int fmr_chain::rfm_init(const fmr_rf_monitor_config &m) {
+  static_assert(sizeof(MonRec) == sizeof(fmr_rf_monitor_record), "MonRec is fmr_rf_monitor_record");
+  static_assert(kRfmBins == FMR_RF_HIST_BINS && kMonPsd == FMR_RF_PSD_BINS, "the header's sizes");
+  rfm_cfg = m;
+  rfm_spr = (int)(m.interval_samples / kMonH);
+  // the modulation monitor's partition: a full call in about 512 runs per stream, sub-blocks of 4 .. 32 segments
+  const size_t max_seg = max_if / kMonH + 2;
+  rfm_sub_n = (int)std::min<size_t>(kMonSubMax, std::max<size_t>(kMonSubMin, (max_seg + 511) / 512));
+  rfm_sb = (rfm_spr + rfm_sub_n - 1) / rfm_sub_n;
+  rfm_rmax = (int)std::min<size_t>(1024, max_seg / rfm_sub_n + 2 * (max_seg / rfm_spr + 2) + 2);
+  std::vector<float> w(kMonN);
+  std::vector<float2> tw(kMonN);
+  rfm_sumw2 = 0.0;
+  for (int i = 0; i < kMonN; i++) {
+    w[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / kMonN));
+    rfm_sumw2 += (double)w[i] * (double)w[i];
+    tw[i] = make_float2((float)std::cos(2.0 * M_PI * i / kMonN), (float)-std::sin(2.0 * M_PI * i / kMonN));
+  }
+  const size_t B = (size_t)kRfmBins, L = (size_t)m.max_records, rows = (size_t)S * rfm_rmax;
+  int rc;
+  if ((rc = upload(d_rfm_win, w.data(), w.size()))) return rc;
+  if ((rc = upload(d_rfm_tw, tw.data(), tw.size()))) return rc;
+  if ((rc = d_rfm_carry.alloc((size_t)S * kMonN))) return rc;
+  if ((rc = d_rfm_ppsd.alloc(rows * kMonPsd))) return rc;
+  if ((rc = d_rfm_phist.alloc(rows * B))) return rc;
+  if ((rc = d_rfm_prec.alloc(rows))) return rc;
+  if ((rc = d_rfm_open_psd.alloc(2 * (size_t)S * kMonPsd))) return rc;
+  if ((rc = d_rfm_open_hist.alloc(2 * (size_t)S * B))) return rc;
+  if ((rc = d_rfm_open_rec.alloc(2 * (size_t)S))) return rc;
+  if ((rc = d_rfm_ring_psd.alloc((size_t)S * L * kMonPsd))) return rc;
+  if ((rc = d_rfm_ring_hist.alloc((size_t)S * L * B))) return rc;
+  if ((rc = d_rfm_ring_rec.alloc((size_t)S * L))) return rc;
+  rfm_read.assign(S, 0);
+  rfm_dropped.assign(S, 0);
+  rfm_n = rfm_next_seg = 0;
+  rfm_par = 0;
+  rfm = true;
+  return FMR_OK;
+}
+
+// one call's decoder input (N samples per stream in the call's IF ring slot: IF samples, or |x|^2 when is_nrm) through
+// the RF monitor, on stream st; the launches of mon_stage
+int fmr_chain::rfm_stage(const float2 *slot, bool is_nrm, long long N, hipStream_t st) {
+  if (N <= 0) return FMR_OK;
+  const long long if_stride = H_if + (long long)max_if;
+  const long long n0 = rfm_n, n1 = n0 + N;
+  const long long j_hi = n1 >= kMonN ? (n1 - kMonN) / kMonH + 1 : 0;
+  MonArgs a{};
+  a.n0 = n0; a.spr = rfm_spr; a.sub = rfm_sub_n; a.sb = rfm_sb; a.bins = kRfmBins;
+  const int L = rfm_cfg.max_records;
+  const long long M = (long long)rfm_cfg.interval_samples;
+  long long j = rfm_next_seg;
+  do {
+    int runs, nrec;
+    mon_plan_launch(a, j, j_hi, rfm_rmax, runs, nrec);
+    if (runs > 0)
+      timed_on(st, "rfm_seg", [&] {
+        auto go = [&](auto kern) {
+          hipLaunchKernelGGL(kern, dim3(runs, S), dim3(kMonT), 0, st, (const void *)slot, if_stride, H_if, d_rfm_carry.p, a,
+                             d_rfm_win.p, d_rfm_tw.p, rfm_rmax, d_rfm_ppsd.p, d_rfm_phist.p, d_rfm_prec.p);
+        };
+        if (is_nrm) go(k_rfm_seg<true>); else go(k_rfm_seg<false>);
+      });
+    j = a.a1;
+    timed_on(st, "rfm_reduce", [&] {
+      auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(nrec, S), dim3(kMonT), 0, st, d_rfm_ppsd.p, d_rfm_phist.p, d_rfm_prec.p, runs, rfm_rmax,
+                           a, L, M, rfm_par, d_rfm_open_psd.p, d_rfm_open_hist.p, d_rfm_open_rec.p, d_rfm_ring_psd.p,
+                           d_rfm_ring_hist.p, d_rfm_ring_rec.p, (const void *)slot, if_stride, H_if, d_rfm_carry.p, n1,
+                           (int)(j >= j_hi));
+      };
+      if (is_nrm) go(k_rfm_reduce<true>); else go(k_rfm_reduce<false>);
+    });
+    if (runs > 0) rfm_par ^= 1;
+  } while (j < j_hi);
+  rfm_next_seg = std::max(rfm_next_seg, j_hi);
+  rfm_n = n1;
+  HIPCHK(hipGetLastError());
+  return FMR_OK;
+}
+
+void fmr_chain::rfm_catch_up(int s) {
+  const unsigned long long done = (unsigned long long)(rfm_next_seg / rfm_spr), L = (unsigned long long)rfm_cfg.max_records;
+  if (done > L && rfm_read[s] < done - L) {
+    rfm_dropped[s] += done - L - rfm_read[s];
+    rfm_read[s] = done - L;
   }
 }
 
@@ -4385,6 +4510,152 @@ int fmr_loudness_derive(const fmr_loudness_record *recs, int n, double silence_d
   full.correlation = den > 0.0 ? slr / std::sqrt(den) : 0.0;
   const double side = sl + sr - 2.0 * slr, mid = sl + sr + 2.0 * slr;
   full.side_to_mid_db = side <= 0.0 && mid <= 0.0 ? 0.0 : side <= 0.0 ? -INFINITY : mid <= 0.0 ? INFINITY : 10.0 * std::log10(side / mid);
+  const size_t osz = out_size ? out_size : sizeof full;
+  memcpy(out, &full, osz < sizeof full ? osz : sizeof full);
+  return FMR_OK;
+}
+
+// ---- RF monitor: C-ABI ----
+int fmr_enable_rf_monitor(fmr_chain *c, const fmr_rf_monitor_config *cfg, size_t cfg_size) {
+  if (!cfg) { set_err("fmr_enable_rf_monitor: cfg is null"); return FMR_ERR_BAD_ARG; }
+  const size_t size = cfg_size ? cfg_size : sizeof(fmr_rf_monitor_config);
+  if (size > sizeof(fmr_rf_monitor_config) || (size >= sizeof(unsigned) && cfg->struct_size > sizeof(fmr_rf_monitor_config))) {
+    set_err("fmr_enable_rf_monitor: struct_size %zu is larger than this library's fmr_rf_monitor_config (%zu): the caller is "
+            "newer than the library", std::max(size, size >= sizeof(unsigned) ? (size_t)cfg->struct_size : (size_t)0),
+            sizeof(fmr_rf_monitor_config));
+    return FMR_ERR_BAD_ARG;
+  }
+  fmr_rf_monitor_config m;
+  memset(&m, 0, sizeof m);
+  memcpy(&m, cfg, size);
+  if (m.interval_samples == 0) m.interval_samples = 38400;
+  if (m.max_records == 0) m.max_records = 64;
+  if (m.interval_samples % kMonH != 0 || m.interval_samples < (uint32_t)kMonH || m.interval_samples > (1u << 30)) {
+    set_err("fmr_enable_rf_monitor: interval_samples %u is not a multiple of 512 in 512 .. 2^30 (0 = 38400)", m.interval_samples);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.max_records < 1 || m.max_records > 4096) {
+    set_err("fmr_enable_rf_monitor: max_records %d is outside 1 .. 4096 (0 = 64)", m.max_records);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!c) { set_err("fmr_enable_rf_monitor: chain is null"); return FMR_ERR_BAD_ARG; }
+  if (c->mode != FMR_MODE_FM) {
+    set_err("fmr_enable_rf_monitor: the RF monitor reads the decoder input of an FM chain (mode FMR_MODE_FM); mode %d %s", c->mode,
+            c->mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no decoder" : "is not measured");
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (c->rfm) { set_err("fmr_enable_rf_monitor: the RF monitor of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
+  if (c->call_seq != 0) {
+    set_err("fmr_enable_rf_monitor: the chain has already taken samples (the RF monitor counts from the chain's first IF sample)");
+    return FMR_ERR_BAD_ARG;
+  }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    return c->rfm_init(m);
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_rf_monitor_read(fmr_chain *c, int stream, fmr_rf_monitor_record *recs, uint32_t *hist, double *psd, int cap,
+                        fmr_rf_monitor_info *info, size_t info_size) {
+  if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_rf_monitor_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
+  if (!c->rfm) { set_err("fmr_rf_monitor_read: the chain has no RF monitor (fmr_enable_rf_monitor)"); return FMR_ERR_BAD_ARG; }
+  if (cap > 0 && !recs) { set_err("fmr_rf_monitor_read: recs is null"); return FMR_ERR_BAD_ARG; }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    const size_t B = (size_t)kRfmBins;
+    const unsigned long long L = (unsigned long long)c->rfm_cfg.max_records;
+    const unsigned long long done = (unsigned long long)(c->rfm_next_seg / c->rfm_spr);
+    c->rfm_catch_up(stream);
+    const unsigned long long first = c->rfm_read[stream], ready = done - first;
+    const size_t n = (size_t)std::min<unsigned long long>(ready, (unsigned long long)cap);
+    for (size_t k = 0; k < n;) {       // the ring slots first % L .. in at most two contiguous pieces
+      const size_t slot = (size_t)((first + k) % L), m = std::min(n - k, (size_t)L - slot), at = (size_t)stream * L + slot;
+      HIPCHK(hipMemcpy(recs + k, c->d_rfm_ring_rec.p + at, m * sizeof(fmr_rf_monitor_record), hipMemcpyDeviceToHost));
+      if (hist) HIPCHK(hipMemcpy(hist + k * B, c->d_rfm_ring_hist.p + at * B, m * B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      if (psd) HIPCHK(hipMemcpy(psd + k * kMonPsd, c->d_rfm_ring_psd.p + at * kMonPsd, m * kMonPsd * sizeof(double), hipMemcpyDeviceToHost));
+      k += m;
+    }
+    if (psd) {
+      const double scale = 1.0 / (kFmRate * c->rfm_sumw2);
+      for (size_t k = 0; k < n; k++) {
+        const double cnt = (double)recs[k].segments;
+        double *p = psd + k * kMonPsd;
+        for (int i = 0; i < kMonPsd; i++)
+          p[i] = recs[k].segments == 0 ? 0.0 : p[i] / cnt * ((i == 0 || i == kMonPsd - 1) ? 1.0 : 2.0) * scale;
+      }
+    }
+    c->rfm_read[stream] = first + n;
+    if (info) {
+      fmr_rf_monitor_info full{};
+      full.struct_size = (unsigned)sizeof full;
+      full.hist_bins = kRfmBins;
+      full.psd_bins = kMonPsd;
+      full.records_complete = done;
+      full.records_dropped = c->rfm_dropped[stream];
+      full.first_unread = c->rfm_read[stream];
+      full.records_ready = done - c->rfm_read[stream];
+      full.interval_samples = c->rfm_cfg.interval_samples;
+      full.max_records = c->rfm_cfg.max_records;
+      full.bin_hz = kFmRate / kMonN;
+      const size_t isz = info_size ? info_size : sizeof full;
+      memcpy(info, &full, isz < sizeof full ? isz : sizeof full);
+    }
+    return cap == 0 ? (int)std::min<unsigned long long>(ready, (unsigned long long)INT_MAX) : (int)n;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_rf_monitor_derive(const fmr_rf_monitor_record *recs, const uint32_t *hist, const double *psd, int n,
+                          fmr_rf_monitor_levels *out, size_t out_size) {
+  if (!recs || !out || n < 1) { set_err("fmr_rf_monitor_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
+  const double F = kFmRate, df = F / kMonN;
+  double m2 = 0.0, m4 = 0.0;
+  unsigned long long nf = 0, seg = 0;
+  std::vector<double> p(kMonPsd, 0.0);
+  std::vector<unsigned long long> h(kRfmBins, 0ull);
+  for (int i = 0; i < n; i++) {
+    const fmr_rf_monitor_record &r = recs[i];
+    m2 += r.m2; m4 += r.m4; nf += r.n_finite; seg += r.segments;
+    if (psd && r.segments > 0)
+      for (int k = 0; k < kMonPsd; k++) p[k] += (double)r.segments * psd[(size_t)i * kMonPsd + k];
+    if (hist)
+      for (int b = 0; b < kRfmBins; b++) h[b] += hist[(size_t)i * kRfmBins + b];
+  }
+  if (seg > 0) for (double &v : p) v /= (double)seg;
+  const double M2 = nf ? m2 / (double)nf : 0.0, M4 = nf ? m4 / (double)nf : 0.0;
+  auto db = [](double x) -> double { return x > 0.0 ? 10.0 * std::log10(x) : -INFINITY; };
+  auto band = [&](double lo, double hi, bool avg) {
+    double b = 0.0; int cnt = 0;
+    for (int k = 0; k < kMonPsd; k++) if (k * df >= lo && k * df <= hi) { b += p[k]; cnt++; }
+    return avg ? (cnt ? b / cnt : 0.0) : b * df;
+  };
+  auto pct = [&](unsigned q) -> double {
+    if (!hist || nf == 0) return -INFINITY;
+    unsigned long long cum = 0;
+    for (int b = 0; b < kRfmBins; b++) {
+      cum += h[b];
+      if (100ull * cum >= (unsigned long long)q * nf) {
+        const int u = b + kRfmBinBase;
+        return 10.0 * std::log10(std::ldexp(1.0 + (u & 7) / 8.0, (u >> 3) - 127));
+      }
+    }
+    return -INFINITY;      // (a histogram that holds fewer counts than n_finite says)
+  };
+  const double d = 2.0 * M2 * M2 - M4, Sc = d > 0.0 ? std::sqrt(d) : 0.0, Nn = M2 - Sc;
+  const double ref = 4.0 * M2 * M2;
+  fmr_rf_monitor_levels full{};
+  full.struct_size = (unsigned)sizeof full;
+  full.level_dbfs = db(M2);
+  full.carrier_dbfs = db(Sc);
+  full.noise_dbfs = db(Nn);
+  full.cn_db = Sc > 0.0 ? (Nn > 0.0 ? 10.0 * std::log10(Sc / Nn) : INFINITY) : -INFINITY;
+  full.am_rms = M2 > 0.0 ? std::sqrt(std::max(M4 / (M2 * M2) - 1.0, 0.0)) / 2.0 : 0.0;
+  full.am_audio_db = M2 > 0.0 ? db(band(750.0, 15000.0, false) / ref) : -INFINITY;
+  full.am_pilot_db = M2 > 0.0 ? db(band(18250.0, 19750.0, false) / ref) : -INFINITY;
+  full.am_floor_dbc_hz = M2 > 0.0 ? db(band(100000.0, 150000.0, true) / ref) : -INFINITY;
+  full.p10_dbfs = pct(10); full.p50_dbfs = pct(50); full.p90_dbfs = pct(90);
+  full.n_finite = nf;
+  full.segments = seg;
   const size_t osz = out_size ? out_size : sizeof full;
   memcpy(out, &full, osz < sizeof full ? osz : sizeof full);
   return FMR_OK;

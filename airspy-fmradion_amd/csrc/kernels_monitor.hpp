@@ -21,6 +21,9 @@
 // parity).  In the call's last launch it also copies the call's last samples into the carry (sample p at
 // carry[p mod 1024]: the up to 1023 samples no complete segment has consumed never collide there).
 //
+// The bodies of both kernels (mon_seg_run, mon_reduce_run, mon_fft) are shared with the RF monitor (kernels_rfmon.hpp),
+// which differs in where a sample comes from and in the histogram's bin rule.
+//
 // Nothing here waits on another workgroup or on the host.  The density scaling c_k / (F sum w^2) and the division by the
 // segment count happen on the host when a record is read.
 #pragma once
@@ -68,22 +71,55 @@ __device__ __forceinline__ int mon_bin(float x, float rf, float scale, int bins)
   return (int)t;
 }
 
-// Stream s = blockIdx.y: the call's MPX at base + s base_stride + base_off (sample n0 first), the carry at
-// carry + s kMonN.  Partials of run r = blockIdx.x at row s rmax + r: ppsd [kMonPsd], phist [bins], prec.
-__global__ __launch_bounds__(kMonT) void k_mon_seg(const float *__restrict__ base, long long base_stride, int base_off,
-                                                   const float *__restrict__ carry, MonArgs a,
-                                                   const float *__restrict__ win, const float2 *__restrict__ tw, int rmax,
-                                                   double *__restrict__ ppsd, unsigned *__restrict__ phist,
-                                                   MonRec *__restrict__ prec) {
+// Where a segment kernel's samples come from and how they are binned: the MPX of the modulation monitor here, the IF
+// power of the RF monitor in kernels_rfmon.hpp.  at(p) is the sample of absolute index p (from the call, or in front of
+// its first sample from the stream's carry), bin(v) the histogram counter of a finite sample.
+struct MonMpxSrc {
+  static constexpr int kHist = kMonMaxHist;
+  const float *xin, *cin;
+  long long n0;
+  float rf, scale;
+  int bins;
+  __device__ __forceinline__ float at(long long p) const { return p < n0 ? cin[p & (kMonN - 1)] : xin[p - n0]; }
+  __device__ __forceinline__ int bin(float v) const { return mon_bin(v, rf, scale, bins); }
+};
+
+// The 1024-point FFT of both monitors: five radix-4 decimation-in-time passes in place over the bit-reversed points in
+// lds (the band spectrum's butterfly and padding), one butterfly per thread and pass; ends behind a barrier.
+__device__ __forceinline__ void mon_fft(float2 *lds, const float2 *__restrict__ tw, int tid) {
+  constexpr int N = kMonN;
+  for (int span = 1; span < N; span *= 4) {
+    const int tstep = N / (4 * span);
+    const int jj = tid & (span - 1);
+    const int b0 = (tid - jj) * 4 + jj;
+    const int e0 = spec_pad(b0), e1 = spec_pad(b0 + 2 * span), e2 = spec_pad(b0 + span), e3 = spec_pad(b0 + 3 * span);
+    const float2 a0 = lds[e0];
+    const float2 a1 = cmul(lds[e1], tw[jj * tstep]);
+    const float2 a2 = cmul(lds[e2], tw[2 * jj * tstep]);
+    const float2 a3 = cmul(lds[e3], tw[3 * jj * tstep]);
+    const float2 s02 = make_float2(a0.x + a2.x, a0.y + a2.y), d02 = make_float2(a0.x - a2.x, a0.y - a2.y);
+    const float2 s13 = make_float2(a1.x + a3.x, a1.y + a3.y), d13 = make_float2(a1.x - a3.x, a1.y - a3.y);
+    lds[e0] = make_float2(s02.x + s13.x, s02.y + s13.y);
+    lds[e2] = make_float2(d02.x + d13.y, d02.y - d13.x);
+    lds[e1] = make_float2(s02.x - s13.x, s02.y - s13.y);
+    lds[e3] = make_float2(d02.x - d13.y, d02.y + d13.x);
+    __syncthreads();
+  }
+}
+
+// One run of segments of stream s (the body of both monitors' segment kernels): run `run` of the launch, samples from
+// src.  Partials of the run at row s rmax + run: ppsd [kMonPsd], phist [a.bins], prec.
+template <class Src>
+__device__ __forceinline__ void mon_seg_run(const Src &src, int run, int s, const MonArgs &a, const float *__restrict__ win,
+                                            const float2 *__restrict__ tw, int rmax, double *__restrict__ ppsd,
+                                            unsigned *__restrict__ phist, MonRec *__restrict__ prec) {
   constexpr int N = kMonN, T = kMonT;
   __shared__ float2 lds[N + (N >> 5)];
-  __shared__ unsigned s_hist[kMonMaxHist];
-  const int tid = threadIdx.x, run = blockIdx.x, s = blockIdx.y;
+  __shared__ unsigned s_hist[Src::kHist];
+  const int tid = threadIdx.x;
   long long lo, hi;
   mon_sub(a.spr, a.sub, a.sb, a.g0 + run, lo, hi);
   const long long j_lo = lo > a.a0 ? lo : a.a0, j_hi = hi < a.a1 ? hi : a.a1;
-  const float *xin = base + (long long)s * base_stride + base_off;
-  const float *cin = carry + (long long)s * N;
   for (int b = tid; b < a.bins; b += T) s_hist[b] = 0u;
   __syncthreads();
 
@@ -99,7 +135,7 @@ __global__ __launch_bounds__(kMonT) void k_mon_seg(const float *__restrict__ bas
     for (int q = 0; q < N / T; q++) {
       const int i = tid + q * T;
       const long long p = p0 + i;
-      const float v = p < a.n0 ? cin[p & (N - 1)] : xin[p - a.n0];
+      const float v = src.at(p);
       const bool fin = isfinite(v);
       bad |= !fin;
       if (q < kMonH / T) {                 // the segment's first H samples: the time-domain part
@@ -109,7 +145,7 @@ __global__ __launch_bounds__(kMonT) void k_mon_seg(const float *__restrict__ bas
           mx = fmaxf(mx, v);
           sum += (double)v;
           sumsq += (double)v * (double)v;
-          atomicAdd(&s_hist[mon_bin(v, a.rf, a.scale, a.bins)], 1u);
+          atomicAdd(&s_hist[src.bin(v)], 1u);
         } else {
           nnon++;
         }
@@ -118,23 +154,7 @@ __global__ __launch_bounds__(kMonT) void k_mon_seg(const float *__restrict__ bas
     }
     bad = __syncthreads_or(bad);
     if (bad) { skipped++; continue; }      // (uniform: nobody has read the LDS, the next segment's stores may follow)
-    for (int span = 1; span < N; span *= 4) {
-      const int tstep = N / (4 * span);
-      const int jj = tid & (span - 1);
-      const int b0 = (tid - jj) * 4 + jj;
-      const int e0 = spec_pad(b0), e1 = spec_pad(b0 + 2 * span), e2 = spec_pad(b0 + span), e3 = spec_pad(b0 + 3 * span);
-      const float2 a0 = lds[e0];
-      const float2 a1 = cmul(lds[e1], tw[jj * tstep]);
-      const float2 a2 = cmul(lds[e2], tw[2 * jj * tstep]);
-      const float2 a3 = cmul(lds[e3], tw[3 * jj * tstep]);
-      const float2 s02 = make_float2(a0.x + a2.x, a0.y + a2.y), d02 = make_float2(a0.x - a2.x, a0.y - a2.y);
-      const float2 s13 = make_float2(a1.x + a3.x, a1.y + a3.y), d13 = make_float2(a1.x - a3.x, a1.y - a3.y);
-      lds[e0] = make_float2(s02.x + s13.x, s02.y + s13.y);
-      lds[e2] = make_float2(d02.x + d13.y, d02.y - d13.x);
-      lds[e1] = make_float2(s02.x - s13.x, s02.y - s13.y);
-      lds[e3] = make_float2(d02.x - d13.y, d02.y + d13.x);
-      __syncthreads();
-    }
+    mon_fft(lds, tw, tid);
     {
       const float2 x0 = lds[spec_pad(tid)], x1 = lds[spec_pad(tid + T)];
       acc0 += (double)(x0.x * x0.x + x0.y * x0.y);
@@ -180,6 +200,91 @@ __global__ __launch_bounds__(kMonT) void k_mon_seg(const float *__restrict__ bas
   }
 }
 
+// Stream s = blockIdx.y: the call's MPX at base + s base_stride + base_off (sample n0 first), the carry at
+// carry + s kMonN.  Partials of run r = blockIdx.x at row s rmax + r.
+__global__ __launch_bounds__(kMonT) void k_mon_seg(const float *__restrict__ base, long long base_stride, int base_off,
+                                                   const float *__restrict__ carry, MonArgs a,
+                                                   const float *__restrict__ win, const float2 *__restrict__ tw, int rmax,
+                                                   double *__restrict__ ppsd, unsigned *__restrict__ phist,
+                                                   MonRec *__restrict__ prec) {
+  const int s = blockIdx.y;
+  const MonMpxSrc src{base + (long long)s * base_stride + base_off, carry + (long long)s * kMonN, a.n0, a.rf, a.scale, a.bins};
+  mon_seg_run(src, blockIdx.x, s, a, win, tw, rmax, ppsd, phist, prec);
+}
+
+// The record part of both monitors' reduce kernels (runs > 0): block (x = record l0 + blockIdx.x of the launch,
+// y = stream), HB = counters per thread (the histogram holds at most HB kMonT of them).
+template <int HB>
+__device__ __forceinline__ void mon_reduce_run(const double *__restrict__ ppsd, const unsigned *__restrict__ phist,
+                                               const MonRec *__restrict__ prec, int runs, int rmax, const MonArgs &a, int L,
+                                               long long M, int par, double *__restrict__ open_psd,
+                                               unsigned *__restrict__ open_hist, MonRec *__restrict__ open_rec,
+                                               double *__restrict__ ring_psd, unsigned *__restrict__ ring_hist,
+                                               MonRec *__restrict__ ring_rec) {
+  constexpr int T = kMonT;
+  const int tid = threadIdx.x, s = blockIdx.y, S = gridDim.y;
+  const long long l = a.g0 / a.sb + blockIdx.x;
+  const long long g_last = a.g0 + runs - 1;
+  const int b_lo = blockIdx.x == 0 ? (int)(a.g0 - l * a.sb) : 0;
+  const int b_hi = (int)(a.sb < g_last - l * a.sb + 1 ? a.sb : g_last - l * a.sb + 1);
+  double p0 = 0.0, p1 = 0.0, p2 = 0.0;
+  unsigned h[HB];
+#pragma unroll
+  for (int k = 0; k < HB; k++) h[k] = 0u;
+  MonRec o{};
+  o.mn = INFINITY; o.mx = -INFINITY;
+  if (a.a0 > l * a.spr) {                 // the record began in an earlier launch (the launch's first record only)
+    const size_t os = (size_t)par * S + s;
+    p0 = open_psd[os * kMonPsd + tid];
+    p1 = open_psd[os * kMonPsd + tid + T];
+#pragma unroll
+    for (int k = 0; k < HB; k++)
+      if (tid + k * T < a.bins) h[k] = open_hist[os * a.bins + tid + k * T];
+    if (tid == 0) { p2 = open_psd[os * kMonPsd + kMonN / 2]; o = open_rec[os]; }
+  }
+  for (int b = b_lo; b < b_hi; b++) {
+    const size_t prow = (size_t)s * rmax + (size_t)(l * a.sb + b - a.g0);
+    p0 += ppsd[prow * kMonPsd + tid];
+    p1 += ppsd[prow * kMonPsd + tid + T];
+#pragma unroll
+    for (int k = 0; k < HB; k++)
+      if (tid + k * T < a.bins) h[k] += phist[prow * a.bins + tid + k * T];
+    if (tid == 0) {
+      const MonRec q = prec[prow];
+      p2 += ppsd[prow * kMonPsd + kMonN / 2];
+      o.n_finite += q.n_finite; o.n_nonfinite += q.n_nonfinite; o.segments += q.segments; o.skipped += q.skipped;
+      o.mn = fminf(o.mn, q.mn); o.mx = fmaxf(o.mx, q.mx);
+      o.sum += q.sum; o.sumsq += q.sumsq;
+    }
+  }
+  const long long last_done = a.a1 / a.spr - 1;      // last record complete after this launch
+  if (l <= last_done) {
+    if (l + L > last_done) {
+      const size_t slot = (size_t)s * L + (size_t)(l % L);
+      ring_psd[slot * kMonPsd + tid] = p0;
+      ring_psd[slot * kMonPsd + tid + T] = p1;
+#pragma unroll
+      for (int k = 0; k < HB; k++)
+        if (tid + k * T < a.bins) ring_hist[slot * a.bins + tid + k * T] = h[k];
+      if (tid == 0) {
+        ring_psd[slot * kMonPsd + kMonN / 2] = p2;
+        o.index = (uint64_t)l;
+        o.first_sample = (uint64_t)(l * M);
+        if (o.n_finite == 0) { o.mn = 0.f; o.mx = 0.f; }
+        ring_rec[slot] = o;
+      }
+    }
+  } else {
+    const size_t os = (size_t)(par ^ 1) * S + s;
+    open_psd[os * kMonPsd + tid] = p0;
+    open_psd[os * kMonPsd + tid + T] = p1;
+#pragma unroll
+    for (int k = 0; k < HB; k++)
+      if (tid + k * T < a.bins) open_hist[os * a.bins + tid + k * T] = h[k];
+    if (tid == 0) { open_psd[os * kMonPsd + kMonN / 2] = p2; open_rec[os] = o; }
+  }
+}
+
 // Block (x = record l0 + blockIdx.x of the launch, y = stream); l0 = the record of segment a0.  The block adds the
 // partials of its record's sub-blocks inside the launch in run order (fp64, no float atomics), starting from the open
 // record of the launch before (open_*[par]: [2][S] records, [2][S][bins] counters, [2][S][kMonPsd] sums) when the record
@@ -195,70 +300,11 @@ __global__ __launch_bounds__(kMonT) void k_mon_reduce(const double *__restrict__
                                                       MonRec *__restrict__ ring_rec, const float *__restrict__ base,
                                                       long long base_stride, int base_off, float *__restrict__ carry,
                                                       long long n_end, int last) {
-  constexpr int T = kMonT, HB = kMonMaxHist / kMonT;
-  const int tid = threadIdx.x, s = blockIdx.y, S = gridDim.y;
-  if (runs > 0) {
-    const long long l = a.g0 / a.sb + blockIdx.x;
-    const long long g_last = a.g0 + runs - 1;
-    const int b_lo = blockIdx.x == 0 ? (int)(a.g0 - l * a.sb) : 0;
-    const int b_hi = (int)(a.sb < g_last - l * a.sb + 1 ? a.sb : g_last - l * a.sb + 1);
-    double p0 = 0.0, p1 = 0.0, p2 = 0.0;
-    unsigned h[HB];
-#pragma unroll
-    for (int k = 0; k < HB; k++) h[k] = 0u;
-    MonRec o{};
-    o.mn = INFINITY; o.mx = -INFINITY;
-    if (a.a0 > l * a.spr) {                 // the record began in an earlier launch (the launch's first record only)
-      const size_t os = (size_t)par * S + s;
-      p0 = open_psd[os * kMonPsd + tid];
-      p1 = open_psd[os * kMonPsd + tid + T];
-#pragma unroll
-      for (int k = 0; k < HB; k++)
-        if (tid + k * T < a.bins) h[k] = open_hist[os * a.bins + tid + k * T];
-      if (tid == 0) { p2 = open_psd[os * kMonPsd + kMonN / 2]; o = open_rec[os]; }
-    }
-    for (int b = b_lo; b < b_hi; b++) {
-      const size_t prow = (size_t)s * rmax + (size_t)(l * a.sb + b - a.g0);
-      p0 += ppsd[prow * kMonPsd + tid];
-      p1 += ppsd[prow * kMonPsd + tid + T];
-#pragma unroll
-      for (int k = 0; k < HB; k++)
-        if (tid + k * T < a.bins) h[k] += phist[prow * a.bins + tid + k * T];
-      if (tid == 0) {
-        const MonRec q = prec[prow];
-        p2 += ppsd[prow * kMonPsd + kMonN / 2];
-        o.n_finite += q.n_finite; o.n_nonfinite += q.n_nonfinite; o.segments += q.segments; o.skipped += q.skipped;
-        o.mn = fminf(o.mn, q.mn); o.mx = fmaxf(o.mx, q.mx);
-        o.sum += q.sum; o.sumsq += q.sumsq;
-      }
-    }
-    const long long last_done = a.a1 / a.spr - 1;      // last record complete after this launch
-    if (l <= last_done) {
-      if (l + L > last_done) {
-        const size_t slot = (size_t)s * L + (size_t)(l % L);
-        ring_psd[slot * kMonPsd + tid] = p0;
-        ring_psd[slot * kMonPsd + tid + T] = p1;
-#pragma unroll
-        for (int k = 0; k < HB; k++)
-          if (tid + k * T < a.bins) ring_hist[slot * a.bins + tid + k * T] = h[k];
-        if (tid == 0) {
-          ring_psd[slot * kMonPsd + kMonN / 2] = p2;
-          o.index = (uint64_t)l;
-          o.first_sample = (uint64_t)(l * M);
-          if (o.n_finite == 0) { o.mn = 0.f; o.mx = 0.f; }
-          ring_rec[slot] = o;
-        }
-      }
-    } else {
-      const size_t os = (size_t)(par ^ 1) * S + s;
-      open_psd[os * kMonPsd + tid] = p0;
-      open_psd[os * kMonPsd + tid + T] = p1;
-#pragma unroll
-      for (int k = 0; k < HB; k++)
-        if (tid + k * T < a.bins) open_hist[os * a.bins + tid + k * T] = h[k];
-      if (tid == 0) { open_psd[os * kMonPsd + kMonN / 2] = p2; open_rec[os] = o; }
-    }
-  }
+  constexpr int T = kMonT;
+  const int tid = threadIdx.x, s = blockIdx.y;
+  if (runs > 0)
+    mon_reduce_run<kMonMaxHist / kMonT>(ppsd, phist, prec, runs, rmax, a, L, M, par, open_psd, open_hist, open_rec, ring_psd,
+                                        ring_hist, ring_rec);
   if (last && blockIdx.x == 0) {
     const float *xin = base + (long long)s * base_stride + base_off;
     for (int q = tid; q < kMonN - 1; q += T) {

@@ -145,7 +145,39 @@ inline LoudnessReport loudness_report(fmr_chain *c, int stream, double silence_d
   if (n > 0) check(fmr_loudness_derive(out.records.data(), n, silence_dbfs, &out.levels, sizeof out.levels), "fmr_loudness_derive");
   return out;
 }
+
+// RF monitor (fmr_enable_rf_monitor / fmr_rf_monitor_read / fmr_rf_monitor_derive): one drained record with its
+// histogram (384 bins, eight per octave of power), the one-sided PSD of |x|^2 (513 bins of 375 Hz) and the levels
+// derived from it alone
+struct RfRecord {
+  fmr_rf_monitor_record rec{};
+  std::vector<uint32_t> hist;
+  std::vector<double> psd;
+  fmr_rf_monitor_levels levels{};
+};
+inline void rf_monitor(fmr_chain *c, const fmr_rf_monitor_config &m) {
+  check(fmr_enable_rf_monitor(c, &m, sizeof m), "fmr_enable_rf_monitor");
+}
+inline std::vector<RfRecord> rf_records(fmr_chain *c, int stream) {
+  fmr_rf_monitor_info info{};
+  const int ready = fmr_rf_monitor_read(c, stream, nullptr, nullptr, nullptr, 0, &info, sizeof info);
+  if (ready < 0) check(ready, "fmr_rf_monitor_read");
+  std::vector<RfRecord> out;
+  for (int i = 0; i < ready; i++) {
+    RfRecord r;
+    r.hist.resize((size_t)info.hist_bins);
+    r.psd.resize((size_t)info.psd_bins);
+    const int n = fmr_rf_monitor_read(c, stream, &r.rec, r.hist.data(), r.psd.data(), 1, nullptr, 0);
+    if (n < 0) check(n, "fmr_rf_monitor_read");
+    if (n == 0) break;
+    r.levels.struct_size = sizeof r.levels;
+    check(fmr_rf_monitor_derive(&r.rec, r.hist.data(), r.psd.data(), 1, &r.levels, sizeof r.levels), "fmr_rf_monitor_derive");
+    out.push_back(std::move(r));
+  }
+  return out;
+}
 }  // namespace fmr_detail
+using RfRecord = fmr_detail::RfRecord;
 using ModulationRecord = fmr_detail::ModulationRecord;
 using LoudnessReport = fmr_detail::LoudnessReport;
 
@@ -284,6 +316,7 @@ public:
     m_chain = fmr_detail::make(m_cfg, m_rds);
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
+    if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
   }
 
   // RDS (no counterpart in the reference; fmr_create_rds): re-creates the chain with the RDS decoder, before the first
@@ -295,6 +328,7 @@ public:
     m_chain = fmr_detail::make(m_cfg, true);
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
+    if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
   }
   // error correction of the RDS blocks (fmr_set_rds_correction: FMR_RDS_FEC_OFF / _BURST / _SOFT; 0 = the defaults); at
   // any time after enable_rds(), from the decoder's next block boundary on.  enable_rds() starts with it off.
@@ -329,6 +363,18 @@ public:
   }
   LoudnessReport read_loudness(double silence_dbfs = -60.0) { return fmr_detail::loudness_report(m_chain, 0, silence_dbfs); }
 
+  // RF monitor (no counterpart in the reference; fmr_enable_rf_monitor): records of interval_samples IF samples (0 =
+  // 38400, 100 ms) with level, C/N, envelope AM and fade percentiles; before the first process(), once.
+  // read_rf_records() drains the complete ones, oldest first.
+  void enable_rf_monitor(uint32_t interval_samples = 0, int max_records = 0) {
+    if (m_started) fmr_detail::fail("FmDecoder::enable_rf_monitor: after the first process()");
+    m_rf_cfg = fmr_rf_monitor_config{};
+    m_rf_cfg.struct_size = sizeof m_rf_cfg; m_rf_cfg.interval_samples = interval_samples; m_rf_cfg.max_records = max_records;
+    fmr_detail::rf_monitor(m_chain, m_rf_cfg);
+    m_rf = true;
+  }
+  std::vector<RfRecord> read_rf_records() { return fmr_detail::rf_records(m_chain, 0); }
+
   // Latency for throughput: hold back `blocks` - 1 calls and decode `blocks` blocks in ONE batched call.  process()
   // then returns an empty vector ("nothing yet": the contract of FmDecode.cpp:89-92,185-188, which main.cpp:981-984
   // already handles) until the batch is full, and the audio of all its blocks at once.  One 65536-sample block per
@@ -350,6 +396,7 @@ public:
       m_chain = fmr_detail::make(m_cfg, m_rds);
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
+    if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
       m_capacity = blocks;
     }
     m_batch = blocks;
@@ -446,6 +493,8 @@ private:
   fmr_monitor_config m_mon_cfg{};
   bool m_ld = false;
   fmr_loudness_config m_ld_cfg{};
+  bool m_rf = false;
+  fmr_rf_monitor_config m_rf_cfg{};
   fmr_chain *m_chain = nullptr;
   bool m_rds = false;
   fmr_rds::Station m_station;
@@ -594,6 +643,7 @@ public:
     m_chain = fmr_detail::make(m_cfg, true);
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
+    if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     m_stations.assign(m_offsets.size(), fmr_rds::Station());
   }
   // error correction of every channel's RDS blocks (fmr_set_rds_correction), at any time after enable_rds()
@@ -630,6 +680,19 @@ public:
   LoudnessReport read_loudness(size_t ch, double silence_dbfs = -60.0) {
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
     return fmr_detail::loudness_report(m_chain, (int)ch, silence_dbfs);
+  }
+
+  // RF monitor of every channel (fmr_enable_rf_monitor), before the first process(), once; FM banks only.
+  // read_rf_records(ch) drains channel ch's complete records, oldest first.
+  void enable_rf_monitor(uint32_t interval_samples = 0, int max_records = 0) {
+    m_rf_cfg = fmr_rf_monitor_config{};
+    m_rf_cfg.struct_size = sizeof m_rf_cfg; m_rf_cfg.interval_samples = interval_samples; m_rf_cfg.max_records = max_records;
+    fmr_detail::rf_monitor(m_chain, m_rf_cfg);
+    m_rf = true;
+  }
+  std::vector<RfRecord> read_rf_records(size_t ch) {
+    if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
+    return fmr_detail::rf_records(m_chain, (int)ch);
   }
 
   // audio[k] = what channel k produced from this capture block (empty = "nothing yet"); blocks longer than the chain's
@@ -684,6 +747,8 @@ private:
   fmr_monitor_config m_mon_cfg{};
   bool m_ld = false;
   fmr_loudness_config m_ld_cfg{};
+  bool m_rf = false;
+  fmr_rf_monitor_config m_rf_cfg{};
   fmr_chain *m_chain = nullptr;
 };
 

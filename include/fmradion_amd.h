@@ -700,6 +700,102 @@ int fmr_loudness_read(fmr_chain *c, int stream, fmr_loudness_record *recs, int c
  * trailing_silence_blocks the run that ends at the last record.  Loudness range (EBU 3342) is not computed. */
 int fmr_loudness_derive(const fmr_loudness_record *recs, int n, double silence_dbfs, fmr_loudness_levels *out, size_t out_size);
 
+/* --- RF monitor (no counterpart in the reference).  An FM chain with it enabled measures the
+ * received signal of every stream / bank channel where it lies on the device: level, C/N, the AM on the envelope
+ * (multipath turns FM into AM: the 19 kHz line of the envelope is the classic indicator) and the depth of fades.  The
+ * audio, fmr_status, PPS events, RDS groups and the records of both other monitors are what they are without it: the
+ * stage only reads the call's IF ring slot.
+ *   F = 384000, N = 1024, H = 512, M = interval_samples.  Indices are absolute, counted from the chain's first IF sample
+ * (IF sample n and MPX sample n are the same instant); nothing depends on the cut into blocks and calls.
+ * Signal: p[n], the squared magnitude of IF sample n as it enters the decoder: before the IF filter (-f), the IF AGC and
+ * the equaliser; the signal fmr_status.if_rms is taken from.  Where the slot holds IF samples (re, im),
+ * p = fl(fl(re re) + fl(im im)) in unfused fp32 (numpy float32 gives the same bits).  Behind a discriminator epilogue
+ * (the fused front end and the R8B class without FMR_DEBUG_TAPS: the production path at 10 MS/s) the front end stored
+ * |x|^2 there instead of the IF samples, and p is that float as stored.  The two forms may differ in the last bits of p:
+ * the epilogue rounds its IF samples and their squares in its own order.
+ * Time-domain part of record i, over [i M, (i + 1) M): a non-finite p is counted in n_nonfinite and enters nothing else;
+ * n_finite; p_min and p_max (fp32, both 0 when n_finite = 0); m2 = sum p and m4 = sum p^2 (fp64 sums of the fp32 values
+ * and of their fp64 squares); a histogram of 384 uint32 counters by an integer rule: with u = (bit pattern of p as
+ * uint32) >> 20, bin = clamp(u - 696, 0, 383).  That is eight bins per octave of power from 2^-40 to 2^8; zero and
+ * everything below go to bin 0, everything above to bin 383.  (p = 0, 1e-13, 2^-40, 0.09, 1, 255.9, 256, 1e9 fall into the
+ * bins 0, 0, 0, 291, 320, 383, 383, 383.)  With u = b + 696 the lower edge of bin b is 2^((u >> 3) - 127) (1 + (u & 7) / 8).
+ * Spectral part, of p, as the modulation monitor treats the MPX: segment j covers [j H, j H + N) and belongs to record
+ * floor(j H / M); periodic Hann window, built in double and rounded once to fp32; one-sided density over k = 0 .. 512,
+ * P_j[k] = c_k |sum_n w[n] p[j H + n] exp(-2 pi i k n / N)|^2 / (F sum w^2), c_k = 2 inside and 1 at both ends.  A segment
+ * that holds a non-finite p is skipped and counted in segments_skipped; psd is the mean of the counted P_j (fp64 sum on
+ * the device, divided on the host when read), all zeros when segments = 0.
+ * Completion, ring and info as fmr_enable_monitor: record i is complete in the call that delivers the sample
+ * (i + 1) M + 511; max_records = L records per stream, an overwritten unread record is counted in records_dropped; the
+ * read positions live on the host.
+ * Reproducibility: counts, histogram, p_min, p_max, segments and segments_skipped are bit-identical for any cut of the
+ * input into calls; m2, m4 and psd add fixed per-segment values in fp64 in a fixed order without float atomics (the same
+ * cut gives the same bits; another cut differs at fp64 rounding). */
+#define FMR_RF_HIST_BINS 384
+#define FMR_RF_PSD_BINS 513
+typedef struct {
+  unsigned struct_size;       /* sizeof(fmr_rf_monitor_config) as the caller knows it (0: cfg_size); a larger size is refused */
+  uint32_t interval_samples;  /* M: a multiple of 512 in 512 .. 2^30; 0 = 38400 (100 ms) */
+  int max_records;            /* L: 1 .. 4096; 0 = 64 */
+} fmr_rf_monitor_config;
+typedef struct {
+  uint64_t index, first_sample;   /* i and i M */
+  uint32_t n_finite, n_nonfinite, segments, segments_skipped;
+  float p_min, p_max;
+  double m2, m4;
+} fmr_rf_monitor_record;
+typedef struct {
+  unsigned struct_size;
+  int hist_bins, psd_bins;        /* 384; 513 */
+  uint64_t records_complete;      /* since create (of every stream: they run in step) */
+  uint64_t records_dropped;       /* of this stream: overwritten unread */
+  uint64_t first_unread;          /* index of the oldest unread record after this call */
+  uint64_t records_ready;         /* complete records still unread after this call */
+  uint32_t interval_samples;      /* M and L as enabled (defaults filled in) */
+  int max_records;
+  double bin_hz;                  /* F / N = 375 */
+} fmr_rf_monitor_info;
+/* With M2 = sum m2 / sum n_finite, M4 = sum m4 / sum n_finite (both 0 when no sample is finite) and B(lo, hi) = sum of
+ * psd[k] F / N over lo <= k F / N <= hi.  0 dBFS is a full-scale complex sinusoid (|x| = 1), the scale
+ * fmr_station.level_db uses.
+ * C/N by second and fourth moments, for a constant-modulus carrier in complex Gaussian noise: d = 2 M2^2 - M4,
+ * S = sqrt(d) when d > 0, otherwise 0, Nn = M2 - S.  The noise bandwidth is the chain's IF bandwidth (what the front end
+ * passes to the decoder at 384 kHz), not a normalised one.  Any variation of the envelope -- synchronous AM, multipath --
+ * reads as noise, so cn_db is a lower bound on the true C/N.
+ * Envelope modulation relative to the carrier, from the spectrum of p (p ~ A^2 (1 + 2 m(t)) for small m). */
+typedef struct {
+  unsigned struct_size;
+  int reserved;
+  double level_dbfs;              /* 10 log10(M2); -INFINITY when M2 <= 0 */
+  double carrier_dbfs;            /* 10 log10(S); -INFINITY when S = 0 */
+  double noise_dbfs;              /* 10 log10(Nn); -INFINITY when Nn <= 0 */
+  double cn_db;                   /* 10 log10(S / Nn); -INFINITY when S = 0, +INFINITY when S > 0 and Nn <= 0 */
+  double am_rms;                  /* sqrt(max(M4 / M2^2 - 1, 0)) / 2: relative rms fluctuation of the envelope; 0 when M2 <= 0 */
+  double am_audio_db;             /* 10 log10(B(750, 15000) / (4 M2^2)) */
+  double am_pilot_db;             /* 10 log10(B(18250, 19750) / (4 M2^2)) */
+  double am_floor_dbc_hz;         /* 10 log10(mean psd[k] over 100 kHz <= k F / N <= 150 kHz / (4 M2^2)); all three -INFINITY where the argument is <= 0 or M2 <= 0 */
+  double p10_dbfs, p50_dbfs, p90_dbfs;   /* 10 log10 of the lower edge of the smallest bin whose cumulative count c satisfies
+                                          * 100 c >= q n_finite (q = 10, 50, 90); -INFINITY when n_finite = 0 or hist is NULL */
+  uint64_t n_finite, segments;    /* pooled */
+} fmr_rf_monitor_levels;
+/* The rules of fmr_enable_monitor: the fields are checked first (FMR_ERR_BAD_ARG, fmr_last_error names the field; also a
+ * size larger than this library's struct), then the chain: NULL is FMR_ERR_BAD_ARG; any FMR_MODE_FM chain is accepted;
+ * every other mode and front-end-only chains are FMR_ERR_UNSUPPORTED.  Allowed once, before the chain's first sample: a
+ * second call, or one after any processing call, is FMR_ERR_BAD_ARG.  No FM chain shape is refused: in every one of them
+ * (-f, the equaliser, either resampler class, banks, the three-kernel front ends, FMR_DEBUG_TAPS=1, pipelined or in_order)
+ * the decoder's input stays in the call's IF slot until that call's tail has run; no kernel of an FM chain writes the slot
+ * in place.  A chain that never calls it allocates nothing for the RF monitor and runs none of its kernels. */
+int fmr_enable_rf_monitor(fmr_chain *c, const fmr_rf_monitor_config *cfg, size_t cfg_size);
+/* Synchronises like the other getters, then drains up to cap complete records of `stream`, oldest first, and returns how
+ * many: recs[cap], hist[cap x 384] and psd[cap x 513] (either may be NULL).  cap = 0 returns the number waiting and drains
+ * nothing.  info (may be NULL) takes info_size bytes (0 = this header's size).  FMR_ERR_BAD_ARG on a chain without the RF
+ * monitor. */
+int fmr_rf_monitor_read(fmr_chain *c, int stream, fmr_rf_monitor_record *recs, uint32_t *hist, double *psd, int cap,
+                        fmr_rf_monitor_info *info, size_t info_size);
+/* Host only, in double, no device.  Pools n records (hist: n x 384 and psd: n x 513 as read; either may be NULL): sums,
+ * counts and histograms add, psd is weighted by segments; fills the levels above. */
+int fmr_rf_monitor_derive(const fmr_rf_monitor_record *recs, const uint32_t *hist, const double *psd, int n,
+                          fmr_rf_monitor_levels *out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif
