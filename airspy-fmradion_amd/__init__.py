@@ -675,6 +675,22 @@ class Chain:
         n = self._chk(self._L.fmr_debug_read(self.h, int(stream), 5, buf.ctypes.data_as(C.c_void_p), buf.nbytes))
         return buf[:n].copy()
 
+    def _read_records(self, read, info_cls, arrays, stream, cap):
+        """The two-step read of a monitor's records: a probe (cap 0) that fills the info and says how many wait, then the
+        read of at most `cap` records (None: all that wait).  arrays lists what the C function fills, in its order, as
+        (dtype, columns): None for the records themselves, a number, or the name of the info field that holds it.
+        Returns the arrays cut to the records read, then the info as a dict."""
+        info = info_cls()
+        tail = (C.byref(info), C.sizeof(info_cls))
+        waiting = self._chk(read(self.h, int(stream), *([None] * len(arrays)), 0, *tail))
+        cap = int(waiting if cap is None else cap)
+        bufs = [np.zeros(cap if cols is None else (cap, int(getattr(info, cols) if isinstance(cols, str) else cols)), dtype=dt)
+                for dt, cols in arrays]
+        n = 0
+        if cap > 0:
+            n = self._chk(read(self.h, int(stream), *(b.ctypes.data for b in bufs), cap, *tail))
+        return (*(b[:n] for b in bufs), {k: getattr(info, k) for k, _ in info_cls._fields_})
+
     def enable_monitor(self, interval_samples=0, hist_bins=0, hist_range=0.0, max_records=0):
         """fmr_enable_monitor: the modulation monitor of every stream / channel (FM chains, once, before the first call);
         0 = the defaults (one-second records, 256 bins over +-2.0, 64 records kept)."""
@@ -684,21 +700,8 @@ class Chain:
     def monitor_records(self, stream=0, cap=None):
         """fmr_monitor_read: the oldest unread complete records of `stream` (at most cap; None: all that wait) as
         (records MONITOR_RECORD [n], hist uint32 [n, B], psd float64 [n, 513], info dict).  Reading drains them."""
-        info = MonitorInfo()
-        L = self._L
-        if cap is None:
-            cap = self._chk(L.fmr_monitor_read(self.h, int(stream), None, None, None, 0, C.byref(info), C.sizeof(MonitorInfo)))
-        else:
-            self._chk(L.fmr_monitor_read(self.h, int(stream), None, None, None, 0, C.byref(info), C.sizeof(MonitorInfo)))
-        cap, B = int(cap), int(info.hist_bins)
-        recs = np.zeros(cap, dtype=MONITOR_RECORD)
-        hist = np.zeros((cap, B), dtype=np.uint32)
-        psd = np.zeros((cap, MONITOR_PSD_BINS), dtype=np.float64)
-        n = 0
-        if cap > 0:
-            n = self._chk(L.fmr_monitor_read(self.h, int(stream), recs.ctypes.data, hist.ctypes.data, psd.ctypes.data, cap,
-                                             C.byref(info), C.sizeof(MonitorInfo)))
-        return recs[:n], hist[:n], psd[:n], {k: getattr(info, k) for k, _ in MonitorInfo._fields_}
+        return self._read_records(self._L.fmr_monitor_read, MonitorInfo, ((MONITOR_RECORD, None), (np.uint32, "hist_bins"),
+                                                                          (np.float64, MONITOR_PSD_BINS)), stream, cap)
 
     def enable_loudness(self, step_samples=0, max_records=0):
         """fmr_enable_loudness: the audio monitor of every stream / channel (FM chains, once, before the first call);
@@ -709,15 +712,7 @@ class Chain:
     def loudness_records(self, stream=0, cap=None):
         """fmr_loudness_read: the oldest unread complete records of `stream` (at most cap; None: all that wait) as
         (records LOUDNESS_RECORD [n], info dict).  Reading drains them."""
-        info = LoudnessInfo()
-        L = self._L
-        waiting = self._chk(L.fmr_loudness_read(self.h, int(stream), None, 0, C.byref(info), C.sizeof(LoudnessInfo)))
-        cap = int(waiting if cap is None else cap)
-        recs = np.zeros(cap, dtype=LOUDNESS_RECORD)
-        n = 0
-        if cap > 0:
-            n = self._chk(L.fmr_loudness_read(self.h, int(stream), recs.ctypes.data, cap, C.byref(info), C.sizeof(LoudnessInfo)))
-        return recs[:n], {k: getattr(info, k) for k, _ in LoudnessInfo._fields_}
+        return self._read_records(self._L.fmr_loudness_read, LoudnessInfo, ((LOUDNESS_RECORD, None),), stream, cap)
 
     def enable_rf_monitor(self, interval_samples=0, max_records=0):
         """fmr_enable_rf_monitor: the RF monitor of every stream / channel (FM chains, once, before the first call);
@@ -728,18 +723,8 @@ class Chain:
     def rf_monitor_records(self, stream=0, cap=None):
         """fmr_rf_monitor_read: the oldest unread complete records of `stream` (at most cap; None: all that wait) as
         (records RF_MONITOR_RECORD [n], hist uint32 [n, 384], psd float64 [n, 513], info dict).  Reading drains them."""
-        info = RfMonitorInfo()
-        L = self._L
-        waiting = self._chk(L.fmr_rf_monitor_read(self.h, int(stream), None, None, None, 0, C.byref(info), C.sizeof(RfMonitorInfo)))
-        cap = int(waiting if cap is None else cap)
-        recs = np.zeros(cap, dtype=RF_MONITOR_RECORD)
-        hist = np.zeros((cap, RF_HIST_BINS), dtype=np.uint32)
-        psd = np.zeros((cap, RF_PSD_BINS), dtype=np.float64)
-        n = 0
-        if cap > 0:
-            n = self._chk(L.fmr_rf_monitor_read(self.h, int(stream), recs.ctypes.data, hist.ctypes.data, psd.ctypes.data, cap,
-                                                C.byref(info), C.sizeof(RfMonitorInfo)))
-        return recs[:n], hist[:n], psd[:n], {k: getattr(info, k) for k, _ in RfMonitorInfo._fields_}
+        return self._read_records(self._L.fmr_rf_monitor_read, RfMonitorInfo, ((RF_MONITOR_RECORD, None), (np.uint32, RF_HIST_BINS),
+                                                                                (np.float64, RF_PSD_BINS)), stream, cap)
 
     def pps_events(self, stream=0):
         ev = (PpsEvent * 64)()

@@ -99,9 +99,94 @@ struct DevBuf {
 
 struct KernelTime { const char *name; hipEvent_t a, b; };
 
+// A struct whose first field is struct_size, as the caller of fn knows it (cfg_size bytes, 0 = this library's size) ->
+// this library's, zero-filled.  A caller that knows more than the library is refused.
+template <class T>
+int take_sized(const char *fn, const char *type_name, const T *cfg, size_t cfg_size, T &full) {
+  const size_t size = cfg_size ? cfg_size : sizeof(T);
+  const size_t stated = size >= sizeof(unsigned) ? (size_t)cfg->struct_size : (size_t)0;
+  if (size > sizeof(T) || stated > sizeof(T)) {
+    set_err("%s: struct_size %zu is larger than this library's %s (%zu): the caller is newer than the library", fn,
+            std::max(size, stated), type_name, sizeof(T));
+    return FMR_ERR_BAD_ARG;
+  }
+  memset(&full, 0, sizeof full);
+  memcpy(&full, cfg, size);
+  return FMR_OK;
+}
+// ... and the way back: at most the caller's out_size bytes (0 = this library's size) of full
+template <class T>
+void give_sized(void *out, size_t out_size, const T &full) {
+  const size_t size = out_size ? out_size : sizeof full;
+  memcpy(out, &full, size < sizeof full ? size : sizeof full);
+}
+
 }  // namespace
 
 using namespace fmr;
+
+namespace {
+// The reader's side of a ring of L records per stream (the three monitors' records, the waterfall's lines): per stream
+// the next unread record and the records overwritten unread.  `done` is the number of records complete so far.
+struct RecCursor {
+  std::vector<unsigned long long> read, dropped;
+  unsigned long long L = 1;
+  void reset(int streams, int depth) { read.assign(streams, 0); dropped.assign(streams, 0); L = (unsigned long long)depth; }
+  // records the ring has overwritten unread: the read position follows, the loss is counted
+  void catch_up(int s, unsigned long long done) {
+    if (done > L && read[s] < done - L) {
+      dropped[s] += done - L - read[s];
+      read[s] = done - L;
+    }
+  }
+  // Drains up to cap records of stream s, oldest first: copy(k, slot, m) fetches records k .. k + m of the read from the
+  // ring slots slot .. slot + m and returns FMR_OK, or an error that ends the read with nothing drained.  Returns the
+  // count; cap = 0 returns the number waiting and drains nothing.
+  template <class F>
+  int take(int s, unsigned long long done, unsigned long long cap, F &&copy) {
+    catch_up(s, done);
+    const unsigned long long first = read[s], ready = std::min<unsigned long long>(done - first, (unsigned long long)INT_MAX);
+    const size_t n = (size_t)std::min(ready, cap);
+    for (size_t k = 0; k < n;) {       // the ring slots first % L .. in at most two contiguous pieces
+      const size_t slot = (size_t)((first + k) % L), m = std::min(n - k, (size_t)L - slot);
+      if (int rc = copy(k, slot, m)) return rc;
+      k += m;
+    }
+    read[s] = first + n;
+    return (int)(cap == 0 ? ready : n);
+  }
+};
+
+// The engine of the modulation monitor and the RF monitor (kernels_monitor.hpp): records of `interval` samples cut into
+// aligned sub-blocks of segments, the window and twiddle tables, the stream's carry, the runs' partials, the open records
+// (two copies by launch parity) and the rings of max_records records per stream with their reader.  It counts in absolute
+// samples (n), so the cut into calls does not matter.  fmr_chain::seg_stage runs a call through it.
+struct SegMonitor {
+  bool on = false;
+  unsigned interval = 0;                     // samples per record
+  int bins = 0;                              // histogram counters per record
+  int spr = 0, sub = 0, sb = 0, rmax = 0;    // segments per record / per sub-block, sub-blocks per record, runs per stream and launch
+  int par = 0;                               // which copy of the open records is current
+  double sumw2 = 0.0;
+  long long n = 0, next_seg = 0;             // samples seen, segments processed
+  DevBuf<float> d_win, d_carry;
+  DevBuf<float2> d_tw;
+  DevBuf<double> d_ppsd, d_open_psd, d_ring_psd;
+  DevBuf<unsigned> d_phist, d_open_hist, d_ring_hist;
+  DevBuf<MonRec> d_prec, d_open_rec, d_ring_rec;
+  RecCursor cur;
+  unsigned long long done() const { return (unsigned long long)(next_seg / spr); }   // records complete
+  int init(int S, size_t max_if, unsigned interval_samples, int hist_bins, int max_records);
+  void release() {
+    d_win.release(); d_carry.release(); d_tw.release(); d_ppsd.release(); d_open_psd.release(); d_ring_psd.release();
+    d_phist.release(); d_open_hist.release(); d_ring_hist.release(); d_prec.release(); d_open_rec.release(); d_ring_rec.release();
+  }
+};
+// both monitors' kernels (k_mon_seg<Src>, k_mon_reduce<Src>) as seg_stage takes them
+using MonSegFn = decltype(&k_mon_seg<MonMpxSrc>);
+using MonReduceFn = decltype(&k_mon_reduce<MonMpxSrc>);
+
+}  // namespace
 
 // Diagnostic switches from the environment, read ONCE when a chain is created (INTEGRATION.md section 4 lists them);
 // nothing on the call path touches the environment.
@@ -333,45 +418,21 @@ struct fmr_chain {
   void rds_drain();
   // ---- modulation monitor (fmr_enable_monitor; kernels_monitor.hpp).  A second reader of the
   // call's MPX at the head of the audio tail, beside the RDS stage: it carries the stream's last unconsumed samples in a
-  // buffer of its own and counts in absolute samples (mon_n), so H_b and the cut into calls do not matter.  Nothing of it
+  // buffer of its own and counts in absolute samples (mon.n), so H_b and the cut into calls do not matter.  Nothing of it
   // exists on a chain that never enabled it.
-  bool mon = false;
+  // ---- RF monitor (fmr_enable_rf_monitor; kernels_rfmon.hpp, DESIGN.md section 13).  A second reader of the call's IF
+  // ring slot (the decoder's input, or |x|^2 behind a discriminator epilogue), beside the modulation monitor: a second
+  // instance of the same engine (SegMonitor) behind the same stage routine.  Nothing of it exists on a chain that never
+  // enabled it.
+  SegMonitor mon, rfm;
   fmr_monitor_config mon_cfg{};              // the defaults filled in
-  int mon_spr = 0, mon_sub_n = 0, mon_sb = 0, mon_rmax = 0;   // segments per record / per sub-block, sub-blocks per record, runs per stream and launch
-  int mon_par = 0;                           // which copy of the open records is current
-  double mon_sumw2 = 0.0;
-  long long mon_n = 0, mon_next_seg = 0;     // MPX samples seen, segments processed
-  DevBuf<float> d_mon_win, d_mon_carry;
-  DevBuf<float2> d_mon_tw;
-  DevBuf<double> d_mon_ppsd, d_mon_open_psd, d_mon_ring_psd;
-  DevBuf<unsigned> d_mon_phist, d_mon_open_hist, d_mon_ring_hist;
-  DevBuf<MonRec> d_mon_prec, d_mon_open_rec, d_mon_ring_rec;
-  std::vector<unsigned long long> mon_read, mon_dropped;   // per stream: next unread record, records overwritten unread
-  int mon_init(const fmr_monitor_config &m);
-  int mon_stage(const fm_mpx_t *base, long long N, hipStream_t st);
-  void mon_catch_up(int s);
+  fmr_rf_monitor_config rfm_cfg{};
+  // one call's N samples per stream through monitor m on stream st: the source as kseg / kreduce read it (from, stride, off)
+  int seg_stage(SegMonitor &m, const void *from, long long stride, int off, float rf, float scale, MonSegFn kseg,
+                MonReduceFn kreduce, const char *seg_name, const char *reduce_name, long long N, hipStream_t st);
   // ---- audio monitor (fmr_enable_loudness; kernels_loudness.hpp).  A reader of the call's finished
   // audio behind the output mux, on the tail's stream: it counts in absolute audio samples (ld_n) and keeps its own
   // carries (the K-weighting state, the true-peak history, the open record).  Nothing of it exists unless it is enabled.
-  // ---- RF monitor (fmr_enable_rf_monitor; kernels_rfmon.hpp, DESIGN.md section 13).  A second reader of the call's IF
-  // ring slot (the decoder's input, or |x|^2 behind a discriminator epilogue) at the head of the audio tail, beside the RDS
-  // stage and the modulation monitor, whose partition, launches and ring it shares.  Nothing of it exists on a chain that
-  // never enabled it.
-  bool rfm = false;
-  fmr_rf_monitor_config rfm_cfg{};           // the defaults filled in
-  int rfm_spr = 0, rfm_sub_n = 0, rfm_sb = 0, rfm_rmax = 0;
-  int rfm_par = 0;
-  double rfm_sumw2 = 0.0;
-  long long rfm_n = 0, rfm_next_seg = 0;     // IF samples seen, segments processed
-  DevBuf<float> d_rfm_win, d_rfm_carry;
-  DevBuf<float2> d_rfm_tw;
-  DevBuf<double> d_rfm_ppsd, d_rfm_open_psd, d_rfm_ring_psd;
-  DevBuf<unsigned> d_rfm_phist, d_rfm_open_hist, d_rfm_ring_hist;
-  DevBuf<MonRec> d_rfm_prec, d_rfm_open_rec, d_rfm_ring_rec;
-  std::vector<unsigned long long> rfm_read, rfm_dropped;
-  int rfm_init(const fmr_rf_monitor_config &m);
-  int rfm_stage(const float2 *slot, bool is_nrm, long long N, hipStream_t st);
-  void rfm_catch_up(int s);
   bool ld = false;
   fmr_loudness_config ld_cfg{};              // the defaults filled in
   int ld_cps = 0, ld_rmax = 0, ld_par = 0;   // chunks per sub-block, runs per stream and launch, current copy of the open records
@@ -380,10 +441,10 @@ struct fmr_chain {
   DevBuf<double> d_ld_pw, d_ld_taps, d_ld_G, d_ld_start, d_ld_pkw, d_ld_state, d_ld_hist;
   DevBuf<LdPart> d_ld_part;
   DevBuf<LdRec> d_ld_open, d_ld_ring;
-  std::vector<unsigned long long> ld_read, ld_dropped;     // per stream: next unread record, records overwritten unread
+  RecCursor ld_cur;
+  unsigned long long ld_done() const { return (unsigned long long)(ld_n / (long long)ld_cfg.step_samples); }   // records complete
   int ld_init(const fmr_loudness_config &m);
   int ld_stage(const double *d_aud, long long astride, long long N, hipStream_t st);
-  void ld_catch_up(int s);
   int in_rows() const { return bank ? 1 : S; }   // rows of the input buffers (d_in, d_in_halo)
   // front end only (fmr_resample_blocks_device): stage B writes row s of this call's IF samples to if_out + s if_out_stride
   // instead of the chain's IF buffer (nullptr: the IF buffer)
@@ -489,14 +550,9 @@ struct fmr_chain {
     d_cb_taps.release(); d_cb_ph.release();
     d_rds_h1.release(); d_rds_h2.release(); d_rds_xhalo.release(); d_rds_lo.release(); d_rds_y1.release(); d_rds_y2.release();
     d_rds_state.release(); d_rds_est.release(); d_rds_rec.release();
-    d_mon_win.release(); d_mon_carry.release(); d_mon_tw.release(); d_mon_ppsd.release(); d_mon_open_psd.release();
-    d_mon_ring_psd.release(); d_mon_phist.release(); d_mon_open_hist.release(); d_mon_ring_hist.release();
-    d_mon_prec.release(); d_mon_open_rec.release(); d_mon_ring_rec.release();
+    mon.release(); rfm.release();
     d_ld_pw.release(); d_ld_taps.release(); d_ld_G.release(); d_ld_start.release(); d_ld_pkw.release(); d_ld_state.release();
     d_ld_hist.release(); d_ld_part.release(); d_ld_open.release(); d_ld_ring.release();
-    d_rfm_win.release(); d_rfm_carry.release(); d_rfm_tw.release(); d_rfm_ppsd.release(); d_rfm_open_psd.release();
-    d_rfm_ring_psd.release(); d_rfm_phist.release(); d_rfm_open_hist.release(); d_rfm_ring_hist.release();
-    d_rfm_prec.release(); d_rfm_open_rec.release(); d_rfm_ring_rec.release();
     if (h_rds_slots) (void)hipHostFree(h_rds_slots);
     if (h_rds_mark) (void)hipHostFree(h_rds_mark);
     if (h_tab_all) (void)hipHostFree(h_tab_all);
@@ -2682,8 +2738,17 @@ void fmr_chain::tail_channels(const TailCtx &t, hipStream_t st, int ch_base, int
 // node pass, the output mux, and the joins with what ran beside the decoder stream (statistics, AGC, lock logic).
 int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
   if (rds) if (int rc = rds_stage(t.base, t.N_if, ts)) return rc;
-  if (mon) if (int rc = mon_stage(t.base, t.N_if, ts)) return rc;
-  if (rfm) if (int rc = rfm_stage(t.ifbuf, t.if_nrm, t.N_if, ts)) return rc;
+  if (mon.on)
+    if (int rc = seg_stage(mon, t.base, H_b + (long long)max_if, H_b, (float)mon_cfg.hist_range,
+                           (float)((double)mon_cfg.hist_bins / (2.0 * mon_cfg.hist_range)), k_mon_seg<MonMpxSrc>,
+                           k_mon_reduce<MonMpxSrc>, "mon_seg", "mon_reduce", t.N_if, ts))
+      return rc;
+  if (rfm.on)      // (the IF ring slot holds IF samples, or |x|^2 when if_nrm; the integer bin rule takes no range)
+    if (int rc = seg_stage(rfm, t.ifbuf, H_if + (long long)max_if, H_if, 0.f, 0.f,
+                           t.if_nrm ? k_mon_seg<RfmSrc<true>> : k_mon_seg<RfmSrc<false>>,
+                           t.if_nrm ? k_mon_reduce<RfmSrc<true>> : k_mon_reduce<RfmSrc<false>>, "rfm_seg", "rfm_reduce",
+                           t.N_if, ts))
+      return rc;
   const int nch = t.nch, dc_nc = t.dc_nc;
   const long long N_au = t.N_au;
   if (t.mono_enqueued) tail_channels(t, ts, 1, 1);
@@ -2821,50 +2886,54 @@ int fmr_chain::rds_stage(const fm_mpx_t *base, long long N, hipStream_t st) {
   return FMR_OK;
 }
 
-// ---- modulation monitor (kernels_monitor.hpp) ----
-int fmr_chain::mon_init(const fmr_monitor_config &m) {
+// ---- modulation monitor and RF monitor (kernels_monitor.hpp, kernels_rfmon.hpp) ----
+int SegMonitor::init(int S, size_t max_if, unsigned interval_samples, int hist_bins, int max_records) {
   static_assert(sizeof(MonRec) == sizeof(fmr_monitor_record), "MonRec is fmr_monitor_record");
-  mon_cfg = m;
-  mon_spr = (int)(m.interval_samples / kMonH);
+  static_assert(sizeof(MonRec) == sizeof(fmr_rf_monitor_record), "MonRec is fmr_rf_monitor_record");
+  static_assert(offsetof(fmr_monitor_record, segments) == offsetof(MonRec, segments) &&
+                offsetof(fmr_rf_monitor_record, segments) == offsetof(MonRec, segments), "the segment count of a record");
+  static_assert(kRfmBins == FMR_RF_HIST_BINS && kMonPsd == FMR_RF_PSD_BINS, "the header's sizes");
+  interval = interval_samples;
+  bins = hist_bins;
+  spr = (int)(interval / kMonH);
   // a full call in about 512 runs per stream: sub-blocks of 4 .. 32 segments (a run is a workgroup's serial work, and the
   // partition only moves the fp64 rounding of the sums)
   const size_t max_seg = max_if / kMonH + 2;
-  mon_sub_n = (int)std::min<size_t>(kMonSubMax, std::max<size_t>(kMonSubMin, (max_seg + 511) / 512));
-  mon_sb = (mon_spr + mon_sub_n - 1) / mon_sub_n;
-  mon_rmax = (int)std::min<size_t>(1024, max_seg / mon_sub_n + 2 * (max_seg / mon_spr + 2) + 2);
+  sub = (int)std::min<size_t>(kMonSubMax, std::max<size_t>(kMonSubMin, (max_seg + 511) / 512));
+  sb = (spr + sub - 1) / sub;
+  rmax = (int)std::min<size_t>(1024, max_seg / sub + 2 * (max_seg / spr + 2) + 2);
   std::vector<float> w(kMonN);
   std::vector<float2> tw(kMonN);
-  mon_sumw2 = 0.0;
+  sumw2 = 0.0;
   for (int i = 0; i < kMonN; i++) {
     w[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / kMonN));
-    mon_sumw2 += (double)w[i] * (double)w[i];
+    sumw2 += (double)w[i] * (double)w[i];
     tw[i] = make_float2((float)std::cos(2.0 * M_PI * i / kMonN), (float)-std::sin(2.0 * M_PI * i / kMonN));
   }
-  const size_t B = (size_t)m.hist_bins, L = (size_t)m.max_records, rows = (size_t)S * mon_rmax;
+  const size_t B = (size_t)bins, L = (size_t)max_records, rows = (size_t)S * rmax;
   int rc;
-  if ((rc = upload(d_mon_win, w.data(), w.size()))) return rc;
-  if ((rc = upload(d_mon_tw, tw.data(), tw.size()))) return rc;
-  if ((rc = d_mon_carry.alloc((size_t)S * kMonN))) return rc;
-  if ((rc = d_mon_ppsd.alloc(rows * kMonPsd))) return rc;
-  if ((rc = d_mon_phist.alloc(rows * B))) return rc;
-  if ((rc = d_mon_prec.alloc(rows))) return rc;
-  if ((rc = d_mon_open_psd.alloc(2 * (size_t)S * kMonPsd))) return rc;
-  if ((rc = d_mon_open_hist.alloc(2 * (size_t)S * B))) return rc;
-  if ((rc = d_mon_open_rec.alloc(2 * (size_t)S))) return rc;
-  if ((rc = d_mon_ring_psd.alloc((size_t)S * L * kMonPsd))) return rc;
-  if ((rc = d_mon_ring_hist.alloc((size_t)S * L * B))) return rc;
-  if ((rc = d_mon_ring_rec.alloc((size_t)S * L))) return rc;
-  mon_read.assign(S, 0);
-  mon_dropped.assign(S, 0);
-  mon_n = mon_next_seg = 0;
-  mon_par = 0;
-  mon = true;
+  if ((rc = upload(d_win, w.data(), w.size()))) return rc;
+  if ((rc = upload(d_tw, tw.data(), tw.size()))) return rc;
+  if ((rc = d_carry.alloc((size_t)S * kMonN))) return rc;
+  if ((rc = d_ppsd.alloc(rows * kMonPsd))) return rc;
+  if ((rc = d_phist.alloc(rows * B))) return rc;
+  if ((rc = d_prec.alloc(rows))) return rc;
+  if ((rc = d_open_psd.alloc(2 * (size_t)S * kMonPsd))) return rc;
+  if ((rc = d_open_hist.alloc(2 * (size_t)S * B))) return rc;
+  if ((rc = d_open_rec.alloc(2 * (size_t)S))) return rc;
+  if ((rc = d_ring_psd.alloc((size_t)S * L * kMonPsd))) return rc;
+  if ((rc = d_ring_hist.alloc((size_t)S * L * B))) return rc;
+  if ((rc = d_ring_rec.alloc((size_t)S * L))) return rc;
+  cur.reset(S, max_records);
+  n = next_seg = 0;
+  par = 0;
+  on = true;
   return FMR_OK;
 }
 
-// The next launch of a monitor's stage (modulation and RF monitor): the segments [j, a.a1) of the call's [j, j_hi) that
-// fit into rmax runs per stream, the runs and the records they touch.  j >= j_hi: no segment is left (runs = 0, one block
-// per stream for the carry).
+// The next launch of a monitor's stage: the segments [j, a.a1) of the call's [j, j_hi) that fit into rmax runs per
+// stream, the runs and the records they touch.  j >= j_hi: no segment is left (runs = 0, one block per stream for the
+// carry).
 static void mon_plan_launch(MonArgs &a, long long j, long long j_hi, int rmax, int &runs, int &nrec) {
   runs = 0; nrec = 1;
   a.a0 = a.a1 = j; a.g0 = 0;
@@ -2879,138 +2948,40 @@ static void mon_plan_launch(MonArgs &a, long long j, long long j_hi, int rmax, i
   nrec = (int)(l_end - l + 1);
 }
 
-// one call's MPX (N samples per stream from the base slot) through the monitor, on stream st: the segments whose last
-// sample the call delivers, in launches of at most mon_rmax runs per stream, then the carry
-int fmr_chain::mon_stage(const fm_mpx_t *base, long long N, hipStream_t st) {
+// One call's samples (N per stream: the MPX in the base slot, or the decoder's input in the IF ring slot) through monitor
+// m, on stream st: the segments whose last sample the call delivers, in launches of at most m.rmax runs per stream, then
+// the carry.
+int fmr_chain::seg_stage(SegMonitor &m, const void *from, long long stride, int off, float rf, float scale, MonSegFn kseg,
+                         MonReduceFn kreduce, const char *seg_name, const char *reduce_name, long long N, hipStream_t st) {
   if (N <= 0) return FMR_OK;
-  const long long base_stride = H_b + (long long)max_if;
-  const long long n0 = mon_n, n1 = n0 + N;
+  const long long n0 = m.n, n1 = n0 + N;
   const long long j_hi = n1 >= kMonN ? (n1 - kMonN) / kMonH + 1 : 0;
   MonArgs a{};
-  a.n0 = n0; a.spr = mon_spr; a.sub = mon_sub_n; a.sb = mon_sb; a.bins = mon_cfg.hist_bins;
-  a.rf = (float)mon_cfg.hist_range; a.scale = (float)((double)mon_cfg.hist_bins / (2.0 * mon_cfg.hist_range));
-  const int L = mon_cfg.max_records;
-  const long long M = (long long)mon_cfg.interval_samples;
-  long long j = mon_next_seg;
+  a.n0 = n0; a.spr = m.spr; a.sub = m.sub; a.sb = m.sb; a.bins = m.bins;
+  a.rf = rf; a.scale = scale;
+  const int L = (int)m.cur.L;
+  const long long M = (long long)m.interval;
+  long long j = m.next_seg;
   do {
     int runs, nrec;
-    mon_plan_launch(a, j, j_hi, mon_rmax, runs, nrec);
+    mon_plan_launch(a, j, j_hi, m.rmax, runs, nrec);
     if (runs > 0)
-      timed_on(st, "mon_seg", [&] {
-        hipLaunchKernelGGL(k_mon_seg, dim3(runs, S), dim3(kMonT), 0, st, base, base_stride, H_b, d_mon_carry.p, a,
-                           d_mon_win.p, d_mon_tw.p, mon_rmax, d_mon_ppsd.p, d_mon_phist.p, d_mon_prec.p);
+      timed_on(st, seg_name, [&] {
+        hipLaunchKernelGGL(kseg, dim3(runs, S), dim3(kMonT), 0, st, from, stride, off, m.d_carry.p, a, m.d_win.p, m.d_tw.p,
+                           m.rmax, m.d_ppsd.p, m.d_phist.p, m.d_prec.p);
       });
     j = a.a1;
-    timed_on(st, "mon_reduce", [&] {
-      hipLaunchKernelGGL(k_mon_reduce, dim3(nrec, S), dim3(kMonT), 0, st, d_mon_ppsd.p, d_mon_phist.p, d_mon_prec.p, runs,
-                         mon_rmax, a, L, M, mon_par, d_mon_open_psd.p, d_mon_open_hist.p, d_mon_open_rec.p, d_mon_ring_psd.p,
-                         d_mon_ring_hist.p, d_mon_ring_rec.p, base, base_stride, H_b, d_mon_carry.p, n1, (int)(j >= j_hi));
+    timed_on(st, reduce_name, [&] {
+      hipLaunchKernelGGL(kreduce, dim3(nrec, S), dim3(kMonT), 0, st, m.d_ppsd.p, m.d_phist.p, m.d_prec.p, runs, m.rmax, a, L,
+                         M, m.par, m.d_open_psd.p, m.d_open_hist.p, m.d_open_rec.p, m.d_ring_psd.p, m.d_ring_hist.p,
+                         m.d_ring_rec.p, from, stride, off, m.d_carry.p, n1, (int)(j >= j_hi));
     });
-    if (runs > 0) mon_par ^= 1;
+    if (runs > 0) m.par ^= 1;
   } while (j < j_hi);
-  mon_next_seg = std::max(mon_next_seg, j_hi);
-  mon_n = n1;
+  m.next_seg = std::max(m.next_seg, j_hi);
+  m.n = n1;
   HIPCHK(hipGetLastError());
   return FMR_OK;
-}
-
-// records the ring has overwritten unread: the read position follows, the loss is counted
-void fmr_chain::mon_catch_up(int s) {
-  const unsigned long long done = (unsigned long long)(mon_next_seg / mon_spr), L = (unsigned long long)mon_cfg.max_records;
-  if (done > L && mon_read[s] < done - L) {
-    mon_dropped[s] += done - L - mon_read[s];
-    mon_read[s] = done - L;
-  }
-}
-
-// ---- RF monitor (kernels_rfmon.hpp) ----
-int fmr_chain::rfm_init(const fmr_rf_monitor_config &m) {
-  static_assert(sizeof(MonRec) == sizeof(fmr_rf_monitor_record), "MonRec is fmr_rf_monitor_record");
-  static_assert(kRfmBins == FMR_RF_HIST_BINS && kMonPsd == FMR_RF_PSD_BINS, "the header's sizes");
-  rfm_cfg = m;
-  rfm_spr = (int)(m.interval_samples / kMonH);
-  // the modulation monitor's partition: a full call in about 512 runs per stream, sub-blocks of 4 .. 32 segments
-  const size_t max_seg = max_if / kMonH + 2;
-  rfm_sub_n = (int)std::min<size_t>(kMonSubMax, std::max<size_t>(kMonSubMin, (max_seg + 511) / 512));
-  rfm_sb = (rfm_spr + rfm_sub_n - 1) / rfm_sub_n;
-  rfm_rmax = (int)std::min<size_t>(1024, max_seg / rfm_sub_n + 2 * (max_seg / rfm_spr + 2) + 2);
-  std::vector<float> w(kMonN);
-  std::vector<float2> tw(kMonN);
-  rfm_sumw2 = 0.0;
-  for (int i = 0; i < kMonN; i++) {
-    w[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / kMonN));
-    rfm_sumw2 += (double)w[i] * (double)w[i];
-    tw[i] = make_float2((float)std::cos(2.0 * M_PI * i / kMonN), (float)-std::sin(2.0 * M_PI * i / kMonN));
-  }
-  const size_t B = (size_t)kRfmBins, L = (size_t)m.max_records, rows = (size_t)S * rfm_rmax;
-  int rc;
-  if ((rc = upload(d_rfm_win, w.data(), w.size()))) return rc;
-  if ((rc = upload(d_rfm_tw, tw.data(), tw.size()))) return rc;
-  if ((rc = d_rfm_carry.alloc((size_t)S * kMonN))) return rc;
-  if ((rc = d_rfm_ppsd.alloc(rows * kMonPsd))) return rc;
-  if ((rc = d_rfm_phist.alloc(rows * B))) return rc;
-  if ((rc = d_rfm_prec.alloc(rows))) return rc;
-  if ((rc = d_rfm_open_psd.alloc(2 * (size_t)S * kMonPsd))) return rc;
-  if ((rc = d_rfm_open_hist.alloc(2 * (size_t)S * B))) return rc;
-  if ((rc = d_rfm_open_rec.alloc(2 * (size_t)S))) return rc;
-  if ((rc = d_rfm_ring_psd.alloc((size_t)S * L * kMonPsd))) return rc;
-  if ((rc = d_rfm_ring_hist.alloc((size_t)S * L * B))) return rc;
-  if ((rc = d_rfm_ring_rec.alloc((size_t)S * L))) return rc;
-  rfm_read.assign(S, 0);
-  rfm_dropped.assign(S, 0);
-  rfm_n = rfm_next_seg = 0;
-  rfm_par = 0;
-  rfm = true;
-  return FMR_OK;
-}
-
-// one call's decoder input (N samples per stream in the call's IF ring slot: IF samples, or |x|^2 when is_nrm) through
-// the RF monitor, on stream st; the launches of mon_stage
-int fmr_chain::rfm_stage(const float2 *slot, bool is_nrm, long long N, hipStream_t st) {
-  if (N <= 0) return FMR_OK;
-  const long long if_stride = H_if + (long long)max_if;
-  const long long n0 = rfm_n, n1 = n0 + N;
-  const long long j_hi = n1 >= kMonN ? (n1 - kMonN) / kMonH + 1 : 0;
-  MonArgs a{};
-  a.n0 = n0; a.spr = rfm_spr; a.sub = rfm_sub_n; a.sb = rfm_sb; a.bins = kRfmBins;
-  const int L = rfm_cfg.max_records;
-  const long long M = (long long)rfm_cfg.interval_samples;
-  long long j = rfm_next_seg;
-  do {
-    int runs, nrec;
-    mon_plan_launch(a, j, j_hi, rfm_rmax, runs, nrec);
-    if (runs > 0)
-      timed_on(st, "rfm_seg", [&] {
-        auto go = [&](auto kern) {
-          hipLaunchKernelGGL(kern, dim3(runs, S), dim3(kMonT), 0, st, (const void *)slot, if_stride, H_if, d_rfm_carry.p, a,
-                             d_rfm_win.p, d_rfm_tw.p, rfm_rmax, d_rfm_ppsd.p, d_rfm_phist.p, d_rfm_prec.p);
-        };
-        if (is_nrm) go(k_rfm_seg<true>); else go(k_rfm_seg<false>);
-      });
-    j = a.a1;
-    timed_on(st, "rfm_reduce", [&] {
-      auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(nrec, S), dim3(kMonT), 0, st, d_rfm_ppsd.p, d_rfm_phist.p, d_rfm_prec.p, runs, rfm_rmax,
-                           a, L, M, rfm_par, d_rfm_open_psd.p, d_rfm_open_hist.p, d_rfm_open_rec.p, d_rfm_ring_psd.p,
-                           d_rfm_ring_hist.p, d_rfm_ring_rec.p, (const void *)slot, if_stride, H_if, d_rfm_carry.p, n1,
-                           (int)(j >= j_hi));
-      };
-      if (is_nrm) go(k_rfm_reduce<true>); else go(k_rfm_reduce<false>);
-    });
-    if (runs > 0) rfm_par ^= 1;
-  } while (j < j_hi);
-  rfm_next_seg = std::max(rfm_next_seg, j_hi);
-  rfm_n = n1;
-  HIPCHK(hipGetLastError());
-  return FMR_OK;
-}
-
-void fmr_chain::rfm_catch_up(int s) {
-  const unsigned long long done = (unsigned long long)(rfm_next_seg / rfm_spr), L = (unsigned long long)rfm_cfg.max_records;
-  if (done > L && rfm_read[s] < done - L) {
-    rfm_dropped[s] += done - L - rfm_read[s];
-    rfm_read[s] = done - L;
-  }
 }
 
 // ---- audio monitor (kernels_loudness.hpp) ----
@@ -3063,8 +3034,7 @@ int fmr_chain::ld_init(const fmr_loudness_config &m) {
   if ((rc = d_ld_hist.alloc((size_t)S * 2 * kLdHist))) return rc;
   if ((rc = d_ld_open.alloc(2 * (size_t)S))) return rc;
   if ((rc = d_ld_ring.alloc((size_t)S * L))) return rc;
-  ld_read.assign(S, 0);
-  ld_dropped.assign(S, 0);
+  ld_cur.reset(S, m.max_records);
   ld_n = 0;
   ld_par = 0;
   ld = true;
@@ -3113,15 +3083,6 @@ int fmr_chain::ld_stage(const double *d_aud, long long astride, long long N, hip
   ld_n = n1;
   HIPCHK(hipGetLastError());
   return FMR_OK;
-}
-
-// records the ring has overwritten unread: the read position follows, the loss is counted
-void fmr_chain::ld_catch_up(int s) {
-  const unsigned long long done = (unsigned long long)(ld_n / (long long)ld_cfg.step_samples), L = (unsigned long long)ld_cfg.max_records;
-  if (done > L && ld_read[s] < done - L) {
-    ld_dropped[s] += done - L - ld_read[s];
-    ld_read[s] = done - L;
-  }
 }
 
 // the filled slots, in call order, through the host decoders (never blocks)
@@ -3297,11 +3258,10 @@ struct fmr_spectrum {
   DevBuf<float> d_plsub, d_wopen, d_wline, d_wring;
   DevBuf<int> d_plcnt, d_wopen_cnt, d_wline_cnt;
   DevBuf<unsigned> d_wring_cnt;
-  std::vector<unsigned long long> wf_read, wf_dropped;   // per row: next unread line, lines overwritten unread
+  RecCursor wf_cur;                      // per row: next unread line, lines overwritten unread
   int init();
   int run(const void *d_in, size_t stride, size_t n);
   int run_waterfall(const void *d_in, size_t stride, long long tb, long long ta, long long j_hi);
-  void wf_catch_up(int row);
   ~fmr_spectrum() {
     if (stream) (void)hipStreamSynchronize(stream);
     d_plsub.release(); d_wopen.release(); d_wline.release(); d_wring.release(); d_plcnt.release(); d_wopen_cnt.release();
@@ -3403,16 +3363,9 @@ int wf_check(const fmr_spectrum_config &c, const fmr_waterfall_config &w) {
   return FMR_OK;
 }
 
-// fmr_spectrum_config as the caller knows it (cfg_size, struct_size) -> this library's, zero-filled; then spec_check
+// fmr_spectrum_config as the caller knows it -> this library's; then spec_check
 int spec_take_cfg(const fmr_spectrum_config *cfg, size_t cfg_size, fmr_spectrum_config &full) {
-  const size_t size = cfg_size ? cfg_size : sizeof(fmr_spectrum_config);
-  if (size > sizeof(fmr_spectrum_config) || cfg->struct_size > sizeof(fmr_spectrum_config)) {
-    set_err("fmr_spectrum_create: struct_size %zu is larger than this library's fmr_spectrum_config (%zu): the caller is "
-            "newer than the library", std::max(size, (size_t)cfg->struct_size), sizeof(fmr_spectrum_config));
-    return FMR_ERR_BAD_ARG;
-  }
-  memset(&full, 0, sizeof full);
-  memcpy(&full, cfg, size);
+  if (int rc = take_sized("fmr_spectrum_create", "fmr_spectrum_config", cfg, cfg_size, full)) return rc;
   return spec_check(full);
 }
 }  // namespace
@@ -3476,8 +3429,7 @@ int fmr_spectrum::init() {
     if (int rc = d_wline_cnt.alloc((size_t)2 * rows)) return rc;
     if (int rc = d_wring.alloc((size_t)rows * wf.max_lines * N)) return rc;
     if (int rc = d_wring_cnt.alloc((size_t)rows * wf.max_lines)) return rc;
-    wf_read.assign(rows, 0);
-    wf_dropped.assign(rows, 0);
+    wf_cur.reset(rows, wf.max_lines);
   }
   HIPCHK(hipDeviceSynchronize());
   return FMR_OK;
@@ -3541,15 +3493,6 @@ int fmr_spectrum::run_waterfall(const void *d_in, size_t stride, long long tb, l
   return FMR_OK;
 }
 
-// Lines of `row` that completed beyond the ring's depth since the last read were overwritten unread: count them
-void fmr_spectrum::wf_catch_up(int row) {
-  const unsigned long long done = next_seg / (unsigned long long)wf.segments_per_line, L = (unsigned long long)wf.max_lines;
-  if (done > L && wf_read[row] < done - L) {
-    wf_dropped[row] += done - L - wf_read[row];
-    wf_read[row] = done - L;
-  }
-}
-
 static int spectrum_call(fmr_spectrum *s, const void *iq, size_t row_stride, size_t n, bool host, int sync) {
   if (!s || (!iq && n > 0)) { set_err("fmr_spectrum_process: null argument"); return FMR_ERR_BAD_ARG; }
   if (n > s->cfg.max_call_len) {
@@ -3582,6 +3525,51 @@ static int spectrum_call(fmr_spectrum *s, const void *iq, size_t row_stride, siz
 
 // 10 log10 of a power ratio
 static double spec_db(double x) { return 10.0 * std::log10(x); }
+
+// The body of fmr_monitor_read and fmr_rf_monitor_read (Rec = either record, which MonRec is): synchronises, then drains up
+// to cap records of `stream` from m's rings, the PSD sums scaled to densities.  Returns what the C-ABI function returns.
+template <class Rec>
+static int seg_monitor_read(fmr_chain *c, SegMonitor &m, int stream, Rec *recs, uint32_t *hist, double *psd, int cap) {
+  HIPCHK(hipSetDevice(c->cfg.device));
+  if (int rc = c->sync_all()) return rc;
+  const size_t B = (size_t)m.bins, L = (size_t)m.cur.L;
+  const double scale = 1.0 / (kFmRate * m.sumw2);
+  return m.cur.take(stream, m.done(), (unsigned long long)cap, [&](size_t k0, size_t slot, size_t nr) -> int {
+    const size_t at = (size_t)stream * L + slot;
+    HIPCHK(hipMemcpy(recs + k0, m.d_ring_rec.p + at, nr * sizeof(Rec), hipMemcpyDeviceToHost));
+    if (hist) HIPCHK(hipMemcpy(hist + k0 * B, m.d_ring_hist.p + at * B, nr * B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!psd) return FMR_OK;
+    HIPCHK(hipMemcpy(psd + k0 * kMonPsd, m.d_ring_psd.p + at * kMonPsd, nr * kMonPsd * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t k = k0; k < k0 + nr; k++) {
+      const double cnt = (double)recs[k].segments;
+      double *p = psd + k * kMonPsd;
+      for (int i = 0; i < kMonPsd; i++)
+        p[i] = recs[k].segments == 0 ? 0.0 : p[i] / cnt * ((i == 0 || i == kMonPsd - 1) ? 1.0 : 2.0) * scale;
+    }
+    return FMR_OK;
+  });
+}
+
+// The PSDs of n records (psd: n x kMonPsd as read, or null: zeros) pooled, each weighted by its record's segments
+template <class Rec>
+static std::vector<double> mon_pool_psd(const Rec *recs, const double *psd, int n) {
+  std::vector<double> p(kMonPsd, 0.0);
+  unsigned long long seg = 0;
+  for (int i = 0; i < n; i++) {
+    seg += recs[i].segments;
+    if (psd && recs[i].segments > 0)
+      for (int k = 0; k < kMonPsd; k++) p[k] += (double)recs[i].segments * psd[(size_t)i * kMonPsd + k];
+  }
+  if (seg > 0) for (double &v : p) v /= (double)seg;
+  return p;
+}
+// ... and the bins of lo <= f <= hi of it: their mean density (avg), or the power in them
+static double mon_band(const std::vector<double> &p, double lo, double hi, bool avg) {
+  const double df = kFmRate / kMonN;
+  double b = 0.0; int cnt = 0;
+  for (int k = 0; k < kMonPsd; k++) if (k * df >= lo && k * df <= hi) { b += p[k]; cnt++; }
+  return avg ? (cnt ? b / cnt : 0.0) : b * df;
+}
 
 // ============================================================================
 // C-ABI
@@ -3911,7 +3899,7 @@ static int fetch_state(fmr_chain *c) {
 int fmr_get_status_sized(fmr_chain *c, int stream, void *st, size_t st_size) {
   fmr_status full;
   const int rc = fmr_get_status(c, stream, &full);
-  if (rc == FMR_OK && st) memcpy(st, &full, st_size < sizeof full ? st_size : sizeof full);      // never past the caller's struct
+  if (rc == FMR_OK && st && st_size) give_sized(st, st_size, full);      // never past the caller's struct
   return st ? rc : FMR_ERR_BAD_ARG;
 }
 
@@ -4184,21 +4172,14 @@ int fmr_get_rds_status(fmr_chain *c, int stream, fmr_rds_status *st, size_t st_s
   full.timing = h.timing_frac;
   full.carrier_phase = h.theta;
   full.carrier_offset_hz = h.freq_hz;
-  memcpy(st, &full, st_size < sizeof full ? st_size : sizeof full);
+  if (st_size) give_sized(st, st_size, full);
   return FMR_OK;
 }
 
 int fmr_set_rds_correction(fmr_chain *c, const fmr_rds_fec *fec, size_t fec_size) {
   if (!fec) { set_err("fmr_set_rds_correction: fec is null"); return FMR_ERR_BAD_ARG; }
-  const size_t size = fec_size ? fec_size : sizeof(fmr_rds_fec);
-  if (size > sizeof(fmr_rds_fec) || (size >= sizeof(unsigned) && fec->struct_size > sizeof(fmr_rds_fec))) {
-    set_err("fmr_set_rds_correction: struct_size %zu is larger than this library's fmr_rds_fec (%zu): the caller is newer "
-            "than the library", std::max(size, size >= sizeof(unsigned) ? (size_t)fec->struct_size : (size_t)0), sizeof(fmr_rds_fec));
-    return FMR_ERR_BAD_ARG;
-  }
   fmr_rds_fec full;
-  memset(&full, 0, sizeof full);
-  memcpy(&full, fec, size);
+  if (int rc = take_sized("fmr_set_rds_correction", "fmr_rds_fec", fec, fec_size, full)) return rc;
   fmr_rds::Correction k;
   k.mode = full.mode;
   if (full.max_burst) k.max_burst = full.max_burst;
@@ -4234,15 +4215,8 @@ int fmr_set_rds_correction(fmr_chain *c, const fmr_rds_fec *fec, size_t fec_size
 // ---- modulation monitor: C-ABI ----
 int fmr_enable_monitor(fmr_chain *c, const fmr_monitor_config *cfg, size_t cfg_size) {
   if (!cfg) { set_err("fmr_enable_monitor: cfg is null"); return FMR_ERR_BAD_ARG; }
-  const size_t size = cfg_size ? cfg_size : sizeof(fmr_monitor_config);
-  if (size > sizeof(fmr_monitor_config) || (size >= sizeof(unsigned) && cfg->struct_size > sizeof(fmr_monitor_config))) {
-    set_err("fmr_enable_monitor: struct_size %zu is larger than this library's fmr_monitor_config (%zu): the caller is newer "
-            "than the library", std::max(size, size >= sizeof(unsigned) ? (size_t)cfg->struct_size : (size_t)0), sizeof(fmr_monitor_config));
-    return FMR_ERR_BAD_ARG;
-  }
   fmr_monitor_config m;
-  memset(&m, 0, sizeof m);
-  memcpy(&m, cfg, size);
+  if (int rc = take_sized("fmr_enable_monitor", "fmr_monitor_config", cfg, cfg_size, m)) return rc;
   if (m.interval_samples == 0) m.interval_samples = 384000;
   if (m.hist_bins == 0) m.hist_bins = 256;
   if (m.hist_range == 0.0) m.hist_range = 2.0;
@@ -4269,117 +4243,76 @@ int fmr_enable_monitor(fmr_chain *c, const fmr_monitor_config *cfg, size_t cfg_s
             c->mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no MPX" : "has no MPX");
     return FMR_ERR_UNSUPPORTED;
   }
-  if (c->mon) { set_err("fmr_enable_monitor: the monitor of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
+  if (c->mon.on) { set_err("fmr_enable_monitor: the monitor of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
   if (c->call_seq != 0) {
     set_err("fmr_enable_monitor: the chain has already taken samples (the monitor counts from the chain's first MPX sample)");
     return FMR_ERR_BAD_ARG;
   }
   try {
     HIPCHK(hipSetDevice(c->cfg.device));
-    return c->mon_init(m);
+    c->mon_cfg = m;
+    return c->mon.init(c->S, c->max_if, m.interval_samples, m.hist_bins, m.max_records);
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
 int fmr_monitor_read(fmr_chain *c, int stream, fmr_monitor_record *recs, uint32_t *hist, double *psd, int cap,
                      fmr_monitor_info *info, size_t info_size) {
   if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_monitor_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
-  if (!c->mon) { set_err("fmr_monitor_read: the chain has no monitor (fmr_enable_monitor)"); return FMR_ERR_BAD_ARG; }
+  if (!c->mon.on) { set_err("fmr_monitor_read: the chain has no monitor (fmr_enable_monitor)"); return FMR_ERR_BAD_ARG; }
   if (cap > 0 && !recs) { set_err("fmr_monitor_read: recs is null"); return FMR_ERR_BAD_ARG; }
   try {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    if (int rc = c->sync_all()) return rc;
-    const size_t B = (size_t)c->mon_cfg.hist_bins;
-    const unsigned long long L = (unsigned long long)c->mon_cfg.max_records;
-    const unsigned long long done = (unsigned long long)(c->mon_next_seg / c->mon_spr);
-    c->mon_catch_up(stream);
-    const unsigned long long first = c->mon_read[stream], ready = done - first;
-    const size_t n = (size_t)std::min<unsigned long long>(ready, (unsigned long long)cap);
-    for (size_t k = 0; k < n;) {       // the ring slots first % L .. in at most two contiguous pieces
-      const size_t slot = (size_t)((first + k) % L), m = std::min(n - k, (size_t)L - slot), at = (size_t)stream * L + slot;
-      HIPCHK(hipMemcpy(recs + k, c->d_mon_ring_rec.p + at, m * sizeof(fmr_monitor_record), hipMemcpyDeviceToHost));
-      if (hist) HIPCHK(hipMemcpy(hist + k * B, c->d_mon_ring_hist.p + at * B, m * B * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      if (psd) HIPCHK(hipMemcpy(psd + k * kMonPsd, c->d_mon_ring_psd.p + at * kMonPsd, m * kMonPsd * sizeof(double), hipMemcpyDeviceToHost));
-      k += m;
-    }
-    if (psd) {
-      const double scale = 1.0 / (kFmRate * c->mon_sumw2);
-      for (size_t k = 0; k < n; k++) {
-        const double cnt = (double)recs[k].segments;
-        double *p = psd + k * kMonPsd;
-        for (int i = 0; i < kMonPsd; i++)
-          p[i] = recs[k].segments == 0 ? 0.0 : p[i] / cnt * ((i == 0 || i == kMonPsd - 1) ? 1.0 : 2.0) * scale;
-      }
-    }
-    c->mon_read[stream] = first + n;
-    if (info) {
+    const int n = seg_monitor_read(c, c->mon, stream, recs, hist, psd, cap);
+    if (n >= 0 && info) {
       fmr_monitor_info full{};
       full.struct_size = (unsigned)sizeof full;
       full.hist_bins = c->mon_cfg.hist_bins;
       full.psd_bins = kMonPsd;
-      full.records_complete = done;
-      full.records_dropped = c->mon_dropped[stream];
-      full.first_unread = c->mon_read[stream];
-      full.records_ready = done - c->mon_read[stream];
+      full.records_complete = c->mon.done();
+      full.records_dropped = c->mon.cur.dropped[stream];
+      full.first_unread = c->mon.cur.read[stream];
+      full.records_ready = c->mon.done() - c->mon.cur.read[stream];
       full.interval_samples = c->mon_cfg.interval_samples;
       full.max_records = c->mon_cfg.max_records;
       full.hist_range = c->mon_cfg.hist_range;
       full.bin_hz = kFmRate / kMonN;
-      const size_t isz = info_size ? info_size : sizeof full;
-      memcpy(info, &full, isz < sizeof full ? isz : sizeof full);
+      give_sized(info, info_size, full);
     }
-    return cap == 0 ? (int)std::min<unsigned long long>(ready, (unsigned long long)INT_MAX) : (int)n;
+    return n;
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
 int fmr_monitor_derive(const fmr_monitor_record *recs, const double *psd, int n, fmr_monitor_levels *out, size_t out_size) {
   if (!recs || !out || n < 1) { set_err("fmr_monitor_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
-  const double F = kFmRate, df = F / kMonN;
   double sum = 0.0, sumsq = 0.0, mn = INFINITY, mx = -INFINITY;
   unsigned long long nf = 0, seg = 0;
-  std::vector<double> p(kMonPsd, 0.0);
   for (int i = 0; i < n; i++) {
     const fmr_monitor_record &r = recs[i];
     sum += r.sum; sumsq += r.sumsq; nf += r.n_finite; seg += r.segments;
     if (r.n_finite > 0) { mn = std::min(mn, (double)r.min); mx = std::max(mx, (double)r.max); }
-    if (psd && r.segments > 0)
-      for (int k = 0; k < kMonPsd; k++) p[k] += (double)r.segments * psd[(size_t)i * kMonPsd + k];
   }
-  if (seg > 0) for (double &v : p) v /= (double)seg;
+  const std::vector<double> p = mon_pool_psd(recs, psd, n);
   const double mean = nf ? sum / (double)nf : 0.0;
   const double var = nf ? sumsq / (double)nf - mean * mean : 0.0;
-  auto band = [&](double lo, double hi, bool avg) {
-    double b = 0.0; int cnt = 0;
-    for (int k = 0; k < kMonPsd; k++) if (k * df >= lo && k * df <= hi) { b += p[k]; cnt++; }
-    return avg ? (cnt ? b / cnt : 0.0) : b * df;
-  };
   fmr_monitor_levels full{};
   full.struct_size = (unsigned)sizeof full;
   full.tuning_offset_hz = 75000.0 * mean;
   full.peak_deviation_hz = nf ? 75000.0 * std::max(mx - mean, mean - mn) : 0.0;
   full.rms = var > 0.0 ? std::sqrt(var) : 0.0;
   full.mpx_power_dbr = var > 0.0 ? 10.0 * std::log10(2.0 * (75.0 / 19.0) * (75.0 / 19.0) * var) : -INFINITY;
-  full.pilot_deviation_hz = 75000.0 * std::sqrt(2.0 * band(17875.0, 20125.0, false));
-  full.rds_deviation_hz = 75000.0 * std::sqrt(2.0 * band(54600.0, 59400.0, false));
-  full.hf_noise_density = band(100000.0, 150000.0, true);
+  full.pilot_deviation_hz = 75000.0 * std::sqrt(2.0 * mon_band(p, 17875.0, 20125.0, false));
+  full.rds_deviation_hz = 75000.0 * std::sqrt(2.0 * mon_band(p, 54600.0, 59400.0, false));
+  full.hf_noise_density = mon_band(p, 100000.0, 150000.0, true);
   full.n_finite = nf;
   full.segments = seg;
-  const size_t osz = out_size ? out_size : sizeof full;
-  memcpy(out, &full, osz < sizeof full ? osz : sizeof full);
+  give_sized(out, out_size, full);
   return FMR_OK;
 }
 
 // ---- audio monitor: C-ABI ----
 int fmr_enable_loudness(fmr_chain *c, const fmr_loudness_config *cfg, size_t cfg_size) {
   if (!cfg) { set_err("fmr_enable_loudness: cfg is null"); return FMR_ERR_BAD_ARG; }
-  const size_t size = cfg_size ? cfg_size : sizeof(fmr_loudness_config);
-  if (size > sizeof(fmr_loudness_config) || (size >= sizeof(unsigned) && cfg->struct_size > sizeof(fmr_loudness_config))) {
-    set_err("fmr_enable_loudness: struct_size %zu is larger than this library's fmr_loudness_config (%zu): the caller is newer "
-            "than the library", std::max(size, size >= sizeof(unsigned) ? (size_t)cfg->struct_size : (size_t)0), sizeof(fmr_loudness_config));
-    return FMR_ERR_BAD_ARG;
-  }
   fmr_loudness_config m;
-  memset(&m, 0, sizeof m);
-  memcpy(&m, cfg, size);
+  if (int rc = take_sized("fmr_enable_loudness", "fmr_loudness_config", cfg, cfg_size, m)) return rc;
   if (m.step_samples == 0) m.step_samples = 4800;
   if (m.max_records == 0) m.max_records = 1024;
   if (m.step_samples % 16 != 0 || m.step_samples < 48 || m.step_samples > (1u << 20)) {
@@ -4414,31 +4347,26 @@ int fmr_loudness_read(fmr_chain *c, int stream, fmr_loudness_record *recs, int c
   try {
     HIPCHK(hipSetDevice(c->cfg.device));
     if (int rc = c->sync_all()) return rc;
-    const unsigned long long L = (unsigned long long)c->ld_cfg.max_records;
-    const unsigned long long done = (unsigned long long)(c->ld_n / (long long)c->ld_cfg.step_samples);
-    c->ld_catch_up(stream);
-    const unsigned long long first = c->ld_read[stream], ready = done - first;
-    const size_t n = (size_t)std::min<unsigned long long>(ready, (unsigned long long)cap);
-    for (size_t k = 0; k < n;) {       // the ring slots first % L .. in at most two contiguous pieces
-      const size_t slot = (size_t)((first + k) % L), m = std::min(n - k, (size_t)L - slot), at = (size_t)stream * L + slot;
-      HIPCHK(hipMemcpy(recs + k, c->d_ld_ring.p + at, m * sizeof(fmr_loudness_record), hipMemcpyDeviceToHost));
-      k += m;
-    }
-    c->ld_read[stream] = first + n;
+    const unsigned long long done = c->ld_done();
+    const int n = c->ld_cur.take(stream, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
+      HIPCHK(hipMemcpy(recs + k, c->d_ld_ring.p + (size_t)stream * c->ld_cur.L + slot, m * sizeof(fmr_loudness_record),
+                       hipMemcpyDeviceToHost));
+      return FMR_OK;
+    });
+    if (n < 0) return n;
     if (info) {
       fmr_loudness_info full{};
       full.struct_size = (unsigned)sizeof full;
       full.channels = c->stereo ? 2 : 1;
       full.records_complete = done;
-      full.records_dropped = c->ld_dropped[stream];
-      full.first_unread = c->ld_read[stream];
-      full.records_ready = done - c->ld_read[stream];
+      full.records_dropped = c->ld_cur.dropped[stream];
+      full.first_unread = c->ld_cur.read[stream];
+      full.records_ready = done - c->ld_cur.read[stream];
       full.step_samples = c->ld_cfg.step_samples;
       full.max_records = c->ld_cfg.max_records;
-      const size_t isz = info_size ? info_size : sizeof full;
-      memcpy(info, &full, isz < sizeof full ? isz : sizeof full);
+      give_sized(info, info_size, full);
     }
-    return cap == 0 ? (int)std::min<unsigned long long>(ready, (unsigned long long)INT_MAX) : (int)n;
+    return n;
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
@@ -4510,24 +4438,15 @@ int fmr_loudness_derive(const fmr_loudness_record *recs, int n, double silence_d
   full.correlation = den > 0.0 ? slr / std::sqrt(den) : 0.0;
   const double side = sl + sr - 2.0 * slr, mid = sl + sr + 2.0 * slr;
   full.side_to_mid_db = side <= 0.0 && mid <= 0.0 ? 0.0 : side <= 0.0 ? -INFINITY : mid <= 0.0 ? INFINITY : 10.0 * std::log10(side / mid);
-  const size_t osz = out_size ? out_size : sizeof full;
-  memcpy(out, &full, osz < sizeof full ? osz : sizeof full);
+  give_sized(out, out_size, full);
   return FMR_OK;
 }
 
 // ---- RF monitor: C-ABI ----
 int fmr_enable_rf_monitor(fmr_chain *c, const fmr_rf_monitor_config *cfg, size_t cfg_size) {
   if (!cfg) { set_err("fmr_enable_rf_monitor: cfg is null"); return FMR_ERR_BAD_ARG; }
-  const size_t size = cfg_size ? cfg_size : sizeof(fmr_rf_monitor_config);
-  if (size > sizeof(fmr_rf_monitor_config) || (size >= sizeof(unsigned) && cfg->struct_size > sizeof(fmr_rf_monitor_config))) {
-    set_err("fmr_enable_rf_monitor: struct_size %zu is larger than this library's fmr_rf_monitor_config (%zu): the caller is "
-            "newer than the library", std::max(size, size >= sizeof(unsigned) ? (size_t)cfg->struct_size : (size_t)0),
-            sizeof(fmr_rf_monitor_config));
-    return FMR_ERR_BAD_ARG;
-  }
   fmr_rf_monitor_config m;
-  memset(&m, 0, sizeof m);
-  memcpy(&m, cfg, size);
+  if (int rc = take_sized("fmr_enable_rf_monitor", "fmr_rf_monitor_config", cfg, cfg_size, m)) return rc;
   if (m.interval_samples == 0) m.interval_samples = 38400;
   if (m.max_records == 0) m.max_records = 64;
   if (m.interval_samples % kMonH != 0 || m.interval_samples < (uint32_t)kMonH || m.interval_samples > (1u << 30)) {
@@ -4544,91 +4463,58 @@ int fmr_enable_rf_monitor(fmr_chain *c, const fmr_rf_monitor_config *cfg, size_t
             c->mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no decoder" : "is not measured");
     return FMR_ERR_UNSUPPORTED;
   }
-  if (c->rfm) { set_err("fmr_enable_rf_monitor: the RF monitor of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
+  if (c->rfm.on) { set_err("fmr_enable_rf_monitor: the RF monitor of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
   if (c->call_seq != 0) {
     set_err("fmr_enable_rf_monitor: the chain has already taken samples (the RF monitor counts from the chain's first IF sample)");
     return FMR_ERR_BAD_ARG;
   }
   try {
     HIPCHK(hipSetDevice(c->cfg.device));
-    return c->rfm_init(m);
+    c->rfm_cfg = m;
+    return c->rfm.init(c->S, c->max_if, m.interval_samples, kRfmBins, m.max_records);
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
 int fmr_rf_monitor_read(fmr_chain *c, int stream, fmr_rf_monitor_record *recs, uint32_t *hist, double *psd, int cap,
                         fmr_rf_monitor_info *info, size_t info_size) {
   if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_rf_monitor_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
-  if (!c->rfm) { set_err("fmr_rf_monitor_read: the chain has no RF monitor (fmr_enable_rf_monitor)"); return FMR_ERR_BAD_ARG; }
+  if (!c->rfm.on) { set_err("fmr_rf_monitor_read: the chain has no RF monitor (fmr_enable_rf_monitor)"); return FMR_ERR_BAD_ARG; }
   if (cap > 0 && !recs) { set_err("fmr_rf_monitor_read: recs is null"); return FMR_ERR_BAD_ARG; }
   try {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    if (int rc = c->sync_all()) return rc;
-    const size_t B = (size_t)kRfmBins;
-    const unsigned long long L = (unsigned long long)c->rfm_cfg.max_records;
-    const unsigned long long done = (unsigned long long)(c->rfm_next_seg / c->rfm_spr);
-    c->rfm_catch_up(stream);
-    const unsigned long long first = c->rfm_read[stream], ready = done - first;
-    const size_t n = (size_t)std::min<unsigned long long>(ready, (unsigned long long)cap);
-    for (size_t k = 0; k < n;) {       // the ring slots first % L .. in at most two contiguous pieces
-      const size_t slot = (size_t)((first + k) % L), m = std::min(n - k, (size_t)L - slot), at = (size_t)stream * L + slot;
-      HIPCHK(hipMemcpy(recs + k, c->d_rfm_ring_rec.p + at, m * sizeof(fmr_rf_monitor_record), hipMemcpyDeviceToHost));
-      if (hist) HIPCHK(hipMemcpy(hist + k * B, c->d_rfm_ring_hist.p + at * B, m * B * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      if (psd) HIPCHK(hipMemcpy(psd + k * kMonPsd, c->d_rfm_ring_psd.p + at * kMonPsd, m * kMonPsd * sizeof(double), hipMemcpyDeviceToHost));
-      k += m;
-    }
-    if (psd) {
-      const double scale = 1.0 / (kFmRate * c->rfm_sumw2);
-      for (size_t k = 0; k < n; k++) {
-        const double cnt = (double)recs[k].segments;
-        double *p = psd + k * kMonPsd;
-        for (int i = 0; i < kMonPsd; i++)
-          p[i] = recs[k].segments == 0 ? 0.0 : p[i] / cnt * ((i == 0 || i == kMonPsd - 1) ? 1.0 : 2.0) * scale;
-      }
-    }
-    c->rfm_read[stream] = first + n;
-    if (info) {
+    const int n = seg_monitor_read(c, c->rfm, stream, recs, hist, psd, cap);
+    if (n >= 0 && info) {
       fmr_rf_monitor_info full{};
       full.struct_size = (unsigned)sizeof full;
       full.hist_bins = kRfmBins;
       full.psd_bins = kMonPsd;
-      full.records_complete = done;
-      full.records_dropped = c->rfm_dropped[stream];
-      full.first_unread = c->rfm_read[stream];
-      full.records_ready = done - c->rfm_read[stream];
+      full.records_complete = c->rfm.done();
+      full.records_dropped = c->rfm.cur.dropped[stream];
+      full.first_unread = c->rfm.cur.read[stream];
+      full.records_ready = c->rfm.done() - c->rfm.cur.read[stream];
       full.interval_samples = c->rfm_cfg.interval_samples;
       full.max_records = c->rfm_cfg.max_records;
       full.bin_hz = kFmRate / kMonN;
-      const size_t isz = info_size ? info_size : sizeof full;
-      memcpy(info, &full, isz < sizeof full ? isz : sizeof full);
+      give_sized(info, info_size, full);
     }
-    return cap == 0 ? (int)std::min<unsigned long long>(ready, (unsigned long long)INT_MAX) : (int)n;
+    return n;
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
 int fmr_rf_monitor_derive(const fmr_rf_monitor_record *recs, const uint32_t *hist, const double *psd, int n,
                           fmr_rf_monitor_levels *out, size_t out_size) {
   if (!recs || !out || n < 1) { set_err("fmr_rf_monitor_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
-  const double F = kFmRate, df = F / kMonN;
   double m2 = 0.0, m4 = 0.0;
   unsigned long long nf = 0, seg = 0;
-  std::vector<double> p(kMonPsd, 0.0);
   std::vector<unsigned long long> h(kRfmBins, 0ull);
   for (int i = 0; i < n; i++) {
     const fmr_rf_monitor_record &r = recs[i];
     m2 += r.m2; m4 += r.m4; nf += r.n_finite; seg += r.segments;
-    if (psd && r.segments > 0)
-      for (int k = 0; k < kMonPsd; k++) p[k] += (double)r.segments * psd[(size_t)i * kMonPsd + k];
     if (hist)
       for (int b = 0; b < kRfmBins; b++) h[b] += hist[(size_t)i * kRfmBins + b];
   }
-  if (seg > 0) for (double &v : p) v /= (double)seg;
+  const std::vector<double> p = mon_pool_psd(recs, psd, n);
   const double M2 = nf ? m2 / (double)nf : 0.0, M4 = nf ? m4 / (double)nf : 0.0;
   auto db = [](double x) -> double { return x > 0.0 ? 10.0 * std::log10(x) : -INFINITY; };
-  auto band = [&](double lo, double hi, bool avg) {
-    double b = 0.0; int cnt = 0;
-    for (int k = 0; k < kMonPsd; k++) if (k * df >= lo && k * df <= hi) { b += p[k]; cnt++; }
-    return avg ? (cnt ? b / cnt : 0.0) : b * df;
-  };
   auto pct = [&](unsigned q) -> double {
     if (!hist || nf == 0) return -INFINITY;
     unsigned long long cum = 0;
@@ -4650,14 +4536,13 @@ int fmr_rf_monitor_derive(const fmr_rf_monitor_record *recs, const uint32_t *his
   full.noise_dbfs = db(Nn);
   full.cn_db = Sc > 0.0 ? (Nn > 0.0 ? 10.0 * std::log10(Sc / Nn) : INFINITY) : -INFINITY;
   full.am_rms = M2 > 0.0 ? std::sqrt(std::max(M4 / (M2 * M2) - 1.0, 0.0)) / 2.0 : 0.0;
-  full.am_audio_db = M2 > 0.0 ? db(band(750.0, 15000.0, false) / ref) : -INFINITY;
-  full.am_pilot_db = M2 > 0.0 ? db(band(18250.0, 19750.0, false) / ref) : -INFINITY;
-  full.am_floor_dbc_hz = M2 > 0.0 ? db(band(100000.0, 150000.0, true) / ref) : -INFINITY;
+  full.am_audio_db = M2 > 0.0 ? db(mon_band(p, 750.0, 15000.0, false) / ref) : -INFINITY;
+  full.am_pilot_db = M2 > 0.0 ? db(mon_band(p, 18250.0, 19750.0, false) / ref) : -INFINITY;
+  full.am_floor_dbc_hz = M2 > 0.0 ? db(mon_band(p, 100000.0, 150000.0, true) / ref) : -INFINITY;
   full.p10_dbfs = pct(10); full.p50_dbfs = pct(50); full.p90_dbfs = pct(90);
   full.n_finite = nf;
   full.segments = seg;
-  const size_t osz = out_size ? out_size : sizeof full;
-  memcpy(out, &full, osz < sizeof full ? osz : sizeof full);
+  give_sized(out, out_size, full);
   return FMR_OK;
 }
 
@@ -4708,15 +4593,8 @@ int fmr_spectrum_create_waterfall(const fmr_spectrum_config *cfg, size_t cfg_siz
   *out = nullptr;
   fmr_spectrum_config full;
   if (int rc = spec_take_cfg(cfg, cfg_size, full)) return rc;
-  const size_t size = wf_size ? wf_size : sizeof(fmr_waterfall_config);
-  if (size > sizeof(fmr_waterfall_config) || wf->struct_size > sizeof(fmr_waterfall_config)) {
-    set_err("fmr_spectrum_create_waterfall: struct_size %zu is larger than this library's fmr_waterfall_config (%zu): the "
-            "caller is newer than the library", std::max(size, (size_t)wf->struct_size), sizeof(fmr_waterfall_config));
-    return FMR_ERR_BAD_ARG;
-  }
   fmr_waterfall_config w;
-  memset(&w, 0, sizeof w);
-  memcpy(&w, wf, size);
+  if (int rc = take_sized("fmr_spectrum_create_waterfall", "fmr_waterfall_config", wf, wf_size, w)) return rc;
   if (int rc = wf_check(full, w)) return rc;
   fmr_spectrum *s = new fmr_spectrum();
   s->cfg = full;
@@ -4788,40 +4666,37 @@ int fmr_spectrum_read_waterfall(fmr_spectrum *s, int row, float *out, uint32_t *
   HIPCHK(hipSetDevice(s->cfg.device));
   HIPCHK(hipStreamSynchronize(s->stream));
   const int N = s->N;
-  const unsigned long long R = (unsigned long long)s->wf.segments_per_line, L = (unsigned long long)s->wf.max_lines;
-  const unsigned long long done = s->next_seg / R;
-  s->wf_catch_up(row);
-  const unsigned long long first = s->wf_read[row], ready = done - first;
-  const size_t n = cap_lines == 0 ? 0 : (size_t)std::min<unsigned long long>({ready, cap_lines, (unsigned long long)INT_MAX});
-  if (n > 0) {
-    // the ring slots first % L .. in at most two contiguous pieces, copied straight into `out` and scaled there
-    std::vector<unsigned> cnt(n);
-    for (size_t k = 0; k < n;) {
-      const size_t slot = (size_t)((first + k) % L), m = std::min(n - k, (size_t)L - slot);
-      HIPCHK(hipMemcpy(out + k * N, s->d_wring.p + ((size_t)row * L + slot) * N, m * N * sizeof(float), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(cnt.data() + k, s->d_wring_cnt.p + (size_t)row * L + slot, m * sizeof(unsigned), hipMemcpyDeviceToHost));
-      k += m;
-    }
-    const double scale = 1.0 / (s->cfg.input_rate * s->sumw2);
-    for (size_t k = 0; k < n; k++) {
+  const unsigned long long R = (unsigned long long)s->wf.segments_per_line, done = s->next_seg / R;
+  RecCursor &cur = s->wf_cur;
+  cur.catch_up(row, done);
+  const unsigned long long first = cur.read[row];
+  const double scale = 1.0 / (s->cfg.input_rate * s->sumw2);
+  std::vector<unsigned> cnt;
+  // the lines are copied straight into `out` and scaled there; cap_lines = 0 reads nothing
+  const int n = cur.take(row, done, cap_lines, [&](size_t k0, size_t slot, size_t m) -> int {
+    cnt.resize(m);
+    HIPCHK(hipMemcpy(out + k0 * N, s->d_wring.p + ((size_t)row * cur.L + slot) * N, m * N * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cnt.data(), s->d_wring_cnt.p + (size_t)row * cur.L + slot, m * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < m; k++) {
       const double div = s->wf.which == FMR_WATERFALL_MEAN ? (double)cnt[k] : 1.0;
-      float *ln = out + k * N;
+      float *ln = out + (k0 + k) * N;
       for (int i = 0; i < N / 2; i++) {                                // fftshift: element i is bin i - N/2
         const double lo = ln[i], hi = ln[i + N / 2];
         ln[i] = cnt[k] == 0 ? 0.f : (float)(hi / div * scale);
         ln[i + N / 2] = cnt[k] == 0 ? 0.f : (float)(lo / div * scale);
       }
-      if (counted) counted[k] = cnt[k];
+      if (counted) counted[k0 + k] = cnt[k];
     }
-    s->wf_read[row] = first + n;
-  }
+    return FMR_OK;
+  });
+  if (n < 0) return n;
   if (info) {
     info->first_line = first;
-    info->lines_ready = done - s->wf_read[row];
-    info->lines_dropped = s->wf_dropped[row];
+    info->lines_ready = done - cur.read[row];
+    info->lines_dropped = cur.dropped[row];
     info->line_seconds = (double)R * s->H / s->cfg.input_rate;
   }
-  return cap_lines == 0 ? (int)std::min<unsigned long long>(ready, (unsigned long long)INT_MAX) : (int)n;
+  return n;
 }
 
 int fmr_spectrum_reset(fmr_spectrum *s) {

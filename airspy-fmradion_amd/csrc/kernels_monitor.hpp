@@ -73,13 +73,19 @@ __device__ __forceinline__ int mon_bin(float x, float rf, float scale, int bins)
 
 // Where a segment kernel's samples come from and how they are binned: the MPX of the modulation monitor here, the IF
 // power of the RF monitor in kernels_rfmon.hpp.  at(p) is the sample of absolute index p (from the call, or in front of
-// its first sample from the stream's carry), bin(v) the histogram counter of a finite sample.
+// its first sample from the stream's carry), bin(v) the histogram counter of a finite sample, fresh(i) sample i of the
+// call (what the carry keeps); make() builds stream s's source from the kernels' arguments (cin = that stream's carry).
 struct MonMpxSrc {
   static constexpr int kHist = kMonMaxHist;
   const float *xin, *cin;
   long long n0;
   float rf, scale;
   int bins;
+  __device__ __forceinline__ static MonMpxSrc make(const void *base, long long stride, int off, int s, const float *cin,
+                                                   const MonArgs &a) {
+    return {reinterpret_cast<const float *>(base) + (long long)s * stride + off, cin, a.n0, a.rf, a.scale, a.bins};
+  }
+  __device__ __forceinline__ float fresh(long long i) const { return xin[i]; }
   __device__ __forceinline__ float at(long long p) const { return p < n0 ? cin[p & (kMonN - 1)] : xin[p - n0]; }
   __device__ __forceinline__ int bin(float v) const { return mon_bin(v, rf, scale, bins); }
 };
@@ -200,15 +206,17 @@ __device__ __forceinline__ void mon_seg_run(const Src &src, int run, int s, cons
   }
 }
 
-// Stream s = blockIdx.y: the call's MPX at base + s base_stride + base_off (sample n0 first), the carry at
-// carry + s kMonN.  Partials of run r = blockIdx.x at row s rmax + r.
-__global__ __launch_bounds__(kMonT) void k_mon_seg(const float *__restrict__ base, long long base_stride, int base_off,
+// Both monitors' segment kernel, Src = MonMpxSrc | RfmSrc<NRM>.  Stream s = blockIdx.y: the call's samples as
+// Src::make reads them (the MPX at (float *)from + s stride + off, sample n0 first; the IF ring slot in kernels_rfmon.hpp),
+// the carry at carry + s kMonN.  Partials of run r = blockIdx.x at row s rmax + r.
+template <class Src>
+__global__ __launch_bounds__(kMonT) void k_mon_seg(const void *__restrict__ from, long long stride, int off,
                                                    const float *__restrict__ carry, MonArgs a,
                                                    const float *__restrict__ win, const float2 *__restrict__ tw, int rmax,
                                                    double *__restrict__ ppsd, unsigned *__restrict__ phist,
                                                    MonRec *__restrict__ prec) {
   const int s = blockIdx.y;
-  const MonMpxSrc src{base + (long long)s * base_stride + base_off, carry + (long long)s * kMonN, a.n0, a.rf, a.scale, a.bins};
+  const Src src = Src::make(from, stride, off, s, carry + (long long)s * kMonN, a);
   mon_seg_run(src, blockIdx.x, s, a, win, tw, rmax, ppsd, phist, prec);
 }
 
@@ -291,25 +299,27 @@ __device__ __forceinline__ void mon_reduce_run(const double *__restrict__ ppsd, 
 // began there.  A record whose last segment is in goes to slot (index mod L) of the rings -- unless a later record of
 // the same launch takes that slot --, an open one to open_*[par ^ 1]: the block that reads the old copy is not the one
 // that writes the new one.  last != 0 (the call's last launch; runs may be 0): block 0 copies the samples
-// [max(n0, n_end - 1023), n_end) of the call to the carry.
+// [max(n0, n_end - 1023), n_end) of the call, as Src::fresh gives them, to the carry.  Src = MonMpxSrc | RfmSrc<NRM>.
+template <class Src>
 __global__ __launch_bounds__(kMonT) void k_mon_reduce(const double *__restrict__ ppsd, const unsigned *__restrict__ phist,
                                                       const MonRec *__restrict__ prec, int runs, int rmax, MonArgs a,
                                                       int L, long long M, int par, double *__restrict__ open_psd,
                                                       unsigned *__restrict__ open_hist, MonRec *__restrict__ open_rec,
                                                       double *__restrict__ ring_psd, unsigned *__restrict__ ring_hist,
-                                                      MonRec *__restrict__ ring_rec, const float *__restrict__ base,
-                                                      long long base_stride, int base_off, float *__restrict__ carry,
+                                                      MonRec *__restrict__ ring_rec, const void *__restrict__ from,
+                                                      long long stride, int off, float *__restrict__ carry,
                                                       long long n_end, int last) {
   constexpr int T = kMonT;
   const int tid = threadIdx.x, s = blockIdx.y;
   if (runs > 0)
-    mon_reduce_run<kMonMaxHist / kMonT>(ppsd, phist, prec, runs, rmax, a, L, M, par, open_psd, open_hist, open_rec, ring_psd,
-                                        ring_hist, ring_rec);
+    mon_reduce_run<(Src::kHist + T - 1) / T>(ppsd, phist, prec, runs, rmax, a, L, M, par, open_psd, open_hist, open_rec,
+                                             ring_psd, ring_hist, ring_rec);
   if (last && blockIdx.x == 0) {
-    const float *xin = base + (long long)s * base_stride + base_off;
+    float *row = carry + (long long)s * kMonN;
+    const Src src = Src::make(from, stride, off, s, row, a);
     for (int q = tid; q < kMonN - 1; q += T) {
       const long long p = n_end - (kMonN - 1) + q;
-      if (p >= a.n0) carry[(long long)s * kMonN + (p & (kMonN - 1))] = xin[p - a.n0];
+      if (p >= a.n0) row[p & (kMonN - 1)] = src.fresh(p - a.n0);
     }
   }
 }

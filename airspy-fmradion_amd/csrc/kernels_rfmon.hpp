@@ -11,6 +11,9 @@
 // mon_reduce_run); what is this file's own is the load of p, the carry of p in front of a call's first sample, and
 // the histogram's integer rule:  bin = clamp((bits of p >> 20) - 696, 0, 383), eight bins per octave from 2^-40 to 2^8.
 //
+// The kernels are kernels_monitor.hpp's k_mon_seg<RfmSrc<NRM>> and k_mon_reduce<RfmSrc<NRM>> (grids (runs, S) and
+// (records the launch touches, S); a.bins = kRfmBins, the carry of p at carry + s kMonN).
+//
 // No sqrt, log or atan on the device; nothing waits on another workgroup or on the host; no float atomics.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,46 +49,15 @@ struct RfmSrc {
   int h_if, s;
   const float *cin;
   long long n0;
+  __device__ __forceinline__ static RfmSrc make(const void *slot, long long if_stride, int h_if, int s, const float *cin,
+                                                const MonArgs &a) {
+    return {slot, if_stride, h_if, s, cin, a.n0};
+  }
+  __device__ __forceinline__ float fresh(long long i) const { return rfm_p<NRM>(slot, if_stride, h_if, s, i); }
   __device__ __forceinline__ float at(long long p) const {
     return p < n0 ? cin[p & (kMonN - 1)] : rfm_p<NRM>(slot, if_stride, h_if, s, p - n0);
   }
   __device__ __forceinline__ int bin(float v) const { return rfm_bin(v); }
 };
-
-// Grid (runs, S).  The call's slot (sample n0 first), the carry of p at carry + s kMonN; a.bins = kRfmBins.
-template <bool NRM>
-__global__ __launch_bounds__(kMonT) void k_rfm_seg(const void *__restrict__ slot, long long if_stride, int h_if,
-                                                   const float *__restrict__ carry, MonArgs a,
-                                                   const float *__restrict__ win, const float2 *__restrict__ tw, int rmax,
-                                                   double *__restrict__ ppsd, unsigned *__restrict__ phist,
-                                                   MonRec *__restrict__ prec) {
-  const int s = blockIdx.y;
-  const RfmSrc<NRM> src{slot, if_stride, h_if, s, carry + (long long)s * kMonN, a.n0};
-  mon_seg_run(src, blockIdx.x, s, a, win, tw, rmax, ppsd, phist, prec);
-}
-
-// Grid (records the launch touches, S): k_mon_reduce with the carry of p.  last != 0 (the call's last launch; runs may
-// be 0): block 0 puts p of the samples [max(n0, n_end - 1023), n_end) of the call into the carry.
-template <bool NRM>
-__global__ __launch_bounds__(kMonT) void k_rfm_reduce(const double *__restrict__ ppsd, const unsigned *__restrict__ phist,
-                                                      const MonRec *__restrict__ prec, int runs, int rmax, MonArgs a,
-                                                      int L, long long M, int par, double *__restrict__ open_psd,
-                                                      unsigned *__restrict__ open_hist, MonRec *__restrict__ open_rec,
-                                                      double *__restrict__ ring_psd, unsigned *__restrict__ ring_hist,
-                                                      MonRec *__restrict__ ring_rec, const void *__restrict__ slot,
-                                                      long long if_stride, int h_if, float *__restrict__ carry,
-                                                      long long n_end, int last) {
-  constexpr int T = kMonT;
-  const int tid = threadIdx.x, s = blockIdx.y;
-  if (runs > 0)
-    mon_reduce_run<(kRfmBins + T - 1) / T>(ppsd, phist, prec, runs, rmax, a, L, M, par, open_psd, open_hist, open_rec, ring_psd,
-                                           ring_hist, ring_rec);
-  if (last && blockIdx.x == 0) {
-    for (int q = tid; q < kMonN - 1; q += T) {
-      const long long p = n_end - (kMonN - 1) + q;
-      if (p >= a.n0) carry[(long long)s * kMonN + (p & (kMonN - 1))] = rfm_p<NRM>(slot, if_stride, h_if, s, p - a.n0);
-    }
-  }
-}
 
 }  // namespace fmr

@@ -14,6 +14,7 @@ import chanbank_fixture as cb
 import rds_fixture as rf
 import rfmon_fixture as rx
 import siggen
+import test_gpu_monitor as tgm
 from conftest import ROOT, load_filter
 
 fmr = importlib.import_module("airspy-fmradion_amd")
@@ -197,6 +198,31 @@ def test_three_streams():
         levels.append(fmr.rf_levels(*got[:3])["level_dbfs"])
         assert abs(levels[-1] - 20.0 * np.log10(amps[s])) <= 0.05, (s, levels)
     assert levels[0] < levels[1] < levels[2]
+    ch.close()
+
+
+def test_beside_the_modulation_monitor_with_unlike_parameters():
+    """Both segment monitors on one two-stream chain, each with its own record length, histogram and ring depth (1024
+    samples, 64 bins, 256 records against 512 samples, 384 bins, 4 records), over the ragged calls: every stream's
+    modulation records against the monitor fixture on its tap 1 with nothing dropped, the RF monitor's ring overrun to
+    its newest four records, which stand against this file's fixture; neither monitor's partition, carry, ring or read
+    position is the other's."""
+    S, n = 2, sum(map(sum, RAGGED))
+    x = np.stack([signal(n, amplitude=a, seed=11 + s) for s, a in enumerate((0.3, 0.1))])
+    ch = chain384(S=S)
+    ch.enable_monitor(interval_samples=1024, hist_bins=64, max_records=256)
+    ch.enable_rf_monitor(interval_samples=512, max_records=4)
+    mpx, _ = tgm.feed(ch, x, RAGGED, S=S)
+    n_mod, n_rf = (n - 512) // 1024, (n - 512) // 512
+    assert n_mod < 256 and n_rf > 4
+    for s in range(S):
+        mod = ch.monitor_records(s)
+        assert len(tgm.check_records(mod[:3], mpx[s], 1024, 64, 2.0)) == n_mod
+        assert mod[3]["records_dropped"] == 0 and mod[3]["records_complete"] == n_mod and mod[3]["hist_bins"] == 64
+        got = ch.rf_monitor_records(s)
+        assert len(check_records(got[:3], rx.power(x[s]), 512, first=n_rf - 4)) == 4
+        assert got[3]["records_dropped"] == n_rf - 4 and got[3]["records_complete"] == n_rf
+        assert ch.monitor_records(s)[3]["records_dropped"] == 0
     ch.close()
 
 

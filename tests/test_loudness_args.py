@@ -3,15 +3,13 @@ fmr_loudness_derive): the struct layouts of header and binding, every configurat
 looked at, and the host-only derive call against tests/loudness_fixture.py."""
 import ctypes as C
 import importlib
-import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import loudness_fixture as lf
-from conftest import ROOT
+from cheader import header_struct as _header_struct
 
 fmr = importlib.import_module("airspy-fmradion_amd")
 
@@ -32,26 +30,6 @@ def _cfg(**kw):
 def _enable(L, cfg, size=None, chain=None):
     rc = L.fmr_enable_loudness(chain, C.byref(cfg), C.sizeof(cfg) if size is None else size)
     return rc, L.fmr_last_error().decode()
-
-
-_CT = {"unsigned": C.c_uint, "int": C.c_int, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "double": C.c_double}
-
-
-def _header_struct(name):
-    """The fields of `typedef struct { ... } name;` in the header as a ctypes Structure (arrays as name[n])."""
-    hdr = open(os.path.join(ROOT, "include", "fmradion_amd.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\}\s*" + name + r"\s*;", hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        typ, names = decl.split(None, 1)
-        for n in names.split(","):
-            m = re.fullmatch(r"(\w+)(?:\[(\d+)\])?", n.strip())
-            fields.append((m.group(1), _CT[typ] * int(m.group(2)) if m.group(2) else _CT[typ]))
-    return type(name, (C.Structure,), {"_fields_": fields})
 
 
 @pytest.mark.parametrize("name,binding,size", [

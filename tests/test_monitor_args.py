@@ -3,15 +3,13 @@ fmr_monitor_read / fmr_monitor_derive): the struct layouts of header and binding
 before the chain is looked at, and the host-only derive call against tests/monitor_fixture.py."""
 import ctypes as C
 import importlib
-import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import monitor_fixture as mf
-from conftest import ROOT
+from cheader import header_struct as _header_struct
 
 fmr = importlib.import_module("airspy-fmradion_amd")
 
@@ -32,25 +30,6 @@ def _cfg(**kw):
 def _enable(L, cfg, size=None, chain=None):
     rc = L.fmr_enable_monitor(chain, C.byref(cfg), C.sizeof(cfg) if size is None else size)
     return rc, L.fmr_last_error().decode()
-
-
-_CT = {"unsigned": C.c_uint, "int": C.c_int, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "double": C.c_double,
-       "float": C.c_float}
-
-
-def _header_struct(name):
-    """The fields of `typedef struct { ... } name;` in the header as a ctypes Structure."""
-    hdr = open(os.path.join(ROOT, "include", "fmradion_amd.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\}\s*" + name + r"\s*;", hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        typ, names = decl.split(None, 1)
-        fields += [(n.strip(), _CT[typ]) for n in names.split(",")]
-    return type(name, (C.Structure,), {"_fields_": fields})
 
 
 @pytest.mark.parametrize("name,binding,size", [
