@@ -51,6 +51,7 @@ EXPORTS = [
     "fmr_enable_monitor", "fmr_monitor_read", "fmr_monitor_derive",
     "fmr_enable_loudness", "fmr_loudness_read", "fmr_loudness_derive",
     "fmr_enable_rf_monitor", "fmr_rf_monitor_read", "fmr_rf_monitor_derive",
+    "fmr_enable_output", "fmr_output_read", "fmr_squelch_level_from_db",
 ]
 # FMR_WINDOW_* (include/fmradion_amd.h): windows of the band spectrum
 WINDOW_HANN, WINDOW_RECT, WINDOW_BLACKMAN_HARRIS = 0, 1, 2
@@ -77,6 +78,14 @@ RF_MONITOR_RECORD = np.dtype([("index", np.uint64), ("first_sample", np.uint64),
                               ("n_nonfinite", np.uint32), ("segments", np.uint32), ("segments_skipped", np.uint32),
                               ("p_min", np.float32), ("p_max", np.float32), ("m2", np.float64), ("m4", np.float64)])
 RF_HIST_BINS, RF_PSD_BINS = 384, 513
+# FMR_PCM_* (include/fmradion_amd.h): sample format of the output stage
+PCM_S16, PCM_F32 = 0, 1
+_PCM_DTYPE = {PCM_S16: np.int16, PCM_F32: np.float32}
+# fmr_output_block as a numpy structured type (56 bytes)
+OUTPUT_BLOCK = np.dtype([("block", np.uint64), ("first_frame", np.uint64), ("n_frames", np.uint32), ("channels", np.uint32),
+                         ("if_rms", np.float32), ("if_level", np.float32), ("audio_mean", np.float32),
+                         ("audio_rms", np.float32), ("audio_level", np.float32), ("gate_open", np.uint32),
+                         ("n_clipped", np.uint32), ("n_nonfinite", np.uint32)])
 
 
 class FmrError(RuntimeError):
@@ -201,6 +210,24 @@ class LoudnessLevels(C.Structure):
                 ("gated_windows", C.c_uint64)]
 
 
+class OutputConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("format", C.c_int), ("squelch_level", C.c_double), ("gain", C.c_double),
+                ("max_frames", C.c_uint32), ("max_blocks", C.c_uint32)]
+
+
+class OutputBlock(C.Structure):
+    _fields_ = [("block", C.c_uint64), ("first_frame", C.c_uint64), ("n_frames", C.c_uint32), ("channels", C.c_uint32),
+                ("if_rms", C.c_float), ("if_level", C.c_float), ("audio_mean", C.c_float), ("audio_rms", C.c_float),
+                ("audio_level", C.c_float), ("gate_open", C.c_uint32), ("n_clipped", C.c_uint32),
+                ("n_nonfinite", C.c_uint32)]
+
+
+class OutputInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("format", C.c_int), ("channels", C.c_int), ("first_frame", C.c_uint64),
+                ("frames_waiting", C.c_uint64), ("frames_dropped", C.c_uint64), ("blocks_waiting", C.c_uint64),
+                ("blocks_dropped", C.c_uint64)]
+
+
 def build_library(force=False, verbose=False):
     """Compile the HIP library (and its A/B partner build) in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     import glob
@@ -317,6 +344,13 @@ def lib(ab=False):
     L.fmr_rf_monitor_read.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.POINTER(RfMonitorInfo), C.c_size_t]
     L.fmr_rf_monitor_derive.restype = C.c_int
     L.fmr_rf_monitor_derive.argtypes = [vp, vp, vp, C.c_int, C.POINTER(RfMonitorLevels), C.c_size_t]
+    L.fmr_enable_output.restype = C.c_int
+    L.fmr_enable_output.argtypes = [vp, C.POINTER(OutputConfig), C.c_size_t]
+    L.fmr_output_read.restype = C.c_int
+    L.fmr_output_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, C.c_int, C.POINTER(C.c_size_t), C.POINTER(OutputInfo),
+                                  C.c_size_t]
+    L.fmr_squelch_level_from_db.restype = C.c_double
+    L.fmr_squelch_level_from_db.argtypes = [C.c_double]
     _libs[ab] = L
     return L
 
@@ -391,6 +425,11 @@ class RdsStatus(C.Structure):
 class RdsFec(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("mode", C.c_int), ("max_burst", C.c_int), ("soft_symbols", C.c_int),
                 ("soft_max_cost", C.c_double)]
+
+
+def squelch_level_from_db(db):
+    """fmr_squelch_level_from_db (host only): the linear squelch level of the reference's -l option, pow(10, -(db / 20))."""
+    return lib().fmr_squelch_level_from_db(float(db))
 
 
 def loudness_levels(records, silence_dbfs=-60.0):
@@ -725,6 +764,34 @@ class Chain:
         (records RF_MONITOR_RECORD [n], hist uint32 [n, 384], psd float64 [n, 513], info dict).  Reading drains them."""
         return self._read_records(self._L.fmr_rf_monitor_read, RfMonitorInfo, ((RF_MONITOR_RECORD, None), (np.uint32, RF_HIST_BINS),
                                                                                 (np.float64, RF_PSD_BINS)), stream, cap)
+
+    def enable_output(self, format="s16", squelch_db=None, gain=0.0, max_frames=0, max_blocks=0, squelch_level=None):
+        """fmr_enable_output: the output stage of every stream / channel (any decoder chain, once, before the first call).
+        format "s16" | "f32" (or PCM_S16 / PCM_F32); squelch_db as the reference's -l option (None: never closed), or
+        squelch_level, the linear level itself; 0 = the defaults (gain 0.5, 2^18 frames and 4096 records kept)."""
+        fmt = {"s16": PCM_S16, "f32": PCM_F32}.get(format, format)
+        level = 0.0 if squelch_db is None else squelch_level_from_db(squelch_db)
+        if squelch_level is not None:
+            level = float(squelch_level)
+        cfg = OutputConfig(C.sizeof(OutputConfig), int(fmt), level, float(gain), int(max_frames), int(max_blocks))
+        self._chk(self._L.fmr_enable_output(self.h, C.byref(cfg), C.sizeof(OutputConfig)))
+
+    def output_read(self, stream=0, cap_frames=None, cap_blocks=None):
+        """fmr_output_read: the oldest unread PCM frames (at most cap_frames; None: all that wait) and block records (at most
+        cap_blocks; None: all) of `stream` as (pcm [n, channels] int16 | float32, blocks OUTPUT_BLOCK [m], info dict).
+        Reading drains them."""
+        info = OutputInfo()
+        tail = (C.byref(info), C.sizeof(OutputInfo))
+        self._chk(self._L.fmr_output_read(self.h, int(stream), None, 0, None, 0, None, *tail))
+        nf = int(info.frames_waiting if cap_frames is None else cap_frames)
+        nb = int(info.blocks_waiting if cap_blocks is None else cap_blocks)
+        ch = int(info.channels)
+        pcm = np.zeros((nf, ch), dtype=_PCM_DTYPE[int(info.format)])
+        blocks = np.zeros(nb, dtype=OUTPUT_BLOCK)
+        got = C.c_size_t(0)
+        m = self._chk(self._L.fmr_output_read(self.h, int(stream), pcm.ctypes.data if nf else None, nf,
+                                              blocks.ctypes.data if nb else None, nb, C.byref(got), *tail))
+        return pcm[:got.value], blocks[:m], {k: getattr(info, k) for k, _ in OutputInfo._fields_}
 
     def pps_events(self, stream=0):
         ev = (PpsEvent * 64)()

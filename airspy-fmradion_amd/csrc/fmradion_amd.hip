@@ -36,6 +36,7 @@
 #include "kernels_monitor.hpp"
 #include "kernels_loudness.hpp"
 #include "kernels_rfmon.hpp"
+#include "kernels_output.hpp"
 #include "../host/fmradion_rds.hpp"
 
 namespace {
@@ -445,6 +446,25 @@ struct fmr_chain {
   unsigned long long ld_done() const { return (unsigned long long)(ld_n / (long long)ld_cfg.step_samples); }   // records complete
   int ld_init(const fmr_loudness_config &m);
   int ld_stage(const double *d_aud, long long astride, long long N, hipStream_t st);
+  // ---- output stage (fmr_enable_output; kernels_output.hpp).  The last reader of the call's
+  // finished audio, on the stream that wrote it: squelch, gain and PCM conversion into a ring of frames per stream, and one
+  // record per block with the stream loop's meters.  The block, frame and record counters live here and are taken when a
+  // call is issued (out_begin); the device carries the two levels.  k_stats leaves every block's IF RMS in the call's
+  // slot of d_out_ifrms (the tail of a pipelined chain runs a call late).  Nothing of it exists unless it is enabled.
+  bool out = false;
+  fmr_output_config out_cfg{};               // the defaults filled in
+  unsigned long long out_block = 0, out_recs = 0, out_frames = 0;   // blocks handed in, records and audio frames produced
+  DevBuf<float> d_out_ifrms;                 // [kPipe][S][max_blocks]
+  DevBuf<OutPart> d_out_part;                // [S][max_blocks]
+  DevBuf<float2> d_out_state;                // [S] if_level, audio_level
+  DevBuf<OutRec> d_out_rec;                  // [S][max_blocks of the config]
+  DevBuf<unsigned char> d_out_pcm;           // [S][max_frames] frames
+  RecCursor out_fcur, out_bcur;              // frames, records
+  size_t out_frame_bytes() const { return (size_t)(stereo ? 2 : 1) * (out_cfg.format == FMR_PCM_F32 ? 4 : 2); }
+  float *out_ifrms_slot(int q) { return out ? d_out_ifrms.p + (size_t)q * S * max_blocks : nullptr; }
+  int out_init(const fmr_output_config &m);
+  OutArgs out_begin(unsigned long long block0, const int *if_len, int nb, long long N_au);
+  int out_stage(const double *d_aud, long long astride, const BlockTab &bt, const float *if_rms_blk, const OutArgs &a, hipStream_t st);
   int in_rows() const { return bank ? 1 : S; }   // rows of the input buffers (d_in, d_in_halo)
   // front end only (fmr_resample_blocks_device): stage B writes row s of this call's IF samples to if_out + s if_out_stride
   // instead of the chain's IF buffer (nullptr: the IF buffer)
@@ -553,6 +573,7 @@ struct fmr_chain {
     mon.release(); rfm.release();
     d_ld_pw.release(); d_ld_taps.release(); d_ld_G.release(); d_ld_start.release(); d_ld_pkw.release(); d_ld_state.release();
     d_ld_hist.release(); d_ld_part.release(); d_ld_open.release(); d_ld_ring.release();
+    d_out_ifrms.release(); d_out_part.release(); d_out_state.release(); d_out_rec.release(); d_out_pcm.release();
     if (h_rds_slots) (void)hipHostFree(h_rds_slots);
     if (h_rds_mark) (void)hipHostFree(h_rds_mark);
     if (h_tab_all) (void)hipHostFree(h_tab_all);
@@ -740,6 +761,7 @@ struct fmr_chain {
     bool agc_deferred{};
     std::function<int(hipEvent_t)> enqueue_agc{};
     bool done = false;                 // the front end found nothing to decode
+    unsigned long long out_block0 = 0; // output stage: absolute index of the call's first block
     hipEvent_t ev_mpx = nullptr;       // recorded where this call's MPX (discriminator output) is complete
     std::function<void()> fe_post{};   // pipelined chain: the front-end stage's end-of-call kernel, when it is still to be launched
     // this call's slot of the rings the stages hand each other (plain chain: the one buffer of each kind)
@@ -771,6 +793,8 @@ struct fmr_chain {
     DcCoef dk{};
     HaloTable ht{};
     unsigned long long seq{};
+    OutArgs out{};                     // output stage: the call's positions and its slot of the per-block IF RMS
+    const float *out_ifrms = nullptr;
   };
   static constexpr int kDeBlock = 256;
   TailCtx tail_job{};
@@ -1568,6 +1592,7 @@ int fmr_chain::run(const float2 *d_iq, size_t stride, const uint32_t *block_len,
   k.d_iq = d_iq; k.stride = stride; k.block_len = block_len; k.nb = nb; k.d_aud = d_aud; k.astride = astride;
   k.audio_len = audio_len; k.N_in = N_in; k.slot = slot; k.h_tab = h_tab; k.d_tab_slot = d_tab_slot;
   k.t_if_off = t_if_off; k.t_if_len = t_if_len; k.t_au_off = t_au_off; k.t_au_len = t_au_len; k.t_mpf = t_mpf;
+  if (out) { k.out_block0 = out_block; out_block += (unsigned long long)nb; }   // (every block handed in counts, empty ones too)
   if (int rc = run_front_end(k)) return rc;
   if (k.done) return flush_tail(nullptr);     // (nothing to decode: a pending tail refers to a table slot this call's successors will reuse)
   k.base = base_slot(k.par); k.raw = raw_slot(k.par); k.part = part_slot(k.par); k.stereo_blk = stereo_slot(k.par);
@@ -1970,7 +1995,7 @@ int fmr_chain::run_tables(CallCtx &k) {
     k.fused_n_tiles = fr.tiles;
     fe_spare_cus = std::max(0, n_cu - fr.grid * S);
     const long long kb_ref = 384 * fused_T_first - p.prev.kB;
-    fused_part_from = k.t_if_off[first_part_block(k.t_if_len, nb)];
+    fused_part_from = k.t_if_off[out ? 0 : first_part_block(k.t_if_len, nb)];
     // Where the runs start: a macro tile whose epilogue writes the per-block partial sums (the last ~400 blocks of a call:
     // block walk, six wave reductions and a store per 128 samples) costs its workgroup kFusedSumWeight more than one that does
     // not -- measured, round 6: the workgroups of the last fifth of a 2048-block call took 207-213 us against the others' 194-197
@@ -2006,7 +2031,7 @@ int fmr_chain::run_tables(CallCtx &k) {
     k.fused_n_tiles = 8 * fr.tiles;                             // in the epilogue's macro tiles of 384 samples
     const long long kb_ref = 48 * (p.prev.kB / 48) - p.prev.kB;
     k.fused_kb_ref = (int)kb_ref;
-    fused_part_from = k.t_if_off[first_part_block(k.t_if_len, nb)];
+    fused_part_from = k.t_if_off[out ? 0 : first_part_block(k.t_if_len, nb)];
     fill_run_blocks(k, t_wg, fr, nullptr, kb_ref, 3072);
     copy_runs(fr.grid);
   }
@@ -2186,7 +2211,7 @@ int fmr_chain::run_if_stage(CallCtx &k) {
     a.dec = debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
     a.nf = disc_nf; a.bound = disc_bound;
     const TileRuns &r = p.fir_runs;
-    a.st = d_state.p; a.part = k.part; a.n_tiles = 8 * r.tiles; a.part_from = k.t_if_off[first_part_block(k.t_if_len, nb)];
+    a.st = d_state.p; a.part = k.part; a.n_tiles = 8 * r.tiles; a.part_from = k.t_if_off[out ? 0 : first_part_block(k.t_if_len, nb)];
     a.if_off = bt.if_off; a.if_len = bt.if_len; a.nb = nb;
     a.wg_blk0 = k.d_tab_slot + (tab_ints - kMaxFusedWg) + kFirBlk0Off;
     a.mid32 = d_run_ph.p;
@@ -2582,7 +2607,7 @@ int fmr_chain::run_fm(CallCtx &k) {
     hipLaunchKernelGGL(k_stats, dim3(S), dim3(FMR_STATS_THREADS), stats_ballast, side, bt, d_if_rms_blk.p, d_bb_mean_blk.p,
                        d_bb_rms_blk.p, d_state.p, S, (int)!(pipelined && p.b_disc),   // (the front-end stage commits its own phase)
                        (p.b_disc || p.fir_tail()) ? k.part : (const FusedPart *)nullptr, p.fir_tail() ? 8 * p.fir_runs.tiles : fused_n_tiles,
-                       p.fir_tail() ? 0 : fused_kb_ref);
+                       p.fir_tail() ? 0 : fused_kb_ref, out_ifrms_slot(k.par));
   });
   HIPCHK(hipEventRecord(ev_stats, side));
   disc_commit_on_side = !(pipelined && p.b_disc);
@@ -2593,6 +2618,7 @@ int fmr_chain::run_fm(CallCtx &k) {
   t.base = k.base; t.raw = k.raw; t.stereo_blk = k.stereo_blk; t.N_if = N_if; t.N_au = N_au; t.nb = nb; t.bt = bt;
   t.d_aud = d_aud; t.astride = (long long)astride; t.amA_prev = amA_prev; t.akB_prev = akB_prev;
   t.nch = stereo ? 2 : 1;
+  if (out) { t.out = out_begin(k.out_block0, k.t_if_len, nb, N_au); t.out_ifrms = out_ifrms_slot(k.par); }
   for (int b = 0; b < nb; b++) t.au_max = std::max(t.au_max, t_au_len[b]);
   t.count_am = (int)(arsc.mA - amA_prev);
   if ((size_t)t.count_am > max_amid || (size_t)N_au > max_au) { set_err("internal audio capacity exceeded"); return FMR_ERR_CAPACITY; }
@@ -2781,6 +2807,7 @@ int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
     if (t.agc_on_side) HIPCHK(hipStreamWaitEvent(ts, ev_agc, 0));
     if (t.fin_on_side) HIPCHK(hipStreamWaitEvent(ts, ev_fin, 0));
   }
+  if (out) if (int rc = out_stage(t.d_aud, t.astride, t.bt, t.out_ifrms, t.out, ts)) return rc;   // (behind the statistics: ev_stats)
   return FMR_OK;
 }
 
@@ -3085,6 +3112,58 @@ int fmr_chain::ld_stage(const double *d_aud, long long astride, long long N, hip
   return FMR_OK;
 }
 
+// ---- output stage (kernels_output.hpp) ----
+int fmr_chain::out_init(const fmr_output_config &m) {
+  static_assert(sizeof(OutRec) == sizeof(fmr_output_block), "OutRec is fmr_output_block");
+  out_cfg = m;
+  int rc;
+  if ((rc = d_out_ifrms.alloc((size_t)(pipelined ? kPipe : 1) * S * max_blocks))) return rc;
+  if ((rc = d_out_part.alloc((size_t)S * max_blocks))) return rc;
+  if ((rc = d_out_state.alloc((size_t)S))) return rc;
+  if ((rc = d_out_rec.alloc((size_t)S * m.max_blocks))) return rc;
+  if ((rc = d_out_pcm.alloc((size_t)S * m.max_frames * out_frame_bytes()))) return rc;
+  out_fcur.reset(S, 1); out_fcur.L = m.max_frames;
+  out_bcur.reset(S, (int)m.max_blocks);
+  out_block = out_recs = out_frames = 0;
+  out = true;
+  return FMR_OK;
+}
+
+// the positions of one call (block0: absolute index of its first block), taken when it is issued; advances the counters
+OutArgs fmr_chain::out_begin(unsigned long long block0, const int *if_len, int nb, long long N_au) {
+  OutArgs a{};
+  a.block0 = block0; a.frame0 = out_frames; a.rec0 = out_recs;
+  a.n_frames = (unsigned long long)N_au;
+  for (int b = 0; b < nb; b++) a.n_recs += if_len[b] != 0;
+  a.squelch = out_cfg.squelch_level; a.gain = out_cfg.gain;
+  a.max_frames = out_cfg.max_frames; a.max_blocks = out_cfg.max_blocks;
+  out_frames += a.n_frames; out_recs += a.n_recs;
+  return a;
+}
+
+// one call's audio (where the decoder wrote it) through the output stage on stream st: the PCM frames and the blocks'
+// partials, then the records
+int fmr_chain::out_stage(const double *d_aud, long long astride, const BlockTab &bt, const float *if_rms_blk, const OutArgs &a,
+                         hipStream_t st) {
+  if (a.n_recs == 0) return FMR_OK;
+  const int ch = stereo ? 2 : 1;
+  if (a.n_frames > 0)
+    timed_on(st, "out_pcm", [&] {
+      auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(bt.nb, S), dim3(kOutThreads), 0, st, d_aud, astride, bt, if_rms_blk, a, (void *)d_out_pcm.p,
+                           d_out_part.p);
+      };
+      if (out_cfg.format == FMR_PCM_F32) { if (ch == 2) go(k_out_pcm<1, 2>); else go(k_out_pcm<1, 1>); }
+      else { if (ch == 2) go(k_out_pcm<0, 2>); else go(k_out_pcm<0, 1>); }
+    });
+  timed_on(st, "out_blocks", [&] {
+    hipLaunchKernelGGL(k_out_blocks, dim3(S), dim3(64), 0, st, bt, if_rms_blk, (const OutPart *)d_out_part.p, a, ch, d_out_state.p,
+                       d_out_rec.p);
+  });
+  HIPCHK(hipGetLastError());
+  return FMR_OK;
+}
+
 // the filled slots, in call order, through the host decoders (never blocks)
 void fmr_chain::rds_drain() {
   while (rds_drained < rds_seq && __atomic_load_n(h_rds_mark, __ATOMIC_ACQUIRE) > rds_drained) {
@@ -3172,7 +3251,7 @@ int fmr_chain::run_nbfm(CallCtx &k) {
   });
   timed("stats", [&] {
     hipLaunchKernelGGL(k_stats, dim3(S), dim3(FMR_STATS_THREADS), 0, stream, bt, d_if_rms_blk.p, d_bb_mean_blk.p,
-                       d_bb_rms_blk.p, d_state.p, S, 1);
+                       d_bb_rms_blk.p, d_state.p, S, 1, (const FusedPart *)nullptr, 0, 0, out_ifrms_slot(0));
   });
   timed("nbfm_audio", [&] {
     hipLaunchKernelGGL((k_pilotcut2<320, 1280>), dim3(nb, S, 1), dim3(320), 0, stream, d_base.p, (double *)nullptr,
@@ -3182,6 +3261,7 @@ int fmr_chain::run_nbfm(CallCtx &k) {
   add_halo(ifbuf, if_stride, H_if, N_if);
   add_halo(d_base.p, base_stride, H_b, N_if);
   if (audio_len) for (int b = 0; b < nb; b++) audio_len[b] = (uint32_t)t_au_len[b];
+  if (out) if (int rc = out_stage(d_aud, (long long)astride, bt, out_ifrms_slot(0), out_begin(k.out_block0, k.t_if_len, nb, k.N_au), stream)) return rc;
   return FMR_OK;
 }
 
@@ -3198,7 +3278,7 @@ int fmr_chain::run_am(CallCtx &k) {
   });
   timed("stats", [&] {
     hipLaunchKernelGGL(k_stats, dim3(S), dim3(FMR_STATS_THREADS), 0, stream, bt, d_if_rms_blk.p, d_bb_mean_blk.p,
-                       d_bb_rms_blk.p, d_state.p, S, 0);
+                       d_bb_rms_blk.p, d_state.p, S, 0, (const FusedPart *)nullptr, 0, 0, out_ifrms_slot(0));
   });
   timed("am_tail", [&] {
     const bool par_tail = !serial_mode;
@@ -3230,6 +3310,7 @@ int fmr_chain::run_am(CallCtx &k) {
   });
   add_halo(ifbuf, if_stride, H_if, N_if);
   if (audio_len) for (int b = 0; b < nb; b++) audio_len[b] = (uint32_t)t_au_len[b];
+  if (out) if (int rc = out_stage(d_aud, (long long)astride, bt, out_ifrms_slot(0), out_begin(k.out_block0, k.t_if_len, nb, k.N_au), stream)) return rc;
   return FMR_OK;
 }
 
@@ -4306,6 +4387,105 @@ int fmr_monitor_derive(const fmr_monitor_record *recs, const double *psd, int n,
   full.segments = seg;
   give_sized(out, out_size, full);
   return FMR_OK;
+}
+
+// ---- output stage: C-ABI ----
+double fmr_squelch_level_from_db(double db) { return std::pow(10.0, -(db / 20.0)); }      // main.cpp:486
+
+int fmr_enable_output(fmr_chain *c, const fmr_output_config *cfg, size_t cfg_size) {
+  if (!cfg) { set_err("fmr_enable_output: cfg is null"); return FMR_ERR_BAD_ARG; }
+  fmr_output_config m;
+  if (int rc = take_sized("fmr_enable_output", "fmr_output_config", cfg, cfg_size, m)) return rc;
+  if (m.format != FMR_PCM_S16 && m.format != FMR_PCM_F32) {
+    set_err("fmr_enable_output: format %d is neither FMR_PCM_S16 (0) nor FMR_PCM_F32 (1)", m.format);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!std::isfinite(m.squelch_level) || m.squelch_level < 0.0) {
+    set_err("fmr_enable_output: squelch_level %g is not a finite linear level >= 0 (0 = never closed)", m.squelch_level);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.gain == 0.0) m.gain = 0.5;
+  if (!std::isfinite(m.gain) || !(m.gain > 0.0)) {
+    set_err("fmr_enable_output: gain %g is not finite and > 0 (0 = 0.5)", m.gain);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.max_frames == 0) m.max_frames = 1u << 18;
+  if (m.max_blocks == 0) m.max_blocks = 4096;
+  if (m.max_frames > (1u << 26)) {
+    set_err("fmr_enable_output: max_frames %u is outside 1 .. 2^26 (0 = 2^18)", m.max_frames);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.max_blocks > 65536) {
+    set_err("fmr_enable_output: max_blocks %u is outside 1 .. 65536 (0 = 4096)", m.max_blocks);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!c) { set_err("fmr_enable_output: chain is null"); return FMR_ERR_BAD_ARG; }
+  if (!c->has_dec) {
+    set_err("fmr_enable_output: a front-end-only chain (mode -1: channelizer / IfResampler) has no audio");
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (c->out) { set_err("fmr_enable_output: the output stage of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
+  if (c->call_seq != 0) {
+    set_err("fmr_enable_output: the chain has already taken samples (the output stage counts from the chain's first block)");
+    return FMR_ERR_BAD_ARG;
+  }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    return c->out_init(m);
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, fmr_output_block *blocks, int cap_blocks,
+                    size_t *n_frames, fmr_output_info *info, size_t info_size) {
+  if (n_frames) *n_frames = 0;
+  if (!c || stream < 0 || stream >= c->S || cap_blocks < 0) { set_err("fmr_output_read: bad chain, stream or cap_blocks"); return FMR_ERR_BAD_ARG; }
+  if (!c->out) { set_err("fmr_output_read: the chain has no output stage (fmr_enable_output)"); return FMR_ERR_BAD_ARG; }
+  if (cap_frames > 0 && !pcm) { set_err("fmr_output_read: pcm is null"); return FMR_ERR_BAD_ARG; }
+  if (cap_blocks > 0 && !blocks) { set_err("fmr_output_read: blocks is null"); return FMR_ERR_BAD_ARG; }
+  if (info && (info_size ? info_size : sizeof(fmr_output_info)) > sizeof(fmr_output_info)) {
+    set_err("fmr_output_read: info_size %zu is larger than this library's fmr_output_info (%zu): the caller is newer than the library",
+            info_size, sizeof(fmr_output_info));
+    return FMR_ERR_BAD_ARG;
+  }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    const size_t fb = c->out_frame_bytes();
+    RecCursor &fc = c->out_fcur, &bc = c->out_bcur;
+    fc.catch_up(stream, c->out_frames);
+    const unsigned long long first = fc.read[stream];
+    int nf = 0;
+    if (cap_frames > 0) {
+      nf = fc.take(stream, c->out_frames, (unsigned long long)cap_frames, [&](size_t k, size_t slot, size_t m) -> int {
+        HIPCHK(hipMemcpy((char *)pcm + k * fb, c->d_out_pcm.p + ((size_t)stream * fc.L + slot) * fb, m * fb, hipMemcpyDeviceToHost));
+        return FMR_OK;
+      });
+      if (nf < 0) return nf;
+    }
+    int nb = 0;
+    bc.catch_up(stream, c->out_recs);
+    if (cap_blocks > 0) {
+      nb = bc.take(stream, c->out_recs, (unsigned long long)cap_blocks, [&](size_t k, size_t slot, size_t m) -> int {
+        HIPCHK(hipMemcpy(blocks + k, c->d_out_rec.p + (size_t)stream * bc.L + slot, m * sizeof(fmr_output_block), hipMemcpyDeviceToHost));
+        return FMR_OK;
+      });
+      if (nb < 0) return nb;
+    }
+    if (n_frames) *n_frames = (size_t)nf;
+    if (info) {
+      fmr_output_info full{};
+      full.struct_size = (unsigned)sizeof full;
+      full.format = c->out_cfg.format;
+      full.channels = c->stereo ? 2 : 1;
+      full.first_frame = first;
+      full.frames_waiting = c->out_frames - fc.read[stream];
+      full.frames_dropped = fc.dropped[stream];
+      full.blocks_waiting = c->out_recs - bc.read[stream];
+      full.blocks_dropped = bc.dropped[stream];
+      give_sized(info, info_size, full);
+    }
+    return nb;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
 // ---- audio monitor: C-ABI ----

@@ -2252,7 +2252,7 @@ __global__ __launch_bounds__(FMR_STATS_THREADS) void k_stats(BlockTab bt, const 
                                               const float *__restrict__ bb_mean_blk,
                                               const float *__restrict__ bb_rms_blk, StreamState *st, int n_streams,
                                               int has_disc, const FusedPart *__restrict__ part = nullptr, int n_tiles = 0,
-                                              int kb_ref = 0) {
+                                              int kb_ref = 0, float *__restrict__ if_rms_out = nullptr) {
   // One workgroup per stream.  Phase 1, all waves: a lane per block fetches (or, behind the fused front end, sums from the
   // partial sums, index order: deterministic) the block's three values -- every load of up to 512 blocks in flight at
   // once; with one wave doing 64 blocks at a time this was 0.15-0.2 ms of memory latency.  Phase 2, wave 0: the EMA
@@ -2275,6 +2275,29 @@ __global__ __launch_bounds__(FMR_STATS_THREADS) void k_stats(BlockTab bt, const 
       if (seen >= 400) { b_first = b0; break; }
     }
   }
+  // if_rms_out != nullptr (the output stage, kernels_output.hpp): every block's IF RMS goes there, also that of the blocks
+  // before b_first, which the chain below never sees -- the same values in the same summation order, and nothing of the
+  // walk below changes
+  if (if_rms_out)
+    for (int b = threadIdx.x; b < b_first; b += NT) {
+      const int n = bt.if_len[b];
+      float v = 0.f;
+      if (n && part) {
+        float se = 0.f;
+        const int lo = bt.if_off[b], hi = lo + n - 1, ng = 3 * n_tiles;
+        const int g0 = (lo - kb_ref) / 128, g1 = min((hi - kb_ref) / 128, ng - 1);
+        for (int g = g0; g <= g1; g++) {
+          const FusedPart pt = part[(long long)s * ng + g];
+#pragma unroll
+          for (int h = 0; h < 2; h++)
+            if (pt.blk[h] == b) se += pt.sum[h][2];
+        }
+        v = sqrtf(se / (float)(unsigned)n);
+      } else if (n) {
+        v = if_rms_blk[(long long)s * bt.nb + b];
+      }
+      if_rms_out[(long long)s * bt.nb + b] = v;
+    }
   for (int b0 = b_first; b0 < bt.nb; b0 += NT) {
     const int b = min(b0 + (int)threadIdx.x, bt.nb - 1);
     const int my_n = (b0 + (int)threadIdx.x < bt.nb) ? bt.if_len[b] : 0;
@@ -2306,6 +2329,7 @@ __global__ __launch_bounds__(FMR_STATS_THREADS) void k_stats(BlockTab bt, const 
       my_m = bb_mean_blk[(long long)s * bt.nb + b];
       my_l = bb_rms_blk[(long long)s * bt.nb + b];
     }
+    if (if_rms_out && b0 + (int)threadIdx.x < bt.nb) if_rms_out[(long long)s * bt.nb + b] = my_r;
     __syncthreads();                     // (the previous stage's chain has read its values)
     s_n[threadIdx.x] = my_n; s_r[threadIdx.x] = my_r; s_m[threadIdx.x] = my_m; s_l[threadIdx.x] = my_l;
     __syncthreads();

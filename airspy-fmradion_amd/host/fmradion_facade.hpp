@@ -176,7 +176,44 @@ inline std::vector<RfRecord> rf_records(fmr_chain *c, int stream) {
   }
   return out;
 }
+
+// output stage (fmr_enable_output / fmr_output_read): everything that waits on one stream -- the PCM frames as bytes
+// (interleaved int16 or float32, what AudioFileWriter::write_i16 / write_f32 take as they are) and the block records
+struct OutputData {
+  std::vector<unsigned char> pcm;
+  size_t frames = 0;
+  std::vector<fmr_output_block> blocks;
+  fmr_output_info info{};
+  const int16_t *s16() const { return reinterpret_cast<const int16_t *>(pcm.data()); }   // format FMR_PCM_S16
+  const float *f32() const { return reinterpret_cast<const float *>(pcm.data()); }       // format FMR_PCM_F32
+  size_t samples() const { return frames * (size_t)info.channels; }
+};
+inline fmr_output_config output_config(int format, double squelch_level, double gain, uint32_t max_frames, uint32_t max_blocks) {
+  fmr_output_config m{};
+  m.struct_size = sizeof m; m.format = format; m.squelch_level = squelch_level; m.gain = gain;
+  m.max_frames = max_frames; m.max_blocks = max_blocks;
+  return m;
+}
+inline void output(fmr_chain *c, const fmr_output_config &m) {
+  check(fmr_enable_output(c, &m, sizeof m), "fmr_enable_output");
+}
+inline OutputData output_data(fmr_chain *c, int stream) {
+  OutputData out;
+  int rc = fmr_output_read(c, stream, nullptr, 0, nullptr, 0, nullptr, &out.info, sizeof out.info);
+  if (rc < 0) check(rc, "fmr_output_read");
+  const size_t fb = (size_t)out.info.channels * (out.info.format == FMR_PCM_F32 ? 4 : 2);
+  out.pcm.resize((size_t)out.info.frames_waiting * fb);
+  out.blocks.resize((size_t)out.info.blocks_waiting);
+  if (out.pcm.empty() && out.blocks.empty()) return out;
+  rc = fmr_output_read(c, stream, out.pcm.data(), (size_t)out.info.frames_waiting, out.blocks.data(), (int)out.blocks.size(),
+                       &out.frames, &out.info, sizeof out.info);
+  if (rc < 0) check(rc, "fmr_output_read");
+  out.pcm.resize(out.frames * fb);
+  out.blocks.resize((size_t)rc);
+  return out;
+}
 }  // namespace fmr_detail
+using OutputData = fmr_detail::OutputData;
 using RfRecord = fmr_detail::RfRecord;
 using ModulationRecord = fmr_detail::ModulationRecord;
 using LoudnessReport = fmr_detail::LoudnessReport;
@@ -317,6 +354,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
+    if (m_out) fmr_detail::output(m_chain, m_out_cfg);
   }
 
   // RDS (no counterpart in the reference; fmr_create_rds): re-creates the chain with the RDS decoder, before the first
@@ -329,6 +367,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
+    if (m_out) fmr_detail::output(m_chain, m_out_cfg);
   }
   // error correction of the RDS blocks (fmr_set_rds_correction: FMR_RDS_FEC_OFF / _BURST / _SOFT; 0 = the defaults); at
   // any time after enable_rds(), from the decoder's next block boundary on.  enable_rds() starts with it off.
@@ -375,6 +414,19 @@ public:
   }
   std::vector<RfRecord> read_rf_records() { return fmr_detail::rf_records(m_chain, 0); }
 
+  // Output stage (what main.cpp:976-1002 does behind the decoder, on the device; fmr_enable_output): the squelched and
+  // scaled audio as FMR_PCM_S16 / FMR_PCM_F32 frames and one record per block with the IF / AF meters; before the first
+  // process(), once.  squelch_level is linear (fmr_squelch_level_from_db gives it from -l dB; 0 = never closed), gain 0 =
+  // 0.5.  read_output() drains everything that waits.
+  void enable_output(int format = FMR_PCM_S16, double squelch_level = 0.0, double gain = 0.0, uint32_t max_frames = 0,
+                     uint32_t max_blocks = 0) {
+    if (m_started) fmr_detail::fail("FmDecoder::enable_output: after the first process()");
+    m_out_cfg = fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks);
+    fmr_detail::output(m_chain, m_out_cfg);
+    m_out = true;
+  }
+  OutputData read_output() { return fmr_detail::output_data(m_chain, 0); }
+
   // Latency for throughput: hold back `blocks` - 1 calls and decode `blocks` blocks in ONE batched call.  process()
   // then returns an empty vector ("nothing yet": the contract of FmDecode.cpp:89-92,185-188, which main.cpp:981-984
   // already handles) until the batch is full, and the audio of all its blocks at once.  One 65536-sample block per
@@ -397,6 +449,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
+    if (m_out) fmr_detail::output(m_chain, m_out_cfg);
       m_capacity = blocks;
     }
     m_batch = blocks;
@@ -495,6 +548,8 @@ private:
   fmr_loudness_config m_ld_cfg{};
   bool m_rf = false;
   fmr_rf_monitor_config m_rf_cfg{};
+  bool m_out = false;
+  fmr_output_config m_out_cfg{};
   fmr_chain *m_chain = nullptr;
   bool m_rds = false;
   fmr_rds::Station m_station;
@@ -531,7 +586,17 @@ public:
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg);
+    if (m_out) fmr_detail::output(m_chain, m_out_cfg);
   }
+  // Output stage (fmr_enable_output): squelch, gain, PCM frames and the per-block IF / AF meters on the device; before
+  // the first process(), once.  read_output() drains everything that waits.
+  void enable_output(int format = FMR_PCM_S16, double squelch_level = 0.0, double gain = 0.0, uint32_t max_frames = 0,
+                     uint32_t max_blocks = 0) {
+    m_out_cfg = fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks);
+    fmr_detail::output(m_chain, m_out_cfg);
+    m_out = true;
+  }
+  OutputData read_output() { return fmr_detail::output_data(m_chain, 0); }
   void process(IQSampleVector samples_in, SampleVector &audio) {
     audio.resize(samples_in.size() + 64);
     size_t n = 0;
@@ -552,6 +617,8 @@ private:
     return st;
   }
   fmr_config m_cfg{};
+  bool m_out = false;
+  fmr_output_config m_out_cfg{};
   fmr_chain *m_chain = nullptr;
 };
 
@@ -577,7 +644,17 @@ public:
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg);
+    if (m_out) fmr_detail::output(m_chain, m_out_cfg);
   }
+  // Output stage (fmr_enable_output): squelch, gain, PCM frames and the per-block IF / AF meters on the device; before
+  // the first process(), once.  read_output() drains everything that waits.
+  void enable_output(int format = FMR_PCM_S16, double squelch_level = 0.0, double gain = 0.0, uint32_t max_frames = 0,
+                     uint32_t max_blocks = 0) {
+    m_out_cfg = fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks);
+    fmr_detail::output(m_chain, m_out_cfg);
+    m_out = true;
+  }
+  OutputData read_output() { return fmr_detail::output_data(m_chain, 0); }
   void process(const IQSampleVector &samples_in, SampleVector &audio) {
     audio.resize(samples_in.size() + 64);
     size_t n = 0;
@@ -598,6 +675,8 @@ private:
   }
   const double m_freq_dev;
   fmr_config m_cfg{};
+  bool m_out = false;
+  fmr_output_config m_out_cfg{};
   fmr_chain *m_chain = nullptr;
 };
 
@@ -644,6 +723,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
+    if (m_out) fmr_detail::output(m_chain, m_out_cfg);
     m_stations.assign(m_offsets.size(), fmr_rds::Station());
   }
   // error correction of every channel's RDS blocks (fmr_set_rds_correction), at any time after enable_rds()
@@ -693,6 +773,19 @@ public:
   std::vector<RfRecord> read_rf_records(size_t ch) {
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
     return fmr_detail::rf_records(m_chain, (int)ch);
+  }
+
+  // Output stage of every channel (fmr_enable_output), before the first process(), once; banks of every mode.
+  // read_output(ch) drains channel ch's PCM frames and block records.
+  void enable_output(int format = FMR_PCM_S16, double squelch_level = 0.0, double gain = 0.0, uint32_t max_frames = 0,
+                     uint32_t max_blocks = 0) {
+    m_out_cfg = fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks);
+    fmr_detail::output(m_chain, m_out_cfg);
+    m_out = true;
+  }
+  OutputData read_output(size_t ch) {
+    if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
+    return fmr_detail::output_data(m_chain, (int)ch);
   }
 
   // audio[k] = what channel k produced from this capture block (empty = "nothing yet"); blocks longer than the chain's
@@ -749,6 +842,8 @@ private:
   fmr_loudness_config m_ld_cfg{};
   bool m_rf = false;
   fmr_rf_monitor_config m_rf_cfg{};
+  bool m_out = false;
+  fmr_output_config m_out_cfg{};
   fmr_chain *m_chain = nullptr;
 };
 

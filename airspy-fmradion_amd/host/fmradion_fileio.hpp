@@ -216,6 +216,13 @@ public:
     m_bytes += 4 * (uint64_t)n;
     return refresh();
   }
+  // int16 formats: n samples as they are (interleaved), e.g. the S16 PCM drained from the output stage (fmr_output_read)
+  bool write_i16(const int16_t *v, size_t n) {
+    if (!m_fp || (m_fmt != AudioFormat::RAW_INT16 && m_fmt != AudioFormat::WAV_INT16)) return false;
+    if (n && std::fwrite(v, 2, n, m_fp) != n) { m_error = "write failed"; return false; }
+    m_bytes += 2 * (uint64_t)n;
+    return refresh();
+  }
   void close() {
     if (!m_fp) return;
     if (is_wav()) {

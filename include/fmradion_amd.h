@@ -796,6 +796,77 @@ int fmr_rf_monitor_read(fmr_chain *c, int stream, fmr_rf_monitor_record *recs, u
 int fmr_rf_monitor_derive(const fmr_rf_monitor_record *recs, const uint32_t *hist, const double *psd, int n,
                           fmr_rf_monitor_levels *out, size_t out_size);
 
+/* --- Output stage: what the reference's stream loop does behind the decoder (main.cpp:950-1002),
+ * on the device.  A decoder chain of any mode with it enabled delivers, per stream / bank channel, the squelched and scaled
+ * audio as S16 or F32 PCM -- the bytes -R / -W and -F / -G put into the file -- and one small record per block with the
+ * loop's meters (the "IF=...dB AF=...dB" pair).  The chain's double audio, fmr_status, PPS events, RDS groups and every
+ * monitor's records are what they are without it: the stage only reads the finished audio and the blocks' IF RMS.
+ * Everything below is per stream, runs over the blocks handed to the chain since create, in order, and does not depend
+ * on how the blocks are grouped into calls.
+ * Blocks and frames: `block` counts every block handed in, 0-based, empty ones included.  A block that yields no IF
+ * sample leaves no record and changes no state (main.cpp:933-936).  A frame is one audio sample per channel; channels
+ * is 2 for a stereo FM chain (interleaved L/R) and 1 otherwise.  first_frame is the absolute index of the block's first
+ * audio frame, n_frames the number of its frames (0 for a block with IF samples that completes no audio sample).
+ * if_rms: the decoder's get_if_rms() after this block, as float32 -- the very bits fmr_status.if_rms reads when a call
+ * ends at this block.
+ * if_level = (float)(0.75 (double)if_level + 0.25 (double)if_rms), from 0, for every block with IF samples (main.cpp:976).
+ * gate_open = ((double)if_rms >= squelch_level), also for a block without audio.
+ * Audio meters (main.cpp:989-996), when n_frames > 0, over the block's n = channels n_frames audio doubles before the
+ * gain: each is narrowed to float32, x_f = (float)x; S1 = sum x_f and S2 = sum x_f^2 in fp64 (x_f^2 the fp64 product) in
+ * a fixed order: partial t, t = 0 .. 255, adds the frames t, t + 256, ... in ascending order, channel 0 before channel 1;
+ * the partials 64 w .. 64 w + 63 are joined by a butterfly (lane i adds lane i xor 32, then 16, 8, 4, 2, 1), the four
+ * results added in ascending w.  audio_mean = (float)(S1 / n), audio_rms = (float)sqrt(S2 / n),
+ * audio_level = (float)(0.95 (double)audio_level + 0.05 (double)audio_rms), from 0.  A block without audio repeats the
+ * previous audio_level and has audio_mean = audio_rms = 0.
+ * PCM: y = x g in fp64, g = gain when the gate is open and 0.0 when it is closed (adjust_gain, main.cpp:999-1002).
+ *   FMR_PCM_S16: rint(y 32767.0), ties to even (AudioFileWriter's lrint(x * 32767)), saturated to [-32768, 32767]; every
+ *     saturated sample counts in n_clipped (+-Inf among them); NaN becomes 0; NaN and +-Inf count in n_nonfinite.  The
+ *     result differs from AudioFileWriter's only where that one overflows.
+ *   FMR_PCM_F32: (float)y, non-finite values passed through and counted in n_nonfinite; n_clipped counts |y| > 1.
+ * n_clipped and n_nonfinite count the values of all of the block's frames, per channel value.
+ * PCM ring: max_frames interleaved frames per stream, frame f at slot f mod max_frames.  When unread frames would be
+ * overwritten the oldest are dropped and counted in frames_dropped; frames that later frames of the same call overwrite
+ * are never written.  Record ring: max_blocks records per stream by the same rule (blocks_dropped).  Processing never
+ * fails because of either.  The read positions live on the host. */
+enum { FMR_PCM_S16 = 0, FMR_PCM_F32 = 1 };
+typedef struct {
+  unsigned struct_size;       /* sizeof(fmr_output_config) as the caller knows it (0: cfg_size); a larger size is refused */
+  int format;                 /* FMR_PCM_S16 or FMR_PCM_F32 */
+  double squelch_level;       /* linear, finite, >= 0; 0 = never closed (the reference's default: if_rms >= 0) */
+  double gain;                /* finite, > 0; 0 = 0.5 (-6 dB, main.cpp:1000) */
+  uint32_t max_frames;        /* PCM ring per stream in frames: 1 .. 2^26; 0 = 2^18 */
+  uint32_t max_blocks;        /* record ring per stream: 1 .. 65536; 0 = 4096 */
+} fmr_output_config;
+typedef struct {
+  uint64_t block, first_frame;
+  uint32_t n_frames, channels;
+  float if_rms, if_level, audio_mean, audio_rms, audio_level;
+  uint32_t gate_open, n_clipped, n_nonfinite;
+} fmr_output_block;
+typedef struct {
+  unsigned struct_size;
+  int format, channels;
+  uint64_t first_frame;           /* absolute index of the first frame this call returned, or of the next one if none */
+  uint64_t frames_waiting;        /* frames / records still unread after this call */
+  uint64_t frames_dropped;        /* of this stream: overwritten unread, since create */
+  uint64_t blocks_waiting, blocks_dropped;
+} fmr_output_info;
+/* Checks the fields first (FMR_ERR_BAD_ARG, fmr_last_error names the field; also a size larger than this library's
+ * struct), then the chain: NULL is FMR_ERR_BAD_ARG; any chain with a decoder is accepted (every mode, banks, pipelined
+ * or in_order); front-end-only chains (mode -1, channelizers) are FMR_ERR_UNSUPPORTED.  Allowed once, before the chain's
+ * first block: a second call, or one after any processing call, is FMR_ERR_BAD_ARG.  A chain that never calls it
+ * allocates nothing for the stage and runs none of its kernels. */
+int fmr_enable_output(fmr_chain *c, const fmr_output_config *cfg, size_t cfg_size);
+/* Synchronises like the other getters, then drains up to cap_frames frames of `stream`, oldest first, into pcm
+ * (interleaved int16 or float32; *n_frames, if not NULL, takes their number) and up to cap_blocks records into blocks;
+ * the two drains are independent.  Returns the number of records drained.  cap_frames = 0 and cap_blocks = 0 drain
+ * nothing: info (may be NULL; info_size bytes, 0 = this header's size) says what waits.  FMR_ERR_BAD_ARG for pcm = NULL
+ * with cap_frames > 0, blocks = NULL with cap_blocks > 0, a bad stream index and a chain without the stage. */
+int fmr_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, fmr_output_block *blocks, int cap_blocks,
+                    size_t *n_frames, fmr_output_info *info, size_t info_size);
+/* pow(10, -(db / 20)): the linear squelch level of the reference's -l option (main.cpp:486).  Host only. */
+double fmr_squelch_level_from_db(double db);
+
 #ifdef __cplusplus
 }
 #endif
