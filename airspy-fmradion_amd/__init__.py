@@ -9,6 +9,7 @@ The directory name carries a hyphen (the contract's package name), so import it
 with importlib:  fmr = importlib.import_module("airspy-fmradion_amd").
 """
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -52,6 +53,7 @@ EXPORTS = [
     "fmr_enable_loudness", "fmr_loudness_read", "fmr_loudness_derive",
     "fmr_enable_rf_monitor", "fmr_rf_monitor_read", "fmr_rf_monitor_derive",
     "fmr_enable_output", "fmr_output_read", "fmr_squelch_level_from_db",
+    "fmr_set_output_rate", "fmr_get_output_rate", "fmr_output_rate_taps",
 ]
 # FMR_WINDOW_* (include/fmradion_amd.h): windows of the band spectrum
 WINDOW_HANN, WINDOW_RECT, WINDOW_BLACKMAN_HARRIS = 0, 1, 2
@@ -90,6 +92,25 @@ OUTPUT_BLOCK = np.dtype([("block", np.uint64), ("first_frame", np.uint64), ("n_f
 
 class FmrError(RuntimeError):
     pass
+
+
+def output_rate_taps(rate):
+    """fmr_output_rate_taps: (h float64 [T L], L, M, T) -- the prototype filter of the output stage at `rate` (host only)."""
+    Lb = lib()
+    l, m, t = C.c_int(), C.c_int(), C.c_int()
+    n = Lb.fmr_output_rate_taps(int(rate), None, 0, C.byref(l), C.byref(m), C.byref(t))
+    if n < 0:
+        raise FmrError(f"fmradion_amd error {n}: {Lb.fmr_last_error().decode()}")
+    h = np.zeros(n, dtype=np.float64)
+    Lb.fmr_output_rate_taps(int(rate), h.ctypes.data_as(C.POINTER(C.c_double)), n, None, None, None)
+    return h, l.value, m.value, t.value
+
+
+def output_frame_of(first_frame, rate):
+    """The first ring frame made from a block whose first_frame is `first_frame`: ceil(first_frame L / M)."""
+    g = math.gcd(int(rate) if rate else 48000, 48000)
+    l, m = (int(rate) if rate else 48000) // g, 48000 // g
+    return -(-int(first_frame) * l // m)
 
 
 class Config(C.Structure):
@@ -228,6 +249,16 @@ class OutputInfo(C.Structure):
                 ("blocks_dropped", C.c_uint64)]
 
 
+class OutputRateConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("rate", C.c_int), ("mono", C.c_int), ("reserved", C.c_int)]
+
+
+class OutputRateInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("rate", C.c_int), ("channels", C.c_int), ("L", C.c_int), ("M", C.c_int),
+                ("taps_per_phase", C.c_int), ("delay_frames", C.c_double), ("frames_in", C.c_uint64),
+                ("pcm_clipped", C.c_uint64), ("pcm_nonfinite", C.c_uint64)]
+
+
 def build_library(force=False, verbose=False):
     """Compile the HIP library (and its A/B partner build) in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     import glob
@@ -346,6 +377,12 @@ def lib(ab=False):
     L.fmr_rf_monitor_derive.argtypes = [vp, vp, vp, C.c_int, C.POINTER(RfMonitorLevels), C.c_size_t]
     L.fmr_enable_output.restype = C.c_int
     L.fmr_enable_output.argtypes = [vp, C.POINTER(OutputConfig), C.c_size_t]
+    L.fmr_set_output_rate.restype = C.c_int
+    L.fmr_set_output_rate.argtypes = [vp, C.POINTER(OutputRateConfig), C.c_size_t]
+    L.fmr_get_output_rate.restype = C.c_int
+    L.fmr_get_output_rate.argtypes = [vp, C.c_int, C.POINTER(OutputRateInfo), C.c_size_t]
+    L.fmr_output_rate_taps.restype = C.c_int
+    L.fmr_output_rate_taps.argtypes = [C.c_int, dp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.fmr_output_read.restype = C.c_int
     L.fmr_output_read.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, C.c_int, C.POINTER(C.c_size_t), C.POINTER(OutputInfo),
                                   C.c_size_t]
@@ -765,16 +802,32 @@ class Chain:
         return self._read_records(self._L.fmr_rf_monitor_read, RfMonitorInfo, ((RF_MONITOR_RECORD, None), (np.uint32, RF_HIST_BINS),
                                                                                 (np.float64, RF_PSD_BINS)), stream, cap)
 
-    def enable_output(self, format="s16", squelch_db=None, gain=0.0, max_frames=0, max_blocks=0, squelch_level=None):
+    def enable_output(self, format="s16", squelch_db=None, gain=0.0, max_frames=0, max_blocks=0, squelch_level=None,
+                      rate=None, mono=False):
         """fmr_enable_output: the output stage of every stream / channel (any decoder chain, once, before the first call).
         format "s16" | "f32" (or PCM_S16 / PCM_F32); squelch_db as the reference's -l option (None: never closed), or
-        squelch_level, the linear level itself; 0 = the defaults (gain 0.5, 2^18 frames and 4096 records kept)."""
+        squelch_level, the linear level itself; 0 = the defaults (gain 0.5, 2^18 frames and 4096 records kept).
+        rate (Hz) and / or mono: fmr_set_output_rate behind it -- the PCM ring at that rate and / or downmixed."""
         fmt = {"s16": PCM_S16, "f32": PCM_F32}.get(format, format)
         level = 0.0 if squelch_db is None else squelch_level_from_db(squelch_db)
         if squelch_level is not None:
             level = float(squelch_level)
         cfg = OutputConfig(C.sizeof(OutputConfig), int(fmt), level, float(gain), int(max_frames), int(max_blocks))
         self._chk(self._L.fmr_enable_output(self.h, C.byref(cfg), C.sizeof(OutputConfig)))
+        if rate is not None or mono:
+            self.set_output_rate(0 if rate is None else rate, mono)
+
+    def set_output_rate(self, rate=0, mono=False):
+        """fmr_set_output_rate: once, behind enable_output and before the first call."""
+        cfg = OutputRateConfig(C.sizeof(OutputRateConfig), int(rate), int(mono), 0)
+        self._chk(self._L.fmr_set_output_rate(self.h, C.byref(cfg), C.sizeof(OutputRateConfig)))
+
+    def output_rate_info(self, stream=0):
+        """fmr_get_output_rate as a dict: rate, channels, L, M, taps_per_phase, delay_frames, frames_in, pcm_clipped,
+        pcm_nonfinite."""
+        info = OutputRateInfo()
+        self._chk(self._L.fmr_get_output_rate(self.h, int(stream), C.byref(info), C.sizeof(OutputRateInfo)))
+        return {k: getattr(info, k) for k, _ in OutputRateInfo._fields_ if k != "struct_size"}
 
     def output_read(self, stream=0, cap_frames=None, cap_blocks=None):
         """fmr_output_read: the oldest unread PCM frames (at most cap_frames; None: all that wait) and block records (at most

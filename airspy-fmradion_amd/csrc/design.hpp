@@ -303,6 +303,47 @@ struct ResamplerCounter {
   }
 };
 
+// Prototype filter of the output stage's rate converter (fmr_set_output_rate): 48000 -> rate
+// by L / M in lowest terms, a Kaiser-windowed sinc at rate 48000 L.  Design attenuation 110 dB, cutoff 0.95 rate / 2,
+// transition 0.05 rate; the Kaiser length estimate N is rounded up to T L taps (T per phase) and the window spans all of
+// them.  Tap i < T L / 2 is computed and scaled, tap T L - 1 - i is a copy of it: the two are the same bits.  Scaled to
+// sum h = L (each of the L phases has unit DC gain to 1e-6).  rate 48000: L = M = T = 1, h = {1}.  False for a rate
+// outside 8000 .. 48000 or with L > 160.
+constexpr int kOutRateIn = 48000, kOutRateMin = 8000, kOutRateMaxL = 160;
+inline bool design_output_rate(int rate, int &L, int &M, int &T, std::vector<double> *taps) {
+  if (rate < kOutRateMin || rate > kOutRateIn) return false;
+  const long long g = gcd_ll(rate, kOutRateIn);
+  if (rate / g > kOutRateMaxL) return false;
+  L = (int)(rate / g); M = (int)(kOutRateIn / g);
+  if (rate == kOutRateIn) {
+    T = 1;
+    if (taps) taps->assign(1, 1.0);
+    return true;
+  }
+  const double A = 110.0, beta = 0.1102 * (A - 8.7);
+  const double hi_rate = (double)kOutRateIn * L;
+  const double dw = 2.0 * M_PI * 0.05 * rate / hi_rate;
+  const long long N = (long long)std::ceil((A - 7.95) / (2.285 * dw)) + 1;
+  T = (int)((N + L - 1) / L);
+  if (!taps) return true;
+  const long long n = (long long)T * L;
+  const double c = 0.5 * (double)(n - 1), fc = 0.95 * 0.5 * rate / hi_rate, i0b = bessel_i0(beta);
+  std::vector<double> &h = *taps;
+  h.assign((size_t)n, 0.0);
+  double sum = 0.0;      // over the whole filter: the first half twice, the middle tap of an odd length once
+  for (long long i = 0; 2 * i < n; i++) {
+    const double t = (double)i - c, r = t / c;
+    h[(size_t)i] = 2.0 * fc * sinc_pi(2.0 * fc * t) * bessel_i0(beta * std::sqrt(std::fmax(0.0, 1.0 - r * r))) / i0b;
+    sum += (2 * i == n - 1) ? h[(size_t)i] : 2.0 * h[(size_t)i];
+  }
+  const double scale = (double)L / sum;
+  for (long long i = 0; 2 * i < n; i++) {
+    h[(size_t)i] *= scale;
+    h[(size_t)(n - 1 - i)] = h[(size_t)i];
+  }
+  return true;
+}
+
 struct Iir1Coef { double b0, b1, a1; };
 struct BiquadCoef { double b0, b1, b2, a1, a2; };
 

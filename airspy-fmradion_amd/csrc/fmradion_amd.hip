@@ -460,7 +460,22 @@ struct fmr_chain {
   DevBuf<OutRec> d_out_rec;                  // [S][max_blocks of the config]
   DevBuf<unsigned char> d_out_pcm;           // [S][max_frames] frames
   RecCursor out_fcur, out_bcur;              // frames, records
-  size_t out_frame_bytes() const { return (size_t)(stereo ? 2 : 1) * (out_cfg.format == FMR_PCM_F32 ? 4 : 2); }
+  // rate converter (fmr_set_output_rate): with out_conv the ring is written by k_out_rate from the
+  // staged z instead of by k_out_pcm, out_oframes counts its frames, and the stream's clip / non-finite totals live in
+  // d_out_tot.  Two staging rows: a call's z goes behind the T - 1 frames of history at the head of row out_zpar, and
+  // what it leaves as history to the head of the other row.  Nothing of it exists without the call.
+  bool out_rate_set = false, out_conv = false;
+  int out_hz = kOutRateIn;
+  OutRateGeom out_geom{1, 1, 1, 0, 0, 0};
+  unsigned long long out_oframes = 0;
+  int out_zpar = 0;
+  DevBuf<double> d_out_z, d_out_taps;        // [2][S][zstride]; the prototype, T L
+  DevBuf<unsigned long long> d_out_tot;      // [S][2]
+  int out_channels() const { return stereo && !(out_conv && out_mono) ? 2 : 1; }     // of the ring
+  bool out_mono = false;
+  unsigned long long out_produced() const { return out_conv ? out_oframes : out_frames; }   // ring frames
+  int out_rate_init(int rate, bool mono);
+  size_t out_frame_bytes() const { return (size_t)out_channels() * (out_cfg.format == FMR_PCM_F32 ? 4 : 2); }
   float *out_ifrms_slot(int q) { return out ? d_out_ifrms.p + (size_t)q * S * max_blocks : nullptr; }
   int out_init(const fmr_output_config &m);
   OutArgs out_begin(unsigned long long block0, const int *if_len, int nb, long long N_au);
@@ -574,6 +589,7 @@ struct fmr_chain {
     d_ld_pw.release(); d_ld_taps.release(); d_ld_G.release(); d_ld_start.release(); d_ld_pkw.release(); d_ld_state.release();
     d_ld_hist.release(); d_ld_part.release(); d_ld_open.release(); d_ld_ring.release();
     d_out_ifrms.release(); d_out_part.release(); d_out_state.release(); d_out_rec.release(); d_out_pcm.release();
+    d_out_z.release(); d_out_taps.release(); d_out_tot.release();
     if (h_rds_slots) (void)hipHostFree(h_rds_slots);
     if (h_rds_mark) (void)hipHostFree(h_rds_mark);
     if (h_tab_all) (void)hipHostFree(h_tab_all);
@@ -3129,6 +3145,26 @@ int fmr_chain::out_init(const fmr_output_config &m) {
   return FMR_OK;
 }
 
+// the rate converter of an enabled stage, before the first block: the prototype, the two staging rows, the totals
+int fmr_chain::out_rate_init(int rate, bool mono) {
+  std::vector<double> h;
+  OutRateGeom gm{};
+  if (!design_output_rate(rate, gm.L, gm.M, gm.T, &h)) { set_err("fmr_set_output_rate: rate %d has no design", rate); return FMR_ERR_BAD_ARG; }
+  out_hz = rate; out_mono = mono; out_conv = true;
+  const int och = out_channels();
+  gm.span = (int)(((long long)(kOutThreads - 1) * gm.M) / gm.L) + 1 + gm.T;
+  gm.zstride = ((long long)(gm.T - 1) + (long long)max_au) * och;
+  gm.zrow = (long long)S * gm.zstride;
+  out_geom = gm;
+  int rc;
+  if ((rc = d_out_taps.alloc(h.size()))) return rc;
+  HIPCHK(hipMemcpy(d_out_taps.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  if ((rc = d_out_z.alloc((size_t)2 * gm.zrow))) return rc;      // (zeroed: z[j] = +0.0 for j < 0)
+  if ((rc = d_out_tot.alloc((size_t)2 * S))) return rc;
+  out_oframes = 0; out_zpar = 0;
+  return FMR_OK;
+}
+
 // the positions of one call (block0: absolute index of its first block), taken when it is issued; advances the counters
 OutArgs fmr_chain::out_begin(unsigned long long block0, const int *if_len, int nb, long long N_au) {
   OutArgs a{};
@@ -3138,6 +3174,14 @@ OutArgs fmr_chain::out_begin(unsigned long long block0, const int *if_len, int n
   a.squelch = out_cfg.squelch_level; a.gain = out_cfg.gain;
   a.max_frames = out_cfg.max_frames; a.max_blocks = out_cfg.max_blocks;
   out_frames += a.n_frames; out_recs += a.n_recs;
+  if (out_conv) {      // ring frames: ceil(F L / M) after F decoder frames
+    const unsigned long long L = (unsigned long long)out_geom.L, M = (unsigned long long)out_geom.M;
+    a.out0 = out_oframes;
+    out_oframes = (out_frames * L + M - 1) / M;
+    a.n_out = out_oframes - a.out0;
+    a.zpar = out_zpar;
+    if (a.n_frames > 0) out_zpar ^= 1;      // (a call without audio launches nothing: the history stays where it is)
+  }
   return a;
 }
 
@@ -3150,8 +3194,8 @@ int fmr_chain::out_stage(const double *d_aud, long long astride, const BlockTab 
   if (a.n_frames > 0)
     timed_on(st, "out_pcm", [&] {
       auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(bt.nb, S), dim3(kOutThreads), 0, st, d_aud, astride, bt, if_rms_blk, a, (void *)d_out_pcm.p,
-                           d_out_part.p);
+        hipLaunchKernelGGL(kern, dim3(bt.nb, S), dim3(kOutThreads), 0, st, d_aud, astride, bt, if_rms_blk, a,
+                           out_conv ? (void *)nullptr : (void *)d_out_pcm.p, d_out_part.p);
       };
       if (out_cfg.format == FMR_PCM_F32) { if (ch == 2) go(k_out_pcm<1, 2>); else go(k_out_pcm<1, 1>); }
       else { if (ch == 2) go(k_out_pcm<0, 2>); else go(k_out_pcm<0, 1>); }
@@ -3160,6 +3204,32 @@ int fmr_chain::out_stage(const double *d_aud, long long astride, const BlockTab 
     hipLaunchKernelGGL(k_out_blocks, dim3(S), dim3(64), 0, st, bt, if_rms_blk, (const OutPart *)d_out_part.p, a, ch, d_out_state.p,
                        d_out_rec.p);
   });
+  if (out_conv && a.n_frames > 0) {
+    const OutRateGeom &gm = out_geom;
+    const int och = out_channels();
+    timed_on(st, "out_z", [&] {
+      auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(bt.nb, S), dim3(kOutThreads), 0, st, d_aud, astride, bt, if_rms_blk, a, gm, d_out_z.p);
+      };
+      if (ch == 1) go(k_out_z<1, 1>); else if (och == 2) go(k_out_z<2, 2>); else go(k_out_z<2, 1>);
+    });
+    if (a.n_out > 0)
+      timed_on(st, "out_rate", [&] {
+        const size_t lds = (size_t)gm.span * och * sizeof(double) + 2 * (kOutThreads / 64) * sizeof(unsigned);
+        auto go = [&](auto kern) {
+          hipLaunchKernelGGL(kern, dim3((unsigned)((a.n_out + kOutThreads - 1) / kOutThreads), S), dim3(kOutThreads), lds, st,
+                             (const double *)d_out_z.p, (const double *)d_out_taps.p, gm, a, (void *)d_out_pcm.p, d_out_tot.p);
+        };
+        if (out_cfg.format == FMR_PCM_F32) { if (och == 2) go(k_out_rate<1, 2>); else go(k_out_rate<1, 1>); }
+        else { if (och == 2) go(k_out_rate<0, 2>); else go(k_out_rate<0, 1>); }
+      });
+    const int hist = (gm.T - 1) * och;
+    if (hist > 0)
+      timed_on(st, "out_hist", [&] {
+        hipLaunchKernelGGL(k_out_hist, dim3((hist + kOutThreads - 1) / kOutThreads, S), dim3(kOutThreads), 0, st, d_out_z.p, gm,
+                           a.zpar, (long long)a.n_frames * och, hist);
+      });
+  }
   HIPCHK(hipGetLastError());
   return FMR_OK;
 }
@@ -4452,11 +4522,11 @@ int fmr_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, fmr_
     if (int rc = c->sync_all()) return rc;
     const size_t fb = c->out_frame_bytes();
     RecCursor &fc = c->out_fcur, &bc = c->out_bcur;
-    fc.catch_up(stream, c->out_frames);
+    fc.catch_up(stream, c->out_produced());
     const unsigned long long first = fc.read[stream];
     int nf = 0;
     if (cap_frames > 0) {
-      nf = fc.take(stream, c->out_frames, (unsigned long long)cap_frames, [&](size_t k, size_t slot, size_t m) -> int {
+      nf = fc.take(stream, c->out_produced(), (unsigned long long)cap_frames, [&](size_t k, size_t slot, size_t m) -> int {
         HIPCHK(hipMemcpy((char *)pcm + k * fb, c->d_out_pcm.p + ((size_t)stream * fc.L + slot) * fb, m * fb, hipMemcpyDeviceToHost));
         return FMR_OK;
       });
@@ -4476,9 +4546,9 @@ int fmr_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, fmr_
       fmr_output_info full{};
       full.struct_size = (unsigned)sizeof full;
       full.format = c->out_cfg.format;
-      full.channels = c->stereo ? 2 : 1;
+      full.channels = c->out_channels();
       full.first_frame = first;
-      full.frames_waiting = c->out_frames - fc.read[stream];
+      full.frames_waiting = c->out_produced() - fc.read[stream];
       full.frames_dropped = fc.dropped[stream];
       full.blocks_waiting = c->out_recs - bc.read[stream];
       full.blocks_dropped = bc.dropped[stream];
@@ -4486,6 +4556,84 @@ int fmr_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, fmr_
     }
     return nb;
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+static int check_output_rate(int rate) {
+  int L, M, T;
+  if (rate < kOutRateMin || rate > kOutRateIn || !design_output_rate(rate, L, M, T, nullptr)) {
+    set_err("fmr_set_output_rate: rate %d is not 0, 48000 or a whole rate in 8000 .. 48000 with L = rate / gcd(rate, 48000) <= %d",
+            rate, kOutRateMaxL);
+    return FMR_ERR_BAD_ARG;
+  }
+  return FMR_OK;
+}
+
+int fmr_set_output_rate(fmr_chain *c, const fmr_output_rate_config *cfg, size_t cfg_size) {
+  if (!cfg) { set_err("fmr_set_output_rate: cfg is null"); return FMR_ERR_BAD_ARG; }
+  fmr_output_rate_config m;
+  if (int rc = take_sized("fmr_set_output_rate", "fmr_output_rate_config", cfg, cfg_size, m)) return rc;
+  if (m.rate == 0) m.rate = kOutRateIn;
+  if (int rc = check_output_rate(m.rate)) return rc;
+  if (m.mono != 0 && m.mono != 1) { set_err("fmr_set_output_rate: mono %d is neither 0 nor 1", m.mono); return FMR_ERR_BAD_ARG; }
+  if (m.reserved != 0) { set_err("fmr_set_output_rate: reserved %d is not 0", m.reserved); return FMR_ERR_BAD_ARG; }
+  if (!c) { set_err("fmr_set_output_rate: chain is null"); return FMR_ERR_BAD_ARG; }
+  if (!c->out) { set_err("fmr_set_output_rate: the chain has no output stage (fmr_enable_output comes first)"); return FMR_ERR_BAD_ARG; }
+  if (c->out_rate_set) { set_err("fmr_set_output_rate: the output rate of this chain is already set"); return FMR_ERR_BAD_ARG; }
+  if (c->call_seq != 0) {
+    set_err("fmr_set_output_rate: the chain has already taken samples (the ring counts from the chain's first block)");
+    return FMR_ERR_BAD_ARG;
+  }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    c->out_rate_set = true;
+    const bool mono = m.mono == 1 && c->stereo;
+    if (m.rate == kOutRateIn && !mono) return FMR_OK;      // the stage as it is
+    return c->out_rate_init(m.rate, mono);
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_get_output_rate(fmr_chain *c, int stream, fmr_output_rate_info *info, size_t info_size) {
+  if (!c || !info || stream < 0 || stream >= c->S) { set_err("fmr_get_output_rate: bad chain, stream or info"); return FMR_ERR_BAD_ARG; }
+  if (!c->out) { set_err("fmr_get_output_rate: the chain has no output stage (fmr_enable_output)"); return FMR_ERR_BAD_ARG; }
+  if ((info_size ? info_size : sizeof(fmr_output_rate_info)) > sizeof(fmr_output_rate_info)) {
+    set_err("fmr_get_output_rate: info_size %zu is larger than this library's fmr_output_rate_info (%zu): the caller is newer than the library",
+            info_size, sizeof(fmr_output_rate_info));
+    return FMR_ERR_BAD_ARG;
+  }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    fmr_output_rate_info full{};
+    full.struct_size = (unsigned)sizeof full;
+    full.rate = c->out_hz; full.channels = c->out_channels();
+    full.L = c->out_geom.L; full.M = c->out_geom.M; full.taps_per_phase = c->out_geom.T;
+    full.delay_frames = full.taps_per_phase > 1 ? ((double)full.taps_per_phase * full.L - 1.0) / (2.0 * full.M) : 0.0;
+    full.frames_in = c->out_frames;
+    if (c->out_conv) {
+      unsigned long long tot[2];
+      HIPCHK(hipMemcpy(tot, c->d_out_tot.p + 2 * (size_t)stream, sizeof tot, hipMemcpyDeviceToHost));
+      full.pcm_clipped = tot[0]; full.pcm_nonfinite = tot[1];
+    }
+    give_sized(info, info_size, full);
+    return FMR_OK;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_output_rate_taps(int rate, double *taps, int cap, int *L, int *M, int *T) {
+  if (rate == 0) rate = kOutRateIn;
+  if (int rc = check_output_rate(rate)) return rc;
+  int l, m, t;
+  std::vector<double> h;
+  design_output_rate(rate, l, m, t, nullptr);
+  if (L) *L = l;
+  if (M) *M = m;
+  if (T) *T = t;
+  const long long n = (long long)t * l;
+  if (taps && (long long)cap >= n) {
+    design_output_rate(rate, l, m, t, &h);
+    memcpy(taps, h.data(), (size_t)n * sizeof(double));
+  }
+  return (int)n;
 }
 
 // ---- audio monitor: C-ABI ----

@@ -15,6 +15,7 @@
 // no atomics: the same audio gives the same bits.  Positions (block, frame and record counters) live on the host and
 // travel as arguments; the device carries the two levels only.  Nothing here waits on another workgroup or on the host.
 // The translation unit is compiled with -ffp-contract=off: every product and sum is rounded by itself.
+// A chain with fmr_set_output_rate adds the three launches of the rate converter at the end of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,6 +46,10 @@ struct OutArgs {
   unsigned long long n_recs;     // blocks of the call with IF samples
   double squelch, gain;
   unsigned max_frames, max_blocks;
+  // rate converter (fmr_set_output_rate); all zero without it
+  unsigned long long out0;       // ring frames produced before this call: ceil(frame0 L / M)
+  unsigned long long n_out;      // ring frames of the call
+  int zpar;                      // which of the two staging rows takes this call's z (the other one gets the next history)
 };
 
 template <int FMT> struct OutSample;
@@ -122,7 +127,7 @@ __global__ __launch_bounds__(kOutThreads) void k_out_pcm(const double *__restric
       sq += xf * xf;
       v[c] = S::conv(xv * g, cl, nf);
     }
-    if (fb + (unsigned long long)i >= keep_from) {
+    if (ring && fb + (unsigned long long)i >= keep_from) {      // (ring = nullptr: k_out_rate writes the ring)
       unsigned slot = slot0 + (unsigned)i % L;      // (slot0, i % L < L <= 2^26: no overflow)
       if (slot >= L) slot -= L;
       row[slot] = F::pack(v);
@@ -183,6 +188,116 @@ __global__ __launch_bounds__(64) void k_out_blocks(BlockTab bt, const float *__r
     }
   }
   if (lane == 0) state[s] = make_float2(ifl, aul);
+}
+
+// ---- rate converter (fmr_set_output_rate): PCM at rate = 48000 L / M and / or downmixed ----
+// Three launches behind k_out_pcm (which then leaves the ring alone and still makes the partials of the records):
+//   k_out_z     one workgroup per (block, stream): z = x g (or ((xL + xR) 0.5) g) as doubles into the call's staging row,
+//               behind the T - 1 frames of history the row starts with.
+//   k_out_rate  256 ring frames per workgroup, one per thread: the workgroup stages the z span its frames reach into LDS,
+//               every thread runs the serial sum of the definition over its phase's taps (read from the prototype as it
+//               is, h[k L + p]: at a fixed k the lanes of a wave read within one row of L doubles, for L = 1 one
+//               address), converts, stores its whole frame at slot m mod max_frames, and the workgroup adds its clip /
+//               non-finite counts to the stream's totals (butterfly, wave order, one integer atomic each).
+//   k_out_hist  the last T - 1 frames of [history | z] to the head of the other staging row, which takes the next call.
+// Positions (first input frame, first ring frame, which row) travel in OutArgs.
+struct OutRateGeom {
+  int L, M, T;               // rate / 48000 = L / M in lowest terms; taps per phase (L = M = T = 1: no filter, acc = z)
+  int span;                  // frames of z a workgroup of k_out_rate stages at most: 255 M / L + 1 + T
+  long long zstride;         // doubles per stream in a staging row: (T - 1 + the call's most frames) channels
+  long long zrow;            // doubles per staging row: S zstride
+};
+
+template <int CH_IN, int CH_OUT>
+__global__ __launch_bounds__(kOutThreads) void k_out_z(const double *__restrict__ aud, long long astride, BlockTab bt,
+                                                       const float *__restrict__ if_rms_blk, OutArgs a, OutRateGeom gm,
+                                                       double *__restrict__ z) {
+  const int b = blockIdx.x, s = blockIdx.y;
+  const int n = bt.au_len[b];
+  if (n == 0) return;
+  const int off = bt.au_off[b];
+  const double g = ((double)if_rms_blk[(long long)s * bt.nb + b] >= a.squelch) ? a.gain : 0.0;
+  const double *x = aud + (long long)s * astride + (long long)off * CH_IN;
+  double *row = z + (long long)a.zpar * gm.zrow + (long long)s * gm.zstride + (long long)(gm.T - 1 + off) * CH_OUT;
+  if (CH_IN == CH_OUT) {
+    for (int j = threadIdx.x; j < n * CH_IN; j += kOutThreads) row[j] = x[j] * g;
+  } else {
+    for (int i = threadIdx.x; i < n; i += kOutThreads) row[i] = ((x[2 * i] + x[2 * i + 1]) * 0.5) * g;
+  }
+}
+
+// z: the two staging rows; h: the prototype, T L doubles; ring [S][max_frames] frames; totals [S][2]: clipped, non-finite.
+// Dynamic LDS: span CH doubles, then 2 (kOutThreads / 64) counters.
+template <int FMT, int CH>
+__global__ __launch_bounds__(kOutThreads) void k_out_rate(const double *__restrict__ z, const double *__restrict__ h,
+                                                          OutRateGeom gm, OutArgs a, void *__restrict__ ring,
+                                                          unsigned long long *__restrict__ totals) {
+  using S = OutSample<FMT>;
+  using V = typename S::type;
+  using F = OutFrame<V, CH>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char out_lds[];
+  double *zs = reinterpret_cast<double *>(out_lds);
+  unsigned *s_cnt = reinterpret_cast<unsigned *>(out_lds + (size_t)gm.span * CH * sizeof(double));
+  const int s = blockIdx.y;
+  const unsigned long long uL = (unsigned long long)gm.L, uM = (unsigned long long)gm.M;
+  const unsigned long long m_end = a.out0 + a.n_out;
+  const unsigned long long m_first = a.out0 + (unsigned long long)blockIdx.x * kOutThreads;     // (< m_end: the grid is ceil(n_out / 256))
+  const unsigned long long m_last = min(m_first + (unsigned long long)(kOutThreads - 1), m_end - 1);
+  const unsigned long long q_first = m_first * uM / uL, q_last = m_last * uM / uL;
+  // z[j] is frame T - 1 + (j - frame0) of the staging row; the span is z[q_first - (T - 1)] .. z[q_last]
+  const int cnt = (int)(q_last - q_first) + gm.T;
+  const double *src = z + (long long)a.zpar * gm.zrow + (long long)s * gm.zstride + (long long)(q_first - a.frame0) * CH;
+  for (int j = threadIdx.x; j < cnt * CH; j += kOutThreads) zs[j] = src[j];
+  __syncthreads();
+  const unsigned long long m = m_first + threadIdx.x;
+  unsigned cl = 0, nf = 0;
+  if (m <= m_last) {
+    const unsigned long long mm = m * uM, q = mm / uL;
+    const int p = (int)(mm - q * uL);
+    const double *zq = zs + ((long long)(q - q_first) + gm.T - 1) * CH;      // z[q]
+    double acc[CH];
+    if (gm.T == 1) {
+#pragma unroll
+      for (int c = 0; c < CH; c++) acc[c] = zq[c];
+    } else {
+#pragma unroll
+      for (int c = 0; c < CH; c++) acc[c] = 0.0;
+      const double *hp = h + p;
+#pragma unroll 4
+      for (int k = 0; k < gm.T; k++) {
+        const double hk = hp[(long long)k * gm.L];
+#pragma unroll
+        for (int c = 0; c < CH; c++) acc[c] = acc[c] + hk * zq[-(long long)k * CH + c];
+      }
+    }
+    V v[CH];
+#pragma unroll
+    for (int c = 0; c < CH; c++) v[c] = S::conv(acc[c], cl, nf);
+    // frames a later frame of this call lands on are not written: no two lanes ever write one slot
+    const unsigned long long keep_from = a.n_out > a.max_frames ? m_end - a.max_frames : 0ull;
+    if (m >= keep_from)
+      (reinterpret_cast<typename F::type *>(ring) + (size_t)s * a.max_frames)[m % a.max_frames] = F::pack(v);
+  }
+  cl = out_wave_sum(cl); nf = out_wave_sum(nf);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { s_cnt[2 * w] = cl; s_cnt[2 * w + 1] = nf; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    unsigned t = 0;
+#pragma unroll
+    for (int k = 0; k < kOutThreads / 64; k++) t += s_cnt[2 * k + threadIdx.x];
+    if (t) atomicAdd(&totals[2 * s + threadIdx.x], (unsigned long long)t);
+  }
+}
+
+// hist = (T - 1) channels doubles per stream, n = the call's frames times channels: from behind them in row zpar to the
+// head of the other row
+__global__ __launch_bounds__(kOutThreads) void k_out_hist(double *__restrict__ z, OutRateGeom gm, int zpar, long long n, int hist) {
+  const int i = blockIdx.x * kOutThreads + threadIdx.x, s = blockIdx.y;
+  if (i >= hist) return;
+  const double *src = z + (long long)zpar * gm.zrow + (long long)s * gm.zstride + n;
+  double *dst = z + (long long)(zpar ^ 1) * gm.zrow + (long long)s * gm.zstride;
+  dst[i] = src[i];
 }
 
 }  // namespace fmr

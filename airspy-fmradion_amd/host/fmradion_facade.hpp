@@ -194,8 +194,20 @@ inline fmr_output_config output_config(int format, double squelch_level, double 
   m.max_frames = max_frames; m.max_blocks = max_blocks;
   return m;
 }
-inline void output(fmr_chain *c, const fmr_output_config &m) {
+// (r: fmr_set_output_rate behind it when a rate or mono is asked for)
+inline void output(fmr_chain *c, const fmr_output_config &m, const fmr_output_rate_config &r) {
   check(fmr_enable_output(c, &m, sizeof m), "fmr_enable_output");
+  if (r.rate != 0 || r.mono != 0) check(fmr_set_output_rate(c, &r, sizeof r), "fmr_set_output_rate");
+}
+inline fmr_output_rate_config output_rate_config(int rate, bool mono) {
+  fmr_output_rate_config r{};
+  r.struct_size = sizeof r; r.rate = rate; r.mono = mono ? 1 : 0;
+  return r;
+}
+inline fmr_output_rate_info output_rate_info(fmr_chain *c, int stream) {
+  fmr_output_rate_info info{};
+  check(fmr_get_output_rate(c, stream, &info, sizeof info), "fmr_get_output_rate");
+  return info;
 }
 inline OutputData output_data(fmr_chain *c, int stream) {
   OutputData out;
@@ -354,7 +366,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
-    if (m_out) fmr_detail::output(m_chain, m_out_cfg);
+    if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
   }
 
   // RDS (no counterpart in the reference; fmr_create_rds): re-creates the chain with the RDS decoder, before the first
@@ -367,7 +379,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
-    if (m_out) fmr_detail::output(m_chain, m_out_cfg);
+    if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
   }
   // error correction of the RDS blocks (fmr_set_rds_correction: FMR_RDS_FEC_OFF / _BURST / _SOFT; 0 = the defaults); at
   // any time after enable_rds(), from the decoder's next block boundary on.  enable_rds() starts with it off.
@@ -417,15 +429,18 @@ public:
   // Output stage (what main.cpp:976-1002 does behind the decoder, on the device; fmr_enable_output): the squelched and
   // scaled audio as FMR_PCM_S16 / FMR_PCM_F32 frames and one record per block with the IF / AF meters; before the first
   // process(), once.  squelch_level is linear (fmr_squelch_level_from_db gives it from -l dB; 0 = never closed), gain 0 =
-  // 0.5.  read_output() drains everything that waits.
+  // 0.5.  rate / mono: the PCM ring at that rate (8000 .. 48000, fmr_set_output_rate) and / or downmixed to one channel.
+  // read_output() drains everything that waits.
   void enable_output(int format = FMR_PCM_S16, double squelch_level = 0.0, double gain = 0.0, uint32_t max_frames = 0,
-                     uint32_t max_blocks = 0) {
+                     uint32_t max_blocks = 0, int rate = 0, bool mono = false) {
     if (m_started) fmr_detail::fail("FmDecoder::enable_output: after the first process()");
     m_out_cfg = fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks);
-    fmr_detail::output(m_chain, m_out_cfg);
+    m_out_rate = fmr_detail::output_rate_config(rate, mono);
+    fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     m_out = true;
   }
   OutputData read_output() { return fmr_detail::output_data(m_chain, 0); }
+  fmr_output_rate_info output_rate_info() { return fmr_detail::output_rate_info(m_chain, 0); }
 
   // Latency for throughput: hold back `blocks` - 1 calls and decode `blocks` blocks in ONE batched call.  process()
   // then returns an empty vector ("nothing yet": the contract of FmDecode.cpp:89-92,185-188, which main.cpp:981-984
@@ -449,7 +464,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
-    if (m_out) fmr_detail::output(m_chain, m_out_cfg);
+    if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
       m_capacity = blocks;
     }
     m_batch = blocks;
@@ -550,6 +565,7 @@ private:
   fmr_rf_monitor_config m_rf_cfg{};
   bool m_out = false;
   fmr_output_config m_out_cfg{};
+  fmr_output_rate_config m_out_rate{};
   fmr_chain *m_chain = nullptr;
   bool m_rds = false;
   fmr_rds::Station m_station;
@@ -586,17 +602,20 @@ public:
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg);
-    if (m_out) fmr_detail::output(m_chain, m_out_cfg);
+    if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
   }
   // Output stage (fmr_enable_output): squelch, gain, PCM frames and the per-block IF / AF meters on the device; before
-  // the first process(), once.  read_output() drains everything that waits.
+  // the first process(), once.  rate: the PCM ring at that rate (fmr_set_output_rate).  read_output() drains everything
+  // that waits.
   void enable_output(int format = FMR_PCM_S16, double squelch_level = 0.0, double gain = 0.0, uint32_t max_frames = 0,
-                     uint32_t max_blocks = 0) {
+                     uint32_t max_blocks = 0, int rate = 0, bool mono = false) {
     m_out_cfg = fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks);
-    fmr_detail::output(m_chain, m_out_cfg);
+    m_out_rate = fmr_detail::output_rate_config(rate, mono);
+    fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     m_out = true;
   }
   OutputData read_output() { return fmr_detail::output_data(m_chain, 0); }
+  fmr_output_rate_info output_rate_info() { return fmr_detail::output_rate_info(m_chain, 0); }
   void process(IQSampleVector samples_in, SampleVector &audio) {
     audio.resize(samples_in.size() + 64);
     size_t n = 0;
@@ -619,6 +638,7 @@ private:
   fmr_config m_cfg{};
   bool m_out = false;
   fmr_output_config m_out_cfg{};
+  fmr_output_rate_config m_out_rate{};
   fmr_chain *m_chain = nullptr;
 };
 
@@ -644,17 +664,20 @@ public:
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg);
-    if (m_out) fmr_detail::output(m_chain, m_out_cfg);
+    if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
   }
   // Output stage (fmr_enable_output): squelch, gain, PCM frames and the per-block IF / AF meters on the device; before
-  // the first process(), once.  read_output() drains everything that waits.
+  // the first process(), once.  rate: the PCM ring at that rate (fmr_set_output_rate).  read_output() drains everything
+  // that waits.
   void enable_output(int format = FMR_PCM_S16, double squelch_level = 0.0, double gain = 0.0, uint32_t max_frames = 0,
-                     uint32_t max_blocks = 0) {
+                     uint32_t max_blocks = 0, int rate = 0, bool mono = false) {
     m_out_cfg = fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks);
-    fmr_detail::output(m_chain, m_out_cfg);
+    m_out_rate = fmr_detail::output_rate_config(rate, mono);
+    fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     m_out = true;
   }
   OutputData read_output() { return fmr_detail::output_data(m_chain, 0); }
+  fmr_output_rate_info output_rate_info() { return fmr_detail::output_rate_info(m_chain, 0); }
   void process(const IQSampleVector &samples_in, SampleVector &audio) {
     audio.resize(samples_in.size() + 64);
     size_t n = 0;
@@ -677,6 +700,7 @@ private:
   fmr_config m_cfg{};
   bool m_out = false;
   fmr_output_config m_out_cfg{};
+  fmr_output_rate_config m_out_rate{};
   fmr_chain *m_chain = nullptr;
 };
 
@@ -723,7 +747,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
-    if (m_out) fmr_detail::output(m_chain, m_out_cfg);
+    if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     m_stations.assign(m_offsets.size(), fmr_rds::Station());
   }
   // error correction of every channel's RDS blocks (fmr_set_rds_correction), at any time after enable_rds()
@@ -776,16 +800,22 @@ public:
   }
 
   // Output stage of every channel (fmr_enable_output), before the first process(), once; banks of every mode.
+  // rate / mono: every channel's PCM ring at that rate and / or downmixed (fmr_set_output_rate).
   // read_output(ch) drains channel ch's PCM frames and block records.
   void enable_output(int format = FMR_PCM_S16, double squelch_level = 0.0, double gain = 0.0, uint32_t max_frames = 0,
-                     uint32_t max_blocks = 0) {
+                     uint32_t max_blocks = 0, int rate = 0, bool mono = false) {
     m_out_cfg = fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks);
-    fmr_detail::output(m_chain, m_out_cfg);
+    m_out_rate = fmr_detail::output_rate_config(rate, mono);
+    fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     m_out = true;
   }
   OutputData read_output(size_t ch) {
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
     return fmr_detail::output_data(m_chain, (int)ch);
+  }
+  fmr_output_rate_info output_rate_info(size_t ch) {
+    if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
+    return fmr_detail::output_rate_info(m_chain, (int)ch);
   }
 
   // audio[k] = what channel k produced from this capture block (empty = "nothing yet"); blocks longer than the chain's
@@ -844,6 +874,7 @@ private:
   fmr_rf_monitor_config m_rf_cfg{};
   bool m_out = false;
   fmr_output_config m_out_cfg{};
+  fmr_output_rate_config m_out_rate{};
   fmr_chain *m_chain = nullptr;
 };
 

@@ -867,6 +867,59 @@ int fmr_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, fmr_
 /* pow(10, -(db / 20)): the linear squelch level of the reference's -l option (main.cpp:486).  Host only. */
 double fmr_squelch_level_from_db(double db);
 
+/* --- Output stage at other rates and mono: the PCM ring at rate = 48000 L / M by a polyphase
+ * filter, and / or a stereo chain's frames downmixed to one channel.  The block records do not change in any field:
+ * first_frame, n_frames, n_clipped, n_nonfinite and the meters keep speaking of the decoder's 48 kHz frames and of x g
+ * before the filter; so do the chain's audio, fmr_status, PPS events, RDS groups and every monitor's records.
+ * fmr_output_read's info.channels, first_frame, frames_waiting, frames_dropped and max_frames / cap_frames then count the
+ * ring's frames, at the new rate and channel count.  The first ring frame made from a block whose first_frame is f is
+ * ceil(f L / M).
+ * Definition, per stream, over the audio frames since create; nothing depends on blocks or calls except the gate:
+ *   x[j] is the decoder's frame j (doubles); g(j) = gain if the gate of the block holding j is open, else 0.0.
+ *   z[j] = x[j] g(j) per channel; with mono on a stereo chain u = (xL + xR) 0.5 and z = u g.  z[j] = +0.0 for j < 0.
+ *   Ring frame m = 0, 1, ... takes q = floor(m M / L), p = (m M) mod L and acc = 0.0; for k = 0 .. T - 1 ascending
+ *   acc = acc + h[k L + p] z[q - k], every product and every sum rounded by itself in fp64 (no fused multiply-add).
+ *   acc is converted by the rules of FMR_PCM_S16 / FMR_PCM_F32 above and counted in pcm_clipped / pcm_nonfinite.
+ *   Frame m exists as soon as x[q] does: after F decoder frames the ring has received ceil(F L / M) frames.
+ *   With L = M = 1 (mono alone) there is no filter: acc = z[j].
+ * A non-finite x therefore reaches up to T ring frames (and a closed gate rings out over T frames before the ring is
+ * exactly zero).
+ * h is the prototype of fmr_output_rate_taps: a Kaiser-windowed sinc at rate 48000 L of T L taps, symmetric bit for bit
+ * about (T L - 1) / 2, sum h = L; pass band 0 .. 0.9 rate / 2 within +-0.001 dB, stop band from rate / 2 on >= 100 dB
+ * down (design attenuation 110 dB, cutoff 0.95 rate / 2). */
+typedef struct {
+  unsigned struct_size;   /* as the other configs: 0 = cfg_size; larger than the library's is refused */
+  int rate;               /* PCM rate in Hz.  0 or 48000: the decoder's rate, no filter.  Otherwise a whole rate,
+                             8000 <= rate < 48000, with L = rate / gcd(rate, 48000) <= 160 (8000, 11025, 12000, 16000,
+                             22050, 24000, 32000, 44100, ...; 8001 is refused) */
+  int mono;               /* 1: a stereo chain's frames become u = (xL + xR) * 0.5 before gate and filter; PCM has one
+                             channel.  Ignored by chains whose audio is mono already.  Other values than 0 / 1 refused */
+  int reserved;           /* must be 0 */
+} fmr_output_rate_config;
+/* Checks its fields first (FMR_ERR_BAD_ARG, fmr_last_error names the field, also with a NULL chain), then the chain:
+ * allowed once, after fmr_enable_output and before the chain's first block; a chain without the stage, a second call and
+ * a call after any processing call are FMR_ERR_BAD_ARG.  rate 0 / 48000 with mono 0 (or with mono 1 on a chain whose
+ * audio is mono) is accepted and leaves the stage exactly as it is: same kernels, same bytes.  A chain that never calls
+ * it allocates nothing for the converter and runs none of its kernels. */
+int fmr_set_output_rate(fmr_chain *c, const fmr_output_rate_config *cfg, size_t cfg_size);
+typedef struct {
+  unsigned struct_size;
+  int rate, channels;            /* of the PCM ring */
+  int L, M, taps_per_phase;      /* rate / 48000 = L / M in lowest terms; T (1 without a filter) */
+  double delay_frames;           /* group delay in OUTPUT frames: (T L - 1) / (2 M); 0 without a filter */
+  uint64_t frames_in;            /* decoder-rate frames taken since create */
+  uint64_t pcm_clipped, pcm_nonfinite;   /* of this stream since create, counted on the resampled values by the rules
+                                            of FMR_PCM_S16 / FMR_PCM_F32, per channel value, every produced frame.  0 on
+                                            a stage left as it is (no filter, no downmix): its block records count */
+} fmr_output_rate_info;
+/* Synchronises like the other getters.  FMR_ERR_BAD_ARG for a bad stream, a chain without the stage, and an info_size
+ * larger than this library's struct.  Valid with or without a call of fmr_set_output_rate. */
+int fmr_get_output_rate(fmr_chain *c, int stream, fmr_output_rate_info *info, size_t info_size);
+/* Host only, no device: the prototype filter of `rate` (T L doubles, tap i of the prototype at taps[i]) and L, M, T (each
+ * may be NULL).  Returns T L, also with taps = NULL or cap too small (then nothing is written); rate 48000 (or 0) gives the
+ * single tap 1.0.  FMR_ERR_BAD_ARG for a rate fmr_set_output_rate refuses. */
+int fmr_output_rate_taps(int rate, double *taps, int cap, int *L, int *M, int *T);
+
 #ifdef __cplusplus
 }
 #endif
