@@ -25,6 +25,7 @@
 //    iteration does not converge the serial kernels of kernels.hpp run instead.
 #pragma once
 #include "kernels.hpp"
+#include "pll_compose.hpp"
 
 namespace fmr {
 
@@ -1079,6 +1080,7 @@ struct PllDownArgs { const double *PRE, *dstart2; int ngrp, ngrp2; double minfre
 __device__ __forceinline__ void pll_down_group(const PllDownArgs &dn, double *nodes_s, const double *g, const double *m, int nck, int s, int grp,
                                                PllSync *sync, double *sm, double *sr, double *so, double *first, int lane);
 __device__ __forceinline__ void pll_up_from_lds(const PllUpArgs &u, int s, int grp, int n, double *sm, double *sh, int lane);
+__device__ __forceinline__ void pll_up_levels23(const PllUpArgs &u, int s, int grp, double val, double *sm, double *sh, int lane);
 __device__ __forceinline__ void pll_stage_group(const double *__restrict__ m, const double *__restrict__ g, const double *__restrict__ nd,
                                                 int c0, int n, int lane, double *sm, double *sr, double *so, int rs = 8);
 
@@ -1108,10 +1110,11 @@ __global__ __launch_bounds__(64) void k_pll_shoot(const fm_mpx_t *__restrict__ b
   const unsigned long long trace_t0 = __builtin_readcyclecounter(), trace_w0 = wall_clock64();
 #endif
   __shared__ float tab[257];
-  __shared__ double xs[64 * TP];
+  __shared__ __attribute__((aligned(16))) double xs[64 * TP];
   __shared__ int s_off[64], s_len[64];
-  static_assert(64 * TP >= 64 * 25, "the tile also carries the Jacobians out, 25 elements per lane at a time");
-  static_assert(64 * TP >= FMR_NODE_GRP2 * 56 + 64, "... and stages the up-sweep of the node pass");
+  static_assert(64 * TP >= FMR_NODE_GRP * FMR_MAP, "the tile also carries a group's maps [M | r] out and into the up-sweep's tree");
+  static_assert(64 * TP >= FMR_NODE_GRP2 * 56 + 64, "... and stages levels 2 and 3 of the up-sweep");
+  static_assert(FMR_NODE_GRP <= FMR_TREE_MAXN && FMR_MAP == 56, "pll_compose_tree's sizes");
   // the integration passes are the decoder stream's critical kernels and share their SIMDs with the audio tail of the call
   // before: their waves win the issue arbitration (round 6: 0.4742 -> 0.4711 ms per step over four interleaved 100-step
   // runs each; without the tail stage the step is 0.4465)
@@ -1260,45 +1263,59 @@ __global__ __launch_bounds__(64) void k_pll_shoot(const fm_mpx_t *__restrict__ b
     }
   }
   if (JAC) {   // JAC == false: frozen-Jacobian round, the stored M of the last JAC round stands
-    // the wave's Jacobians are one contiguous block of 64 x 49 doubles: through the tile, 25 + 24 elements per lane, so
-    // that a store instruction covers two or three rows instead of 64 (row-per-lane stores are issue-bound in the TA)
+    // Every lane holds its chunk's Jacobian and boundary mismatch.  A group of 32 chunks at a time, the lanes put their
+    // maps [M | r] into the tile (7 rows of 8), and from there
+    //  - the Jacobians leave for HBM (the down-sweep and the chord rounds read them): the group's are one contiguous block
+    //    of 32 x 49 doubles, so a store instruction covers one or two rows instead of 64 (row-per-lane stores are
+    //    issue-bound in the TA);
+    //  - the node pass's up-sweep composes the group's maps, here: k_pll_up would start behind a launch boundary, with every
+    //    workgroup of this pass gone, and read the 31 MB of Jacobians of a 2^27-sample call back from HBM.  The maps come
+    //    from the registers, not from the stores (no wait for them, no way back through L2), and are composed pairwise in
+    //    five levels, four pairs a round on 56 lanes with four independent entries each (pll_compose_tree: nine rounds a
+    //    group; the chain of k_pll_up is 32 dependent steps of one entry per lane).  Same maps, bit for bit, as k_pll_up
+    //    stages; another association.
     double *mb = M + ((long long)s * ct.nck + (long long)blockIdx.x * 64) * 49;
-    const int rows = min(64, ct.nck - blockIdx.x * 64);
-    auto part = [&](auto e0c, auto nec) {
-      constexpr int E0 = decltype(e0c)::value, NE = decltype(nec)::value;
-      __syncthreads();
+    double rr[7];
 #pragma unroll
-      for (int e = 0; e < NE; e++) xs[lane * 25 + e] = Mx[(E0 + e) / 7][(E0 + e) % 7];
-      __syncthreads();
-#pragma unroll 5
-      for (int it = 0; it < NE; it++) {
-        const int q = it * 64 + lane, r = q / NE, e = q - r * NE;
-        if (r < rows) mb[r * 49 + E0 + e] = xs[r * 25 + e];
-      }
-    };
-    part(std::integral_constant<int, 0>{}, std::integral_constant<int, 25>{});
-    part(std::integral_constant<int, 25>{}, std::integral_constant<int, 24>{});
-  }
-  // ---- the node pass's up-sweep, here: k_pll_up would start behind a launch boundary, with every workgroup of this pass
-  // gone, and read the 31 MB of Jacobians of a 2^27-sample call back from HBM -- 49 us of the step for 2 x 32 dependent
-  // 7 x 8 compositions per wave.  This wave's two groups of 32 chunks are composed as soon as it has stored them (read
-  // back through L2, 12.5 KB each, by the same staging code: held in registers across the sweep they cost the pass its
-  // second wave per SIMD).  Same arithmetic, same order: pll_up_from_lds is k_pll_up's body.
-  if (JAC && up.PQ) {
-    double *sm = xs, *sh = xs + FMR_NODE_GRP2 * 56, *sr = sm + FMR_NODE_GRP * 49;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's G and M stores are in L2
-    const double *ndb = nodes + (long long)s * (ct.nck + 1) * 7;
-    const double *gb = G + (long long)s * ct.nck * 9;
-    const double *mb2 = M + (long long)s * ct.nck * 49;
+    for (int k = 0; k < 7; k++) rr[k] = S.v[k] - nd[7 + k];          // pll_mismatch of this chunk
+    rr[0] = wrap_pm_pi(rr[0]);
+    double pq0 = 0.0, pq1 = 0.0;      // the two groups' composites, one entry per lane
 #pragma unroll 1
     for (int h = 0; h < 2; h++) {
       const int grp = 2 * blockIdx.x + h, c0 = grp * FMR_NODE_GRP;
       if (c0 >= ct.nck) break;
       const int ng = min(FMR_NODE_GRP, ct.nck - c0);
       __syncthreads();
-      pll_stage_group(mb2, gb, ndb, c0, ng, lane, sm, sr, nullptr, 7);
+      if (half == h) {
+        double *mp = xs + l5 * FMR_MAP;
+#pragma unroll
+        for (int r = 0; r < 7; r++) {
+#pragma unroll
+          for (int k = 0; k < 7; k++) mp[r * 8 + k] = Mx[r][k];
+          mp[r * 8 + 7] = rr[r];
+        }
+      }
       __syncthreads();
-      pll_up_from_lds(up, s, grp, ng, sm, sh, lane);
+      double *mg = mb + h * (FMR_NODE_GRP * 49);
+#pragma unroll 5
+      for (int it = 0; it < (FMR_NODE_GRP * 49 + 63) / 64; it++) {
+        const int q = it * 64 + lane, r = q / 49, e = q - r * 49, er = e / 7;
+        if (q < ng * 49) mg[q] = xs[r * FMR_MAP + er * 8 + (e - er * 7)];
+      }
+      if (up.PQ) {
+        pll_compose_tree<64>(xs, ng, lane, [] { __syncthreads(); });
+        const double val = lane < FMR_MAP ? xs[lane] : 0.0;        // lane i * 8 + k: P[i][k], k == 7: q[i]
+        if (h == 0) pq0 = val; else pq1 = val;
+      }
+    }
+    // levels 2 and 3 behind both trees: they stage a set's maps through registers, which the Jacobians still held
+    // above (in between the pass needs more than 256 registers: one wave per SIMD)
+#pragma unroll 1
+    for (int h = 0; h < 2 && up.PQ; h++) {
+      const int grp = 2 * blockIdx.x + h;
+      if (grp * FMR_NODE_GRP >= ct.nck) break;
+      __syncthreads();
+      pll_up_levels23(up, s, grp, h ? pq1 : pq0, xs, xs + FMR_NODE_GRP2 * 56, lane);
     }
   }
 #ifdef FMR_PLL_TRACE
@@ -1666,25 +1683,33 @@ __global__ __launch_bounds__(1024) void k_pll_check(IterFlags *fl, int n_streams
 __device__ __forceinline__ void pll_up_from_lds(const PllUpArgs &u, int s, int grp, int n, double *sm, double *sh, int lane) {
   // sm: the group's n Jacobians (49 doubles each), then its mismatches at sm + FMR_NODE_GRP * 49 (stride 7); at least
   // FMR_NODE_GRP2 * 56 doubles long (level 2 stages a set's maps there); sh: 64 doubles
+  // Level 1 as a chain (k_pll_up, the chord rounds >= 3 and the A/B partner of the tree in k_pll_shoot's tail)
   double *const sr = sm + FMR_NODE_GRP * 49;
+  const int i = lane >> 3, k = lane & 7;
+  const bool act = i < 7;
+  const int ii = act ? i : 0;
+  double val = (act && i == k) ? 1.0 : 0.0;   // P = I, q = 0
+  for (int t = 0; t < n; t++) {
+    sh[lane] = val;
+    __syncthreads();                      // one wave per block: just orders the LDS write
+    double acc = (k == 7) ? sr[t * 7 + ii] : 0.0;
+    const double *row = sm + t * 49 + ii * 7;
+#pragma unroll
+    for (int j = 0; j < 7; j++) acc = fma(row[j], sh[j * 8 + k], acc);
+    __syncthreads();
+    val = acc;
+  }
+  pll_up_levels23(u, s, grp, val, sm, sh, lane);
+}
+
+// Levels 2 and 3 of the up-sweep behind a group's composite (lane i * 8 + k holds P[i][k], k == 7: q[i]); sm: at least
+// FMR_NODE_GRP2 * 56 doubles of LDS, sh: 64
+__device__ __forceinline__ void pll_up_levels23(const PllUpArgs &u, int s, int grp, double val0, double *sm, double *sh, int lane) {
   const int ngrp = u.ngrp, ngrp2 = u.ngrp2;
   const int i = lane >> 3, k = lane & 7;
   const bool act = i < 7;
   const int ii = act ? i : 0;
-  {
-    double val = (act && i == k) ? 1.0 : 0.0;   // P = I, q = 0
-    for (int t = 0; t < n; t++) {
-      sh[lane] = val;
-      __syncthreads();                      // one wave per block: just orders the LDS write
-      double acc = (k == 7) ? sr[t * 7 + ii] : 0.0;
-      const double *row = sm + t * 49 + ii * 7;
-#pragma unroll
-      for (int j = 0; j < 7; j++) acc = fma(row[j], sh[j * 8 + k], acc);
-      __syncthreads();
-      val = acc;
-    }
-    if (act) st_agent(&u.PQ[(((long long)s * ngrp + grp) * 7 + i) * 8 + k], val);
-  }
+  if (act) st_agent(&u.PQ[(((long long)s * ngrp + grp) * 7 + i) * 8 + k], val0);
   // ---- level 2: the last group of the set composes the set
   const int set = grp / FMR_NODE_GRP2;
   const int g0 = set * FMR_NODE_GRP2, g1 = min(g0 + FMR_NODE_GRP2, ngrp);
