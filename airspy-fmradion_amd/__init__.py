@@ -40,7 +40,8 @@ CB_FORMS = {"modtap": 1 << 0}
 EXPORTS = [
     "fmr_create", "fmr_destroy", "fmr_last_error", "fmr_version", "fmr_resampler_info", "fmr_process",
     "fmr_process_blocks", "fmr_process_blocks_device", "fmr_synchronize", "fmr_resample", "fmr_get_status",
-    "fmr_get_pps_events", "fmr_get_multipath_coefficients", "fmr_debug_read", "fmr_get_kernel_times",
+    "fmr_get_pps_events", "fmr_get_multipath_coefficients", "fmr_debug_read", "fmr_debug_live_resources",
+    "fmr_get_kernel_times",
     "fmr_probe_read_bandwidth", "fmr_probe_shader_clock", "fmr_get_kernel_trace",
     "fmr_enable_kernel_timing", "fmr_filter_table", "fmr_fourth_convert", "fmr_design_taps", "fmr_design_taps_class",
     "fmr_host_alloc", "fmr_host_free", "fmr_create_sized", "fmr_get_status_sized",
@@ -324,6 +325,8 @@ def lib(ab=False):
     L.fmr_get_multipath_coefficients.argtypes = [vp, C.c_int, fp, C.c_int]
     L.fmr_debug_read.restype = C.c_longlong
     L.fmr_debug_read.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
+    L.fmr_debug_live_resources.restype = C.c_longlong
+    L.fmr_debug_live_resources.argtypes = []
     L.fmr_get_kernel_times.restype = C.c_int
     L.fmr_get_kernel_times.argtypes = [vp, C.POINTER(C.c_char_p), fp, C.c_int]
     L.fmr_enable_kernel_timing.restype = None
@@ -426,6 +429,11 @@ def design_taps_class(in_rate, out_rate, resampler_class, stage):
     d = dict(zip(["D", "NA", "LB", "MB", "TB", "LT"], [int(v) for v in info]))
     rows = d["LT"] + 1 if d["LT"] else d["LB"]
     return (buf.reshape(rows, d["TB"]) if stage else buf), d
+
+
+def debug_live_resources(ab=False):
+    """fmr_debug_live_resources: device buffers, pinned blocks, events and streams the library holds in this process."""
+    return lib(ab=ab).fmr_debug_live_resources()
 
 
 def probe_shader_clock(device=0):

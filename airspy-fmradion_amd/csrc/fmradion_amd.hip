@@ -10,6 +10,7 @@
 // the host derives from the resampler's integer output-count law.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <atomic>
 #include <chrono>
 #include <functional>
 #include <thread>
@@ -85,20 +86,65 @@ constexpr unsigned kAgcWaitTicks = 50000000u;   // 0.5 s of the 100 MHz clock: h
                                                 // kernel beside it is three times faster than the equaliser: it never waits in practice)
 constexpr int K_AGC_ITERS = 6, K_PLL_ITERS = 4;   // PLL: 2 rounds in lock, 2 spare (an unused round is three launches that return at once: ~6 us measured)
 
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t n = 0;
-  int alloc(size_t count) {
-    n = count ? count : 1;
-    HIPCHK(hipMalloc((void **)&p, n * sizeof(T)));
-    HIPCHK(hipMemset(p, 0, n * sizeof(T)));
-    return FMR_OK;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; }
+// ---- owners of what the HIP runtime hands out: device memory, page-locked host memory, events, streams.  Each holds one
+// resource, is move-only, and gives the resource back (Free) when it dies or takes another; nothing else in this file
+// frees.  g_live counts what the owners of the process hold (fmr_debug_live_resources).
+std::atomic<long long> g_live{0};
+template <class P, auto Free>
+struct Owned {
+  P p = nullptr;
+  Owned() = default;
+  Owned(Owned &&o) noexcept : p(o.p) { o.p = nullptr; }
+  Owned &operator=(Owned &&o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+  ~Owned() { reset(); }
+  void reset() { if (p) { (void)Free(p); g_live--; } p = nullptr; }
 };
 
-struct KernelTime { const char *name; hipEvent_t a, b; };
+template <class T>
+struct DevBuf : Owned<T *, hipFree> {
+  size_t n = 0;
+  int alloc(size_t count) {      // zeroed; a buffer that holds memory gives it back first
+    this->reset();
+    n = count ? count : 1;
+    HIPCHK(hipMalloc((void **)&this->p, n * sizeof(T)));
+    g_live++;
+    HIPCHK(hipMemset(this->p, 0, n * sizeof(T)));
+    return FMR_OK;
+  }
+};
+static_assert(!std::is_copy_constructible_v<DevBuf<float>> && std::is_move_constructible_v<DevBuf<float>>, "owners are move-only");
+
+template <class T>
+struct HostBuf : Owned<T *, hipHostFree> {      // page-locked host memory (not zeroed)
+  int alloc(size_t count, unsigned flags) {
+    this->reset();
+    HIPCHK(hipHostMalloc((void **)&this->p, (count ? count : 1) * sizeof(T), flags));
+    g_live++;
+    return FMR_OK;
+  }
+};
+
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+  int create(unsigned flags = hipEventDefault) {
+    reset();
+    HIPCHK(hipEventCreateWithFlags(&p, flags));
+    g_live++;
+    return FMR_OK;
+  }
+  operator hipEvent_t() const { return p; }
+};
+
+struct Stream : Owned<hipStream_t, hipStreamDestroy> {
+  int create() {      // non-blocking
+    reset();
+    HIPCHK(hipStreamCreateWithFlags(&p, hipStreamNonBlocking));
+    g_live++;
+    return FMR_OK;
+  }
+  operator hipStream_t() const { return p; }
+};
+
+struct KernelTime { const char *name; Event a, b; };
 
 // A struct whose first field is struct_size, as the caller of fn knows it (cfg_size bytes, 0 = this library's size) ->
 // this library's, zero-filled.  A caller that knows more than the library is refused.
@@ -162,10 +208,15 @@ struct RecCursor {
 // aligned sub-blocks of segments, the window and twiddle tables, the stream's carry, the runs' partials, the open records
 // (two copies by launch parity) and the rings of max_records records per stream with their reader.  It counts in absolute
 // samples (n), so the cut into calls does not matter.  fmr_chain::seg_stage runs a call through it.
+// The modulation monitor (fmr_enable_monitor) is a second reader of the call's MPX at the head of the
+// audio tail, beside the RDS stage; the RF monitor (fmr_enable_rf_monitor; kernels_rfmon.hpp) is a
+// second instance that reads the call's IF ring slot (the decoder's input, or |x|^2 behind a discriminator epilogue).
+// This and the three stages below are the OPTIONAL stages of a chain: each owns all its state (build_stage).
 struct SegMonitor {
   bool on = false;
   unsigned interval = 0;                     // samples per record
   int bins = 0;                              // histogram counters per record
+  double hist_range = 0.0;                   // modulation monitor: the histogram covers +- this (the RF monitor's bin rule takes none)
   int spr = 0, sub = 0, sb = 0, rmax = 0;    // segments per record / per sub-block, sub-blocks per record, runs per stream and launch
   int par = 0;                               // which copy of the open records is current
   double sumw2 = 0.0;
@@ -177,15 +228,97 @@ struct SegMonitor {
   DevBuf<MonRec> d_prec, d_open_rec, d_ring_rec;
   RecCursor cur;
   unsigned long long done() const { return (unsigned long long)(next_seg / spr); }   // records complete
-  int init(int S, size_t max_if, unsigned interval_samples, int hist_bins, int max_records);
-  void release() {
-    d_win.release(); d_carry.release(); d_tw.release(); d_ppsd.release(); d_open_psd.release(); d_ring_psd.release();
-    d_phist.release(); d_open_hist.release(); d_ring_hist.release(); d_prec.release(); d_open_rec.release(); d_ring_rec.release();
-  }
+  int init(int S, size_t max_if, unsigned interval_samples, int hist_bins, double range, int max_records);
 };
 // both monitors' kernels (k_mon_seg<Src>, k_mon_reduce<Src>) as seg_stage takes them
 using MonSegFn = decltype(&k_mon_seg<MonMpxSrc>);
 using MonReduceFn = decltype(&k_mon_reduce<MonMpxSrc>);
+
+// RDS (fmr_create_rds; kernels_rds.hpp, host/fmradion_rds.hpp).  The stage runs at the head of the
+// audio tail (fmr_chain::rds_stage): it reads the call's MPX from the base slot and carries everything else in buffers of
+// its own (MPX history, y1 / y2 rings, RdsState), which only it writes.  The bits of a call go to a slot of a ring of
+// page-locked host slots; k_signal_host marks the slot filled and the host decoders drain it (drain).
+struct RdsStage {
+  bool on = false;
+  static constexpr int kSlots = 8;
+  int S = 0;
+  int R = 0, maxw = 0;                       // ring length (power of two), windows per call
+  size_t slot_stride = 0;                    // bytes per stream in a host slot
+  DevBuf<float> d_h1, d_h2, d_xhalo;
+  DevBuf<float2> d_lo, d_y1, d_y2;
+  DevBuf<RdsState> d_state;
+  DevBuf<RdsEst> d_est;
+  DevBuf<RdsRec> d_rec;
+  HostBuf<char> h_slots;
+  HostBuf<unsigned long long> h_mark;        // calls whose RDS slot is filled
+  long long n = 0, w = 0;                    // MPX samples seen, next window
+  unsigned long long seq = 0, drained = 0;
+  unsigned long long tap_seq = 0;            // slot of the most recent call's windows (0: it completed none): fmr_debug_read 5
+  double gain = 1.0;                         // |soft symbol| of a unit subcarrier (injection estimate)
+  std::vector<fmr_rds::Decoder> dec;
+  std::vector<RdsSlotHdr> hdr;
+  int init(int streams, size_t max_if);
+  void drain();
+};
+
+// Audio monitor (fmr_enable_loudness; kernels_loudness.hpp).  A reader of the call's finished audio
+// behind the output mux, on the tail's stream (fmr_chain::ld_stage): it counts in absolute audio samples (n) and keeps its
+// own carries (the K-weighting state, the true-peak history, the open record).
+struct LoudnessStage {
+  bool on = false;
+  fmr_loudness_config cfg{};                 // the defaults filled in
+  int cps = 0, rmax = 0, par = 0;            // chunks per sub-block, runs per stream and launch, current copy of the open records
+  long long n = 0;                           // audio samples seen (per channel)
+  LdCoef coef{};
+  DevBuf<double> d_pw, d_taps, d_G, d_start, d_pkw, d_state, d_hist;
+  DevBuf<LdPart> d_part;
+  DevBuf<LdRec> d_open, d_ring;
+  RecCursor cur;
+  unsigned long long done() const { return (unsigned long long)(n / (long long)cfg.step_samples); }   // records complete
+  int init(int S, size_t max_au, const fmr_loudness_config &m);
+};
+
+// Rate converter of the output stage (fmr_set_output_rate): with `on` the ring is written by
+// k_out_rate from the staged z instead of by k_out_pcm, oframes counts its frames, and the stream's clip / non-finite
+// totals live in d_tot.  Two staging rows: a call's z goes behind the T - 1 frames of history at the head of row zpar,
+// and what it leaves as history to the head of the other row.
+struct OutRate {
+  bool on = false, mono = false;
+  int hz = kOutRateIn;
+  OutRateGeom geom{1, 1, 1, 0, 0, 0};
+  unsigned long long oframes = 0;
+  int zpar = 0;
+  DevBuf<double> d_z, d_taps;                // [2][S][zstride]; the prototype, T L
+  DevBuf<unsigned long long> d_tot;          // [S][2]
+  int init(int rate, bool to_mono, int S, bool stereo, size_t max_au);
+};
+
+// Output stage (fmr_enable_output; kernels_output.hpp).  The last reader of the call's finished
+// audio, on the stream that wrote it (fmr_chain::out_stage): squelch, gain and PCM conversion into a ring of frames per
+// stream, and one record per block with the stream loop's meters.  The block, frame and record counters live here and are
+// taken when a call is issued (begin); the device carries the two levels.  k_stats leaves every block's IF RMS in the
+// call's slot of d_ifrms (the tail of a pipelined chain runs a call late).
+struct OutputStage {
+  bool on = false;
+  bool stereo = false;                       // of the chain
+  fmr_output_config cfg{};                   // the defaults filled in
+  unsigned long long block = 0, recs = 0, frames = 0;   // blocks handed in, records and audio frames produced
+  size_t ifrms_slot_len = 0;                 // S max_blocks of the chain
+  DevBuf<float> d_ifrms;                     // [slots][S][max_blocks]
+  DevBuf<OutPart> d_part;                    // [S][max_blocks]
+  DevBuf<float2> d_state;                    // [S] if_level, audio_level
+  DevBuf<OutRec> d_rec;                      // [S][max_blocks of the config]
+  DevBuf<unsigned char> d_pcm;               // [S][max_frames] frames
+  RecCursor fcur, bcur;                      // frames, records
+  bool rate_set = false;                     // fmr_set_output_rate has been called (48000 stereo leaves `rate` as it is)
+  OutRate rate;
+  int channels() const { return stereo && !(rate.on && rate.mono) ? 2 : 1; }     // of the ring
+  unsigned long long produced() const { return rate.on ? rate.oframes : frames; }   // ring frames
+  size_t frame_bytes() const { return (size_t)channels() * (cfg.format == FMR_PCM_F32 ? 4 : 2); }
+  float *ifrms_slot(int q) { return on ? d_ifrms.p + (size_t)q * ifrms_slot_len : nullptr; }
+  int init(int S, bool chain_stereo, int max_blocks, int slots, const fmr_output_config &m);
+  OutArgs begin(unsigned long long block0, const int *if_len, int nb, long long N_au);
+};
 
 }  // namespace
 
@@ -250,7 +383,7 @@ struct fmr_chain {
   int S = 1, mode = FMR_MODE_FM;
   bool has_rs = false, has_dec = true, fir_enable = false, stereo = false, pilot_shift = false;
   bool enable_mpf = false;
-  hipStream_t stream = nullptr;
+  Stream stream;
   // side stream: per-block bookkeeping (statistics EMAs, PLL lock logic / PPS) runs beside the
   // audio chain instead of in front of it
   bool dec_valid = true;
@@ -277,9 +410,9 @@ struct fmr_chain {
   // statistics, AGC, pilot PLL, lock logic) and audio tail (tail: de-emphasis, audio resampler, pilot cut, DC block,
   // mux) -- and stage k of call N runs beside stage k-1 of call N+1.  What one stage hands the next lives in a ring
   // of kPipe slots (IF samples, MPX, L-R, partial sums, per-block lock flags); a slot is refilled once the tail of the
-  // call that used it kPipe calls ago has finished (h_marks[1], polled by the host).  Everything a stage carries from
+  // call that used it kPipe calls ago has finished (h_marks.p[1], polled by the host).  Everything a stage carries from
   // call to call (halos, StreamState fields) is written by that stage only.
-  hipStream_t tail = nullptr;
+  Stream tail;
   bool pipelined = false;
   static constexpr int kPipe = 4;        // ring slots
   unsigned long long pipe_seq = 0;       // decoded calls issued (slot = pipe_seq % kPipe)
@@ -295,18 +428,18 @@ struct fmr_chain {
   FusedPart *part_slot(int q) { return q ? d_part_pp[q].p : d_fused_part.p; }
   int *stereo_slot(int q) { return q ? d_stereo_pp[q].p : d_stereo_blk.p; }
   float2 *last_if = nullptr;
-  hipEvent_t ev_fe[kPipe] = {};
+  Event ev_fe[kPipe];
   bool disc_commit_on_side = false;      // the last decoded call's discriminator phase is committed by its k_stats (side stream)
   int sync_all() {                       // every stream of the chain is idle afterwards
     if (int rc = flush_tail(nullptr)) return rc;
-    for (hipStream_t st : {stream, side, side2, tail})
+    for (hipStream_t st : {stream.p, side.p, side2, tail.p})
       if (st) HIPCHK(hipStreamSynchronize(st));
     return FMR_OK;
   }
-  hipStream_t side = nullptr, side2 = nullptr;   // side2: the IF AGC when it is off the critical path
-  hipEvent_t ev_pll1 = nullptr;      // pipelined chain: the PLL's second pass is done (the passes after it may run on the side stream)
-  hipEvent_t ev_disc = nullptr, ev_pll = nullptr, ev_stats = nullptr, ev_fin = nullptr, ev_if = nullptr, ev_agc = nullptr,
-             ev_tab = nullptr, ev_mono = nullptr;
+  Stream side, side2_own;
+  hipStream_t side2 = nullptr;       // the IF AGC when it is off the critical path: side2_own, or on a pipelined chain the side stream
+  Event ev_pll1;                     // pipelined chain: the PLL's second pass is done (the passes after it may run on the side stream)
+  Event ev_disc, ev_pll, ev_stats, ev_fin, ev_if, ev_agc, ev_tab, ev_mono;
   int pll_tick2_per_stream = 0;
   bool ev_agc_live = false;            // ev_agc has been recorded by an earlier call
   // designs + counters
@@ -393,92 +526,16 @@ struct fmr_chain {
   DevBuf<float2> d_cb_taps;                 // modulated stage-A taps [group][k][FMR_CB_G]
   DevBuf<ChanPhase> d_cb_ph;                // per channel: f mod F, f D mod F
   unsigned cb_forms = 0;                    // FMR_CB_* bits launched since create
-  // ---- RDS (fmr_create_rds; kernels_rds.hpp, host/fmradion_rds.hpp).  The stage runs at the head
-  // of the audio tail (tail_stage): it reads the call's MPX from the base slot and carries everything else in buffers of
-  // its own (MPX history, y1 / y2 rings, RdsState), which only it writes.  The bits of a call go to a slot of a ring of
-  // page-locked host slots; k_signal_host marks the slot filled and the host decoders drain it (rds_drain).
-  bool rds = false;
-  static constexpr int kRdsSlots = 8;
-  int rds_R = 0, rds_maxw = 0;               // ring length (power of two), windows per call
-  size_t rds_slot_stride = 0;                // bytes per stream in a host slot
-  DevBuf<float> d_rds_h1, d_rds_h2, d_rds_xhalo;
-  DevBuf<float2> d_rds_lo, d_rds_y1, d_rds_y2;
-  DevBuf<RdsState> d_rds_state;
-  DevBuf<RdsEst> d_rds_est;
-  DevBuf<RdsRec> d_rds_rec;
-  char *h_rds_slots = nullptr;
-  unsigned long long *h_rds_mark = nullptr;  // calls whose RDS slot is filled
-  long long rds_n = 0, rds_w = 0;            // MPX samples seen, next window
-  unsigned long long rds_seq = 0, rds_drained = 0;
-  unsigned long long rds_tap_seq = 0;        // slot of the most recent call's windows (0: it completed none): fmr_debug_read 5
-  double rds_gain = 1.0;                     // |soft symbol| of a unit subcarrier (injection estimate)
-  std::vector<fmr_rds::Decoder> rds_dec;
-  std::vector<RdsSlotHdr> rds_hdr;
-  int rds_init();
-  int rds_stage(const fm_mpx_t *base, long long N, hipStream_t st);
-  void rds_drain();
-  // ---- modulation monitor (fmr_enable_monitor; kernels_monitor.hpp).  A second reader of the
-  // call's MPX at the head of the audio tail, beside the RDS stage: it carries the stream's last unconsumed samples in a
-  // buffer of its own and counts in absolute samples (mon.n), so H_b and the cut into calls do not matter.  Nothing of it
-  // exists on a chain that never enabled it.
-  // ---- RF monitor (fmr_enable_rf_monitor; kernels_rfmon.hpp).  A second reader of the call's IF
-  // ring slot (the decoder's input, or |x|^2 behind a discriminator epilogue), beside the modulation monitor: a second
-  // instance of the same engine (SegMonitor) behind the same stage routine.  Nothing of it exists on a chain that never
-  // enabled it.
+  // ---- optional stages (the structs above say what each is).  Nothing of a stage exists on a chain that never enabled it.
+  RdsStage rds;
   SegMonitor mon, rfm;
-  fmr_monitor_config mon_cfg{};              // the defaults filled in
-  fmr_rf_monitor_config rfm_cfg{};
+  LoudnessStage ld;
+  OutputStage out;
+  int rds_stage(const fm_mpx_t *base, long long N, hipStream_t st);
   // one call's N samples per stream through monitor m on stream st: the source as kseg / kreduce read it (from, stride, off)
   int seg_stage(SegMonitor &m, const void *from, long long stride, int off, float rf, float scale, MonSegFn kseg,
                 MonReduceFn kreduce, const char *seg_name, const char *reduce_name, long long N, hipStream_t st);
-  // ---- audio monitor (fmr_enable_loudness; kernels_loudness.hpp).  A reader of the call's finished
-  // audio behind the output mux, on the tail's stream: it counts in absolute audio samples (ld_n) and keeps its own
-  // carries (the K-weighting state, the true-peak history, the open record).  Nothing of it exists unless it is enabled.
-  bool ld = false;
-  fmr_loudness_config ld_cfg{};              // the defaults filled in
-  int ld_cps = 0, ld_rmax = 0, ld_par = 0;   // chunks per sub-block, runs per stream and launch, current copy of the open records
-  long long ld_n = 0;                        // audio samples seen (per channel)
-  LdCoef ld_coef{};
-  DevBuf<double> d_ld_pw, d_ld_taps, d_ld_G, d_ld_start, d_ld_pkw, d_ld_state, d_ld_hist;
-  DevBuf<LdPart> d_ld_part;
-  DevBuf<LdRec> d_ld_open, d_ld_ring;
-  RecCursor ld_cur;
-  unsigned long long ld_done() const { return (unsigned long long)(ld_n / (long long)ld_cfg.step_samples); }   // records complete
-  int ld_init(const fmr_loudness_config &m);
   int ld_stage(const double *d_aud, long long astride, long long N, hipStream_t st);
-  // ---- output stage (fmr_enable_output; kernels_output.hpp).  The last reader of the call's
-  // finished audio, on the stream that wrote it: squelch, gain and PCM conversion into a ring of frames per stream, and one
-  // record per block with the stream loop's meters.  The block, frame and record counters live here and are taken when a
-  // call is issued (out_begin); the device carries the two levels.  k_stats leaves every block's IF RMS in the call's
-  // slot of d_out_ifrms (the tail of a pipelined chain runs a call late).  Nothing of it exists unless it is enabled.
-  bool out = false;
-  fmr_output_config out_cfg{};               // the defaults filled in
-  unsigned long long out_block = 0, out_recs = 0, out_frames = 0;   // blocks handed in, records and audio frames produced
-  DevBuf<float> d_out_ifrms;                 // [kPipe][S][max_blocks]
-  DevBuf<OutPart> d_out_part;                // [S][max_blocks]
-  DevBuf<float2> d_out_state;                // [S] if_level, audio_level
-  DevBuf<OutRec> d_out_rec;                  // [S][max_blocks of the config]
-  DevBuf<unsigned char> d_out_pcm;           // [S][max_frames] frames
-  RecCursor out_fcur, out_bcur;              // frames, records
-  // rate converter (fmr_set_output_rate): with out_conv the ring is written by k_out_rate from the
-  // staged z instead of by k_out_pcm, out_oframes counts its frames, and the stream's clip / non-finite totals live in
-  // d_out_tot.  Two staging rows: a call's z goes behind the T - 1 frames of history at the head of row out_zpar, and
-  // what it leaves as history to the head of the other row.  Nothing of it exists without the call.
-  bool out_rate_set = false, out_conv = false;
-  int out_hz = kOutRateIn;
-  OutRateGeom out_geom{1, 1, 1, 0, 0, 0};
-  unsigned long long out_oframes = 0;
-  int out_zpar = 0;
-  DevBuf<double> d_out_z, d_out_taps;        // [2][S][zstride]; the prototype, T L
-  DevBuf<unsigned long long> d_out_tot;      // [S][2]
-  int out_channels() const { return stereo && !(out_conv && out_mono) ? 2 : 1; }     // of the ring
-  bool out_mono = false;
-  unsigned long long out_produced() const { return out_conv ? out_oframes : out_frames; }   // ring frames
-  int out_rate_init(int rate, bool mono);
-  size_t out_frame_bytes() const { return (size_t)out_channels() * (out_cfg.format == FMR_PCM_F32 ? 4 : 2); }
-  float *out_ifrms_slot(int q) { return out ? d_out_ifrms.p + (size_t)q * S * max_blocks : nullptr; }
-  int out_init(const fmr_output_config &m);
-  OutArgs out_begin(unsigned long long block0, const int *if_len, int nb, long long N_au);
   int out_stage(const double *d_aud, long long astride, const BlockTab &bt, const float *if_rms_blk, const OutArgs &a, hipStream_t st);
   int in_rows() const { return bank ? 1 : S; }   // rows of the input buffers (d_in, d_in_halo)
   // front end only (fmr_resample_blocks_device): stage B writes row s of this call's IF samples to if_out + s if_out_stride
@@ -530,10 +587,10 @@ struct fmr_chain {
   int fe_spare_cus = 0;           // compute units the last front-end launch left alone
   size_t side_ballast() const { return (pipelined && fe_spare_cus >= kBallastMinSpare) ? (size_t)kBallastBytes : 0; }
   static constexpr int kFeSpareCus = FMR_FE_SPARE_CUS;      // CUs the pipelined chain's front end leaves to the kernels beside it
-  int *h_tab_all = nullptr;  // pinned, kTabSlots * tab_ints
+  HostBuf<int> h_tab_all;    // pinned, kTabSlots * tab_ints
   size_t tab_ints = 0;       // 5*max_blocks block table + 3*max_ck chunk table + (max_blocks+1) first-chunk table
   unsigned long long call_seq = 0;      // calls issued
-  unsigned long long *h_marks = nullptr; // pinned: [0] calls whose table copy has run, [1] pipelined calls whose decoder has finished
+  HostBuf<unsigned long long> h_marks;   // pinned: [0] calls whose table copy has run, [1] pipelined calls whose decoder has finished
   std::vector<StreamState> h_state;
   // constants
   PllConst pllc{};
@@ -551,7 +608,7 @@ struct fmr_chain {
   std::vector<KernelTime> ktimes;
   std::vector<KernelTime> trace;        // mode 3
   std::vector<int> trace_stream;        //   0 decoder, 1 side, 2 side2, 3 front end, 4 tail
-  hipEvent_t trace_base = nullptr;
+  Event trace_base;
   static constexpr size_t kMaxTrace = 1u << 16;      // event pairs kept until fmr_get_kernel_trace fetches them (further kernels run untraced)
 
   ~fmr_chain() {
@@ -566,53 +623,13 @@ struct fmr_chain {
     // a tail stage that was never enqueued (an asynchronous last call nobody synchronised) is dropped, not launched: its
     // output mux would write into the caller's audio buffer, which the caller may have freed by now
     tail_pending = false; walk_pending = false; walk_job = nullptr;
-    for (hipStream_t st : {stream, side, side2, tail}) if (st) (void)hipStreamSynchronize(st);
-    for (auto &k : ktimes) { (void)hipEventDestroy(k.a); (void)hipEventDestroy(k.b); }
-    for (auto &k : trace) { (void)hipEventDestroy(k.a); (void)hipEventDestroy(k.b); }
-    if (trace_base) (void)hipEventDestroy(trace_base);
-    for (auto &k : dom_times) { (void)hipEventDestroy(k.a); (void)hipEventDestroy(k.b); }
-    d_in.release(); d_in_halo.release(); d_mid.release(); d_if.release(); d_fir.release();
-    d_mpf.release(); d_mpf_coeff.release(); d_mpf_state.release(); d_gain.release(); d_dec.release(); d_agc_progress.release();
-    d_hA.release(); d_hB.release(); d_coeff.release(); d_atan.release(); d_if_rms_blk.release();
-    d_bb_mean_blk.release(); d_bb_rms_blk.release(); d_blk_ph.release(); d_base.release(); d_raw.release();
-    d_am0.release(); d_am1.release(); d_a10.release(); d_a11.release(); d_pc0.release();
-    d_pc1.release(); d_audio.release(); d_ahA.release(); d_ahB.release(); d_pilotcut.release();
-    d_ft_pre.release(); d_ft_post.release(); d_hB_last.release(); d_zero16.release(); d_fe_stamps.release(); d_fused_mid32.release(); d_fused_afragA.release(); d_fused_afragB.release(); d_fused_part.release(); d_afrag.release(); d_afrag_fir_fm.release(); d_dec16_afrag.release(); d_run_ph.release(); d_afrag_fir.release(); d_afrag5h.release(); d_hBp.release(); d_hpA.release(); d_bphi.release(); d_boff.release(); d_tab.release(); d_mpf_ok.release(); d_stereo_blk.release(); d_state.release();
-    d_base_de.release(); d_raw_de.release(); d_pll_nodes.release(); d_pll_G.release(); d_pll_M.release();
-    d_pll_wgr.release(); d_pll_pre.release(); d_pll_wfirst.release(); d_pll_sync.release(); d_pll_tick2.release(); d_ck_mask.release(); d_walk_go.release(); d_pll_gres.release(); d_pll_PQ2.release(); d_pll_dstart2.release(); d_pll_PQ.release(); d_pll_dstart.release(); d_blk_level.release(); d_blk_wraps.release(); d_agc_M.release(); d_agc_tick.release(); d_af_tick.release(); d_dc_G.release(); d_dc_start.release(); d_agc_nodes.release();
-    d_agc_G.release(); d_ck_wraps.release(); d_flags.release();
-    d_af_nodes.release(); d_af_G.release(); d_af_M.release(); d_af_out.release();
-    d_cb_taps.release(); d_cb_ph.release();
-    d_rds_h1.release(); d_rds_h2.release(); d_rds_xhalo.release(); d_rds_lo.release(); d_rds_y1.release(); d_rds_y2.release();
-    d_rds_state.release(); d_rds_est.release(); d_rds_rec.release();
-    mon.release(); rfm.release();
-    d_ld_pw.release(); d_ld_taps.release(); d_ld_G.release(); d_ld_start.release(); d_ld_pkw.release(); d_ld_state.release();
-    d_ld_hist.release(); d_ld_part.release(); d_ld_open.release(); d_ld_ring.release();
-    d_out_ifrms.release(); d_out_part.release(); d_out_state.release(); d_out_rec.release(); d_out_pcm.release();
-    d_out_z.release(); d_out_taps.release(); d_out_tot.release();
-    if (h_rds_slots) (void)hipHostFree(h_rds_slots);
-    if (h_rds_mark) (void)hipHostFree(h_rds_mark);
-    if (h_tab_all) (void)hipHostFree(h_tab_all);
-    if (h_marks) (void)hipHostFree(h_marks);
-    for (hipEvent_t e : {ev_disc, ev_pll, ev_stats, ev_fin, ev_if}) if (e) (void)hipEventDestroy(e);
-    if (side2 == side) side2 = nullptr;      // (pipelined chain: the AGC runs on the side stream)
-    if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
+    // THE rule of this destructor: every stream of the chain is idle before any member dies.  Then nothing on the device
+    // refers to a buffer, an event or a pinned block any more, the owners give everything back, and the order in which
+    // the members die does not matter.
+    for (hipStream_t st : {stream.p, side.p, side2, tail.p}) if (st) (void)hipStreamSynchronize(st);
     if (host_prof && hp_calls)
       fprintf(stderr, "[fmr host prof] calls %lld  front-end %.1f us  tables %.1f us  decoder %.1f us per call\n", hp_calls,
               hp_fe / hp_calls, hp_tab / hp_calls, hp_dec / hp_calls);
-    if (side2 && side2 != side) { (void)hipStreamSynchronize(side2); (void)hipStreamDestroy(side2); }
-    if (tail) (void)hipStreamDestroy(tail);
-    for (auto &e : ev_fe) if (e) (void)hipEventDestroy(e);
-    for (auto &b : d_if_pp) b.release();
-    for (auto &b : d_base_pp) b.release();
-    for (auto &b : d_raw_pp) b.release();
-    for (auto &b : d_part_pp) b.release();
-    for (auto &b : d_stereo_pp) b.release();
-    if (ev_agc) (void)hipEventDestroy(ev_agc);
-    if (ev_pll1) (void)hipEventDestroy(ev_pll1);
-    if (ev_tab) (void)hipEventDestroy(ev_tab);
-    if (ev_mono) (void)hipEventDestroy(ev_mono);
-    if (stream) (void)hipStreamDestroy(stream);
   }
 
   // ---- kernel launch with optional HIP-event timing on the chain's stream ----
@@ -641,9 +658,8 @@ struct fmr_chain {
     const bool own_events = !env.evt_markers && std::strcmp(name, "ifr_fused") == 0;
     const bool sampled = timing == 2 || ((timing == 4 || timing == 5) && (call_seq & 3ull) == 0);
     if (stage_kernel && (sampled || (timing == 5 && own_events))) {
-      KernelTime kt{name, nullptr, nullptr};
-      (void)hipEventCreate(&kt.a);
-      (void)hipEventCreate(&kt.b);
+      KernelTime kt{name};
+      (void)kt.a.create(); (void)kt.b.create();
       if (own_events) {
         ext_a = kt.a; ext_b = kt.b;
         launch();
@@ -653,29 +669,23 @@ struct fmr_chain {
         launch();
         (void)hipEventRecord(kt.b, st);
       }
-      dom_times.push_back(kt);
+      dom_times.push_back(std::move(kt));
       return;
     }
-    if (timing == 3 && trace.size() < kMaxTrace) {      // trace: every instrumented kernel of every call since the mode was switched on, with its stream
-      if (!trace_base) { (void)hipEventCreate(&trace_base); (void)hipEventRecord(trace_base, st); }
-      KernelTime kt{name, nullptr, nullptr};
-      (void)hipEventCreate(&kt.a);
-      (void)hipEventCreate(&kt.b);
+    auto between_markers = [&](std::vector<KernelTime> &into) {
+      KernelTime kt{name};
+      (void)kt.a.create(); (void)kt.b.create();
       (void)hipEventRecord(kt.a, st);
       launch();
       (void)hipEventRecord(kt.b, st);
-      trace.push_back(kt);
+      into.push_back(std::move(kt));
+    };
+    if (timing == 3 && trace.size() < kMaxTrace) {      // trace: every instrumented kernel of every call since the mode was switched on, with its stream
+      if (!trace_base) { (void)trace_base.create(); (void)hipEventRecord(trace_base, st); }
+      between_markers(trace);
       trace_stream.push_back(st == stream ? 0 : st == side ? 1 : st == side2 ? 2 : 4);
-      return;
-    }
-    if (timing != 1) { launch(); return; }
-    KernelTime kt{name, nullptr, nullptr};
-    (void)hipEventCreate(&kt.a);
-    (void)hipEventCreate(&kt.b);
-    (void)hipEventRecord(kt.a, st);
-    launch();
-    (void)hipEventRecord(kt.b, st);
-    ktimes.push_back(kt);
+    } else if (timing == 1) between_markers(ktimes);
+    else launch();
   }
   template <class F>
   void timed(const char *name, F &&launch) { timed_on(stream, name, launch); }
@@ -844,6 +854,17 @@ struct fmr_chain {
           size_t astride, uint32_t *audio_len);
 };
 
+// An optional stage is all or nothing: it is built in a local object and moved into the chain only when its init() has
+// succeeded.  A failed enable leaves the chain exactly as it was (the local dies with whatever it had allocated), and the
+// same call may be made again.
+template <class St, class... A>
+static int build_stage(St &into, A &&...args) {
+  St s;
+  if (int rc = s.init(args...)) return rc;
+  into = std::move(s);
+  return FMR_OK;
+}
+
 template <class T>
 static int upload(DevBuf<T> &b, const T *src, size_t n) {
   int rc = b.alloc(n);
@@ -919,20 +940,18 @@ int fmr_chain::init(const fmr_config *c, bool channelizer) {
   // busy queues than that take turns on a pipe in slices of 3.55 ms (measured with four and five busy queues, with and
   // without stream priorities: one process in two then runs at 4-36 ms per step).
   pipelined = mode == FMR_MODE_FM && c->enable_resampler != 0 && !env.serial && env.pipeline != 0 && c->in_order == 0;
-  HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  HIPCHK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+  int rc0;
+  if ((rc0 = stream.create()) || (rc0 = side.create())) return rc0;
   if (pipelined) {
     side2 = side;
-    HIPCHK(hipStreamCreateWithFlags(&tail, hipStreamNonBlocking));
-    for (int q = 0; q < kPipe; q++) HIPCHK(hipEventCreateWithFlags(&ev_fe[q], hipEventDisableTiming));
+    if ((rc0 = tail.create())) return rc0;
+    for (Event &e : ev_fe) if ((rc0 = e.create(hipEventDisableTiming))) return rc0;
   } else {
-    HIPCHK(hipStreamCreateWithFlags(&side2, hipStreamNonBlocking));
+    if ((rc0 = side2_own.create())) return rc0;
+    side2 = side2_own;
   }
-  HIPCHK(hipEventCreateWithFlags(&ev_agc, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&ev_pll1, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&ev_tab, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&ev_mono, hipEventDisableTiming));
-  for (hipEvent_t *e : {&ev_disc, &ev_pll, &ev_stats, &ev_fin, &ev_if}) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  for (Event *e : {&ev_agc, &ev_pll1, &ev_tab, &ev_mono, &ev_disc, &ev_pll, &ev_stats, &ev_fin, &ev_if})
+    if ((rc0 = e->create(hipEventDisableTiming))) return rc0;
   double dec_rate = (mode == FMR_MODE_FM || mode == FMR_MODE_NONE) ? kFmRate : kAmRate;
   if (mode == FMR_MODE_NONE && c->output_rate > 0) dec_rate = c->output_rate;     // IfResampler(in, out), IfResampler.h:35
   has_rs = c->enable_resampler != 0;
@@ -1163,19 +1182,17 @@ int fmr_chain::init(const fmr_config *c, bool channelizer) {
   if ((rc = upload(d_state, h_state.data(), h_state.size()))) return rc;
   max_ck = std::max(max_if / (size_t)c_pll, std::min<size_t>(max_if, (size_t)kSmallCall) / (size_t)kCPllSmall) + (size_t)max_blocks + 2;
   tab_ints = 5 * (size_t)max_blocks + 3 * max_ck + (size_t)max_blocks + 1 + kMaxFusedWg;   // tail: first block of each fused workgroup
-  HIPCHK(hipHostMalloc((void **)&h_tab_all, sizeof(int) * kTabSlots * tab_ints));
+  if (int rch = h_tab_all.alloc(kTabSlots * tab_ints, hipHostMallocDefault)) return rch;
   // The marks are written by one-thread kernels and polled by the host while more work is queued behind them: COHERENT
   // (fine-grained) host memory, so that the store leaves the GPU when it is made.  With the default flags the line may sit
   // in the GPU's L2 until some later system-scope release writes it back, and a host that waits for a mark sees it
   // milliseconds late (measured: one process in two ran at 4-36 ms per step, in multiples of 3.55 ms).
-  HIPCHK(hipHostMalloc((void **)&h_marks, 2 * sizeof(unsigned long long), hipHostMallocCoherent));
-  h_marks[0] = h_marks[1] = 0;
+  if (int rch = h_marks.alloc(2, hipHostMallocCoherent)) return rch;
+  h_marks.p[0] = h_marks.p[1] = 0;
   if ((rc = d_tab.alloc((size_t)kTabSlots * tab_ints))) return rc;
   h_flags.assign(S, IterFlags{});
   if ((rc = d_flags.alloc((size_t)S))) return rc;
-  {
-    serial_mode = env.serial;
-  }
+  serial_mode = env.serial;
   max_agc_nc = max_if / C_AGC + 2;
   if (has_dec) {
     if ((rc = d_agc_nodes.alloc((size_t)S * (max_agc_nc + 1)))) return rc;
@@ -1589,17 +1606,16 @@ int fmr_chain::run(const float2 *d_iq, size_t stride, const uint32_t *block_len,
       c->hp_calls++;
     }
   } host_prof_guard{this, hp0, hp1, hp2};
-  for (auto &k : ktimes) { (void)hipEventDestroy(k.a); (void)hipEventDestroy(k.b); }
   ktimes.clear();
   // Table slot ring: the slot is free once the copy kernel of the call that used it kTabSlots calls ago has run.
   // That kernel's successor writes a counter into pinned host memory which is polled here -- hipEventSynchronize
   // would block until the newest signal of the side stream at call time (most of the PREVIOUS call) and stop the
   // host from enqueueing ahead (measured).
-  if (rds) rds_drain();                 // (what the device has finished: keeps the host decoders a call or two behind)
+  if (rds.on) rds.drain();                 // (what the device has finished: keeps the host decoders a call or two behind)
   call_seq++;
   const int slot = (int)(call_seq % kTabSlots);
-  if (int rcw = wait_mark(&h_marks[0], call_seq > (unsigned long long)kTabSlots ? call_seq - kTabSlots : 0)) return rcw;
-  int *h_tab = h_tab_all + (size_t)slot * tab_ints;
+  if (int rcw = wait_mark(&h_marks.p[0], call_seq > (unsigned long long)kTabSlots ? call_seq - kTabSlots : 0)) return rcw;
+  int *h_tab = h_tab_all.p + (size_t)slot * tab_ints;
   int *d_tab_slot = d_tab.p + (size_t)slot * tab_ints;
   int *t_if_off = h_tab, *t_if_len = h_tab + max_blocks, *t_au_off = h_tab + 2 * max_blocks,
       *t_au_len = h_tab + 3 * max_blocks, *t_mpf = h_tab + 4 * max_blocks;
@@ -1608,7 +1624,7 @@ int fmr_chain::run(const float2 *d_iq, size_t stride, const uint32_t *block_len,
   k.d_iq = d_iq; k.stride = stride; k.block_len = block_len; k.nb = nb; k.d_aud = d_aud; k.astride = astride;
   k.audio_len = audio_len; k.N_in = N_in; k.slot = slot; k.h_tab = h_tab; k.d_tab_slot = d_tab_slot;
   k.t_if_off = t_if_off; k.t_if_len = t_if_len; k.t_au_off = t_au_off; k.t_au_len = t_au_len; k.t_mpf = t_mpf;
-  if (out) { k.out_block0 = out_block; out_block += (unsigned long long)nb; }   // (every block handed in counts, empty ones too)
+  if (out.on) { k.out_block0 = out.block; out.block += (unsigned long long)nb; }   // (every block handed in counts, empty ones too)
   if (int rc = run_front_end(k)) return rc;
   if (k.done) return flush_tail(nullptr);     // (nothing to decode: a pending tail refers to a table slot this call's successors will reuse)
   k.base = base_slot(k.par); k.raw = raw_slot(k.par); k.part = part_slot(k.par); k.stereo_blk = stereo_slot(k.par);
@@ -1744,7 +1760,7 @@ int fmr_chain::run_front_end(CallCtx &k) {
       k.par = (int)(pipe_seq % kPipe);
       // (one slot less than the ring holds: the slot of call N is still read at the head of call N+1, by the kernel that
       // carries its halos over, and that kernel is only ordered before the tail of call N+1)
-      if (int rcw = wait_mark(&h_marks[1], pipe_seq > (unsigned long long)(kPipe - 1) ? pipe_seq - (kPipe - 1) : 0)) return rcw;
+      if (int rcw = wait_mark(&h_marks.p[1], pipe_seq > (unsigned long long)(kPipe - 1) ? pipe_seq - (kPipe - 1) : 0)) return rcw;
     }
     k.ifbuf = if_slot(k.par);
     last_if = k.ifbuf;
@@ -1905,7 +1921,7 @@ int fmr_chain::run_front_end(CallCtx &k) {
     k.add_halo(d_mid.p, H_mid + (long long)max_mid, H_mid, count_mid);
   }
   if (!has_dec || N_if == 0) {
-    hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, side, &h_marks[0], call_seq);   // no table this call
+    hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, side, &h_marks.p[0], call_seq);   // no table this call
     if (k.audio_len) for (int b = 0; b < k.nb; b++) k.audio_len[b] = 0;
     if (has_dec && fir_enable && !pipelined) k.add_halo(k.ifbuf, H_if + (long long)max_if, H_if, N_if);
     if (k.ht.n) hipLaunchKernelGGL(k_shift_halo<256>, dim3(k.ht.n, S), dim3(256), 0, stream, k.ht);
@@ -2011,7 +2027,7 @@ int fmr_chain::run_tables(CallCtx &k) {
     k.fused_n_tiles = fr.tiles;
     fe_spare_cus = std::max(0, n_cu - fr.grid * S);
     const long long kb_ref = 384 * fused_T_first - p.prev.kB;
-    fused_part_from = k.t_if_off[out ? 0 : first_part_block(k.t_if_len, nb)];
+    fused_part_from = k.t_if_off[out.on ? 0 : first_part_block(k.t_if_len, nb)];
     // Where the runs start: a macro tile whose epilogue writes the per-block partial sums (the last ~400 blocks of a call:
     // block walk, six wave reductions and a store per 128 samples) costs its workgroup kFusedSumWeight more than one that does
     // not -- measured, round 6: the workgroups of the last fifth of a 2048-block call took 207-213 us against the others' 194-197
@@ -2047,14 +2063,14 @@ int fmr_chain::run_tables(CallCtx &k) {
     k.fused_n_tiles = 8 * fr.tiles;                             // in the epilogue's macro tiles of 384 samples
     const long long kb_ref = 48 * (p.prev.kB / 48) - p.prev.kB;
     k.fused_kb_ref = (int)kb_ref;
-    fused_part_from = k.t_if_off[out ? 0 : first_part_block(k.t_if_len, nb)];
+    fused_part_from = k.t_if_off[out.on ? 0 : first_part_block(k.t_if_len, nb)];
     fill_run_blocks(k, t_wg, fr, nullptr, kb_ref, 3072);
     copy_runs(fr.grid);
   }
   int *d_first = d_tab_slot + 5 * (size_t)max_blocks;
   int *d_ck = d_tab_slot + head_ints;
   k.ct = ChunkTab{d_ck, d_ck + max_ck, d_ck + 2 * max_ck, d_first, k.nck};
-  hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, side, &h_marks[0], call_seq);
+  hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, side, &h_marks.p[0], call_seq);
   if (mode == FMR_MODE_FM && k.nck > 0) {
     hipLaunchKernelGGL(k_chunk_tab, dim3(nb), dim3(64), 0, side, d_tab_slot, d_tab_slot + max_blocks, d_first, c_call,
                        d_ck, d_ck + max_ck, d_ck + 2 * max_ck);
@@ -2227,7 +2243,7 @@ int fmr_chain::run_if_stage(CallCtx &k) {
     a.dec = debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
     a.nf = disc_nf; a.bound = disc_bound;
     const TileRuns &r = p.fir_runs;
-    a.st = d_state.p; a.part = k.part; a.n_tiles = 8 * r.tiles; a.part_from = k.t_if_off[out ? 0 : first_part_block(k.t_if_len, nb)];
+    a.st = d_state.p; a.part = k.part; a.n_tiles = 8 * r.tiles; a.part_from = k.t_if_off[out.on ? 0 : first_part_block(k.t_if_len, nb)];
     a.if_off = bt.if_off; a.if_len = bt.if_len; a.nb = nb;
     a.wg_blk0 = k.d_tab_slot + (tab_ints - kMaxFusedWg) + kFirBlk0Off;
     a.mid32 = d_run_ph.p;
@@ -2623,7 +2639,7 @@ int fmr_chain::run_fm(CallCtx &k) {
     hipLaunchKernelGGL(k_stats, dim3(S), dim3(FMR_STATS_THREADS), stats_ballast, side, bt, d_if_rms_blk.p, d_bb_mean_blk.p,
                        d_bb_rms_blk.p, d_state.p, S, (int)!(pipelined && p.b_disc),   // (the front-end stage commits its own phase)
                        (p.b_disc || p.fir_tail()) ? k.part : (const FusedPart *)nullptr, p.fir_tail() ? 8 * p.fir_runs.tiles : fused_n_tiles,
-                       p.fir_tail() ? 0 : fused_kb_ref, out_ifrms_slot(k.par));
+                       p.fir_tail() ? 0 : fused_kb_ref, out.ifrms_slot(k.par));
   });
   HIPCHK(hipEventRecord(ev_stats, side));
   disc_commit_on_side = !(pipelined && p.b_disc);
@@ -2634,7 +2650,7 @@ int fmr_chain::run_fm(CallCtx &k) {
   t.base = k.base; t.raw = k.raw; t.stereo_blk = k.stereo_blk; t.N_if = N_if; t.N_au = N_au; t.nb = nb; t.bt = bt;
   t.d_aud = d_aud; t.astride = (long long)astride; t.amA_prev = amA_prev; t.akB_prev = akB_prev;
   t.nch = stereo ? 2 : 1;
-  if (out) { t.out = out_begin(k.out_block0, k.t_if_len, nb, N_au); t.out_ifrms = out_ifrms_slot(k.par); }
+  if (out.on) { t.out = out.begin(k.out_block0, k.t_if_len, nb, N_au); t.out_ifrms = out.ifrms_slot(k.par); }
   for (int b = 0; b < nb; b++) t.au_max = std::max(t.au_max, t_au_len[b]);
   t.count_am = (int)(arsc.mA - amA_prev);
   if ((size_t)t.count_am > max_amid || (size_t)N_au > max_au) { set_err("internal audio capacity exceeded"); return FMR_ERR_CAPACITY; }
@@ -2779,10 +2795,10 @@ void fmr_chain::tail_channels(const TailCtx &t, hipStream_t st, int ch_base, int
 // The audio tail of one call on stream ts: the channels the PLL stage has not already run beside itself, the DC block's
 // node pass, the output mux, and the joins with what ran beside the decoder stream (statistics, AGC, lock logic).
 int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
-  if (rds) if (int rc = rds_stage(t.base, t.N_if, ts)) return rc;
+  if (rds.on) if (int rc = rds_stage(t.base, t.N_if, ts)) return rc;
   if (mon.on)
-    if (int rc = seg_stage(mon, t.base, H_b + (long long)max_if, H_b, (float)mon_cfg.hist_range,
-                           (float)((double)mon_cfg.hist_bins / (2.0 * mon_cfg.hist_range)), k_mon_seg<MonMpxSrc>,
+    if (int rc = seg_stage(mon, t.base, H_b + (long long)max_if, H_b, (float)mon.hist_range,
+                           (float)((double)mon.bins / (2.0 * mon.hist_range)), k_mon_seg<MonMpxSrc>,
                            k_mon_reduce<MonMpxSrc>, "mon_seg", "mon_reduce", t.N_if, ts))
       return rc;
   if (rfm.on)      // (the IF ring slot holds IF samples, or |x|^2 when if_nrm; the integer bin rule takes no range)
@@ -2817,13 +2833,13 @@ int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
       });
     }
   }
-  if (ld) if (int rc = ld_stage(t.d_aud, t.astride, N_au, ts)) return rc;
+  if (ld.on) if (int rc = ld_stage(t.d_aud, t.astride, N_au, ts)) return rc;
   if (!(t.fin_covers_all && N_au > 0)) {        // (otherwise the wait before the output mux covered all three)
     HIPCHK(hipStreamWaitEvent(ts, ev_stats, 0));
     if (t.agc_on_side) HIPCHK(hipStreamWaitEvent(ts, ev_agc, 0));
     if (t.fin_on_side) HIPCHK(hipStreamWaitEvent(ts, ev_fin, 0));
   }
-  if (out) if (int rc = out_stage(t.d_aud, t.astride, t.bt, t.out_ifrms, t.out, ts)) return rc;   // (behind the statistics: ev_stats)
+  if (out.on) if (int rc = out_stage(t.d_aud, t.astride, t.bt, t.out_ifrms, t.out, ts)) return rc;   // (behind the statistics: ev_stats)
   return FMR_OK;
 }
 
@@ -2836,11 +2852,12 @@ static double rds_pulse(double t) {
   if (std::fabs(std::fabs(u) - 1.0) < 1e-9) return M_PI / 4.0;
   return std::cos(M_PI * u / 2.0) / (1.0 - u * u);
 }
-int fmr_chain::rds_init() {
+int RdsStage::init(int streams, size_t max_if) {
+  S = streams;
   const size_t need = max_if / kRdsD + 5 * 1300 + 256;
-  rds_R = 1;
-  while ((size_t)rds_R < need) rds_R <<= 1;
-  rds_maxw = (int)(((double)max_if * 19.0) / (double)(kRdsWin * kRdsSym)) + 3;
+  R = 1;
+  while ((size_t)R < need) R <<= 1;
+  maxw = (int)(((double)max_if * 19.0) / (double)(kRdsWin * kRdsSym)) + 3;
   std::vector<float> h1(kRdsNT1), h2(kRdsNT2);
   double sum = 0.0;
   std::vector<double> hd(kRdsNT1);
@@ -2862,75 +2879,76 @@ int fmr_chain::rds_init() {
     y0 += h2[j] * 0.5 * d(-u);
     yT += h2[j] * 0.5 * d(T - u);
   }
-  rds_gain = std::fabs(y0 - yT);
+  gain = std::fabs(y0 - yT);
   std::vector<float2> lo(128);
   for (int i = 0; i < 128; i++) lo[i] = make_float2((float)std::cos(2.0 * M_PI * i / 128.0), (float)-std::sin(2.0 * M_PI * i / 128.0));
   int rc;
-  if ((rc = upload(d_rds_h1, h1.data(), h1.size()))) return rc;
-  if ((rc = upload(d_rds_h2, h2.data(), h2.size()))) return rc;
-  if ((rc = upload(d_rds_lo, lo.data(), lo.size()))) return rc;
-  if ((rc = d_rds_xhalo.alloc((size_t)S * kRdsHalo))) return rc;
-  if ((rc = d_rds_y1.alloc((size_t)S * rds_R))) return rc;
-  if ((rc = d_rds_y2.alloc((size_t)S * rds_R))) return rc;
-  if ((rc = d_rds_state.alloc((size_t)S))) return rc;
-  if ((rc = d_rds_est.alloc((size_t)S * rds_maxw))) return rc;
-  if ((rc = d_rds_rec.alloc((size_t)S * (rds_maxw + 1)))) return rc;
-  rds_slot_stride = (rds_slot_bytes(rds_maxw) + 63) & ~(size_t)63;
-  HIPCHK(hipHostMalloc((void **)&h_rds_slots, rds_slot_stride * (size_t)S * kRdsSlots, hipHostMallocCoherent));
-  HIPCHK(hipHostMalloc((void **)&h_rds_mark, sizeof(unsigned long long), hipHostMallocCoherent));
-  *h_rds_mark = 0;
-  rds_dec.assign(S, fmr_rds::Decoder());
-  rds_hdr.assign(S, RdsSlotHdr{});
+  if ((rc = upload(d_h1, h1.data(), h1.size()))) return rc;
+  if ((rc = upload(d_h2, h2.data(), h2.size()))) return rc;
+  if ((rc = upload(d_lo, lo.data(), lo.size()))) return rc;
+  if ((rc = d_xhalo.alloc((size_t)S * kRdsHalo))) return rc;
+  if ((rc = d_y1.alloc((size_t)S * R))) return rc;
+  if ((rc = d_y2.alloc((size_t)S * R))) return rc;
+  if ((rc = d_state.alloc((size_t)S))) return rc;
+  if ((rc = d_est.alloc((size_t)S * maxw))) return rc;
+  if ((rc = d_rec.alloc((size_t)S * (maxw + 1)))) return rc;
+  slot_stride = (rds_slot_bytes(maxw) + 63) & ~(size_t)63;
+  if ((rc = h_slots.alloc(slot_stride * (size_t)S * kSlots, hipHostMallocCoherent))) return rc;
+  if ((rc = h_mark.alloc(1, hipHostMallocCoherent))) return rc;
+  *h_mark.p = 0;
+  dec.assign(S, fmr_rds::Decoder());
+  hdr.assign(S, RdsSlotHdr{});
+  on = true;
   return FMR_OK;
 }
 
 // one call's MPX (N samples per stream from the base slot) through the RDS stage, on stream st
 int fmr_chain::rds_stage(const fm_mpx_t *base, long long N, hipStream_t st) {
-  rds_tap_seq = 0;
+  rds.tap_seq = 0;
   if (N <= 0) return FMR_OK;
   const long long base_stride = H_b + (long long)max_if;
-  const long long n0 = rds_n, m0 = (n0 + kRdsD - 1) / kRdsD, m1 = (n0 + N + kRdsD - 1) / kRdsD;
+  const long long n0 = rds.n, m0 = (n0 + kRdsD - 1) / kRdsD, m1 = (n0 + N + kRdsD - 1) / kRdsD;
   const int cnt = (int)(m1 - m0);
   timed_on(st, "rds_mix", [&] {
     if (cnt > 0) {
-      hipLaunchKernelGGL(k_rds_mix<256>, dim3((cnt + 255) / 256, S), dim3(256), 0, st, base, base_stride, H_b, d_rds_xhalo.p,
-                         n0, m0, cnt, d_rds_h1.p, d_rds_lo.p, d_rds_y1.p, rds_R);
-      hipLaunchKernelGGL(k_rds_mf<256>, dim3((cnt + 255) / 256, S), dim3(256), 0, st, d_rds_y1.p, d_rds_y2.p, rds_R, m0, cnt,
-                         d_rds_h2.p);
+      hipLaunchKernelGGL(k_rds_mix<256>, dim3((cnt + 255) / 256, S), dim3(256), 0, st, base, base_stride, H_b, rds.d_xhalo.p,
+                         n0, m0, cnt, rds.d_h1.p, rds.d_lo.p, rds.d_y1.p, rds.R);
+      hipLaunchKernelGGL(k_rds_mf<256>, dim3((cnt + 255) / 256, S), dim3(256), 0, st, rds.d_y1.p, rds.d_y2.p, rds.R, m0, cnt,
+                         rds.d_h2.p);
     }
-    hipLaunchKernelGGL(k_rds_halo, dim3(S), dim3(kRdsHalo), 0, st, base, base_stride, H_b, d_rds_xhalo.p, n0, (int)N);
+    hipLaunchKernelGGL(k_rds_halo, dim3(S), dim3(kRdsHalo), 0, st, base, base_stride, H_b, rds.d_xhalo.p, n0, (int)N);
   });
-  rds_n = n0 + N;
+  rds.n = n0 + N;
   // window w is complete once the y2 sample behind its last symbol's second half (+ the interpolator's reach) is there
   auto ready = [&](long long w) {
     const double T = (double)((w + 1) * kRdsWin * kRdsSym + kRdsSym) / 19.0;
     return (long long)std::floor((T + kRdsDelay1) / kRdsD + kRdsDelay2) + 3 <= m1;
   };
   int nw = 0;
-  while (nw < rds_maxw && ready(rds_w + nw)) nw++;
+  while (nw < rds.maxw && ready(rds.w + nw)) nw++;
   if (nw == 0) { HIPCHK(hipGetLastError()); return FMR_OK; }
-  const unsigned long long seq = ++rds_seq;
-  if (seq > (unsigned long long)kRdsSlots) {      // the slot's previous call must have been drained
-    if (int rc = wait_mark(h_rds_mark, seq - kRdsSlots)) return rc;
-    rds_drain();
+  const unsigned long long seq = ++rds.seq;
+  if (seq > (unsigned long long)rds.kSlots) {      // the slot's previous call must have been drained
+    if (int rc = wait_mark(rds.h_mark.p, seq - rds.kSlots)) return rc;
+    rds.drain();
   }
-  char *slot = h_rds_slots + (size_t)(seq % kRdsSlots) * S * rds_slot_stride;
+  char *slot = rds.h_slots.p + (size_t)(seq % rds.kSlots) * S * rds.slot_stride;
   timed_on(st, "rds_sym", [&] {
-    hipLaunchKernelGGL(k_rds_est, dim3(nw, S), dim3(64), 0, st, d_rds_y2.p, rds_R, rds_w, d_rds_est.p, rds_maxw);
-    hipLaunchKernelGGL(k_rds_scan, dim3((S + 63) / 64), dim3(64), 0, st, d_rds_est.p, nw, rds_w, rds_maxw, d_rds_state.p,
-                       d_rds_rec.p, slot, rds_slot_stride, S);
-    hipLaunchKernelGGL(k_rds_bits, dim3(nw, S), dim3(128), 0, st, d_rds_y2.p, rds_R, d_rds_rec.p, rds_maxw, slot,
-                       rds_slot_stride);
+    hipLaunchKernelGGL(k_rds_est, dim3(nw, S), dim3(64), 0, st, rds.d_y2.p, rds.R, rds.w, rds.d_est.p, rds.maxw);
+    hipLaunchKernelGGL(k_rds_scan, dim3((S + 63) / 64), dim3(64), 0, st, rds.d_est.p, nw, rds.w, rds.maxw, rds.d_state.p,
+                       rds.d_rec.p, slot, rds.slot_stride, S);
+    hipLaunchKernelGGL(k_rds_bits, dim3(nw, S), dim3(128), 0, st, rds.d_y2.p, rds.R, rds.d_rec.p, rds.maxw, slot,
+                       rds.slot_stride);
   });
-  hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, st, h_rds_mark, seq);
-  rds_w += nw;
-  rds_tap_seq = seq;
+  hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, st, rds.h_mark.p, seq);
+  rds.w += nw;
+  rds.tap_seq = seq;
   HIPCHK(hipGetLastError());
   return FMR_OK;
 }
 
 // ---- modulation monitor and RF monitor (kernels_monitor.hpp, kernels_rfmon.hpp) ----
-int SegMonitor::init(int S, size_t max_if, unsigned interval_samples, int hist_bins, int max_records) {
+int SegMonitor::init(int S, size_t max_if, unsigned interval_samples, int hist_bins, double range, int max_records) {
   static_assert(sizeof(MonRec) == sizeof(fmr_monitor_record), "MonRec is fmr_monitor_record");
   static_assert(sizeof(MonRec) == sizeof(fmr_rf_monitor_record), "MonRec is fmr_rf_monitor_record");
   static_assert(offsetof(fmr_monitor_record, segments) == offsetof(MonRec, segments) &&
@@ -2938,6 +2956,7 @@ int SegMonitor::init(int S, size_t max_if, unsigned interval_samples, int hist_b
   static_assert(kRfmBins == FMR_RF_HIST_BINS && kMonPsd == FMR_RF_PSD_BINS, "the header's sizes");
   interval = interval_samples;
   bins = hist_bins;
+  hist_range = range;
   spr = (int)(interval / kMonH);
   // a full call in about 512 runs per stream: sub-blocks of 4 .. 32 segments (a run is a workgroup's serial work, and the
   // partition only moves the fp64 rounding of the sums)
@@ -3028,24 +3047,24 @@ int fmr_chain::seg_stage(SegMonitor &m, const void *from, long long stride, int 
 }
 
 // ---- audio monitor (kernels_loudness.hpp) ----
-int fmr_chain::ld_init(const fmr_loudness_config &m) {
+int LoudnessStage::init(int S, size_t max_au, const fmr_loudness_config &m) {
   static_assert(sizeof(LdRec) == sizeof(fmr_loudness_record), "LdRec is fmr_loudness_record");
-  ld_cfg = m;
+  cfg = m;
   const int Q = (int)m.step_samples;
-  ld_cps = (Q + kLdC - 1) / kLdC;
+  cps = (Q + kLdC - 1) / kLdC;
   // a call's runs: its whole chunks, one more per sub-block it touches, one at either end
-  ld_rmax = (int)std::min<size_t>(kLdMaxRuns, max_au / kLdC + max_au / Q + 4);
+  rmax = (int)std::min<size_t>(kLdMaxRuns, max_au / kLdC + max_au / Q + 4);
   // BS.1770-4 K-weighting at 48 kHz: the shelf, then the high-pass
-  ld_coef.b0[0] = 1.53512485958697; ld_coef.b1[0] = -2.69169618940638; ld_coef.b2[0] = 1.19839281085285;
-  ld_coef.a1[0] = -1.69065929318241; ld_coef.a2[0] = 0.73248077421585;
-  ld_coef.b0[1] = 1.0; ld_coef.b1[1] = -2.0; ld_coef.b2[1] = 1.0;
-  ld_coef.a1[1] = -1.99004745483398; ld_coef.a2[1] = 0.99007225036621;
+  coef.b0[0] = 1.53512485958697; coef.b1[0] = -2.69169618940638; coef.b2[0] = 1.19839281085285;
+  coef.a1[0] = -1.69065929318241; coef.a2[0] = 0.73248077421585;
+  coef.b0[1] = 1.0; coef.b1[1] = -2.0; coef.b2[1] = 1.0;
+  coef.a1[1] = -1.99004745483398; coef.a2[1] = 0.99007225036621;
   // A: one step of the recurrence itself on the unit states (column j = the state after e_j), then A^(2^b) by squaring
   std::vector<double> pw((size_t)kLdPow * 16);
   for (int j = 0; j < 4; j++) {
     double z[4] = {0.0, 0.0, 0.0, 0.0};
     z[j] = 1.0;
-    (void)ld_step(ld_coef, 0.0, z);
+    (void)ld_step(coef, 0.0, z);
     for (int i = 0; i < 4; i++) pw[(size_t)i * 4 + j] = z[i];
   }
   for (int b = 1; b < kLdPow; b++) {
@@ -3065,122 +3084,124 @@ int fmr_chain::ld_init(const fmr_loudness_config &m) {
       const double u = M_PI * t;
       taps[(size_t)(p - 1) * kLdTaps + (k + 5)] = (std::sin(u) / u) * (0.5 + 0.5 * std::cos(u / 6.0));
     }
-  const size_t L = (size_t)m.max_records, rows = (size_t)S * 2 * ld_rmax;
+  const size_t L = (size_t)m.max_records, rows = (size_t)S * 2 * rmax;
   int rc;
-  if ((rc = upload(d_ld_pw, pw.data(), pw.size()))) return rc;
-  if ((rc = upload(d_ld_taps, taps.data(), taps.size()))) return rc;
-  if ((rc = d_ld_G.alloc(rows * 4))) return rc;
-  if ((rc = d_ld_start.alloc(rows * 4))) return rc;
-  if ((rc = d_ld_pkw.alloc(rows))) return rc;
-  if ((rc = d_ld_part.alloc((size_t)S * ld_rmax))) return rc;
-  if ((rc = d_ld_state.alloc((size_t)S * 2 * 4))) return rc;
-  if ((rc = d_ld_hist.alloc((size_t)S * 2 * kLdHist))) return rc;
-  if ((rc = d_ld_open.alloc(2 * (size_t)S))) return rc;
-  if ((rc = d_ld_ring.alloc((size_t)S * L))) return rc;
-  ld_cur.reset(S, m.max_records);
-  ld_n = 0;
-  ld_par = 0;
-  ld = true;
+  if ((rc = upload(d_pw, pw.data(), pw.size()))) return rc;
+  if ((rc = upload(d_taps, taps.data(), taps.size()))) return rc;
+  if ((rc = d_G.alloc(rows * 4))) return rc;
+  if ((rc = d_start.alloc(rows * 4))) return rc;
+  if ((rc = d_pkw.alloc(rows))) return rc;
+  if ((rc = d_part.alloc((size_t)S * rmax))) return rc;
+  if ((rc = d_state.alloc((size_t)S * 2 * 4))) return rc;
+  if ((rc = d_hist.alloc((size_t)S * 2 * kLdHist))) return rc;
+  if ((rc = d_open.alloc(2 * (size_t)S))) return rc;
+  if ((rc = d_ring.alloc((size_t)S * L))) return rc;
+  cur.reset(S, m.max_records);
+  n = 0;
+  par = 0;
+  on = true;
   return FMR_OK;
 }
 
 // one call's audio (N samples per channel and stream, where the mux wrote them) through the audio monitor, on stream st,
-// in launches of at most ld_rmax runs per stream
+// in launches of at most ld.rmax runs per stream
 int fmr_chain::ld_stage(const double *d_aud, long long astride, long long N, hipStream_t st) {
   if (N <= 0) return FMR_OK;
   LdArgs a{};
-  a.n0 = ld_n; a.Q = (int)ld_cfg.step_samples; a.cps = ld_cps; a.ch = stereo ? 2 : 1;
-  const long long n1 = ld_n + N;
+  a.n0 = ld.n; a.Q = (int)ld.cfg.step_samples; a.cps = ld.cps; a.ch = stereo ? 2 : 1;
+  const long long n1 = ld.n + N;
   auto chunk_of = [&](long long p) { const long long q = p / a.Q; return q * a.cps + (p - q * a.Q) / kLdC; };
-  long long p = ld_n;
+  long long p = ld.n;
   while (p < n1) {
     a.a0 = p; a.g0 = chunk_of(p);
     long long lo, hi;
-    ld_chunk(a.Q, a.cps, a.g0 + ld_rmax - 1, lo, hi);
+    ld_chunk(a.Q, a.cps, a.g0 + ld.rmax - 1, lo, hi);
     a.a1 = std::min(n1, hi);
     const int runs = (int)(chunk_of(a.a1 - 1) - a.g0 + 1);
     const int nrec = (int)((a.a1 - 1) / a.Q - a.a0 / a.Q + 1);
     const int lanes = runs * a.ch;
     timed_on(st, "ld_nodes", [&] {
-      hipLaunchKernelGGL(k_ld_pass1, dim3((lanes + 63) / 64, S), dim3(64), 0, st, d_aud, astride, a, ld_coef, runs, ld_rmax,
-                         d_ld_G.p);
-      hipLaunchKernelGGL(k_ld_nodes, dim3(S * a.ch), dim3(64), 0, st, d_ld_G.p, d_ld_start.p, a, runs, ld_rmax, d_ld_pw.p,
-                         d_ld_state.p);
+      hipLaunchKernelGGL(k_ld_pass1, dim3((lanes + 63) / 64, S), dim3(64), 0, st, d_aud, astride, a, ld.coef, runs, ld.rmax,
+                         ld.d_G.p);
+      hipLaunchKernelGGL(k_ld_nodes, dim3(S * a.ch), dim3(64), 0, st, ld.d_G.p, ld.d_start.p, a, runs, ld.rmax, ld.d_pw.p,
+                         ld.d_state.p);
     });
     timed_on(st, "ld_pass2", [&] {
-      hipLaunchKernelGGL(k_ld_pass2, dim3((lanes + 63) / 64, S), dim3(64), 0, st, d_aud, astride, a, ld_coef, runs, ld_rmax,
-                         d_ld_start.p, d_ld_pkw.p, d_ld_state.p);
+      hipLaunchKernelGGL(k_ld_pass2, dim3((lanes + 63) / 64, S), dim3(64), 0, st, d_aud, astride, a, ld.coef, runs, ld.rmax,
+                         ld.d_start.p, ld.d_pkw.p, ld.d_state.p);
     });
     timed_on(st, "ld_block", [&] {
-      hipLaunchKernelGGL(k_ld_block, dim3(runs, S), dim3(kLdC), 0, st, d_aud, astride, a, ld_rmax, d_ld_taps.p, d_ld_hist.p,
-                         d_ld_part.p);
+      hipLaunchKernelGGL(k_ld_block, dim3(runs, S), dim3(kLdC), 0, st, d_aud, astride, a, ld.rmax, ld.d_taps.p, ld.d_hist.p,
+                         ld.d_part.p);
     });
     timed_on(st, "ld_reduce", [&] {
-      hipLaunchKernelGGL(k_ld_reduce, dim3(nrec, S), dim3(64), 0, st, d_ld_pkw.p, d_ld_part.p, runs, ld_rmax, a,
-                         (int)ld_cfg.max_records, ld_par, d_ld_open.p, d_ld_ring.p, d_aud, astride, d_ld_hist.p,
+      hipLaunchKernelGGL(k_ld_reduce, dim3(nrec, S), dim3(64), 0, st, ld.d_pkw.p, ld.d_part.p, runs, ld.rmax, a,
+                         (int)ld.cfg.max_records, ld.par, ld.d_open.p, ld.d_ring.p, d_aud, astride, ld.d_hist.p,
                          (int)(a.a1 >= n1));
     });
-    ld_par ^= 1;
+    ld.par ^= 1;
     p = a.a1;
   }
-  ld_n = n1;
+  ld.n = n1;
   HIPCHK(hipGetLastError());
   return FMR_OK;
 }
 
 // ---- output stage (kernels_output.hpp) ----
-int fmr_chain::out_init(const fmr_output_config &m) {
+int OutputStage::init(int S, bool chain_stereo, int max_blocks, int slots, const fmr_output_config &m) {
   static_assert(sizeof(OutRec) == sizeof(fmr_output_block), "OutRec is fmr_output_block");
-  out_cfg = m;
+  cfg = m;
+  stereo = chain_stereo;
+  ifrms_slot_len = (size_t)S * max_blocks;
   int rc;
-  if ((rc = d_out_ifrms.alloc((size_t)(pipelined ? kPipe : 1) * S * max_blocks))) return rc;
-  if ((rc = d_out_part.alloc((size_t)S * max_blocks))) return rc;
-  if ((rc = d_out_state.alloc((size_t)S))) return rc;
-  if ((rc = d_out_rec.alloc((size_t)S * m.max_blocks))) return rc;
-  if ((rc = d_out_pcm.alloc((size_t)S * m.max_frames * out_frame_bytes()))) return rc;
-  out_fcur.reset(S, 1); out_fcur.L = m.max_frames;
-  out_bcur.reset(S, (int)m.max_blocks);
-  out_block = out_recs = out_frames = 0;
-  out = true;
+  if ((rc = d_ifrms.alloc((size_t)slots * ifrms_slot_len))) return rc;
+  if ((rc = d_part.alloc((size_t)S * max_blocks))) return rc;
+  if ((rc = d_state.alloc((size_t)S))) return rc;
+  if ((rc = d_rec.alloc((size_t)S * m.max_blocks))) return rc;
+  if ((rc = d_pcm.alloc((size_t)S * m.max_frames * frame_bytes()))) return rc;
+  fcur.reset(S, 1); fcur.L = m.max_frames;
+  bcur.reset(S, (int)m.max_blocks);
+  block = recs = frames = 0;
+  on = true;
   return FMR_OK;
 }
 
 // the rate converter of an enabled stage, before the first block: the prototype, the two staging rows, the totals
-int fmr_chain::out_rate_init(int rate, bool mono) {
+int OutRate::init(int rate, bool to_mono, int S, bool stereo, size_t max_au) {
   std::vector<double> h;
   OutRateGeom gm{};
   if (!design_output_rate(rate, gm.L, gm.M, gm.T, &h)) { set_err("fmr_set_output_rate: rate %d has no design", rate); return FMR_ERR_BAD_ARG; }
-  out_hz = rate; out_mono = mono; out_conv = true;
-  const int och = out_channels();
+  hz = rate; mono = to_mono; on = true;
+  const int och = stereo && !mono ? 2 : 1;      // (OutputStage::channels with this converter)
   gm.span = (int)(((long long)(kOutThreads - 1) * gm.M) / gm.L) + 1 + gm.T;
   gm.zstride = ((long long)(gm.T - 1) + (long long)max_au) * och;
   gm.zrow = (long long)S * gm.zstride;
-  out_geom = gm;
+  geom = gm;
   int rc;
-  if ((rc = d_out_taps.alloc(h.size()))) return rc;
-  HIPCHK(hipMemcpy(d_out_taps.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-  if ((rc = d_out_z.alloc((size_t)2 * gm.zrow))) return rc;      // (zeroed: z[j] = +0.0 for j < 0)
-  if ((rc = d_out_tot.alloc((size_t)2 * S))) return rc;
-  out_oframes = 0; out_zpar = 0;
+  if ((rc = d_taps.alloc(h.size()))) return rc;
+  HIPCHK(hipMemcpy(d_taps.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  if ((rc = d_z.alloc((size_t)2 * gm.zrow))) return rc;      // (zeroed: z[j] = +0.0 for j < 0)
+  if ((rc = d_tot.alloc((size_t)2 * S))) return rc;
+  oframes = 0; zpar = 0;
   return FMR_OK;
 }
 
 // the positions of one call (block0: absolute index of its first block), taken when it is issued; advances the counters
-OutArgs fmr_chain::out_begin(unsigned long long block0, const int *if_len, int nb, long long N_au) {
+OutArgs OutputStage::begin(unsigned long long block0, const int *if_len, int nb, long long N_au) {
   OutArgs a{};
-  a.block0 = block0; a.frame0 = out_frames; a.rec0 = out_recs;
+  a.block0 = block0; a.frame0 = frames; a.rec0 = recs;
   a.n_frames = (unsigned long long)N_au;
   for (int b = 0; b < nb; b++) a.n_recs += if_len[b] != 0;
-  a.squelch = out_cfg.squelch_level; a.gain = out_cfg.gain;
-  a.max_frames = out_cfg.max_frames; a.max_blocks = out_cfg.max_blocks;
-  out_frames += a.n_frames; out_recs += a.n_recs;
-  if (out_conv) {      // ring frames: ceil(F L / M) after F decoder frames
-    const unsigned long long L = (unsigned long long)out_geom.L, M = (unsigned long long)out_geom.M;
-    a.out0 = out_oframes;
-    out_oframes = (out_frames * L + M - 1) / M;
-    a.n_out = out_oframes - a.out0;
-    a.zpar = out_zpar;
-    if (a.n_frames > 0) out_zpar ^= 1;      // (a call without audio launches nothing: the history stays where it is)
+  a.squelch = cfg.squelch_level; a.gain = cfg.gain;
+  a.max_frames = cfg.max_frames; a.max_blocks = cfg.max_blocks;
+  frames += a.n_frames; recs += a.n_recs;
+  if (rate.on) {      // ring frames: ceil(F L / M) after F decoder frames
+    const unsigned long long L = (unsigned long long)rate.geom.L, M = (unsigned long long)rate.geom.M;
+    a.out0 = rate.oframes;
+    rate.oframes = (frames * L + M - 1) / M;
+    a.n_out = rate.oframes - a.out0;
+    a.zpar = rate.zpar;
+    if (a.n_frames > 0) rate.zpar ^= 1;      // (a call without audio launches nothing: the history stays where it is)
   }
   return a;
 }
@@ -3195,21 +3216,21 @@ int fmr_chain::out_stage(const double *d_aud, long long astride, const BlockTab 
     timed_on(st, "out_pcm", [&] {
       auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(bt.nb, S), dim3(kOutThreads), 0, st, d_aud, astride, bt, if_rms_blk, a,
-                           out_conv ? (void *)nullptr : (void *)d_out_pcm.p, d_out_part.p);
+                           out.rate.on ? (void *)nullptr : (void *)out.d_pcm.p, out.d_part.p);
       };
-      if (out_cfg.format == FMR_PCM_F32) { if (ch == 2) go(k_out_pcm<1, 2>); else go(k_out_pcm<1, 1>); }
+      if (out.cfg.format == FMR_PCM_F32) { if (ch == 2) go(k_out_pcm<1, 2>); else go(k_out_pcm<1, 1>); }
       else { if (ch == 2) go(k_out_pcm<0, 2>); else go(k_out_pcm<0, 1>); }
     });
   timed_on(st, "out_blocks", [&] {
-    hipLaunchKernelGGL(k_out_blocks, dim3(S), dim3(64), 0, st, bt, if_rms_blk, (const OutPart *)d_out_part.p, a, ch, d_out_state.p,
-                       d_out_rec.p);
+    hipLaunchKernelGGL(k_out_blocks, dim3(S), dim3(64), 0, st, bt, if_rms_blk, (const OutPart *)out.d_part.p, a, ch, out.d_state.p,
+                       out.d_rec.p);
   });
-  if (out_conv && a.n_frames > 0) {
-    const OutRateGeom &gm = out_geom;
-    const int och = out_channels();
+  if (out.rate.on && a.n_frames > 0) {
+    const OutRateGeom &gm = out.rate.geom;
+    const int och = out.channels();
     timed_on(st, "out_z", [&] {
       auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(bt.nb, S), dim3(kOutThreads), 0, st, d_aud, astride, bt, if_rms_blk, a, gm, d_out_z.p);
+        hipLaunchKernelGGL(kern, dim3(bt.nb, S), dim3(kOutThreads), 0, st, d_aud, astride, bt, if_rms_blk, a, gm, out.rate.d_z.p);
       };
       if (ch == 1) go(k_out_z<1, 1>); else if (och == 2) go(k_out_z<2, 2>); else go(k_out_z<2, 1>);
     });
@@ -3218,15 +3239,15 @@ int fmr_chain::out_stage(const double *d_aud, long long astride, const BlockTab 
         const size_t lds = (size_t)gm.span * och * sizeof(double) + 2 * (kOutThreads / 64) * sizeof(unsigned);
         auto go = [&](auto kern) {
           hipLaunchKernelGGL(kern, dim3((unsigned)((a.n_out + kOutThreads - 1) / kOutThreads), S), dim3(kOutThreads), lds, st,
-                             (const double *)d_out_z.p, (const double *)d_out_taps.p, gm, a, (void *)d_out_pcm.p, d_out_tot.p);
+                             (const double *)out.rate.d_z.p, (const double *)out.rate.d_taps.p, gm, a, (void *)out.d_pcm.p, out.rate.d_tot.p);
         };
-        if (out_cfg.format == FMR_PCM_F32) { if (och == 2) go(k_out_rate<1, 2>); else go(k_out_rate<1, 1>); }
+        if (out.cfg.format == FMR_PCM_F32) { if (och == 2) go(k_out_rate<1, 2>); else go(k_out_rate<1, 1>); }
         else { if (och == 2) go(k_out_rate<0, 2>); else go(k_out_rate<0, 1>); }
       });
     const int hist = (gm.T - 1) * och;
     if (hist > 0)
       timed_on(st, "out_hist", [&] {
-        hipLaunchKernelGGL(k_out_hist, dim3((hist + kOutThreads - 1) / kOutThreads, S), dim3(kOutThreads), 0, st, d_out_z.p, gm,
+        hipLaunchKernelGGL(k_out_hist, dim3((hist + kOutThreads - 1) / kOutThreads, S), dim3(kOutThreads), 0, st, out.rate.d_z.p, gm,
                            a.zpar, (long long)a.n_frames * och, hist);
       });
   }
@@ -3235,27 +3256,27 @@ int fmr_chain::out_stage(const double *d_aud, long long astride, const BlockTab 
 }
 
 // the filled slots, in call order, through the host decoders (never blocks)
-void fmr_chain::rds_drain() {
-  while (rds_drained < rds_seq && __atomic_load_n(h_rds_mark, __ATOMIC_ACQUIRE) > rds_drained) {
-    const unsigned long long seq = ++rds_drained;
-    const char *slot = h_rds_slots + (size_t)(seq % kRdsSlots) * S * rds_slot_stride;
+void RdsStage::drain() {
+  while (drained < seq && __atomic_load_n(h_mark.p, __ATOMIC_ACQUIRE) > drained) {
+    const unsigned long long q = ++drained;
+    const char *slot = h_slots.p + (size_t)(q % kSlots) * S * slot_stride;
     for (int s = 0; s < S; s++) {
-      const char *sl = slot + (size_t)s * rds_slot_stride;
+      const char *sl = slot + (size_t)s * slot_stride;
       RdsSlotHdr h;
       memcpy(&h, sl, sizeof h);
       const RdsRec *rec = reinterpret_cast<const RdsRec *>(sl + sizeof(RdsSlotHdr));
-      const unsigned char *bits = reinterpret_cast<const unsigned char *>(sl + rds_slot_bits_off(rds_maxw));
-      const float *rho = reinterpret_cast<const float *>(sl + rds_slot_rho_off(rds_maxw));
-      for (int w = 0; w < h.nw && w < rds_maxw; w++) {
+      const unsigned char *bits = reinterpret_cast<const unsigned char *>(sl + rds_slot_bits_off(maxw));
+      const float *rho = reinterpret_cast<const float *>(sl + rds_slot_rho_off(maxw));
+      for (int w = 0; w < h.nw && w < maxw; w++) {
         const RdsRec r = rec[w];
         const float *rw = rho + (size_t)w * (kRdsMaxSym + 1);
-        if (r.count > 0) rds_dec[s].carried(rw[0]);
+        if (r.count > 0) dec[s].carried(rw[0]);
         for (int t = 0; t < r.count && t < kRdsMaxSym; t++) {
           const long long pos = (r.k_first + t) * kRdsSym + r.tau;       // [U]
-          rds_dec[s].push(bits[(size_t)w * kRdsMaxSym + t], pos > 0 ? (uint64_t)((pos + 9) / 19) : 0, rw[t + 1]);
+          dec[s].push(bits[(size_t)w * kRdsMaxSym + t], pos > 0 ? (uint64_t)((pos + 9) / 19) : 0, rw[t + 1]);
         }
       }
-      rds_hdr[s] = h;
+      hdr[s] = h;
     }
   }
 }
@@ -3276,7 +3297,7 @@ int fmr_chain::flush_tail(hipEvent_t gate) {
   tail_pending = false;
   const int rc = enqueue_tail(gate);
   if (rc != FMR_OK)      // the slot of the ring must still be released, or the calls that reuse it wait for a mark that never comes
-    hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, tail, &h_marks[1], tail_job.seq);
+    hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, tail, &h_marks.p[1], tail_job.seq);
   return rc != FMR_OK ? rc : rc_walk;     // (a walk that could not be enqueued leaves that call's lock flags and PPS events stale: an error of this call)
 }
 int fmr_chain::enqueue_tail(hipEvent_t gate) {
@@ -3299,7 +3320,7 @@ int fmr_chain::enqueue_tail(hipEvent_t gate) {
   if (t.ht.n) {
     timed_on(tail, "shift_halo", [&] { hipLaunchKernelGGL(k_shift_halo<256>, dim3(t.ht.n, S), dim3(256), 0, tail, t.ht); });
   }
-  hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, tail, &h_marks[1], t.seq);
+  hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, tail, &h_marks.p[1], t.seq);
   HIPCHK(hipGetLastError());
   return FMR_OK;
 }
@@ -3321,7 +3342,7 @@ int fmr_chain::run_nbfm(CallCtx &k) {
   });
   timed("stats", [&] {
     hipLaunchKernelGGL(k_stats, dim3(S), dim3(FMR_STATS_THREADS), 0, stream, bt, d_if_rms_blk.p, d_bb_mean_blk.p,
-                       d_bb_rms_blk.p, d_state.p, S, 1, (const FusedPart *)nullptr, 0, 0, out_ifrms_slot(0));
+                       d_bb_rms_blk.p, d_state.p, S, 1, (const FusedPart *)nullptr, 0, 0, out.ifrms_slot(0));
   });
   timed("nbfm_audio", [&] {
     hipLaunchKernelGGL((k_pilotcut2<320, 1280>), dim3(nb, S, 1), dim3(320), 0, stream, d_base.p, (double *)nullptr,
@@ -3331,7 +3352,7 @@ int fmr_chain::run_nbfm(CallCtx &k) {
   add_halo(ifbuf, if_stride, H_if, N_if);
   add_halo(d_base.p, base_stride, H_b, N_if);
   if (audio_len) for (int b = 0; b < nb; b++) audio_len[b] = (uint32_t)t_au_len[b];
-  if (out) if (int rc = out_stage(d_aud, (long long)astride, bt, out_ifrms_slot(0), out_begin(k.out_block0, k.t_if_len, nb, k.N_au), stream)) return rc;
+  if (out.on) if (int rc = out_stage(d_aud, (long long)astride, bt, out.ifrms_slot(0), out.begin(k.out_block0, k.t_if_len, nb, k.N_au), stream)) return rc;
   return FMR_OK;
 }
 
@@ -3348,7 +3369,7 @@ int fmr_chain::run_am(CallCtx &k) {
   });
   timed("stats", [&] {
     hipLaunchKernelGGL(k_stats, dim3(S), dim3(FMR_STATS_THREADS), 0, stream, bt, d_if_rms_blk.p, d_bb_mean_blk.p,
-                       d_bb_rms_blk.p, d_state.p, S, 0, (const FusedPart *)nullptr, 0, 0, out_ifrms_slot(0));
+                       d_bb_rms_blk.p, d_state.p, S, 0, (const FusedPart *)nullptr, 0, 0, out.ifrms_slot(0));
   });
   timed("am_tail", [&] {
     const bool par_tail = !serial_mode;
@@ -3380,7 +3401,7 @@ int fmr_chain::run_am(CallCtx &k) {
   });
   add_halo(ifbuf, if_stride, H_if, N_if);
   if (audio_len) for (int b = 0; b < nb; b++) audio_len[b] = (uint32_t)t_au_len[b];
-  if (out) if (int rc = out_stage(d_aud, (long long)astride, bt, out_ifrms_slot(0), out_begin(k.out_block0, k.t_if_len, nb, k.N_au), stream)) return rc;
+  if (out.on) if (int rc = out_stage(d_aud, (long long)astride, bt, out.ifrms_slot(0), out.begin(k.out_block0, k.t_if_len, nb, k.N_au), stream)) return rc;
   return FMR_OK;
 }
 
@@ -3392,7 +3413,7 @@ struct fmr_spectrum {
   int N = 0, H = 0, logn = 0, rows = 0, fmt = 0;
   int rmax = 1;                          // runs per row and call (capacity of the partials)
   int n_cu = 256;
-  hipStream_t stream = nullptr;
+  Stream stream;
   DevBuf<float> d_win, d_pmax, d_max;
   DevBuf<float2> d_tw, d_ring;
   DevBuf<double> d_psum, d_sum;
@@ -3413,14 +3434,7 @@ struct fmr_spectrum {
   int init();
   int run(const void *d_in, size_t stride, size_t n);
   int run_waterfall(const void *d_in, size_t stride, long long tb, long long ta, long long j_hi);
-  ~fmr_spectrum() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    d_plsub.release(); d_wopen.release(); d_wline.release(); d_wring.release(); d_plcnt.release(); d_wopen_cnt.release();
-    d_wline_cnt.release(); d_wring_cnt.release();
-    d_win.release(); d_pmax.release(); d_max.release(); d_tw.release(); d_ring.release(); d_psum.release(); d_sum.release();
-    d_pcnt.release(); d_cnt.release(); d_stage.release();
-    if (stream) (void)hipStreamDestroy(stream);
-  }
+  ~fmr_spectrum() { if (stream) (void)hipStreamSynchronize(stream); }      // (the stream idle, then the members: as ~fmr_chain)
 };
 
 namespace {
@@ -3534,7 +3548,7 @@ int fmr_spectrum::init() {
   HIPCHK(hipSetDevice(cfg.device));
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, cfg.device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-  HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  if (int rc = stream.create()) return rc;
   const bool wfon = wf.segments_per_line > 0;
   if (int rc = kSpecAttr[logn - 8][fmt](wfon)) return rc;
   // window and twiddles: double, rounded once to fp32
@@ -3751,9 +3765,8 @@ static int create_chain(const fmr_config *cfg, fmr_chain **out, bool channelizer
     return FMR_ERR_BAD_ARG;
   }
   fmr_chain *c = new fmr_chain();
-  c->rds = rds;
   int rc = c->init(cfg, channelizer);
-  if (rc == FMR_OK && rds) rc = c->rds_init();
+  if (rc == FMR_OK && rds) rc = build_stage(c->rds, c->S, c->max_if);
   if (rc != FMR_OK) { delete c; return rc; }
   if (c->sync_all() != FMR_OK) { delete c; return FMR_ERR_HIP; }
   *out = c;
@@ -4108,6 +4121,8 @@ int fmr_get_multipath_coefficients(fmr_chain *c, int stream, float *coeff, int c
   return c->mpf_N;
 }
 
+long long fmr_debug_live_resources(void) { return g_live.load(); }
+
 long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t cap_bytes) {
   if (!c || stream < 0 || stream >= c->S) return FMR_ERR_BAD_ARG;
   HIPCHK(hipSetDevice(c->cfg.device));
@@ -4116,19 +4131,19 @@ long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t 
   const void *src = nullptr;
   size_t esz = 0;
   if (which == 5 && !c->d_fe_stamps.p) {      // the symbol reliabilities of the most recent call (chains with RDS)
-    if (!c->rds) { set_err("fmr_debug_read: tap 5 (RDS symbol reliabilities) needs a chain made by fmr_create_rds"); return FMR_ERR_BAD_ARG; }
-    c->rds_drain();
-    if (!c->rds_tap_seq) return 0;
-    const char *sl = c->h_rds_slots + ((size_t)(c->rds_tap_seq % fmr_chain::kRdsSlots) * c->S + stream) * c->rds_slot_stride;
+    if (!c->rds.on) { set_err("fmr_debug_read: tap 5 (RDS symbol reliabilities) needs a chain made by fmr_create_rds"); return FMR_ERR_BAD_ARG; }
+    c->rds.drain();
+    if (!c->rds.tap_seq) return 0;
+    const char *sl = c->rds.h_slots.p + ((size_t)(c->rds.tap_seq % RdsStage::kSlots) * c->S + stream) * c->rds.slot_stride;
     RdsSlotHdr h;
     memcpy(&h, sl, sizeof h);
     const RdsRec *rec = reinterpret_cast<const RdsRec *>(sl + sizeof(RdsSlotHdr));
-    const float *rho = reinterpret_cast<const float *>(sl + rds_slot_rho_off(c->rds_maxw));
+    const float *rho = reinterpret_cast<const float *>(sl + rds_slot_rho_off(c->rds.maxw));
     n = 0;
-    for (int w = 0; w < h.nw && w < c->rds_maxw; w++) n += std::min(std::max(rec[w].count, 0), kRdsMaxSym);
+    for (int w = 0; w < h.nw && w < c->rds.maxw; w++) n += std::min(std::max(rec[w].count, 0), kRdsMaxSym);
     if ((size_t)n * sizeof(float) > cap_bytes) return FMR_ERR_CAPACITY;
     float *o = reinterpret_cast<float *>(out);
-    for (int w = 0; w < h.nw && w < c->rds_maxw; w++)
+    for (int w = 0; w < h.nw && w < c->rds.maxw; w++)
       for (int t = 0; t < rec[w].count && t < kRdsMaxSym; t++) *o++ = rho[(size_t)w * (kRdsMaxSym + 1) + t + 1];
     return n;
   }
@@ -4172,39 +4187,38 @@ __global__ __launch_bounds__(256) void k_probe_read(const float *__restrict__ p0
   if (acc.x + acc.y + acc.z + acc.w == 1.2345678e-30f) *sink = acc.x;       // keeps the loads alive; never true in practice
 }
 
+namespace {
+// the probes run on `device` and leave the caller's current device as it was
+struct DeviceScope {
+  int prev = -1;
+  int enter(int device) { HIPCHK(hipGetDevice(&prev)); HIPCHK(hipSetDevice(device)); return FMR_OK; }
+  ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+}  // namespace
+
 int fmr_probe_read_bandwidth(int device, const void *d_buf, size_t bytes, int reps, double *gbytes_per_s) {
   if (!d_buf || !gbytes_per_s || bytes < (1u << 20) || reps < 1) return FMR_ERR_BAD_ARG;
   // everything this function takes is given back on every path out of it, the caller's current device included
-  struct Scope {
-    int prev_dev = -1;
-    float *sink = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Scope() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-      if (st) (void)hipStreamDestroy(st);
-      if (sink) (void)hipFree(sink);
-      if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
-    }
-  } sc;
-  HIPCHK(hipGetDevice(&sc.prev_dev));
-  HIPCHK(hipSetDevice(device));
+  DeviceScope dev;
+  DevBuf<float> sink;
+  Stream st;      // (the null stream would wait for every blocking stream)
+  Event ev_a, ev_b;
+  if (int rc = dev.enter(device)) return rc;
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, device));
   const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  HIPCHK(hipMalloc((void **)&sc.sink, sizeof(float)));
-  HIPCHK(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));      // (the null stream would wait for every blocking stream)
-  HIPCHK(hipEventCreate(&sc.a));
-  HIPCHK(hipEventCreate(&sc.b));
+  if (int rc = sink.alloc(1)) return rc;
+  if (int rc = st.create()) return rc;
+  if (int rc = ev_a.create()) return rc;
+  if (int rc = ev_b.create()) return rc;
   double best = 0.0;
   for (int r = 0; r < reps + 1; r++) {          // (the first pass warms up and is not counted)
-    HIPCHK(hipEventRecord(sc.a, sc.st));
-    hipLaunchKernelGGL(k_probe_read, dim3(n_cu * 8), dim3(256), 0, sc.st, (const float *)d_buf, bytes / 16, sc.sink);
-    HIPCHK(hipEventRecord(sc.b, sc.st));
-    HIPCHK(hipEventSynchronize(sc.b));
+    HIPCHK(hipEventRecord(ev_a, st));
+    hipLaunchKernelGGL(k_probe_read, dim3(n_cu * 8), dim3(256), 0, st, (const float *)d_buf, bytes / 16, sink.p);
+    HIPCHK(hipEventRecord(ev_b, st));
+    HIPCHK(hipEventSynchronize(ev_b));
     float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, sc.a, sc.b));
+    HIPCHK(hipEventElapsedTime(&ms, ev_a, ev_b));
     if (r > 0 && ms > 0.f) best = std::max(best, (double)(bytes / 16 * 16) / (ms * 1e-3) / 1e9);
   }
   *gbytes_per_s = best;
@@ -4213,24 +4227,16 @@ int fmr_probe_read_bandwidth(int device, const void *d_buf, size_t bytes, int re
 
 int fmr_probe_shader_clock(int device, double *mhz) {
   if (!mhz) return FMR_ERR_BAD_ARG;
-  struct Scope {
-    int prev_dev = -1;
-    unsigned long long *out = nullptr;
-    hipStream_t st = nullptr;
-    ~Scope() {
-      if (st) (void)hipStreamDestroy(st);
-      if (out) (void)hipHostFree(out);
-      if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
-    }
-  } sc;
-  HIPCHK(hipGetDevice(&sc.prev_dev));
-  HIPCHK(hipSetDevice(device));
-  HIPCHK(hipHostMalloc((void **)&sc.out, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-  HIPCHK(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
-  hipLaunchKernelGGL(k_probe_clock, dim3(1), dim3(64), 0, sc.st, sc.out, 2000);
+  DeviceScope dev;
+  HostBuf<unsigned long long> out;
+  Stream st;
+  if (int rc = dev.enter(device)) return rc;
+  if (int rc = out.alloc(2, hipHostMallocDefault)) return rc;
+  if (int rc = st.create()) return rc;
+  hipLaunchKernelGGL(k_probe_clock, dim3(1), dim3(64), 0, st, out.p, 2000);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(sc.st));
-  *mhz = sc.out[1] ? (double)sc.out[0] / ((double)sc.out[1] * 0.01) : 0.0;     // cycles per microsecond
+  HIPCHK(hipStreamSynchronize(st));
+  *mhz = out.p[1] ? (double)out.p[0] / ((double)out.p[1] * 0.01) : 0.0;     // cycles per microsecond
   return FMR_OK;
 }
 
@@ -4246,10 +4252,9 @@ int fmr_get_kernel_trace(fmr_chain *c, const char **names, int *streams, float *
     (void)hipEventElapsedTime(&t1, c->trace_base, c->trace[i].b);
     if (n < cap) { names[n] = c->trace[i].name; streams[n] = c->trace_stream[i]; start_ms[n] = t0; end_ms[n] = t1; }
     n++;
-    (void)hipEventDestroy(c->trace[i].a); (void)hipEventDestroy(c->trace[i].b);
   }
   c->trace.clear(); c->trace_stream.clear();
-  if (c->trace_base) { (void)hipEventDestroy(c->trace_base); c->trace_base = nullptr; }
+  c->trace_base.reset();
   return n;
 }
 
@@ -4257,23 +4262,14 @@ int fmr_get_kernel_times(fmr_chain *c, const char **names, float *ms, int cap) {
   if (!c) return FMR_ERR_BAD_ARG;
   if (int rc = c->sync_all()) return rc;
   int n = 0;
-  if (c->timing == 2 || c->timing == 4 || c->timing == 5) {   // dominant kernel only: one entry per call since the last query
-    for (auto &k : c->dom_times) {
-      float t = 0.f;
-      (void)hipEventElapsedTime(&t, k.a, k.b);
-      if (n < cap) { names[n] = k.name; ms[n] = t; }
-      n++;
-      (void)hipEventDestroy(k.a); (void)hipEventDestroy(k.b);
-    }
-    c->dom_times.clear();
-    return n;
-  }
-  for (auto &k : c->ktimes) {
+  const bool dom = c->timing == 2 || c->timing == 4 || c->timing == 5;   // dominant kernel only: one entry per call since the last query
+  for (auto &k : dom ? c->dom_times : c->ktimes) {
     float t = 0.f;
     (void)hipEventElapsedTime(&t, k.a, k.b);
     if (n < cap) { names[n] = k.name; ms[n] = t; }
     n++;
   }
+  if (dom) c->dom_times.clear();      // (the last call's times stay until the next call replaces them)
   return n;
 }
 
@@ -4293,12 +4289,12 @@ int fmr_create_rds(const fmr_config *cfg, size_t cfg_size, fmr_chain **out) {
 
 int fmr_get_rds_groups(fmr_chain *c, int stream, fmr_rds_group *groups, int cap) {
   if (!c || stream < 0 || stream >= c->S || cap < 0 || (cap > 0 && !groups)) return FMR_ERR_BAD_ARG;
-  if (!c->rds) { set_err("fmr_get_rds_groups: the chain was created without the RDS decoder (fmr_create_rds)"); return FMR_ERR_BAD_ARG; }
+  if (!c->rds.on) { set_err("fmr_get_rds_groups: the chain was created without the RDS decoder (fmr_create_rds)"); return FMR_ERR_BAD_ARG; }
   try {
     HIPCHK(hipSetDevice(c->cfg.device));
     if (int rc = c->sync_all()) return rc;
-    c->rds_drain();
-    fmr_rds::Decoder &d = c->rds_dec[stream];
+    c->rds.drain();
+    fmr_rds::Decoder &d = c->rds.dec[stream];
     if (cap == 0) return (int)d.queued();
     return (int)d.pop(groups, (size_t)cap);
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
@@ -4306,12 +4302,12 @@ int fmr_get_rds_groups(fmr_chain *c, int stream, fmr_rds_group *groups, int cap)
 
 int fmr_get_rds_status(fmr_chain *c, int stream, fmr_rds_status *st, size_t st_size) {
   if (!c || !st || stream < 0 || stream >= c->S) return FMR_ERR_BAD_ARG;
-  if (!c->rds) { set_err("fmr_get_rds_status: the chain was created without the RDS decoder (fmr_create_rds)"); return FMR_ERR_BAD_ARG; }
+  if (!c->rds.on) { set_err("fmr_get_rds_status: the chain was created without the RDS decoder (fmr_create_rds)"); return FMR_ERR_BAD_ARG; }
   HIPCHK(hipSetDevice(c->cfg.device));
   if (int rc = c->sync_all()) return rc;
-  c->rds_drain();
-  const fmr_rds::Decoder &d = c->rds_dec[stream];
-  const RdsSlotHdr &h = c->rds_hdr[stream];
+  c->rds.drain();
+  const fmr_rds::Decoder &d = c->rds.dec[stream];
+  const RdsSlotHdr &h = c->rds.hdr[stream];
   fmr_rds_status full{};
   full.synced = d.synced();
   full.blocks_ok = d.blocks_ok();
@@ -4319,7 +4315,7 @@ int fmr_get_rds_status(fmr_chain *c, int stream, fmr_rds_status *st, size_t st_s
   full.blocks_corrected = d.blocks_corrected();
   full.groups_decoded = d.groups_decoded();
   full.groups_dropped = d.groups_dropped();
-  full.injection = h.level > 0.f ? std::sqrt((double)h.level) / c->rds_gain : 0.0;
+  full.injection = h.level > 0.f ? std::sqrt((double)h.level) / c->rds.gain : 0.0;
   full.timing = h.timing_frac;
   full.carrier_phase = h.theta;
   full.carrier_offset_hz = h.freq_hz;
@@ -4353,12 +4349,12 @@ int fmr_set_rds_correction(fmr_chain *c, const fmr_rds_fec *fec, size_t fec_size
     return FMR_ERR_BAD_ARG;
   }
   if (!c) { set_err("fmr_set_rds_correction: chain is null"); return FMR_ERR_BAD_ARG; }
-  if (!c->rds) { set_err("fmr_set_rds_correction: the chain was created without the RDS decoder (fmr_create_rds)"); return FMR_ERR_BAD_ARG; }
+  if (!c->rds.on) { set_err("fmr_set_rds_correction: the chain was created without the RDS decoder (fmr_create_rds)"); return FMR_ERR_BAD_ARG; }
   try {
     HIPCHK(hipSetDevice(c->cfg.device));
     if (int rc = c->sync_all()) return rc;
-    c->rds_drain();
-    for (fmr_rds::Decoder &d : c->rds_dec) d.set_correction(k);
+    c->rds.drain();
+    for (fmr_rds::Decoder &d : c->rds.dec) d.set_correction(k);
     return FMR_OK;
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
@@ -4401,8 +4397,7 @@ int fmr_enable_monitor(fmr_chain *c, const fmr_monitor_config *cfg, size_t cfg_s
   }
   try {
     HIPCHK(hipSetDevice(c->cfg.device));
-    c->mon_cfg = m;
-    return c->mon.init(c->S, c->max_if, m.interval_samples, m.hist_bins, m.max_records);
+    return build_stage(c->mon, c->S, c->max_if, m.interval_samples, m.hist_bins, m.hist_range, m.max_records);
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
@@ -4416,15 +4411,15 @@ int fmr_monitor_read(fmr_chain *c, int stream, fmr_monitor_record *recs, uint32_
     if (n >= 0 && info) {
       fmr_monitor_info full{};
       full.struct_size = (unsigned)sizeof full;
-      full.hist_bins = c->mon_cfg.hist_bins;
+      full.hist_bins = c->mon.bins;
       full.psd_bins = kMonPsd;
       full.records_complete = c->mon.done();
       full.records_dropped = c->mon.cur.dropped[stream];
       full.first_unread = c->mon.cur.read[stream];
       full.records_ready = c->mon.done() - c->mon.cur.read[stream];
-      full.interval_samples = c->mon_cfg.interval_samples;
-      full.max_records = c->mon_cfg.max_records;
-      full.hist_range = c->mon_cfg.hist_range;
+      full.interval_samples = c->mon.interval;
+      full.max_records = (int)c->mon.cur.L;
+      full.hist_range = c->mon.hist_range;
       full.bin_hz = kFmRate / kMonN;
       give_sized(info, info_size, full);
     }
@@ -4494,14 +4489,14 @@ int fmr_enable_output(fmr_chain *c, const fmr_output_config *cfg, size_t cfg_siz
     set_err("fmr_enable_output: a front-end-only chain (mode -1: channelizer / IfResampler) has no audio");
     return FMR_ERR_UNSUPPORTED;
   }
-  if (c->out) { set_err("fmr_enable_output: the output stage of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
+  if (c->out.on) { set_err("fmr_enable_output: the output stage of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
   if (c->call_seq != 0) {
     set_err("fmr_enable_output: the chain has already taken samples (the output stage counts from the chain's first block)");
     return FMR_ERR_BAD_ARG;
   }
   try {
     HIPCHK(hipSetDevice(c->cfg.device));
-    return c->out_init(m);
+    return build_stage(c->out, c->S, c->stereo, c->max_blocks, c->pipelined ? fmr_chain::kPipe : 1, m);
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
@@ -4509,7 +4504,7 @@ int fmr_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, fmr_
                     size_t *n_frames, fmr_output_info *info, size_t info_size) {
   if (n_frames) *n_frames = 0;
   if (!c || stream < 0 || stream >= c->S || cap_blocks < 0) { set_err("fmr_output_read: bad chain, stream or cap_blocks"); return FMR_ERR_BAD_ARG; }
-  if (!c->out) { set_err("fmr_output_read: the chain has no output stage (fmr_enable_output)"); return FMR_ERR_BAD_ARG; }
+  if (!c->out.on) { set_err("fmr_output_read: the chain has no output stage (fmr_enable_output)"); return FMR_ERR_BAD_ARG; }
   if (cap_frames > 0 && !pcm) { set_err("fmr_output_read: pcm is null"); return FMR_ERR_BAD_ARG; }
   if (cap_blocks > 0 && !blocks) { set_err("fmr_output_read: blocks is null"); return FMR_ERR_BAD_ARG; }
   if (info && (info_size ? info_size : sizeof(fmr_output_info)) > sizeof(fmr_output_info)) {
@@ -4520,23 +4515,23 @@ int fmr_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, fmr_
   try {
     HIPCHK(hipSetDevice(c->cfg.device));
     if (int rc = c->sync_all()) return rc;
-    const size_t fb = c->out_frame_bytes();
-    RecCursor &fc = c->out_fcur, &bc = c->out_bcur;
-    fc.catch_up(stream, c->out_produced());
+    const size_t fb = c->out.frame_bytes();
+    RecCursor &fc = c->out.fcur, &bc = c->out.bcur;
+    fc.catch_up(stream, c->out.produced());
     const unsigned long long first = fc.read[stream];
     int nf = 0;
     if (cap_frames > 0) {
-      nf = fc.take(stream, c->out_produced(), (unsigned long long)cap_frames, [&](size_t k, size_t slot, size_t m) -> int {
-        HIPCHK(hipMemcpy((char *)pcm + k * fb, c->d_out_pcm.p + ((size_t)stream * fc.L + slot) * fb, m * fb, hipMemcpyDeviceToHost));
+      nf = fc.take(stream, c->out.produced(), (unsigned long long)cap_frames, [&](size_t k, size_t slot, size_t m) -> int {
+        HIPCHK(hipMemcpy((char *)pcm + k * fb, c->out.d_pcm.p + ((size_t)stream * fc.L + slot) * fb, m * fb, hipMemcpyDeviceToHost));
         return FMR_OK;
       });
       if (nf < 0) return nf;
     }
     int nb = 0;
-    bc.catch_up(stream, c->out_recs);
+    bc.catch_up(stream, c->out.recs);
     if (cap_blocks > 0) {
-      nb = bc.take(stream, c->out_recs, (unsigned long long)cap_blocks, [&](size_t k, size_t slot, size_t m) -> int {
-        HIPCHK(hipMemcpy(blocks + k, c->d_out_rec.p + (size_t)stream * bc.L + slot, m * sizeof(fmr_output_block), hipMemcpyDeviceToHost));
+      nb = bc.take(stream, c->out.recs, (unsigned long long)cap_blocks, [&](size_t k, size_t slot, size_t m) -> int {
+        HIPCHK(hipMemcpy(blocks + k, c->out.d_rec.p + (size_t)stream * bc.L + slot, m * sizeof(fmr_output_block), hipMemcpyDeviceToHost));
         return FMR_OK;
       });
       if (nb < 0) return nb;
@@ -4545,12 +4540,12 @@ int fmr_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, fmr_
     if (info) {
       fmr_output_info full{};
       full.struct_size = (unsigned)sizeof full;
-      full.format = c->out_cfg.format;
-      full.channels = c->out_channels();
+      full.format = c->out.cfg.format;
+      full.channels = c->out.channels();
       full.first_frame = first;
-      full.frames_waiting = c->out_produced() - fc.read[stream];
+      full.frames_waiting = c->out.produced() - fc.read[stream];
       full.frames_dropped = fc.dropped[stream];
-      full.blocks_waiting = c->out_recs - bc.read[stream];
+      full.blocks_waiting = c->out.recs - bc.read[stream];
       full.blocks_dropped = bc.dropped[stream];
       give_sized(info, info_size, full);
     }
@@ -4577,24 +4572,25 @@ int fmr_set_output_rate(fmr_chain *c, const fmr_output_rate_config *cfg, size_t 
   if (m.mono != 0 && m.mono != 1) { set_err("fmr_set_output_rate: mono %d is neither 0 nor 1", m.mono); return FMR_ERR_BAD_ARG; }
   if (m.reserved != 0) { set_err("fmr_set_output_rate: reserved %d is not 0", m.reserved); return FMR_ERR_BAD_ARG; }
   if (!c) { set_err("fmr_set_output_rate: chain is null"); return FMR_ERR_BAD_ARG; }
-  if (!c->out) { set_err("fmr_set_output_rate: the chain has no output stage (fmr_enable_output comes first)"); return FMR_ERR_BAD_ARG; }
-  if (c->out_rate_set) { set_err("fmr_set_output_rate: the output rate of this chain is already set"); return FMR_ERR_BAD_ARG; }
+  if (!c->out.on) { set_err("fmr_set_output_rate: the chain has no output stage (fmr_enable_output comes first)"); return FMR_ERR_BAD_ARG; }
+  if (c->out.rate_set) { set_err("fmr_set_output_rate: the output rate of this chain is already set"); return FMR_ERR_BAD_ARG; }
   if (c->call_seq != 0) {
     set_err("fmr_set_output_rate: the chain has already taken samples (the ring counts from the chain's first block)");
     return FMR_ERR_BAD_ARG;
   }
   try {
     HIPCHK(hipSetDevice(c->cfg.device));
-    c->out_rate_set = true;
     const bool mono = m.mono == 1 && c->stereo;
-    if (m.rate == kOutRateIn && !mono) return FMR_OK;      // the stage as it is
-    return c->out_rate_init(m.rate, mono);
+    if (m.rate != kOutRateIn || mono)      // (else: the stage as it is)
+      if (int rc = build_stage(c->out.rate, m.rate, mono, c->S, c->stereo, c->max_au)) return rc;
+    c->out.rate_set = true;
+    return FMR_OK;
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
 int fmr_get_output_rate(fmr_chain *c, int stream, fmr_output_rate_info *info, size_t info_size) {
   if (!c || !info || stream < 0 || stream >= c->S) { set_err("fmr_get_output_rate: bad chain, stream or info"); return FMR_ERR_BAD_ARG; }
-  if (!c->out) { set_err("fmr_get_output_rate: the chain has no output stage (fmr_enable_output)"); return FMR_ERR_BAD_ARG; }
+  if (!c->out.on) { set_err("fmr_get_output_rate: the chain has no output stage (fmr_enable_output)"); return FMR_ERR_BAD_ARG; }
   if ((info_size ? info_size : sizeof(fmr_output_rate_info)) > sizeof(fmr_output_rate_info)) {
     set_err("fmr_get_output_rate: info_size %zu is larger than this library's fmr_output_rate_info (%zu): the caller is newer than the library",
             info_size, sizeof(fmr_output_rate_info));
@@ -4605,13 +4601,13 @@ int fmr_get_output_rate(fmr_chain *c, int stream, fmr_output_rate_info *info, si
     if (int rc = c->sync_all()) return rc;
     fmr_output_rate_info full{};
     full.struct_size = (unsigned)sizeof full;
-    full.rate = c->out_hz; full.channels = c->out_channels();
-    full.L = c->out_geom.L; full.M = c->out_geom.M; full.taps_per_phase = c->out_geom.T;
+    full.rate = c->out.rate.hz; full.channels = c->out.channels();
+    full.L = c->out.rate.geom.L; full.M = c->out.rate.geom.M; full.taps_per_phase = c->out.rate.geom.T;
     full.delay_frames = full.taps_per_phase > 1 ? ((double)full.taps_per_phase * full.L - 1.0) / (2.0 * full.M) : 0.0;
-    full.frames_in = c->out_frames;
-    if (c->out_conv) {
+    full.frames_in = c->out.frames;
+    if (c->out.rate.on) {
       unsigned long long tot[2];
-      HIPCHK(hipMemcpy(tot, c->d_out_tot.p + 2 * (size_t)stream, sizeof tot, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(tot, c->out.rate.d_tot.p + 2 * (size_t)stream, sizeof tot, hipMemcpyDeviceToHost));
       full.pcm_clipped = tot[0]; full.pcm_nonfinite = tot[1];
     }
     give_sized(info, info_size, full);
@@ -4657,27 +4653,27 @@ int fmr_enable_loudness(fmr_chain *c, const fmr_loudness_config *cfg, size_t cfg
             c->mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no audio" : "is not covered");
     return FMR_ERR_UNSUPPORTED;
   }
-  if (c->ld) { set_err("fmr_enable_loudness: the audio monitor of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
+  if (c->ld.on) { set_err("fmr_enable_loudness: the audio monitor of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
   if (c->call_seq != 0) {
     set_err("fmr_enable_loudness: the chain has already taken samples (the audio monitor counts from the chain's first audio sample)");
     return FMR_ERR_BAD_ARG;
   }
   try {
     HIPCHK(hipSetDevice(c->cfg.device));
-    return c->ld_init(m);
+    return build_stage(c->ld, c->S, c->max_au, m);
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
 int fmr_loudness_read(fmr_chain *c, int stream, fmr_loudness_record *recs, int cap, fmr_loudness_info *info, size_t info_size) {
   if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_loudness_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
-  if (!c->ld) { set_err("fmr_loudness_read: the chain has no audio monitor (fmr_enable_loudness)"); return FMR_ERR_BAD_ARG; }
+  if (!c->ld.on) { set_err("fmr_loudness_read: the chain has no audio monitor (fmr_enable_loudness)"); return FMR_ERR_BAD_ARG; }
   if (cap > 0 && !recs) { set_err("fmr_loudness_read: recs is null"); return FMR_ERR_BAD_ARG; }
   try {
     HIPCHK(hipSetDevice(c->cfg.device));
     if (int rc = c->sync_all()) return rc;
-    const unsigned long long done = c->ld_done();
-    const int n = c->ld_cur.take(stream, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
-      HIPCHK(hipMemcpy(recs + k, c->d_ld_ring.p + (size_t)stream * c->ld_cur.L + slot, m * sizeof(fmr_loudness_record),
+    const unsigned long long done = c->ld.done();
+    const int n = c->ld.cur.take(stream, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
+      HIPCHK(hipMemcpy(recs + k, c->ld.d_ring.p + (size_t)stream * c->ld.cur.L + slot, m * sizeof(fmr_loudness_record),
                        hipMemcpyDeviceToHost));
       return FMR_OK;
     });
@@ -4687,11 +4683,11 @@ int fmr_loudness_read(fmr_chain *c, int stream, fmr_loudness_record *recs, int c
       full.struct_size = (unsigned)sizeof full;
       full.channels = c->stereo ? 2 : 1;
       full.records_complete = done;
-      full.records_dropped = c->ld_cur.dropped[stream];
-      full.first_unread = c->ld_cur.read[stream];
-      full.records_ready = done - c->ld_cur.read[stream];
-      full.step_samples = c->ld_cfg.step_samples;
-      full.max_records = c->ld_cfg.max_records;
+      full.records_dropped = c->ld.cur.dropped[stream];
+      full.first_unread = c->ld.cur.read[stream];
+      full.records_ready = done - c->ld.cur.read[stream];
+      full.step_samples = c->ld.cfg.step_samples;
+      full.max_records = c->ld.cfg.max_records;
       give_sized(info, info_size, full);
     }
     return n;
@@ -4798,8 +4794,7 @@ int fmr_enable_rf_monitor(fmr_chain *c, const fmr_rf_monitor_config *cfg, size_t
   }
   try {
     HIPCHK(hipSetDevice(c->cfg.device));
-    c->rfm_cfg = m;
-    return c->rfm.init(c->S, c->max_if, m.interval_samples, kRfmBins, m.max_records);
+    return build_stage(c->rfm, c->S, c->max_if, m.interval_samples, kRfmBins, 0.0, m.max_records);
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
 }
 
@@ -4819,8 +4814,8 @@ int fmr_rf_monitor_read(fmr_chain *c, int stream, fmr_rf_monitor_record *recs, u
       full.records_dropped = c->rfm.cur.dropped[stream];
       full.first_unread = c->rfm.cur.read[stream];
       full.records_ready = c->rfm.done() - c->rfm.cur.read[stream];
-      full.interval_samples = c->rfm_cfg.interval_samples;
-      full.max_records = c->rfm_cfg.max_records;
+      full.interval_samples = c->rfm.interval;
+      full.max_records = (int)c->rfm.cur.L;
       full.bin_hz = kFmRate / kMonN;
       give_sized(info, info_size, full);
     }

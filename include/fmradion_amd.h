@@ -312,6 +312,11 @@ int fmr_get_multipath_coefficients(fmr_chain *c, int stream, float *coeff, int c
  * environment -- the product keeps those signals on chip. */
 long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t cap_bytes);
 
+/* What this library holds of the HIP runtime right now, in the whole process: device buffers, page-locked host blocks,
+ * events and streams, one count each.  0 once every chain and spectrum has been destroyed; a failed create or enable
+ * leaves it where it was (tests/test_gpu_lifecycle.py). */
+long long fmr_debug_live_resources(void);
+
 /* Kernel timing with HIP events on the chain's own streams.  enable = 1: every kernel of
  * the most recent call (diagnostics; the extra events cost host time).  enable = 2: only the
  * kernels of the FIR + discriminator stage ("ifr_fused", or "ifr_decim" / "ifr_poly" / "disc", a channel bank's stage A

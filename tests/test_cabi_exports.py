@@ -39,6 +39,7 @@ def test_no_silent_cpu_fallback(lib):
         pytest.skip("GPU present")
     with pytest.raises(fmr.FmrError, match="no HIP device"):
         fmr.Chain()
+    assert fmr.debug_live_resources() == 0       # (the failed create left nothing behind)
 
 
 def test_product_does_not_reference_the_oracle():

@@ -110,6 +110,7 @@ def test_valid_pair_opens_the_device_next(L):
         assert rc == want, (ckw, wkw, rc, msg)
         if want == fmr.ERR_NO_DEVICE:
             assert "no HIP device" in msg, msg
+            assert L.fmr_debug_live_resources() == 0       # (the failed create left nothing behind)
 
 
 def test_struct_layout_and_exports(L):
