@@ -12,7 +12,6 @@
 #include <hip/hip_ext.h>
 #include <atomic>
 #include <chrono>
-#include <functional>
 #include <thread>
 
 #include <cstdarg>
@@ -82,6 +81,7 @@ constexpr long long kSmallCall = 8192;   // IF samples: calls up to this size en
 // passes of a call whose whole budget is ~250 us (main.cpp:916-956 calls block by block) -- or 158 chunks of 16: three
 // waves side by side, a quarter of the samples each (round 6)
 constexpr int kCPllSmall = 16;
+constexpr int kMaxMpfTaps = 1280;         // equaliser taps (4 multipath_stages + 1) the widest form of k_mpf4 holds: 64 lanes x 20
 constexpr unsigned kAgcWaitTicks = 50000000u;   // 0.5 s of the 100 MHz clock: how long k_mpf4 waits for a chunk's gains (the AGC
                                                 // kernel beside it is three times faster than the equaliser: it never waits in practice)
 constexpr int K_AGC_ITERS = 6, K_PLL_ITERS = 4;   // PLL: 2 rounds in lock, 2 spare (an unused round is three launches that return at once: ~6 us measured)
@@ -622,7 +622,7 @@ struct fmr_chain {
 #endif
     // a tail stage that was never enqueued (an asynchronous last call nobody synchronised) is dropped, not launched: its
     // output mux would write into the caller's audio buffer, which the caller may have freed by now
-    tail_pending = false; walk_pending = false; walk_job = nullptr;
+    tail_pending = false; walk_pending = false;
     // THE rule of this destructor: every stream of the chain is idle before any member dies.  Then nothing on the device
     // refers to a buffer, an event or a pinned block any more, the owners give everything back, and the order in which
     // the members die does not matter.
@@ -728,7 +728,16 @@ struct fmr_chain {
     int tiles = 0, grid = 0, tpw = 0, rem = 0;
     static TileRuns balanced(int tiles, int wgs) { const int g = std::min(wgs, tiles); return {tiles, g, tiles / g, tiles % g}; }
   };
-  // what one call runs (plan_call): decided before anything is enqueued or any counter moves
+  // Where the IF AGC of a call runs (run_if_stage launches it, or leaves the job to run_fm / run_fm_pll)
+  enum class AgcPlace {
+    beside_mpf,      // FM with the equaliser: the wave kernel on side2, the equaliser consumes the gains as they are published
+    serial,          // FMR_SERIAL=1: the serial kernel on the decoder stream
+    aside_after_pll, // FM stereo: Newton rounds on side2, enqueued behind the PLL's first pass (run_fm_pll)
+    aside,           // FM mono: Newton rounds on side2, enqueued at once
+    in_line,         // NBFM / AM family: Newton rounds on the decoder stream
+  };
+  // What one call runs (plan_call): every choice that follows from the chain's shape and this call's block lengths, decided
+  // before anything is enqueued or any counter moves.  The stages read it and launch; none of them derives a choice again.
   struct CallPlan {
     StageA a = StageA::none;
     StageB b = StageB::none;
@@ -738,65 +747,78 @@ struct fmr_chain {
     size_t lds_fb = 0;            // ... and its LDS
     ResamplerCounter prev, next;  // the IF resampler's counters before and after the call
     int count_mid = 0;            // stage-A outputs of the call
+    int fe_cus = 0;               // compute units the front end's persistent kernels take (pipelined: one per XCD stays free)
     TileRuns fe_runs, fir_runs;   // fused (macro tiles of 384 IF samples) or poly5h_disc (3072), and poly4_disc (3072)
+    TileRuns dec16_runs;          // decim16: a contiguous run of 500-output epochs per workgroup (tpw for all but the last)
+    int part_from = 0;            // first IF sample whose partial sums k_stats reads (first_part_block; output stage on: 0)
+    bool small = false;           // a call of at most kSmallCall IF samples is launch-bound on the host: fewer spare rounds ...
+    int c_call = 0;               // ... and shorter PLL chunks (the same rule in both chain forms: N_if only)
+    int agc_iters = 0, pll_iters = 0, agc_nc = 0;   // Newton rounds enqueued; chunks of C_AGC samples
+    bool iter_on_side = false;    // FM without the equaliser: round flags and AGC start nodes are reset beside the front end
+    AgcPlace agc = AgcPlace::in_line;
+    bool walk_late = false;       // pipelined chain: the lock logic's walk is enqueued a call late (WalkJob)
+    bool spare_aside = false;     // pipelined chain, few blocks: the PLL passes after the second go to the side stream
     bool fir_disc() const { return fir == IfForm::poly4_disc || fir == IfForm::block3_disc; }
     bool fir_tail() const { return fir == IfForm::poly4_disc; }
     bool b_in_tables() const { return b == StageB::fused || b == StageB::poly5h_disc; }   // launched from run_tables (it needs the block table)
   };
-  // values one call's stages hand each other (run() fills the head, every stage adds its part)
+  // Deferred work is a job: a plain struct of the values it took from the call that made it, and a member function that
+  // takes it by const reference (as TailCtx / tail_stage below); everything else it reads from the chain when it runs.
+  struct AgcJob {                 // the IF AGC's Newton rounds + fallback (enqueue_agc)
+    const float2 *xin = nullptr; long long x_stride{}; int x_off{};
+    const float *nrm_in = nullptr; long long nrm_stride{};   // (non-null: the front end stored |x|^2, not the IF samples)
+    long long N_if{}; int nc{}, iters{};
+    bool aside{};                 // on side2 beside the decoder stream (FM), else on the decoder stream
+    float *gain_out = nullptr;    // null: the recurrence is solved for its state only
+    int ginv{};
+  };
+  struct FePostJob {              // pipelined chain: the front-end stage's end-of-call kernel (launch_fe_post)
+    const float2 *d_iq = nullptr; long long stride{}, n_in{}; int count_mid{}, commit{};
+    bool pending = false;
+  };
+  struct WalkJob {                // the lock logic's walk over the blocks of a call (pll_walk)
+    const fm_mpx_t *base = nullptr; long long base_stride{};
+    BlockTab bt{}; ChunkTab ct{};
+    int *ck_wraps = nullptr; unsigned long long *ck_mask = nullptr;   // the creating call's copy of the wrap counts / masks
+    int *stereo_blk = nullptr, *walk_go = nullptr;
+    size_t ballast{}; bool late{};
+  };
+  struct HostTab { int *if_off = nullptr, *if_len = nullptr, *au_off = nullptr, *au_len = nullptr, *mpf = nullptr; };
+  // values one call's stages hand each other (run() fills the first two groups, every stage adds its part to the third)
   struct CallCtx {
-    const float2 *d_iq = nullptr;
-    size_t stride{};
-    const uint32_t *block_len = nullptr;
-    int nb{};
-    double *d_aud = nullptr;
-    size_t astride{};
-    uint32_t *audio_len = nullptr;
-    long long N_in{};
-    int slot{};
-    int *h_tab = nullptr;
-    int *d_tab_slot = nullptr;
-    int *t_if_off = nullptr;
-    int *t_if_len = nullptr;
-    int *t_au_off = nullptr;
-    int *t_au_len = nullptr;
-    int *t_mpf = nullptr;
+    // ---- what the caller handed in
+    const float2 *d_iq = nullptr; size_t stride{};
+    const uint32_t *block_len = nullptr; int nb{};
+    double *d_aud = nullptr; size_t astride{};
+    uint32_t *audio_len = nullptr; long long N_in{};
+    unsigned long long out_block0 = 0; // output stage: absolute index of the call's first block
+    // ---- this call's table slot: the pinned host copy (its block rows in tab), the device copy
+    int *h_tab = nullptr, *d_tab_slot = nullptr; HostTab tab{};
+    // ---- what each stage adds.  plan_call / run_front_end:
     long long N_if{};
     CallPlan plan{};
-    bool tail_deferred{};  // the previous call's tail stage is still to be enqueued (behind this call's IF filter kernel)
-    int par{};
-    float2 *ifbuf = nullptr;
-    HaloTable ht{};
-    long long N_au{};
-    bool any_mpf{};
-    long long amA_prev{};
-    long long akB_prev{};
-    long long an_prev{};
-    int nck{};
-    int fused_n_tiles{};
-    int fused_kb_ref{};
-    ChunkTab ct{};
-    bool iter_on_side{};
-    BlockTab bt{};
-    long long if_stride{};
-    const float2 *xin = nullptr;
-    long long x_stride{};
-    int x_off{};
-    const float *disc_gain = nullptr;
-    bool agc_on_side{};
-    bool agc_deferred{};
-    std::function<int(hipEvent_t)> enqueue_agc{};
     bool done = false;                 // the front end found nothing to decode
-    unsigned long long out_block0 = 0; // output stage: absolute index of the call's first block
-    hipEvent_t ev_mpx = nullptr;       // recorded where this call's MPX (discriminator output) is complete
-    std::function<void()> fe_post{};   // pipelined chain: the front-end stage's end-of-call kernel, when it is still to be launched
-    // this call's slot of the rings the stages hand each other (plain chain: the one buffer of each kind)
-    fm_mpx_t *base = nullptr;
-    double *raw = nullptr;
+    int par{};                         // this call's slot of the rings the stages hand each other (plain chain: 0, the one buffer of each kind)
+    float2 *ifbuf = nullptr; fm_mpx_t *base = nullptr; double *raw = nullptr; FusedPart *part = nullptr; int *stereo_blk = nullptr;
+    HaloTable ht{};
+    // run_tables:
+    long long N_au{}, amA_prev{}, akB_prev{}, an_prev{}, if_stride{};
+    bool any_mpf{};
+    int nck{}, fused_n_tiles{}, fused_kb_ref{};
+    ChunkTab ct{};
+    BlockTab bt{};
     float *nrm = nullptr;              // fused front end with the discriminator epilogue: |x|^2 of the IF samples (in the IF slot's memory) instead of the IF samples
     long long nrm_stride{};
-    FusedPart *part = nullptr;
-    int *stereo_blk = nullptr;
+    FePostJob fe_post{};
+    bool tail_deferred{};              // the previous call's tail stage is still to be enqueued (behind this call's IF filter kernel)
+    // run_if_stage:
+    const float2 *xin = nullptr; long long x_stride{}; int x_off{};
+    const float *disc_gain = nullptr;  // gain sequence the discriminator multiplies in (null: none)
+    bool agc_on_side{};
+    AgcJob agc{};
+    bool agc_deferred{};               // agc is still to be enqueued (run_fm_pll behind the first pass, else run_fm)
+    // run_fm:
+    hipEvent_t ev_mpx = nullptr;       // recorded where this call's MPX (discriminator output) is complete
     void add_halo(void *buf, long long stride_e, int H, long long N, int words = 2) {   // history to move to the buffer heads at the end of the call (words: 32-bit words per element)
       if (H > 0 && N > 0) ht.d[ht.n++] = HaloDesc{(unsigned *)buf, stride_e * words, H * words, (int)N * words};
     }
@@ -830,7 +852,8 @@ struct fmr_chain {
   // front end of call N+1 -- or by whatever drains the chain.  What the next PLL needs of it, k_pll_commit has committed
   // in call N (kernels_par.hpp): the next call's tables no longer wait for a one-wave walk over 2048 blocks.
   bool walk_pending = false;
-  std::function<int()> walk_job{};
+  WalkJob walk_job{};
+  int pll_walk(const WalkJob &w);
   int flush_walk();
   int walk_par = 0;               // which copy of the PLL's wrap counts / wrap masks / verdict the next call writes
   void tail_channels(const TailCtx &t, hipStream_t st, int ch_base, int nch_l);
@@ -844,10 +867,10 @@ struct fmr_chain {
   int run_tables(CallCtx &k);
   void fill_run_blocks(const CallCtx &k, int *blk0, const TileRuns &r, const int *tile0, long long kb_ref, int tile_len);
   int run_if_stage(CallCtx &k);
+  int enqueue_agc(const AgcJob &j, hipEvent_t gate);
+  void launch_fe_post(FePostJob &j);
   int run_fm(CallCtx &k);
-  int run_fm_pll(CallCtx &k, long long base_stride, bool split_mono,
-                 const std::function<void(hipStream_t, int, int)> &enqueue_tail_channels, bool &mono_enqueued,
-                 bool &fin_on_side, bool &fin_covers_all);
+  int run_fm_pll(CallCtx &k, TailCtx &t);
   int run_nbfm(CallCtx &k);
   int run_am(CallCtx &k);
   int run(const float2 *d_iq, size_t stride, const uint32_t *block_len, int nb, double *d_aud,
@@ -916,6 +939,12 @@ int fmr_chain::init(const fmr_config *c, bool channelizer) {
     return FMR_ERR_UNSUPPORTED;
   }
   has_dec = (mode != FMR_MODE_NONE);
+  // MultipathFilter(stages) holds 4 stages + 1 taps; the equaliser kernel takes up to kMaxMpfTaps of them (k_mpf4<20>)
+  if (mode == FMR_MODE_FM && c->multipath_stages > (kMaxMpfTaps - 1) / 4) {
+    set_err("multipath_stages %u is above %d: the equaliser holds 4 stages + 1 taps, %d at most", c->multipath_stages,
+            (kMaxMpfTaps - 1) / 4, kMaxMpfTaps);
+    return FMR_ERR_UNSUPPORTED;
+  }
   if (c->channel_offset_hz || channelizer) {
     if (int rc = check_bank(c, channelizer)) return rc;
     bank = true;
@@ -1254,7 +1283,6 @@ int fmr_chain::init(const fmr_config *c, bool channelizer) {
     stereo = c->stereo != 0;
     pilot_shift = c->pilot_shift != 0;
     enable_mpf = c->multipath_stages > 0;
-    if (c->multipath_stages > 300) { set_err("multipath_stages > 300 unsupported"); return FMR_ERR_UNSUPPORTED; }
     agc_init = 1.0f; agc_max = 100000.0f; agc_rate = 0.0001f;          // FmDecode.cpp:74
     disc_nf = (float)((75000.0 / kFmRate) * 2.0 * M_PI);                 // PhaseDiscriminator.cpp:28
     disc_bound = (float)(1.0 / ((75000.0 / kFmRate) * 2.0));             // :30
@@ -1615,15 +1643,13 @@ int fmr_chain::run(const float2 *d_iq, size_t stride, const uint32_t *block_len,
   call_seq++;
   const int slot = (int)(call_seq % kTabSlots);
   if (int rcw = wait_mark(&h_marks.p[0], call_seq > (unsigned long long)kTabSlots ? call_seq - kTabSlots : 0)) return rcw;
-  int *h_tab = h_tab_all.p + (size_t)slot * tab_ints;
-  int *d_tab_slot = d_tab.p + (size_t)slot * tab_ints;
-  int *t_if_off = h_tab, *t_if_len = h_tab + max_blocks, *t_au_off = h_tab + 2 * max_blocks,
-      *t_au_len = h_tab + 3 * max_blocks, *t_mpf = h_tab + 4 * max_blocks;
   // ---- the stages of one call share their per-call values through CallCtx (run_front_end ... run_am below)
   CallCtx k{};
   k.d_iq = d_iq; k.stride = stride; k.block_len = block_len; k.nb = nb; k.d_aud = d_aud; k.astride = astride;
-  k.audio_len = audio_len; k.N_in = N_in; k.slot = slot; k.h_tab = h_tab; k.d_tab_slot = d_tab_slot;
-  k.t_if_off = t_if_off; k.t_if_len = t_if_len; k.t_au_off = t_au_off; k.t_au_len = t_au_len; k.t_mpf = t_mpf;
+  k.audio_len = audio_len; k.N_in = N_in;
+  k.h_tab = h_tab_all.p + (size_t)slot * tab_ints;
+  k.d_tab_slot = d_tab.p + (size_t)slot * tab_ints;
+  k.tab = HostTab{k.h_tab, k.h_tab + max_blocks, k.h_tab + 2 * max_blocks, k.h_tab + 3 * max_blocks, k.h_tab + 4 * max_blocks};
   if (out.on) { k.out_block0 = out.block; out.block += (unsigned long long)nb; }   // (every block handed in counts, empty ones too)
   if (int rc = run_front_end(k)) return rc;
   if (k.done) return flush_tail(nullptr);     // (nothing to decode: a pending tail refers to a table slot this call's successors will reuse)
@@ -1633,10 +1659,8 @@ int fmr_chain::run(const float2 *d_iq, size_t stride, const uint32_t *block_len,
   hp2 = std::chrono::steady_clock::now();
   if (int rc = run_if_stage(k)) return rc;
   if (int rc = (mode == FMR_MODE_FM) ? run_fm(k) : (mode == FMR_MODE_NBFM) ? run_nbfm(k) : run_am(k)) return rc;
-  HaloTable &ht = k.ht;
-  if (ht.n) {      // (pipelined chain: the tail stage has taken the table with it, flush_tail)
-    timed("shift_halo", [&] { hipLaunchKernelGGL(k_shift_halo<256>, dim3(ht.n, S), dim3(256), 0, stream, ht); });
-  }
+  if (k.ht.n)      // (pipelined chain: the tail stage has taken the table with it, flush_tail)
+    timed("shift_halo", [&] { hipLaunchKernelGGL(k_shift_halo<256>, dim3(k.ht.n, S), dim3(256), 0, stream, k.ht); });
   if (pipelined) { ring_prev = k.par; ring_prev_n = k.N_if; }
   HIPCHK(hipGetLastError());
   return FMR_OK;
@@ -1658,8 +1682,8 @@ int fmr_chain::plan_call(CallCtx &k) {
   int tl = 4;
   for (int b = 0; b < k.nb; b++) {
     const int n = has_rs ? (int)p.next.advance(rs, k.block_len[b]) : (int)k.block_len[b];
-    k.t_if_off[b] = (int)k.N_if;
-    k.t_if_len[b] = n;
+    k.tab.if_off[b] = (int)k.N_if;
+    k.tab.if_len[b] = n;
     k.N_if += n;
     short_blk |= n != 0 && n < 128;
     tl = std::max(tl, (n + 3) & ~3);
@@ -1671,7 +1695,26 @@ int fmr_chain::plan_call(CallCtx &k) {
   // maps to, and the kernels that run beside the front end -- lock logic (32 KB of LDS), the DC block's node pass (213
   // VGPRs), the spare PLL rounds -- do not fit beside a 152 KB workgroup: on an XCD the front end fills they wait for
   // it to end (measured: the lock logic 250 instead of 55 us, and the next PLL pass behind it).
-  const int fe_cus = pipelined ? std::max(8, n_cu - kFeSpareCus) : n_cu;
+  const int fe_cus = p.fe_cus = pipelined ? std::max(8, n_cu - kFeSpareCus) : n_cu;
+  p.part_from = k.tab.if_off[out.on ? 0 : first_part_block(k.tab.if_len, k.nb)];
+  p.small = N_if <= kSmallCall;
+  p.agc_nc = (int)((N_if + C_AGC - 1) / C_AGC);
+  p.c_call = (p.small && env.x_cpll == 0) ? kCPllSmall : c_pll;
+  p.agc_iters = (mode == FMR_MODE_FM && p.small) ? 3 : K_AGC_ITERS;     // one spare round instead of two to four; if that is not
+  p.pll_iters = p.small ? 3 : K_PLL_ITERS;                              // enough the serial kernel runs over these few thousand samples
+  p.iter_on_side = mode == FMR_MODE_FM && !serial_mode && !enable_mpf;
+  p.agc = (enable_mpf && !serial_mode && mode == FMR_MODE_FM) ? AgcPlace::beside_mpf
+        : (serial_mode || enable_mpf) ? AgcPlace::serial
+        : mode != FMR_MODE_FM ? AgcPlace::in_line
+        : stereo ? AgcPlace::aside_after_pll : AgcPlace::aside;
+  p.walk_late = pipelined && !env.pll_v1 && !serial_mode;
+  // Pipelined chain, streams of few blocks: the PLL passes after the second -- which a call in lock does not need, and which
+  // then cost five launches that read a flag and leave, ~25 us between this call's accepted pass and the next call's front
+  // end -- go to the side stream, in front of the lock logic that waits for them anyway (32 streams x 64 blocks: 0.503 ->
+  // 0.478 ms per step).  When they are needed they run beside the next front end; nothing of that call reads what they
+  // write before its tables, which are behind the lock logic on the same stream.  Not with one long stream: there the side
+  // stream is as long as the step already, and five more launches on it hold the next call's tables back (0.517 -> 0.539).
+  p.spare_aside = pipelined && !env.pll_v1 && k.nb <= (env.x_spare_aside >= 0 ? env.x_spare_aside : kSpareAsideMaxBlocks);
   if (!has_rs) {
     p.a = StageA::pass;
   } else {
@@ -1700,6 +1743,13 @@ int fmr_chain::plan_call(CallCtx &k) {
         p.a = bank ? StageA::bank
             : (fe.decim16 && p.count_mid >= 4 * 500 && aligned) ? StageA::decim16
             : qa == 24 ? StageA::decim2_24 : qa == 16 ? StageA::decim2_16 : StageA::decim;
+      if (p.a == StageA::decim16) {
+        TileRuns &r = p.dec16_runs;
+        r.tiles = (p.count_mid + Decim16Shape<10, 195>::ME - 1) / Decim16Shape<10, 195>::ME;
+        const int wgs = std::max(1, fe_cus / S);
+        r.tpw = (r.tiles + wgs - 1) / wgs;
+        r.grid = (r.tiles + r.tpw - 1) / r.tpw;
+      }
       if (p.a == StageA::decim && in_fmt != 0) { set_err("input_format != cf32 needs the v2 front-end kernel (decimation ratio out of its range)"); return FMR_ERR_UNSUPPORTED; }
       if (fe.poly5h_disc && tiled && N_if >= 3072 && p.count_mid > 0) {
         // R8B class: the dense stage B carries the discriminator epilogue (it needs the block table: launched from
@@ -1770,8 +1820,7 @@ int fmr_chain::run_front_end(CallCtx &k) {
     if (p.a == StageA::bank) {
       if (int rc = launch_chan(fes, k.d_iq, N_in, mA_prev, p.prev.n_in, count_mid)) return rc;
     } else if (p.a == StageA::decim16) {
-      // R8B class, 10 MS/s: the matrix-core form behind the fused front end's input ring, a contiguous run of 500-output epochs
-      // per workgroup (calls of a few epochs per compute unit and up)
+      // R8B class, 10 MS/s: the matrix-core form behind the fused front end's input ring (runs: plan_call)
       using SH16 = Decim16Shape<10, 195>;
       FusedArgs a{};
       a.iq = k.d_iq; a.iq_stride = (long long)k.stride; a.n_valid = N_in;
@@ -1782,11 +1831,9 @@ int fmr_chain::run_front_end(CallCtx &k) {
       a.nbase = lo0 - par16;
       a.count_mid = count_mid;
       a.mid = d_mid.p; a.mid_stride = (long long)(H_mid + max_mid); a.H_mid = H_mid;
-      a.n_tiles = (count_mid + SH16::ME - 1) / SH16::ME;
-      const int fe_cus = pipelined ? std::max(8, n_cu - kFeSpareCus) : n_cu;
-      const int wgs = std::max(1, fe_cus / S);
-      a.tiles_per_wg = (a.n_tiles + wgs - 1) / wgs;
-      const int grid16 = (a.n_tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
+      a.n_tiles = p.dec16_runs.tiles;
+      a.tiles_per_wg = p.dec16_runs.tpw;
+      const int grid16 = p.dec16_runs.grid;
       timed_on(fes, "ifr_decim", [&] {
         if (par16) hipLaunchKernelGGL((k_ifr_decim16<10, 195, 1>), dim3(grid16, S), dim3(DECIM16_THREADS), SH16::LDS_BYTES, fes, a);
         else hipLaunchKernelGGL((k_ifr_decim16<10, 195, 0>), dim3(grid16, S), dim3(DECIM16_THREADS), SH16::LDS_BYTES, fes, a);
@@ -1956,7 +2003,7 @@ void fmr_chain::fill_run_blocks(const CallCtx &k, int *blk0, const TileRuns &r, 
   for (int w = 0; w < r.grid; w++) {
     const long long t = tile0 ? tile0[w] : (long long)w * r.tpw + std::min(w, r.rem);
     const long long kf = std::max<long long>(0, kb_ref + tile_len * t);
-    while (b < k.nb && (long long)k.t_if_off[b] + k.t_if_len[b] <= kf) b++;
+    while (b < k.nb && (long long)k.tab.if_off[b] + k.tab.if_len[b] <= kf) b++;
     blk0[w] = b;
   }
 }
@@ -1972,19 +2019,19 @@ int fmr_chain::run_tables(CallCtx &k) {
   k.any_mpf = false;
   k.amA_prev = arsc.mA; k.akB_prev = arsc.kB; k.an_prev = arsc.n_in;
   for (int b = 0; b < nb; b++) {
-    k.t_mpf[b] = 0;
-    k.t_au_off[b] = (int)k.N_au;
-    k.t_au_len[b] = 0;
-    if (k.t_if_len[b] == 0) continue;          // the decoder is not called for an empty IF block (main.cpp:931-934)
+    k.tab.mpf[b] = 0;
+    k.tab.au_off[b] = (int)k.N_au;
+    k.tab.au_len[b] = 0;
+    if (k.tab.if_len[b] == 0) continue;          // the decoder is not called for an empty IF block (main.cpp:931-934)
     if (mode == FMR_MODE_FM) {
       if (wait_multipath_blocks > 0) wait_multipath_blocks--;     // FmDecode.cpp:107-110
-      else if (enable_mpf) { k.t_mpf[b] = 1; k.any_mpf = true; }
-      const long long n = arsc.advance(ars, k.t_if_len[b]);
-      k.t_au_len[b] = (int)n;
+      else if (enable_mpf) { k.tab.mpf[b] = 1; k.any_mpf = true; }
+      const long long n = arsc.advance(ars, k.tab.if_len[b]);
+      k.tab.au_len[b] = (int)n;
       k.N_au += n;
     } else {
-      k.t_au_len[b] = k.t_if_len[b];
-      k.N_au += k.t_if_len[b];
+      k.tab.au_len[b] = k.tab.if_len[b];
+      k.N_au += k.tab.if_len[b];
     }
   }
   last_n_au = k.N_au;
@@ -1993,10 +2040,9 @@ int fmr_chain::run_tables(CallCtx &k) {
   // host only sends 6*max_blocks+1 ints per call.
   int *t_first = h_tab + 5 * (size_t)max_blocks;
   k.nck = 0;
-  const int c_call = (N_if <= kSmallCall && env.x_cpll == 0) ? kCPllSmall : c_pll;       // (the same rule in both chain forms: N_if only)
   for (int b = 0; b < nb; b++) {
     t_first[b] = k.nck;
-    k.nck += (k.t_if_len[b] + c_call - 1) / c_call;
+    k.nck += (k.tab.if_len[b] + p.c_call - 1) / p.c_call;
   }
   t_first[nb] = k.nck;
   const size_t head_ints = 6 * (size_t)max_blocks + 1;
@@ -2019,7 +2065,6 @@ int fmr_chain::run_tables(CallCtx &k) {
       hipLaunchKernelGGL(k_copy_ints, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, side, (const int *)t_wg, d_wg, n);
   };
   const TileRuns &fr = p.fe_runs;
-  int fused_part_from = 0;
   k.fused_n_tiles = 0; k.fused_kb_ref = 0;
   const long long fused_T_first = p.prev.kB / 48 / 8;
   if (p.b == StageB::fused) {
@@ -2027,7 +2072,6 @@ int fmr_chain::run_tables(CallCtx &k) {
     k.fused_n_tiles = fr.tiles;
     fe_spare_cus = std::max(0, n_cu - fr.grid * S);
     const long long kb_ref = 384 * fused_T_first - p.prev.kB;
-    fused_part_from = k.t_if_off[out.on ? 0 : first_part_block(k.t_if_len, nb)];
     // Where the runs start: a macro tile whose epilogue writes the per-block partial sums (the last ~400 blocks of a call:
     // block walk, six wave reductions and a store per 128 samples) costs its workgroup kFusedSumWeight more than one that does
     // not -- measured, round 6: the workgroups of the last fifth of a 2048-block call took 207-213 us against the others' 194-197
@@ -2036,7 +2080,7 @@ int fmr_chain::run_tables(CallCtx &k) {
     int *t_tile0 = t_wg + kFusedTile0Off;
     {
       const double eps = p.b_disc ? (env.x_sumw >= 0 ? env.x_sumw * 1e-3 : kFusedSumWeight) : 0.0;
-      const long long tp = std::min<long long>(fr.tiles, std::max<long long>(0, (fused_part_from - kb_ref) / 384));   // first tile with sums
+      const long long tp = std::min<long long>(fr.tiles, std::max<long long>(0, (p.part_from - kb_ref) / 384));   // first tile with sums
       const double W = (double)tp + (double)(fr.tiles - tp) * (1.0 + eps);
       t_tile0[0] = 0;
       for (int w = 1; w < fr.grid; w++) {
@@ -2063,7 +2107,6 @@ int fmr_chain::run_tables(CallCtx &k) {
     k.fused_n_tiles = 8 * fr.tiles;                             // in the epilogue's macro tiles of 384 samples
     const long long kb_ref = 48 * (p.prev.kB / 48) - p.prev.kB;
     k.fused_kb_ref = (int)kb_ref;
-    fused_part_from = k.t_if_off[out.on ? 0 : first_part_block(k.t_if_len, nb)];
     fill_run_blocks(k, t_wg, fr, nullptr, kb_ref, 3072);
     copy_runs(fr.grid);
   }
@@ -2072,7 +2115,7 @@ int fmr_chain::run_tables(CallCtx &k) {
   k.ct = ChunkTab{d_ck, d_ck + max_ck, d_ck + 2 * max_ck, d_first, k.nck};
   hipLaunchKernelGGL(k_signal_host, dim3(1), dim3(1), 0, side, &h_marks.p[0], call_seq);
   if (mode == FMR_MODE_FM && k.nck > 0) {
-    hipLaunchKernelGGL(k_chunk_tab, dim3(nb), dim3(64), 0, side, d_tab_slot, d_tab_slot + max_blocks, d_first, c_call,
+    hipLaunchKernelGGL(k_chunk_tab, dim3(nb), dim3(64), 0, side, d_tab_slot, d_tab_slot + max_blocks, d_first, p.c_call,
                        d_ck, d_ck + max_ck, d_ck + 2 * max_ck);
     if (stereo && !serial_mode)
       timed_on(side, "pll_begin", [&] {
@@ -2083,11 +2126,9 @@ int fmr_chain::run_tables(CallCtx &k) {
   // FM without the equaliser: the round flags and the AGC's start nodes are reset here too, beside the front end (5-10 us
   // of the critical path when launched between the front end and the PLL's first pass).  Their last readers of the previous
   // call are the PLL kernels (ordered before this stream's k_pll_finish) and the side-stream AGC (ev_agc).
-  k.iter_on_side = (mode == FMR_MODE_FM) && !serial_mode && !enable_mpf;
-  if (k.iter_on_side) {
+  if (p.iter_on_side) {
     if (ev_agc_live) HIPCHK(hipStreamWaitEvent(side, ev_agc, 0));
-    const int nc = (int)((N_if + C_AGC - 1) / C_AGC);
-    hipLaunchKernelGGL(k_iter_begin, dim3(S), dim3(256), 0, side, d_flags.p, d_agc_nodes.p, nc, d_state.p, S,
+    hipLaunchKernelGGL(k_iter_begin, dim3(S), dim3(256), 0, side, d_flags.p, d_agc_nodes.p, p.agc_nc, d_state.p, S,
                        (unsigned long long *)d_pll_sync.p, (int)(sizeof(PllSync) / 8), d_pll_tick2.p, pll_tick2_per_stream, d_agc_tick.p);
   }
   if (pipelined && ring_prev >= 0 && ring_prev != k.par) {
@@ -2108,11 +2149,6 @@ int fmr_chain::run_tables(CallCtx &k) {
   k.bt = BlockTab{d_tab_slot, d_tab_slot + max_blocks, d_tab_slot + 2 * max_blocks, d_tab_slot + 3 * max_blocks,
                   d_tab_slot + 4 * max_blocks, nb};
   k.if_stride = H_if + (long long)max_if;
-  float2 *const ifbuf = k.ifbuf;
-  const long long if_stride = k.if_stride;
-  // (what the pipelined chain's k_fe_post reads, by value)
-  const float2 *const d_iq = k.d_iq;
-  const long long stride = (long long)k.stride, N_in = k.N_in;
   // the discriminator's carried phase: when the previous call ran the discriminator in its decoder stage (a call too
   // short for the fused kernel), its phase is committed by that call's statistics kernel on the side stream
   if (pipelined && p.b_disc && disc_commit_on_side) HIPCHK(hipStreamWaitEvent(stream, ev_stats, 0));
@@ -2120,7 +2156,7 @@ int fmr_chain::run_tables(CallCtx &k) {
     // ---- fused front end: needs the block table (per-block statistics), hence launched here, after the table copy
     constexpr int D = kFusedD, NA = kFusedNA;
     FusedArgs a{};
-    a.iq = d_iq; a.iq_stride = stride; a.n_valid = N_in;
+    a.iq = k.d_iq; a.iq_stride = (long long)k.stride; a.n_valid = k.N_in;
     a.in_halo = d_in_halo.p; a.H_in = H_in; a.afragA = reinterpret_cast<const uint4 *>(d_fused_afragA.p); a.hA = d_hA.p; a.hB = d_hB.p;
     const long long n0 = (long long)rs.D * p.prev.mA - p.prev.n_in;
     const long long lo0 = n0 + rs.ca() - (NA - 1);
@@ -2135,13 +2171,13 @@ int fmr_chain::run_tables(CallCtx &k) {
     a.count_mid = p.count_mid;
     a.mid = d_mid.p; a.mid_stride = (long long)(H_mid + max_mid); a.H_mid = H_mid;
     a.afragB = reinterpret_cast<const uint4 *>(d_fused_afragB.p); a.hB_inv_scale = fused_hB_inv_scale; a.n_if = (int)N_if;
-    a.out = ifbuf; a.out_stride = if_stride; a.out_off = H_if;
+    a.out = k.ifbuf; a.out_stride = k.if_stride; a.out_off = H_if;
     k.nrm = nullptr;
     if (p.b_disc && !debug_taps) {
       // nobody but the AGC's state solve reads the IF behind the discriminator epilogue: it gets |x|^2 (4 B per sample, in the
       // IF slot's memory) and the IF samples stay on chip
       a.out = nullptr;
-      a.nrm = reinterpret_cast<float *>(ifbuf); a.nrm_stride = 2 * if_stride; a.nrm_off = 0;
+      a.nrm = reinterpret_cast<float *>(k.ifbuf); a.nrm_stride = 2 * k.if_stride; a.nrm_off = 0;
       k.nrm = a.nrm; k.nrm_stride = a.nrm_stride;
     }
     a.n_tiles = fr.tiles;
@@ -2156,7 +2192,7 @@ int fmr_chain::run_tables(CallCtx &k) {
     a.nf = disc_nf; a.bound = disc_bound;
     a.st = d_state.p; a.hB_last = d_hB_last.p; a.part = k.part;
     a.if_off = k.bt.if_off; a.if_len = k.bt.if_len; a.nb = nb;
-    a.part_from = fused_part_from;
+    a.part_from = p.part_from;
     constexpr size_t kLds = FusedShape<D, NA>::LDS_BYTES;
     hipStream_t fes = stream;
     if (d_fe_stamps.p) { a.stamps = d_fe_stamps.p; fe_stamps_n = grid * S; }
@@ -2178,14 +2214,14 @@ int fmr_chain::run_tables(CallCtx &k) {
     // ---- R8B class: stage B with the discriminator epilogue (the fused front end's, a wave per 384 staged samples)
     FusedArgs a{};
     a.n_if = (int)N_if; a.kb_ref = k.fused_kb_ref;
-    a.out = nullptr; a.out_stride = if_stride; a.out_off = H_if;
-    a.nrm = reinterpret_cast<float *>(ifbuf); a.nrm_stride = 2 * if_stride; a.nrm_off = 0;
-    if (debug_taps) { a.out = ifbuf; a.nrm = nullptr; }      // the IF samples themselves (fmr_debug_read 0); the AGC reads them then
+    a.out = nullptr; a.out_stride = k.if_stride; a.out_off = H_if;
+    a.nrm = reinterpret_cast<float *>(k.ifbuf); a.nrm_stride = 2 * k.if_stride; a.nrm_off = 0;
+    if (debug_taps) { a.out = k.ifbuf; a.nrm = nullptr; }      // the IF samples themselves (fmr_debug_read 0); the AGC reads them then
     k.nrm = a.nrm; k.nrm_stride = a.nrm_stride;
     a.base = k.base; a.base_stride = H_b + (long long)max_if; a.base_off = H_b;
     a.dec = debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
     a.nf = disc_nf; a.bound = disc_bound;
-    a.st = d_state.p; a.part = k.part; a.n_tiles = k.fused_n_tiles; a.part_from = fused_part_from;
+    a.st = d_state.p; a.part = k.part; a.n_tiles = k.fused_n_tiles; a.part_from = p.part_from;
     a.if_off = k.bt.if_off; a.if_len = k.bt.if_len; a.nb = nb;
     a.wg_blk0 = d_wg;
     a.mid32 = d_run_ph.p;
@@ -2204,12 +2240,7 @@ int fmr_chain::run_tables(CallCtx &k) {
     // when that stream is the decoder's it is launched behind the PLL's first pass (run_fm_pll), not between the front end
     // and that pass.
     HIPCHK(hipEventRecord(ev_fe[k.par], stream));
-    const int commit = (int)p.b_disc, count_mid = p.count_mid;
-    const long long n_in = bank ? 0ll : N_in;
-    k.fe_post = [=] {
-      hipLaunchKernelGGL(k_fe_post<256>, dim3(3, S), dim3(256), 0, stream, d_in_halo.p, H_in, d_iq, stride, n_in,
-                         d_mid.p, (long long)(H_mid + max_mid), H_mid, count_mid, d_state.p, commit);
-    };
+    k.fe_post = FePostJob{k.d_iq, (long long)k.stride, bank ? 0ll : k.N_in, p.count_mid, (int)p.b_disc, true};
     // the previous call's tail stage: behind this front end, beside this call's PLL stage
 #ifndef FMR_FIR_TAIL_EARLY
     // (... and behind the IF filter's kernel where that one sits between front end and PLL: run_fm)
@@ -2221,13 +2252,21 @@ int fmr_chain::run_tables(CallCtx &k) {
   return FMR_OK;
 }
 
+// Pipelined chain: what the front-end stage carries into its next call (input history, stage-B history, the discriminator's
+// last phase), one small kernel on the decoder stream, if this call still owes it.
+void fmr_chain::launch_fe_post(FePostJob &j) {
+  if (!j.pending) return;
+  j.pending = false;
+  hipLaunchKernelGGL(k_fe_post<256>, dim3(3, S), dim3(256), 0, stream, d_in_halo.p, H_in, j.d_iq, j.stride, j.n_in,
+                     d_mid.p, (long long)(H_mid + max_mid), H_mid, j.count_mid, d_state.p, j.commit);
+}
+
 // IF-rate part common to all decoders: fine tuner, IF filter + level, IF AGC
 int fmr_chain::run_if_stage(CallCtx &k) {
   const CallPlan &p = k.plan;
   const int nb = k.nb;
   const long long N_if = k.N_if, if_stride = k.if_stride;
-  float2 *const ifbuf = k.ifbuf;
-  const BlockTab &bt = k.bt;
+  float2 *const ifbuf = k.ifbuf; const BlockTab &bt = k.bt;
   // ------------------------------------------------------- decoder, IF-rate part
   // SSB / WSPR: mix the new IF samples in place before the filter (the filter history in the halo is already mixed)
   if (ssb_like && d_ft_pre.p)
@@ -2243,7 +2282,7 @@ int fmr_chain::run_if_stage(CallCtx &k) {
     a.dec = debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
     a.nf = disc_nf; a.bound = disc_bound;
     const TileRuns &r = p.fir_runs;
-    a.st = d_state.p; a.part = k.part; a.n_tiles = 8 * r.tiles; a.part_from = k.t_if_off[out.on ? 0 : first_part_block(k.t_if_len, nb)];
+    a.st = d_state.p; a.part = k.part; a.n_tiles = 8 * r.tiles; a.part_from = p.part_from;
     a.if_off = bt.if_off; a.if_len = bt.if_len; a.nb = nb;
     a.wg_blk0 = k.d_tab_slot + (tab_ints - kMaxFusedWg) + kFirBlk0Off;
     a.mid32 = d_run_ph.p;
@@ -2306,25 +2345,23 @@ int fmr_chain::run_if_stage(CallCtx &k) {
     });
     ft_index = (unsigned)((ft_index + (unsigned long long)N_if) % 480u);
   }
-  const float2 *const xin = k.xin = fir_enable ? d_fir.p : ifbuf;
-  const long long x_stride = k.x_stride = fir_enable ? (long long)max_if : if_stride;
-  const int x_off = k.x_off = fir_enable ? 0 : H_if;
+  k.xin = fir_enable ? d_fir.p : ifbuf;
+  k.x_stride = fir_enable ? (long long)max_if : if_stride;
+  k.x_off = fir_enable ? 0 : H_if;
   // ---- IF AGC: Newton multiple shooting over chunks of C_AGC samples (kernels_par.hpp)
   k.disc_gain = d_gain.p;      // gain sequence the discriminator multiplies in (nullptr = none)
   k.agc_on_side = false; k.agc_deferred = false; agc_beside_mpf = false;
-  k.enqueue_agc = nullptr;      // argument: event that gates the side stream (null: a new marker on the main stream)
-  const int agc_nc = (int)((N_if + C_AGC - 1) / C_AGC);
-  if (!k.iter_on_side)
+  if (!p.iter_on_side)
     hipLaunchKernelGGL(k_iter_begin, dim3(S), dim3(256), 0, stream, d_flags.p,
                        (serial_mode || enable_mpf) ? (float *)nullptr : d_agc_nodes.p,
-                       agc_nc, d_state.p, S, (unsigned long long *)d_pll_sync.p, (int)(sizeof(PllSync) / 8), d_pll_tick2.p,
+                       p.agc_nc, d_state.p, S, (unsigned long long *)d_pll_sync.p, (int)(sizeof(PllSync) / 8), d_pll_tick2.p,
                        pll_tick2_per_stream, d_agc_tick.p);
-  // With the equaliser on, the AGC'd amplitude feeds the constant-modulus error, and
-  // the equaliser kernel is the serial bottleneck anyway: use the exact serial AGC.
-  if (enable_mpf && !serial_mode && mode == FMR_MODE_FM) {
-    // beside the equaliser, which consumes the gains as they are published (k_if_agc_wave / k_mpf4, kernels.hpp)
-    // (the progress words count the samples of THIS call: zeroed here, in front of both kernels -- a call that failed
-    // half way cannot leave a count behind that a later call would take for its own)
+  switch (p.agc) {
+  case AgcPlace::beside_mpf:
+    // With the equaliser on, the AGC'd amplitude feeds the constant-modulus error, and the equaliser kernel is the serial
+    // bottleneck anyway: the exact serial AGC, beside the equaliser, which consumes the gains as they are published
+    // (k_if_agc_wave / k_mpf4, kernels.hpp).  The progress words count the samples of THIS call: zeroed here, in front of both
+    // kernels -- a call that failed half way cannot leave a count behind that a later call would take for its own.
     HIPCHK(hipMemsetAsync(d_agc_progress.p, 0, sizeof(unsigned long long) * (size_t)S, stream));
     HIPCHK(hipEventRecord(ev_if, stream));
     HIPCHK(hipStreamWaitEvent(side2, ev_if, 0));
@@ -2334,88 +2371,84 @@ int fmr_chain::run_if_stage(CallCtx &k) {
 #endif
     timed_on(side2, "if_agc", [&] {
       if (env.test_agc_late >= 0)   // (test hook, < 0: the AGC kernel is not launched at all)
-      hipLaunchKernelGGL(k_if_agc_wave, dim3(S), dim3(64), 0, side2, xin, x_stride, x_off, (int)N_if, d_gain.p,
+      hipLaunchKernelGGL(k_if_agc_wave, dim3(S), dim3(64), 0, side2, k.xin, k.x_stride, k.x_off, (int)N_if, d_gain.p,
                          (long long)max_if, d_state.p, agc_init, agc_max, agc_rate, d_agc_progress.p);
     });
     HIPCHK(hipEventRecord(ev_agc, side2));
-    ev_agc_live = true;
-    agc_beside_mpf = true;
-  } else if (serial_mode || enable_mpf) {
+    ev_agc_live = agc_beside_mpf = true;
+    break;
+  case AgcPlace::serial:
     timed("if_agc", [&] {
-      if (enable_mpf && !serial_mode)
-        hipLaunchKernelGGL(k_if_agc_wave, dim3(S), dim3(64), 0, stream, xin, x_stride, x_off, (int)N_if, d_gain.p,
-                           (long long)max_if, d_state.p, agc_init, agc_max, agc_rate, (unsigned long long *)nullptr);
-      else
-      hipLaunchKernelGGL(k_if_agc, dim3((S + 63) / 64), dim3(64), 0, stream, xin, x_stride, x_off, (int)N_if, d_gain.p,
+      hipLaunchKernelGGL(k_if_agc, dim3((S + 63) / 64), dim3(64), 0, stream, k.xin, k.x_stride, k.x_off, (int)N_if, d_gain.p,
                          (long long)max_if, d_state.p, S, agc_init, agc_max, agc_rate, (unsigned long long *)nullptr);
     });
-  } else {
-    // FM without the equaliser: the AGC output only feeds atan2, which is invariant to the
-    // (positive) gain, so the discriminator reads the un-gained samples and the gain recurrence
-    // -- still solved exactly as before, its state carries -- runs on the side stream, off the
-    // critical path (the two paths differ by 3.8e-8 RMS of float rounding).
-    const bool agc_aside = (mode == FMR_MODE_FM);
-    // a short call (one or two source blocks) is launch-bound on the host: one spare round instead of two to four; if
-    // that is not enough the serial kernel runs over these few thousand samples (milliseconds)
-    const int agc_iters = (agc_aside && N_if <= kSmallCall) ? 3 : K_AGC_ITERS;
-    hipStream_t as = agc_aside ? side2 : stream;
+    break;
+  case AgcPlace::aside_after_pll: case AgcPlace::aside: case AgcPlace::in_line: {
+    // FM without the equaliser (aside): the AGC output only feeds atan2, which is invariant to the (positive) gain, so the
+    // discriminator reads the un-gained samples and the gain recurrence -- still solved exactly as before, its state carries
+    // -- runs on the side stream, off the critical path (the two paths differ by 3.8e-8 RMS of float rounding).
+    AgcJob &j = k.agc;
+    j.aside = p.agc != AgcPlace::in_line;
+    j.xin = k.xin; j.x_stride = k.x_stride; j.x_off = k.x_off;
+    j.nrm_in = (j.aside && !fir_enable) ? k.nrm : nullptr; j.nrm_stride = k.nrm_stride;
+    j.N_if = N_if; j.nc = p.agc_nc; j.iters = p.agc_iters;
+    // the discriminator does not see the gains then -- the recurrence is solved for its state only, and its 4 bytes per IF
+    // sample stay out of HBM unless the debug tap asks for them
+    j.gain_out = (j.aside && !debug_taps) ? (float *)nullptr : d_gain.p;
+    j.ginv = (mode == FMR_MODE_FM || mode == FMR_MODE_NBFM) ? (j.gain_out ? 1 : 2) : -env.x_amtol;
+    if (j.aside) { k.disc_gain = nullptr; k.agc_on_side = true; }
+    gain_valid = j.gain_out != nullptr;
     // With the PLL on, the side-stream AGC starts only after the PLL's first (Jacobian) integration pass: that
     // pass runs one wave per SIMD and every co-resident AGC wave stretches it (measured 118 -> 160 us).
-    k.agc_deferred = agc_aside && stereo;
-    const float *const nrm_in = (agc_aside && !fir_enable) ? k.nrm : nullptr;     // (non-null: the front end stored |x|^2, not the IF samples)
-    const long long nrm_in_stride = k.nrm_stride;
-    k.enqueue_agc = [=](hipEvent_t gate) -> int {
-    if (agc_aside) {
-      if (gate) {
-        HIPCHK(hipStreamWaitEvent(side2, gate, 0));
-      } else {
-        HIPCHK(hipEventRecord(ev_if, stream));
-        HIPCHK(hipStreamWaitEvent(side2, ev_if, 0));
-      }
-    }
-    // FM without the equaliser: the discriminator does not see the gains (atan2 is invariant to them) -- the recurrence is
-    // solved for its state only, and its 4 bytes per IF sample stay out of HBM unless the debug tap asks for them
-    float *const gain_out = (agc_aside && !debug_taps) ? (float *)nullptr : d_gain.p;
-    timed_on(as, "if_agc", [&] {
-      const int ginv = (mode == FMR_MODE_FM || mode == FMR_MODE_NBFM) ? (gain_out ? 1 : 2) : -env.x_amtol;
-      // (four waves, one per SIMD: a workgroup of sixteen finds no compute unit with room for all of them while the PLL's
-      // first pass -- one 260-register wave per SIMD, 1258 workgroups queueing -- holds the chip)
-      constexpr int kAgcWg = 256;
-      const size_t agc_ballast = agc_aside ? side_ballast() : 0;
-      const dim3 rgrid((agc_nc + kAgcWg - 1) / kAgcWg, S);
-      for (int it = 0; it < agc_iters; it++) {
-        if (nrm_in)
-          hipLaunchKernelGGL((k_agc_round<C_AGC, float>), rgrid, dim3(kAgcWg), agc_ballast, as, nrm_in, nrm_in_stride, 0, (int)N_if,
-                             gain_out, (long long)max_if, d_agc_nodes.p, d_agc_G.p, d_agc_M.p, agc_nc, agc_init, agc_max,
-                             agc_rate, d_state.p, d_flags.p, ginv, d_agc_tick.p);
-        else
-          hipLaunchKernelGGL((k_agc_round<C_AGC, float2>), rgrid, dim3(kAgcWg), agc_ballast, as, xin, x_stride, x_off, (int)N_if,
-                             gain_out, (long long)max_if, d_agc_nodes.p, d_agc_G.p, d_agc_M.p, agc_nc, agc_init, agc_max,
-                             agc_rate, d_state.p, d_flags.p, ginv, d_agc_tick.p);
-      }
-      if (nrm_in)
-        hipLaunchKernelGGL(k_if_agc_fallback<float>, dim3((S + 63) / 64), dim3(64), 0, as, nrm_in, nrm_in_stride, 0, (int)N_if,
-                           gain_out, (long long)max_if, d_state.p, S, agc_init, agc_max, agc_rate, d_flags.p);
-      else
-      hipLaunchKernelGGL(k_if_agc_fallback<float2>, dim3((S + 63) / 64), dim3(64), 0, as, xin, x_stride, x_off, (int)N_if,
-                         gain_out, (long long)max_if, d_state.p, S, agc_init, agc_max, agc_rate, d_flags.p);
-    });
-    if (agc_aside) { HIPCHK(hipEventRecord(ev_agc, side2)); ev_agc_live = true; }
-    return FMR_OK;
-    };
-    if (agc_aside) { k.disc_gain = nullptr; k.agc_on_side = true; }
-    gain_valid = !(agc_aside && !debug_taps);
-    if (!k.agc_deferred) { if (int rca = k.enqueue_agc(nullptr)) return rca; }
+    k.agc_deferred = p.agc == AgcPlace::aside_after_pll;
+    if (!k.agc_deferred) { if (int rca = enqueue_agc(j, nullptr)) return rca; }
+    break;
+  }
   }
   return FMR_OK;
 }
 
+// The IF AGC's Newton rounds and their fallback, on side2 behind `gate` (null: behind a new marker on the decoder stream)
+// when the job runs aside, else on the decoder stream.
+int fmr_chain::enqueue_agc(const AgcJob &j, hipEvent_t gate) {
+  hipStream_t as = j.aside ? side2 : stream;
+  if (j.aside && !gate) { HIPCHK(hipEventRecord(ev_if, stream)); gate = ev_if; }
+  if (j.aside) HIPCHK(hipStreamWaitEvent(side2, gate, 0));
+  timed_on(as, "if_agc", [&] {
+    // (four waves, one per SIMD: a workgroup of sixteen finds no compute unit with room for all of them while the PLL's
+    // first pass -- one 260-register wave per SIMD, 1258 workgroups queueing -- holds the chip)
+    constexpr int kAgcWg = 256;
+    const size_t agc_ballast = j.aside ? side_ballast() : 0;
+    const dim3 rgrid((j.nc + kAgcWg - 1) / kAgcWg, S);
+    for (int it = 0; it < j.iters; it++) {
+      if (j.nrm_in)
+        hipLaunchKernelGGL((k_agc_round<C_AGC, float>), rgrid, dim3(kAgcWg), agc_ballast, as, j.nrm_in, j.nrm_stride, 0, (int)j.N_if,
+                           j.gain_out, (long long)max_if, d_agc_nodes.p, d_agc_G.p, d_agc_M.p, j.nc, agc_init, agc_max,
+                           agc_rate, d_state.p, d_flags.p, j.ginv, d_agc_tick.p);
+      else
+        hipLaunchKernelGGL((k_agc_round<C_AGC, float2>), rgrid, dim3(kAgcWg), agc_ballast, as, j.xin, j.x_stride, j.x_off, (int)j.N_if,
+                           j.gain_out, (long long)max_if, d_agc_nodes.p, d_agc_G.p, d_agc_M.p, j.nc, agc_init, agc_max,
+                           agc_rate, d_state.p, d_flags.p, j.ginv, d_agc_tick.p);
+    }
+    if (j.nrm_in)
+      hipLaunchKernelGGL(k_if_agc_fallback<float>, dim3((S + 63) / 64), dim3(64), 0, as, j.nrm_in, j.nrm_stride, 0, (int)j.N_if,
+                         j.gain_out, (long long)max_if, d_state.p, S, agc_init, agc_max, agc_rate, d_flags.p);
+    else
+      hipLaunchKernelGGL(k_if_agc_fallback<float2>, dim3((S + 63) / 64), dim3(64), 0, as, j.xin, j.x_stride, j.x_off, (int)j.N_if,
+                         j.gain_out, (long long)max_if, d_state.p, S, agc_init, agc_max, agc_rate, d_flags.p);
+  });
+  if (j.aside) { HIPCHK(hipEventRecord(ev_agc, side2)); ev_agc_live = true; }
+  return FMR_OK;
+}
+
 // PilotPhaseLock: Newton multiple shooting over chunks (kernels_par.hpp); beside it, on side2, the IF AGC and the mono
-// audio tail; after it, on side, the lock logic.  tail(stream, first channel, channels) enqueues the per-channel audio tail.
-int fmr_chain::run_fm_pll(CallCtx &k, long long base_stride, bool split_mono,
-                          const std::function<void(hipStream_t, int, int)> &enqueue_tail_channels, bool &mono_enqueued,
-                          bool &fin_on_side, bool &fin_covers_all) {
-  auto &nb = k.nb; auto &N_if = k.N_if; auto &nck = k.nck; auto &ct = k.ct; auto &bt = k.bt; auto &agc_on_side = k.agc_on_side; auto &agc_deferred = k.agc_deferred; auto &enqueue_agc = k.enqueue_agc;
+// audio tail; after it, on side, the lock logic.  Says in t which of these the tail has to wait for.
+int fmr_chain::run_fm_pll(CallCtx &k, TailCtx &t) {
+  const CallPlan &p = k.plan;
+  const int nb = k.nb, nck = k.nck;
+  const ChunkTab &ct = k.ct; const BlockTab &bt = k.bt;
+  const long long base_stride = H_b + (long long)max_if;
+  const bool split_mono = t.can_split && !pipelined;      // the mono channel of the audio tail beside the PLL, on side2
   if (serial_mode) {
     timed("pll", [&] {
       hipLaunchKernelGGL(k_pll, dim3((S + 63) / 64), dim3(64), 0, stream, k.base, base_stride, H_b, bt, k.raw,
@@ -2427,8 +2460,8 @@ int fmr_chain::run_fm_pll(CallCtx &k, long long base_stride, bool split_mono,
     bool spare_moved = false;     // the passes after the second went to the side stream
     // the wrap counts and masks the lock logic's walk reads: two copies in the pipelined chain, where the walk of this call
     // runs beside the next call's front end and is not ordered before that call's PLL passes, which write them again
-    const bool walk_late = pipelined && !env.pll_v1 && !serial_mode;
-    const int wpar = walk_late ? walk_par : 0;
+    const bool walk_late = p.walk_late, spare_aside = p.spare_aside;
+    const int pll_iters = p.pll_iters, wpar = walk_late ? walk_par : 0;
     if (walk_late) walk_par ^= 1;
     int *const ck_wraps_now = d_ck_wraps.p + (size_t)wpar * ck_copy;
     unsigned long long *const ck_mask_now = d_ck_mask.p + (size_t)wpar * ck_copy * mask_words;
@@ -2437,17 +2470,7 @@ int fmr_chain::run_fm_pll(CallCtx &k, long long base_stride, bool split_mono,
     timed("pll", [&] {
       const int ngrp = (nck + FMR_NODE_GRP - 1) / FMR_NODE_GRP;
       const int ngrp2 = (ngrp + FMR_NODE_GRP2 - 1) / FMR_NODE_GRP2;
-      const int pll_iters = (N_if <= kSmallCall) ? 3 : K_PLL_ITERS;       // (short calls: see the AGC above)
       hipStream_t ps = stream;
-      // Pipelined chain, streams of few blocks: the passes after the second -- which a call in lock does not need, and which
-      // then cost five launches of workgroups that read a flag and leave, ~25 us between this call's accepted pass and the
-      // next call's front end on this stream -- go to the side stream, in front of the lock logic that waits for them anyway
-      // (32 streams x 64 blocks: 0.503 -> 0.478 ms per step).  When they are needed (rounds 3+, the serial fallback) they
-      // run beside the next front end; nothing of that call reads what they write before its tables, which are behind the
-      // lock logic on the same stream.  Not with one long stream: there the side stream -- lock logic over 2048 blocks in
-      // one wave, the AGC's rounds -- is as long as the step already, and five more launches on it hold the next call's
-      // tables back (0.517 -> 0.539).
-      const bool spare_aside = pipelined && !env.pll_v1 && nb <= (env.x_spare_aside >= 0 ? env.x_spare_aside : kSpareAsideMaxBlocks);
       for (int it = 0; it < pll_iters; it++) {
         if (spare_aside && it == 2 && !spare_moved) { (void)hipEventRecord(ev_pll1, stream); (void)hipStreamWaitEvent(side, ev_pll1, 0); spare_moved = true; ps = side; }
         // round 0 integrates the sensitivities too; later rounds reuse them (chord Newton: measured
@@ -2475,22 +2498,21 @@ int fmr_chain::run_fm_pll(CallCtx &k, long long base_stride, bool split_mono,
         const bool wout = it > 0 || env.pll_v1 || nck <= 2;
         if (it < pll_jac_rounds) { if (wout) shoot(k_pll_shoot<true, true>); else shoot(k_pll_shoot<true, false>); }
         else shoot(k_pll_shoot<false, true>);
-        if (it == 0 && k.fe_post) { k.fe_post(); k.fe_post = nullptr; }
-        if (it == 0 && agc_deferred) {
+        if (it == 0) launch_fe_post(k.fe_post);
+        if (it == 0 && k.agc_deferred) {
           // side2: the AGC and the mono audio tail beside the PLL.  Gated on an event that exists already -- the
           // front end's (ev_disc) -- because a marker of its own on this stream costs ~10 us between the first pass
           // and the node pass.
-          agc_deferred = false;
+          k.agc_deferred = false;
           hipEvent_t gate = k.ev_mpx;
           if (!gate) { (void)hipEventRecord(ev_if, stream); gate = ev_if; }
-          auto mono_aside = [&] {
+          if ((rc_agc = enqueue_agc(k.agc, gate))) return;
+          if (split_mono) {
             (void)hipStreamWaitEvent(side2, gate, 0);
-            enqueue_tail_channels(side2, 0, 1);
+            tail_channels(t, side2, 0, 1);
             (void)hipEventRecord(ev_mono, side2);
-            mono_enqueued = true;
-          };
-          if ((rc_agc = enqueue_agc(gate))) return;
-          if (split_mono) mono_aside();
+            t.mono_enqueued = true;
+          }
         }
 #ifdef FMR_AB_PARTNERS
         if (env.pll_v1)
@@ -2540,87 +2562,77 @@ int fmr_chain::run_fm_pll(CallCtx &k, long long base_stride, bool split_mono,
       HIPCHK(hipEventRecord(ev_pll, stream));
       HIPCHK(hipStreamWaitEvent(side, ev_pll, 0));
     }
-    const size_t fin_ballast = side_ballast();
-    int *const walk_go = d_walk_go.p + (size_t)wpar * S;
-    const fm_mpx_t *const base_l = k.base; int *const stereo_blk_l = k.stereo_blk;
-    const BlockTab bt_l = bt; const ChunkTab ct_l = ct;
-    auto walk = [=]() -> int {
-      timed_on(side, "pll_finish", [&] {
-        hipLaunchKernelGGL(k_pll_finish, dim3(S), dim3(64), (env.x_ballast & 1) ? (size_t)kBallastBytes : fin_ballast, side, base_l, base_stride, H_b, bt_l, ct_l, d_atan.p,
-                           pllc, (int)pilot_shift, d_pll_nodes.p, d_pll_G.p, ck_wraps_now, ck_mask_now, mask_words,
-                           d_blk_wraps.p, d_blk_level.p, stereo_blk_l, d_state.p, d_flags.p,
-                           walk_late ? walk_go : (const int *)nullptr);
-      });
-      if (walk_late) HIPCHK(hipEventRecord(ev_fin, side));
-      return FMR_OK;
-    };
+    // the lock logic's walk over the blocks: with the values of THIS call, whichever call enqueues it
+    const WalkJob w{k.base, base_stride, bt, ct, ck_wraps_now, ck_mask_now, k.stereo_blk, d_walk_go.p + (size_t)wpar * S,
+                    side_ballast(), walk_late};
     timed_on(side, walk_late ? "pll_commit" : "pll_blocks", [&] {
-      hipLaunchKernelGGL(k_pll_blocks, dim3((nb + 3) / 4, S), dim3(256), fin_ballast, side, bt, ct, d_pll_G.p,
+      hipLaunchKernelGGL(k_pll_blocks, dim3((nb + 3) / 4, S), dim3(256), w.ballast, side, bt, ct, d_pll_G.p,
                          ck_wraps_now, d_blk_wraps.p, d_blk_level.p, d_flags.p);
       if (walk_late)
-        hipLaunchKernelGGL(k_pll_commit, dim3(S), dim3(FMR_COMMIT_THREADS), (env.x_ballast & 2) ? (size_t)kBallastBytes : fin_ballast, side, bt, ct, pllc, d_pll_G.p, d_blk_wraps.p,
-                           d_blk_level.p, d_state.p, d_flags.p, walk_go);
+        hipLaunchKernelGGL(k_pll_commit, dim3(S), dim3(FMR_COMMIT_THREADS), (env.x_ballast & 2) ? (size_t)kBallastBytes : w.ballast, side, bt, ct, pllc, d_pll_G.p, d_blk_wraps.p,
+                           d_blk_level.p, d_state.p, d_flags.p, w.walk_go);
     });
     if (walk_late) {
       // (the tail waits for this stream's statistics and AGC itself: ev_fin, recorded behind the late walk, covers neither)
-      walk_job = walk; walk_pending = true;
-      fin_on_side = true;
+      walk_job = w; walk_pending = true;
+      t.fin_on_side = true;
       return FMR_OK;
     }
-    if (int rcw = walk()) return rcw;
+    if (int rcw = pll_walk(w)) return rcw;
     // one event for everything beside the main stream: this stream's own work (statistics, lock logic) and the
     // AGC stream's -- the main stream then waits once, before the output mux, instead of four times
-    if (agc_on_side && !agc_deferred) { HIPCHK(hipStreamWaitEvent(side, ev_agc, 0)); fin_covers_all = true; }
+    if (k.agc_on_side && !k.agc_deferred) { HIPCHK(hipStreamWaitEvent(side, ev_agc, 0)); t.fin_covers_all = true; }
     HIPCHK(hipEventRecord(ev_fin, side));
-    fin_on_side = true;
+    t.fin_on_side = true;
   }
+  return FMR_OK;
+}
+
+// k_pll_finish on the side stream: lock counters, PPS events and the per-block stereo flags of the call that made the job
+int fmr_chain::pll_walk(const WalkJob &w) {
+  timed_on(side, "pll_finish", [&] {
+    hipLaunchKernelGGL(k_pll_finish, dim3(S), dim3(64), (env.x_ballast & 1) ? (size_t)kBallastBytes : w.ballast, side, w.base, w.base_stride, H_b, w.bt, w.ct, d_atan.p,
+                       pllc, (int)pilot_shift, d_pll_nodes.p, d_pll_G.p, w.ck_wraps, w.ck_mask, mask_words,
+                       d_blk_wraps.p, d_blk_level.p, w.stereo_blk, d_state.p, d_flags.p,
+                       w.late ? w.walk_go : (const int *)nullptr);
+  });
+  if (w.late) HIPCHK(hipEventRecord(ev_fin, side));
   return FMR_OK;
 }
 
 // FmDecoder: equaliser, discriminator, statistics, pilot PLL, audio resampler + tail, DC block + mux
 int fmr_chain::run_fm(CallCtx &k) {
-  auto &d_iq = k.d_iq; auto &stride = k.stride; auto &nb = k.nb; auto &d_aud = k.d_aud; auto &astride = k.astride;
-  auto &audio_len = k.audio_len; auto &N_in = k.N_in; auto &t_au_len = k.t_au_len; auto &N_if = k.N_if;
-  auto &ifbuf = k.ifbuf; auto &N_au = k.N_au; auto &any_mpf = k.any_mpf;
-  auto &amA_prev = k.amA_prev; auto &akB_prev = k.akB_prev; auto &an_prev = k.an_prev;
-  auto &fused_n_tiles = k.fused_n_tiles; auto &fused_kb_ref = k.fused_kb_ref; auto &bt = k.bt;
-  auto &if_stride = k.if_stride; auto &xin = k.xin; auto &x_stride = k.x_stride;
-  auto &x_off = k.x_off; auto &disc_gain = k.disc_gain; auto &agc_on_side = k.agc_on_side;
-  auto &agc_deferred = k.agc_deferred; auto &enqueue_agc = k.enqueue_agc;
-  auto add_halo = [&](void *buf, long long stride_e, int H, long long N, int words = 2) { k.add_halo(buf, stride_e, H, N, words); };
   const CallPlan &p = k.plan;
-  if (any_mpf) {
+  const int nb = k.nb;
+  const long long N_if = k.N_if, N_au = k.N_au; const BlockTab &bt = k.bt;
+  if (k.any_mpf)
     timed("mpf", [&] {
       // the chain-and-helpers form (k_mpf4: no barrier inside a chunk)
       constexpr int NG4 = FMR_MPF_CH / 4 + 2;
-      const int tpl4 = mpf_N <= 320 ? 5 : mpf_N <= 640 ? 10 : 20;
+      const int tpl4 = mpf_N <= 320 ? 5 : mpf_N <= 640 ? 10 : 20;      // (init(): mpf_N <= kMaxMpfTaps = 1280)
       const size_t lds4 = sizeof(float2) * ((size_t)mpf_N + FMR_MPF_CH + 8) + sizeof(float) * NG4 + sizeof(float2) * FMR_MPF_CH +
                           sizeof(double) * NG4 + sizeof(float2) * (tpl4 <= 10 ? 16 : 8) * 64 * (size_t)tpl4 + sizeof(int) * 16 +
                           sizeof(float2);
       auto go4 = [&](auto kern) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
-        hipLaunchKernelGGL(kern, dim3(S), dim3(256), lds4, stream, xin, x_stride, x_off, d_gain.p, (long long)max_if,
+        hipLaunchKernelGGL(kern, dim3(S), dim3(256), lds4, stream, k.xin, k.x_stride, k.x_off, d_gain.p, (long long)max_if,
                            bt, d_mpf.p, (long long)max_if, d_mpf_coeff.p, d_mpf_state.p, mpf_N, mpf_ref,
                            d_mpf_ok.p, d_state.p, agc_beside_mpf ? d_agc_progress.p : (const unsigned long long *)nullptr,
                            kAgcWaitTicks);
       };
       if (mpf_N <= 64 * 5) go4(k_mpf4<5>);
       else if (mpf_N <= 64 * 10) go4(k_mpf4<10>);
-      else if (mpf_N <= 64 * 20) go4(k_mpf4<20>);                                     // N <= 1280
-      else set_err("equaliser length out of range");
+      else go4(k_mpf4<20>);
     });
-  }
-  if (agc_beside_mpf) {
-    // the discriminator multiplies the gains into the blocks the equaliser passed over (warm-up, resets), and the AGC's
-    // state must be committed before the next call: the AGC kernel finished long ago (it is three times faster)
-    HIPCHK(hipStreamWaitEvent(stream, ev_agc, 0));
-  }
+  // the discriminator multiplies the gains into the blocks the equaliser passed over (warm-up, resets), and the AGC's
+  // state must be committed before the next call: the AGC kernel finished long ago (it is three times faster)
+  if (agc_beside_mpf) HIPCHK(hipStreamWaitEvent(stream, ev_agc, 0));
   const long long base_stride = H_b + (long long)max_if;   // pre-de-emphasis buffers
   const long long de_stride = H_a + (long long)max_if;     // de-emphasised copies feeding the audio resampler
   if (!p.b_disc && !p.fir_disc())     // (the fused front end's / the IF filter's discriminator epilogue has already written the MPX and the block statistics)
   timed("disc", [&] {
-    hipLaunchKernelGGL((k_disc<256, fm_mpx_t>), dim3(nb, S), dim3(256), 0, stream, xin, x_stride, x_off, disc_gain,
-                       (long long)max_if, any_mpf ? d_mpf.p : (float2 *)nullptr, (long long)max_if, d_mpf_ok.p, bt,
+    hipLaunchKernelGGL((k_disc<256, fm_mpx_t>), dim3(nb, S), dim3(256), 0, stream, k.xin, k.x_stride, k.x_off, k.disc_gain,
+                       (long long)max_if, k.any_mpf ? d_mpf.p : (float2 *)nullptr, (long long)max_if, d_mpf_ok.p, bt,
                        disc_nf, disc_bound, d_dec.p, (long long)max_if, k.base, base_stride, H_b,
                        d_bb_mean_blk.p, d_bb_rms_blk.p, d_state.p, p.fir == IfForm::none ? d_if_rms_blk.p : (float *)nullptr);
   });
@@ -2632,29 +2644,28 @@ int fmr_chain::run_fm(CallCtx &k) {
   HIPCHK(hipStreamWaitEvent(side, k.ev_mpx, 0));
   if (p.b == StageB::fused && !pipelined)      // input history for the next call's front end: off the critical path (the next
     timed_on(side, "in_halo", [&] {   // front end waits for this stream's table kernels anyway)
-      hipLaunchKernelGGL((k_update_in_halo<256, 0>), dim3(1, S), dim3(256), 0, side, d_in_halo.p, H_in, d_iq, (long long)stride, N_in);
+      hipLaunchKernelGGL((k_update_in_halo<256, 0>), dim3(1, S), dim3(256), 0, side, d_in_halo.p, H_in, k.d_iq, (long long)k.stride, k.N_in);
     });
   const size_t stats_ballast = side_ballast();
   timed_on(side, "stats", [&] {     // (fused front end: the block values are summed from its partial sums on the fly)
     hipLaunchKernelGGL(k_stats, dim3(S), dim3(FMR_STATS_THREADS), stats_ballast, side, bt, d_if_rms_blk.p, d_bb_mean_blk.p,
                        d_bb_rms_blk.p, d_state.p, S, (int)!(pipelined && p.b_disc),   // (the front-end stage commits its own phase)
-                       (p.b_disc || p.fir_tail()) ? k.part : (const FusedPart *)nullptr, p.fir_tail() ? 8 * p.fir_runs.tiles : fused_n_tiles,
-                       p.fir_tail() ? 0 : fused_kb_ref, out.ifrms_slot(k.par));
+                       (p.b_disc || p.fir_tail()) ? k.part : (const FusedPart *)nullptr, p.fir_tail() ? 8 * p.fir_runs.tiles : k.fused_n_tiles,
+                       p.fir_tail() ? 0 : k.fused_kb_ref, out.ifrms_slot(k.par));
   });
   HIPCHK(hipEventRecord(ev_stats, side));
   disc_commit_on_side = !(pipelined && p.b_disc);
-  bool fin_on_side = false, fin_covers_all = false;
   // ---------------------------------------------------- audio resampler + tail
   TailCtx t{};
-  t.ifbuf = ifbuf; t.if_nrm = k.nrm != nullptr;
+  t.ifbuf = k.ifbuf; t.if_nrm = k.nrm != nullptr;
   t.base = k.base; t.raw = k.raw; t.stereo_blk = k.stereo_blk; t.N_if = N_if; t.N_au = N_au; t.nb = nb; t.bt = bt;
-  t.d_aud = d_aud; t.astride = (long long)astride; t.amA_prev = amA_prev; t.akB_prev = akB_prev;
+  t.d_aud = k.d_aud; t.astride = (long long)k.astride; t.amA_prev = k.amA_prev; t.akB_prev = k.akB_prev;
   t.nch = stereo ? 2 : 1;
-  if (out.on) { t.out = out.begin(k.out_block0, k.t_if_len, nb, N_au); t.out_ifrms = out.ifrms_slot(k.par); }
-  for (int b = 0; b < nb; b++) t.au_max = std::max(t.au_max, t_au_len[b]);
-  t.count_am = (int)(arsc.mA - amA_prev);
+  if (out.on) { t.out = out.begin(k.out_block0, k.tab.if_len, nb, N_au); t.out_ifrms = out.ifrms_slot(k.par); }
+  for (int b = 0; b < nb; b++) t.au_max = std::max(t.au_max, k.tab.au_len[b]);
+  t.count_am = (int)(arsc.mA - k.amA_prev);
   if ((size_t)t.count_am > max_amid || (size_t)N_au > max_au) { set_err("internal audio capacity exceeded"); return FMR_ERR_CAPACITY; }
-  t.a_top0 = (long long)ars.D * amA_prev + ars.ca() - an_prev;
+  t.a_top0 = (long long)ars.D * k.amA_prev + ars.ca() - k.an_prev;
   // fused de-emphasis + stage A: the tile (warm-up + (TOUT-1) D + NA samples) must fit BLOCK * LPL LDS slots;
   // at most 4 * DE_BLOCK outputs per tile: every lane then owns exactly one run of 4 outputs in the FIR phase
   t.de_tout = std::min(4 * kDeBlock, ((kDeBlock * FMR_DE_LPL - FMR_DE_WARMUP - ars.NA - ars.D) / ars.D) & ~3);
@@ -2663,7 +2674,6 @@ int fmr_chain::run_fm(CallCtx &k) {
   t.dk.b0 = dcblock.b0; t.dk.b1 = dcblock.b1; t.dk.b2 = dcblock.b2; t.dk.a1 = dcblock.a1; t.dk.a2 = dcblock.a2;
   for (int j = 0; j < 4; j++) t.dk.ac[j] = dc_ac[j];
   for (int lv = 0; lv < 6; lv++) for (int j = 0; j < 4; j++) t.dk.agp[lv][j] = dc_agp[lv][j];
-  const long long base_stride_ = base_stride;
   const long long am_stride = H_am + (long long)max_amid;
   const long long a1_stride = H_pc + (long long)max_au;
   // Channel 0 (mono = L+R) does not depend on the PLL: in the in-order chain with stereo on it runs on the AGC stream while
@@ -2672,38 +2682,30 @@ int fmr_chain::run_fm(CallCtx &k) {
   // previous call's DC block and mux while this call's PLL iterates.
   t.can_split = stereo && !serial_mode && t.de_fused && (ars.LB == 3 && ars.MB == 8) && n_pilotcut <= FMR_PCUT_MAXTAPS;
   t.ev_mpx = k.ev_mpx;
-  const bool split_mono = t.can_split && !pipelined;
-  bool mono_enqueued = false;
-  if (stereo) {
-    auto tail_fn = [&](hipStream_t st, int ch_base, int nch_l) { tail_channels(t, st, ch_base, nch_l); };
-    if (int rcp = run_fm_pll(k, base_stride_, split_mono, tail_fn, mono_enqueued, fin_on_side, fin_covers_all)) return rcp;
-  }
-  if (agc_deferred) { agc_deferred = false; if (int rca = enqueue_agc(nullptr)) return rca; }   // PLL path not taken
-  if (k.fe_post) { k.fe_post(); k.fe_post = nullptr; }
-  t.fin_on_side = fin_on_side; t.fin_covers_all = fin_covers_all; t.agc_on_side = agc_on_side; t.mono_enqueued = mono_enqueued;
-
+  if (stereo) if (int rcp = run_fm_pll(k, t)) return rcp;
+  if (k.agc_deferred) { k.agc_deferred = false; if (int rca = enqueue_agc(k.agc, nullptr)) return rca; }   // PLL path not taken
+  launch_fe_post(k.fe_post);
+  t.agc_on_side = k.agc_on_side;
   if (!pipelined) {
-    if (fir_enable) add_halo(ifbuf, if_stride, H_if, N_if);
-    add_halo(k.base, base_stride, H_b, N_if, 1);
-    if (stereo) add_halo(k.raw, base_stride, H_b, N_if);
+    if (fir_enable) k.add_halo(k.ifbuf, k.if_stride, H_if, N_if);
+    k.add_halo(k.base, base_stride, H_b, N_if, 1);
+    if (stereo) k.add_halo(k.raw, base_stride, H_b, N_if);
   }       // (pipelined: the halos of the ring slots are carried over at the head of the next call, run_tables)
   if (!t.de_fused || debug_taps) {     // (the fused de-emphasis keeps the 384 kHz signal in LDS: these are taps then)
-    add_halo(d_base_de.p, de_stride, H_a, N_if);
-    if (stereo) add_halo(d_raw_de.p, de_stride, H_a, N_if);
+    k.add_halo(d_base_de.p, de_stride, H_a, N_if);
+    if (stereo) k.add_halo(d_raw_de.p, de_stride, H_a, N_if);
   }
-  add_halo(d_am0.p, am_stride, H_am, t.count_am);
-  if (stereo) add_halo(d_am1.p, am_stride, H_am, t.count_am);
-  add_halo(d_a10.p, a1_stride, H_pc, N_au);
-  if (stereo) add_halo(d_a11.p, a1_stride, H_pc, N_au);
-  if (audio_len) for (int b = 0; b < nb; b++) audio_len[b] = (uint32_t)(stereo ? 2 * t_au_len[b] : t_au_len[b]);
+  k.add_halo(d_am0.p, am_stride, H_am, t.count_am);
+  if (stereo) k.add_halo(d_am1.p, am_stride, H_am, t.count_am);
+  k.add_halo(d_a10.p, a1_stride, H_pc, N_au);
+  if (stereo) k.add_halo(d_a11.p, a1_stride, H_pc, N_au);
+  if (k.audio_len) for (int b = 0; b < nb; b++) k.audio_len[b] = (uint32_t)(stereo ? 2 * k.tab.au_len[b] : k.tab.au_len[b]);
   if (pipelined) {
     // end of the PLL stage on the decoder stream: the tail of this call starts from it.  The tail stage itself is enqueued behind the NEXT call's front end (or by whatever
     // synchronises the chain first): it then runs beside that call's PLL stage and leaves the front end the whole chip.
     if (!stereo) HIPCHK(hipEventRecord(ev_pll, stream));
-    t.ht = k.ht; k.ht.n = 0;
-    t.seq = pipe_seq;
-    tail_job = t;
-    tail_pending = true;
+    t.ht = k.ht; k.ht.n = 0; t.seq = pipe_seq;
+    tail_job = t; tail_pending = true;
     return FMR_OK;
   }
   return tail_stage(t, stream);
@@ -3286,9 +3288,7 @@ void RdsStage::drain() {
 int fmr_chain::flush_walk() {
   if (!walk_pending) return FMR_OK;
   walk_pending = false;
-  const int rc = walk_job();
-  walk_job = nullptr;
-  return rc;
+  return pll_walk(walk_job);
 }
 int fmr_chain::flush_tail(hipEvent_t gate) {
   const int rc_walk = flush_walk();       // (the tail's output mux waits for its call's walk: enqueued first, or the wait finds an older record)
@@ -3327,15 +3327,14 @@ int fmr_chain::enqueue_tail(hipEvent_t gate) {
 
 // NbfmDecoder
 int fmr_chain::run_nbfm(CallCtx &k) {
-  auto &nb = k.nb; auto &d_aud = k.d_aud; auto &astride = k.astride; auto &audio_len = k.audio_len;
-  auto &t_au_len = k.t_au_len; auto &N_if = k.N_if; auto &ifbuf = k.ifbuf; auto &bt = k.bt;
-  auto &if_stride = k.if_stride; auto &xin = k.xin; auto &x_stride = k.x_stride; auto &x_off = k.x_off;
-  auto add_halo = [&](void *buf, long long stride_e, int H, long long N, int words = 2) { k.add_halo(buf, stride_e, H, N, words); };
+  const int nb = k.nb;
+  const long long N_if = k.N_if, astride = (long long)k.astride;
+  const BlockTab &bt = k.bt; double *const d_aud = k.d_aud;
   // NbfmDecoder (NbfmDecode.cpp:47-96): discriminator on the AGC'd IF, statistics, 63-tap audio FIR (same
   // block-head path as the FM pilot cut: LowPassFilterFirAudio), -3 dB.  No resampling: audio block = IF block.
   const long long base_stride = H_b + (long long)max_if;
   timed("disc", [&] {
-    hipLaunchKernelGGL((k_disc<256, double>), dim3(nb, S), dim3(256), 0, stream, xin, x_stride, x_off, d_gain.p,
+    hipLaunchKernelGGL((k_disc<256, double>), dim3(nb, S), dim3(256), 0, stream, k.xin, k.x_stride, k.x_off, d_gain.p,
                        (long long)max_if, (float2 *)nullptr, (long long)max_if, d_mpf_ok.p, bt, disc_nf, disc_bound,
                        d_dec.p, (long long)max_if, d_base.p, base_stride, H_b, d_bb_mean_blk.p, d_bb_rms_blk.p,
                        d_state.p, (float *)nullptr);
@@ -3346,24 +3345,23 @@ int fmr_chain::run_nbfm(CallCtx &k) {
   });
   timed("nbfm_audio", [&] {
     hipLaunchKernelGGL((k_pilotcut2<320, 1280>), dim3(nb, S, 1), dim3(320), 0, stream, d_base.p, (double *)nullptr,
-                       base_stride, H_b, bt, d_pilotcut.p, n_pilotcut, d_aud, (double *)nullptr, (long long)astride,
+                       base_stride, H_b, bt, d_pilotcut.p, n_pilotcut, d_aud, (double *)nullptr, astride,
                        0.70794578438413791, 0);       // std::pow(10.0, -3.0 / 20.0), NbfmDecode.cpp:91
   });
-  add_halo(ifbuf, if_stride, H_if, N_if);
-  add_halo(d_base.p, base_stride, H_b, N_if);
-  if (audio_len) for (int b = 0; b < nb; b++) audio_len[b] = (uint32_t)t_au_len[b];
-  if (out.on) if (int rc = out_stage(d_aud, (long long)astride, bt, out.ifrms_slot(0), out.begin(k.out_block0, k.t_if_len, nb, k.N_au), stream)) return rc;
+  k.add_halo(k.ifbuf, k.if_stride, H_if, N_if);
+  k.add_halo(d_base.p, base_stride, H_b, N_if);
+  if (k.audio_len) for (int b = 0; b < nb; b++) k.audio_len[b] = (uint32_t)k.tab.au_len[b];
+  if (out.on) if (int rc = out_stage(d_aud, astride, bt, out.ifrms_slot(0), out.begin(k.out_block0, k.tab.if_len, nb, k.N_au), stream)) return rc;
   return FMR_OK;
 }
 
 // AmDecoder (AM / DSB / USB / LSB / CW / WSPR)
 int fmr_chain::run_am(CallCtx &k) {
-  auto &nb = k.nb; auto &d_aud = k.d_aud; auto &astride = k.astride; auto &audio_len = k.audio_len;
-  auto &t_au_len = k.t_au_len; auto &N_if = k.N_if; auto &ifbuf = k.ifbuf; auto &bt = k.bt;
-  auto &if_stride = k.if_stride; auto &xin = k.xin; auto &x_stride = k.x_stride; auto &x_off = k.x_off;
-  auto add_halo = [&](void *buf, long long stride_e, int H, long long N, int words = 2) { k.add_halo(buf, stride_e, H, N, words); };
+  const int nb = k.nb;
+  const long long N_if = k.N_if, astride = (long long)k.astride;
+  const BlockTab &bt = k.bt; double *const d_aud = k.d_aud;
   timed("am_demod", [&] {
-    hipLaunchKernelGGL(k_am_demod<256>, dim3(nb, S), dim3(256), 0, stream, xin, x_stride, x_off, d_gain.p,
+    hipLaunchKernelGGL(k_am_demod<256>, dim3(nb, S), dim3(256), 0, stream, k.xin, k.x_stride, k.x_off, d_gain.p,
                        (long long)max_if, bt, (int)(mode != FMR_MODE_AM), d_dec.p, (long long)max_if, d_base.p,
                        (long long)max_if, d_bb_mean_blk.p, d_bb_rms_blk.p);
   });
@@ -3389,19 +3387,19 @@ int fmr_chain::run_am(CallCtx &k) {
                            d_state.p, d_flags.p, d_af_tick.p);
       const int ncd = (int)((N_if + C_AM_DE - 1) / C_AM_DE);
       hipLaunchKernelGGL(k_am_deemph_out<C_AM_DE>, dim3((ncd + 63) / 64, S), dim3(64), 0, stream, d_af_out.p, (long long)max_if,
-                         (int)N_if, am_deemph.b0, am_deemph.a1, (int)(mode == FMR_MODE_AM), d_aud, (long long)astride,
+                         (int)N_if, am_deemph.b0, am_deemph.a1, (int)(mode == FMR_MODE_AM), d_aud, astride,
                          d_state.p, d_flags.p);
       hipLaunchKernelGGL(k_am_commit, dim3((S + 63) / 64), dim3(64), 0, stream, d_state.p, d_flags.p, S);
     }
     hipLaunchKernelGGL(k_am_tail, dim3((S + 63) / 64), dim3(64), 0, stream, d_base.p, (long long)max_if, (int)N_if,
                        am_dcblock.b0, am_dcblock.b1, am_dcblock.b2, am_dcblock.a1, am_dcblock.a2, 1.0, 1.5, af_ref,
-                       af_rate, am_deemph.b0, am_deemph.a1, (int)(mode == FMR_MODE_AM), d_aud, (long long)astride,
+                       af_rate, am_deemph.b0, am_deemph.a1, (int)(mode == FMR_MODE_AM), d_aud, astride,
                        d_state.p, S, par_tail ? &d_flags.p->af_converged : (const int *)nullptr, (int)sizeof(IterFlags),
                        par_tail ? &d_flags.p->af_fallback : (int *)nullptr);
   });
-  add_halo(ifbuf, if_stride, H_if, N_if);
-  if (audio_len) for (int b = 0; b < nb; b++) audio_len[b] = (uint32_t)t_au_len[b];
-  if (out.on) if (int rc = out_stage(d_aud, (long long)astride, bt, out.ifrms_slot(0), out.begin(k.out_block0, k.t_if_len, nb, k.N_au), stream)) return rc;
+  k.add_halo(k.ifbuf, k.if_stride, H_if, N_if);
+  if (k.audio_len) for (int b = 0; b < nb; b++) k.audio_len[b] = (uint32_t)k.tab.au_len[b];
+  if (out.on) if (int rc = out_stage(d_aud, astride, bt, out.ifrms_slot(0), out.begin(k.out_block0, k.tab.if_len, nb, k.N_au), stream)) return rc;
   return FMR_OK;
 }
 

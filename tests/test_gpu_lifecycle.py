@@ -125,6 +125,27 @@ def test_create_that_fails_with_the_device_open(kw, words):
     assert live() == before
 
 
+def test_multipath_stages_are_bounded_by_the_equaliser_kernel():
+    """MultipathFilter(stages) holds 4 stages + 1 taps and the widest equaliser kernel 1280: 320 stages are refused before
+    anything is allocated, 319 (1277 taps) make a chain whose equaliser runs: its 100 warm-up blocks end inside the call, and
+    the six blocks behind them push 3072 samples into its window, past the reference tap (3 stages + 1 = 958 samples back),
+    from where on the constant-modulus error is not zero and the taps move."""
+    before = live()
+    cfg = dict(mode=fmr.MODE_FM, input_rate=384e3, stereo=True, max_block_len=512, max_blocks=106)
+    with pytest.raises(fmr.FmrError, match="multipath_stages 320 is above 319") as e:
+        fmr.Chain(multipath_stages=320, **cfg)
+    assert f"({fmr.ERR_UNSUPPORTED})" in str(e.value)
+    assert live() == before
+    ch = fmr.Chain(multipath_stages=319, **cfg)
+    audio, alen = ch.process_blocks(siggen.fm_stereo_iq(106 * 512, 384e3)[None, :], [512] * 106)
+    assert int(alen.sum()) == audio.shape[1] > 0 and np.isfinite(audio).all()
+    coeff = ch.multipath_coefficients()
+    assert len(coeff) == 4 * 319 + 1 and np.isfinite(coeff).all()
+    assert np.abs(coeff - (np.arange(len(coeff)) == 3 * 319 + 1)).max() > 0
+    ch.close()
+    assert live() == before
+
+
 def test_refused_enables_leave_the_chain_as_it_was(x_fm):
     before = live()
 

@@ -277,11 +277,11 @@ def test_fm_multipath_config4(pilotcut):
     ch.close()
 
 
-@pytest.mark.parametrize("stages", [100, 300])
+@pytest.mark.parametrize("stages", [100, 300, 319])
 def test_fm_multipath_long_equalisers(pilotcut, stages):
-    """-E 100 (401 taps: ten per lane of the chain wave) and -E 300 (1201 taps, the longest the chain takes: twenty per
-    lane, an eight-slot snapshot ring) -- the other two shapes of k_mpf4 (MultipathFilter.cpp:39-75: order = 4 stages + 1,
-    reference tap 3 stages + 1)."""
+    """-E 100 (401 taps: ten per lane of the chain wave), -E 300 (1201 taps: twenty per lane, an eight-slot snapshot
+    ring) and -E 319 (1277 taps, the longest the chain takes: 1280 is what twenty taps per lane hold) -- the other two
+    shapes of k_mpf4 (MultipathFilter.cpp:39-75: order = 4 stages + 1, reference tap 3 stages + 1)."""
     x = siggen.two_ray(siggen.fm_stereo_iq(130 * 2517, 384e3), 20)
     ch, fm, got, ref = _fm_case("fm_multipath_E%d" % stages, x, 2517, 10, stages=stages, tol=1e-5, pilotcut=pilotcut)
     c_got, c_ref = ch.multipath_coefficients(), fm.get_multipath_coefficients()
