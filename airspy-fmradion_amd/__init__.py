@@ -8,6 +8,7 @@ the library is missing or no GPU is present, creation fails loudly.
 The directory name carries a hyphen (the contract's package name), so import it
 with importlib:  fmr = importlib.import_module("airspy-fmradion_amd").
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -40,7 +41,7 @@ CB_FORMS = {"modtap": 1 << 0}
 EXPORTS = [
     "fmr_create", "fmr_destroy", "fmr_last_error", "fmr_version", "fmr_resampler_info", "fmr_process",
     "fmr_process_blocks", "fmr_process_blocks_device", "fmr_synchronize", "fmr_resample", "fmr_get_status",
-    "fmr_get_pps_events", "fmr_get_multipath_coefficients", "fmr_debug_read", "fmr_debug_live_resources",
+    "fmr_get_pps_events", "fmr_get_multipath_coefficients", "fmr_debug_read", "fmr_debug_live_resources", "fmr_debug_chain_shape",
     "fmr_get_kernel_times",
     "fmr_probe_read_bandwidth", "fmr_probe_shader_clock", "fmr_get_kernel_trace",
     "fmr_enable_kernel_timing", "fmr_filter_table", "fmr_fourth_convert", "fmr_design_taps", "fmr_design_taps_class",
@@ -546,6 +547,80 @@ def rds_ps(groups):
 DELAY_3TAPS = np.array([0.0, 1.0, 0.0], dtype=np.float32)  # FilterParameters::delay_3taps_only_iq
 
 
+def _make_config(mode, input_rate, enable_resampler, fourth_down, fmfilter_enable, filter_coeff, stereo, deemphasis_us,
+                 pilot_shift, multipath_stages, max_block_len, max_blocks, n_streams, device, nbfm_freq_dev, input_format,
+                 output_rate, resampler_class, in_order, channel_offsets_hz):
+    """(fmr_config of Chain's arguments, the arrays it points to: keep them alive as long as the config is used)."""
+    offsets = None
+    if channel_offsets_hz is not None:
+        offsets = (C.c_int32 * len(channel_offsets_hz))(*[int(f) for f in channel_offsets_hz])
+        if n_streams == 1:
+            n_streams = len(channel_offsets_hz)
+        assert n_streams == len(channel_offsets_hz), "channel_offsets_hz needs n_streams entries"
+    coeff = np.ascontiguousarray(DELAY_3TAPS if filter_coeff is None else filter_coeff, dtype=np.float32)
+    cfg = Config()
+    cfg.device, cfg.n_streams, cfg.mode, cfg.input_rate = device, n_streams, mode, float(input_rate)
+    cfg.enable_resampler, cfg.enable_fourth_down = int(enable_resampler), int(fourth_down)
+    cfg.fmfilter_enable = int(fmfilter_enable)
+    cfg.filter_coeff = coeff.ctypes.data_as(C.POINTER(C.c_float))
+    cfg.n_filter_coeff = len(coeff)
+    cfg.stereo, cfg.deemphasis_us, cfg.pilot_shift = int(stereo), float(deemphasis_us), int(pilot_shift)
+    cfg.multipath_stages = int(multipath_stages)
+    cfg.max_block_len, cfg.max_blocks = int(max_block_len), int(max_blocks)
+    cfg.nbfm_freq_dev = float(nbfm_freq_dev)
+    cfg.input_format = int(input_format)
+    cfg.output_rate = float(output_rate)
+    cfg.resampler_class = int(resampler_class)
+    cfg.struct_size = C.sizeof(Config)
+    cfg.in_order = int(bool(in_order))
+    if offsets is not None:
+        cfg.channel_offset_hz = offsets
+    return cfg, (coeff, offsets)
+
+
+class ChainShapeInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("D", C.c_int), ("NA", C.c_int), ("LB", C.c_longlong), ("MB", C.c_longlong),
+                ("TB", C.c_int), ("LT", C.c_int), ("stage_b", C.c_uint), ("fused", C.c_int), ("decim16", C.c_int),
+                ("poly5h_disc", C.c_int), ("fir", C.c_int), ("qa", C.c_int), ("pipelined", C.c_int),
+                ("max_if", C.c_uint64), ("max_au", C.c_uint64)]
+
+
+ChainShape = collections.namedtuple("ChainShape", "design stage_b fused decim16 poly5h_disc fir qa pipelined max_if max_au")
+
+
+def chain_shape(mode=MODE_FM, input_rate=384000.0, enable_resampler=False, fourth_down=False, fmfilter_enable=False,
+                filter_coeff=None, stereo=True, deemphasis_us=50.0, pilot_shift=False, multipath_stages=0,
+                max_block_len=65536, max_blocks=1, n_streams=1, device=0, nbfm_freq_dev=0.0, input_format=0, output_rate=0.0,
+                resampler_class=RESAMPLER_FAST, in_order=False, ab=False, channel_offsets_hz=None, enable_rds=False,
+                channelizer=False):
+    """fmr_debug_chain_shape: what creating Chain(...) (channelizer=True: fmr_create_channelizer) would decide before it
+    builds anything -- no device is opened, so this runs without a GPU.  A configuration the create would refuse raises
+    FmrError with the create's code (.code) and message (.message).  Otherwise: design (D, NA, LB, MB, TB, LT; None without
+    the resampler), stage_b (FE_FORMS name of stage B of a call that takes no upgrade), fused (None, "if_only", "disc"),
+    decim16, poly5h_disc, fir (None, "poly4_disc", "poly4_finish"), qa, pipelined, max_if, max_au."""
+    cfg, _keep = _make_config(mode, input_rate, enable_resampler, fourth_down, fmfilter_enable, filter_coeff, stereo,
+                              deemphasis_us, pilot_shift, multipath_stages, max_block_len, max_blocks, n_streams, device,
+                              nbfm_freq_dev, input_format, output_rate, resampler_class, in_order, channel_offsets_hz)
+    return chain_shape_config(cfg, channelizer=channelizer, ab=ab)
+
+
+def chain_shape_config(cfg, channelizer=False, ab=False):
+    """chain_shape for an fmr_config (Config) filled in by the caller."""
+    L = lib(ab=bool(ab))
+    L.fmr_debug_chain_shape.restype = C.c_int
+    L.fmr_debug_chain_shape.argtypes = [C.POINTER(Config), C.c_size_t, C.c_int, C.POINTER(ChainShapeInfo), C.c_size_t]
+    o = ChainShapeInfo()
+    rc = L.fmr_debug_chain_shape(C.byref(cfg), C.sizeof(Config), int(bool(channelizer)), C.byref(o), C.sizeof(ChainShapeInfo))
+    if rc != OK:
+        e = FmrError(f"fmr_debug_chain_shape failed ({rc}): {L.fmr_last_error().decode()}")
+        e.code, e.message = rc, L.fmr_last_error().decode()
+        raise e
+    b = [k for k, bit in FE_FORMS.items() if bit == o.stage_b]
+    return ChainShape({k: int(getattr(o, k)) for k in ("D", "NA", "LB", "MB", "TB", "LT")} if cfg.enable_resampler else None,
+                      b[0] if b else None, [None, "if_only", "disc"][o.fused], bool(o.decim16), bool(o.poly5h_disc),
+                      [None, "poly4_disc", "poly4_finish"][o.fir], o.qa, bool(o.pipelined), int(o.max_if), int(o.max_au))
+
+
 class Chain:
     """One decoder chain (fmr_chain) for n_streams independent IQ streams."""
 
@@ -560,30 +635,11 @@ class Chain:
         self.enable_rds = bool(enable_rds)
         self._L = lib(ab=bool(ab))
         self.bank = channel_offsets_hz is not None
-        if self.bank:
-            self._offsets = (C.c_int32 * len(channel_offsets_hz))(*[int(f) for f in channel_offsets_hz])
-            if n_streams == 1:
-                n_streams = len(channel_offsets_hz)
-            assert n_streams == len(channel_offsets_hz), "channel_offsets_hz needs n_streams entries"
-        coeff = np.ascontiguousarray(DELAY_3TAPS if filter_coeff is None else filter_coeff, dtype=np.float32)
-        self._coeff = coeff
-        cfg = Config()
-        cfg.device, cfg.n_streams, cfg.mode, cfg.input_rate = device, n_streams, mode, float(input_rate)
-        cfg.enable_resampler, cfg.enable_fourth_down = int(enable_resampler), int(fourth_down)
-        cfg.fmfilter_enable = int(fmfilter_enable)
-        cfg.filter_coeff = coeff.ctypes.data_as(C.POINTER(C.c_float))
-        cfg.n_filter_coeff = len(coeff)
-        cfg.stereo, cfg.deemphasis_us, cfg.pilot_shift = int(stereo), float(deemphasis_us), int(pilot_shift)
-        cfg.multipath_stages = int(multipath_stages)
-        cfg.max_block_len, cfg.max_blocks = int(max_block_len), int(max_blocks)
-        cfg.nbfm_freq_dev = float(nbfm_freq_dev)
-        cfg.input_format = int(input_format)
-        cfg.output_rate = float(output_rate)
-        cfg.resampler_class = int(resampler_class)
-        cfg.struct_size = C.sizeof(Config)
-        cfg.in_order = int(bool(in_order))
-        if self.bank:
-            cfg.channel_offset_hz = self._offsets
+        cfg, self._keep = _make_config(mode, input_rate, enable_resampler, fourth_down, fmfilter_enable, filter_coeff, stereo,
+                                       deemphasis_us, pilot_shift, multipath_stages, max_block_len, max_blocks, n_streams,
+                                       device, nbfm_freq_dev, input_format, output_rate, resampler_class, in_order,
+                                       channel_offsets_hz)
+        n_streams = cfg.n_streams
         self.input_format = int(input_format)
         self.n_streams, self.mode, self.stereo = n_streams, mode, bool(stereo) and mode == MODE_FM
         self.h = C.c_void_p()

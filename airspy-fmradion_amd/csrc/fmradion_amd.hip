@@ -377,34 +377,33 @@ struct EnvKnobs {
   }
 };
 
-struct fmr_chain {
+// k_ifr_decim2, 128 lanes per workgroup (256 -- half the tile-halo over-fetch, twice the LDS per workgroup -- measured no
+// faster in round 2): kDecim2Out outputs per tile, and the padded row length of its LDS tile for qa taps per phase
+constexpr int kDecim2Lanes = 128, kDecim2Out = 2 * kDecim2Lanes;
+static int decim2_pad(int qa) {
+  int s_pad = kDecim2Out + qa;
+  while ((s_pad & 15) != 2) s_pad++;
+  return s_pad;
+}
+
+#include "chain_shape.hpp"
+
+// The chain: its shape (what plan_create() decided; the call path reads those members as its own), and what init() built
+// from it -- streams, events, tables, buffers -- plus the state calls carry.
+struct fmr_chain : ChainShape {
   EnvKnobs env;
-  fmr_config cfg{};
-  int S = 1, mode = FMR_MODE_FM;
-  bool has_rs = false, has_dec = true, fir_enable = false, stereo = false, pilot_shift = false;
-  bool enable_mpf = false;
   Stream stream;
   // side stream: per-block bookkeeping (statistics EMAs, PLL lock logic / PPS) runs beside the
   // audio chain instead of in front of it
   bool dec_valid = true;
   bool if_valid = true;                 // the IF samples of the last call are in last_if (false: the fused front end's discriminator epilogue kept them on chip and stored |x|^2 there)
   bool gain_valid = true;               // the per-sample AGC gains of the last call are in d_gain (fmr_debug_read 4)
-  bool debug_taps = false;               // FMR_DEBUG_TAPS=1: keep the de-emphasised 384 kHz signal readable (fmr_debug_read 2,3)
-  DeScan de_scan{};
   DevBuf<double> d_de_pow;
-  // Mismatch-based acceptance threshold of the PLL rounds, in units of the convergence scales (phase 1e-7 rad,
-  // freq 1e-9, phase error 1e-5, biquad delays 1e-7 relative); env FMR_PLL_RTOL, 0 = off.  The second integration pass of
-  // a call in lock sees a boundary mismatch of 8.7 .. 9.0 behind the FAST resampler class and 10.4 behind the R8B class
-  // (tools/pll_mismatch.py: 7e4 after the nominal-ramp guess, 0.008 after a third pass): at 16 both are accepted there.
-  // Measured against the 0.01 setting (third pass) the audio moves by 1.7e-9 RMS -- a tenth of the float32 front end's
-  // own 1.8e-8 deviation from the fp64-accumulating oracle, 6000x inside the 1e-5 target -- and get_pilot_level by
-  // up to 2e-6 relative.  (Round 3's 10 put the R8B class one pass -- 0.15 ms per 2^27-sample call -- behind.)
-  double pll_rtol = 16.0;
   DevBuf<double> d_pll_wgr, d_pll_pre;
   DevBuf<PllSync> d_pll_sync;
   DevBuf<unsigned int> d_pll_tick2;
   int pll_jac_rounds = 1;                // rounds that re-integrate the sensitivities
-  double hp_fe = 0, hp_tab = 0, hp_dec = 0; long long hp_calls = 0; bool host_prof = false;   // FMR_HOST_PROF=1
+  double hp_fe = 0, hp_tab = 0, hp_dec = 0; long long hp_calls = 0;   // FMR_HOST_PROF=1
   // ---- cross-call pipelining (FM chains with the resampler; DESIGN.md section 5 "Three stages in flight").  A call is
   // three stages on three streams -- front end (fe: IfResampler + discriminator), PLL stage (stream / side / side2:
   // statistics, AGC, pilot PLL, lock logic) and audio tail (tail: de-emphasis, audio resampler, pilot cut, DC block,
@@ -413,7 +412,6 @@ struct fmr_chain {
   // call that used it kPipe calls ago has finished (h_marks.p[1], polled by the host).  Everything a stage carries from
   // call to call (halos, StreamState fields) is written by that stage only.
   Stream tail;
-  bool pipelined = false;
   static constexpr int kPipe = 4;        // ring slots
   unsigned long long pipe_seq = 0;       // decoded calls issued (slot = pipe_seq % kPipe)
   int ring_prev = -1;                    // slot of the previous decoded call (-1: none yet) and its IF sample count:
@@ -440,19 +438,11 @@ struct fmr_chain {
   hipStream_t side2 = nullptr;       // the IF AGC when it is off the critical path: side2_own, or on a pipelined chain the side stream
   Event ev_pll1;                     // pipelined chain: the PLL's second pass is done (the passes after it may run on the side stream)
   Event ev_disc, ev_pll, ev_stats, ev_fin, ev_if, ev_agc, ev_tab, ev_mono;
-  int pll_tick2_per_stream = 0;
   bool ev_agc_live = false;            // ev_agc has been recorded by an earlier call
-  // designs + counters
-  ResamplerDesign rs, ars;
+  // counters
   ResamplerCounter rsc, arsc;
   unsigned long long abs_in = 0;          // absolute input sample index (FourthConverter phase)
   unsigned wait_multipath_blocks = 100;   // FmDecode.cpp:33
-  // capacities
-  size_t max_in = 0, max_mid = 0, max_if = 0, max_amid = 0, max_au = 0;
-  int max_blocks = 0;
-  int H_in = 0, H_mid = 0, H_if = 0, H_a = 0, H_am = 0, H_pc = 0;
-  int ntaps = 0, n_pilotcut = 0, mpf_N = 0, mpf_ref = 0;
-  float h_coeff0 = 0.f;                // filter_coeff[0]
   // device buffers
   DevBuf<float2> d_in, d_in_halo, d_mid, d_if, d_fir, d_mpf, d_mpf_coeff, d_mpf_state;
   // FM with the equaliser: the serial IF AGC runs beside the equaliser kernel, which follows its progress counter
@@ -461,40 +451,10 @@ struct fmr_chain {
   std::vector<unsigned> agc_timeouts_seen;      // per stream: StreamState::agc_sync_timeouts already reported
   bool agc_beside_mpf = false;
   DevBuf<int> d_bphi, d_boff;          // stage-B per-position tap phase / sample offset (k_ifr_poly2)
-  int poly2_tile = 0;                  // staged mid samples per tile, 0 = v2 kernel not applicable
-  double nbfm_freq_dev = 8000.0;
-  // SSB / CW / WSPR (AmDecode.cpp:83-90,107-136): mixers before and after the 2049-tap filter
-  bool ssb_like = false;
   DevBuf<float2> d_ft_pre, d_ft_post;   // FineTuner tables (480 entries), empty = no mixer at that place
   unsigned ft_index = 0;                 // FineTuner::m_index, the same for every tuner of the chain
-  double af_ref = 0.6, af_rate = 0.001;  // AfSimpleAgc reference / rate (AmDecode.cpp:54-66)
-  int in_fmt = 0, in_bps = 8;          // source sample format (fmr_config.input_format) and its bytes per IQ sample
-  // ---- front-end kernel forms: init() records what the chain's shape allows, plan_call() picks per call what runs
-  enum class StageA : unsigned char { none, pass, bank, fused, decim16, decim2_16, decim2_24, decim };
-  enum class StageB : unsigned char { none, fused, poly5h_disc, poly5h, poly4_am, poly4, poly3, poly2, poly_frac, poly };
-  // the IF filter: none (FM without it: the block RMS is taken inside the discriminator kernel), the matrix-core form with
-  // the discriminator epilogue (FM -f), k_fm_block3 with / without it, the matrix-core form + k_fir_finish (48 kHz modes),
-  // k_fm_block2, k_fm_block
-  enum class IfForm : unsigned char { none, poly4_disc, block3_disc, block3, poly4_finish, block2, block };
-  enum class FusedFe : unsigned char { none, if_only, disc };
-  struct FeForms {
-    // stage B of a call that takes no upgrade, the first the shape allows of: poly5h (48/125 on the fp16 matrix cores,
-    // three-product split), poly4_am (the 3/8 shape of 384 k -> 48 k as sixteen periods per row block: 48/128), poly4 (f32
-    // MFMA, 48/125/210), poly3 (Q positions per wave share the LDS reads), poly2, poly_frac (fractional phases), poly
-    StageB b = StageB::poly;
-    FusedFe fused = FusedFe::none;   // fused front end (kernels_fused.hpp; 10 MS/s class, FM, cf32, no Fs/4): IF samples only, or
-                                     // with the discriminator as its epilogue (nothing between resampler and discriminator)
-    bool decim16 = false;            // R8B class at 10 MS/s: stage A in the fused front end's matrix-core form (k_ifr_decim16<10, 195>)
-    bool poly5h_disc = false;        // R8B class, FM, nothing between resampler and discriminator: the discriminator is k_ifr_poly5h's epilogue
-    IfForm fir = IfForm::none;       // the IF filter on the matrix cores: poly4_disc (FM -f, k_ifr_poly4<48, 48, 127, 2, Poly4FirDiscEpi>:
-                                     // filter + discriminator + block sums) or poly4_finish (k_ifr_poly4<48, 48, 255 | 127> + k_fir_finish)
-  } fe;
   DevBuf<float> d_afrag_fir_fm;
   DevBuf<float> d_afrag_fir;
-  int poly4_am_tile = 0;
-  int poly5h_nkb = 0;
-  float poly5h_inv_scale = 1.f;
-  size_t poly5h_lds = 0;
   DevBuf<_Float16> d_afrag5h;
   DevBuf<float> d_afrag;               // v4: constant A fragments
   // fused front end (kernels_fused.hpp): stage A + stage B + discriminator in one persistent kernel
@@ -517,13 +477,9 @@ struct fmr_chain {
   int n_cu = 256;                      // compute units of the device (read at create)
   DevBuf<float> d_hBp;                 // zero-padded tap rows for v3
   DevBuf<float> d_hpA;                 // stage-A taps in polyphase order [D][Q] (k_ifr_decim2)
-  int qa = 0;                          // stage-A taps per phase of k_ifr_decim2 (16 or 24), 0 = that kernel not applicable
   unsigned fe_forms_a = 0, fe_forms_b = 0;   // FMR_FE_* bits of the stage-A / stage-B forms launched since create
-  // channel bank (fmr_config.channel_offset_hz): S channels of one input row, stage A in k_ifr_chan (kernels_chanbank.hpp)
-  bool bank = false;
-  std::vector<int32_t> cb_off;              // the offsets [Hz], copied at create
-  unsigned long long cb_F = 0;              // input_rate [Hz]
-  DevBuf<float2> d_cb_taps;                 // modulated stage-A taps [group][k][FMR_CB_G]
+  // channel bank: stage A in k_ifr_chan (kernels_chanbank.hpp)
+  DevBuf<float2> d_cb_taps;                // modulated stage-A taps [group][k][FMR_CB_G]
   DevBuf<ChanPhase> d_cb_ph;                // per channel: f mod F, f D mod F
   unsigned cb_forms = 0;                    // FMR_CB_* bits launched since create
   // ---- optional stages (the structs above say what each is).  Nothing of a stage exists on a chain that never enabled it.
@@ -537,22 +493,16 @@ struct fmr_chain {
                 MonReduceFn kreduce, const char *seg_name, const char *reduce_name, long long N, hipStream_t st);
   int ld_stage(const double *d_aud, long long astride, long long N, hipStream_t st);
   int out_stage(const double *d_aud, long long astride, const BlockTab &bt, const float *if_rms_blk, const OutArgs &a, hipStream_t st);
-  int in_rows() const { return bank ? 1 : S; }   // rows of the input buffers (d_in, d_in_halo)
   // front end only (fmr_resample_blocks_device): stage B writes row s of this call's IF samples to if_out + s if_out_stride
   // instead of the chain's IF buffer (nullptr: the IF buffer)
   float2 *if_out = nullptr;
   long long if_out_stride = 0;
-  int hB_pitch = 0;                    // fractional-phase stage B: row pitch of d_hB (floats)
   DevBuf<float> d_gain, d_dec, d_hA, d_hB, d_coeff, d_atan, d_if_rms_blk, d_bb_mean_blk, d_bb_rms_blk, d_blk_ph;
   DevBuf<double> d_base, d_raw, d_am0, d_am1, d_a10, d_a11, d_pc0, d_pc1, d_audio, d_ahA, d_ahB, d_pilotcut;
   DevBuf<int> d_tab, d_mpf_ok, d_stereo_blk;
   DevBuf<StreamState> d_state;
   // time-parallel recurrences
-  bool serial_mode = false;            // FMR_SERIAL=1: plain serial kernels (A/B, debugging)
-  int c_pll = 64;                      // PLL chunk length (>= C_PLL_MIN; 32: 0.40 ms, 48: 0.345, 64: 0.33, 96 / 128: 0.47 per 2^27-sample call)
-  int H_b = 0;                         // halo of the pre-de-emphasis buffers (>= warm-up)
-  size_t max_ck = 0, max_agc_nc = 0, max_dc_nc = 0;
-  DevBuf<double> d_pll_wfirst;          // start node of every integration wave's first chunk (the fused down-sweep reads it)
+  DevBuf<double> d_pll_wfirst;         // start node of every integration wave's first chunk (the fused down-sweep reads it)
   DevBuf<double> d_base_de, d_raw_de, d_pll_nodes, d_pll_G, d_pll_M, d_pll_PQ, d_pll_dstart, d_pll_PQ2, d_pll_dstart2, d_pll_gres,
       d_blk_level, d_agc_M,
       d_dc_G, d_dc_start;
@@ -560,17 +510,13 @@ struct fmr_chain {
   DevBuf<unsigned int> d_agc_tick;      // k_agc_round's last-arrival ticket, one per stream (left at zero by its users)
   DevBuf<unsigned int> d_af_tick;       // ... and k_af_round's
   DevBuf<double> d_af_nodes, d_af_G, d_af_M, d_af_out;   // AmDecoder audio tail, time-parallel form
-  DcCoef am_dk{};
   DevBuf<int> d_ck_wraps, d_blk_wraps, d_walk_go;
-  size_t ck_copy = 0;             // elements of one copy of d_ck_wraps
   DevBuf<unsigned long long> d_ck_mask;
-  int mask_words = 2;
   DevBuf<IterFlags> d_flags;
   std::vector<IterFlags> h_flags;
   // block tables: ring of pinned host slots + device slots so that queued
   // asynchronous calls never overwrite a table that is still being copied
   static constexpr int kTabSlots = 8;
-  static constexpr int kMaxFusedWg = 2048;
   static constexpr int kFirBlk0Off = 1024;                // ... [1024, 2048) first block of every run of the IF filter's matrix-core kernel
   static constexpr int kFusedTile0Off = 512;             // the table's tail: [0, 512) first block of every run of the fused front end, [512, 1024) first macro tile of every run (+ the end)
   static constexpr double kFusedSumWeight = 0.10;        // what a macro tile with per-block partial sums costs more than one without (run_tables)
@@ -588,18 +534,9 @@ struct fmr_chain {
   size_t side_ballast() const { return (pipelined && fe_spare_cus >= kBallastMinSpare) ? (size_t)kBallastBytes : 0; }
   static constexpr int kFeSpareCus = FMR_FE_SPARE_CUS;      // CUs the pipelined chain's front end leaves to the kernels beside it
   HostBuf<int> h_tab_all;    // pinned, kTabSlots * tab_ints
-  size_t tab_ints = 0;       // 5*max_blocks block table + 3*max_ck chunk table + (max_blocks+1) first-chunk table
   unsigned long long call_seq = 0;      // calls issued
   HostBuf<unsigned long long> h_marks;   // pinned: [0] calls whose table copy has run, [1] pipelined calls whose decoder has finished
   std::vector<StreamState> h_state;
-  // constants
-  PllConst pllc{};
-  Iir1Coef deemph{}, am_deemph{};
-  BiquadCoef dcblock{}, am_dcblock{};
-  double dc_ac[4] = {1, 0, 0, 1};       // A^C_DC of the DC-block biquad (state transition over one chunk)
-  double dc_agp[6][4] = {};             // (A^(C_DC*K))^(2^k): lane-group transitions of the node scan
-  float agc_init = 1.f, agc_max = 1e5f, agc_rate = 1e-4f;
-  float disc_nf = 1.f, disc_bound = 1.f;
   // last call
   long long last_n_if = 0, last_n_au = 0;
   int last_nb = 0;
@@ -627,7 +564,7 @@ struct fmr_chain {
     // refers to a buffer, an event or a pinned block any more, the owners give everything back, and the order in which
     // the members die does not matter.
     for (hipStream_t st : {stream.p, side.p, side2, tail.p}) if (st) (void)hipStreamSynchronize(st);
-    if (host_prof && hp_calls)
+    if (env.host_prof && hp_calls)
       fprintf(stderr, "[fmr host prof] calls %lld  front-end %.1f us  tables %.1f us  decoder %.1f us per call\n", hp_calls,
               hp_fe / hp_calls, hp_tab / hp_calls, hp_dec / hp_calls);
   }
@@ -717,9 +654,17 @@ struct fmr_chain {
     }
     return FMR_OK;
   }
+  // create: the shape (plan_create), then the build from it, by stage in the order the call path uses them
   int init(const fmr_config *c, bool channelizer = false);
-  int check_bank(const fmr_config *c, bool channelizer);
-  int upload_bank(const std::vector<float> &fa);
+  int open_device();
+  int build_front_end();
+  int build_stage_b(const std::vector<float> &fb);
+  int build_fused(const std::vector<float> &fa, const std::vector<float> &fb);
+  int build_if_filter();
+  int build_stats();
+  int build_fm();
+  int build_nbfm();
+  int build_am();
   bool cold = true;                     // no call yet: AGC at its initial gain, PLL unlocked
   int pps_block_base = 0;               // blocks of the call that ran before the part whose PPS events the state holds
   int run_cold_aware(const float2 *d_iq, size_t stride, const uint32_t *block_len, int nb, double *d_aud,
@@ -896,15 +841,6 @@ static int upload(DevBuf<T> &b, const T *src, size_t n) {
   return FMR_OK;
 }
 
-// k_ifr_decim2, 128 lanes per workgroup (256 -- half the tile-halo over-fetch, twice the LDS per workgroup -- measured no
-// faster in round 2): kDecim2Out outputs per tile, and the padded row length of its LDS tile for qa taps per phase
-constexpr int kDecim2Lanes = 128, kDecim2Out = 2 * kDecim2Lanes;
-static int decim2_pad(int qa) {
-  int s_pad = kDecim2Out + qa;
-  while ((s_pad & 15) != 2) s_pad++;
-  return s_pad;
-}
-
 // A fragments of the banded matrix-core kernel (k_ifr_poly4, shape SH): the row of output position pp = 16 mt + lane % 16
 // over window position m = 4 (ks_lo(mt) + i) + lane / 16 holds tap(pp, m) (0 where the row has no tap)
 template <class SH, class Tap>
@@ -927,39 +863,140 @@ static int first_part_block(const int *if_len, int nb) {
   return 0;
 }
 
+// ---- create, the build step: small helpers, the tables (each a function of what it needs), then the chain stage by stage
+template <class T>
+static int upload(DevBuf<T> &b, const std::vector<T> &v) { return upload(b, v.data(), v.size()); }
+
+// zeroed buffers for a list of (buffer, count) pairs; the first error ends it
+static int alloc_all() { return FMR_OK; }
+template <class B, class... Rest>
+static int alloc_all(B &b, size_t n, Rest &&...rest) {
+  if (int rc = b.alloc(n)) return rc;
+  return alloc_all(rest...);
+}
+
+// a kernel may ask for up to `bytes` of dynamic LDS (more than the 64 KB every kernel gets)
+template <class K>
+static int set_dyn_lds(K *kernel, size_t bytes) {
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return FMR_OK;
+}
+
+static std::vector<float> to_float(const std::vector<double> &h) { return std::vector<float>(h.begin(), h.end()); }
+
+// stage-B tap rows as d_hB holds them: [LB][TB], or in the fractional-phase form [LT + 1][pitch]
+static std::vector<float> hB_rows(const ResamplerDesign &rs, int pitch) {
+  if (!rs.LT) return to_float(rs.hB);
+  std::vector<float> fb((size_t)(rs.LT + 1) * pitch, 0.f);
+  for (int p = 0; p <= rs.LT; p++)
+    for (int j = 0; j < rs.TB; j++) fb[(size_t)p * pitch + j] = (float)rs.hB[(size_t)p * rs.TB + j];
+  return fb;
+}
+
+// stage-A taps in polyphase order [D][qa] (k_ifr_decim2)
+static std::vector<float> hpA_table(const std::vector<float> &fa, int D, int qa) {
+  std::vector<float> hp((size_t)D * qa, 0.f);
+  for (size_t k = 0; k < fa.size(); k++) hp[(k % D) * qa + k / D] = fa[k];
+  return hp;
+}
+
+// stage-B rows between FMR_POLY_PADZ zeros on either side (k_ifr_poly3 shifts its window into them)
+static std::vector<float> hBp_table(const std::vector<float> &fb, const ResamplerDesign &rs) {
+  const int TBP = rs.TB + 2 * FMR_POLY_PADZ;
+  std::vector<float> hp((size_t)rs.LB * TBP, 0.f);
+  for (long long r = 0; r < rs.LB; r++)
+    for (int j = 0; j < rs.TB; j++) hp[(size_t)r * TBP + FMR_POLY_PADZ + j] = fb[(size_t)r * rs.TB + j];
+  return hp;
+}
+
+// the fp16 three-product form (k_ifr_poly5h): A fragments [k-block of 32 taps][row tile][h | l][lane][8] of the taps times 2^ea
+static std::vector<_Float16> poly5h_afrag(const std::vector<float> &fb, const StageBLayout &l, int TB, int nkb, int ea) {
+  const float sa = std::ldexp(1.0f, ea);
+  std::vector<_Float16> ah((size_t)nkb * 3 * 2 * 64 * 8, (_Float16)0.f);
+  for (int kb = 0; kb < nkb; kb++)
+    for (int mt = 0; mt < 3; mt++)
+      for (int ln = 0; ln < 64; ln++)
+        for (int e = 0; e < 8; e++) {
+          const int pp = 16 * mt + (ln & 15), m = 32 * kb + 8 * (ln >> 4) + e, j = m - l.off[pp];
+          if (j < 0 || j >= TB) continue;
+          const float t = fb[(size_t)l.phi[pp] * TB + j] * sa;
+          const _Float16 hi = (_Float16)t;
+          const size_t base = ((((size_t)kb * 3 + mt) * 2) * 64 + ln) * 8 + e;
+          ah[base] = hi;
+          ah[base + 64 * 8] = (_Float16)(t - (float)hi);
+        }
+  return ah;
+}
+
+// the IF filter (order + 1 taps c) as the 1 : 1 "polyphase" shape 48 / 48 of the banded matrix-core kernel -- one phase,
+// window start = output index; tap row h[j'] = c[order - j'] over x[i - order + j'], the lag-0 tap (j' = order) left out:
+// the kernel's epilogue (FM -f) or k_fir_finish (48 kHz modes) adds it where the reference has it
+template <class SH>
+static std::vector<float> fir_afrag(const std::vector<float> &c) {
+  const int order = (int)c.size() - 1;
+  return poly4_afrag<SH>([&](int pp, int m) { const int j = m - SH::off(pp); return j >= 0 && j < order ? c[order - j] : 0.f; });
+}
+
+// a channel bank's stage-A taps c_s[k] = hA[k] exp(+2 pi i ((f_s k) mod F) / F) in double, rounded once: [group][k][g],
+// channels beyond S are zero; and per channel f mod F, f D mod F
+static void bank_tables(const std::vector<float> &fa, const std::vector<int32_t> &off, unsigned long long F, int D,
+                        std::vector<float2> &taps, std::vector<ChanPhase> &ph) {
+  const int G = FMR_CB_G, S = (int)off.size(), ng = (S + G - 1) / G, NA = (int)fa.size();
+  taps.assign((size_t)ng * NA * G, make_float2(0.f, 0.f));
+  ph.resize((size_t)S);
+  for (int s = 0; s < S; s++) {
+    const long long fl = off[s];
+    const unsigned long long fm = (unsigned long long)(((fl % (long long)F) + (long long)F) % (long long)F);
+    ph[s] = ChanPhase{fm, (fm * (unsigned long long)D) % F};
+    for (int k = 0; k < NA; k++) {
+      const double a = 2.0 * M_PI * (double)((fm * (unsigned long long)k) % F) / (double)F;
+      const double h = (double)fa[k];
+      taps[((size_t)(s / G) * NA + k) * G + (s % G)] = make_float2((float)(h * std::cos(a)), (float)(h * std::sin(a)));
+    }
+  }
+}
+
+// FineTuner(table_size 480 = 48000/100, freq_shift): FineTuner.cpp:25-52 with m_index = 0, phase offset 0
+static std::vector<float2> finetuner_table(int freq_shift) {
+  const int ts = 480;
+  std::vector<float2> t((size_t)ts);
+  const double phase_step = 2.0 * M_PI / double(ts);
+  for (int i = 0; i < ts; i++) {
+    const double phi = (double)(((int64_t)freq_shift * i) % ts) * phase_step;
+    t[(size_t)i] = make_float2((float)std::cos(phi), (float)std::sin(phi));
+  }
+  return t;
+}
+
+// (A^LPL)^k, k = 0 .. 64, of the de-emphasis (DeScan::apow)
+static std::vector<double> deemph_powers(const Iir1Coef &d) {
+  const double a = deemph_step(d);
+  std::vector<double> apow(65);
+  apow[0] = 1.0;
+  for (int k = 1; k <= 64; k++) apow[k] = apow[k - 1] * a;
+  return apow;
+}
+
 int fmr_chain::init(const fmr_config *c, bool channelizer) {
   env.load();
-  if (env.x_cpll >= C_PLL_MIN) c_pll = env.x_cpll;
-  cfg = *c;
-  S = c->n_streams;
-  mode = c->mode;
-  if (S < 1 || c->max_block_len == 0 || c->max_blocks < 1) { set_err("bad capacity / n_streams"); return FMR_ERR_BAD_ARG; }
-  if (mode != FMR_MODE_NONE && (mode < FMR_MODE_FM || mode > FMR_MODE_WSPR)) {
-    set_err("mode %d is not on the hot path (FM, AM, DSB only)", mode);
-    return FMR_ERR_UNSUPPORTED;
-  }
-  has_dec = (mode != FMR_MODE_NONE);
-  // MultipathFilter(stages) holds 4 stages + 1 taps; the equaliser kernel takes up to kMaxMpfTaps of them (k_mpf4<20>)
-  if (mode == FMR_MODE_FM && c->multipath_stages > (kMaxMpfTaps - 1) / 4) {
-    set_err("multipath_stages %u is above %d: the equaliser holds 4 stages + 1 taps, %d at most", c->multipath_stages,
-            (kMaxMpfTaps - 1) / 4, kMaxMpfTaps);
-    return FMR_ERR_UNSUPPORTED;
-  }
-  if (c->channel_offset_hz || channelizer) {
-    if (int rc = check_bank(c, channelizer)) return rc;
-    bank = true;
-    cb_off.assign(c->channel_offset_hz, c->channel_offset_hz + S);
-    cb_F = (unsigned long long)c->input_rate;
-    cfg.channel_offset_hz = nullptr;       // (copied: the caller's array need not outlive fmr_create)
-  }
+  int rc;
+  if ((rc = plan_create(*this, c, env, channelizer))) return rc;      // (a refused configuration never opens the device)
+  if ((rc = open_device())) return rc;
+  if (has_rs && (rc = build_front_end())) return rc;
+  if ((rc = d_in.alloc((size_t)in_rows() * max_in))) return rc;
+  if ((rc = build_if_filter()) || (rc = build_stats())) return rc;
+  if (!has_dec) return FMR_OK;
+  return mode == FMR_MODE_FM ? build_fm() : mode == FMR_MODE_NBFM ? build_nbfm() : build_am();
+}
+
+int fmr_chain::open_device() {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err("no HIP device"); return FMR_ERR_NO_DEVICE; }
-  if (c->device < 0 || c->device >= ndev) { set_err("device %d out of range (%d devices)", c->device, ndev); return FMR_ERR_BAD_ARG; }
-  HIPCHK(hipSetDevice(c->device));
+  if (cfg.device < 0 || cfg.device >= ndev) { set_err("device %d out of range (%d devices)", cfg.device, ndev); return FMR_ERR_BAD_ARG; }
+  HIPCHK(hipSetDevice(cfg.device));
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-  // The stages of consecutive calls run beside each other for FM chains with the resampler (the default; FMR_PIPELINE=0:
-  // one in-order chain per call).  THREE streams ("Three stages in flight"):
+  if (hipGetDeviceProperties(&prop, cfg.device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
+  // A pipelined chain has THREE streams ("Three stages in flight"):
   //   stream  the critical chain: front end of call N, PLL of call N, front end of call N+1 ... -- both hold the whole chip
   //           (152 KB of LDS per CU; 1258 one-wave workgroups), so they alternate anyway, and on ONE queue the hand-off
   //           between them is a packet boundary, not an event travelling between two queues (~50 us each way, measured)
@@ -968,586 +1005,198 @@ int fmr_chain::init(const fmr_config *c, bool channelizer) {
   // Three, because a process gets four hardware queues from HIP, the host application's own stream included, and more
   // busy queues than that take turns on a pipe in slices of 3.55 ms (measured with four and five busy queues, with and
   // without stream priorities: one process in two then runs at 4-36 ms per step).
-  pipelined = mode == FMR_MODE_FM && c->enable_resampler != 0 && !env.serial && env.pipeline != 0 && c->in_order == 0;
-  int rc0;
-  if ((rc0 = stream.create()) || (rc0 = side.create())) return rc0;
+  int rc;
+  if ((rc = stream.create()) || (rc = side.create())) return rc;
   if (pipelined) {
     side2 = side;
-    if ((rc0 = tail.create())) return rc0;
-    for (Event &e : ev_fe) if ((rc0 = e.create(hipEventDisableTiming))) return rc0;
+    if ((rc = tail.create())) return rc;
+    for (Event &e : ev_fe) if ((rc = e.create(hipEventDisableTiming))) return rc;
   } else {
-    if ((rc0 = side2_own.create())) return rc0;
+    if ((rc = side2_own.create())) return rc;
     side2 = side2_own;
   }
   for (Event *e : {&ev_agc, &ev_pll1, &ev_tab, &ev_mono, &ev_disc, &ev_pll, &ev_stats, &ev_fin, &ev_if})
-    if ((rc0 = e->create(hipEventDisableTiming))) return rc0;
-  double dec_rate = (mode == FMR_MODE_FM || mode == FMR_MODE_NONE) ? kFmRate : kAmRate;
-  if (mode == FMR_MODE_NONE && c->output_rate > 0) dec_rate = c->output_rate;     // IfResampler(in, out), IfResampler.h:35
-  has_rs = c->enable_resampler != 0;
-  max_blocks = c->max_blocks;
-  max_in = c->max_block_len * (size_t)c->max_blocks;
-  max_in = (max_in + 15) & ~(size_t)15;          // row pitch keeps every stream 16-byte aligned in every format
-  in_fmt = c->input_format;
-  if (in_fmt < 0 || in_fmt > 3) { set_err("input_format %d unknown", in_fmt); return FMR_ERR_BAD_ARG; }
-  in_bps = in_fmt == 0 ? 8 : in_fmt == 1 ? 4 : 2;
-  if (in_fmt != 0 && !c->enable_resampler) {
-    set_err("input_format != cf32 is converted inside the front-end kernel: enable_resampler must be set");
-    return FMR_ERR_UNSUPPORTED;
-  }
-  if (has_rs) {
-    if (c->resampler_class != FMR_RESAMPLER_FAST && c->resampler_class != FMR_RESAMPLER_R8B) {
-      set_err("unknown resampler_class %d", c->resampler_class);
-      return FMR_ERR_BAD_ARG;
-    }
-    const bool r8b = c->resampler_class == FMR_RESAMPLER_R8B;
-    if (!(r8b ? rs.design(c->input_rate, dec_rate, kR8bAtten, kR8bPassFrac, true) : rs.design(c->input_rate, dec_rate, kIfAtten))) {
-      set_err("resampling ratio %.9g -> %.9g is outside the supported design range", c->input_rate, dec_rate);
-      return FMR_ERR_UNSUPPORTED;
-    }
-    if (rs.D == 1) {  // stage A degenerates to a copy (one unit tap)
-      rs.NA = 1; rs.hA.assign(1, 1.0);
-    }
-    if (sizeof(float2) * ((size_t)64 * rs.D + rs.NA - 1) > 60000) {
-      set_err("decimation %d of the front end is outside the supported range", rs.D);
-      return FMR_ERR_UNSUPPORTED;
-    }
-    {
-      // the generic stage-B kernels stage a window of (255 MB / LB + TB + 6) mid samples in LDS (64 KB without an attribute)
-      const unsigned long long span = (255ull * (unsigned long long)rs.MB) / (unsigned long long)rs.LB + (unsigned long long)rs.TB + 6;
-      if (span * sizeof(float2) > 65536) {
-        set_err("resampling ratio %.9g -> %.9g: stage B needs %d taps per phase at this ratio and class, more than the kernels stage",
-                c->input_rate, dec_rate, rs.TB);
-        return FMR_ERR_UNSUPPORTED;
-      }
-    }
-    H_in = rs.NA - 1 + rs.D;
-    H_mid = rs.TB;
-    max_mid = max_in / rs.D + 2;
-    max_if = (size_t)((double)max_in * rs.L / rs.M) + 4;
-    std::vector<float> fa(rs.hA.begin(), rs.hA.end()), fb(rs.hB.begin(), rs.hB.end());
-    if (rs.LT) {            // fractional-phase form: rows padded to a multiple of four taps (float4 row loads)
-      hB_pitch = (rs.TB + 3) & ~3;
-      fb.assign((size_t)(rs.LT + 1) * hB_pitch, 0.f);
-      for (int p = 0; p <= rs.LT; p++)
-        for (int j = 0; j < rs.TB; j++) fb[(size_t)p * hB_pitch + j] = (float)rs.hB[(size_t)p * rs.TB + j];
-    }
-    int rc;
-    if ((rc = upload(d_hA, fa.data(), fa.size()))) return rc;
-    if ((rc = upload(d_hB, fb.data(), fb.size()))) return rc;
-    if (rs.D >= 2) {
-      int q = (rs.NA + rs.D - 1) / rs.D;
-      if (q & 1) q++;
-      const int qa2 = (q <= 16) ? 16 : 24;     // 24: stage A of the R8B class (195 taps at D = 10), cf32 input only
-      const size_t lds2 = sizeof(float2) * ((size_t)rs.D * decim2_pad(qa2) + 2);   // + the spare slot
-      if (q <= 24 && (qa2 == 16 || in_fmt == 0) && lds2 <= 64000 && (size_t)rs.D * (kDecim2Out + qa2) <= (size_t)16 * kDecim2Out) {
-        qa = qa2;
-        std::vector<float> hp((size_t)rs.D * qa, 0.f);
-        for (int k = 0; k < rs.NA; k++) hp[(size_t)(k % rs.D) * qa + k / rs.D] = fa[k];
-        if ((rc = upload(d_hpA, hp.data(), hp.size()))) return rc;
-      }
-    }
-    if (in_fmt != 0 && qa != 16) {
-      // the fused sample conversion lives in the v2 front-end kernel only: refuse the chain now, not on every call
-      set_err("input_format != cf32 needs the FAST resampler class and a source rate with integer pre-decimation >= 2 (%.0f -> %.0f Hz gives D = %d): "
-              "convert on the host or use cf32 input", c->input_rate, dec_rate, rs.D);
-      return FMR_ERR_UNSUPPORTED;
-    }
-    if (rs.D == 10 && rs.NA == 195 && in_fmt == 0 && !c->enable_fourth_down && !bank && !env.no_fused && !env.serial) {
-      bool sym = true;
-      for (int k = 0; sym && k < rs.NA / 2; k++) sym = (fa[k] == fa[rs.NA - 1 - k]);
-      if (sym) {
-        using SH16 = Decim16Shape<10, 195>;
-        std::vector<unsigned short> fr((size_t)2 * SH16::NKT * 2 * 64 * 8);
-        decim16_make_afragA<10, 195>(fa.data(), fr.data());
-        if ((rc = upload(d_dec16_afrag, fr.data(), fr.size()))) return rc;
-        if ((rc = d_zero16.alloc(4))) return rc;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_decim16<10, 195, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, SH16::LDS_BYTES));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_decim16<10, 195, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, SH16::LDS_BYTES));
-        fe.decim16 = true;
-      }
-    }
-    fe.b = rs.LT ? StageB::poly_frac : StageB::poly;
-    if (!rs.LT) {
-      // stage-B v2: 64 periods per tile must fit in LDS, odd MB keeps the lane stride conflict-free
-      std::vector<int> phi((size_t)rs.LB), off((size_t)rs.LB);
-      for (long long q = 0; q < rs.LB; q++) { phi[q] = (int)((q * rs.MB) % rs.LB); off[q] = (int)((q * rs.MB) / rs.LB); }
-      const long long tl = 64 * rs.MB + off[rs.LB - 1] + rs.TB;
-      if (tl * 8 <= 98304 && rs.LB <= 4096) {
-        poly2_tile = (int)tl;
-        fe.b = StageB::poly2;
-        if ((rc = upload(d_bphi, phi.data(), phi.size()))) return rc;
-        if ((rc = upload(d_boff, off.data(), off.size()))) return rc;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly2<512>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
-        // v3: Q = 4 consecutive positions per wave; their window shift must fit the zero padding
-        constexpr int Q3 = 4;
-        int dmax = 0;
-        for (long long g = 0; g * Q3 < rs.LB; g++)
-          dmax = std::max(dmax, off[std::min<long long>(g * Q3 + Q3 - 1, rs.LB - 1)] - off[g * Q3]);
-        if (dmax <= FMR_POLY_PADZ - 8 && (tl + 64) * 8 <= 98304) {
-          const int TBP = rs.TB + 2 * FMR_POLY_PADZ;
-          std::vector<float> hp((size_t)rs.LB * TBP, 0.f);
-          for (long long r = 0; r < rs.LB; r++)
-            for (int j = 0; j < rs.TB; j++) hp[(size_t)r * TBP + FMR_POLY_PADZ + j] = fb[(size_t)r * rs.TB + j];
-          if ((rc = upload(d_hBp, hp.data(), hp.size()))) return rc;
-          poly2_tile = (int)tl + 64;       // slack: the last 8-sample step may run past the union window
-          fe.b = StageB::poly3;
-          HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly3<384, Q3>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
-        }
-        if (rs.LB == 48 && rs.MB == 125 && rs.TB != 210 && (rs.TB & 1) == 0) {
-          // any other stage-B length at 48 / 125 (R8B class: TB = 3122): dense product on the fp16 matrix cores, A fragments
-          // streamed through LDS (k_ifr_poly5h)
-          {
-            poly2_tile = (int)tl + 64;
-            // the fp16 three-product form (k_ifr_poly5h): A fragments [k-block of 32 taps][row tile][h | l][lane][8], the
-            // taps scaled by the power of two that puts the largest into [512, 1024)
-            {
-              constexpr int KCH = FMR_POLY5H_KCH;
-              const int nkb = (((off[47] + rs.TB + 31) / 32 + KCH - 1) / KCH) * KCH;
-              double tmax = 0.0;
-              for (float v : fb) tmax = std::max(tmax, (double)std::fabs(v));
-              int ea = 0;
-              if (tmax > 0.0) { int e2; (void)std::frexp(tmax, &e2); ea = 10 - e2; }      // tmax 2^ea in [512, 1024)
-              const float sa = std::ldexp(1.0f, ea);
-              std::vector<_Float16> ah((size_t)nkb * 3 * 2 * 64 * 8, (_Float16)0.f);
-              for (int kb = 0; kb < nkb; kb++)
-                for (int mt = 0; mt < 3; mt++)
-                  for (int l = 0; l < 64; l++)
-                    for (int e = 0; e < 8; e++) {
-                      const int pp = 16 * mt + (l & 15), m = 32 * kb + 8 * (l >> 4) + e, j = m - off[pp];
-                      if (j < 0 || j >= rs.TB) continue;
-                      const float t = fb[(size_t)phi[pp] * rs.TB + j] * sa;
-                      const _Float16 hi = (_Float16)t;
-                      const size_t base = ((((size_t)kb * 3 + mt) * 2) * 64 + l) * 8 + e;
-                      ah[base] = hi;
-                      ah[base + 64 * 8] = (_Float16)(t - (float)hi);
-                    }
-              const size_t x_len = (size_t)((((int)tl + 64 + 127) / 128) * 128 + 96);
-              const size_t lds5h = 8 * x_len + 2 * (size_t)KCH * 3 * 2 * 64 * 16;      // (planes + two A chunks; the results are staged over the A buffers)
-              if (lds5h <= 160 * 1024 - 64 && (size_t)63 * 125 + 32 * (size_t)nkb <= x_len && x_len <= 48 * 256) {
-                if ((rc = upload(d_afrag5h, ah.data(), ah.size()))) return rc;
-                fe.b = StageB::poly5h; poly5h_nkb = nkb; poly5h_inv_scale = std::ldexp(1.0f, -ea); poly5h_lds = lds5h;
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly5h<48, 125>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5h));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly5h<48, 125, Poly5hDiscEpi>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5h));
-                fe.poly5h_disc = mode == FMR_MODE_FM && in_fmt == 0 && !c->fmfilter_enable && c->multipath_stages == 0 && !env.no_fused;
-              }
-            }
-          }
-        }
-        if (fe.b == StageB::poly3 && rs.LB == 3 && rs.MB == 8 && rs.TB == 214 && !env.no_fused) {
-          // 384 k -> 48 k (config 3): sixteen periods of 3 outputs / 8 mid samples are one period of 48 / 128 -- output
-          // 3 a + b of it starts (8 (3 a + b)) / 3 = 8 a + off[b] samples in and takes phase row phi[b] -- so the banded
-          // matrix-core kernel of the 48/125 shape serves it (round 6: k_ifr_poly3 took 0.147 ms per 2.1 M IF samples)
-          using SH = Poly4Shape<48, 128, 214>;
-          const auto af = poly4_afrag<SH>([&](int pp, int m) {
-            const int j = m - SH::off(pp); return j >= 0 && j < rs.TB ? fb[(size_t)phi[pp % 3] * rs.TB + j] : 0.f; });
-          if ((rc = upload(d_afrag, af.data(), af.size()))) return rc;
-          fe.b = StageB::poly4_am;
-          poly4_am_tile = 64 * 128 + SH::off(47) + rs.TB + 64;
-          HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly4<48, 128, 214>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
-        }
-        if (fe.b == StageB::poly3 && rs.LB == 48 && rs.MB == 125 && rs.TB == 210) {
-          using SH = Poly4Shape<48, 125, 210>;
-          const auto af = poly4_afrag<SH>([&](int pp, int m) {
-            const int j = m - off[pp]; return j >= 0 && j < rs.TB ? fb[(size_t)phi[pp] * rs.TB + j] : 0.f; });
-          if ((rc = upload(d_afrag, af.data(), af.size()))) return rc;
-          fe.b = StageB::poly4;
-          HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly4<48, 125, 210>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
-          // fused front end: the 10 MS/s shape (D = 10, NA = 103) with a symmetric stage-A filter, FM, cf32 input, no
-          // Fs/4 shift.  Without IF FIR and equaliser the discriminator reads the IF directly and is the kernel's
-          // epilogue; with either of them the epilogue stores the IF samples and the chain goes on as usual.
-          bool sym = rs.D == kFusedD && rs.NA == kFusedNA;
-          for (int k = 0; sym && k < rs.NA / 2; k++) sym = (fa[k] == fa[rs.NA - 1 - k]);
-          if (sym && mode == FMR_MODE_FM && in_fmt == 0 && !c->enable_fourth_down && !bank && !env.no_fused) {
-            if ((rc = upload(d_hB_last, fb.data() + (size_t)phi[47] * rs.TB, (size_t)rs.TB))) return rc;
-            { std::vector<unsigned short> fr((size_t)2 * 8 * 2 * 64 * 8);
-              fused_make_afragA<kFusedD, kFusedNA>(fa.data(), fr.data());
-              if ((rc = upload(d_fused_afragA, fr.data(), fr.size()))) return rc;
-              std::vector<unsigned short> frb((size_t)3 * 9 * 2 * 64 * 8);
-              fused_hB_inv_scale = fused_make_afragB(fb.data(), frb.data());
-              if ((rc = upload(d_fused_afragB, frb.data(), frb.size()))) return rc; }
-            constexpr int kL = FusedShape<kFusedD, kFusedNA>::LDS_BYTES;
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_fused<kFusedD, kFusedNA, 0, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, kL));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_fused<kFusedD, kFusedNA, 1, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, kL));
-            fe.fused = (!c->fmfilter_enable && c->multipath_stages == 0) ? FusedFe::disc : FusedFe::if_only;
-          }
-        }
-      }
-    }
-    if ((rc = d_in_halo.alloc((size_t)in_rows() * H_in))) return rc;
-    if ((rc = d_mid.alloc((size_t)S * (H_mid + max_mid)))) return rc;
-    if (bank && (rc = upload_bank(fa))) return rc;
-  } else {
-    max_if = max_in;
-  }
+    if ((rc = e->create(hipEventDisableTiming))) return rc;
+  return FMR_OK;
+}
+
+// IF resampler: the taps of both stages in every layout the chain's forms read, their LDS, the buffers up to the IF
+int fmr_chain::build_front_end() {
+  const std::vector<float> fa = to_float(rs.hA), fb = hB_rows(rs, hB_pitch);
   int rc;
-  if ((rc = d_in.alloc((size_t)in_rows() * max_in))) return rc;
-  ntaps = c->n_filter_coeff;
-  ssb_like = (mode == FMR_MODE_USB || mode == FMR_MODE_LSB || mode == FMR_MODE_CW || mode == FMR_MODE_WSPR);
-  const float *filter_src = c->filter_coeff;
-  if (ssb_like) {     // AmDecoder's own filters: m_ssbfilter for USB/LSB, m_cwfilter for CW/WSPR (AmDecode.cpp:36,40)
-    filter_src = (mode == FMR_MODE_USB || mode == FMR_MODE_LSB) ? k_jj1bdx_ssb_48khz_1500hz : k_jj1bdx_cw_48khz_500hz;
-    ntaps = 2049;
+  if ((rc = upload(d_hA, fa)) || (rc = upload(d_hB, fb))) return rc;
+  if (qa && (rc = upload(d_hpA, hpA_table(fa, rs.D, qa)))) return rc;
+  if (fe.decim16) {
+    using SH16 = Decim16Shape<10, 195>;
+    std::vector<unsigned short> fr((size_t)2 * SH16::NKT * 2 * 64 * 8);
+    decim16_make_afragA<10, 195>(fa.data(), fr.data());
+    if ((rc = upload(d_dec16_afrag, fr)) || (rc = set_dyn_lds(&k_ifr_decim16<10, 195, 0>, SH16::LDS_BYTES)) ||
+        (rc = set_dyn_lds(&k_ifr_decim16<10, 195, 1>, SH16::LDS_BYTES))) return rc;
   }
-  fir_enable = (mode == FMR_MODE_FM) ? (c->fmfilter_enable != 0) : (mode != FMR_MODE_NONE);
-  if (has_dec && (ntaps < 1 || !filter_src)) { set_err("filter_coeff missing"); return FMR_ERR_BAD_ARG; }
-  H_if = has_dec ? (ntaps > 1 ? ntaps - 1 : 1) : 1;
-  if ((rc = d_if.alloc((size_t)S * (H_if + max_if)))) return rc;
+  if ((rc = build_stage_b(fb))) return rc;
+  const bool fused = fe.fused != FusedFe::none;
+  if (fused && (rc = build_fused(fa, fb))) return rc;
+  if ((fused || fe.decim16) && (rc = d_zero16.alloc(4))) return rc;
+  if ((rc = alloc_all(d_in_halo, (size_t)in_rows() * H_in, d_mid, (size_t)S * (H_mid + max_mid)))) return rc;
+  if (bank) {
+    std::vector<float2> taps;
+    std::vector<ChanPhase> ph;
+    bank_tables(fa, cb_off, cb_F, rs.D, taps, ph);
+    if ((rc = upload(d_cb_taps, taps)) || (rc = upload(d_cb_ph, ph))) return rc;
+  }
+  return FMR_OK;
+}
+
+// stage B, whole-phase forms: the position tables every tiled form reads, the padded rows where poly3 fits, and the tap
+// fragments of the chain's matrix-core form
+int fmr_chain::build_stage_b(const std::vector<float> &fb) {
+  if (!poly2_ok) return FMR_OK;      // (poly_frac and poly read d_hB alone)
+  const StageBLayout l(rs);
+  int rc;
+  if ((rc = upload(d_bphi, l.phi)) || (rc = upload(d_boff, l.off)) || (rc = set_dyn_lds(&k_ifr_poly2<512>, 98304))) return rc;
+  if (poly3_ok && ((rc = upload(d_hBp, hBp_table(fb, rs))) || (rc = set_dyn_lds(&k_ifr_poly3<384, StageBLayout::Q3>, 98304)))) return rc;
+  auto tap = [&](int row, int j) { return j >= 0 && j < rs.TB ? fb[(size_t)row * rs.TB + j] : 0.f; };
+  if (fe.b == StageB::poly5h) {
+    if ((rc = upload(d_afrag5h, poly5h_afrag(fb, l, rs.TB, poly5h_nkb, poly5h_ea))) || (rc = set_dyn_lds(&k_ifr_poly5h<48, 125>, poly5h_lds)) ||
+        (rc = set_dyn_lds(&k_ifr_poly5h<48, 125, Poly5hDiscEpi>, poly5h_lds))) return rc;
+  } else if (fe.b == StageB::poly4_am) {
+    using SH = Poly4Shape<48, 128, 214>;
+    if ((rc = upload(d_afrag, poly4_afrag<SH>([&](int pp, int m) { return tap(l.phi[pp % 3], m - SH::off(pp)); }))) ||
+        (rc = set_dyn_lds(&k_ifr_poly4<48, 128, 214>, 98304))) return rc;
+  } else if (fe.b == StageB::poly4) {
+    using SH = Poly4Shape<48, 125, 210>;
+    if ((rc = upload(d_afrag, poly4_afrag<SH>([&](int pp, int m) { return tap(l.phi[pp], m - l.off[pp]); }))) ||
+        (rc = set_dyn_lds(&k_ifr_poly4<48, 125, 210>, 98304))) return rc;
+  }
+  return FMR_OK;
+}
+
+// fused front end (stage B is poly4's 48 / 125 / 210 here): both stages' taps as fp16 fragments, the tap row of position
+// 47, and per workgroup the fp32 copies of mid samples beyond fp16's range -- the one size that follows from the device
+int fmr_chain::build_fused(const std::vector<float> &fa, const std::vector<float> &fb) {
+  std::vector<unsigned short> fr((size_t)2 * 8 * 2 * 64 * 8), frb((size_t)3 * 9 * 2 * 64 * 8);
+  fused_make_afragA<kFusedD, kFusedNA>(fa.data(), fr.data());
+  fused_hB_inv_scale = fused_make_afragB(fb.data(), frb.data());
+  constexpr int kL = FusedShape<kFusedD, kFusedNA>::LDS_BYTES;
+  int rc;
+  if ((rc = upload(d_hB_last, fb.data() + (size_t)((47 * rs.MB) % rs.LB) * rs.TB, (size_t)rs.TB)) ||
+      (rc = upload(d_fused_afragA, fr)) || (rc = upload(d_fused_afragB, frb)) ||
+      (rc = set_dyn_lds(&k_ifr_fused<kFusedD, kFusedNA, 0, 0>, kL)) || (rc = set_dyn_lds(&k_ifr_fused<kFusedD, kFusedNA, 1, 0>, kL)) ||
+      (rc = d_fused_mid32.alloc((size_t)std::max(std::max(n_cu, S), 256) * 2 * FusedShape<kFusedD, kFusedNA>::MIDR))) return rc;
+  if (env.fe_stamps && (rc = d_fe_stamps.alloc(3 * (size_t)kMaxFusedWg * S + 2 * kStampCalls * 16))) return rc;
+  return FMR_OK;
+}
+
+// IF buffers (one per ring slot on a pipelined chain) and the IF filter: its taps, and its matrix-core form's fragments
+int fmr_chain::build_if_filter() {
+  int rc;
+  for (int q = 0; q < (pipelined ? kPipe : 1); q++)
+    if ((rc = (q ? d_if_pp[q] : d_if).alloc((size_t)S * (H_if + max_if)))) return rc;
   last_if = d_if.p;
-  host_prof = env.host_prof; debug_taps = env.debug_taps;
-  if (env.pll_rtol >= 0.0) pll_rtol = env.pll_rtol;
-  if (pipelined)
-    for (int q = 1; q < kPipe; q++)
-      if ((rc = d_if_pp[q].alloc((size_t)S * (H_if + max_if)))) return rc;
+  if (!has_dec) return FMR_OK;
+  if ((rc = upload(d_coeff, filter))) return rc;
+  if (fir_enable && (rc = d_fir.alloc((size_t)S * max_if))) return rc;
+  if (fe.fir == IfForm::poly4_disc) {      // FM -f: lags 1 .. 126, lag 0 and the discriminator in the epilogue (Poly4FirDiscEpi)
+    if ((rc = upload(d_afrag_fir_fm, fir_afrag<Poly4Shape<48, 48, 127>>(filter))) ||
+        (rc = set_dyn_lds(&k_ifr_poly4<48, 48, 127, 2, Poly4FirDiscEpi>, 98304))) return rc;
+  } else if (fe.fir == IfForm::poly4_finish) {      // AM / DSB / NBFM (round 6: k_fm_block2 took 0.139 ms per 2.1 M IF samples, a fifth of the AM step)
+    if (ntaps == 255) {
+      if ((rc = upload(d_afrag_fir, fir_afrag<Poly4Shape<48, 48, 255>>(filter))) || (rc = set_dyn_lds(&k_ifr_poly4<48, 48, 255, 1>, 98304))) return rc;
+    } else {
+      if ((rc = upload(d_afrag_fir, fir_afrag<Poly4Shape<48, 48, 127>>(filter))) || (rc = set_dyn_lds(&k_ifr_poly4<48, 48, 127, 2>, 98304))) return rc;
+    }
+  }
+  return FMR_OK;
+}
+
+// per-stream state, the call tables' slots, round flags; with a decoder the IF AGC, the discriminator's outputs, the
+// partial sums of the epilogues that leave block sums, and the per-block statistics
+int fmr_chain::build_stats() {
+  int rc;
   h_state.assign(S, StreamState{});
   for (auto &st : h_state) {
     st.agc_gain = 1.0f;
     st.pll_freq = (19000.0 / kFmRate) * 2.0 * M_PI;   // PilotPhaseLock.cpp:40
     st.af_gain = 1.0;
   }
-  if ((rc = upload(d_state, h_state.data(), h_state.size()))) return rc;
-  max_ck = std::max(max_if / (size_t)c_pll, std::min<size_t>(max_if, (size_t)kSmallCall) / (size_t)kCPllSmall) + (size_t)max_blocks + 2;
-  tab_ints = 5 * (size_t)max_blocks + 3 * max_ck + (size_t)max_blocks + 1 + kMaxFusedWg;   // tail: first block of each fused workgroup
-  if (int rch = h_tab_all.alloc(kTabSlots * tab_ints, hipHostMallocDefault)) return rch;
+  if ((rc = upload(d_state, h_state))) return rc;
+  if ((rc = h_tab_all.alloc(kTabSlots * tab_ints, hipHostMallocDefault))) return rc;
   // The marks are written by one-thread kernels and polled by the host while more work is queued behind them: COHERENT
   // (fine-grained) host memory, so that the store leaves the GPU when it is made.  With the default flags the line may sit
   // in the GPU's L2 until some later system-scope release writes it back, and a host that waits for a mark sees it
   // milliseconds late (measured: one process in two ran at 4-36 ms per step, in multiples of 3.55 ms).
-  if (int rch = h_marks.alloc(2, hipHostMallocCoherent)) return rch;
+  if ((rc = h_marks.alloc(2, hipHostMallocCoherent))) return rc;
   h_marks.p[0] = h_marks.p[1] = 0;
-  if ((rc = d_tab.alloc((size_t)kTabSlots * tab_ints))) return rc;
   h_flags.assign(S, IterFlags{});
-  if ((rc = d_flags.alloc((size_t)S))) return rc;
-  serial_mode = env.serial;
-  max_agc_nc = max_if / C_AGC + 2;
-  if (has_dec) {
-    if ((rc = d_agc_nodes.alloc((size_t)S * (max_agc_nc + 1)))) return rc;
-    if ((rc = d_agc_tick.alloc((size_t)S))) return rc;
-    if ((rc = d_af_tick.alloc((size_t)S))) return rc;
-    if ((rc = d_agc_G.alloc((size_t)S * max_agc_nc))) return rc;
-    if ((rc = d_agc_M.alloc((size_t)S * max_agc_nc))) return rc;
-  }
+  if ((rc = alloc_all(d_tab, (size_t)kTabSlots * tab_ints, d_flags, (size_t)S))) return rc;
   if (!has_dec) return FMR_OK;
-
-  if ((rc = upload(d_coeff, filter_src, (size_t)ntaps))) return rc;
-  h_coeff0 = filter_src[0];
-  if (fir_enable && (rc = d_fir.alloc((size_t)S * max_if))) return rc;
-  if (fir_enable && mode == FMR_MODE_FM && ntaps == 127 && c->multipath_stages == 0 && !env.no_fused && !env.serial) {
-    // FM -f: lags 1 .. 126 as the 48 / 48 shape of the banded matrix-core kernel (see the 48 kHz modes below), lag 0 and the
-    // discriminator in its epilogue (Poly4FirDiscEpi)
-    using SH = Poly4Shape<48, 48, 127>;
-    const auto af = poly4_afrag<SH>([&](int pp, int m) { const int j = m - SH::off(pp); return j >= 0 && j < 126 ? filter_src[126 - j] : 0.f; });
-    if ((rc = upload(d_afrag_fir_fm, af.data(), af.size()))) return rc;
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly4<48, 48, 127, 2, Poly4FirDiscEpi>), hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
-    fe.fir = IfForm::poly4_disc;
-  }
-  if (fir_enable && mode != FMR_MODE_FM && !ssb_like && (ntaps == 255 || ntaps == 127) && !env.no_fused && !env.serial) {
-    // AM / DSB / NBFM (255 or 127 taps): out[i] = sum_{j = 1 .. order} c[j] x[i - j] as the 1 : 1 "polyphase" shape 48 / 48 of the
-    // banded matrix-core kernel -- one phase, window start = output index; tap row h[j'] = c[order - j'] over x[i - order + j'],
-    // with the lag-0 tap (j' = order) left out: k_fir_finish adds it where the reference has it.  (Round 6: k_fm_block2 took
-    // 0.139 ms per 2.1 M IF samples, a fifth of the AM step.)
-    auto make = [&](auto sh_tag) {
-      using SH = decltype(sh_tag);
-      const int order = ntaps - 1;
-      const auto af = poly4_afrag<SH>([&](int pp, int m) { const int j = m - SH::off(pp); return j >= 0 && j < order ? filter_src[order - j] : 0.f; });
-      return upload(d_afrag_fir, af.data(), af.size());
-    };
-    if (ntaps == 255) {
-      if ((rc = make(Poly4Shape<48, 48, 255>{}))) return rc;
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly4<48, 48, 255, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
-    } else {
-      if ((rc = make(Poly4Shape<48, 48, 127>{}))) return rc;
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ifr_poly4<48, 48, 127, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
-    }
-    fe.fir = IfForm::poly4_finish;
-  }
-  if ((rc = d_gain.alloc((size_t)S * max_if))) return rc;
-  if ((rc = d_dec.alloc((size_t)S * max_if))) return rc;
-  const bool fused = fe.fused != FusedFe::none, tiled_epi = fe.poly5h_disc || fe.fir == IfForm::poly4_disc;   // (the epilogues that leave block sums)
-  if ((fused || tiled_epi) && (rc = d_fused_part.alloc((size_t)S * 3 * (max_if / 384 + 20)))) return rc;
+  const size_t SB = (size_t)S * max_blocks;
+  if ((rc = alloc_all(d_agc_nodes, (size_t)S * (max_agc_nc + 1), d_agc_tick, (size_t)S, d_af_tick, (size_t)S,
+                      d_agc_G, (size_t)S * max_agc_nc, d_agc_M, (size_t)S * max_agc_nc, d_gain, (size_t)S * max_if,
+                      d_dec, (size_t)S * max_if, d_if_rms_blk, SB, d_bb_mean_blk, SB, d_bb_rms_blk, SB, d_blk_ph, SB * 2,
+                      d_mpf_ok, SB, d_stereo_blk, SB))) return rc;
+  const bool tiled_epi = fe.poly5h_disc || fe.fir == IfForm::poly4_disc;
+  if ((fe.fused != FusedFe::none || tiled_epi) && (rc = d_fused_part.alloc((size_t)S * 3 * (max_if / 384 + 20)))) return rc;
   if (tiled_epi && (rc = d_run_ph.alloc((size_t)S * 2 * kMaxFusedWg))) return rc;
-  if (fused && (rc = d_fused_mid32.alloc((size_t)std::max(std::max(n_cu, S), 256) * 2 * FusedShape<kFusedD, kFusedNA>::MIDR))) return rc;
-  if (fused && (rc = d_zero16.alloc(4))) return rc;
-  if (fused && env.fe_stamps && (rc = d_fe_stamps.alloc(3 * (size_t)kMaxFusedWg * S + 2 * kStampCalls * 16))) return rc;
-  if ((rc = d_if_rms_blk.alloc((size_t)S * max_blocks))) return rc;
-  if ((rc = d_bb_mean_blk.alloc((size_t)S * max_blocks))) return rc;
-  if ((rc = d_bb_rms_blk.alloc((size_t)S * max_blocks))) return rc;
-  if ((rc = d_blk_ph.alloc((size_t)S * max_blocks * 2))) return rc;
-  if ((rc = d_mpf_ok.alloc((size_t)S * max_blocks))) return rc;
-  if ((rc = d_stereo_blk.alloc((size_t)S * max_blocks))) return rc;
-
-  if (mode == FMR_MODE_FM) {
-    stereo = c->stereo != 0;
-    pilot_shift = c->pilot_shift != 0;
-    enable_mpf = c->multipath_stages > 0;
-    agc_init = 1.0f; agc_max = 100000.0f; agc_rate = 0.0001f;          // FmDecode.cpp:74
-    disc_nf = (float)((75000.0 / kFmRate) * 2.0 * M_PI);                 // PhaseDiscriminator.cpp:28
-    disc_bound = (float)(1.0 / ((75000.0 / kFmRate) * 2.0));             // :30
-    const double freq = 19000.0 / kFmRate, bw = 30 / kFmRate;           // PilotPhaseLock.h:31-35
-    pllc.minfreq = (freq - bw) * 2.0 * M_PI;
-    pllc.maxfreq = (freq + bw) * 2.0 * M_PI;
-    pllc.bq_b0 = 1.46974784e-06; pllc.bq_a1 = -1.99682419; pllc.bq_a2 = 0.996825659;  // PilotPhaseLock.cpp:48
-    pllc.lf_b0 = 0.000304341788; pllc.lf_b1 = -0.000304324564;                          // :51
-    pllc.lock_delay = int(15.0 / bw);
-    pllc.pilot_frequency = 19000;
-    pllc.minsignal = 0.001;
-    const double de = c->deemphasis_us;
-    deemph = lowpass_rc((de == 0) ? 1.0 : (de * kFmRate * 1.0e-6));      // FmDecode.cpp:67-70
-    dcblock = highpass_iir(0.0001);                                       // FmDecode.cpp:62
-    {
-      double a16 = 1.0;
-      for (int i = 0; i < FMR_DE_LPL; i++) a16 *= -deemph.a1;             // A^LPL, A = -a1 = exp(-1/tau)
-      std::vector<double> apow(65);
-      apow[0] = 1.0;
-      for (int k = 1; k <= 64; k++) apow[k] = apow[k - 1] * a16;
-      double pwr = a16;
-      for (int j = 0; j < 7; j++) { de_scan.pw[j] = pwr; pwr *= pwr; }
-      if ((rc = upload(d_de_pow, apow.data(), apow.size()))) return rc;
-      de_scan.apow = d_de_pow.p;
-    }
-    {
-      // A = [[-a1, -a2], [1, 0]] acts on (w[n-1], w[n-2]); A^C by repeated multiplication
-      double a[4] = {-dcblock.a1, -dcblock.a2, 1.0, 0.0}, r[4] = {1, 0, 0, 1};
-      for (int i = 0; i < C_DC; i++) {
-        const double t[4] = {a[0] * r[0] + a[1] * r[2], a[0] * r[1] + a[1] * r[3], a[2] * r[0] + a[3] * r[2],
-                             a[2] * r[1] + a[3] * r[3]};
-        for (int j = 0; j < 4; j++) r[j] = t[j];
-      }
-      for (int j = 0; j < 4; j++) dc_ac[j] = r[j];
-      auto mul = [](const double *x, const double *y, double *z) {
-        const double t[4] = {x[0] * y[0] + x[1] * y[2], x[0] * y[1] + x[1] * y[3], x[2] * y[0] + x[3] * y[2],
-                             x[2] * y[1] + x[3] * y[3]};
-        for (int j = 0; j < 4; j++) z[j] = t[j];
-      };
-      double gk[4] = {1, 0, 0, 1};
-      for (int i = 0; i < FMR_DC_K; i++) mul(dc_ac, gk, gk);          // A^(C*K)
-      for (int lv = 0; lv < 6; lv++) {
-        for (int j = 0; j < 4; j++) dc_agp[lv][j] = gk[j];
-        mul(gk, gk, gk);
-      }
-    }
-    if (!ars.design(kFmRate, kPcmRate, kAudioAtten)) { set_err("audio resampler design failed"); return FMR_ERR_UNSUPPORTED; }
-    if (ars.D == 1) { ars.NA = 1; ars.hA.assign(1, 1.0); }
-    H_a = ars.NA - 1 + ars.D;
-    H_am = ars.TB;
-    n_pilotcut = 127;
-    H_pc = n_pilotcut - 1;
-    max_amid = max_if / ars.D + 2;
-    max_au = (size_t)((double)max_if * ars.L / ars.M) + 4;
-    if ((rc = upload(d_ahA, ars.hA.data(), ars.hA.size()))) return rc;
-    if ((rc = upload(d_ahB, ars.hB.data(), ars.hB.size()))) return rc;
-    if ((rc = upload(d_pilotcut, k_jj1bdx_48khz_fmaudio, (size_t)127))) return rc;   // FmDecode.cpp:48-49
-    float tab[257];
-    make_fast_atan_table(tab);
-    if ((rc = upload(d_atan, tab, (size_t)257))) return rc;
-    H_b = FMR_DE_WARMUP + H_a;           // warm-up of the fused de-emphasis reaches below the oldest stage-A tap
-    if ((rc = d_base.alloc((size_t)S * (H_b + max_if)))) return rc;
-    if ((rc = d_raw.alloc((size_t)S * (H_b + max_if)))) return rc;
-    if (pipelined)
-      for (int q = 1; q < kPipe; q++) {
-        if ((rc = d_base_pp[q].alloc((size_t)S * (H_b + max_if)))) return rc;
-        if ((rc = d_raw_pp[q].alloc((size_t)S * (H_b + max_if)))) return rc;
-        if ((fused || tiled_epi) && (rc = d_part_pp[q].alloc(d_fused_part.n))) return rc;
-        if ((rc = d_stereo_pp[q].alloc((size_t)S * max_blocks))) return rc;
-      }
-    if ((rc = d_base_de.alloc((size_t)S * (H_a + max_if)))) return rc;
-    if ((rc = d_raw_de.alloc((size_t)S * (H_a + max_if)))) return rc;
-    if ((rc = d_pll_nodes.alloc((size_t)S * (max_ck + 1) * 7))) return rc;
-    if ((rc = d_pll_G.alloc((size_t)S * max_ck * 9))) return rc;
-    if ((rc = d_pll_M.alloc((size_t)S * max_ck * 49))) return rc;
-    if ((rc = d_ck_wraps.alloc((size_t)S * max_ck * (pipelined ? 2 : 1)))) return rc;      // (pipelined chain: two copies, see walk_par)
-    ck_copy = (size_t)S * max_ck;
-    if ((rc = d_walk_go.alloc((size_t)S * 2))) return rc;
-    {
-      const size_t max_grp = max_ck / FMR_NODE_GRP + 2;
-      if ((rc = d_pll_PQ.alloc((size_t)S * max_grp * 56))) return rc;
-      if ((rc = d_pll_dstart.alloc((size_t)S * max_grp * 7))) return rc;
-      if ((rc = d_pll_gres.alloc((size_t)S * max_grp * 8))) return rc;
-      if ((rc = d_pll_wgr.alloc((size_t)S * (max_ck / 64 + 2) * 8))) return rc;      // (x 8: room for the FMR_PLL_TRACE records)
-      const size_t max_grp2 = max_grp / FMR_NODE_GRP2 + 2;
-      if ((rc = d_pll_PQ2.alloc((size_t)S * max_grp2 * 56))) return rc;
-      if ((rc = d_pll_dstart2.alloc((size_t)S * max_grp2 * 7))) return rc;
-      if ((rc = d_pll_pre.alloc((size_t)S * max_grp * 56))) return rc;
-      if ((rc = d_pll_wfirst.alloc((size_t)S * (max_ck / 64 + 2) * 7))) return rc;
-      if ((rc = d_pll_sync.alloc((size_t)S))) return rc;               // zeroed here; the kernels leave it zeroed
-      if ((rc = d_pll_tick2.alloc((size_t)S * max_grp2))) return rc;
-      pll_tick2_per_stream = (int)max_grp2;
-    }
-    mask_words = (std::max(c_pll, 128) + 63) / 64;   // wrap bit masks: one word per 64 samples of a chunk
-    if ((rc = d_ck_mask.alloc((size_t)S * max_ck * mask_words * (pipelined ? 2 : 1)))) return rc;
-    if ((rc = d_blk_wraps.alloc((size_t)S * max_blocks))) return rc;
-    if ((rc = d_blk_level.alloc((size_t)S * max_blocks))) return rc;
-    max_dc_nc = max_au / C_DC + 2;
-    if ((rc = d_dc_G.alloc((size_t)S * 2 * max_dc_nc * 2))) return rc;
-    if ((rc = d_dc_start.alloc((size_t)S * 2 * max_dc_nc * 2))) return rc;
-    if ((rc = d_am0.alloc((size_t)S * (H_am + max_amid)))) return rc;
-    if ((rc = d_am1.alloc((size_t)S * (H_am + max_amid)))) return rc;
-    if ((rc = d_a10.alloc((size_t)S * (H_pc + max_au)))) return rc;
-    if ((rc = d_a11.alloc((size_t)S * (H_pc + max_au)))) return rc;
-    if ((rc = d_pc0.alloc((size_t)S * max_au))) return rc;
-    if ((rc = d_pc1.alloc((size_t)S * max_au))) return rc;
-    if ((rc = d_audio.alloc((size_t)S * 2 * max_au))) return rc;
-    // MultipathFilter(m_enable ? stages : 1)  (FmDecode.cpp:79)
-    const unsigned stages = enable_mpf ? c->multipath_stages : 1;
-    mpf_N = (int)(stages * 4 + 1);
-    mpf_ref = (int)(stages * 3 + 1);
-    std::vector<float2> cf((size_t)S * mpf_N, make_float2(0.f, 0.f));
-    for (int s = 0; s < S; s++) cf[(size_t)s * mpf_N + mpf_ref] = make_float2(1.f, 0.f);
-    if ((rc = upload(d_mpf_coeff, cf.data(), cf.size()))) return rc;
-    if ((rc = d_mpf_state.alloc((size_t)S * mpf_N))) return rc;
-    if (enable_mpf && (rc = d_mpf.alloc((size_t)S * max_if))) return rc;
-    if (enable_mpf && (rc = d_agc_progress.alloc((size_t)S))) return rc;
-  } else if (mode == FMR_MODE_NBFM) {
-    nbfm_freq_dev = (c->nbfm_freq_dev > 0) ? c->nbfm_freq_dev : 8000.0;  // NbfmDecode.h:39 freq_dev_normal
-    agc_init = 1.0f; agc_max = 100000.0f; agc_rate = 0.0001f;           // NbfmDecode.cpp:43
-    disc_nf = (float)((nbfm_freq_dev / kAmRate) * 2.0 * M_PI);           // NbfmDecode.cpp:35, PhaseDiscriminator.cpp:28
-    disc_bound = (float)(1.0 / ((nbfm_freq_dev / kAmRate) * 2.0));
-    n_pilotcut = 63;                                                      // jj1bdx_48khz_nbfmaudio, NbfmDecode.cpp:39
-    H_b = n_pilotcut - 1;
-    max_au = max_if;
-    if ((rc = upload(d_pilotcut, k_jj1bdx_48khz_nbfmaudio, (size_t)n_pilotcut))) return rc;
-    if ((rc = d_base.alloc((size_t)S * (H_b + max_if)))) return rc;
-    if ((rc = d_audio.alloc((size_t)S * max_au))) return rc;
-  } else {
-    const bool cw_like = (mode == FMR_MODE_CW || mode == FMR_MODE_WSPR);
-    agc_init = 1.0f; agc_max = 1000000.0f; agc_rate = cw_like ? 0.0006f : 0.0003f;   // AmDecode.cpp:71-77
-    af_ref = ssb_like ? 0.24 : 0.6;                                       // AmDecode.cpp:54-66
-    af_rate = cw_like ? 0.00125 : 0.001;
-    if (ssb_like) {
-      // FineTuner(table_size 480 = 48000/100, freq_shift) tables: FineTuner.cpp:25-52 with m_index = 0, phase offset 0
-      auto table = [](int freq_shift) {
-        const int ts = 480;
-        std::vector<float2> t((size_t)ts);
-        const double phase_step = 2.0 * M_PI / double(ts);
-        for (int i = 0; i < ts; i++) {
-          const double phi = (double)(((int64_t)freq_shift * i) % ts) * phase_step;
-          t[(size_t)i] = make_float2((float)std::cos(phi), (float)std::sin(phi));
-        }
-        return t;
-      };
-      const auto up = table(15), down = table(-15), cw = table(5);       // AmDecode.cpp:83-90
-      switch (mode) {
-      case FMR_MODE_USB: rc = upload(d_ft_pre, down.data(), down.size()); if (!rc) rc = upload(d_ft_post, up.data(), up.size()); break;
-      case FMR_MODE_LSB: rc = upload(d_ft_pre, up.data(), up.size()); if (!rc) rc = upload(d_ft_post, down.data(), down.size()); break;
-      case FMR_MODE_CW: rc = upload(d_ft_post, cw.data(), cw.size()); break;
-      default: rc = upload(d_ft_pre, down.data(), down.size()); if (!rc) rc = upload(d_ft_post, up.data(), up.size()); break;   // WSPR
-      }
-      if (rc) return rc;
-    }
-    am_dcblock = highpass_iir(60 / kAmRate);                              // AmDecode.cpp:45
-    am_deemph = lowpass_rc(100 * kPcmRate * 1.0e-6);                      // AmDecode.cpp:49
-    max_au = max_if;
-    if ((rc = d_base.alloc((size_t)S * max_if))) return rc;
-    if ((rc = d_audio.alloc((size_t)S * max_au))) return rc;
-    {
-      // time-parallel audio tail: DC-block transition matrices over one chunk and over the node scan's lane groups
-      const size_t nc = max_if / C_AM + 2;
-      if ((rc = d_dc_G.alloc((size_t)S * 2 * nc * 2))) return rc;
-      if ((rc = d_dc_start.alloc((size_t)S * 2 * nc * 2))) return rc;
-      if ((rc = d_af_nodes.alloc((size_t)S * (nc + 1)))) return rc;
-      if ((rc = d_af_G.alloc((size_t)S * nc))) return rc;
-      if ((rc = d_af_M.alloc((size_t)S * nc))) return rc;
-      if ((rc = d_af_out.alloc((size_t)S * max_if))) return rc;
-      am_dk.b0 = am_dcblock.b0; am_dk.b1 = am_dcblock.b1; am_dk.b2 = am_dcblock.b2; am_dk.a1 = am_dcblock.a1; am_dk.a2 = am_dcblock.a2;
-      auto mul = [](const double *x, const double *y, double *z) {
-        const double t[4] = {x[0] * y[0] + x[1] * y[2], x[0] * y[1] + x[1] * y[3], x[2] * y[0] + x[3] * y[2],
-                             x[2] * y[1] + x[3] * y[3]};
-        for (int j = 0; j < 4; j++) z[j] = t[j];
-      };
-      const double a[4] = {-am_dcblock.a1, -am_dcblock.a2, 1.0, 0.0};
-      double r[4] = {1, 0, 0, 1};
-      for (int i = 0; i < C_AM; i++) mul(a, r, r);
-      for (int j = 0; j < 4; j++) am_dk.ac[j] = r[j];
-      double gk[4] = {1, 0, 0, 1};
-      for (int i = 0; i < FMR_DC_K; i++) mul(am_dk.ac, gk, gk);
-      for (int lv = 0; lv < 6; lv++) { for (int j = 0; j < 4; j++) am_dk.agp[lv][j] = gk[j]; mul(gk, gk, gk); }
-    }
-  }
   return FMR_OK;
 }
 
-// ---- channel bank (fmr_config.channel_offset_hz; DESIGN.md "Channel bank") ----
-// The rules of a bank, checked before the device is opened.  Stage-A shapes in the kernel's range: D = 2 .. 24 (the LDS
-// span of 64 outputs stays under 60 KB) and NA <= 400 (the taps of a group of channels stay in the scalar cache's reach).
-// A channelizer (fmr_create_channelizer) is a bank without a decoder: the same rules, with output_rate as the target
-// rate where a decoder bank has its decoder's rate.
-constexpr int kBankMaxD = 24, kBankMaxNA = 400;
-int fmr_chain::check_bank(const fmr_config *c, bool channelizer) {
-  if (channelizer) {
-    if (c->mode != FMR_MODE_NONE || !c->enable_resampler) {
-      set_err("channelizer: needs a front-end-only chain with the IF resampler (mode = -1, enable_resampler = 1); "
-              "a decoder bank is fmr_create with channel_offset_hz");
-      return FMR_ERR_UNSUPPORTED;
-    }
-    if (!c->channel_offset_hz) {
-      set_err("channelizer: channel_offset_hz is NULL (it needs n_streams offsets, one per channel)");
-      return FMR_ERR_BAD_ARG;
-    }
-  } else if (c->mode == FMR_MODE_NONE || !c->enable_resampler) {
-    set_err("channel bank: needs a decoder chain with the IF resampler (enable_resampler = 1, mode != -1)");
-    return FMR_ERR_UNSUPPORTED;
+// FM: the ring slots behind the discriminator, the pilot PLL's multiple-shooting buffers, the audio tail, the equaliser
+int fmr_chain::build_fm() {
+  int rc;
+  float atan_tab[257];
+  make_fast_atan_table(atan_tab);
+  if ((rc = upload(d_de_pow, deemph_powers(deemph))) || (rc = upload(d_ahA, ars.hA)) || (rc = upload(d_ahB, ars.hB)) ||
+      (rc = upload(d_pilotcut, k_jj1bdx_48khz_fmaudio, (size_t)n_pilotcut)) ||   // FmDecode.cpp:48-49
+      (rc = upload(d_atan, atan_tab, (size_t)257))) return rc;
+  de_scan.apow = d_de_pow.p;
+  const size_t SB = (size_t)S * max_blocks, mpx = (size_t)S * (H_b + max_if);
+  for (int q = 0; q < (pipelined ? kPipe : 1); q++) {
+    if ((rc = alloc_all(q ? d_base_pp[q] : d_base, mpx, q ? d_raw_pp[q] : d_raw, mpx))) return rc;
+    if (q && d_fused_part.p && (rc = d_part_pp[q].alloc(d_fused_part.n))) return rc;
+    if (q && (rc = d_stereo_pp[q].alloc(SB))) return rc;
   }
-  const char *const who = channelizer ? "channelizer" : "channel bank";
-  if (c->input_format != FMR_IQ_CF32) {
-    set_err("%s: input_format must be FMR_IQ_CF32 (convert raw samples on the host)", who);
-    return FMR_ERR_UNSUPPORTED;
-  }
-  if (c->enable_fourth_down) {
-    set_err("%s: enable_fourth_down must be 0 (add input_rate / 4 to the offsets instead)", who);
-    return FMR_ERR_BAD_ARG;
-  }
-  const double F = c->input_rate;
-  if (!(F >= 1.0 && F < 4294967296.0) || F != std::floor(F)) {
-    set_err("%s: input_rate %.6f is not a whole number of hertz (ppm-corrected rates are not supported)", who, F);
-    return FMR_ERR_UNSUPPORTED;
-  }
-  // the rate stage B delivers: the decoder's, or a channelizer's output_rate (0: the FM IF rate, as for any front-end-only chain)
-  const double dec_rate = channelizer ? (c->output_rate > 0 ? c->output_rate : kFmRate)
-                                      : c->mode == FMR_MODE_FM ? kFmRate : kAmRate;
-  const char *const rate_name = channelizer ? "output_rate" : "decoder rate";
-  for (int s = 0; s < c->n_streams; s++) {
-    const double f = (double)c->channel_offset_hz[s];
-    if (std::fabs(f) > 0.5 * (F - dec_rate)) {
-      set_err("%s: |channel_offset_hz[%d]| = %.0f Hz exceeds (input_rate - %s) / 2 = %.0f Hz", who, s,
-              std::fabs(f), rate_name, 0.5 * (F - dec_rate));
-      return FMR_ERR_BAD_ARG;
-    }
-  }
-  if (c->resampler_class != FMR_RESAMPLER_FAST && c->resampler_class != FMR_RESAMPLER_R8B) return FMR_OK;   // (init refuses it)
-  ResamplerDesign d;
-  const bool ok = c->resampler_class == FMR_RESAMPLER_R8B ? d.design(F, dec_rate, kR8bAtten, kR8bPassFrac, true)
-                                                          : d.design(F, dec_rate, kIfAtten);
-  if (!ok) return FMR_OK;     // (init refuses the ratio)
-  if (d.D < 2 || d.D > kBankMaxD || d.NA > kBankMaxNA) {
-    set_err("%s: stage-A shape D = %d, NA = %d (%.0f -> %.0f Hz) is outside the bank kernel's range "
-            "(D = 2 .. %d, NA <= %d)", who, d.D, d.D == 1 ? 1 : d.NA, F, dec_rate, kBankMaxD, kBankMaxNA);
-    return FMR_ERR_UNSUPPORTED;
-  }
+  const size_t copies = pipelined ? 2 : 1;      // (pipelined chain: two copies of the wrap counts and masks, see walk_par)
+  const size_t max_grp = max_ck / FMR_NODE_GRP + 2, max_grp2 = (size_t)pll_tick2_per_stream, waves = max_ck / 64 + 2;
+  if ((rc = alloc_all(d_base_de, (size_t)S * (H_a + max_if), d_raw_de, (size_t)S * (H_a + max_if),
+                      d_pll_nodes, (size_t)S * (max_ck + 1) * 7, d_pll_G, (size_t)S * max_ck * 9, d_pll_M, (size_t)S * max_ck * 49,
+                      d_ck_wraps, ck_copy * copies, d_walk_go, (size_t)S * 2,
+                      d_pll_PQ, (size_t)S * max_grp * 56, d_pll_dstart, (size_t)S * max_grp * 7, d_pll_gres, (size_t)S * max_grp * 8,
+                      d_pll_wgr, (size_t)S * waves * 8,      // (x 8: room for the FMR_PLL_TRACE records)
+                      d_pll_PQ2, (size_t)S * max_grp2 * 56, d_pll_dstart2, (size_t)S * max_grp2 * 7, d_pll_pre, (size_t)S * max_grp * 56,
+                      d_pll_wfirst, (size_t)S * waves * 7, d_pll_sync, (size_t)S,      // (zeroed here; the kernels leave it zeroed)
+                      d_pll_tick2, (size_t)S * max_grp2, d_ck_mask, ck_copy * mask_words * copies,
+                      d_blk_wraps, SB, d_blk_level, SB))) return rc;
+  const size_t dc = (size_t)S * 2 * max_dc_nc * 2;
+  if ((rc = alloc_all(d_dc_G, dc, d_dc_start, dc, d_am0, (size_t)S * (H_am + max_amid), d_am1, (size_t)S * (H_am + max_amid),
+                      d_a10, (size_t)S * (H_pc + max_au), d_a11, (size_t)S * (H_pc + max_au), d_pc0, (size_t)S * max_au,
+                      d_pc1, (size_t)S * max_au, d_audio, (size_t)S * 2 * max_au))) return rc;
+  // MultipathFilter: the reference tap at one, the rest at zero
+  std::vector<float2> cf((size_t)S * mpf_N, make_float2(0.f, 0.f));
+  for (int s = 0; s < S; s++) cf[(size_t)s * mpf_N + mpf_ref] = make_float2(1.f, 0.f);
+  if ((rc = upload(d_mpf_coeff, cf)) || (rc = d_mpf_state.alloc((size_t)S * mpf_N))) return rc;
+  if (enable_mpf && (rc = alloc_all(d_mpf, (size_t)S * max_if, d_agc_progress, (size_t)S))) return rc;
   return FMR_OK;
 }
 
-// c_s[k] = hA[k] exp(+2 pi i ((f_s k) mod F) / F) in double, rounded once; [group][k][g], channels beyond S are zero
-int fmr_chain::upload_bank(const std::vector<float> &fa) {
-  const int G = FMR_CB_G, ng = (S + G - 1) / G, NA = rs.NA;
-  const unsigned long long F = cb_F;
-  std::vector<float2> taps((size_t)ng * NA * G, make_float2(0.f, 0.f));
-  std::vector<ChanPhase> ph((size_t)S);
-  for (int s = 0; s < S; s++) {
-    const long long fl = cb_off[s];
-    const unsigned long long fm = (unsigned long long)(((fl % (long long)F) + (long long)F) % (long long)F);
-    ph[s] = ChanPhase{fm, (fm * (unsigned long long)rs.D) % F};
-    for (int k = 0; k < NA; k++) {
-      const double a = 2.0 * M_PI * (double)((fm * (unsigned long long)k) % F) / (double)F;
-      const double h = (double)fa[k];
-      taps[((size_t)(s / G) * NA + k) * G + (s % G)] = make_float2((float)(h * std::cos(a)), (float)(h * std::sin(a)));
-    }
+int fmr_chain::build_nbfm() {
+  int rc;
+  if ((rc = upload(d_pilotcut, k_jj1bdx_48khz_nbfmaudio, (size_t)n_pilotcut))) return rc;
+  return alloc_all(d_base, (size_t)S * (H_b + max_if), d_audio, (size_t)S * max_au);
+}
+
+// AM family: the SSB modes' mixers, and the time-parallel audio tail (DC block and audio AGC in chunks of C_AM)
+int fmr_chain::build_am() {
+  int rc;
+  if (ssb_like) {      // AmDecode.cpp:83-90: USB / WSPR mix down 1500 Hz in front of the filter and up behind it, LSB the other way, CW up 500 Hz behind it
+    const int pre = mode == FMR_MODE_LSB ? 15 : mode == FMR_MODE_CW ? 0 : -15, post = mode == FMR_MODE_LSB ? -15 : mode == FMR_MODE_CW ? 5 : 15;
+    if (pre && (rc = upload(d_ft_pre, finetuner_table(pre)))) return rc;
+    if ((rc = upload(d_ft_post, finetuner_table(post)))) return rc;
   }
-  if (int rc = upload(d_cb_taps, taps.data(), taps.size())) return rc;
-  if (int rc = upload(d_cb_ph, ph.data(), ph.size())) return rc;
-  return FMR_OK;
+  const size_t nc = max_if / C_AM + 2;
+  return alloc_all(d_base, (size_t)S * max_if, d_audio, (size_t)S * max_au, d_dc_G, (size_t)S * 2 * nc * 2,
+                   d_dc_start, (size_t)S * 2 * nc * 2, d_af_nodes, (size_t)S * (nc + 1), d_af_G, (size_t)S * nc,
+                   d_af_M, (size_t)S * nc, d_af_out, (size_t)S * max_if);
 }
 
 // stage A of every channel for count_mid outputs from mA_prev on (k_ifr_chan)
@@ -1626,7 +1275,7 @@ int fmr_chain::run(const float2 *d_iq, size_t stride, const uint32_t *block_len,
   struct HostProf {
     fmr_chain *c; const std::chrono::steady_clock::time_point &t0, &t1, &t2;
     ~HostProf() {
-      if (!c->host_prof) return;
+      if (!c->env.host_prof) return;
       const auto t3 = std::chrono::steady_clock::now();
       c->hp_fe += std::chrono::duration<double, std::micro>(t1 - t0).count();
       c->hp_tab += std::chrono::duration<double, std::micro>(t2 - t1).count();
@@ -1671,7 +1320,7 @@ static constexpr unsigned kFeBitA[] = {0, 0, 0, FMR_FE_FUSED, FMR_FE_DECIM16, FM
 static constexpr unsigned kFeBitB[] = {0, FMR_FE_FUSED, FMR_FE_POLY5H_DISC, FMR_FE_POLY5H, FMR_FE_POLY4_AM, FMR_FE_POLY4,
                                        FMR_FE_POLY3, FMR_FE_POLY2, FMR_FE_POLY_FRAC, FMR_FE_POLY};
 
-// The kernel forms of one call, from its IF block lengths, the input's alignment and the forms init() allowed.  Fills the
+// The kernel forms of one call, from its IF block lengths, the input's alignment and the forms plan_create() allowed.  Fills the
 // IF block table and nothing else: a call refused here leaves the chain as it found it.
 int fmr_chain::plan_call(CallCtx &k) {
   CallPlan &p = k.plan;
@@ -1690,7 +1339,7 @@ int fmr_chain::plan_call(CallCtx &k) {
   }
   const long long N_if = k.N_if;
   p.count_mid = (int)(p.next.mA - p.prev.mA);
-  const bool tiled = has_dec && !serial_mode && !short_blk;
+  const bool tiled = has_dec && !env.serial && !short_blk;
   // Pipelined chain: the front end leaves one CU of every XCD free.  A workgroup is dispatched inside the XCD its index
   // maps to, and the kernels that run beside the front end -- lock logic (32 KB of LDS), the DC block's node pass (213
   // VGPRs), the spare PLL rounds -- do not fit beside a 152 KB workgroup: on an XCD the front end fills they wait for
@@ -1702,12 +1351,12 @@ int fmr_chain::plan_call(CallCtx &k) {
   p.c_call = (p.small && env.x_cpll == 0) ? kCPllSmall : c_pll;
   p.agc_iters = (mode == FMR_MODE_FM && p.small) ? 3 : K_AGC_ITERS;     // one spare round instead of two to four; if that is not
   p.pll_iters = p.small ? 3 : K_PLL_ITERS;                              // enough the serial kernel runs over these few thousand samples
-  p.iter_on_side = mode == FMR_MODE_FM && !serial_mode && !enable_mpf;
-  p.agc = (enable_mpf && !serial_mode && mode == FMR_MODE_FM) ? AgcPlace::beside_mpf
-        : (serial_mode || enable_mpf) ? AgcPlace::serial
+  p.iter_on_side = mode == FMR_MODE_FM && !env.serial && !enable_mpf;
+  p.agc = (enable_mpf && !env.serial && mode == FMR_MODE_FM) ? AgcPlace::beside_mpf
+        : (env.serial || enable_mpf) ? AgcPlace::serial
         : mode != FMR_MODE_FM ? AgcPlace::in_line
         : stereo ? AgcPlace::aside_after_pll : AgcPlace::aside;
-  p.walk_late = pipelined && !env.pll_v1 && !serial_mode;
+  p.walk_late = pipelined && !env.pll_v1 && !env.serial;
   // Pipelined chain, streams of few blocks: the PLL passes after the second -- which a call in lock does not need, and which
   // then cost five launches that read a flag and leave, ~25 us between this call's accepted pass and the next call's front
   // end -- go to the side stream, in front of the lock logic that waits for them anyway (32 streams x 64 blocks: 0.503 ->
@@ -1765,11 +1414,11 @@ int fmr_chain::plan_call(CallCtx &k) {
       }
     }
   }
-  if (has_dec && !(mode == FMR_MODE_FM && !fir_enable && !serial_mode)) {
+  if (has_dec && !(mode == FMR_MODE_FM && !fir_enable && !env.serial)) {
     // (FM without the IF FIR: the block RMS is taken inside the discriminator kernel, IfForm::none)
     p.TL = std::min(1024, tl);
     p.lds_fb = sizeof(float2) * (4 * (size_t)fm_block3_plane(ntaps - 1, p.TL) + ((size_t)ntaps + 4) / 2 + (size_t)(ntaps - 1) + p.TL);
-    const bool blocked = fir_enable && ntaps >= 2 && p.lds_fb <= 60000 && !serial_mode;
+    const bool blocked = fir_enable && ntaps >= 2 && p.lds_fb <= 60000 && !env.serial;
     if (blocked && mode == FMR_MODE_FM && !enable_mpf)
       p.fir = (fe.fir == IfForm::poly4_disc && tiled && N_if >= 3072) ? IfForm::poly4_disc : IfForm::block3_disc;
     else if (blocked && mode == FMR_MODE_FM) p.fir = IfForm::block3;
@@ -1814,7 +1463,7 @@ int fmr_chain::run_front_end(CallCtx &k) {
     }
     k.ifbuf = if_slot(k.par);
     last_if = k.ifbuf;
-    dec_valid = !p.b_disc || debug_taps;   // the float copy of the discriminator output is a debug tap of the fused kernel
+    dec_valid = !p.b_disc || env.debug_taps;   // the float copy of the discriminator output is a debug tap of the fused kernel
     if_valid = dec_valid;                  // ... and so are the IF samples behind its discriminator epilogue (the slot holds |x|^2 then)
     const long long top0 = (long long)rs.D * mA_prev + rs.ca() - p.prev.n_in;
     if (p.a == StageA::bank) {
@@ -2117,7 +1766,7 @@ int fmr_chain::run_tables(CallCtx &k) {
   if (mode == FMR_MODE_FM && k.nck > 0) {
     hipLaunchKernelGGL(k_chunk_tab, dim3(nb), dim3(64), 0, side, d_tab_slot, d_tab_slot + max_blocks, d_first, p.c_call,
                        d_ck, d_ck + max_ck, d_ck + 2 * max_ck);
-    if (stereo && !serial_mode)
+    if (stereo && !env.serial)
       timed_on(side, "pll_begin", [&] {
         hipLaunchKernelGGL(k_pll_begin, dim3((k.nck + 1 + 63) / 64, S), dim3(64), 0, side, d_pll_nodes.p, k.ct, d_state.p,
                            pllc);
@@ -2173,7 +1822,7 @@ int fmr_chain::run_tables(CallCtx &k) {
     a.afragB = reinterpret_cast<const uint4 *>(d_fused_afragB.p); a.hB_inv_scale = fused_hB_inv_scale; a.n_if = (int)N_if;
     a.out = k.ifbuf; a.out_stride = k.if_stride; a.out_off = H_if;
     k.nrm = nullptr;
-    if (p.b_disc && !debug_taps) {
+    if (p.b_disc && !env.debug_taps) {
       // nobody but the AGC's state solve reads the IF behind the discriminator epilogue: it gets |x|^2 (4 B per sample, in the
       // IF slot's memory) and the IF samples stay on chip
       a.out = nullptr;
@@ -2188,7 +1837,7 @@ int fmr_chain::run_tables(CallCtx &k) {
     a.zero16 = reinterpret_cast<const float2 *>(d_zero16.p);
     a.base = p.b_disc ? k.base : nullptr;        // null: IF samples only (an IF FIR or the equaliser comes first)
     a.base_stride = H_b + (long long)max_if; a.base_off = H_b;
-    a.dec = debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
+    a.dec = env.debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
     a.nf = disc_nf; a.bound = disc_bound;
     a.st = d_state.p; a.hB_last = d_hB_last.p; a.part = k.part;
     a.if_off = k.bt.if_off; a.if_len = k.bt.if_len; a.nb = nb;
@@ -2216,10 +1865,10 @@ int fmr_chain::run_tables(CallCtx &k) {
     a.n_if = (int)N_if; a.kb_ref = k.fused_kb_ref;
     a.out = nullptr; a.out_stride = k.if_stride; a.out_off = H_if;
     a.nrm = reinterpret_cast<float *>(k.ifbuf); a.nrm_stride = 2 * k.if_stride; a.nrm_off = 0;
-    if (debug_taps) { a.out = k.ifbuf; a.nrm = nullptr; }      // the IF samples themselves (fmr_debug_read 0); the AGC reads them then
+    if (env.debug_taps) { a.out = k.ifbuf; a.nrm = nullptr; }      // the IF samples themselves (fmr_debug_read 0); the AGC reads them then
     k.nrm = a.nrm; k.nrm_stride = a.nrm_stride;
     a.base = k.base; a.base_stride = H_b + (long long)max_if; a.base_off = H_b;
-    a.dec = debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
+    a.dec = env.debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
     a.nf = disc_nf; a.bound = disc_bound;
     a.st = d_state.p; a.part = k.part; a.n_tiles = k.fused_n_tiles; a.part_from = p.part_from;
     a.if_off = k.bt.if_off; a.if_len = k.bt.if_len; a.nb = nb;
@@ -2279,7 +1928,7 @@ int fmr_chain::run_if_stage(CallCtx &k) {
     a.n_if = (int)N_if; a.kb_ref = 0;
     a.out = d_fir.p; a.out_stride = (long long)max_if; a.out_off = 0;
     a.base = k.base; a.base_stride = H_b + (long long)max_if; a.base_off = H_b;
-    a.dec = debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
+    a.dec = env.debug_taps ? d_dec.p : nullptr; a.dec_stride = (long long)max_if;
     a.nf = disc_nf; a.bound = disc_bound;
     const TileRuns &r = p.fir_runs;
     a.st = d_state.p; a.part = k.part; a.n_tiles = 8 * r.tiles; a.part_from = p.part_from;
@@ -2353,7 +2002,7 @@ int fmr_chain::run_if_stage(CallCtx &k) {
   k.agc_on_side = false; k.agc_deferred = false; agc_beside_mpf = false;
   if (!p.iter_on_side)
     hipLaunchKernelGGL(k_iter_begin, dim3(S), dim3(256), 0, stream, d_flags.p,
-                       (serial_mode || enable_mpf) ? (float *)nullptr : d_agc_nodes.p,
+                       (env.serial || enable_mpf) ? (float *)nullptr : d_agc_nodes.p,
                        p.agc_nc, d_state.p, S, (unsigned long long *)d_pll_sync.p, (int)(sizeof(PllSync) / 8), d_pll_tick2.p,
                        pll_tick2_per_stream, d_agc_tick.p);
   switch (p.agc) {
@@ -2394,7 +2043,7 @@ int fmr_chain::run_if_stage(CallCtx &k) {
     j.N_if = N_if; j.nc = p.agc_nc; j.iters = p.agc_iters;
     // the discriminator does not see the gains then -- the recurrence is solved for its state only, and its 4 bytes per IF
     // sample stay out of HBM unless the debug tap asks for them
-    j.gain_out = (j.aside && !debug_taps) ? (float *)nullptr : d_gain.p;
+    j.gain_out = (j.aside && !env.debug_taps) ? (float *)nullptr : d_gain.p;
     j.ginv = (mode == FMR_MODE_FM || mode == FMR_MODE_NBFM) ? (j.gain_out ? 1 : 2) : -env.x_amtol;
     if (j.aside) { k.disc_gain = nullptr; k.agc_on_side = true; }
     gain_valid = j.gain_out != nullptr;
@@ -2449,7 +2098,7 @@ int fmr_chain::run_fm_pll(CallCtx &k, TailCtx &t) {
   const ChunkTab &ct = k.ct; const BlockTab &bt = k.bt;
   const long long base_stride = H_b + (long long)max_if;
   const bool split_mono = t.can_split && !pipelined;      // the mono channel of the audio tail beside the PLL, on side2
-  if (serial_mode) {
+  if (env.serial) {
     timed("pll", [&] {
       hipLaunchKernelGGL(k_pll, dim3((S + 63) / 64), dim3(64), 0, stream, k.base, base_stride, H_b, bt, k.raw,
                          base_stride, H_b, d_atan.p, pllc, (int)pilot_shift, k.stereo_blk, d_state.p, S);
@@ -2609,7 +2258,7 @@ int fmr_chain::run_fm(CallCtx &k) {
     timed("mpf", [&] {
       // the chain-and-helpers form (k_mpf4: no barrier inside a chunk)
       constexpr int NG4 = FMR_MPF_CH / 4 + 2;
-      const int tpl4 = mpf_N <= 320 ? 5 : mpf_N <= 640 ? 10 : 20;      // (init(): mpf_N <= kMaxMpfTaps = 1280)
+      const int tpl4 = mpf_N <= 320 ? 5 : mpf_N <= 640 ? 10 : 20;      // (plan_create(): mpf_N <= kMaxMpfTaps = 1280)
       const size_t lds4 = sizeof(float2) * ((size_t)mpf_N + FMR_MPF_CH + 8) + sizeof(float) * NG4 + sizeof(float2) * FMR_MPF_CH +
                           sizeof(double) * NG4 + sizeof(float2) * (tpl4 <= 10 ? 16 : 8) * 64 * (size_t)tpl4 + sizeof(int) * 16 +
                           sizeof(float2);
@@ -2669,18 +2318,16 @@ int fmr_chain::run_fm(CallCtx &k) {
   // fused de-emphasis + stage A: the tile (warm-up + (TOUT-1) D + NA samples) must fit BLOCK * LPL LDS slots;
   // at most 4 * DE_BLOCK outputs per tile: every lane then owns exactly one run of 4 outputs in the FIR phase
   t.de_tout = std::min(4 * kDeBlock, ((kDeBlock * FMR_DE_LPL - FMR_DE_WARMUP - ars.NA - ars.D) / ars.D) & ~3);
-  t.de_fused = !serial_mode && t.de_tout >= 64;
+  t.de_fused = !env.serial && t.de_tout >= 64;
   t.dc_nc = (int)((N_au + C_DC - 1) / C_DC);
-  t.dk.b0 = dcblock.b0; t.dk.b1 = dcblock.b1; t.dk.b2 = dcblock.b2; t.dk.a1 = dcblock.a1; t.dk.a2 = dcblock.a2;
-  for (int j = 0; j < 4; j++) t.dk.ac[j] = dc_ac[j];
-  for (int lv = 0; lv < 6; lv++) for (int j = 0; j < 4; j++) t.dk.agp[lv][j] = dc_agp[lv][j];
+  t.dk = dk;
   const long long am_stride = H_am + (long long)max_amid;
   const long long a1_stride = H_pc + (long long)max_au;
   // Channel 0 (mono = L+R) does not depend on the PLL: in the in-order chain with stereo on it runs on the AGC stream while
   // the PLL iterates, and only L-R stays behind the PLL on the decoder stream.  In the pipelined chain both channels belong
   // to the tail STAGE (its own stream, a call behind the PLL stage): the mono channel's buffers are still being read by the
   // previous call's DC block and mux while this call's PLL iterates.
-  t.can_split = stereo && !serial_mode && t.de_fused && (ars.LB == 3 && ars.MB == 8) && n_pilotcut <= FMR_PCUT_MAXTAPS;
+  t.can_split = stereo && !env.serial && t.de_fused && (ars.LB == 3 && ars.MB == 8) && n_pilotcut <= FMR_PCUT_MAXTAPS;
   t.ev_mpx = k.ev_mpx;
   if (stereo) if (int rcp = run_fm_pll(k, t)) return rcp;
   if (k.agc_deferred) { k.agc_deferred = false; if (int rca = enqueue_agc(k.agc, nullptr)) return rca; }   // PLL path not taken
@@ -2691,7 +2338,7 @@ int fmr_chain::run_fm(CallCtx &k) {
     k.add_halo(k.base, base_stride, H_b, N_if, 1);
     if (stereo) k.add_halo(k.raw, base_stride, H_b, N_if);
   }       // (pipelined: the halos of the ring slots are carried over at the head of the next call, run_tables)
-  if (!t.de_fused || debug_taps) {     // (the fused de-emphasis keeps the 384 kHz signal in LDS: these are taps then)
+  if (!t.de_fused || env.debug_taps) {     // (the fused de-emphasis keeps the 384 kHz signal in LDS: these are taps then)
     k.add_halo(d_base_de.p, de_stride, H_a, N_if);
     if (stereo) k.add_halo(d_raw_de.p, de_stride, H_a, N_if);
   }
@@ -2730,8 +2377,8 @@ void fmr_chain::tail_channels(const TailCtx &t, hipStream_t st, int ch_base, int
           hipLaunchKernelGGL(kern, dim3(tiles, S, nch_l), dim3(DE_BLOCK), lds, st, t.base, t.raw, base_stride, H_b,
                              (int)N_if, deemph.b0, deemph.a1, de_scan, 1, (int)(stereo && !pilot_shift), d_ahA.p,
                              ars.NA, ars.D, a_top0, count_am, de_tout, d_am0.p, d_am1.p, am_stride, H_am,
-                             debug_taps ? d_base_de.p : (double *)nullptr,
-                             debug_taps ? d_raw_de.p : (double *)nullptr, de_stride, H_a, ch_base);
+                             env.debug_taps ? d_base_de.p : (double *)nullptr,
+                             env.debug_taps ? d_raw_de.p : (double *)nullptr, de_stride, H_a, ch_base);
         };
         if (ars.NA == 59 && ars.D == 3) go(k_deemph_decim<DE_BLOCK, 59, 3>);     // 384 kHz -> 48 kHz
         else go(k_deemph_decim<DE_BLOCK, 0, 0>);
@@ -2787,7 +2434,7 @@ void fmr_chain::tail_channels(const TailCtx &t, hipStream_t st, int ch_base, int
                            bt, d_pilotcut.p, n_pilotcut, d_pc0.p, d_pc1.p, (long long)max_au);
     });
   }
-  if (N_au > 0 && !serial_mode)
+  if (N_au > 0 && !env.serial)
     timed_on(st, "dc_pass1", [&] {
       hipLaunchKernelGGL(k_dc_pass1<C_DC>, dim3((dc_nc + 63) / 64, S, nch_l), dim3(64), 0, st, d_pc0.p, d_pc1.p,
                          (long long)max_au, (int)N_au, t.dk, d_dc_G.p, dc_nc, ch_base);
@@ -2815,8 +2462,8 @@ int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
   else tail_channels(t, ts, 0, nch);
   if (t.mono_enqueued) HIPCHK(hipStreamWaitEvent(ts, ev_mono, 0));   // DC-block node pass needs both channels
   if (N_au > 0) {
-    if (t.fin_on_side && serial_mode) HIPCHK(hipStreamWaitEvent(ts, ev_fin, 0));
-    if (serial_mode) {
+    if (t.fin_on_side && env.serial) HIPCHK(hipStreamWaitEvent(ts, ev_fin, 0));
+    if (env.serial) {
       timed_on(ts, "fm_out", [&] {
         hipLaunchKernelGGL(k_fm_out, dim3(S), dim3(64), 0, ts, d_pc0.p, d_pc1.p, (long long)max_au, t.bt, (int)N_au,
                            dcblock.b0, dcblock.b1, dcblock.b2, dcblock.a1, dcblock.a2, (int)stereo, (int)pilot_shift,
@@ -3370,7 +3017,7 @@ int fmr_chain::run_am(CallCtx &k) {
                        d_bb_rms_blk.p, d_state.p, S, 0, (const FusedPart *)nullptr, 0, 0, out.ifrms_slot(0));
   });
   timed("am_tail", [&] {
-    const bool par_tail = !serial_mode;
+    const bool par_tail = !env.serial;
     if (par_tail) {
       // DC block -> AfSimpleAgc -> de-emphasis in time-parallel form (kernels_par.hpp); the serial kernel below only
       // runs for a stream whose Newton rounds did not converge
@@ -4120,6 +3767,35 @@ int fmr_get_multipath_coefficients(fmr_chain *c, int stream, float *coeff, int c
 }
 
 long long fmr_debug_live_resources(void) { return g_live.load(); }
+
+int fmr_debug_chain_shape(const fmr_config *cfg, size_t cfg_size, int channelizer, fmr_chain_shape_info *out, size_t out_size) {
+  if (!cfg || !out) { set_err("fmr_debug_chain_shape: cfg or out is NULL"); return FMR_ERR_BAD_ARG; }
+  if ((out_size ? out_size : sizeof *out) > sizeof *out) {
+    set_err("fmr_debug_chain_shape: out_size %zu is larger than this library's fmr_chain_shape_info (%zu): the caller is newer than the library",
+            out_size, sizeof *out);
+    return FMR_ERR_BAD_ARG;
+  }
+  fmr_config full;
+  if (int rc = widen_config("fmr_debug_chain_shape", cfg, cfg_size ? cfg_size : sizeof(fmr_config), &full)) return rc;
+  try {
+    EnvKnobs env;
+    env.load();
+    ChainShape sh;
+    if (int rc = plan_create(sh, &full, env, channelizer != 0)) return rc;
+    fmr_chain_shape_info o{};
+    o.struct_size = (unsigned)sizeof o;
+    if (sh.has_rs) {
+      o.D = sh.rs.D; o.NA = sh.rs.NA; o.LB = sh.rs.LB; o.MB = sh.rs.MB; o.TB = sh.rs.TB; o.LT = sh.rs.LT;
+      o.stage_b = kFeBitB[(int)sh.fe.b];
+    }
+    o.fused = (int)sh.fe.fused; o.decim16 = sh.fe.decim16; o.poly5h_disc = sh.fe.poly5h_disc;
+    o.fir = sh.fe.fir == ChainShape::IfForm::poly4_disc ? 1 : sh.fe.fir == ChainShape::IfForm::poly4_finish ? 2 : 0;
+    o.qa = sh.qa; o.pipelined = sh.pipelined;
+    o.max_if = sh.max_if; o.max_au = sh.max_au;
+    give_sized(out, out_size, o);
+    return FMR_OK;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
 
 long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t cap_bytes) {
   if (!c || stream < 0 || stream >= c->S) return FMR_ERR_BAD_ARG;

@@ -317,6 +317,25 @@ long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t 
  * leaves it where it was (tests/test_gpu_lifecycle.py). */
 long long fmr_debug_live_resources(void);
 
+/* What fmr_create (channelizer = 0) or fmr_create_channelizer (1) would decide about cfg before it builds anything: the
+ * shape step of a create, run by itself.  It opens no device and allocates nothing, so it works on a machine without a
+ * GPU.  Returns the create's code and leaves its message in fmr_last_error() when the configuration is refused; FMR_OK
+ * fills out.  cfg_size: the size of fmr_config as the caller knows it, 0 = as this library does; out_size likewise. */
+typedef struct fmr_chain_shape_info {
+  unsigned struct_size;       /* set by the library */
+  int D, NA;                  /* the IF resampler's design, as fmr_design_taps_class reports it (all 0 without the resampler) */
+  long long LB, MB;
+  int TB, LT;
+  unsigned stage_b;           /* FMR_FE_* bit of stage B of a call that takes no upgrade (0 without the resampler) */
+  int fused;                  /* fused front end: 0 no, 1 IF samples only, 2 with the discriminator as its epilogue */
+  int decim16, poly5h_disc;   /* the upgrades of stage A (R8B class) and of poly5h the shape allows */
+  int fir;                    /* IF filter on the matrix cores: 0 no, 1 with the discriminator epilogue (FM), 2 + k_fir_finish */
+  int qa;                     /* taps per phase of k_ifr_decim2: 16, 24, or 0 (the generic stage A) */
+  int pipelined;              /* the stages of consecutive calls run beside each other */
+  unsigned long long max_if, max_au;   /* capacity per stream and call: IF samples, audio samples per channel */
+} fmr_chain_shape_info;
+int fmr_debug_chain_shape(const fmr_config *cfg, size_t cfg_size, int channelizer, fmr_chain_shape_info *out, size_t out_size);
+
 /* Kernel timing with HIP events on the chain's own streams.  enable = 1: every kernel of
  * the most recent call (diagnostics; the extra events cost host time).  enable = 2: only the
  * kernels of the FIR + discriminator stage ("ifr_fused", or "ifr_decim" / "ifr_poly" / "disc", a channel bank's stage A

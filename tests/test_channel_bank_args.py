@@ -28,7 +28,7 @@ def _create(**kw):
 FM10 = dict(mode=fmr.MODE_FM, input_rate=10e6, enable_resampler=True, stereo=True, max_block_len=65536, max_blocks=4)
 
 
-@pytest.mark.parametrize("kw, code, words", [
+REFUSALS = [
     (dict(FM10, enable_resampler=False), fmr.ERR_UNSUPPORTED, "enable_resampler"),
     (dict(FM10, mode=fmr.MODE_NONE), fmr.ERR_UNSUPPORTED, "mode != -1"),
     (dict(FM10, input_format=fmr.IQ_U8), fmr.ERR_UNSUPPORTED, "input_format"),
@@ -38,16 +38,23 @@ FM10 = dict(mode=fmr.MODE_FM, input_rate=10e6, enable_resampler=True, stereo=Tru
     (dict(FM10, input_rate=912e3), fmr.ERR_UNSUPPORTED, "D = 1"),
     (dict(FM10, input_rate=456e3), fmr.ERR_UNSUPPORTED, "D = 1"),
     (dict(FM10, mode=fmr.MODE_AM), fmr.ERR_UNSUPPORTED, "D = 80"),
-], ids=["no_resampler", "front_end_only", "raw_format", "fourth_down", "ppm_rate", "d1_1m152", "d1_912k", "d1_456k",
-        "d80_10m_am"])
+]
+REFUSAL_IDS = ["no_resampler", "front_end_only", "raw_format", "fourth_down", "ppm_rate", "d1_1m152", "d1_912k", "d1_456k",
+               "d80_10m_am"]
+
+
+@pytest.mark.parametrize("kw, code, words", REFUSALS, ids=REFUSAL_IDS)
 def test_refusals(kw, code, words):
     rc, msg = _create(channel_offsets_hz=[0, 20000], **kw)
     assert rc == code, (rc, msg)
     assert "channel bank" in msg and words in msg, msg
 
 
-@pytest.mark.parametrize("mode, F, f", [(fmr.MODE_FM, 10e6, 4_808_001), (fmr.MODE_FM, 10e6, -4_808_001),
-                                        (fmr.MODE_AM, 2.4e6, 1_176_001), (fmr.MODE_NBFM, 1.48e6, -716_001)])
+OFFSETS_BEYOND = [(fmr.MODE_FM, 10e6, 4_808_001), (fmr.MODE_FM, 10e6, -4_808_001),
+                  (fmr.MODE_AM, 2.4e6, 1_176_001), (fmr.MODE_NBFM, 1.48e6, -716_001)]
+
+
+@pytest.mark.parametrize("mode, F, f", OFFSETS_BEYOND)
 def test_offset_beyond_half_the_band_refused(mode, F, f):
     rc, msg = _create(**dict(FM10, mode=mode, input_rate=F), channel_offsets_hz=[0, f])
     assert rc == fmr.ERR_BAD_ARG, (rc, msg)

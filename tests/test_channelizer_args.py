@@ -16,9 +16,8 @@ fmr = importlib.import_module("airspy-fmradion_amd")
 NEW = ["fmr_create_channelizer", "fmr_resample_blocks", "fmr_resample_blocks_device"]
 
 
-def _create(input_rate, offsets, output_rate=0.0, resampler_class=fmr.RESAMPLER_FAST, **over):
-    """(rc, message) of fmr_create_channelizer; the config fields in `over` are set after the channelizer's own."""
-    L = fmr.lib()
+def _config(input_rate, offsets, output_rate=0.0, resampler_class=fmr.RESAMPLER_FAST, **over):
+    """(fmr_config of a channelizer, the offsets it points to); the fields in `over` are set after the channelizer's own."""
     cfg = fmr.Config()
     cfg.n_streams, cfg.mode, cfg.input_rate, cfg.enable_resampler = len(offsets) or 1, fmr.MODE_NONE, float(input_rate), 1
     cfg.output_rate, cfg.resampler_class = float(output_rate), int(resampler_class)
@@ -28,6 +27,13 @@ def _create(input_rate, offsets, output_rate=0.0, resampler_class=fmr.RESAMPLER_
         cfg.channel_offset_hz = arr
     for k, v in over.items():
         setattr(cfg, k, v)
+    return cfg, arr
+
+
+def _create(input_rate, offsets, output_rate=0.0, resampler_class=fmr.RESAMPLER_FAST, **over):
+    """(rc, message) of fmr_create_channelizer for _config(...)."""
+    L = fmr.lib()
+    cfg, _arr = _config(input_rate, offsets, output_rate, resampler_class, **over)
     h = C.c_void_p()
     rc = L.fmr_create_channelizer(C.byref(cfg), 0, C.byref(h))
     msg = L.fmr_last_error().decode()
@@ -78,7 +84,7 @@ def test_output_rate_zero_is_384k():
     assert rc == fmr.ERR_BAD_ARG and "(input_rate - output_rate) / 2" in msg, (rc, msg)
 
 
-@pytest.mark.parametrize("over, code, words", [
+RULES = [
     (dict(mode=fmr.MODE_FM), fmr.ERR_UNSUPPORTED, "mode = -1"),
     (dict(mode=fmr.MODE_AM), fmr.ERR_UNSUPPORTED, "mode = -1"),
     (dict(enable_resampler=0), fmr.ERR_UNSUPPORTED, "enable_resampler = 1"),
@@ -86,7 +92,11 @@ def test_output_rate_zero_is_384k():
     (dict(input_format=fmr.IQ_U8), fmr.ERR_UNSUPPORTED, "input_format"),
     (dict(enable_fourth_down=1), fmr.ERR_BAD_ARG, "enable_fourth_down"),
     (dict(input_rate=2.4e6 * (1 + 37e-6)), fmr.ERR_UNSUPPORTED, "whole number of hertz"),
-], ids=["fm_mode", "am_mode", "no_resampler", "s16", "u8", "fourth_down", "ppm_rate"])
+]
+RULE_IDS = ["fm_mode", "am_mode", "no_resampler", "s16", "u8", "fourth_down", "ppm_rate"]
+
+
+@pytest.mark.parametrize("over, code, words", RULES, ids=RULE_IDS)
 def test_rules_refused_by_name(over, code, words):
     over = dict(over)
     rc, msg = _create(over.pop("input_rate", 10e6), [0, 20000], **over)
@@ -99,7 +109,10 @@ def test_no_offsets_refused():
     assert rc == fmr.ERR_BAD_ARG and msg.startswith("channelizer:") and "channel_offset_hz" in msg, (rc, msg)
 
 
-@pytest.mark.parametrize("F, out", [(10e6, 384e3), (2.4e6, 48e3), (10e6, 250e3)])
+OFFSET_RATES = [(10e6, 384e3), (2.4e6, 48e3), (10e6, 250e3)]
+
+
+@pytest.mark.parametrize("F, out", OFFSET_RATES)
 def test_offset_beyond_half_the_band_refused(F, out):
     edge = int((F - out) // 2)
     assert _accepted(*_create(F, [0, -edge], output_rate=out))

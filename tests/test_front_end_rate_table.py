@@ -8,7 +8,8 @@ Fs/4) with the forms each one reaches; the GPU file runs every row against the f
 these forms ran (Chain.front_end_forms()).  What this file checks without a GPU:
   * product design == oracle design (info and taps, both classes) for every row -- the GPU comparison rests on it;
   * the rows together reach every FMR_FE_* form (two are covered by named tests elsewhere);
-  * the raw-format refusals are refusals of the documented rule, and no case row falls under it;
+  * the raw-format refusals are refusals of the documented rule, and no case row falls under it (the create refuses
+    them before it opens a device: tests/test_chain_shape.py asserts that here, without one);
   * the call schedules hold the edge lengths the GPU rows are meant to exercise;
   * the IF parity check itself trips on one sample shifted by 1e-4 x rms.
 """
@@ -21,7 +22,7 @@ import numpy as np
 import pytest
 
 import oracle_py as ora
-from conftest import ROOT
+from conftest import ROOT, load_filter
 
 fmr = importlib.import_module("airspy-fmradion_amd")
 
@@ -66,12 +67,44 @@ COVERED_ELSEWHERE = {
 }
 
 # Raw formats are converted inside k_ifr_decim2's FAST form only: U8 needs the FAST class and 2 <= D <= 15.  These source
-# configurations are refused at create (the GPU file asserts it); the reference converts them on the host.
+# configurations are refused at create (tests/test_chain_shape.py asserts it without a device, the GPU file with one); the
+# reference converts them on the host.
 REFUSED_CASES = [
     _c("rtl_1m152_fm_u8_d1", "RTL-SDR", 1.152e6, 384e3, FAST, U8, 1, 16384, "fm", ""),
     _c("rtl_2m4_nbfm_u8_d19", "RTL-SDR", 2.4e6, 48e3, FAST, U8, 1, 16384, "nbfm", ""),
     _c("rtl_2m4_fm_u8_r8b", "RTL-SDR", 2.4e6, 384e3, R8B, U8, 1, 16384, "fm", ""),
 ]
+
+
+MODES = {"fm": fmr.MODE_FM, "am": fmr.MODE_AM, "nbfm": fmr.MODE_NBFM}
+STAGE_B_FORMS = {"poly5h", "poly4", "poly4_am", "poly3", "poly2", "poly_frac", "poly"}
+STAGE_B_UPGRADES = {"fused", "poly5h_disc"}
+
+
+def chain_kwargs(case, max_blocks, n_streams=2, **kw):
+    """Chain(...) / chain_shape(...) arguments of a row's decoder chain."""
+    extra = {}
+    if case.mode == "am":
+        extra["filter_coeff"] = load_filter("jj1bdx_am_48khz_narrow")
+    elif case.mode == "nbfm":
+        extra["filter_coeff"] = load_filter("jj1bdx_nbfm_48khz_default")
+    extra.update(kw)
+    return dict(mode=MODES[case.mode], input_rate=case.fin, enable_resampler=True, fourth_down=case.f4, stereo=True,
+                max_block_len=case.blk, max_blocks=max_blocks, n_streams=n_streams, input_format=case.fmt,
+                resampler_class=case.cls, **extra)
+
+
+def assert_forms_permitted(forms, shape):
+    """Every kernel form in `forms` (a row's, or what a chain ran) is one the chain's shape (fmr.chain_shape) permits."""
+    forms = set(forms)
+    assert "decim16" not in forms or shape.decim16, (forms, shape)
+    assert "poly5h_disc" not in forms or shape.poly5h_disc, (forms, shape)
+    assert "fused" not in forms or shape.fused, (forms, shape)
+    assert "decim2_16" not in forms or shape.qa == 16, (forms, shape)
+    assert "decim2_24" not in forms or shape.qa == 24, (forms, shape)
+    assert "decim" not in forms or shape.qa == 0, (forms, shape)      # (the generic stage A runs only where k_ifr_decim2 cannot)
+    assert shape.stage_b in forms or forms & STAGE_B_UPGRADES, (forms, shape)
+    assert forms & STAGE_B_FORMS <= {shape.stage_b}, (forms, shape)
 
 
 def design(case, cls=None):

@@ -6,7 +6,7 @@ rows quantised, and converted on the oracle side with ora.iq_convert, then Fourt
 ragged calls of several blocks.  The IF samples of every call (fmr_debug_read 0, FMR_DEBUG_TAPS=1 where the
 discriminator epilogue keeps them on chip) are held against ora.IfResampler of the row's class:
   * the same output counts, call by call (and block by block where the decoder's audio counts are the IF counts);
-  * exactly the row's kernel forms ran (Chain.front_end_forms());
+  * exactly the row's kernel forms ran (Chain.front_end_forms()), and the chain's shape (fmr.chain_shape) permits them;
   * relative RMS error <= 2e-6 (FAST forms), or K_R8B * 2^-24 * sqrt(TB) where the R8B class accumulates its thousands
     of stage-B taps in one fp32 chain; and max |err| <= 30 x that bound x rms(ref): one wrong sample at a tile seam,
     a phase-table edge or an Fs/4 index carried across an odd block fails the row.
@@ -20,15 +20,14 @@ import pytest
 import oracle_py as ora
 import siggen
 from conftest import load_filter
-from test_front_end_rate_table import (MAX_OVER_RMS, RATE_CASES, REFUSED_CASES, REL_RMS_FAST, U8, CF32, R8B, FAST,
-                                       call_schedule, check_if_parity, design, oracle_if_resampler, rel_rms_bound,
-                                       tile_b)
+from test_front_end_rate_table import (MAX_OVER_RMS, MODES, RATE_CASES, REFUSED_CASES, REL_RMS_FAST, U8, CF32, R8B, FAST,
+                                       assert_forms_permitted, call_schedule, chain_kwargs, check_if_parity, design,
+                                       oracle_if_resampler, rel_rms_bound, tile_b)
 from test_gpu_parity import _report
 
 pytestmark = pytest.mark.gpu
 
 fmr = importlib.import_module("airspy-fmradion_amd")
-MODES = {"fm": fmr.MODE_FM, "am": fmr.MODE_AM, "nbfm": fmr.MODE_NBFM}
 S = 2
 
 
@@ -63,15 +62,7 @@ def source(case, n):
 
 
 def make_chain(case, max_blocks, **kw):
-    extra = {}
-    if case.mode == "am":
-        extra["filter_coeff"] = load_filter("jj1bdx_am_48khz_narrow")
-    elif case.mode == "nbfm":
-        extra["filter_coeff"] = load_filter("jj1bdx_nbfm_48khz_default")
-    extra.update(kw)
-    return fmr.Chain(mode=MODES[case.mode], input_rate=case.fin, enable_resampler=True, fourth_down=case.f4,
-                     stereo=True, max_block_len=case.blk, max_blocks=max_blocks, n_streams=S, input_format=case.fmt,
-                     resampler_class=case.cls, **extra)
+    return fmr.Chain(**chain_kwargs(case, max_blocks, n_streams=S, **kw))
 
 
 # ------------------------------------------------------------------ IF samples, every row
@@ -131,6 +122,7 @@ def test_if_samples_against_the_fp64_oracle(case, monkeypatch):
             bound_rel_rms=bound, bound_max_err_over_rms=MAX_OVER_RMS * bound, forms=sorted(forms), expected_forms=sorted(case.forms),
             info=info, cls="r8b" if case.cls == R8B else "fast", fmt=case.fmt, fourth=case.f4, calls=len(calls))
     assert forms == set(case.forms), (case.name, sorted(forms), sorted(case.forms))
+    assert_forms_permitted(forms, fmr.chain_shape(**chain_kwargs(case, max(len(c) for c in calls), n_streams=S)))
     # sensitivity on the measured arrays: one product sample off by 1e-4 x rms fails the max-error bound
     if bound == REL_RMS_FAST:
         g, q = np.concatenate(got[0]), np.concatenate(ref[0])

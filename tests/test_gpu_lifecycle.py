@@ -1,9 +1,10 @@
 """Nothing is left behind: every path that makes device buffers, pinned blocks, events or streams gives all of them back.
 fmr_debug_live_resources() counts what the library's owners hold in the process; each case reads it before, while its
 objects are open (> before: the counter counts) and after everything is closed (== before; 0 in a fresh process).  Also:
-a create that fails after the device is open and an enable that is refused leave the count -- and the chain -- as they were.
-No case forces an allocation to fail (that takes a request of hundreds of gigabytes on a shared card): that a failed enable
-leaves nothing behind follows from how enables are built (a local stage, moved into the chain on success)."""
+a create that is refused and an enable that is refused leave the count -- and the chain -- as they were.
+No case forces an allocation to fail (that takes a request of hundreds of gigabytes on a shared card): that a partly built
+chain gives everything back rests on the owners (each member frees what it holds when the chain dies), and that a failed
+enable leaves nothing behind on how enables are built (a local stage, moved into the chain on success)."""
 import gc
 import importlib
 
@@ -115,7 +116,10 @@ def test_spectrum_with_waterfall(x_fm):
     (dict(input_format=fmr.IQ_S16, resampler_class=fmr.RESAMPLER_R8B), "needs the FAST resampler class"),
     (dict(mode=fmr.MODE_NONE, input_rate=5e9), "outside the supported design range"),
 ], ids=["s16_r8b", "ratio"])
-def test_create_that_fails_with_the_device_open(kw, words):
+def test_create_that_is_refused_before_the_device_is_opened(kw, words):
+    """Both configurations used to be refused with the device open and streams made; the create now decides its shape
+    first (plan_create) and refuses them before it opens the device (tests/test_chain_shape.py: the same refusals on a
+    machine without one).  Either way nothing may be left behind."""
     before = live()
     cfg = dict(mode=fmr.MODE_FM, input_rate=10e6, enable_resampler=True, max_block_len=BLK, max_blocks=NB)
     cfg.update(kw)

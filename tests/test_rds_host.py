@@ -218,6 +218,8 @@ def _cfg(**over):
     cfg = fmr.Config()
     cfg.n_streams, cfg.mode, cfg.input_rate, cfg.enable_resampler = 1, fmr.MODE_FM, 10e6, 1
     cfg.max_block_len, cfg.max_blocks = 65536, 4
+    # (a complete decoder configuration: a create refuses a missing filter before it opens the device)
+    cfg.filter_coeff, cfg.n_filter_coeff = fmr.DELAY_3TAPS.ctypes.data_as(C.POINTER(C.c_float)), len(fmr.DELAY_3TAPS)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg
