@@ -2988,7 +2988,7 @@ int fmr_chain::run_nbfm(CallCtx &k) {
   });
   timed("stats", [&] {
     hipLaunchKernelGGL(k_stats, dim3(S), dim3(FMR_STATS_THREADS), 0, stream, bt, d_if_rms_blk.p, d_bb_mean_blk.p,
-                       d_bb_rms_blk.p, d_state.p, S, 1, (const FusedPart *)nullptr, 0, 0, out.ifrms_slot(0));
+                       d_bb_rms_blk.p, d_state.p, S, 1, (const FusedPart *)nullptr, 0, 0, out.ifrms_slot(0), 1);
   });
   timed("nbfm_audio", [&] {
     hipLaunchKernelGGL((k_pilotcut2<320, 1280>), dim3(nb, S, 1), dim3(320), 0, stream, d_base.p, (double *)nullptr,

@@ -2252,7 +2252,8 @@ __global__ __launch_bounds__(FMR_STATS_THREADS) void k_stats(BlockTab bt, const 
                                               const float *__restrict__ bb_mean_blk,
                                               const float *__restrict__ bb_rms_blk, StreamState *st, int n_streams,
                                               int has_disc, const FusedPart *__restrict__ part = nullptr, int n_tiles = 0,
-                                              int kb_ref = 0, float *__restrict__ if_rms_out = nullptr) {
+                                              int kb_ref = 0, float *__restrict__ if_rms_out = nullptr,
+                                              int empty_zeroes_rms = 0 /* NbfmDecode.cpp:54 takes the IF level of an empty block too: 0 */) {
   // One workgroup per stream.  Phase 1, all waves: a lane per block fetches (or, behind the fused front end, sums from the
   // partial sums, index order: deterministic) the block's three values -- every load of up to 512 blocks in flight at
   // once; with one wave doing 64 blocks at a time this was 0.15-0.2 ms of memory latency.  Phase 2, wave 0: the EMA
@@ -2340,7 +2341,7 @@ __global__ __launch_bounds__(FMR_STATS_THREADS) void k_stats(BlockTab bt, const 
         const float vr = s_r[j0 + lane], vm = s_m[j0 + lane], vl = s_l[j0 + lane];
         const int c2 = min(64, cnt - j0);
         for (int j = 0; j < c2; j++) {
-          if (__builtin_amdgcn_readlane(vn, j) == 0) continue;
+          if (__builtin_amdgcn_readlane(vn, j) == 0) { if (empty_zeroes_rms) r = 0.f; continue; }
           r = readlane_f(vr, j);
           m = (float)(0.95 * (double)m + 0.05 * (double)readlane_f(vm, j));
           l = (float)(0.95 * (double)l + 0.05 * (double)readlane_f(vl, j));
