@@ -53,6 +53,7 @@ EXPORTS = [
     "fmr_spectrum_create_waterfall", "fmr_spectrum_read_waterfall",
     "fmr_enable_monitor", "fmr_monitor_read", "fmr_monitor_derive",
     "fmr_enable_loudness", "fmr_loudness_read", "fmr_loudness_derive",
+    "fmr_enable_analyser", "fmr_analyser_read", "fmr_analyser_derive",
     "fmr_enable_rf_monitor", "fmr_rf_monitor_read", "fmr_rf_monitor_derive",
     "fmr_enable_output", "fmr_output_read", "fmr_squelch_level_from_db",
     "fmr_set_output_rate", "fmr_get_output_rate", "fmr_output_rate_taps",
@@ -77,6 +78,12 @@ LOUDNESS_RECORD = np.dtype([("index", np.uint64), ("first_sample", np.uint64), (
                             ("channels", np.uint32), ("step_samples", np.uint32), ("reserved", np.uint32),
                             ("kw_sumsq", np.float64, 2), ("sumsq", np.float64, 2), ("sum_lr", np.float64),
                             ("sample_peak", np.float64, 2), ("true_peak", np.float64, 2)])
+# fmr_analyser_record as a numpy structured type (72 bytes)
+ANALYSER_RECORD = np.dtype([("index", np.uint64), ("first_sample", np.uint64), ("segments", np.uint32),
+                            ("skipped", np.uint32), ("n_nonfinite", np.uint32), ("channels", np.uint32),
+                            ("fft_size", np.uint32), ("interval_samples", np.uint32), ("sum", np.float64, 2),
+                            ("sumsq", np.float64, 2)])
+ANALYSER_VIEWS = {"L": 0, "R": 1, "M": 2, "S": 3}
 # fmr_rf_monitor_record as a numpy structured type (56 bytes)
 RF_MONITOR_RECORD = np.dtype([("index", np.uint64), ("first_sample", np.uint64), ("n_finite", np.uint32),
                               ("n_nonfinite", np.uint32), ("segments", np.uint32), ("segments_skipped", np.uint32),
@@ -233,6 +240,31 @@ class LoudnessLevels(C.Structure):
                 ("gated_windows", C.c_uint64)]
 
 
+class AnalyserConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("fft_size", C.c_int), ("interval_samples", C.c_uint32), ("max_records", C.c_int)]
+
+
+class AnalyserInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("channels", C.c_int), ("records_complete", C.c_uint64),
+                ("records_dropped", C.c_uint64), ("first_unread", C.c_uint64), ("records_ready", C.c_uint64),
+                ("interval_samples", C.c_uint32), ("max_records", C.c_int), ("fft_size", C.c_int), ("bins", C.c_int),
+                ("bin_hz", C.c_double)]
+
+
+class AnalyserRule(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("view", C.c_int), ("band_lo_hz", C.c_double), ("band_hi_hz", C.c_double),
+                ("tone_hz", C.c_double), ("tone_search_hz", C.c_double), ("max_harmonic", C.c_int), ("reserved", C.c_int),
+                ("min_tone_dbfs", C.c_double)]
+
+
+class AnalyserLevels(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("tone_found", C.c_int), ("tone_hz", C.c_double), ("tone_dbfs", C.c_double),
+                ("thd", C.c_double), ("thd_n", C.c_double), ("sinad_db", C.c_double), ("noise_dbfs", C.c_double),
+                ("band_dbfs", C.c_double), ("harmonic_dbc", C.c_double * 8), ("dc", C.c_double), ("total_dbfs", C.c_double),
+                ("segments", C.c_uint64), ("skipped", C.c_uint64), ("n_nonfinite", C.c_uint64),
+                ("harmonics_counted", C.c_int), ("reserved", C.c_int)]
+
+
 class OutputConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("format", C.c_int), ("squelch_level", C.c_double), ("gain", C.c_double),
                 ("max_frames", C.c_uint32), ("max_blocks", C.c_uint32)]
@@ -373,6 +405,12 @@ def lib(ab=False):
     L.fmr_loudness_read.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(LoudnessInfo), C.c_size_t]
     L.fmr_loudness_derive.restype = C.c_int
     L.fmr_loudness_derive.argtypes = [vp, C.c_int, C.c_double, C.POINTER(LoudnessLevels), C.c_size_t]
+    L.fmr_enable_analyser.restype = C.c_int
+    L.fmr_enable_analyser.argtypes = [vp, C.POINTER(AnalyserConfig), C.c_size_t]
+    L.fmr_analyser_read.restype = C.c_int
+    L.fmr_analyser_read.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.POINTER(AnalyserInfo), C.c_size_t]
+    L.fmr_analyser_derive.restype = C.c_int
+    L.fmr_analyser_derive.argtypes = [vp, vp, C.c_int, C.POINTER(AnalyserRule), C.c_size_t, C.POINTER(AnalyserLevels), C.c_size_t]
     L.fmr_enable_rf_monitor.restype = C.c_int
     L.fmr_enable_rf_monitor.argtypes = [vp, C.POINTER(RfMonitorConfig), C.c_size_t]
     L.fmr_rf_monitor_read.restype = C.c_int
@@ -488,6 +526,28 @@ def loudness_levels(records, silence_dbfs=-60.0):
     if rc != OK:
         raise FmrError(f"fmr_loudness_derive failed ({rc}): {L.fmr_last_error().decode()}")
     return {k: getattr(out, k) for k, _ in LoudnessLevels._fields_ if k not in ("struct_size", "reserved")}
+
+
+def analyser_levels(records, spectra, view="L", band_lo_hz=0.0, band_hi_hz=0.0, tone_hz=0.0, tone_search_hz=0.0,
+                    max_harmonic=0, min_tone_dbfs=0.0):
+    """fmr_analyser_derive (host only): tone, THD, THD+N, SINAD and noise of the pooled records (an ANALYSER_RECORD array
+    with spectra [n, 3, N / 2 + 1], as Chain.analyser_records returns them) in view "L" | "R" | "M" | "S" (or 0 .. 3), as a
+    dict of fmr_analyser_levels; every 0 is the rule's default."""
+    L = lib()
+    records = np.ascontiguousarray(records, dtype=ANALYSER_RECORD)
+    spectra = np.ascontiguousarray(spectra, dtype=np.float64)
+    if spectra.size != len(records) * 3 * (int(records["fft_size"][0]) // 2 + 1 if len(records) else 0):
+        raise FmrError(f"analyser_levels: spectra of shape {spectra.shape} do not belong to {len(records)} records")
+    rule = AnalyserRule(C.sizeof(AnalyserRule), int(ANALYSER_VIEWS.get(view, view)), float(band_lo_hz), float(band_hi_hz),
+                        float(tone_hz), float(tone_search_hz), int(max_harmonic), 0, float(min_tone_dbfs))
+    out = AnalyserLevels()
+    rc = L.fmr_analyser_derive(records.ctypes.data, spectra.ctypes.data, len(records), C.byref(rule), C.sizeof(AnalyserRule),
+                               C.byref(out), C.sizeof(AnalyserLevels))
+    if rc != OK:
+        raise FmrError(f"fmr_analyser_derive failed ({rc}): {L.fmr_last_error().decode()}")
+    d = {k: getattr(out, k) for k, _ in AnalyserLevels._fields_ if k not in ("struct_size", "reserved")}
+    d["harmonic_dbc"] = [float(v) for v in out.harmonic_dbc]
+    return d
 
 
 def rf_levels(records, hist, psd):
@@ -853,6 +913,26 @@ class Chain:
         """fmr_loudness_read: the oldest unread complete records of `stream` (at most cap; None: all that wait) as
         (records LOUDNESS_RECORD [n], info dict).  Reading drains them."""
         return self._read_records(self._L.fmr_loudness_read, LoudnessInfo, ((LOUDNESS_RECORD, None),), stream, cap)
+
+    def enable_analyser(self, fft_size=0, interval_samples=0, max_records=0):
+        """fmr_enable_analyser: the audio analyser of every stream / channel (any decoder chain, once, before the first
+        call); 0 = the defaults (N = 4096, records of 6 N audio frames, 64 records kept)."""
+        cfg = AnalyserConfig(C.sizeof(AnalyserConfig), int(fft_size), int(interval_samples), int(max_records))
+        self._chk(self._L.fmr_enable_analyser(self.h, C.byref(cfg), C.sizeof(AnalyserConfig)))
+        self._an_bins, self._an_ring = (int(fft_size) or 4096) // 2 + 1, int(max_records) or 64
+
+    def analyser_records(self, stream=0, cap=None):
+        """fmr_analyser_read: the oldest unread complete records of `stream` (at most cap; None: all that wait) as
+        (records ANALYSER_RECORD [n], spectra float64 [n, 3, N / 2 + 1] scaled to power, info dict).  Reading drains them."""
+        # one read, sized by the ring (no more than max_records can wait): every read synchronises the chain
+        bins = getattr(self, "_an_bins", 1)      # (a chain without the analyser: the library refuses the read)
+        cap = getattr(self, "_an_ring", 1) if cap is None else int(cap)
+        recs, spectra = np.zeros(cap, dtype=ANALYSER_RECORD), np.empty((cap, 3, bins), dtype=np.float64)
+        info = AnalyserInfo()
+        n = self._chk(self._L.fmr_analyser_read(self.h, int(stream), recs.ctypes.data if cap else None,
+                                                spectra.ctypes.data if cap else None, cap, C.byref(info), C.sizeof(AnalyserInfo)))
+        n = n if cap else 0
+        return recs[:n], spectra[:n], {k: getattr(info, k) for k, _ in AnalyserInfo._fields_}
 
     def enable_rf_monitor(self, interval_samples=0, max_records=0):
         """fmr_enable_rf_monitor: the RF monitor of every stream / channel (FM chains, once, before the first call);

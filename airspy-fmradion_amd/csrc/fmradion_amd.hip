@@ -35,6 +35,7 @@
 #include "kernels_spectrum.hpp"
 #include "kernels_monitor.hpp"
 #include "kernels_loudness.hpp"
+#include "kernels_analyser.hpp"
 #include "kernels_rfmon.hpp"
 #include "kernels_output.hpp"
 #include "../host/fmradion_rds.hpp"
@@ -211,7 +212,7 @@ struct RecCursor {
 // The modulation monitor (fmr_enable_monitor) is a second reader of the call's MPX at the head of the
 // audio tail, beside the RDS stage; the RF monitor (fmr_enable_rf_monitor; kernels_rfmon.hpp) is a
 // second instance that reads the call's IF ring slot (the decoder's input, or |x|^2 behind a discriminator epilogue).
-// This and the three stages below are the OPTIONAL stages of a chain: each owns all its state (build_stage).
+// This and the four stages below are the OPTIONAL stages of a chain: each owns all its state (build_stage).
 struct SegMonitor {
   bool on = false;
   unsigned interval = 0;                     // samples per record
@@ -276,6 +277,30 @@ struct LoudnessStage {
   RecCursor cur;
   unsigned long long done() const { return (unsigned long long)(n / (long long)cfg.step_samples); }   // records complete
   int init(int S, size_t max_au, const fmr_loudness_config &m);
+};
+
+// Audio analyser (fmr_enable_analyser; kernels_analyser.hpp).  A second reader of the call's finished
+// audio behind the output mux, on the stream that wrote it (fmr_chain::an_stage), in every decoder mode: it counts in
+// absolute audio frames (n) and keeps its own carry (the last N frames), partials, open records and rings.
+using AnSegFn = decltype(&k_an_seg<kAnLogMin>);
+struct AnalyserStage {
+  bool on = false;
+  fmr_analyser_config cfg{};                 // the defaults filled in
+  int N = 0, H = 0, nb = 0, logn = 0;        // fft_size, hop, bins per row = N / 2 + 1
+  int spr = 0, sub = 0, sb = 0, rmax = 0;    // segments per record / per sub-block, sub-blocks per record, runs per stream and launch
+  int par = 0;                               // which copy of the open records is current
+  int threads = 0, lds = 0;                  // of k_an_seg at this N
+  AnSegFn kseg = nullptr;
+  double sumw2 = 0.0;
+  long long n = 0, next_seg = 0;             // audio frames seen, segments processed
+  DevBuf<float> d_win;
+  DevBuf<float2> d_tw;
+  DevBuf<double> d_carry, d_ppsd, d_open_psd, d_ring_psd;
+  DevBuf<AnPart> d_ppart;
+  DevBuf<AnRec> d_open_rec, d_ring_rec;
+  RecCursor cur;
+  unsigned long long done() const { return (unsigned long long)(next_seg / spr); }   // records complete
+  int init(int S, size_t max_au, const fmr_analyser_config &m);
 };
 
 // Rate converter of the output stage (fmr_set_output_rate): with `on` the ring is written by
@@ -486,12 +511,14 @@ struct fmr_chain : ChainShape {
   RdsStage rds;
   SegMonitor mon, rfm;
   LoudnessStage ld;
+  AnalyserStage an;
   OutputStage out;
   int rds_stage(const fm_mpx_t *base, long long N, hipStream_t st);
   // one call's N samples per stream through monitor m on stream st: the source as kseg / kreduce read it (from, stride, off)
   int seg_stage(SegMonitor &m, const void *from, long long stride, int off, float rf, float scale, MonSegFn kseg,
                 MonReduceFn kreduce, const char *seg_name, const char *reduce_name, long long N, hipStream_t st);
   int ld_stage(const double *d_aud, long long astride, long long N, hipStream_t st);
+  int an_stage(const double *d_aud, long long astride, long long N, hipStream_t st);
   int out_stage(const double *d_aud, long long astride, const BlockTab &bt, const float *if_rms_blk, const OutArgs &a, hipStream_t st);
   // front end only (fmr_resample_blocks_device): stage B writes row s of this call's IF samples to if_out + s if_out_stride
   // instead of the chain's IF buffer (nullptr: the IF buffer)
@@ -2483,6 +2510,7 @@ int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
     }
   }
   if (ld.on) if (int rc = ld_stage(t.d_aud, t.astride, N_au, ts)) return rc;
+  if (an.on) if (int rc = an_stage(t.d_aud, t.astride, N_au, ts)) return rc;
   if (!(t.fin_covers_all && N_au > 0)) {        // (otherwise the wait before the output mux covered all three)
     HIPCHK(hipStreamWaitEvent(ts, ev_stats, 0));
     if (t.agc_on_side) HIPCHK(hipStreamWaitEvent(ts, ev_agc, 0));
@@ -2796,6 +2824,107 @@ int fmr_chain::ld_stage(const double *d_aud, long long astride, long long N, hip
   return FMR_OK;
 }
 
+// ---- audio analyser (kernels_analyser.hpp) ----
+template <int LOGN>
+static void an_shape(AnalyserStage &a) {
+  a.kseg = k_an_seg<LOGN>;
+  a.threads = AnShape<LOGN>::T;
+  a.lds = AnShape<LOGN>::LDS_BYTES;
+}
+
+int AnalyserStage::init(int S, size_t max_au, const fmr_analyser_config &m) {
+  static_assert(sizeof(AnRec) == sizeof(fmr_analyser_record), "AnRec is fmr_analyser_record");
+  static_assert(offsetof(fmr_analyser_record, sum) == offsetof(AnRec, sum), "the sums of a record");
+  cfg = m;
+  N = m.fft_size; H = N / 2; nb = N / 2 + 1;
+  logn = 0;
+  while ((1 << logn) < N) logn++;
+  switch (logn) {
+    case 10: an_shape<10>(*this); break;
+    case 11: an_shape<11>(*this); break;
+    case 12: an_shape<12>(*this); break;
+    default: an_shape<13>(*this); break;
+  }
+  if (int rc = set_dyn_lds(kseg, (size_t)lds)) return rc;
+  spr = (int)(m.interval_samples / (unsigned)H);
+  // a full call in about 64 runs per stream: sub-blocks of 1 .. 16 segments (a run is a workgroup's serial work, and the
+  // partition only moves the fp64 rounding of the sums)
+  const size_t max_seg = max_au / H + 2;
+  sub = (int)std::min<size_t>(16, std::max<size_t>(1, (max_seg + 63) / 64));
+  sb = (spr + sub - 1) / sub;
+  rmax = (int)std::min<size_t>(kAnMaxRuns, max_seg / sub + 2 * (max_seg / spr + 2) + 2);
+  // periodic 4-term Blackman-Harris and the twiddles, in double, rounded once
+  std::vector<float> w(N);
+  std::vector<float2> tw(N);
+  sumw2 = 0.0;
+  for (int i = 0; i < N; i++) {
+    const double t = 2.0 * M_PI * i / N;
+    w[i] = (float)(0.35875 - 0.48829 * std::cos(t) + 0.14128 * std::cos(2.0 * t) - 0.01168 * std::cos(3.0 * t));
+    sumw2 += (double)w[i] * (double)w[i];
+    tw[i] = make_float2((float)std::cos(t), (float)-std::sin(t));
+  }
+  const size_t L = (size_t)m.max_records, rows = (size_t)S * rmax, nb3 = (size_t)kAnRows * nb;
+  int rc;
+  if ((rc = upload(d_win, w.data(), w.size()))) return rc;
+  if ((rc = upload(d_tw, tw.data(), tw.size()))) return rc;
+  if ((rc = d_carry.alloc((size_t)S * N * 2))) return rc;
+  if ((rc = d_ppsd.alloc(rows * nb3))) return rc;
+  if ((rc = d_ppart.alloc(rows))) return rc;
+  if ((rc = d_open_psd.alloc(2 * (size_t)S * nb3))) return rc;
+  if ((rc = d_open_rec.alloc(2 * (size_t)S))) return rc;
+  if ((rc = d_ring_psd.alloc((size_t)S * L * nb3))) return rc;
+  if ((rc = d_ring_rec.alloc((size_t)S * L))) return rc;
+  cur.reset(S, m.max_records);
+  n = next_seg = 0;
+  par = 0;
+  on = true;
+  return FMR_OK;
+}
+
+// One call's audio (N_au frames per stream, where the mux wrote them) through the analyser, on stream st: the segments
+// whose last frame the call delivers, in launches of at most an.rmax runs per stream, then the carry.
+int fmr_chain::an_stage(const double *d_aud, long long astride, long long N_au, hipStream_t st) {
+  if (N_au <= 0) return FMR_OK;
+  const long long n0 = an.n, n1 = n0 + N_au;
+  const long long j_hi = n1 >= an.N ? (n1 - an.N) / an.H + 1 : 0;
+  AnArgs a{};
+  a.n0 = n0; a.spr = an.spr; a.sub = an.sub; a.sb = an.sb; a.ch = stereo ? 2 : 1;
+  const int L = (int)an.cur.L;
+  const long long M = (long long)an.cfg.interval_samples;
+  long long j = an.next_seg;
+  do {
+    // the segments [j, a.a1) of the call's [j, j_hi) that fit into rmax runs per stream, the runs and records they touch
+    int runs = 0, nrec = 1;
+    a.a0 = a.a1 = j; a.g0 = 0;
+    if (j < j_hi) {
+      const long long l = j / a.spr;
+      a.g0 = l * a.sb + (j - l * a.spr) / a.sub;
+      long long lo, hi;
+      an_sub(a.spr, a.sub, a.sb, a.g0 + an.rmax - 1, lo, hi);
+      a.a1 = std::min(j_hi, hi);
+      const long long l_end = (a.a1 - 1) / a.spr;
+      runs = (int)(l_end * a.sb + (a.a1 - 1 - l_end * a.spr) / a.sub - a.g0 + 1);
+      nrec = (int)(l_end - l + 1);
+    }
+    if (runs > 0)
+      timed_on(st, "an_seg", [&] {
+        hipLaunchKernelGGL(an.kseg, dim3(runs, S), dim3(an.threads), an.lds, st, d_aud, astride, an.d_carry.p, a, an.d_win.p,
+                           an.d_tw.p, an.rmax, an.d_ppsd.p, an.d_ppart.p);
+      });
+    j = a.a1;
+    timed_on(st, "an_reduce", [&] {
+      hipLaunchKernelGGL(k_an_reduce, dim3(nrec, S), dim3(kAnRT), 0, st, an.d_ppsd.p, an.d_ppart.p, runs, an.rmax, a, an.N, L, M,
+                         an.par, an.d_open_psd.p, an.d_open_rec.p, an.d_ring_psd.p, an.d_ring_rec.p, d_aud, astride,
+                         an.d_carry.p, n1, (int)(j >= j_hi));
+    });
+    if (runs > 0) an.par ^= 1;
+  } while (j < j_hi);
+  an.next_seg = std::max(an.next_seg, j_hi);
+  an.n = n1;
+  HIPCHK(hipGetLastError());
+  return FMR_OK;
+}
+
 // ---- output stage (kernels_output.hpp) ----
 int OutputStage::init(int S, bool chain_stereo, int max_blocks, int slots, const fmr_output_config &m) {
   static_assert(sizeof(OutRec) == sizeof(fmr_output_block), "OutRec is fmr_output_block");
@@ -2998,6 +3127,7 @@ int fmr_chain::run_nbfm(CallCtx &k) {
   k.add_halo(k.ifbuf, k.if_stride, H_if, N_if);
   k.add_halo(d_base.p, base_stride, H_b, N_if);
   if (k.audio_len) for (int b = 0; b < nb; b++) k.audio_len[b] = (uint32_t)k.tab.au_len[b];
+  if (an.on) if (int rc = an_stage(d_aud, astride, k.N_au, stream)) return rc;
   if (out.on) if (int rc = out_stage(d_aud, astride, bt, out.ifrms_slot(0), out.begin(k.out_block0, k.tab.if_len, nb, k.N_au), stream)) return rc;
   return FMR_OK;
 }
@@ -3046,6 +3176,7 @@ int fmr_chain::run_am(CallCtx &k) {
   });
   k.add_halo(k.ifbuf, k.if_stride, H_if, N_if);
   if (k.audio_len) for (int b = 0; b < nb; b++) k.audio_len[b] = (uint32_t)k.tab.au_len[b];
+  if (an.on) if (int rc = an_stage(d_aud, astride, k.N_au, stream)) return rc;
   if (out.on) if (int rc = out_stage(d_aud, astride, bt, out.ifrms_slot(0), out.begin(k.out_block0, k.tab.if_len, nb, k.N_au), stream)) return rc;
   return FMR_OK;
 }
@@ -4436,6 +4567,225 @@ int fmr_loudness_derive(const fmr_loudness_record *recs, int n, double silence_d
   full.correlation = den > 0.0 ? slr / std::sqrt(den) : 0.0;
   const double side = sl + sr - 2.0 * slr, mid = sl + sr + 2.0 * slr;
   full.side_to_mid_db = side <= 0.0 && mid <= 0.0 ? 0.0 : side <= 0.0 ? -INFINITY : mid <= 0.0 ? INFINITY : 10.0 * std::log10(side / mid);
+  give_sized(out, out_size, full);
+  return FMR_OK;
+}
+
+// ---- audio analyser: C-ABI ----
+int fmr_enable_analyser(fmr_chain *c, const fmr_analyser_config *cfg, size_t cfg_size) {
+  if (!cfg) { set_err("fmr_enable_analyser: cfg is null"); return FMR_ERR_BAD_ARG; }
+  fmr_analyser_config m;
+  if (int rc = take_sized("fmr_enable_analyser", "fmr_analyser_config", cfg, cfg_size, m)) return rc;
+  if (m.fft_size == 0) m.fft_size = 4096;
+  if (m.fft_size != 1024 && m.fft_size != 2048 && m.fft_size != 4096 && m.fft_size != 8192) {
+    set_err("fmr_enable_analyser: fft_size %d is not 1024, 2048, 4096 or 8192 (0 = 4096)", m.fft_size);
+    return FMR_ERR_BAD_ARG;
+  }
+  const uint32_t H = (uint32_t)m.fft_size / 2;
+  if (m.interval_samples == 0) m.interval_samples = 6u * (uint32_t)m.fft_size;
+  if (m.max_records == 0) m.max_records = 64;
+  if (m.interval_samples % H != 0 || m.interval_samples < H || m.interval_samples > (1u << 24)) {
+    set_err("fmr_enable_analyser: interval_samples %u is not a multiple of fft_size / 2 = %u in %u .. 2^24 (0 = 6 fft_size)",
+            m.interval_samples, H, H);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.max_records < 1 || m.max_records > 4096) {
+    set_err("fmr_enable_analyser: max_records %d is outside 1 .. 4096 (0 = 64)", m.max_records);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!c) { set_err("fmr_enable_analyser: chain is null"); return FMR_ERR_BAD_ARG; }
+  if (!c->has_dec) {
+    set_err("fmr_enable_analyser: a front-end-only chain (mode -1: channelizer / IfResampler) has no audio");
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (c->an.on) { set_err("fmr_enable_analyser: the analyser of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
+  if (c->call_seq != 0) {
+    set_err("fmr_enable_analyser: the chain has already taken samples (the analyser counts from the chain's first audio sample)");
+    return FMR_ERR_BAD_ARG;
+  }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    return build_stage(c->an, c->S, c->max_au, m);
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_analyser_read(fmr_chain *c, int stream, fmr_analyser_record *recs, double *spectra, int cap, fmr_analyser_info *info,
+                      size_t info_size) {
+  if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_analyser_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
+  if (!c->an.on) { set_err("fmr_analyser_read: the chain has no analyser (fmr_enable_analyser)"); return FMR_ERR_BAD_ARG; }
+  if (cap > 0 && !recs) { set_err("fmr_analyser_read: recs is null"); return FMR_ERR_BAD_ARG; }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    AnalyserStage &an = c->an;
+    const unsigned long long done = an.done();
+    const size_t nb = (size_t)an.nb, nb3 = (size_t)kAnRows * nb;
+    const int n = an.cur.take(stream, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
+      const size_t at = (size_t)stream * an.cur.L + slot;
+      HIPCHK(hipMemcpy(recs + k, an.d_ring_rec.p + at, m * sizeof(fmr_analyser_record), hipMemcpyDeviceToHost));
+      if (spectra) HIPCHK(hipMemcpy(spectra + k * nb3, an.d_ring_psd.p + at * nb3, m * nb3 * sizeof(double), hipMemcpyDeviceToHost));
+      return FMR_OK;
+    });
+    if (n < 0) return n;
+    if (spectra && cap > 0)      // the sums of the counted segments -> power
+      for (int i = 0; i < n; i++) {
+        const double seg = (double)recs[i].segments;
+        const double g = seg > 0.0 ? 1.0 / ((double)an.N * an.sumw2 * seg) : 0.0;
+        for (int r = 0; r < kAnRows; r++) {
+          double *row = spectra + (size_t)i * nb3 + (size_t)r * nb;
+          for (size_t k = 0; k < nb; k++) row[k] = row[k] * ((k == 0 || k == nb - 1) ? 1.0 : 2.0) * g;
+        }
+      }
+    if (info) {
+      fmr_analyser_info full{};
+      full.struct_size = (unsigned)sizeof full;
+      full.channels = c->stereo ? 2 : 1;
+      full.records_complete = done;
+      full.records_dropped = an.cur.dropped[stream];
+      full.first_unread = an.cur.read[stream];
+      full.records_ready = done - an.cur.read[stream];
+      full.interval_samples = an.cfg.interval_samples;
+      full.max_records = an.cfg.max_records;
+      full.fft_size = an.N;
+      full.bins = an.nb;
+      full.bin_hz = kPcmRate / an.N;
+      give_sized(info, info_size, full);
+    }
+    return n;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_analyser_derive(const fmr_analyser_record *recs, const double *spectra, int n, const fmr_analyser_rule *rule,
+                        size_t rule_size, fmr_analyser_levels *out, size_t out_size) {
+  if (!recs || !spectra || !out || n < 1) { set_err("fmr_analyser_derive: recs, spectra or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
+  fmr_analyser_rule r{};
+  if (rule) if (int rc = take_sized("fmr_analyser_derive", "fmr_analyser_rule", rule, rule_size, r)) return rc;
+  const int N = (int)recs[0].fft_size, ch = (int)recs[0].channels;
+  if ((N != 1024 && N != 2048 && N != 4096 && N != 8192) || ch < 1 || ch > 2) {
+    set_err("fmr_analyser_derive: record 0 has fft_size %d and channels %d (not a record of fmr_analyser_read)", N, ch);
+    return FMR_ERR_BAD_ARG;
+  }
+  for (int i = 1; i < n; i++)
+    if ((int)recs[i].fft_size != N || (int)recs[i].channels != ch) {
+      set_err("fmr_analyser_derive: record %d has fft_size %u and channels %u, record 0 has %d and %d", i, recs[i].fft_size,
+              recs[i].channels, N, ch);
+      return FMR_ERR_BAD_ARG;
+    }
+  if (r.view < 0 || r.view > 3 || (ch == 1 && r.view != 0)) {
+    set_err("fmr_analyser_derive: view %d is not 0 .. 3 (0 only for records of one channel; these have %d)", r.view, ch);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (r.band_lo_hz == 0.0) r.band_lo_hz = 20.0;
+  if (r.band_hi_hz == 0.0) r.band_hi_hz = 15000.0;
+  if (r.tone_search_hz == 0.0) r.tone_search_hz = 50.0;
+  if (r.max_harmonic == 0) r.max_harmonic = 10;
+  if (r.min_tone_dbfs == 0.0) r.min_tone_dbfs = -60.0;
+  constexpr int W = 4;
+  const double bin_hz = kPcmRate / N;
+  if (!(r.band_lo_hz >= 0.0) || !(r.band_hi_hz <= kPcmRate / 2) || !(r.band_lo_hz < r.band_hi_hz)) {
+    set_err("fmr_analyser_derive: band_lo_hz %g and band_hi_hz %g are not 0 <= lo < hi <= 24000 (0 = 20 and 15000)", r.band_lo_hz,
+            r.band_hi_hz);
+    return FMR_ERR_BAD_ARG;
+  }
+  const int k_lo = (int)std::ceil(r.band_lo_hz / bin_hz), k_hi = (int)std::floor(r.band_hi_hz / bin_hz);
+  const int B = k_hi - k_lo + 1;
+  if (B < 2 * W + 1) {
+    set_err("fmr_analyser_derive: band_lo_hz %g .. band_hi_hz %g holds %d bins of %g Hz, fewer than %d", r.band_lo_hz, r.band_hi_hz,
+            B, bin_hz, 2 * W + 1);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!(r.tone_hz >= 0.0) || !(r.tone_hz <= kPcmRate / 2)) {
+    set_err("fmr_analyser_derive: tone_hz %g is outside 0 .. 24000 (0 = the strongest bin)", r.tone_hz);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!(r.tone_search_hz > 0.0) || !std::isfinite(r.tone_search_hz)) {
+    set_err("fmr_analyser_derive: tone_search_hz %g is not a finite value > 0 (0 = 50)", r.tone_search_hz);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (r.max_harmonic < 2 || r.max_harmonic > 64) {
+    set_err("fmr_analyser_derive: max_harmonic %d is outside 2 .. 64 (0 = 10)", r.max_harmonic);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (r.reserved != 0) { set_err("fmr_analyser_derive: reserved is %d, not 0", r.reserved); return FMR_ERR_BAD_ARG; }
+  if (std::isnan(r.min_tone_dbfs)) { set_err("fmr_analyser_derive: min_tone_dbfs is not a number"); return FMR_ERR_BAD_ARG; }
+
+  // the pooled view
+  const size_t nb = (size_t)N / 2 + 1, nb3 = 3 * nb;
+  fmr_analyser_levels full{};
+  full.struct_size = (unsigned)sizeof full;
+  double seg = 0.0, s0 = 0.0, s1 = 0.0, q0 = 0.0, q1 = 0.0;
+  for (int i = 0; i < n; i++) {
+    seg += (double)recs[i].segments;
+    full.segments += recs[i].segments; full.skipped += recs[i].skipped; full.n_nonfinite += recs[i].n_nonfinite;
+    s0 += recs[i].sum[0]; s1 += recs[i].sum[1]; q0 += recs[i].sumsq[0]; q1 += recs[i].sumsq[1];
+  }
+  std::vector<double> P(nb, 0.0);
+  for (size_t k = 0; k < nb; k++) {
+    double pl = 0.0, pr = 0.0, pc = 0.0;
+    for (int i = 0; i < n; i++) {
+      const double w = (double)recs[i].segments;
+      const double *sp = spectra + (size_t)i * nb3;
+      pl += w * sp[k]; pr += w * sp[nb + k]; pc += w * sp[2 * nb + k];
+    }
+    if (seg > 0.0) { pl /= seg; pr /= seg; pc /= seg; }
+    P[k] = r.view == 0 ? pl : r.view == 1 ? pr : r.view == 2 ? (pl + pr + 2.0 * pc) / 4.0 : std::max(0.0, (pl + pr - 2.0 * pc) / 4.0);
+  }
+  auto db = [](double p) { return p > 0.0 ? 10.0 * std::log10(2.0 * p) : -INFINITY; };
+  const double frames = (double)(full.segments + full.skipped) * (double)(N / 2);
+  const double sv = r.view == 0 ? s0 : r.view == 1 ? s1 : r.view == 2 ? (s0 + s1) / 2.0 : (s0 - s1) / 2.0;
+  full.dc = frames > 0.0 ? sv / frames : 0.0;
+  full.total_dbfs = r.view >= 2 ? NAN : frames > 0.0 ? db((r.view == 0 ? q0 : q1) / frames) : -INFINITY;
+  double p_band = 0.0;
+  for (int k = k_lo; k <= k_hi; k++) p_band += P[k];
+  full.band_dbfs = db(p_band);
+
+  // the tone
+  int s_lo = k_lo, s_hi = k_hi;
+  if (r.tone_hz > 0.0) {
+    s_lo = std::max(k_lo, (int)std::ceil((r.tone_hz - r.tone_search_hz) / bin_hz));
+    s_hi = std::min(k_hi, (int)std::floor((r.tone_hz + r.tone_search_hz) / bin_hz));
+  }
+  int k0 = -1;
+  for (int k = s_lo; k <= s_hi; k++)
+    if (k0 < 0 || P[k] > P[k0]) k0 = k;
+  double p_t = 0.0, cen = 0.0;
+  if (k0 >= 0) {
+    k0 = std::min(std::max(k0, k_lo + W), k_hi - W);
+    for (int k = k0 - W; k <= k0 + W; k++) { p_t += P[k]; cen += (double)k * P[k]; }
+  }
+  const bool found = k0 >= 2 * W + 1 && p_t > 0.0 && db(p_t) >= r.min_tone_dbfs;
+  full.tone_found = found ? 1 : 0;
+  for (double &h : full.harmonic_dbc) h = NAN;
+  if (!found) {
+    full.tone_hz = full.tone_dbfs = full.thd = full.thd_n = full.sinad_db = NAN;
+    full.noise_dbfs = full.band_dbfs;
+    give_sized(out, out_size, full);
+    return FMR_OK;
+  }
+  full.tone_hz = cen / p_t * bin_hz;
+  full.tone_dbfs = db(p_t);
+  std::vector<char> taken(nb, 0);
+  int E = 0;
+  for (int k = k0 - W; k <= k0 + W; k++) { taken[k] = 1; E++; }
+  double p_h = 0.0;
+  for (int h = 2; h <= r.max_harmonic; h++) {
+    const int kh = (int)std::floor((double)h * full.tone_hz / bin_hz + 0.5);
+    if (kh + W > k_hi) break;
+    double ph = 0.0;
+    for (int k = kh - W; k <= kh + W; k++)
+      if (!taken[k]) { ph += P[k]; taken[k] = 1; E++; }
+    p_h += ph;
+    full.harmonics_counted++;
+    if (h <= 9) full.harmonic_dbc[h - 2] = ph > 0.0 ? 10.0 * std::log10(ph / p_t) : -INFINITY;
+  }
+  double p_free = 0.0;               // = P_band - P_t - P_h, without the cancellation
+  for (int k = k_lo; k <= k_hi; k++)
+    if (!taken[k]) p_free += P[k];
+  const double p_n = B > E ? p_free * (double)B / (double)(B - E) : 0.0;
+  full.noise_dbfs = db(p_n);
+  full.thd = std::sqrt(p_h / p_t);
+  full.thd_n = std::sqrt((p_h + p_n) / p_t);
+  full.sinad_db = p_h + p_n > 0.0 ? 10.0 * std::log10((p_t + p_h + p_n) / (p_h + p_n)) : INFINITY;
   give_sized(out, out_size, full);
   return FMR_OK;
 }

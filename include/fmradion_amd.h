@@ -724,6 +724,124 @@ int fmr_loudness_read(fmr_chain *c, int stream, fmr_loudness_record *recs, int c
  * trailing_silence_blocks the run that ends at the last record.  Loudness range (EBU 3342) is not computed. */
 int fmr_loudness_derive(const fmr_loudness_record *recs, int n, double silence_dbfs, fmr_loudness_levels *out, size_t out_size);
 
+/* --- Audio analyser: the spectrum analyser the reference's author judges receivers with, on the
+ * device.  A decoder chain of any mode with it enabled measures the finished audio of every stream / bank channel where
+ * the output mux wrote it: the level and frequency of a test tone, THD, THD+N, SINAD and the noise floor, per channel or
+ * in the mid / side view.  The audio, fmr_status, PPS events, RDS groups, every monitor's records and the output PCM of
+ * the chain are what they are without it: the stage only reads the audio.
+ * Input: 48 kHz doubles, a frame being one sample per channel; ch = 2 for a stereo chain (interleaved L/R), otherwise 1.
+ * Indices are absolute frame indices per stream, counted from the chain's first audio frame; nothing depends on the cut
+ * into blocks and calls.
+ *   N = fft_size, H = N / 2, M = interval_samples (a multiple of H).  Segment j covers the frames [j H, j H + N) and is
+ * processed in the call that delivers its last frame; record i covers [i M, (i + 1) M); segment j belongs to record
+ * floor(j H / M) (a record holds M / H segments, its last one reaches H frames into the next record).
+ * Time-domain part of a record, over the first H frames of each of its segments (every frame enters once): sum[c] and
+ * sumsq[c], fp64 sums of the samples and of their squares; a non-finite sample is counted in n_nonfinite (once per
+ * channel value) and enters as 0.0.  Channel-1 fields are 0 when ch = 1.
+ * Spectral part of a segment: each sample is rounded once to fp32 and multiplied by the fp32 window, the periodic 4-term
+ * Blackman-Harris w[n] = 0.35875 - 0.48829 cos(2 pi n / N) + 0.14128 cos(4 pi n / N) - 0.01168 cos(6 pi n / N), built in
+ * double and rounded once (the twiddles likewise).  One complex N-point FFT takes z[n] = wL[n] + i wR[n]; with X = Z[k]
+ * and Y = conj Z[(N - k) mod N] the channels are L[k] = (X + Y) / 2 and R[k] = (X - Y) / (2 i), k = 0 .. N / 2.  A record
+ * accumulates in fp64, over its counted segments, three rows of N / 2 + 1 bins: |L[k]|^2, |R[k]|^2 and
+ * C[k] = Re(L[k] conj R[k]).  With ch = 1 the imaginary input is 0, the first row is |Z[k]|^2 and the other two are 0.
+ * A segment that holds a sample which is not finite as fp32 is skipped for the spectral part and counted in `skipped`;
+ * `segments` counts the others.
+ * What fmr_analyser_read returns is scaled to POWER: row[k] c_k / (N sum w^2 segments), c_k = 2 for 0 < k < N / 2 and 1 at
+ * both ends (all zeros when segments = 0): a sine of amplitude A at any frequency sums to A^2 / 2 over its main lobe
+ * (+-4 bins), and white noise of variance v sums to v over all bins.
+ * Completion: record i is complete in the call that delivers the frame (i + 1) M + H - 1, the last frame of its last
+ * segment.
+ * Ring: max_records = L records per stream.  When L unread records exist and another completes, the oldest is
+ * overwritten and counted in records_dropped; processing never fails because of it.
+ * Device memory: the ring takes n_streams L 3 (N / 2 + 1) 8 bytes (3.1 MB per stream at the defaults, 100 MB for a
+ * 32-channel bank; 403 MB per stream at N = 8192 with L = 4096), the partial sums of a call up to 128 rows of
+ * 3 (N / 2 + 1) doubles per stream more.  Size L for the reader's period.
+ * Reproducibility: the integer fields are bit-identical for any cut of the input into calls; the sums add fixed
+ * per-segment values in fp64 in a fixed order without float atomics (the same cut gives the same bits; another cut
+ * differs at fp64 rounding). */
+typedef struct {
+  unsigned struct_size;       /* sizeof(fmr_analyser_config) as the caller knows it (0: cfg_size); a larger size is refused */
+  int fft_size;               /* N: 1024, 2048, 4096 or 8192; 0 = 4096 */
+  uint32_t interval_samples;  /* M: a multiple of N / 2 in N / 2 .. 2^24; 0 = 6 N */
+  int max_records;            /* L: 1 .. 4096; 0 = 64 */
+} fmr_analyser_config;
+typedef struct {
+  uint64_t index, first_sample;   /* i and i M */
+  uint32_t segments, skipped;     /* segments counted in the rows; segments skipped */
+  uint32_t n_nonfinite, channels; /* ch */
+  uint32_t fft_size, interval_samples;   /* N and M, so that records can be derived from by themselves */
+  double sum[2], sumsq[2];
+} fmr_analyser_record;
+typedef struct {
+  unsigned struct_size;
+  int channels;                   /* ch */
+  uint64_t records_complete;      /* since create (of every stream: they run in step) */
+  uint64_t records_dropped;       /* of this stream: overwritten unread */
+  uint64_t first_unread;          /* index of the oldest unread record after this call */
+  uint64_t records_ready;         /* complete records still unread after this call */
+  uint32_t interval_samples;      /* M, L and N as enabled (defaults filled in) */
+  int max_records;
+  int fft_size, bins;             /* N; N / 2 + 1 */
+  double bin_hz;                  /* 48000 / N */
+} fmr_analyser_info;
+/* What to measure (every 0 is the default named). */
+typedef struct {
+  unsigned struct_size;
+  int view;                       /* 0 = L (the only view of ch = 1 records), 1 = R, 2 = M: P = (P_L + P_R + 2 C) / 4,
+                                     3 = S: P = max(0, (P_L + P_R - 2 C) / 4) */
+  double band_lo_hz, band_hi_hz;  /* the measurement band: 0 = 20 and 0 = 15000; 0 <= lo < hi <= 24000 */
+  double tone_hz;                 /* 0 = the strongest bin of the band; otherwise the strongest bin within +- tone_search_hz */
+  double tone_search_hz;          /* 0 = 50 */
+  int max_harmonic;               /* 2 .. 64; 0 = 10 */
+  int reserved;                   /* must be 0 */
+  double min_tone_dbfs;           /* a tone below it is none; 0 = -60 */
+} fmr_analyser_rule;
+typedef struct {
+  unsigned struct_size;
+  int tone_found;                 /* 0: tone_hz, tone_dbfs, thd, thd_n, sinad_db and harmonic_dbc are NaN, noise_dbfs is the whole band */
+  double tone_hz;                 /* power centroid of the tone's lobe */
+  double tone_dbfs;               /* 10 log10(2 P_t): a full-scale sine reads 0 */
+  double thd;                     /* sqrt(P_h / P_t), a ratio (x 100 = per cent) */
+  double thd_n;                   /* sqrt((P_h + P_n) / P_t) */
+  double sinad_db;                /* 10 log10((P_t + P_h + P_n) / (P_h + P_n)); +INFINITY when P_h + P_n = 0 */
+  double noise_dbfs;              /* 10 log10(2 P_n); -INFINITY for 0 */
+  double band_dbfs;               /* 10 log10(2 P_band) */
+  double harmonic_dbc[8];         /* 10 log10(P of harmonic h / P_t), h = 2 .. 9; NaN where the harmonic is not counted */
+  double dc;                      /* mean of the view's samples: sum / frames (M and S: (sum_0 +- sum_1) / 2 / frames) */
+  double total_dbfs;              /* 10 log10(2 sumsq / frames) of view L or R; NaN for M and S (the records hold no sum L R) */
+  uint64_t segments, skipped, n_nonfinite;   /* pooled */
+  int harmonics_counted, reserved;
+} fmr_analyser_levels;
+/* Checks the fields first (FMR_ERR_BAD_ARG, fmr_last_error names the field; also a size larger than this library's
+ * struct), then the chain: NULL is FMR_ERR_BAD_ARG; any chain with a decoder is accepted (every mode, banks, pipelined
+ * or in_order); front-end-only chains (mode -1, channelizers) are FMR_ERR_UNSUPPORTED.  Allowed once, before the chain's
+ * first sample: a second call, or one after any processing call, is FMR_ERR_BAD_ARG.  A failed call leaves the chain as
+ * it was.  A chain that never calls it allocates nothing for the analyser and runs none of its kernels. */
+int fmr_enable_analyser(fmr_chain *c, const fmr_analyser_config *cfg, size_t cfg_size);
+/* Synchronises like the other getters, then drains up to cap complete records of `stream`, oldest first, and returns how
+ * many: recs[cap] and spectra[cap][3][N / 2 + 1], scaled to power as above (spectra may be NULL).  cap = 0 returns the
+ * number waiting and drains nothing; since no more than max_records can wait, one call with cap = max_records drains
+ * everything without asking first (every call synchronises the chain).  info (may be NULL) takes info_size bytes (0 = this header's size).
+ * FMR_ERR_BAD_ARG on a chain without the analyser. */
+int fmr_analyser_read(fmr_chain *c, int stream, fmr_analyser_record *recs, double *spectra, int cap,
+                      fmr_analyser_info *info, size_t info_size);
+/* Host only, in double, no device.  Pools the n records (spectra: n x 3 x (N / 2 + 1) as read) weighted by `segments`
+ * (all zeros when no segment was counted); records of unlike fft_size or channels, n < 1, a view other than 0 on ch = 1
+ * records and a rule field out of range are FMR_ERR_BAD_ARG (rule may be NULL: all defaults).
+ * With bin k at k 48000 / N Hz, the band is the bins ceil(band_lo N / 48000) .. floor(band_hi N / 48000), B of them (at
+ * least 9), P_band their sum, and W = 4 (the window's main lobe):
+ *   k0 = the strongest bin of the band (tone_hz = 0) or of the band's bins within tone_hz +- tone_search_hz (the first of
+ *   equals), clamped so that k0 - W .. k0 + W lie inside the band.  tone_found = 0 when there is no such bin, when
+ *   k0 < 2 W + 1, or when 10 log10(2 P_t) < min_tone_dbfs, with P_t = sum of P[k] over |k - k0| <= W.
+ *   tone_hz = (sum k P[k] / P_t) 48000 / N over the same bins.
+ *   Harmonic h = 2 .. max_harmonic has its lobe at k_h = floor(h tone_hz N / 48000 + 0.5), bins k_h - W .. k_h + W; the
+ *   first h whose lobe leaves the band ends the list.  A harmonic's power is the sum over those of its bins that no
+ *   earlier lobe holds; P_h sums the harmonics, E counts the bins of all lobes, the tone's included.
+ *   P_n = (P_band - P_t - P_h) B / (B - E)  (0 when B = E): the noise of the band's free bins (summed as such, not as
+ *   the difference), spread over the band. */
+int fmr_analyser_derive(const fmr_analyser_record *recs, const double *spectra, int n, const fmr_analyser_rule *rule,
+                        size_t rule_size, fmr_analyser_levels *out, size_t out_size);
+
 /* --- RF monitor (no counterpart in the reference).  An FM chain with it enabled measures the
  * received signal of every stream / bank channel where it lies on the device: level, C/N, the AM on the envelope
  * (multipath turns FM into AM: the 19 kHz line of the envelope is the classic indicator) and the depth of fades.  The
