@@ -2472,9 +2472,15 @@ __global__ __launch_bounds__(64) void k_pll(
 
 // ---------------------------------------------------------------------------
 // Audio resampler (AudioResampler.cpp:37-61 stand-in), FP64, two channels:
-// stage A integer decimation, stage B polyphase.  Sequential accumulation in
-// tap order (bit-comparable with the oracle).
+// stage A integer decimation, stage B polyphase.
+// The arithmetic of the audio tail's three FIRs (stage A, stage B, the pilot cut), in every kernel form: one output is
+// the chain acc = fma(h[k], x[top - k], acc), k ascending from acc = 0 -- the oracle's tap order with one rounding per
+// tap instead of two (the build keeps -ffp-contract=off, so the fusion is spelled out here).  Half the VALU
+// instructions of a multiply and an add, on the pipe the PLL passes of the next call issue on; and calls of any shape
+// (tiled, plain, serial environment) produce the same bits as each other.
 // ---------------------------------------------------------------------------
+__device__ __forceinline__ double fir_step(double h, double x, double acc) { return fma(h, x, acc); }
+
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_aud_decim(
     const double *__restrict__ x0, const double *__restrict__ x1, long long x_stride, int x_off,
@@ -2487,16 +2493,16 @@ __global__ __launch_bounds__(BLOCK) void k_aud_decim(
   double *y = (ch ? y1 : y0) + (long long)s * y_stride + y_off;
   const double *xp = x + top0 + (long long)m * D - (NA - 1);   // oldest tap first in memory
   double acc = 0.0;
-  // acc += hA[k] * x[top - k], k ascending: walk memory backwards, 8 loads in flight
+  // fir_step over hA[k], x[top - k], k ascending: walk memory backwards, 8 loads in flight
   int k = 0;
   for (; k + 8 <= NA; k += 8) {
     double xv[8], hv[8];
 #pragma unroll
     for (int u = 0; u < 8; u++) { xv[u] = xp[(NA - 1) - (k + u)]; hv[u] = hA[k + u]; }
 #pragma unroll
-    for (int u = 0; u < 8; u++) acc += hv[u] * xv[u];
+    for (int u = 0; u < 8; u++) acc = fir_step(hv[u], xv[u], acc);
   }
-  for (; k < NA; k++) acc += hA[k] * xp[(NA - 1) - k];
+  for (; k < NA; k++) acc = fir_step(hA[k], xp[(NA - 1) - k], acc);
   y[m] = acc;
 }
 
@@ -2516,7 +2522,7 @@ __global__ __launch_bounds__(BLOCK) void k_aud_poly(
   const double *h = hB + (size_t)p * TB;
   const double *xp = mid + (nk - (TB >> 1) + 1 - mid_abs0);
   double acc = 0.0;
-  serial_prefetch2<8>(h, xp, 0, TB, [&](int, double hv, double xv) { acc += hv * xv; });
+  serial_prefetch2<8>(h, xp, 0, TB, [&](int, double hv, double xv) { acc = fir_step(hv, xv, acc); });
   y[k] = acc;
 }
 
@@ -2577,13 +2583,13 @@ __global__ __launch_bounds__(BLOCK) void k_aud_poly2(
 #pragma unroll
     for (int u = 0; u < 8; u++)
 #pragma unroll
-      for (int p = 0; p < LBT; p++) acc[p] += hv[p][u] * xv[p][u];      // same order as the oracle
+      for (int p = 0; p < LBT; p++) acc[p] = fir_step(hv[p][u], xv[p][u], acc[p]);      // same order as the oracle
   }
   for (; j < TB; j++) {
 #pragma unroll
     for (int p = 0; p < LBT; p++) {
       const int jj = off[p] + j;
-      acc[p] += hB[(size_t)phi[p] * TB + j] * lds_ap[(jj % MB) * ni_pad + tid + jj / MB];
+      acc[p] = fir_step(hB[(size_t)phi[p] * TB + j], lds_ap[(jj % MB) * ni_pad + tid + jj / MB], acc[p]);
     }
   }
   const long long kb = (Pt + tid) * LBT - k0;
@@ -2612,11 +2618,12 @@ __global__ __launch_bounds__(BLOCK) void k_pilotcut(
   for (int i = threadIdx.x; i < n; i += BLOCK) {
     double acc = 0.0;
     if (i < order) {
-      for (int j = i + 1; j <= order; j++) acc += x[i - j] * coeff[j];
-      for (int j = 1; j <= i; j++) acc += x[i - j] * coeff[j];
+      for (int j = i + 1; j <= order; j++) acc = fir_step(coeff[j], x[i - j], acc);
+      for (int j = 1; j <= i; j++) acc = fir_step(coeff[j], x[i - j], acc);
     } else {
-      for (int k = 0; k <= half_order; k++) acc += (x[i - k] + x[i - (order - k)]) * coeff[k];
-      if ((order % 2) == 0) acc += x[i - order / 2] * coeff[order / 2];
+      // the body as one chain over all taps, k ascending; the far half takes the near half's coefficients, as the
+      // reference's folded sum (x[i - k] + x[i - (order - k)]) * coeff[k] does
+      for (int k = 0; k <= order; k++) acc = fir_step(coeff[min(k, order - k)], x[i - k], acc);
     }
     y[i] = acc;
   }
@@ -2649,13 +2656,16 @@ __global__ __launch_bounds__(BLOCK) void k_pilotcut2(
       const double *xc = xs + r + order;      // xc[-j] = x[i - j]
       double acc = 0.0;
       if (i < order) {
-        for (int j = i + 1; j <= order; j++) acc += xc[-j] * cs[j];
-        for (int j = 1; j <= i; j++) acc += xc[-j] * cs[j];
+        for (int j = i + 1; j <= order; j++) acc = fir_step(cs[j], xc[-j], acc);
+        for (int j = 1; j <= i; j++) acc = fir_step(cs[j], xc[-j], acc);
       } else {
-        // body taps are wave-uniform: scalar loads, not LDS traffic (the kernel is LDS-bandwidth bound)
+        // body taps are wave-uniform: scalar loads, not LDS traffic (the kernel is LDS-bandwidth bound).  One chain over
+        // all taps, k ascending (k_pilotcut); the near half, the middle tap of an even order, then the far half
 #pragma unroll 8
-        for (int k = 0; k <= half_order; k++) acc += (xc[-k] + xc[-(order - k)]) * coeff[k];
-        if ((order % 2) == 0) acc += xc[-(order / 2)] * coeff[order / 2];
+        for (int k = 0; k <= half_order; k++) acc = fir_step(coeff[k], xc[-k], acc);
+        if ((order % 2) == 0) acc = fir_step(coeff[order / 2], xc[-(order / 2)], acc);
+#pragma unroll 8
+        for (int k = half_order; k >= 0; k--) acc = fir_step(coeff[k], xc[-(order - k)], acc);
       }
       y[i] = acc * out_gain;     // 1.0 for the FM pilot cut (exact); NbfmDecoder's -3 dB (Utility.h:307-312)
     }

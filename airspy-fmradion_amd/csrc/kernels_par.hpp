@@ -89,7 +89,7 @@ __global__ void k_deemph_par(const fm_mpx_t *__restrict__ in0 /* MPX */, const d
 // affine maps (A^LPL, e) -> true start state per lane, (3) the lane replays its samples with the
 // reference's arithmetic.  Only the start state goes through the re-associated scan (a few ulp,
 // decaying like A^n); the far end of the warm-up starts from 0 (A^768 = 4e-18).
-// FIR: acc += hA[k] * x[top-k], k ascending (same order as k_aud_decim / the oracle).
+// FIR: acc = fir_step(hA[k], x[top-k], acc), k ascending (the same chain as k_aud_decim, the oracle's tap order).
 // ---------------------------------------------------------------------------
 // 15, not 16: the workgroup's tile is then 256 x 15 doubles = 30.7 KB, and TWO of them fit beside the five one-wave
 // workgroups (18.4 KB each) a PLL integration pass keeps on every compute unit -- with 16 samples per lane (34.8 KB with the
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(BLOCK) void k_deemph_decim(
 #pragma unroll
         for (int i = 0; i < R; i++) {
           const int k = u - (R - 1 - i) * D_T;       // tap of output r0+i that meets this sample
-          if (k >= 0 && k < NA_T) acc[i] += hA[k] * xv;
+          if (k >= 0 && k < NA_T) acc[i] = fir_step(hA[k], xv, acc[i]);
         }
       }
 #pragma unroll
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(BLOCK) void k_deemph_decim(
       const int jt = FMR_DE_WARMUP + (NA - 1) + r * D;
       double acc = 0.0;
 #pragma unroll 4
-      for (int k = 0; k < NA; k++) acc += hA[k] * de_xs[de_idx(jt - k)];
+      for (int k = 0; k < NA; k++) acc = fir_step(hA[k], de_xs[de_idx(jt - k)], acc);
       y[m0 + r] = acc;
     }
   }
@@ -1119,15 +1119,32 @@ __global__ __launch_bounds__(64) void k_pll_shoot(const fm_mpx_t *__restrict__ b
   // before: their waves win the issue arbitration (round 6: 0.4742 -> 0.4711 ms per step over four interleaved 100-step
   // runs each; without the tail stage the step is 0.4465)
   __builtin_amdgcn_s_setprio(3);
-  for (int i = threadIdx.x; i < 257; i += blockDim.x) tab[i] = atan_tab[i];
   const int lane = threadIdx.x;
   const int c = blockIdx.x * blockDim.x + lane;
   const int s = blockIdx.y;
-  if (fl[s].pll_converged) return;          // uniform: every workgroup of the stream leaves
   const bool valid = c < ct.nck;
   const int cc = valid ? c : ct.nck - 1;
-  const int n = valid ? ct.len[cc] : 0;
+  // Everything the head reads from memory -- the stream's flag, the chunk's length and offset, its start node and the
+  // atan table -- is in flight together and waited for once: behind the test of the flag the same loads were a second
+  // dependent round trip at the head of every pass.  Same addresses as before, whatever the flag says.
+  const int done = fl[s].pll_converged;
+  float tabv[5];
+#pragma unroll
+  for (int u = 0; u < 5; u++) tabv[u] = atan_tab[min(lane + 64 * u, 256)];
+  const int len_c = ct.len[cc];
   const int off = ct.off[cc];
+  const double *nd = nodes + ((long long)s * (ct.nck + 1) + cc) * 7;
+  const bool nodes_from_sweep = !JAC && dn.PRE != nullptr;      // (the down-sweep below writes `nodes`: not read here then)
+  double nd0[7];
+#pragma unroll
+  for (int k = 0; k < 7; k++) nd0[k] = nodes_from_sweep ? 0.0 : nd[k];
+  // (the compiler would otherwise sink the loads behind the branch, next to their first use)
+  asm volatile("" ::"v"(tabv[0]), "v"(tabv[1]), "v"(tabv[2]), "v"(tabv[3]), "v"(tabv[4]), "v"(len_c), "v"(off), "v"(nd0[0]),
+               "v"(nd0[1]), "v"(nd0[2]), "v"(nd0[3]), "v"(nd0[4]), "v"(nd0[5]), "v"(nd0[6]));
+  if (done) return;                         // uniform: every workgroup of the stream leaves
+#pragma unroll
+  for (int u = 0; u < 5; u++) if (lane + 64 * u < 257) tab[lane + 64 * u] = tabv[u];
+  const int n = valid ? len_c : 0;
   s_off[lane] = off; s_len[lane] = n;
   int nmax = n;
 #pragma unroll
@@ -1136,7 +1153,6 @@ __global__ __launch_bounds__(64) void k_pll_shoot(const fm_mpx_t *__restrict__ b
   double *ob = raw + (long long)s * raw_stride + raw_off;
   double rmax = 0.0;
   PllRegs S;
-  const double *nd = nodes + ((long long)s * (ct.nck + 1) + cc) * 7;
   double nxt[7];                             // start node of the NEXT chunk (the boundary mismatch at the end)
   if (!JAC && dn.PRE) {
     // ---- the node pass's down-sweep for this wave's two groups of 32 chunks, here: k_pll_down was a launch of its own
@@ -1176,7 +1192,7 @@ __global__ __launch_bounds__(64) void k_pll_shoot(const fm_mpx_t *__restrict__ b
     __syncthreads();
   } else {
 #pragma unroll
-    for (int k = 0; k < 7; k++) { S.v[k] = nd[k]; nxt[k] = 0.0; }
+    for (int k = 0; k < 7; k++) { S.v[k] = nd0[k]; nxt[k] = 0.0; }
   }
   const bool nxt_in_regs = !JAC && dn.PRE != nullptr;       // (else the next chunk's start node is read where it is needed)
   if (wave_first && lane == 0) {
