@@ -85,19 +85,27 @@ struct ChainShape {
 };
 
 // ---- DC block: A = [[-a1, -a2], [1, 0]] acts on (w[n-1], w[n-2]); A^chunk by repeated multiplication, then the node
-// scan's lane-group transitions (A^(chunk K))^(2^k).  (The order of the products is part of the result: bit for bit.)
-static void mat2_mul(const double *x, const double *y, double *z) {      // z = x y, row-major 2 x 2; z may be x or y
-  const double t[4] = {x[0] * y[0] + x[1] * y[2], x[0] * y[1] + x[1] * y[3], x[2] * y[0] + x[3] * y[2], x[2] * y[1] + x[3] * y[3]};
+// scan's lane-group transitions (A^(chunk K))^(2^k).  The poles of FM's DC block lie 4.4e-4 from 1 and from each other: A^n has
+// entries of n r^n (830 at n = 2048) that cancel on a state whose two words are nearly equal, and a chain of n products in
+// double leaves it n^2 2^-53 wrong (4e-10 of A^2048: 130 ulp of the DC block's state in the audio).  So the
+// powers are formed in long double (n^2 2^-64) and handed to the kernel as the double next to each entry plus what that
+// double leaves (k_dc_nodes: mv2c).
+static void mat2_mul(const long double *x, const long double *y, long double *z) {      // z = x y, row-major 2 x 2; z may be x or y
+  const long double t[4] = {x[0] * y[0] + x[1] * y[2], x[0] * y[1] + x[1] * y[3], x[2] * y[0] + x[3] * y[2], x[2] * y[1] + x[3] * y[3]};
   for (int j = 0; j < 4; j++) z[j] = t[j];
 }
 static DcCoef make_dc_coef(const BiquadCoef &q, int chunk) {
-  DcCoef k{q.b0, q.b1, q.b2, q.a1, q.a2, {1, 0, 0, 1}, {}};
-  const double a[4] = {-q.a1, -q.a2, 1.0, 0.0};
-  for (int i = 0; i < chunk; i++) mat2_mul(a, k.ac, k.ac);
-  double gk[4] = {1, 0, 0, 1};
-  for (int i = 0; i < FMR_DC_K; i++) mat2_mul(k.ac, gk, gk);          // A^(C*K)
+  DcCoef k{q.b0, q.b1, q.b2, q.a1, q.a2, {}, {}, {}, {}};
+  const long double a[4] = {-(long double)q.a1, -(long double)q.a2, 1.0L, 0.0L};
+  long double ac[4] = {1, 0, 0, 1}, gk[4] = {1, 0, 0, 1};
+  auto put = [](const long double *m, double *hi, double *lo) {
+    for (int j = 0; j < 4; j++) { hi[j] = (double)m[j]; lo[j] = (double)(m[j] - (long double)hi[j]); }
+  };
+  for (int i = 0; i < chunk; i++) mat2_mul(a, ac, ac);
+  put(ac, k.ac, k.ac_lo);
+  for (int i = 0; i < FMR_DC_K; i++) mat2_mul(ac, gk, gk);          // A^(C*K)
   for (int lv = 0; lv < 6; lv++) {
-    for (int j = 0; j < 4; j++) k.agp[lv][j] = gk[j];
+    put(gk, k.agp[lv], k.agp_lo[lv]);
     mat2_mul(gk, gk, gk);
   }
   return k;

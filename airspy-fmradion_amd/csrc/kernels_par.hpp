@@ -222,6 +222,7 @@ struct DcCoef {
   double b0, b1, b2, a1, a2;
   double ac[4];        // A^C row-major: state transition over one chunk
   double agp[6][4];    // (A^(C*K))^(2^k), k = 0..5: transitions over 1,2,4,..,32 lane groups
+  double ac_lo[4], agp_lo[6][4];   // what the doubles above leave of the powers (make_dc_coef)
 };
 
 template <int C>
@@ -250,6 +251,17 @@ __device__ __forceinline__ void mv2(const double *m, double x1, double x2, doubl
   y1 = m[0] * x1 + m[1] * x2;
   y2 = m[2] * x1 + m[3] * x2;
 }
+// M x for a transition M = hi + lo over n samples.  M's entries are of size n r^n and the state's two words nearly equal: the
+// two products of a row cancel, and rounded one by one they leave n ulp of the state in a chunk's start state, which the audio
+// shows (its second difference).  Here a row's sum is rounded once: h1 x2 = p + e exactly, fma(h0, x1, p) the rounded sum.
+__device__ __forceinline__ double mv2c_row(double h0, double h1, double l0, double l1, double x1, double x2) {
+  const double p = h1 * x2, e = fma(h1, x2, -p);
+  return (fma(h0, x1, p) + e) + (l0 * x1 + l1 * x2);
+}
+__device__ __forceinline__ void mv2c(const double *h, const double *l, double x1, double x2, double &y1, double &y2) {
+  y1 = mv2c_row(h[0], h[1], l[0], l[1], x1, x2);
+  y2 = mv2c_row(h[2], h[3], l[2], l[3], x1, x2);
+}
 __global__ __launch_bounds__(64 * FMR_DC_MAXW) void k_dc_nodes(const double *__restrict__ G, double *__restrict__ start, int nc,
                                                     DcCoef k, StreamState *st, int n_streams, int nch) {
   // blockDim.x = 64 * NW: the NW waves take consecutive 64*K-chunk segments of a pass, scan them with a zero
@@ -266,7 +278,7 @@ __global__ __launch_bounds__(64 * FMR_DC_MAXW) void k_dc_nodes(const double *__r
   double c2 = ch ? st[s].dc_st_x2 : st[s].dc_mono_x2;
   if (nch == 0) { c1 = st[s].am_dc_x1; c2 = st[s].am_dc_x2; }   // AmDecoder's DC block (one channel, its own state)
   constexpr int K = FMR_DC_K;
-  // AG^64 = (AG^32)^2: transition over one wave segment
+  // AG^64 = (AG^32)^2: transition over one wave segment (FM: 2^17 samples, entries of 1e-20 -- plain products do)
   double ag64[4];
   {
     const double *x = k.agp[5];
@@ -290,7 +302,7 @@ __global__ __launch_bounds__(64 * FMR_DC_MAXW) void k_dc_nodes(const double *__r
       const int c = cb + j;
       if (c < nc) {
         double n1, n2;
-        mv2(k.ac, q1, q2, n1, n2);
+        mv2c(k.ac, k.ac_lo, q1, q2, n1, n2);
         q1 = n1 + g1[j]; q2 = n2 + g2[j];
       }
       // past the end: identity step would need A^-C; lanes past nc are never read back
@@ -302,7 +314,7 @@ __global__ __launch_bounds__(64 * FMR_DC_MAXW) void k_dc_nodes(const double *__r
       const double p1 = __shfl_up(q1, o_, 64), p2 = __shfl_up(q2, o_, 64);
       if (lane >= o_) {
         double m1, m2;
-        mv2(k.agp[lv], p1, p2, m1, m2);
+        mv2c(k.agp[lv], k.agp_lo[lv], p1, p2, m1, m2);
         q1 += m1; q2 += m2;
       }
     }
@@ -321,7 +333,7 @@ __global__ __launch_bounds__(64 * FMR_DC_MAXW) void k_dc_nodes(const double *__r
     double t1 = w1, t2 = w2;
 #pragma unroll
     for (int lv = 0; lv < 6; lv++) {
-      if (lane & (1 << lv)) { double m1, m2; mv2(k.agp[lv], t1, t2, m1, m2); t1 = m1; t2 = m2; }
+      if (lane & (1 << lv)) { double m1, m2; mv2c(k.agp[lv], k.agp_lo[lv], t1, t2, m1, m2); t1 = m1; t2 = m2; }
     }
     double x1 = t1 + e1, x2 = t2 + e2;
 #pragma unroll
@@ -330,7 +342,7 @@ __global__ __launch_bounds__(64 * FMR_DC_MAXW) void k_dc_nodes(const double *__r
       if (c < nc) {
         *reinterpret_cast<double2 *>(o + 2 * (long long)c) = make_double2(x1, x2);
         double n1, n2;
-        mv2(k.ac, x1, x2, n1, n2);
+        mv2c(k.ac, k.ac_lo, x1, x2, n1, n2);
         x1 = n1 + g1[j]; x2 = n2 + g2[j];
       }
     }
