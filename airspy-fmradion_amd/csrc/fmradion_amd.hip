@@ -32,6 +32,7 @@
 #include "kernels_decim16.hpp"
 #include "kernels_chanbank.hpp"
 #include "kernels_rds.hpp"
+#include "welch_plan.hpp"
 #include "kernels_spectrum.hpp"
 #include "kernels_monitor.hpp"
 #include "kernels_loudness.hpp"
@@ -218,17 +219,15 @@ struct SegMonitor {
   unsigned interval = 0;                     // samples per record
   int bins = 0;                              // histogram counters per record
   double hist_range = 0.0;                   // modulation monitor: the histogram covers +- this (the RF monitor's bin rule takes none)
-  int spr = 0, sub = 0, sb = 0, rmax = 0;    // segments per record / per sub-block, sub-blocks per record, runs per stream and launch
-  int par = 0;                               // which copy of the open records is current
+  WelchSched ws;                             // the partition, the open records' parity, samples seen, segments processed
   double sumw2 = 0.0;
-  long long n = 0, next_seg = 0;             // samples seen, segments processed
   DevBuf<float> d_win, d_carry;
   DevBuf<float2> d_tw;
   DevBuf<double> d_ppsd, d_open_psd, d_ring_psd;
   DevBuf<unsigned> d_phist, d_open_hist, d_ring_hist;
   DevBuf<MonRec> d_prec, d_open_rec, d_ring_rec;
   RecCursor cur;
-  unsigned long long done() const { return (unsigned long long)(next_seg / spr); }   // records complete
+  unsigned long long done() const { return ws.done(); }
   int init(int S, size_t max_if, unsigned interval_samples, int hist_bins, double range, int max_records);
 };
 // both monitors' kernels (k_mon_seg<Src>, k_mon_reduce<Src>) as seg_stage takes them
@@ -287,19 +286,17 @@ struct AnalyserStage {
   bool on = false;
   fmr_analyser_config cfg{};                 // the defaults filled in
   int N = 0, H = 0, nb = 0, logn = 0;        // fft_size, hop, bins per row = N / 2 + 1
-  int spr = 0, sub = 0, sb = 0, rmax = 0;    // segments per record / per sub-block, sub-blocks per record, runs per stream and launch
-  int par = 0;                               // which copy of the open records is current
+  WelchSched ws;                             // the partition, the open records' parity, frames seen, segments processed
   int threads = 0, lds = 0;                  // of k_an_seg at this N
   AnSegFn kseg = nullptr;
   double sumw2 = 0.0;
-  long long n = 0, next_seg = 0;             // audio frames seen, segments processed
   DevBuf<float> d_win;
   DevBuf<float2> d_tw;
   DevBuf<double> d_carry, d_ppsd, d_open_psd, d_ring_psd;
   DevBuf<AnPart> d_ppart;
   DevBuf<AnRec> d_open_rec, d_ring_rec;
   RecCursor cur;
-  unsigned long long done() const { return (unsigned long long)(next_seg / spr); }   // records complete
+  unsigned long long done() const { return ws.done(); }
   int init(int S, size_t max_au, const fmr_analyser_config &m);
 };
 
@@ -860,6 +857,32 @@ static int build_stage(St &into, A &&...args) {
   return FMR_OK;
 }
 
+// The end of every fmr_enable_*, once the configuration has passed and the chain is there and fits: the stage is not on
+// yet and no call has been made; then it is built on the chain's device from args (St::init's).  `what` names the stage,
+// `first` what it counts from.
+template <class St, class... A>
+static int enable_stage(const char *fn, fmr_chain *c, St &stage, const char *what, const char *first, A &&...args) {
+  if (stage.on) { set_err("%s: the %s of this chain is already enabled", fn, what); return FMR_ERR_BAD_ARG; }
+  if (c->call_seq != 0) {
+    set_err("%s: the chain has already taken samples (the %s counts from the chain's first %s)", fn, what, first);
+    return FMR_ERR_BAD_ARG;
+  }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    return build_stage(stage, args...);
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+// The reader's view of stream s of a record ring, after a read, into a *_info: records complete, records overwritten
+// unread, the next unread one and how many wait.
+template <class Info>
+static void ring_info(Info &i, const RecCursor &cur, int s, unsigned long long done) {
+  i.records_complete = done;
+  i.records_dropped = cur.dropped[s];
+  i.first_unread = cur.read[s];
+  i.records_ready = done - cur.read[s];
+}
+
 template <class T>
 static int upload(DevBuf<T> &b, const T *src, size_t n) {
   int rc = b.alloc(n);
@@ -893,6 +916,13 @@ static int first_part_block(const int *if_len, int nb) {
 // ---- create, the build step: small helpers, the tables (each a function of what it needs), then the chain stage by stage
 template <class T>
 static int upload(DevBuf<T> &b, const std::vector<T> &v) { return upload(b, v.data(), v.size()); }
+// the window and the twiddles of a Welch stage (welch_tables)
+static int upload_welch(const WelchTables &t, DevBuf<float> &d_win, DevBuf<float2> &d_tw) {
+  static_assert(sizeof(WelchCpx) == sizeof(float2) && FMR_WINDOW_HANN == kWelchHann && FMR_WINDOW_RECT == kWelchRect &&
+                FMR_WINDOW_BLACKMAN_HARRIS == kWelchBlackmanHarris, "welch_plan.hpp's float2 and window kinds");
+  if (int rc = upload(d_win, t.win)) return rc;
+  return upload(d_tw, reinterpret_cast<const float2 *>(t.tw.data()), t.tw.size());
+}
 
 // zeroed buffers for a list of (buffer, count) pairs; the first error ends it
 static int alloc_all() { return FMR_OK; }
@@ -2634,91 +2664,66 @@ int SegMonitor::init(int S, size_t max_if, unsigned interval_samples, int hist_b
   interval = interval_samples;
   bins = hist_bins;
   hist_range = range;
-  spr = (int)(interval / kMonH);
-  // a full call in about 512 runs per stream: sub-blocks of 4 .. 32 segments (a run is a workgroup's serial work, and the
-  // partition only moves the fp64 rounding of the sums)
-  const size_t max_seg = max_if / kMonH + 2;
-  sub = (int)std::min<size_t>(kMonSubMax, std::max<size_t>(kMonSubMin, (max_seg + 511) / 512));
-  sb = (spr + sub - 1) / sub;
-  rmax = (int)std::min<size_t>(1024, max_seg / sub + 2 * (max_seg / spr + 2) + 2);
-  std::vector<float> w(kMonN);
-  std::vector<float2> tw(kMonN);
-  sumw2 = 0.0;
-  for (int i = 0; i < kMonN; i++) {
-    w[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / kMonN));
-    sumw2 += (double)w[i] * (double)w[i];
-    tw[i] = make_float2((float)std::cos(2.0 * M_PI * i / kMonN), (float)-std::sin(2.0 * M_PI * i / kMonN));
-  }
-  const size_t B = (size_t)bins, L = (size_t)max_records, rows = (size_t)S * rmax;
+  ws = welch_size(kMonH, interval, max_if, kMonSubMin, kMonSubMax, 512, 1024);
+  const WelchTables t = welch_tables(kMonN, kWelchHann);
+  sumw2 = t.sumw2;
+  const size_t B = (size_t)bins, L = (size_t)max_records, rows = (size_t)S * ws.rmax;
   int rc;
-  if ((rc = upload(d_win, w.data(), w.size()))) return rc;
-  if ((rc = upload(d_tw, tw.data(), tw.size()))) return rc;
-  if ((rc = d_carry.alloc((size_t)S * kMonN))) return rc;
-  if ((rc = d_ppsd.alloc(rows * kMonPsd))) return rc;
-  if ((rc = d_phist.alloc(rows * B))) return rc;
-  if ((rc = d_prec.alloc(rows))) return rc;
-  if ((rc = d_open_psd.alloc(2 * (size_t)S * kMonPsd))) return rc;
-  if ((rc = d_open_hist.alloc(2 * (size_t)S * B))) return rc;
-  if ((rc = d_open_rec.alloc(2 * (size_t)S))) return rc;
-  if ((rc = d_ring_psd.alloc((size_t)S * L * kMonPsd))) return rc;
-  if ((rc = d_ring_hist.alloc((size_t)S * L * B))) return rc;
-  if ((rc = d_ring_rec.alloc((size_t)S * L))) return rc;
+  if ((rc = upload_welch(t, d_win, d_tw))) return rc;
+  if ((rc = alloc_all(d_carry, (size_t)S * kMonN, d_ppsd, rows * kMonPsd, d_phist, rows * B, d_prec, rows,
+                      d_open_psd, 2 * (size_t)S * kMonPsd, d_open_hist, 2 * (size_t)S * B, d_open_rec, 2 * (size_t)S,
+                      d_ring_psd, (size_t)S * L * kMonPsd, d_ring_hist, (size_t)S * L * B, d_ring_rec, (size_t)S * L)))
+    return rc;
   cur.reset(S, max_records);
-  n = next_seg = 0;
-  par = 0;
   on = true;
   return FMR_OK;
 }
 
-// The next launch of a monitor's stage: the segments [j, a.a1) of the call's [j, j_hi) that fit into rmax runs per
-// stream, the runs and the records they touch.  j >= j_hi: no segment is left (runs = 0, one block per stream for the
-// carry).
-static void mon_plan_launch(MonArgs &a, long long j, long long j_hi, int rmax, int &runs, int &nrec) {
-  runs = 0; nrec = 1;
-  a.a0 = a.a1 = j; a.g0 = 0;
-  if (j >= j_hi) return;
-  const long long l = j / a.spr;
-  a.g0 = l * a.sb + (j - l * a.spr) / a.sub;
-  long long lo, hi;
-  mon_sub(a.spr, a.sub, a.sb, a.g0 + rmax - 1, lo, hi);
-  a.a1 = std::min(j_hi, hi);
-  const long long l_end = (a.a1 - 1) / a.spr;
-  runs = (int)(l_end * a.sb + (a.a1 - 1 - l_end * a.spr) / a.sub - a.g0 + 1);
-  nrec = (int)(l_end - l + 1);
+// One call's N samples per stream through a stage of the Welch segment engine (FFT size fft, hop `hop`): the segments whose
+// last sample the call delivers, in launches of at most w.rmax runs per stream.  `a` carries the launch's fields to the
+// kernels; seg(runs) launches the segment kernel, reduce(runs, nrec, n1, last) the reduce kernel, which refreshes the
+// carry in the call's last launch (that one may have no segment: runs = 0).
+template <class Args, class Seg, class Reduce>
+static void welch_call(WelchSched &w, Args &a, int fft, int hop, long long N, Seg &&seg, Reduce &&reduce) {
+  const long long n1 = w.n + N;
+  const long long j_hi = n1 >= fft ? (n1 - fft) / hop + 1 : 0;
+  a.n0 = w.n; a.spr = w.spr; a.sub = w.sub; a.sb = w.sb;
+  long long j = w.next_seg;
+  do {
+    const WelchLaunch p = welch_plan(w.spr, w.sub, w.sb, w.rmax, j, j_hi);
+    a.a0 = j; a.a1 = p.a1; a.g0 = p.g0;
+    if (p.runs > 0) seg(p.runs);
+    j = p.a1;
+    reduce(p.runs, p.nrec, n1, (int)(j >= j_hi));
+    if (p.runs > 0) w.par ^= 1;
+  } while (j < j_hi);
+  w.next_seg = std::max(w.next_seg, j_hi);
+  w.n = n1;
 }
 
 // One call's samples (N per stream: the MPX in the base slot, or the decoder's input in the IF ring slot) through monitor
-// m, on stream st: the segments whose last sample the call delivers, in launches of at most m.rmax runs per stream, then
-// the carry.
+// m, on stream st.
 int fmr_chain::seg_stage(SegMonitor &m, const void *from, long long stride, int off, float rf, float scale, MonSegFn kseg,
                          MonReduceFn kreduce, const char *seg_name, const char *reduce_name, long long N, hipStream_t st) {
   if (N <= 0) return FMR_OK;
-  const long long n0 = m.n, n1 = n0 + N;
-  const long long j_hi = n1 >= kMonN ? (n1 - kMonN) / kMonH + 1 : 0;
   MonArgs a{};
-  a.n0 = n0; a.spr = m.spr; a.sub = m.sub; a.sb = m.sb; a.bins = m.bins;
-  a.rf = rf; a.scale = scale;
-  const int L = (int)m.cur.L;
+  a.bins = m.bins; a.rf = rf; a.scale = scale;
+  const int L = (int)m.cur.L, rmax = m.ws.rmax;
   const long long M = (long long)m.interval;
-  long long j = m.next_seg;
-  do {
-    int runs, nrec;
-    mon_plan_launch(a, j, j_hi, m.rmax, runs, nrec);
-    if (runs > 0)
+  welch_call(m.ws, a, kMonN, kMonH, N,
+    [&](int runs) {
       timed_on(st, seg_name, [&] {
         hipLaunchKernelGGL(kseg, dim3(runs, S), dim3(kMonT), 0, st, from, stride, off, m.d_carry.p, a, m.d_win.p, m.d_tw.p,
-                           m.rmax, m.d_ppsd.p, m.d_phist.p, m.d_prec.p);
+                           rmax, m.d_ppsd.p, m.d_phist.p, m.d_prec.p);
       });
-    j = a.a1;
-    timed_on(st, reduce_name, [&] {
-      hipLaunchKernelGGL(kreduce, dim3(nrec, S), dim3(kMonT), 0, st, m.d_ppsd.p, m.d_phist.p, m.d_prec.p, runs, m.rmax, a, L,
-                         M, m.par, m.d_open_psd.p, m.d_open_hist.p, m.d_open_rec.p, m.d_ring_psd.p, m.d_ring_hist.p,
-                         m.d_ring_rec.p, from, stride, off, m.d_carry.p, n1, (int)(j >= j_hi));
+    },
+    [&](int runs, int nrec, long long n1, int last) {
+      timed_on(st, reduce_name, [&] {
+        hipLaunchKernelGGL(kreduce, dim3(nrec, S), dim3(kMonT), 0, st, m.d_ppsd.p, m.d_phist.p, m.d_prec.p, runs, rmax, a, L,
+                           M, m.ws.par, m.d_open_psd.p, m.d_open_hist.p, m.d_open_rec.p, m.d_ring_psd.p, m.d_ring_hist.p,
+                           m.d_ring_rec.p, from, stride, off, m.d_carry.p, n1, last);
+      });
     });
-    if (runs > 0) m.par ^= 1;
-  } while (j < j_hi);
-  m.next_seg = std::max(m.next_seg, j_hi);
-  m.n = n1;
   HIPCHK(hipGetLastError());
   return FMR_OK;
 }
@@ -2846,81 +2851,41 @@ int AnalyserStage::init(int S, size_t max_au, const fmr_analyser_config &m) {
     default: an_shape<13>(*this); break;
   }
   if (int rc = set_dyn_lds(kseg, (size_t)lds)) return rc;
-  spr = (int)(m.interval_samples / (unsigned)H);
-  // a full call in about 64 runs per stream: sub-blocks of 1 .. 16 segments (a run is a workgroup's serial work, and the
-  // partition only moves the fp64 rounding of the sums)
-  const size_t max_seg = max_au / H + 2;
-  sub = (int)std::min<size_t>(16, std::max<size_t>(1, (max_seg + 63) / 64));
-  sb = (spr + sub - 1) / sub;
-  rmax = (int)std::min<size_t>(kAnMaxRuns, max_seg / sub + 2 * (max_seg / spr + 2) + 2);
-  // periodic 4-term Blackman-Harris and the twiddles, in double, rounded once
-  std::vector<float> w(N);
-  std::vector<float2> tw(N);
-  sumw2 = 0.0;
-  for (int i = 0; i < N; i++) {
-    const double t = 2.0 * M_PI * i / N;
-    w[i] = (float)(0.35875 - 0.48829 * std::cos(t) + 0.14128 * std::cos(2.0 * t) - 0.01168 * std::cos(3.0 * t));
-    sumw2 += (double)w[i] * (double)w[i];
-    tw[i] = make_float2((float)std::cos(t), (float)-std::sin(t));
-  }
-  const size_t L = (size_t)m.max_records, rows = (size_t)S * rmax, nb3 = (size_t)kAnRows * nb;
+  ws = welch_size((unsigned)H, m.interval_samples, max_au, 1, 16, 64, kAnMaxRuns);
+  const WelchTables t = welch_tables(N, kWelchBlackmanHarris);
+  sumw2 = t.sumw2;
+  const size_t L = (size_t)m.max_records, rows = (size_t)S * ws.rmax, nb3 = (size_t)kAnRows * nb;
   int rc;
-  if ((rc = upload(d_win, w.data(), w.size()))) return rc;
-  if ((rc = upload(d_tw, tw.data(), tw.size()))) return rc;
-  if ((rc = d_carry.alloc((size_t)S * N * 2))) return rc;
-  if ((rc = d_ppsd.alloc(rows * nb3))) return rc;
-  if ((rc = d_ppart.alloc(rows))) return rc;
-  if ((rc = d_open_psd.alloc(2 * (size_t)S * nb3))) return rc;
-  if ((rc = d_open_rec.alloc(2 * (size_t)S))) return rc;
-  if ((rc = d_ring_psd.alloc((size_t)S * L * nb3))) return rc;
-  if ((rc = d_ring_rec.alloc((size_t)S * L))) return rc;
+  if ((rc = upload_welch(t, d_win, d_tw))) return rc;
+  if ((rc = alloc_all(d_carry, (size_t)S * N * 2, d_ppsd, rows * nb3, d_ppart, rows, d_open_psd, 2 * (size_t)S * nb3,
+                      d_open_rec, 2 * (size_t)S, d_ring_psd, (size_t)S * L * nb3, d_ring_rec, (size_t)S * L)))
+    return rc;
   cur.reset(S, m.max_records);
-  n = next_seg = 0;
-  par = 0;
   on = true;
   return FMR_OK;
 }
 
-// One call's audio (N_au frames per stream, where the mux wrote them) through the analyser, on stream st: the segments
-// whose last frame the call delivers, in launches of at most an.rmax runs per stream, then the carry.
+// one call's audio (N_au frames per stream, where the mux wrote them) through the analyser, on stream st
 int fmr_chain::an_stage(const double *d_aud, long long astride, long long N_au, hipStream_t st) {
   if (N_au <= 0) return FMR_OK;
-  const long long n0 = an.n, n1 = n0 + N_au;
-  const long long j_hi = n1 >= an.N ? (n1 - an.N) / an.H + 1 : 0;
   AnArgs a{};
-  a.n0 = n0; a.spr = an.spr; a.sub = an.sub; a.sb = an.sb; a.ch = stereo ? 2 : 1;
-  const int L = (int)an.cur.L;
+  a.ch = stereo ? 2 : 1;
+  const int L = (int)an.cur.L, rmax = an.ws.rmax;
   const long long M = (long long)an.cfg.interval_samples;
-  long long j = an.next_seg;
-  do {
-    // the segments [j, a.a1) of the call's [j, j_hi) that fit into rmax runs per stream, the runs and records they touch
-    int runs = 0, nrec = 1;
-    a.a0 = a.a1 = j; a.g0 = 0;
-    if (j < j_hi) {
-      const long long l = j / a.spr;
-      a.g0 = l * a.sb + (j - l * a.spr) / a.sub;
-      long long lo, hi;
-      an_sub(a.spr, a.sub, a.sb, a.g0 + an.rmax - 1, lo, hi);
-      a.a1 = std::min(j_hi, hi);
-      const long long l_end = (a.a1 - 1) / a.spr;
-      runs = (int)(l_end * a.sb + (a.a1 - 1 - l_end * a.spr) / a.sub - a.g0 + 1);
-      nrec = (int)(l_end - l + 1);
-    }
-    if (runs > 0)
+  welch_call(an.ws, a, an.N, an.H, N_au,
+    [&](int runs) {
       timed_on(st, "an_seg", [&] {
         hipLaunchKernelGGL(an.kseg, dim3(runs, S), dim3(an.threads), an.lds, st, d_aud, astride, an.d_carry.p, a, an.d_win.p,
-                           an.d_tw.p, an.rmax, an.d_ppsd.p, an.d_ppart.p);
+                           an.d_tw.p, rmax, an.d_ppsd.p, an.d_ppart.p);
       });
-    j = a.a1;
-    timed_on(st, "an_reduce", [&] {
-      hipLaunchKernelGGL(k_an_reduce, dim3(nrec, S), dim3(kAnRT), 0, st, an.d_ppsd.p, an.d_ppart.p, runs, an.rmax, a, an.N, L, M,
-                         an.par, an.d_open_psd.p, an.d_open_rec.p, an.d_ring_psd.p, an.d_ring_rec.p, d_aud, astride,
-                         an.d_carry.p, n1, (int)(j >= j_hi));
+    },
+    [&](int runs, int nrec, long long n1, int last) {
+      timed_on(st, "an_reduce", [&] {
+        hipLaunchKernelGGL(k_an_reduce, dim3(nrec, S), dim3(kAnRT), 0, st, an.d_ppsd.p, an.d_ppart.p, runs, rmax, a, an.N, L, M,
+                           an.ws.par, an.d_open_psd.p, an.d_open_rec.p, an.d_ring_psd.p, an.d_ring_rec.p, d_aud, astride,
+                           an.d_carry.p, n1, last);
+      });
     });
-    if (runs > 0) an.par ^= 1;
-  } while (j < j_hi);
-  an.next_seg = std::max(an.next_seg, j_hi);
-  an.n = n1;
   HIPCHK(hipGetLastError());
   return FMR_OK;
 }
@@ -3255,14 +3220,6 @@ const SpecAttrFn kSpecAttr[7][4] = {FMR_SPEC_ATTR(8), FMR_SPEC_ATTR(9), FMR_SPEC
 const decltype(&k_spec_reduce<0>) kSpecReduce[4] = {&k_spec_reduce<0>, &k_spec_reduce<1>, &k_spec_reduce<2>, &k_spec_reduce<3>};
 
 
-// the periodic window of kind `window` at N points, in double
-double spec_window(int window, int n, int N) {
-  const double x = 2.0 * M_PI * n / N;
-  if (window == FMR_WINDOW_HANN) return 0.5 - 0.5 * std::cos(x);
-  if (window == FMR_WINDOW_BLACKMAN_HARRIS) return 0.35875 - 0.48829 * std::cos(x) + 0.14128 * std::cos(2 * x) - 0.01168 * std::cos(3 * x);
-  return 1.0;
-}
-
 // the rules of fmr_spectrum_create, before the device is opened
 int spec_check(const fmr_spectrum_config &c) {
   if (c.fft_size < 256 || c.fft_size > 16384 || (c.fft_size & (c.fft_size - 1)) != 0) {
@@ -3327,21 +3284,10 @@ int fmr_spectrum::init() {
   if (int rc = stream.create()) return rc;
   const bool wfon = wf.segments_per_line > 0;
   if (int rc = kSpecAttr[logn - 8][fmt](wfon)) return rc;
-  // window and twiddles: double, rounded once to fp32
-  std::vector<float> w(N);
-  std::vector<float2> tw(N);
-  double sw = 0.0, sw2 = 0.0;
-  for (int n = 0; n < N; n++) {
-    w[n] = (float)spec_window(cfg.window, n, N);
-    sw += w[n];
-    sw2 += (double)w[n] * w[n];
-    const double a = -2.0 * M_PI * n / N;
-    tw[n] = make_float2((float)std::cos(a), (float)std::sin(a));
-  }
-  sumw = sw;
-  sumw2 = sw2;
-  if (int rc = upload(d_win, w.data(), w.size())) return rc;
-  if (int rc = upload(d_tw, tw.data(), tw.size())) return rc;
+  const WelchTables t = welch_tables(N, cfg.window);
+  sumw = t.sumw;
+  sumw2 = t.sumw2;
+  if (int rc = upload_welch(t, d_win, d_tw)) return rc;
   // runs: about one workgroup per slot the chip holds at this N, shared by the rows; no more than a call's segments
   const int occ = std::max(1, std::min(163840 / spec_lds_bytes(logn), 2048 / spec_threads(logn)));
   const long long smax = (long long)((cfg.max_call_len + H - 1) / H) + 1;
@@ -3406,16 +3352,10 @@ int fmr_spectrum::run_waterfall(const void *d_in, size_t stride, long long tb, l
   const int R = wf.segments_per_line;
   long long a = (long long)next_seg;
   while (a < j_hi) {
-    const long long l = a / R;
+    const WelchLaunch p = welch_plan(R, SPEC_WF_SUB, wf_sb, rmax, a, j_hi);
+    const int runs = p.runs;
     SpecWf w{};
-    w.which = wf.which; w.R = R; w.SB = wf_sb;
-    w.g0 = l * wf_sb + (a - l * R) / SPEC_WF_SUB;
-    long long lo, hi;
-    spec_wf_sub(R, wf_sb, w.g0 + rmax - 1, lo, hi);
-    w.a1 = std::min(j_hi, hi);
-    const long long l_end = (w.a1 - 1) / R;
-    const long long g_last = l_end * wf_sb + (w.a1 - 1 - l_end * R) / SPEC_WF_SUB;
-    const int runs = (int)(g_last - w.g0 + 1);
+    w.which = wf.which; w.R = R; w.SB = wf_sb; w.g0 = p.g0; w.a1 = p.a1;
     w.plsub = d_plsub.p; w.plcnt = d_plcnt.p; w.open_sub = d_wopen.p; w.open_cnt = d_wopen_cnt.p;
     if (int rc = kSpecSeg[logn - 8][fmt](this, dim3(runs, rows), d_in, (long long)stride, tb, a, (int)(w.a1 - a), 0, &w))
       return rc;
@@ -3423,7 +3363,7 @@ int fmr_spectrum::run_waterfall(const void *d_in, size_t stride, long long tb, l
                        (const float *)d_pmax.p, (const int2 *)d_pcnt.p, runs, rmax, N, d_sum.p, d_max.p, d_cnt.p, d_in,
                        (long long)stride, tb, w.a1 == j_hi ? ta : tb, d_ring.p);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_spec_lines, dim3((unsigned)(l_end - l + 1), rows, (N + 255) / 256), dim3(256), 0, stream, w, a, runs,
+    hipLaunchKernelGGL(k_spec_lines, dim3((unsigned)p.nrec, rows, (N + 255) / 256), dim3(256), 0, stream, w, a, runs,
                        rmax, N, wf.max_lines, wf_par, d_wline.p, d_wline_cnt.p, d_wring.p, d_wring_cnt.p);
     HIPCHK(hipGetLastError());
     wf_par ^= 1;
@@ -4195,15 +4135,8 @@ int fmr_enable_monitor(fmr_chain *c, const fmr_monitor_config *cfg, size_t cfg_s
             c->mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no MPX" : "has no MPX");
     return FMR_ERR_UNSUPPORTED;
   }
-  if (c->mon.on) { set_err("fmr_enable_monitor: the monitor of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
-  if (c->call_seq != 0) {
-    set_err("fmr_enable_monitor: the chain has already taken samples (the monitor counts from the chain's first MPX sample)");
-    return FMR_ERR_BAD_ARG;
-  }
-  try {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    return build_stage(c->mon, c->S, c->max_if, m.interval_samples, m.hist_bins, m.hist_range, m.max_records);
-  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+  return enable_stage("fmr_enable_monitor", c, c->mon, "monitor", "MPX sample", c->S, c->max_if, m.interval_samples, m.hist_bins,
+                      m.hist_range, m.max_records);
 }
 
 int fmr_monitor_read(fmr_chain *c, int stream, fmr_monitor_record *recs, uint32_t *hist, double *psd, int cap,
@@ -4218,10 +4151,7 @@ int fmr_monitor_read(fmr_chain *c, int stream, fmr_monitor_record *recs, uint32_
       full.struct_size = (unsigned)sizeof full;
       full.hist_bins = c->mon.bins;
       full.psd_bins = kMonPsd;
-      full.records_complete = c->mon.done();
-      full.records_dropped = c->mon.cur.dropped[stream];
-      full.first_unread = c->mon.cur.read[stream];
-      full.records_ready = c->mon.done() - c->mon.cur.read[stream];
+      ring_info(full, c->mon.cur, stream, c->mon.done());
       full.interval_samples = c->mon.interval;
       full.max_records = (int)c->mon.cur.L;
       full.hist_range = c->mon.hist_range;
@@ -4294,15 +4224,8 @@ int fmr_enable_output(fmr_chain *c, const fmr_output_config *cfg, size_t cfg_siz
     set_err("fmr_enable_output: a front-end-only chain (mode -1: channelizer / IfResampler) has no audio");
     return FMR_ERR_UNSUPPORTED;
   }
-  if (c->out.on) { set_err("fmr_enable_output: the output stage of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
-  if (c->call_seq != 0) {
-    set_err("fmr_enable_output: the chain has already taken samples (the output stage counts from the chain's first block)");
-    return FMR_ERR_BAD_ARG;
-  }
-  try {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    return build_stage(c->out, c->S, c->stereo, c->max_blocks, c->pipelined ? fmr_chain::kPipe : 1, m);
-  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+  return enable_stage("fmr_enable_output", c, c->out, "output stage", "block", c->S, c->stereo, c->max_blocks,
+                      c->pipelined ? fmr_chain::kPipe : 1, m);
 }
 
 int fmr_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, fmr_output_block *blocks, int cap_blocks,
@@ -4458,15 +4381,7 @@ int fmr_enable_loudness(fmr_chain *c, const fmr_loudness_config *cfg, size_t cfg
             c->mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no audio" : "is not covered");
     return FMR_ERR_UNSUPPORTED;
   }
-  if (c->ld.on) { set_err("fmr_enable_loudness: the audio monitor of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
-  if (c->call_seq != 0) {
-    set_err("fmr_enable_loudness: the chain has already taken samples (the audio monitor counts from the chain's first audio sample)");
-    return FMR_ERR_BAD_ARG;
-  }
-  try {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    return build_stage(c->ld, c->S, c->max_au, m);
-  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+  return enable_stage("fmr_enable_loudness", c, c->ld, "audio monitor", "audio sample", c->S, c->max_au, m);
 }
 
 int fmr_loudness_read(fmr_chain *c, int stream, fmr_loudness_record *recs, int cap, fmr_loudness_info *info, size_t info_size) {
@@ -4487,10 +4402,7 @@ int fmr_loudness_read(fmr_chain *c, int stream, fmr_loudness_record *recs, int c
       fmr_loudness_info full{};
       full.struct_size = (unsigned)sizeof full;
       full.channels = c->stereo ? 2 : 1;
-      full.records_complete = done;
-      full.records_dropped = c->ld.cur.dropped[stream];
-      full.first_unread = c->ld.cur.read[stream];
-      full.records_ready = done - c->ld.cur.read[stream];
+      ring_info(full, c->ld.cur, stream, done);
       full.step_samples = c->ld.cfg.step_samples;
       full.max_records = c->ld.cfg.max_records;
       give_sized(info, info_size, full);
@@ -4598,15 +4510,7 @@ int fmr_enable_analyser(fmr_chain *c, const fmr_analyser_config *cfg, size_t cfg
     set_err("fmr_enable_analyser: a front-end-only chain (mode -1: channelizer / IfResampler) has no audio");
     return FMR_ERR_UNSUPPORTED;
   }
-  if (c->an.on) { set_err("fmr_enable_analyser: the analyser of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
-  if (c->call_seq != 0) {
-    set_err("fmr_enable_analyser: the chain has already taken samples (the analyser counts from the chain's first audio sample)");
-    return FMR_ERR_BAD_ARG;
-  }
-  try {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    return build_stage(c->an, c->S, c->max_au, m);
-  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+  return enable_stage("fmr_enable_analyser", c, c->an, "analyser", "audio sample", c->S, c->max_au, m);
 }
 
 int fmr_analyser_read(fmr_chain *c, int stream, fmr_analyser_record *recs, double *spectra, int cap, fmr_analyser_info *info,
@@ -4640,10 +4544,7 @@ int fmr_analyser_read(fmr_chain *c, int stream, fmr_analyser_record *recs, doubl
       fmr_analyser_info full{};
       full.struct_size = (unsigned)sizeof full;
       full.channels = c->stereo ? 2 : 1;
-      full.records_complete = done;
-      full.records_dropped = an.cur.dropped[stream];
-      full.first_unread = an.cur.read[stream];
-      full.records_ready = done - an.cur.read[stream];
+      ring_info(full, an.cur, stream, done);
       full.interval_samples = an.cfg.interval_samples;
       full.max_records = an.cfg.max_records;
       full.fft_size = an.N;
@@ -4811,15 +4712,8 @@ int fmr_enable_rf_monitor(fmr_chain *c, const fmr_rf_monitor_config *cfg, size_t
             c->mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no decoder" : "is not measured");
     return FMR_ERR_UNSUPPORTED;
   }
-  if (c->rfm.on) { set_err("fmr_enable_rf_monitor: the RF monitor of this chain is already enabled"); return FMR_ERR_BAD_ARG; }
-  if (c->call_seq != 0) {
-    set_err("fmr_enable_rf_monitor: the chain has already taken samples (the RF monitor counts from the chain's first IF sample)");
-    return FMR_ERR_BAD_ARG;
-  }
-  try {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    return build_stage(c->rfm, c->S, c->max_if, m.interval_samples, kRfmBins, 0.0, m.max_records);
-  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+  return enable_stage("fmr_enable_rf_monitor", c, c->rfm, "RF monitor", "IF sample", c->S, c->max_if, m.interval_samples, kRfmBins,
+                      0.0, m.max_records);
 }
 
 int fmr_rf_monitor_read(fmr_chain *c, int stream, fmr_rf_monitor_record *recs, uint32_t *hist, double *psd, int cap,
@@ -4834,10 +4728,7 @@ int fmr_rf_monitor_read(fmr_chain *c, int stream, fmr_rf_monitor_record *recs, u
       full.struct_size = (unsigned)sizeof full;
       full.hist_bins = kRfmBins;
       full.psd_bins = kMonPsd;
-      full.records_complete = c->rfm.done();
-      full.records_dropped = c->rfm.cur.dropped[stream];
-      full.first_unread = c->rfm.cur.read[stream];
-      full.records_ready = c->rfm.done() - c->rfm.cur.read[stream];
+      ring_info(full, c->rfm.cur, stream, c->rfm.done());
       full.interval_samples = c->rfm.interval;
       full.max_records = (int)c->rfm.cur.L;
       full.bin_hz = kFmRate / kMonN;

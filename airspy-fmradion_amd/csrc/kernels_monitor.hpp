@@ -1,36 +1,28 @@
 // kernels_monitor.hpp -- modulation monitor of the 384 kHz MPX (fmr_enable_monitor).
 //
-// Indices are absolute, counted from the chain's first MPX sample.  N = 1024, H = 512, M = interval_samples (a multiple
-// of H).  Record i covers the samples [i M, (i + 1) M); segment j covers [j H, j H + N) and belongs to record
-// floor(j H / M): a record holds M / H segments, and its last one reaches H samples into the next record.  A segment is
-// processed in the call that delivers its last sample; the time-domain part of a record (counts, min, max, sum, sum of
-// squares, histogram) is taken over the FIRST H samples of each of its segments, so every sample enters it exactly
-// once, in the segment it starts, wherever a call ends.
+// An instance of the Welch segment engine (kernels_welch.hpp: indices, the partition into sub-blocks and runs, the carry,
+// the open records and the ring) with N = 1024, H = 512, M = interval_samples and sub-blocks of 4 .. 32 segments.  What
+// is this stage's own:
 //
-// k_mon_seg: one workgroup (256 threads) = one run of segments of one stream.  A record is cut into aligned sub-blocks
-// of `sub` segments (4 .. 32, fixed per chain; the last one shorter); run r of a launch is sub-block g0 + r clipped to the launch's segments, so
-// a run never straddles a record boundary.  Per segment: 1024 floats from the call's MPX (or, in front of the call's
-// first sample, from the stream's carry), the time-domain part of the first 512 (histogram through LDS integer
-// atomics), then window, bit-reversed store, five radix-4 passes in LDS (the band spectrum's butterfly and padding)
-// and |X[k]|^2 of the bins 0 .. 512 into fp64 registers.  A segment with a non-finite sample is skipped for the spectral
-// part and counted; its finite samples still enter the time-domain part.  The run's values go to a partial once.
+// k_mon_seg: one workgroup (256 threads) = one run.  Per segment: 1024 floats from the call's MPX or the carry, the
+// time-domain part of a record (counts, min, max, sum, sum of squares, histogram through LDS integer atomics) over the
+// segment's FIRST 512 samples -- so every sample enters it exactly once, in the segment it starts, wherever a call ends --,
+// then window, bit-reversed store, welch_fft and |X[k]|^2 of the bins 0 .. 512 into fp64 registers.  A segment with a
+// non-finite sample is skipped for the spectral part and counted; its finite samples still enter the time-domain part.
+// The run's values go to a partial once.
 //
-// k_mon_reduce: one workgroup per stream and record the launch touches adds the record's partials in run order (fp64,
-// fixed order, no float atomics), starting from the stream's open record when the record began in an earlier launch;
-// a record whose last segment is in goes to the ring [S][L], an open one back to the open record (two copies by launch
-// parity).  In the call's last launch it also copies the call's last samples into the carry (sample p at
-// carry[p mod 1024]: the up to 1023 samples no complete segment has consumed never collide there).
+// k_mon_reduce: the engine's reduce over PSD sums, histogram counters and MonRec; in the call's last launch it also
+// copies the call's last 1023 samples into the carry.
 //
-// The bodies of both kernels (mon_seg_run, mon_reduce_run, mon_fft) are shared with the RF monitor (kernels_rfmon.hpp),
-// which differs in where a sample comes from and in the histogram's bin rule.
+// The bodies of both kernels (mon_seg_run, mon_reduce_run) are shared with the RF monitor (kernels_rfmon.hpp), which
+// differs in where a sample comes from and in the histogram's bin rule.
 //
-// Nothing here waits on another workgroup or on the host.  The density scaling c_k / (F sum w^2) and the division by the
-// segment count happen on the host when a record is read.
+// The density scaling c_k / (F sum w^2) and the division by the segment count happen on the host when a record is read.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernels_spectrum.hpp"
+#include "kernels_welch.hpp"
 
 namespace fmr {
 
@@ -47,21 +39,10 @@ struct MonRec {
   double sum, sumsq;
 };
 
-struct MonArgs {
-  long long n0;        // absolute index of the call's first sample
-  long long a0, a1;    // the launch takes the segments [a0, a1)
-  long long g0;        // sub-block of segment a0
-  int spr, sub, sb;    // segments per record, per sub-block, sub-blocks per record = ceil(spr / sub)
+struct MonArgs : WelchArgs {
   int bins;            // histogram: B, Rf = (float)R, scale = (float)(B / (2 R))
   float rf, scale;
 };
-
-// segments [lo, hi) of sub-block g (whole, before a launch clips it)
-__host__ __device__ inline void mon_sub(int spr, int sub, int sb, long long g, long long &lo, long long &hi) {
-  const long long l = g / sb, b = g - l * sb;
-  lo = l * spr + b * sub;
-  hi = lo + sub < (l + 1) * spr ? lo + sub : (l + 1) * spr;
-}
 
 // the histogram's bin rule, unfused fp32 (the clamp runs on the float: a huge sample never reaches the conversion)
 __device__ __forceinline__ int mon_bin(float x, float rf, float scale, int bins) {
@@ -90,29 +71,6 @@ struct MonMpxSrc {
   __device__ __forceinline__ int bin(float v) const { return mon_bin(v, rf, scale, bins); }
 };
 
-// The 1024-point FFT of both monitors: five radix-4 decimation-in-time passes in place over the bit-reversed points in
-// lds (the band spectrum's butterfly and padding), one butterfly per thread and pass; ends behind a barrier.
-__device__ __forceinline__ void mon_fft(float2 *lds, const float2 *__restrict__ tw, int tid) {
-  constexpr int N = kMonN;
-  for (int span = 1; span < N; span *= 4) {
-    const int tstep = N / (4 * span);
-    const int jj = tid & (span - 1);
-    const int b0 = (tid - jj) * 4 + jj;
-    const int e0 = spec_pad(b0), e1 = spec_pad(b0 + 2 * span), e2 = spec_pad(b0 + span), e3 = spec_pad(b0 + 3 * span);
-    const float2 a0 = lds[e0];
-    const float2 a1 = cmul(lds[e1], tw[jj * tstep]);
-    const float2 a2 = cmul(lds[e2], tw[2 * jj * tstep]);
-    const float2 a3 = cmul(lds[e3], tw[3 * jj * tstep]);
-    const float2 s02 = make_float2(a0.x + a2.x, a0.y + a2.y), d02 = make_float2(a0.x - a2.x, a0.y - a2.y);
-    const float2 s13 = make_float2(a1.x + a3.x, a1.y + a3.y), d13 = make_float2(a1.x - a3.x, a1.y - a3.y);
-    lds[e0] = make_float2(s02.x + s13.x, s02.y + s13.y);
-    lds[e2] = make_float2(d02.x + d13.y, d02.y - d13.x);
-    lds[e1] = make_float2(s02.x - s13.x, s02.y - s13.y);
-    lds[e3] = make_float2(d02.x - d13.y, d02.y + d13.x);
-    __syncthreads();
-  }
-}
-
 // One run of segments of stream s (the body of both monitors' segment kernels): run `run` of the launch, samples from
 // src.  Partials of the run at row s rmax + run: ppsd [kMonPsd], phist [a.bins], prec.
 template <class Src>
@@ -124,7 +82,7 @@ __device__ __forceinline__ void mon_seg_run(const Src &src, int run, int s, cons
   __shared__ unsigned s_hist[Src::kHist];
   const int tid = threadIdx.x;
   long long lo, hi;
-  mon_sub(a.spr, a.sub, a.sb, a.g0 + run, lo, hi);
+  welch_sub(a.spr, a.sub, a.sb, a.g0 + run, lo, hi);
   const long long j_lo = lo > a.a0 ? lo : a.a0, j_hi = hi < a.a1 ? hi : a.a1;
   for (int b = tid; b < a.bins; b += T) s_hist[b] = 0u;
   __syncthreads();
@@ -160,7 +118,7 @@ __device__ __forceinline__ void mon_seg_run(const Src &src, int run, int s, cons
     }
     bad = __syncthreads_or(bad);
     if (bad) { skipped++; continue; }      // (uniform: nobody has read the LDS, the next segment's stores may follow)
-    mon_fft(lds, tw, tid);
+    welch_fft<kMonLog, kMonT>(lds, tw, tid);
     {
       const float2 x0 = lds[spec_pad(tid)], x1 = lds[spec_pad(tid + T)];
       acc0 += (double)(x0.x * x0.x + x0.y * x0.y);
@@ -230,19 +188,16 @@ __device__ __forceinline__ void mon_reduce_run(const double *__restrict__ ppsd, 
                                                double *__restrict__ ring_psd, unsigned *__restrict__ ring_hist,
                                                MonRec *__restrict__ ring_rec) {
   constexpr int T = kMonT;
-  const int tid = threadIdx.x, s = blockIdx.y, S = gridDim.y;
-  const long long l = a.g0 / a.sb + blockIdx.x;
-  const long long g_last = a.g0 + runs - 1;
-  const int b_lo = blockIdx.x == 0 ? (int)(a.g0 - l * a.sb) : 0;
-  const int b_hi = (int)(a.sb < g_last - l * a.sb + 1 ? a.sb : g_last - l * a.sb + 1);
+  const int tid = threadIdx.x;
+  const WelchRec w = welch_rec(a, runs, rmax, L, par, gridDim.y, blockIdx.y, blockIdx.x);
   double p0 = 0.0, p1 = 0.0, p2 = 0.0;
   unsigned h[HB];
 #pragma unroll
   for (int k = 0; k < HB; k++) h[k] = 0u;
   MonRec o{};
   o.mn = INFINITY; o.mx = -INFINITY;
-  if (a.a0 > l * a.spr) {                 // the record began in an earlier launch (the launch's first record only)
-    const size_t os = (size_t)par * S + s;
+  if (w.carried) {
+    const size_t os = w.os_in;
     p0 = open_psd[os * kMonPsd + tid];
     p1 = open_psd[os * kMonPsd + tid + T];
 #pragma unroll
@@ -250,8 +205,8 @@ __device__ __forceinline__ void mon_reduce_run(const double *__restrict__ ppsd, 
       if (tid + k * T < a.bins) h[k] = open_hist[os * a.bins + tid + k * T];
     if (tid == 0) { p2 = open_psd[os * kMonPsd + kMonN / 2]; o = open_rec[os]; }
   }
-  for (int b = b_lo; b < b_hi; b++) {
-    const size_t prow = (size_t)s * rmax + (size_t)(l * a.sb + b - a.g0);
+  for (int b = 0; b < w.nsub; b++) {
+    const size_t prow = w.p_first + b;
     p0 += ppsd[prow * kMonPsd + tid];
     p1 += ppsd[prow * kMonPsd + tid + T];
 #pragma unroll
@@ -265,10 +220,9 @@ __device__ __forceinline__ void mon_reduce_run(const double *__restrict__ ppsd, 
       o.sum += q.sum; o.sumsq += q.sumsq;
     }
   }
-  const long long last_done = a.a1 / a.spr - 1;      // last record complete after this launch
-  if (l <= last_done) {
-    if (l + L > last_done) {
-      const size_t slot = (size_t)s * L + (size_t)(l % L);
+  if (w.done) {
+    if (w.keep) {
+      const size_t slot = w.slot;
       ring_psd[slot * kMonPsd + tid] = p0;
       ring_psd[slot * kMonPsd + tid + T] = p1;
 #pragma unroll
@@ -276,14 +230,14 @@ __device__ __forceinline__ void mon_reduce_run(const double *__restrict__ ppsd, 
         if (tid + k * T < a.bins) ring_hist[slot * a.bins + tid + k * T] = h[k];
       if (tid == 0) {
         ring_psd[slot * kMonPsd + kMonN / 2] = p2;
-        o.index = (uint64_t)l;
-        o.first_sample = (uint64_t)(l * M);
+        o.index = (uint64_t)w.l;
+        o.first_sample = (uint64_t)(w.l * M);
         if (o.n_finite == 0) { o.mn = 0.f; o.mx = 0.f; }
         ring_rec[slot] = o;
       }
     }
   } else {
-    const size_t os = (size_t)(par ^ 1) * S + s;
+    const size_t os = w.os_out;
     open_psd[os * kMonPsd + tid] = p0;
     open_psd[os * kMonPsd + tid + T] = p1;
 #pragma unroll
@@ -293,13 +247,10 @@ __device__ __forceinline__ void mon_reduce_run(const double *__restrict__ ppsd, 
   }
 }
 
-// Block (x = record l0 + blockIdx.x of the launch, y = stream); l0 = the record of segment a0.  The block adds the
-// partials of its record's sub-blocks inside the launch in run order (fp64, no float atomics), starting from the open
-// record of the launch before (open_*[par]: [2][S] records, [2][S][bins] counters, [2][S][kMonPsd] sums) when the record
-// began there.  A record whose last segment is in goes to slot (index mod L) of the rings -- unless a later record of
-// the same launch takes that slot --, an open one to open_*[par ^ 1]: the block that reads the old copy is not the one
-// that writes the new one.  last != 0 (the call's last launch; runs may be 0): block 0 copies the samples
-// [max(n0, n_end - 1023), n_end) of the call, as Src::fresh gives them, to the carry.  Src = MonMpxSrc | RfmSrc<NRM>.
+// The engine's reduce (kernels_welch.hpp): block (x = record of the launch, y = stream); the open records are open_*[par]:
+// [2][S] records, [2][S][bins] counters, [2][S][kMonPsd] sums.  last != 0 (the call's last launch; runs may be 0): block 0
+// copies the samples [max(n0, n_end - 1023), n_end) of the call, as Src::fresh gives them, to the carry.
+// Src = MonMpxSrc | RfmSrc<NRM>.
 template <class Src>
 __global__ __launch_bounds__(kMonT) void k_mon_reduce(const double *__restrict__ ppsd, const unsigned *__restrict__ phist,
                                                       const MonRec *__restrict__ prec, int runs, int rmax, MonArgs a,

@@ -15,9 +15,9 @@
 // cut).  Only the run's partial sums go to HBM; k_spec_reduce adds them in run order into the row's accumulators (no
 // float atomics) and refreshes the ring.
 //
-// LDS: element e lives at e + (e >> 5) (one float2 of padding per 32): the radix-4 pass of span 1, whose lanes read at a
-// stride of 4 elements, spreads a 32-lane ds_read_b64 group over all 64 banks instead of 16 of them.  N = 16384 needs
-// 132 KiB: one workgroup per CU; N <= 8192 fits two.
+// The LDS padding and the sub-block partition are the Welch segment engine's (kernels_welch.hpp); the passes are
+// welch_fft's arithmetic, written out in this kernel.
+// N = 16384 needs 132 KiB of LDS: one workgroup per CU; N <= 8192 fits two.
 // Twiddles tw[i] = exp(-2 pi i i / N) and the window are built on the host in double and rounded once to fp32.
 //
 // Waterfall (fmr_spectrum_create_waterfall; k_spec_seg<.., WF = true> and k_spec_lines).  Line l of a row is made of the
@@ -39,6 +39,8 @@
 // the LDS of the segment pass is unchanged.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "kernels_welch.hpp"
 
 // threads and LDS bytes of k_spec_seg at 2^logn points (host and device: the engine sizes its runs with them)
 __host__ __device__ constexpr int spec_threads(int logn) { return (1 << logn) / 4 < 1024 ? (1 << logn) / 4 : 1024; }
@@ -63,17 +65,6 @@ struct SpecWf {
   float *open_sub;           // [row][N], open_cnt [row]: the sub-block a call's end cut
   int *open_cnt;
 };
-// segments [lo, hi) of sub-block g (whole, before a launch clips it)
-__host__ __device__ inline void spec_wf_sub(int R, int SB, long long g, long long &lo, long long &hi) {
-  const long long l = g / SB, b = g - l * SB;
-  lo = l * R + b * SPEC_WF_SUB;
-  hi = lo + SPEC_WF_SUB < (l + 1) * R ? lo + SPEC_WF_SUB : (l + 1) * R;
-}
-
-__device__ __forceinline__ int spec_pad(int e) { return e + (e >> 5); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-  return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
 
 // Row `row` of the call: input at in + row * in_stride (IQ samples of format FMT, in_n of them), ring row at
 // ring + row * N (sample p of the stream at ring[p mod N] for p < tb).  Segments seg0 .. seg0 + n_seg - 1 of this call,
@@ -97,7 +88,7 @@ __global__ __launch_bounds__(SpecShape<LOGN>::T) void k_spec_seg(
   [[maybe_unused]] int lcnt = 0;
   if constexpr (WF) {
     long long lo, hi;
-    spec_wf_sub(wf.R, wf.SB, wf.g0 + run, lo, hi);
+    fmr::welch_sub(wf.R, SPEC_WF_SUB, wf.SB, wf.g0 + run, lo, hi);
     const bool carried = lo < seg0;        // the call before ended inside this sub-block (the launch's first run only)
     j_lo = (int)(max(lo, seg0) - seg0);
     j_hi = (int)(min(hi, wf.a1) - seg0);
@@ -123,14 +114,15 @@ __global__ __launch_bounds__(SpecShape<LOGN>::T) void k_spec_seg(
       bad |= !(isfinite(v.x) && isfinite(v.y));
       const float w = win[i];
       const int r = (int)(__brev((unsigned)i) >> (32 - LOGN));
-      lds_sp[spec_pad(r)] = make_float2(v.x * w, v.y * w);
+      lds_sp[fmr::spec_pad(r)] = make_float2(v.x * w, v.y * w);
     }
     bad = __syncthreads_or(bad);
     if (bad) { skipped++; continue; }      // (uniform: the whole workgroup skips; the next store waits on the barrier above)
+    // welch_fft's passes, written out: called as a function they cost this kernel registers (kernels_welch.hpp)
     int span = 1;
     if (LOGN & 1) {                        // one radix-2 pass first when log2 N is odd
       for (int b = tid; b < N / 2; b += T) {
-        const int e0 = spec_pad(2 * b), e1 = spec_pad(2 * b + 1);
+        const int e0 = fmr::spec_pad(2 * b), e1 = fmr::spec_pad(2 * b + 1);
         const float2 a0 = lds_sp[e0], a1 = lds_sp[e1];
         lds_sp[e0] = make_float2(a0.x + a1.x, a0.y + a1.y);
         lds_sp[e1] = make_float2(a0.x - a1.x, a0.y - a1.y);
@@ -147,24 +139,25 @@ __global__ __launch_bounds__(SpecShape<LOGN>::T) void k_spec_seg(
         const int b = tid + q * T;
         const int jj = b & (span - 1);
         const int base = (b - jj) * 4 + jj;
-        const int e0 = spec_pad(base), e1 = spec_pad(base + 2 * span), e2 = spec_pad(base + span), e3 = spec_pad(base + 3 * span);
+        const int e0 = fmr::spec_pad(base), e1 = fmr::spec_pad(base + 2 * span), e2 = fmr::spec_pad(base + span),
+                  e3 = fmr::spec_pad(base + 3 * span);
         const float2 a0 = lds_sp[e0];
-        const float2 a1 = cmul(lds_sp[e1], tw[jj * tstep]);
-        const float2 a2 = cmul(lds_sp[e2], tw[2 * jj * tstep]);
-        const float2 a3 = cmul(lds_sp[e3], tw[3 * jj * tstep]);
+        const float2 a1 = fmr::cmul(lds_sp[e1], tw[jj * tstep]);
+        const float2 a2 = fmr::cmul(lds_sp[e2], tw[2 * jj * tstep]);
+        const float2 a3 = fmr::cmul(lds_sp[e3], tw[3 * jj * tstep]);
         const float2 s02 = make_float2(a0.x + a2.x, a0.y + a2.y), d02 = make_float2(a0.x - a2.x, a0.y - a2.y);
         const float2 s13 = make_float2(a1.x + a3.x, a1.y + a3.y), d13 = make_float2(a1.x - a3.x, a1.y - a3.y);
         // X0 = s02 + s13, X2 = s02 - s13, X1 = d02 - i d13, X3 = d02 + i d13
-        lds_sp[spec_pad(base)] = make_float2(s02.x + s13.x, s02.y + s13.y);
-        lds_sp[spec_pad(base + span)] = make_float2(d02.x + d13.y, d02.y - d13.x);
-        lds_sp[spec_pad(base + 2 * span)] = make_float2(s02.x - s13.x, s02.y - s13.y);
-        lds_sp[spec_pad(base + 3 * span)] = make_float2(d02.x - d13.y, d02.y + d13.x);
+        lds_sp[fmr::spec_pad(base)] = make_float2(s02.x + s13.x, s02.y + s13.y);
+        lds_sp[fmr::spec_pad(base + span)] = make_float2(d02.x + d13.y, d02.y - d13.x);
+        lds_sp[fmr::spec_pad(base + 2 * span)] = make_float2(s02.x - s13.x, s02.y - s13.y);
+        lds_sp[fmr::spec_pad(base + 3 * span)] = make_float2(d02.x - d13.y, d02.y + d13.x);
       }
       __syncthreads();
     }
 #pragma unroll
     for (int b = 0; b < S::BINS; b++) {
-      const float2 x = lds_sp[spec_pad(tid + b * T)];
+      const float2 x = lds_sp[fmr::spec_pad(tid + b * T)];
       const float pw = x.x * x.x + x.y * x.y;
       acc[b] += (double)pw;
       pk[b] = fmaxf(pk[b], pw);
@@ -272,7 +265,7 @@ __global__ __launch_bounds__(256) void k_spec_lines(SpecWf wf, long long a0, int
     const long long g = l * wf.SB + b;
     const size_t pr = (size_t)row * rmax + (size_t)(g - wf.g0);
     long long lo, hi;
-    spec_wf_sub(wf.R, wf.SB, g, lo, hi);
+    fmr::welch_sub(wf.R, SPEC_WF_SUB, wf.SB, g, lo, hi);
     const float s = wf.plsub[pr * N + i];
     if (hi <= wf.a1) {
       v = b == 0 ? s : wf.which ? fmaxf(v, s) : v + s;
