@@ -57,6 +57,7 @@ EXPORTS = [
     "fmr_enable_rf_monitor", "fmr_rf_monitor_read", "fmr_rf_monitor_derive",
     "fmr_enable_output", "fmr_output_read", "fmr_squelch_level_from_db",
     "fmr_set_output_rate", "fmr_get_output_rate", "fmr_output_rate_taps",
+    "fmr_enable_weak_signal", "fmr_weak_signal_read", "fmr_weak_signal_derive",
 ]
 # FMR_WINDOW_* (include/fmradion_amd.h): windows of the band spectrum
 WINDOW_HANN, WINDOW_RECT, WINDOW_BLACKMAN_HARRIS = 0, 1, 2
@@ -97,6 +98,15 @@ OUTPUT_BLOCK = np.dtype([("block", np.uint64), ("first_frame", np.uint64), ("n_f
                          ("if_rms", np.float32), ("if_level", np.float32), ("audio_mean", np.float32),
                          ("audio_rms", np.float32), ("audio_level", np.float32), ("gate_open", np.uint32),
                          ("n_clipped", np.uint32), ("n_nonfinite", np.uint32)])
+# FMR_WS_* (include/fmradion_amd.h): mode and actions of the weak-signal stage
+WS_MEASURE, WS_ACT = 0, 1
+WS_BLEND, WS_HIGHCUT, WS_MUTE = 1, 2, 4
+# fmr_weak_signal_record as a numpy structured type (96 bytes)
+WEAK_SIGNAL_RECORD = np.dtype([("index", np.uint64), ("first_interval", np.uint64), ("n_intervals", np.uint32),
+                               ("n_nonfinite", np.uint32), ("usn_sum", np.float64), ("usn_peak", np.float64),
+                               ("smoothed", np.float64), ("t_blend", np.float64), ("t_highcut", np.float64),
+                               ("t_mute", np.float64), ("max_blend", np.float64), ("max_highcut", np.float64),
+                               ("max_mute", np.float64)])
 
 
 class FmrError(RuntimeError):
@@ -219,6 +229,28 @@ class RfMonitorLevels(C.Structure):
                 ("noise_dbfs", C.c_double), ("cn_db", C.c_double), ("am_rms", C.c_double), ("am_audio_db", C.c_double),
                 ("am_pilot_db", C.c_double), ("am_floor_dbc_hz", C.c_double), ("p10_dbfs", C.c_double),
                 ("p50_dbfs", C.c_double), ("p90_dbfs", C.c_double), ("n_finite", C.c_uint64), ("segments", C.c_uint64)]
+
+
+class WeakSignalConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("mode", C.c_int), ("actions", C.c_uint), ("record_intervals", C.c_int),
+                ("max_records", C.c_int), ("reserved", C.c_int), ("attack_ms", C.c_double), ("release_ms", C.c_double),
+                ("blend_lo_db", C.c_double), ("blend_hi_db", C.c_double), ("highcut_lo_db", C.c_double),
+                ("highcut_hi_db", C.c_double), ("mute_lo_db", C.c_double), ("mute_hi_db", C.c_double),
+                ("highcut_hz", C.c_double), ("mute_floor_db", C.c_double)]
+
+
+class WeakSignalInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("channels", C.c_int), ("records_complete", C.c_uint64),
+                ("records_dropped", C.c_uint64), ("first_unread", C.c_uint64), ("records_ready", C.c_uint64),
+                ("intervals_complete", C.c_uint64), ("record_intervals", C.c_int), ("max_records", C.c_int),
+                ("mode", C.c_int), ("actions", C.c_uint)]
+
+
+class WeakSignalLevels(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("reserved", C.c_int), ("usn_mean_db", C.c_double), ("usn_peak_db", C.c_double),
+                ("usn_mean_hz", C.c_double), ("usn_peak_hz", C.c_double), ("blend_share", C.c_double),
+                ("highcut_share", C.c_double), ("mute_share", C.c_double), ("t_blend", C.c_double),
+                ("t_highcut", C.c_double), ("t_mute", C.c_double), ("n_intervals", C.c_uint64), ("n_nonfinite", C.c_uint64)]
 
 
 class LoudnessConfig(C.Structure):
@@ -430,6 +462,12 @@ def lib(ab=False):
                                   C.c_size_t]
     L.fmr_squelch_level_from_db.restype = C.c_double
     L.fmr_squelch_level_from_db.argtypes = [C.c_double]
+    L.fmr_enable_weak_signal.restype = C.c_int
+    L.fmr_enable_weak_signal.argtypes = [vp, C.POINTER(WeakSignalConfig), C.c_size_t]
+    L.fmr_weak_signal_read.restype = C.c_int
+    L.fmr_weak_signal_read.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(WeakSignalInfo), C.c_size_t]
+    L.fmr_weak_signal_derive.restype = C.c_int
+    L.fmr_weak_signal_derive.argtypes = [vp, C.c_int, C.POINTER(WeakSignalLevels), C.c_size_t]
     _libs[ab] = L
     return L
 
@@ -526,6 +564,19 @@ def loudness_levels(records, silence_dbfs=-60.0):
     if rc != OK:
         raise FmrError(f"fmr_loudness_derive failed ({rc}): {L.fmr_last_error().decode()}")
     return {k: getattr(out, k) for k, _ in LoudnessLevels._fields_ if k not in ("struct_size", "reserved")}
+
+
+def weak_signal_levels(records):
+    """fmr_weak_signal_derive (host only): the pooled ultrasonic noise, the share of intervals with each action engaged and
+    the last control values of the records (a WEAK_SIGNAL_RECORD array as Chain.weak_signal_records returns them), as a
+    dict of fmr_weak_signal_levels."""
+    L = lib()
+    records = np.ascontiguousarray(records, dtype=WEAK_SIGNAL_RECORD)
+    out = WeakSignalLevels()
+    rc = L.fmr_weak_signal_derive(records.ctypes.data, len(records), C.byref(out), C.sizeof(WeakSignalLevels))
+    if rc != OK:
+        raise FmrError(f"fmr_weak_signal_derive failed ({rc}): {L.fmr_last_error().decode()}")
+    return {k: getattr(out, k) for k, _ in WeakSignalLevels._fields_ if k not in ("struct_size", "reserved")}
 
 
 def analyser_levels(records, spectra, view="L", band_lo_hz=0.0, band_hi_hz=0.0, tone_hz=0.0, tone_search_hz=0.0,
@@ -913,6 +964,25 @@ class Chain:
         """fmr_loudness_read: the oldest unread complete records of `stream` (at most cap; None: all that wait) as
         (records LOUDNESS_RECORD [n], info dict).  Reading drains them."""
         return self._read_records(self._L.fmr_loudness_read, LoudnessInfo, ((LOUDNESS_RECORD, None),), stream, cap)
+
+    def enable_weak_signal(self, act=False, actions=0, attack_ms=0.0, release_ms=0.0, blend_db=(0.0, 0.0),
+                           highcut_db=(0.0, 0.0), mute_db=(0.0, 0.0), highcut_hz=0.0, mute_floor_db=0.0,
+                           record_intervals=0, max_records=0):
+        """fmr_enable_weak_signal: weak-signal handling of every stream / channel (FM chains, once, before the first
+        call).  act=False measures and records only; act=True also applies stereo blend, high cut and soft mute (actions:
+        WS_BLEND | WS_HIGHCUT | WS_MUTE) to the audio the chain returns.  *_db are (lo, hi) pairs in dB of the smoothed
+        ultrasonic noise; 0 = the defaults (all three actions, 10 / 500 ms, 2500 Hz, -20 dB, records of 50 intervals,
+        1024 kept)."""
+        cfg = WeakSignalConfig(C.sizeof(WeakSignalConfig), WS_ACT if act else WS_MEASURE, int(actions), int(record_intervals),
+                               int(max_records), 0, float(attack_ms), float(release_ms), float(blend_db[0]),
+                               float(blend_db[1]), float(highcut_db[0]), float(highcut_db[1]), float(mute_db[0]),
+                               float(mute_db[1]), float(highcut_hz), float(mute_floor_db))
+        self._chk(self._L.fmr_enable_weak_signal(self.h, C.byref(cfg), C.sizeof(WeakSignalConfig)))
+
+    def weak_signal_records(self, stream=0, cap=None):
+        """fmr_weak_signal_read: the oldest unread complete records of `stream` (at most cap; None: all that wait) as
+        (records WEAK_SIGNAL_RECORD [n], info dict).  Reading drains them."""
+        return self._read_records(self._L.fmr_weak_signal_read, WeakSignalInfo, ((WEAK_SIGNAL_RECORD, None),), stream, cap)
 
     def enable_analyser(self, fft_size=0, interval_samples=0, max_records=0):
         """fmr_enable_analyser: the audio analyser of every stream / channel (any decoder chain, once, before the first

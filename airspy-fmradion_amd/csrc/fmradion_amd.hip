@@ -10,6 +10,7 @@
 // the host derives from the resampler's integer output-count law.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <thread>
@@ -39,6 +40,7 @@
 #include "kernels_analyser.hpp"
 #include "kernels_rfmon.hpp"
 #include "kernels_output.hpp"
+#include "kernels_weaksignal.hpp"
 #include "../host/fmradion_rds.hpp"
 
 namespace {
@@ -71,6 +73,8 @@ constexpr double kIfAtten = 140.0;     // resampler spec, DESIGN.md (FAST class)
 constexpr double kR8bAtten = 180.0, kR8bPassFrac = 0.98;   // R8B class: the defaults of r8b::CDSPResampler24 (IfResampler.cpp:25-29)
 constexpr double kAudioAtten = 180.0;
 constexpr int FMR_MODE_NONE = -1;
+// weak-signal handling: the default thresholds in dB of the smoothed detector reading (DESIGN.md section 16 has the table)
+constexpr double kWsBlendLo = -33.0, kWsBlendHi = -23.0, kWsHighcutHi = -15.0, kWsMuteHi = -9.0;
 // chunk lengths of the time-parallel recurrences (kernels_par.hpp)
 constexpr int C_AGC = 256, C_DC = 64, C_DE = 256, C_AM = 256, C_AM_DE = 128, K_AF_ITERS = 6;
 #ifndef FMR_C_PLL_MIN
@@ -342,6 +346,36 @@ struct OutputStage {
   OutArgs begin(unsigned long long block0, const int *if_len, int nb, long long N_au);
 };
 
+// Weak-signal handling (fmr_enable_weak_signal; kernels_weaksignal.hpp).  Two halves on the tail's
+// stream: the detector and the control read the call's MPX beside the other MPX readers (fmr_chain::ws_measure); in
+// FMR_WS_ACT the action rewrites the finished audio directly behind the output mux (fmr_chain::ws_act).  The sample and
+// frame counters live here and are taken when a call is issued (begin): the pipelined tail runs a call late.  The device
+// carries s, the open interval and record, the MPX history and the high cut's state.
+struct WsArgs { long long n0 = 0, n1 = 0, f0 = 0, f1 = 0; };     // the call's MPX samples [n0, n1) and audio frames [f0, f1)
+struct WeakSignalStage {
+  bool on = false;
+  fmr_weak_signal_config cfg{};              // the defaults filled in
+  WsCoef coef{};
+  double alpha = 0.0, drop = 0.0;            // the high cut's coefficient, 1 - g_floor
+  int pmax = 0, cring = 0, rmax = 0;         // interval pieces and audio chunks of a call at most, control ring length (2^k)
+  long long n = 0, f = 0;                    // MPX samples and audio frames handed in
+  DevBuf<double> d_h, d_pw, d_G, d_start;
+  DevBuf<float> d_hist;
+  DevBuf<WsPart> d_part;
+  DevBuf<WsState> d_state;
+  DevBuf<WsCtl> d_ctl;
+  DevBuf<WsRec> d_ring;
+  RecCursor cur;
+  unsigned long long intervals() const { return (unsigned long long)(n / kWsQ); }
+  unsigned long long done() const { return intervals() / (unsigned long long)cfg.record_intervals; }   // records complete
+  int init(int S, size_t max_if, size_t max_au, const fmr_weak_signal_config &m);
+  WsArgs begin(long long N_if, long long N_au) {
+    WsArgs a{n, n + N_if, f, f + N_au};
+    n += N_if; f += N_au;
+    return a;
+  }
+};
+
 }  // namespace
 
 // Diagnostic switches from the environment, read ONCE when a chain is created (INTEGRATION.md section 4 lists them);
@@ -510,6 +544,9 @@ struct fmr_chain : ChainShape {
   LoudnessStage ld;
   AnalyserStage an;
   OutputStage out;
+  WeakSignalStage ws;
+  int ws_measure(const fm_mpx_t *base, const WsArgs &a, hipStream_t st);
+  int ws_act(double *d_aud, long long astride, const WsArgs &a, hipStream_t st);
   int rds_stage(const fm_mpx_t *base, long long N, hipStream_t st);
   // one call's N samples per stream through monitor m on stream st: the source as kseg / kreduce read it (from, stride, off)
   int seg_stage(SegMonitor &m, const void *from, long long stride, int off, float rf, float scale, MonSegFn kseg,
@@ -812,6 +849,7 @@ struct fmr_chain : ChainShape {
     unsigned long long seq{};
     OutArgs out{};                     // output stage: the call's positions and its slot of the per-block IF RMS
     const float *out_ifrms = nullptr;
+    WsArgs ws{};                       // weak-signal handling: the call's positions
   };
   static constexpr int kDeBlock = 256;
   TailCtx tail_job{};
@@ -2368,6 +2406,7 @@ int fmr_chain::run_fm(CallCtx &k) {
   t.d_aud = k.d_aud; t.astride = (long long)k.astride; t.amA_prev = k.amA_prev; t.akB_prev = k.akB_prev;
   t.nch = stereo ? 2 : 1;
   if (out.on) { t.out = out.begin(k.out_block0, k.tab.if_len, nb, N_au); t.out_ifrms = out.ifrms_slot(k.par); }
+  if (ws.on) t.ws = ws.begin(N_if, N_au);
   for (int b = 0; b < nb; b++) t.au_max = std::max(t.au_max, k.tab.au_len[b]);
   t.count_am = (int)(arsc.mA - k.amA_prev);
   if ((size_t)t.count_am > max_amid || (size_t)N_au > max_au) { set_err("internal audio capacity exceeded"); return FMR_ERR_CAPACITY; }
@@ -2513,6 +2552,7 @@ int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
                            t.if_nrm ? k_mon_reduce<RfmSrc<true>> : k_mon_reduce<RfmSrc<false>>, "rfm_seg", "rfm_reduce",
                            t.N_if, ts))
       return rc;
+  if (ws.on) if (int rc = ws_measure(t.base, t.ws, ts)) return rc;
   const int nch = t.nch, dc_nc = t.dc_nc;
   const long long N_au = t.N_au;
   if (t.mono_enqueued) tail_channels(t, ts, 1, 1);
@@ -2539,6 +2579,7 @@ int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
       });
     }
   }
+  if (ws.on && ws.cfg.mode == FMR_WS_ACT) if (int rc = ws_act(t.d_aud, t.astride, t.ws, ts)) return rc;
   if (ld.on) if (int rc = ld_stage(t.d_aud, t.astride, N_au, ts)) return rc;
   if (an.on) if (int rc = an_stage(t.d_aud, t.astride, N_au, ts)) return rc;
   if (!(t.fin_covers_all && N_au > 0)) {        // (otherwise the wait before the output mux covered all three)
@@ -2825,6 +2866,110 @@ int fmr_chain::ld_stage(const double *d_aud, long long astride, long long N, hip
     p = a.a1;
   }
   ld.n = n1;
+  HIPCHK(hipGetLastError());
+  return FMR_OK;
+}
+
+// ---- weak-signal handling (kernels_weaksignal.hpp) ----
+// the detector's taps (fmr_filter_table "ws_usn"): delta - (Blackman-windowed sinc, cut-off 110 kHz at 384 kHz, sum 1)
+static const double *ws_taps() {
+  static const std::array<double, kWsTaps> h = [] {
+    std::array<double, kWsTaps> lp{};
+    const double fc = 110000.0 / kFmRate;
+    double sum = 0.0;
+    for (int k = 0; k < kWsTaps; k++) {
+      const double x = 2.0 * fc * (double)(k - 31);
+      const double sinc = k == 31 ? 1.0 : std::sin(M_PI * x) / (M_PI * x);
+      const double w = 0.42 - 0.5 * std::cos(2.0 * M_PI * (double)k / 62.0) + 0.08 * std::cos(4.0 * M_PI * (double)k / 62.0);
+      lp[k] = 2.0 * fc * sinc * w;
+      sum += lp[k];
+    }
+    for (int k = 0; k < kWsTaps; k++) lp[k] = (k == 31 ? 1.0 : 0.0) - lp[k] / sum;
+    return lp;
+  }();
+  return h.data();
+}
+
+int WeakSignalStage::init(int S, size_t max_if, size_t max_au, const fmr_weak_signal_config &m) {
+  static_assert(sizeof(WsRec) == sizeof(fmr_weak_signal_record), "WsRec is fmr_weak_signal_record");
+  static_assert(offsetof(WsRec, usn_sum) == offsetof(fmr_weak_signal_record, usn_sum), "the doubles of a record");
+  cfg = m;
+  coef.c_att = 1.0 - std::exp(-2.0 / m.attack_ms);
+  coef.c_rel = 1.0 - std::exp(-2.0 / m.release_ms);
+  const double lo[3] = {m.blend_lo_db, m.highcut_lo_db, m.mute_lo_db}, hi[3] = {m.blend_hi_db, m.highcut_hi_db, m.mute_hi_db};
+  const unsigned bit[3] = {FMR_WS_BLEND, FMR_WS_HIGHCUT, FMR_WS_MUTE};
+  for (int a = 0; a < 3; a++) { coef.lo[a] = lo[a]; coef.hi[a] = hi[a]; coef.on[a] = (m.actions & bit[a]) != 0; }
+  coef.R = m.record_intervals; coef.L = m.max_records;
+  alpha = 1.0 - std::exp(-2.0 * M_PI * m.highcut_hz / 48000.0);
+  drop = 1.0 - std::pow(10.0, m.mute_floor_db / 20.0);
+  // a call touches its whole intervals and one more at either end; the ring keeps the call's intervals and the few the
+  // audio still lags behind (ws_act checks both ends)
+  pmax = (int)(max_if / kWsQ + 2);
+  rmax = (int)(max_au / kWsA + 2);
+  cring = 64;
+  while ((size_t)cring < (size_t)pmax + 64) cring <<= 1;
+  // beta = one step of the recurrence itself on the unit state, then beta^(2^b) by squaring
+  std::vector<double> pw(kWsPow);
+  pw[0] = 1.0 + alpha * (0.0 - 1.0);
+  for (int b = 1; b < kWsPow; b++) pw[b] = pw[b - 1] * pw[b - 1];
+  int rc;
+  if ((rc = upload(d_h, ws_taps(), (size_t)kWsTaps))) return rc;
+  if ((rc = upload(d_pw, pw.data(), pw.size()))) return rc;
+  if ((rc = d_hist.alloc((size_t)S * kWsHist))) return rc;
+  if ((rc = d_part.alloc((size_t)S * pmax))) return rc;
+  if ((rc = d_state.alloc((size_t)S))) return rc;
+  if ((rc = d_ctl.alloc((size_t)S * cring))) return rc;
+  if ((rc = d_ring.alloc((size_t)S * (size_t)m.max_records))) return rc;
+  if (m.mode == FMR_WS_ACT) {
+    if ((rc = d_G.alloc((size_t)S * 2 * rmax))) return rc;
+    if ((rc = d_start.alloc((size_t)S * 2 * rmax))) return rc;
+  }
+  cur.reset(S, m.max_records);
+  n = f = 0;
+  on = true;
+  return FMR_OK;
+}
+
+// one call's MPX (the samples [a.n0, a.n1) of every stream, in the base slot) through the detector and the control
+int fmr_chain::ws_measure(const fm_mpx_t *base, const WsArgs &a, hipStream_t st) {
+  if (a.n1 <= a.n0) return FMR_OK;
+  const long long tiles = (a.n1 - 1) / kWsQ - a.n0 / kWsQ + 1, base_stride = H_b + (long long)max_if;
+  if (tiles > ws.pmax) { set_err("internal: a call of %lld MPX samples has more control intervals than the weak-signal stage holds", a.n1 - a.n0); return FMR_ERR_CAPACITY; }
+  timed_on(st, "ws_usn", [&] {
+    hipLaunchKernelGGL(k_ws_usn, dim3((unsigned)tiles, S), dim3(kWsT), 0, st, base, base_stride, H_b, ws.d_hist.p, ws.d_h.p, a.n0,
+                       a.n1, ws.pmax, ws.d_part.p);
+  });
+  timed_on(st, "ws_control", [&] {
+    hipLaunchKernelGGL(k_ws_control, dim3(S), dim3(64), 0, st, ws.d_part.p, ws.pmax, a.n0, a.n1, ws.coef, ws.d_state.p, ws.d_ctl.p,
+                       ws.cring - 1, ws.d_ring.p, base, base_stride, H_b, ws.d_hist.p);
+  });
+  HIPCHK(hipGetLastError());
+  return FMR_OK;
+}
+
+// one call's audio (the frames [a.f0, a.f1) of every stream, where the mux wrote them) through the action, in place
+int fmr_chain::ws_act(double *d_aud, long long astride, const WsArgs &a, hipStream_t st) {
+  if (a.f1 <= a.f0) return FMR_OK;
+  // Frame f takes the intervals floor(f / A) - 1 and the one before.  The audio resampler has delivered frame f only
+  // after MPX sample 8 f, so Q floor(f / A) <= 8 f < n1 and the interval is complete; and the ring still holds the oldest.
+  const long long done = a.n1 / kWsQ, g_lo = a.f0 / kWsA, g_hi = (a.f1 - 1) / kWsA;
+  if (g_hi > done || done - (g_lo - 2) > ws.cring) {
+    set_err("internal: weak-signal control intervals %lld .. %lld of the call's audio are not among the %d kept up to %lld",
+            g_lo - 2, g_hi - 1, ws.cring, done - 1);
+    return FMR_ERR_CAPACITY;
+  }
+  const int runs = (int)(g_hi - g_lo + 1);
+  if (runs > ws.rmax) { set_err("internal: a call of %lld audio frames has more chunks than the weak-signal stage holds", a.f1 - a.f0); return FMR_ERR_CAPACITY; }
+  WsActArgs w{};
+  w.f0 = a.f0; w.f1 = a.f1; w.ch = stereo ? 2 : 1; w.cmask = ws.cring - 1; w.alpha = ws.alpha; w.drop = ws.drop;
+  timed_on(st, "ws_nodes", [&] {
+    hipLaunchKernelGGL(k_ws_pass1, dim3((runs + 63) / 64, S), dim3(64), 0, st, d_aud, astride, w, ws.d_ctl.p, runs, ws.rmax, ws.d_G.p);
+    hipLaunchKernelGGL(k_ws_nodes, dim3(S * w.ch), dim3(64), 0, st, ws.d_G.p, ws.d_start.p, w, runs, ws.rmax, ws.d_pw.p, ws.d_state.p);
+  });
+  timed_on(st, "ws_pass2", [&] {
+    hipLaunchKernelGGL(k_ws_pass2, dim3((runs + 63) / 64, S), dim3(64), 0, st, d_aud, astride, w, ws.d_ctl.p, runs, ws.rmax,
+                       ws.d_start.p, ws.d_state.p);
+  });
   HIPCHK(hipGetLastError());
   return FMR_OK;
 }
@@ -4360,6 +4505,122 @@ int fmr_output_rate_taps(int rate, double *taps, int cap, int *L, int *M, int *T
   return (int)n;
 }
 
+// ---- weak-signal handling: C-ABI ----
+int fmr_enable_weak_signal(fmr_chain *c, const fmr_weak_signal_config *cfg, size_t cfg_size) {
+  const char *fn = "fmr_enable_weak_signal";
+  if (!cfg) { set_err("%s: cfg is null", fn); return FMR_ERR_BAD_ARG; }
+  fmr_weak_signal_config m;
+  if (int rc = take_sized(fn, "fmr_weak_signal_config", cfg, cfg_size, m)) return rc;
+  if (m.mode != FMR_WS_MEASURE && m.mode != FMR_WS_ACT) {
+    set_err("%s: mode %d is neither FMR_WS_MEASURE (0) nor FMR_WS_ACT (1)", fn, m.mode);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.actions == 0) m.actions = FMR_WS_BLEND | FMR_WS_HIGHCUT | FMR_WS_MUTE;
+  if (m.actions & ~7u) { set_err("%s: actions 0x%x has bits beyond FMR_WS_BLEND | FMR_WS_HIGHCUT | FMR_WS_MUTE", fn, m.actions); return FMR_ERR_BAD_ARG; }
+  if (m.record_intervals == 0) m.record_intervals = 50;
+  if (m.max_records == 0) m.max_records = 1024;
+  if (m.record_intervals < 1 || m.record_intervals > 1000) {
+    set_err("%s: record_intervals %d is outside 1 .. 1000 (0 = 50)", fn, m.record_intervals);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.max_records < 1 || m.max_records > 65536) {
+    set_err("%s: max_records %d is outside 1 .. 65536 (0 = 1024)", fn, m.max_records);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.attack_ms == 0.0) m.attack_ms = 10.0;
+  if (m.release_ms == 0.0) m.release_ms = 500.0;
+  if (!(m.attack_ms > 0.0 && m.attack_ms <= 60000.0)) { set_err("%s: attack_ms %g is outside (0, 60000] (0 = 10)", fn, m.attack_ms); return FMR_ERR_BAD_ARG; }
+  if (!(m.release_ms > 0.0 && m.release_ms <= 60000.0)) { set_err("%s: release_ms %g is outside (0, 60000] (0 = 500)", fn, m.release_ms); return FMR_ERR_BAD_ARG; }
+  struct Pair { const char *name; double *lo, *hi; double dlo, dhi; };
+  const Pair pairs[3] = {{"blend", &m.blend_lo_db, &m.blend_hi_db, kWsBlendLo, kWsBlendHi},
+                         {"highcut", &m.highcut_lo_db, &m.highcut_hi_db, kWsBlendHi, kWsHighcutHi},
+                         {"mute", &m.mute_lo_db, &m.mute_hi_db, kWsHighcutHi, kWsMuteHi}};
+  for (const Pair &p : pairs) {
+    if (*p.lo == 0.0 && *p.hi == 0.0) { *p.lo = p.dlo; *p.hi = p.dhi; }
+    if (!(std::isfinite(*p.lo) && std::isfinite(*p.hi) && *p.lo < *p.hi)) {
+      set_err("%s: %s_lo_db %g and %s_hi_db %g are not finite with lo < hi (both 0 = %g and %g)", fn, p.name, *p.lo, p.name, *p.hi, p.dlo, p.dhi);
+      return FMR_ERR_BAD_ARG;
+    }
+  }
+  if (m.highcut_hz == 0.0) m.highcut_hz = 2500.0;
+  if (!(m.highcut_hz >= 500.0 && m.highcut_hz <= 15000.0)) { set_err("%s: highcut_hz %g is outside 500 .. 15000 (0 = 2500)", fn, m.highcut_hz); return FMR_ERR_BAD_ARG; }
+  if (m.mute_floor_db == 0.0) m.mute_floor_db = -20.0;
+  if (!(std::isfinite(m.mute_floor_db) && m.mute_floor_db < 0.0)) { set_err("%s: mute_floor_db %g is not finite and below 0 (0 = -20)", fn, m.mute_floor_db); return FMR_ERR_BAD_ARG; }
+  if (!c) { set_err("%s: chain is null", fn); return FMR_ERR_BAD_ARG; }
+  if (c->mode != FMR_MODE_FM) {
+    set_err("%s: weak-signal handling reads the MPX of an FM chain (mode FMR_MODE_FM); mode %d %s", fn, c->mode,
+            c->mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no MPX" : "is not covered");
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (c->pilot_shift) {
+    set_err("%s: the chain has pilot_shift (the QMM output): its two channels are not L and R", fn);
+    return FMR_ERR_UNSUPPORTED;
+  }
+  return enable_stage(fn, c, c->ws, "weak-signal stage", "MPX sample", c->S, c->max_if, c->max_au, m);
+}
+
+int fmr_weak_signal_read(fmr_chain *c, int stream, fmr_weak_signal_record *recs, int cap, fmr_weak_signal_info *info,
+                         size_t info_size) {
+  if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_weak_signal_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
+  if (!c->ws.on) { set_err("fmr_weak_signal_read: the chain has no weak-signal stage (fmr_enable_weak_signal)"); return FMR_ERR_BAD_ARG; }
+  if (cap > 0 && !recs) { set_err("fmr_weak_signal_read: recs is null"); return FMR_ERR_BAD_ARG; }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    const unsigned long long done = c->ws.done();
+    const int n = c->ws.cur.take(stream, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
+      HIPCHK(hipMemcpy(recs + k, c->ws.d_ring.p + (size_t)stream * c->ws.cur.L + slot, m * sizeof(fmr_weak_signal_record),
+                       hipMemcpyDeviceToHost));
+      return FMR_OK;
+    });
+    if (n < 0) return n;
+    if (info) {
+      fmr_weak_signal_info full{};
+      full.struct_size = (unsigned)sizeof full;
+      full.channels = c->stereo ? 2 : 1;
+      ring_info(full, c->ws.cur, stream, done);
+      full.intervals_complete = c->ws.intervals();
+      full.record_intervals = c->ws.cfg.record_intervals;
+      full.max_records = c->ws.cfg.max_records;
+      full.mode = c->ws.cfg.mode;
+      full.actions = c->ws.cfg.actions;
+      give_sized(info, info_size, full);
+    }
+    return n;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_weak_signal_derive(const fmr_weak_signal_record *recs, int n, fmr_weak_signal_levels *out, size_t out_size) {
+  if (!recs || !out || n < 1) { set_err("fmr_weak_signal_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
+  for (int i = 0; i < n; i++)
+    if (recs[i].n_intervals == 0) {
+      set_err("fmr_weak_signal_derive: record %d has n_intervals 0 (not a record of fmr_weak_signal_read)", i);
+      return FMR_ERR_BAD_ARG;
+    }
+  fmr_weak_signal_levels full{};
+  full.struct_size = (unsigned)sizeof full;
+  double sum = 0.0, peak = 0.0;
+  unsigned long long ni = 0, nb = 0, nh = 0, nm = 0, non = 0;
+  for (int i = 0; i < n; i++) {
+    const fmr_weak_signal_record &r = recs[i];
+    sum += r.usn_sum;
+    peak = std::max(peak, r.usn_peak);
+    ni += r.n_intervals; non += r.n_nonfinite;
+    if (r.max_blend > 0.0) nb += r.n_intervals;
+    if (r.max_highcut > 0.0) nh += r.n_intervals;
+    if (r.max_mute > 0.0) nm += r.n_intervals;
+  }
+  auto db10 = [](double v) { return v > 0.0 ? 10.0 * std::log10(v) : -INFINITY; };
+  const double mean = sum / (double)ni;
+  full.usn_mean_db = db10(mean); full.usn_peak_db = db10(peak);
+  full.usn_mean_hz = 75000.0 * std::sqrt(mean); full.usn_peak_hz = 75000.0 * std::sqrt(peak);
+  full.blend_share = (double)nb / (double)ni; full.highcut_share = (double)nh / (double)ni; full.mute_share = (double)nm / (double)ni;
+  full.t_blend = recs[n - 1].t_blend; full.t_highcut = recs[n - 1].t_highcut; full.t_mute = recs[n - 1].t_mute;
+  full.n_intervals = ni; full.n_nonfinite = non;
+  give_sized(out, out_size, full);
+  return FMR_OK;
+}
+
 // ---- audio monitor: C-ABI ----
 int fmr_enable_loudness(fmr_chain *c, const fmr_loudness_config *cfg, size_t cfg_size) {
   if (!cfg) { set_err("fmr_enable_loudness: cfg is null"); return FMR_ERR_BAD_ARG; }
@@ -4801,6 +5062,7 @@ int fmr_filter_table(const char *name, const void **data, int *is_double) {
       {"jj1bdx_fm_384kHz_medium", k_jj1bdx_fm_384kHz_medium, 127, 0},
       {"jj1bdx_cw_48khz_500hz", k_jj1bdx_cw_48khz_500hz, 2049, 0},
       {"jj1bdx_ssb_48khz_1500hz", k_jj1bdx_ssb_48khz_1500hz, 2049, 0},
+      {"ws_usn", ws_taps(), kWsTaps, 1},       // the weak-signal detector's high-pass (built in double at first use)
   };
   if (!name) return FMR_ERR_BAD_ARG;
   for (const auto &e : tabs)

@@ -146,6 +146,29 @@ inline LoudnessReport loudness_report(fmr_chain *c, int stream, double silence_d
   return out;
 }
 
+// weak-signal handling (fmr_enable_weak_signal / fmr_weak_signal_read / fmr_weak_signal_derive): the drained records in
+// ascending order and the levels pooled from them
+struct WeakSignalReport {
+  std::vector<fmr_weak_signal_record> records;
+  fmr_weak_signal_info info{};
+  fmr_weak_signal_levels levels{};   // (of `records`; all zero when there are none)
+};
+inline void weak_signal(fmr_chain *c, const fmr_weak_signal_config &m) {
+  check(fmr_enable_weak_signal(c, &m, sizeof m), "fmr_enable_weak_signal");
+}
+inline WeakSignalReport weak_signal_report(fmr_chain *c, int stream) {
+  WeakSignalReport out;
+  const int ready = fmr_weak_signal_read(c, stream, nullptr, 0, &out.info, sizeof out.info);
+  if (ready < 0) check(ready, "fmr_weak_signal_read");
+  if (ready == 0) return out;
+  out.records.resize((size_t)ready);
+  const int n = fmr_weak_signal_read(c, stream, out.records.data(), ready, &out.info, sizeof out.info);
+  if (n < 0) check(n, "fmr_weak_signal_read");
+  out.records.resize((size_t)n);
+  if (n > 0) check(fmr_weak_signal_derive(out.records.data(), n, &out.levels, sizeof out.levels), "fmr_weak_signal_derive");
+  return out;
+}
+
 // audio analyser (fmr_enable_analyser / fmr_analyser_read / fmr_analyser_derive): the drained records in ascending order
 // with their spectra [n][3][bins] (scaled to power), and the levels of all of them pooled under `rule`
 struct AnalyserReport {
@@ -267,6 +290,7 @@ using OutputData = fmr_detail::OutputData;
 using RfRecord = fmr_detail::RfRecord;
 using ModulationRecord = fmr_detail::ModulationRecord;
 using LoudnessReport = fmr_detail::LoudnessReport;
+using WeakSignalReport = fmr_detail::WeakSignalReport;
 using AnalyserReport = fmr_detail::AnalyserReport;
 
 // FilterParameters (include/FilterParameters.h:31-49): tables served by the library.
@@ -404,6 +428,7 @@ public:
     m_chain = fmr_detail::make(m_cfg, m_rds);
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
+    if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
@@ -418,6 +443,7 @@ public:
     m_chain = fmr_detail::make(m_cfg, true);
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
+    if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
@@ -454,6 +480,19 @@ public:
     m_ld = true;
   }
   LoudnessReport read_loudness(double silence_dbfs = -60.0) { return fmr_detail::loudness_report(m_chain, 0, silence_dbfs); }
+
+  // Weak-signal handling (no counterpart in the reference; fmr_enable_weak_signal): stereo blend, high cut and soft mute
+  // driven by the MPX's ultrasonic noise; before the first process(), once.  cfg: the fields to set (zeros = the defaults;
+  // mode FMR_WS_MEASURE records only, FMR_WS_ACT also rewrites the audio process() returns).  read_weak_signal() drains
+  // the complete records and pools them.
+  void enable_weak_signal(fmr_weak_signal_config cfg = fmr_weak_signal_config{}) {
+    if (m_started) fmr_detail::fail("FmDecoder::enable_weak_signal: after the first process()");
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::weak_signal(m_chain, cfg);
+    m_ws_cfg = cfg;
+    m_ws = true;
+  }
+  WeakSignalReport read_weak_signal() { return fmr_detail::weak_signal_report(m_chain, 0); }
 
   // RF monitor (no counterpart in the reference; fmr_enable_rf_monitor): records of interval_samples IF samples (0 =
   // 38400, 100 ms) with level, C/N, envelope AM and fade percentiles; before the first process(), once.
@@ -516,6 +555,7 @@ public:
       m_chain = fmr_detail::make(m_cfg, m_rds);
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
+    if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
@@ -615,6 +655,8 @@ private:
   fmr_monitor_config m_mon_cfg{};
   bool m_ld = false;
   fmr_loudness_config m_ld_cfg{};
+  bool m_ws = false;
+  fmr_weak_signal_config m_ws_cfg{};
   bool m_rf = false;
   fmr_rf_monitor_config m_rf_cfg{};
   bool m_an = false;
@@ -832,6 +874,7 @@ public:
     m_chain = fmr_detail::make(m_cfg, true);
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
+    if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
@@ -871,6 +914,18 @@ public:
   LoudnessReport read_loudness(size_t ch, double silence_dbfs = -60.0) {
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
     return fmr_detail::loudness_report(m_chain, (int)ch, silence_dbfs);
+  }
+  // Weak-signal handling of every channel (fmr_enable_weak_signal), before the first process(), once; FM banks only.
+  // read_weak_signal(ch) drains channel ch's complete records and pools them.
+  void enable_weak_signal(fmr_weak_signal_config cfg = fmr_weak_signal_config{}) {
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::weak_signal(m_chain, cfg);
+    m_ws_cfg = cfg;
+    m_ws = true;
+  }
+  WeakSignalReport read_weak_signal(size_t ch) {
+    if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
+    return fmr_detail::weak_signal_report(m_chain, (int)ch);
   }
 
   // Audio analyser of every channel (fmr_enable_analyser), before the first process(), once.  read_analyser(ch) drains
@@ -969,6 +1024,8 @@ private:
   fmr_monitor_config m_mon_cfg{};
   bool m_ld = false;
   fmr_loudness_config m_ld_cfg{};
+  bool m_ws = false;
+  fmr_weak_signal_config m_ws_cfg{};
   bool m_rf = false;
   fmr_rf_monitor_config m_rf_cfg{};
   bool m_an = false;

@@ -724,6 +724,103 @@ int fmr_loudness_read(fmr_chain *c, int stream, fmr_loudness_record *recs, int c
  * trailing_silence_blocks the run that ends at the last record.  Loudness range (EBU 3342) is not computed. */
 int fmr_loudness_derive(const fmr_loudness_record *recs, int n, double silence_dbfs, fmr_loudness_levels *out, size_t out_size);
 
+/* --- Weak-signal handling: what every FM receiver does to a station near the FM threshold --
+ * stereo blend, high cut and soft mute -- driven by the ultrasonic noise of the station's own MPX.  The stage is off by
+ * default and absent when off; the reference has no weak-signal logic, so parity with it is a matter of chains without the
+ * stage.  In FMR_WS_MEASURE the stage only reads: audio, fmr_status, PPS events, RDS groups and every monitor's records are
+ * what they are without it.  In FMR_WS_ACT it rewrites the finished audio behind the output mux, in front of the audio
+ * monitor, the analyser and the output stage: they and the caller get the handled audio.
+ * Timeline: the MPX has F = 384000 and absolute sample indices from the chain's first MPX sample; samples in front of
+ * index 0 are 0.  A control interval is Q = 768 MPX samples (2 ms); interval j covers [j Q, (j + 1) Q).  The audio has
+ * 48000 frames per second and absolute frame indices; an audio interval is A = 96 frames.
+ * Detector (ultrasonic noise): h is a 63-tap linear-phase high-pass built on the host in double,
+ *   lp[k] = 2 fc sinc(2 fc (k - 31)) w[k],  fc = 110000 / F,  w[k] = 0.42 - 0.5 cos(2 pi k / 62) + 0.08 cos(4 pi k / 62),
+ *   lp scaled to sum 1,  h = delta[k - 31] - lp        (sinc(x) = sin(pi x) / (pi x); fmr_filter_table("ws_usn"))
+ * (DC gain -2e-16, at most -75 dB up to 90 kHz, within +-0.015 dB from 125 kHz up: programme, pilot and RDS lie below
+ * 60 kHz, what is left is discriminator noise).  y[n] = sum_k h[k] (double)x[n - k] with x the chain's fp32 MPX, k
+ * ascending, in fp64; u_j = (sum of y[n]^2 over interval j) / Q.  A non-finite x is counted in n_nonfinite and enters as 0.
+ * Control, per stream, serial in j, in fp64, carried on the device across calls:
+ *   s_j = s_{j-1} + c (u_j - s_{j-1}),  c = the attack coefficient when u_j > s_{j-1}, else the release coefficient,
+ *   coefficient = 1 - exp(-2 / tau_ms) (computed on the host),  s_{-1} = 0;
+ *   D_j = 10 log10(s_j) in dB re full-scale MPX^2 (full-scale MPX = 1.0 = 75 kHz; -INFINITY for s_j = 0);
+ *   per action a: t_a(j) = clamp((D_j - lo_a) / (hi_a - lo_a), 0, 1); 0 for -INFINITY and for an action switched off.
+ * Action: audio frame f uses the control values of interval J = floor(f / A) - 1 and ramps to them from those of J - 1:
+ *   p = ((f mod A) + 1) / A,  v(f) = v_{J-1} + p (v_J - v_{J-1}) for each of the three t; intervals below 0 hold 0.
+ * (Interval J is complete when frame f exists: the audio resampler delivers frame f only after MPX sample 8 f.)  Then, in
+ * fp64, unfused, in this order, with L = R = x on a stereo = 0 chain, which skips steps 1 and 2:
+ *   1. S = 0.5 (L - R)                2. L1 = L - t_b S,  R1 = R + t_b S
+ *   3. w[f] = w[f - 1] + alpha (x1[f] - w[f - 1]) per channel,  alpha = 1 - exp(-2 pi highcut_hz / 48000),  w[-1] = 0
+ *   4. x2 = x1 + t_h (w - x1)         5. out = (1 - t_m (1 - g_floor)) x2,  g_floor = 10^(mute_floor_db / 20)
+ * With all three t at 0 every step returns its input bit for bit on finite audio: a clean station's audio is unchanged.
+ * The high cut is a crossfade to a fixed one-pole low-pass, so its recurrence is time-invariant.
+ * Records: record i covers the intervals [i R, (i + 1) R), R = record_intervals, and is complete in the call that delivers
+ * MPX sample (i + 1) R Q - 1.  usn_sum = sum of u_j, usn_peak = max u_j, smoothed = s at the record's end, t_* the three
+ * t at its end, max_* their maxima over the record.  Ring, drop counting and info as for the audio monitor.
+ * Reproducibility: the integer fields are bit-identical for any cut of the input into calls; the doubles agree between
+ * cuts at fp64 rounding (u within 1e-12 of mean_n (sum_k |h_k| |x_{n-k}|)^2); the same cut gives the same bits; no float
+ * atomics.
+ * Default thresholds, in dB of s: the steady detector reading of the benchmark's station at an IF C/N (in 384 kHz) of 30,
+ * 20, 12 and 6 dB, measured on the float64 oracle's MPX (DESIGN.md section 16 has the table): blend -33 .. -23, high cut
+ * -23 .. -15, mute -15 .. -9. */
+enum { FMR_WS_MEASURE = 0, FMR_WS_ACT = 1 };
+enum { FMR_WS_BLEND = 1, FMR_WS_HIGHCUT = 2, FMR_WS_MUTE = 4 };
+typedef struct {
+  unsigned struct_size;       /* sizeof(fmr_weak_signal_config) as the caller knows it (0: cfg_size); a larger size is refused */
+  int mode;                   /* FMR_WS_MEASURE (the audio is never written) | FMR_WS_ACT */
+  unsigned actions;           /* FMR_WS_BLEND | FMR_WS_HIGHCUT | FMR_WS_MUTE; 0 = all three */
+  int record_intervals;       /* R: 1 .. 1000; 0 = 50 (100 ms) */
+  int max_records;            /* L: 1 .. 65536; 0 = 1024 */
+  int reserved;
+  double attack_ms, release_ms;            /* > 0 .. 60000; 0 = 10 and 500 */
+  double blend_lo_db, blend_hi_db;         /* lo < hi, finite; both 0 = the defaults above */
+  double highcut_lo_db, highcut_hi_db;
+  double mute_lo_db, mute_hi_db;
+  double highcut_hz;                       /* 500 .. 15000; 0 = 2500 */
+  double mute_floor_db;                    /* < 0 and finite; 0 = -20 */
+} fmr_weak_signal_config;
+typedef struct {
+  uint64_t index, first_interval;          /* i and i R */
+  uint32_t n_intervals, n_nonfinite;       /* R; non-finite MPX samples of the record */
+  double usn_sum, usn_peak, smoothed;
+  double t_blend, t_highcut, t_mute;
+  double max_blend, max_highcut, max_mute;
+} fmr_weak_signal_record;
+typedef struct {
+  unsigned struct_size;
+  int channels;                   /* 2 for a stereo chain, 1 for stereo = 0 */
+  uint64_t records_complete;      /* since create (of every stream: they run in step) */
+  uint64_t records_dropped;       /* of this stream: overwritten unread */
+  uint64_t first_unread;          /* index of the oldest unread record after this call */
+  uint64_t records_ready;         /* complete records still unread after this call */
+  uint64_t intervals_complete;    /* control intervals complete since create */
+  int record_intervals, max_records;   /* R and L as enabled (defaults filled in) */
+  int mode;
+  unsigned actions;
+} fmr_weak_signal_info;
+typedef struct {
+  unsigned struct_size;
+  int reserved;
+  double usn_mean_db, usn_peak_db;         /* 10 log10 of (sum usn_sum / sum n_intervals) and of max usn_peak; -INFINITY for 0 */
+  double usn_mean_hz, usn_peak_hz;         /* 75000 sqrt of the same: RMS deviation of the ultrasonic noise */
+  double blend_share, highcut_share, mute_share;   /* sum n_intervals of the records with max_* > 0 / sum n_intervals */
+  double t_blend, t_highcut, t_mute;       /* of the last record */
+  uint64_t n_intervals, n_nonfinite;       /* pooled */
+} fmr_weak_signal_levels;
+/* Checks the fields first (FMR_ERR_BAD_ARG, fmr_last_error names the field; also a size larger than this library's
+ * struct), then the chain: NULL is FMR_ERR_BAD_ARG; any FMR_MODE_FM chain is accepted (stereo or stereo = 0, banks,
+ * fmr_create_rds, either resampler class, pipelined or in_order, the equaliser); every other mode, front-end-only chains
+ * and channelizers, and a chain with pilot_shift (its two channels are not L and R) are FMR_ERR_UNSUPPORTED.  Allowed
+ * once, before the chain's first sample: a second call, or one after any processing call, is FMR_ERR_BAD_ARG.  A chain that
+ * never calls it allocates nothing for the stage and launches none of its kernels. */
+int fmr_enable_weak_signal(fmr_chain *c, const fmr_weak_signal_config *cfg, size_t cfg_size);
+/* Synchronises like the other getters, then drains up to cap complete records of `stream`, oldest first, and returns how
+ * many.  cap = 0 returns the number waiting and drains nothing.  info (may be NULL) takes info_size bytes (0 = this
+ * header's size).  FMR_ERR_BAD_ARG on a chain without the stage. */
+int fmr_weak_signal_read(fmr_chain *c, int stream, fmr_weak_signal_record *recs, int cap, fmr_weak_signal_info *info,
+                         size_t info_size);
+/* Host only, in double, no device: pools n records (n >= 1, each with n_intervals > 0) into the levels above. */
+int fmr_weak_signal_derive(const fmr_weak_signal_record *recs, int n, fmr_weak_signal_levels *out, size_t out_size);
+
 /* --- Audio analyser: the spectrum analyser the reference's author judges receivers with, on the
  * device.  A decoder chain of any mode with it enabled measures the finished audio of every stream / bank channel where
  * the output mux wrote it: the level and frequency of a test tone, THD, THD+N, SINAD and the noise floor, per channel or
