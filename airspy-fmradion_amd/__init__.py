@@ -58,6 +58,7 @@ EXPORTS = [
     "fmr_enable_output", "fmr_output_read", "fmr_squelch_level_from_db",
     "fmr_set_output_rate", "fmr_get_output_rate", "fmr_output_rate_taps",
     "fmr_enable_weak_signal", "fmr_weak_signal_read", "fmr_weak_signal_derive",
+    "fmr_enable_blanker", "fmr_blanker_read", "fmr_blanker_derive",
 ]
 # FMR_WINDOW_* (include/fmradion_amd.h): windows of the band spectrum
 WINDOW_HANN, WINDOW_RECT, WINDOW_BLACKMAN_HARRIS = 0, 1, 2
@@ -107,6 +108,14 @@ WEAK_SIGNAL_RECORD = np.dtype([("index", np.uint64), ("first_interval", np.uint6
                                ("smoothed", np.float64), ("t_blend", np.float64), ("t_highcut", np.float64),
                                ("t_mute", np.float64), ("max_blend", np.float64), ("max_highcut", np.float64),
                                ("max_mute", np.float64)])
+# FMR_NB_* (include/fmradion_amd.h): mode of the impulse blanker; NB_Q: samples per interval
+NB_MEASURE, NB_ACT = 0, 1
+NB_Q = 4096
+# fmr_blanker_record as a numpy structured type (72 bytes)
+BLANKER_RECORD = np.dtype([("index", np.uint64), ("first_interval", np.uint64), ("n_triggers", np.uint64),
+                           ("n_blanked", np.uint64), ("n_nonfinite", np.uint64), ("n_runs", np.uint64),
+                           ("power_q", np.uint64), ("threshold", np.float64), ("n_intervals", np.uint32),
+                           ("peak", np.float32)])
 
 
 class FmrError(RuntimeError):
@@ -251,6 +260,27 @@ class WeakSignalLevels(C.Structure):
                 ("usn_mean_hz", C.c_double), ("usn_peak_hz", C.c_double), ("blend_share", C.c_double),
                 ("highcut_share", C.c_double), ("mute_share", C.c_double), ("t_blend", C.c_double),
                 ("t_highcut", C.c_double), ("t_mute", C.c_double), ("n_intervals", C.c_uint64), ("n_nonfinite", C.c_uint64)]
+
+
+class BlankerConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("mode", C.c_int), ("threshold_db", C.c_double), ("gate_samples", C.c_int),
+                ("max_run_samples", C.c_int), ("average_intervals", C.c_int), ("record_intervals", C.c_int),
+                ("max_records", C.c_int), ("reserved", C.c_int)]
+
+
+class BlankerInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("rows", C.c_int), ("records_complete", C.c_uint64),
+                ("records_dropped", C.c_uint64), ("first_unread", C.c_uint64), ("records_ready", C.c_uint64),
+                ("intervals_complete", C.c_uint64), ("mode", C.c_int), ("gate_samples", C.c_int),
+                ("max_run_samples", C.c_int), ("average_intervals", C.c_int), ("record_intervals", C.c_int),
+                ("max_records", C.c_int)]
+
+
+class BlankerLevels(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("reserved", C.c_int), ("blanked_share", C.c_double),
+                ("runs_per_second", C.c_double), ("level_dbfs", C.c_double), ("peak_dbfs", C.c_double),
+                ("n_intervals", C.c_uint64), ("n_triggers", C.c_uint64), ("n_blanked", C.c_uint64),
+                ("n_nonfinite", C.c_uint64), ("n_runs", C.c_uint64)]
 
 
 class LoudnessConfig(C.Structure):
@@ -468,6 +498,12 @@ def lib(ab=False):
     L.fmr_weak_signal_read.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(WeakSignalInfo), C.c_size_t]
     L.fmr_weak_signal_derive.restype = C.c_int
     L.fmr_weak_signal_derive.argtypes = [vp, C.c_int, C.POINTER(WeakSignalLevels), C.c_size_t]
+    L.fmr_enable_blanker.restype = C.c_int
+    L.fmr_enable_blanker.argtypes = [vp, C.POINTER(BlankerConfig), C.c_size_t]
+    L.fmr_blanker_read.restype = C.c_int
+    L.fmr_blanker_read.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(BlankerInfo), C.c_size_t]
+    L.fmr_blanker_derive.restype = C.c_int
+    L.fmr_blanker_derive.argtypes = [vp, C.c_int, C.c_double, C.POINTER(BlankerLevels), C.c_size_t]
     _libs[ab] = L
     return L
 
@@ -564,6 +600,19 @@ def loudness_levels(records, silence_dbfs=-60.0):
     if rc != OK:
         raise FmrError(f"fmr_loudness_derive failed ({rc}): {L.fmr_last_error().decode()}")
     return {k: getattr(out, k) for k, _ in LoudnessLevels._fields_ if k not in ("struct_size", "reserved")}
+
+
+def blanker_levels(records, rate):
+    """fmr_blanker_derive (host only): blanked_share, runs_per_second (at `rate` input samples per second), level_dbfs,
+    peak_dbfs and the pooled counts of the records (a BLANKER_RECORD array as Chain.blanker_records returns them), as a dict
+    of fmr_blanker_levels."""
+    L = lib()
+    records = np.ascontiguousarray(records, dtype=BLANKER_RECORD)
+    out = BlankerLevels()
+    rc = L.fmr_blanker_derive(records.ctypes.data, len(records), float(rate), C.byref(out), C.sizeof(BlankerLevels))
+    if rc != OK:
+        raise FmrError(f"fmr_blanker_derive failed ({rc}): {L.fmr_last_error().decode()}")
+    return {k: getattr(out, k) for k, _ in BlankerLevels._fields_ if k not in ("struct_size", "reserved")}
 
 
 def weak_signal_levels(records):
@@ -984,6 +1033,22 @@ class Chain:
         (records WEAK_SIGNAL_RECORD [n], info dict).  Reading drains them."""
         return self._read_records(self._L.fmr_weak_signal_read, WeakSignalInfo, ((WEAK_SIGNAL_RECORD, None),), stream, cap)
 
+    def enable_blanker(self, act=False, threshold_db=0.0, gate_samples=0, max_run_samples=0, average_intervals=0,
+                       record_intervals=0, max_records=0):
+        """fmr_enable_blanker: the impulse blanker on the input rows, in front of every front end (chains with the IF
+        resampler on complex-float input, banks and channelizers included; once, before the first call).  act=False
+        measures and records only; act=True zeroes the gated samples in what the front end reads.  0 = the defaults
+        (12 dB over the mean of 16 intervals of 4096 samples, a gate of 0.8 us, runs of 8 gates at most, records of 256
+        intervals, 1024 kept)."""
+        cfg = BlankerConfig(C.sizeof(BlankerConfig), NB_ACT if act else NB_MEASURE, float(threshold_db), int(gate_samples),
+                            int(max_run_samples), int(average_intervals), int(record_intervals), int(max_records), 0)
+        self._chk(self._L.fmr_enable_blanker(self.h, C.byref(cfg), C.sizeof(BlankerConfig)))
+
+    def blanker_records(self, row=0, cap=None):
+        """fmr_blanker_read: the oldest unread complete records of input row `row` (0 for a bank or a channelizer; at most
+        cap; None: all that wait) as (records BLANKER_RECORD [n], info dict).  Reading drains them."""
+        return self._read_records(self._L.fmr_blanker_read, BlankerInfo, ((BLANKER_RECORD, None),), row, cap)
+
     def enable_analyser(self, fft_size=0, interval_samples=0, max_records=0):
         """fmr_enable_analyser: the audio analyser of every stream / channel (any decoder chain, once, before the first
         call); 0 = the defaults (N = 4096, records of 6 N audio frames, 64 records kept)."""
@@ -1071,7 +1136,7 @@ class Chain:
         return buf[:2 * n].view(np.complex64).copy()
 
     def debug_read(self, which, stream=0, cap=1 << 24):
-        dt = {0: np.complex64, 1: np.float32, 2: np.float64, 3: np.float64, 4: np.float32, 5: np.uint64}[which]
+        dt = {0: np.complex64, 1: np.float32, 2: np.float64, 3: np.float64, 4: np.float32, 5: np.uint64, 6: np.complex64}[which]
         buf = np.empty(cap, dtype=dt)
         n = self._chk(self._L.fmr_debug_read(self.h, stream, which, buf.ctypes.data_as(C.c_void_p), buf.nbytes))
         return buf[:n].copy()

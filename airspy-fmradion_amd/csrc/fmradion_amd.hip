@@ -41,6 +41,7 @@
 #include "kernels_rfmon.hpp"
 #include "kernels_output.hpp"
 #include "kernels_weaksignal.hpp"
+#include "kernels_blanker.hpp"
 #include "../host/fmradion_rds.hpp"
 
 namespace {
@@ -376,6 +377,36 @@ struct WeakSignalStage {
   }
 };
 
+// Impulse blanker on the capture (fmr_enable_blanker; kernels_blanker.hpp).  It runs at the head of a
+// call on the decoder stream, where CallCtx receives the input (fmr_chain::nb_stage): the level and the apply kernel in front
+// of the front end, the records on the side stream behind an event.  The sample counter lives here and is taken when a call
+// is issued.  In FMR_NB_ACT the call's readers get the blanked rows instead of the caller's: two row buffers by call parity,
+// because a reader of call N's rows (the input history, on the side stream of an in_order chain) may still be pending when
+// call N + 1 is blanked; it is done before call N + 1's front end, which call N + 2's blanker follows on the same stream.
+// The parts of a call are kept twice as well: the records kernel of call N reads them beside call N + 1, and call N + 2 waits
+// for that kernel's event before it writes them again.
+struct BlankerStage {
+  bool on = false;
+  fmr_blanker_config cfg{};                  // the defaults filled in
+  NbCoef coef{};
+  int rows = 0, pmax = 0, aring = 0;         // input rows, pieces of a call at most, ring of A per row (2^k)
+  size_t pitch = 0;                          // samples between the rows of a row buffer (one more under an odd caller's stride)
+  long long n = 0;                           // samples handed in per row
+  unsigned long long calls = 0;              // calls that brought samples
+  const float2 *last_rows = nullptr; long long last_stride = 0, last_n = 0;    // FMR_NB_ACT: what the last call's front end read
+  DevBuf<NbPart> d_part;                     // [2][rows][pmax]
+  DevBuf<unsigned long long> d_aring;        // [rows][aring]
+  DevBuf<unsigned char> d_carry;             // [2][rows][G + M]
+  DevBuf<NbState> d_state;
+  DevBuf<NbRec> d_ring;
+  DevBuf<float2> d_rows[2];
+  Event ev_apply, ev_rec[2];
+  RecCursor cur;
+  unsigned long long intervals() const { return (unsigned long long)(n / kNbQ); }
+  unsigned long long done() const { return intervals() / (unsigned long long)cfg.record_intervals; }   // records complete
+  int init(int rows_, size_t max_in, const fmr_blanker_config &m);
+};
+
 }  // namespace
 
 // Diagnostic switches from the environment, read ONCE when a chain is created (INTEGRATION.md section 4 lists them);
@@ -545,6 +576,8 @@ struct fmr_chain : ChainShape {
   AnalyserStage an;
   OutputStage out;
   WeakSignalStage ws;
+  BlankerStage nb;
+  int nb_stage(const float2 *&d_iq, size_t &stride, long long N_in);
   int ws_measure(const fm_mpx_t *base, const WsArgs &a, hipStream_t st);
   int ws_act(double *d_aud, long long astride, const WsArgs &a, hipStream_t st);
   int rds_stage(const fm_mpx_t *base, long long N, hipStream_t st);
@@ -1391,6 +1424,7 @@ int fmr_chain::run(const float2 *d_iq, size_t stride, const uint32_t *block_len,
   CallCtx k{};
   k.d_iq = d_iq; k.stride = stride; k.block_len = block_len; k.nb = nb; k.d_aud = d_aud; k.astride = astride;
   k.audio_len = audio_len; k.N_in = N_in;
+  if (this->nb.on && N_in > 0) if (int rc = nb_stage(k.d_iq, k.stride, N_in)) return rc;     // (FMR_NB_ACT: every reader below takes the blanked rows)
   k.h_tab = h_tab_all.p + (size_t)slot * tab_ints;
   k.d_tab_slot = d_tab.p + (size_t)slot * tab_ints;
   k.tab = HostTab{k.h_tab, k.h_tab + max_blocks, k.h_tab + 2 * max_blocks, k.h_tab + 3 * max_blocks, k.h_tab + 4 * max_blocks};
@@ -2974,6 +3008,76 @@ int fmr_chain::ws_act(double *d_aud, long long astride, const WsArgs &a, hipStre
   return FMR_OK;
 }
 
+// ---- impulse blanker (kernels_blanker.hpp) ----
+int BlankerStage::init(int rows_, size_t max_in, const fmr_blanker_config &m) {
+  static_assert(sizeof(NbRec) == sizeof(fmr_blanker_record), "NbRec is fmr_blanker_record");
+  static_assert(offsetof(NbRec, threshold) == offsetof(fmr_blanker_record, threshold) &&
+                offsetof(NbRec, peak) == offsetof(fmr_blanker_record, peak), "the fields of a record");
+  cfg = m;
+  rows = rows_;
+  coef.G = m.gate_samples; coef.M = m.max_run_samples; coef.W = m.average_intervals; coef.R = m.record_intervals;
+  coef.L = m.max_records; coef.act = m.mode == FMR_NB_ACT;
+  coef.g = std::pow(10.0, m.threshold_db / 10.0);
+  coef.r[0] = 0.0;
+  for (int c = 1; c <= kNbMaxW; c++) coef.r[c] = 1.0 / ((double)c * 281474976710656.0);
+  pmax = (int)(max_in / kNbQ + 2);       // a call touches its whole intervals and one more at either end
+  aring = 64;
+  while (aring < pmax + m.average_intervals + 2) aring <<= 1;
+  pitch = (max_in + 1) & ~(size_t)1;
+  int rc;
+  if ((rc = d_part.alloc((size_t)2 * rows * pmax))) return rc;
+  if ((rc = d_aring.alloc((size_t)rows * aring))) return rc;
+  if ((rc = d_carry.alloc((size_t)2 * rows * (coef.G + coef.M)))) return rc;
+  if ((rc = d_state.alloc((size_t)rows))) return rc;
+  if ((rc = d_ring.alloc((size_t)rows * (size_t)m.max_records))) return rc;
+  if (coef.act)      // (a row may start one sample in, to sit on the caller's 16-byte phase, and be one sample further apart)
+    for (DevBuf<float2> &b : d_rows) if ((rc = b.alloc((size_t)rows * (pitch + 1) + 2))) return rc;
+  if ((rc = ev_apply.create(hipEventDisableTiming))) return rc;
+  for (Event &e : ev_rec) if ((rc = e.create(hipEventDisableTiming))) return rc;
+  cur.reset(rows, m.max_records);
+  n = 0; calls = 0;
+  on = true;
+  return FMR_OK;
+}
+
+// One call's input rows (the samples [nb.n, nb.n + N_in) of every row at d_iq) through the blanker, in front of everything
+// that reads them; in FMR_NB_ACT d_iq and stride then name the blanked rows.
+int fmr_chain::nb_stage(const float2 *&d_iq, size_t &stride, long long N_in) {
+  BlankerStage &b = this->nb;
+  const long long n0 = b.n, n1 = n0 + N_in;
+  const int pieces = (int)((n1 - 1) / kNbQ - n0 / kNbQ + 1);
+  if (pieces > b.pmax) { set_err("internal: a call of %lld input samples has more intervals than the blanker holds", N_in); return FMR_ERR_CAPACITY; }
+  b.n = n1;
+  const int par = (int)(++b.calls & 1);
+  NbPart *part = b.d_part.p + (size_t)par * b.rows * b.pmax;
+  if (b.calls > 2) HIPCHK(hipStreamWaitEvent(stream, b.ev_rec[par], 0));     // (the records kernel of two calls ago read these parts)
+  float2 *out = nullptr;
+  long long ostride = 0;
+  if (b.coef.act) {      // the same 16-byte phase as the caller's rows, row by row: the front end picks the forms it would have
+    ostride = (long long)(b.pitch + (stride & 1));
+    out = b.d_rows[par].p + (((uintptr_t)d_iq >> 3) & 1);
+  }
+  timed_on(stream, "nb_level", [&] {
+    hipLaunchKernelGGL(k_nb_level, dim3((unsigned)pieces, b.rows), dim3(kNbT), 0, stream, d_iq, (long long)stride, n0, n1, b.pmax, part);
+  });
+  timed_on(stream, "nb_apply", [&] {
+    hipLaunchKernelGGL(k_nb_apply, dim3((unsigned)pieces, b.rows), dim3(kNbT), 0, stream, d_iq, (long long)stride, out, ostride, n0, n1,
+                       b.pmax, par, part, b.d_aring.p, b.aring - 1, b.d_carry.p, b.d_state.p, b.coef);
+  });
+  HIPCHK(hipEventRecord(b.ev_apply, stream));
+  HIPCHK(hipStreamWaitEvent(side, b.ev_apply, 0));
+  timed_on(side, "nb_records", [&] {
+    hipLaunchKernelGGL(k_nb_records, dim3(b.rows), dim3(64), 0, side, part, b.pmax, n0, n1, b.d_state.p, b.d_ring.p, b.coef.R, b.coef.L);
+  });
+  HIPCHK(hipEventRecord(b.ev_rec[par], side));
+  HIPCHK(hipGetLastError());
+  if (b.coef.act) {
+    d_iq = out; stride = (size_t)ostride;
+    b.last_rows = out; b.last_stride = ostride; b.last_n = N_in;
+  }
+  return FMR_OK;
+}
+
 // ---- audio analyser (kernels_analyser.hpp) ----
 template <int LOGN>
 static void an_shape(AnalyserStage &a) {
@@ -4020,6 +4124,13 @@ long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t 
   long long n = c->last_n_if;
   const void *src = nullptr;
   size_t esz = 0;
+  if (which == 6) {       // the input row the front end read in the most recent call (chains whose blanker acts; `stream` is an input row)
+    if (!c->nb.on || !c->nb.coef.act || stream >= c->nb.rows) { set_err("fmr_debug_read: tap 6 (blanked input rows) needs a chain with fmr_enable_blanker in FMR_NB_ACT, and an input row"); return FMR_ERR_BAD_ARG; }
+    n = c->nb.last_n;
+    if ((size_t)n * sizeof(float2) > cap_bytes) return FMR_ERR_CAPACITY;
+    if (n) HIPCHK(hipMemcpy(out, c->nb.last_rows + (long long)stream * c->nb.last_stride, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost));
+    return n;
+  }
   if (which == 5 && !c->d_fe_stamps.p) {      // the symbol reliabilities of the most recent call (chains with RDS)
     if (!c->rds.on) { set_err("fmr_debug_read: tap 5 (RDS symbol reliabilities) needs a chain made by fmr_create_rds"); return FMR_ERR_BAD_ARG; }
     c->rds.drain();
@@ -4617,6 +4728,118 @@ int fmr_weak_signal_derive(const fmr_weak_signal_record *recs, int n, fmr_weak_s
   full.blend_share = (double)nb / (double)ni; full.highcut_share = (double)nh / (double)ni; full.mute_share = (double)nm / (double)ni;
   full.t_blend = recs[n - 1].t_blend; full.t_highcut = recs[n - 1].t_highcut; full.t_mute = recs[n - 1].t_mute;
   full.n_intervals = ni; full.n_nonfinite = non;
+  give_sized(out, out_size, full);
+  return FMR_OK;
+}
+
+// ---- impulse blanker: C-ABI ----
+int fmr_enable_blanker(fmr_chain *c, const fmr_blanker_config *cfg, size_t cfg_size) {
+  const char *fn = "fmr_enable_blanker";
+  if (!cfg) { set_err("%s: cfg is null", fn); return FMR_ERR_BAD_ARG; }
+  fmr_blanker_config m;
+  if (int rc = take_sized(fn, "fmr_blanker_config", cfg, cfg_size, m)) return rc;
+  if (m.mode != FMR_NB_MEASURE && m.mode != FMR_NB_ACT) {
+    set_err("%s: mode %d is neither FMR_NB_MEASURE (0) nor FMR_NB_ACT (1)", fn, m.mode);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.threshold_db == 0.0) m.threshold_db = 12.0;
+  if (!(m.threshold_db >= 6.0 && m.threshold_db <= 40.0)) { set_err("%s: threshold_db %g is outside 6 .. 40 (0 = 12)", fn, m.threshold_db); return FMR_ERR_BAD_ARG; }
+  if (m.gate_samples < 0 || m.gate_samples > kNbMaxG) {
+    set_err("%s: gate_samples %d is outside 1 .. %d (0 = max(2, ceil(0.8e-6 input_rate)))", fn, m.gate_samples, kNbMaxG);
+    return FMR_ERR_BAD_ARG;
+  }
+  auto bad_run = [&](int G) {
+    set_err("%s: max_run_samples %d is outside gate_samples (%d) .. %d (0 = 8 gate_samples, %d at most)", fn, m.max_run_samples, G, kNbMaxM, kNbMaxM);
+    return FMR_ERR_BAD_ARG;
+  };
+  if (m.max_run_samples < 0 || m.max_run_samples > kNbMaxM || (m.max_run_samples && m.max_run_samples < std::max(1, m.gate_samples)))
+    return bad_run(std::max(1, m.gate_samples));
+  if (m.average_intervals == 0) m.average_intervals = 16;
+  if (m.average_intervals < 1 || m.average_intervals > kNbMaxW) {
+    set_err("%s: average_intervals %d is outside 1 .. %d (0 = 16)", fn, m.average_intervals, kNbMaxW);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.record_intervals == 0) m.record_intervals = 256;
+  if (m.record_intervals < 1 || m.record_intervals > 4096) {
+    set_err("%s: record_intervals %d is outside 1 .. 4096 (0 = 256)", fn, m.record_intervals);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.max_records == 0) m.max_records = 1024;
+  if (m.max_records < 1 || m.max_records > 65536) {
+    set_err("%s: max_records %d is outside 1 .. 65536 (0 = 1024)", fn, m.max_records);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!c) { set_err("%s: chain is null", fn); return FMR_ERR_BAD_ARG; }
+  if (c->in_fmt != 0) {
+    set_err("%s: the blanker reads complex float samples (FMR_IQ_CF32); this chain takes a raw input format", fn);
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (!c->has_rs) {
+    set_err("%s: the blanker sits in front of the IF resampler; this chain has none (enable_resampler = 0)", fn);
+    return FMR_ERR_UNSUPPORTED;
+  }
+  // (the gate is a time, 0.8 us: longer than an impulse, shorter than one IF sample)
+  if (m.gate_samples == 0) m.gate_samples = std::min(kNbMaxG, std::max(2, (int)std::ceil(0.8e-6 * c->cfg.input_rate)));
+  if (m.max_run_samples == 0) m.max_run_samples = std::min(kNbMaxM, 8 * m.gate_samples);
+  if (m.max_run_samples < m.gate_samples) return bad_run(m.gate_samples);
+  static_assert(kNbMaxG - 1 + kNbMaxM <= kNbQ, "G - 1 + M <= Q holds for every accepted G and M");
+  return enable_stage(fn, c, c->nb, "blanker", "input sample", c->in_rows(), c->max_in, m);
+}
+
+int fmr_blanker_read(fmr_chain *c, int row, fmr_blanker_record *recs, int cap, fmr_blanker_info *info, size_t info_size) {
+  if (!c || cap < 0) { set_err("fmr_blanker_read: bad chain or cap"); return FMR_ERR_BAD_ARG; }
+  if (!c->nb.on) { set_err("fmr_blanker_read: the chain has no blanker (fmr_enable_blanker)"); return FMR_ERR_BAD_ARG; }
+  if (row < 0 || row >= c->nb.rows) { set_err("fmr_blanker_read: row %d is not one of the chain's %d input rows", row, c->nb.rows); return FMR_ERR_BAD_ARG; }
+  if (cap > 0 && !recs) { set_err("fmr_blanker_read: recs is null"); return FMR_ERR_BAD_ARG; }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    const unsigned long long done = c->nb.done();
+    const int n = c->nb.cur.take(row, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
+      HIPCHK(hipMemcpy(recs + k, c->nb.d_ring.p + (size_t)row * c->nb.cur.L + slot, m * sizeof(fmr_blanker_record), hipMemcpyDeviceToHost));
+      return FMR_OK;
+    });
+    if (n < 0) return n;
+    if (info) {
+      fmr_blanker_info full{};
+      full.struct_size = (unsigned)sizeof full;
+      full.rows = c->nb.rows;
+      ring_info(full, c->nb.cur, row, done);
+      full.intervals_complete = c->nb.intervals();
+      const fmr_blanker_config &m = c->nb.cfg;
+      full.mode = m.mode; full.gate_samples = m.gate_samples; full.max_run_samples = m.max_run_samples;
+      full.average_intervals = m.average_intervals; full.record_intervals = m.record_intervals; full.max_records = m.max_records;
+      give_sized(info, info_size, full);
+    }
+    return n;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_blanker_derive(const fmr_blanker_record *recs, int n, double input_rate, fmr_blanker_levels *out, size_t out_size) {
+  if (!recs || !out || n < 1) { set_err("fmr_blanker_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
+  if (!(input_rate > 0.0) || !std::isfinite(input_rate)) { set_err("fmr_blanker_derive: input_rate %g is not a positive rate", input_rate); return FMR_ERR_BAD_ARG; }
+  for (int i = 0; i < n; i++)
+    if (recs[i].n_intervals == 0) {
+      set_err("fmr_blanker_derive: record %d has n_intervals 0 (not a record of fmr_blanker_read)", i);
+      return FMR_ERR_BAD_ARG;
+    }
+  fmr_blanker_levels full{};
+  full.struct_size = (unsigned)sizeof full;
+  double pq = 0.0;
+  float peak = 0.f;
+  for (int i = 0; i < n; i++) {
+    const fmr_blanker_record &r = recs[i];
+    full.n_intervals += r.n_intervals; full.n_triggers += r.n_triggers; full.n_blanked += r.n_blanked;
+    full.n_nonfinite += r.n_nonfinite; full.n_runs += r.n_runs;
+    pq += (double)r.power_q;
+    peak = std::max(peak, r.peak);
+  }
+  auto db10 = [](double v) { return v > 0.0 ? 10.0 * std::log10(v) : -INFINITY; };
+  const double samples = (double)full.n_intervals * (double)kNbQ;
+  full.blanked_share = (double)full.n_blanked / samples;
+  full.runs_per_second = (double)full.n_runs * input_rate / samples;
+  full.level_dbfs = db10(pq / ((double)full.n_intervals * 68719476736.0));
+  full.peak_dbfs = db10((double)peak);
   give_sized(out, out_size, full);
   return FMR_OK;
 }

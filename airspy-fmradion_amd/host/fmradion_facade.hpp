@@ -169,6 +169,29 @@ inline WeakSignalReport weak_signal_report(fmr_chain *c, int stream) {
   return out;
 }
 
+// impulse blanker on the capture (fmr_enable_blanker / fmr_blanker_read / fmr_blanker_derive): the drained records of one
+// input row in ascending order and the levels pooled from them
+struct BlankerReport {
+  std::vector<fmr_blanker_record> records;
+  fmr_blanker_info info{};
+  fmr_blanker_levels levels{};   // (of `records`; all zero when there are none)
+};
+inline void blanker(fmr_chain *c, const fmr_blanker_config &m) {
+  check(fmr_enable_blanker(c, &m, sizeof m), "fmr_enable_blanker");
+}
+inline BlankerReport blanker_report(fmr_chain *c, int row, double input_rate) {
+  BlankerReport out;
+  const int ready = fmr_blanker_read(c, row, nullptr, 0, &out.info, sizeof out.info);
+  if (ready < 0) check(ready, "fmr_blanker_read");
+  if (ready == 0) return out;
+  out.records.resize((size_t)ready);
+  const int n = fmr_blanker_read(c, row, out.records.data(), ready, &out.info, sizeof out.info);
+  if (n < 0) check(n, "fmr_blanker_read");
+  out.records.resize((size_t)n);
+  if (n > 0) check(fmr_blanker_derive(out.records.data(), n, input_rate, &out.levels, sizeof out.levels), "fmr_blanker_derive");
+  return out;
+}
+
 // audio analyser (fmr_enable_analyser / fmr_analyser_read / fmr_analyser_derive): the drained records in ascending order
 // with their spectra [n][3][bins] (scaled to power), and the levels of all of them pooled under `rule`
 struct AnalyserReport {
@@ -291,6 +314,7 @@ using RfRecord = fmr_detail::RfRecord;
 using ModulationRecord = fmr_detail::ModulationRecord;
 using LoudnessReport = fmr_detail::LoudnessReport;
 using WeakSignalReport = fmr_detail::WeakSignalReport;
+using BlankerReport = fmr_detail::BlankerReport;
 using AnalyserReport = fmr_detail::AnalyserReport;
 
 // FilterParameters (include/FilterParameters.h:31-49): tables served by the library.
@@ -368,6 +392,7 @@ public:
     cfg.device = device; cfg.n_streams = 1; cfg.mode = -1; cfg.input_rate = input_rate; cfg.output_rate = output_rate;
     cfg.enable_resampler = 1; cfg.max_block_len = max_input_length; cfg.max_blocks = 1; cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(cfg);
+    m_rate = input_rate;
   }
   ~IfResampler() { if (m_chain) fmr_destroy(m_chain); }
   IfResampler(const IfResampler &) = delete;
@@ -381,9 +406,19 @@ public:
                       "fmr_resample");
     samples_out.resize(n);
   }
+  // Impulse blanker on the input (no counterpart in the reference; fmr_enable_blanker): before the first process(), once;
+  // cfg: the fields to set (zeros = the defaults; mode FMR_NB_MEASURE records only, FMR_NB_ACT zeroes the gated samples in
+  // what the resampler reads).  read_blanker() drains the complete records and pools them.
+  void enable_blanker(fmr_blanker_config cfg = fmr_blanker_config{}) {
+    if (!m_chain) fmr_detail::fail("IfResampler::enable_blanker: equal rates, nothing is resampled");
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::blanker(m_chain, cfg);
+  }
+  BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_rate); }
 
 private:
   fmr_chain *m_chain = nullptr;
+  double m_rate = 0.0;
 };
 
 // PilotPhaseLock::PpsEvent (PilotPhaseLock.h:40-44)
@@ -429,6 +464,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
+    if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
@@ -444,6 +480,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
+    if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
@@ -493,6 +530,19 @@ public:
     m_ws = true;
   }
   WeakSignalReport read_weak_signal() { return fmr_detail::weak_signal_report(m_chain, 0); }
+
+  // Impulse blanker on the source-rate input (no counterpart in the reference; fmr_enable_blanker): after
+  // attach_front_end() (the stage sits in front of the IF resampler), before the first process(), once.  cfg: the fields
+  // to set (zeros = the defaults; FMR_NB_MEASURE records only, FMR_NB_ACT zeroes the gated samples in what the front end
+  // reads).  read_blanker() drains the complete records and pools them.
+  void enable_blanker(fmr_blanker_config cfg = fmr_blanker_config{}) {
+    if (m_started) fmr_detail::fail("FmDecoder::enable_blanker: after the first process()");
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::blanker(m_chain, cfg);
+    m_nb_cfg = cfg;
+    m_nb = true;
+  }
+  BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_cfg.input_rate); }
 
   // RF monitor (no counterpart in the reference; fmr_enable_rf_monitor): records of interval_samples IF samples (0 =
   // 38400, 100 ms) with level, C/N, envelope AM and fade percentiles; before the first process(), once.
@@ -556,6 +606,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
+    if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
@@ -657,6 +708,8 @@ private:
   fmr_loudness_config m_ld_cfg{};
   bool m_ws = false;
   fmr_weak_signal_config m_ws_cfg{};
+  bool m_nb = false;
+  fmr_blanker_config m_nb_cfg{};
   bool m_rf = false;
   fmr_rf_monitor_config m_rf_cfg{};
   bool m_an = false;
@@ -700,9 +753,19 @@ public:
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg);
+    if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
   }
+  // Impulse blanker on the source-rate input (fmr_enable_blanker): after attach_front_end(), before the first process(),
+  // once; cfg: the fields to set (zeros = the defaults).  read_blanker() drains the complete records and pools them.
+  void enable_blanker(fmr_blanker_config cfg = fmr_blanker_config{}) {
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::blanker(m_chain, cfg);
+    m_nb_cfg = cfg;
+    m_nb = true;
+  }
+  BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_cfg.input_rate); }
   // Output stage (fmr_enable_output): squelch, gain, PCM frames and the per-block IF / AF meters on the device; before
   // the first process(), once.  rate: the PCM ring at that rate (fmr_set_output_rate).  read_output() drains everything
   // that waits.
@@ -747,6 +810,8 @@ private:
     return st;
   }
   fmr_config m_cfg{};
+  bool m_nb = false;
+  fmr_blanker_config m_nb_cfg{};
   bool m_an = false;
   fmr_analyser_config m_an_cfg{};
   bool m_out = false;
@@ -777,9 +842,19 @@ public:
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg);
+    if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
   }
+  // Impulse blanker on the source-rate input (fmr_enable_blanker): after attach_front_end(), before the first process(),
+  // once; cfg: the fields to set (zeros = the defaults).  read_blanker() drains the complete records and pools them.
+  void enable_blanker(fmr_blanker_config cfg = fmr_blanker_config{}) {
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::blanker(m_chain, cfg);
+    m_nb_cfg = cfg;
+    m_nb = true;
+  }
+  BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_cfg.input_rate); }
   // Output stage (fmr_enable_output): squelch, gain, PCM frames and the per-block IF / AF meters on the device; before
   // the first process(), once.  rate: the PCM ring at that rate (fmr_set_output_rate).  read_output() drains everything
   // that waits.
@@ -824,6 +899,8 @@ private:
   }
   const double m_freq_dev;
   fmr_config m_cfg{};
+  bool m_nb = false;
+  fmr_blanker_config m_nb_cfg{};
   bool m_an = false;
   fmr_analyser_config m_an_cfg{};
   bool m_out = false;
@@ -875,6 +952,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
+    if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
@@ -927,6 +1005,15 @@ public:
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
     return fmr_detail::weak_signal_report(m_chain, (int)ch);
   }
+  // Impulse blanker on the capture (fmr_enable_blanker), before the first process(), once: one row serves all channels.
+  // read_blanker() drains the capture's complete records and pools them.
+  void enable_blanker(fmr_blanker_config cfg = fmr_blanker_config{}) {
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::blanker(m_chain, cfg);
+    m_nb_cfg = cfg;
+    m_nb = true;
+  }
+  BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_cfg.input_rate); }
 
   // Audio analyser of every channel (fmr_enable_analyser), before the first process(), once.  read_analyser(ch) drains
   // channel ch's complete records and derives their pooled levels.
@@ -1026,6 +1113,8 @@ private:
   fmr_loudness_config m_ld_cfg{};
   bool m_ws = false;
   fmr_weak_signal_config m_ws_cfg{};
+  bool m_nb = false;
+  fmr_blanker_config m_nb_cfg{};
   bool m_rf = false;
   fmr_rf_monitor_config m_rf_cfg{};
   bool m_an = false;
@@ -1051,6 +1140,7 @@ public:
     cfg.output_rate = output_rate; cfg.enable_resampler = 1; cfg.resampler_class = resampler_class;
     cfg.max_block_len = max_block_len; cfg.max_blocks = 1; cfg.channel_offset_hz = m_offsets.data();
     fmr_detail::check(fmr_create_channelizer(&cfg, sizeof cfg, &m_chain), "fmr_create_channelizer");
+    m_rate = input_rate;
   }
   ~Channelizer() { fmr_destroy(m_chain); }
   Channelizer(const Channelizer &) = delete;
@@ -1058,6 +1148,14 @@ public:
 
   size_t channels() const { return m_offsets.size(); }
   int32_t offset_hz(size_t ch) const { return m_offsets.at(ch); }
+
+  // Impulse blanker on the capture (fmr_enable_blanker), before the first process(), once: one row serves all channels.
+  // read_blanker() drains the capture's complete records and pools them.
+  void enable_blanker(fmr_blanker_config cfg = fmr_blanker_config{}) {
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::blanker(m_chain, cfg);
+  }
+  BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_rate); }
 
   // out[k] = what channel k produced from this capture block; blocks longer than the chain's block capacity are
   // resampled in consecutive pieces
@@ -1080,6 +1178,7 @@ public:
 private:
   std::vector<int32_t> m_offsets;
   size_t m_max_block;
+  double m_rate = 0.0;
   fmr_chain *m_chain = nullptr;
 };
 

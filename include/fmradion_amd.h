@@ -122,7 +122,9 @@ typedef struct {
    * KNOWN LIMITATION: a bank never takes the fused front end, and the stage B it runs instead at some shapes (the banded
    * matrix-core k_ifr_poly4 at 10 MS/s FAST) widens a non-finite input sample to its whole tile of IF samples, where a
    * one-stream chain fed u_s keeps the reference's tap support: around a NaN in the capture a channel's audio can
-   * differ from that chain's (the NaN itself never reaches the audio).  DESIGN.md, "Channel bank". */
+   * differ from that chain's (the NaN itself never reaches the audio).  In a bank whose blanker acts (fmr_enable_blanker,
+   * FMR_NB_ACT) a non-finite capture sample is zeroed before stage A reads it, so nothing is widened.  DESIGN.md,
+   * "Channel bank". */
   const int32_t *channel_offset_hz;
 } fmr_config;
 
@@ -309,7 +311,9 @@ int fmr_get_multipath_coefficients(fmr_chain *c, int stream, float *coeff, int c
  * chain without RDS).  Returns element count, or FMR_ERR_BAD_ARG for a
  * tap the most recent call did not leave in memory: behind the fused front end's discriminator epilogue (FM at
  * 10 MS/s without IF filter / equaliser) taps 0, 1 and 4 exist only in a chain created with FMR_DEBUG_TAPS=1 in the
- * environment -- the product keeps those signals on chip. */
+ * environment -- the product keeps those signals on chip.  6 = on a chain whose blanker acts (fmr_enable_blanker,
+ * FMR_NB_ACT), the input row `stream` as the front end read it in the most recent call (complex float; `stream` is an
+ * input row: 0 for a bank; returns the samples of that call); FMR_ERR_BAD_ARG on every other chain. */
 long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t cap_bytes);
 
 /* What this library holds of the HIP runtime right now, in the whole process: device buffers, page-locked host blocks,
@@ -820,6 +824,88 @@ int fmr_weak_signal_read(fmr_chain *c, int stream, fmr_weak_signal_record *recs,
                          size_t info_size);
 /* Host only, in double, no device: pools n records (n >= 1, each with n_intervals > 0) into the levels above. */
 int fmr_weak_signal_derive(const fmr_weak_signal_record *recs, int n, fmr_weak_signal_levels *out, size_t out_size);
+
+/* --- Impulse blanker on the capture: ignition, switching supplies, lightning, ADC glitches and
+ * dropped packets are one or two samples long in the wideband capture; the front end spreads each over its 103 + 210
+ * taps.  The stage zeroes them in the input rows of a call before any front-end form reads them.  It is off by default
+ * and absent when off.  In FMR_NB_MEASURE it only reads: every output of the chain is what it is without the stage.  In
+ * FMR_NB_ACT every reader of the call's input (every front-end form, the input history on whichever stream it is
+ * carried over, a bank's one-row history) reads the blanked rows, which the stage keeps in buffers of its own: the
+ * caller's buffer is never written.
+ * Timeline: per input row, sample index n counts from the chain's first sample, across blocks and calls of any length.
+ * Interval j covers [j Q, (j + 1) Q), Q = 4096.
+ * Power: p[n] = fl32(fl32(re re) + fl32(im im)), unfused.  A non-finite p (NaN or Inf) makes the sample non-finite.
+ * Level (exact: any cut into calls and any summation order gives the same bits): q[n] = 0 for a non-finite sample, else
+ * floor(min(p[n], 256) 2^36) as a 64-bit integer; A_j = sum of q[n] over interval j (below 2^56).
+ * Threshold (no recurrence): W = average_intervals, g = 10^(threshold_db / 10) and r[c] = 1 / (c 2^48), c = 1 .. W, are
+ * computed on the host in double.  T_0 = +INFINITY.  For j >= 1: c = min(j, W), S = A_{j-c} + .. + A_{j-1} (integer),
+ * T_j = max(g ((double)S r[c]), 2^-30): two fp64 products in this order.
+ * Trigger: trig[n] = non-finite[n] or (double)p[n] > T_{floor(n / Q)}.
+ * Gate, G = gate_samples: gate[n] = some trig[i], i in [max(0, n - G + 1), n].  Causal: the first sample over the
+ * threshold is itself gated, nothing in front of it is; a call boundary decides nothing.
+ * Give-up, M = max_run_samples: blank[n] = gate[n] and some i in [n - M, n - 1] with i < 0 or not gate[i].  A gate that
+ * stays closed longer than M samples passes its input through again until it has opened once: a +20 dB level step
+ * zeroes M samples, not everything until the average has caught up, and a run of non-finite samples longer than M
+ * passes through as it is.  blank[n] depends on the samples n - (G - 1 + M) .. n only.
+ * Output: out[n] = (0, 0) where blank[n], else x[n] bit for bit.
+ * Records: record i covers the intervals [i R, (i + 1) R), R = record_intervals, and is complete in the call that
+ * delivers sample (i + 1) R Q - 1.  n_runs counts the samples with blank[n] and not blank[n - 1]; power_q = sum of
+ * (A_j >> 12); peak = the largest finite p; threshold = T of the record's last interval.  Every field is bit-identical
+ * for any cut of the input into blocks and calls.  Ring, drop counting and info as for the audio monitor. */
+enum { FMR_NB_MEASURE = 0, FMR_NB_ACT = 1 };
+typedef struct {
+  unsigned struct_size;       /* sizeof(fmr_blanker_config) as the caller knows it (0: cfg_size); a larger size is refused */
+  int mode;                   /* FMR_NB_MEASURE (default) | FMR_NB_ACT */
+  double threshold_db;        /* 6 .. 40; 0 = 12 */
+  int gate_samples;           /* G: 1 .. 256; 0 = max(2, ceil(0.8e-6 input_rate)): 8 at 10 MS/s, 2 at 2.5 MS/s */
+  int max_run_samples;        /* M: G .. 1024 with G - 1 + M <= Q; 0 = 8 G */
+  int average_intervals;      /* W: 1 .. 64; 0 = 16 (6.6 ms at 10 MS/s) */
+  int record_intervals;       /* R: 1 .. 4096; 0 = 256 */
+  int max_records;            /* L: 1 .. 65536; 0 = 1024 */
+  int reserved;
+} fmr_blanker_config;
+typedef struct {
+  uint64_t index, first_interval;          /* i and i R */
+  uint64_t n_triggers, n_blanked, n_nonfinite, n_runs;
+  uint64_t power_q;
+  double threshold;
+  uint32_t n_intervals;                    /* R */
+  float peak;
+} fmr_blanker_record;
+typedef struct {
+  unsigned struct_size;
+  int rows;                       /* input rows of the chain: 1 for a bank or a channelizer */
+  uint64_t records_complete;      /* since create (of every row: they run in step) */
+  uint64_t records_dropped;       /* of this row: overwritten unread */
+  uint64_t first_unread;          /* index of the oldest unread record after this call */
+  uint64_t records_ready;         /* complete records still unread after this call */
+  uint64_t intervals_complete;    /* intervals complete since create */
+  int mode, gate_samples, max_run_samples, average_intervals, record_intervals, max_records;   /* as enabled (defaults filled in) */
+} fmr_blanker_info;
+typedef struct {
+  unsigned struct_size;
+  int reserved;
+  double blanked_share;           /* sum n_blanked / (sum n_intervals Q) */
+  double runs_per_second;         /* sum n_runs input_rate / (sum n_intervals Q), input_rate being fmr_blanker_derive's argument */
+  double level_dbfs;              /* 10 log10(sum power_q / (sum n_intervals 2^36)): mean |x|^2 re full scale 1.0; -INFINITY for 0 */
+  double peak_dbfs;               /* 10 log10(max peak); -INFINITY for 0 */
+  uint64_t n_intervals, n_triggers, n_blanked, n_nonfinite, n_runs;   /* pooled */
+} fmr_blanker_levels;
+/* Checks the fields first (FMR_ERR_BAD_ARG, fmr_last_error names the field; also a size larger than this library's
+ * struct), then the chain: NULL is FMR_ERR_BAD_ARG.  Accepted is every chain that runs the IF resampler on FMR_IQ_CF32
+ * input: plain chains of any mode, with or without enable_fourth_down, banks (one row serves all channels),
+ * channelizers and front-end-only chains, either resampler class, pipelined or in_order, through every processing entry
+ * point.  Raw input formats and chains without the resampler are FMR_ERR_UNSUPPORTED.  Allowed once, before the chain's
+ * first sample: a second call, or one after any processing call, is FMR_ERR_BAD_ARG.  A failed call leaves the chain and
+ * fmr_debug_live_resources as they were. */
+int fmr_enable_blanker(fmr_chain *c, const fmr_blanker_config *cfg, size_t cfg_size);
+/* Synchronises like the other getters, then drains up to cap complete records of input row `row` (0 for a bank), oldest
+ * first, and returns how many.  cap = 0 returns the number waiting and drains nothing.  info (may be NULL) takes info_size
+ * bytes (0 = this header's size).  FMR_ERR_BAD_ARG on a chain without the stage. */
+int fmr_blanker_read(fmr_chain *c, int row, fmr_blanker_record *recs, int cap, fmr_blanker_info *info, size_t info_size);
+/* Host only, in double, no device: pools n records (n >= 1, each with n_intervals > 0) into the levels above.  input_rate
+ * (samples per second, > 0) is only used for runs_per_second. */
+int fmr_blanker_derive(const fmr_blanker_record *recs, int n, double input_rate, fmr_blanker_levels *out, size_t out_size);
 
 /* --- Audio analyser: the spectrum analyser the reference's author judges receivers with, on the
  * device.  A decoder chain of any mode with it enabled measures the finished audio of every stream / bank channel where
