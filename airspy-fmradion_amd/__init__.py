@@ -59,6 +59,7 @@ EXPORTS = [
     "fmr_set_output_rate", "fmr_get_output_rate", "fmr_output_rate_taps",
     "fmr_enable_weak_signal", "fmr_weak_signal_read", "fmr_weak_signal_derive",
     "fmr_enable_blanker", "fmr_blanker_read", "fmr_blanker_derive",
+    "fmr_enable_iq_correction", "fmr_iq_correction_read", "fmr_iq_correction_derive",
 ]
 # FMR_WINDOW_* (include/fmradion_amd.h): windows of the band spectrum
 WINDOW_HANN, WINDOW_RECT, WINDOW_BLACKMAN_HARRIS = 0, 1, 2
@@ -116,6 +117,16 @@ BLANKER_RECORD = np.dtype([("index", np.uint64), ("first_interval", np.uint64), 
                            ("n_blanked", np.uint64), ("n_nonfinite", np.uint64), ("n_runs", np.uint64),
                            ("power_q", np.uint64), ("threshold", np.float64), ("n_intervals", np.uint32),
                            ("peak", np.float32)])
+# FMR_IQC_* (include/fmradion_amd.h): mode of the IQ corrector, and the mask of what it applies
+IQC_MEASURE, IQC_ACT = 0, 1
+IQC_DC, IQC_BALANCE = 1, 2
+# fmr_iq_correction_record as a numpy structured type (112 bytes)
+IQ_CORRECTION_RECORD = np.dtype([("index", np.uint64), ("first_interval", np.uint64), ("n_usable", np.uint64),
+                                 ("n_nonfinite", np.uint64), ("n_skipped", np.uint64), ("n_refused", np.uint64),
+                                 ("sum_re", np.int64), ("sum_im", np.int64), ("sum_rr", np.int64), ("sum_ii", np.int64),
+                                 ("sum_ri", np.int64), ("n_intervals", np.uint32), ("dc_re", np.float32),
+                                 ("dc_im", np.float32), ("w_re", np.float32), ("w_im", np.float32),
+                                 ("reserved", np.uint32)])
 
 
 class FmrError(RuntimeError):
@@ -281,6 +292,27 @@ class BlankerLevels(C.Structure):
                 ("runs_per_second", C.c_double), ("level_dbfs", C.c_double), ("peak_dbfs", C.c_double),
                 ("n_intervals", C.c_uint64), ("n_triggers", C.c_uint64), ("n_blanked", C.c_uint64),
                 ("n_nonfinite", C.c_uint64), ("n_runs", C.c_uint64)]
+
+
+class IqCorrectionConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("mode", C.c_int), ("correct", C.c_int), ("average_intervals", C.c_int),
+                ("record_intervals", C.c_int), ("max_records", C.c_int), ("reserved", C.c_int)]
+
+
+class IqCorrectionInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("rows", C.c_int), ("records_complete", C.c_uint64),
+                ("records_dropped", C.c_uint64), ("first_unread", C.c_uint64), ("records_ready", C.c_uint64),
+                ("intervals_complete", C.c_uint64), ("mode", C.c_int), ("correct", C.c_int),
+                ("average_intervals", C.c_int), ("record_intervals", C.c_int), ("max_records", C.c_int),
+                ("reserved", C.c_int)]
+
+
+class IqCorrectionLevels(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("refused", C.c_int), ("dc_re", C.c_double), ("dc_im", C.c_double),
+                ("dc_dbfs", C.c_double), ("w_re", C.c_double), ("w_im", C.c_double), ("image_rejection_db", C.c_double),
+                ("gain_imbalance_db", C.c_double), ("phase_error_deg", C.c_double), ("usable_share", C.c_double),
+                ("n_intervals", C.c_uint64), ("n_usable", C.c_uint64), ("n_nonfinite", C.c_uint64),
+                ("n_skipped", C.c_uint64), ("n_refused", C.c_uint64)]
 
 
 class LoudnessConfig(C.Structure):
@@ -504,6 +536,12 @@ def lib(ab=False):
     L.fmr_blanker_read.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(BlankerInfo), C.c_size_t]
     L.fmr_blanker_derive.restype = C.c_int
     L.fmr_blanker_derive.argtypes = [vp, C.c_int, C.c_double, C.POINTER(BlankerLevels), C.c_size_t]
+    L.fmr_enable_iq_correction.restype = C.c_int
+    L.fmr_enable_iq_correction.argtypes = [vp, C.POINTER(IqCorrectionConfig), C.c_size_t]
+    L.fmr_iq_correction_read.restype = C.c_int
+    L.fmr_iq_correction_read.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(IqCorrectionInfo), C.c_size_t]
+    L.fmr_iq_correction_derive.restype = C.c_int
+    L.fmr_iq_correction_derive.argtypes = [vp, C.c_int, C.POINTER(IqCorrectionLevels), C.c_size_t]
     _libs[ab] = L
     return L
 
@@ -613,6 +651,19 @@ def blanker_levels(records, rate):
     if rc != OK:
         raise FmrError(f"fmr_blanker_derive failed ({rc}): {L.fmr_last_error().decode()}")
     return {k: getattr(out, k) for k, _ in BlankerLevels._fields_ if k not in ("struct_size", "reserved")}
+
+
+def iq_correction_levels(records):
+    """fmr_iq_correction_derive (host only): the DC offset, the image coefficient w, the image rejection of the uncorrected
+    capture, gain imbalance and phase error, usable_share and the pooled counts of the records (an IQ_CORRECTION_RECORD
+    array as Chain.iq_correction_records returns them), as a dict of fmr_iq_correction_levels."""
+    L = lib()
+    records = np.ascontiguousarray(records, dtype=IQ_CORRECTION_RECORD)
+    out = IqCorrectionLevels()
+    rc = L.fmr_iq_correction_derive(records.ctypes.data, len(records), C.byref(out), C.sizeof(IqCorrectionLevels))
+    if rc != OK:
+        raise FmrError(f"fmr_iq_correction_derive failed ({rc}): {L.fmr_last_error().decode()}")
+    return {k: getattr(out, k) for k, _ in IqCorrectionLevels._fields_ if k != "struct_size"}
 
 
 def weak_signal_levels(records):
@@ -1049,6 +1100,21 @@ class Chain:
         cap; None: all that wait) as (records BLANKER_RECORD [n], info dict).  Reading drains them."""
         return self._read_records(self._L.fmr_blanker_read, BlankerInfo, ((BLANKER_RECORD, None),), row, cap)
 
+    def enable_iq_correction(self, act=False, correct=0, average_intervals=0, record_intervals=0, max_records=0):
+        """fmr_enable_iq_correction: DC-offset and IQ-imbalance correction of the input rows, in front of the blanker and
+        of every front end (chains with the IF resampler on complex-float input, banks and channelizers included; once,
+        before the first call).  act=False measures and records only; act=True corrects what the blanker and the front
+        end read.  correct: IQC_DC | IQC_BALANCE (0 = both).  0 = the defaults (a window of 64 intervals of 4096
+        samples, records of 256 intervals, 1024 kept)."""
+        cfg = IqCorrectionConfig(C.sizeof(IqCorrectionConfig), IQC_ACT if act else IQC_MEASURE, int(correct),
+                                 int(average_intervals), int(record_intervals), int(max_records), 0)
+        self._chk(self._L.fmr_enable_iq_correction(self.h, C.byref(cfg), C.sizeof(IqCorrectionConfig)))
+
+    def iq_correction_records(self, row=0, cap=None):
+        """fmr_iq_correction_read: the oldest unread complete records of input row `row` (0 for a bank or a channelizer;
+        at most cap; None: all that wait) as (records IQ_CORRECTION_RECORD [n], info dict).  Reading drains them."""
+        return self._read_records(self._L.fmr_iq_correction_read, IqCorrectionInfo, ((IQ_CORRECTION_RECORD, None),), row, cap)
+
     def enable_analyser(self, fft_size=0, interval_samples=0, max_records=0):
         """fmr_enable_analyser: the audio analyser of every stream / channel (any decoder chain, once, before the first
         call); 0 = the defaults (N = 4096, records of 6 N audio frames, 64 records kept)."""
@@ -1136,7 +1202,8 @@ class Chain:
         return buf[:2 * n].view(np.complex64).copy()
 
     def debug_read(self, which, stream=0, cap=1 << 24):
-        dt = {0: np.complex64, 1: np.float32, 2: np.float64, 3: np.float64, 4: np.float32, 5: np.uint64, 6: np.complex64}[which]
+        dt = {0: np.complex64, 1: np.float32, 2: np.float64, 3: np.float64, 4: np.float32, 5: np.uint64, 6: np.complex64,
+              7: np.complex64}[which]
         buf = np.empty(cap, dtype=dt)
         n = self._chk(self._L.fmr_debug_read(self.h, stream, which, buf.ctypes.data_as(C.c_void_p), buf.nbytes))
         return buf[:n].copy()

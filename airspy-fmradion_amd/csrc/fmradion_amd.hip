@@ -41,7 +41,9 @@
 #include "kernels_rfmon.hpp"
 #include "kernels_output.hpp"
 #include "kernels_weaksignal.hpp"
+#include <complex>
 #include "kernels_blanker.hpp"
+#include "kernels_iqcorr.hpp"
 #include "../host/fmradion_rds.hpp"
 
 namespace {
@@ -407,6 +409,35 @@ struct BlankerStage {
   int init(int rows_, size_t max_in, const fmr_blanker_config &m);
 };
 
+// DC-offset and IQ-imbalance correction on the capture (fmr_enable_iq_correction; kernels_iqcorr.hpp).
+// The second stage of the blanker's kind, and in front of it (fmr_chain::iqc_stage): moments, coefficients and, in
+// FMR_IQC_ACT, the apply kernel on the decoder stream, the records on the side stream behind an event.  The corrected rows
+// live in two buffers by call parity with the blanker's argument: a reader of call N's rows may still be pending when call
+// N + 1 is corrected, and is done before call N + 1's front end, which call N + 2's corrector follows on the same stream.
+// The parts of a call are kept twice as well, for the records kernel that reads them beside the next call.
+struct IqCorrectionStage {
+  bool on = false;
+  fmr_iq_correction_config cfg{};            // the defaults filled in
+  IqcCoef coef{};
+  int rows = 0, pmax = 0, tring = 0;         // input rows, pieces of a call at most, ring of running totals per row (2^k)
+  int tiles() const { return (pmax + kIqcCoefT - 1) / kIqcCoefT; }
+  size_t pitch = 0;                          // samples between the rows of a row buffer (one more under an odd caller's stride)
+  long long n = 0;                           // samples handed in per row
+  unsigned long long calls = 0;              // calls that brought samples
+  const float2 *last_rows = nullptr; long long last_stride = 0, last_n = 0;    // FMR_IQC_ACT: what the last call wrote
+  DevBuf<IqcPart> d_part;                    // [2][rows][pmax]
+  DevBuf<IqcSum> d_tot;                      // [rows][tiles][(kIqcBack + 1) kIqcCoefT + 1]: the running totals a k_iqc_coef workgroup forms
+  DevBuf<IqcSum> d_tring;                    // [rows][tring]
+  DevBuf<IqcState> d_state;
+  DevBuf<IqcRec> d_ring;
+  DevBuf<float2> d_rows[2];
+  Event ev_coef, ev_rec[2];
+  RecCursor cur;
+  unsigned long long intervals() const { return (unsigned long long)(n / kNbQ); }
+  unsigned long long done() const { return intervals() / (unsigned long long)cfg.record_intervals; }   // records complete
+  int init(int rows_, size_t max_in, const fmr_iq_correction_config &m);
+};
+
 }  // namespace
 
 // Diagnostic switches from the environment, read ONCE when a chain is created (INTEGRATION.md section 4 lists them);
@@ -577,6 +608,8 @@ struct fmr_chain : ChainShape {
   OutputStage out;
   WeakSignalStage ws;
   BlankerStage nb;
+  IqCorrectionStage iqc;
+  int iqc_stage(const float2 *&d_iq, size_t &stride, long long N_in);
   int nb_stage(const float2 *&d_iq, size_t &stride, long long N_in);
   int ws_measure(const fm_mpx_t *base, const WsArgs &a, hipStream_t st);
   int ws_act(double *d_aud, long long astride, const WsArgs &a, hipStream_t st);
@@ -1424,6 +1457,7 @@ int fmr_chain::run(const float2 *d_iq, size_t stride, const uint32_t *block_len,
   CallCtx k{};
   k.d_iq = d_iq; k.stride = stride; k.block_len = block_len; k.nb = nb; k.d_aud = d_aud; k.astride = astride;
   k.audio_len = audio_len; k.N_in = N_in;
+  if (iqc.on && N_in > 0) if (int rc = iqc_stage(k.d_iq, k.stride, N_in)) return rc;         // (FMR_IQC_ACT: the blanker and every reader below take the corrected rows)
   if (this->nb.on && N_in > 0) if (int rc = nb_stage(k.d_iq, k.stride, N_in)) return rc;     // (FMR_NB_ACT: every reader below takes the blanked rows)
   k.h_tab = h_tab_all.p + (size_t)slot * tab_ints;
   k.d_tab_slot = d_tab.p + (size_t)slot * tab_ints;
@@ -3078,6 +3112,79 @@ int fmr_chain::nb_stage(const float2 *&d_iq, size_t &stride, long long N_in) {
   return FMR_OK;
 }
 
+// ---- IQ correction (kernels_iqcorr.hpp) ----
+int IqCorrectionStage::init(int rows_, size_t max_in, const fmr_iq_correction_config &m) {
+  static_assert(sizeof(IqcRec) == sizeof(fmr_iq_correction_record), "IqcRec is fmr_iq_correction_record");
+  static_assert(offsetof(IqcRec, sum_re) == offsetof(fmr_iq_correction_record, sum_re) &&
+                offsetof(IqcRec, n_intervals) == offsetof(fmr_iq_correction_record, n_intervals) &&
+                offsetof(IqcRec, w_im) == offsetof(fmr_iq_correction_record, w_im), "the fields of a record");
+  cfg = m;
+  rows = rows_;
+  coef.W = m.average_intervals; coef.R = m.record_intervals; coef.L = m.max_records; coef.act = m.mode == FMR_IQC_ACT;
+  coef.dc = (m.correct & FMR_IQC_DC) != 0; coef.balance = (m.correct & FMR_IQC_BALANCE) != 0;
+  pmax = (int)(max_in / kNbQ + 2);       // a call touches its whole intervals and one more at either end
+  tring = 64;
+  while (tring < pmax + m.average_intervals + 2) tring <<= 1;
+  pitch = (max_in + 1) & ~(size_t)1;
+  int rc;
+  if ((rc = d_part.alloc((size_t)2 * rows * pmax))) return rc;
+  if ((rc = d_tot.alloc((size_t)rows * tiles() * ((kIqcBack + 1) * kIqcCoefT + 1)))) return rc;
+  if ((rc = d_tring.alloc((size_t)rows * tring))) return rc;
+  if ((rc = d_state.alloc((size_t)rows))) return rc;
+  if ((rc = d_ring.alloc((size_t)rows * (size_t)m.max_records))) return rc;
+  if (coef.act)      // (a row may start one sample in, to sit on the caller's 16-byte phase, and be one sample further apart)
+    for (DevBuf<float2> &b : d_rows) if ((rc = b.alloc((size_t)rows * (pitch + 1) + 2))) return rc;
+  if ((rc = ev_coef.create(hipEventDisableTiming))) return rc;
+  for (Event &e : ev_rec) if ((rc = e.create(hipEventDisableTiming))) return rc;
+  cur.reset(rows, m.max_records);
+  n = 0; calls = 0;
+  on = true;
+  return FMR_OK;
+}
+
+// One call's input rows (the samples [iqc.n, iqc.n + N_in) of every row at d_iq) through the corrector, in front of the
+// blanker and of everything else that reads them; in FMR_IQC_ACT d_iq and stride then name the corrected rows.
+int fmr_chain::iqc_stage(const float2 *&d_iq, size_t &stride, long long N_in) {
+  IqCorrectionStage &b = iqc;
+  const long long n0 = b.n, n1 = n0 + N_in;
+  const int pieces = (int)((n1 - 1) / kNbQ - n0 / kNbQ + 1);
+  if (pieces > b.pmax) { set_err("internal: a call of %lld input samples has more intervals than the IQ corrector holds", N_in); return FMR_ERR_CAPACITY; }
+  b.n = n1;
+  const int par = (int)(++b.calls & 1);
+  IqcPart *part = b.d_part.p + (size_t)par * b.rows * b.pmax;
+  if (b.calls > 2) HIPCHK(hipStreamWaitEvent(stream, b.ev_rec[par], 0));     // (the records kernel of two calls ago read these parts)
+  timed_on(stream, "iqc_moments", [&] {
+    hipLaunchKernelGGL(k_iqc_moments, dim3((unsigned)pieces, b.rows), dim3(kNbT), 0, stream, d_iq, (long long)stride, n0, n1, b.pmax, part);
+  });
+  timed_on(stream, "iqc_coef", [&] {
+    hipLaunchKernelGGL(k_iqc_coef, dim3((unsigned)((pieces + kIqcCoefT - 1) / kIqcCoefT), b.rows), dim3(kIqcCoefT), 0, stream, part, b.pmax, n0, n1, par, b.d_tot.p, b.d_tring.p,
+                       b.tring - 1, b.d_state.p, b.coef);
+  });
+  HIPCHK(hipEventRecord(b.ev_coef, stream));
+  float2 *out = nullptr;
+  long long ostride = 0;
+  if (b.coef.act) {      // the same 16-byte phase as the caller's rows, row by row: the front end picks the forms it would have
+    ostride = (long long)(b.pitch + (stride & 1));
+    out = b.d_rows[par].p + (((uintptr_t)d_iq >> 3) & 1);
+    timed_on(stream, "iqc_apply", [&] {
+      hipLaunchKernelGGL(k_iqc_apply, dim3((unsigned)pieces, b.rows), dim3(kNbT), 0, stream, d_iq, (long long)stride, out, ostride, n0, n1,
+                         b.pmax, (const IqcPart *)part);
+    });
+  }
+  HIPCHK(hipStreamWaitEvent(side, b.ev_coef, 0));
+  timed_on(side, "iqc_records", [&] {
+    hipLaunchKernelGGL(k_iqc_records, dim3(b.rows), dim3(64), 0, side, (const IqcPart *)part, b.pmax, n0, n1, b.d_state.p, b.d_ring.p,
+                       b.coef.R, b.coef.L);
+  });
+  HIPCHK(hipEventRecord(b.ev_rec[par], side));
+  HIPCHK(hipGetLastError());
+  if (b.coef.act) {
+    d_iq = out; stride = (size_t)ostride;
+    b.last_rows = out; b.last_stride = ostride; b.last_n = N_in;
+  }
+  return FMR_OK;
+}
+
 // ---- audio analyser (kernels_analyser.hpp) ----
 template <int LOGN>
 static void an_shape(AnalyserStage &a) {
@@ -4131,6 +4238,13 @@ long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t 
     if (n) HIPCHK(hipMemcpy(out, c->nb.last_rows + (long long)stream * c->nb.last_stride, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost));
     return n;
   }
+  if (which == 7) {       // the input row the corrector wrote in the most recent call (chains whose IQ corrector acts; `stream` is an input row)
+    if (!c->iqc.on || !c->iqc.coef.act || stream >= c->iqc.rows) { set_err("fmr_debug_read: tap 7 (corrected input rows) needs a chain with fmr_enable_iq_correction in FMR_IQC_ACT, and an input row"); return FMR_ERR_BAD_ARG; }
+    n = c->iqc.last_n;
+    if ((size_t)n * sizeof(float2) > cap_bytes) return FMR_ERR_CAPACITY;
+    if (n) HIPCHK(hipMemcpy(out, c->iqc.last_rows + (long long)stream * c->iqc.last_stride, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost));
+    return n;
+  }
   if (which == 5 && !c->d_fe_stamps.p) {      // the symbol reliabilities of the most recent call (chains with RDS)
     if (!c->rds.on) { set_err("fmr_debug_read: tap 5 (RDS symbol reliabilities) needs a chain made by fmr_create_rds"); return FMR_ERR_BAD_ARG; }
     c->rds.drain();
@@ -4840,6 +4954,122 @@ int fmr_blanker_derive(const fmr_blanker_record *recs, int n, double input_rate,
   full.runs_per_second = (double)full.n_runs * input_rate / samples;
   full.level_dbfs = db10(pq / ((double)full.n_intervals * 68719476736.0));
   full.peak_dbfs = db10((double)peak);
+  give_sized(out, out_size, full);
+  return FMR_OK;
+}
+
+// ---- IQ correction: C-ABI ----
+int fmr_enable_iq_correction(fmr_chain *c, const fmr_iq_correction_config *cfg, size_t cfg_size) {
+  const char *fn = "fmr_enable_iq_correction";
+  if (!cfg) { set_err("%s: cfg is null", fn); return FMR_ERR_BAD_ARG; }
+  fmr_iq_correction_config m;
+  if (int rc = take_sized(fn, "fmr_iq_correction_config", cfg, cfg_size, m)) return rc;
+  if (m.mode != FMR_IQC_MEASURE && m.mode != FMR_IQC_ACT) {
+    set_err("%s: mode %d is neither FMR_IQC_MEASURE (0) nor FMR_IQC_ACT (1)", fn, m.mode);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.correct == 0) m.correct = FMR_IQC_DC | FMR_IQC_BALANCE;
+  if (m.correct < 0 || m.correct > (FMR_IQC_DC | FMR_IQC_BALANCE)) {
+    set_err("%s: correct %d is not a mask of FMR_IQC_DC (1) and FMR_IQC_BALANCE (2) (0 = both)", fn, m.correct);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.average_intervals == 0) m.average_intervals = 64;
+  if (m.average_intervals < 1 || m.average_intervals > kIqcMaxW) {
+    set_err("%s: average_intervals %d is outside 1 .. %d (0 = 64)", fn, m.average_intervals, kIqcMaxW);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.record_intervals == 0) m.record_intervals = 256;
+  if (m.record_intervals < 1 || m.record_intervals > 4096) {
+    set_err("%s: record_intervals %d is outside 1 .. 4096 (0 = 256)", fn, m.record_intervals);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.max_records == 0) m.max_records = 1024;
+  if (m.max_records < 1 || m.max_records > 65536) {
+    set_err("%s: max_records %d is outside 1 .. 65536 (0 = 1024)", fn, m.max_records);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (!c) { set_err("%s: chain is null", fn); return FMR_ERR_BAD_ARG; }
+  if (c->in_fmt != 0) {
+    set_err("%s: the IQ corrector reads complex float samples (FMR_IQ_CF32); this chain takes a raw input format", fn);
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (!c->has_rs) {
+    set_err("%s: the IQ corrector sits in front of the IF resampler; this chain has none (enable_resampler = 0)", fn);
+    return FMR_ERR_UNSUPPORTED;
+  }
+  return enable_stage(fn, c, c->iqc, "IQ corrector", "input sample", c->in_rows(), c->max_in, m);
+}
+
+int fmr_iq_correction_read(fmr_chain *c, int row, fmr_iq_correction_record *recs, int cap, fmr_iq_correction_info *info,
+                           size_t info_size) {
+  if (!c || cap < 0) { set_err("fmr_iq_correction_read: bad chain or cap"); return FMR_ERR_BAD_ARG; }
+  if (!c->iqc.on) { set_err("fmr_iq_correction_read: the chain has no IQ corrector (fmr_enable_iq_correction)"); return FMR_ERR_BAD_ARG; }
+  if (row < 0 || row >= c->iqc.rows) { set_err("fmr_iq_correction_read: row %d is not one of the chain's %d input rows", row, c->iqc.rows); return FMR_ERR_BAD_ARG; }
+  if (cap > 0 && !recs) { set_err("fmr_iq_correction_read: recs is null"); return FMR_ERR_BAD_ARG; }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    const unsigned long long done = c->iqc.done();
+    const int n = c->iqc.cur.take(row, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
+      HIPCHK(hipMemcpy(recs + k, c->iqc.d_ring.p + (size_t)row * c->iqc.cur.L + slot, m * sizeof(fmr_iq_correction_record), hipMemcpyDeviceToHost));
+      return FMR_OK;
+    });
+    if (n < 0) return n;
+    if (info) {
+      fmr_iq_correction_info full{};
+      full.struct_size = (unsigned)sizeof full;
+      full.rows = c->iqc.rows;
+      ring_info(full, c->iqc.cur, row, done);
+      full.intervals_complete = c->iqc.intervals();
+      const fmr_iq_correction_config &m = c->iqc.cfg;
+      full.mode = m.mode; full.correct = m.correct; full.average_intervals = m.average_intervals;
+      full.record_intervals = m.record_intervals; full.max_records = m.max_records;
+      give_sized(info, info_size, full);
+    }
+    return n;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_iq_correction_derive(const fmr_iq_correction_record *recs, int n, fmr_iq_correction_levels *out, size_t out_size) {
+  if (!recs || !out || n < 1) { set_err("fmr_iq_correction_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
+  for (int i = 0; i < n; i++)
+    if (recs[i].n_intervals == 0) {
+      set_err("fmr_iq_correction_derive: record %d has n_intervals 0 (not a record of fmr_iq_correction_read)", i);
+      return FMR_ERR_BAD_ARG;
+    }
+  fmr_iq_correction_levels full{};
+  full.struct_size = (unsigned)sizeof full;
+  int64_t S_r = 0, S_i = 0, S_rr = 0, S_ii = 0, S_ri = 0;
+  for (int i = 0; i < n; i++) {
+    const fmr_iq_correction_record &r = recs[i];
+    full.n_intervals += r.n_intervals; full.n_usable += r.n_usable; full.n_nonfinite += r.n_nonfinite;
+    full.n_skipped += r.n_skipped; full.n_refused += r.n_refused;
+    S_r += r.sum_re; S_i += r.sum_im; S_rr += r.sum_rr; S_ii += r.sum_ii; S_ri += r.sum_ri;
+  }
+  full.usable_share = (double)full.n_usable / ((double)full.n_intervals * (double)kNbQ);
+  double w_r = 0.0, w_i = 0.0;
+  if (full.n_usable >= (uint64_t)(kNbQ / 2)) {       // the header's formulas, operation by operation
+    const double r = 1.0 / ((double)full.n_usable * 68719476736.0);
+    const double m_r = (double)S_r * r, m_i = (double)S_i * r;
+    const double E_rr = (double)S_rr * r, E_ii = (double)S_ii * r, E_ri = (double)S_ri * r;
+    const double P = (E_rr + E_ii) - (m_r * m_r + m_i * m_i);
+    const double C_r = (E_rr - E_ii) - (m_r * m_r - m_i * m_i);
+    const double C_i = 2.0 * E_ri - 2.0 * (m_r * m_i);
+    const double D = P * P - (C_r * C_r + C_i * C_i);
+    if (P > 9.094947017729282e-13 && D > 0.0) {
+      const double t = P + std::sqrt(D);
+      w_r = C_r / t; w_i = C_i / t;
+      if (w_r * w_r + w_i * w_i > 0.0625) { w_r = 0.0; w_i = 0.0; full.refused = 1; }
+    }
+    full.dc_re = m_r; full.dc_im = m_i;
+  }
+  full.w_re = w_r; full.w_im = w_i;
+  const double ad = std::hypot(full.dc_re, full.dc_im), aw = std::hypot(w_r, w_i);
+  full.dc_dbfs = ad > 0.0 ? 20.0 * std::log10(ad) : -INFINITY;
+  full.image_rejection_db = aw > 0.0 ? -20.0 * std::log10(aw) : INFINITY;
+  const std::complex<double> rho = (1.0 - std::complex<double>(w_r, w_i)) / (1.0 + std::complex<double>(w_r, w_i));
+  full.gain_imbalance_db = 20.0 * std::log10(std::abs(rho));
+  full.phase_error_deg = -std::arg(rho) * (180.0 / 3.14159265358979323846);
   give_sized(out, out_size, full);
   return FMR_OK;
 }

@@ -192,6 +192,29 @@ inline BlankerReport blanker_report(fmr_chain *c, int row, double input_rate) {
   return out;
 }
 
+// DC-offset and IQ-imbalance correction on the capture (fmr_enable_iq_correction / fmr_iq_correction_read /
+// fmr_iq_correction_derive): the drained records of one input row in ascending order and the levels pooled from them
+struct IqCorrectionReport {
+  std::vector<fmr_iq_correction_record> records;
+  fmr_iq_correction_info info{};
+  fmr_iq_correction_levels levels{};   // (of `records`; all zero when there are none)
+};
+inline void iq_correction(fmr_chain *c, const fmr_iq_correction_config &m) {
+  check(fmr_enable_iq_correction(c, &m, sizeof m), "fmr_enable_iq_correction");
+}
+inline IqCorrectionReport iq_correction_report(fmr_chain *c, int row) {
+  IqCorrectionReport out;
+  const int ready = fmr_iq_correction_read(c, row, nullptr, 0, &out.info, sizeof out.info);
+  if (ready < 0) check(ready, "fmr_iq_correction_read");
+  if (ready == 0) return out;
+  out.records.resize((size_t)ready);
+  const int n = fmr_iq_correction_read(c, row, out.records.data(), ready, &out.info, sizeof out.info);
+  if (n < 0) check(n, "fmr_iq_correction_read");
+  out.records.resize((size_t)n);
+  if (n > 0) check(fmr_iq_correction_derive(out.records.data(), n, &out.levels, sizeof out.levels), "fmr_iq_correction_derive");
+  return out;
+}
+
 // audio analyser (fmr_enable_analyser / fmr_analyser_read / fmr_analyser_derive): the drained records in ascending order
 // with their spectra [n][3][bins] (scaled to power), and the levels of all of them pooled under `rule`
 struct AnalyserReport {
@@ -315,6 +338,7 @@ using ModulationRecord = fmr_detail::ModulationRecord;
 using LoudnessReport = fmr_detail::LoudnessReport;
 using WeakSignalReport = fmr_detail::WeakSignalReport;
 using BlankerReport = fmr_detail::BlankerReport;
+using IqCorrectionReport = fmr_detail::IqCorrectionReport;
 using AnalyserReport = fmr_detail::AnalyserReport;
 
 // FilterParameters (include/FilterParameters.h:31-49): tables served by the library.
@@ -415,6 +439,16 @@ public:
     fmr_detail::blanker(m_chain, cfg);
   }
   BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_rate); }
+  // DC-offset and IQ-imbalance correction of the same input (fmr_enable_iq_correction), under the same rules as
+  // enable_blanker() and before or after it: cfg holds the fields to set (zeros = the defaults; FMR_IQC_MEASURE records
+  // only, FMR_IQC_ACT corrects what the blanker and the front end read).  read_iq_correction() drains the complete
+  // records and pools them.
+  void enable_iq_correction(fmr_iq_correction_config cfg = fmr_iq_correction_config{}) {
+    if (!m_chain) fmr_detail::fail("IfResampler::enable_iq_correction: equal rates, nothing is resampled");
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::iq_correction(m_chain, cfg);
+  }
+  IqCorrectionReport read_iq_correction() { return fmr_detail::iq_correction_report(m_chain, 0); }
 
 private:
   fmr_chain *m_chain = nullptr;
@@ -464,6 +498,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
+    if (m_iqc) fmr_detail::iq_correction(m_chain, m_iqc_cfg);
     if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
@@ -480,6 +515,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
+    if (m_iqc) fmr_detail::iq_correction(m_chain, m_iqc_cfg);
     if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
@@ -543,6 +579,18 @@ public:
     m_nb = true;
   }
   BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_cfg.input_rate); }
+  // DC-offset and IQ-imbalance correction of the same input (fmr_enable_iq_correction), under the same rules as
+  // enable_blanker() and before or after it: cfg holds the fields to set (zeros = the defaults; FMR_IQC_MEASURE records
+  // only, FMR_IQC_ACT corrects what the blanker and the front end read).  read_iq_correction() drains the complete
+  // records and pools them.
+  void enable_iq_correction(fmr_iq_correction_config cfg = fmr_iq_correction_config{}) {
+    if (m_started) fmr_detail::fail("FmDecoder::enable_iq_correction: after the first process()");
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::iq_correction(m_chain, cfg);
+    m_iqc_cfg = cfg;
+    m_iqc = true;
+  }
+  IqCorrectionReport read_iq_correction() { return fmr_detail::iq_correction_report(m_chain, 0); }
 
   // RF monitor (no counterpart in the reference; fmr_enable_rf_monitor): records of interval_samples IF samples (0 =
   // 38400, 100 ms) with level, C/N, envelope AM and fade percentiles; before the first process(), once.
@@ -606,6 +654,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
+    if (m_iqc) fmr_detail::iq_correction(m_chain, m_iqc_cfg);
     if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
@@ -710,6 +759,8 @@ private:
   fmr_weak_signal_config m_ws_cfg{};
   bool m_nb = false;
   fmr_blanker_config m_nb_cfg{};
+  bool m_iqc = false;
+  fmr_iq_correction_config m_iqc_cfg{};
   bool m_rf = false;
   fmr_rf_monitor_config m_rf_cfg{};
   bool m_an = false;
@@ -753,6 +804,7 @@ public:
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg);
+    if (m_iqc) fmr_detail::iq_correction(m_chain, m_iqc_cfg);
     if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
@@ -766,6 +818,17 @@ public:
     m_nb = true;
   }
   BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_cfg.input_rate); }
+  // DC-offset and IQ-imbalance correction of the same input (fmr_enable_iq_correction), under the same rules as
+  // enable_blanker() and before or after it: cfg holds the fields to set (zeros = the defaults; FMR_IQC_MEASURE records
+  // only, FMR_IQC_ACT corrects what the blanker and the front end read).  read_iq_correction() drains the complete
+  // records and pools them.
+  void enable_iq_correction(fmr_iq_correction_config cfg = fmr_iq_correction_config{}) {
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::iq_correction(m_chain, cfg);
+    m_iqc_cfg = cfg;
+    m_iqc = true;
+  }
+  IqCorrectionReport read_iq_correction() { return fmr_detail::iq_correction_report(m_chain, 0); }
   // Output stage (fmr_enable_output): squelch, gain, PCM frames and the per-block IF / AF meters on the device; before
   // the first process(), once.  rate: the PCM ring at that rate (fmr_set_output_rate).  read_output() drains everything
   // that waits.
@@ -812,6 +875,8 @@ private:
   fmr_config m_cfg{};
   bool m_nb = false;
   fmr_blanker_config m_nb_cfg{};
+  bool m_iqc = false;
+  fmr_iq_correction_config m_iqc_cfg{};
   bool m_an = false;
   fmr_analyser_config m_an_cfg{};
   bool m_out = false;
@@ -842,6 +907,7 @@ public:
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg);
+    if (m_iqc) fmr_detail::iq_correction(m_chain, m_iqc_cfg);
     if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
     if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
@@ -855,6 +921,17 @@ public:
     m_nb = true;
   }
   BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_cfg.input_rate); }
+  // DC-offset and IQ-imbalance correction of the same input (fmr_enable_iq_correction), under the same rules as
+  // enable_blanker() and before or after it: cfg holds the fields to set (zeros = the defaults; FMR_IQC_MEASURE records
+  // only, FMR_IQC_ACT corrects what the blanker and the front end read).  read_iq_correction() drains the complete
+  // records and pools them.
+  void enable_iq_correction(fmr_iq_correction_config cfg = fmr_iq_correction_config{}) {
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::iq_correction(m_chain, cfg);
+    m_iqc_cfg = cfg;
+    m_iqc = true;
+  }
+  IqCorrectionReport read_iq_correction() { return fmr_detail::iq_correction_report(m_chain, 0); }
   // Output stage (fmr_enable_output): squelch, gain, PCM frames and the per-block IF / AF meters on the device; before
   // the first process(), once.  rate: the PCM ring at that rate (fmr_set_output_rate).  read_output() drains everything
   // that waits.
@@ -901,6 +978,8 @@ private:
   fmr_config m_cfg{};
   bool m_nb = false;
   fmr_blanker_config m_nb_cfg{};
+  bool m_iqc = false;
+  fmr_iq_correction_config m_iqc_cfg{};
   bool m_an = false;
   fmr_analyser_config m_an_cfg{};
   bool m_out = false;
@@ -952,6 +1031,7 @@ public:
     if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
     if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
     if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
+    if (m_iqc) fmr_detail::iq_correction(m_chain, m_iqc_cfg);
     if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
     if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
     if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
@@ -1014,6 +1094,17 @@ public:
     m_nb = true;
   }
   BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_cfg.input_rate); }
+  // DC-offset and IQ-imbalance correction of the same input (fmr_enable_iq_correction), under the same rules as
+  // enable_blanker() and before or after it: cfg holds the fields to set (zeros = the defaults; FMR_IQC_MEASURE records
+  // only, FMR_IQC_ACT corrects what the blanker and the front end read).  read_iq_correction() drains the complete
+  // records and pools them.
+  void enable_iq_correction(fmr_iq_correction_config cfg = fmr_iq_correction_config{}) {
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::iq_correction(m_chain, cfg);
+    m_iqc_cfg = cfg;
+    m_iqc = true;
+  }
+  IqCorrectionReport read_iq_correction() { return fmr_detail::iq_correction_report(m_chain, 0); }
 
   // Audio analyser of every channel (fmr_enable_analyser), before the first process(), once.  read_analyser(ch) drains
   // channel ch's complete records and derives their pooled levels.
@@ -1115,6 +1206,8 @@ private:
   fmr_weak_signal_config m_ws_cfg{};
   bool m_nb = false;
   fmr_blanker_config m_nb_cfg{};
+  bool m_iqc = false;
+  fmr_iq_correction_config m_iqc_cfg{};
   bool m_rf = false;
   fmr_rf_monitor_config m_rf_cfg{};
   bool m_an = false;
@@ -1156,6 +1249,15 @@ public:
     fmr_detail::blanker(m_chain, cfg);
   }
   BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_rate); }
+  // DC-offset and IQ-imbalance correction of the same input (fmr_enable_iq_correction), under the same rules as
+  // enable_blanker() and before or after it: cfg holds the fields to set (zeros = the defaults; FMR_IQC_MEASURE records
+  // only, FMR_IQC_ACT corrects what the blanker and the front end read).  read_iq_correction() drains the complete
+  // records and pools them.
+  void enable_iq_correction(fmr_iq_correction_config cfg = fmr_iq_correction_config{}) {
+    cfg.struct_size = sizeof cfg;
+    fmr_detail::iq_correction(m_chain, cfg);
+  }
+  IqCorrectionReport read_iq_correction() { return fmr_detail::iq_correction_report(m_chain, 0); }
 
   // out[k] = what channel k produced from this capture block; blocks longer than the chain's block capacity are
   // resampled in consecutive pieces

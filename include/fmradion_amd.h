@@ -313,7 +313,9 @@ int fmr_get_multipath_coefficients(fmr_chain *c, int stream, float *coeff, int c
  * 10 MS/s without IF filter / equaliser) taps 0, 1 and 4 exist only in a chain created with FMR_DEBUG_TAPS=1 in the
  * environment -- the product keeps those signals on chip.  6 = on a chain whose blanker acts (fmr_enable_blanker,
  * FMR_NB_ACT), the input row `stream` as the front end read it in the most recent call (complex float; `stream` is an
- * input row: 0 for a bank; returns the samples of that call); FMR_ERR_BAD_ARG on every other chain. */
+ * input row: 0 for a bank; returns the samples of that call); FMR_ERR_BAD_ARG on every other chain.  7 = on a chain
+ * whose IQ corrector acts (fmr_enable_iq_correction, FMR_IQC_ACT), the input row `stream` as the corrector wrote it in the
+ * most recent call, ahead of the blanker (complex float, as tap 6); FMR_ERR_BAD_ARG on every other chain. */
 long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t cap_bytes);
 
 /* What this library holds of the HIP runtime right now, in the whole process: device buffers, page-locked host blocks,
@@ -906,6 +908,104 @@ int fmr_blanker_read(fmr_chain *c, int row, fmr_blanker_record *recs, int cap, f
 /* Host only, in double, no device: pools n records (n >= 1, each with n_intervals > 0) into the levels above.  input_rate
  * (samples per second, > 0) is only used for runs_per_second. */
 int fmr_blanker_derive(const fmr_blanker_record *recs, int n, double input_rate, fmr_blanker_levels *out, size_t out_size);
+
+/* --- DC-offset and IQ-imbalance correction on the capture: a direct-conversion SDR adds a carrier
+ * at 0 Hz and mirrors every station at +f onto -f, 25 to 40 dB down.  A single-station chain does not mind; a bank, a
+ * channelizer, the band spectrum and the station finder see the carrier as a station and a strong station's image on
+ * another raster point.  The stage estimates both errors from the capture itself and removes them in the input rows of a
+ * call, ahead of the blanker and of every front-end form.  It is off by default and absent when off.  In FMR_IQC_MEASURE
+ * it only reads: every output of the chain is what it is without the stage.  In FMR_IQC_ACT every reader of the call's
+ * input (the blanker first, when there is one) reads the corrected rows, which the stage keeps in buffers of its own: the
+ * caller's buffer is never written.
+ * Everything below applies per input row.  Sample index n counts from the chain's first sample, across blocks and calls
+ * of any length.
+ * Interval: interval j covers [j Q, (j + 1) Q), Q = 4096 (the blanker's).
+ * Usable sample: p = fl32(fl32(re re) + fl32(im im)), unfused.  A sample is non-finite if either component is NaN or Inf.
+ * It is usable if it is finite and p <= 4: anything more than 6 dB over full scale is an impulse or a mis-scaled capture,
+ * contributes to no sum and is counted (n_skipped).
+ * Moments (exact integers: any cut into calls and any summation order gives the same bits): for a usable sample
+ * a_r = floor(re 2^36), a_i = floor(im 2^36), a_rr = floor(fl32(re re) 2^36), a_ii = floor(fl32(im im) 2^36),
+ * a_ri = floor(fl32(re im) 2^36), signed 64-bit, floor towards -INFINITY, the float widened to double first.  Per
+ * interval: N_j (usable samples), S_r, S_i, S_rr, S_ii, S_ri.  With W <= 1024 a window sum stays below 2^60.
+ * Window: W = average_intervals.  For interval j, c = min(j, W); the window is the intervals j - c .. j - 1: strictly
+ * past, so a call boundary decides nothing.  Window sums are differences of running 64-bit totals (wrap-around is
+ * harmless).
+ * Coefficients of interval j, in fp64, each operation rounded once, in this order.  If c = 0 or the window's N < Q / 2:
+ * d = 0, w = 0.  Otherwise r = 1 / ((double)N 2^36); m_r = (double)S_r r, m_i likewise; E_rr = (double)S_rr r, E_ii and
+ * E_ri likewise; P = (E_rr + E_ii) - (m_r m_r + m_i m_i); C_r = (E_rr - E_ii) - (m_r m_r - m_i m_i);
+ * C_i = 2 E_ri - 2 (m_r m_i); D = P P - (C_r C_r + C_i C_i).  If !(P > 2^-40) or !(D > 0): w = 0.  Else t = P + sqrt(D),
+ * w_r = C_r / t, w_i = C_i / t: the exact root of E[y^2] = 0 for y = z - w conj(z), to first order C / 2P.  If
+ * w_r w_r + w_i w_i > 1/16: w = 0 and the interval counts as refused -- an image less than 12 dB down is not receiver
+ * mismatch but an improper signal (a real-valued capture, an AM carrier at 0 Hz).  d = (m_r, m_i).  `correct` selects
+ * what is applied (FMR_IQC_DC | FMR_IQC_BALANCE; 0 = both); the part not selected is set to 0.  The applied coefficients
+ * are then rounded to fp32: dr, di, wr, wi.
+ * Output: a non-finite sample passes bit for bit (the blanker behind the stage still sees it).  A sample of an interval
+ * whose four applied coefficients are all zero passes bit for bit.  Otherwise, in fp32, every product and sum rounded,
+ * nothing fused: zr = re - dr, zi = im - di, yr = zr - fl32(fl32(wr zr) + fl32(wi zi)),
+ * yi = zi - fl32(fl32(wi zr) - fl32(wr zi)).  Denormals follow IEEE.
+ * Records: record i covers the intervals [i R, (i + 1) R), R = record_intervals, and is complete in the call that delivers
+ * its last sample.  The sums are over the record's usable samples; n_refused counts intervals; dc_re .. w_im are the
+ * applied coefficients of the record's last interval.  Every field is bit-identical for any cut of the input into
+ * blocks and calls.  Ring, drop counting and info as for the blanker.
+ * A station at offset 0 has its carrier notched (about input_rate / (W Q) wide): hence `correct`, and off by default.  A
+ * capture not scaled to full scale 1.0 is skipped whole and passes unchanged. */
+enum { FMR_IQC_MEASURE = 0, FMR_IQC_ACT = 1 };
+enum { FMR_IQC_DC = 1, FMR_IQC_BALANCE = 2 };
+typedef struct {
+  unsigned struct_size;       /* sizeof(fmr_iq_correction_config) as the caller knows it (0: cfg_size); a larger size is refused */
+  int mode;                   /* FMR_IQC_MEASURE (default) | FMR_IQC_ACT */
+  int correct;                /* FMR_IQC_DC | FMR_IQC_BALANCE; 0 = both */
+  int average_intervals;      /* W: 1 .. 1024; 0 = 64 (105 ms at 2.5 MS/s) */
+  int record_intervals;       /* R: 1 .. 4096; 0 = 256 */
+  int max_records;            /* L: 1 .. 65536; 0 = 1024 */
+  int reserved;
+} fmr_iq_correction_config;
+typedef struct {
+  uint64_t index, first_interval;          /* i and i R */
+  uint64_t n_usable, n_nonfinite, n_skipped, n_refused;
+  int64_t sum_re, sum_im, sum_rr, sum_ii, sum_ri;
+  uint32_t n_intervals;                    /* R */
+  float dc_re, dc_im, w_re, w_im;
+  uint32_t reserved;
+} fmr_iq_correction_record;
+typedef struct {
+  unsigned struct_size;
+  int rows;                       /* input rows of the chain: 1 for a bank or a channelizer */
+  uint64_t records_complete;      /* since create (of every row: they run in step) */
+  uint64_t records_dropped;       /* of this row: overwritten unread */
+  uint64_t first_unread;          /* index of the oldest unread record after this call */
+  uint64_t records_ready;         /* complete records still unread after this call */
+  uint64_t intervals_complete;    /* intervals complete since create */
+  int mode, correct, average_intervals, record_intervals, max_records;   /* as enabled (defaults filled in) */
+  int reserved;
+} fmr_iq_correction_info;
+typedef struct {
+  unsigned struct_size;
+  int refused;                    /* 1: the pooled sums give an image less than 12 dB down, w is reported as 0 */
+  double dc_re, dc_im;            /* d from the pooled sums (0 when fewer than Q / 2 usable samples) */
+  double dc_dbfs;                 /* 20 log10 |d|; -INFINITY for 0 */
+  double w_re, w_im;
+  double image_rejection_db;      /* -20 log10 |w|: of the uncorrected capture; +INFINITY for 0 */
+  double gain_imbalance_db;       /* 20 log10 |rho|, rho = (1 - w) / (1 + w): inverts "I exact, Q' = g (Q cos phi + I sin phi)" */
+  double phase_error_deg;         /* -arg rho */
+  double usable_share;            /* sum n_usable / (sum n_intervals Q) */
+  uint64_t n_intervals, n_usable, n_nonfinite, n_skipped, n_refused;   /* pooled */
+} fmr_iq_correction_levels;
+/* Checks the fields first (FMR_ERR_BAD_ARG, fmr_last_error names the field; also a size larger than this library's
+ * struct), then the chain: NULL is FMR_ERR_BAD_ARG.  Accepted is every chain that runs the IF resampler on FMR_IQ_CF32
+ * input, of any mode and shape (as fmr_enable_blanker).  Raw input formats and chains without the resampler are
+ * FMR_ERR_UNSUPPORTED.  Allowed once, before the chain's first sample, before or after fmr_enable_blanker: a second
+ * call, or one after any processing call, is FMR_ERR_BAD_ARG.  A failed call leaves the chain and
+ * fmr_debug_live_resources as they were. */
+int fmr_enable_iq_correction(fmr_chain *c, const fmr_iq_correction_config *cfg, size_t cfg_size);
+/* Synchronises like the other getters, then drains up to cap complete records of input row `row` (0 for a bank), oldest
+ * first, and returns how many.  cap = 0 returns the number waiting and drains nothing.  info (may be NULL) takes info_size
+ * bytes (0 = this header's size).  FMR_ERR_BAD_ARG on a chain without the stage. */
+int fmr_iq_correction_read(fmr_chain *c, int row, fmr_iq_correction_record *recs, int cap, fmr_iq_correction_info *info,
+                           size_t info_size);
+/* Host only, in double, no device: pools n records (n >= 1, each with n_intervals > 0) and recomputes d and w from the
+ * pooled sums with the formulas above (both parts, whatever `correct` was). */
+int fmr_iq_correction_derive(const fmr_iq_correction_record *recs, int n, fmr_iq_correction_levels *out, size_t out_size);
 
 /* --- Audio analyser: the spectrum analyser the reference's author judges receivers with, on the
  * device.  A decoder chain of any mode with it enabled measures the finished audio of every stream / bank channel where
