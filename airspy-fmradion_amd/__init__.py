@@ -57,6 +57,7 @@ EXPORTS = [
     "fmr_enable_rf_monitor", "fmr_rf_monitor_read", "fmr_rf_monitor_derive",
     "fmr_enable_output", "fmr_output_read", "fmr_squelch_level_from_db",
     "fmr_set_output_rate", "fmr_get_output_rate", "fmr_output_rate_taps",
+    "fmr_enable_mpx_output", "fmr_mpx_output_read", "fmr_mpx_output_taps",
     "fmr_enable_weak_signal", "fmr_weak_signal_read", "fmr_weak_signal_derive",
     "fmr_enable_blanker", "fmr_blanker_read", "fmr_blanker_derive",
     "fmr_enable_iq_correction", "fmr_iq_correction_read", "fmr_iq_correction_derive",
@@ -142,6 +143,18 @@ def output_rate_taps(rate):
         raise FmrError(f"fmradion_amd error {n}: {Lb.fmr_last_error().decode()}")
     h = np.zeros(n, dtype=np.float64)
     Lb.fmr_output_rate_taps(int(rate), h.ctypes.data_as(C.POINTER(C.c_double)), n, None, None, None)
+    return h, l.value, m.value, t.value
+
+
+def mpx_output_taps(rate):
+    """fmr_mpx_output_taps: (h float64 [T L], L, M, T) -- the prototype filter of the MPX output at `rate` (host only)."""
+    Lb = lib()
+    l, m, t = C.c_int(), C.c_int(), C.c_int()
+    n = Lb.fmr_mpx_output_taps(int(rate), None, 0, C.byref(l), C.byref(m), C.byref(t))
+    if n < 0:
+        raise FmrError(f"fmradion_amd error {n}: {Lb.fmr_last_error().decode()}")
+    h = np.zeros(n, dtype=np.float64)
+    Lb.fmr_mpx_output_taps(int(rate), h.ctypes.data_as(C.POINTER(C.c_double)), n, None, None, None)
     return h, l.value, m.value, t.value
 
 
@@ -387,6 +400,18 @@ class OutputRateInfo(C.Structure):
                 ("pcm_clipped", C.c_uint64), ("pcm_nonfinite", C.c_uint64)]
 
 
+class MpxOutputConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("format", C.c_int), ("rate", C.c_int), ("gain", C.c_double),
+                ("max_frames", C.c_uint32)]
+
+
+class MpxOutputInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("format", C.c_int), ("rate", C.c_int), ("L", C.c_int), ("M", C.c_int),
+                ("taps_per_phase", C.c_int), ("delay_frames", C.c_double), ("full_scale_hz", C.c_double),
+                ("first_frame", C.c_uint64), ("frames_waiting", C.c_uint64), ("frames_dropped", C.c_uint64),
+                ("samples_in", C.c_uint64), ("pcm_clipped", C.c_uint64), ("pcm_nonfinite", C.c_uint64)]
+
+
 def build_library(force=False, verbose=False):
     """Compile the HIP library (and its A/B partner build) in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     import glob
@@ -524,6 +549,12 @@ def lib(ab=False):
                                   C.c_size_t]
     L.fmr_squelch_level_from_db.restype = C.c_double
     L.fmr_squelch_level_from_db.argtypes = [C.c_double]
+    L.fmr_enable_mpx_output.restype = C.c_int
+    L.fmr_enable_mpx_output.argtypes = [vp, C.POINTER(MpxOutputConfig), C.c_size_t]
+    L.fmr_mpx_output_read.restype = C.c_int
+    L.fmr_mpx_output_read.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(MpxOutputInfo), C.c_size_t]
+    L.fmr_mpx_output_taps.restype = C.c_int
+    L.fmr_mpx_output_taps.argtypes = [C.c_int, dp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.fmr_enable_weak_signal.restype = C.c_int
     L.fmr_enable_weak_signal.argtypes = [vp, C.POINTER(WeakSignalConfig), C.c_size_t]
     L.fmr_weak_signal_read.restype = C.c_int
@@ -1190,6 +1221,26 @@ class Chain:
         m = self._chk(self._L.fmr_output_read(self.h, int(stream), pcm.ctypes.data if nf else None, nf,
                                               blocks.ctypes.data if nb else None, nb, C.byref(got), *tail))
         return pcm[:got.value], blocks[:m], {k: getattr(info, k) for k, _ in OutputInfo._fields_}
+
+    def enable_mpx_output(self, format="s16", rate=192000, gain=0.0, max_frames=0):
+        """fmr_enable_mpx_output: the composite baseband of every stream / channel of an FM chain as mono PCM at `rate`
+        (once, before the first call).  format "s16" | "f32" (or PCM_S16 / PCM_F32); rate 0 = 384000, the MPX as it is;
+        0 = the defaults (gain 0.5: full scale +-150 kHz; 2^20 frames kept)."""
+        fmt = {"s16": PCM_S16, "f32": PCM_F32}.get(format, format)
+        cfg = MpxOutputConfig(C.sizeof(MpxOutputConfig), int(fmt), int(rate), float(gain), int(max_frames))
+        self._chk(self._L.fmr_enable_mpx_output(self.h, C.byref(cfg), C.sizeof(MpxOutputConfig)))
+
+    def mpx_output_read(self, stream=0, cap_frames=None):
+        """fmr_mpx_output_read: the oldest unread frames of `stream` (at most cap_frames; None: all that wait) as
+        (pcm [n] int16 | float32, info dict).  Reading drains them."""
+        info = MpxOutputInfo()
+        tail = (C.byref(info), C.sizeof(MpxOutputInfo))
+        self._chk(self._L.fmr_mpx_output_read(self.h, int(stream), None, 0, None, *tail))
+        nf = int(info.frames_waiting if cap_frames is None else cap_frames)
+        pcm = np.zeros(nf, dtype=_PCM_DTYPE[int(info.format)])
+        got = C.c_size_t(0)
+        self._chk(self._L.fmr_mpx_output_read(self.h, int(stream), pcm.ctypes.data if nf else None, nf, C.byref(got), *tail))
+        return pcm[:got.value], {k: getattr(info, k) for k, _ in MpxOutputInfo._fields_ if k != "struct_size"}
 
     def pps_events(self, stream=0):
         ev = (PpsEvent * 64)()

@@ -303,25 +303,27 @@ struct ResamplerCounter {
   }
 };
 
-// Prototype filter of the output stage's rate converter (fmr_set_output_rate): 48000 -> rate
-// by L / M in lowest terms, a Kaiser-windowed sinc at rate 48000 L.  Design attenuation 110 dB, cutoff 0.95 rate / 2,
-// transition 0.05 rate; the Kaiser length estimate N is rounded up to T L taps (T per phase) and the window spans all of
-// them.  Tap i < T L / 2 is computed and scaled, tap T L - 1 - i is a copy of it: the two are the same bits.  Scaled to
-// sum h = L (each of the L phases has unit DC gain to 1e-6).  rate 48000: L = M = T = 1, h = {1}.  False for a rate
-// outside 8000 .. 48000 or with L > 160.
+// Prototype filter of a rate converter behind the decoder: base -> rate by L / M in lowest terms, a Kaiser-windowed sinc
+// at rate base L.  Design attenuation 110 dB, cutoff 0.95 rate / 2, transition 0.05 rate; the Kaiser length estimate N is
+// rounded up to T L taps (T per phase) and the window spans all of them.  Tap i < T L / 2 is computed and scaled, tap
+// T L - 1 - i is a copy of it: the two are the same bits.  Scaled to sum h = L (each of the L phases has unit DC gain to
+// 1e-6).  rate = base: L = M = T = 1, h = {1}.  False for a rate outside rate_min .. base or with L > kOutRateMaxL.
+// Two users: the output stage (fmr_set_output_rate, DESIGN.md section 14.1: base 48000, from 8000 on) and the MPX output
+// (fmr_enable_mpx_output, DESIGN.md section 19: base 384000, from 96000 on).
 constexpr int kOutRateIn = 48000, kOutRateMin = 8000, kOutRateMaxL = 160;
-inline bool design_output_rate(int rate, int &L, int &M, int &T, std::vector<double> *taps) {
-  if (rate < kOutRateMin || rate > kOutRateIn) return false;
-  const long long g = gcd_ll(rate, kOutRateIn);
+constexpr int kMpxRateIn = 384000, kMpxRateMin = 96000;
+inline bool design_rate_filter(int base, int rate_min, int rate, int &L, int &M, int &T, std::vector<double> *taps) {
+  if (rate < rate_min || rate > base) return false;
+  const long long g = gcd_ll(rate, base);
   if (rate / g > kOutRateMaxL) return false;
-  L = (int)(rate / g); M = (int)(kOutRateIn / g);
-  if (rate == kOutRateIn) {
+  L = (int)(rate / g); M = (int)(base / g);
+  if (rate == base) {
     T = 1;
     if (taps) taps->assign(1, 1.0);
     return true;
   }
   const double A = 110.0, beta = 0.1102 * (A - 8.7);
-  const double hi_rate = (double)kOutRateIn * L;
+  const double hi_rate = (double)base * L;
   const double dw = 2.0 * M_PI * 0.05 * rate / hi_rate;
   const long long N = (long long)std::ceil((A - 7.95) / (2.285 * dw)) + 1;
   T = (int)((N + L - 1) / L);
@@ -342,6 +344,12 @@ inline bool design_output_rate(int rate, int &L, int &M, int &T, std::vector<dou
     h[(size_t)(n - 1 - i)] = h[(size_t)i];
   }
   return true;
+}
+inline bool design_output_rate(int rate, int &L, int &M, int &T, std::vector<double> *taps) {
+  return design_rate_filter(kOutRateIn, kOutRateMin, rate, L, M, T, taps);
+}
+inline bool design_mpx_rate(int rate, int &L, int &M, int &T, std::vector<double> *taps) {
+  return design_rate_filter(kMpxRateIn, kMpxRateMin, rate, L, M, T, taps);
 }
 
 struct Iir1Coef { double b0, b1, a1; };

@@ -40,6 +40,7 @@
 #include "kernels_analyser.hpp"
 #include "kernels_rfmon.hpp"
 #include "kernels_output.hpp"
+#include "kernels_mpxout.hpp"
 #include "kernels_weaksignal.hpp"
 #include <complex>
 #include "kernels_blanker.hpp"
@@ -349,6 +350,27 @@ struct OutputStage {
   OutArgs begin(unsigned long long block0, const int *if_len, int nb, long long N_au);
 };
 
+// MPX output (fmr_enable_mpx_output; kernels_mpxout.hpp).  One more reader of the call's MPX at the head
+// of the audio tail (fmr_chain::mpxout_stage): the composite at rate = 384000 L / M as PCM into a ring of mono frames per
+// stream.  The sample and frame counters and the carry's parity live here and are taken when a call is issued (begin): the
+// pipelined tail runs a call late.  The device carries the last T - 1 MPX samples (two rows by call parity, written by the
+// stage on the tail's stream) and the stream's clip / non-finite totals.
+struct MpxOutStage {
+  bool on = false;
+  fmr_mpx_output_config cfg{};               // the defaults filled in
+  MpxOutGeom geom{1, 1, 1, 0};
+  unsigned long long n = 0, oframes = 0;     // MPX samples handed in, ring frames produced: ceil(n L / M)
+  int par = 0;
+  DevBuf<double> d_taps;                     // the prototype, T L (none at 384000)
+  DevBuf<float> d_carry;                     // [2][S][T - 1] (none at 384000)
+  DevBuf<unsigned long long> d_tot;          // [S][2]
+  DevBuf<unsigned char> d_pcm;               // [S][max_frames] samples
+  RecCursor cur;
+  size_t frame_bytes() const { return cfg.format == FMR_PCM_F32 ? 4 : 2; }
+  int init(int S, const fmr_mpx_output_config &m);
+  MpxOutArgs begin(long long N_if);
+};
+
 // Weak-signal handling (fmr_enable_weak_signal; kernels_weaksignal.hpp).  Two halves on the tail's
 // stream: the detector and the control read the call's MPX beside the other MPX readers (fmr_chain::ws_measure); in
 // FMR_WS_ACT the action rewrites the finished audio directly behind the output mux (fmr_chain::ws_act).  The sample and
@@ -607,6 +629,7 @@ struct fmr_chain : ChainShape {
   AnalyserStage an;
   OutputStage out;
   WeakSignalStage ws;
+  MpxOutStage mpxo;
   BlankerStage nb;
   IqCorrectionStage iqc;
   int iqc_stage(const float2 *&d_iq, size_t &stride, long long N_in);
@@ -614,6 +637,7 @@ struct fmr_chain : ChainShape {
   int ws_measure(const fm_mpx_t *base, const WsArgs &a, hipStream_t st);
   int ws_act(double *d_aud, long long astride, const WsArgs &a, hipStream_t st);
   int rds_stage(const fm_mpx_t *base, long long N, hipStream_t st);
+  int mpxout_stage(const fm_mpx_t *base, const MpxOutArgs &a, hipStream_t st);
   // one call's N samples per stream through monitor m on stream st: the source as kseg / kreduce read it (from, stride, off)
   int seg_stage(SegMonitor &m, const void *from, long long stride, int off, float rf, float scale, MonSegFn kseg,
                 MonReduceFn kreduce, const char *seg_name, const char *reduce_name, long long N, hipStream_t st);
@@ -916,6 +940,7 @@ struct fmr_chain : ChainShape {
     OutArgs out{};                     // output stage: the call's positions and its slot of the per-block IF RMS
     const float *out_ifrms = nullptr;
     WsArgs ws{};                       // weak-signal handling: the call's positions
+    MpxOutArgs mpxo{};                 // MPX output: the call's positions
   };
   static constexpr int kDeBlock = 256;
   TailCtx tail_job{};
@@ -2475,6 +2500,7 @@ int fmr_chain::run_fm(CallCtx &k) {
   t.nch = stereo ? 2 : 1;
   if (out.on) { t.out = out.begin(k.out_block0, k.tab.if_len, nb, N_au); t.out_ifrms = out.ifrms_slot(k.par); }
   if (ws.on) t.ws = ws.begin(N_if, N_au);
+  if (mpxo.on) t.mpxo = mpxo.begin(N_if);
   for (int b = 0; b < nb; b++) t.au_max = std::max(t.au_max, k.tab.au_len[b]);
   t.count_am = (int)(arsc.mA - k.amA_prev);
   if ((size_t)t.count_am > max_amid || (size_t)N_au > max_au) { set_err("internal audio capacity exceeded"); return FMR_ERR_CAPACITY; }
@@ -2621,6 +2647,7 @@ int fmr_chain::tail_stage(const TailCtx &t, hipStream_t ts) {
                            t.N_if, ts))
       return rc;
   if (ws.on) if (int rc = ws_measure(t.base, t.ws, ts)) return rc;
+  if (mpxo.on) if (int rc = mpxout_stage(t.base, t.mpxo, ts)) return rc;
   const int nch = t.nch, dc_nc = t.dc_nc;
   const long long N_au = t.N_au;
   if (t.mono_enqueued) tail_channels(t, ts, 1, 1);
@@ -3349,6 +3376,73 @@ int fmr_chain::out_stage(const double *d_aud, long long astride, const BlockTab 
         hipLaunchKernelGGL(k_out_hist, dim3((hist + kOutThreads - 1) / kOutThreads, S), dim3(kOutThreads), 0, st, out.rate.d_z.p, gm,
                            a.zpar, (long long)a.n_frames * och, hist);
       });
+  }
+  HIPCHK(hipGetLastError());
+  return FMR_OK;
+}
+
+// ---- MPX output (kernels_mpxout.hpp) ----
+int MpxOutStage::init(int S, const fmr_mpx_output_config &m) {
+  std::vector<double> h;
+  MpxOutGeom gm{};
+  if (!design_mpx_rate(m.rate, gm.L, gm.M, gm.T, &h)) { set_err("fmr_enable_mpx_output: rate %d has no design", m.rate); return FMR_ERR_BAD_ARG; }
+  gm.span = (int)(((long long)(kMpxThreads - 1) * gm.M) / gm.L) + 1 + gm.T;
+  cfg = m; geom = gm;
+  int rc;
+  if (gm.T > 1) {
+    if ((rc = d_taps.alloc(h.size()))) return rc;
+    HIPCHK(hipMemcpy(d_taps.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = d_carry.alloc((size_t)2 * S * (gm.T - 1)))) return rc;      // (zeroed: z[j] = +0.0 for j < 0)
+  }
+  if ((rc = d_tot.alloc((size_t)2 * S))) return rc;
+  if ((rc = d_pcm.alloc((size_t)S * m.max_frames * frame_bytes()))) return rc;
+  cur.reset(S, 1); cur.L = m.max_frames;
+  n = oframes = 0; par = 0;
+  on = true;
+  return FMR_OK;
+}
+
+// the positions of one call, taken when it is issued; advances the counters
+MpxOutArgs MpxOutStage::begin(long long N_if) {
+  MpxOutArgs a{};
+  const unsigned long long L = (unsigned long long)geom.L, M = (unsigned long long)geom.M;
+  a.n0 = n; a.n = (unsigned long long)N_if;
+  n += a.n;
+  a.out0 = oframes;
+  oframes = (n * L + M - 1) / M;      // ring frames: ceil(F L / M) after F MPX samples
+  a.n_out = oframes - a.out0;
+  a.gain = cfg.gain; a.max_frames = cfg.max_frames;
+  a.par = par;
+  if (a.n > 0) par ^= 1;      // (a call without MPX samples launches nothing: the carry stays where it is)
+  return a;
+}
+
+// one call's MPX (the base slot of the call) through the MPX output on stream st
+int fmr_chain::mpxout_stage(const fm_mpx_t *base, const MpxOutArgs &a, hipStream_t st) {
+  if (a.n == 0) return FMR_OK;
+  static_assert(sizeof(fm_mpx_t) == sizeof(float), "the MPX output reads the MPX as floats");
+  const float *x = reinterpret_cast<const float *>(base);
+  const long long bstride = H_b + (long long)max_if;
+  const MpxOutGeom &gm = mpxo.geom;
+  const bool f32 = mpxo.cfg.format == FMR_PCM_F32;
+  if (gm.T == 1) {
+    timed_on(st, "mpx_copy", [&] {
+      hipLaunchKernelGGL(f32 ? k_mpx_copy<1> : k_mpx_copy<0>, dim3((unsigned)((a.n + kMpxThreads - 1) / kMpxThreads), S),
+                         dim3(kMpxThreads), 0, st, x, bstride, H_b, a, (void *)mpxo.d_pcm.p, mpxo.d_tot.p);
+    });
+  } else {
+    if (a.n_out > 0)
+      timed_on(st, "mpx_rate", [&] {
+        const size_t lds = (size_t)gm.span * sizeof(float) + 2 * (kMpxThreads / 64) * sizeof(unsigned);
+        hipLaunchKernelGGL(f32 ? k_mpx_rate<1> : k_mpx_rate<0>, dim3((unsigned)((a.n_out + kMpxThreads - 1) / kMpxThreads), S),
+                           dim3(kMpxThreads), lds, st, x, bstride, H_b, (const float *)mpxo.d_carry.p,
+                           (const double *)mpxo.d_taps.p, gm, a, (void *)mpxo.d_pcm.p, mpxo.d_tot.p);
+      });
+    const int hist = gm.T - 1;
+    timed_on(st, "mpx_hist", [&] {
+      hipLaunchKernelGGL(k_mpx_hist, dim3((hist + kMpxThreads - 1) / kMpxThreads, S), dim3(kMpxThreads), 0, st, x, bstride, H_b,
+                         mpxo.d_carry.p, hist, a);
+    });
   }
   HIPCHK(hipGetLastError());
   return FMR_OK;
@@ -4725,6 +4819,106 @@ int fmr_output_rate_taps(int rate, double *taps, int cap, int *L, int *M, int *T
   const long long n = (long long)t * l;
   if (taps && (long long)cap >= n) {
     design_output_rate(rate, l, m, t, &h);
+    memcpy(taps, h.data(), (size_t)n * sizeof(double));
+  }
+  return (int)n;
+}
+
+// ---- MPX output: C-ABI ----
+static int check_mpx_rate(const char *fn, int rate) {
+  int L, M, T;
+  if (!design_mpx_rate(rate, L, M, T, nullptr)) {
+    set_err("%s: rate %d is not 0, 384000 or a whole rate in 96000 .. 384000 with L = rate / gcd(rate, 384000) <= %d", fn, rate,
+            kOutRateMaxL);
+    return FMR_ERR_BAD_ARG;
+  }
+  return FMR_OK;
+}
+
+int fmr_enable_mpx_output(fmr_chain *c, const fmr_mpx_output_config *cfg, size_t cfg_size) {
+  const char *fn = "fmr_enable_mpx_output";
+  if (!cfg) { set_err("%s: cfg is null", fn); return FMR_ERR_BAD_ARG; }
+  fmr_mpx_output_config m;
+  if (int rc = take_sized(fn, "fmr_mpx_output_config", cfg, cfg_size, m)) return rc;
+  if (m.format != FMR_PCM_S16 && m.format != FMR_PCM_F32) {
+    set_err("%s: format %d is neither FMR_PCM_S16 (0) nor FMR_PCM_F32 (1)", fn, m.format);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (m.rate == 0) m.rate = kMpxRateIn;
+  if (int rc = check_mpx_rate(fn, m.rate)) return rc;
+  if (m.gain == 0.0) m.gain = 0.5;
+  if (!std::isfinite(m.gain) || !(m.gain > 0.0)) { set_err("%s: gain %g is not finite and > 0 (0 = 0.5)", fn, m.gain); return FMR_ERR_BAD_ARG; }
+  if (m.max_frames == 0) m.max_frames = 1u << 20;
+  if (m.max_frames > (1u << 26)) { set_err("%s: max_frames %u is outside 1 .. 2^26 (0 = 2^20)", fn, m.max_frames); return FMR_ERR_BAD_ARG; }
+  if (!c) { set_err("%s: chain is null", fn); return FMR_ERR_BAD_ARG; }
+  if (c->mode != FMR_MODE_FM) {
+    set_err("%s: the MPX output reads the MPX of an FM chain (mode FMR_MODE_FM); mode %d %s", fn, c->mode,
+            c->mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no MPX" : "has no MPX");
+    return FMR_ERR_UNSUPPORTED;
+  }
+  return enable_stage(fn, c, c->mpxo, "MPX output", "MPX sample", c->S, m);
+}
+
+int fmr_mpx_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, size_t *n_frames, fmr_mpx_output_info *info,
+                        size_t info_size) {
+  if (n_frames) *n_frames = 0;
+  if (!c || stream < 0 || stream >= c->S) { set_err("fmr_mpx_output_read: bad chain or stream"); return FMR_ERR_BAD_ARG; }
+  if (!c->mpxo.on) { set_err("fmr_mpx_output_read: the chain has no MPX output (fmr_enable_mpx_output)"); return FMR_ERR_BAD_ARG; }
+  if (cap_frames > 0 && !pcm) { set_err("fmr_mpx_output_read: pcm is null"); return FMR_ERR_BAD_ARG; }
+  if (info && (info_size ? info_size : sizeof(fmr_mpx_output_info)) > sizeof(fmr_mpx_output_info)) {
+    set_err("fmr_mpx_output_read: info_size %zu is larger than this library's fmr_mpx_output_info (%zu): the caller is newer than the library",
+            info_size, sizeof(fmr_mpx_output_info));
+    return FMR_ERR_BAD_ARG;
+  }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    MpxOutStage &st = c->mpxo;
+    const size_t fb = st.frame_bytes();
+    RecCursor &fc = st.cur;
+    fc.catch_up(stream, st.oframes);
+    const unsigned long long first = fc.read[stream];
+    int nf = 0;
+    if (cap_frames > 0) {
+      nf = fc.take(stream, st.oframes, (unsigned long long)cap_frames, [&](size_t k, size_t slot, size_t m) -> int {
+        HIPCHK(hipMemcpy((char *)pcm + k * fb, st.d_pcm.p + ((size_t)stream * fc.L + slot) * fb, m * fb, hipMemcpyDeviceToHost));
+        return FMR_OK;
+      });
+      if (nf < 0) return nf;
+    }
+    if (n_frames) *n_frames = (size_t)nf;
+    if (info) {
+      fmr_mpx_output_info full{};
+      full.struct_size = (unsigned)sizeof full;
+      full.format = st.cfg.format; full.rate = st.cfg.rate;
+      full.L = st.geom.L; full.M = st.geom.M; full.taps_per_phase = st.geom.T;
+      full.delay_frames = st.geom.T > 1 ? ((double)st.geom.T * st.geom.L - 1.0) / (2.0 * st.geom.M) : 0.0;
+      full.full_scale_hz = 75000.0 / st.cfg.gain;
+      full.first_frame = first;
+      full.frames_waiting = st.oframes - fc.read[stream];
+      full.frames_dropped = fc.dropped[stream];
+      full.samples_in = st.n;
+      unsigned long long tot[2];
+      HIPCHK(hipMemcpy(tot, st.d_tot.p + 2 * (size_t)stream, sizeof tot, hipMemcpyDeviceToHost));
+      full.pcm_clipped = tot[0]; full.pcm_nonfinite = tot[1];
+      give_sized(info, info_size, full);
+    }
+    return nf;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_mpx_output_taps(int rate, double *taps, int cap, int *L, int *M, int *T) {
+  if (rate == 0) rate = kMpxRateIn;
+  if (int rc = check_mpx_rate("fmr_mpx_output_taps", rate)) return rc;
+  int l, m, t;
+  std::vector<double> h;
+  design_mpx_rate(rate, l, m, t, nullptr);
+  if (L) *L = l;
+  if (M) *M = m;
+  if (T) *T = t;
+  const long long n = (long long)t * l;
+  if (taps && (long long)cap >= n) {
+    design_mpx_rate(rate, l, m, t, &h);
     memcpy(taps, h.data(), (size_t)n * sizeof(double));
   }
   return (int)n;

@@ -92,6 +92,21 @@ __device__ __forceinline__ unsigned out_wave_sum(unsigned v) {
   return v;
 }
 
+// A workgroup of kOutThreads adds its clip / non-finite counts to a stream's totals, totals[0] and totals[1]: butterfly per
+// wave, the waves in order, one integer atomic each.  s_cnt: 2 (kOutThreads / 64) words of LDS.  (k_out_rate, kernels_mpxout.hpp)
+__device__ __forceinline__ void out_add_totals(unsigned cl, unsigned nf, unsigned *s_cnt, unsigned long long *totals) {
+  cl = out_wave_sum(cl); nf = out_wave_sum(nf);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { s_cnt[2 * w] = cl; s_cnt[2 * w + 1] = nf; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    unsigned t = 0;
+#pragma unroll
+    for (int k = 0; k < kOutThreads / 64; k++) t += s_cnt[2 * k + threadIdx.x];
+    if (t) atomicAdd(&totals[threadIdx.x], (unsigned long long)t);
+  }
+}
+
 // aud: the call's audio as the decoder wrote it (row s at s astride, frames interleaved); if_rms_blk [S][nb]: the IF RMS of
 // every block of this call (k_stats); ring [S][max_frames] frames; part [S][nb]
 template <int FMT, int CH>
@@ -278,16 +293,7 @@ __global__ __launch_bounds__(kOutThreads) void k_out_rate(const double *__restri
     if (m >= keep_from)
       (reinterpret_cast<typename F::type *>(ring) + (size_t)s * a.max_frames)[m % a.max_frames] = F::pack(v);
   }
-  cl = out_wave_sum(cl); nf = out_wave_sum(nf);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { s_cnt[2 * w] = cl; s_cnt[2 * w + 1] = nf; }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    unsigned t = 0;
-#pragma unroll
-    for (int k = 0; k < kOutThreads / 64; k++) t += s_cnt[2 * k + threadIdx.x];
-    if (t) atomicAdd(&totals[2 * s + threadIdx.x], (unsigned long long)t);
-  }
+  out_add_totals(cl, nf, s_cnt, totals + 2 * s);
 }
 
 // hist = (T - 1) channels doubles per stream, n = the call's frames times channels: from behind them in row zpar to the

@@ -1345,6 +1345,66 @@ int fmr_get_output_rate(fmr_chain *c, int stream, fmr_output_rate_info *info, si
  * single tap 1.0.  FMR_ERR_BAD_ARG for a rate fmr_set_output_rate refuses. */
 int fmr_output_rate_taps(int rate, double *taps, int cap, int *L, int *M, int *T);
 
+/* --- MPX output: every stream's / bank channel's composite baseband -- the 384 kHz MPX the chain
+ * demodulates on the device, which the modulation monitor measures and the RDS stage reads -- as mono PCM at
+ * rate = 384000 L / M, for MPX analysers, external RDS / RDS2 decoders, archive recorders and a later stereo decode.
+ * Off unless enabled; the stage only reads the MPX: the chain's audio, fmr_status, PPS events, RDS groups, every monitor's
+ * records and the output stage's PCM are what they are without it.
+ * Definition, per stream, over the MPX samples since the chain's first sample; nothing depends on blocks or calls:
+ *   x[j] is MPX sample j as the fp32 value it is; 1.0 means 75 kHz deviation, as in the modulation monitor.
+ *   z[j] = (double)x[j] gain, one fp64 product.  z[j] = +0.0 for j < 0.
+ *   Ring frame m = 0, 1, ... takes q = floor(m M / L), p = (m M) mod L and acc = 0.0; for k = 0 .. T - 1 ascending
+ *   acc = acc + h[k L + p] z[q - k], every product and every sum rounded by itself in fp64 (no fused multiply-add).
+ *   acc is converted by the rules of FMR_PCM_S16 / FMR_PCM_F32 above (S16: rint(acc 32767), ties to even, saturated; NaN
+ *   becomes 0) and counted in pcm_clipped / pcm_nonfinite as in fmr_output_rate_info.
+ *   Frame m exists as soon as x[q] does: after F MPX samples the ring has received ceil(F L / M) frames.
+ *   At rate 384000 there is no filter: L = M = T = 1 and acc = z[j].
+ * h is the prototype of fmr_mpx_output_taps, the design rule of fmr_output_rate_taps with 384000 in place of 48000: a
+ * Kaiser-windowed sinc at rate 384000 L of T L taps, symmetric bit for bit about (T L - 1) / 2, sum h = L; pass band
+ * 0 .. 0.9 rate / 2 within +-0.001 dB, stop band from rate / 2 on >= 100 dB down (design attenuation 110 dB, cutoff
+ * 0.95 rate / 2).  At 192000 the pass band reaches 86.4 kHz: pilot, stereo subcarrier, RDS and the RDS2 carriers.
+ * PCM ring: max_frames mono frames per stream, frame f at slot f mod max_frames.  When unread frames would be overwritten
+ * the oldest are dropped and counted in frames_dropped, exactly as in fmr_output_read; processing never fails because of
+ * the ring.  The read positions live on the host. */
+typedef struct {
+  unsigned struct_size;   /* as the other configs: 0 = cfg_size; larger than the library's is refused */
+  int format;             /* FMR_PCM_S16 or FMR_PCM_F32 */
+  int rate;               /* PCM rate in Hz.  0 or 384000: the MPX as it is, no filter.  Otherwise a whole rate,
+                             96000 <= rate < 384000, with L = rate / gcd(rate, 384000) <= 160: 96000, 171000 (3 x 57 kHz,
+                             57 / 128), 192000 (1 / 2), 228000 (12 x 19 kHz, 19 / 32), 256000 (2 / 3), ...; 100001 is refused */
+  double gain;            /* finite, > 0; 0 = 0.5: S16 full scale is +-150 kHz, a legal +-75 kHz station never clips */
+  uint32_t max_frames;    /* PCM ring per stream in frames: 1 .. 2^26; 0 = 2^20 */
+} fmr_mpx_output_config;
+typedef struct {
+  unsigned struct_size;
+  int format, rate;
+  int L, M, taps_per_phase;      /* rate / 384000 = L / M in lowest terms; T (1 without a filter) */
+  double delay_frames;           /* group delay in ring frames: (T L - 1) / (2 M); 0 without a filter */
+  double full_scale_hz;          /* the deviation that PCM 1.0 (S16: 32767) stands for: 75000 / gain */
+  uint64_t first_frame;          /* absolute index of the first frame this call returned, or of the next one if none */
+  uint64_t frames_waiting;       /* frames still unread after this call */
+  uint64_t frames_dropped;       /* of this stream: overwritten unread, since create */
+  uint64_t samples_in;           /* MPX samples taken since create */
+  uint64_t pcm_clipped, pcm_nonfinite;   /* of this stream since create, every produced frame, by the rules of the format */
+} fmr_mpx_output_info;
+/* Checks the fields first (FMR_ERR_BAD_ARG, fmr_last_error names the field, also with a NULL chain; also a size larger
+ * than this library's struct), then the chain: NULL is FMR_ERR_BAD_ARG; any FMR_MODE_FM chain is accepted (plain and
+ * fmr_create_rds chains, banks, both resampler classes, pipelined or in_order, with the IF filter and the equaliser);
+ * other modes and front-end-only chains (mode -1, channelizers) are FMR_ERR_UNSUPPORTED.  Allowed once, before the chain's
+ * first sample: a second call, or one after any processing call, is FMR_ERR_BAD_ARG.  A chain that never calls it
+ * allocates nothing for the stage and runs none of its kernels. */
+int fmr_enable_mpx_output(fmr_chain *c, const fmr_mpx_output_config *cfg, size_t cfg_size);
+/* Synchronises like the other getters, then drains up to cap_frames frames of `stream`, oldest first, into pcm (int16 or
+ * float32) and returns their number (*n_frames, if not NULL, takes it too).  cap_frames = 0 drains nothing: info (may be
+ * NULL; info_size bytes, 0 = this header's size) says what waits.  FMR_ERR_BAD_ARG for pcm = NULL with cap_frames > 0, a
+ * bad stream index, a chain without the stage and an info_size larger than this library's struct. */
+int fmr_mpx_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, size_t *n_frames, fmr_mpx_output_info *info,
+                        size_t info_size);
+/* Host only, no device: the prototype filter of `rate` (T L doubles) and L, M, T (each may be NULL), with the contract of
+ * fmr_output_rate_taps.  rate 384000 (or 0) gives the single tap 1.0.  FMR_ERR_BAD_ARG for a rate fmr_enable_mpx_output
+ * refuses. */
+int fmr_mpx_output_taps(int rate, double *taps, int cap, int *L, int *M, int *T);
+
 #ifdef __cplusplus
 }
 #endif
