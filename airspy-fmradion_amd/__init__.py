@@ -58,6 +58,8 @@ EXPORTS = [
     "fmr_enable_output", "fmr_output_read", "fmr_squelch_level_from_db",
     "fmr_set_output_rate", "fmr_get_output_rate", "fmr_output_rate_taps",
     "fmr_enable_mpx_output", "fmr_mpx_output_read", "fmr_mpx_output_taps",
+    "fmr_create_mpx_decoder", "fmr_process_mpx_blocks", "fmr_process_mpx_blocks_device", "fmr_get_mpx_input_info",
+    "fmr_mpx_input_geometry", "fmr_debug_mpx_chain_shape",
     "fmr_enable_weak_signal", "fmr_weak_signal_read", "fmr_weak_signal_derive",
     "fmr_enable_blanker", "fmr_blanker_read", "fmr_blanker_derive",
     "fmr_enable_iq_correction", "fmr_iq_correction_read", "fmr_iq_correction_derive",
@@ -156,6 +158,16 @@ def mpx_output_taps(rate):
     h = np.zeros(n, dtype=np.float64)
     Lb.fmr_mpx_output_taps(int(rate), h.ctypes.data_as(C.POINTER(C.c_double)), n, None, None, None)
     return h, l.value, m.value, t.value
+
+
+def mpx_input_geometry(rate):
+    """fmr_mpx_input_geometry: (L, M, T, K, delay_samples) of an MPX input at `rate` (host only)."""
+    Lb = lib()
+    l, m, t, k, d = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_double()
+    rc = Lb.fmr_mpx_input_geometry(int(rate), C.byref(l), C.byref(m), C.byref(t), C.byref(k), C.byref(d))
+    if rc < 0:
+        raise FmrError(f"fmradion_amd error {rc}: {Lb.fmr_last_error().decode()}")
+    return l.value, m.value, t.value, k.value, d.value
 
 
 def output_frame_of(first_frame, rate):
@@ -412,6 +424,17 @@ class MpxOutputInfo(C.Structure):
                 ("samples_in", C.c_uint64), ("pcm_clipped", C.c_uint64), ("pcm_nonfinite", C.c_uint64)]
 
 
+class MpxInputConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("format", C.c_int), ("rate", C.c_int), ("gain", C.c_double), ("rds", C.c_int)]
+
+
+class MpxInputInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("format", C.c_int), ("rate", C.c_int), ("L", C.c_int), ("M", C.c_int),
+                ("taps_per_phase", C.c_int), ("taps_per_sample", C.c_int), ("delay_samples", C.c_double),
+                ("full_scale_hz", C.c_double), ("frames_in", C.c_uint64), ("samples_out", C.c_uint64),
+                ("nonfinite_in", C.c_uint64)]
+
+
 def build_library(force=False, verbose=False):
     """Compile the HIP library (and its A/B partner build) in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     import glob
@@ -555,6 +578,19 @@ def lib(ab=False):
     L.fmr_mpx_output_read.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(MpxOutputInfo), C.c_size_t]
     L.fmr_mpx_output_taps.restype = C.c_int
     L.fmr_mpx_output_taps.argtypes = [C.c_int, dp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.fmr_create_mpx_decoder.restype = C.c_int
+    L.fmr_create_mpx_decoder.argtypes = [C.POINTER(Config), C.c_size_t, C.POINTER(MpxInputConfig), C.c_size_t, C.POINTER(vp)]
+    L.fmr_process_mpx_blocks.restype = C.c_int
+    L.fmr_process_mpx_blocks.argtypes = [vp, vp, C.c_size_t, u32p, C.c_int, dp, C.c_size_t, u32p]
+    L.fmr_process_mpx_blocks_device.restype = C.c_int
+    L.fmr_process_mpx_blocks_device.argtypes = [vp, vp, C.c_size_t, u32p, C.c_int, vp, C.c_size_t, u32p, C.c_int]
+    L.fmr_get_mpx_input_info.restype = C.c_int
+    L.fmr_get_mpx_input_info.argtypes = [vp, C.c_int, C.POINTER(MpxInputInfo), C.c_size_t]
+    L.fmr_mpx_input_geometry.restype = C.c_int
+    L.fmr_mpx_input_geometry.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), dp]
+    L.fmr_debug_mpx_chain_shape.restype = C.c_int
+    L.fmr_debug_mpx_chain_shape.argtypes = [C.POINTER(Config), C.c_size_t, C.POINTER(MpxInputConfig), C.c_size_t,
+                                            C.POINTER(ChainShapeInfo), C.c_size_t]
     L.fmr_enable_weak_signal.restype = C.c_int
     L.fmr_enable_weak_signal.argtypes = [vp, C.POINTER(WeakSignalConfig), C.c_size_t]
     L.fmr_weak_signal_read.restype = C.c_int
@@ -824,7 +860,8 @@ class ChainShapeInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("D", C.c_int), ("NA", C.c_int), ("LB", C.c_longlong), ("MB", C.c_longlong),
                 ("TB", C.c_int), ("LT", C.c_int), ("stage_b", C.c_uint), ("fused", C.c_int), ("decim16", C.c_int),
                 ("poly5h_disc", C.c_int), ("fir", C.c_int), ("qa", C.c_int), ("pipelined", C.c_int),
-                ("max_if", C.c_uint64), ("max_au", C.c_uint64)]
+                ("max_if", C.c_uint64), ("max_au", C.c_uint64), ("mpx_in", C.c_int), ("mpx_format", C.c_int),
+                ("mpx_L", C.c_int), ("mpx_M", C.c_int), ("mpx_T", C.c_int), ("mpx_K", C.c_int)]
 
 
 ChainShape = collections.namedtuple("ChainShape", "design stage_b fused decim16 poly5h_disc fir qa pipelined max_if max_au")
@@ -1280,6 +1317,100 @@ class Chain:
         ms = (C.c_float * cap)()
         n = self._chk(self._L.fmr_get_kernel_times(self.h, names, ms, cap))
         return [(names[i].decode(), ms[i]) for i in range(min(n, cap))]
+
+
+def _mpx_configs(rate, format, gain, n_streams, stereo, deemphasis_us, pilot_shift, rds, max_block_len, max_blocks, device):
+    """(fmr_config, fmr_mpx_input_config, keep-alive) of MpxChain's arguments."""
+    cfg, keep = _make_config(MODE_FM, 0.0, False, False, False, None, stereo, deemphasis_us, pilot_shift, 0, max_block_len,
+                             max_blocks, n_streams, device, 0.0, IQ_CF32, 0.0, RESAMPLER_FAST, False, None)
+    cfg.filter_coeff, cfg.n_filter_coeff = None, 0       # (not needed: there is no IF filter)
+    fmt = {"s16": PCM_S16, "f32": PCM_F32}.get(format, format)
+    return cfg, MpxInputConfig(C.sizeof(MpxInputConfig), int(fmt), int(rate), float(gain), int(bool(rds))), keep
+
+
+def mpx_chain_shape(rate=192000, format="s16", gain=0.0, n_streams=1, stereo=True, deemphasis_us=50.0, pilot_shift=False,
+                    rds=False, max_block_len=65536, max_blocks=1, device=0):
+    """fmr_debug_mpx_chain_shape: what creating MpxChain(...) would decide, without a device, as a dict of
+    fmr_chain_shape_info's fields; a refusal raises FmrError with .code and .message."""
+    L = lib()
+    cfg, mi, _keep = _mpx_configs(rate, format, gain, n_streams, stereo, deemphasis_us, pilot_shift, rds, max_block_len,
+                                  max_blocks, device)
+    o = ChainShapeInfo()
+    rc = L.fmr_debug_mpx_chain_shape(C.byref(cfg), C.sizeof(Config), C.byref(mi), C.sizeof(MpxInputConfig), C.byref(o),
+                                     C.sizeof(ChainShapeInfo))
+    if rc != OK:
+        e = FmrError(f"fmr_debug_mpx_chain_shape failed ({rc}): {L.fmr_last_error().decode()}")
+        e.code, e.message = rc, L.fmr_last_error().decode()
+        raise e
+    return {k: int(getattr(o, k)) for k, _ in ChainShapeInfo._fields_ if k != "struct_size"}
+
+
+class MpxChain(Chain):
+    """An FM decoder fed composite baseband (fmr_create_mpx_decoder): n_streams rows of mono PCM at `rate` -- int16
+    ("s16") or float32 ("f32") -- instead of IQ.  rate 0 / 384000: the MPX as it is; gain 0 = 2.0.  Everything behind the
+    front end is Chain's: status, pps_events, the monitors, the output stage, enable_mpx_output, and with rds=True
+    rds_groups / rds_status / set_rds_correction."""
+
+    _CREATE = "fmr_create_mpx_decoder"
+
+    def __init__(self, rate=192000, format="s16", gain=0.0, n_streams=1, stereo=True, deemphasis_us=50.0, pilot_shift=False,
+                 rds=False, max_block_len=65536, max_blocks=1, device=0):
+        self._L = lib()
+        self.enable_rds, self.bank, self.input_format = bool(rds), False, IQ_CF32
+        cfg, self._mi, self._keep = _mpx_configs(rate, format, gain, n_streams, stereo, deemphasis_us, pilot_shift, rds,
+                                                 max_block_len, max_blocks, device)
+        self.format = int(self._mi.format)
+        self.n_streams, self.mode, self.stereo = int(n_streams), MODE_FM, bool(stereo)
+        self.h = C.c_void_p()
+        rc = self._L.fmr_create_mpx_decoder(C.byref(cfg), C.sizeof(Config), C.byref(self._mi), C.sizeof(MpxInputConfig),
+                                            C.byref(self.h))
+        if rc != OK:
+            self.h = None
+            e = FmrError(f"{self._CREATE} failed ({rc}): {self._L.fmr_last_error().decode()}")
+            e.code, e.message = rc, self._L.fmr_last_error().decode()
+            raise e
+
+    def process(self, pcm):
+        """One block of one stream: frames in, audio doubles out."""
+        pcm = np.ascontiguousarray(pcm, dtype=_PCM_DTYPE[self.format])
+        assert pcm.ndim == 1 and self.n_streams == 1
+        if len(pcm) == 0:
+            return np.zeros(0, dtype=np.float64)
+        audio, _ = self.process_blocks(pcm[None, :], [len(pcm)])
+        return audio[0]
+
+    def process_blocks(self, pcm, block_len):
+        """pcm: (n_streams, N) int16 / float32 frames; block_len: consecutive block lengths in frames.  Returns
+        (audio[S][total], audio_len)."""
+        pcm = np.atleast_2d(np.asarray(pcm))
+        assert pcm.dtype == _PCM_DTYPE[self.format], (pcm.dtype, self.format)
+        pcm = np.ascontiguousarray(pcm)
+        assert pcm.shape[0] == self.n_streams
+        bl = np.ascontiguousarray(block_len, dtype=np.uint32)
+        assert int(bl.sum()) <= pcm.shape[1]
+        acap = int(bl.sum()) + 64 * len(bl) + 64      # (at most 4 MPX samples per frame, 2 doubles per 8 of them)
+        audio = np.zeros((self.n_streams, acap), dtype=np.float64)
+        alen = np.zeros(len(bl), dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        self._chk(self._L.fmr_process_mpx_blocks(self.h, pcm.ctypes.data, pcm.shape[1], bl.ctypes.data_as(u32p), len(bl),
+                                                 audio.ctypes.data_as(C.POINTER(C.c_double)), acap, alen.ctypes.data_as(u32p)))
+        return audio[:, :int(alen.sum())].copy(), alen
+
+    def process_blocks_device(self, d_pcm_ptr, stream_stride, block_len, d_audio_ptr, audio_stride, sync=False):
+        """fmr_process_mpx_blocks_device: rows of stream_stride frames at d_pcm_ptr (16-byte aligned rows and stride)."""
+        bl = np.ascontiguousarray(block_len, dtype=np.uint32)
+        alen = np.zeros(len(bl), dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        self._chk(self._L.fmr_process_mpx_blocks_device(self.h, C.c_void_p(d_pcm_ptr), stream_stride, bl.ctypes.data_as(u32p),
+                                                        len(bl), C.c_void_p(d_audio_ptr), audio_stride,
+                                                        alen.ctypes.data_as(u32p), int(sync)))
+        return alen
+
+    def mpx_input_info(self, stream=0):
+        """fmr_get_mpx_input_info as a dict."""
+        info = MpxInputInfo()
+        self._chk(self._L.fmr_get_mpx_input_info(self.h, int(stream), C.byref(info), C.sizeof(MpxInputInfo)))
+        return {k: getattr(info, k) for k, _ in MpxInputInfo._fields_ if k != "struct_size"}
 
 
 class Channelizer(Chain):

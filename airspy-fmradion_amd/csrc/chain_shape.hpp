@@ -81,6 +81,12 @@ struct ChainShape {
   DeScan de_scan{};                    // pw here; apow points into device memory (the build step sets it)
   float agc_init = 1.f, agc_max = 1e5f, agc_rate = 1e-4f;
   float disc_nf = 1.f, disc_bound = 1.f;
+  // MPX-input form (fmr_create_mpx_decoder; kernels_mpxin.hpp): no IF at all -- StageA::none / StageB::none / IfForm::none in
+  // every call -- the front end reads mono PCM at 384000 L / M and writes the MPX row; max_in counts frames, max_if MPX samples
+  bool mpx_in = false;
+  int mi_format = 0, mi_rate = 0, mi_L = 1, mi_M = 1, mi_T = 1, mi_K = 1;
+  double mi_gain = 1.0;                // as configured (the default filled in); the kernels take gain M / L
+  bool mi_rds = false;
   int in_rows() const { return bank ? 1 : S; }   // rows of the input buffers (d_in, d_in_halo)
 };
 
@@ -383,10 +389,53 @@ static int plan_decoder(ChainShape &sh) {
   return FMR_OK;
 }
 
+// ---- MPX input (fmr_create_mpx_decoder): what its two structs may hold, and the geometry of the rate
+static inline int mpx_in_taps_per_sample(int L, int M, int T) { return (int)(((long long)T * L + M - 1) / M); }
+static int plan_mpx_input(ChainShape &sh, const fmr_mpx_input_config &in) {
+  const char *fn = "fmr_create_mpx_decoder";
+  const fmr_config &c = sh.cfg;
+  if (c.mode != FMR_MODE_FM) {
+    set_err("%s: mode %d: the MPX input feeds the FM decoder (mode = FMR_MODE_FM)", fn, c.mode);
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (c.fmfilter_enable) { set_err("%s: fmfilter_enable: the IF filter works on IF samples, and an MPX input has none", fn); return FMR_ERR_UNSUPPORTED; }
+  if (c.multipath_stages > 0) { set_err("%s: multipath_stages %u: the equaliser works on IF samples, and an MPX input has none", fn, c.multipath_stages); return FMR_ERR_UNSUPPORTED; }
+  if (c.input_format != FMR_IQ_CF32) { set_err("%s: input_format %d: the PCM format is fmr_mpx_input_config.format; input_format must stay FMR_IQ_CF32 (0)", fn, c.input_format); return FMR_ERR_UNSUPPORTED; }
+  if (c.enable_fourth_down) { set_err("%s: enable_fourth_down: there is no IQ input to shift", fn); return FMR_ERR_UNSUPPORTED; }
+  if (c.enable_resampler) { set_err("%s: enable_resampler must be 0: the IF resampler works on IQ; the PCM rate is fmr_mpx_input_config.rate", fn); return FMR_ERR_BAD_ARG; }
+  if (c.channel_offset_hz) { set_err("%s: channel_offset_hz must be NULL: a channel bank cuts an IQ capture", fn); return FMR_ERR_BAD_ARG; }
+  if (in.format != FMR_PCM_S16 && in.format != FMR_PCM_F32) {
+    set_err("%s: format %d is neither FMR_PCM_S16 (0) nor FMR_PCM_F32 (1)", fn, in.format);
+    return FMR_ERR_BAD_ARG;
+  }
+  const int rate = in.rate == 0 ? kMpxRateIn : in.rate;
+  int L, M, T;
+  if (!design_mpx_rate(rate, L, M, T, nullptr)) {
+    set_err("%s: rate %d is not 0, 384000 or a whole rate in 96000 .. 384000 with L = rate / gcd(rate, 384000) <= %d", fn, in.rate, kOutRateMaxL);
+    return FMR_ERR_BAD_ARG;
+  }
+  if (c.input_rate != 0.0 && c.input_rate != (double)rate) {
+    set_err("%s: input_rate %.9g is neither 0 nor the PCM rate %d", fn, c.input_rate, rate);
+    return FMR_ERR_BAD_ARG;
+  }
+  const double gain = in.gain == 0.0 ? 2.0 : in.gain;
+  if (!std::isfinite(gain) || !(gain > 0.0)) { set_err("%s: gain %g is not finite and > 0 (0 = 2.0)", fn, in.gain); return FMR_ERR_BAD_ARG; }
+  if (in.rds != 0 && in.rds != 1) { set_err("%s: rds %d is neither 0 nor 1", fn, in.rds); return FMR_ERR_BAD_ARG; }
+  sh.mpx_in = true;
+  sh.mi_format = in.format; sh.mi_rate = rate; sh.mi_L = L; sh.mi_M = M; sh.mi_T = T;
+  sh.mi_K = T > 1 ? mpx_in_taps_per_sample(L, M, T) : 1;
+  sh.mi_gain = gain; sh.mi_rds = in.rds != 0;
+  sh.cfg.input_rate = (double)rate;
+  return FMR_OK;
+}
+
 // The whole shape, or the refusal: every rule a configuration can break, in one order, with no device in sight.
-static int plan_create(ChainShape &sh, const fmr_config *c, const EnvKnobs &env, bool channelizer) {
+// mpx_in != nullptr: the MPX-input form (fmr_create_mpx_decoder).
+static int plan_create(ChainShape &sh, const fmr_config *c, const EnvKnobs &env, bool channelizer,
+                       const fmr_mpx_input_config *mpx_in = nullptr) {
   sh = ChainShape{};
   sh.cfg = *c;
+  if (mpx_in) { if (int rc = plan_mpx_input(sh, *mpx_in)) return rc; }
   const int S = sh.S = c->n_streams, mode = sh.mode = c->mode;
   if (env.x_cpll >= C_PLL_MIN) sh.c_pll = env.x_cpll;
   if (env.pll_rtol >= 0.0) sh.pll_rtol = env.pll_rtol;
@@ -427,10 +476,13 @@ static int plan_create(ChainShape &sh, const fmr_config *c, const EnvKnobs &env,
   }
   if (sh.has_rs) {
     if (int rc = plan_front_end(sh, env)) return rc;
+  } else if (sh.mpx_in) {
+    sh.max_if = (size_t)(((unsigned long long)sh.max_in * (unsigned)sh.mi_M + (unsigned)sh.mi_L - 1) / (unsigned)sh.mi_L) + 4;   // MPX samples: ceil(max_in M / L) + 4
   } else {
     sh.max_if = sh.max_in;
   }
   sh.ntaps = c->n_filter_coeff;
+  if (sh.mpx_in) sh.ntaps = 0;         // (nothing of the IF: no filter taps, no IF halo)
   sh.ssb_like = (mode == FMR_MODE_USB || mode == FMR_MODE_LSB || mode == FMR_MODE_CW || mode == FMR_MODE_WSPR);
   const float *filter_src = c->filter_coeff;
   if (sh.ssb_like) {     // AmDecoder's own filters: m_ssbfilter for USB/LSB, m_cwfilter for CW/WSPR (AmDecode.cpp:36,40)
@@ -438,12 +490,13 @@ static int plan_create(ChainShape &sh, const fmr_config *c, const EnvKnobs &env,
     sh.ntaps = 2049;
   }
   sh.fir_enable = (mode == FMR_MODE_FM) ? (c->fmfilter_enable != 0) : (mode != FMR_MODE_NONE);
-  if (sh.has_dec && (sh.ntaps < 1 || !filter_src)) { set_err("filter_coeff missing"); return FMR_ERR_BAD_ARG; }
-  sh.H_if = sh.has_dec ? (sh.ntaps > 1 ? sh.ntaps - 1 : 1) : 1;
+  if (sh.has_dec && !sh.mpx_in && (sh.ntaps < 1 || !filter_src)) { set_err("filter_coeff missing"); return FMR_ERR_BAD_ARG; }
+  sh.H_if = sh.mpx_in ? 0 : sh.has_dec ? (sh.ntaps > 1 ? sh.ntaps - 1 : 1) : 1;
   sh.max_ck = std::max(sh.max_if / (size_t)sh.c_pll, std::min<size_t>(sh.max_if, (size_t)kSmallCall) / (size_t)kCPllSmall) + (size_t)sh.max_blocks + 2;
   sh.tab_ints = 5 * (size_t)sh.max_blocks + 3 * sh.max_ck + (size_t)sh.max_blocks + 1 + ChainShape::kMaxFusedWg;   // tail: first block of each fused workgroup
   sh.max_agc_nc = sh.max_if / C_AGC + 2;
   if (!sh.has_dec) return FMR_OK;
+  if (sh.mpx_in) return plan_decoder(sh);
   sh.filter.assign(filter_src, filter_src + sh.ntaps);
   sh.h_coeff0 = sh.filter[0];
   // the IF filter on the matrix cores (127 or 255 taps): FM -f with the discriminator as the kernel's epilogue, and the

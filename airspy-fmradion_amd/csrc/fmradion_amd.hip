@@ -41,6 +41,7 @@
 #include "kernels_rfmon.hpp"
 #include "kernels_output.hpp"
 #include "kernels_mpxout.hpp"
+#include "kernels_mpxin.hpp"
 #include "kernels_weaksignal.hpp"
 #include <complex>
 #include "kernels_blanker.hpp"
@@ -371,6 +372,32 @@ struct MpxOutStage {
   MpxOutArgs begin(long long N_if);
 };
 
+// MPX input (fmr_create_mpx_decoder; kernels_mpxin.hpp).  The front end of a chain that is fed PCM: it
+// stands where IF resampler, IF AGC and discriminator stand on an IQ chain (fmr_chain::mpxin_stage, on the decoder stream) and
+// writes the call's MPX row, its float copy and the per-block baseband sums.  The frame and sample counters and the
+// carry's parity live here; plan_call reads them for the count law, mpxin_stage advances them (begin).  The device carries
+// the last K - 1 frames as u (two rows by call parity) and the streams' non-finite totals; d_pcm takes the rows of the
+// host entry point (fmr_process_mpx_blocks).  Built by init() of such a chain and of no other.
+struct MpxInStage {
+  bool on = false;
+  MpxInGeom geom{1, 1, 1, 1, 0};
+  int format = FMR_PCM_S16;
+  double gain = 1.0, g = 1.0;                // as configured; gain M / L (the kernels' factor)
+  unsigned long long frames = 0, samples = 0;   // frames taken, MPX samples made of them: ceil(frames M / L)
+  int par = 0;
+  DevBuf<double> d_taps;                     // the prototype padded to K M (none at 384000)
+  DevBuf<double> d_carry;                    // [2][S][K - 1] (none at 384000)
+  DevBuf<double> d_s16;                      // FMR_PCM_S16: v / 32767.0 for every v, formed here on the host ([v + 32768])
+  DevBuf<unsigned long long> d_tot;          // [S]
+  DevBuf<unsigned char> d_pcm;               // [S][max_in] frames
+  size_t frame_bytes() const { return format == FMR_PCM_F32 ? 4 : 2; }
+  unsigned long long samples_after(unsigned long long f) const {      // the count law
+    return (f * (unsigned long long)geom.M + (unsigned long long)geom.L - 1) / (unsigned long long)geom.L;
+  }
+  int init(int S, size_t max_in, int rate, int fmt, double gain_);
+  MpxInArgs begin(long long n_frames);
+};
+
 // Weak-signal handling (fmr_enable_weak_signal; kernels_weaksignal.hpp).  Two halves on the tail's
 // stream: the detector and the control read the call's MPX beside the other MPX readers (fmr_chain::ws_measure); in
 // FMR_WS_ACT the action rewrites the finished audio directly behind the output mux (fmr_chain::ws_act).  The sample and
@@ -630,6 +657,7 @@ struct fmr_chain : ChainShape {
   OutputStage out;
   WeakSignalStage ws;
   MpxOutStage mpxo;
+  MpxInStage mpxi;
   BlankerStage nb;
   IqCorrectionStage iqc;
   int iqc_stage(const float2 *&d_iq, size_t &stride, long long N_in);
@@ -806,7 +834,7 @@ struct fmr_chain : ChainShape {
     return FMR_OK;
   }
   // create: the shape (plan_create), then the build from it, by stage in the order the call path uses them
-  int init(const fmr_config *c, bool channelizer = false);
+  int init(const fmr_config *c, bool channelizer = false, const fmr_mpx_input_config *mpx_in = nullptr);
   int open_device();
   int build_front_end();
   int build_stage_b(const std::vector<float> &fb);
@@ -965,6 +993,7 @@ struct fmr_chain : ChainShape {
   int run_tables(CallCtx &k);
   void fill_run_blocks(const CallCtx &k, int *blk0, const TileRuns &r, const int *tile0, long long kb_ref, int tile_len);
   int run_if_stage(CallCtx &k);
+  int mpxin_stage(CallCtx &k);
   int enqueue_agc(const AgcJob &j, hipEvent_t gate);
   void launch_fe_post(FePostJob &j);
   int run_fm(CallCtx &k);
@@ -1163,12 +1192,16 @@ static std::vector<double> deemph_powers(const Iir1Coef &d) {
   return apow;
 }
 
-int fmr_chain::init(const fmr_config *c, bool channelizer) {
+int fmr_chain::init(const fmr_config *c, bool channelizer, const fmr_mpx_input_config *mpx_in) {
   env.load();
   int rc;
-  if ((rc = plan_create(*this, c, env, channelizer))) return rc;      // (a refused configuration never opens the device)
+  if ((rc = plan_create(*this, c, env, channelizer, mpx_in))) return rc;      // (a refused configuration never opens the device)
   if ((rc = open_device())) return rc;
   if (has_rs && (rc = build_front_end())) return rc;
+  if (this->mpx_in) {      // nothing of the IF: no IQ input buffer, no IF buffers, no filter
+    if ((rc = build_stage(mpxi, S, max_in, mi_rate, mi_format, mi_gain)) || (rc = build_stats())) return rc;
+    return build_fm();
+  }
   if ((rc = d_in.alloc((size_t)in_rows() * max_in))) return rc;
   if ((rc = build_if_filter()) || (rc = build_stats())) return rc;
   if (!has_dec) return FMR_OK;
@@ -1317,9 +1350,11 @@ int fmr_chain::build_stats() {
   if ((rc = alloc_all(d_tab, (size_t)kTabSlots * tab_ints, d_flags, (size_t)S))) return rc;
   if (!has_dec) return FMR_OK;
   const size_t SB = (size_t)S * max_blocks;
-  if ((rc = alloc_all(d_agc_nodes, (size_t)S * (max_agc_nc + 1), d_agc_tick, (size_t)S, d_af_tick, (size_t)S,
+  if (!mpx_in &&      // (the IF AGC's buffers: an MPX input has no IF)
+      (rc = alloc_all(d_agc_nodes, (size_t)S * (max_agc_nc + 1), d_agc_tick, (size_t)S, d_af_tick, (size_t)S,
                       d_agc_G, (size_t)S * max_agc_nc, d_agc_M, (size_t)S * max_agc_nc, d_gain, (size_t)S * max_if,
-                      d_dec, (size_t)S * max_if, d_if_rms_blk, SB, d_bb_mean_blk, SB, d_bb_rms_blk, SB, d_blk_ph, SB * 2,
+                      d_blk_ph, SB * 2))) return rc;
+  if ((rc = alloc_all(d_dec, (size_t)S * max_if, d_if_rms_blk, SB, d_bb_mean_blk, SB, d_bb_rms_blk, SB,
                       d_mpf_ok, SB, d_stereo_blk, SB))) return rc;
   const bool tiled_epi = fe.poly5h_disc || fe.fir == IfForm::poly4_disc;
   if ((fe.fused != FusedFe::none || tiled_epi) && (rc = d_fused_part.alloc((size_t)S * 3 * (max_if / 384 + 20)))) return rc;
@@ -1494,7 +1529,7 @@ int fmr_chain::run(const float2 *d_iq, size_t stride, const uint32_t *block_len,
   hp1 = std::chrono::steady_clock::now();
   if (int rc = run_tables(k)) return rc;
   hp2 = std::chrono::steady_clock::now();
-  if (int rc = run_if_stage(k)) return rc;
+  if (int rc = mpx_in ? mpxin_stage(k) : run_if_stage(k)) return rc;
   if (int rc = (mode == FMR_MODE_FM) ? run_fm(k) : (mode == FMR_MODE_NBFM) ? run_nbfm(k) : run_am(k)) return rc;
   if (k.ht.n)      // (pipelined chain: the tail stage has taken the table with it, flush_tail)
     timed("shift_halo", [&] { hipLaunchKernelGGL(k_shift_halo<256>, dim3(k.ht.n, S), dim3(256), 0, stream, k.ht); });
@@ -1517,8 +1552,14 @@ int fmr_chain::plan_call(CallCtx &k) {
   k.N_if = 0;
   bool short_blk = false;      // a non-empty IF block shorter than 128 samples: the tiled forms' epilogues take none
   int tl = 4;
+  unsigned long long mi_f = mpxi.frames;      // MPX input: the count law over the frames, from a copy of the counter
   for (int b = 0; b < k.nb; b++) {
-    const int n = has_rs ? (int)p.next.advance(rs, k.block_len[b]) : (int)k.block_len[b];
+    int n;
+    if (mpx_in) {
+      n = (int)(mpxi.samples_after(mi_f + k.block_len[b]) - mpxi.samples_after(mi_f));
+      mi_f += k.block_len[b];
+    } else
+      n = has_rs ? (int)p.next.advance(rs, k.block_len[b]) : (int)k.block_len[b];
     k.tab.if_off[b] = (int)k.N_if;
     k.tab.if_len[b] = n;
     k.N_if += n;
@@ -1552,7 +1593,9 @@ int fmr_chain::plan_call(CallCtx &k) {
   // write before its tables, which are behind the lock logic on the same stream.  Not with one long stream: there the side
   // stream is as long as the step already, and five more launches on it hold the next call's tables back (0.517 -> 0.539).
   p.spare_aside = pipelined && !env.pll_v1 && k.nb <= (env.x_spare_aside >= 0 ? env.x_spare_aside : kSpareAsideMaxBlocks);
-  if (!has_rs) {
+  if (mpx_in) {
+    if ((size_t)N_if > max_if) { set_err("internal capacity exceeded"); return FMR_ERR_CAPACITY; }      // (StageA::none / StageB::none: mpxin_stage is the front end)
+  } else if (!has_rs) {
     p.a = StageA::pass;
   } else {
     if ((size_t)p.count_mid > max_mid || (size_t)N_if > max_if) { set_err("internal capacity exceeded"); return FMR_ERR_CAPACITY; }
@@ -1602,7 +1645,7 @@ int fmr_chain::plan_call(CallCtx &k) {
       }
     }
   }
-  if (has_dec && !(mode == FMR_MODE_FM && !fir_enable && !env.serial)) {
+  if (has_dec && !mpx_in && !(mode == FMR_MODE_FM && !fir_enable && !env.serial)) {
     // (FM without the IF FIR: the block RMS is taken inside the discriminator kernel, IfForm::none)
     p.TL = std::min(1024, tl);
     p.lds_fb = sizeof(float2) * (4 * (size_t)fm_block3_plane(ntaps - 1, p.TL) + ((size_t)ntaps + 4) / 2 + (size_t)(ntaps - 1) + p.TL);
@@ -1784,6 +1827,11 @@ int fmr_chain::run_front_end(CallCtx &k) {
         }
       });
     }
+  } else if (mpx_in) {      // (the PCM is read by mpxin_stage, behind the tables; there is no IF buffer)
+    k.ifbuf = nullptr;
+    last_if = nullptr;
+    if_valid = gain_valid = false;
+    dec_valid = true;
   } else {
     k.ifbuf = d_if.p;
     last_if = k.ifbuf;
@@ -2466,7 +2514,7 @@ int fmr_chain::run_fm(CallCtx &k) {
   if (agc_beside_mpf) HIPCHK(hipStreamWaitEvent(stream, ev_agc, 0));
   const long long base_stride = H_b + (long long)max_if;   // pre-de-emphasis buffers
   const long long de_stride = H_a + (long long)max_if;     // de-emphasised copies feeding the audio resampler
-  if (!p.b_disc && !p.fir_disc())     // (the fused front end's / the IF filter's discriminator epilogue has already written the MPX and the block statistics)
+  if (!p.b_disc && !p.fir_disc() && !mpx_in)     // (the fused front end's / the IF filter's discriminator epilogue, or the MPX input, has already written the MPX and the block statistics)
   timed("disc", [&] {
     hipLaunchKernelGGL((k_disc<256, fm_mpx_t>), dim3(nb, S), dim3(256), 0, stream, k.xin, k.x_stride, k.x_off, k.disc_gain,
                        (long long)max_if, k.any_mpf ? d_mpf.p : (float2 *)nullptr, (long long)max_if, d_mpf_ok.p, bt,
@@ -3448,6 +3496,95 @@ int fmr_chain::mpxout_stage(const fm_mpx_t *base, const MpxOutArgs &a, hipStream
   return FMR_OK;
 }
 
+// ---- MPX input (kernels_mpxin.hpp) ----
+int MpxInStage::init(int S, size_t max_in, int rate, int fmt, double gain_) {
+  std::vector<double> h;
+  MpxInGeom gm{1, 1, 1, 1, 0};
+  if (!design_mpx_rate(rate, gm.L, gm.M, gm.T, &h)) { set_err("fmr_create_mpx_decoder: rate %d has no design", rate); return FMR_ERR_BAD_ARG; }
+  gm.K = gm.T > 1 ? (int)(((long long)gm.T * gm.L + gm.M - 1) / gm.M) : 1;
+  gm.span = (int)(((long long)(kMpxInThreads - 1) * gm.L) / gm.M) + 1 + gm.K;
+  geom = gm; format = fmt; gain = gain_;
+  g = gm.T > 1 ? gain_ * ((double)gm.M / (double)gm.L) : gain_;
+  int rc;
+  if (gm.T > 1) {
+    std::vector<double> hp((size_t)gm.K * gm.M, 0.0);      // h[p + k M], zero from T L on
+    std::copy(h.begin(), h.end(), hp.begin());
+    if ((rc = upload(d_taps, hp.data(), hp.size()))) return rc;
+    if (gm.K > 1 && (rc = d_carry.alloc((size_t)2 * S * (gm.K - 1)))) return rc;      // (zeroed: z[i] = +0.0 for i < 0)
+  }
+  if (fmt == FMR_PCM_S16) {
+    std::vector<double> q(65536);
+    for (int v = -32768; v <= 32767; v++) q[(size_t)(v + 32768)] = (double)v / 32767.0;
+    if ((rc = upload(d_s16, q.data(), q.size()))) return rc;
+  }
+  if ((rc = d_tot.alloc((size_t)S))) return rc;
+  if ((rc = d_pcm.alloc((size_t)S * max_in * frame_bytes()))) return rc;
+  frames = samples = 0; par = 0;
+  on = true;
+  return FMR_OK;
+}
+
+// the positions of one call; advances the counters
+MpxInArgs MpxInStage::begin(long long n_frames) {
+  MpxInArgs a{};
+  a.f0 = frames; a.nf = (unsigned long long)n_frames;
+  frames += a.nf;
+  a.j0 = samples;
+  samples = samples_after(frames);
+  a.n = samples - a.j0;
+  a.g = g;
+  a.par = par;
+  if (a.nf > 0) par ^= 1;      // (a call without frames launches nothing: the carry stays where it is)
+  return a;
+}
+
+// The front end of an MPX-input chain, where run_if_stage and k_disc stand on an IQ chain: the call's PCM rows to its MPX
+// row and d_dec, the carry for the next call, then (behind the block table) the per-block baseband sums.
+int fmr_chain::mpxin_stage(CallCtx &k) {
+  const CallPlan &p = k.plan;
+  k.xin = nullptr; k.x_stride = 0; k.x_off = 0; k.disc_gain = nullptr;
+  k.agc_on_side = false; k.agc_deferred = false; agc_beside_mpf = false;
+  if (!p.iter_on_side)      // (FMR_SERIAL=1: the round flags are reset here, as run_if_stage does it)
+    hipLaunchKernelGGL(k_iter_begin, dim3(S), dim3(256), 0, stream, d_flags.p, (float *)nullptr, p.agc_nc, d_state.p, S,
+                       (unsigned long long *)d_pll_sync.p, (int)(sizeof(PllSync) / 8), d_pll_tick2.p, pll_tick2_per_stream,
+                       (unsigned int *)nullptr);
+  const MpxInArgs a = mpxi.begin(k.N_in);
+  if ((long long)a.n != k.N_if) { set_err("internal: the MPX input's count law and the block table disagree"); return FMR_ERR_HIP; }
+  static_assert(sizeof(fm_mpx_t) == sizeof(float), "the MPX input writes the MPX as floats");
+  float *x = reinterpret_cast<float *>(k.base);
+  const long long bstride = H_b + (long long)max_if;
+  const MpxInGeom &gm = mpxi.geom;
+  const bool f32 = mpxi.format == FMR_PCM_F32;
+  const void *pcm = k.d_iq;
+  const long long pstride = (long long)k.stride;
+  const dim3 grid((unsigned)((a.n + kMpxInThreads - 1) / kMpxInThreads), S);
+  if (gm.T == 1) {
+    timed("mpx_in_copy", [&] {
+      hipLaunchKernelGGL(f32 ? k_mpx_in_copy<1> : k_mpx_in_copy<0>, grid, dim3(kMpxInThreads), 0, stream, pcm, pstride,
+                         (const double *)mpxi.d_s16.p, a, x, bstride, H_b, d_dec.p, (long long)max_if, mpxi.d_tot.p);
+    });
+  } else {
+    timed("mpx_in_rate", [&] {
+      const size_t lds = (size_t)gm.span * sizeof(double) + (kMpxInThreads / 64) * sizeof(unsigned);
+      hipLaunchKernelGGL(f32 ? k_mpx_in_rate<1> : k_mpx_in_rate<0>, grid, dim3(kMpxInThreads), lds, stream, pcm, pstride,
+                         (const double *)mpxi.d_s16.p, (const double *)mpxi.d_carry.p, (const double *)mpxi.d_taps.p, gm, a, x, bstride, H_b, d_dec.p,
+                         (long long)max_if, mpxi.d_tot.p);
+    });
+    const int hist = gm.K - 1;
+    if (hist > 0)
+      timed("mpx_in_hist", [&] {
+        hipLaunchKernelGGL(f32 ? k_mpx_in_hist<1> : k_mpx_in_hist<0>, dim3((hist + kMpxInThreads - 1) / kMpxInThreads, S),
+                           dim3(kMpxInThreads), 0, stream, pcm, pstride, (const double *)mpxi.d_s16.p, mpxi.d_carry.p, hist, a);
+      });
+  }
+  timed("mpx_in_stats", [&] {      // (the decoder stream has waited for the block table: run_tables)
+    hipLaunchKernelGGL(k_mpx_in_stats, dim3(k.nb, S), dim3(kMpxInThreads), 0, stream, (const float *)x, bstride, H_b, k.bt,
+                       d_bb_mean_blk.p, d_bb_rms_blk.p, d_if_rms_blk.p);
+  });
+  HIPCHK(hipGetLastError());
+  return FMR_OK;
+}
+
 // the filled slots, in call order, through the host decoders (never blocks)
 void RdsStage::drain() {
   while (drained < seq && __atomic_load_n(h_mark.p, __ATOMIC_ACQUIRE) > drained) {
@@ -3922,7 +4059,8 @@ static int widen_config(const char *fn, const fmr_config *cfg, size_t cfg_size, 
   return FMR_OK;
 }
 
-static int create_chain(const fmr_config *cfg, fmr_chain **out, bool channelizer, bool rds = false) {
+static int create_chain(const fmr_config *cfg, fmr_chain **out, bool channelizer, bool rds = false,
+                        const fmr_mpx_input_config *mpx_in = nullptr) {
   if (!cfg || !out) return FMR_ERR_BAD_ARG;
   *out = nullptr;
   if (cfg->struct_size != 0 && cfg->struct_size != sizeof(fmr_config)) {
@@ -3931,7 +4069,7 @@ static int create_chain(const fmr_config *cfg, fmr_chain **out, bool channelizer
     return FMR_ERR_BAD_ARG;
   }
   fmr_chain *c = new fmr_chain();
-  int rc = c->init(cfg, channelizer);
+  int rc = c->init(cfg, channelizer, mpx_in);
   if (rc == FMR_OK && rds) rc = build_stage(c->rds, c->S, c->max_if);
   if (rc != FMR_OK) { delete c; return rc; }
   if (c->sync_all() != FMR_OK) { delete c; return FMR_ERR_HIP; }
@@ -4021,6 +4159,13 @@ int fmr_synchronize(fmr_chain *c) {
   return c->check_agc_sync();
 }
 
+// an MPX-input chain takes PCM through fmr_process_mpx_blocks* only
+static int refuse_mpx_chain(const char *fn, const fmr_chain *c) {
+  if (!c->mpx_in) return FMR_OK;
+  set_err("%s: the chain is an MPX decoder (fmr_create_mpx_decoder): it takes PCM frames through fmr_process_mpx_blocks / fmr_process_mpx_blocks_device", fn);
+  return FMR_ERR_BAD_ARG;
+}
+
 // how many IF samples per stream every block would produce (if_len[b]) and in all, from a copy of the resampler counter
 // (nothing is advanced)
 static size_t predict_if(const fmr_chain *c, const uint32_t *block_len, int nb, uint32_t *if_len) {
@@ -4038,8 +4183,14 @@ static size_t predict_if(const fmr_chain *c, const uint32_t *block_len, int nb, 
 static size_t predict_audio(const fmr_chain *c, const uint32_t *block_len, int nb) {
   ResamplerCounter r = c->rsc, ar = c->arsc;
   size_t total = 0;
+  unsigned long long mi_f = c->mpxi.frames;
   for (int b = 0; b < nb; b++) {
-    const long long n_if = c->has_rs ? r.advance(c->rs, block_len[b]) : (long long)block_len[b];
+    long long n_if;
+    if (c->mpx_in) {
+      n_if = (long long)(c->mpxi.samples_after(mi_f + block_len[b]) - c->mpxi.samples_after(mi_f));
+      mi_f += block_len[b];
+    } else
+      n_if = c->has_rs ? r.advance(c->rs, block_len[b]) : (long long)block_len[b];
     if (!c->has_dec || n_if == 0) continue;
     if (c->mode == FMR_MODE_FM) total += (size_t)ar.advance(c->ars, n_if) * (c->stereo ? 2 : 1);
     else total += (size_t)n_if;
@@ -4050,6 +4201,7 @@ static size_t predict_audio(const fmr_chain *c, const uint32_t *block_len, int n
 int fmr_process_blocks_device(fmr_chain *c, const float *d_iq, size_t stream_stride, const uint32_t *block_len,
                               int n_blocks, double *d_audio, size_t audio_stride, uint32_t *audio_len, int sync) {
   if (!c || !d_iq || !block_len || n_blocks < 1) return FMR_ERR_BAD_ARG;
+  if (int rc = refuse_mpx_chain("fmr_process_blocks_device", c)) return rc;
   try {
     if (c->has_dec) {
       if (!d_audio) { set_err("d_audio is null"); return FMR_ERR_BAD_ARG; }
@@ -4068,6 +4220,7 @@ int fmr_process_blocks_device(fmr_chain *c, const float *d_iq, size_t stream_str
 int fmr_process_blocks(fmr_chain *c, const float *iq, size_t stream_stride, const uint32_t *block_len, int n_blocks,
                        double *audio, size_t audio_stride, uint32_t *audio_len) {
   if (!c || !iq || !block_len || n_blocks < 1) return FMR_ERR_BAD_ARG;
+  if (int rc = refuse_mpx_chain("fmr_process_blocks", c)) return rc;
   try {
   size_t N_in = 0;
   for (int b = 0; b < n_blocks; b++) N_in += block_len[b];
@@ -4101,6 +4254,7 @@ int fmr_process_blocks(fmr_chain *c, const float *iq, size_t stream_stride, cons
 
 int fmr_fourth_convert(fmr_chain *c, const float *iq, size_t n, float *out_iq, int up, unsigned *index) {
   if (!c || !index || (n && (!iq || !out_iq))) return FMR_ERR_BAD_ARG;
+  if (int rc = refuse_mpx_chain("fmr_fourth_convert", c)) return rc;
   if (n == 0) return FMR_OK;
   if (n > c->max_in || c->in_fmt != 0) { set_err("fmr_fourth_convert: block longer than the chain's capacity, or raw-format chain"); return FMR_ERR_CAPACITY; }
   HIPCHK(hipSetDevice(c->cfg.device));
@@ -4116,6 +4270,7 @@ int fmr_fourth_convert(fmr_chain *c, const float *iq, size_t n, float *out_iq, i
 int fmr_process(fmr_chain *c, const float *iq, size_t n, double *audio, size_t audio_cap, size_t *n_audio) {
   if (!c || !n_audio) return FMR_ERR_BAD_ARG;
   *n_audio = 0;
+  if (int rc = refuse_mpx_chain("fmr_process", c)) return rc;
   if (c->bank && c->S > 1) {
     set_err("fmr_process: a channel bank of %d channels produces %d audio rows; use fmr_process_blocks", c->S, c->S);
     return FMR_ERR_BAD_ARG;
@@ -4129,6 +4284,7 @@ int fmr_process(fmr_chain *c, const float *iq, size_t n, double *audio, size_t a
 }
 
 int fmr_resample(fmr_chain *c, const float *iq, size_t n, float *out_iq, size_t out_cap, size_t *n_out) {
+  if (c) if (int rc = refuse_mpx_chain("fmr_resample", c)) return rc;
   if (!c || !n_out || !c->has_rs) return FMR_ERR_BAD_ARG;
   *n_out = 0;
   if (c->has_dec) { set_err("fmr_resample needs a chain created with mode -1 (front end only)"); return FMR_ERR_BAD_ARG; }
@@ -4156,6 +4312,7 @@ int fmr_resample(fmr_chain *c, const float *iq, size_t n, float *out_iq, size_t 
 static int check_resample_blocks(fmr_chain *c, const void *iq, size_t stream_stride, const uint32_t *block_len, int n_blocks,
                                  const void *out_iq, size_t out_stride, uint32_t *if_len, size_t *n_if) {
   if (!c || !iq || !block_len || n_blocks < 1 || !out_iq) return FMR_ERR_BAD_ARG;
+  if (int rc = refuse_mpx_chain("fmr_resample_blocks", c)) return rc;
   if (!c->has_rs || c->has_dec) {
     set_err("fmr_resample_blocks needs a front-end-only chain with the IF resampler (mode -1, enable_resampler)");
     return FMR_ERR_BAD_ARG;
@@ -4289,20 +4446,21 @@ int fmr_get_multipath_coefficients(fmr_chain *c, int stream, float *coeff, int c
 
 long long fmr_debug_live_resources(void) { return g_live.load(); }
 
-int fmr_debug_chain_shape(const fmr_config *cfg, size_t cfg_size, int channelizer, fmr_chain_shape_info *out, size_t out_size) {
-  if (!cfg || !out) { set_err("fmr_debug_chain_shape: cfg or out is NULL"); return FMR_ERR_BAD_ARG; }
+static int debug_chain_shape(const char *fn, const fmr_config *cfg, size_t cfg_size, int channelizer, const fmr_mpx_input_config *mpx_in,
+                             fmr_chain_shape_info *out, size_t out_size) {
+  if (!cfg || !out) { set_err("%s: cfg or out is NULL", fn); return FMR_ERR_BAD_ARG; }
   if ((out_size ? out_size : sizeof *out) > sizeof *out) {
-    set_err("fmr_debug_chain_shape: out_size %zu is larger than this library's fmr_chain_shape_info (%zu): the caller is newer than the library",
-            out_size, sizeof *out);
+    set_err("%s: out_size %zu is larger than this library's fmr_chain_shape_info (%zu): the caller is newer than the library",
+            fn, out_size, sizeof *out);
     return FMR_ERR_BAD_ARG;
   }
   fmr_config full;
-  if (int rc = widen_config("fmr_debug_chain_shape", cfg, cfg_size ? cfg_size : sizeof(fmr_config), &full)) return rc;
+  if (int rc = widen_config(fn, cfg, cfg_size ? cfg_size : sizeof(fmr_config), &full)) return rc;
   try {
     EnvKnobs env;
     env.load();
     ChainShape sh;
-    if (int rc = plan_create(sh, &full, env, channelizer != 0)) return rc;
+    if (int rc = plan_create(sh, &full, env, channelizer != 0, mpx_in)) return rc;
     fmr_chain_shape_info o{};
     o.struct_size = (unsigned)sizeof o;
     if (sh.has_rs) {
@@ -4313,9 +4471,14 @@ int fmr_debug_chain_shape(const fmr_config *cfg, size_t cfg_size, int channelize
     o.fir = sh.fe.fir == ChainShape::IfForm::poly4_disc ? 1 : sh.fe.fir == ChainShape::IfForm::poly4_finish ? 2 : 0;
     o.qa = sh.qa; o.pipelined = sh.pipelined;
     o.max_if = sh.max_if; o.max_au = sh.max_au;
+    if (sh.mpx_in) { o.mpx_in = 1; o.mpx_format = sh.mi_format; o.mpx_L = sh.mi_L; o.mpx_M = sh.mi_M; o.mpx_T = sh.mi_T; o.mpx_K = sh.mi_K; }
     give_sized(out, out_size, o);
     return FMR_OK;
   } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_debug_chain_shape(const fmr_config *cfg, size_t cfg_size, int channelizer, fmr_chain_shape_info *out, size_t out_size) {
+  return debug_chain_shape("fmr_debug_chain_shape", cfg, cfg_size, channelizer, nullptr, out, out_size);
 }
 
 long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t cap_bytes) {
@@ -4684,6 +4847,10 @@ int fmr_enable_output(fmr_chain *c, const fmr_output_config *cfg, size_t cfg_siz
     return FMR_ERR_BAD_ARG;
   }
   if (!c) { set_err("fmr_enable_output: chain is null"); return FMR_ERR_BAD_ARG; }
+  if (c->mpx_in && m.squelch_level != 0.0) {
+    set_err("fmr_enable_output: squelch_level %g on an MPX decoder: the squelch gates on the IF level, and a chain fed composite PCM has no IF (squelch_level must be 0)", m.squelch_level);
+    return FMR_ERR_UNSUPPORTED;
+  }
   if (!c->has_dec) {
     set_err("fmr_enable_output: a front-end-only chain (mode -1: channelizer / IfResampler) has no audio");
     return FMR_ERR_UNSUPPORTED;
@@ -4924,6 +5091,143 @@ int fmr_mpx_output_taps(int rate, double *taps, int cap, int *L, int *M, int *T)
   return (int)n;
 }
 
+// ---- MPX input: C-ABI ----
+// cfg and in as this library knows them, from the caller's sizes
+static int take_mpx_input(const char *fn, const fmr_config *cfg, size_t cfg_size, const fmr_mpx_input_config *in, size_t in_size,
+                          fmr_config &full, fmr_mpx_input_config &m) {
+  if (!cfg) { set_err("%s: cfg is null", fn); return FMR_ERR_BAD_ARG; }
+  if (!in) { set_err("%s: in is null", fn); return FMR_ERR_BAD_ARG; }
+  if (int rc = widen_config(fn, cfg, cfg_size ? cfg_size : sizeof(fmr_config), &full)) return rc;
+  return take_sized(fn, "fmr_mpx_input_config", in, in_size, m);
+}
+
+int fmr_create_mpx_decoder(const fmr_config *cfg, size_t cfg_size, const fmr_mpx_input_config *in, size_t in_size, fmr_chain **out) {
+  const char *fn = "fmr_create_mpx_decoder";
+  if (!out) { set_err("%s: out is null", fn); return FMR_ERR_BAD_ARG; }
+  *out = nullptr;
+  fmr_config full;
+  fmr_mpx_input_config m;
+  if (int rc = take_mpx_input(fn, cfg, cfg_size, in, in_size, full, m)) return rc;
+  return create_chain(&full, out, false, m.rds == 1, &m);
+}
+
+int fmr_debug_mpx_chain_shape(const fmr_config *cfg, size_t cfg_size, const fmr_mpx_input_config *in, size_t in_size,
+                              fmr_chain_shape_info *out, size_t out_size) {
+  const char *fn = "fmr_debug_mpx_chain_shape";
+  fmr_config full;
+  fmr_mpx_input_config m;
+  if (int rc = take_mpx_input(fn, cfg, cfg_size, in, in_size, full, m)) return rc;
+  return debug_chain_shape(fn, &full, sizeof full, 0, &m, out, out_size);
+}
+
+// what both process entry points check before anything is enqueued or any counter moves
+static int check_mpx_blocks(const char *fn, fmr_chain *c, const void *pcm, const uint32_t *block_len, int n_blocks, size_t *n_frames) {
+  if (!c || !pcm || !block_len || n_blocks < 1) { set_err("%s: chain, pcm or block_len is null, or n_blocks < 1", fn); return FMR_ERR_BAD_ARG; }
+  if (!c->mpx_in) {
+    set_err("%s: the chain takes IQ (fmr_process_blocks): only a chain made by fmr_create_mpx_decoder takes PCM frames", fn);
+    return FMR_ERR_BAD_ARG;
+  }
+  size_t N = 0;
+  for (int b = 0; b < n_blocks; b++) N += block_len[b];
+  *n_frames = N;
+  return FMR_OK;
+}
+
+int fmr_process_mpx_blocks_device(fmr_chain *c, const void *d_pcm, size_t stream_stride, const uint32_t *block_len,
+                                  int n_blocks, double *d_audio, size_t audio_stride, uint32_t *audio_len, int sync) {
+  const char *fn = "fmr_process_mpx_blocks_device";
+  size_t N_in = 0;
+  if (int rc = check_mpx_blocks(fn, c, d_pcm, block_len, n_blocks, &N_in)) return rc;
+  try {
+    if (!d_audio) { set_err("%s: d_audio is null", fn); return FMR_ERR_BAD_ARG; }
+    if ((stream_stride * c->mpxi.frame_bytes()) % 16 != 0 || ((uintptr_t)d_pcm % 16) != 0) {
+      set_err("%s: the PCM rows and the stream stride must be 16-byte aligned", fn);
+      return FMR_ERR_BAD_ARG;
+    }
+    if (c->S > 1 && stream_stride < N_in) { set_err("%s: stream_stride %zu is shorter than the %zu frames of a row", fn, stream_stride, N_in); return FMR_ERR_BAD_ARG; }
+    if (n_blocks <= c->max_blocks && predict_audio(c, block_len, n_blocks) > audio_stride) {
+      set_err("audio_stride too small for the audio these blocks produce (nothing was processed)");
+      return FMR_ERR_CAPACITY;
+    }
+    const int rc = c->run_cold_aware((const float2 *)d_pcm, stream_stride, block_len, n_blocks, d_audio, audio_stride, audio_len);
+    if (rc) return rc;
+    if (sync) return c->sync_all();
+    return FMR_OK;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_process_mpx_blocks(fmr_chain *c, const void *pcm, size_t stream_stride, const uint32_t *block_len, int n_blocks,
+                           double *audio, size_t audio_stride, uint32_t *audio_len) {
+  const char *fn = "fmr_process_mpx_blocks";
+  size_t N_in = 0;
+  if (int rc = check_mpx_blocks(fn, c, pcm, block_len, n_blocks, &N_in)) return rc;
+  try {
+    if (N_in > c->max_in) { set_err("input longer than max_block_len*max_blocks"); return FMR_ERR_CAPACITY; }
+    if (c->S > 1 && stream_stride < N_in) { set_err("%s: stream_stride %zu is shorter than the %zu frames of a row", fn, stream_stride, N_in); return FMR_ERR_BAD_ARG; }
+    if (n_blocks <= c->max_blocks && audio) {
+      const size_t need = predict_audio(c, block_len, n_blocks);
+      if (need > audio_stride) { set_err("audio capacity %zu too small: these blocks produce %zu doubles (nothing was processed)", audio_stride, need); return FMR_ERR_CAPACITY; }
+    }
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t fb = c->mpxi.frame_bytes();
+    if (N_in)
+      HIPCHK(hipMemcpy2DAsync(c->mpxi.d_pcm.p, fb * c->max_in, pcm, fb * stream_stride, fb * N_in, (size_t)c->S, hipMemcpyHostToDevice, c->stream));
+    const size_t dstride = c->stereo ? 2 * c->max_au : c->max_au;
+    std::vector<uint32_t> alen(n_blocks, 0);
+    const int rc = c->run_cold_aware(reinterpret_cast<const float2 *>(c->mpxi.d_pcm.p), c->max_in, block_len, n_blocks, c->d_audio.p, dstride, alen.data());
+    if (rc) return rc;
+    size_t total = 0;
+    for (int b = 0; b < n_blocks; b++) { total += alen[b]; if (audio_len) audio_len[b] = alen[b]; }
+    if (total && audio) {
+      if (total > audio_stride) { set_err("audio capacity too small"); return FMR_ERR_CAPACITY; }
+      HIPCHK(hipMemcpy2DAsync(audio, sizeof(double) * audio_stride, c->d_audio.p, sizeof(double) * dstride, sizeof(double) * total, c->S,
+                              hipMemcpyDeviceToHost, c->stream));
+    }
+    return c->sync_all();
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+int fmr_mpx_input_geometry(int rate, int *L, int *M, int *T, int *K, double *delay_samples) {
+  if (rate == 0) rate = kMpxRateIn;
+  if (int rc = check_mpx_rate("fmr_mpx_input_geometry", rate)) return rc;
+  int l, m, t;
+  design_mpx_rate(rate, l, m, t, nullptr);
+  if (L) *L = l;
+  if (M) *M = m;
+  if (T) *T = t;
+  if (K) *K = t > 1 ? mpx_in_taps_per_sample(l, m, t) : 1;
+  if (delay_samples) *delay_samples = t > 1 ? ((double)t * l - 1.0) / (2.0 * l) : 0.0;
+  return FMR_OK;
+}
+
+int fmr_get_mpx_input_info(fmr_chain *c, int stream, fmr_mpx_input_info *info, size_t info_size) {
+  const char *fn = "fmr_get_mpx_input_info";
+  if (!c || !info || stream < 0 || stream >= c->S) { set_err("%s: bad chain, info or stream", fn); return FMR_ERR_BAD_ARG; }
+  if (!c->mpx_in) { set_err("%s: the chain is not an MPX decoder (fmr_create_mpx_decoder)", fn); return FMR_ERR_BAD_ARG; }
+  if ((info_size ? info_size : sizeof(fmr_mpx_input_info)) > sizeof(fmr_mpx_input_info)) {
+    set_err("%s: info_size %zu is larger than this library's fmr_mpx_input_info (%zu): the caller is newer than the library", fn, info_size,
+            sizeof(fmr_mpx_input_info));
+    return FMR_ERR_BAD_ARG;
+  }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    const MpxInStage &st = c->mpxi;
+    fmr_mpx_input_info full{};
+    full.struct_size = (unsigned)sizeof full;
+    full.format = st.format; full.rate = c->mi_rate;
+    full.L = st.geom.L; full.M = st.geom.M; full.taps_per_phase = st.geom.T; full.taps_per_sample = st.geom.K;
+    full.delay_samples = st.geom.T > 1 ? ((double)st.geom.T * st.geom.L - 1.0) / (2.0 * st.geom.L) : 0.0;
+    full.full_scale_hz = 75000.0 * st.gain;
+    full.frames_in = st.frames; full.samples_out = st.samples;
+    unsigned long long tot = 0;
+    HIPCHK(hipMemcpy(&tot, st.d_tot.p + stream, sizeof tot, hipMemcpyDeviceToHost));
+    full.nonfinite_in = tot;
+    give_sized(info, info_size, full);
+    return FMR_OK;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
 // ---- weak-signal handling: C-ABI ----
 int fmr_enable_weak_signal(fmr_chain *c, const fmr_weak_signal_config *cfg, size_t cfg_size) {
   const char *fn = "fmr_enable_weak_signal";
@@ -5078,6 +5382,10 @@ int fmr_enable_blanker(fmr_chain *c, const fmr_blanker_config *cfg, size_t cfg_s
     return FMR_ERR_BAD_ARG;
   }
   if (!c) { set_err("%s: chain is null", fn); return FMR_ERR_BAD_ARG; }
+  if (c->mpx_in) {
+    set_err("%s: the blanker works on an IQ capture; an MPX decoder (fmr_create_mpx_decoder) is fed composite PCM", fn);
+    return FMR_ERR_UNSUPPORTED;
+  }
   if (c->in_fmt != 0) {
     set_err("%s: the blanker reads complex float samples (FMR_IQ_CF32); this chain takes a raw input format", fn);
     return FMR_ERR_UNSUPPORTED;
@@ -5183,6 +5491,10 @@ int fmr_enable_iq_correction(fmr_chain *c, const fmr_iq_correction_config *cfg, 
     return FMR_ERR_BAD_ARG;
   }
   if (!c) { set_err("%s: chain is null", fn); return FMR_ERR_BAD_ARG; }
+  if (c->mpx_in) {
+    set_err("%s: the IQ corrector works on an IQ capture; an MPX decoder (fmr_create_mpx_decoder) is fed composite PCM", fn);
+    return FMR_ERR_UNSUPPORTED;
+  }
   if (c->in_fmt != 0) {
     set_err("%s: the IQ corrector reads complex float samples (FMR_IQ_CF32); this chain takes a raw input format", fn);
     return FMR_ERR_UNSUPPORTED;
@@ -5615,6 +5927,10 @@ int fmr_enable_rf_monitor(fmr_chain *c, const fmr_rf_monitor_config *cfg, size_t
     return FMR_ERR_BAD_ARG;
   }
   if (!c) { set_err("fmr_enable_rf_monitor: chain is null"); return FMR_ERR_BAD_ARG; }
+  if (c->mpx_in) {
+    set_err("fmr_enable_rf_monitor: the RF monitor reads the IF samples in front of the discriminator; an MPX decoder (fmr_create_mpx_decoder) is fed composite PCM and has none");
+    return FMR_ERR_UNSUPPORTED;
+  }
   if (c->mode != FMR_MODE_FM) {
     set_err("fmr_enable_rf_monitor: the RF monitor reads the decoder input of an FM chain (mode FMR_MODE_FM); mode %d %s", c->mode,
             c->mode == FMR_MODE_NONE ? "is a front-end-only chain (channelizer / IfResampler): it has no decoder" : "is not measured");

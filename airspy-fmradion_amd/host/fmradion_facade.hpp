@@ -827,6 +827,102 @@ private:
   std::vector<std::complex<float>> m_coeff;
 };
 
+// MpxDecoder (no counterpart in the reference; fmr_create_mpx_decoder): FmDecoder's decoder behind a composite input -- an
+// MPX archive (MpxFileReader, fmradion_fileio.hpp), a stereo generator's output from a 192 kHz sound card -- as mono
+// FMR_PCM_S16 / FMR_PCM_F32 frames at `rate` (0 = 384000).  gain 0 = 2.0, the inverse of the MPX output's default.  It has
+// the getters of FmDecoder that still have a meaning: there is no IF level, no equaliser.
+class MpxDecoder {
+public:
+  MpxDecoder(int rate, int format, bool stereo, double deemphasis = FmDecoder::deemphasis_time_eu, bool pilot_shift = false,
+             double gain = 0.0, bool rds = false, int device = 0)
+      : m_format(format) {
+    fmr_config cfg{};
+    cfg.struct_size = sizeof cfg;
+    cfg.device = device; cfg.n_streams = 1; cfg.mode = FMR_MODE_FM; cfg.stereo = stereo; cfg.deemphasis_us = deemphasis;
+    cfg.pilot_shift = pilot_shift; cfg.max_block_len = 65536; cfg.max_blocks = 1;
+    fmr_mpx_input_config in{};
+    in.struct_size = sizeof in; in.format = format; in.rate = rate; in.gain = gain; in.rds = rds ? 1 : 0;
+    fmr_detail::check(fmr_create_mpx_decoder(&cfg, sizeof cfg, &in, sizeof in, &m_chain), "fmr_create_mpx_decoder");
+  }
+  ~MpxDecoder() { fmr_destroy(m_chain); }
+  MpxDecoder(const MpxDecoder &) = delete;
+  MpxDecoder &operator=(const MpxDecoder &) = delete;
+
+  // one block of frames (at most 65536) in, interleaved audio out; the vector's type must be the decoder's format
+  void process(const std::vector<float> &frames, SampleVector &audio) {
+    if (m_format != FMR_PCM_F32) fmr_detail::fail("MpxDecoder::process(float): the decoder was made for FMR_PCM_S16");
+    run(frames.data(), frames.size(), audio);
+  }
+  void process(const std::vector<int16_t> &frames, SampleVector &audio) {
+    if (m_format != FMR_PCM_S16) fmr_detail::fail("MpxDecoder::process(int16_t): the decoder was made for FMR_PCM_F32");
+    run(frames.data(), frames.size(), audio);
+  }
+  fmr_mpx_input_info input_info() {
+    fmr_mpx_input_info i{};
+    fmr_detail::check(fmr_get_mpx_input_info(m_chain, 0, &i, sizeof i), "fmr_get_mpx_input_info");
+    return i;
+  }
+  bool stereo_detected() { return status().stereo_detected != 0; }
+  float get_tuning_offset() { return status().baseband_mean * (float)FmDecoder::freq_dev; }
+  float get_baseband_level() { return status().baseband_level; }
+  double get_pilot_level() { return status().pilot_level; }
+  // events of the most recent process() call
+  std::vector<PilotPhaseLock::PpsEvent> get_pps_events() {
+    fmr_pps_event ev[64];
+    const int n = fmr_get_pps_events(m_chain, 0, ev, 64);
+    std::vector<PilotPhaseLock::PpsEvent> out;
+    for (int i = 0; i < n && i < 64; i++) out.push_back({ev[i].pps_index, ev[i].sample_index, ev[i].block_position});
+    return out;
+  }
+  // with rds = true: as FmDecoder's
+  void set_rds_correction(int mode, int max_burst = 0, int soft_symbols = 0, double soft_max_cost = 0.0) {
+    fmr_detail::rds_correction(m_chain, mode, max_burst, soft_symbols, soft_max_cost);
+  }
+  std::vector<fmr_rds_group> get_rds_groups() { return fmr_detail::rds_groups(m_chain, 0, m_station); }
+  const fmr_rds::Station &rds_station() { get_rds_groups(); return m_station; }
+  // the stages an MPX decoder accepts, as FmDecoder's (before the first process(), once each)
+  void enable_modulation_monitor(uint32_t interval_samples = 0, int hist_bins = 0, double hist_range = 0.0, int max_records = 0) {
+    fmr_monitor_config m{};
+    m.struct_size = sizeof m; m.interval_samples = interval_samples; m.hist_bins = hist_bins; m.hist_range = hist_range;
+    m.max_records = max_records;
+    fmr_detail::monitor(m_chain, m);
+  }
+  std::vector<ModulationRecord> read_modulation_records() { return fmr_detail::monitor_records(m_chain, 0); }
+  void enable_loudness(uint32_t step_samples = 0, int max_records = 0) {
+    fmr_loudness_config m{};
+    m.struct_size = sizeof m; m.step_samples = step_samples; m.max_records = max_records;
+    fmr_detail::loudness(m_chain, m);
+  }
+  LoudnessReport read_loudness(double silence_dbfs = -60.0) { return fmr_detail::loudness_report(m_chain, 0, silence_dbfs); }
+  void enable_output(int format = FMR_PCM_S16, double gain = 0.0, uint32_t max_frames = 0, uint32_t max_blocks = 0, int rate = 0,
+                     bool mono = false) {      // (no squelch: there is no IF level)
+    fmr_detail::output(m_chain, fmr_detail::output_config(format, 0.0, gain, max_frames, max_blocks), fmr_detail::output_rate_config(rate, mono));
+  }
+  OutputData read_output() { return fmr_detail::output_data(m_chain, 0); }
+  void enable_mpx_output(int format = FMR_PCM_S16, int rate = 192000, double gain = 0.0, uint32_t max_frames = 0) {
+    fmr_detail::mpx_output(m_chain, fmr_detail::mpx_output_config(format, rate, gain, max_frames));
+  }
+  MpxOutputData read_mpx_output() { return fmr_detail::mpx_output_data(m_chain, 0); }
+
+private:
+  fmr_status status() {
+    fmr_status st{};
+    fmr_detail::check(fmr_get_status(m_chain, 0, &st), "fmr_get_status");
+    return st;
+  }
+  void run(const void *frames, size_t n, SampleVector &audio) {
+    audio.clear();
+    if (n == 0) return;
+    audio.resize(n + 128);      // (at most 4 MPX samples per frame, 2 doubles per 8 of them)
+    uint32_t bl = (uint32_t)n, al = 0;
+    fmr_detail::check(fmr_process_mpx_blocks(m_chain, frames, n, &bl, 1, audio.data(), audio.size(), &al), "fmr_process_mpx_blocks");
+    audio.resize(al);
+  }
+  fmr_chain *m_chain = nullptr;
+  int m_format;
+  fmr_rds::Station m_station;
+};
+
 // AmDecoder (AmDecode.h:48-65), all of its modes: AM, DSB, USB, LSB, CW, WSPR
 class AmDecoder {
 public:

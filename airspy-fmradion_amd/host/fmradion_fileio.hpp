@@ -15,6 +15,8 @@
 //                   IEEE float32 frames of 2 channels (I = ch 0, Q = ch 1), the samples' bits as they are; the header is
 //                   valid from the start and refreshed as the data grow, as AudioFileWriter's.  For the IQ rows of a
 //                   Channelizer (fmradion_facade.hpp), to be replayed through the reference's -t filesource.
+//   MpxFileReader   a composite (MPX) archive for the MPX decoder (fmr_create_mpx_decoder, MpxDecoder): a mono WAV / RF64 of
+//                   int16 or IEEE float32 frames as AudioFileWriter writes them; rate, format and the frames as they are.
 //   adjust_gain     the -6 dB of main.cpp:1000-1002;  pps_line: the PPS text record of main.cpp:1084-1111.
 //
 // Host-side plumbing only: nothing here touches the GPU; the decoders take the blocks these classes deliver.
@@ -299,6 +301,92 @@ public:
 
 private:
   AudioFileWriter m_w;
+};
+
+// A composite (MPX) archive: a mono WAV / RF64 of int16 or IEEE float32 frames, of the kind AudioFileWriter writes from the
+// frames of the MPX output (fmr_enable_mpx_output) or a sound card records from a stereo generator.  It delivers the rate,
+// the format and the frames as they are in the file -- the conversion is the MPX decoder's (MpxDecoder,
+// fmr_create_mpx_decoder).  A data size of 0 or 0xFFFFFFFF (a recorder that was killed) reads to the end of the file.
+class MpxFileReader {
+public:
+  ~MpxFileReader() { close(); }
+  bool open(const std::string &path) {
+    close();
+    m_fp = std::fopen(path.c_str(), "rb");
+    if (!m_fp) { m_error = "Failed to open " + path; return false; }
+    if (parse(path)) return true;
+    close();
+    return false;
+  }
+  void close() { if (m_fp) std::fclose(m_fp); m_fp = nullptr; }
+  uint32_t sample_rate() const { return m_rate; }
+  bool is_float() const { return m_float; }      // false: int16 frames (FMR_PCM_S16), true: float32 (FMR_PCM_F32)
+  const std::string &error() const { return m_error; }
+  // up to n frames of an int16 / a float32 file; false at the end of the data or for the other format
+  bool read_i16(std::vector<int16_t> &frames, size_t n) { return !m_float && read_frames(frames, n); }
+  bool read_f32(std::vector<float> &frames, size_t n) { return m_float && read_frames(frames, n); }
+
+private:
+  static uint32_t rd32(const unsigned char *p) { return p[0] | p[1] << 8 | p[2] << 16 | (uint32_t)p[3] << 24; }
+  template <class T>
+  bool read_frames(std::vector<T> &frames, size_t n) {
+    frames.clear();
+    if (!m_fp || n == 0) return false;
+    uint64_t want = (uint64_t)n * sizeof(T);
+    if (want > m_left) want = m_left - (m_left % sizeof(T));
+    frames.resize((size_t)(want / sizeof(T)));
+    const size_t got = want ? std::fread(frames.data(), sizeof(T), frames.size(), m_fp) : 0;      // (little-endian hosts, as the writer)
+    frames.resize(got);
+    if (m_left != UINT64_MAX) m_left -= (uint64_t)got * sizeof(T);
+    return got > 0;
+  }
+  bool parse(const std::string &path) {
+    unsigned char h[12];
+    if (std::fread(h, 1, 12, m_fp) != 12 || (std::memcmp(h, "RIFF", 4) && std::memcmp(h, "RF64", 4)) || std::memcmp(h + 8, "WAVE", 4)) {
+      m_error = "Unsupported major format " + path;
+      return false;
+    }
+    const bool rf64 = !std::memcmp(h, "RF64", 4);
+    uint64_t data64 = 0;
+    bool have_fmt = false;
+    for (;;) {
+      unsigned char ck[8];
+      if (std::fread(ck, 1, 8, m_fp) != 8) { m_error = "no data chunk in " + path; return false; }
+      const uint64_t size = rd32(ck + 4);
+      if (!std::memcmp(ck, "data", 4)) {
+        if (!have_fmt) { m_error = "data chunk before fmt chunk"; return false; }
+        m_left = (rf64 && size == 0xFFFFFFFFu) ? data64 : size;
+        if (m_left == 0 || (!rf64 && size == 0xFFFFFFFFu)) m_left = UINT64_MAX;
+        return true;
+      }
+      const bool keep = !std::memcmp(ck, "ds64", 4) || !std::memcmp(ck, "fmt ", 4);
+      if (!keep) {
+        if (std::fseek(m_fp, (long)(size + (size & 1)), SEEK_CUR)) { m_error = "truncated file"; return false; }
+        continue;
+      }
+      if (size < 16 || size > 4096) { m_error = "bad header chunk"; return false; }      // sizes come from an untrusted header
+      std::vector<unsigned char> b((size_t)(size + (size & 1)));
+      if (std::fread(b.data(), 1, b.size(), m_fp) != b.size()) { m_error = "bad header chunk"; return false; }
+      if (!std::memcmp(ck, "ds64", 4)) {
+        data64 = (uint64_t)rd32(b.data() + 8) | (uint64_t)rd32(b.data() + 12) << 32;
+        continue;
+      }
+      unsigned tag = b[0] | b[1] << 8;
+      const unsigned channels = b[2] | b[3] << 8, bits = b[14] | b[15] << 8;
+      m_rate = rd32(b.data() + 4);
+      if (tag == 0xFFFE && size >= 26) tag = b[24] | b[25] << 8;          // WAVE_FORMAT_EXTENSIBLE: sub-format GUID
+      if (channels != 1) { m_error = "MPX files have one channel"; return false; }
+      if (tag == 1 && bits == 16) m_float = false;
+      else if (tag == 3 && bits == 32) m_float = true;
+      else { m_error = "Unsupported sub type in " + path; return false; }
+      have_fmt = true;
+    }
+  }
+  std::FILE *m_fp = nullptr;
+  uint32_t m_rate = 0;
+  bool m_float = false;
+  uint64_t m_left = UINT64_MAX;
+  std::string m_error;
 };
 
 // Utility::adjust_gain (include/Utility.h), used at main.cpp:1000-1002 with 0.5 (squelch open) or 0.0

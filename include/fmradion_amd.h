@@ -339,6 +339,8 @@ typedef struct fmr_chain_shape_info {
   int qa;                     /* taps per phase of k_ifr_decim2: 16, 24, or 0 (the generic stage A) */
   int pipelined;              /* the stages of consecutive calls run beside each other */
   unsigned long long max_if, max_au;   /* capacity per stream and call: IF samples, audio samples per channel */
+  int mpx_in;                 /* 1: the MPX-input form (fmr_debug_mpx_chain_shape): no IF, the front end reads PCM; max_if counts MPX samples */
+  int mpx_format, mpx_L, mpx_M, mpx_T, mpx_K;   /* ... its PCM format and geometry (all 0 otherwise) */
 } fmr_chain_shape_info;
 int fmr_debug_chain_shape(const fmr_config *cfg, size_t cfg_size, int channelizer, fmr_chain_shape_info *out, size_t out_size);
 
@@ -1404,6 +1406,80 @@ int fmr_mpx_output_read(fmr_chain *c, int stream, void *pcm, size_t cap_frames, 
  * fmr_output_rate_taps.  rate 384000 (or 0) gives the single tap 1.0.  FMR_ERR_BAD_ARG for a rate fmr_enable_mpx_output
  * refuses. */
 int fmr_mpx_output_taps(int rate, double *taps, int cap, int *L, int *M, int *T);
+
+/* --- MPX input: an FM chain that is fed composite baseband -- an MPX archive written through
+ * fmr_enable_mpx_output, a stereo generator's output sampled by a 192 kHz sound card, another receiver's MPX -- as mono PCM
+ * at rate = 384000 L / M instead of IQ.  Its front end brings the PCM to the 384 kHz MPX; from there on it is the FM chain:
+ * pilot PLL, stereo decode, audio tail, and with rds = 1 the RDS decoder of fmr_create_rds.  There is no IF: no resampler,
+ * no IF AGC, no discriminator.
+ * Definition, per stream, over the frames since create; nothing depends on blocks or calls:
+ *   L / M = rate / 384000 in lowest terms; h is the prototype of fmr_mpx_output_taps(rate): T L taps at rate 384000 L,
+ *   sum h = L.
+ *   Frame i gives u[i].  FMR_PCM_S16: (double)v / 32767.0, one fp64 division.  FMR_PCM_F32: (double)v; a non-finite value
+ *   becomes +0.0 and counts in nonfinite_in.
+ *   z[i] = u[i] g', g' = gain ((double)M / (double)L), formed once on the host.  z[i] = +0.0 for i < 0.
+ *   MPX sample j = 0, 1, ... takes i0 = floor(j L / M), p = j L - i0 M and acc = 0.0; for k = 0, 1, ... ascending while
+ *   p + k M < T L: acc = acc + h[p + k M] z[i0 - k] -- at most K = ceil(T L / M) terms, every product and every sum rounded
+ *   by itself in fp64 (no fused multiply-add).  x[j] = (float)acc, round to nearest even.
+ *   Sample j exists as soon as u[i0] does: after F frames the chain has taken ceil(F M / L) MPX samples, and a block yields
+ *   the difference of that count across it (this can be 0; such a block behaves as a block without IF samples does on an
+ *   IQ chain).  Group delay: (T L - 1) / (2 L) MPX samples.
+ *   At rate 384000 there is no filter: x[j] = (float)(u[j] gain).
+ * x stands where the discriminator output stands on an IQ chain; 1.0 means 75 kHz deviation.  With gain 1.0 at 384000 F32
+ * the chain reproduces, bit for bit, the audio, PPS events and RDS groups of the IQ chain whose fmr_enable_mpx_output ring
+ * (384000, F32, gain 1.0) it is fed.
+ * fmr_status: if_rms = 0, if_agc_gain = 1, agc_iterations = agc_fallback = 0, the multipath fields 0; baseband_mean /
+ * baseband_level are formed as on an IQ chain (the same sums in the same order); everything else as on an FM chain.
+ * fmr_debug_read: tap 1 is the MPX of the most recent call, taps 2 and 3 as on an FM chain, tap 5 as on an RDS chain when
+ * rds = 1; taps 0, 4, 6 and 7 are FMR_ERR_BAD_ARG.
+ * Accepted stages: fmr_enable_monitor, _loudness, _analyser, _weak_signal, _mpx_output, and _output with
+ * squelch_level == 0.  FMR_ERR_UNSUPPORTED: fmr_enable_output with a squelch level (there is no IF level to gate on),
+ * fmr_enable_rf_monitor, fmr_enable_blanker, fmr_enable_iq_correction.  fmr_process* and fmr_resample* on such a chain are
+ * FMR_ERR_BAD_ARG, and so are fmr_process_mpx_blocks* on any other chain. */
+typedef struct {
+  unsigned struct_size;   /* as the other configs: 0 = in_size; larger than the library's is refused */
+  int format;             /* FMR_PCM_S16 or FMR_PCM_F32 */
+  int rate;               /* 0 or 384000: MPX as it is; else a rate fmr_enable_mpx_output accepts (96000 <= rate < 384000,
+                             rate / gcd(rate, 384000) <= 160) */
+  double gain;            /* finite, > 0; 0 = 2.0, the inverse of the MPX output's default 0.5 */
+  int rds;                /* 1: with the RDS decoder, as fmr_create_rds */
+} fmr_mpx_input_config;
+typedef struct {
+  unsigned struct_size;
+  int format, rate;
+  int L, M, taps_per_phase;      /* rate / 384000 = L / M in lowest terms; T (1 without a filter) */
+  int taps_per_sample;           /* K = ceil(T L / M) (1 without a filter) */
+  double delay_samples;          /* group delay in MPX samples: (T L - 1) / (2 L); 0 without a filter */
+  double full_scale_hz;          /* the deviation that PCM 1.0 (S16: 32767) stands for: 75000 gain */
+  uint64_t frames_in;            /* PCM frames taken since create */
+  uint64_t samples_out;          /* MPX samples made of them: ceil(frames_in M / L) */
+  uint64_t nonfinite_in;         /* of this stream since create: F32 frames that were NaN or +-Inf (taken as +0.0) */
+} fmr_mpx_input_info;
+/* cfg: mode = FMR_MODE_FM and enable_resampler = 0 are required; n_streams, stereo, deemphasis_us, pilot_shift,
+ * max_block_len and max_blocks (in frames), device and struct_size are honoured; input_rate must be 0 or the PCM rate;
+ * filter_coeff is not needed.  FMR_ERR_UNSUPPORTED for another mode, fmfilter_enable, multipath_stages > 0,
+ * input_format != FMR_IQ_CF32 and enable_fourth_down; FMR_ERR_BAD_ARG for enable_resampler, channel_offset_hz, and a bad
+ * format, rate or gain (fmr_last_error names the field).  Every refusal is made before the device is opened.  The chain
+ * is in-order.  cfg_size / in_size: the sizes of the structs as the caller knows them, 0 = this header's. */
+int fmr_create_mpx_decoder(const fmr_config *cfg, size_t cfg_size, const fmr_mpx_input_config *in, size_t in_size, fmr_chain **out);
+/* pcm holds n_streams rows of stream_stride mono frames of the chain's format; block_len is in frames.  Otherwise the
+ * contract of fmr_process_blocks: audio rows of audio_stride doubles, audio_len[b] the doubles block b produced, the
+ * capacity checked before any state advances. */
+int fmr_process_mpx_blocks(fmr_chain *c, const void *pcm, size_t stream_stride, const uint32_t *block_len, int n_blocks,
+                           double *audio, size_t audio_stride, uint32_t *audio_len);
+/* The contract of fmr_process_blocks_device; the device rows and their stride (in bytes) are 16-byte aligned, as for the
+ * raw IQ formats. */
+int fmr_process_mpx_blocks_device(fmr_chain *c, const void *d_pcm, size_t stream_stride, const uint32_t *block_len,
+                                  int n_blocks, double *d_audio, size_t audio_stride, uint32_t *audio_len, int sync);
+/* Synchronises like the other getters.  FMR_ERR_BAD_ARG for a bad stream, a chain that is not an MPX decoder, and an
+ * info_size larger than this library's struct (0 = this header's size). */
+int fmr_get_mpx_input_info(fmr_chain *c, int stream, fmr_mpx_input_info *info, size_t info_size);
+/* Host only, no device: L, M, T, K and the group delay in MPX samples of `rate` (each may be NULL).  rate 384000 (or 0)
+ * gives 1, 1, 1, 1 and 0.  FMR_ERR_BAD_ARG for a rate fmr_enable_mpx_output refuses. */
+int fmr_mpx_input_geometry(int rate, int *L, int *M, int *T, int *K, double *delay_samples);
+/* fmr_debug_chain_shape for fmr_create_mpx_decoder: what that create would decide, or its refusal.  No device. */
+int fmr_debug_mpx_chain_shape(const fmr_config *cfg, size_t cfg_size, const fmr_mpx_input_config *in, size_t in_size,
+                              fmr_chain_shape_info *out, size_t out_size);
 
 #ifdef __cplusplus
 }
