@@ -506,6 +506,8 @@ struct EnvKnobs {
   bool debug_taps = false;      // FMR_DEBUG_TAPS=1   keep intermediate signals readable through fmr_debug_read
   bool host_prof = false;       // FMR_HOST_PROF=1    host enqueue time per call on stderr
   bool no_fused = false;        // FMR_NO_FUSED=1     three-kernel front end, 384 k -> 48 k stage B on the vector ALUs (tests: the product against the form it replaced)
+  bool x_pll_chain_head = false; // FMR_X_PLL_CHAIN_HEAD=1  the PLL's second pass runs its down-sweep as two chains of 32 steps, not as a descent
+                                //                    through the Jacobian pass's tree (tests and A/B runs: the product against the form it replaced)
 #ifdef FMR_AB_PARTNERS          // (libfmradion_amd_ab.so only: the slower forms two GPU tests compare the product with, and a test hook)
   bool pll_v1 = false;          // FMR_PLL_V1         seven launches per Newton round of the PLL instead of three: no hand-off
                                 //                    between workgroups inside a launch (tests: bit-equality stress test)
@@ -532,7 +534,7 @@ struct EnvKnobs {
     serial = on("FMR_SERIAL"); debug_taps = on("FMR_DEBUG_TAPS");
     auto num = [](const char *n, int dflt) { const char *e = getenv(n); return (e && e[0]) ? atoi(e) : dflt; };
     pipeline = num("FMR_PIPELINE", -1); fe_cus = num("FMR_FE_CUS", 0);
-    host_prof = on("FMR_HOST_PROF"); no_fused = on("FMR_NO_FUSED");
+    host_prof = on("FMR_HOST_PROF"); no_fused = on("FMR_NO_FUSED"); x_pll_chain_head = on("FMR_X_PLL_CHAIN_HEAD");
     fe_stamps = on("FMR_FE_STAMPS"); evt_markers = on("FMR_EVT_MARKERS");
 #ifdef FMR_AB_PARTNERS
     test_agc_late = num("FMR_TEST_AGC_LATE", 0); pll_v1 = set("FMR_PLL_V1");
@@ -566,7 +568,7 @@ struct fmr_chain : ChainShape {
   bool if_valid = true;                 // the IF samples of the last call are in last_if (false: the fused front end's discriminator epilogue kept them on chip and stored |x|^2 there)
   bool gain_valid = true;               // the per-sample AGC gains of the last call are in d_gain (fmr_debug_read 4)
   DevBuf<double> d_de_pow;
-  DevBuf<double> d_pll_wgr, d_pll_pre;
+  DevBuf<double> d_pll_wgr, d_pll_pre, d_pll_te;
   DevBuf<PllSync> d_pll_sync;
   DevBuf<unsigned int> d_pll_tick2;
   int pll_jac_rounds = 1;                // rounds that re-integrate the sensitivities
@@ -1385,6 +1387,7 @@ int fmr_chain::build_fm() {
                       d_pll_PQ, (size_t)S * max_grp * 56, d_pll_dstart, (size_t)S * max_grp * 7, d_pll_gres, (size_t)S * max_grp * 8,
                       d_pll_wgr, (size_t)S * waves * 8,      // (x 8: room for the FMR_PLL_TRACE records)
                       d_pll_PQ2, (size_t)S * max_grp2 * 56, d_pll_dstart2, (size_t)S * max_grp2 * 7, d_pll_pre, (size_t)S * max_grp * 56,
+                      d_pll_te, (size_t)S * max_grp * FMR_TREE_SINK * FMR_MAP,      // (17 MB at 2^27 samples a call)
                       d_pll_wfirst, (size_t)S * waves * 7, d_pll_sync, (size_t)S,      // (zeroed here; the kernels leave it zeroed)
                       d_pll_tick2, (size_t)S * max_grp2, d_ck_mask, ck_copy * mask_words * copies,
                       d_blk_wraps, SB, d_blk_level, SB))) return rc;
@@ -2364,12 +2367,16 @@ int fmr_chain::run_fm_pll(CallCtx &k, TailCtx &t) {
         // The pass that integrates the Jacobians composes them in its own tail (the node pass's up-sweep: k_pll_up's work
         // without its launch and without reading 31 MB of Jacobians back), see k_pll_shoot
         const bool up_in_shoot = sy != nullptr && it < pll_jac_rounds && it + 1 < pll_iters;
-        const PllUpArgs upa = up_in_shoot ? PllUpArgs{d_pll_PQ.p, d_pll_pre.p, d_pll_PQ2.p, ngrp, ngrp2, d_pll_dstart2.p, d_pll_sync.p, d_pll_tick2.p}
+        const PllUpArgs upa = up_in_shoot ? PllUpArgs{d_pll_PQ.p, d_pll_pre.p, d_pll_PQ2.p, ngrp, ngrp2, d_pll_dstart2.p, d_pll_sync.p, d_pll_tick2.p, d_pll_te.p}
                                           : PllUpArgs{};
         // ... and every later pass runs the down-sweep of the node pass before it in its own head (k_pll_down's work without
         // its launch): a round is two launches, integration + up-sweep kernel (the first round: one)
         const bool down_in_shoot = sy != nullptr && it > 0;
-        const PllDownArgs dna = down_in_shoot ? PllDownArgs{d_pll_pre.p, d_pll_dstart2.p, ngrp, ngrp2, pllc.minfreq, pllc.maxfreq, d_pll_wfirst.p}
+        // Right behind the Jacobian round the sweep is a descent through that round's tree; a chord round's mismatches are
+        // new, the tree's composites are not: it keeps the chain, behind k_pll_up
+        const bool descend = down_in_shoot && it == pll_jac_rounds && !env.x_pll_chain_head;
+        const PllDownArgs dna = down_in_shoot ? PllDownArgs{d_pll_pre.p, d_pll_dstart2.p, ngrp, ngrp2, pllc.minfreq, pllc.maxfreq, d_pll_wfirst.p,
+                                                            descend ? d_pll_te.p : (const double *)nullptr}
                                               : PllDownArgs{};
         auto shoot = [&](auto kern) {
           sub(ps, it == 0 ? "pll_shoot_jac" : "pll_shoot", [&] {

@@ -1086,11 +1086,17 @@ __device__ __forceinline__ void pll_round_check(IterFlags &F, PllSync &Y, double
 #define FMR_NODE_GRP2 32   // level-1 groups per level-2 group
 // The up-sweep of the node pass from a group's Jacobians and mismatches in LDS (defined with the node pass below): the
 // integration pass that has just computed them runs it in its own tail (round 5), k_pll_up stages them from HBM first.
-struct PllUpArgs { double *PQ, *PRE, *PQ2; int ngrp, ngrp2; double *dstart2; PllSync *sync; unsigned int *tick2; };
+// TE: the composites of the tree's inner nodes' earlier halves (pll_compose_tree's sink), FMR_TREE_SINK maps per group: the
+// tail of the Jacobian pass leaves them, the head of the pass behind it descends through them (pll_descend_tree).
+struct PllUpArgs { double *PQ, *PRE, *PQ2; int ngrp, ngrp2; double *dstart2; PllSync *sync; unsigned int *tick2; double *TE; };
 // ... and the down-sweep of the node pass in the HEAD of the pass that integrates from its result (pll_down_group).
-struct PllDownArgs { const double *PRE, *dstart2; int ngrp, ngrp2; double minfreq, maxfreq; const double *wave_first; };
+// TE != null: as a descent through the Jacobian pass's tree (the pass right behind it); null: the chain (chord rounds, whose
+// mismatches are no longer the ones the stored composites were made from).
+struct PllDownArgs { const double *PRE, *dstart2; int ngrp, ngrp2; double minfreq, maxfreq; const double *wave_first; const double *TE; };
 __device__ __forceinline__ void pll_down_group(const PllDownArgs &dn, double *nodes_s, const double *g, const double *m, int nck, int s, int grp,
                                                PllSync *sync, double *sm, double *sr, double *so, double *first, int lane);
+__device__ __forceinline__ void pll_descend_head(const PllDownArgs &dn, double *nd, const double *g, const double *m, int nck, int s,
+                                                 PllSync *sync, double *xs, int lane, double (&sv)[7], double (&nxt)[7]);
 __device__ __forceinline__ void pll_up_from_lds(const PllUpArgs &u, int s, int grp, int n, double *sm, double *sh, int lane);
 __device__ __forceinline__ void pll_up_levels23(const PllUpArgs &u, int s, int grp, double val, double *sm, double *sh, int lane);
 __device__ __forceinline__ void pll_stage_group(const double *__restrict__ m, const double *__restrict__ g, const double *__restrict__ nd,
@@ -1166,7 +1172,11 @@ __global__ __launch_bounds__(64) void k_pll_shoot(const fm_mpx_t *__restrict__ b
   double rmax = 0.0;
   PllRegs S;
   double nxt[7];                             // start node of the NEXT chunk (the boundary mismatch at the end)
-  if (!JAC && dn.PRE) {
+  if (!JAC && dn.PRE && dn.TE) {
+    // ---- the node pass's down-sweep behind a Jacobian round: a descent through that round's tree (pll_descend_head)
+    pll_descend_head(dn, const_cast<double *>(nodes) + (long long)s * (ct.nck + 1) * 7, G + (long long)s * ct.nck * 9,
+                     M + (long long)s * ct.nck * 49, ct.nck, s, sync, xs, lane, S.v, nxt);
+  } else if (!JAC && dn.PRE) {
     // ---- the node pass's down-sweep for this wave's two groups of 32 chunks, here: k_pll_down was a launch of its own
     // (26 us + a launch gap) whose every workgroup did 32 dependent 7 x 7 steps and went away.  A wave needs the new start
     // nodes of ITS chunks only: those of chunks c0 + 1 .. from its own two sweeps, that of its first chunk from the group's
@@ -1331,7 +1341,8 @@ __global__ __launch_bounds__(64) void k_pll_shoot(const fm_mpx_t *__restrict__ b
         if (q < ng * 49) mg[q] = xs[r * FMR_MAP + er * 8 + (e - er * 7)];
       }
       if (up.PQ) {
-        pll_compose_tree<64>(xs, ng, lane, [] { __syncthreads(); });
+        pll_compose_tree<64>(xs, ng, lane, [] { __syncthreads(); },
+                             up.TE ? up.TE + ((long long)s * up.ngrp + grp) * (FMR_TREE_SINK * FMR_MAP) : nullptr);
         const double val = lane < FMR_MAP ? xs[lane] : 0.0;        // lane i * 8 + k: P[i][k], k == 7: q[i]
         if (h == 0) pq0 = val; else pq1 = val;
       }
@@ -1881,6 +1892,128 @@ __device__ __forceinline__ void pll_down_group(const PllDownArgs &dn, double *nd
   for (int idx = i; idx < (c1 - c0) * 7; idx += 64) nd[(long long)(c0 + 1) * 7 + idx] = so[idx];
   // ~40 groups share a slot: same-address atomics from all the groups would serialise in L2
   if (act) atomicMax(&sync[s].dslot[grp & 63][i], pll_max_bits(resid));
+}
+
+// The same down-sweep for a wave's two groups at once, as a descent through the tree the Jacobian pass composed them with
+// (pll_descend_tree, pll_compose.hpp): five dependent levels instead of two chains of 32 steps, both groups in the same
+// rounds (a half-wave each, 28 of its 32 lanes a row of a node).  Lane l owns the node BEHIND its chunk, w0 + l + 1, as the
+// chain's groups do: it reads the old one (which no other wave of this launch writes), adds the delta, stores it and keeps it
+// as nxt; its own start node is its neighbour's nxt, lane 0's the wave's first (old from wave_first, as in the chain).
+// The deltas at the starts of the wave's groups and of the group behind it come from PRE x dstart2; at the call's end there
+// is no group behind, and the last chunk's own map gives the end node's delta (one step, one wave of the launch).
+// xs: the sample tile.  Staged in two turns: the tree's composites (2 x 15 maps), then the even chunks' maps [M | r] (32).
+__device__ __forceinline__ void pll_descend_head(const PllDownArgs &dn, double *nd, const double *g, const double *m, int nck, int s,
+                                                 PllSync *sync, double *xs, int lane, double (&sv)[7], double (&nxt)[7]) {
+  constexpr int GW = FMR_TREE_SINK * FMR_MAP;            // a group's composites
+  constexpr int LFW = FMR_NODE_GRP * FMR_MAP;            // the maps of the wave's 32 even chunks
+  constexpr int NU = (2 * GW + 63) / 64, NM = (32 * 49 + 63) / 64, NR = (32 * 7 + 63) / 64;
+  static_assert(FMR_NODE_GRP == FMR_TREE_MAXN && 2 * GW <= LFW, "the composites are staged where the even chunks' maps follow");
+  double *const de = xs + LFW;                           // [33][7]: deltas at the starts of chunks 0, 2, .. 64 of the wave
+  const int w0 = blockIdx.x * 64, nw = min(64, nck - w0), g0 = 2 * blockIdx.x;
+  const int half = lane >> 5, l5 = lane & 31;
+  const bool valid = lane < nw, at_end = w0 + nw == nck;
+  const double two_pi = 2.0 * 3.14159265358979323846, inv_two_pi = 1.0 / two_pi;
+  // ---- everything the head reads from memory, in flight together
+  const int nup = min(2, dn.ngrp - g0) * GW;
+  const double *te = dn.TE + ((long long)s * dn.ngrp + g0) * GW;
+  double tu[NU];
+#pragma unroll
+  for (int u = 0; u < NU; u++) { const int idx = lane + 64 * u; tu[u] = idx < nup ? te[idx] : 0.0; }
+  // start deltas of groups g0, g0 + 1 and g0 + 2: lane G * 8 + i, the chain's expression
+  const int G = lane >> 3, gi = lane & 7;
+  const bool gact = G < 3 && gi < 7 && g0 + G < dn.ngrp;
+  double pr[8], dv[7];
+  {
+    const int grp = gact ? g0 + G : g0;
+    const double *pre = dn.PRE + (((long long)s * dn.ngrp + grp) * 7 + (gact ? gi : 0)) * 8;
+    const double *d2 = dn.dstart2 + ((long long)s * dn.ngrp2 + grp / FMR_NODE_GRP2) * 7;
+#pragma unroll
+    for (int q = 0; q < 8; q++) pr[q] = pre[q];
+#pragma unroll
+    for (int q = 0; q < 7; q++) dv[q] = d2[q];
+  }
+  double on[7], old0[7], er[8];
+  const double *ndn = nd + (long long)(w0 + (valid ? lane : 0) + 1) * 7;
+  const double *wf = dn.wave_first + ((long long)s * gridDim.x + blockIdx.x) * 7;
+#pragma unroll
+  for (int k = 0; k < 7; k++) { on[k] = ndn[k]; old0[k] = wf[k]; }
+  const int c0g = min(w0 + 32 * half, nck - 1);          // scale of the biquad delays: the (I,Q) delay pair at the group's start
+  const double wm = fabs(g[(long long)c0g * 9 + 3]) + fabs(g[(long long)c0g * 9 + 5]);
+  const int ei = lane < 7 ? lane : 0;
+  if (at_end) {                                          // the last chunk's map, row per lane
+#pragma unroll
+    for (int j = 0; j < 7; j++) er[j] = m[(long long)(nck - 1) * 49 + ei * 7 + j];
+    er[7] = pll_mismatch(g, nd, nck - 1, ei);
+  }
+  // ---- upper levels
+#pragma unroll
+  for (int u = 0; u < NU; u++) { const int idx = lane + 64 * u; if (idx < 2 * GW) xs[idx] = tu[u]; }
+  if (gact)
+    de[G * 16 * 7 + gi] = fma(pr[0], dv[0], fma(pr[1], dv[1], pr[7])) + (fma(pr[2], dv[2], pr[3] * dv[3]) +
+                          fma(pr[4], dv[4], fma(pr[5], dv[5], pr[6] * dv[6])));
+  double tm[NM], tr[NR];
+  // (the even chunks' maps are asked for once the composites have left the registers: with both held the pass is over 256)
+#pragma unroll
+  for (int u = 0; u < NM; u++) {
+    const int q = lane + 64 * u, p = q / 49, c = w0 + 2 * p;
+    tm[u] = (q < 32 * 49 && c < nck) ? m[(long long)c * 49 + (q - 49 * p)] : 0.0;
+  }
+#pragma unroll
+  for (int u = 0; u < NR; u++) {
+    const int q = lane + 64 * u, p = q / 7, c = w0 + 2 * p;
+    tr[u] = (q < 32 * 7 && c < nck) ? pll_mismatch(g, nd, c, q - 7 * p) : 0.0;
+  }
+  __syncthreads();
+  const int nh = max(0, min(32, nw - 32 * half));
+  pll_descend_upper<32>(xs + half * GW, de + half * 16 * 7, nh, l5, [] { __syncthreads(); });
+  // ---- leaves: the composites give way to the even chunks' maps (the last barrier above is behind every read of them)
+#pragma unroll
+  for (int u = 0; u < NM; u++) {
+    const int q = lane + 64 * u, p = q / 49, e = q - 49 * p, er_ = e / 7;
+    if (q < 32 * 49) xs[p * FMR_MAP + er_ * 8 + (e - 7 * er_)] = tm[u];
+  }
+#pragma unroll
+  for (int u = 0; u < NR; u++) {
+    const int q = lane + 64 * u, p = q / 7;
+    if (q < 32 * 7) xs[p * FMR_MAP + (q - 7 * p) * 8 + 7] = tr[u];
+  }
+  __syncthreads();
+  pll_descend_leaves<32>(xs + half * 16 * FMR_MAP, de + half * 16 * 7, nh, l5, [] { __syncthreads(); });
+  if (at_end) {                                          // the end node's delta: where the delta of chunk nw would stand
+    if (lane < 7) {
+      double acc = er[7];
+#pragma unroll
+      for (int j = 0; j < 7; j++) acc = fma(er[j], pll_descend_delta(xs, de, nw - 1, j), acc);
+      if (nw & 1) xs[(nw >> 1) * FMR_MAP + lane * 8 + 7] = acc; else de[(nw >> 1) * 7 + lane] = acc;
+    }
+    __syncthreads();
+  }
+  // ---- every lane: the node behind its chunk
+  auto fix = [&](int k, double nv) {
+    if (k == 0) {                             // keep the phase inside (0, 2 pi] like the reference
+      nv -= two_pi * floor(nv * inv_two_pi);
+      if (nv <= 0.0) nv += two_pi;
+    }
+    if (k == 1) nv = fmax(dn.minfreq, fmin(dn.maxfreq, nv));   // the true freq never leaves the clamp range
+    return nv;
+  };
+  const double wsc = 1.0 / (1e-7 * (wm + 1.0));
+  double resid[7];
+#pragma unroll
+  for (int k = 0; k < 7; k++) {
+    const double d = valid ? pll_descend_delta(xs, de, lane + 1, k) : 0.0;
+    nxt[k] = valid ? fix(k, on[k] + d) : 0.0;
+    resid[k] = wave_max_d(fabs(d) * (k == 0 ? 1e7 : k == 1 ? 1e9 : k == 2 ? 1e5 : wsc));
+    if (valid) nd[(long long)(w0 + lane + 1) * 7 + k] = nxt[k];
+    const double first = blockIdx.x == 0 ? old0[k] : fix(k, old0[k] + de[k]);      // (chunk 0 starts from the carried state: fixed)
+    const double prev = __shfl_up(nxt[k], 1, 64);
+    sv[k] = !valid ? 0.0 : lane == 0 ? first : prev;
+  }
+  // residual maxima: one slot row per wave (pll_round_check takes the maximum over all of them)
+  double rk = 0.0;
+#pragma unroll
+  for (int k = 0; k < 7; k++) if (lane == k) rk = resid[k];
+  if (lane < 7) atomicMax(&sync[s].dslot[blockIdx.x & 63][lane], pll_max_bits(rk));
 }
 
 // initial node guess: nominal ramp from the carried state
