@@ -428,62 +428,65 @@ struct WeakSignalStage {
   }
 };
 
-// Impulse blanker on the capture (fmr_enable_blanker; kernels_blanker.hpp).  It runs at the head of a
-// call on the decoder stream, where CallCtx receives the input (fmr_chain::nb_stage): the level and the apply kernel in front
-// of the front end, the records on the side stream behind an event.  The sample counter lives here and is taken when a call
-// is issued.  In FMR_NB_ACT the call's readers get the blanked rows instead of the caller's: two row buffers by call parity,
-// because a reader of call N's rows (the input history, on the side stream of an in_order chain) may still be pending when
-// call N + 1 is blanked; it is done before call N + 1's front end, which call N + 2's blanker follows on the same stream.
-// The parts of a call are kept twice as well: the records kernel of call N reads them beside call N + 1, and call N + 2 waits
-// for that kernel's event before it writes them again.
-struct BlankerStage {
-  bool on = false;
-  fmr_blanker_config cfg{};                  // the defaults filled in
-  NbCoef coef{};
-  int rows = 0, pmax = 0, aring = 0;         // input rows, pieces of a call at most, ring of A per row (2^k)
+// What the two stages on the capture share (the impulse blanker and the IQ corrector below; DESIGN.md sections 17 and 18).
+// Such a stage runs at the head of a call on the decoder stream, where CallCtx receives the input, its records kernel on
+// the side stream behind an event of the stage's own.  It counts in absolute input samples per row (n), cut into intervals
+// of kNbQ.  When it acts, the call's readers get its rows instead of the caller's: two row buffers by call parity, because
+// a reader of call N's rows (the input history, on the side stream of an in_order chain) may still be pending when call
+// N + 1 is written; it is done before call N + 1's front end, which the stage's call N + 2 follows on the same stream.
+// The parts of a call are kept twice as well (by the stage: their type is its own): the records kernel of call N reads
+// them beside call N + 1, and call N + 2 waits for that kernel's event (ev_rec) before it writes them again.
+// A call is begin(), the stage's kernels with out_rows() where it writes rows, and finish().
+struct CaptureStage {
+  bool on = false, act = false;              // act: the stage rewrites the rows (FMR_NB_ACT / FMR_IQC_ACT)
+  int rows = 0, pmax = 0;                    // input rows, pieces of a call at most
+  int record_intervals = 1;
   size_t pitch = 0;                          // samples between the rows of a row buffer (one more under an odd caller's stride)
   long long n = 0;                           // samples handed in per row
   unsigned long long calls = 0;              // calls that brought samples
-  const float2 *last_rows = nullptr; long long last_stride = 0, last_n = 0;    // FMR_NB_ACT: what the last call's front end read
+  const float2 *last_rows = nullptr; long long last_stride = 0, last_n = 0;    // acting: the rows the last call wrote
+  DevBuf<float2> d_rows[2];
+  Event ev_rec[2];
+  RecCursor cur;
+  // one call: its samples [n0, n1) of every row, the intervals they touch, the parity of its parts and rows, the rows it writes
+  struct Call { long long n0 = 0, n1 = 0; int pieces = 0, par = 0; float2 *out = nullptr; long long ostride = 0; };
+  unsigned long long intervals() const { return (unsigned long long)(n / kNbQ); }
+  unsigned long long done() const { return intervals() / (unsigned long long)record_intervals; }   // records complete
+  int init(int rows_, size_t max_in, bool act_, int record_intervals_, int max_records);
+  int begin(Call &k, const char *noun, long long N_in, hipStream_t stream);
+  void out_rows(Call &k, const float2 *d_iq, size_t stride) const;
+  int finish(const Call &k, hipStream_t side, const float2 *&d_iq, size_t &stride);
+};
+
+// Impulse blanker on the capture (fmr_enable_blanker; kernels_blanker.hpp), fmr_chain::nb_stage: the
+// level and the apply kernel in front of the front end, the records on the side stream behind ev_apply.
+struct BlankerStage : CaptureStage {
+  fmr_blanker_config cfg{};                  // the defaults filled in
+  NbCoef coef{};
+  int aring = 0;                             // ring of A per row (2^k)
   DevBuf<NbPart> d_part;                     // [2][rows][pmax]
   DevBuf<unsigned long long> d_aring;        // [rows][aring]
   DevBuf<unsigned char> d_carry;             // [2][rows][G + M]
   DevBuf<NbState> d_state;
   DevBuf<NbRec> d_ring;
-  DevBuf<float2> d_rows[2];
-  Event ev_apply, ev_rec[2];
-  RecCursor cur;
-  unsigned long long intervals() const { return (unsigned long long)(n / kNbQ); }
-  unsigned long long done() const { return intervals() / (unsigned long long)cfg.record_intervals; }   // records complete
+  Event ev_apply;
   int init(int rows_, size_t max_in, const fmr_blanker_config &m);
 };
 
-// DC-offset and IQ-imbalance correction on the capture (fmr_enable_iq_correction; kernels_iqcorr.hpp).
-// The second stage of the blanker's kind, and in front of it (fmr_chain::iqc_stage): moments, coefficients and, in
-// FMR_IQC_ACT, the apply kernel on the decoder stream, the records on the side stream behind an event.  The corrected rows
-// live in two buffers by call parity with the blanker's argument: a reader of call N's rows may still be pending when call
-// N + 1 is corrected, and is done before call N + 1's front end, which call N + 2's corrector follows on the same stream.
-// The parts of a call are kept twice as well, for the records kernel that reads them beside the next call.
-struct IqCorrectionStage {
-  bool on = false;
+// DC-offset and IQ-imbalance correction on the capture (fmr_enable_iq_correction; kernels_iqcorr.hpp),
+// in front of the blanker (fmr_chain::iqc_stage): moments, coefficients and, in FMR_IQC_ACT, the apply kernel on the decoder
+// stream, the records on the side stream behind ev_coef.
+struct IqCorrectionStage : CaptureStage {
   fmr_iq_correction_config cfg{};            // the defaults filled in
   IqcCoef coef{};
-  int rows = 0, pmax = 0, tring = 0;         // input rows, pieces of a call at most, ring of running totals per row (2^k)
+  int tring = 0;                             // ring of running totals per row (2^k)
   int tiles() const { return (pmax + kIqcCoefT - 1) / kIqcCoefT; }
-  size_t pitch = 0;                          // samples between the rows of a row buffer (one more under an odd caller's stride)
-  long long n = 0;                           // samples handed in per row
-  unsigned long long calls = 0;              // calls that brought samples
-  const float2 *last_rows = nullptr; long long last_stride = 0, last_n = 0;    // FMR_IQC_ACT: what the last call wrote
   DevBuf<IqcPart> d_part;                    // [2][rows][pmax]
   DevBuf<IqcSum> d_tot;                      // [rows][tiles][(kIqcBack + 1) kIqcCoefT + 1]: the running totals a k_iqc_coef workgroup forms
   DevBuf<IqcSum> d_tring;                    // [rows][tring]
   DevBuf<IqcState> d_state;
   DevBuf<IqcRec> d_ring;
-  DevBuf<float2> d_rows[2];
-  Event ev_coef, ev_rec[2];
-  RecCursor cur;
-  unsigned long long intervals() const { return (unsigned long long)(n / kNbQ); }
-  unsigned long long done() const { return intervals() / (unsigned long long)cfg.record_intervals; }   // records complete
+  Event ev_coef;
   int init(int rows_, size_t max_in, const fmr_iq_correction_config &m);
 };
 
@@ -3124,34 +3127,72 @@ int fmr_chain::ws_act(double *d_aud, long long astride, const WsArgs &a, hipStre
   return FMR_OK;
 }
 
+// ---- the capture stages' common part ----
+int CaptureStage::init(int rows_, size_t max_in, bool act_, int record_intervals_, int max_records) {
+  rows = rows_; act = act_; record_intervals = record_intervals_;
+  pmax = (int)(max_in / kNbQ + 2);       // a call touches its whole intervals and one more at either end
+  pitch = (max_in + 1) & ~(size_t)1;
+  int rc;
+  if (act)      // (a row may start one sample in, to sit on the caller's 16-byte phase, and be one sample further apart)
+    for (DevBuf<float2> &b : d_rows) if ((rc = b.alloc((size_t)rows * (pitch + 1) + 2))) return rc;
+  for (Event &e : ev_rec) if ((rc = e.create(hipEventDisableTiming))) return rc;
+  cur.reset(rows, max_records);
+  n = 0; calls = 0;
+  return FMR_OK;
+}
+
+// The call's samples, pieces and parity; from the third call on the stream waits for the records kernel of two calls ago,
+// which read the parts this call writes.
+int CaptureStage::begin(Call &k, const char *noun, long long N_in, hipStream_t stream) {
+  k.n0 = n; k.n1 = n + N_in;
+  k.pieces = (int)((k.n1 - 1) / kNbQ - k.n0 / kNbQ + 1);
+  if (k.pieces > pmax) { set_err("internal: a call of %lld input samples has more intervals than %s holds", N_in, noun); return FMR_ERR_CAPACITY; }
+  n = k.n1;
+  k.par = (int)(++calls & 1);
+  if (calls > 2) HIPCHK(hipStreamWaitEvent(stream, ev_rec[k.par], 0));
+  return FMR_OK;
+}
+
+// The rows an acting stage writes in this call: the same 16-byte phase as the caller's rows, row by row, so that the front
+// end picks the forms it would have.  None when the stage only measures.
+void CaptureStage::out_rows(Call &k, const float2 *d_iq, size_t stride) const {
+  if (!act) return;
+  k.ostride = (long long)(pitch + (stride & 1));
+  k.out = d_rows[k.par].p + (((uintptr_t)d_iq >> 3) & 1);
+}
+
+// Behind the records kernel on the side stream; an acting stage's rows then stand for the caller's.
+int CaptureStage::finish(const Call &k, hipStream_t side, const float2 *&d_iq, size_t &stride) {
+  HIPCHK(hipEventRecord(ev_rec[k.par], side));
+  HIPCHK(hipGetLastError());
+  if (act) {
+    d_iq = k.out; stride = (size_t)k.ostride;
+    last_rows = k.out; last_stride = k.ostride; last_n = k.n1 - k.n0;
+  }
+  return FMR_OK;
+}
+
 // ---- impulse blanker (kernels_blanker.hpp) ----
 int BlankerStage::init(int rows_, size_t max_in, const fmr_blanker_config &m) {
   static_assert(sizeof(NbRec) == sizeof(fmr_blanker_record), "NbRec is fmr_blanker_record");
   static_assert(offsetof(NbRec, threshold) == offsetof(fmr_blanker_record, threshold) &&
                 offsetof(NbRec, peak) == offsetof(fmr_blanker_record, peak), "the fields of a record");
   cfg = m;
-  rows = rows_;
   coef.G = m.gate_samples; coef.M = m.max_run_samples; coef.W = m.average_intervals; coef.R = m.record_intervals;
   coef.L = m.max_records; coef.act = m.mode == FMR_NB_ACT;
   coef.g = std::pow(10.0, m.threshold_db / 10.0);
   coef.r[0] = 0.0;
   for (int c = 1; c <= kNbMaxW; c++) coef.r[c] = 1.0 / ((double)c * 281474976710656.0);
-  pmax = (int)(max_in / kNbQ + 2);       // a call touches its whole intervals and one more at either end
+  int rc;
+  if ((rc = CaptureStage::init(rows_, max_in, coef.act, m.record_intervals, m.max_records))) return rc;
   aring = 64;
   while (aring < pmax + m.average_intervals + 2) aring <<= 1;
-  pitch = (max_in + 1) & ~(size_t)1;
-  int rc;
   if ((rc = d_part.alloc((size_t)2 * rows * pmax))) return rc;
   if ((rc = d_aring.alloc((size_t)rows * aring))) return rc;
   if ((rc = d_carry.alloc((size_t)2 * rows * (coef.G + coef.M)))) return rc;
   if ((rc = d_state.alloc((size_t)rows))) return rc;
   if ((rc = d_ring.alloc((size_t)rows * (size_t)m.max_records))) return rc;
-  if (coef.act)      // (a row may start one sample in, to sit on the caller's 16-byte phase, and be one sample further apart)
-    for (DevBuf<float2> &b : d_rows) if ((rc = b.alloc((size_t)rows * (pitch + 1) + 2))) return rc;
   if ((rc = ev_apply.create(hipEventDisableTiming))) return rc;
-  for (Event &e : ev_rec) if ((rc = e.create(hipEventDisableTiming))) return rc;
-  cur.reset(rows, m.max_records);
-  n = 0; calls = 0;
   on = true;
   return FMR_OK;
 }
@@ -3160,38 +3201,23 @@ int BlankerStage::init(int rows_, size_t max_in, const fmr_blanker_config &m) {
 // that reads them; in FMR_NB_ACT d_iq and stride then name the blanked rows.
 int fmr_chain::nb_stage(const float2 *&d_iq, size_t &stride, long long N_in) {
   BlankerStage &b = this->nb;
-  const long long n0 = b.n, n1 = n0 + N_in;
-  const int pieces = (int)((n1 - 1) / kNbQ - n0 / kNbQ + 1);
-  if (pieces > b.pmax) { set_err("internal: a call of %lld input samples has more intervals than the blanker holds", N_in); return FMR_ERR_CAPACITY; }
-  b.n = n1;
-  const int par = (int)(++b.calls & 1);
-  NbPart *part = b.d_part.p + (size_t)par * b.rows * b.pmax;
-  if (b.calls > 2) HIPCHK(hipStreamWaitEvent(stream, b.ev_rec[par], 0));     // (the records kernel of two calls ago read these parts)
-  float2 *out = nullptr;
-  long long ostride = 0;
-  if (b.coef.act) {      // the same 16-byte phase as the caller's rows, row by row: the front end picks the forms it would have
-    ostride = (long long)(b.pitch + (stride & 1));
-    out = b.d_rows[par].p + (((uintptr_t)d_iq >> 3) & 1);
-  }
+  CaptureStage::Call k;
+  if (int rc = b.begin(k, "the blanker", N_in, stream)) return rc;
+  NbPart *part = b.d_part.p + (size_t)k.par * b.rows * b.pmax;
+  b.out_rows(k, d_iq, stride);
   timed_on(stream, "nb_level", [&] {
-    hipLaunchKernelGGL(k_nb_level, dim3((unsigned)pieces, b.rows), dim3(kNbT), 0, stream, d_iq, (long long)stride, n0, n1, b.pmax, part);
+    hipLaunchKernelGGL(k_nb_level, dim3((unsigned)k.pieces, b.rows), dim3(kNbT), 0, stream, d_iq, (long long)stride, k.n0, k.n1, b.pmax, part);
   });
   timed_on(stream, "nb_apply", [&] {
-    hipLaunchKernelGGL(k_nb_apply, dim3((unsigned)pieces, b.rows), dim3(kNbT), 0, stream, d_iq, (long long)stride, out, ostride, n0, n1,
-                       b.pmax, par, part, b.d_aring.p, b.aring - 1, b.d_carry.p, b.d_state.p, b.coef);
+    hipLaunchKernelGGL(k_nb_apply, dim3((unsigned)k.pieces, b.rows), dim3(kNbT), 0, stream, d_iq, (long long)stride, k.out, k.ostride, k.n0, k.n1,
+                       b.pmax, k.par, part, b.d_aring.p, b.aring - 1, b.d_carry.p, b.d_state.p, b.coef);
   });
   HIPCHK(hipEventRecord(b.ev_apply, stream));
   HIPCHK(hipStreamWaitEvent(side, b.ev_apply, 0));
   timed_on(side, "nb_records", [&] {
-    hipLaunchKernelGGL(k_nb_records, dim3(b.rows), dim3(64), 0, side, part, b.pmax, n0, n1, b.d_state.p, b.d_ring.p, b.coef.R, b.coef.L);
+    hipLaunchKernelGGL(k_nb_records, dim3(b.rows), dim3(64), 0, side, part, b.pmax, k.n0, k.n1, b.d_state.p, b.d_ring.p, b.coef.R, b.coef.L);
   });
-  HIPCHK(hipEventRecord(b.ev_rec[par], side));
-  HIPCHK(hipGetLastError());
-  if (b.coef.act) {
-    d_iq = out; stride = (size_t)ostride;
-    b.last_rows = out; b.last_stride = ostride; b.last_n = N_in;
-  }
-  return FMR_OK;
+  return b.finish(k, side, d_iq, stride);
 }
 
 // ---- IQ correction (kernels_iqcorr.hpp) ----
@@ -3201,25 +3227,18 @@ int IqCorrectionStage::init(int rows_, size_t max_in, const fmr_iq_correction_co
                 offsetof(IqcRec, n_intervals) == offsetof(fmr_iq_correction_record, n_intervals) &&
                 offsetof(IqcRec, w_im) == offsetof(fmr_iq_correction_record, w_im), "the fields of a record");
   cfg = m;
-  rows = rows_;
   coef.W = m.average_intervals; coef.R = m.record_intervals; coef.L = m.max_records; coef.act = m.mode == FMR_IQC_ACT;
   coef.dc = (m.correct & FMR_IQC_DC) != 0; coef.balance = (m.correct & FMR_IQC_BALANCE) != 0;
-  pmax = (int)(max_in / kNbQ + 2);       // a call touches its whole intervals and one more at either end
+  int rc;
+  if ((rc = CaptureStage::init(rows_, max_in, coef.act, m.record_intervals, m.max_records))) return rc;
   tring = 64;
   while (tring < pmax + m.average_intervals + 2) tring <<= 1;
-  pitch = (max_in + 1) & ~(size_t)1;
-  int rc;
   if ((rc = d_part.alloc((size_t)2 * rows * pmax))) return rc;
   if ((rc = d_tot.alloc((size_t)rows * tiles() * ((kIqcBack + 1) * kIqcCoefT + 1)))) return rc;
   if ((rc = d_tring.alloc((size_t)rows * tring))) return rc;
   if ((rc = d_state.alloc((size_t)rows))) return rc;
   if ((rc = d_ring.alloc((size_t)rows * (size_t)m.max_records))) return rc;
-  if (coef.act)      // (a row may start one sample in, to sit on the caller's 16-byte phase, and be one sample further apart)
-    for (DevBuf<float2> &b : d_rows) if ((rc = b.alloc((size_t)rows * (pitch + 1) + 2))) return rc;
   if ((rc = ev_coef.create(hipEventDisableTiming))) return rc;
-  for (Event &e : ev_rec) if ((rc = e.create(hipEventDisableTiming))) return rc;
-  cur.reset(rows, m.max_records);
-  n = 0; calls = 0;
   on = true;
   return FMR_OK;
 }
@@ -3228,43 +3247,29 @@ int IqCorrectionStage::init(int rows_, size_t max_in, const fmr_iq_correction_co
 // blanker and of everything else that reads them; in FMR_IQC_ACT d_iq and stride then name the corrected rows.
 int fmr_chain::iqc_stage(const float2 *&d_iq, size_t &stride, long long N_in) {
   IqCorrectionStage &b = iqc;
-  const long long n0 = b.n, n1 = n0 + N_in;
-  const int pieces = (int)((n1 - 1) / kNbQ - n0 / kNbQ + 1);
-  if (pieces > b.pmax) { set_err("internal: a call of %lld input samples has more intervals than the IQ corrector holds", N_in); return FMR_ERR_CAPACITY; }
-  b.n = n1;
-  const int par = (int)(++b.calls & 1);
-  IqcPart *part = b.d_part.p + (size_t)par * b.rows * b.pmax;
-  if (b.calls > 2) HIPCHK(hipStreamWaitEvent(stream, b.ev_rec[par], 0));     // (the records kernel of two calls ago read these parts)
+  CaptureStage::Call k;
+  if (int rc = b.begin(k, "the IQ corrector", N_in, stream)) return rc;
+  IqcPart *part = b.d_part.p + (size_t)k.par * b.rows * b.pmax;
   timed_on(stream, "iqc_moments", [&] {
-    hipLaunchKernelGGL(k_iqc_moments, dim3((unsigned)pieces, b.rows), dim3(kNbT), 0, stream, d_iq, (long long)stride, n0, n1, b.pmax, part);
+    hipLaunchKernelGGL(k_iqc_moments, dim3((unsigned)k.pieces, b.rows), dim3(kNbT), 0, stream, d_iq, (long long)stride, k.n0, k.n1, b.pmax, part);
   });
   timed_on(stream, "iqc_coef", [&] {
-    hipLaunchKernelGGL(k_iqc_coef, dim3((unsigned)((pieces + kIqcCoefT - 1) / kIqcCoefT), b.rows), dim3(kIqcCoefT), 0, stream, part, b.pmax, n0, n1, par, b.d_tot.p, b.d_tring.p,
+    hipLaunchKernelGGL(k_iqc_coef, dim3((unsigned)((k.pieces + kIqcCoefT - 1) / kIqcCoefT), b.rows), dim3(kIqcCoefT), 0, stream, part, b.pmax, k.n0, k.n1, k.par, b.d_tot.p, b.d_tring.p,
                        b.tring - 1, b.d_state.p, b.coef);
   });
   HIPCHK(hipEventRecord(b.ev_coef, stream));
-  float2 *out = nullptr;
-  long long ostride = 0;
-  if (b.coef.act) {      // the same 16-byte phase as the caller's rows, row by row: the front end picks the forms it would have
-    ostride = (long long)(b.pitch + (stride & 1));
-    out = b.d_rows[par].p + (((uintptr_t)d_iq >> 3) & 1);
+  b.out_rows(k, d_iq, stride);
+  if (b.act)
     timed_on(stream, "iqc_apply", [&] {
-      hipLaunchKernelGGL(k_iqc_apply, dim3((unsigned)pieces, b.rows), dim3(kNbT), 0, stream, d_iq, (long long)stride, out, ostride, n0, n1,
+      hipLaunchKernelGGL(k_iqc_apply, dim3((unsigned)k.pieces, b.rows), dim3(kNbT), 0, stream, d_iq, (long long)stride, k.out, k.ostride, k.n0, k.n1,
                          b.pmax, (const IqcPart *)part);
     });
-  }
   HIPCHK(hipStreamWaitEvent(side, b.ev_coef, 0));
   timed_on(side, "iqc_records", [&] {
-    hipLaunchKernelGGL(k_iqc_records, dim3(b.rows), dim3(64), 0, side, (const IqcPart *)part, b.pmax, n0, n1, b.d_state.p, b.d_ring.p,
+    hipLaunchKernelGGL(k_iqc_records, dim3(b.rows), dim3(64), 0, side, (const IqcPart *)part, b.pmax, k.n0, k.n1, b.d_state.p, b.d_ring.p,
                        b.coef.R, b.coef.L);
   });
-  HIPCHK(hipEventRecord(b.ev_rec[par], side));
-  HIPCHK(hipGetLastError());
-  if (b.coef.act) {
-    d_iq = out; stride = (size_t)ostride;
-    b.last_rows = out; b.last_stride = ostride; b.last_n = N_in;
-  }
-  return FMR_OK;
+  return b.finish(k, side, d_iq, stride);
 }
 
 // ---- audio analyser (kernels_analyser.hpp) ----
@@ -4001,16 +4006,63 @@ static int spectrum_call(fmr_spectrum *s, const void *iq, size_t row_stride, siz
 // 10 log10 of a power ratio
 static double spec_db(double x) { return 10.0 * std::log10(x); }
 
-// The body of fmr_monitor_read and fmr_rf_monitor_read (Rec = either record, which MonRec is): synchronises, then drains up
-// to cap records of `stream` from m's rings, the PSD sums scaled to densities.  Returns what the C-ABI function returns.
+// The body of every fmr_*_read of a record ring.  `which` is the stage in the chain, `noun` and `enable` name it and its
+// fmr_enable_*; idx is a stream of the chain, or an input row of a capture stage.  Refuses bad arguments and a chain
+// without the stage, synchronises, then drains up to cap records of idx, oldest first: copy(st, k, at, m) fetches records
+// k .. k + m of the read from the ring positions at .. at + m (at = idx L + slot) and returns FMR_OK or an error;
+// scale(st, n), where given, turns what was drained into what the caller gets; fill(full, st) sets the stage's own fields
+// of the info, whose struct_size and reader's view (ring_info) are set here.  Returns the count (cap = 0: the number
+// waiting, nothing drained) or an error code.
+template <class Stage, class Rec, class Info, class Copy, class Scale, class Fill>
+static int read_records(const char *fn, fmr_chain *c, Stage fmr_chain::*which, const char *noun, const char *enable, int idx,
+                        Rec *recs, int cap, Info *info, size_t info_size, Copy &&copy, Scale &&scale, Fill &&fill) {
+  constexpr bool by_row = std::is_base_of_v<CaptureStage, Stage>;
+  if (!c || cap < 0 || (!by_row && (idx < 0 || idx >= c->S))) {
+    set_err(by_row ? "%s: bad chain or cap" : "%s: bad chain, stream or cap", fn);
+    return FMR_ERR_BAD_ARG;
+  }
+  Stage &st = c->*which;
+  if (!st.on) { set_err("%s: the chain has no %s (%s)", fn, noun, enable); return FMR_ERR_BAD_ARG; }
+  if constexpr (by_row)
+    if (idx < 0 || idx >= st.rows) { set_err("%s: row %d is not one of the chain's %d input rows", fn, idx, st.rows); return FMR_ERR_BAD_ARG; }
+  if (cap > 0 && !recs) { set_err("%s: recs is null", fn); return FMR_ERR_BAD_ARG; }
+  try {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int rc = c->sync_all()) return rc;
+    const unsigned long long done = st.done();
+    const int n = st.cur.take(idx, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
+      return copy(st, k, (size_t)idx * (size_t)st.cur.L + slot, m);
+    });
+    if (n < 0) return n;
+    if constexpr (!std::is_null_pointer_v<std::decay_t<Scale>>) scale(st, n);
+    if (info) {
+      Info full{};
+      full.struct_size = (unsigned)sizeof full;
+      ring_info(full, st.cur, idx, done);
+      fill(full, st);
+      give_sized(info, info_size, full);
+    }
+    return n;
+  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+}
+
+// copy() of a stage whose records lie in one ring, d_ring, as the caller gets them
 template <class Rec>
-static int seg_monitor_read(fmr_chain *c, SegMonitor &m, int stream, Rec *recs, uint32_t *hist, double *psd, int cap) {
-  HIPCHK(hipSetDevice(c->cfg.device));
-  if (int rc = c->sync_all()) return rc;
-  const size_t B = (size_t)m.bins, L = (size_t)m.cur.L;
-  const double scale = 1.0 / (kFmRate * m.sumw2);
-  return m.cur.take(stream, m.done(), (unsigned long long)cap, [&](size_t k0, size_t slot, size_t nr) -> int {
-    const size_t at = (size_t)stream * L + slot;
+static auto copy_ring(Rec *recs) {
+  return [recs](auto &st, size_t k, size_t at, size_t m) -> int {
+    static_assert(sizeof *st.d_ring.p == sizeof(Rec), "the ring holds the caller's records");
+    HIPCHK(hipMemcpy(recs + k, st.d_ring.p + at, m * sizeof(Rec), hipMemcpyDeviceToHost));
+    return FMR_OK;
+  };
+}
+
+// copy() of the modulation monitor and the RF monitor (Rec = either record, which MonRec is): records, histograms and
+// the PSD sums scaled to densities
+template <class Rec>
+static auto copy_seg_monitor(Rec *recs, uint32_t *hist, double *psd) {
+  return [=](SegMonitor &m, size_t k0, size_t at, size_t nr) -> int {
+    const size_t B = (size_t)m.bins;
+    const double scale = 1.0 / (kFmRate * m.sumw2);
     HIPCHK(hipMemcpy(recs + k0, m.d_ring_rec.p + at, nr * sizeof(Rec), hipMemcpyDeviceToHost));
     if (hist) HIPCHK(hipMemcpy(hist + k0 * B, m.d_ring_hist.p + at * B, nr * B * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (!psd) return FMR_OK;
@@ -4022,8 +4074,60 @@ static int seg_monitor_read(fmr_chain *c, SegMonitor &m, int stream, Rec *recs, 
         p[i] = recs[k].segments == 0 ? 0.0 : p[i] / cnt * ((i == 0 || i == kMonPsd - 1) ? 1.0 : 2.0) * scale;
     }
     return FMR_OK;
-  });
+  };
 }
+
+// A field of an fmr_enable_* configuration that has a default for 0 and a closed range: fills the default, refuses the rest
+template <class T>
+static int check_field(const char *fn, const char *name, T &x, long long lo, long long hi, long long dflt) {
+  if (x == 0) x = (T)dflt;
+  if ((long long)x >= lo && (long long)x <= hi) return FMR_OK;
+  set_err("%s: %s %lld is outside %lld .. %lld (0 = %lld)", fn, name, (long long)x, lo, hi, dflt);
+  return FMR_ERR_BAD_ARG;
+}
+static int check_field(const char *fn, const char *name, double &x, double lo, double hi, double dflt) {
+  if (x == 0.0) x = dflt;
+  if (x >= lo && x <= hi) return FMR_OK;
+  set_err("%s: %s %g is outside %g .. %g (0 = %g)", fn, name, x, lo, hi, dflt);
+  return FMR_ERR_BAD_ARG;
+}
+
+// A stage on the capture (noun: "the blanker", "the IQ corrector") wants a chain that takes complex float samples into an
+// IF resampler
+static int refuse_no_capture(const char *fn, const fmr_chain *c, const char *noun) {
+  if (c->mpx_in) {
+    set_err("%s: %s works on an IQ capture; an MPX decoder (fmr_create_mpx_decoder) is fed composite PCM", fn, noun);
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (c->in_fmt != 0) {
+    set_err("%s: %s reads complex float samples (FMR_IQ_CF32); this chain takes a raw input format", fn, noun);
+    return FMR_ERR_UNSUPPORTED;
+  }
+  if (!c->has_rs) {
+    set_err("%s: %s sits in front of the IF resampler; this chain has none (enable_resampler = 0)", fn, noun);
+    return FMR_ERR_UNSUPPORTED;
+  }
+  return FMR_OK;
+}
+
+// The front of every fmr_*_derive: the pointers it needs (have: all there; names: as the message lists them) and n >= 1 ...
+static int derive_args(const char *fn, bool have, const char *names, int n) {
+  if (have && n >= 1) return FMR_OK;
+  set_err("%s: %s is null, or n < 1", fn, names);
+  return FMR_ERR_BAD_ARG;
+}
+// ... and, for records that count intervals, that each is one a read (`reader`) has filled
+template <class Rec>
+static int derive_intervals(const char *fn, const char *reader, const Rec *recs, int n) {
+  for (int i = 0; i < n; i++)
+    if (recs[i].n_intervals == 0) {
+      set_err("%s: record %d has n_intervals 0 (not a record of %s)", fn, i, reader);
+      return FMR_ERR_BAD_ARG;
+    }
+  return FMR_OK;
+}
+// 10 log10 of a power, -inf for none
+static double db10(double v) { return v > 0.0 ? 10.0 * std::log10(v) : -INFINITY; }
 
 // The PSDs of n records (psd: n x kMonPsd as read, or null: zeros) pooled, each weighted by its record's segments
 template <class Rec>
@@ -4495,18 +4599,17 @@ long long fmr_debug_read(fmr_chain *c, int stream, int which, void *out, size_t 
   long long n = c->last_n_if;
   const void *src = nullptr;
   size_t esz = 0;
-  if (which == 6) {       // the input row the front end read in the most recent call (chains whose blanker acts; `stream` is an input row)
-    if (!c->nb.on || !c->nb.coef.act || stream >= c->nb.rows) { set_err("fmr_debug_read: tap 6 (blanked input rows) needs a chain with fmr_enable_blanker in FMR_NB_ACT, and an input row"); return FMR_ERR_BAD_ARG; }
-    n = c->nb.last_n;
+  if (which == 6 || which == 7) {     // the input row an acting capture stage wrote in the most recent call (`stream` is an input row):
+    // 6 the blanker's, which the front end read; 7 the IQ corrector's
+    const CaptureStage &st = which == 6 ? (const CaptureStage &)c->nb : c->iqc;
+    if (!st.on || !st.act || stream >= st.rows) {
+      set_err(which == 6 ? "fmr_debug_read: tap 6 (blanked input rows) needs a chain with fmr_enable_blanker in FMR_NB_ACT, and an input row"
+                         : "fmr_debug_read: tap 7 (corrected input rows) needs a chain with fmr_enable_iq_correction in FMR_IQC_ACT, and an input row");
+      return FMR_ERR_BAD_ARG;
+    }
+    n = st.last_n;
     if ((size_t)n * sizeof(float2) > cap_bytes) return FMR_ERR_CAPACITY;
-    if (n) HIPCHK(hipMemcpy(out, c->nb.last_rows + (long long)stream * c->nb.last_stride, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost));
-    return n;
-  }
-  if (which == 7) {       // the input row the corrector wrote in the most recent call (chains whose IQ corrector acts; `stream` is an input row)
-    if (!c->iqc.on || !c->iqc.coef.act || stream >= c->iqc.rows) { set_err("fmr_debug_read: tap 7 (corrected input rows) needs a chain with fmr_enable_iq_correction in FMR_IQC_ACT, and an input row"); return FMR_ERR_BAD_ARG; }
-    n = c->iqc.last_n;
-    if ((size_t)n * sizeof(float2) > cap_bytes) return FMR_ERR_CAPACITY;
-    if (n) HIPCHK(hipMemcpy(out, c->iqc.last_rows + (long long)stream * c->iqc.last_stride, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost));
+    if (n) HIPCHK(hipMemcpy(out, st.last_rows + (long long)stream * st.last_stride, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost));
     return n;
   }
   if (which == 5 && !c->d_fe_stamps.p) {      // the symbol reliabilities of the most recent call (chains with RDS)
@@ -4744,25 +4847,17 @@ int fmr_enable_monitor(fmr_chain *c, const fmr_monitor_config *cfg, size_t cfg_s
   fmr_monitor_config m;
   if (int rc = take_sized("fmr_enable_monitor", "fmr_monitor_config", cfg, cfg_size, m)) return rc;
   if (m.interval_samples == 0) m.interval_samples = 384000;
-  if (m.hist_bins == 0) m.hist_bins = 256;
   if (m.hist_range == 0.0) m.hist_range = 2.0;
-  if (m.max_records == 0) m.max_records = 64;
   if (m.interval_samples % kMonH != 0 || m.interval_samples < (uint32_t)kMonH || m.interval_samples > (1u << 30)) {
     set_err("fmr_enable_monitor: interval_samples %u is not a multiple of 512 in 512 .. 2^30 (0 = 384000)", m.interval_samples);
     return FMR_ERR_BAD_ARG;
   }
-  if (m.hist_bins < 2 || m.hist_bins > kMonMaxHist) {
-    set_err("fmr_enable_monitor: hist_bins %d is outside 2 .. %d (0 = 256)", m.hist_bins, kMonMaxHist);
-    return FMR_ERR_BAD_ARG;
-  }
+  if (int rc = check_field("fmr_enable_monitor", "hist_bins", m.hist_bins, 2, kMonMaxHist, 256)) return rc;
   if (!(m.hist_range > 0.0) || !std::isfinite(m.hist_range)) {
     set_err("fmr_enable_monitor: hist_range %g is not a finite value > 0 (0 = 2.0)", m.hist_range);
     return FMR_ERR_BAD_ARG;
   }
-  if (m.max_records < 1 || m.max_records > 4096) {
-    set_err("fmr_enable_monitor: max_records %d is outside 1 .. 4096 (0 = 64)", m.max_records);
-    return FMR_ERR_BAD_ARG;
-  }
+  if (int rc = check_field("fmr_enable_monitor", "max_records", m.max_records, 1, 4096, 64)) return rc;
   if (!c) { set_err("fmr_enable_monitor: chain is null"); return FMR_ERR_BAD_ARG; }
   if (c->mode != FMR_MODE_FM) {
     set_err("fmr_enable_monitor: the monitor reads the MPX of an FM chain (mode FMR_MODE_FM); mode %d %s", c->mode,
@@ -4775,29 +4870,19 @@ int fmr_enable_monitor(fmr_chain *c, const fmr_monitor_config *cfg, size_t cfg_s
 
 int fmr_monitor_read(fmr_chain *c, int stream, fmr_monitor_record *recs, uint32_t *hist, double *psd, int cap,
                      fmr_monitor_info *info, size_t info_size) {
-  if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_monitor_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
-  if (!c->mon.on) { set_err("fmr_monitor_read: the chain has no monitor (fmr_enable_monitor)"); return FMR_ERR_BAD_ARG; }
-  if (cap > 0 && !recs) { set_err("fmr_monitor_read: recs is null"); return FMR_ERR_BAD_ARG; }
-  try {
-    const int n = seg_monitor_read(c, c->mon, stream, recs, hist, psd, cap);
-    if (n >= 0 && info) {
-      fmr_monitor_info full{};
-      full.struct_size = (unsigned)sizeof full;
-      full.hist_bins = c->mon.bins;
-      full.psd_bins = kMonPsd;
-      ring_info(full, c->mon.cur, stream, c->mon.done());
-      full.interval_samples = c->mon.interval;
-      full.max_records = (int)c->mon.cur.L;
-      full.hist_range = c->mon.hist_range;
-      full.bin_hz = kFmRate / kMonN;
-      give_sized(info, info_size, full);
-    }
-    return n;
-  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+  return read_records("fmr_monitor_read", c, &fmr_chain::mon, "monitor", "fmr_enable_monitor", stream, recs, cap, info, info_size,
+                      copy_seg_monitor(recs, hist, psd), nullptr, [](fmr_monitor_info &full, const SegMonitor &m) {
+    full.hist_bins = m.bins;
+    full.psd_bins = kMonPsd;
+    full.interval_samples = m.interval;
+    full.max_records = (int)m.cur.L;
+    full.hist_range = m.hist_range;
+    full.bin_hz = kFmRate / kMonN;
+  });
 }
 
 int fmr_monitor_derive(const fmr_monitor_record *recs, const double *psd, int n, fmr_monitor_levels *out, size_t out_size) {
-  if (!recs || !out || n < 1) { set_err("fmr_monitor_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
+  if (int rc = derive_args("fmr_monitor_derive", recs && out, "recs or out", n)) return rc;
   double sum = 0.0, sumsq = 0.0, mn = INFINITY, mx = -INFINITY;
   unsigned long long nf = 0, seg = 0;
   for (int i = 0; i < n; i++) {
@@ -5247,16 +5332,8 @@ int fmr_enable_weak_signal(fmr_chain *c, const fmr_weak_signal_config *cfg, size
   }
   if (m.actions == 0) m.actions = FMR_WS_BLEND | FMR_WS_HIGHCUT | FMR_WS_MUTE;
   if (m.actions & ~7u) { set_err("%s: actions 0x%x has bits beyond FMR_WS_BLEND | FMR_WS_HIGHCUT | FMR_WS_MUTE", fn, m.actions); return FMR_ERR_BAD_ARG; }
-  if (m.record_intervals == 0) m.record_intervals = 50;
-  if (m.max_records == 0) m.max_records = 1024;
-  if (m.record_intervals < 1 || m.record_intervals > 1000) {
-    set_err("%s: record_intervals %d is outside 1 .. 1000 (0 = 50)", fn, m.record_intervals);
-    return FMR_ERR_BAD_ARG;
-  }
-  if (m.max_records < 1 || m.max_records > 65536) {
-    set_err("%s: max_records %d is outside 1 .. 65536 (0 = 1024)", fn, m.max_records);
-    return FMR_ERR_BAD_ARG;
-  }
+  if (int rc = check_field(fn, "record_intervals", m.record_intervals, 1, 1000, 50)) return rc;
+  if (int rc = check_field(fn, "max_records", m.max_records, 1, 65536, 1024)) return rc;
   if (m.attack_ms == 0.0) m.attack_ms = 10.0;
   if (m.release_ms == 0.0) m.release_ms = 500.0;
   if (!(m.attack_ms > 0.0 && m.attack_ms <= 60000.0)) { set_err("%s: attack_ms %g is outside (0, 60000] (0 = 10)", fn, m.attack_ms); return FMR_ERR_BAD_ARG; }
@@ -5272,8 +5349,7 @@ int fmr_enable_weak_signal(fmr_chain *c, const fmr_weak_signal_config *cfg, size
       return FMR_ERR_BAD_ARG;
     }
   }
-  if (m.highcut_hz == 0.0) m.highcut_hz = 2500.0;
-  if (!(m.highcut_hz >= 500.0 && m.highcut_hz <= 15000.0)) { set_err("%s: highcut_hz %g is outside 500 .. 15000 (0 = 2500)", fn, m.highcut_hz); return FMR_ERR_BAD_ARG; }
+  if (int rc = check_field(fn, "highcut_hz", m.highcut_hz, 500.0, 15000.0, 2500.0)) return rc;
   if (m.mute_floor_db == 0.0) m.mute_floor_db = -20.0;
   if (!(std::isfinite(m.mute_floor_db) && m.mute_floor_db < 0.0)) { set_err("%s: mute_floor_db %g is not finite and below 0 (0 = -20)", fn, m.mute_floor_db); return FMR_ERR_BAD_ARG; }
   if (!c) { set_err("%s: chain is null", fn); return FMR_ERR_BAD_ARG; }
@@ -5291,42 +5367,20 @@ int fmr_enable_weak_signal(fmr_chain *c, const fmr_weak_signal_config *cfg, size
 
 int fmr_weak_signal_read(fmr_chain *c, int stream, fmr_weak_signal_record *recs, int cap, fmr_weak_signal_info *info,
                          size_t info_size) {
-  if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_weak_signal_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
-  if (!c->ws.on) { set_err("fmr_weak_signal_read: the chain has no weak-signal stage (fmr_enable_weak_signal)"); return FMR_ERR_BAD_ARG; }
-  if (cap > 0 && !recs) { set_err("fmr_weak_signal_read: recs is null"); return FMR_ERR_BAD_ARG; }
-  try {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    if (int rc = c->sync_all()) return rc;
-    const unsigned long long done = c->ws.done();
-    const int n = c->ws.cur.take(stream, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
-      HIPCHK(hipMemcpy(recs + k, c->ws.d_ring.p + (size_t)stream * c->ws.cur.L + slot, m * sizeof(fmr_weak_signal_record),
-                       hipMemcpyDeviceToHost));
-      return FMR_OK;
-    });
-    if (n < 0) return n;
-    if (info) {
-      fmr_weak_signal_info full{};
-      full.struct_size = (unsigned)sizeof full;
-      full.channels = c->stereo ? 2 : 1;
-      ring_info(full, c->ws.cur, stream, done);
-      full.intervals_complete = c->ws.intervals();
-      full.record_intervals = c->ws.cfg.record_intervals;
-      full.max_records = c->ws.cfg.max_records;
-      full.mode = c->ws.cfg.mode;
-      full.actions = c->ws.cfg.actions;
-      give_sized(info, info_size, full);
-    }
-    return n;
-  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+  return read_records("fmr_weak_signal_read", c, &fmr_chain::ws, "weak-signal stage", "fmr_enable_weak_signal", stream, recs, cap, info,
+                      info_size, copy_ring(recs), nullptr, [c](fmr_weak_signal_info &full, const WeakSignalStage &ws) {
+    full.channels = c->stereo ? 2 : 1;
+    full.intervals_complete = ws.intervals();
+    full.record_intervals = ws.cfg.record_intervals;
+    full.max_records = ws.cfg.max_records;
+    full.mode = ws.cfg.mode;
+    full.actions = ws.cfg.actions;
+  });
 }
 
 int fmr_weak_signal_derive(const fmr_weak_signal_record *recs, int n, fmr_weak_signal_levels *out, size_t out_size) {
-  if (!recs || !out || n < 1) { set_err("fmr_weak_signal_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
-  for (int i = 0; i < n; i++)
-    if (recs[i].n_intervals == 0) {
-      set_err("fmr_weak_signal_derive: record %d has n_intervals 0 (not a record of fmr_weak_signal_read)", i);
-      return FMR_ERR_BAD_ARG;
-    }
+  if (int rc = derive_args("fmr_weak_signal_derive", recs && out, "recs or out", n)) return rc;
+  if (int rc = derive_intervals("fmr_weak_signal_derive", "fmr_weak_signal_read", recs, n)) return rc;
   fmr_weak_signal_levels full{};
   full.struct_size = (unsigned)sizeof full;
   double sum = 0.0, peak = 0.0;
@@ -5340,7 +5394,6 @@ int fmr_weak_signal_derive(const fmr_weak_signal_record *recs, int n, fmr_weak_s
     if (r.max_highcut > 0.0) nh += r.n_intervals;
     if (r.max_mute > 0.0) nm += r.n_intervals;
   }
-  auto db10 = [](double v) { return v > 0.0 ? 10.0 * std::log10(v) : -INFINITY; };
   const double mean = sum / (double)ni;
   full.usn_mean_db = db10(mean); full.usn_peak_db = db10(peak);
   full.usn_mean_hz = 75000.0 * std::sqrt(mean); full.usn_peak_hz = 75000.0 * std::sqrt(peak);
@@ -5361,8 +5414,7 @@ int fmr_enable_blanker(fmr_chain *c, const fmr_blanker_config *cfg, size_t cfg_s
     set_err("%s: mode %d is neither FMR_NB_MEASURE (0) nor FMR_NB_ACT (1)", fn, m.mode);
     return FMR_ERR_BAD_ARG;
   }
-  if (m.threshold_db == 0.0) m.threshold_db = 12.0;
-  if (!(m.threshold_db >= 6.0 && m.threshold_db <= 40.0)) { set_err("%s: threshold_db %g is outside 6 .. 40 (0 = 12)", fn, m.threshold_db); return FMR_ERR_BAD_ARG; }
+  if (int rc = check_field(fn, "threshold_db", m.threshold_db, 6.0, 40.0, 12.0)) return rc;
   if (m.gate_samples < 0 || m.gate_samples > kNbMaxG) {
     set_err("%s: gate_samples %d is outside 1 .. %d (0 = max(2, ceil(0.8e-6 input_rate)))", fn, m.gate_samples, kNbMaxG);
     return FMR_ERR_BAD_ARG;
@@ -5373,34 +5425,11 @@ int fmr_enable_blanker(fmr_chain *c, const fmr_blanker_config *cfg, size_t cfg_s
   };
   if (m.max_run_samples < 0 || m.max_run_samples > kNbMaxM || (m.max_run_samples && m.max_run_samples < std::max(1, m.gate_samples)))
     return bad_run(std::max(1, m.gate_samples));
-  if (m.average_intervals == 0) m.average_intervals = 16;
-  if (m.average_intervals < 1 || m.average_intervals > kNbMaxW) {
-    set_err("%s: average_intervals %d is outside 1 .. %d (0 = 16)", fn, m.average_intervals, kNbMaxW);
-    return FMR_ERR_BAD_ARG;
-  }
-  if (m.record_intervals == 0) m.record_intervals = 256;
-  if (m.record_intervals < 1 || m.record_intervals > 4096) {
-    set_err("%s: record_intervals %d is outside 1 .. 4096 (0 = 256)", fn, m.record_intervals);
-    return FMR_ERR_BAD_ARG;
-  }
-  if (m.max_records == 0) m.max_records = 1024;
-  if (m.max_records < 1 || m.max_records > 65536) {
-    set_err("%s: max_records %d is outside 1 .. 65536 (0 = 1024)", fn, m.max_records);
-    return FMR_ERR_BAD_ARG;
-  }
+  if (int rc = check_field(fn, "average_intervals", m.average_intervals, 1, kNbMaxW, 16)) return rc;
+  if (int rc = check_field(fn, "record_intervals", m.record_intervals, 1, 4096, 256)) return rc;
+  if (int rc = check_field(fn, "max_records", m.max_records, 1, 65536, 1024)) return rc;
   if (!c) { set_err("%s: chain is null", fn); return FMR_ERR_BAD_ARG; }
-  if (c->mpx_in) {
-    set_err("%s: the blanker works on an IQ capture; an MPX decoder (fmr_create_mpx_decoder) is fed composite PCM", fn);
-    return FMR_ERR_UNSUPPORTED;
-  }
-  if (c->in_fmt != 0) {
-    set_err("%s: the blanker reads complex float samples (FMR_IQ_CF32); this chain takes a raw input format", fn);
-    return FMR_ERR_UNSUPPORTED;
-  }
-  if (!c->has_rs) {
-    set_err("%s: the blanker sits in front of the IF resampler; this chain has none (enable_resampler = 0)", fn);
-    return FMR_ERR_UNSUPPORTED;
-  }
+  if (int rc = refuse_no_capture(fn, c, "the blanker")) return rc;
   // (the gate is a time, 0.8 us: longer than an impulse, shorter than one IF sample)
   if (m.gate_samples == 0) m.gate_samples = std::min(kNbMaxG, std::max(2, (int)std::ceil(0.8e-6 * c->cfg.input_rate)));
   if (m.max_run_samples == 0) m.max_run_samples = std::min(kNbMaxM, 8 * m.gate_samples);
@@ -5410,42 +5439,20 @@ int fmr_enable_blanker(fmr_chain *c, const fmr_blanker_config *cfg, size_t cfg_s
 }
 
 int fmr_blanker_read(fmr_chain *c, int row, fmr_blanker_record *recs, int cap, fmr_blanker_info *info, size_t info_size) {
-  if (!c || cap < 0) { set_err("fmr_blanker_read: bad chain or cap"); return FMR_ERR_BAD_ARG; }
-  if (!c->nb.on) { set_err("fmr_blanker_read: the chain has no blanker (fmr_enable_blanker)"); return FMR_ERR_BAD_ARG; }
-  if (row < 0 || row >= c->nb.rows) { set_err("fmr_blanker_read: row %d is not one of the chain's %d input rows", row, c->nb.rows); return FMR_ERR_BAD_ARG; }
-  if (cap > 0 && !recs) { set_err("fmr_blanker_read: recs is null"); return FMR_ERR_BAD_ARG; }
-  try {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    if (int rc = c->sync_all()) return rc;
-    const unsigned long long done = c->nb.done();
-    const int n = c->nb.cur.take(row, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
-      HIPCHK(hipMemcpy(recs + k, c->nb.d_ring.p + (size_t)row * c->nb.cur.L + slot, m * sizeof(fmr_blanker_record), hipMemcpyDeviceToHost));
-      return FMR_OK;
-    });
-    if (n < 0) return n;
-    if (info) {
-      fmr_blanker_info full{};
-      full.struct_size = (unsigned)sizeof full;
-      full.rows = c->nb.rows;
-      ring_info(full, c->nb.cur, row, done);
-      full.intervals_complete = c->nb.intervals();
-      const fmr_blanker_config &m = c->nb.cfg;
-      full.mode = m.mode; full.gate_samples = m.gate_samples; full.max_run_samples = m.max_run_samples;
-      full.average_intervals = m.average_intervals; full.record_intervals = m.record_intervals; full.max_records = m.max_records;
-      give_sized(info, info_size, full);
-    }
-    return n;
-  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+  return read_records("fmr_blanker_read", c, &fmr_chain::nb, "blanker", "fmr_enable_blanker", row, recs, cap, info, info_size,
+                      copy_ring(recs), nullptr, [](fmr_blanker_info &full, const BlankerStage &nb) {
+    const fmr_blanker_config &m = nb.cfg;
+    full.rows = nb.rows;
+    full.intervals_complete = nb.intervals();
+    full.mode = m.mode; full.gate_samples = m.gate_samples; full.max_run_samples = m.max_run_samples;
+    full.average_intervals = m.average_intervals; full.record_intervals = m.record_intervals; full.max_records = m.max_records;
+  });
 }
 
 int fmr_blanker_derive(const fmr_blanker_record *recs, int n, double input_rate, fmr_blanker_levels *out, size_t out_size) {
-  if (!recs || !out || n < 1) { set_err("fmr_blanker_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
+  if (int rc = derive_args("fmr_blanker_derive", recs && out, "recs or out", n)) return rc;
   if (!(input_rate > 0.0) || !std::isfinite(input_rate)) { set_err("fmr_blanker_derive: input_rate %g is not a positive rate", input_rate); return FMR_ERR_BAD_ARG; }
-  for (int i = 0; i < n; i++)
-    if (recs[i].n_intervals == 0) {
-      set_err("fmr_blanker_derive: record %d has n_intervals 0 (not a record of fmr_blanker_read)", i);
-      return FMR_ERR_BAD_ARG;
-    }
+  if (int rc = derive_intervals("fmr_blanker_derive", "fmr_blanker_read", recs, n)) return rc;
   fmr_blanker_levels full{};
   full.struct_size = (unsigned)sizeof full;
   double pq = 0.0;
@@ -5457,7 +5464,6 @@ int fmr_blanker_derive(const fmr_blanker_record *recs, int n, double input_rate,
     pq += (double)r.power_q;
     peak = std::max(peak, r.peak);
   }
-  auto db10 = [](double v) { return v > 0.0 ? 10.0 * std::log10(v) : -INFINITY; };
   const double samples = (double)full.n_intervals * (double)kNbQ;
   full.blanked_share = (double)full.n_blanked / samples;
   full.runs_per_second = (double)full.n_runs * input_rate / samples;
@@ -5482,74 +5488,29 @@ int fmr_enable_iq_correction(fmr_chain *c, const fmr_iq_correction_config *cfg, 
     set_err("%s: correct %d is not a mask of FMR_IQC_DC (1) and FMR_IQC_BALANCE (2) (0 = both)", fn, m.correct);
     return FMR_ERR_BAD_ARG;
   }
-  if (m.average_intervals == 0) m.average_intervals = 64;
-  if (m.average_intervals < 1 || m.average_intervals > kIqcMaxW) {
-    set_err("%s: average_intervals %d is outside 1 .. %d (0 = 64)", fn, m.average_intervals, kIqcMaxW);
-    return FMR_ERR_BAD_ARG;
-  }
-  if (m.record_intervals == 0) m.record_intervals = 256;
-  if (m.record_intervals < 1 || m.record_intervals > 4096) {
-    set_err("%s: record_intervals %d is outside 1 .. 4096 (0 = 256)", fn, m.record_intervals);
-    return FMR_ERR_BAD_ARG;
-  }
-  if (m.max_records == 0) m.max_records = 1024;
-  if (m.max_records < 1 || m.max_records > 65536) {
-    set_err("%s: max_records %d is outside 1 .. 65536 (0 = 1024)", fn, m.max_records);
-    return FMR_ERR_BAD_ARG;
-  }
+  if (int rc = check_field(fn, "average_intervals", m.average_intervals, 1, kIqcMaxW, 64)) return rc;
+  if (int rc = check_field(fn, "record_intervals", m.record_intervals, 1, 4096, 256)) return rc;
+  if (int rc = check_field(fn, "max_records", m.max_records, 1, 65536, 1024)) return rc;
   if (!c) { set_err("%s: chain is null", fn); return FMR_ERR_BAD_ARG; }
-  if (c->mpx_in) {
-    set_err("%s: the IQ corrector works on an IQ capture; an MPX decoder (fmr_create_mpx_decoder) is fed composite PCM", fn);
-    return FMR_ERR_UNSUPPORTED;
-  }
-  if (c->in_fmt != 0) {
-    set_err("%s: the IQ corrector reads complex float samples (FMR_IQ_CF32); this chain takes a raw input format", fn);
-    return FMR_ERR_UNSUPPORTED;
-  }
-  if (!c->has_rs) {
-    set_err("%s: the IQ corrector sits in front of the IF resampler; this chain has none (enable_resampler = 0)", fn);
-    return FMR_ERR_UNSUPPORTED;
-  }
+  if (int rc = refuse_no_capture(fn, c, "the IQ corrector")) return rc;
   return enable_stage(fn, c, c->iqc, "IQ corrector", "input sample", c->in_rows(), c->max_in, m);
 }
 
 int fmr_iq_correction_read(fmr_chain *c, int row, fmr_iq_correction_record *recs, int cap, fmr_iq_correction_info *info,
                            size_t info_size) {
-  if (!c || cap < 0) { set_err("fmr_iq_correction_read: bad chain or cap"); return FMR_ERR_BAD_ARG; }
-  if (!c->iqc.on) { set_err("fmr_iq_correction_read: the chain has no IQ corrector (fmr_enable_iq_correction)"); return FMR_ERR_BAD_ARG; }
-  if (row < 0 || row >= c->iqc.rows) { set_err("fmr_iq_correction_read: row %d is not one of the chain's %d input rows", row, c->iqc.rows); return FMR_ERR_BAD_ARG; }
-  if (cap > 0 && !recs) { set_err("fmr_iq_correction_read: recs is null"); return FMR_ERR_BAD_ARG; }
-  try {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    if (int rc = c->sync_all()) return rc;
-    const unsigned long long done = c->iqc.done();
-    const int n = c->iqc.cur.take(row, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
-      HIPCHK(hipMemcpy(recs + k, c->iqc.d_ring.p + (size_t)row * c->iqc.cur.L + slot, m * sizeof(fmr_iq_correction_record), hipMemcpyDeviceToHost));
-      return FMR_OK;
-    });
-    if (n < 0) return n;
-    if (info) {
-      fmr_iq_correction_info full{};
-      full.struct_size = (unsigned)sizeof full;
-      full.rows = c->iqc.rows;
-      ring_info(full, c->iqc.cur, row, done);
-      full.intervals_complete = c->iqc.intervals();
-      const fmr_iq_correction_config &m = c->iqc.cfg;
-      full.mode = m.mode; full.correct = m.correct; full.average_intervals = m.average_intervals;
-      full.record_intervals = m.record_intervals; full.max_records = m.max_records;
-      give_sized(info, info_size, full);
-    }
-    return n;
-  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+  return read_records("fmr_iq_correction_read", c, &fmr_chain::iqc, "IQ corrector", "fmr_enable_iq_correction", row, recs, cap, info,
+                      info_size, copy_ring(recs), nullptr, [](fmr_iq_correction_info &full, const IqCorrectionStage &iqc) {
+    const fmr_iq_correction_config &m = iqc.cfg;
+    full.rows = iqc.rows;
+    full.intervals_complete = iqc.intervals();
+    full.mode = m.mode; full.correct = m.correct; full.average_intervals = m.average_intervals;
+    full.record_intervals = m.record_intervals; full.max_records = m.max_records;
+  });
 }
 
 int fmr_iq_correction_derive(const fmr_iq_correction_record *recs, int n, fmr_iq_correction_levels *out, size_t out_size) {
-  if (!recs || !out || n < 1) { set_err("fmr_iq_correction_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
-  for (int i = 0; i < n; i++)
-    if (recs[i].n_intervals == 0) {
-      set_err("fmr_iq_correction_derive: record %d has n_intervals 0 (not a record of fmr_iq_correction_read)", i);
-      return FMR_ERR_BAD_ARG;
-    }
+  if (int rc = derive_args("fmr_iq_correction_derive", recs && out, "recs or out", n)) return rc;
+  if (int rc = derive_intervals("fmr_iq_correction_derive", "fmr_iq_correction_read", recs, n)) return rc;
   fmr_iq_correction_levels full{};
   full.struct_size = (unsigned)sizeof full;
   int64_t S_r = 0, S_i = 0, S_rr = 0, S_ii = 0, S_ri = 0;
@@ -5593,15 +5554,11 @@ int fmr_enable_loudness(fmr_chain *c, const fmr_loudness_config *cfg, size_t cfg
   fmr_loudness_config m;
   if (int rc = take_sized("fmr_enable_loudness", "fmr_loudness_config", cfg, cfg_size, m)) return rc;
   if (m.step_samples == 0) m.step_samples = 4800;
-  if (m.max_records == 0) m.max_records = 1024;
   if (m.step_samples % 16 != 0 || m.step_samples < 48 || m.step_samples > (1u << 20)) {
     set_err("fmr_enable_loudness: step_samples %u is not a multiple of 16 in 48 .. 2^20 (0 = 4800)", m.step_samples);
     return FMR_ERR_BAD_ARG;
   }
-  if (m.max_records < 1 || m.max_records > 65536) {
-    set_err("fmr_enable_loudness: max_records %d is outside 1 .. 65536 (0 = 1024)", m.max_records);
-    return FMR_ERR_BAD_ARG;
-  }
+  if (int rc = check_field("fmr_enable_loudness", "max_records", m.max_records, 1, 65536, 1024)) return rc;
   if (!c) { set_err("fmr_enable_loudness: chain is null"); return FMR_ERR_BAD_ARG; }
   if (c->mode != FMR_MODE_FM) {
     set_err("fmr_enable_loudness: the audio monitor reads the audio of an FM chain (mode FMR_MODE_FM); mode %d %s", c->mode,
@@ -5612,34 +5569,16 @@ int fmr_enable_loudness(fmr_chain *c, const fmr_loudness_config *cfg, size_t cfg
 }
 
 int fmr_loudness_read(fmr_chain *c, int stream, fmr_loudness_record *recs, int cap, fmr_loudness_info *info, size_t info_size) {
-  if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_loudness_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
-  if (!c->ld.on) { set_err("fmr_loudness_read: the chain has no audio monitor (fmr_enable_loudness)"); return FMR_ERR_BAD_ARG; }
-  if (cap > 0 && !recs) { set_err("fmr_loudness_read: recs is null"); return FMR_ERR_BAD_ARG; }
-  try {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    if (int rc = c->sync_all()) return rc;
-    const unsigned long long done = c->ld.done();
-    const int n = c->ld.cur.take(stream, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
-      HIPCHK(hipMemcpy(recs + k, c->ld.d_ring.p + (size_t)stream * c->ld.cur.L + slot, m * sizeof(fmr_loudness_record),
-                       hipMemcpyDeviceToHost));
-      return FMR_OK;
-    });
-    if (n < 0) return n;
-    if (info) {
-      fmr_loudness_info full{};
-      full.struct_size = (unsigned)sizeof full;
-      full.channels = c->stereo ? 2 : 1;
-      ring_info(full, c->ld.cur, stream, done);
-      full.step_samples = c->ld.cfg.step_samples;
-      full.max_records = c->ld.cfg.max_records;
-      give_sized(info, info_size, full);
-    }
-    return n;
-  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+  return read_records("fmr_loudness_read", c, &fmr_chain::ld, "audio monitor", "fmr_enable_loudness", stream, recs, cap, info, info_size,
+                      copy_ring(recs), nullptr, [c](fmr_loudness_info &full, const LoudnessStage &ld) {
+    full.channels = c->stereo ? 2 : 1;
+    full.step_samples = ld.cfg.step_samples;
+    full.max_records = ld.cfg.max_records;
+  });
 }
 
 int fmr_loudness_derive(const fmr_loudness_record *recs, int n, double silence_dbfs, fmr_loudness_levels *out, size_t out_size) {
-  if (!recs || !out || n < 1) { set_err("fmr_loudness_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
+  if (int rc = derive_args("fmr_loudness_derive", recs && out, "recs or out", n)) return rc;
   if (std::isnan(silence_dbfs)) { set_err("fmr_loudness_derive: silence_dbfs is not a number"); return FMR_ERR_BAD_ARG; }
   for (int i = 0; i < n; i++)
     if (recs[i].step_samples == 0 || recs[i].channels < 1 || recs[i].channels > 2) {
@@ -5722,16 +5661,12 @@ int fmr_enable_analyser(fmr_chain *c, const fmr_analyser_config *cfg, size_t cfg
   }
   const uint32_t H = (uint32_t)m.fft_size / 2;
   if (m.interval_samples == 0) m.interval_samples = 6u * (uint32_t)m.fft_size;
-  if (m.max_records == 0) m.max_records = 64;
   if (m.interval_samples % H != 0 || m.interval_samples < H || m.interval_samples > (1u << 24)) {
     set_err("fmr_enable_analyser: interval_samples %u is not a multiple of fft_size / 2 = %u in %u .. 2^24 (0 = 6 fft_size)",
             m.interval_samples, H, H);
     return FMR_ERR_BAD_ARG;
   }
-  if (m.max_records < 1 || m.max_records > 4096) {
-    set_err("fmr_enable_analyser: max_records %d is outside 1 .. 4096 (0 = 64)", m.max_records);
-    return FMR_ERR_BAD_ARG;
-  }
+  if (int rc = check_field("fmr_enable_analyser", "max_records", m.max_records, 1, 4096, 64)) return rc;
   if (!c) { set_err("fmr_enable_analyser: chain is null"); return FMR_ERR_BAD_ARG; }
   if (!c->has_dec) {
     set_err("fmr_enable_analyser: a front-end-only chain (mode -1: channelizer / IfResampler) has no audio");
@@ -5742,50 +5677,39 @@ int fmr_enable_analyser(fmr_chain *c, const fmr_analyser_config *cfg, size_t cfg
 
 int fmr_analyser_read(fmr_chain *c, int stream, fmr_analyser_record *recs, double *spectra, int cap, fmr_analyser_info *info,
                       size_t info_size) {
-  if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_analyser_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
-  if (!c->an.on) { set_err("fmr_analyser_read: the chain has no analyser (fmr_enable_analyser)"); return FMR_ERR_BAD_ARG; }
-  if (cap > 0 && !recs) { set_err("fmr_analyser_read: recs is null"); return FMR_ERR_BAD_ARG; }
-  try {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    if (int rc = c->sync_all()) return rc;
-    AnalyserStage &an = c->an;
-    const unsigned long long done = an.done();
-    const size_t nb = (size_t)an.nb, nb3 = (size_t)kAnRows * nb;
-    const int n = an.cur.take(stream, done, (unsigned long long)cap, [&](size_t k, size_t slot, size_t m) -> int {
-      const size_t at = (size_t)stream * an.cur.L + slot;
-      HIPCHK(hipMemcpy(recs + k, an.d_ring_rec.p + at, m * sizeof(fmr_analyser_record), hipMemcpyDeviceToHost));
-      if (spectra) HIPCHK(hipMemcpy(spectra + k * nb3, an.d_ring_psd.p + at * nb3, m * nb3 * sizeof(double), hipMemcpyDeviceToHost));
-      return FMR_OK;
-    });
-    if (n < 0) return n;
-    if (spectra && cap > 0)      // the sums of the counted segments -> power
-      for (int i = 0; i < n; i++) {
-        const double seg = (double)recs[i].segments;
-        const double g = seg > 0.0 ? 1.0 / ((double)an.N * an.sumw2 * seg) : 0.0;
-        for (int r = 0; r < kAnRows; r++) {
-          double *row = spectra + (size_t)i * nb3 + (size_t)r * nb;
-          for (size_t k = 0; k < nb; k++) row[k] = row[k] * ((k == 0 || k == nb - 1) ? 1.0 : 2.0) * g;
+  return read_records(
+      "fmr_analyser_read", c, &fmr_chain::an, "analyser", "fmr_enable_analyser", stream, recs, cap, info, info_size,
+      [=](AnalyserStage &an, size_t k, size_t at, size_t m) -> int {
+        const size_t nb3 = (size_t)kAnRows * (size_t)an.nb;
+        HIPCHK(hipMemcpy(recs + k, an.d_ring_rec.p + at, m * sizeof(fmr_analyser_record), hipMemcpyDeviceToHost));
+        if (spectra) HIPCHK(hipMemcpy(spectra + k * nb3, an.d_ring_psd.p + at * nb3, m * nb3 * sizeof(double), hipMemcpyDeviceToHost));
+        return FMR_OK;
+      },
+      [=](const AnalyserStage &an, int n) {      // the sums of the counted segments -> power
+        if (!spectra || cap == 0) return;
+        const size_t nb = (size_t)an.nb, nb3 = (size_t)kAnRows * nb;
+        for (int i = 0; i < n; i++) {
+          const double seg = (double)recs[i].segments;
+          const double g = seg > 0.0 ? 1.0 / ((double)an.N * an.sumw2 * seg) : 0.0;
+          for (int r = 0; r < kAnRows; r++) {
+            double *row = spectra + (size_t)i * nb3 + (size_t)r * nb;
+            for (size_t k = 0; k < nb; k++) row[k] = row[k] * ((k == 0 || k == nb - 1) ? 1.0 : 2.0) * g;
+          }
         }
-      }
-    if (info) {
-      fmr_analyser_info full{};
-      full.struct_size = (unsigned)sizeof full;
-      full.channels = c->stereo ? 2 : 1;
-      ring_info(full, an.cur, stream, done);
-      full.interval_samples = an.cfg.interval_samples;
-      full.max_records = an.cfg.max_records;
-      full.fft_size = an.N;
-      full.bins = an.nb;
-      full.bin_hz = kPcmRate / an.N;
-      give_sized(info, info_size, full);
-    }
-    return n;
-  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+      },
+      [c](fmr_analyser_info &full, const AnalyserStage &an) {
+        full.channels = c->stereo ? 2 : 1;
+        full.interval_samples = an.cfg.interval_samples;
+        full.max_records = an.cfg.max_records;
+        full.fft_size = an.N;
+        full.bins = an.nb;
+        full.bin_hz = kPcmRate / an.N;
+      });
 }
 
 int fmr_analyser_derive(const fmr_analyser_record *recs, const double *spectra, int n, const fmr_analyser_rule *rule,
                         size_t rule_size, fmr_analyser_levels *out, size_t out_size) {
-  if (!recs || !spectra || !out || n < 1) { set_err("fmr_analyser_derive: recs, spectra or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
+  if (int rc = derive_args("fmr_analyser_derive", recs && spectra && out, "recs, spectra or out", n)) return rc;
   fmr_analyser_rule r{};
   if (rule) if (int rc = take_sized("fmr_analyser_derive", "fmr_analyser_rule", rule, rule_size, r)) return rc;
   const int N = (int)recs[0].fft_size, ch = (int)recs[0].channels;
@@ -5924,15 +5848,11 @@ int fmr_enable_rf_monitor(fmr_chain *c, const fmr_rf_monitor_config *cfg, size_t
   fmr_rf_monitor_config m;
   if (int rc = take_sized("fmr_enable_rf_monitor", "fmr_rf_monitor_config", cfg, cfg_size, m)) return rc;
   if (m.interval_samples == 0) m.interval_samples = 38400;
-  if (m.max_records == 0) m.max_records = 64;
   if (m.interval_samples % kMonH != 0 || m.interval_samples < (uint32_t)kMonH || m.interval_samples > (1u << 30)) {
     set_err("fmr_enable_rf_monitor: interval_samples %u is not a multiple of 512 in 512 .. 2^30 (0 = 38400)", m.interval_samples);
     return FMR_ERR_BAD_ARG;
   }
-  if (m.max_records < 1 || m.max_records > 4096) {
-    set_err("fmr_enable_rf_monitor: max_records %d is outside 1 .. 4096 (0 = 64)", m.max_records);
-    return FMR_ERR_BAD_ARG;
-  }
+  if (int rc = check_field("fmr_enable_rf_monitor", "max_records", m.max_records, 1, 4096, 64)) return rc;
   if (!c) { set_err("fmr_enable_rf_monitor: chain is null"); return FMR_ERR_BAD_ARG; }
   if (c->mpx_in) {
     set_err("fmr_enable_rf_monitor: the RF monitor reads the IF samples in front of the discriminator; an MPX decoder (fmr_create_mpx_decoder) is fed composite PCM and has none");
@@ -5949,29 +5869,19 @@ int fmr_enable_rf_monitor(fmr_chain *c, const fmr_rf_monitor_config *cfg, size_t
 
 int fmr_rf_monitor_read(fmr_chain *c, int stream, fmr_rf_monitor_record *recs, uint32_t *hist, double *psd, int cap,
                         fmr_rf_monitor_info *info, size_t info_size) {
-  if (!c || stream < 0 || stream >= c->S || cap < 0) { set_err("fmr_rf_monitor_read: bad chain, stream or cap"); return FMR_ERR_BAD_ARG; }
-  if (!c->rfm.on) { set_err("fmr_rf_monitor_read: the chain has no RF monitor (fmr_enable_rf_monitor)"); return FMR_ERR_BAD_ARG; }
-  if (cap > 0 && !recs) { set_err("fmr_rf_monitor_read: recs is null"); return FMR_ERR_BAD_ARG; }
-  try {
-    const int n = seg_monitor_read(c, c->rfm, stream, recs, hist, psd, cap);
-    if (n >= 0 && info) {
-      fmr_rf_monitor_info full{};
-      full.struct_size = (unsigned)sizeof full;
-      full.hist_bins = kRfmBins;
-      full.psd_bins = kMonPsd;
-      ring_info(full, c->rfm.cur, stream, c->rfm.done());
-      full.interval_samples = c->rfm.interval;
-      full.max_records = (int)c->rfm.cur.L;
-      full.bin_hz = kFmRate / kMonN;
-      give_sized(info, info_size, full);
-    }
-    return n;
-  } catch (const std::exception &e) { set_err("exception: %s", e.what()); return FMR_ERR_HIP; }
+  return read_records("fmr_rf_monitor_read", c, &fmr_chain::rfm, "RF monitor", "fmr_enable_rf_monitor", stream, recs, cap, info,
+                      info_size, copy_seg_monitor(recs, hist, psd), nullptr, [](fmr_rf_monitor_info &full, const SegMonitor &m) {
+    full.hist_bins = kRfmBins;
+    full.psd_bins = kMonPsd;
+    full.interval_samples = m.interval;
+    full.max_records = (int)m.cur.L;
+    full.bin_hz = kFmRate / kMonN;
+  });
 }
 
 int fmr_rf_monitor_derive(const fmr_rf_monitor_record *recs, const uint32_t *hist, const double *psd, int n,
                           fmr_rf_monitor_levels *out, size_t out_size) {
-  if (!recs || !out || n < 1) { set_err("fmr_rf_monitor_derive: recs or out is null, or n < 1"); return FMR_ERR_BAD_ARG; }
+  if (int rc = derive_args("fmr_rf_monitor_derive", recs && out, "recs or out", n)) return rc;
   double m2 = 0.0, m4 = 0.0;
   unsigned long long nf = 0, seg = 0;
   std::vector<unsigned long long> h(kRfmBins, 0ull);
@@ -5983,7 +5893,7 @@ int fmr_rf_monitor_derive(const fmr_rf_monitor_record *recs, const uint32_t *his
   }
   const std::vector<double> p = mon_pool_psd(recs, psd, n);
   const double M2 = nf ? m2 / (double)nf : 0.0, M4 = nf ? m4 / (double)nf : 0.0;
-  auto db = [](double x) -> double { return x > 0.0 ? 10.0 * std::log10(x) : -INFINITY; };
+  const auto db = db10;
   auto pct = [&](unsigned q) -> double {
     if (!hist || nf == 0) return -INFINITY;
     unsigned long long cum = 0;

@@ -34,6 +34,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -94,125 +95,103 @@ inline std::vector<fmr_rds_group> rds_groups(fmr_chain *c, int stream, fmr_rds::
   return out;
 }
 
-// modulation monitor (fmr_enable_monitor / fmr_monitor_read / fmr_monitor_derive): one drained record with its histogram,
-// its one-sided PSD (513 bins of 375 Hz) and the levels derived from it alone
-struct ModulationRecord {
-  fmr_monitor_record rec{};
+// One drained record of the modulation monitor (fmr_monitor_*: histogram of hist_bins counters, one-sided PSD of the MPX,
+// 513 bins of 375 Hz) or of the RF monitor (fmr_rf_monitor_*: 384 bins, eight per octave of power; the PSD of |x|^2), with
+// the levels derived from it alone
+template <class Rec, class Levels>
+struct MonitorRecord {
+  Rec rec{};
   std::vector<uint32_t> hist;
   std::vector<double> psd;
-  fmr_monitor_levels levels{};
+  Levels levels{};
 };
-inline void monitor(fmr_chain *c, const fmr_monitor_config &m) {
-  check(fmr_enable_monitor(c, &m, sizeof m), "fmr_enable_monitor");
-}
-inline std::vector<ModulationRecord> monitor_records(fmr_chain *c, int stream) {
-  fmr_monitor_info info{};
-  const int ready = fmr_monitor_read(c, stream, nullptr, nullptr, nullptr, 0, &info, sizeof info);
-  if (ready < 0) check(ready, "fmr_monitor_read");
-  std::vector<ModulationRecord> out;
+using ModulationRecord = MonitorRecord<fmr_monitor_record, fmr_monitor_levels>;
+using RfRecord = MonitorRecord<fmr_rf_monitor_record, fmr_rf_monitor_levels>;
+// ... and all that wait, oldest first, record by record: read(rec, hist, psd, cap, info) and derive(r) are the monitor's
+// C functions
+template <class R, class Info, class Read, class Derive>
+std::vector<R> monitor_drain(const char *read_name, const char *derive_name, Read &&read, Derive &&derive) {
+  Info info{};
+  const int ready = read(nullptr, nullptr, nullptr, 0, &info);
+  if (ready < 0) check(ready, read_name);
+  std::vector<R> out;
   for (int i = 0; i < ready; i++) {
-    ModulationRecord r;
+    R r;
     r.hist.resize((size_t)info.hist_bins);
     r.psd.resize((size_t)info.psd_bins);
-    const int n = fmr_monitor_read(c, stream, &r.rec, r.hist.data(), r.psd.data(), 1, nullptr, 0);
-    if (n < 0) check(n, "fmr_monitor_read");
+    const int n = read(&r.rec, r.hist.data(), r.psd.data(), 1, nullptr);
+    if (n < 0) check(n, read_name);
     if (n == 0) break;
     r.levels.struct_size = sizeof r.levels;
-    check(fmr_monitor_derive(&r.rec, r.psd.data(), 1, &r.levels, sizeof r.levels), "fmr_monitor_derive");
+    check(derive(r), derive_name);
     out.push_back(std::move(r));
   }
   return out;
 }
-// audio monitor (fmr_enable_loudness / fmr_loudness_read / fmr_loudness_derive): the drained sub-block records in
-// ascending order and the levels derived from them together
-struct LoudnessReport {
-  std::vector<fmr_loudness_record> records;
-  fmr_loudness_info info{};
-  fmr_loudness_levels levels{};      // (of `records`; all zero when there are none)
+inline std::vector<ModulationRecord> monitor_records(fmr_chain *c, int stream) {
+  return monitor_drain<ModulationRecord, fmr_monitor_info>(
+      "fmr_monitor_read", "fmr_monitor_derive",
+      [&](fmr_monitor_record *rec, uint32_t *hist, double *psd, int cap, fmr_monitor_info *info) {
+        return fmr_monitor_read(c, stream, rec, hist, psd, cap, info, info ? sizeof *info : 0);
+      },
+      [](ModulationRecord &r) { return fmr_monitor_derive(&r.rec, r.psd.data(), 1, &r.levels, sizeof r.levels); });
+}
+inline std::vector<RfRecord> rf_records(fmr_chain *c, int stream) {
+  return monitor_drain<RfRecord, fmr_rf_monitor_info>(
+      "fmr_rf_monitor_read", "fmr_rf_monitor_derive",
+      [&](fmr_rf_monitor_record *rec, uint32_t *hist, double *psd, int cap, fmr_rf_monitor_info *info) {
+        return fmr_rf_monitor_read(c, stream, rec, hist, psd, cap, info, info ? sizeof *info : 0);
+      },
+      [](RfRecord &r) { return fmr_rf_monitor_derive(&r.rec, r.hist.data(), r.psd.data(), 1, &r.levels, sizeof r.levels); });
+}
+
+// What waits on one stream (or input row) of a stage whose records are pooled: the drained records in ascending order and
+// the levels derived from them together.  The audio monitor (fmr_loudness_*), weak-signal handling (fmr_weak_signal_*),
+// the impulse blanker (fmr_blanker_*) and the DC-offset and IQ-imbalance correction (fmr_iq_correction_*) report so.
+template <class Rec, class Info, class Levels>
+struct Report {
+  std::vector<Rec> records;
+  Info info{};
+  Levels levels{};      // (of `records`; all zero when there are none)
 };
-inline void loudness(fmr_chain *c, const fmr_loudness_config &m) {
-  check(fmr_enable_loudness(c, &m, sizeof m), "fmr_enable_loudness");
+using LoudnessReport = Report<fmr_loudness_record, fmr_loudness_info, fmr_loudness_levels>;
+using WeakSignalReport = Report<fmr_weak_signal_record, fmr_weak_signal_info, fmr_weak_signal_levels>;
+using BlankerReport = Report<fmr_blanker_record, fmr_blanker_info, fmr_blanker_levels>;
+using IqCorrectionReport = Report<fmr_iq_correction_record, fmr_iq_correction_info, fmr_iq_correction_levels>;
+// count (cap = 0), size, read, derive: read(recs, cap, info, info_size) and derive(recs, n, levels, levels_size) are the
+// stage's C functions
+template <class R, class Read, class Derive>
+R report(const char *read_name, const char *derive_name, Read &&read, Derive &&derive) {
+  R out;
+  const int ready = read(nullptr, 0, &out.info, sizeof out.info);
+  if (ready < 0) check(ready, read_name);
+  if (ready == 0) return out;
+  out.records.resize((size_t)ready);
+  const int n = read(out.records.data(), ready, &out.info, sizeof out.info);
+  if (n < 0) check(n, read_name);
+  out.records.resize((size_t)n);
+  if (n > 0) check(derive(out.records.data(), n, &out.levels, sizeof out.levels), derive_name);
+  return out;
 }
 inline LoudnessReport loudness_report(fmr_chain *c, int stream, double silence_dbfs) {
-  LoudnessReport out;
-  const int ready = fmr_loudness_read(c, stream, nullptr, 0, &out.info, sizeof out.info);
-  if (ready < 0) check(ready, "fmr_loudness_read");
-  if (ready == 0) return out;
-  out.records.resize((size_t)ready);
-  const int n = fmr_loudness_read(c, stream, out.records.data(), ready, &out.info, sizeof out.info);
-  if (n < 0) check(n, "fmr_loudness_read");
-  out.records.resize((size_t)n);
-  if (n > 0) check(fmr_loudness_derive(out.records.data(), n, silence_dbfs, &out.levels, sizeof out.levels), "fmr_loudness_derive");
-  return out;
-}
-
-// weak-signal handling (fmr_enable_weak_signal / fmr_weak_signal_read / fmr_weak_signal_derive): the drained records in
-// ascending order and the levels pooled from them
-struct WeakSignalReport {
-  std::vector<fmr_weak_signal_record> records;
-  fmr_weak_signal_info info{};
-  fmr_weak_signal_levels levels{};   // (of `records`; all zero when there are none)
-};
-inline void weak_signal(fmr_chain *c, const fmr_weak_signal_config &m) {
-  check(fmr_enable_weak_signal(c, &m, sizeof m), "fmr_enable_weak_signal");
+  return report<LoudnessReport>(
+      "fmr_loudness_read", "fmr_loudness_derive", [&](auto... a) { return fmr_loudness_read(c, stream, a...); },
+      [&](const fmr_loudness_record *r, int n, auto... a) { return fmr_loudness_derive(r, n, silence_dbfs, a...); });
 }
 inline WeakSignalReport weak_signal_report(fmr_chain *c, int stream) {
-  WeakSignalReport out;
-  const int ready = fmr_weak_signal_read(c, stream, nullptr, 0, &out.info, sizeof out.info);
-  if (ready < 0) check(ready, "fmr_weak_signal_read");
-  if (ready == 0) return out;
-  out.records.resize((size_t)ready);
-  const int n = fmr_weak_signal_read(c, stream, out.records.data(), ready, &out.info, sizeof out.info);
-  if (n < 0) check(n, "fmr_weak_signal_read");
-  out.records.resize((size_t)n);
-  if (n > 0) check(fmr_weak_signal_derive(out.records.data(), n, &out.levels, sizeof out.levels), "fmr_weak_signal_derive");
-  return out;
-}
-
-// impulse blanker on the capture (fmr_enable_blanker / fmr_blanker_read / fmr_blanker_derive): the drained records of one
-// input row in ascending order and the levels pooled from them
-struct BlankerReport {
-  std::vector<fmr_blanker_record> records;
-  fmr_blanker_info info{};
-  fmr_blanker_levels levels{};   // (of `records`; all zero when there are none)
-};
-inline void blanker(fmr_chain *c, const fmr_blanker_config &m) {
-  check(fmr_enable_blanker(c, &m, sizeof m), "fmr_enable_blanker");
+  return report<WeakSignalReport>("fmr_weak_signal_read", "fmr_weak_signal_derive",
+                                  [&](auto... a) { return fmr_weak_signal_read(c, stream, a...); },
+                                  [](auto... a) { return fmr_weak_signal_derive(a...); });
 }
 inline BlankerReport blanker_report(fmr_chain *c, int row, double input_rate) {
-  BlankerReport out;
-  const int ready = fmr_blanker_read(c, row, nullptr, 0, &out.info, sizeof out.info);
-  if (ready < 0) check(ready, "fmr_blanker_read");
-  if (ready == 0) return out;
-  out.records.resize((size_t)ready);
-  const int n = fmr_blanker_read(c, row, out.records.data(), ready, &out.info, sizeof out.info);
-  if (n < 0) check(n, "fmr_blanker_read");
-  out.records.resize((size_t)n);
-  if (n > 0) check(fmr_blanker_derive(out.records.data(), n, input_rate, &out.levels, sizeof out.levels), "fmr_blanker_derive");
-  return out;
-}
-
-// DC-offset and IQ-imbalance correction on the capture (fmr_enable_iq_correction / fmr_iq_correction_read /
-// fmr_iq_correction_derive): the drained records of one input row in ascending order and the levels pooled from them
-struct IqCorrectionReport {
-  std::vector<fmr_iq_correction_record> records;
-  fmr_iq_correction_info info{};
-  fmr_iq_correction_levels levels{};   // (of `records`; all zero when there are none)
-};
-inline void iq_correction(fmr_chain *c, const fmr_iq_correction_config &m) {
-  check(fmr_enable_iq_correction(c, &m, sizeof m), "fmr_enable_iq_correction");
+  return report<BlankerReport>(
+      "fmr_blanker_read", "fmr_blanker_derive", [&](auto... a) { return fmr_blanker_read(c, row, a...); },
+      [&](const fmr_blanker_record *r, int n, auto... a) { return fmr_blanker_derive(r, n, input_rate, a...); });
 }
 inline IqCorrectionReport iq_correction_report(fmr_chain *c, int row) {
-  IqCorrectionReport out;
-  const int ready = fmr_iq_correction_read(c, row, nullptr, 0, &out.info, sizeof out.info);
-  if (ready < 0) check(ready, "fmr_iq_correction_read");
-  if (ready == 0) return out;
-  out.records.resize((size_t)ready);
-  const int n = fmr_iq_correction_read(c, row, out.records.data(), ready, &out.info, sizeof out.info);
-  if (n < 0) check(n, "fmr_iq_correction_read");
-  out.records.resize((size_t)n);
-  if (n > 0) check(fmr_iq_correction_derive(out.records.data(), n, &out.levels, sizeof out.levels), "fmr_iq_correction_derive");
-  return out;
+  return report<IqCorrectionReport>("fmr_iq_correction_read", "fmr_iq_correction_derive",
+                                    [&](auto... a) { return fmr_iq_correction_read(c, row, a...); },
+                                    [](auto... a) { return fmr_iq_correction_derive(a...); });
 }
 
 // audio analyser (fmr_enable_analyser / fmr_analyser_read / fmr_analyser_derive): the drained records in ascending order
@@ -223,14 +202,6 @@ struct AnalyserReport {
   fmr_analyser_info info{};
   fmr_analyser_levels levels{};      // (of `records`; all zero when there are none)
 };
-inline fmr_analyser_config analyser_config(int fft_size, uint32_t interval_samples, int max_records) {
-  fmr_analyser_config m{};
-  m.struct_size = sizeof m; m.fft_size = fft_size; m.interval_samples = interval_samples; m.max_records = max_records;
-  return m;
-}
-inline void analyser(fmr_chain *c, const fmr_analyser_config &m) {
-  check(fmr_enable_analyser(c, &m, sizeof m), "fmr_enable_analyser");
-}
 // (one read, sized by the ring of cfg: no more than max_records can wait, and every read synchronises the chain)
 inline AnalyserReport analyser_report(fmr_chain *c, int stream, const fmr_analyser_config &cfg, const fmr_analyser_rule &rule) {
   AnalyserReport out;
@@ -253,37 +224,6 @@ inline fmr_analyser_rule analyser_rule(int view = 0, double tone_hz = 0.0) {
   return r;
 }
 
-// RF monitor (fmr_enable_rf_monitor / fmr_rf_monitor_read / fmr_rf_monitor_derive): one drained record with its
-// histogram (384 bins, eight per octave of power), the one-sided PSD of |x|^2 (513 bins of 375 Hz) and the levels
-// derived from it alone
-struct RfRecord {
-  fmr_rf_monitor_record rec{};
-  std::vector<uint32_t> hist;
-  std::vector<double> psd;
-  fmr_rf_monitor_levels levels{};
-};
-inline void rf_monitor(fmr_chain *c, const fmr_rf_monitor_config &m) {
-  check(fmr_enable_rf_monitor(c, &m, sizeof m), "fmr_enable_rf_monitor");
-}
-inline std::vector<RfRecord> rf_records(fmr_chain *c, int stream) {
-  fmr_rf_monitor_info info{};
-  const int ready = fmr_rf_monitor_read(c, stream, nullptr, nullptr, nullptr, 0, &info, sizeof info);
-  if (ready < 0) check(ready, "fmr_rf_monitor_read");
-  std::vector<RfRecord> out;
-  for (int i = 0; i < ready; i++) {
-    RfRecord r;
-    r.hist.resize((size_t)info.hist_bins);
-    r.psd.resize((size_t)info.psd_bins);
-    const int n = fmr_rf_monitor_read(c, stream, &r.rec, r.hist.data(), r.psd.data(), 1, nullptr, 0);
-    if (n < 0) check(n, "fmr_rf_monitor_read");
-    if (n == 0) break;
-    r.levels.struct_size = sizeof r.levels;
-    check(fmr_rf_monitor_derive(&r.rec, r.hist.data(), r.psd.data(), 1, &r.levels, sizeof r.levels), "fmr_rf_monitor_derive");
-    out.push_back(std::move(r));
-  }
-  return out;
-}
-
 // output stage (fmr_enable_output / fmr_output_read): everything that waits on one stream -- the PCM frames as bytes
 // (interleaved int16 or float32, what AudioFileWriter::write_i16 / write_f32 take as they are) and the block records
 struct OutputData {
@@ -300,11 +240,6 @@ inline fmr_output_config output_config(int format, double squelch_level, double 
   m.struct_size = sizeof m; m.format = format; m.squelch_level = squelch_level; m.gain = gain;
   m.max_frames = max_frames; m.max_blocks = max_blocks;
   return m;
-}
-// (r: fmr_set_output_rate behind it when a rate or mono is asked for)
-inline void output(fmr_chain *c, const fmr_output_config &m, const fmr_output_rate_config &r) {
-  check(fmr_enable_output(c, &m, sizeof m), "fmr_enable_output");
-  if (r.rate != 0 || r.mono != 0) check(fmr_set_output_rate(c, &r, sizeof r), "fmr_set_output_rate");
 }
 inline fmr_output_rate_config output_rate_config(int rate, bool mono) {
   fmr_output_rate_config r{};
@@ -346,9 +281,6 @@ inline fmr_mpx_output_config mpx_output_config(int format, int rate, double gain
   m.struct_size = sizeof m; m.format = format; m.rate = rate; m.gain = gain; m.max_frames = max_frames;
   return m;
 }
-inline void mpx_output(fmr_chain *c, const fmr_mpx_output_config &m) {
-  check(fmr_enable_mpx_output(c, &m, sizeof m), "fmr_enable_mpx_output");
-}
 inline MpxOutputData mpx_output_data(fmr_chain *c, int stream) {
   MpxOutputData out;
   int rc = fmr_mpx_output_read(c, stream, nullptr, 0, nullptr, &out.info, sizeof out.info);
@@ -361,6 +293,74 @@ inline MpxOutputData mpx_output_data(fmr_chain *c, int stream) {
   out.pcm.resize(out.frames * fb);
   return out;
 }
+
+// The optional stages a decoder object has enabled on its chain, each with its configuration.  The members enable a stage
+// (fmr_enable_*: before the first process(), once) and remember it; apply() enables on a chain made anew -- for a front
+// end, for RDS, for a larger batch -- what the one before it had.  A stage added here is added to apply().
+struct Stages {
+  std::optional<fmr_monitor_config> mon;
+  std::optional<fmr_loudness_config> ld;
+  std::optional<fmr_weak_signal_config> ws;
+  std::optional<fmr_iq_correction_config> iqc;
+  std::optional<fmr_blanker_config> nb;
+  std::optional<fmr_rf_monitor_config> rf;
+  std::optional<fmr_output_config> out;
+  fmr_output_rate_config out_rate{};
+  std::optional<fmr_analyser_config> an;
+  std::optional<fmr_mpx_output_config> mpx;
+
+  void monitor(fmr_chain *c, uint32_t interval_samples, int hist_bins, double hist_range, int max_records) {
+    fmr_monitor_config m{};
+    m.interval_samples = interval_samples; m.hist_bins = hist_bins; m.hist_range = hist_range; m.max_records = max_records;
+    enable(c, mon, m, fmr_enable_monitor, "fmr_enable_monitor");
+  }
+  void loudness(fmr_chain *c, uint32_t step_samples, int max_records) {
+    fmr_loudness_config m{};
+    m.step_samples = step_samples; m.max_records = max_records;
+    enable(c, ld, m, fmr_enable_loudness, "fmr_enable_loudness");
+  }
+  void weak_signal(fmr_chain *c, const fmr_weak_signal_config &m) { enable(c, ws, m, fmr_enable_weak_signal, "fmr_enable_weak_signal"); }
+  void iq_correction(fmr_chain *c, const fmr_iq_correction_config &m) { enable(c, iqc, m, fmr_enable_iq_correction, "fmr_enable_iq_correction"); }
+  void blanker(fmr_chain *c, const fmr_blanker_config &m) { enable(c, nb, m, fmr_enable_blanker, "fmr_enable_blanker"); }
+  void rf_monitor(fmr_chain *c, uint32_t interval_samples, int max_records) {
+    fmr_rf_monitor_config m{};
+    m.interval_samples = interval_samples; m.max_records = max_records;
+    enable(c, rf, m, fmr_enable_rf_monitor, "fmr_enable_rf_monitor");
+  }
+  // (fmr_set_output_rate behind it when a rate or mono is asked for)
+  void output(fmr_chain *c, const fmr_output_config &m, const fmr_output_rate_config &r) {
+    enable(c, out, m, fmr_enable_output, "fmr_enable_output");
+    out_rate = r;
+    if (r.rate != 0 || r.mono != 0) check(fmr_set_output_rate(c, &r, sizeof r), "fmr_set_output_rate");
+  }
+  void analyser(fmr_chain *c, int fft_size, uint32_t interval_samples, int max_records) {
+    fmr_analyser_config m{};
+    m.fft_size = fft_size; m.interval_samples = interval_samples; m.max_records = max_records;
+    enable(c, an, m, fmr_enable_analyser, "fmr_enable_analyser");
+  }
+  fmr_analyser_config analyser_cfg() const { return an.value_or(fmr_analyser_config{}); }      // (what analyser_report sizes its read by)
+  void mpx_output(fmr_chain *c, const fmr_mpx_output_config &m) { enable(c, mpx, m, fmr_enable_mpx_output, "fmr_enable_mpx_output"); }
+
+  void apply(fmr_chain *c) {
+    if (mon) enable(c, mon, *mon, fmr_enable_monitor, "fmr_enable_monitor");
+    if (ld) enable(c, ld, *ld, fmr_enable_loudness, "fmr_enable_loudness");
+    if (ws) weak_signal(c, *ws);
+    if (iqc) iq_correction(c, *iqc);
+    if (nb) blanker(c, *nb);
+    if (rf) enable(c, rf, *rf, fmr_enable_rf_monitor, "fmr_enable_rf_monitor");
+    if (out) output(c, *out, fmr_output_rate_config(out_rate));
+    if (an) enable(c, an, *an, fmr_enable_analyser, "fmr_enable_analyser");
+    if (mpx) mpx_output(c, *mpx);
+  }
+
+private:
+  template <class Cfg, class Fn>
+  static void enable(fmr_chain *c, std::optional<Cfg> &slot, Cfg m, Fn *fn, const char *name) {
+    m.struct_size = sizeof m;
+    check(fn(c, &m, sizeof m), name);
+    slot = m;
+  }
+};
 }  // namespace fmr_detail
 using OutputData = fmr_detail::OutputData;
 using MpxOutputData = fmr_detail::MpxOutputData;
@@ -466,8 +466,7 @@ public:
   // what the resampler reads).  read_blanker() drains the complete records and pools them.
   void enable_blanker(fmr_blanker_config cfg = fmr_blanker_config{}) {
     if (!m_chain) fmr_detail::fail("IfResampler::enable_blanker: equal rates, nothing is resampled");
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::blanker(m_chain, cfg);
+    m_stages.blanker(m_chain, cfg);
   }
   BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_rate); }
   // DC-offset and IQ-imbalance correction of the same input (fmr_enable_iq_correction), under the same rules as
@@ -476,14 +475,14 @@ public:
   // records and pools them.
   void enable_iq_correction(fmr_iq_correction_config cfg = fmr_iq_correction_config{}) {
     if (!m_chain) fmr_detail::fail("IfResampler::enable_iq_correction: equal rates, nothing is resampled");
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::iq_correction(m_chain, cfg);
+    m_stages.iq_correction(m_chain, cfg);
   }
   IqCorrectionReport read_iq_correction() { return fmr_detail::iq_correction_report(m_chain, 0); }
 
 private:
   fmr_chain *m_chain = nullptr;
   double m_rate = 0.0;
+  fmr_detail::Stages m_stages;
 };
 
 // PilotPhaseLock::PpsEvent (PilotPhaseLock.h:40-44)
@@ -526,15 +525,7 @@ public:
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg, m_rds);
-    if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
-    if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
-    if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
-    if (m_iqc) fmr_detail::iq_correction(m_chain, m_iqc_cfg);
-    if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
-    if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
-    if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
-    if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
-    if (m_mpx) fmr_detail::mpx_output(m_chain, m_mpx_cfg);
+    m_stages.apply(m_chain);
   }
 
   // RDS (no counterpart in the reference; fmr_create_rds): re-creates the chain with the RDS decoder, before the first
@@ -544,15 +535,7 @@ public:
     m_rds = true;
     fmr_destroy(m_chain);
     m_chain = fmr_detail::make(m_cfg, true);
-    if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
-    if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
-    if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
-    if (m_iqc) fmr_detail::iq_correction(m_chain, m_iqc_cfg);
-    if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
-    if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
-    if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
-    if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
-    if (m_mpx) fmr_detail::mpx_output(m_chain, m_mpx_cfg);
+    m_stages.apply(m_chain);
   }
   // error correction of the RDS blocks (fmr_set_rds_correction: FMR_RDS_FEC_OFF / _BURST / _SOFT; 0 = the defaults); at
   // any time after enable_rds(), from the decoder's next block boundary on.  enable_rds() starts with it off.
@@ -567,11 +550,7 @@ public:
   // read_modulation_records() drains the complete ones, oldest first.
   void enable_modulation_monitor(uint32_t interval_samples = 0, int hist_bins = 0, double hist_range = 0.0, int max_records = 0) {
     if (m_started) fmr_detail::fail("FmDecoder::enable_modulation_monitor: after the first process()");
-    m_mon_cfg = fmr_monitor_config{};
-    m_mon_cfg.struct_size = sizeof m_mon_cfg; m_mon_cfg.interval_samples = interval_samples; m_mon_cfg.hist_bins = hist_bins;
-    m_mon_cfg.hist_range = hist_range; m_mon_cfg.max_records = max_records;
-    fmr_detail::monitor(m_chain, m_mon_cfg);
-    m_mon = true;
+    m_stages.monitor(m_chain, interval_samples, hist_bins, hist_range, max_records);
   }
   std::vector<ModulationRecord> read_modulation_records() { return fmr_detail::monitor_records(m_chain, 0); }
 
@@ -580,10 +559,7 @@ public:
   // process(), once.  read_loudness() drains the complete ones and derives loudness, peaks, correlation and silence.
   void enable_loudness(uint32_t step_samples = 0, int max_records = 0) {
     if (m_started) fmr_detail::fail("FmDecoder::enable_loudness: after the first process()");
-    m_ld_cfg = fmr_loudness_config{};
-    m_ld_cfg.struct_size = sizeof m_ld_cfg; m_ld_cfg.step_samples = step_samples; m_ld_cfg.max_records = max_records;
-    fmr_detail::loudness(m_chain, m_ld_cfg);
-    m_ld = true;
+    m_stages.loudness(m_chain, step_samples, max_records);
   }
   LoudnessReport read_loudness(double silence_dbfs = -60.0) { return fmr_detail::loudness_report(m_chain, 0, silence_dbfs); }
 
@@ -593,10 +569,7 @@ public:
   // the complete records and pools them.
   void enable_weak_signal(fmr_weak_signal_config cfg = fmr_weak_signal_config{}) {
     if (m_started) fmr_detail::fail("FmDecoder::enable_weak_signal: after the first process()");
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::weak_signal(m_chain, cfg);
-    m_ws_cfg = cfg;
-    m_ws = true;
+    m_stages.weak_signal(m_chain, cfg);
   }
   WeakSignalReport read_weak_signal() { return fmr_detail::weak_signal_report(m_chain, 0); }
 
@@ -606,10 +579,7 @@ public:
   // reads).  read_blanker() drains the complete records and pools them.
   void enable_blanker(fmr_blanker_config cfg = fmr_blanker_config{}) {
     if (m_started) fmr_detail::fail("FmDecoder::enable_blanker: after the first process()");
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::blanker(m_chain, cfg);
-    m_nb_cfg = cfg;
-    m_nb = true;
+    m_stages.blanker(m_chain, cfg);
   }
   BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_cfg.input_rate); }
   // DC-offset and IQ-imbalance correction of the same input (fmr_enable_iq_correction), under the same rules as
@@ -618,10 +588,7 @@ public:
   // records and pools them.
   void enable_iq_correction(fmr_iq_correction_config cfg = fmr_iq_correction_config{}) {
     if (m_started) fmr_detail::fail("FmDecoder::enable_iq_correction: after the first process()");
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::iq_correction(m_chain, cfg);
-    m_iqc_cfg = cfg;
-    m_iqc = true;
+    m_stages.iq_correction(m_chain, cfg);
   }
   IqCorrectionReport read_iq_correction() { return fmr_detail::iq_correction_report(m_chain, 0); }
 
@@ -630,10 +597,7 @@ public:
   // read_rf_records() drains the complete ones, oldest first.
   void enable_rf_monitor(uint32_t interval_samples = 0, int max_records = 0) {
     if (m_started) fmr_detail::fail("FmDecoder::enable_rf_monitor: after the first process()");
-    m_rf_cfg = fmr_rf_monitor_config{};
-    m_rf_cfg.struct_size = sizeof m_rf_cfg; m_rf_cfg.interval_samples = interval_samples; m_rf_cfg.max_records = max_records;
-    fmr_detail::rf_monitor(m_chain, m_rf_cfg);
-    m_rf = true;
+    m_stages.rf_monitor(m_chain, interval_samples, max_records);
   }
   std::vector<RfRecord> read_rf_records() { return fmr_detail::rf_records(m_chain, 0); }
 
@@ -645,10 +609,8 @@ public:
   void enable_output(int format = FMR_PCM_S16, double squelch_level = 0.0, double gain = 0.0, uint32_t max_frames = 0,
                      uint32_t max_blocks = 0, int rate = 0, bool mono = false) {
     if (m_started) fmr_detail::fail("FmDecoder::enable_output: after the first process()");
-    m_out_cfg = fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks);
-    m_out_rate = fmr_detail::output_rate_config(rate, mono);
-    fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
-    m_out = true;
+    m_stages.output(m_chain, fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks),
+                    fmr_detail::output_rate_config(rate, mono));
   }
   OutputData read_output() { return fmr_detail::output_data(m_chain, 0); }
   fmr_output_rate_info output_rate_info() { return fmr_detail::output_rate_info(m_chain, 0); }
@@ -657,9 +619,7 @@ public:
   // (full scale +-150 kHz); before the first process(), once.  read_mpx_output() drains everything that waits.
   void enable_mpx_output(int format = FMR_PCM_S16, int rate = 192000, double gain = 0.0, uint32_t max_frames = 0) {
     if (m_started) fmr_detail::fail("FmDecoder::enable_mpx_output: after the first process()");
-    m_mpx_cfg = fmr_detail::mpx_output_config(format, rate, gain, max_frames);
-    fmr_detail::mpx_output(m_chain, m_mpx_cfg);
-    m_mpx = true;
+    m_stages.mpx_output(m_chain, fmr_detail::mpx_output_config(format, rate, gain, max_frames));
   }
   MpxOutputData read_mpx_output() { return fmr_detail::mpx_output_data(m_chain, 0); }
   // Audio analyser (the spectrum analyser the reference's author judges receivers with, on the device;
@@ -667,12 +627,10 @@ public:
   // of the channels; before the first process(), once.  read_analyser() drains the complete ones and derives tone, THD,
   // THD+N, SINAD and noise of all of them pooled (view 0 = L .. 3 = S; tone_hz 0 = the strongest bin of 20 Hz .. 15 kHz).
   void enable_analyser(int fft_size = 0, uint32_t interval_samples = 0, int max_records = 0) {
-    m_an_cfg = fmr_detail::analyser_config(fft_size, interval_samples, max_records);
-    fmr_detail::analyser(m_chain, m_an_cfg);
-    m_an = true;
+    m_stages.analyser(m_chain, fft_size, interval_samples, max_records);
   }
   AnalyserReport read_analyser(int view = 0, double tone_hz = 0.0) {
-    return fmr_detail::analyser_report(m_chain, 0, m_an_cfg, fmr_detail::analyser_rule(view, tone_hz));
+    return fmr_detail::analyser_report(m_chain, 0, m_stages.analyser_cfg(), fmr_detail::analyser_rule(view, tone_hz));
   }
 
   // Latency for throughput: hold back `blocks` - 1 calls and decode `blocks` blocks in ONE batched call.  process()
@@ -694,15 +652,7 @@ public:
       fmr_destroy(m_chain);
       m_cfg.max_blocks = (int)blocks;
       m_chain = fmr_detail::make(m_cfg, m_rds);
-    if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
-    if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
-    if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
-    if (m_iqc) fmr_detail::iq_correction(m_chain, m_iqc_cfg);
-    if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
-    if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
-    if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
-    if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
-    if (m_mpx) fmr_detail::mpx_output(m_chain, m_mpx_cfg);
+      m_stages.apply(m_chain);
       m_capacity = blocks;
     }
     m_batch = blocks;
@@ -795,25 +745,7 @@ private:
     m_pps_fetched = true;
   }
   fmr_config m_cfg{};
-  bool m_mon = false;
-  fmr_monitor_config m_mon_cfg{};
-  bool m_ld = false;
-  fmr_loudness_config m_ld_cfg{};
-  bool m_ws = false;
-  fmr_weak_signal_config m_ws_cfg{};
-  bool m_mpx = false;
-  fmr_mpx_output_config m_mpx_cfg{};
-  bool m_nb = false;
-  fmr_blanker_config m_nb_cfg{};
-  bool m_iqc = false;
-  fmr_iq_correction_config m_iqc_cfg{};
-  bool m_rf = false;
-  fmr_rf_monitor_config m_rf_cfg{};
-  bool m_an = false;
-  fmr_analyser_config m_an_cfg{};
-  bool m_out = false;
-  fmr_output_config m_out_cfg{};
-  fmr_output_rate_config m_out_rate{};
+  fmr_detail::Stages m_stages;
   fmr_chain *m_chain = nullptr;
   bool m_rds = false;
   fmr_rds::Station m_station;
@@ -882,25 +814,20 @@ public:
   const fmr_rds::Station &rds_station() { get_rds_groups(); return m_station; }
   // the stages an MPX decoder accepts, as FmDecoder's (before the first process(), once each)
   void enable_modulation_monitor(uint32_t interval_samples = 0, int hist_bins = 0, double hist_range = 0.0, int max_records = 0) {
-    fmr_monitor_config m{};
-    m.struct_size = sizeof m; m.interval_samples = interval_samples; m.hist_bins = hist_bins; m.hist_range = hist_range;
-    m.max_records = max_records;
-    fmr_detail::monitor(m_chain, m);
+    m_stages.monitor(m_chain, interval_samples, hist_bins, hist_range, max_records);
   }
   std::vector<ModulationRecord> read_modulation_records() { return fmr_detail::monitor_records(m_chain, 0); }
   void enable_loudness(uint32_t step_samples = 0, int max_records = 0) {
-    fmr_loudness_config m{};
-    m.struct_size = sizeof m; m.step_samples = step_samples; m.max_records = max_records;
-    fmr_detail::loudness(m_chain, m);
+    m_stages.loudness(m_chain, step_samples, max_records);
   }
   LoudnessReport read_loudness(double silence_dbfs = -60.0) { return fmr_detail::loudness_report(m_chain, 0, silence_dbfs); }
   void enable_output(int format = FMR_PCM_S16, double gain = 0.0, uint32_t max_frames = 0, uint32_t max_blocks = 0, int rate = 0,
                      bool mono = false) {      // (no squelch: there is no IF level)
-    fmr_detail::output(m_chain, fmr_detail::output_config(format, 0.0, gain, max_frames, max_blocks), fmr_detail::output_rate_config(rate, mono));
+    m_stages.output(m_chain, fmr_detail::output_config(format, 0.0, gain, max_frames, max_blocks), fmr_detail::output_rate_config(rate, mono));
   }
   OutputData read_output() { return fmr_detail::output_data(m_chain, 0); }
   void enable_mpx_output(int format = FMR_PCM_S16, int rate = 192000, double gain = 0.0, uint32_t max_frames = 0) {
-    fmr_detail::mpx_output(m_chain, fmr_detail::mpx_output_config(format, rate, gain, max_frames));
+    m_stages.mpx_output(m_chain, fmr_detail::mpx_output_config(format, rate, gain, max_frames));
   }
   MpxOutputData read_mpx_output() { return fmr_detail::mpx_output_data(m_chain, 0); }
 
@@ -921,6 +848,7 @@ private:
   fmr_chain *m_chain = nullptr;
   int m_format;
   fmr_rds::Station m_station;
+  fmr_detail::Stages m_stages;
 };
 
 // AmDecoder (AmDecode.h:48-65), all of its modes: AM, DSB, USB, LSB, CW, WSPR
@@ -946,18 +874,12 @@ public:
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg);
-    if (m_iqc) fmr_detail::iq_correction(m_chain, m_iqc_cfg);
-    if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
-    if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
-    if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
+    m_stages.apply(m_chain);
   }
   // Impulse blanker on the source-rate input (fmr_enable_blanker): after attach_front_end(), before the first process(),
   // once; cfg: the fields to set (zeros = the defaults).  read_blanker() drains the complete records and pools them.
   void enable_blanker(fmr_blanker_config cfg = fmr_blanker_config{}) {
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::blanker(m_chain, cfg);
-    m_nb_cfg = cfg;
-    m_nb = true;
+    m_stages.blanker(m_chain, cfg);
   }
   BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_cfg.input_rate); }
   // DC-offset and IQ-imbalance correction of the same input (fmr_enable_iq_correction), under the same rules as
@@ -965,10 +887,7 @@ public:
   // only, FMR_IQC_ACT corrects what the blanker and the front end read).  read_iq_correction() drains the complete
   // records and pools them.
   void enable_iq_correction(fmr_iq_correction_config cfg = fmr_iq_correction_config{}) {
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::iq_correction(m_chain, cfg);
-    m_iqc_cfg = cfg;
-    m_iqc = true;
+    m_stages.iq_correction(m_chain, cfg);
   }
   IqCorrectionReport read_iq_correction() { return fmr_detail::iq_correction_report(m_chain, 0); }
   // Output stage (fmr_enable_output): squelch, gain, PCM frames and the per-block IF / AF meters on the device; before
@@ -976,10 +895,8 @@ public:
   // that waits.
   void enable_output(int format = FMR_PCM_S16, double squelch_level = 0.0, double gain = 0.0, uint32_t max_frames = 0,
                      uint32_t max_blocks = 0, int rate = 0, bool mono = false) {
-    m_out_cfg = fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks);
-    m_out_rate = fmr_detail::output_rate_config(rate, mono);
-    fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
-    m_out = true;
+    m_stages.output(m_chain, fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks),
+                    fmr_detail::output_rate_config(rate, mono));
   }
   OutputData read_output() { return fmr_detail::output_data(m_chain, 0); }
   fmr_output_rate_info output_rate_info() { return fmr_detail::output_rate_info(m_chain, 0); }
@@ -988,12 +905,10 @@ public:
   // of the channels; before the first process(), once.  read_analyser() drains the complete ones and derives tone, THD,
   // THD+N, SINAD and noise of all of them pooled (view 0 = L .. 3 = S; tone_hz 0 = the strongest bin of 20 Hz .. 15 kHz).
   void enable_analyser(int fft_size = 0, uint32_t interval_samples = 0, int max_records = 0) {
-    m_an_cfg = fmr_detail::analyser_config(fft_size, interval_samples, max_records);
-    fmr_detail::analyser(m_chain, m_an_cfg);
-    m_an = true;
+    m_stages.analyser(m_chain, fft_size, interval_samples, max_records);
   }
   AnalyserReport read_analyser(int view = 0, double tone_hz = 0.0) {
-    return fmr_detail::analyser_report(m_chain, 0, m_an_cfg, fmr_detail::analyser_rule(view, tone_hz));
+    return fmr_detail::analyser_report(m_chain, 0, m_stages.analyser_cfg(), fmr_detail::analyser_rule(view, tone_hz));
   }
   void process(IQSampleVector samples_in, SampleVector &audio) {
     audio.resize(samples_in.size() + 64);
@@ -1015,15 +930,7 @@ private:
     return st;
   }
   fmr_config m_cfg{};
-  bool m_nb = false;
-  fmr_blanker_config m_nb_cfg{};
-  bool m_iqc = false;
-  fmr_iq_correction_config m_iqc_cfg{};
-  bool m_an = false;
-  fmr_analyser_config m_an_cfg{};
-  bool m_out = false;
-  fmr_output_config m_out_cfg{};
-  fmr_output_rate_config m_out_rate{};
+  fmr_detail::Stages m_stages;
   fmr_chain *m_chain = nullptr;
 };
 
@@ -1049,18 +956,12 @@ public:
     m_cfg.input_rate = input_rate; m_cfg.enable_resampler = 1; m_cfg.enable_fourth_down = fourth_down;
     m_cfg.resampler_class = resampler_class;
     m_chain = fmr_detail::make(m_cfg);
-    if (m_iqc) fmr_detail::iq_correction(m_chain, m_iqc_cfg);
-    if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
-    if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
-    if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
+    m_stages.apply(m_chain);
   }
   // Impulse blanker on the source-rate input (fmr_enable_blanker): after attach_front_end(), before the first process(),
   // once; cfg: the fields to set (zeros = the defaults).  read_blanker() drains the complete records and pools them.
   void enable_blanker(fmr_blanker_config cfg = fmr_blanker_config{}) {
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::blanker(m_chain, cfg);
-    m_nb_cfg = cfg;
-    m_nb = true;
+    m_stages.blanker(m_chain, cfg);
   }
   BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_cfg.input_rate); }
   // DC-offset and IQ-imbalance correction of the same input (fmr_enable_iq_correction), under the same rules as
@@ -1068,10 +969,7 @@ public:
   // only, FMR_IQC_ACT corrects what the blanker and the front end read).  read_iq_correction() drains the complete
   // records and pools them.
   void enable_iq_correction(fmr_iq_correction_config cfg = fmr_iq_correction_config{}) {
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::iq_correction(m_chain, cfg);
-    m_iqc_cfg = cfg;
-    m_iqc = true;
+    m_stages.iq_correction(m_chain, cfg);
   }
   IqCorrectionReport read_iq_correction() { return fmr_detail::iq_correction_report(m_chain, 0); }
   // Output stage (fmr_enable_output): squelch, gain, PCM frames and the per-block IF / AF meters on the device; before
@@ -1079,10 +977,8 @@ public:
   // that waits.
   void enable_output(int format = FMR_PCM_S16, double squelch_level = 0.0, double gain = 0.0, uint32_t max_frames = 0,
                      uint32_t max_blocks = 0, int rate = 0, bool mono = false) {
-    m_out_cfg = fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks);
-    m_out_rate = fmr_detail::output_rate_config(rate, mono);
-    fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
-    m_out = true;
+    m_stages.output(m_chain, fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks),
+                    fmr_detail::output_rate_config(rate, mono));
   }
   OutputData read_output() { return fmr_detail::output_data(m_chain, 0); }
   fmr_output_rate_info output_rate_info() { return fmr_detail::output_rate_info(m_chain, 0); }
@@ -1091,12 +987,10 @@ public:
   // of the channels; before the first process(), once.  read_analyser() drains the complete ones and derives tone, THD,
   // THD+N, SINAD and noise of all of them pooled (view 0 = L .. 3 = S; tone_hz 0 = the strongest bin of 20 Hz .. 15 kHz).
   void enable_analyser(int fft_size = 0, uint32_t interval_samples = 0, int max_records = 0) {
-    m_an_cfg = fmr_detail::analyser_config(fft_size, interval_samples, max_records);
-    fmr_detail::analyser(m_chain, m_an_cfg);
-    m_an = true;
+    m_stages.analyser(m_chain, fft_size, interval_samples, max_records);
   }
   AnalyserReport read_analyser(int view = 0, double tone_hz = 0.0) {
-    return fmr_detail::analyser_report(m_chain, 0, m_an_cfg, fmr_detail::analyser_rule(view, tone_hz));
+    return fmr_detail::analyser_report(m_chain, 0, m_stages.analyser_cfg(), fmr_detail::analyser_rule(view, tone_hz));
   }
   void process(const IQSampleVector &samples_in, SampleVector &audio) {
     audio.resize(samples_in.size() + 64);
@@ -1118,15 +1012,7 @@ private:
   }
   const double m_freq_dev;
   fmr_config m_cfg{};
-  bool m_nb = false;
-  fmr_blanker_config m_nb_cfg{};
-  bool m_iqc = false;
-  fmr_iq_correction_config m_iqc_cfg{};
-  bool m_an = false;
-  fmr_analyser_config m_an_cfg{};
-  bool m_out = false;
-  fmr_output_config m_out_cfg{};
-  fmr_output_rate_config m_out_rate{};
+  fmr_detail::Stages m_stages;
   fmr_chain *m_chain = nullptr;
 };
 
@@ -1170,15 +1056,7 @@ public:
     fmr_destroy(m_chain);
     m_cfg.channel_offset_hz = m_offsets.data();
     m_chain = fmr_detail::make(m_cfg, true);
-    if (m_mon) fmr_detail::monitor(m_chain, m_mon_cfg);
-    if (m_ld) fmr_detail::loudness(m_chain, m_ld_cfg);
-    if (m_ws) fmr_detail::weak_signal(m_chain, m_ws_cfg);
-    if (m_iqc) fmr_detail::iq_correction(m_chain, m_iqc_cfg);
-    if (m_nb) fmr_detail::blanker(m_chain, m_nb_cfg);
-    if (m_rf) fmr_detail::rf_monitor(m_chain, m_rf_cfg);
-    if (m_out) fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
-    if (m_an) fmr_detail::analyser(m_chain, m_an_cfg);
-    if (m_mpx) fmr_detail::mpx_output(m_chain, m_mpx_cfg);
+    m_stages.apply(m_chain);
     m_stations.assign(m_offsets.size(), fmr_rds::Station());
   }
   // error correction of every channel's RDS blocks (fmr_set_rds_correction), at any time after enable_rds()
@@ -1194,11 +1072,7 @@ public:
   // Modulation monitor of every channel (fmr_enable_monitor), before the first process(), once; FM banks only.
   // read_modulation_records(ch) drains channel ch's complete records, oldest first.
   void enable_modulation_monitor(uint32_t interval_samples = 0, int hist_bins = 0, double hist_range = 0.0, int max_records = 0) {
-    m_mon_cfg = fmr_monitor_config{};
-    m_mon_cfg.struct_size = sizeof m_mon_cfg; m_mon_cfg.interval_samples = interval_samples; m_mon_cfg.hist_bins = hist_bins;
-    m_mon_cfg.hist_range = hist_range; m_mon_cfg.max_records = max_records;
-    fmr_detail::monitor(m_chain, m_mon_cfg);
-    m_mon = true;
+    m_stages.monitor(m_chain, interval_samples, hist_bins, hist_range, max_records);
   }
   std::vector<ModulationRecord> read_modulation_records(size_t ch) {
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
@@ -1207,10 +1081,7 @@ public:
   // Audio monitor of every channel (fmr_enable_loudness), before the first process(), once; FM banks only.
   // read_loudness(ch) drains channel ch's complete records and derives their levels.
   void enable_loudness(uint32_t step_samples = 0, int max_records = 0) {
-    m_ld_cfg = fmr_loudness_config{};
-    m_ld_cfg.struct_size = sizeof m_ld_cfg; m_ld_cfg.step_samples = step_samples; m_ld_cfg.max_records = max_records;
-    fmr_detail::loudness(m_chain, m_ld_cfg);
-    m_ld = true;
+    m_stages.loudness(m_chain, step_samples, max_records);
   }
   LoudnessReport read_loudness(size_t ch, double silence_dbfs = -60.0) {
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
@@ -1219,10 +1090,7 @@ public:
   // Weak-signal handling of every channel (fmr_enable_weak_signal), before the first process(), once; FM banks only.
   // read_weak_signal(ch) drains channel ch's complete records and pools them.
   void enable_weak_signal(fmr_weak_signal_config cfg = fmr_weak_signal_config{}) {
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::weak_signal(m_chain, cfg);
-    m_ws_cfg = cfg;
-    m_ws = true;
+    m_stages.weak_signal(m_chain, cfg);
   }
   WeakSignalReport read_weak_signal(size_t ch) {
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
@@ -1231,10 +1099,7 @@ public:
   // Impulse blanker on the capture (fmr_enable_blanker), before the first process(), once: one row serves all channels.
   // read_blanker() drains the capture's complete records and pools them.
   void enable_blanker(fmr_blanker_config cfg = fmr_blanker_config{}) {
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::blanker(m_chain, cfg);
-    m_nb_cfg = cfg;
-    m_nb = true;
+    m_stages.blanker(m_chain, cfg);
   }
   BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_cfg.input_rate); }
   // DC-offset and IQ-imbalance correction of the same input (fmr_enable_iq_correction), under the same rules as
@@ -1242,32 +1107,24 @@ public:
   // only, FMR_IQC_ACT corrects what the blanker and the front end read).  read_iq_correction() drains the complete
   // records and pools them.
   void enable_iq_correction(fmr_iq_correction_config cfg = fmr_iq_correction_config{}) {
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::iq_correction(m_chain, cfg);
-    m_iqc_cfg = cfg;
-    m_iqc = true;
+    m_stages.iq_correction(m_chain, cfg);
   }
   IqCorrectionReport read_iq_correction() { return fmr_detail::iq_correction_report(m_chain, 0); }
 
   // Audio analyser of every channel (fmr_enable_analyser), before the first process(), once.  read_analyser(ch) drains
   // channel ch's complete records and derives their pooled levels.
   void enable_analyser(int fft_size = 0, uint32_t interval_samples = 0, int max_records = 0) {
-    m_an_cfg = fmr_detail::analyser_config(fft_size, interval_samples, max_records);
-    fmr_detail::analyser(m_chain, m_an_cfg);
-    m_an = true;
+    m_stages.analyser(m_chain, fft_size, interval_samples, max_records);
   }
   AnalyserReport read_analyser(size_t ch, int view = 0, double tone_hz = 0.0) {
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
-    return fmr_detail::analyser_report(m_chain, (int)ch, m_an_cfg, fmr_detail::analyser_rule(view, tone_hz));
+    return fmr_detail::analyser_report(m_chain, (int)ch, m_stages.analyser_cfg(), fmr_detail::analyser_rule(view, tone_hz));
   }
 
   // RF monitor of every channel (fmr_enable_rf_monitor), before the first process(), once; FM banks only.
   // read_rf_records(ch) drains channel ch's complete records, oldest first.
   void enable_rf_monitor(uint32_t interval_samples = 0, int max_records = 0) {
-    m_rf_cfg = fmr_rf_monitor_config{};
-    m_rf_cfg.struct_size = sizeof m_rf_cfg; m_rf_cfg.interval_samples = interval_samples; m_rf_cfg.max_records = max_records;
-    fmr_detail::rf_monitor(m_chain, m_rf_cfg);
-    m_rf = true;
+    m_stages.rf_monitor(m_chain, interval_samples, max_records);
   }
   std::vector<RfRecord> read_rf_records(size_t ch) {
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
@@ -1279,10 +1136,8 @@ public:
   // read_output(ch) drains channel ch's PCM frames and block records.
   void enable_output(int format = FMR_PCM_S16, double squelch_level = 0.0, double gain = 0.0, uint32_t max_frames = 0,
                      uint32_t max_blocks = 0, int rate = 0, bool mono = false) {
-    m_out_cfg = fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks);
-    m_out_rate = fmr_detail::output_rate_config(rate, mono);
-    fmr_detail::output(m_chain, m_out_cfg, m_out_rate);
-    m_out = true;
+    m_stages.output(m_chain, fmr_detail::output_config(format, squelch_level, gain, max_frames, max_blocks),
+                    fmr_detail::output_rate_config(rate, mono));
   }
   OutputData read_output(size_t ch) {
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
@@ -1295,9 +1150,7 @@ public:
   // MPX output of every channel (fmr_enable_mpx_output), before the first process(), once; FM banks only.
   // read_mpx_output(ch) drains channel ch's composite baseband as mono PCM at `rate`.
   void enable_mpx_output(int format = FMR_PCM_S16, int rate = 192000, double gain = 0.0, uint32_t max_frames = 0) {
-    m_mpx_cfg = fmr_detail::mpx_output_config(format, rate, gain, max_frames);
-    fmr_detail::mpx_output(m_chain, m_mpx_cfg);
-    m_mpx = true;
+    m_stages.mpx_output(m_chain, fmr_detail::mpx_output_config(format, rate, gain, max_frames));
   }
   MpxOutputData read_mpx_output(size_t ch) {
     if (ch >= m_offsets.size()) fmr_detail::fail("ChannelBank: channel index out of range");
@@ -1352,25 +1205,7 @@ private:
   double m_freq_dev;
   fmr_config m_cfg{};
   std::vector<fmr_rds::Station> m_stations;
-  bool m_mon = false;
-  fmr_monitor_config m_mon_cfg{};
-  bool m_ld = false;
-  fmr_loudness_config m_ld_cfg{};
-  bool m_ws = false;
-  fmr_weak_signal_config m_ws_cfg{};
-  bool m_mpx = false;
-  fmr_mpx_output_config m_mpx_cfg{};
-  bool m_nb = false;
-  fmr_blanker_config m_nb_cfg{};
-  bool m_iqc = false;
-  fmr_iq_correction_config m_iqc_cfg{};
-  bool m_rf = false;
-  fmr_rf_monitor_config m_rf_cfg{};
-  bool m_an = false;
-  fmr_analyser_config m_an_cfg{};
-  bool m_out = false;
-  fmr_output_config m_out_cfg{};
-  fmr_output_rate_config m_out_rate{};
+  fmr_detail::Stages m_stages;
   fmr_chain *m_chain = nullptr;
 };
 
@@ -1401,8 +1236,7 @@ public:
   // Impulse blanker on the capture (fmr_enable_blanker), before the first process(), once: one row serves all channels.
   // read_blanker() drains the capture's complete records and pools them.
   void enable_blanker(fmr_blanker_config cfg = fmr_blanker_config{}) {
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::blanker(m_chain, cfg);
+    m_stages.blanker(m_chain, cfg);
   }
   BlankerReport read_blanker() { return fmr_detail::blanker_report(m_chain, 0, m_rate); }
   // DC-offset and IQ-imbalance correction of the same input (fmr_enable_iq_correction), under the same rules as
@@ -1410,8 +1244,7 @@ public:
   // only, FMR_IQC_ACT corrects what the blanker and the front end read).  read_iq_correction() drains the complete
   // records and pools them.
   void enable_iq_correction(fmr_iq_correction_config cfg = fmr_iq_correction_config{}) {
-    cfg.struct_size = sizeof cfg;
-    fmr_detail::iq_correction(m_chain, cfg);
+    m_stages.iq_correction(m_chain, cfg);
   }
   IqCorrectionReport read_iq_correction() { return fmr_detail::iq_correction_report(m_chain, 0); }
 
@@ -1438,6 +1271,7 @@ private:
   size_t m_max_block;
   double m_rate = 0.0;
   fmr_chain *m_chain = nullptr;
+  fmr_detail::Stages m_stages;
 };
 
 // SpectrumMonitor (fmr_spectrum_*): the Welch power spectrum of a capture on the GPU (mean PSD, density-scaled, fftshift

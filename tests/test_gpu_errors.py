@@ -85,3 +85,61 @@ def test_unsupported_shapes_are_refused_at_create():
         fmr.Chain(mode=fmr.MODE_FM, input_rate=384e3, enable_resampler=False, input_format=fmr.IQ_S16, max_block_len=2048)
     with pytest.raises(fmr.FmrError):                     # a ratio outside the design range
         fmr.Chain(mode=fmr.MODE_NONE, input_rate=5e9, enable_resampler=True, max_block_len=2048)
+
+
+# The record stages' refusals that need a chain, as the library words them: stage -> (enable, read, the stage's noun, what it
+# counts from, the smallest chain that accepts it).
+_FM = dict(mode=fmr.MODE_FM, input_rate=384e3, max_block_len=4096)
+_FE = dict(mode=fmr.MODE_NONE, input_rate=2.5e6, enable_resampler=True, max_block_len=4096)
+STAGES = {
+    "monitor": ("enable_monitor", "monitor_records", "monitor", "MPX sample", _FM),
+    "rf_monitor": ("enable_rf_monitor", "rf_monitor_records", "RF monitor", "IF sample", _FM),
+    "loudness": ("enable_loudness", "loudness_records", "audio monitor", "audio sample", _FM),
+    "analyser": ("enable_analyser", "analyser_records", "analyser", "audio sample", _FM),
+    "weak_signal": ("enable_weak_signal", "weak_signal_records", "weak-signal stage", "MPX sample", _FM),
+    "blanker": ("enable_blanker", "blanker_records", "blanker", "input sample", _FE),
+    "iq_correction": ("enable_iq_correction", "iq_correction_records", "IQ corrector", "input sample", _FE),
+}
+CAPTURE = {"blanker": ("the blanker", 6, "tap 6 (blanked input rows) needs a chain with fmr_enable_blanker in FMR_NB_ACT, and an input row"),
+           "iq_correction": ("the IQ corrector", 7, "tap 7 (corrected input rows) needs a chain with fmr_enable_iq_correction in "
+                                                    "FMR_IQC_ACT, and an input row")}
+
+
+def _refused(call, rc, msg):
+    with pytest.raises(fmr.FmrError) as e:
+        call()
+    assert str(e.value) == f"fmradion_amd error {rc}: {msg}"
+
+
+@pytest.mark.parametrize("stage", list(STAGES))
+def test_record_stage_refusals_word_for_word(stage):
+    """Every refusal of a record stage that needs a chain, text and code in full: the read before the enable, the second
+    enable, the enable after a call of one block of 4096 samples; for the two stages on the capture also a row the chain
+    does not have, the three chains they do not fit and their debug tap on a chain without them."""
+    enable, read, noun, first, kw = STAGES[stage]
+    fn, rd = f"fmr_{enable}", f"fmr_{stage}_read"
+    block = np.full((1, 4096), 0.1, dtype=np.complex64)
+    ch = fmr.Chain(**kw)
+    _refused(getattr(ch, read), -2, f"{rd}: the chain has no {noun} ({fn})")
+    if stage in CAPTURE:
+        _refused(lambda: ch.debug_read(CAPTURE[stage][1]), -2, "fmr_debug_read: " + CAPTURE[stage][2])
+    getattr(ch, enable)()
+    _refused(getattr(ch, enable), -2, f"{fn}: the {noun} of this chain is already enabled")
+    if stage in CAPTURE:
+        _refused(lambda: getattr(ch, read)(5), -2, f"{rd}: row 5 is not one of the chain's 1 input rows")
+    ch.close()
+    ch = fmr.Chain(**kw)
+    (ch.resample_blocks if kw is _FE else ch.process_blocks)(block, [4096])
+    _refused(getattr(ch, enable), -2, f"{fn}: the chain has already taken samples (the {noun} counts from the chain's first {first})")
+    ch.close()
+    if stage not in CAPTURE:
+        return
+    the = CAPTURE[stage][0]
+    for make, msg in (
+            (lambda: fmr.MpxChain(), f"{the} works on an IQ capture; an MPX decoder (fmr_create_mpx_decoder) is fed composite PCM"),
+            (lambda: fmr.Chain(mode=fmr.MODE_FM, input_rate=2.5e6, enable_resampler=True, max_block_len=16384, input_format=fmr.IQ_S16),
+             f"{the} reads complex float samples (FMR_IQ_CF32); this chain takes a raw input format"),
+            (lambda: fmr.Chain(**_FM), f"{the} sits in front of the IF resampler; this chain has none (enable_resampler = 0)")):
+        ch = make()
+        _refused(getattr(ch, enable), -3, f"{fn}: {msg}")
+        ch.close()

@@ -292,6 +292,65 @@ def test_both_stages_acting(order):
     same_outputs(got, twin_of(blanker_only, fx["out"], CALLS))
 
 
+def device_feed(ch, rows, lens, taps=()):
+    """rows [2, n] from a device buffer whose rows start one complex sample behind a 16-byte boundary and lie an odd
+    number of samples apart, through resample_blocks_device, one call of one block per entry of `lens`.  Returns the IQ
+    rows of all calls joined and, per tap, per input row, the tap of every call joined."""
+    import torch
+    n = rows.shape[1]
+    stride = n + 65
+    buf = np.zeros(1 + 2 * stride + 64, dtype=np.complex64)
+    for r in range(2):
+        buf[1 + r * stride:1 + r * stride + n] = rows[r]
+    d_x = torch.from_numpy(buf.view(np.float32)).cuda()
+    assert d_x.data_ptr() % 16 == 0 and stride % 2 == 1
+    ocap = max(lens) + 64
+    d_o = torch.zeros(2 * 2 * ocap, dtype=torch.float32, device="cuda")
+    out, got = [], {t: [[], []] for t in taps}
+    pos = 0
+    for m in lens:
+        ol = ch.resample_blocks_device(d_x.data_ptr() + 8 * (1 + pos), stride, [m], d_o.data_ptr(), ocap, sync=True)
+        out.append(d_o.cpu().numpy().view(np.complex64).reshape(2, ocap)[:, :int(ol.sum())].copy())
+        for t in taps:
+            for r in range(2):
+                got[t][r].append(ch.debug_read(t, stream=r, cap=m + 16))
+        pos += m
+    return np.concatenate(out, axis=1), {t: [np.concatenate(g) for g in got[t]] for t in taps}
+
+
+def test_both_stages_acting_on_unaligned_device_rows():
+    """What the two capture stages share, where the other tests do not go together: a two-stream front-end-only chain,
+    both stages acting, fed from device rows off the 16-byte phase and an odd stride apart in five calls of 8209, 1, 4095,
+    8192 and 4097 samples (they straddle intervals, one brings a single sample, and from the third on a call waits for the
+    records kernel of two calls before).  Taps 7 and 6 and the records are the fixtures', and the IQ rows are those of a
+    twin without the stages fed the fixtures' output the same way."""
+    lens = [8209, 1, 4095, 8192, 4097]
+    n = sum(lens)
+    rows = np.stack([capture()[:n], cached("x2", qf.second_row)[:n]])
+    rows[0, [17000, 20496, 20497, 24000]] = np.complex64(30 - 20j)       # impulses for the blanker, behind its first window:
+    rows[1, [16500, 20479, 20480, 22222]] = np.complex64(-25 + 35j)      # a gate across a call's edge, one across an interval's
+    fxs =[fixture(rows[r], key=("corner", r), R=1) for r in range(2)]
+    nbxs = [bf.run(fx["out"], G=2, M=16, W=4, threshold_db=12.0, R=1) for fx in fxs]
+    assert all(x["blank"].sum() > 0 for x in nbxs) and len(fxs[0]["records"]) == n // Q == 6
+    make = lambda: fmr.Chain(mode=fmr.MODE_NONE, input_rate=F, enable_resampler=True, n_streams=2, max_block_len=BLK, max_blocks=1)
+    ch = make()
+    ch.enable_iq_correction(act=True, **{**IQC, "record_intervals": 1})
+    ch.enable_blanker(act=True, **{**NB, "record_intervals": 1})
+    out, taps = device_feed(ch, rows, lens, taps=(7, 6))
+    recs = [(ch.iq_correction_records(r)[0], ch.blanker_records(r)[0]) for r in range(2)]
+    ch.close()
+    for r in range(2):
+        assert same_bits(taps[7][r], fxs[r]["out"]), r
+        assert same_bits(taps[6][r], nbxs[r]["out"]), r
+        check_records(recs[r][0], fxs[r]["records"])
+        for k in bf.RECORD.names:
+            assert same_bits(recs[r][1][k], nbxs[r]["records"][k]), (r, k)
+    ch = make()
+    tw, _ = device_feed(ch, np.stack([x["out"] for x in nbxs]), lens)
+    ch.close()
+    assert same_bits(out, tw) and out.shape[1] > 3000
+
+
 @pytest.mark.parametrize("pipeline", ["pipelined", "in_order"])
 def test_fused_front_end_at_10ms(pipeline, monkeypatch):
     """The benchmark's station at 10 MS/s (the fused front end), impaired, 8 x 65536 samples in two calls, the defaults
