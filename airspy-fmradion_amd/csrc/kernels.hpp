@@ -1940,10 +1940,19 @@ __global__ __launch_bounds__(256) void k_mpf4(
       // mu of every update position of the chunk: p = q0 + 4 k, window xw[p + 1 .. p + N] = psum[p + 1 + N] - psum[p + 1]
       const int q0 = (4 - (c0 & 3)) & 3;
       const int nu = (q0 < cn) ? (cn - q0 + 3) / 4 : 0;
+      // Cell 0 is never inside a window (the first push drops it, :92-105): a non-finite value there -- the end of its walk
+      // through the state, one cell per failed block -- stays out of the sums.  A non-finite term further up makes every
+      // difference behind it inf - inf or NaN - NaN although the window may hold finite cells only: those few positions
+      // sum their window directly.
       {
+        auto pw = [&](int i) {
+          const float2 v = xw[i];
+          const float t = v.x * v.x + v.y * v.y;
+          return (i == 0 && !isfinite(t)) ? 0.0 : (double)t;
+        };
         const int L = N + cn, seg = (L + NT - 1) / NT, i0 = tid * seg, i1 = min(L, i0 + seg);
         double acc = 0.0;
-        for (int i = i0; i < i1; i++) { const float2 v = xw[i]; acc += (double)(v.x * v.x + v.y * v.y); }
+        for (int i = i0; i < i1; i++) acc += pw(i);
         ptot[tid] = acc;
         __syncthreads();
         double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
@@ -1951,12 +1960,16 @@ __global__ __launch_bounds__(256) void k_mpf4(
         for (; t + 4 <= tid; t += 4) { a0 += ptot[t]; a1 += ptot[t + 1]; a2 += ptot[t + 2]; a3 += ptot[t + 3]; }
         for (; t < tid; t++) a0 += ptot[t];
         double run = (a0 + a1) + (a2 + a3);
-        for (int i = i0; i < i1; i++) { psum[i] = run; const float2 v = xw[i]; run += (double)(v.x * v.x + v.y * v.y); }
+        for (int i = i0; i < i1; i++) { psum[i] = run; run += pw(i); }
         if (i1 == L && i0 < i1) psum[L] = run;
         __syncthreads();
         for (int k = tid; k < nu; k += NT) {
           const int p = q0 + 4 * k;
-          const double e = psum[p + 1 + N] - psum[p + 1];
+          double e = psum[p + 1 + N] - psum[p + 1];
+          if (!isfinite(e)) {                                        // (rare: inf where the window holds such a cell, as the reference's sum)
+            e = 0.0;
+            for (int i = p + 1; i <= p + N; i++) e += pw(i);
+          }
           smu[k] = (float)(0.1 / ((double)(float)e + 1e-10));        // :130
         }
         __syncthreads();

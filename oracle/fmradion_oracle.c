@@ -977,7 +977,7 @@ void ora_fourth_process(ora_fourth *f, const float *in, int n, float *out) {
 /* ======================================================================== */
 struct ora_fm {
   int fmfilter_enable, pilot_shift, enable_multipath, stereo_enabled, stereo_detected;
-  unsigned wait_multipath_blocks;
+  unsigned wait_multipath_blocks, multipath_resets;
   float baseband_mean, baseband_level, if_rms;
   ora_firiq *fmfilter;
   ora_resampler *rs_mono, *rs_stereo;
@@ -1066,7 +1066,7 @@ int ora_fm_process(ora_fm *fm, const float *iq, int n, double *audio, int cap) {
     fm->wait_multipath_blocks--;
   } else if (fm->enable_multipath) {
     int ok = ora_mpf_process(fm->mpf, fm->b_agc, n, fm->b_mpf); /* :114 */
-    if (!ok) ora_mpf_initialize_coefficients(fm->mpf);      /* :117-123 */
+    if (!ok) { ora_mpf_initialize_coefficients(fm->mpf); fm->multipath_resets++; } /* :117-123 */
     else mp = fm->b_mpf;
   }
   ora_disc_process(&fm->disc, mp, n, fm->b_dec);            /* :131 */
@@ -1128,6 +1128,7 @@ float ora_fm_baseband_level(const ora_fm *fm) { return fm->baseband_level; }
 double ora_fm_pilot_level(const ora_fm *fm) { return ora_pll_pilot_level(fm->pll); }
 float ora_fm_if_rms(const ora_fm *fm) { return fm->if_rms; }
 double ora_fm_multipath_error(const ora_fm *fm) { return ora_mpf_error(fm->mpf); }
+unsigned ora_fm_multipath_resets(const ora_fm *fm) { return fm->multipath_resets; }
 float ora_fm_if_agc_gain(const ora_fm *fm) { return fm->ifagc.current_gain; }
 int ora_fm_pps_events(const ora_fm *fm, ora_pps_event *ev, int cap) { return ora_pll_pps_events(fm->pll, ev, cap); }
 const float *ora_fm_multipath_coeff(const ora_fm *fm, int *order) {

@@ -166,6 +166,8 @@ float ora_fm_baseband_level(const ora_fm *fm);
 double ora_fm_pilot_level(const ora_fm *fm);
 float ora_fm_if_rms(const ora_fm *fm);
 double ora_fm_multipath_error(const ora_fm *fm);
+/* how often process() re-initialised the equaliser after a failed block (FmDecode.cpp:117-123) */
+unsigned ora_fm_multipath_resets(const ora_fm *fm);
 float ora_fm_if_agc_gain(const ora_fm *fm);
 int ora_fm_pps_events(const ora_fm *fm, ora_pps_event *ev, int cap);
 const float *ora_fm_multipath_coeff(const ora_fm *fm, int *order);

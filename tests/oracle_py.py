@@ -82,6 +82,7 @@ def lib():
         "ora_fm_pilot_level": (C.c_double, [vp]),
         "ora_fm_if_rms": (C.c_float, [vp]),
         "ora_fm_multipath_error": (C.c_double, [vp]),
+        "ora_fm_multipath_resets": (C.c_uint, [vp]),
         "ora_fm_if_agc_gain": (C.c_float, [vp]),
         "ora_fm_pps_events": (C.c_int, [vp, C.POINTER(PpsEvent), C.c_int]),
         "ora_fm_multipath_coeff": (c_float_p, [vp, C.POINTER(C.c_int)]),
@@ -455,6 +456,9 @@ class FmDecoder:
 
     def get_multipath_error(self):
         return lib().ora_fm_multipath_error(self.h)
+
+    def get_multipath_resets(self):
+        return int(lib().ora_fm_multipath_resets(self.h))
 
     def get_if_agc_gain(self):
         return lib().ora_fm_if_agc_gain(self.h)
